@@ -20,7 +20,11 @@ barcode_hmm.c:172).  Reads shard with no data-path collective (weak scaling: eve
 the only exchange is one all-reduce of the 264 outcome / per-barcode counters per run (RCCL over xGMI, in place on
 the library's device counters).
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`, `config`, `launch_timeline`); `--full` adds everything else the bench measures or checks: the oracle spot-check
+before timing, `roofline` (isolated launches of the decode kernel), `extra` (sustained, label-free and other-buffer runs,
+configs 2, 4 and 5, the streaming end-to-end run) and `cpu_baseline`.  `--dump-outputs DIR` writes what the last timed step
+returned to the caller as DIR/<name>.npy (float32 / float64); the inputs depend on the arguments alone.
 """
 import argparse
 import json
@@ -138,16 +142,19 @@ def synth_batch_c3(n, seed, read_len=READ_LEN, random_frac=0.1, sub=0.02):
     keep = rng.integers(0, len(ADAPTER) + 1, n)            # how much of the 3' adapter is present
     y = x.copy()
     y[:, :head.shape[1]] = head
-    pos = np.arange(read_len)[None, :]
+    # the adapter lies within the last len(ADAPTER) positions: only that tail is worked on (same draws, same result)
+    t0 = max(read_len - len(ADAPTER), 0)
+    pos = np.arange(t0, read_len)[None, :]
     start = (read_len - keep)[:, None]
     in_ad = pos >= start
     ad_idx = np.clip(pos - start, 0, len(ADAPTER) - 1)
-    y = np.where(in_ad, ad[ad_idx], y)
+    y[:, t0:] = np.where(in_ad, ad[ad_idx], y[:, t0:])
     structured = np.zeros((n, read_len), bool)
     structured[:, :head.shape[1]] = True
-    structured |= in_ad
-    mut = structured & (rng.random((n, read_len)) < sub)
-    y = np.where(mut, rng.integers(0, 4, size=(n, read_len), dtype=np.uint8), y)
+    structured[:, t0:] |= in_ad
+    mut = structured
+    mut &= rng.random((n, read_len)) < sub
+    np.copyto(y, rng.integers(0, 4, size=(n, read_len), dtype=np.uint8), where=mut)
     is_random = rng.random(n) < random_frac
     y[is_random] = x[is_random]
     return np.ascontiguousarray(y)
@@ -414,21 +421,73 @@ def timeline_summary(tl):
             "overlap_with_previous_mean_ms": sum(max(0.0, stops[i - 1] - starts[i]) for i in range(1, n)) / (n - 1)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_MAX_RECORDS = 1 << 20      # records of every read up to this many (else a fixed sample of this many)
+DUMP_SAMPLE_READS = 8192        # reads whose rewritten sequence and per-base labels are written
+DUMP_SEED = 20241016
+
+
+def dump_outputs(dirname, offs, bufs):
+    """What one step of the timed path handed its caller -- records (input order), rewritten sequences, per-base labels -- as
+    DIR/<name>.npy: every record field of every read (float32 fields as float32, integer fields as float64, both exact; above
+    DUMP_MAX_RECORDS reads, of a fixed sample named by record_index), and the sequences and labels of a fixed, seeded sample of
+    reads (sample_index), concatenated, with their offsets.  The samples depend on the number of reads alone, so two builds run
+    with the same arguments write the same reads."""
+    res, seq, lab = bufs
+    offs = np.asarray(offs, np.int64)
+    n = len(offs) - 1
+    res = res[:n]
+    rec_idx = (np.arange(n) if n <= DUMP_MAX_RECORDS
+               else np.sort(np.random.default_rng(DUMP_SEED + 1).choice(n, DUMP_MAX_RECORDS, replace=False)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_SAMPLE_READS), replace=False))
+    base = offs[0]
+    lens = offs[idx + 1] - offs[idx]
+    out = {"sample_index": idx.astype(np.float64), "sample_seq_offsets": np.concatenate([[0], np.cumsum(lens)]).astype(np.float64)}
+    if len(rec_idx) < n:
+        out["record_index"] = rec_idx.astype(np.float64)
+    for f in res.dtype.names:
+        col = res[f][rec_idx]
+        out["record_" + f] = col.astype(np.float32 if col.dtype.kind == "f" else np.float64)
+    out["sample_seq"] = np.concatenate([seq[offs[i] - base:offs[i + 1] - base] for i in idx]).astype(np.float32)
+    if lab is not None:
+        # labels of read i at offs[i] - offs[0] + i, len_i + 1 of them (include/tagdust_hip.h)
+        out["sample_labels"] = np.concatenate([lab[offs[i] - base + i:offs[i + 1] - base + i + 1] for i in idx]).astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return total
+
+
 def measure_workload(name, n, steps, warmup, dev_index, specialize=1, depth=2, pinned=False, check=0, kernel_only_steps=0, labels=True):
     """One workload on this rank's GPU: model upload, oracle spot-check, warm-up, then the caller times `go()`."""
     from tagdust_amd import TagdustHip, RESULT_DTYPE
     from tagdust_amd.lib import PinnedArray
+    from concurrent.futures import ThreadPoolExecutor
     select_workload(name)
     model = load_model()
-    ctx = TagdustHip(dev_index)
-    ctx.set_option("specialize", specialize)
-    ctx.set_option("pipeline_depth", depth)
-    if pinned:
-        ctx.set_option("stable_input", 1)     # the input buffers below are never refilled: page-locked input keeps the compact egress
-    ctx.upload_model(model)
-    ctx.set_params(float(model["threshold"]), 16, 100)
     rank = int(os.environ.get("RANK", "0"))
     n_host = 3            # distinct host batches, handed over in turn: every step uploads reads the device does not hold
+    # the host batches are generated while the context is created and the kernel compiled (numpy and the library's calls
+    # release the GIL); each batch has its own seeded generator, so they are the same batches as generated one by one.  The
+    # simreads workload calls the library's own generator: on this thread, before the context
+    seeds = [1000 + 17 * rank + b for b in range(n_host)]
+    pool = None if _ACTIVE.get("simreads") else ThreadPoolExecutor(n_host)
+    synth = [pool.submit(synth_host_batch, n, s) for s in seeds] if pool else [synth_host_batch(n, s) for s in seeds]
+    try:
+        ctx = TagdustHip(dev_index)
+        ctx.set_option("specialize", specialize)
+        ctx.set_option("pipeline_depth", depth)
+        if pinned:
+            ctx.set_option("stable_input", 1)     # the input buffers below are never refilled: page-locked input keeps the compact egress
+        ctx.upload_model(model)
+        ctx.set_params(float(model["threshold"]), 16, 100)
+    finally:
+        if pool:
+            synth = [f.result() for f in synth]
+            pool.shutdown()
     pins = []
 
     def host_array(shape, dtype):
@@ -439,8 +498,7 @@ def measure_workload(name, n, steps, warmup, dev_index, specialize=1, depth=2, p
         return np.zeros(shape, dtype)     # pageable; zero-filled so that its pages exist before the timed region
 
     host_batches = []
-    for b in range(n_host):
-        codes, boffs = synth_host_batch(n, seed=1000 + 17 * rank + b)
+    for codes, boffs in synth:
         a = host_array((len(codes),), np.uint8)
         a[:] = codes
         host_batches.append((a, boffs))
@@ -477,7 +535,10 @@ def measure_workload(name, n, steps, warmup, dev_index, specialize=1, depth=2, p
         state["timeline"] = []
         o = outs if with_labels else [(a, b, None) for a, b, _ in outs]
         ctx.timeline_origin()
-        state["k_ms"] = run_pipelined(ctx, host_batches, o, n_steps or steps, depth, state["timeline"])
+        k = n_steps or steps
+        state["k_ms"] = run_pipelined(ctx, host_batches, o, k, depth, state["timeline"])
+        # the last step's input offsets and the host buffers it was returned in (run_pipelined's rotation)
+        state["last_step"] = (host_batches[(k - 1) % len(host_batches)][1], o[(k - 1) % len(o)])
 
     def kernel_only(n_steps=None):
         """The decode kernel alone over a resident batch (round 1's figure), outside the timed region."""
@@ -578,8 +639,14 @@ def main():
     ap.add_argument("--steps", type=int, default=60, help="timed steps (60 x 2^20 reads = 1.2 s per GPU: the pipeline's fill and drain are one step of them)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reads", type=int, default=1 << 20, help="reads per step per GPU")
-    ap.add_argument("--cpu-sample", type=int, default=200000, help="reads in the CPU baseline sample (0 = skip)")
-    ap.add_argument("--check", type=int, default=2048, help="reads verified against the oracle before timing (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: the oracle spot-check before timing, the "
+                    "isolated-launch kernel time and roofline, the sustained / label-free / other-buffer runs, configs 2, 4 and 5, the "
+                    "streaming end-to-end run and the CPU baseline (without it a run sets up, warms up, times --steps steps and prints "
+                    "the headline; --check, --cpu-sample, --sustained and --extras still do what they say when given)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "returned to the caller (records of every read, sequences and labels of a fixed sample of reads) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="reads in the CPU baseline sample (0 = skip; default 200000 with --full, else 0)")
+    ap.add_argument("--check", type=int, default=None, help="reads verified against the oracle before timing (0 = skip; default 2048 with --full, else 0)")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS), help="development only; the bench line is c3")
     ap.add_argument("--specialize", type=int, default=1, help="0 = generic ahead-of-time kernel")
     ap.add_argument("--depth", type=int, default=3, help="batches in flight (td_submit pipeline depth)")
@@ -587,11 +654,14 @@ def main():
                     "since the end of round 4 (a rank's host work and DRAM traffic are what eight ranks share on one node; at one GPU the two modes are equal within "
                     "the box-to-box spread); 0 = pageable numpy arrays, staged through the library's pinned memory (the headline of rounds 3-4, reported beside it)")
     ap.add_argument("--labels", type=int, default=1, help="0 = the timed region does not download the per-base labels (rounds 1-2)")
-    ap.add_argument("--sustained", type=int, default=200, help="steps of the extra sustained run (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="0 = skip the extra measurements (kernel only, pinned I/O, configs 2 and 5)")
+    ap.add_argument("--sustained", type=int, default=None, help="steps of the extra sustained run (0 = skip; default 200 with --full, else 0)")
+    ap.add_argument("--extras", type=int, default=None, help="0 = skip the extra measurements (sustained, label-free and other-buffer runs, configs 2, 4 and 5, the streaming end-to-end run; default 1 with --full, else 0)")
     ap.add_argument("--isolated", type=int, default=0, help="N > 0: nothing but N isolated launches of the decode kernel on a resident batch "
                     "(what roofline.kernel_ms measures) -- the run tools/profile_lease.sh traces to hold rocprofv3's duration against it")
     args = ap.parse_args()
+    for name, full_default in (("cpu_sample", 200000), ("check", 2048), ("sustained", 200), ("extras", 1)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)      # does not return
     # Rank 0 prints ONE JSON line on stdout: everything else that writes to file descriptor 1 while this runs (RCCL's version
@@ -717,6 +787,9 @@ def main():
     timeline = timeline_summary(state["timeline"])
     overlap_active = ctx.get_option("overlap_active")
     prune_active = ctx.get_option("prune_active")
+    if args.dump_outputs and rank == 0:
+        # before anything else reuses the host buffers
+        dump_outputs(args.dump_outputs, *state["last_step"])
 
     # beside the headline, on every rank (these are collective timings): the same pipeline sustained over many more steps, so
     # that an outside clock / a GPU-busy sampler can see it, and the label-free variant rounds 1-2 reported
@@ -735,22 +808,46 @@ def main():
         extra["no_labels"] = {"value": n * st * world / dt, "unit": "reads/s", "steps": st, "ms_per_step": dt / st * 1e3,
                               "note": "records + rewritten sequences only, no label download (the timed region of rounds 1-2)"}
 
+    def roofline(iso, value):
+        """The decode kernel against the chip (--full): isolated-launch kernel time, algorithmic and PMC-recorded traffic, VALU."""
+        k_ms = float(iso["kernel_ms"])
+        bpr = algorithmic_bytes_per_read(READ_LEN)
+        achieved = bpr * n / (k_ms * 1e-3) / 1e9
+        rec, traffic_note = load_pmc_record(n, args.workload)
+        traffic = rec.get("hbm_bytes_per_launch") if rec else None
+        kname = "td_spec_kernel" if args.specialize else "td_decode_kernel"
+        return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "kernel": kname, "kernel_ms": k_ms,
+                "kernel_ms_how": "average of %d isolated launches on a resident batch (HIP events, same process, after the timed region)" % iso["steps"],
+                "kernel_event_span_ms_in_timed_region": float(np.mean(ev_ms)),
+                "kernel_reads_per_s": n / (k_ms * 1e-3),
+                "host_inclusive_over_kernel": value / world / (n / (k_ms * 1e-3)),
+                "algorithmic_bytes_per_read": bpr, "reads_per_launch": n,
+                "traffic_gbps": (traffic / (k_ms * 1e-3) / 1e9) if traffic else None,
+                "traffic_frac_of_peak": (traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                "traffic_frac_of_achievable": (traffic / (k_ms * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBS) if traffic else None,
+                "lds": ({"idx_active_share": rec.get("lds_idx_active_share_of_cu_cycles"),
+                         "bank_conflict_share": rec.get("lds_bank_conflict_share"),
+                         "how": "SQ_LDS_IDX_ACTIVE / CU cycles of the launch, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE (PMC passes of the "
+                                "same kernel source, profiles/): the logsum table gather"} if rec else None),
+                "traffic_source": traffic_note,
+                "valu": valu_roofline(rec, n, k_ms, args.workload),
+                "note": "algorithmic bytes are tiny (SURVEY.md 8d: not HBM-bound); the kernel's real HBM traffic is the "
+                        "backward-row spill (traffic_gbps), which no longer binds since the position pruning.  What binds is "
+                        "the compute side: `valu` prices the kernel's VALU wave-instructions (PMC, same kernel source) against "
+                        "the chip's issue peak"}
+
     # The decode kernel's own launch duration: isolated launches over a resident batch, HIP events on the kernel's stream, in
     # this process right after the timed region.  Inside the timed region consecutive launches overlap on purpose (the next
     # batch's workgroups move in as the last one's retire), so the event span of a launch there includes the time it waits
     # for compute units and is reported separately.
-    iso = kernel_only() if rank == 0 else None
+    iso = kernel_only() if rank == 0 and args.full else None
 
     if rank == 0:
         total_reads = n * args.steps * world
         value = total_reads / elapsed
-        k_ms = float(iso["kernel_ms"])
-        bpr = algorithmic_bytes_per_read(READ_LEN)
-        achieved = bpr * n / (k_ms * 1e-3) / 1e9
         nreads, ws_bytes, slots = ctx.batch_info()
-        rec, traffic_note = load_pmc_record(n, args.workload)
-        traffic = rec.get("hbm_bytes_per_launch") if rec else None
-        kname = "td_spec_kernel" if args.specialize else "td_decode_kernel"
         out = {
             "metric": "reads/s (150 bp, 8-barcode arch)", "value": value, "unit": "reads/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -770,30 +867,11 @@ def main():
                            world, ("RCCL" if backend == "nccl" else backend) if use_dist else "single rank: no exchange"),
                        "overlap_active": overlap_active, "prune_active": prune_active,
                        "wave_slots": slots, "workspace_bytes": ws_bytes},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": kname, "kernel_ms": k_ms,
-                         "kernel_ms_how": "average of %d isolated launches on a resident batch (HIP events, same process, after the timed region)" % iso["steps"],
-                         "kernel_event_span_ms_in_timed_region": float(np.mean(ev_ms)),
-                         "kernel_reads_per_s": n / (k_ms * 1e-3),
-                         "host_inclusive_over_kernel": value / world / (n / (k_ms * 1e-3)),
-                         "algorithmic_bytes_per_read": bpr, "reads_per_launch": n,
-                         "traffic_gbps": (traffic / (k_ms * 1e-3) / 1e9) if traffic else None,
-                         "traffic_frac_of_peak": (traffic / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                         "traffic_frac_of_achievable": (traffic / (k_ms * 1e-3) / 1e9 / HBM_ACHIEVABLE_GBS) if traffic else None,
-                         "lds": ({"idx_active_share": rec.get("lds_idx_active_share_of_cu_cycles"),
-                                  "bank_conflict_share": rec.get("lds_bank_conflict_share"),
-                                  "how": "SQ_LDS_IDX_ACTIVE / CU cycles of the launch, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE (PMC passes of the "
-                                         "same kernel source, profiles/): the logsum table gather"} if rec else None),
-                         "traffic_source": traffic_note,
-                         "valu": valu_roofline(rec, n, k_ms, args.workload),
-                         "note": "algorithmic bytes are tiny (SURVEY.md 8d: not HBM-bound); the kernel's real HBM traffic is the "
-                                 "backward-row spill (traffic_gbps), which no longer binds since the position pruning.  What binds is "
-                                 "the compute side: `valu` prices the kernel's VALU wave-instructions (PMC, same kernel source) against "
-                                 "the chip's issue peak"},
+            "roofline": roofline(iso, value) if iso else None,
             "launch_timeline": timeline,
         }
-        extra["kernel_only"] = iso
+        if iso:
+            extra["kernel_only"] = iso
     close()
     other_key = "pageable_io" if args.pinned else "pinned_io"
     other_buffers = "pageable numpy arrays (library stages through pinned memory)" if args.pinned else "page-locked (td_host_alloc)"

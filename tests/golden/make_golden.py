@@ -14,6 +14,7 @@ of backward()/forward_max_posterior_decoding()/run_pHMM(MODE_GET_LABEL).  No ref
 text is stored.
 
 usage: python tests/golden/make_golden.py [scenario ...]
+       python tests/golden/make_golden.py --cli-recorded   (tests/golden/ref_cli_recorded.json.gz, record_cli)
 """
 import gzip
 import os
@@ -432,7 +433,43 @@ def scenarios(tmp):
     return sc
 
 
+# fixtures whose reference CLI files tests/test_io.py compares with (test_writer_reproduces_reference_files, test_io_gpu,
+# test_whole_pipeline_without_the_reference)
+CLI_NAMES = ["c2_b4_r", "c3_b6_s_r_p", "scen2_endloss", "umi_f_s_r", "short_q_given", "casava_index", "b_r_s_r", "dust_b_r", "scen2_p_b_r_p"]
+
+
+def record_cli():
+    """tests/golden/ref_cli_recorded.json.gz: what the reference CLI writes and logs for the committed fixtures, so that the
+    tests comparing with it run where the reference is not built (they still check the recording against it where it is):
+      writer_outputs[name][suffix]: the files oracle/_ref/tagdust_rtest writes for fixture `name` (FASTQ text, latin-1),
+      libc_calibration["c2_b4_r"]["selected_threshold"]: the threshold oracle/_ref/tagdust (C library rand()) logs."""
+    import gzip
+    import json
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_calibration
+    import test_io
+    from conftest import load_golden
+    out = {"writer_outputs": {}, "libc_calibration": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for name in CLI_NAMES:
+            d = os.path.join(tmp, name)
+            os.makedirs(d)
+            files = test_io.run_reference_cli(load_golden(name), d)
+            out["writer_outputs"][name] = {k: v.decode("latin-1") for k, v in sorted(files.items())}
+            print("%-18s %d files, %d bytes" % (name, len(files), sum(len(v) for v in files.values())))
+        import pathlib
+        thr = test_calibration.reference_selected_threshold(os.path.join(RBIN, "tagdust"), load_golden("c2_b4_r"), pathlib.Path(tmp))
+        out["libc_calibration"]["c2_b4_r"] = {"selected_threshold": repr(thr)}
+        print("libc calibration c2_b4_r: selected threshold %r" % thr)
+    path = os.path.join(HERE, "ref_cli_recorded.json.gz")
+    with gzip.GzipFile(path, "wb", mtime=0) as fh:
+        fh.write(json.dumps(out, sort_keys=True, indent=0).encode())
+    print("%s: %.0f KB" % (path, os.path.getsize(path) / 1024))
+
+
 def main():
+    if sys.argv[1:] == ["--cli-recorded"]:
+        return record_cli()
     want = sys.argv[1:]
     with tempfile.TemporaryDirectory() as tmp:
         for name, fn in scenarios(tmp).items():

@@ -92,20 +92,10 @@ def test_compare_architectures_on_gpu():
     assert np.array_equal(post.view(np.uint32), want.view(np.uint32)), (post, want)
 
 
-def test_libc_rng_variant_matches_the_reference_binary(tmp_path):
-    """The production path (C library rand(), 400 000 simulated reads): the threshold td_calibration_emit + scoring +
-    td_calibration_select give must be the one the reference's regular (non -DRTEST) binary logs for the same input
-    and -seed.  Needs oracle/_ref/tagdust (built in the build container by `make -C oracle ref`); the emitted reads are
-    scored by the CPU oracle here, by the device in td_estimate_threshold."""
-    import os
+def reference_selected_threshold(exe, g, tmp_path):
+    """The threshold the reference's regular (non -DRTEST) binary `exe` logs for fixture g's reads and command line."""
     import re
     import subprocess
-    from conftest import REPO
-    from oracle import pyoracle
-    exe = os.path.join(REPO, "oracle", "_ref", "tagdust")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/tagdust not built")
-    g = load_golden("c2_b4_r")
     fq = str(tmp_path / "in.fq")
     names = bytes(g["names"]).split(b"\n")
     offs = g["offs"]
@@ -118,7 +108,25 @@ def test_libc_rng_variant_matches_the_reference_binary(tmp_path):
     assert p.returncode == 0, p.stdout.decode(errors="replace")[-1500:]
     m = re.search(r"Selected Threshold::? ([0-9.eE+-]+)", p.stdout.decode(errors="replace"))
     assert m, p.stdout.decode(errors="replace")[-1500:]
-    want = float(m.group(1))
+    return float(m.group(1))
+
+
+def test_libc_rng_variant_matches_the_reference_binary(tmp_path):
+    """The production path (C library rand(), 400 000 simulated reads): the threshold td_calibration_emit + scoring +
+    td_calibration_select give must be the one the reference's regular (non -DRTEST) binary logs for the same input
+    and -seed -- as recorded in tests/golden/ref_cli_recorded.json.gz, and from oracle/_ref/tagdust itself where it is
+    built (`make -C oracle ref`).  The emitted reads are scored by the CPU oracle here, by the device in td_estimate_threshold."""
+    import gzip
+    import json
+    import os
+    from conftest import GOLDEN_DIR, REPO
+    from oracle import pyoracle
+    g = load_golden("c2_b4_r")
+    with gzip.open(os.path.join(GOLDEN_DIR, "ref_cli_recorded.json.gz"), "rt") as fh:
+        want = float(json.load(fh)["libc_calibration"]["c2_b4_r"]["selected_threshold"])
+    exe = os.path.join(REPO, "oracle", "_ref", "tagdust")
+    if os.path.exists(exe):
+        assert reference_selected_threshold(exe, g, tmp_path) == want, "the recorded threshold differs from the reference binary's"
     segs = _segments(g)
     codes, offs2, is_random = tdlib.calibration_emit(segs, g["seq"], g["offs"], float(g["d"]), seed=42, n_reads=400000, rng=0)
     scoring, _ = tdlib.build_model(segs, g["seq"], g["offs"], 0.05, float(g["d"]))

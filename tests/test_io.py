@@ -2,13 +2,15 @@
 own parser + decode + own writer must produce the files the unmodified reference CLI writes, byte for byte.
 The decode step is the oracle here (CPU); tests/test_dropin_gpu.py and test_io_gpu below use the HIP path."""
 import glob
+import gzip
+import json
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import load_golden, REPO
+from conftest import GOLDEN_DIR, load_golden, REPO
 from tagdust_amd import lib as tdlib
 
 RBIN = os.path.join(REPO, "oracle", "_ref")
@@ -37,13 +39,31 @@ def segments_of(g):
     return segs
 
 
-def reference_outputs(g, tmp):
+def recorded_cli():
+    """What the reference CLI wrote and logged for the fixtures, recorded where it is built (tests/golden/make_golden.py)."""
+    with gzip.open(os.path.join(GOLDEN_DIR, "ref_cli_recorded.json.gz"), "rt") as fh:
+        return json.load(fh)
+
+
+def run_reference_cli(g, tmp):
+    """The files the reference CLI (oracle/_ref/tagdust_rtest) writes for fixture g: {suffix after "ref": bytes}."""
     fq = os.path.join(tmp, "in.fq")
     open(fq, "wb").write(fastq_text(g))
     p = subprocess.run([os.path.join(RBIN, "tagdust_rtest")] + str(g["cmdline"]).split() + [fq, "-o", "ref"], cwd=tmp,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     assert p.returncode == 0, p.stdout.decode(errors="replace")[-1500:]
     return {os.path.basename(f)[3:]: open(f, "rb").read() for f in glob.glob(os.path.join(tmp, "ref*.fq"))}
+
+
+def reference_outputs(name, g, tmp):
+    """The reference CLI's files for fixture `name` as recorded in tests/golden/ref_cli_recorded.json.gz (make_golden.py
+    --cli-recorded); where the reference binary is built, the recording is checked against a run of it as well."""
+    rec = recorded_cli()["writer_outputs"]
+    assert name in rec, "no recorded reference outputs for %s" % name
+    want = {k: v.encode("latin-1") for k, v in rec[name].items()}
+    if HAVE_REF:
+        assert run_reference_cli(g, tmp) == want, "tests/golden/ref_cli_recorded.json.gz differs from the reference binary (%s)" % name
+    return want
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -78,12 +98,11 @@ def test_parser_chunked_large_input_and_fasta():
     assert fa.n == 2 and list(fa.codes) == [0, 1, 2, 3, 2, 2, 4, 0] and list(fa.qual_off) == [-1, -1]
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref/tagdust_rtest not built")
 @pytest.mark.parametrize("name", NAMES)
 def test_writer_reproduces_reference_files(tmp_path, name):
     from oracle import pyoracle
     g = load_golden(name)
-    want = reference_outputs(g, str(tmp_path))
+    want = reference_outputs(name, g, str(tmp_path))
     pr = tdlib.ParsedReads(fastq_text(g), 2)
     ores, _, oseq = pyoracle.label_batch(pyoracle.OracleModel(g), pr.codes, pr.offs, float(g["threshold"]), int(g["minlen"]), int(g["dust"]), 2)
     res = np.zeros(pr.n, tdlib.RESULT_DTYPE)
@@ -99,13 +118,12 @@ def test_writer_reproduces_reference_files(tmp_path, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref/tagdust_rtest not built")
 @pytest.mark.parametrize("name", ["c3_b6_s_r_p", "scen2_endloss"])
 def test_io_gpu(tmp_path, name):
     """parse -> HIP decode -> write == the reference CLI's files."""
     from tagdust_amd import TagdustHip
     g = load_golden(name)
-    want = reference_outputs(g, str(tmp_path))
+    want = reference_outputs(name, g, str(tmp_path))
     pr = tdlib.ParsedReads(fastq_text(g), 2)
     c = TagdustHip(0)
     try:
@@ -124,7 +142,6 @@ def test_io_gpu(tmp_path, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref/tagdust_rtest not built")
 @pytest.mark.parametrize("name", ["c2_b4_r", "c3_b6_s_r_p", "scen2_p_b_r_p"])
 def test_whole_pipeline_without_the_reference(tmp_path, name):
     """Everything from the library alone -- parse FASTQ, sequence statistics, model construction, threshold calibration
@@ -132,7 +149,7 @@ def test_whole_pipeline_without_the_reference(tmp_path, name):
     reference CLI writes for the same command line."""
     from tagdust_amd import TagdustHip
     g = load_golden(name)
-    want = reference_outputs(g, str(tmp_path))
+    want = reference_outputs(name, g, str(tmp_path))
     segs = segments_of(g)
     pr = tdlib.ParsedReads(fastq_text(g), 2)
     c = TagdustHip(0)

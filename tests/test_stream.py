@@ -127,15 +127,17 @@ def test_pipeline_with_too_few_batch_buffers_does_not_hang(tmp_path):
         for i in range(20000):
             L = int(rng.randint(20, 90))
             fh.write(("@r%d\n%s\n+\n%s\n" % (i, "".join(rng.choice(list("ACGT"), L)), "I" * L)).encode())
-    os.makedirs("/tmp/td_tsan", exist_ok=True)       # (the stub's output prefix)
+    outdir = str(tmp_path / "out")                   # (the stub's output directory, TD_STUB_OUT)
+    os.makedirs(outdir)
 
     def run(limit):
         env = dict(os.environ)
         env.pop("TD_STUB_ALLOC_LIMIT", None)
+        env["TD_STUB_OUT"] = outdir
         if limit is not None:
             env["TD_STUB_ALLOC_LIMIT"] = str(limit)
         r = subprocess.run([exe, fq, "777", "2", "20000", "decode"], env=env, capture_output=True, timeout=120)   # a hang fails here
-        files = {os.path.basename(f): open(f, "rb").read() for f in sorted(glob.glob("/tmp/td_tsan/out*.fq"))}
+        files = {os.path.basename(f): open(f, "rb").read() for f in sorted(glob.glob(os.path.join(outdir, "out*.fq")))}
         return r.stdout.decode().splitlines()[0], files
 
     want_line, want_files = run(None)

@@ -9,7 +9,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp TD_SPEC_CACHE_DIR=/tmp/td_spec_cache
 mkdir -p $TD_SPEC_CACHE_DIR
 cd $ROOT
-ARGS="--workload $WL --reads $N --steps 8 --warmup 3 --extras 0 --cpu-sample 0 --check 256"
+ARGS="--full --workload $WL --reads $N --steps 8 --warmup 3 --extras 0 --cpu-sample 0 --check 256"
 i=0
 for cfg in "$A" "$B" "$A" "$B"; do
 	i=$((i+1))

@@ -3,14 +3,15 @@
 # each argument is one configuration (environment assignments); prints kernel_ms of the bench workload for each.
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $ROOT
-mkdir -p gpurun_out/sweep
+OUT=${SWEEP_OUT:-${TMPDIR:-/tmp}/knob_sweep}    # one bench line (.json) and its stderr (.err) per configuration
+mkdir -p $OUT
 export TD_SPEC_CACHE_DIR=/tmp/td_spec_cache; mkdir -p $TD_SPEC_CACHE_DIR
 i=0
 WL=${SWEEP_WORKLOAD:-c3}
 for cfg in "$@"; do
 	i=$((i+1))
-	env $cfg timeout -k 10 200 python3 bench.py --workload $WL --steps 6 --warmup 2 --extras 0 --cpu-sample 0 --check 512 --reads ${SWEEP_READS:-1048576} > gpurun_out/sweep/$i.json 2> gpurun_out/sweep/$i.err
-	python3 - "$cfg" gpurun_out/sweep/$i.json gpurun_out/sweep/$i.err <<'PY'
+	env $cfg timeout -k 10 200 python3 bench.py --full --workload $WL --steps 6 --warmup 2 --extras 0 --cpu-sample 0 --check 512 --reads ${SWEEP_READS:-1048576} > $OUT/$i.json 2> $OUT/$i.err
+	python3 - "$cfg" $OUT/$i.json $OUT/$i.err <<'PY'
 import json, sys
 cfg, f, e = sys.argv[1:4]
 try:

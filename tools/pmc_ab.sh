@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd $ROOT
 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_BUSY_CYCLES \
-	--output-format csv -d $OUT -o td -- python3 $ROOT/bench.py --reads 262144 --steps 3 --warmup 1 --cpu-sample 0 --check 0 > $OUT/run.log 2>&1 || { echo failed; tail -3 $OUT/run.log; exit 1; }
+	--output-format csv -d $OUT -o td -- python3 $ROOT/bench.py --full --reads 262144 --steps 3 --warmup 1 --cpu-sample 0 --check 0 > $OUT/run.log 2>&1 || { echo failed; tail -3 $OUT/run.log; exit 1; }
 python3 - <<PY
 import csv, glob, collections
 tot = collections.Counter(); n = 0

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 cd $ROOT
 pass() {
 	local name=$1; shift
-	timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o td -- python3 $ROOT/bench.py --reads 1048576 --steps 2 --warmup 1 --cpu-sample 0 --check 0 > $OUT/$name.log 2>&1 || { echo "$name failed"; tail -3 $OUT/$name.log; return 1; }
+	timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o td -- python3 $ROOT/bench.py --full --reads 1048576 --steps 2 --warmup 1 --cpu-sample 0 --check 0 > $OUT/$name.log 2>&1 || { echo "$name failed"; tail -3 $OUT/$name.log; return 1; }
 }
 pass a GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_ANY &&
 pass b GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_THREAD_CYCLES_VALU

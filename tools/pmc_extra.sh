@@ -3,7 +3,7 @@
 #   tools/pmc_extra.sh <tag> [bench args...]
 set -u
 TAG=${1:-x}; shift || true
-ARGS=${@:---reads 262144 --steps 3 --warmup 1 --cpu-sample 0 --check 0}
+ARGS=${@:---full --reads 262144 --steps 3 --warmup 1 --cpu-sample 0 --check 0}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/pmcx_$TAG
 mkdir -p $OUT

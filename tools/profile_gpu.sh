@@ -5,7 +5,7 @@
 # Counters go in their own passes (never combined with --sys-trace etc.), program directly after "--".
 set -u
 TAG=${1:-run}; shift || true
-ARGS=${@:---reads 262144 --steps 3 --warmup 1 --cpu-sample 0 --check 0}
+ARGS=${@:---full --reads 262144 --steps 3 --warmup 1 --cpu-sample 0 --check 0}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT

@@ -20,8 +20,8 @@ mkdir -p $TD_SPEC_CACHE_DIR
 cd $ROOT
 echo "== bench (the driver's command)"
 if [ "$WL" = c3 ]; then BENCH_ARGS=""; else BENCH_ARGS="--workload $WL --reads $READS --extras 0 --cpu-sample 0"; fi
-timeout -k 10 500 python3 bench.py --gpus 1 --steps $STEPS --warmup 5 $BENCH_ARGS > $P/${TAG}${SFX}_bench_line.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
-PROF_ARGS="--workload $WL --reads $READS --steps $STEPS --warmup 5 --extras 0 --cpu-sample 0 --check 0"
+timeout -k 10 500 python3 bench.py --gpus 1 --steps $STEPS --warmup 5 --full $BENCH_ARGS > $P/${TAG}${SFX}_bench_line.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
+PROF_ARGS="--full --workload $WL --reads $READS --steps $STEPS --warmup 5 --extras 0 --cpu-sample 0 --check 0"
 run() { local name=$1; shift
 	timeout -k 10 300 rocprofv3 "$@" --output-format csv -d $OUT/$name -o td -- python3 $ROOT/bench.py $PROF_ARGS > $OUT/$name.log 2>&1 \
 		|| { echo "rocprofv3 pass $name failed"; tail -5 $OUT/$name.log; return 1; }

@@ -2,7 +2,7 @@
 # HBM traffic (FETCH_SIZE / WRITE_SIZE passes) and kernel time of the bench workload: tools/traffic_gpu.sh <tag> [bench args]
 set -u
 TAG=${1:-x}; shift || true
-ARGS=${@:---reads 1048576 --steps 3 --warmup 1 --cpu-sample 0 --check 0}
+ARGS=${@:---full --reads 1048576 --steps 3 --warmup 1 --cpu-sample 0 --check 0}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/traffic_$TAG
 mkdir -p $OUT

@@ -32,6 +32,11 @@ int main(int argc, char** argv)
 	arch.n_segments = 2; arch.type[0] = 'B'; arch.type[1] = 'R'; arch.n_seq[0] = 4; arch.n_seq[1] = 1; arch.seq_len[0] = 4; arch.seq_len[1] = 1;
 	arch.seqs[0] = bs; arch.seqs[1] = rs;
 	td_arch* a = &arch;
+	// TD_STUB_OUT: directory of the output files (default /tmp/td_tsan)
+	const char* dir = getenv("TD_STUB_OUT") ? getenv("TD_STUB_OUT") : "/tmp/td_tsan";
+	char out[4096], outm[4096];
+	snprintf(out, sizeof out, "%s/out", dir);
+	snprintf(outm, sizeof outm, "%s/outm", dir);
 	if (argc > 5 && !strcmp(argv[5], "multi")) {
 		// two input files in lock-step (the same file twice): file 0 "decoded" by the stub with the barcode architecture, file 1 a
 		// plain read (R:N: not decoded, run_rna_dust on the host), two "devices"
@@ -41,7 +46,7 @@ int main(int argc, char** argv)
 		td_stream_file fl[2] = { { argv[1], a, ctxs }, { argv[1], &plain, nullptr } };
 		int64_t counts[TD_NUM_COUNTERS];
 		for (int rep = 0; rep < 2; rep++) {
-			int rc = td_stream_run_multi(fl, 2, 2, "/tmp/td_tsan/outm", 100, &o, &st, counts);
+			int rc = td_stream_run_multi(fl, 2, 2, outm, 100, &o, &st, counts);
 			if (rc) { printf("error: %s\n", td_io_last_error()); return 1; }
 			printf("rc %d reads %lld batches %lld bytes_out %lld counts %lld %lld %lld\n", rc, (long long)st.n_reads, (long long)st.n_batches, (long long)st.bytes_out,
 			       (long long)counts[0], (long long)counts[6], (long long)counts[8] + counts[9] + counts[10]);
@@ -50,7 +55,7 @@ int main(int argc, char** argv)
 		return 0;
 	}
 	for (int rep = 0; rep < 2; rep++) {
-		int rc = td_stream_run(argc > 5 ? (td_ctx*)0x1 : nullptr, argv[1], a, "/tmp/td_tsan/out", &o, &st);
+		int rc = td_stream_run(argc > 5 ? (td_ctx*)0x1 : nullptr, argv[1], a, out, &o, &st);
 		printf("rc %d reads %lld batches %lld bytes_out %lld fnv %llx%s%s\n", rc, (long long)st.n_reads, (long long)st.n_batches, (long long)st.bytes_out, (unsigned long long)st.codes_fnv,
 		       rc ? "  error: " : "", rc ? td_io_last_error() : "");
 	}
