@@ -468,9 +468,10 @@ static int load_spec_kernel(td_ctx* c, int lsum_oob, int window = -1)
 	return TD_OK;
 }
 
-// The clamp-free logsum of the specialised kernel turns |a - b| * 1000 into an LDS byte address that wraps at
-// |a - b| = 2^30 / 1000.  Every finite DP value is a sum of at most 2 parameters per position, and the posterior terms
-// add two such values, so 4 * max|parameter| * (L + 2) bounds every finite difference; 6 * keeps a margin.
+// The clamp-free logsum of the specialised kernel turns |a - b| * 4000 into an LDS byte address (a saturating conversion; the
+// shift form it replaced wrapped at |a - b| = 2^30 / 1000, and the limit still keeps that margin).  Every finite DP value is
+// a sum of at most 2 parameters per position, and the posterior terms add two such values, so 4 * max|parameter| * (L + 2)
+// bounds every finite difference; 6 * keeps a margin.
 static bool spec_lsum_range_ok(const td_ctx* c, int lmax)
 {
 	const double limit = c->lsum_limit;   // (1e6; tests lower it to force the switch to the clamped form)

@@ -25,13 +25,6 @@
 #ifndef TDS_MIN_WAVES
 #define TDS_MIN_WAVES 4
 #endif
-#ifndef TDS_LSUM_ABS
-#define TDS_LSUM_ABS 0
-#endif
-#ifndef TDS_FAKE_SPILL
-#define TDS_FAKE_SPILL 0   // diagnostic only: spill every position to the same lines (wrong results, no HBM traffic)
-#endif
-#define TDS_SPILL_POS(i) (TDS_FAKE_SPILL ? 0 : (i))
 #define TDS_REG_H 32   // label DP row / total_prob in registers up to this many HMMs, in the workspace beyond
 #define TDS_WPB (TDS_BLOCK / TD_WAVE)
 #define NEG_INF (-__builtin_inff())
@@ -67,51 +60,30 @@
 // relies on every time a compiled kernel is loaded).
 __shared__ float g_T[TDS_TABLE_N];
 
-#ifndef TDS_DIAG_NO_SPILL
-#define TDS_DIAG_NO_SPILL 0   // diagnostic only (results invalid): 1 = the backward sweeps do not store their rows -- what the stores cost
-#endif
-#ifndef TDS_COUNT_PER_READ
-#define TDS_COUNT_PER_READ 0   // 1: one atomic per read for the outcome counters (the first builds; A/B only)
-#endif
-#ifndef TDS_LSUM_AND
-#define TDS_LSUM_AND 1   // clamp-free logsum: table byte address by multiply-by-4000 and AND (1) or multiply-by-1000 and shift (0)
-#endif
-
 // logsum, src/misc.c:72-78.
 DEV float lsum(float a, float b)
 {
 #if TDS_LSUM_OOB
-	// 6 VALU + 1 ds_read_b32: sub, mul with |.| source modifier, cvt, and (or shl), max, add.  max - min == |a - b| bit for
-	// bit (negation is exact).  The reference's "return max" for d >= 15.7 needs no clamp here: indices 15700..16639 hit the
-	// zero padding, anything larger (d = +inf -> INT_MAX, address 0x7ffffffc / 0xfffffffc) is out of LDS range and reads as 0,
-	// and d = NaN (both operands -inf) converts to index 0, -inf + ln 2 = -inf.  In the shift form byte addresses wrap at
-	// index 2^30, i.e. |a - b| >= 1.07e6: the host only selects the clamp-free logsum when the model's parameters and the
-	// batch's longest read bound every finite score difference far below that (td_api.hip, spec_lsum_range_ok).
-#if TDS_LSUM_AND
+	// 6 VALU + 1 ds_read_b32: sub, mul with |.| source modifier, cvt, and, max, add.  max - min == |a - b| bit for bit
+	// (negation is exact).  The reference's "return max" for d >= 15.7 needs no clamp here: indices 15700..16639 hit the
+	// zero padding, anything larger (d = +inf -> INT_MAX, address 0x7ffffffc) is out of LDS range and reads as 0, and
+	// d = NaN (both operands -inf) converts to index 0, -inf + ln 2 = -inf.  The host only selects the clamp-free logsum
+	// when the model's parameters and the batch's longest read bound every finite score difference far below 1e6
+	// (td_api.hip, spec_lsum_range_ok).
 	// (byte address = trunc(4000 |a - b|) with its two low bits cleared: 4000 x = 4 * (1000 x) exactly in floating point, so
 	// that is 4 * trunc(1000 |a - b|) -- an AND of the fast issue class instead of a shift of the slow one, and a conversion
-	// that saturates where the shift wrapped)
+	// that saturates where a shift would wrap at index 2^30; -1 % on config 3)
 	const float t = __builtin_fabsf(a - b) * 4000.0f;
 	int idx;
 	asm("v_cvt_i32_f32 %0, %1" : "=v"(idx) : "v"(t));
 	const float tv = *(const float*)((const char*)g_T + ((unsigned)idx & ~3u));
-#else
-	const float t = __builtin_fabsf(a - b) * 1000.0f;
-	int idx;
-	asm("v_cvt_i32_f32 %0, %1" : "=v"(idx) : "v"(t)); // saturating conversion (a C cast is undefined past INT_MAX)
-	const float tv = *(const float*)((const char*)g_T + ((unsigned)idx << 2));
-#endif
 	return fmaxf(a, b) + tv;
 #else
 	// 8 VALU + 1 ds_read_b32.  d = max-min; d >= 15.7f, d = +inf (min = -inf) and d = NaN (both -inf) all clamp
 	// to 15.7f -> index 15700 -> + 0.0f, i.e. the reference's "return max"; below that (int)(d*1000.0f) <= 15699.
+	// (measured on MI355X: max - min is 5 % faster than fabsf(a - b) as a source modifier on the clamp)
 	const float mx = fmaxf(a, b);
-#if TDS_LSUM_ABS
-	// the |.| is a source modifier on the clamp
-	const float dc = fminf(fabsf(a - b), 15.7f);
-#else
 	const float dc = fminf(mx - fminf(a, b), 15.7f);
-#endif
 	return mx + g_T[(int)(dc * 1000.0f)];
 #endif
 }
@@ -132,20 +104,17 @@ DEV SV lsum(const SV a, const SV b) { if (a.z) return b; if (b.z) return a; retu
 
 // Two independent folds at once: both table look-ups are issued before either result is used, so a wave keeps two LDS
 // round trips in flight instead of one (the compiler, left alone, serialises the chains under the register budget).
-#ifndef TDS_PAIR
-#define TDS_PAIR 1
-#endif
 DEV void lsum2(SV& a0, const SV b0, SV& a1, const SV b1)
 {
-#if TDS_PAIR && TDS_LSUM_OOB
+#if TDS_LSUM_OOB
 	if (!a0.z && !b0.z && !a1.z && !b1.z) {
-		const float t0 = __builtin_fabsf(a0.v - b0.v) * (TDS_LSUM_AND ? 4000.0f : 1000.0f), t1 = __builtin_fabsf(a1.v - b1.v) * (TDS_LSUM_AND ? 4000.0f : 1000.0f);
+		const float t0 = __builtin_fabsf(a0.v - b0.v) * 4000.0f, t1 = __builtin_fabsf(a1.v - b1.v) * 4000.0f;
 		int i0, i1;
 		asm("v_cvt_i32_f32 %0, %1" : "=v"(i0) : "v"(t0));
 		asm("v_cvt_i32_f32 %0, %1" : "=v"(i1) : "v"(t1));
 		const float m0 = fmaxf(a0.v, b0.v), m1 = fmaxf(a1.v, b1.v);
-		const float v0 = *(const float*)((const char*)g_T + (TDS_LSUM_AND ? ((unsigned)i0 & ~3u) : ((unsigned)i0 << 2)));
-		const float v1 = *(const float*)((const char*)g_T + (TDS_LSUM_AND ? ((unsigned)i1 & ~3u) : ((unsigned)i1 << 2)));
+		const float v0 = *(const float*)((const char*)g_T + ((unsigned)i0 & ~3u));
+		const float v1 = *(const float*)((const char*)g_T + ((unsigned)i1 & ~3u));
 		__builtin_amdgcn_sched_barrier(0);
 		a0 = sv(m0 + v0);
 		a1 = sv(m1 + v1);
@@ -177,10 +146,10 @@ DEV SI addv(const SI a, const float x) { SI r; r.z = a.z; r.lo = a.z ? NEG_INF :
 DEV float lsum_term(const float d)
 {
 #if TDS_LSUM_OOB
-	const float t = d * (TDS_LSUM_AND ? 4000.0f : 1000.0f);
+	const float t = d * 4000.0f;
 	int idx;
 	asm("v_cvt_i32_f32 %0, %1" : "=v"(idx) : "v"(t));
-	return *(const float*)((const char*)g_T + (TDS_LSUM_AND ? ((unsigned)idx & ~3u) : ((unsigned)idx << 2)));
+	return *(const float*)((const char*)g_T + ((unsigned)idx & ~3u));
 #else
 	// (the clamped form: NaN -> fminf gives 15.7 -> T[15700] = 0, and -inf + 0 = -inf as well)
 	return g_T[(int)(fminf(d, 15.7f) * 1000.0f)];
@@ -195,38 +164,27 @@ DEV SI lsum(const SI a, const SI b)
 	return si(fmaxf(a.lo, b.lo) + lsum_term(dmax), fmaxf(a.hi, b.hi) + lsum_term(dmin));
 }
 DEV bool same(const SI a) { return a.lo == a.hi || (!(a.lo > NEG_INF) && !(a.hi > NEG_INF)); }
-// (for code written once over SV and SI)
-DEV void set_exact(SV& a, const float v) { a.v = v; a.z = false; }
-DEV void set_exact(SI& a, const float v) { a.lo = v; a.hi = v; a.z = false; }
-DEV void set_none(SV& a) { a = sv_none(); }
-DEV void set_none(SI& a) { a = si_none(); }
 
-// Spilled backward rows: written once, read once, 20+ GB apart -- optionally with the non-temporal hint (TDS_NT).
-#ifndef TDS_NT
-#define TDS_NT 0
-#endif
+// Spilled backward rows: written once, read once, 20+ GB apart -- with the non-temporal hint (plain accesses measured 3 %
+// slower; the hint on the posterior and silent rows as well changed nothing).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 DEV void st4(uint8_t* p, int lane, float a, float b, float c, float d)
 {
 	const f32x4 v = { a, b, c, d };
-	if (TDS_NT) __builtin_nontemporal_store(v, (f32x4*)p + lane); else ((f32x4*)p)[lane] = v;
+	__builtin_nontemporal_store(v, (f32x4*)p + lane);
 }
 DEV void st2(uint8_t* p, int lane, float a, float b)
 {
 	const f32x2 v = { a, b };
-	if (TDS_NT) __builtin_nontemporal_store(v, (f32x2*)p + lane); else ((f32x2*)p)[lane] = v;
+	__builtin_nontemporal_store(v, (f32x2*)p + lane);
 }
-DEV void st1(uint8_t* p, int lane, float a) { if (TDS_NT) __builtin_nontemporal_store(a, (float*)p + lane); else ((float*)p)[lane] = a; }
-DEV float ld1(const uint8_t* p, int lane) { return TDS_NT ? __builtin_nontemporal_load((const float*)p + lane) : ((const float*)p)[lane]; }
-DEV void stf(float* p, float v) { if (TDS_NT >= 2) __builtin_nontemporal_store(v, p); else *p = v; }
-DEV float ldf(const float* p) { return (TDS_NT >= 2) ? __builtin_nontemporal_load(p) : *p; }
-DEV void stfs(float* p, float v) { if (TDS_NT >= 3) __builtin_nontemporal_store(v, p); else *p = v; }   // silent rows
-DEV float ldfs(const float* p) { return (TDS_NT >= 3) ? __builtin_nontemporal_load(p) : *p; }
-DEV f32x4 ld4(const uint8_t* p, int lane) { return TDS_NT ? __builtin_nontemporal_load((const f32x4*)p + lane) : ((const f32x4*)p)[lane]; }
-DEV f32x2 ld2(const uint8_t* p, int lane) { return TDS_NT ? __builtin_nontemporal_load((const f32x2*)p + lane) : ((const f32x2*)p)[lane]; }
+DEV void st1(uint8_t* p, int lane, float a) { __builtin_nontemporal_store(a, (float*)p + lane); }
+DEV float ld1(const uint8_t* p, int lane) { return __builtin_nontemporal_load((const float*)p + lane); }
+DEV f32x4 ld4(const uint8_t* p, int lane) { return __builtin_nontemporal_load((const f32x4*)p + lane); }
+DEV f32x2 ld2(const uint8_t* p, int lane) { return __builtin_nontemporal_load((const f32x2*)p + lane); }
 // float number k of a lane's stride-byte record at p
-DEV float ldk(const uint8_t* p, int lane, int stride, int k) { const float* q = (const float*)(p + lane * stride) + k; return TDS_NT ? __builtin_nontemporal_load(q) : *q; }
+DEV float ldk(const uint8_t* p, int lane, int stride, int k) { return __builtin_nontemporal_load((const float*)(p + lane * stride) + k); }
 // Entry i of a host table that no kernel writes (the pruning bounds), i the same in every lane: a scalar load.  A vector load the
 // wave waits for at once would also wait for every row requested ahead of it (the counter is in-order) -- it would undo the
 // request rings of the sweeps.
@@ -282,13 +240,10 @@ DEV float emit_rt(const int b, const float hi, const float lo, const float nv, c
 #ifndef TDS_WINDOW
 #define TDS_WINDOW 0
 #endif
-#ifndef TDS_MASKDP
-#define TDS_MASKDP 1
-#endif
 // Posterior rows that are zero for every read of the tile (most barcode labels beyond the first positions, the adapter
 // label before the last ones) are neither stored by the forward sweep nor loaded by the label DP: one bit per label and
 // position (per wave) records which rows exist.  Only on the register path of the label DP.
-constexpr bool kMaskDP = TDS_MASKDP && (TD_H - kFirstN <= TDS_REG_H);
+constexpr bool kMaskDP = TD_H - kFirstN <= TDS_REG_H;
 
 struct Wv {
 	uint32_t* pmask;   // [TD_H][nwm] posterior-row bits
@@ -359,19 +314,8 @@ struct Wv {
 // single HMM.  Bound tables for both ends: td_spec_prune_tables (td_jit.hip), checked against the oracle's DP matrices in
 // tests/test_prune.py.
 // ---------------------------------------------------------------------------------------------------------
-#ifndef TDS_DEADCS
-#define TDS_DEADCS 1   // the first segment's silent_backward row is only folded where it is read (position 1); 0: everywhere
-// (The mirror image -- the last segment's silent_forward row is only read at each read's last position -- was built too: its
-// folds moved behind the column chain under one branch cost the forward sweep more than they saved, 24.0 -> 26.8 ms.)
-#endif
 #ifndef TDS_LATE_CS
 #define TDS_LATE_CS 1   // the last segment's silent_forward row is folded from the tile's shortest read on only (0: everywhere)
-#endif
-#ifndef TDS_SPLIT_BWD
-#define TDS_SPLIT_BWD 1   // the positions past the spill cut of a pruned segment run in a loop of their own (0: one loop, branch per HMM)
-#endif
-#ifndef TDS_DYNAMIC
-#define TDS_DYNAMIC 1   // tiles handed out through a counter (0: static stride over the wave slots)
 #endif
 #ifndef TDS_PF_DIST
 #define TDS_PF_DIST 4   // positions a light group of the sweeps requests its rows ahead (1: one position, as the heavy groups)
@@ -403,18 +347,9 @@ struct Wv {
 #define TDS_PRUNE_STATS 0    // diagnostic: counter slots 194.. = restarted sweeps: forward bridges' interval steps, forward bridges, backward bridges' interval steps, backward bridges, tiles with a forward restart, tiles failing on a bridge in the forward sweep; 206, 207 = tiles with a backward restart, of those failing; 224.. = trailing: decisions, sum of required stops, fall-backs, sum of stops used; 228.. lanes failing wa / wb / total_prob; 232.. = leading: cut decisions, sum of required cuts, spill-too-short, failed checks, tiles, sum of cuts used, dense tiles, sum of spill cuts
 #endif
 
-// Checkpointing of the spilled backward rows: the kernel is bound by the HBM traffic of that spill, and has VALU issue
-// slots to spare, so every TDS_CKPT-th position's rows are not stored; the forward sweep recomputes them from the next
-// position's stored rows with one backward step (bwd_row), bit for bit.  The rule is wave-uniform: only positions below
-// the tile's shortest read are skipped, so the row i+1 a recomputation needs always exists.
-#ifndef TDS_CKPT
-#define TDS_CKPT 0
-#endif
-DEV bool ckpt_skipped(const Wv& w, int i) { return TDS_CKPT > 0 && (i % (TDS_CKPT > 0 ? TDS_CKPT : 1)) == 0 && i < w.tmin; }
-
 constexpr int cmin(int a, int b) { return a < b ? a : b; }
 // request distance of a group of the sweeps with `cols` columns in all (see bwd_group)
-constexpr int pf_dist(int cols, bool rt) { return (!rt && TDS_CKPT == 0 && cols <= TDS_PF_COLS) ? TDS_PF_DIST : 1; }
+constexpr int pf_dist(int cols, bool rt) { return (!rt && cols <= TDS_PF_COLS) ? TDS_PF_DIST : 1; }
 // A request ring of PD slots is walked in blocks of PD positions with the slot index a compile-time constant.  Whole blocks run
 // as straight code: were each position guarded on its own, the copies of the step would be joined by branches, the slots would
 // change registers from copy to copy, and the moves between them would wait for the very loads just issued.  The last, partial
@@ -439,8 +374,7 @@ DEV void ring_rest(F& step, const int base, const int iend)
 
 // ---------------------------------------------------------------------------------------------------------
 // One backward step of one HMM: (M, I)_backward of every column at position i from the values at i+1.
-// barcode_hmm.c:3518-3586 without the silent-state folds.  Used by the backward sweep and, for the positions whose
-// rows the backward sweep does not store (TDS_CKPT), by the forward sweep.
+// barcode_hmm.c:3518-3586 without the silent-state folds.
 //   Mn, In: rows of position i+1;  Pn = P_backward_next[i+1];  kc / c: base x_{i+1};  kx / xi: base x_i
 // ---------------------------------------------------------------------------------------------------------
 template <int J, bool RT>
@@ -530,8 +464,9 @@ DEV void bwd_cols(const int fa, const float (&Mn)[kNCol[J]], const float (&In)[k
 // n positions further on fades like e^(-8.3 n): after a few positions it is below the resolution of the table operator --
 // the sweep can start ANYWHERE with ANY rows and arrives at the same floats.  Proving that for a given read is what the
 // interval type is for: the sweep is started W positions early with the interval [-inf, host upper bound] in every row and
-// run in interval arithmetic (bwd_row over SI), which encloses the reference's floats at every step; once lo == hi in every
-// row the enclosure IS the reference's value, bit for bit, and the plain sweep takes over from there.  Rows that have not
+// run in interval arithmetic (SI), which encloses the reference's floats at every step; once lo == hi in every row the
+// enclosure IS the reference's value, bit for bit, and the plain sweep takes over from there (the staircase bridges below
+// run the intervals column by column).  Rows that have not
 // closed after W positions fail the tile (w.bad bit 5): it is decoded again densely, like after any other failed check.
 // Mirror image at the 3' end: the forward values of the trailing segments (the adapter) are only used from `sstop` on; their
 // forward sweep starts W positions before it from [-inf, bound].  tests/test_prune.py forces both failure routes.
@@ -550,7 +485,7 @@ DEV void bwd_cols(const int fa, const float (&Mn)[kNCol[J]], const float (&In)[k
 // HMM loop) 30.3 -> 27.0 ms per 2^18 reads, config 3 (nine barcode HMMs and a spacer) 19.1 -> 18.6 ms per 2^20.  OFF for config
 // 2's eight 4-column HMMs: a bridge runs one HMM at a time, a single dependent chain without the interleaving the grouped
 // sweeps live on, and there it costs more than the dense positions it replaces.  The forward restart of the trailing segments
-// (TDS_RESTART_FWD) is off as well: a 13-column adapter needs ~27 positions to close, and W is shared with the backward bridges.
+// (TDS_RESTART_FWD) was off as well in round 3: a 13-column adapter needed ~27 positions of all-interval arithmetic to close.
 // ---------------------------------------------------------------------------------------------------------
 #ifndef TDS_RESTART
 #define TDS_RESTART 0
@@ -562,163 +497,31 @@ DEV void bwd_cols(const int fa, const float (&Mn)[kNCol[J]], const float (&In)[k
 #define TDS_RESTART_FWD 1  // the trailing segments' forward sweep as well (round 4: on, as a staircase -- a 13-column adapter closes in 37 positions of a 44-position window; the all-interval bridge of round 3 needed 27 positions of all-interval arithmetic and lost)
 #endif
 
-// bwd_row over intervals: same terms, same order
-template <int J, bool RT>
-DEV void bwd_row_iv(const int fa, const SI (&Mn)[kNCol[J]], const SI (&In)[kNCol[J]], const float Pn,
-                    const BaseMask& kc, const int c, const BaseMask& kx, const int xi, SI (&Mc)[kNCol[J]], SI (&Ic)[kNCol[J]])
-{
-#define EM(gcol, mask, xval) (RT ? emit_rt(kBase[colr + (gcol)], kHi[J], kLo[J], kNv[J], mask, xval) : EMIT_M(col0 + (gcol), mask))
-	constexpr int NC = kNCol[J];
-	constexpr int K = NC - 1;
-	const int col0 = kColOff[J] + (RT ? 0 : fa) * NC;
-	const int colr = kColOff[J] + fa * NC;
-	(void)colr;
-	SI Dp = si_none();
-	{
-		const int q = col0 + K;
-		const SI M = addc(si(Pn), kCols[q].t[7]);
-		SI I = addc(si(Pn), kCols[q].t[8]);
-		I = lsum(I, addv(addc(Mn[K], kCols[q].t[4]), EM(K, kc, c)));
-		I = lsum(I, addv(addc(In[K], kCols[q].t[3]), EMIT_I(q, kc)));
-		Mc[K] = M; Ic[K] = I;
-	}
-#pragma unroll
-	for (int g = K - 1; g >= 0; --g) {
-		const int q = col0 + g;
-		const float epc = EM(g + 1, kc, c);
-		const float eic = EMIT_I(q, kc);
-		SI M = addc(addv(Mn[g + 1], epc), kCols[q].t[0]);
-		SI I = addv(addc(In[g], kCols[q].t[3]), eic);
-		M = lsum(M, addc(si(Pn), kCols[q].t[7]));
-		I = lsum(I, addc(si(Pn), kCols[q].t[8]));
-		M = lsum(M, addc(addv(In[g], eic), kCols[q].t[1]));
-		I = lsum(I, addv(addc(Mn[g + 1], kCols[q].t[4]), epc));
-		SI D = addc(Dp, kCols[q].t[5]);
-		M = lsum(M, addc(Dp, kCols[q].t[2]));
-		D = lsum(D, addc(addv(Mc[g + 1], EM(g + 1, kx, xi)), kCols[q].t[6]));
-		Mc[g] = M; Ic[g] = I; Dp = D;
-	}
-#undef EM
-}
-
-// Bridge for one HMM of a leading segment: positions p_hi .. p_lo + 1 from [-inf, bound], the rows of position p_lo + 1 go to
-// w.rs.  Interval steps until every row of every lane has closed, plain steps after that.
-// Upper end the backward bridges of leading segment J start from: every row of position p_hi + 1 is at most
-// max_k (gq_J[k] + Q[p_hi + 2 + k]) + log(number of k) (td_jit.hip, "impulse responses") -- and at most the absolute bound.
-template <int J>
-DEV float bwd_restart_hi(const Wv& w, const int p_hi)
-{
-	if (!(w.len > p_hi)) return NEG_INF;   // the read ends at or before p_hi: its rows there are the -inf the dense sweep starts from
-	const float* gq = w.ptab + (int64_t)(8 + J) * w.pstride;
-	float hi = NEG_INF;
-	for (int k = 0; p_hi + 2 + k <= w.tmax + 1; k++) {
-		const int pos = p_hi + 2 + k;
-		if (pos <= w.len + 1) hi = fmaxf(hi, gq[k] + w.qr[pos * TD_WAVE + w.lane]);
-	}
-	hi = hi + (__logf((float)(w.len - p_hi)) + 0.02f);
-	return fminf(hi, w.bwt[w.len - p_hi - 1]);
-}
-
-template <int J, bool RT>
-DEV void bwd_restart(const Wv& w, const uint8_t* __restrict__ codes, const float* __restrict__ P, const int fa, const int p_hi, const int p_lo, const float hi_bound)
-{
-	constexpr int NC = kNCol[J];
-	constexpr bool p_init = (J == TD_S - 1);
-#define PBW(pos) (p_init ? (((pos) == w.len + 1) ? 0.0f : NEG_INF) : P[(pos) * TD_WAVE + w.lane])
-	// rows of position p_hi + 1: -inf for a read that ends at or before p_hi (where the dense sweep starts from -inf too)
-#ifdef TDS_RESTART_FAKE_INIT
-	const float hi0 = NEG_INF;   // diagnostic only (unsound): timing of the bridges with a start that closes at once
-#else
-	const float hi0 = hi_bound;
-#endif
-	SI Mn[NC], In[NC];
-#pragma unroll
-	for (int g = 0; g < NC; g++) { Mn[g] = si(NEG_INF, hi0); In[g] = si(NEG_INF, hi0); }
-	int c = codes[(p_hi + 1) * TD_WAVE + w.lane];
-	float Pn = PBW(p_hi + 1);
-	int i = p_hi;
-	bool open = true;
-	for (; i > p_lo && open; --i) {
-		const int xi = codes[i * TD_WAVE + w.lane];
-		if (i <= w.len) {
-			SI Mc[NC], Ic[NC];
-			bwd_row_iv<J, RT>(fa, Mn, In, Pn, mk_mask(c), c, mk_mask(xi), xi, Mc, Ic);
-#pragma unroll
-			for (int g = 0; g < NC; g++) { Mn[g] = Mc[g]; In[g] = Ic[g]; }
-		}
-		c = xi;
-		Pn = PBW(i);
-		bool cl = true;
-#pragma unroll
-		for (int g = 0; g < NC; g++) cl = cl && same(Mn[g]) && same(In[g]);
-		open = __builtin_amdgcn_ballot_w64(!cl) != 0;
-#ifdef TDS_RESTART_MIN_IV
-		if (p_hi - i + 1 < TDS_RESTART_MIN_IV) open = true;   // diagnostic only: stay in interval arithmetic for so many positions
-#endif
-	}
-#ifdef TDS_RESTART_MIN_IV
-	open = false;
-#endif
-	if (open) w.bad |= 32;
-	if (TDS_PRUNE_STATS && w.lane == 0) { atomicAdd(&w.stats[TDS_DIAG(196)], (unsigned long long)(p_hi - i)); atomicAdd(&w.stats[TDS_DIAG(197)], 1ull); }
-	float Mx[NC], Ix[NC];
-#pragma unroll
-	for (int g = 0; g < NC; g++) { Mx[g] = Mn[g].lo; Ix[g] = In[g].lo; }
-	for (; i > p_lo; --i) {   // closed: the reference's own arithmetic from here on
-		const int xi = codes[i * TD_WAVE + w.lane];
-		if (i <= w.len) {
-			SV Mc[NC], Ic[NC];
-			bwd_row<J, RT>(fa, Mx, Ix, Pn, mk_mask(c), c, mk_mask(xi), xi, Mc, Ic);
-#pragma unroll
-			for (int g = 0; g < NC; g++) { Mx[g] = Mc[g].v; Ix[g] = Ic[g].v; }
-		}
-		c = xi;
-		Pn = PBW(i);
-	}
-	float* rs = w.rs + (int64_t)(kColOff[J] + fa * NC) * 2 * TD_WAVE + w.lane;
-#pragma unroll
-	for (int g = 0; g < NC; g++) { rs[(2 * g) * TD_WAVE] = Mx[g]; rs[(2 * g + 1) * TD_WAVE] = Ix[g]; }
-#undef PBW
-}
-
-template <int J, int F>
-DEV void bwd_restart_rest(const Wv& w, const uint8_t* __restrict__ codes, const float* __restrict__ P, const int p_hi, const int p_lo, const float hi_bound)
-{
-	if constexpr (F < kNHmm[J]) {   // (unrolled HMMs: F must be a compile-time constant for their parameters to be literals)
-		bwd_restart<J, false>(w, codes, P, F, p_hi, p_lo, hi_bound);
-		bwd_restart_rest<J, F + 1>(w, codes, P, p_hi, p_lo, hi_bound);
-	}
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// Staircase bridges (TDS_STAIR, round 4): the same certificate at a third of the cost.
-//
-// The interval bridge above treats every row of the HMM alike: all 2 * columns rows are intervals until the last one has
-// closed.  But the recurrence has structure: column g at position i reads column g + 1 (at i + 1 and at i), the silent row behind
-// the segment, and ONE value of its own -- I_backward[g][i + 1], the insert self-loop (barcode_hmm.c:3544-3586: M_backward and
+// Staircase bridges (round 4): the same certificate at a third of the cost of round 3's bridges, which treated every row of
+// the HMM alike -- all 2 * columns rows intervals until the last one had closed (removed; see git history).  But the
+// recurrence has structure: column g at position i reads column g + 1 (at i + 1 and at i), the silent row behind the segment,
+// and ONE value of its own -- I_backward[g][i + 1], the insert self-loop (barcode_hmm.c:3544-3586: M_backward and
 // D_backward of a column never read that column's own row).  So exactness spreads from the last column (which reads the silent
 // row only) to the first, one column at a time, and at any position the columns fall into three classes:
 //   * g >  gc: exact at position i + 1 -- computed in the reference's plain arithmetic, one table look-up per fold;
 //   * g == gc: the "candidate": column gc + 1 is exact, its own rows are intervals that start as [-inf, bound] and enclose the
-//              reference's floats (SI, as above); as soon as both have closed in every lane the column is exact and gc - 1 takes over;
+//              reference's floats (SI); as soon as both have closed in every lane the column is exact and gc - 1 takes over;
 //   * g <  gc: not computed at all -- nothing that is computed reads them.
 // Only one column per position pays for interval arithmetic, the columns above it cost what a dense position costs and the
 // ones below cost nothing: config 3's barcode HMMs (five live columns, three positions per column to close) take ~270 logsum
-// evaluations' worth per bridge instead of ~820, config 5's likewise.  The certificate is the one of the interval bridges, row by
-// row: a candidate starts from an upper end that holds for every state of the segment at that position (bwd_stair_bounds: the
+// evaluations' worth per bridge instead of ~820, config 5's likewise.  The certificate is the one above, row by row: a
+// candidate starts from an upper end that holds for every state of the segment at that position (bwd_stair_bounds: the
 // relative bound, td_jit.hip "impulse responses"), and it is only ever declared exact when lo == hi bit for bit.
 // A wave whose bridges do not close inside their window widens the window before it gives the restarts up (w.rW).
 // ---------------------------------------------------------------------------------------------------------
-#ifndef TDS_STAIR
-#define TDS_STAIR 1
-#endif
 #ifndef TDS_RESTART_WMAX
 #define TDS_RESTART_WMAX 44   // widest bridge window a wave tries before it goes on without restarts
 #endif
 DEV SI to_si(const SV a) { return a.z ? si_none() : si(a.v); }
 
 // Upper ends for the rows of positions p_lo + 1 .. p_hi + 1 of leading segment J (any state; this lane's read), into w.hb:
-// max_k (gq_J[k] + Q[t + 1 + k]) + log(number of k) + 0.02, at most the absolute bound (bwd_restart_hi for every position).
+// max_k (gq_J[k] + Q[t + 1 + k]) + log(number of k) + 0.02 (td_jit.hip, "impulse responses"), at most the absolute bound.
 template <int J>
 DEV void bwd_stair_bounds(const Wv& w, const int p_lo, const int p_hi)
 {
@@ -761,7 +564,7 @@ DEV float ub_done(const float mx, const int n)
 }
 
 // One position of one HMM whose columns above GC are exact (GC compile-time; -1: every column is).  barcode_hmm.c:3518-3586, the
-// terms and their order as in bwd_row() / bwd_row_iv().  The rows of position i + 1 come in as intervals (Mlo / Mhi, Ilo / Ihi)
+// terms and their order as in bwd_row().  The rows of position i + 1 come in as intervals (Mlo / Mhi, Ilo / Ihi)
 // and are replaced by those of position i; by column:
 //   g > GC                    exact: lo == hi, the reference's plain arithmetic on lo;
 //   GC >= g > GC - TDS_STAIR_WN    the window: interval arithmetic, enclosing the reference's floats (lo may still be -inf);
@@ -969,8 +772,8 @@ DEV void bwd_stair_rest(const Wv& w, const uint8_t* __restrict__ codes, const fl
 		{ \
 			const int ip = (i > PD) ? i - PD : 1; \
 			xi_q[d_] = codes[ip * TD_WAVE + w.lane]; \
-			Pi_q[d_] = p_init ? ((ip == w.len + 1) ? 0.0f : NEG_INF) : ldfs(&P[ip * TD_WAVE + w.lane]); \
-			if (!first && (!TDS_DEADCS || J > 0 || ip == 1)) cs_q[d_] = ldfs(&Cs[ip * TD_WAVE + w.lane]); \
+			Pi_q[d_] = p_init ? ((ip == w.len + 1) ? 0.0f : NEG_INF) : P[ip * TD_WAVE + w.lane]; \
+			if (!first && (J > 0 || ip == 1)) cs_q[d_] = Cs[ip * TD_WAVE + w.lane]; \
 			if (sfx_nb && ip < w.sstopS) { TDS_BWD_BOUNDS(d_, ip) } \
 		} \
 		const bool want_cs = (WANT_CS_) && !defer_cs; \
@@ -1014,8 +817,8 @@ _Pragma("unroll") \
 					if (sfx_nb && tailb && skip_live) { if (!(cs.v >= wd_q[d_])) w.bad |= 16; } \
 					cs = lsum(cs, addc(sv(Pi), kSkip[J])); \
 				} \
-				if (!TDS_DIAG_NO_SPILL && !ckpt_skipped(w, i) && (SPILL_)) { \
-					uint8_t* bw = BW + ((int64_t)kBwOff[kHmmOff[J] + FL(f)] * w.lmax + (int64_t)TDS_SPILL_POS(i - 1) * ROWH) * (TD_WAVE * 4); \
+				if (SPILL_) { \
+					uint8_t* bw = BW + ((int64_t)kBwOff[kHmmOff[J] + FL(f)] * w.lmax + (int64_t)(i - 1) * ROWH) * (TD_WAVE * 4); \
 _Pragma("unroll") \
 					for (int p = 0; p < NSF / 2; p++) \
 						st4(bw + p * (TD_WAVE * 16), w.lane, Mc[2 * p].v, Ic[2 * p].v, Mc[2 * p + 1].v, Ic[2 * p + 1].v); \
@@ -1030,7 +833,7 @@ _Pragma("unroll") \
 _Pragma("unroll") \
 				for (int g = 0; g < NC; g++) { Mn[f][g] = Mc[g].v; In[f][g] = Ic[g].v; } \
 			} \
-			if (want_cs) stfs(&Cs[i * TD_WAVE + w.lane], cs.v); \
+			if (want_cs) Cs[i * TD_WAVE + w.lane] = cs.v; \
 		} \
 		c = xi; \
 		Pn = Pi;
@@ -1069,7 +872,7 @@ DEV void bwd_group(const Wv& w, const uint8_t* __restrict__ codes, const float* 
 #pragma unroll
 		for (int g = 0; g < NC; g++) { Mn[f][g] = NEG_INF; In[f][g] = NEG_INF; }
 	}
-	if (TDS_RESTART && J < kPruneSegs && w.rb_on) {   // rows of position istart + 1, left by bwd_restart()
+	if (TDS_RESTART && J < kPruneSegs && w.rb_on) {   // rows of position istart + 1, left by bwd_stair()
 #pragma unroll
 		for (int f = 0; f < NF; f++) {
 			const float* rs = w.rs + (int64_t)(kColOff[J] + FL(f) * NC) * 2 * TD_WAVE + w.lane;
@@ -1085,7 +888,7 @@ DEV void bwd_group(const Wv& w, const uint8_t* __restrict__ codes, const float* 
 	// known, so they are formed in registers instead of being written to and read from the workspace.
 	constexpr bool p_init = (J == TD_S - 1);
 #define PBW(pos) (p_init ? (((pos) == w.len + 1) ? 0.0f : NEG_INF) : P[(pos) * TD_WAVE + w.lane])
-	// a leading segment whose far positions were bridged by bwd_restart() is swept from the hand-over position on
+	// a leading segment whose far positions were bridged by bwd_stair() is swept from the hand-over position on
 	const bool resumed = TDS_RESTART && (J < kPruneSegs) && w.rb_on;
 	const int istart = resumed ? w.cutS + J * (w.rW + 1) : w.tmax;
 	int c = resumed ? (int)codes[(istart + 1) * TD_WAVE + w.lane] : 0;   // x_{i+1} (0 past the end of the read)
@@ -1113,28 +916,31 @@ DEV void bwd_group(const Wv& w, const uint8_t* __restrict__ codes, const float* 
 	const int ilow = (J >= kSfxFirst) ? w.sstopS : 1;
 	// One position of the group (TDS_BWD_STEP above).  The sweeps live off one long basic block per iteration that the
 	// scheduler can interleave, so the positions whose rows are not spilled (past the spill cut of a pruned segment) run in a
-	// loop of their own without the spill code instead of branching around it per HMM.
+	// loop of their own without the spill code instead of branching around it per HMM.  The first segment's silent row is only
+	// folded where it is read, at position 1.  (The mirror image -- the last segment's silent_forward row is only read at each
+	// read's last position -- was built too: its folds moved behind the column chain under one branch cost the forward sweep
+	// more than they saved, 24.0 -> 26.8 ms.)
 	if constexpr (PD > 1) {
 		int base = istart;
 		for (; base - (PD - 1) >= ilow; base -= PD) {   // whole blocks as straight code, then the partial one (see ring_block)
 #pragma unroll
 			for (int d_ = 0; d_ < PD; d_++) {
 				const int i = base - d_;
-				{ TDS_BWD_STEP((J >= kPruneSegs || i <= w.cutS || i == 1), (!TDS_DEADCS || (J > 0) || i == 1)) }
+				{ TDS_BWD_STEP((J >= kPruneSegs || i <= w.cutS || i == 1), ((J > 0) || i == 1)) }
 			}
 		}
 #pragma unroll
 		for (int d_ = 0; d_ < PD - 1; d_++) {
 			const int i = base - d_;
-			if (i >= ilow) { TDS_BWD_STEP((J >= kPruneSegs || i <= w.cutS || i == 1), (!TDS_DEADCS || (J > 0) || i == 1)) }
+			if (i >= ilow) { TDS_BWD_STEP((J >= kPruneSegs || i <= w.cutS || i == 1), ((J > 0) || i == 1)) }
 		}
 	} else {
 		constexpr int d_ = 0;
 		int i = istart;
-		if (TDS_SPLIT_BWD && J < kPruneSegs) {
-			for (; i > w.cutS && i >= 2 && i >= ilow; --i) { TDS_BWD_STEP(false, (!TDS_DEADCS || (J > 0))) }
+		if (J < kPruneSegs) {
+			for (; i > w.cutS && i >= 2 && i >= ilow; --i) { TDS_BWD_STEP(false, (J > 0)) }
 		}
-		for (; i >= ilow; --i) { TDS_BWD_STEP((TDS_SPLIT_BWD || J >= kPruneSegs || i <= w.cutS), (!TDS_DEADCS || (J > 0) || i == 1)) }
+		for (; i >= ilow; --i) { TDS_BWD_STEP(true, ((J > 0) || i == 1)) }
 	}
 #undef EM
 #undef PBW
@@ -1184,7 +990,7 @@ DEV void bwd_fold_first(const Wv& w, const uint8_t* __restrict__ codes, const fl
 	SV cs; cs.v = NEG_INF; cs.z = false;            // (an empty accumulator: logsum(-inf, x) == x bit for bit)
 	if constexpr (kRt[J] > 0) { for (int f = 0; f < kRt[J]; f++) fold_first_hmm<J, 0, true>(w, f, x1, kx, Pi, cs); }
 	fold_first_rest<J, kRt[J]>(w, x1, kx, Pi, cs);
-	stfs(&Cs[1 * TD_WAVE + w.lane], cs.v);
+	Cs[1 * TD_WAVE + w.lane] = cs.v;
 }
 
 template <int J, int F0>
@@ -1194,23 +1000,9 @@ DEV void bwd_groups(const Wv& w, const uint8_t* __restrict__ codes, const float*
 	if constexpr (TDS_RESTART && F0 == 0 && J < kPruneSegs) {
 		if (w.rb_on) {   // bridge the positions between the end of the read and the hand-over, HMM by HMM
 			const int p_lo = w.cutS + J * (w.rW + 1), p_hi = p_lo + w.rW;
-#ifdef TDS_DIAG_SKIP_BRIDGE
-			// diagnostic only (results unproven): what the bridges cost -- the dense sweep resumes from -inf rows
-			{
-				for (int f = 0; f < kNHmm[J]; f++) {
-					float* rs = w.rs + (int64_t)(kColOff[J] + f * kNCol[J]) * 2 * TD_WAVE + w.lane;
-					for (int g = 0; g < 2 * kNCol[J]; g++) rs[g * TD_WAVE] = NEG_INF;
-				}
-			}
-#elif TDS_STAIR
 			bwd_stair_bounds<J>(w, p_hi, p_hi);   // (the rows of position p_hi + 1)
 			if constexpr (kRtB[J] > 0) { for (int f = 0; f < kRtB[J]; f++) bwd_stair<J, true>(w, codes, P, f, p_hi, p_lo); }
 			bwd_stair_rest<J, kRtB[J]>(w, codes, P, p_hi, p_lo);
-#else
-			const float hi_bound = bwd_restart_hi<J>(w, p_hi);
-			if constexpr (kRtB[J] > 0) { for (int f = 0; f < kRtB[J]; f++) bwd_restart<J, true>(w, codes, P, f, p_hi, p_lo, hi_bound); }
-			bwd_restart_rest<J, kRtB[J]>(w, codes, P, p_hi, p_lo, hi_bound);
-#endif
 		}
 	}
 	if constexpr (F0 == 0 && kRt[J] > 0) {
@@ -1254,97 +1046,6 @@ DEV float post_prob(float lp)
 	return p;
 }
 
-// The forward column chain of the single HMM of segment J at one position (barcode_hmm.c:4220-4334 without the silent-state and
-// posterior folds), over plain values and over intervals: the terms and their order are fwd_group's.  Used by fwd_restart().
-template <int J, typename V>
-DEV void fwd_row(const V (&Mp)[kNCol[J]], const V (&Ip)[kNCol[J]], const float Pm, const BaseMask& kc, V (&Mc)[kNCol[J]], V (&Ic)[kNCol[J]])
-{
-	constexpr int NC = kNCol[J];
-	constexpr int K = NC - 1;
-	constexpr int col0 = kColOff[J];
-	V PmS; PmS = Mp[0]; PmS.z = false; set_exact(PmS, Pm);
-	V Dc = Mp[0]; set_none(Dc);
-	{
-		const int q = col0;
-		const V M = addv(addc(PmS, kCols[q].sM), EMIT_M(q, kc));
-		V I = addc(PmS, kCols[q].sI);
-		I = lsum(I, addc(Ip[0], kCols[q].t[3]));
-		I = lsum(I, addc(Mp[0], kCols[q].t[1]));
-		I = addv(I, EMIT_I(q, kc));
-		Mc[0] = M; Ic[0] = I;
-	}
-#pragma unroll
-	for (int g = 1; g <= K; ++g) {
-		const int q = col0 + g, qp = q - 1;
-		V M = addc(PmS, kCols[q].sM);
-		V I = addc(PmS, kCols[q].sI);
-		M = lsum(M, addc(Mp[g - 1], kCols[qp].t[0])); I = lsum(I, addc(Ip[g], kCols[q].t[3]));
-		M = lsum(M, addc(Ip[g - 1], kCols[qp].t[4])); I = lsum(I, addc(Mp[g], kCols[q].t[1]));
-		V D = addc(Mc[g - 1], kCols[qp].t[2]);
-		M = lsum(M, addc(Dc, kCols[qp].t[6])); D = lsum(D, addc(Dc, kCols[qp].t[5]));
-		M = addv(M, EMIT_M(q, kc));
-		I = addv(I, EMIT_I(q, kc));
-		Mc[g] = M; Ic[g] = I; Dc = D;
-	}
-}
-
-// Bridge for a trailing segment (one HMM): positions q_lo .. q_hi - 1 from [-inf, bound] at q_lo - 1; the rows of position
-// q_hi - 1 go to w.rs.  Every read of the tile reaches q_hi (q_hi <= sstop <= the tile's shortest read).
-template <int J>
-DEV void fwd_restart(const Wv& w, const uint8_t* __restrict__ codes, const float* __restrict__ P, const int q_lo, const int q_hi)
-{
-	constexpr int NC = kNCol[J];
-#ifdef TDS_RESTART_FAKE_INIT
-	const float hi0 = NEG_INF;
-#else
-	// every row of position t = q_lo - 1 is at most max_k (gf_J[k] + PR[t - k]) + log(number of k), and at most the absolute bound
-	float hi0 = NEG_INF;
-	{
-		const float* gf = w.ptab + (int64_t)(12 + J - kSfxFirst) * w.pstride;
-		const int t = q_lo - 1;
-		for (int k = 1; k <= t; k++) hi0 = fmaxf(hi0, gf[k] + w.pr[(t - k) * TD_WAVE + w.lane]);
-		hi0 = fminf(hi0 + (__logf((float)t) + 0.02f), w.fbs[t]);
-	}
-#endif
-	SI Mp[NC], Ip[NC];
-#pragma unroll
-	for (int g = 0; g < NC; g++) { Mp[g] = si(NEG_INF, hi0); Ip[g] = si(NEG_INF, hi0); }
-	int i = q_lo;
-	bool open = true;
-	for (; i < q_hi && open; ++i) {
-		const int c = codes[i * TD_WAVE + w.lane];
-		const float Pm = P[(i - 1) * TD_WAVE + w.lane];
-		SI Mc[NC], Ic[NC];
-		fwd_row<J, SI>(Mp, Ip, Pm, mk_mask(c), Mc, Ic);
-		bool cl = true;
-#pragma unroll
-		for (int g = 0; g < NC; g++) { Mp[g] = Mc[g]; Ip[g] = Ic[g]; cl = cl && same(Mc[g]) && same(Ic[g]); }
-		open = __builtin_amdgcn_ballot_w64(!cl) != 0;
-#ifdef TDS_RESTART_MIN_IV
-		if (i - q_lo + 1 < TDS_RESTART_MIN_IV) open = true;
-#endif
-	}
-#ifdef TDS_RESTART_MIN_IV
-	open = false;
-#endif
-	if (open) w.bad |= 32;
-	if (TDS_PRUNE_STATS && w.lane == 0) { atomicAdd(&w.stats[TDS_DIAG(194)], (unsigned long long)(i - q_lo)); atomicAdd(&w.stats[TDS_DIAG(195)], 1ull); }
-	SV Mx[NC], Ix[NC];
-#pragma unroll
-	for (int g = 0; g < NC; g++) { Mx[g] = sv(Mp[g].lo); Ix[g] = sv(Ip[g].lo); }
-	for (; i < q_hi; ++i) {   // closed: the reference's own arithmetic from here on
-		const int c = codes[i * TD_WAVE + w.lane];
-		const float Pm = P[(i - 1) * TD_WAVE + w.lane];
-		SV Mc[NC], Ic[NC];
-		fwd_row<J, SV>(Mx, Ix, Pm, mk_mask(c), Mc, Ic);
-#pragma unroll
-		for (int g = 0; g < NC; g++) { Mx[g] = sv(Mc[g].v); Ix[g] = sv(Ic[g].v); }
-	}
-	float* rs = w.rs + (int64_t)kColOff[J] * 2 * TD_WAVE + w.lane;
-#pragma unroll
-	for (int g = 0; g < NC; g++) { rs[(2 * g) * TD_WAVE] = Mx[g].v; rs[(2 * g + 1) * TD_WAVE] = Ix[g].v; }
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Forward staircase (round 4): the mirror image of bwd_stair for the single HMM of a trailing segment (the 3' adapter).  Its
 // forward rows are only used from position sstop on; the sweep starts `w.rWf` positions before that from unknown rows.  Column g
@@ -1380,7 +1081,7 @@ DEV void fstair_step(const int gcr, float (&Mlo)[kNCol[J]], float (&Mhi)[kNCol[J
 		const int q = col0 + g, qp = q - 1;
 		const float em = EMIT_M(q, kc), ei = EMIT_I(q, kc);
 		if (g < gcv) {
-			// exact: fwd_row over plain values
+			// exact: plain values
 			SV M = addc(sv(Pm), kCols[q].sM);
 			SV I = addc(sv(Pm), kCols[q].sI);
 			SV Dx; Dx.z = Dc.z; Dx.v = Dc.lo;
@@ -1542,7 +1243,7 @@ DEV void fwd_group(const Wv& w, const uint8_t* __restrict__ codes, const float* 
 #pragma unroll
 		for (int g = 0; g < NC; g++) { Mp[f][g] = NEG_INF; Ip[f][g] = NEG_INF; }
 	}
-	if (TDS_RESTART && J >= kSfxFirst && w.rf_on) {   // rows of position i0 - 1, left by fwd_restart() (one HMM: NF == 1)
+	if (TDS_RESTART && J >= kSfxFirst && w.rf_on) {   // rows of position i0 - 1, left by fwd_stair() (one HMM: NF == 1)
 		const float* rs = w.rs + (int64_t)kColOff[J] * 2 * TD_WAVE + w.lane;
 #pragma unroll
 		for (int g = 0; g < NC; g++) { Mp[0][g] = rs[(2 * g) * TD_WAVE]; Ip[0][g] = rs[(2 * g + 1) * TD_WAVE]; }
@@ -1554,7 +1255,7 @@ DEV void fwd_group(const Wv& w, const uint8_t* __restrict__ codes, const float* 
 	// The first segment's P is the initial previous_silent row (barcode_hmm.c:4191-4196: [0] = 0, -inf elsewhere): formed in
 	// registers, never stored.
 	constexpr bool p_init = (J == 0);
-	// a trailing segment whose early positions were bridged by fwd_restart() is swept from the hand-over position on
+	// a trailing segment whose early positions were bridged by fwd_stair() is swept from the hand-over position on
 	const bool resumed = TDS_RESTART && (J >= kSfxFirst) && w.rf_on;
 	const int i0 = resumed ? w.sstop - (TD_S - 1 - J) * (w.rWf + 1) : 1;
 	float Pm = p_init ? 0.0f : P[(i0 - 1) * TD_WAVE + w.lane]; // P[i-1], carried
@@ -1570,14 +1271,14 @@ DEV void fwd_group(const Wv& w, const uint8_t* __restrict__ codes, const float* 
 	                                                       // then costs no load, and no register is overwritten under a pending one)
 	// P_backward_next of the last segment is the initial previous_silent row of the backward pass: formed, not loaded
 	constexpr bool pb_init = (J == TD_S - 1);
-#define PBR(pos) (pb_init ? (((pos) == w.len + 1) ? 0.0f : NEG_INF) : ldfs(&PB[(pos) * TD_WAVE + w.lane]))
-#define BWROW(f_, pos_) (BW + ((int64_t)kBwOff[kHmmOff[J] + f0 + (f_)] * w.lmax + (int64_t)TDS_SPILL_POS((pos_) - 1) * ROWH) * (TD_WAVE * 4))
+#define PBR(pos) (pb_init ? (((pos) == w.len + 1) ? 0.0f : NEG_INF) : PB[(pos) * TD_WAVE + w.lane])
+#define BWROW(f_, pos_) (BW + ((int64_t)kBwOff[kHmmOff[J] + f0 + (f_)] * w.lmax + (int64_t)((pos_) - 1) * ROWH) * (TD_WAVE * 4))
 	// what position p needs, into slot d (p clamped to the tile's positions: a slot past the end is filled but never used)
 #define TDS_FWD_FILL(d, p_raw) { \
 		const int p_ = ((p_raw) <= pmax) ? (p_raw) : pmax; \
 		c_q[d] = codes[p_ * TD_WAVE + w.lane]; \
-		Pi_q[d] = p_init ? NEG_INF : ldfs(&P[p_ * TD_WAVE + w.lane]); \
-		if (!first) cs_q[d] = ldfs(&Cs[p_ * TD_WAVE + w.lane]); \
+		Pi_q[d] = p_init ? NEG_INF : P[p_ * TD_WAVE + w.lane]; \
+		if (!first) cs_q[d] = Cs[p_ * TD_WAVE + w.lane]; \
 		if (pure) pb_q[d] = PBR(p_ + 1); \
 		if (own_sum && !first) { bm_q[d] = w.bm[p_ * TD_WAVE + w.lane]; ba_q[d] = w.ba[p_ * TD_WAVE + w.lane]; } \
 		const bool rows_ = !((J >= kSfxFirst) && p_ < w.sstop);   /* wave-uniform: below sstop the rows were not computed */ \
@@ -1635,21 +1336,13 @@ _Pragma("unroll") \
 		int ba = ba_q[d_];
 		f32x4 cb[NF][NQ + 1];
 		f32x2 ct[NF];
-		// a position whose rows were not stored (ckpt_skipped) loads the rows of position i+1 instead and steps back
-		const bool ck = ckpt_skipped(w, i);
-		const int brow = ck ? i : i - 1;
-		float pb1 = 0.0f, pb2 = 0.0f;   // P_backward_next[i+1], [i+2] for the recomputation
-		if (ck) {
-			pb1 = PBR(i + 1);
-			if (pure) pb2 = PBR(i + 2);
-		}
 		// trailing pruned segment below sstop: every posterior there is exactly zero, the backward rows were not even computed
 		const bool sfx_skip = (J >= kSfxFirst) && i < w.sstop;   // wave-uniform
 		float ik[NF];     // I_backward[K-1] at position i and (ik_n) at position i+1
 #pragma unroll
 		for (int f = 0; f < NF; f++) {
 			if constexpr (PD == 1) {
-				const uint8_t* bw = BW + ((int64_t)kBwOff[kHmmOff[J] + f0 + f] * w.lmax + (int64_t)TDS_SPILL_POS(brow) * ROWH) * (TD_WAVE * 4);
+				const uint8_t* bw = BW + ((int64_t)kBwOff[kHmmOff[J] + f0 + f] * w.lmax + (int64_t)(i - 1) * ROWH) * (TD_WAVE * 4);
 				if (!sfx_skip) {
 #pragma unroll
 					for (int p = 0; p < NQ; p++) cb[f][p] = ld4(bw + p * (TD_WAVE * 16), w.lane);
@@ -1750,14 +1443,8 @@ _Pragma("unroll") \
 					MB[g] = Mr.v; IB[g] = ik[f];
 				}
 				if (pure) {
-					MB[K] = (ck ? pb2 : pb) + kCols[col0 + K].t[7];
-					IB[K] = (ck ? pb2 : pb) + kCols[col0 + K].t[8];
-				}
-				if (ck) {   // MB / IB hold the rows of position i+1: one backward step gives those of position i
-					SV Mr[NC], Ir[NC];
-					bwd_row<J, RT>(f0 + f, MB, IB, pb1, mk_mask(c_n), c_n, kc, c, Mr, Ir);
-#pragma unroll
-					for (int g = 0; g < NC; g++) { MB[g] = Mr[g].v; IB[g] = Ir[g].v; }
+					MB[K] = pb + kCols[col0 + K].t[7];
+					IB[K] = pb + kCols[col0 + K].t[8];
 				}
 				// total_prob is only read for segments with several HMMs (:4354-4429)
 				constexpr bool want_tt = kNHmm[J] > 1;
@@ -1777,13 +1464,13 @@ _Pragma("unroll") \
 				} else if (kMaskDP) {
 					lpost[f] = acc.v;   // stored (or skipped) below, in uniform control flow
 				} else {
-					stf(&DP[((int64_t)(i - 1) * TD_H + h) * TD_WAVE + w.lane], post_prob(acc.v));
+					DP[((int64_t)(i - 1) * TD_H + h) * TD_WAVE + w.lane] = post_prob(acc.v);
 				}
 				}
 #pragma unroll
 				for (int g = 0; g < NC; g++) { Mp[f][g] = Mc[g].v; Ip[f][g] = Ic[g].v; }
 			}
-			if (want_cs) stfs(&Cs[i * TD_WAVE + w.lane], cs.v);
+			if (want_cs) Cs[i * TD_WAVE + w.lane] = cs.v;
 			if (own_sum) { w.bm[i * TD_WAVE + w.lane] = bm; w.ba[i * TD_WAVE + w.lane] = (uint8_t)ba; }
 		}
 		if (kMaskDP && !own_sum) {   // in uniform control flow: the bits are the same in every lane
@@ -1794,12 +1481,8 @@ _Pragma("unroll") \
 				const bool any_on = __builtin_amdgcn_ballot_w64(on) != 0;
 				if (any_on) {
 					float pp = 0.0f;
-#ifdef TDS_FAKE_EXP
-					if (on) pp = __expf(lpost[f]);   // diagnostic only (results differ): what the double-precision exp costs this loop
-#else
 					if (on) pp = (float)exp((double)lpost[f]);
-#endif
-					if (i <= w.len) stf(&DP[((int64_t)(i - 1) * TD_H + kHmmOff[J] + f0 + f) * TD_WAVE + w.lane], pp);
+					if (i <= w.len) DP[((int64_t)(i - 1) * TD_H + kHmmOff[J] + f0 + f) * TD_WAVE + w.lane] = pp;
 				}
 				mbits[f] |= (any_on ? 1u : 0u) << ((i - 1) & 31);
 				if ((((i - 1) & 31) == 31) || i == iend) {
@@ -1858,11 +1541,7 @@ DEV void fwd_groups(const Wv& w, const uint8_t* __restrict__ codes, const float*
 	if constexpr (TDS_RESTART && F0 == 0 && J >= kSfxFirst) {
 		if (w.rf_on) {
 			const int q_hi = w.sstop - (TD_S - 1 - J) * (w.rWf + 1);
-#if TDS_STAIR
 			fwd_stair<J>(w, codes, P, q_hi - w.rWf, q_hi);
-#else
-			fwd_restart<J>(w, codes, P, q_hi - w.rWf, q_hi);
-#endif
 		}
 	}
 	if constexpr (F0 == 0 && kRt[J] > 0) {
@@ -1933,9 +1612,6 @@ DEV int prune_scan(const float thr, const int len, const int tmax, const float* 
 	return __builtin_amdgcn_readfirstlane(cl);
 }
 
-#ifndef TDS_CUT_REFINE
-#define TDS_CUT_REFINE 1
-#endif
 // max over the leading segments of the relative backward bound at position i: every backward value of theirs at i is at most
 // max_k (gq_J[k] + Q[i + 1 + k]) + log(len - i + 1) + 0.02 (tests/test_prune.py::test_restart_bounds_dominate_reference_values)
 DEV float leading_bwd_bound(const Wv& w, const int i)
@@ -2067,7 +1743,7 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 	w.rs = (float*)(w.slot + lay.rs);
 	w.hb = SB + (int64_t)TD_S * rowlen;   // (row S of the silent_backward block: previous_silent, formed in registers -- free)
 	w.rW = TDS_RESTART_W;
-	w.rWf = TDS_STAIR ? fwd_window_all() : TDS_RESTART_W;
+	w.rWf = fwd_window_all();
 	w.stats = ka.counters;
 	w.tprof = &tprof;
 	w.bwt = ka.prune + 1 * (int64_t)ka.prune_stride;
@@ -2079,15 +1755,11 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 	// length ascending).  The waves do not run at one speed -- on the boxes measured the waves of four of the eight XCDs take
 	// ~10 % longer for the same tiles (tools/endstats.py) -- so a static share per wave leaves the fast ones idle at the end.
 	auto next_tile = [&](void) -> int {
-#if TDS_DYNAMIC
 		int t = 0;
 		if (lane == 0) t = atomicAdd(ka.tile_next, 1);
 		return ka.n_tiles - 1 - ka.n_slots - __builtin_amdgcn_readfirstlane(t);
-#else
-		return 0;
-#endif
 	};
-	for (int tile = TDS_DYNAMIC ? ka.n_tiles - 1 - slot : slot; TDS_DYNAMIC ? tile >= 0 : tile < ka.n_tiles; tile = TDS_DYNAMIC ? next_tile() : tile + ka.n_slots) {
+	for (int tile = ka.n_tiles - 1 - slot; tile >= 0; tile = next_tile()) {
 		const int64_t rid = (int64_t)tile * TD_WAVE + lane;
 		// -start / -end (td_set_window): the DP phases see bases [woff, woff + len) of every read (do_label_thread /
 		// do_probability_estimation decode seq + matchstart for matchend - matchstart bases, barcode_hmm.c:2290-2296), the
@@ -2201,7 +1873,7 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 				// and so the wave's following tiles (reads rich in N close late: 19.5 positions at 20 % N against 12.9)
 				// (a staircase bridge that ran out of positions gets a wider window first -- for this tile and the wave's following ones)
 				if (open) {
-					if (TDS_STAIR && w.rW + 8 <= TDS_RESTART_WMAX) w.rW += 8; else restart_on = false;
+					if (w.rW + 8 <= TDS_RESTART_WMAX) w.rW += 8; else restart_on = false;
 					continue;
 				}
 			}
@@ -2235,7 +1907,7 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 				// front of the first unpruned segment exists -- it was swept densely -- the bound relative to it (the restarted sweeps'
 				// impulse responses, td_jit.hip) is tighter by what this read loses behind the leading segments: the cut moves down
 				// while no lane has a state that can still be above the zero bound under the smaller of the two.
-				if (TDS_CUT_REFINE && kPruneSegs <= 4 && !any_dead && cq + 1 < tmax) cq = refine_cut(w, cq, b_use - kPruneZ, ka.prune, ka.prune + ka.prune_stride);
+				if (kPruneSegs <= 4 && !any_dead && cq + 1 < tmax) cq = refine_cut(w, cq, b_use - kPruneZ, ka.prune, ka.prune + ka.prune_stride);
 				if (TDS_PRUNE_STATS && lane == 0) {
 					atomicAdd(&ka.counters[TDS_DIAG(232)], 1ull);
 					atomicAdd(&ka.counters[TDS_DIAG(233)], (unsigned long long)cq);
@@ -2272,7 +1944,7 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 						// run again from position 1 (it rewrites every row and mask word it owns), the rest of the tile stands.  The
 						// wave's next tiles get a wider window, and after two such failures none.
 						if (TDS_PRUNE_STATS && lane == 0) atomicAdd(&ka.counters[TDS_DIAG(199)], 1ull);
-						if (TDS_STAIR && n_fwd_fail == 0 && w.rWf + 12 <= 96) w.rWf += 12; else restart_fwd_on = false;
+						if (n_fwd_fail == 0 && w.rWf + 12 <= 96) w.rWf += 12; else restart_fwd_on = false;
 						n_fwd_fail++;
 						w.rf_on = false;
 						w.bad &= ~32;
@@ -2452,7 +2124,7 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 #pragma unroll
 					for (int v = 0; v < HL; v++) {
 						if (with_lead || !label_leading(F1 + v)) {
-							dq[d][v] = ldf(&dpn[v * TD_WAVE]);
+							dq[d][v] = dpn[v * TD_WAVE];
 							bits |= ((mw[v] >> (nb & 31)) & 1u) << v;
 						} else {
 							dq[d][v] = 0.0f;
@@ -2640,7 +2312,7 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 								for (int k = 0; k < CH; k++) {
 									const bool in = v + k < v1;
 									self[k] = in ? a0[(v + k) * TD_WAVE] : 0.0f;
-									dpv[k] = in ? ldf(&dpi[(v + k) * TD_WAVE]) : 0.0f;
+									dpv[k] = in ? dpi[(v + k) * TD_WAVE] : 0.0f;
 								}
 	#pragma unroll
 								for (int k = 0; k < CH; k++) {
@@ -2907,14 +2579,7 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 			// Outcome counters (the controller's serial counting, barcode_hmm.c:354-384): one atomic per wave and distinct value,
 			// not one per read.  A million reads adding 1 to the same two or three words is a million atomics queued on one L2
 			// channel -- they return nothing, so no phase of the wave clock shows them, but every memory operation of the
-			// machine waits behind them: 4 ms of an 18.5 ms launch on config 3, 8.4 of 13.2 on config 2 (TDS_COUNT_PER_READ=1
-			// brings them back for the A/B).
-#if TDS_COUNT_PER_READ
-			if (lenF >= 1) {
-				atomicAdd(&ka.counters[read_type & (N_OUTCOME_SLOTS - 1)], 1ull);
-				if (read_type == OUT_SUCCESS && barcode >= 0) atomicAdd(&ka.counters[N_OUTCOME_SLOTS + (barcode & 0xFF)], 1ull);
-			}
-#else
+			// machine waits behind them: 4 ms of an 18.5 ms launch on config 3, 8.4 of 13.2 on config 2.
 			const int key1 = (lenF >= 1) ? (read_type & (N_OUTCOME_SLOTS - 1)) : -1;
 			const int key2 = (lenF >= 1 && read_type == OUT_SUCCESS && barcode >= 0) ? N_OUTCOME_SLOTS + (barcode & 0xFF) : -1;
 #pragma unroll
@@ -2929,7 +2594,6 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 					todo &= ~same;
 				}
 			}
-#endif
 		}
 		TDS_PHASE(9);   // outputs
 	}

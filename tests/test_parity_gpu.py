@@ -468,7 +468,7 @@ def test_logsum_selfcheck_falls_back_to_clamped_form(monkeypatch, capfd):
     message, and the results stay bit-exact.  The failure is forced through TD_SPEC_SELFCHECK_FAIL."""
     from tagdust_amd import TagdustHip
     g = load_golden("c2_b4_r")
-    monkeypatch.setenv("TD_SPEC_NT", "0")               # a source variant of its own: not served from the in-memory cache
+    monkeypatch.setenv("TD_SPEC_EXTRA_OPTS", "-DTD_TEST_UNIQUE_KEY=1")   # a cache key of its own: not served from the in-memory cache
     monkeypatch.setenv("TD_SPEC_SELFCHECK_FAIL", "1")
     c = TagdustHip(0)
     try:
@@ -581,8 +581,8 @@ def test_disk_cache_of_compiled_kernels(tmp_path, monkeypatch):
     from tagdust_amd import TagdustHip
     g = load_golden("umi_f_s_r")
     monkeypatch.setenv("TD_SPEC_CACHE_DIR", str(tmp_path))
-    monkeypatch.setenv("TD_SPEC_NT", "0")                  # a source variant no other test compiled: not in the
-    monkeypatch.setenv("TD_SPEC_PAIR", "0")                # in-memory cache of this process
+    monkeypatch.setenv("TD_SPEC_EXTRA_OPTS", "-DTD_TEST_UNIQUE_KEY=2")   # a cache key no other test compiled: not in the
+                                                                          # in-memory cache of this process
     c = TagdustHip(0)
     try:
         c.set_option("specialize", 1)

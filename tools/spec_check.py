@@ -22,13 +22,8 @@ def check(name="c3_b6_s_r_p", keep=False, outdir="/tmp/td_spec"):
     open(path, "w").write(src)
     t0 = time.time()
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-           "--cuda-device-only", "-c", path, "-o", os.path.join(outdir, name + ".o"), "-Rpass-analysis=kernel-resource-usage"]
-    if os.environ.get("TD_SPEC_SLP", "0") == "0":
-        cmd += ["-fno-slp-vectorize"]      # as td_jit.hip compiles it
-    if os.environ.get("TD_SPEC_MLICM", "0") == "0":
-        cmd += ["-mllvm", "-disable-machine-licm"]
-    if os.environ.get("TD_SPEC_SCHED", "default") not in ("", "default"):
-        cmd += ["-mllvm", "-amdgpu-sched-strategy=" + os.environ["TD_SPEC_SCHED"]]
+           "--cuda-device-only", "-c", path, "-o", os.path.join(outdir, name + ".o"), "-Rpass-analysis=kernel-resource-usage",
+           "-fno-slp-vectorize", "-mllvm", "-disable-machine-licm"]      # as td_jit.hip compiles it
     cmd += os.environ.get("TD_SPEC_EXTRA_OPTS", "").split()
     if keep:
         cmd += ["-save-temps=obj"]
