@@ -44,6 +44,13 @@ extern "C" {
 #define TD_MODE_GET_LABEL 1   /* label + Q + extraction (+ DUST)           do_label_thread            */
 #define TD_MODE_GET_PROB  4   /* Q only (threshold calibration)            do_probability_estimation  */
 #define TD_MODE_ARCH_COMP 5   /* backward() only: b_score per read         do_arch_comparison         */
+/* not a mode of the reference's run_pHMM: what its controller runs instead of the HMM for a file whose architecture is one read
+ * segment ("R:N"), run_rna_dust (src/barcode_hmm.c:313-325, do_rna_dust :2370-2395).  No model: every read gets read_type
+ * EXTRACT_SUCCESS, then -ref's match_to_reference on the read as it was read (td_set_artifacts, thread ranges as in
+ * TD_MODE_GET_LABEL), then dust_sequences with the `dust` of td_set_params, which overwrites the outcome with LOW_COMPLEXITY.
+ * The record is what read_fasta_fastq leaves (scores 0, mapq -1, barcode -1, fingerprint -1) with that read_type; seq_out gets
+ * the codes back unchanged (0..4); labels must be NULL.  td_set_window does not apply. */
+#define TD_MODE_RNA_DUST  6
 
 /* extraction outcomes, src/io.h:40-46 */
 #define TD_EXTRACT_SUCCESS                    0
@@ -134,7 +141,7 @@ int td_set_option(td_ctx* ctx, const char* name, int32_t value);
  * for models without a read segment behind a bounded prefix, for reads beyond 8192 bases, before the first batch) and
  * "overlap_active" (1 when pipelined batches really alternate between two compute streams and workspaces; 0 when the option
  * is off, the pipeline is one deep, the generic kernel runs, or HBM could not hold the second workspace);
- * "artifacts_active" (1 while a -ref artifact filter is set, td_set_artifacts); "length_classes" (the number of wave slots
+ * "artifacts_active" (1 while a -ref artifact filter is set, td_set_artifacts); "dust" (param->dust as td_set_params set it); "length_classes" (the number of wave slots
  * that were laid out for the last batch's longest read while the others kept the geometry of the reads at the 99 % mark --
  * a batch with a few very long reads among many short ones; 0: one geometry);
  * "hw_queues" (hardware queues of the HIP runtime as far as the library can tell: the user's GPU_MAX_HW_QUEUES, else the 8 the
@@ -156,7 +163,7 @@ int td_spec_prune_info(const td_model_desc* model, int32_t lcap, float* tab, flo
  * its far sweeps (big leading segments; TD_SPEC_RESTART=0 / 1 forces it).  No GPU needed; for inspection and tests. */
 int td_spec_restart_info(const td_model_desc* model, int32_t lcap, float* tab, int32_t* restart);
 /* -ref artifact filter, match_to_reference() src/barcode_hmm.c:2478-2583 (runs between extraction and DUST in
- * TD_MODE_GET_LABEL): string / s_index[n_seq+1] are struct fasta's fields as read_fasta() leaves them (io.c:1912-2001:
+ * TD_MODE_GET_LABEL, before DUST in TD_MODE_RNA_DUST): string / s_index[n_seq+1] are struct fasta's fields as read_fasta() leaves them (io.c:1912-2001:
  * per sequence one 'X' byte followed by the base codes); filter_error = param->filter_error (-fe);
  * n_threads = param->num_threads -- the reference pairs reads in fours from the start of each thread's range and
  * scores the up-to-3 left-over reads of a range with a different routine, which is reproduced.  A matching read gets
@@ -188,8 +195,10 @@ int td_batch_upload(td_ctx* ctx, const uint8_t* codes, const int64_t* offs, int6
 /* Same from ASCII FASTQ sequence lines (applies the nuc_code mapping). */
 int td_batch_upload_ascii(td_ctx* ctx, const char* bases, const int64_t* offs, int64_t n_reads);
 /* Run the hot path over the resident batch on the context's stream (asynchronous; td_sync / td_batch_download
- * wait).  mode = TD_MODE_GET_LABEL, TD_MODE_GET_PROB or TD_MODE_ARCH_COMP (only td_read_result.b_score is then
- * meaningful).  TD_MODE_GET_LABEL adds this batch's outcomes to the counters. */
+ * wait).  mode = TD_MODE_GET_LABEL, TD_MODE_GET_PROB, TD_MODE_ARCH_COMP (only td_read_result.b_score is then
+ * meaningful) or TD_MODE_RNA_DUST.  TD_MODE_GET_LABEL and TD_MODE_RNA_DUST add this batch's outcomes to the counters.
+ * TD_MODE_RNA_DUST needs no model; td_batch_upload still does (it sizes the decode workspace), so without one the batch goes
+ * through td_submit. */
 int td_run(td_ctx* ctx, int mode);
 int td_sync(td_ctx* ctx);
 /* Copy results of the resident batch back.  Any pointer may be NULL.
@@ -206,6 +215,7 @@ int td_batch_download(td_ctx* ctx, td_read_result* res, int8_t* labels, uint8_t*
  * res / labels / seq_out as in td_batch_download (any may be NULL); they are complete after td_wait(ticket).  offs[0]
  * need not be 0: read i is bases[offs[i] .. offs[i+1]) and output positions count from offs[0] (seq_out + offs[i] - offs[0],
  * labels + offs[i] - offs[0] + i), so a contiguous range of a larger batch can be handed over with its own offsets.
+ * TD_MODE_RNA_DUST needs no model and no labels buffer (labels must be NULL).
  * At most "pipeline_depth" tickets may be outstanding (TD_FAIL beyond that).  Page-locked buffers (td_host_alloc, or
  * registered with hipHostRegister) are read and written by the DMA engines directly -- td_submit then waits for the upload
  * of `bases` before it returns, so the contract above holds for them too; any other host memory goes through

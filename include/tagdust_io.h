@@ -104,17 +104,25 @@ int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* arch, const c
  * 1000 names compared like compare_read_names(), io.c:2128-2393) -> each file's records through that file's own model --
  * run_pHMM's contiguous ranges (:1911-1922) over the n_devices contexts the caller holds for it, every range a td_submit /
  * td_wait on its device, results in input order -- or, for a file whose architecture is a single read segment, through
- * run_rna_dust (:315-319, :2370-2395: no HMM; DUST with `dust`, src/barcode_hmm.c:2407-2467) -> the per-record combination
+ * run_rna_dust (:315-319, :2370-2395: no HMM; with -ref match_to_reference, then DUST with `dust`, src/barcode_hmm.c:2407-2467)
+ * -> the per-record combination
  * (:329-351: the outcome is the maximum over the files, the barcode that of the one file that has a barcode segment) ->
  * print_all() (io.c:757-1016): every file that has read segments writes its records to its own "_READ<k>" files, named after the
  * barcode file's architecture, by the combined outcome and barcode.  The same three-stage pipeline as td_stream_run, one
  * reader / parser per input file.  counts (may be NULL) receives the controller's serial counting over the combined records
- * (TD_NUM_COUNTERS words: outcome slots, then per-barcode bins).  A -ref artifact filter is not supported here. */
+ * (TD_NUM_COUNTERS words: outcome slots, then per-barcode bins).
+ * -ref (the controller hands the one FASTA to every file's step, :209-214): set the filter (td_set_artifacts, the reference's
+ * -fe and -t) on every file's contexts; with N > 1 devices each range is submitted with td_set_batch_window, so that the
+ * filter's thread ranges are those of the whole batch, and the windows are reset to whole batches at the end.  A filter on some
+ * files' contexts but not on others', or an R:N file without contexts in such a run, fails.  batch_reads then defaults to the
+ * reference's 1 000 001 records (thread ranges, and with them batch boundaries, are part of the result). */
 typedef struct td_stream_file {
 	const char*    path;   /* one input file (plain, .gz, .bz2) */
 	const td_arch* arch;   /* its architecture: param->read_structures[i], barcode_hmm.c:105-137 */
 	td_ctx* const* ctx;    /* n_devices contexts holding this file's model, threshold, minlen and dust (one per device, in device
-	                          order); NULL for an architecture that is one read segment ("R:N"): that file is not decoded */
+	                          order).  A file whose architecture is one read segment ("R:N") is not decoded: with contexts (no
+	                          model needed; their dust must equal the call's `dust`) run_rna_dust runs on its devices
+	                          (TD_MODE_RNA_DUST), with NULL on the host (DUST only: no -ref filter there) */
 } td_stream_file;
 int td_stream_run_multi(const td_stream_file* files, int32_t n_files, int32_t n_devices, const char* out_prefix, int32_t dust,
                         const td_stream_opts* opts, td_stream_stats* stats, int64_t* counts /* [TD_NUM_COUNTERS] */);

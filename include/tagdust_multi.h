@@ -63,8 +63,9 @@ int  td_multi_set_params(td_multi* m, float threshold, int32_t minlen, int32_t d
 int  td_multi_set_window(td_multi* m, int32_t matchstart, int32_t matchend);   /* -start / -end on every device (td_set_window) */
 int  td_multi_set_artifacts(td_multi* m, const uint8_t* string, const int32_t* s_index, int32_t n_seq,
                             int32_t filter_error, int32_t n_threads);
-/* One run_pHMM call over all devices: reads [0, n) are split with td_shard_bounds, every device runs td_submit / td_wait
- * on its range, results arrive in input order (res / labels / seq_out as in td_batch_download; any may be NULL).
+/* One run_pHMM call over all devices (or one run_rna_dust call: mode TD_MODE_RNA_DUST, labels NULL): reads [0, n) are split
+ * with td_shard_bounds, every device runs td_submit / td_wait on its range, results arrive in input order (res / labels /
+ * seq_out as in td_batch_download; any may be NULL).
  * Per-read results are identical to a single context's: the artifact filter's thread ranges are taken over the whole
  * batch, not over a device's share. */
 int  td_multi_decode(td_multi* m, const void* bases, int32_t is_ascii, const int64_t* offs, int64_t n_reads, int mode,

@@ -27,6 +27,7 @@
 #include "td_jit.h"
 #include "td_stage.h"
 #include "td_host_inner.h"
+#include "td_rnadust.h"
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t td_launch_decode(const TdKernelArgs* ka, hipStream_t stream);   // library-internal
 extern "C" __attribute__((visibility("hidden"))) int td_kernel_block_threads(void);
@@ -221,6 +222,7 @@ struct td_ctx {
 
 	// -ref artifact filter
 	uint8_t* d_art_text = nullptr; int32_t* d_art_index = nullptr;
+	uint32_t* d_art_pk = nullptr; int32_t* d_art_seq = nullptr;   // the same text as 2-bit codes for TD_MODE_RNA_DUST (td_rnadust.hip)
 	int32_t art_n = 0, art_fe = 0, art_threads = 1;
 	int64_t win_first = 0, win_total = 0;   // td_set_batch_window
 	int32_t match_start = 0, match_len = 0;  // td_set_window (-start / -end); match_len = 0: whole reads
@@ -393,7 +395,7 @@ extern "C" void td_ctx_destroy(td_ctx* c)
 	if (c->s_up) (void)hipStreamSynchronize(c->s_up);
 	if (c->s_down) (void)hipStreamSynchronize(c->s_down);
 	void* bufs[] = { c->d_hdr, c->d_cols, c->d_hinfo, c->d_pred_off, c->d_pred_idx, c->d_logsum, c->d_counters,
-	                 c->d_ws, c->d_art_text, c->d_art_index, c->d_prune, c->d_tile_next, c->d_ws2, c->d_tile_next2 };
+	                 c->d_ws, c->d_art_text, c->d_art_index, c->d_art_pk, c->d_art_seq, c->d_prune, c->d_tile_next, c->d_ws2, c->d_tile_next2 };
 	for (void* p : bufs) if (p) (void)hipFree(p);
 	for (int k = 0; k < TD_MAX_PIPELINE; k++) slot_release(c->slots[k]);
 	if (c->ev_origin) (void)hipEventDestroy(c->ev_origin);
@@ -684,6 +686,7 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	if (!strcmp(name, "pipeline_depth")) { *value = c->pipeline_depth; return TD_OK; }
 	if (!strcmp(name, "host_threads")) { *value = c->host_threads; return TD_OK; }
 	if (!strcmp(name, "artifacts_active")) { *value = c->art_n > 0; return TD_OK; }
+	if (!strcmp(name, "dust")) { *value = c->dust; return TD_OK; }   // param->dust as td_set_params set it
 	if (!strcmp(name, "length_classes")) { *value = c->slots[c->last_slot].n_big; return TD_OK; }   // wave slots of the long geometry in the last batch
 	if (!strcmp(name, "overlap_decode")) { *value = c->overlap; return TD_OK; }
 	if (!strcmp(name, "compact_egress")) { *value = c->compact_egress; return TD_OK; }
@@ -715,6 +718,8 @@ extern "C" int td_set_artifacts(td_ctx* c, const uint8_t* string, const int32_t*
 	HIPCHK(c, hipSetDevice(c->device));
 	if (c->d_art_text) { HIPCHK(c, hipFree(c->d_art_text)); c->d_art_text = nullptr; }
 	if (c->d_art_index) { HIPCHK(c, hipFree(c->d_art_index)); c->d_art_index = nullptr; }
+	if (c->d_art_pk) { HIPCHK(c, hipFree(c->d_art_pk)); c->d_art_pk = nullptr; }
+	if (c->d_art_seq) { HIPCHK(c, hipFree(c->d_art_seq)); c->d_art_seq = nullptr; }
 	c->art_n = 0;
 	if (n_seq <= 0) return TD_OK;
 	if (!string || !s_index) return fail(c, "td_set_artifacts: null argument");
@@ -726,6 +731,23 @@ extern "C" int td_set_artifacts(td_ctx* c, const uint8_t* string, const int32_t*
 	HIPCHK(c, hipMalloc((void**)&c->d_art_index, sizeof(int32_t) * ((size_t)n_seq + 1)));
 	if (bytes) HIPCHK(c, hipMemcpy(c->d_art_text, string, bytes, hipMemcpyHostToDevice));
 	HIPCHK(c, hipMemcpy(c->d_art_index, s_index, sizeof(int32_t) * ((size_t)n_seq + 1), hipMemcpyHostToDevice));
+	// TD_MODE_RNA_DUST reads the text as 2-bit codes (only the low two bits are looked at; the leading 'X' is 'X' & 3 = 0),
+	// 16 per dword, every sequence from a dword boundary: one wave-uniform load per 16 characters
+	std::vector<int32_t> seq((size_t)n_seq * 2);
+	size_t words = 0;
+	for (int32_t j = 0; j < n_seq; j++) {
+		seq[(size_t)j * 2] = (int32_t)words;
+		seq[(size_t)j * 2 + 1] = s_index[j + 1] - s_index[j];
+		words += (size_t)(s_index[j + 1] - s_index[j] + 15) / 16;
+	}
+	std::vector<uint32_t> pk(words + 1, 0u);
+	for (int32_t j = 0; j < n_seq; j++)
+		for (int32_t q = 0; q < seq[(size_t)j * 2 + 1]; q++)
+			pk[(size_t)seq[(size_t)j * 2] + (size_t)(q >> 4)] |= (uint32_t)(string[s_index[j] + q] & 3u) << (2 * (q & 15));
+	HIPCHK(c, hipMalloc((void**)&c->d_art_pk, pk.size() * 4));
+	HIPCHK(c, hipMalloc((void**)&c->d_art_seq, seq.size() * 4));
+	HIPCHK(c, hipMemcpy(c->d_art_pk, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
+	HIPCHK(c, hipMemcpy(c->d_art_seq, seq.data(), seq.size() * 4, hipMemcpyHostToDevice));
 	c->art_n = n_seq; c->art_fe = filter_error; c->art_threads = n_threads;
 	return TD_OK;
 }
@@ -1080,11 +1102,15 @@ static int rle_capacity(const td_ctx* c)
 }
 
 // the decode kernel over a staged slot
+static int slot_rna_dust(td_ctx* c, TdSlot& s);
+
 static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 {
+	if (mode == TD_MODE_RNA_DUST) return slot_rna_dust(c, s);
 	if (!c->have_model) return fail(c, "td_run: no model uploaded");
 	if (mode != TD_MODE_GET_LABEL && mode != TD_MODE_GET_PROB && mode != TD_MODE_ARCH_COMP) return fail(c, "td_run: unsupported mode %d", mode);
 	if (!s.staged) return fail(c, "td_run: no batch resident (td_batch_upload failed or was not called)");
+	if (s.n_tiles > 0 && s.n_wave_slots == 0) return fail(c, "td_run: the resident batch was staged for TD_MODE_RNA_DUST, without a decode workspace (upload it again)");
 	HIPCHK(c, hipSetDevice(c->device));
 	s.reset_decoded();   // (runs_cap above all: a launch of the generic kernel, or an empty batch, must not hand the label runs of this
 	                     // slot's previous launch to the finish kernel)
@@ -1166,6 +1192,42 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	return TD_OK;
 }
 
+// run_rna_dust over a staged slot (TD_MODE_RNA_DUST, td_rnadust.hip): no model, no workspace.  The outputs take the decode
+// kernels' place, so that the finish kernel and the downloads are the same.
+static int slot_rna_dust(td_ctx* c, TdSlot& s)
+{
+	if (!s.staged) return fail(c, "td_run: no batch resident (td_batch_upload failed or was not called)");
+	HIPCHK(c, hipSetDevice(c->device));
+	s.reset_decoded();
+	s.mode = TD_MODE_RNA_DUST;
+	if (s.n_tiles == 0) { s.ran = true; s.last_ms = 0.0f; return TD_OK; }
+	const OutLayout ol = out_layout(s.n_tiles, s.lmax, s.nw1);
+	TdRnaDustArgs ra{};
+	ra.packed = s.d_packed; ra.lens = s.d_lens; ra.n_tiles = s.n_tiles; ra.nw2 = s.nw2; ra.nw1 = s.nw1;
+	ra.raw = s.d_raw; ra.offs = s.d_offs; ra.read_at = s.sorted ? s.d_read_at : nullptr; ra.n_reads = s.n_reads; ra.is_ascii = s.is_ascii;
+	ra.dust = c->dust;
+	if (c->art_n > 0) {
+		s.sb.art_threads = c->art_threads;
+		s.sb.art_first = c->win_first; s.sb.art_total = c->win_total;
+		HIPCHK(c, td_stage_art_left(s.sb, s.cs));
+		ra.art_pk = c->d_art_pk; ra.art_seq = c->d_art_seq; ra.art_left = s.d_art_left;
+		ra.art_n = c->art_n; ra.art_fe = c->art_fe;
+	}
+	float* soa = (float*)s.d_out;
+	const int64_t st = ol.soa_stride / 4;
+	ra.out_f = soa; ra.out_b = soa + st; ra.out_r = soa + 2 * st; ra.out_bar = soa + 3 * st; ra.out_q = soa + 4 * st;
+	ra.out_type = (int32_t*)(soa + 5 * st); ra.out_barcode = (int32_t*)(soa + 6 * st); ra.out_finger = (int32_t*)(soa + 7 * st);
+	ra.out_keep = (uint32_t*)(s.d_out + ol.keep);
+	ra.counters = c->d_counters;
+	HIPCHK(c, hipEventRecord(s.ev_k0, s.cs));
+	HIPCHK(c, td_launch_rna_dust(ra, s.cs));
+	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
+	s.ran = true;
+	s.last_ms = -1.0f;
+	c->last_slot = (int)(&s - c->slots);
+	return TD_OK;
+}
+
 // Results into the caller's order on the device (finish kernel on the compute stream), then device -> host.  A page-locked
 // destination is written by the DMA engine directly; anything else is reached through pinned staging and copied out by
 // slot_fetch_end.  The synchronous calls queue the copies behind the finish kernel on the compute stream.  The pipelined
@@ -1198,6 +1260,7 @@ static int slot_issue_copies(td_ctx* c, TdSlot& s, hipStream_t down)
 static int slot_fetch_begin(td_ctx* c, TdSlot& s, td_read_result* res, int8_t* labels, uint8_t* seq_out, bool deferred)
 {
 	if (!s.ran) return fail(c, "td_batch_download: td_run has not been called on this batch");
+	if (s.mode == TD_MODE_RNA_DUST && labels) return fail(c, "td_batch_download: TD_MODE_RNA_DUST has no labels (pass NULL)");
 	s.reset_fetch();
 	s.u_res = res; s.u_labels = labels; s.u_seq = seq_out;
 	s.copies_deferred = deferred;
@@ -1324,7 +1387,7 @@ extern "C" int td_batch_upload_ascii(td_ctx* c, const char* bases, const int64_t
 extern "C" int td_run(td_ctx* c, int mode)
 {
 	if (!c) return TD_FAIL;
-	if (!c->have_model) return fail(c, "td_run: no model uploaded");
+	if (!c->have_model && mode != TD_MODE_RNA_DUST) return fail(c, "td_run: no model uploaded");
 	return slot_decode(c, c->slots[0], mode);
 }
 
@@ -1366,6 +1429,7 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 		if (!c->slots[cand].ticket) { k = cand; break; }
 	}
 	if (k < 0) return fail(c, "td_submit: all %d pipeline slots hold batches that have not been waited for", c->pipeline_depth);
+	if (mode == TD_MODE_RNA_DUST && labels) return fail(c, "td_submit: TD_MODE_RNA_DUST has no labels (pass NULL)");
 	TdSlot& s = c->slots[k];
 	TdRoute rt;
 	rt.cs = c->stream; rt.wsi = 0; rt.aux = c->stream; rt.fin = c->stream; rt.pipelined = true;
@@ -1375,7 +1439,7 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 		c->submit_parity ^= 1;
 		rt.aux = c->s_aux; rt.fin = c->s_fin;
 	}
-	if (slot_stage(c, s, rt, bases, is_ascii != 0, offs, n_reads, c->s_up) != TD_OK) return TD_FAIL;
+	if (slot_stage(c, s, rt, bases, is_ascii != 0, offs, n_reads, c->s_up, mode != TD_MODE_RNA_DUST) != TD_OK) return TD_FAIL;
 	if (slot_decode(c, s, mode, labels != nullptr) != TD_OK) return TD_FAIL;
 	if (slot_fetch_begin(c, s, res, labels, seq_out, true) != TD_OK) return TD_FAIL;
 	// "returns once the reads have left the caller's buffers": a page-locked source is read by the DMA engine itself, so wait

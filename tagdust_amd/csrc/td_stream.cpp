@@ -576,6 +576,7 @@ struct Pipeline {
 	std::vector<int64_t> file_off;
 	int num_alternatives = 2;
 	bool dry = false;
+	bool want_seq = true;      // page-locked room for rewritten sequences (not for a file that goes through TD_MODE_RNA_DUST)
 	uint64_t fnv = 1469598103934665603ULL;
 	double dbg_pass1 = 0, dbg_grow = 0, dbg_encode = 0, dbg_format = 0, dbg_pwrite = 0;
 	size_t batch_hint = 0;
@@ -628,7 +629,7 @@ struct Pipeline {
 		for (int k = 0; k < n_more; k++) {
 			{ std::lock_guard<std::mutex> lk(all_mu); if (stop_alloc) return; }
 			Batch* b = new_batch();
-			if (!b || !grow_buf(dry, &b->codes, &b->cap_codes, hint, 0, hint) || !grow_buf(dry, &b->seq_out, &b->cap_seq, hint, 0, hint)) return;   // (the pipeline runs with what it has)
+			if (!b || !grow_buf(dry, &b->codes, &b->cap_codes, hint, 0, hint) || (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, hint, 0, hint))) return;   // (the pipeline runs with what it has)
 			if (!free_list->push(b)) return;
 		}
 	}
@@ -705,7 +706,7 @@ struct Pipeline {
 					for (const Job& j : jobs) if (j.b == b) { keep = (size_t)b->offs[b->pieces[j.piece].first]; mine = true; break; }
 					if (!mine) continue;
 					if (!grow_buf(dry, &b->codes, &b->cap_codes, (size_t)b->n_bases + 1, keep, batch_hint) ||
-					    !grow_buf(dry, &b->seq_out, &b->cap_seq, (size_t)b->n_bases + 1, 0, batch_hint)) { fail("td_stream_run: page-locked memory exhausted"); return false; }
+					    (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, (size_t)b->n_bases + 1, 0, batch_hint))) { fail("td_stream_run: page-locked memory exhausted"); return false; }
 				}
 				dbg_grow += now_s() - tf0;
 				const double tf1 = now_s();
@@ -1138,6 +1139,8 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 	// barcode_hmm.c:105-153: which file holds the barcode (at most one may), how many read segments every file contributes
 	int bar_file = -1, num_out_reads = 0;
 	std::vector<int> read_present((size_t)K, 0);
+	std::vector<char> rna((size_t)K, 0);          // run_rna_dust on the file's devices (TD_MODE_RNA_DUST)
+	int n_art = 0;
 	for (int k = 0; k < K; k++) {
 		const td_arch* a = files[k].arch;
 		if (!files[k].path || !a || a->n_segments < 1) { td_io_set_error("td_stream_run_multi: every input file needs a path and an architecture"); return TD_FAIL; }
@@ -1148,14 +1151,38 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 			bar_file = k;
 		}
 		num_out_reads += read_present[(size_t)k];
+		// run_rna_dust (barcode_hmm.c:315-319) is what the controller runs instead of the HMM for an architecture that is one read segment
+		const bool one_read = a->n_segments == 1 && a->type[0] == 'R';
 		if (!files[k].ctx) {
-			// run_rna_dust (barcode_hmm.c:315-319) is what the controller runs instead of the HMM for an architecture that is one read segment
-			if (!(a->n_segments == 1 && a->type[0] == 'R')) { td_io_set_error("td_stream_run_multi: a file without contexts must have the architecture R:N"); return TD_FAIL; }
+			if (!one_read) { td_io_set_error("td_stream_run_multi: a file without contexts must have the architecture R:N"); return TD_FAIL; }
 		} else {
 			for (int d = 0; d < N; d++) if (!files[k].ctx[d]) { td_io_set_error("td_stream_run_multi: NULL context"); return TD_FAIL; }
+			rna[(size_t)k] = one_read;
 			int32_t art = 0;
 			(void)td_get_option(files[k].ctx[0], "artifacts_active", &art);
-			if (art) { td_io_set_error("td_stream_run_multi: a -ref artifact filter is not supported here (its thread ranges belong to the reference's batches; use td_stream_run / td_multi_decode)"); return TD_FAIL; }
+			n_art += art != 0;
+			if (one_read) {   // the devices run the DUST of this call
+				int32_t cd = 0;
+				(void)td_get_option(files[k].ctx[0], "dust", &cd);
+				if (cd != dust) {
+					td_io_set_error(std::string("td_stream_run_multi: ") + files[k].path + " (R:N) has contexts with dust " + std::to_string(cd) +
+					                ", the call has dust " + std::to_string(dust));
+					return TD_FAIL;
+				}
+			}
+		}
+	}
+	// -ref (hmm_controller_multiple, barcode_hmm.c:209-214, :313-325): the controller hands the one FASTA to every file's step
+	if (n_art > 0) {
+		for (int k = 0; k < K; k++) {
+			if (!files[k].ctx) {
+				td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set, but ") + files[k].path +
+				                " (R:N) has no contexts: its reads must be filtered too (give it contexts: TD_MODE_RNA_DUST)");
+				return TD_FAIL;
+			}
+			int32_t art = 0;
+			(void)td_get_option(files[k].ctx[0], "artifacts_active", &art);
+			if (!art) { td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set for some files but not for ") + files[k].path); return TD_FAIL; }
 		}
 	}
 	if (num_out_reads == 0) { td_io_set_error("td_stream_run_multi: no read segment in any architecture: no output files to create (io.c:846-852)"); return TD_FAIL; }
@@ -1163,7 +1190,7 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 	const td_arch* print_arch = files[bar_file >= 0 ? bar_file : K - 1].arch;
 	td_stream_opts o{};
 	if (opts) o = *opts;
-	if (o.batch_reads <= 0) o.batch_reads = 1 << 18;
+	if (o.batch_reads <= 0) o.batch_reads = n_art > 0 ? 1000001 : (1 << 18);   // (the filter's thread ranges: as td_stream_run)
 	if (o.block_bytes <= 0) o.block_bytes = (int64_t)64 << 20;
 	if (o.block_bytes < 4096) o.block_bytes = 4096;
 	int hw = (int)std::thread::hardware_concurrency();
@@ -1200,6 +1227,7 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 	for (int k = 0; k < K && rc == TD_OK; k++) {
 		Pipeline& p = *pf[(size_t)k];
 		p.o = o; p.dry = files[k].ctx == nullptr;       // (a file that is not decoded needs no page-locked buffers)
+		p.want_seq = files[k].ctx != nullptr && !rna[(size_t)k];   // (nor one whose reads come back unchanged)
 		p.ready.reset(new Queue<Batch*>((size_t)n_batches));
 		p.done.reset(new Queue<Batch*>((size_t)n_batches));
 		p.free_list.reset(new Queue<Batch*>((size_t)n_batches));
@@ -1235,10 +1263,11 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 			const int64_t n = t->b[0]->n;
 			for (int k = 0; k < K; k++) {
 				Batch* b = t->b[(size_t)k];
-				if (files[k].ctx) { b->seq_src = nullptr; continue; }
+				if (files[k].ctx && !rna[(size_t)k]) { b->seq_src = nullptr; continue; }
 				b->seq_src = b->codes;
+				if (files[k].ctx) continue;             // (TD_MODE_RNA_DUST ran on the file's devices)
 				const int64_t chunk = 16384, nch = (n + chunk - 1) / chunk;
-				pw.write_pool->run(nch, [&](int64_t c) {   // do_rna_dust, barcode_hmm.c:2370-2395 (no -ref filter here)
+				pw.write_pool->run(nch, [&](int64_t c) {   // do_rna_dust, barcode_hmm.c:2370-2395 (no -ref filter: a run with one has contexts here)
 					for (int64_t i = c * chunk; i < std::min(n, (c + 1) * chunk); i++) {
 						td_read_result& r = b->res[i];
 						memset(&r, 0, sizeof r);
@@ -1332,8 +1361,15 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 			for (int d = 0; d < N && ok; d++) {      // run_pHMM's contiguous ranges over the devices (barcode_hmm.c:1911-1922)
 				const int64_t interval = n / N, lo = (int64_t)d * interval, hi = (d == N - 1) ? n : lo + interval;
 				if (hi <= lo) continue;
-				if (td_submit(files[k].ctx[d], b->codes, 0, b->offs + lo, hi - lo, TD_MODE_GET_LABEL, b->res + lo, nullptr, b->seq_out + b->offs[lo],
-				              &t->tickets[(size_t)k][(size_t)d]) != TD_OK) {
+				// the artifact filter's thread ranges are those of the whole batch, not of a device's range
+				if (N > 1 && td_set_batch_window(files[k].ctx[d], lo, n) != TD_OK) {
+					fail_all(std::string("td_stream_run_multi: ") + td_last_error(files[k].ctx[d]));
+					ok = false;
+					break;
+				}
+				const bool r = rna[(size_t)k] != 0;
+				if (td_submit(files[k].ctx[d], b->codes, 0, b->offs + lo, hi - lo, r ? TD_MODE_RNA_DUST : TD_MODE_GET_LABEL, b->res + lo, nullptr,
+				              r ? nullptr : b->seq_out + b->offs[lo], &t->tickets[(size_t)k][(size_t)d]) != TD_OK) {
 					fail_all(std::string("td_stream_run_multi: ") + td_last_error(files[k].ctx[d]));
 					ok = false;
 				}
@@ -1355,6 +1391,7 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 	done_t.close();
 	t_write.join();
 	pw.append_stop();
+	if (N > 1) for (int k = 0; k < K; k++) if (files[k].ctx) for (int d = 0; d < N; d++) (void)td_set_batch_window(files[k].ctx[d], 0, 0);
 	for (int k = 0; k < K; k++) {
 		Pipeline& p = *pf[(size_t)k];
 		if (pw.failed()) p.fail(pw.err);

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("TD_LIB_PATH", os.path.join(HERE, "libtagdust_hip.so")
 MODE_GET_LABEL = 1
 MODE_GET_PROB = 4
 MODE_ARCH_COMP = 5
+MODE_RNA_DUST = 6      # run_rna_dust: -ref filter + DUST on reads as they were read; needs no model, no labels
 NUM_OUTCOME_SLOTS = 8
 NUM_BARCODE_BINS = 256
 NUM_COUNTERS = NUM_OUTCOME_SLOTS + NUM_BARCODE_BINS
@@ -456,8 +457,11 @@ class _StreamFile(C.Structure):
 
 def stream_run_multi(files, out_prefix, n_devices=1, dust=100, batch_reads=0, n_threads=0, block_bytes=0):
     """td_stream_run_multi: the input files of one paired / multi-read run in lock-step.  files: a list of
-    (path, segments, contexts) -- contexts = one TagdustHip per device holding that file's model and parameters, or None for a
-    file whose architecture is a single read segment (not decoded: run_rna_dust).  Returns (statistics dict, counters int64[264])."""
+    (path, segments, contexts) -- contexts = one TagdustHip per device holding that file's model and parameters.  A file whose
+    architecture is a single read segment ("R:N") is not decoded but goes through run_rna_dust: with contexts (no model needed;
+    their dust must equal `dust`) on the devices, TD_MODE_RNA_DUST; with None on the host.  A -ref artifact filter
+    (set_artifacts) set on any file's contexts must be set on every file's, so that every file needs contexts then; batch_reads
+    defaults to the reference's 1 000 001 records with a filter.  Returns (statistics dict, counters int64[264])."""
     lib = load_library()
     lib.td_stream_run_multi.argtypes = [C.POINTER(_StreamFile), C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(_StreamOpts),
                                         C.POINTER(_StreamStats), C.c_void_p]

@@ -20,6 +20,7 @@ static int64_t g_t = 0;
 int td_submit(td_ctx*, const void*, int32_t, const int64_t* offs, int64_t n, int, td_read_result* res, int8_t*, uint8_t* seq_out, int64_t* ticket)
 { memset(res, 0, sizeof(td_read_result) * (size_t)n); for (int64_t i = 0; i < n; i++) { res[i].barcode = (int32_t)(i % 3); res[i].fingerprint = -1; res[i].mapq = 12.345f; } memset(seq_out, 1, (size_t)(offs[n] - offs[0])); *ticket = ++g_t; return 0; }
 int td_wait(td_ctx*, int64_t) { return 0; }
+int td_set_batch_window(td_ctx*, int64_t, int64_t) { return 0; }
 }
 int main(int argc, char** argv)
 {
