@@ -1,15 +1,22 @@
-// td_stream.cpp -- one input file of any size through the decode path as a pipeline (include/tagdust_io.h, td_stream_run):
+// td_stream.cpp -- input files of any size through the decode path as a pipeline (include/tagdust_io.h): td_stream_run, one
+// input file on one device, and td_stream_run_multi, the K input files of a paired / multi-read run in lock-step on N devices.
 //
-//   reader / parser thread            caller's thread                     writer thread
+//   reader / parser thread (per file) caller's thread                     writer thread
 //   block k+1: read or map, find      batch k: td_submit ... td_wait      batch k-1: format per output file, append
 //   records, base-code them into      (several batches in flight on the
-//   the next batch's pinned buffers   device)
+//   the next batch's pinned buffers   devices)
 //
-// It replaces the reference's batch loop around run_pHMM for one file (src/barcode_hmm.c:244-385): read_fasta_fastq() of
-// <= 1 000 001 records (io.c:1684-1815, through popen("cat|zcat|bzcat"), io.c:382-608) -> run_pHMM -> print_all() appending
+// It replaces the reference's batch loop around run_pHMM (src/barcode_hmm.c:244-385): read_fasta_fastq() of <= 1 000 001
+// records of every file (io.c:1684-1815, through popen("cat|zcat|bzcat"), io.c:382-608) -> run_pHMM -> print_all() appending
 // to the per-barcode files (io.c:757-1016) -- with the three steps of consecutive batches running side by side, each of the
 // two host steps on several threads.  Batches hold exactly `batch_reads` records like the reference's (the -ref artifact
 // filter's per-thread read ranges are taken over a batch, barcode_hmm.c:2478-2583, so the boundaries are part of the result).
+//
+// The pieces: a Reader per input file (Source, parse pool, the batches it owns, its allocator and producer threads), one
+// run_stages() for both entry points (the device stage over tuples of one batch per file, the write-stage thread, the
+// teardown), one Writer (output files, format pool, appender thread) and one RunError that all of them share: the first
+// failure anywhere is the run's message and ends every stage.  An entry point validates its arguments, sets these up and
+// gives run_stages what is its own: the check of a tuple and what the write stage does with a finished one.
 #include <errno.h>
 #include <fcntl.h>
 #include <stdio.h>
@@ -359,9 +366,7 @@ struct Batch {
 	int64_t* offs = nullptr;
 	td_read_result* res = nullptr;
 	std::vector<Piece> pieces;
-	int64_t ticket = 0;
-	bool last = false;
-	int64_t cap_reads = 0;      // offs / res hold this many reads
+	int64_t cap_reads = 0;     // offs / res hold this many reads
 	const uint8_t* seq_src = nullptr;   // what the writer prints: seq_out, or codes for a file that is not decoded (run_rna_dust)
 };
 
@@ -548,48 +553,103 @@ void format_records(const Batch& b, const Piece& pc, int64_t lo, int64_t hi, int
 	}
 }
 
-struct Pipeline {
-	td_ctx* ctx = nullptr;
-	const td_arch* arch = nullptr;
-	td_stream_opts o{};
-	td_stream_stats st{};
+// ---- the error of a run: the first message stays, and failing ends the run by aborting every queue between its stages ----
+class RunError {
+public:
+	template <typename Q>
+	void watch(Q* q)        // q->abort() when the run fails (at once when it already has); q outlives the run's threads
+	{
+		std::lock_guard<std::mutex> lk(mu_);
+		if (!msg_.empty()) q->abort();
+		aborts_.push_back([q] { q->abort(); });
+	}
+	void fail(const std::string& m)
+	{
+		std::lock_guard<std::mutex> lk(mu_);
+		if (msg_.empty()) msg_ = m;
+		for (auto& a : aborts_) a();
+	}
+	bool failed() { std::lock_guard<std::mutex> lk(mu_); return !msg_.empty(); }
+	std::string message() { std::lock_guard<std::mutex> lk(mu_); return msg_; }
+
+private:
+	std::mutex mu_;
+	std::string msg_;
+	std::vector<std::function<void()>> aborts_;
+};
+
+// ---- stage 1 of one input file: its source, the batches it owns, an allocator thread and a producer thread with a parse pool ----
+struct Reader {
+	RunError& err;
+	const td_stream_opts o;
+	const bool dry;            // batch buffers in plain memory: a file that no device sees
+	const bool want_seq;       // page-locked room for rewritten sequences (not for a file that goes through TD_MODE_RNA_DUST)
+	const int parse_threads;
 	Source src;
-	std::string err;
-	std::mutex err_mu;
-	std::unique_ptr<Pool> parse_pool, write_pool;
-	// Appends run beside the formatting of the next batch: every append is a pwrite at an offset fixed when the batch was
-	// formatted, so the order in which they reach the files is free.  Two sets of formatted text; a set is reused once its
-	// appends have been written (append_wait).
-	struct Wr { size_t file, k0, k1; int64_t at; };
-	struct AppendJob { int set; std::vector<Wr> wr; };
-	std::unique_ptr<Pool> append_pool;
-	std::thread appender;
-	std::mutex ap_mu;
-	std::condition_variable ap_cv;
-	std::deque<AppendJob> ap_jobs;
-	bool ap_busy[2] = { false, false }, ap_stop = false, ap_started = false;
-	int ap_errno = 0, ap_set = 0;
-	std::vector<OutBufs> ap_bufs[2];
-	std::unique_ptr<Queue<Batch*>> ready, done, free_list;
+	std::unique_ptr<Pool> parse_pool;
+	std::unique_ptr<Queue<Batch*>> ready, free_list;
 	std::vector<Batch*> all;
-	std::vector<int> fds;
-	std::vector<int64_t> file_off;
-	int num_alternatives = 2;
-	bool dry = false;
-	bool want_seq = true;      // page-locked room for rewritten sequences (not for a file that goes through TD_MODE_RNA_DUST)
-	uint64_t fnv = 1469598103934665603ULL;
-	double dbg_pass1 = 0, dbg_grow = 0, dbg_encode = 0, dbg_format = 0, dbg_pwrite = 0;
+	int64_t bytes_in = 0;
+	double read_s = 0, parse_s = 0;
+	double dbg_pass1 = 0, dbg_grow = 0, dbg_encode = 0;
 	size_t batch_hint = 0;
 	std::mutex all_mu;
 	std::condition_variable hint_cv;
 	bool hint_ready = false, stop_alloc = false;
+	std::thread t_alloc, t_prod;
 
-	void fail(const std::string& m)
+	Reader(RunError& e, const td_stream_opts& opts, bool dry_, bool want_seq_, int parse_threads_)
+		: err(e), o(opts), dry(dry_), want_seq(want_seq_), parse_threads(parse_threads_) {}
+	~Reader() { stop(); release(false); }
+
+	// the queues (n_batches: `depth` on the device, one being filled, one being written, one spare on either side), the first
+	// two batches, the two threads; false: not even those two batches could be had (nothing was started)
+	bool start(int n_batches)
 	{
-		{ std::lock_guard<std::mutex> lk(err_mu); if (err.empty()) err = m; }
-		ready->abort(); done->abort(); free_list->abort();
+		parse_pool.reset(new Pool(parse_threads));
+		ready.reset(new Queue<Batch*>((size_t)n_batches));
+		free_list.reset(new Queue<Batch*>((size_t)n_batches));
+		err.watch(ready.get());
+		err.watch(free_list.get());
+		for (int k = 0; k < 2; k++) {
+			Batch* b = new_batch();
+			if (!b) return false;
+			free_list->push(b);
+		}
+		t_alloc = std::thread([this, n_batches] { allocator(n_batches - 2); });
+		t_prod = std::thread([this] { producer(); });
+		return true;
 	}
-	bool failed() { std::lock_guard<std::mutex> lk(err_mu); return !err.empty(); }
+
+	// ends the two threads: once the input has been read to its end or the run has failed (the producer leaves a wait on an
+	// aborted queue), also when start() failed or was never called
+	void stop()
+	{
+		if (t_prod.joinable()) t_prod.join();
+		{ std::lock_guard<std::mutex> lk(all_mu); stop_alloc = true; }
+		hint_cv.notify_all();
+		if (free_list) free_list->abort();          // (an allocator waiting to hand over a batch)
+		if (t_alloc.joinable()) t_alloc.join();
+	}
+
+	// the batches of a finished run: kept for the next one (page-locked, within the cache's size) or freed
+	void release(bool keep)
+	{
+		std::lock_guard<std::mutex> lk(g_cache_mu);
+		size_t held = 0;
+		for (const Batch* q : g_cache) held += batch_bytes(q);
+		for (Batch* q : all) {
+			if (!dry && keep && q->codes && held + batch_bytes(q) <= kCacheBytes) {
+				q->pieces.clear(); q->n = 0; q->n_bases = 0; q->seq_src = nullptr;
+				held += batch_bytes(q);
+				g_cache.push_back(q);
+				continue;
+			}
+			buf_free(dry, q->codes); buf_free(dry, q->seq_out); buf_free(dry, q->offs); buf_free(dry, q->res);
+			delete q;
+		}
+		all.clear();
+	}
 
 	Batch* new_batch()
 	{
@@ -634,17 +694,17 @@ struct Pipeline {
 		}
 	}
 
-	// ---- stage 1: read / map a block, find its records, hand them out to batches, base-code them ----
+	// read / map a block, find its records, hand them out to batches, base-code them
 	void producer()
 	{
 		Batch* cur = nullptr;
 		const int P = parse_pool->size();
 		for (;;) {
 			std::string e;
-			std::shared_ptr<Block> blk = src.next(&st.read_s, e);
-			if (!blk) { if (!e.empty()) { fail(e); return; } break; }
+			std::shared_ptr<Block> blk = src.next(&read_s, e);
+			if (!blk) { if (!e.empty()) { err.fail(e); return; } break; }
 			const double t0 = now_s();
-			st.bytes_in += blk->len;
+			bytes_in += blk->len;
 			// records: P chunks cut at record starts, each parsed by the reference's line state machine
 			const bool fasta = blk->len > 0 && blk->data[0] == '>';
 			std::vector<int64_t> cut(1, 0);
@@ -673,7 +733,7 @@ struct Pipeline {
 					char msg[256];
 					snprintf(msg, sizeof msg, "td_stream_run: record \"%.*s\": sequence has %d characters, base qualities %d",
 					         q.name_len < 60 ? q.name_len : 60, blk->data + q.name_off, q.seq_off >= 0 ? q.seq_len : 0, q.qual_len);
-					fail(msg);
+					err.fail(msg);
 					return;
 				}
 			{   // bases a full batch of reads like this block's will hold (+6 %)
@@ -706,7 +766,7 @@ struct Pipeline {
 					for (const Job& j : jobs) if (j.b == b) { keep = (size_t)b->offs[b->pieces[j.piece].first]; mine = true; break; }
 					if (!mine) continue;
 					if (!grow_buf(dry, &b->codes, &b->cap_codes, (size_t)b->n_bases + 1, keep, batch_hint) ||
-					    (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, (size_t)b->n_bases + 1, 0, batch_hint))) { fail("td_stream_run: page-locked memory exhausted"); return false; }
+					    (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, (size_t)b->n_bases + 1, 0, batch_hint))) { err.fail("td_stream_run: page-locked memory exhausted"); return false; }
 				}
 				dbg_grow += now_s() - tf0;
 				const double tf1 = now_s();
@@ -730,7 +790,7 @@ struct Pipeline {
 				});
 				jobs.clear();
 				dbg_encode += now_s() - tf1;
-				st.parse_s += now_s() - t_seg;                          // (time spent waiting for a free batch is not parsing)
+				parse_s += now_s() - t_seg;                             // (time spent waiting for a free batch is not parsing)
 				for (Batch* b : full) if (!ready->push(b)) return false;
 				full.clear();
 				t_seg = now_s();
@@ -742,10 +802,10 @@ struct Pipeline {
 				while (lo < (int64_t)v.size()) {
 					if (!cur) {
 						if (!full.empty() && !flush()) return;
-						st.parse_s += now_s() - t_seg;
+						parse_s += now_s() - t_seg;
 						if (!free_list->pop(cur)) return;                  // aborted
 						t_seg = now_s();
-						cur->n = 0; cur->n_bases = 0; cur->pieces.clear(); cur->last = false; cur->ticket = 0;
+						cur->n = 0; cur->n_bases = 0; cur->pieces.clear();
 					}
 					const int64_t take = std::min<int64_t>((int64_t)v.size() - lo, (int64_t)o.batch_reads - cur->n);
 					Piece pc; pc.blk = blk; pc.recs = recs[(size_t)k]; pc.lo = lo; pc.hi = lo + take; pc.first = cur->n;
@@ -763,10 +823,61 @@ struct Pipeline {
 			}
 			if (!flush()) return;
 		}
-		if (getenv("TD_STREAM_DEBUG")) fprintf(stderr, "td_stream: records %.3f s, buffers %.3f s, base codes %.3f s (parse stage %.3f s)\n", dbg_pass1, dbg_grow, dbg_encode, st.parse_s);
-		if (cur && cur->n > 0) { cur->last = true; if (!ready->push(cur)) return; }
+		if (getenv("TD_STREAM_DEBUG")) fprintf(stderr, "td_stream: records %.3f s, buffers %.3f s, base codes %.3f s (parse stage %.3f s)\n", dbg_pass1, dbg_grow, dbg_encode, parse_s);
+		if (cur && cur->n > 0) { if (!ready->push(cur)) return; }
 		else if (cur) free_list->push(cur);
 		ready->close();
+	}
+};
+
+// ---- the output side of stage 3: the output files, a pool that formats a batch's records, an appender thread that writes them ----
+struct Writer {
+	RunError& err;
+	Pool pool;
+	const int num_alternatives;
+	std::vector<int> fds;
+	std::vector<int64_t> file_off;
+	int64_t bytes_out = 0;
+	double dbg_format = 0, dbg_pwrite = 0;
+	// Appends run beside the formatting of the next batch: every append is a pwrite at an offset fixed when the batch was
+	// formatted, so the order in which they reach the files is free.  Two sets of formatted text; a set is reused once its
+	// appends have been written (append_wait).
+	struct Wr { size_t file, k0, k1; int64_t at; };
+	struct AppendJob { int set; std::vector<Wr> wr; };
+	std::unique_ptr<Pool> append_pool;
+	std::thread appender;
+	std::mutex ap_mu;
+	std::condition_variable ap_cv;
+	std::deque<AppendJob> ap_jobs;
+	bool ap_busy[2] = { false, false }, ap_stop = false, ap_started = false;
+	int ap_errno = 0, ap_set = 0;
+	std::vector<OutBufs> ap_bufs[2];
+
+	Writer(RunError& e, int n_threads, int num_alternatives_) : err(e), pool(n_threads), num_alternatives(num_alternatives_) {}
+	~Writer() { (void)close(); }
+
+	// creates the output files; false: `why` says which one could not be created, and none of them stays open
+	bool open(const std::vector<std::string>& names, std::string& why)
+	{
+		for (auto& nm : names) {
+			const int fd = ::open(nm.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+			if (fd < 0) { why = nm + ": " + strerror(errno); (void)close(); return false; }
+			fds.push_back(fd);
+		}
+		file_off.assign(fds.size(), 0);
+		return true;
+	}
+	// waits for the appends of every batch written; false if one of them failed
+	bool finish() { return append_wait(-1); }
+	// stops the appender (after a failure appends may still be queued: none may outlive the descriptors) and closes the files;
+	// the errno of the first close that failed, 0 if none did
+	int close()
+	{
+		append_stop();
+		int first = 0;
+		for (int fd : fds) if (::close(fd) != 0 && !first) first = errno;
+		fds.clear();
+		return first;
 	}
 
 	void append_loop()
@@ -809,7 +920,7 @@ struct Pipeline {
 	{
 		std::unique_lock<std::mutex> lk(ap_mu);
 		ap_cv.wait(lk, [&] { return set < 0 ? (!ap_busy[0] && !ap_busy[1]) : !ap_busy[set]; });
-		if (ap_errno) { const int e = ap_errno; lk.unlock(); fail(std::string("td_stream_run: write failed: ") + strerror(e)); return false; }
+		if (ap_errno) { const int e = ap_errno; lk.unlock(); err.fail(std::string("td_stream_run: write failed: ") + strerror(e)); return false; }
 		return true;
 	}
 	void append_stop()
@@ -818,15 +929,14 @@ struct Pipeline {
 		ap_cv.notify_all();
 		if (appender.joinable()) appender.join();
 	}
-	~Pipeline() { append_stop(); }
 
-	// format the records of one batch per output file (on the write pool) and hand the appends (in input order per file) to the
-	// appender thread; append_wait(-1) before the files are closed
+	// format the records of one batch per output file (on the pool) and hand the appends (in input order per file) to the
+	// appender thread; finish() before the files are closed
 	bool write_batch(Batch* b, const int32_t* ctype, const int32_t* cbar, size_t file_base)
 	{
 		if (!ap_started) {
 			ap_started = true;
-			append_pool.reset(new Pool(write_pool->size()));
+			append_pool.reset(new Pool(pool.size()));
 			appender = std::thread([this] { append_loop(); });
 		}
 		const int set = ap_set;
@@ -834,7 +944,7 @@ struct Pipeline {
 		if (!append_wait(set)) return false;
 		std::vector<OutBufs>& bufs = ap_bufs[set];
 		const double t0 = now_s();
-		const int W = write_pool->size();
+		const int W = pool.size();
 		struct Sub { size_t piece; int64_t lo, hi; };
 		std::vector<Sub> subs;
 		const int64_t step = std::max<int64_t>(4096, (b->n + W * 4 - 1) / (W * 4));
@@ -846,7 +956,7 @@ struct Pipeline {
 			if (bufs[k].file.size() != fds.size()) bufs[k].file.resize(fds.size());
 			for (auto& s : bufs[k].file) s.n = 0;
 		}
-		write_pool->run((int64_t)subs.size(), [&](int64_t k) {
+		pool.run((int64_t)subs.size(), [&](int64_t k) {
 			const Sub& sb = subs[(size_t)k];
 			format_records(*b, b->pieces[sb.piece], sb.lo, sb.hi, num_alternatives, bufs[(size_t)k], ctype, cbar, file_base);
 		});
@@ -877,7 +987,7 @@ struct Pipeline {
 				}
 			}
 			file_off[f] += per_file[f];
-			st.bytes_out += per_file[f];
+			bytes_out += per_file[f];
 		}
 		{
 			std::lock_guard<std::mutex> lk(ap_mu);
@@ -885,60 +995,168 @@ struct Pipeline {
 			ap_jobs.push_back(AppendJob{ set, std::move(wr) });
 		}
 		ap_cv.notify_all();
-		static const bool sync_appends = getenv("TD_STREAM_SYNC_APPENDS") && atoi(getenv("TD_STREAM_SYNC_APPENDS")) != 0;   // A/B: round 3's order
-		if (sync_appends && !append_wait(set)) return false;
 		return true;
-	}
-
-	// ---- stage 3: format the records per output file and append them in input order ----
-	void consumer()
-	{
-		Batch* b = nullptr;
-		while (done->pop(b)) {
-			const double t0 = now_s();
-			if (!dry) {
-				if (!write_batch(b, nullptr, nullptr, 0)) return;
-			} else {
-				// parse-only run: a checksum over what would have gone to the device (lengths and codes, in order)
-				for (int64_t i = 0; i < b->n; i++) {
-					const int64_t l = b->offs[i + 1] - b->offs[i];
-					fnv = (fnv ^ (uint64_t)l) * 1099511628211ULL;
-					const uint8_t* s = b->codes + b->offs[i];
-					for (int64_t j = 0; j < l; j++) fnv = (fnv ^ s[j]) * 1099511628211ULL;
-				}
-			}
-			st.n_reads += b->n; st.n_batches++;
-			b->pieces.clear();                 // releases the blocks
-			st.write_s += now_s() - t0;
-			if (!free_list->push(b)) return;
-		}
-		{
-			const double t0 = now_s();
-			const bool ok = append_wait(-1);
-			st.write_s += now_s() - t0;
-			if (!ok) return;
-		}
-		if (getenv("TD_STREAM_DEBUG")) fprintf(stderr, "td_stream: formatting %.3f s, appends %.3f s beside it (write stage %.3f s)\n", dbg_format, dbg_pwrite, st.write_s);
 	}
 };
 
-// the batches of a finished run: kept for the next one (page-locked, within the cache's size) or freed
-static void release_batches(Pipeline& p, bool keep)
+// ---- td_stream_opts as the run uses them (the defaults of include/tagdust_io.h) ----
+// The reference reads 1 000 001 records at a time (param->num_query, barcode_hmm.c:172).  Per-read results do not depend on how
+// a file is cut into batches -- except through the -ref artifact filter, whose per-thread read ranges are taken over a batch:
+// with a filter set (and in a parse-only run) the batches are the reference's (reference_batches), otherwise they are 2^18
+// reads (one tile per wave slot of the device; a quarter of the page-locked memory and a pipeline that fills four times sooner).
+td_stream_opts resolve_opts(const td_stream_opts* opts, bool reference_batches)
 {
-	std::lock_guard<std::mutex> lk(g_cache_mu);
-	size_t held = 0;
-	for (const Batch* q : g_cache) held += batch_bytes(q);
-	for (Batch* q : p.all) {
-		if (!p.dry && keep && q->codes && held + batch_bytes(q) <= kCacheBytes) {
-			q->pieces.clear(); q->n = 0; q->n_bases = 0; q->ticket = 0; q->seq_src = nullptr;
-			held += batch_bytes(q);
-			g_cache.push_back(q);
-			continue;
+	td_stream_opts o{};
+	if (opts) o = *opts;
+	if (o.batch_reads <= 0) o.batch_reads = reference_batches ? 1000001 : (1 << 18);
+	if (o.block_bytes <= 0) o.block_bytes = (int64_t)64 << 20;
+	if (o.block_bytes < 4096) o.block_bytes = 4096;
+	int hw = (int)std::thread::hardware_concurrency();
+	if (hw < 1) hw = 1;
+	if (o.n_threads <= 0) o.n_threads = hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1);
+	if (o.n_threads > 32) o.n_threads = 32;
+	return o;
+}
+
+// batches (record ranges of every file) in flight on the devices: the option of a context of the run, 3 when it has none
+int pipeline_depth(td_ctx* ctx)
+{
+	int32_t depth = 3;
+	if (ctx) (void)td_get_option(ctx, "pipeline_depth", &depth);
+	return depth;
+}
+
+bool artifacts_active(td_ctx* ctx)
+{
+	int32_t art = 0;
+	(void)td_get_option(ctx, "artifacts_active", &art);
+	return art != 0;
+}
+
+// ---- the three stages of a run over K input files in lock-step and N devices (td_stream_run: K = 1, N = 1) ----
+struct Tuple {                        // batch j of every input file: records [j * batch_reads, ...) of each
+	std::vector<Batch*> b;            // [file]; the batches stay their readers'
+	std::vector<int64_t> tickets;     // [file * N + device]; 0: nothing was submitted
+	Tuple(int K, int N) : b((size_t)K, nullptr), tickets((size_t)(K * N), 0) {}
+};
+
+struct Target {                       // where the batches of one input file go
+	td_ctx* const* ctx;               // its context on each of the N devices; NULL: no device sees this file
+	bool rna;                         // run_rna_dust (TD_MODE_RNA_DUST: the reads come back unchanged) instead of the HMM
+};
+
+// Starts the readers, runs the write stage on a thread of its own (`write` for every finished tuple in input order, then the
+// wait for the writer's appends; writer == NULL: a parse-only run, no output files) and the device stage on the calling thread
+// (a context is driven from one thread): a ready batch of every reader -> `check` (an error message, or empty) -> submit, at most
+// `depth` tuples in flight, waited for in order.  Then the teardown, the same after a failure at any point: every ticket still
+// outstanding waited for, write stage and appender ended, files closed, readers stopped, batches released.  The run's error, if
+// any, is in `err`; `prefix` starts the messages of this function.
+void run_stages(const std::string& prefix, RunError& err, const std::vector<std::unique_ptr<Reader>>& readers, const std::vector<Target>& dev,
+                const int N, const int depth, Writer* writer, const std::function<std::string(const Tuple&)>& check,
+                const std::function<bool(Tuple&)>& write, td_stream_stats& st)
+{
+	const int K = (int)readers.size();
+	const int n_batches = depth + 4;
+	Queue<std::unique_ptr<Tuple>> done((size_t)n_batches);      // (tuples left in it by a failed run are freed with it)
+	err.watch(&done);
+	for (auto& r : readers)
+		if (!r->start(n_batches)) { err.fail(prefix + "page-locked memory exhausted"); break; }
+	std::thread t_write([&] {
+		std::unique_ptr<Tuple> t;
+		while (done.pop(t)) {
+			const double t0 = now_s();
+			if (!write(*t)) return;
+			st.n_reads += t->b[0]->n; st.n_batches++;
+			for (Batch* b : t->b) b->pieces.clear();               // releases the blocks
+			st.write_s += now_s() - t0;
+			for (int k = 0; k < K; k++) if (!readers[(size_t)k]->free_list->push(t->b[(size_t)k])) return;
 		}
-		buf_free(p.dry, q->codes); buf_free(p.dry, q->seq_out); buf_free(p.dry, q->offs); buf_free(p.dry, q->res);
-		delete q;
+		const double t0 = now_s();
+		if (writer) (void)writer->finish();
+		st.write_s += now_s() - t0;
+	});
+	std::deque<std::unique_ptr<Tuple>> flying;
+	auto wait_for = [&](const Tuple& t) -> bool {   // every ticket of the tuple, also after one of them has failed
+		bool ok = true;
+		for (int k = 0; k < K; k++)
+			for (int d = 0; d < N; d++) {
+				const int64_t ticket = t.tickets[(size_t)(k * N + d)];
+				if (dev[(size_t)k].ctx && ticket && td_wait(dev[(size_t)k].ctx[d], ticket) != TD_OK) {
+					if (ok) err.fail(prefix + td_last_error(dev[(size_t)k].ctx[d]));
+					ok = false;
+				}
+			}
+		return ok;
+	};
+	auto retire = [&]() -> bool {
+		std::unique_ptr<Tuple> t = std::move(flying.front());
+		flying.pop_front();
+		const double t0 = now_s();
+		const bool ok = wait_for(*t);
+		st.decode_s += now_s() - t0;
+		return ok && done.push(std::move(t));
+	};
+	while (!err.failed()) {
+		std::unique_ptr<Tuple> t(new Tuple(K, N));
+		int n_closed = 0;
+		bool bad = false;
+		// With nothing ready from a reader and tuples in flight the oldest one is retired instead of waiting: the reader may be
+		// waiting for exactly that tuple's buffers.  (The allocator thread "runs with what it has" when page-locking fails part-way
+		// -- a memlock limit, a container -- and with fewer than depth + 2 batches in all a loop that only retires at full depth
+		// leaves the reader waiting for a free batch, this thread for a ready one and the writer for a finished one, forever.)
+		for (int k = 0; k < K && !bad; k++)
+			for (;;) {
+				const Reader& r = *readers[(size_t)k];
+				Batch* b = nullptr;
+				const int got = flying.empty() ? (r.ready->pop(b) ? 1 : -1) : r.ready->try_pop(b);
+				if (got == 1) { t->b[(size_t)k] = b; break; }
+				if (got < 0) { n_closed++; break; }
+				if (!retire()) { bad = true; break; }
+			}
+		if (bad || n_closed == K) break;
+		const std::string objection = check(*t);
+		if (!objection.empty()) { err.fail(objection); break; }
+		if ((int)flying.size() >= depth && !retire()) break;
+		const double t0 = now_s();
+		const int64_t n = t->b[0]->n;
+		bool ok = true;
+		for (int k = 0; k < K && ok; k++) {
+			if (!dev[(size_t)k].ctx) continue;
+			Batch* b = t->b[(size_t)k];
+			for (int d = 0; d < N && ok; d++) {      // run_pHMM's contiguous ranges over the devices (barcode_hmm.c:1911-1922)
+				td_ctx* ctx = dev[(size_t)k].ctx[d];
+				const int64_t interval = n / N, lo = (int64_t)d * interval, hi = (d == N - 1) ? n : lo + interval;
+				if (hi <= lo) continue;
+				const bool r = dev[(size_t)k].rna;
+				// (the window: the artifact filter's thread ranges are those of the whole batch, not of a device's range)
+				ok = (N == 1 || td_set_batch_window(ctx, lo, n) == TD_OK) &&
+				     td_submit(ctx, b->codes, 0, b->offs + lo, hi - lo, r ? TD_MODE_RNA_DUST : TD_MODE_GET_LABEL, b->res + lo, nullptr,
+				               r ? nullptr : b->seq_out + b->offs[lo], &t->tickets[(size_t)(k * N + d)]) == TD_OK;
+				if (!ok) err.fail(prefix + td_last_error(ctx));
+			}
+		}
+		st.decode_s += now_s() - t0;
+		flying.push_back(std::move(t));     // (also after a failed submit: the ranges already on other devices are waited for below)
+		if (!ok) break;
 	}
-	p.all.clear();
+	while (!flying.empty() && !err.failed()) if (!retire()) break;
+	if (err.failed()) {                     // nothing of ours may stay queued on the devices
+		for (auto& t : flying) (void)wait_for(*t);
+		flying.clear();
+	}
+	done.close();
+	t_write.join();
+	if (writer) {
+		const int e = writer->close();
+		if (e) err.fail(prefix + "close failed: " + strerror(e));
+	}
+	if (N > 1) for (const Target& tg : dev) if (tg.ctx) for (int d = 0; d < N; d++) (void)td_set_batch_window(tg.ctx[d], 0, 0);
+	for (auto& r : readers) r->stop();
+	for (auto& r : readers) {
+		st.bytes_in += r->bytes_in; st.parse_s += r->parse_s; st.read_s += r->read_s;
+		r->release(!err.failed());
+	}
+	if (writer) st.bytes_out = writer->bytes_out;
 }
 
 } // namespace
@@ -958,102 +1176,46 @@ extern "C" int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* ar
 {
 	if (!in_path) { td_io_set_error("td_stream_run: NULL input path"); return TD_FAIL; }
 	if (ctx && (!arch || !out_prefix)) { td_io_set_error("td_stream_run: a decoding run needs the architecture and an output prefix"); return TD_FAIL; }
-	Pipeline p;
-	p.ctx = ctx; p.arch = arch; p.dry = ctx == nullptr;
-	if (opts) p.o = *opts;
-	if (p.o.batch_reads <= 0) {
-		// The reference reads 1 000 001 records at a time (param->num_query, barcode_hmm.c:172).  Per-read results do not depend on
-		// how a file is cut into batches -- except through the -ref artifact filter, whose per-thread read ranges are taken over a
-		// batch: with a filter set the batches are the reference's, without one they are 2^18 reads (one tile per wave slot of
-		// the device; a quarter of the page-locked memory and a pipeline that fills four times sooner).
-		int32_t art = 0;
-		if (ctx) (void)td_get_option(ctx, "artifacts_active", &art);
-		p.o.batch_reads = (!ctx || art) ? 1000001 : (1 << 18);
-	}
-	if (p.o.block_bytes <= 0) p.o.block_bytes = (int64_t)64 << 20;
-	if (p.o.block_bytes < 4096) p.o.block_bytes = 4096;
-	int hw = (int)std::thread::hardware_concurrency();
-	if (hw < 1) hw = 1;
-	if (p.o.n_threads <= 0) p.o.n_threads = hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1);
-	if (p.o.n_threads > 32) p.o.n_threads = 32;
-	int32_t depth = 3;
-	if (ctx) (void)td_get_option(ctx, "pipeline_depth", &depth);
+	const td_stream_opts o = resolve_opts(opts, !ctx || artifacts_active(ctx));
 	const double t_start = now_s();
-	std::string err;
-	if (!p.src.open(in_path, p.o.block_bytes, err)) { td_io_set_error(err); return TD_FAIL; }
-	if (!p.dry) {
+	RunError err;
+	std::vector<std::unique_ptr<Reader>> readers;
+	readers.emplace_back(new Reader(err, o, ctx == nullptr, true, o.n_threads));
+	std::string why;
+	if (!readers[0]->src.open(in_path, o.block_bytes, why)) { td_io_set_error(why); return TD_FAIL; }
+	std::unique_ptr<Writer> w;
+	if (ctx) {
 		std::vector<std::string> names;
-		td_writer_file_names(out_prefix, arch, names, &p.num_alternatives);
-		for (auto& nm : names) {
-			const int fd = open(nm.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-			if (fd < 0) { for (int g : p.fds) close(g); td_io_set_error("td_stream_run: cannot create " + nm + ": " + strerror(errno)); return TD_FAIL; }
-			p.fds.push_back(fd);
+		int num_alternatives = 2;
+		td_writer_file_names(out_prefix, arch, names, &num_alternatives);
+		w.reset(new Writer(err, o.n_threads, num_alternatives));
+		if (!w->open(names, why)) { td_io_set_error("td_stream_run: cannot create " + why); return TD_FAIL; }
+	}
+	td_stream_stats st{};
+	uint64_t fnv = 1469598103934665603ULL;
+	std::function<bool(Tuple&)> write;
+	if (ctx) write = [&](Tuple& t) { return w->write_batch(t.b[0], nullptr, nullptr, 0); };
+	else write = [&](Tuple& t) {
+		// parse-only run: a checksum over what would have gone to the device (lengths and codes, in order)
+		const Batch* b = t.b[0];
+		for (int64_t i = 0; i < b->n; i++) {
+			const int64_t l = b->offs[i + 1] - b->offs[i];
+			fnv = (fnv ^ (uint64_t)l) * 1099511628211ULL;
+			const uint8_t* s = b->codes + b->offs[i];
+			for (int64_t j = 0; j < l; j++) fnv = (fnv ^ s[j]) * 1099511628211ULL;
 		}
-		p.file_off.assign(p.fds.size(), 0);
-	}
-	p.parse_pool.reset(new Pool(p.o.n_threads));
-	p.write_pool.reset(new Pool(p.o.n_threads));
-	// batches: `depth` on the device, one being filled, one being written, one spare on either side
-	const int n_batches = depth + 4;
-	p.ready.reset(new Queue<Batch*>((size_t)n_batches));
-	p.done.reset(new Queue<Batch*>((size_t)n_batches));
-	p.free_list.reset(new Queue<Batch*>((size_t)n_batches));
-	bool ok = true;
-	for (int k = 0; k < 2 && ok; k++) {
-		Batch* b = p.new_batch();
-		if (!b) { ok = false; break; }
-		p.free_list->push(b);
-	}
-	int rc = TD_OK;
-	if (!ok) { p.fail("td_stream_run: page-locked memory exhausted"); rc = TD_FAIL; }
-	std::thread t_alloc([&] { p.allocator(n_batches - 2); });
-	std::thread t_prod([&] { p.producer(); });
-	std::thread t_cons([&] { p.consumer(); });
-	// ---- stage 2, on the caller's thread (a context is driven from one thread): submit, keep `depth` in flight, wait in order ----
-	std::deque<Batch*> flying;
-	auto retire = [&]() -> bool {
-		Batch* b = flying.front();
-		flying.pop_front();
-		const double t0 = now_s();
-		if (ctx && td_wait(ctx, b->ticket) != TD_OK) { p.fail(std::string("td_stream_run: ") + td_last_error(ctx)); return false; }
-		p.st.decode_s += now_s() - t0;
-		return p.done->push(b);
+		return true;
 	};
-	// With nothing ready to submit and batches in flight the oldest one is retired instead of waiting: the reader may be waiting
-	// for exactly that batch's buffers.  (The allocator thread "runs with what it has" when page-locking fails part-way -- a
-	// memlock limit, a container -- and with fewer than depth + 2 batches in all a loop that only retires at full depth leaves
-	// the reader waiting for a free batch, this thread for a ready one and the writer for a finished one, forever.)
-	while (rc == TD_OK) {
-		Batch* b = nullptr;
-		const int got = flying.empty() ? (p.ready->pop(b) ? 1 : -1) : p.ready->try_pop(b);
-		if (got < 0) break;
-		if (got == 0) { if (!retire()) break; continue; }
-		if ((int)flying.size() >= depth && !retire()) break;
-		const double t0 = now_s();
-		if (ctx && td_submit(ctx, b->codes, 0, b->offs, b->n, TD_MODE_GET_LABEL, b->res, nullptr, b->seq_out, &b->ticket) != TD_OK) {
-			p.fail(std::string("td_stream_run: ") + td_last_error(ctx));
-			break;
-		}
-		p.st.decode_s += now_s() - t0;
-		flying.push_back(b);
-	}
-	while (!flying.empty() && !p.failed()) if (!retire()) break;
-	if (p.failed() && ctx) for (Batch* f : flying) (void)td_wait(ctx, f->ticket);   // nothing of ours may stay queued on the device
-	p.done->close();
-	t_prod.join();
-	t_cons.join();
-	p.append_stop();                       // (after a failure appends may still be queued: none may outlive the descriptors)
-	{ std::lock_guard<std::mutex> lk(p.all_mu); p.stop_alloc = true; }
-	p.hint_cv.notify_all();
-	p.free_list->abort();          // (an allocator waiting to hand over a batch)
-	t_alloc.join();
-	for (int fd : p.fds) if (close(fd) != 0 && !p.failed()) p.fail(std::string("td_stream_run: close failed: ") + strerror(errno));
-	release_batches(p, !p.failed());
-	p.st.wall_s = now_s() - t_start;
-	p.st.codes_fnv = p.dry ? p.fnv : 0;
-	if (stats) *stats = p.st;
-	if (p.failed()) { td_io_set_error(p.err); return TD_FAIL; }
-	return rc;
+	td_ctx* const one[1] = { ctx };
+	run_stages("td_stream_run: ", err, readers, { Target{ ctx ? one : nullptr, false } }, 1, pipeline_depth(ctx), w.get(),
+	           [](const Tuple&) { return std::string(); }, write, st);
+	if (!err.failed() && getenv("TD_STREAM_DEBUG"))
+		fprintf(stderr, "td_stream: formatting %.3f s, appends %.3f s beside it (write stage %.3f s)\n", w ? w->dbg_format : 0.0, w ? w->dbg_pwrite : 0.0, st.write_s);
+	st.wall_s = now_s() - t_start;
+	st.codes_fnv = ctx ? 0 : fnv;
+	if (stats) *stats = st;
+	if (err.failed()) { td_io_set_error(err.message()); return TD_FAIL; }
+	return TD_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1123,10 +1285,63 @@ std::string record_name(const Batch& b, int64_t i)
 	return std::string();
 }
 
-struct Tuple {                        // record range [k * batch_reads, ...) of every input file
-	std::vector<Batch*> b;
-	std::vector<std::vector<int64_t>> tickets;   // [file][device]
+// what the architectures and contexts of the input files say about the run (barcode_hmm.c:105-153)
+struct MultiPlan {
+	int bar_file = -1;                // the file that holds the barcode (at most one may), -1: none
+	int num_out_reads = 0;            // read segments over all files
+	int n_art = 0;                    // files whose contexts have a -ref artifact filter: none or all
+	std::vector<int> read_present;    // read segments of every file
+	std::vector<char> rna;            // run_rna_dust on the file's devices (TD_MODE_RNA_DUST)
 };
+
+// false: the files cannot make a run (td_io_set_error says why)
+bool plan_multi(const td_stream_file* files, const int K, const int N, const int32_t dust, MultiPlan& m)
+{
+	m.read_present.assign((size_t)K, 0);
+	m.rna.assign((size_t)K, 0);
+	for (int k = 0; k < K; k++) {
+		const td_arch* a = files[k].arch;
+		if (!files[k].path || !a || a->n_segments < 1) { td_io_set_error("td_stream_run_multi: every input file needs a path and an architecture"); return false; }
+		bool has_bar = false;
+		for (int j = 0; j < a->n_segments; j++) { if (a->type[j] == 'B') has_bar = true; if (a->type[j] == 'R') m.read_present[(size_t)k]++; }
+		if (has_bar) {
+			if (m.bar_file >= 0) { td_io_set_error("td_stream_run_multi: barcodes seem to be in both architectures (barcode_hmm.c:140-145)"); return false; }
+			m.bar_file = k;
+		}
+		m.num_out_reads += m.read_present[(size_t)k];
+		// run_rna_dust (barcode_hmm.c:315-319) is what the controller runs instead of the HMM for an architecture that is one read segment
+		const bool one_read = a->n_segments == 1 && a->type[0] == 'R';
+		if (!files[k].ctx) {
+			if (!one_read) { td_io_set_error("td_stream_run_multi: a file without contexts must have the architecture R:N"); return false; }
+		} else {
+			for (int d = 0; d < N; d++) if (!files[k].ctx[d]) { td_io_set_error("td_stream_run_multi: NULL context"); return false; }
+			m.rna[(size_t)k] = one_read;
+			m.n_art += artifacts_active(files[k].ctx[0]);
+			if (one_read) {   // the devices run the DUST of this call
+				int32_t cd = 0;
+				(void)td_get_option(files[k].ctx[0], "dust", &cd);
+				if (cd != dust) {
+					td_io_set_error(std::string("td_stream_run_multi: ") + files[k].path + " (R:N) has contexts with dust " + std::to_string(cd) +
+					                ", the call has dust " + std::to_string(dust));
+					return false;
+				}
+			}
+		}
+	}
+	// -ref (hmm_controller_multiple, barcode_hmm.c:209-214, :313-325): the controller hands the one FASTA to every file's step
+	if (m.n_art > 0) {
+		for (int k = 0; k < K; k++) {
+			if (!files[k].ctx) {
+				td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set, but ") + files[k].path +
+				                " (R:N) has no contexts: its reads must be filtered too (give it contexts: TD_MODE_RNA_DUST)");
+				return false;
+			}
+			if (!artifacts_active(files[k].ctx[0])) { td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set for some files but not for ") + files[k].path); return false; }
+		}
+	}
+	if (m.num_out_reads == 0) { td_io_set_error("td_stream_run_multi: no read segment in any architecture: no output files to create (io.c:846-852)"); return false; }
+	return true;
+}
 
 } // namespace
 
@@ -1136,278 +1351,91 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 	if (!files || n_files < 1 || n_files > 8 || !out_prefix) { td_io_set_error("td_stream_run_multi: bad arguments (1..8 input files, an output prefix)"); return TD_FAIL; }
 	if (n_devices < 1) n_devices = 1;
 	const int K = n_files, N = n_devices;
-	// barcode_hmm.c:105-153: which file holds the barcode (at most one may), how many read segments every file contributes
-	int bar_file = -1, num_out_reads = 0;
-	std::vector<int> read_present((size_t)K, 0);
-	std::vector<char> rna((size_t)K, 0);          // run_rna_dust on the file's devices (TD_MODE_RNA_DUST)
-	int n_art = 0;
-	for (int k = 0; k < K; k++) {
-		const td_arch* a = files[k].arch;
-		if (!files[k].path || !a || a->n_segments < 1) { td_io_set_error("td_stream_run_multi: every input file needs a path and an architecture"); return TD_FAIL; }
-		bool has_bar = false;
-		for (int j = 0; j < a->n_segments; j++) { if (a->type[j] == 'B') has_bar = true; if (a->type[j] == 'R') read_present[(size_t)k]++; }
-		if (has_bar) {
-			if (bar_file >= 0) { td_io_set_error("td_stream_run_multi: barcodes seem to be in both architectures (barcode_hmm.c:140-145)"); return TD_FAIL; }
-			bar_file = k;
-		}
-		num_out_reads += read_present[(size_t)k];
-		// run_rna_dust (barcode_hmm.c:315-319) is what the controller runs instead of the HMM for an architecture that is one read segment
-		const bool one_read = a->n_segments == 1 && a->type[0] == 'R';
-		if (!files[k].ctx) {
-			if (!one_read) { td_io_set_error("td_stream_run_multi: a file without contexts must have the architecture R:N"); return TD_FAIL; }
-		} else {
-			for (int d = 0; d < N; d++) if (!files[k].ctx[d]) { td_io_set_error("td_stream_run_multi: NULL context"); return TD_FAIL; }
-			rna[(size_t)k] = one_read;
-			int32_t art = 0;
-			(void)td_get_option(files[k].ctx[0], "artifacts_active", &art);
-			n_art += art != 0;
-			if (one_read) {   // the devices run the DUST of this call
-				int32_t cd = 0;
-				(void)td_get_option(files[k].ctx[0], "dust", &cd);
-				if (cd != dust) {
-					td_io_set_error(std::string("td_stream_run_multi: ") + files[k].path + " (R:N) has contexts with dust " + std::to_string(cd) +
-					                ", the call has dust " + std::to_string(dust));
-					return TD_FAIL;
-				}
-			}
-		}
-	}
-	// -ref (hmm_controller_multiple, barcode_hmm.c:209-214, :313-325): the controller hands the one FASTA to every file's step
-	if (n_art > 0) {
-		for (int k = 0; k < K; k++) {
-			if (!files[k].ctx) {
-				td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set, but ") + files[k].path +
-				                " (R:N) has no contexts: its reads must be filtered too (give it contexts: TD_MODE_RNA_DUST)");
-				return TD_FAIL;
-			}
-			int32_t art = 0;
-			(void)td_get_option(files[k].ctx[0], "artifacts_active", &art);
-			if (!art) { td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set for some files but not for ") + files[k].path); return TD_FAIL; }
-		}
-	}
-	if (num_out_reads == 0) { td_io_set_error("td_stream_run_multi: no read segment in any architecture: no output files to create (io.c:846-852)"); return TD_FAIL; }
-	// print_all() names its files after param->read_structure: the barcode file's architecture, else the last file's
-	const td_arch* print_arch = files[bar_file >= 0 ? bar_file : K - 1].arch;
-	td_stream_opts o{};
-	if (opts) o = *opts;
-	if (o.batch_reads <= 0) o.batch_reads = n_art > 0 ? 1000001 : (1 << 18);   // (the filter's thread ranges: as td_stream_run)
-	if (o.block_bytes <= 0) o.block_bytes = (int64_t)64 << 20;
-	if (o.block_bytes < 4096) o.block_bytes = 4096;
-	int hw = (int)std::thread::hardware_concurrency();
-	if (hw < 1) hw = 1;
-	if (o.n_threads <= 0) o.n_threads = hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1);
-	if (o.n_threads > 32) o.n_threads = 32;
-	int32_t depth = 3;
-	for (int k = 0; k < K; k++) if (files[k].ctx) { (void)td_get_option(files[k].ctx[0], "pipeline_depth", &depth); break; }
+	MultiPlan m;
+	if (!plan_multi(files, K, N, dust, m)) return TD_FAIL;
+	const td_stream_opts o = resolve_opts(opts, m.n_art > 0);
+	td_ctx* first_ctx = nullptr;
+	for (int k = 0; k < K && !first_ctx; k++) if (files[k].ctx) first_ctx = files[k].ctx[0];
 	const double t_start = now_s();
 
-	// the writer's side lives in one Pipeline object (output files, write pool, statistics), the readers' in one per input file
-	Pipeline pw;
-	pw.o = o; pw.dry = false;
-	std::vector<std::unique_ptr<Pipeline>> pf;
-	for (int k = 0; k < K; k++) pf.emplace_back(new Pipeline());
-	const int n_batches = depth + 4;
-	auto fail_all = [&](const std::string& m) { pw.fail(m); for (auto& q : pf) q->fail(m); };
-	pw.ready.reset(new Queue<Batch*>(1)); pw.done.reset(new Queue<Batch*>(1)); pw.free_list.reset(new Queue<Batch*>(1));
-	{
-		std::vector<std::string> names;
-		td_writer_file_names_n(out_prefix, print_arch, num_out_reads, names, &pw.num_alternatives);
-		for (auto& nm : names) {
-			const int fd = open(nm.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-			if (fd < 0) { for (int g : pw.fds) close(g); td_io_set_error("td_stream_run_multi: cannot create " + nm + ": " + strerror(errno)); return TD_FAIL; }
-			pw.fds.push_back(fd);
-		}
-		pw.file_off.assign(pw.fds.size(), 0);
-	}
+	RunError err;
+	// print_all() names its files after param->read_structure: the barcode file's architecture, else the last file's
+	std::vector<std::string> names;
+	int num_alternatives = 2;
+	td_writer_file_names_n(out_prefix, files[m.bar_file >= 0 ? m.bar_file : K - 1].arch, m.num_out_reads, names, &num_alternatives);
+	Writer w(err, o.n_threads, num_alternatives);
+	std::string why;
+	if (!w.open(names, why)) { td_io_set_error("td_stream_run_multi: cannot create " + why); return TD_FAIL; }
 	std::vector<size_t> file_base((size_t)K, 0);      // io.c:917-1001: c
-	{ size_t c = 0; for (int k = 0; k < K; k++) { file_base[(size_t)k] = c; c += (size_t)pw.num_alternatives * (size_t)read_present[(size_t)k]; } }
-	pw.write_pool.reset(new Pool(o.n_threads));
-	const int parse_threads = std::max(1, o.n_threads / K);
-	int rc = TD_OK;
-	for (int k = 0; k < K && rc == TD_OK; k++) {
-		Pipeline& p = *pf[(size_t)k];
-		p.o = o; p.dry = files[k].ctx == nullptr;       // (a file that is not decoded needs no page-locked buffers)
-		p.want_seq = files[k].ctx != nullptr && !rna[(size_t)k];   // (nor one whose reads come back unchanged)
-		p.ready.reset(new Queue<Batch*>((size_t)n_batches));
-		p.done.reset(new Queue<Batch*>((size_t)n_batches));
-		p.free_list.reset(new Queue<Batch*>((size_t)n_batches));
-		std::string err;
-		if (!p.src.open(files[k].path, o.block_bytes, err)) { td_io_set_error(err); rc = TD_FAIL; break; }
-		p.parse_pool.reset(new Pool(parse_threads));
-		for (int b = 0; b < 2; b++) {
-			Batch* q = p.new_batch();
-			if (!q) { rc = TD_FAIL; td_io_set_error("td_stream_run_multi: page-locked memory exhausted"); break; }
-			p.free_list->push(q);
-		}
-	}
-	if (rc != TD_OK) {
-		for (int g : pw.fds) close(g);
-		for (auto& q : pf) release_batches(*q, false);
-		return TD_FAIL;
-	}
-	std::vector<std::thread> th_alloc, th_prod;
+	{ size_t c = 0; for (int k = 0; k < K; k++) { file_base[(size_t)k] = c; c += (size_t)num_alternatives * (size_t)m.read_present[(size_t)k]; } }
+	std::vector<std::unique_ptr<Reader>> readers;
+	std::vector<Target> dev;
 	for (int k = 0; k < K; k++) {
-		Pipeline* p = pf[(size_t)k].get();
-		th_alloc.emplace_back([p, n_batches] { p->allocator(n_batches - 2); });
-		th_prod.emplace_back([p] { p->producer(); });
+		// (a file that is not decoded needs no page-locked buffers, nor does one whose reads come back unchanged need room for rewritten ones)
+		readers.emplace_back(new Reader(err, o, files[k].ctx == nullptr, files[k].ctx != nullptr && !m.rna[(size_t)k], std::max(1, o.n_threads / K)));
+		dev.push_back(Target{ files[k].ctx, m.rna[(size_t)k] != 0 });
+		if (!readers.back()->src.open(files[k].path, o.block_bytes, why)) { td_io_set_error(why); return TD_FAIL; }
 	}
-	Queue<Tuple*> done_t((size_t)n_batches);
-	int64_t cnt[TD_NUM_COUNTERS];
-	for (int q = 0; q < TD_NUM_COUNTERS; q++) cnt[q] = 0;
-	// ---- writer: run_rna_dust for the files that are not decoded, the per-record combination, print_all ----
-	std::thread t_write([&] {
-		Tuple* t = nullptr;
-		std::vector<int32_t> ctype, cbar;
-		while (done_t.pop(t)) {
-			const double t0 = now_s();
-			const int64_t n = t->b[0]->n;
-			for (int k = 0; k < K; k++) {
-				Batch* b = t->b[(size_t)k];
-				if (files[k].ctx && !rna[(size_t)k]) { b->seq_src = nullptr; continue; }
-				b->seq_src = b->codes;
-				if (files[k].ctx) continue;             // (TD_MODE_RNA_DUST ran on the file's devices)
-				const int64_t chunk = 16384, nch = (n + chunk - 1) / chunk;
-				pw.write_pool->run(nch, [&](int64_t c) {   // do_rna_dust, barcode_hmm.c:2370-2395 (no -ref filter: a run with one has contexts here)
-					for (int64_t i = c * chunk; i < std::min(n, (c + 1) * chunk); i++) {
-						td_read_result& r = b->res[i];
-						memset(&r, 0, sizeof r);
-						r.mapq = -1.0f; r.barcode = -1; r.fingerprint = -1;        // read_fasta_fastq's defaults, io.c:1698-1702
-						r.read_type = TD_EXTRACT_SUCCESS;
-						if (dust && rna_dust_low(b->codes + b->offs[i], b->offs[i + 1] - b->offs[i], dust)) r.read_type = TD_EXTRACT_FAIL_LOW_COMPLEXITY;
-					}
-				});
-			}
-			ctype.resize((size_t)n); cbar.resize((size_t)n);
-			for (int64_t i = 0; i < n; i++) {          // barcode_hmm.c:329-351
-				int32_t c = -100000;
-				for (int k = 0; k < K; k++) c = std::max(c, t->b[(size_t)k]->res[i].read_type);
-				ctype[(size_t)i] = c;
-				cbar[(size_t)i] = t->b[(size_t)(bar_file >= 0 ? bar_file : 0)]->res[i].barcode;
-				cnt[c & (TD_NUM_OUTCOME_SLOTS - 1)]++;                                      // the controller's counting, :354-384
-				if (c == TD_EXTRACT_SUCCESS && cbar[(size_t)i] >= 0) cnt[TD_NUM_OUTCOME_SLOTS + (cbar[(size_t)i] & 0xFF)]++;
-			}
-			bool ok = true;
-			for (int k = 0; k < K && ok; k++)
-				if (read_present[(size_t)k] > 0) ok = pw.write_batch(t->b[(size_t)k], ctype.data(), cbar.data(), file_base[(size_t)k]);
-			pw.st.n_reads += n; pw.st.n_batches++;
-			pw.st.write_s += now_s() - t0;
-			for (int k = 0; k < K; k++) { t->b[(size_t)k]->pieces.clear(); t->b[(size_t)k]->seq_src = nullptr; (void)pf[(size_t)k]->free_list->push(t->b[(size_t)k]); }
-			delete t;
-			if (!ok) return;
-		}
-		const double t0 = now_s();
-		(void)pw.append_wait(-1);
-		pw.st.write_s += now_s() - t0;
-	});
-	// ---- the calling thread: one record range of every file at a time, `depth` of them on the devices ----
-	std::deque<Tuple*> flying;
-	auto retire = [&]() -> bool {
-		Tuple* t = flying.front();
-		flying.pop_front();
-		const double t0 = now_s();
-		bool ok = true;
-		for (int k = 0; k < K; k++)
-			for (int d = 0; d < N; d++)
-				if (files[k].ctx && t->tickets[(size_t)k][(size_t)d] && td_wait(files[k].ctx[d], t->tickets[(size_t)k][(size_t)d]) != TD_OK) {
-					if (ok) fail_all(std::string("td_stream_run_multi: ") + td_last_error(files[k].ctx[d]));
-					ok = false;
-				}
-		pw.st.decode_s += now_s() - t0;
-		if (!ok) { delete t; return false; }
-		return done_t.push(t);
-	};
+
+	// barcode_hmm.c:257-289: the files hold the same number of records, and the first 1000 names of every pair of files name the same reads
 	bool first = true;
 	int name_format = -1;
-	while (!pw.failed()) {
-		Tuple* t = new Tuple();
-		t->b.assign((size_t)K, nullptr);
-		t->tickets.assign((size_t)K, std::vector<int64_t>((size_t)N, 0));
-		int n_closed = 0;
-		bool bad = false;
-		for (int k = 0; k < K && !bad; k++) {
-			for (;;) {   // (nothing ready from this file and record ranges in flight: retire the oldest -- its buffers may be what the reader waits for)
-				Batch* b = nullptr;
-				const int got = flying.empty() ? (pf[(size_t)k]->ready->pop(b) ? 1 : -1) : pf[(size_t)k]->ready->try_pop(b);
-				if (got == 1) { t->b[(size_t)k] = b; break; }
-				if (got < 0) { n_closed++; break; }
-				if (!retire()) { bad = true; break; }
+	auto check = [&](const Tuple& t) -> std::string {
+		for (int k = 0; k < K; k++)
+			if (!t.b[(size_t)k] || t.b[(size_t)k]->n != t.b[0]->n) return "td_stream_run_multi: the input files differ in their number of records";
+		if (!first) return std::string();
+		first = false;
+		for (int64_t i = 0; i < std::min<int64_t>(1000, t.b[0]->n); i++) {
+			const std::string na = record_name(*t.b[0], i);
+			for (int k = 1; k < K; k++) {
+				const std::string nb = record_name(*t.b[(size_t)k], i);
+				if (names_differ(na, nb, name_format)) return "td_stream_run_multi: the input files seem to contain reads in different order: " + na + " / " + nb;
 			}
 		}
-		if (bad || n_closed == K) { for (Batch* b : t->b) if (b) (void)b; delete t; break; }
-		bool same_n = n_closed == 0;
-		for (int k = 1; k < K && same_n; k++) same_n = t->b[(size_t)k]->n == t->b[0]->n;
-		if (!same_n) {   // barcode_hmm.c:257-268
-			fail_all("td_stream_run_multi: the input files differ in their number of records");
-			delete t;
-			break;
+		return std::string();
+	};
+	// the write stage: run_rna_dust for the files that no device sees, the per-record combination, print_all
+	int64_t cnt[TD_NUM_COUNTERS];
+	for (int q = 0; q < TD_NUM_COUNTERS; q++) cnt[q] = 0;
+	std::vector<int32_t> ctype, cbar;
+	auto write = [&](Tuple& t) -> bool {
+		const int64_t n = t.b[0]->n;
+		for (int k = 0; k < K; k++) {
+			Batch* b = t.b[(size_t)k];
+			if (files[k].ctx && !m.rna[(size_t)k]) { b->seq_src = nullptr; continue; }
+			b->seq_src = b->codes;
+			if (files[k].ctx) continue;             // (TD_MODE_RNA_DUST ran on the file's devices)
+			const int64_t chunk = 16384, nch = (n + chunk - 1) / chunk;
+			w.pool.run(nch, [&](int64_t c) {        // do_rna_dust, barcode_hmm.c:2370-2395 (no -ref filter: a run with one has contexts here)
+				for (int64_t i = c * chunk; i < std::min(n, (c + 1) * chunk); i++) {
+					td_read_result& r = b->res[i];
+					memset(&r, 0, sizeof r);
+					r.mapq = -1.0f; r.barcode = -1; r.fingerprint = -1;        // read_fasta_fastq's defaults, io.c:1698-1702
+					r.read_type = TD_EXTRACT_SUCCESS;
+					if (dust && rna_dust_low(b->codes + b->offs[i], b->offs[i + 1] - b->offs[i], dust)) r.read_type = TD_EXTRACT_FAIL_LOW_COMPLEXITY;
+				}
+			});
 		}
-		const int64_t n = t->b[0]->n;
-		if (first) {     // the first 1000 names of every pair of files name the same reads (barcode_hmm.c:272-289)
-			first = false;
-			bool differ = false;
-			std::string na, nb;
-			for (int64_t i = 0; i < std::min<int64_t>(1000, n) && !differ; i++) {
-				na = record_name(*t->b[0], i);
-				for (int k = 1; k < K && !differ; k++) { nb = record_name(*t->b[(size_t)k], i); differ = names_differ(na, nb, name_format); }
-			}
-			if (differ) { fail_all("td_stream_run_multi: the input files seem to contain reads in different order: " + na + " / " + nb); delete t; break; }
+		ctype.resize((size_t)n); cbar.resize((size_t)n);
+		for (int64_t i = 0; i < n; i++) {          // barcode_hmm.c:329-351
+			int32_t c = -100000;
+			for (int k = 0; k < K; k++) c = std::max(c, t.b[(size_t)k]->res[i].read_type);
+			ctype[(size_t)i] = c;
+			cbar[(size_t)i] = t.b[(size_t)(m.bar_file >= 0 ? m.bar_file : 0)]->res[i].barcode;
+			cnt[c & (TD_NUM_OUTCOME_SLOTS - 1)]++;                                      // the controller's counting, :354-384
+			if (c == TD_EXTRACT_SUCCESS && cbar[(size_t)i] >= 0) cnt[TD_NUM_OUTCOME_SLOTS + (cbar[(size_t)i] & 0xFF)]++;
 		}
-		if ((int)flying.size() >= depth && !retire()) { delete t; break; }
-		const double t0 = now_s();
 		bool ok = true;
-		for (int k = 0; k < K && ok; k++) {
-			if (!files[k].ctx) continue;
-			Batch* b = t->b[(size_t)k];
-			for (int d = 0; d < N && ok; d++) {      // run_pHMM's contiguous ranges over the devices (barcode_hmm.c:1911-1922)
-				const int64_t interval = n / N, lo = (int64_t)d * interval, hi = (d == N - 1) ? n : lo + interval;
-				if (hi <= lo) continue;
-				// the artifact filter's thread ranges are those of the whole batch, not of a device's range
-				if (N > 1 && td_set_batch_window(files[k].ctx[d], lo, n) != TD_OK) {
-					fail_all(std::string("td_stream_run_multi: ") + td_last_error(files[k].ctx[d]));
-					ok = false;
-					break;
-				}
-				const bool r = rna[(size_t)k] != 0;
-				if (td_submit(files[k].ctx[d], b->codes, 0, b->offs + lo, hi - lo, r ? TD_MODE_RNA_DUST : TD_MODE_GET_LABEL, b->res + lo, nullptr,
-				              r ? nullptr : b->seq_out + b->offs[lo], &t->tickets[(size_t)k][(size_t)d]) != TD_OK) {
-					fail_all(std::string("td_stream_run_multi: ") + td_last_error(files[k].ctx[d]));
-					ok = false;
-				}
-			}
-		}
-		pw.st.decode_s += now_s() - t0;
-		flying.push_back(t);
-		if (!ok) break;
-	}
-	while (!flying.empty() && !pw.failed()) if (!retire()) break;
-	if (pw.failed()) {   // nothing of ours may stay queued on the devices
-		for (Tuple* t : flying) {
-			for (int k = 0; k < K; k++) for (int d = 0; d < N; d++) if (files[k].ctx && t->tickets[(size_t)k][(size_t)d]) (void)td_wait(files[k].ctx[d], t->tickets[(size_t)k][(size_t)d]);
-			delete t;
-		}
-		flying.clear();
-		done_t.abort();
-	}
-	done_t.close();
-	t_write.join();
-	pw.append_stop();
-	if (N > 1) for (int k = 0; k < K; k++) if (files[k].ctx) for (int d = 0; d < N; d++) (void)td_set_batch_window(files[k].ctx[d], 0, 0);
-	for (int k = 0; k < K; k++) {
-		Pipeline& p = *pf[(size_t)k];
-		if (pw.failed()) p.fail(pw.err);
-		th_prod[(size_t)k].join();
-		{ std::lock_guard<std::mutex> lk(p.all_mu); p.stop_alloc = true; }
-		p.hint_cv.notify_all();
-		p.free_list->abort();
-		th_alloc[(size_t)k].join();
-		pw.st.bytes_in += p.st.bytes_in; pw.st.parse_s += p.st.parse_s; pw.st.read_s += p.st.read_s;
-		if (p.failed() && !pw.failed()) pw.fail(p.err);
-	}
-	for (int fd : pw.fds) if (close(fd) != 0 && !pw.failed()) pw.fail(std::string("td_stream_run_multi: close failed: ") + strerror(errno));
-	for (auto& q : pf) release_batches(*q, !pw.failed());
-	pw.st.wall_s = now_s() - t_start;
-	if (stats) *stats = pw.st;
+		for (int k = 0; k < K && ok; k++)
+			if (m.read_present[(size_t)k] > 0) ok = w.write_batch(t.b[(size_t)k], ctype.data(), cbar.data(), file_base[(size_t)k]);
+		for (Batch* b : t.b) b->seq_src = nullptr;
+		return ok;
+	};
+	td_stream_stats st{};
+	run_stages("td_stream_run_multi: ", err, readers, dev, N, pipeline_depth(first_ctx), &w, check, write, st);
+	st.wall_s = now_s() - t_start;
+	if (stats) *stats = st;
 	if (counts) for (int q = 0; q < TD_NUM_COUNTERS; q++) counts[q] = cnt[q];
-	if (pw.failed()) { td_io_set_error(pw.err); return TD_FAIL; }
+	if (err.failed()) { td_io_set_error(err.message()); return TD_FAIL; }
 	return TD_OK;
 }

@@ -111,6 +111,34 @@ def test_truncated_gz_is_an_error(tmp_path):
         tdlib.stream_run(None, gz, batch_reads=500, n_threads=2, block_bytes=8192)
 
 
+def test_multi_file_run_reports_the_failing_files_own_error(tmp_path):
+    """td_stream_run_multi on two files of which the second is a .gz cut in half: the run ends with that file's error (zcat's
+    status), not with "the input files differ in their number of records", which is only what the device stage sees of it.
+    The same two files intact run through; two intact files of different lengths still get the count message.  (R:N files
+    without contexts: run_rna_dust on the host, no device needed.)"""
+    from tagdust_amd import lib as tdlib
+    from tagdust_amd import TdError
+    text = _ugly_fastq(4000, 21)
+    r1, r2, cut, short = (str(tmp_path / n) for n in ("r1.fq", "r2.fq.gz", "cut.fq.gz", "short.fq"))
+    open(r1, "wb").write(text)
+    with gzip.open(r2, "wb") as fh:
+        fh.write(text)
+    data = open(r2, "rb").read()
+    open(cut, "wb").write(data[: len(data) // 2])
+    open(short, "wb").write(_ugly_fastq(3500, 21))
+    opts = dict(batch_reads=500, n_threads=2, block_bytes=8192)
+
+    def run(second):
+        return tdlib.stream_run_multi([(r1, ["R:N"], None), (second, ["R:N"], None)], str(tmp_path / "out"), **opts)
+
+    with pytest.raises(TdError, match="zcat.*failed.*truncated or corrupt input"):
+        run(cut)
+    st, _ = run(r2)
+    assert st["n_reads"] == 4000 and st["n_reads"] == tdlib.stream_run(None, r1, **opts)["n_reads"]
+    with pytest.raises(TdError, match="differ in their number of records"):
+        run(short)
+
+
 def test_pipeline_with_too_few_batch_buffers_does_not_hang(tmp_path):
     """Page-locking can fail part-way (memlock limit, container): the helper thread that adds batch buffers then stops and the
     pipeline runs with what it has.  With fewer batches than the in-flight depth + 2 it used to wait forever (reader for a free

@@ -1,10 +1,10 @@
 #!/bin/bash
-# The streaming pipeline (csrc/td_stream.cpp: reader/parser thread, writer thread, two thread pools, the caller's thread) under
+# The streaming pipeline (csrc/td_stream.cpp: reader/parser threads, writer thread, appender thread, their pools, the caller's thread) under
 # ThreadSanitizer on the CPU: td_stream.cpp + td_fastq.cpp as they are, the device entry points replaced by stand-ins
 # (tools/tsan_stream/stub.cpp), a 60 000-read ragged FASTQ file in batches of 777 reads and blocks of 20 KB -- parse-only and
 # with the stubbed decode + real formatting / appends, each twice (the second run reuses the cached batch buffers), and the
 # multi-file pipeline (td_stream_run_multi: two input files in lock-step, two "devices", one file not decoded).
-# usage: tools/tsan_stream.sh      (prints the result lines, the last one of a run into a full disk; any ThreadSanitizer report goes to stderr)
+# usage: tools/tsan_stream.sh      (prints the result lines, the last two of runs into a full disk; any ThreadSanitizer report goes to stderr)
 set -e
 cd "$(dirname "$0")/.."
 OUT=/tmp/td_tsan
@@ -21,6 +21,7 @@ cd $OUT
 for mode in "" decode multi; do ./tsan_stream in.fq 777 4 20000 $mode; done
 # a full disk: every output file a link to /dev/full -- the appender thread's pwrite fails, the run must end with TD_FAIL and
 # "write failed" (not hang, not report success)
-for f in out_*.fq; do rm -f $f; ln -s /dev/full $f; done
+for f in out_*.fq outm_*.fq; do rm -f $f; ln -s /dev/full $f; done
 timeout 120 ./tsan_stream in.fq 777 4 20000 decode | head -1
-rm -f out_*.fq
+timeout 120 ./tsan_stream in.fq 777 4 20000 multi | head -1     # (the same through the multi-file run's teardown)
+rm -f out_*.fq outm_*.fq
