@@ -207,6 +207,7 @@ struct td_ctx {
 	std::vector<float> m_trans;
 	// deep copy of the uploaded description (a batch with very long reads recompiles the kernel with the clamped logsum)
 	td_model_desc m_desc{};
+	TdSpecPlan plan;            // what the specialised kernel is for m_desc, under the TD_SPEC_* knobs as they stood at the upload
 	std::vector<float> m_skip, m_eM, m_eI, m_sM, m_sI, m_A;
 	std::vector<int8_t> m_seg_type;
 	std::vector<int32_t> m_finger_len;
@@ -425,7 +426,7 @@ static int load_spec_kernel(td_ctx* c, int lsum_oob, int window = -1)
 	c->spec_fn = nullptr; c->spec_ready = false;
 	std::vector<char> code;
 	std::string log;
-	if (td_spec_compile(&c->m_desc, code, log, lsum_oob, window) != TD_OK) return fail(c, "td_model_upload: specialised kernel did not compile: %.400s", log.c_str());
+	if (td_spec_compile(&c->m_desc, c->plan, lsum_oob, window, code, log) != TD_OK) return fail(c, "td_model_upload: specialised kernel did not compile: %.400s", log.c_str());
 	HIPCHK(c, hipModuleLoadData(&c->spec_mod, code.data()));
 	HIPCHK(c, hipModuleGetFunction(&c->spec_fn, c->spec_mod, "td_spec_kernel"));
 	// lsum() as compiled against the reference's formula on the operand pairs that matter (either or both operands -inf,
@@ -450,7 +451,7 @@ static int load_spec_kernel(td_ctx* c, int lsum_oob, int window = -1)
 		struct { const float* logsum; const float* pairs; int n; int pad; int* bad; } a = { c->d_logsum, d_pairs, n_pairs, 0, d_bad };
 		size_t sz = sizeof a;
 		void* cfg[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END };
-		const int block = td_spec_block_threads();
+		const int block = c->plan.k.block;
 		hipError_t e = n_pairs <= block ? hipModuleLaunchKernel(chk, 1, 1, 1, (unsigned)block, 1, 1, 0, c->stream, nullptr, cfg) : hipErrorInvalidValue;
 		if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 		if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost);
@@ -620,8 +621,9 @@ extern "C" int td_model_upload(td_ctx* c, const td_model_desc* m)
 		scan(m->trans, (size_t)m->C * 9); scan(m->eM, (size_t)m->C * 5); scan(m->eI, (size_t)m->C * 5);
 		scan(m->sM, m->C); scan(m->sI, m->C); scan(m->skip, m->S); scan(m->bg, 5);
 		c->m_maxabs = mx;
-		if (load_spec_kernel(c, c->spec_oob_unsafe ? 0 : td_spec_lsum_oob()) != TD_OK) return TD_FAIL;
-		c->spec_block = td_spec_block_threads();
+		c->plan = td_spec_plan(&c->m_desc, td_spec_knobs());
+		if (load_spec_kernel(c, c->spec_oob_unsafe ? 0 : c->plan.k.lsum_oob) != TD_OK) return TD_FAIL;
+		c->spec_block = c->plan.k.block;
 		// resident waves per CU: two LDS tables fit a CU; a 1024-thread workgroup fills it alone
 		{
 			const int wpb = c->spec_block / TD_WAVE;
@@ -630,7 +632,7 @@ extern "C" int td_model_upload(td_ctx* c, const td_model_desc* m)
 			if (blocks_per_cu < 1) blocks_per_cu = 1;
 			c->spec_waves_per_cu = blocks_per_cu * wpb;
 		}
-		const int by_regs = 4 * td_spec_min_waves();
+		const int by_regs = 4 * c->plan.k.min_waves;
 		if (c->spec_waves_per_cu > by_regs) c->spec_waves_per_cu = by_regs;
 	}
 	c->have_model = true;
@@ -699,7 +701,7 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	// which fast paths the model / the last batch actually got (read-only)
 	if (!strcmp(name, "prune_active")) {
 		// the loaded specialised kernel prunes by position AND the bound tables of the last batch's geometry are live
-		*value = c->spec_ready && c->prune_live && (td_spec_prune_segs(&c->m_desc) > 0 || td_spec_prune_sfx(&c->m_desc) < c->m_desc.S);
+		*value = c->spec_ready && c->prune_live && (c->plan.prune_segs > 0 || c->plan.sfx_first < c->plan.S);
 		return TD_OK;
 	}
 	if (!strcmp(name, "overlap_active")) {
@@ -868,22 +870,18 @@ static int ensure_workspace(td_ctx* c, TdSlot& s)
 		if (load_spec_kernel(c, 0) != TD_OK) return TD_FAIL;   // reads this long need the clamped logsum (seconds, once)
 	}
 	if (c->spec_ready) {
-		td_model_desc md{};
-		md.S = c->hdr.S; md.H = c->hdr.H; md.C = c->hdr.C;
-		md.n_hmm = c->m_n_hmm.data(); md.n_col = c->m_n_col.data(); md.trans = c->m_trans.data();
-		td_spec_layout(s.slay, &md, s.n_long > 0 ? s.lmax_small : s.lmax);   // the geometry of the many
-		td_spec_layout(s.slay_big, &md, s.lmax);
+		td_spec_layout(s.slay, c->plan, s.n_long > 0 ? s.lmax_small : s.lmax);   // the geometry of the many
+		td_spec_layout(s.slay_big, c->plan, s.lmax);
 		slot_bytes = s.slay.slot_bytes;
 		if (s.lmax > c->prune_lcap || !c->d_prune) {
 			// bound tables of the position pruning, for reads up to lcap bases (kernels in flight read the old ones)
 			HIPCHK(c, sync_compute(c));
 			const int lcap = (s.lmax + 2 + 255) / 256 * 256, stride = lcap + 24;   // (the scans request TDS_SCAN_B = 16 entries at a time: spare entries behind lcap)
 			std::vector<float> tab;
-			const int ps = td_spec_prune_segs(&c->m_desc), sf = td_spec_prune_sfx(&c->m_desc);
 			// (the bound recurrences cost columns x positions on the host: for reads beyond 8192 bases the tables stay zero, which
 			// the kernel reads as "nothing can be pruned" -- every position violates the zero bound -- and decodes densely)
-			c->prune_live = (ps > 0 || sf < c->m_desc.S) && lcap <= 8192;
-			if (c->prune_live) td_spec_prune_tables(&c->m_desc, ps, sf, lcap, stride, tab);
+			c->prune_live = (c->plan.prune_segs > 0 || c->plan.sfx_first < c->plan.S) && lcap <= 8192;
+			if (c->prune_live) td_spec_prune_tables(&c->m_desc, c->plan, lcap, stride, tab);
 			else tab.assign((size_t)TD_PRUNE_TABLES * stride, 0.0f);
 			if (c->d_prune) { HIPCHK(c, hipFree(c->d_prune)); c->d_prune = nullptr; }
 			HIPCHK(c, hipMalloc((void**)&c->d_prune, tab.size() * sizeof(float)));

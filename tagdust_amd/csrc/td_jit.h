@@ -1,27 +1,61 @@
-// td_jit.h -- interface between the C-ABI layer (td_api.hip) and the model-specialised kernel builder (td_jit.hip)
+// td_jit.h -- interface between the C-ABI layer (td_api.hip) and the model-specialised kernel builder (td_jit.hip: plan, model
+// section, layout, compile + cache; td_spec_bounds.cpp: the bound tables)
 #pragma once
 #include <string>
 #include <vector>
 #include "../../include/tagdust_hip.h"
 #include "td_device.h"
 
-int td_spec_group_size(int n_hmm, int n_col, int target_override);
-int td_spec_pure_last(const td_model_desc* m, int j, int col_off);
-int td_spec_drop_m(const td_model_desc* m, int j, int col_off);      /* 1: the column before the pure last column spills I_backward only */
-int td_spec_rt_prefix(const td_model_desc* m, int j, int col_off, int8_t* base, float* hi, float* lo, float* nv);
-int td_spec_block_threads(void);
-int td_spec_min_waves(void);
-int td_spec_first_labels(const td_model_desc* m);   /* labels whose posteriors the forward sweep sums up itself (0: none) */
-int td_spec_prune_segs(const td_model_desc* m);    /* leading segments the forward sweep may cut short (0: none), td_spec_kernel.inc "Position pruning" */
-int td_spec_prune_sfx(const td_model_desc* m);     /* first trailing segment the backward sweep may cut short (S: none) */
-float td_spec_prune_z(const td_model_desc* m, int n_seg, int sfx_first);
+// The TD_SPEC_* environment knobs (DESIGN.md has the table).  They are read when a model is uploaded, or when a context-free
+// query is made, and hold for that model.
+struct TdSpecKnobs {
+	int block = 512;          // TD_SPEC_BLOCK: threads per workgroup, 64..1024 in multiples of 64
+	int min_waves = 4;        // TD_SPEC_MINWAVES: waves per SIMD of __launch_bounds__, 1..8
+	int lsum_oob = 1;         // TD_SPEC_LSUM_OOB: clamp-free logsum (LDS out-of-range reads as 0), see td_spec_kernel.inc.  The form a
+	                          // model starts with: a loaded kernel's own form is td_spec_compile's lsum_oob argument
+	int rt_min = 16;          // TD_SPEC_RT_MIN: HMMs a segment needs for the run-time HMM loop
+	int groupcols = 18;       // TD_SPEC_GROUPCOLS: columns swept together (> 0)
+	int groupcols_fwd = 12;   // TD_SPEC_GROUPCOLS_FWD: ... in the forward sweep (<= 0: as groupcols)
+	int prune = 1;            // TD_SPEC_PRUNE: position pruning
+	int prune_sfx = 1;        // TD_SPEC_PRUNE_SFX: ... of the trailing segments too
+	int restart = -1;         // TD_SPEC_RESTART: restarted sweeps (-1: by the size of the leading segments)
+	int firstseg = -1;        // TD_SPEC_FIRSTSEG: the first segment's labels as running sums (-1: when H > 32)
+	int trie_sh = 2;          // TD_SPEC_TRIE_SH: match columns HMMs of the first segment share in its backward sweep
+	int profile = 0;          // TD_SPEC_PROFILE: TDS_PROFILE
+	int prune_stats = -1;     // TD_SPEC_PRUNE_STATS: TDS_PRUNE_STATS (-1: the kernel's own default)
+	std::string extra_opts;   // TD_SPEC_EXTRA_OPTS: further compiler options, space separated
+};
+TdSpecKnobs td_spec_knobs(void);
+
 #define TD_PRUNE_TABLES 16   /* 8 position-pruning tables, then up to 4 + 4 impulse-response tables of the restarted sweeps */
 #define TD_PRUNE_RESTART_MAX 4   /* leading / trailing segments a restart can bridge */
-int td_spec_restart(const td_model_desc* m);   /* 1: the specialised kernel restarts the far sweeps of the pruned segments (TDS_RESTART) */
-void td_spec_prune_tables(const td_model_desc* m, int n_seg, int sfx_first, int lcap, int stride, std::vector<float>& tab);
-int td_spec_lsum_oob(void);      /* 1: clamp-free logsum (LDS out-of-range reads as 0), see td_spec_kernel.inc */
-std::string td_spec_model_section(const td_model_desc* m, int lsum_oob = -1, int window = 0);   /* lsum_oob < 0: td_spec_lsum_oob(); window: -start/-end support compiled in */
-std::string td_spec_full_source(const td_model_desc* m, int lsum_oob = -1, int window = 0);
-void td_spec_layout(TdSpecLayout& L, const td_model_desc* m, int lmax);
-std::string td_spec_cache_dir(void);   /* on-disk cache of compiled kernels ("" = off) */
-int td_spec_compile(const td_model_desc* m, std::vector<char>& code, std::string& log, int lsum_oob = -1, int window = 0);
+
+// What the kernel is for one model under one set of knobs: built once, read by the source generator, the workspace layout, the
+// bound tables and the C-ABI layer alike.
+struct TdSpecPlan {
+	TdSpecKnobs k;
+	int S = 0, H = 0, C = 0;
+	std::vector<int> col_off, hmm_off;       // [S] first column / first HMM (label) of a segment
+	std::vector<int> group, group_f;         // [S] HMMs swept together, backward / forward
+	std::vector<int> pure_last, drop_m;      // [S] the last column is not spilled / the one before it spills I_backward only
+	std::vector<int> bw_off;                 // [H] first stored half-column of an HMM
+	int64_t halves = 0;                      // stored half-columns (4 B per lane and position)
+	std::vector<int> rt, rt_b;               // [S] HMMs in the run-time loop of the sweeps / of the restarted sweeps' bridges
+	std::vector<int> base;                   // [C] ... the base their match column expects
+	std::vector<float> hi, lo, nv;           // [S] ... and its three emission values
+	bool trie_on = false;                    // suffix order of the first segment's backward sweep
+	int trie_sh = 1, trie_n_share = 0;
+	std::vector<int> trie_ord;
+	int first_n = 0;                         // labels whose posteriors the forward sweep sums up itself (0: none)
+	int prune_segs = 0;                      // leading segments the forward sweep may cut short (0: none)
+	int sfx_first = 0;                       // first trailing segment the backward sweep may cut short (S: none)
+	float prune_z = 0.0f;                    // zero-posterior margin
+	int restart = 0;                         // the kernel restarts the far sweeps of the pruned segments (TDS_RESTART)
+};
+TdSpecPlan td_spec_plan(const td_model_desc* m, const TdSpecKnobs& k);
+
+float td_spec_prune_z(const td_model_desc* m, int n_seg, int sfx_first);
+void td_spec_prune_tables(const td_model_desc* m, const TdSpecPlan& p, int lcap, int stride, std::vector<float>& tab);
+void td_spec_layout(TdSpecLayout& L, const TdSpecPlan& p, int lmax);
+// lsum_oob: the logsum form (the plan's k.lsum_oob unless the context had to fall back); window: -start/-end support compiled in
+int td_spec_compile(const td_model_desc* m, const TdSpecPlan& p, int lsum_oob, int window, std::vector<char>& code, std::string& log);

@@ -791,7 +791,11 @@ extern "C" int td_estimate_threshold(td_ctx* ctx, const td_arch* a, const td_seq
 	const bool overlap = getenv("TD_CAL_OVERLAP") ? atoi(getenv("TD_CAL_OVERLAP")) != 0 : true;
 	if (overlap && td_get_option(ctx, "specialize", &specialize) == TD_OK && specialize &&
 	    td_model_build(a, ssi, 0.05f, d, &scoring) == TD_OK) {
-		warm = std::thread([scoring] { std::vector<char> code; std::string log; (void)td_spec_compile(&scoring->desc, code, log); });
+		warm = std::thread([scoring] {
+			const TdSpecPlan plan = td_spec_plan(&scoring->desc, td_spec_knobs());
+			std::vector<char> code; std::string log;
+			(void)td_spec_compile(&scoring->desc, plan, plan.k.lsum_oob, 0, code, log);
+		});
 	}
 	td_calibration* cal = nullptr;
 	const int emitted = td_calibration_emit(a, ssi, d, seed, n_reads, rng, &cal);

@@ -136,7 +136,7 @@ def _long_reads(g, L, n, seed):
 @pytest.mark.parametrize("L", [1000, 3000, 8000])
 def test_bounds_dominate_on_long_reads(L):
     """Scores grow by ~1.4 nats per base, and half a float spacing per addition with them (2.4e-4 at |score| = 4096): the
-    bound tables carry a slack that grows with the magnitude of the bound (td_jit.hip row_slack / lse_up), so that they still
+    bound tables carry a slack that grows with the magnitude of the bound (td_spec_bounds.cpp row_slack / lse_up), so that they still
     dominate every value of the oracle's matrices on reads of thousands of bases -- maximum-emission inserts included, for
     which the bounds have no other slack.  Same for the starts of the restarted sweeps."""
     g = load_golden("c3_b6_s_r_p")
@@ -270,6 +270,57 @@ def test_pruning_on_ragged_short_and_dead_reads():
     assert np.array_equal(labels, olab) and np.array_equal(seq_after, oseq)
     for k in ("read_type", "barcode", "fingerprint"):
         assert np.array_equal(res[k], ores[k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("at_upload,later", [("0", "1"), ("1", "0")], ids=["uploaded-dense", "uploaded-pruned"])
+def test_prune_knob_holds_from_the_upload(at_upload, later):
+    """TD_SPEC_* knobs are read when the model is uploaded and hold for that model: a change of TD_SPEC_PRUNE after the upload
+    reaches neither the bound tables a longer batch makes the context rebuild (their capacity is a multiple of 256 bases) nor
+    "prune_active", which both keep describing the kernel that was compiled -- and the bytes are those of a context that had
+    the upload's value all along."""
+    from tagdust_amd import TagdustHip
+    g = load_golden("c3_b6_s_r_p")
+    seq_a, offs_a = g["seq"], g["offs"]
+    assert int(np.diff(offs_a).max()) < 254
+    rng = np.random.RandomState(31)
+    reads = []
+    for i in range(len(offs_a) - 1):
+        r = seq_a[offs_a[i]:offs_a[i + 1]]
+        reads.append(np.concatenate([r[:20], rng.randint(0, 4, rng.randint(60, 121)).astype(np.uint8), r[20:]]))   # (position 20: the read segment)
+    offs_b = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.int64)
+    seq_b = np.concatenate(reads)
+    assert int(np.diff(offs_b).max()) > 256
+
+    def run(c, seq, offs):
+        c.upload_batch(seq, offs)
+        c.run()
+        return c.download()
+
+    old = os.environ.get("TD_SPEC_PRUNE")
+    try:
+        os.environ["TD_SPEC_PRUNE"] = at_upload
+        c, ref = TagdustHip(0), TagdustHip(0)
+        try:
+            for x in (c, ref):
+                x.upload_model(g)
+                x.set_params(float(g["threshold"]), int(g["minlen"]), int(g["dust"]))
+            want = run(ref, seq_b, offs_b)
+            assert ref.get_option("prune_active") == int(at_upload)
+            run(c, seq_a, offs_a)
+            assert c.get_option("prune_active") == int(at_upload)
+            os.environ["TD_SPEC_PRUNE"] = later
+            got = run(c, seq_b, offs_b)
+            assert c.get_option("prune_active") == int(at_upload)
+            assert _same(got, want)
+        finally:
+            c.close()
+            ref.close()
+    finally:
+        if old is None:
+            os.environ.pop("TD_SPEC_PRUNE", None)
+        else:
+            os.environ["TD_SPEC_PRUNE"] = old
 
 
 _LONG_SEEDS = list(range(10)) + [455]     # 455: the architecture an alternative machine scheduler miscompiled (td_jit.hip, td_spec_compile)
