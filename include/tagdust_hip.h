@@ -132,7 +132,8 @@ int td_model_upload(td_ctx* ctx, const td_model_desc* model);
  * of as full device-side copies: the page-locked path then does strictly less host work and moves fewer bytes than the pageable one;
  * "compact_egress" 1 (default; env TD_COMPACT_EGRESS) = rewritten sequences travel as keep bits, labels as runs;
  * "length_classes_enabled" 1 (default; env TD_NO_LENGTH_CLASSES turns it off), "rle_cap", "debug_wait", "spec_lsum_limit" = test and
- * diagnosis knobs.  Every environment variable is read once, when the context is created. */
+ * diagnosis knobs;  "async_compile" (env TD_ASYNC_COMPILE, default 0; set before td_model_upload) and "spec_probe" (default 1): see
+ * td_spec_wait / td_spec_probe below.  Every environment variable is read once, when the context is created. */
 int td_set_option(td_ctx* ctx, const char* name, int32_t value);
 /* Read a setting back: "specialize", "pipeline_depth", "overlap_decode", or "spec_lsum_clamped" (1 when the loaded specialised kernel uses the clamped
  * logsum: the clamp-free form is only selected while model parameters x read length bound every score difference).
@@ -147,7 +148,11 @@ int td_set_option(td_ctx* ctx, const char* name, int32_t value);
  * "hw_queues" (hardware queues of the HIP runtime as far as the library can tell: the user's GPU_MAX_HW_QUEUES, else the 8 the
  * library asks for when it is loaded BEFORE the process's first HIP call, else the runtime's default 4) and "hw_queues_late" (1: the
  * runtime was already initialised when the library was loaded, so its request had no effect -- set GPU_MAX_HW_QUEUES=8 in the
- * environment instead; the pipelined calls keep six streams busy). */
+ * environment instead; the pipelined calls keep six streams busy);
+ * "async_compile", "spec_probe" (as set); "spec_state" (0 generic by choice; 1 compiling; 2 compiled, not yet handed over;
+ * 3 specialised kernel active; 4 rejected by the probe, generic in use; 5 compile failed); "spec_batches_generic" (decode launches
+ * on the generic kernel since the last td_model_upload); "spec_compiles_started" (process-wide count of hiprtc compiles actually
+ * started: cache hits and jobs shared between contexts do not count); "spec_probe_us" (microseconds the last probe took, 0: none ran). */
 int td_get_option(td_ctx* ctx, const char* name, int32_t* value);
 /* The HIP source td_model_upload would compile for this model (no GPU needed).  Returns its length; copies at
  * most cap-1 bytes + NUL into buf when buf != NULL. */
@@ -162,6 +167,41 @@ int td_spec_prune_info(const td_model_desc* model, int32_t lcap, float* tab, flo
  * = leading segments 0..3, then the first four trailing segments; *restart = 1 when the kernel compiled for this model restarts
  * its far sweeps (big leading segments; TD_SPEC_RESTART=0 / 1 forces it).  No GPU needed; for inspection and tests. */
 int td_spec_restart_info(const td_model_desc* model, int32_t lcap, float* tab, int32_t* restart);
+/* The probe: every load of a specialised kernel (a fresh compile, a code object from the disk cache, a mid-run variant) decodes
+ * TD_PROBE_READS reads made from the model description with the new kernel and with the generic ahead-of-time kernel, in
+ * TD_MODE_GET_LABEL under the fixed parameters below (no artifact filter; the window variant under the fixed window), on scratch
+ * buffers and scratch counters, both workspaces filled with 0xFF first.  A device kernel compares what a caller could see: every
+ * td_read_result field bit for bit, labels[0..len], the keep bits of the rewritten sequence over len, the outcome counters.  The
+ * specialised kernel takes over only when nothing differs; else one line on stderr names the probe, the cache key and the first
+ * differing read and field, the context goes on decoding with the generic kernel (about ten times slower, and correct) and
+ * td_model_upload still returns TD_OK.  The verdict is remembered per (code object, device) for the life of the process; the cache
+ * file stays, so that the next process rejects it in milliseconds.  Option "spec_probe" 0 skips the probe (A/B runs).
+ * td_spec_probe gives the reads themselves (host only, no GPU; a private fixed-seed generator that never touches rand()):
+ * offs[TD_PROBE_READS + 1] when offs != NULL, the base codes 0..4 into codes when cap holds them all; returns the number of bases
+ * (-1: bad description).  Reads that follow the architecture -- each HMM of every multi-HMM segment in turn, the most probable base
+ * of every match column, random bases where the emission is flat, read segments of a random length up to avg_len (at most 256) --
+ * mutated by substitutions, single-base insertions / deletions and N; one read in eight uniformly random; lengths ragged in every tile. */
+#define TD_PROBE_READS     256
+#define TD_PROBE_THRESHOLD 5.0f  /* Q: an architecture with little evidence per read (a two-base spacer) tops out near 7 */
+#define TD_PROBE_MINLEN    16
+#define TD_PROBE_DUST      100
+#define TD_PROBE_WIN_START 2      /* td_set_window(2, 34) for the window variant */
+#define TD_PROBE_WIN_END   34
+int64_t td_spec_probe(const td_model_desc* model, uint8_t* codes, int64_t cap, int64_t* offs);
+void td_spec_probe_params(float* threshold, int32_t* minlen, int32_t* dust, int32_t* matchstart, int32_t* matchend);
+/* Option "async_compile" 1 (env TD_ASYNC_COMPILE; default 0): td_model_upload uploads the tables, starts the hiprtc compile on a
+ * host thread and returns; td_run / td_submit decode with the generic kernel until the compiled kernel has been handed over.  The
+ * hand-over is polled, without blocking, when a batch is staged (td_batch_upload, td_batch_upload_ascii, td_submit) before any
+ * geometry is chosen -- never in td_run or td_batch_download: a resident batch is decoded by the kernel it was staged for.  It
+ * waits for the compute streams (outstanding tickets stay valid), loads the module, runs the logsum self-check (a failing
+ * clamp-free form sends the clamped compile back to the background) and the probe, and only then switches.  One compile per code
+ * object is in flight per process: contexts that upload the same architecture wait on the same job.  A new td_model_upload
+ * supersedes a pending job (its result may land in the caches, never in the context); td_ctx_destroy waits for the jobs the context
+ * started, so teardown may take as long as the compile -- the code object is in the disk cache afterwards.  The two mid-run reloads
+ * (clamped logsum for very long reads, window variant) stay synchronous.
+ * td_spec_wait blocks until the pending compile is finished and handed over: TD_OK when nothing is pending and when the probe
+ * rejected the kernel, TD_FAIL with the compiler's log when the compile failed (the next staging call fails the same way). */
+int td_spec_wait(td_ctx* ctx);
 /* -ref artifact filter, match_to_reference() src/barcode_hmm.c:2478-2583 (runs between extraction and DUST in
  * TD_MODE_GET_LABEL, before DUST in TD_MODE_RNA_DUST): string / s_index[n_seq+1] are struct fasta's fields as read_fasta() leaves them (io.c:1912-2001:
  * per sequence one 'X' byte followed by the base codes); filter_error = param->filter_error (-fe);

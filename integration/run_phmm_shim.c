@@ -78,6 +78,18 @@ static int delegate(const char* why, struct arch_bag* ab, struct model_bag* mb, 
 	return ref_run_pHMM(ab, mb, ri, param, reference_fasta, numseq, mode);
 }
 
+/* TAGDUST_HIP_ASYNC_COMPILE=1: the model-specialised kernel is compiled in the background and the first batches of a new
+ * architecture are decoded by the generic kernel meanwhile (option "async_compile", tagdust_hip.h) -- on every context. */
+static int set_async_compile(void)
+{
+	const char* a = getenv("TAGDUST_HIP_ASYNC_COMPILE");
+	int k, n = g_multi ? td_multi_size(g_multi) : 1;
+	if (!a || atoi(a) == 0) return TD_OK;
+	for (k = 0; k < n; k++)
+		if (td_set_option(g_multi ? td_multi_ctx(g_multi, k) : g_ctx, "async_compile", 1) != TD_OK) return TD_FAIL;
+	return TD_OK;
+}
+
 /* one context per device listed in TAGDUST_HIP_DEVICES (default: "0") behind a td_multi; context 0 of it also serves the
  * calls that run on one device only: architecture comparison, windowed scores */
 static int ensure_context(void)
@@ -111,10 +123,10 @@ static int ensure_context(void)
 		if (n == 0) { fprintf(stderr, "tagdust_hip: TAGDUST_HIP_DEVICES names no device\n"); return TD_FAIL; }
 		if (td_multi_create(dev, n, &g_multi) != TD_OK) { fprintf(stderr, "tagdust_hip: %s\n", td_multi_last_error(NULL)); return TD_FAIL; }
 		g_ctx = td_multi_ctx(g_multi, 0);
-		return TD_OK;
+		return set_async_compile();
 	}
 	if (td_ctx_create(0, &g_ctx) != TD_OK) { fprintf(stderr, "tagdust_hip: %s\n", td_last_error(NULL)); return TD_FAIL; }
-	return TD_OK;
+	return set_async_compile();
 }
 
 /* FNV-1a over everything that defines the model, so a rebuilt model_bag (calibration, "long sequence" realloc)

@@ -17,6 +17,8 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -73,6 +75,8 @@ struct TdStaged : TdRoute {
 	int is_ascii = 0;
 	bool sorted = false;      // device order differs from the caller's (reads of several lengths)
 	bool staged = false;      // inputs are packed on the device: td_run may launch
+	bool for_spec = false;    // ... and the workspace geometry is the specialised kernel's: a batch is decoded by the kernel it was staged
+	                          // for, also when a background compile is handed over between its upload and its td_run
 	bool raw_direct = false;  // the upload read the caller's page-locked buffer itself (no staging copy)
 	const uint8_t* raw_host = nullptr;   // the batch's bases on the host, valid until the batch has been waited for: the pinned staging
 	                                     // copy, or the caller's own page-locked buffer under the "stable_input" contract; else NULL
@@ -177,6 +181,74 @@ __attribute__((constructor)) static void td_want_hw_queues()
 	if (!g_hwq_late) setenv("GPU_MAX_HW_QUEUES", "8", 0);
 }
 
+// The description a background compile works on: its own copy (a context's m_desc points into the context's vectors).
+struct ModelCopy {
+	td_model_desc d{};
+	std::vector<int32_t> n_hmm, n_col, finger_len, label;
+	std::vector<float> skip, trans, eM, eI, sM, sI, A;
+	std::vector<int8_t> seg_type;
+	void assign(const td_model_desc* m)
+	{
+		n_hmm.assign(m->n_hmm, m->n_hmm + m->S); n_col.assign(m->n_col, m->n_col + m->S); skip.assign(m->skip, m->skip + m->S);
+		seg_type.assign(m->seg_type, m->seg_type + m->S); finger_len.assign(m->finger_len, m->finger_len + m->S);
+		trans.assign(m->trans, m->trans + (size_t)m->C * 9); eM.assign(m->eM, m->eM + (size_t)m->C * 5); eI.assign(m->eI, m->eI + (size_t)m->C * 5);
+		sM.assign(m->sM, m->sM + m->C); sI.assign(m->sI, m->sI + m->C);
+		label.assign(m->label, m->label + m->H); A.assign(m->A, m->A + (size_t)m->H * m->H);
+		d = *m;
+		d.n_hmm = n_hmm.data(); d.n_col = n_col.data(); d.skip = skip.data(); d.seg_type = seg_type.data(); d.finger_len = finger_len.data();
+		d.trans = trans.data(); d.eM = eM.data(); d.eI = eI.data(); d.sM = sM.data(); d.sI = sI.data(); d.label = label.data(); d.A = A.data();
+	}
+};
+
+// One background compile.  The worker calls td_spec_compile on the job's own copies and nothing else: it touches no context and no
+// device.  Contexts that want the same code object share the job (g_jobs, by cache key); whoever lets go of it last joins the
+// thread, and every context waits for its jobs before it goes (td_ctx_destroy), so no thread is ever detached.
+struct SpecJob {
+	uint64_t key = 0;
+	ModelCopy model;
+	TdSpecPlan plan;
+	int lsum_oob = 0, window = 0;
+	std::mutex mu;
+	std::condition_variable cv;
+	bool done = false;
+	int rc = TD_FAIL;
+	std::vector<char> code;
+	std::string log;
+	std::thread th;
+	void run()
+	{
+		std::vector<char> out;
+		std::string lg;
+		const int r = td_spec_compile(&model.d, plan, lsum_oob, window, out, lg);
+		std::lock_guard<std::mutex> lk(mu);
+		code.swap(out); log.swap(lg); rc = r; done = true;
+		cv.notify_all();
+	}
+	bool finished() { std::lock_guard<std::mutex> lk(mu); return done; }
+	void wait() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return done; }); }
+	~SpecJob() { if (th.joinable()) th.join(); }
+};
+static std::mutex g_jobs_mu;
+static std::map<uint64_t, std::weak_ptr<SpecJob>> g_jobs;   // by cache key: one compile per code object in flight per process
+
+// A process that ends with a context it never destroyed must not run the library's static destructors under a compile that is
+// still going: registered (once, with the first job -- so it runs before the destructors of the statics above and of the code
+// cache, which were constructed when the library was loaded), this waits for every job in flight.
+static void wait_for_all_spec_jobs()
+{
+	std::vector<std::shared_ptr<SpecJob>> live;
+	{
+		std::lock_guard<std::mutex> lk(g_jobs_mu);
+		for (auto& kv : g_jobs) if (auto j = kv.second.lock()) live.push_back(j);
+	}
+	for (auto& j : live) j->wait();
+}
+
+// what the probe said about a code object on a device, for the life of the process
+struct ProbeVerdict { int mismatches = 0, read = -1, field = -1; };
+static std::mutex g_probe_mu;
+static std::map<std::pair<uint64_t, int>, ProbeVerdict> g_probe_verdicts;
+
 struct td_ctx {
 	int device = 0;
 	int host_threads = default_host_threads();
@@ -216,6 +288,16 @@ struct td_ctx {
 	bool spec_oob_unsafe = false; // the clamp-free form failed its self-check once: never again in this context
 	float m_maxabs = 0.0f;      // largest |finite parameter|
 	int spec_block = 256, spec_waves_per_cu = 8;
+	// background compile and load-time probe (tagdust_hip.h, td_spec_wait / td_spec_probe)
+	int async_compile = 0;      // TD_ASYNC_COMPILE ["async_compile"]
+	int spec_probe = 1;         // ["spec_probe"]
+	int spec_state = 0;         // "spec_state" (1 / 2 are told apart when asked: is the job done?)
+	int batches_generic = 0;    // "spec_batches_generic"
+	int probe_us = 0;           // "spec_probe_us"
+	std::shared_ptr<SpecJob> job;                   // the compile this context waits for (nullptr: none)
+	int job_oob = 0, job_window = 0;                // ... and the variant it is
+	std::vector<std::shared_ptr<SpecJob>> retired;  // superseded jobs: never loaded, waited for when the context goes
+	std::string job_err;                            // the compiler's log of a failed background compile
 
 	// params
 	float threshold = 0.0f;
@@ -366,6 +448,7 @@ extern "C" int td_ctx_create(int device, td_ctx** out)
 	if (const char* e = getenv("TD_WS_CANDIDATES")) c->ws_candidates = atoi(e);
 	if (const char* e = getenv("TD_SPEC_LSUM_LIMIT")) c->lsum_limit = atof(e);
 	if (getenv("TD_SPEC_SELFCHECK_FAIL")) c->selfcheck_fail = 1;
+	if (const char* e = getenv("TD_ASYNC_COMPILE")) c->async_compile = atoi(e) != 0;
 	c->hbm_total = prop.totalGlobalMem;
 	init_logsum_host();
 	bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
@@ -388,6 +471,11 @@ static bool tickets_outstanding(const td_ctx* c);
 extern "C" void td_ctx_destroy(td_ctx* c)
 {
 	if (!c) return;
+	// the background compiles this context started (pending or superseded) finish first: as long as the compile at worst, and the
+	// code object is in the caches afterwards
+	if (c->job) { c->retired.push_back(c->job); c->job.reset(); }
+	for (auto& j : c->retired) j->wait();
+	c->retired.clear();
 	(void)hipSetDevice(c->device);
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	if (c->stream2) (void)hipStreamSynchronize(c->stream2);
@@ -418,15 +506,133 @@ extern "C" void td_ctx_destroy(td_ctx* c)
 // ---------------------------------------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------------------------------------
-// Compile (or fetch from the cache) and load the model-specialised kernel.  lsum_oob selects the clamp-free logsum.
-static int load_spec_kernel(td_ctx* c, int lsum_oob, int window = -1)
+static int ensure_prune_tables(td_ctx* c, int lmax);
+static double wall_ms();
+static inline int64_t align256(int64_t v);
+static void make_layout(TdWsLayout& L, int S, int H, int C, int lmax, int max_ncol);
+struct OutLayout { int64_t soa_stride, keep, labels, total; };
+static OutLayout out_layout(int64_t n_tiles, int lmax, int nw1);
+
+static const char* probe_field_name(int f)
 {
-	if (window < 0) window = c->match_len > 0;   // a context with a -start/-end window gets the kernel that can apply it
+	static const char* res[] = { "f_score", "b_score", "r_score", "bar_prob", "mapq", "read_type", "barcode", "fingerprint" };
+	if (f >= 0 && f < 8) return res[f];
+	return f == TD_PROBE_FIELD_LABELS ? "labels" : f == TD_PROBE_FIELD_SEQ ? "sequence" : f == TD_PROBE_FIELD_COUNTERS ? "counters" : "?";
+}
+
+// The whole-kernel probe (tagdust_hip.h, td_spec_probe): the loaded specialised kernel (c->spec_fn) and the generic kernel decode
+// the probe reads under the fixed probe parameters, on scratch buffers of their own; a device kernel compares what a caller could
+// see.  Nothing of the context's batches, slots or counters is touched.  The compute streams are idle when this runs.
+static int probe_spec_kernel(td_ctx* c, int window, ProbeVerdict& v)
+{
+	std::vector<int64_t> offs(TD_PROBE_READS + 1);
+	const int64_t n_bases = td_spec_probe(&c->m_desc, nullptr, 0, offs.data());
+	if (n_bases <= 0) return fail(c, "td_model_upload: the probe reads could not be made from this model");
+	std::vector<uint8_t> codes((size_t)n_bases);
+	(void)td_spec_probe(&c->m_desc, codes.data(), n_bases, nullptr);
+	const int n = TD_PROBE_READS, n_tiles = TD_PROBE_READS / TD_WAVE;
+	int lmax = 1;
+	for (int i = 0; i < n; i++) if (offs[(size_t)i + 1] - offs[(size_t)i] > lmax) lmax = (int)(offs[(size_t)i + 1] - offs[(size_t)i]);
+	const int nw2 = (lmax + 15) / 16, nw1 = (lmax + 31) / 32;
+	if (ensure_prune_tables(c, lmax) != TD_OK) return TD_FAIL;
+	TdWsLayout glay{};
+	make_layout(glay, c->hdr.S, c->hdr.H, c->hdr.C, lmax, c->hdr.max_ncol);
+	TdSpecLayout slay{};
+	td_spec_layout(slay, c->plan, lmax);
+	const int gwpb = td_kernel_block_threads() / TD_WAVE, swpb = c->plan.k.block / TD_WAVE;
+	const int gslots = (n_tiles + gwpb - 1) / gwpb * gwpb, sslots = (n_tiles + swpb - 1) / swpb * swpb;
+	const OutLayout ol = out_layout(n_tiles, lmax, nw1);
+	// one scratch allocation, carved up
+	int64_t o = 0;
+	auto carve = [&](int64_t bytes) { const int64_t at = o; o = align256(o + bytes); return at; };
+	const int64_t o_raw = carve(n_bases), o_offs = carve((int64_t)(n + 1) * 8), o_packed = carve((int64_t)n_tiles * (nw2 + nw1) * TD_WAVE * 4),
+	              o_lens = carve((int64_t)n * 4), o_outa = carve(ol.total), o_outb = carve(ol.total),
+	              o_cnt = carve((int64_t)2 * TD_COUNTER_WORDS * 8), o_cmp = carve(256), o_tile = carve(256);
+	const int64_t small_bytes = o;
+	const int64_t o_wsa = carve((int64_t)gslots * glay.slot_bytes), o_wsb = carve((int64_t)sslots * slay.slot_bytes);
+	uint8_t* d = nullptr;
+	HIPCHK(c, hipMalloc((void**)&d, (size_t)o));
+	struct Free { uint8_t* p; ~Free() { (void)hipFree(p); } } free_{ d };
+	hipStream_t st = c->stream;
+	HIPCHK(c, hipMemsetAsync(d, 0, (size_t)small_bytes, st));
+	HIPCHK(c, hipMemsetAsync(d + o_cmp, 0xFF, 256, st));   // "this tile agrees" = -1
+	HIPCHK(c, hipMemsetAsync(d + o_cmp, 0, 4, st));
+	HIPCHK(c, hipMemsetAsync(d + o_wsa, 0xFF, (size_t)(o - o_wsa), st));   // both workspaces poisoned: a read-before-write computes on NaNs
+	HIPCHK(c, hipMemcpyAsync(d + o_raw, codes.data(), (size_t)n_bases, hipMemcpyHostToDevice, st));
+	HIPCHK(c, hipMemcpyAsync(d + o_offs, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+	TdStageBatch sb{};
+	sb.raw = d + o_raw; sb.offs = (const int64_t*)(d + o_offs); sb.n_reads = n; sb.is_ascii = 0;
+	sb.n_tiles = n_tiles; sb.lmax = lmax; sb.nw2 = nw2; sb.nw1 = nw1;
+	sb.read_at = nullptr;   // the reads stay in the generator's order: ragged inside every tile
+	sb.packed = (uint32_t*)(d + o_packed); sb.lens = (int32_t*)(d + o_lens);
+	HIPCHK(c, td_stage_pack(sb, st));
+	unsigned long long* cnt_a = (unsigned long long*)(d + o_cnt);
+	unsigned long long* cnt_b = cnt_a + TD_COUNTER_WORDS;
+	const int64_t sst = ol.soa_stride / 4;
+	TdKernelArgs ka{};
+	ka.hdr = c->d_hdr; ka.cols = c->d_cols; ka.hinfo = c->d_hinfo; ka.pred_off = c->d_pred_off; ka.pred_idx = c->d_pred_idx; ka.logsum = c->d_logsum;
+	ka.packed = sb.packed; ka.lens = sb.lens;
+	ka.n_tiles = n_tiles; ka.n_slots = gslots; ka.lmax = lmax; ka.nw2 = nw2; ka.nw1 = nw1;
+	ka.mode = TD_MODE_GET_LABEL; ka.threshold = TD_PROBE_THRESHOLD; ka.minlen = TD_PROBE_MINLEN; ka.dust = TD_PROBE_DUST; ka.want_labels = 1;
+	if (window) { ka.win_start = TD_PROBE_WIN_START; ka.win_len = TD_PROBE_WIN_END - TD_PROBE_WIN_START; }
+	{
+		float* soa = (float*)(d + o_outa);
+		ka.out_f = soa; ka.out_b = soa + sst; ka.out_r = soa + 2 * sst; ka.out_bar = soa + 3 * sst; ka.out_q = soa + 4 * sst;
+		ka.out_type = (int32_t*)(soa + 5 * sst); ka.out_barcode = (int32_t*)(soa + 6 * sst); ka.out_finger = (int32_t*)(soa + 7 * sst);
+		ka.out_keep = (uint32_t*)(d + o_outa + ol.keep); ka.out_labels = (int8_t*)(d + o_outa + ol.labels);
+	}
+	ka.counters = cnt_a;
+	ka.ws = d + o_wsa; ka.lay = glay;
+	HIPCHK(c, td_launch_decode(&ka, st));
+	TdSpecArgs sa{};
+	sa.logsum = c->d_logsum; sa.packed = sb.packed; sa.lens = sb.lens;
+	sa.n_tiles = n_tiles; sa.n_slots = sslots; sa.lmax = lmax; sa.nw2 = nw2; sa.nw1 = nw1;
+	sa.mode = ka.mode; sa.threshold = ka.threshold; sa.minlen = ka.minlen; sa.dust = ka.dust;
+	sa.win_start = ka.win_start; sa.win_len = ka.win_len;
+	{
+		float* soa = (float*)(d + o_outb);
+		sa.out_f = soa; sa.out_b = soa + sst; sa.out_r = soa + 2 * sst; sa.out_bar = soa + 3 * sst; sa.out_q = soa + 4 * sst;
+		sa.out_type = (int32_t*)(soa + 5 * sst); sa.out_barcode = (int32_t*)(soa + 6 * sst); sa.out_finger = (int32_t*)(soa + 7 * sst);
+		sa.out_keep = (uint32_t*)(d + o_outb + ol.keep); sa.out_labels = (int8_t*)(d + o_outb + ol.labels);
+	}
+	sa.counters = cnt_b;
+	sa.ws = d + o_wsb; sa.lay = slay; sa.lay_big = slay;
+	sa.n_big = 0; sa.lmax_big = lmax; sa.out_lmax = lmax;
+	sa.prune = c->d_prune; sa.prune_stride = c->prune_stride;
+	sa.tile_next = (int32_t*)(d + o_tile);
+	{
+		size_t sz = sizeof sa;
+		void* cfg[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, &sa, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END };
+		HIPCHK(c, hipModuleLaunchKernel(c->spec_fn, (unsigned)(sslots / swpb), 1, 1, (unsigned)c->plan.k.block, 1, 1, 0, st, nullptr, cfg));
+	}
+	TdProbeCmp pc{};
+	pc.lens = sb.lens; pc.n_tiles = n_tiles; pc.lmax = lmax; pc.nw1 = nw1; pc.n_counters = TD_NUM_COUNTERS;
+	pc.soa_a = d + o_outa; pc.soa_b = d + o_outb; pc.soa_stride = ol.soa_stride;
+	pc.keep_a = ka.out_keep; pc.keep_b = sa.out_keep; pc.labels_a = ka.out_labels; pc.labels_b = sa.out_labels;
+	pc.counters_a = cnt_a; pc.counters_b = cnt_b;
+	pc.out = (int32_t*)(d + o_cmp);
+	HIPCHK(c, td_probe_compare(pc, st));
+	int32_t out[1 + 2 * (TD_PROBE_READS / TD_WAVE + 1)];
+	HIPCHK(c, hipMemcpyAsync(out, d + o_cmp, sizeof out, hipMemcpyDeviceToHost, st));
+	HIPCHK(c, hipStreamSynchronize(st));
+	// the bound tables were laid out for the probe's reads: the first batch lays them out for its own (as without a probe)
+	c->prune_lcap = 0; c->prune_live = false;
+	v = ProbeVerdict();
+	v.mismatches = out[0];
+	for (int w = 0; w <= n_tiles && v.read < 0; w++) if (out[1 + 2 * w] >= 0) { v.read = out[1 + 2 * w]; v.field = out[2 + 2 * w]; }
+	return TD_OK;
+}
+
+static int load_spec_kernel(td_ctx* c, int lsum_oob, int window = -1);
+static int start_spec_job(td_ctx* c, int lsum_oob, int window);
+
+// A compiled code object becomes the context's decode kernel: module load, logsum self-check, probe, spec_ready -- in that order.
+// The compute streams are idle.  background: a self-check that demands the clamped form sends that compile to the background
+// again (a hand-over) instead of compiling it here.  A kernel the probe rejects leaves the context on the generic kernel: TD_OK.
+static int install_spec_kernel(td_ctx* c, const std::vector<char>& code, uint64_t key, int lsum_oob, int window, bool background)
+{
 	if (c->spec_mod) { HIPCHK(c, hipModuleUnload(c->spec_mod)); c->spec_mod = nullptr; }
 	c->spec_fn = nullptr; c->spec_ready = false;
-	std::vector<char> code;
-	std::string log;
-	if (td_spec_compile(&c->m_desc, c->plan, lsum_oob, window, code, log) != TD_OK) return fail(c, "td_model_upload: specialised kernel did not compile: %.400s", log.c_str());
 	HIPCHK(c, hipModuleLoadData(&c->spec_mod, code.data()));
 	HIPCHK(c, hipModuleGetFunction(&c->spec_fn, c->spec_mod, "td_spec_kernel"));
 	// lsum() as compiled against the reference's formula on the operand pairs that matter (either or both operands -inf,
@@ -462,13 +668,123 @@ static int load_spec_kernel(td_ctx* c, int lsum_oob, int window = -1)
 			if (!lsum_oob) return fail(c, "td_model_upload: the compiled logsum differs from the reference formula on %d of %d operand pairs", bad, n_pairs);
 			fprintf(stderr, "tagdust_hip: clamp-free logsum failed its self-check on this device / toolchain (%d of %d pairs); using the clamped form\n", bad, n_pairs);
 			c->spec_oob_unsafe = true;
+			if (background) {
+				HIPCHK(c, hipModuleUnload(c->spec_mod));
+				c->spec_mod = nullptr; c->spec_fn = nullptr;
+				return start_spec_job(c, 0, window);
+			}
 			return load_spec_kernel(c, 0, window);
+		}
+	}
+	// the whole kernel against the generic one, once per (code object, device) and process
+	if (c->spec_probe) {
+		ProbeVerdict v;
+		bool known = false;
+		{
+			std::lock_guard<std::mutex> lk(g_probe_mu);
+			auto it = g_probe_verdicts.find({ key, c->device });
+			if (it != g_probe_verdicts.end()) { v = it->second; known = true; }
+		}
+		if (!known) {
+			const double t0 = wall_ms();
+			if (probe_spec_kernel(c, window, v) != TD_OK) return TD_FAIL;
+			c->probe_us = (int)((wall_ms() - t0) * 1000.0);
+			std::lock_guard<std::mutex> lk(g_probe_mu);
+			g_probe_verdicts[{ key, c->device }] = v;
+		}
+		if (v.mismatches != 0) {
+			fprintf(stderr, "tagdust_hip: PROBE REJECTED the specialised kernel %016llx on device %d: %d of %d probe reads differ from the generic "
+			        "kernel, first at read %d, field %s%s.  This context decodes with the generic kernel: correct, about ten times slower.\n",
+			        (unsigned long long)key, c->device, v.mismatches, TD_PROBE_READS, v.read, probe_field_name(v.field), known ? " (verdict of an earlier load)" : "");
+			HIPCHK(c, hipModuleUnload(c->spec_mod));
+			c->spec_mod = nullptr; c->spec_fn = nullptr;
+			c->spec_state = 4;
+			return TD_OK;
 		}
 	}
 	c->spec_ready = true;
 	c->spec_window = window != 0;
 	c->spec_oob = lsum_oob != 0;
+	c->spec_state = 3;
 	return TD_OK;
+}
+
+// Compile (or fetch from the cache) and load the model-specialised kernel, here and now.  lsum_oob selects the clamp-free logsum.
+static int load_spec_kernel(td_ctx* c, int lsum_oob, int window)
+{
+	if (window < 0) window = c->match_len > 0;   // a context with a -start/-end window gets the kernel that can apply it
+	if (c->spec_mod) { HIPCHK(c, hipModuleUnload(c->spec_mod)); c->spec_mod = nullptr; }
+	c->spec_fn = nullptr; c->spec_ready = false;
+	std::vector<char> code;
+	std::string log;
+	uint64_t key = 0;
+	if (td_spec_compile(&c->m_desc, c->plan, lsum_oob, window, code, log, &key) != TD_OK) {
+		c->spec_state = 5;
+		return fail(c, "td_model_upload: specialised kernel did not compile: %.400s", log.c_str());
+	}
+	return install_spec_kernel(c, code, key, lsum_oob, window, false);
+}
+
+// The same compile on a host thread (option "async_compile"): the context goes on with the generic kernel until
+// spec_handover finds the job done.  Contexts that ask for the same code object share one job.
+static int start_spec_job(td_ctx* c, int lsum_oob, int window)
+{
+	std::vector<char> none;
+	std::string log;
+	uint64_t key = 0;
+	(void)td_spec_compile(&c->m_desc, c->plan, lsum_oob, window, none, log, &key, true);
+	static std::once_flag at_exit_once;
+	std::call_once(at_exit_once, [] { (void)atexit(wait_for_all_spec_jobs); });
+	std::shared_ptr<SpecJob> job;
+	{
+		std::lock_guard<std::mutex> lk(g_jobs_mu);
+		for (auto it = g_jobs.begin(); it != g_jobs.end();) { if (it->second.expired()) it = g_jobs.erase(it); else ++it; }
+		auto it = g_jobs.find(key);
+		if (it != g_jobs.end()) job = it->second.lock();
+		if (!job) {
+			job = std::make_shared<SpecJob>();
+			job->key = key; job->model.assign(&c->m_desc); job->plan = c->plan; job->lsum_oob = lsum_oob; job->window = window;
+			SpecJob* raw = job.get();   // (the job outlives its thread: its destructor joins)
+			job->th = std::thread([raw] { raw->run(); });
+			g_jobs[key] = job;
+		}
+	}
+	c->job = job; c->job_oob = lsum_oob; c->job_window = window;
+	c->spec_state = 1;
+	return TD_OK;
+}
+
+// Hand-over of a finished background compile, polled where a batch is staged (block: td_spec_wait).  Everything queued on the
+// compute streams finishes first -- the step the mid-run reloads take too; outstanding tickets stay valid -- then the kernel is
+// installed as after a synchronous compile.
+static int spec_handover(td_ctx* c, bool block)
+{
+	if (!c->job) {
+		if (c->spec_state == 5 && !c->job_err.empty()) return fail(c, "%s", c->job_err.c_str());
+		return TD_OK;
+	}
+	if (!block && !c->job->finished()) return TD_OK;
+	c->job->wait();
+	std::shared_ptr<SpecJob> job = c->job;
+	c->job.reset();
+	if (job->rc != TD_OK) {
+		c->spec_state = 5;
+		char buf[512];
+		snprintf(buf, sizeof buf, "td_model_upload: specialised kernel did not compile (background compile): %.400s", job->log.c_str());
+		c->job_err = buf;
+		return fail(c, "%s", buf);
+	}
+	c->spec_state = 2;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	return install_spec_kernel(c, job->code, job->key, c->job_oob, c->job_window, true);
+}
+
+extern "C" int td_spec_wait(td_ctx* c)
+{
+	if (!c) return TD_FAIL;
+	while (c->job) if (spec_handover(c, true) != TD_OK) return TD_FAIL;   // (a self-check fallback starts a second job)
+	return spec_handover(c, false);
 }
 
 // The clamp-free logsum of the specialised kernel turns |a - b| * 4000 into an LDS byte address (a saturating conversion; the
@@ -582,6 +898,10 @@ extern "C" int td_model_upload(td_ctx* c, const td_model_desc* m)
 	HIPCHK(c, hipSetDevice(c->device));
 	// a rejected upload (tickets in flight, an invalid description) leaves the context as it was
 	if (tickets_outstanding(c)) return fail(c, "td_model_upload: td_submit tickets are outstanding (td_wait them first)");
+	// a pending background compile is superseded: its result may land in the caches, never in this context
+	if (c->job) { c->retired.push_back(c->job); c->job.reset(); }
+	for (size_t k = 0; k < c->retired.size();) { if (c->retired[k]->finished()) c->retired.erase(c->retired.begin() + (long)k); else k++; }
+	c->job_err.clear();
 	DevModel dm;
 	if (build_dev_model(c, m, dm) != TD_OK) return TD_FAIL;
 	const TdModelHeader h = dm.h;
@@ -603,6 +923,7 @@ extern "C" int td_model_upload(td_ctx* c, const td_model_desc* m)
 	c->spec_fn = nullptr; c->spec_ready = false;
 	c->prune_lcap = 0; c->prune_live = false;   // the pruning tables belong to the model
 	c->half_slots = false;                      // ... and so does the workspace geometry
+	c->spec_state = 0; c->batches_generic = 0; c->probe_us = 0;
 	if (c->specialize) {
 		// keep what a later recompile needs
 		c->m_skip.assign(m->skip, m->skip + m->S);
@@ -622,7 +943,9 @@ extern "C" int td_model_upload(td_ctx* c, const td_model_desc* m)
 		scan(m->sM, m->C); scan(m->sI, m->C); scan(m->skip, m->S); scan(m->bg, 5);
 		c->m_maxabs = mx;
 		c->plan = td_spec_plan(&c->m_desc, td_spec_knobs());
-		if (load_spec_kernel(c, c->spec_oob_unsafe ? 0 : c->plan.k.lsum_oob) != TD_OK) return TD_FAIL;
+		// ... or, with "async_compile", on a host thread: the generic kernel decodes until the hand-over (spec_handover)
+		const int oob = c->spec_oob_unsafe ? 0 : c->plan.k.lsum_oob;
+		if ((c->async_compile ? start_spec_job(c, oob, c->match_len > 0) : load_spec_kernel(c, oob)) != TD_OK) return TD_FAIL;
 		c->spec_block = c->plan.k.block;
 		// resident waves per CU: two LDS tables fit a CU; a 1024-thread workgroup fills it alone
 		{
@@ -647,6 +970,8 @@ extern "C" int td_set_option(td_ctx* c, const char* name, int32_t value)
 		return TD_OK;
 	}
 	if (!strcmp(name, "poison_workspace")) { c->poison = value != 0; return TD_OK; }
+	if (!strcmp(name, "async_compile")) { c->async_compile = value != 0; return TD_OK; }   // ... the next td_model_upload
+	if (!strcmp(name, "spec_probe")) { c->spec_probe = value != 0; return TD_OK; }         // ... the next load of a specialised kernel
 	if (!strcmp(name, "compact_egress")) { c->compact_egress = value != 0; return TD_OK; }          // takes effect with the next download / td_submit
 	if (!strcmp(name, "stable_input")) {
 		if (tickets_outstanding(c)) return fail(c, "td_set_option: stable_input cannot change while tickets are outstanding");
@@ -686,6 +1011,12 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	if (!strcmp(name, "specialize")) { *value = c->specialize; return TD_OK; }
 	if (!strcmp(name, "spec_lsum_clamped")) { *value = c->spec_ready && !c->spec_oob; return TD_OK; }
 	if (!strcmp(name, "pipeline_depth")) { *value = c->pipeline_depth; return TD_OK; }
+	if (!strcmp(name, "async_compile")) { *value = c->async_compile; return TD_OK; }
+	if (!strcmp(name, "spec_probe")) { *value = c->spec_probe; return TD_OK; }
+	if (!strcmp(name, "spec_state")) { *value = c->job ? (c->job->finished() ? 2 : 1) : c->spec_state; return TD_OK; }
+	if (!strcmp(name, "spec_batches_generic")) { *value = c->batches_generic; return TD_OK; }
+	if (!strcmp(name, "spec_compiles_started")) { *value = td_spec_compiles_started(); return TD_OK; }
+	if (!strcmp(name, "spec_probe_us")) { *value = c->probe_us; return TD_OK; }
 	if (!strcmp(name, "host_threads")) { *value = c->host_threads; return TD_OK; }
 	if (!strcmp(name, "artifacts_active")) { *value = c->art_n > 0; return TD_OK; }
 	if (!strcmp(name, "dust")) { *value = c->dust; return TD_OK; }   // param->dust as td_set_params set it
@@ -808,7 +1139,6 @@ static void make_layout(TdWsLayout& L, int S, int H, int C, int lmax, int max_nc
 
 // output block of the decode kernels: eight SoA arrays over n_tiles*64 reads (f, b, r, bar, q, type, barcode, finger: equal
 // strides), then keep words, then labels -- all in device order
-struct OutLayout { int64_t soa_stride, keep, labels, total; };
 static OutLayout out_layout(int64_t n_tiles, int lmax, int nw1)
 {
 	OutLayout o;
@@ -859,6 +1189,25 @@ static void slot_release(TdSlot& s)
 	s = TdSlot();
 }
 
+// bound tables of the position pruning, for reads up to lcap >= lmax bases (kernels in flight read the old ones)
+static int ensure_prune_tables(td_ctx* c, int lmax)
+{
+	if (lmax <= c->prune_lcap && c->d_prune) return TD_OK;
+	HIPCHK(c, sync_compute(c));
+	const int lcap = (lmax + 2 + 255) / 256 * 256, stride = lcap + 24;   // (the scans request TDS_SCAN_B = 16 entries at a time: spare entries behind lcap)
+	std::vector<float> tab;
+	// (the bound recurrences cost columns x positions on the host: for reads beyond 8192 bases the tables stay zero, which
+	// the kernel reads as "nothing can be pruned" -- every position violates the zero bound -- and decodes densely)
+	c->prune_live = (c->plan.prune_segs > 0 || c->plan.sfx_first < c->plan.S) && lcap <= 8192;
+	if (c->prune_live) td_spec_prune_tables(&c->m_desc, c->plan, lcap, stride, tab);
+	else tab.assign((size_t)TD_PRUNE_TABLES * stride, 0.0f);
+	if (c->d_prune) { HIPCHK(c, hipFree(c->d_prune)); c->d_prune = nullptr; }
+	HIPCHK(c, hipMalloc((void**)&c->d_prune, tab.size() * sizeof(float)));
+	HIPCHK(c, hipMemcpy(c->d_prune, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+	c->prune_lcap = lcap; c->prune_stride = stride;
+	return TD_OK;
+}
+
 // Size the shared workspace for a batch with this geometry.  Growing it (or switching the kernel to the clamped logsum)
 // waits for the decode kernels in flight first.
 static int ensure_workspace(td_ctx* c, TdSlot& s)
@@ -873,21 +1222,7 @@ static int ensure_workspace(td_ctx* c, TdSlot& s)
 		td_spec_layout(s.slay, c->plan, s.n_long > 0 ? s.lmax_small : s.lmax);   // the geometry of the many
 		td_spec_layout(s.slay_big, c->plan, s.lmax);
 		slot_bytes = s.slay.slot_bytes;
-		if (s.lmax > c->prune_lcap || !c->d_prune) {
-			// bound tables of the position pruning, for reads up to lcap bases (kernels in flight read the old ones)
-			HIPCHK(c, sync_compute(c));
-			const int lcap = (s.lmax + 2 + 255) / 256 * 256, stride = lcap + 24;   // (the scans request TDS_SCAN_B = 16 entries at a time: spare entries behind lcap)
-			std::vector<float> tab;
-			// (the bound recurrences cost columns x positions on the host: for reads beyond 8192 bases the tables stay zero, which
-			// the kernel reads as "nothing can be pruned" -- every position violates the zero bound -- and decodes densely)
-			c->prune_live = (c->plan.prune_segs > 0 || c->plan.sfx_first < c->plan.S) && lcap <= 8192;
-			if (c->prune_live) td_spec_prune_tables(&c->m_desc, c->plan, lcap, stride, tab);
-			else tab.assign((size_t)TD_PRUNE_TABLES * stride, 0.0f);
-			if (c->d_prune) { HIPCHK(c, hipFree(c->d_prune)); c->d_prune = nullptr; }
-			HIPCHK(c, hipMalloc((void**)&c->d_prune, tab.size() * sizeof(float)));
-			HIPCHK(c, hipMemcpy(c->d_prune, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-			c->prune_lcap = lcap; c->prune_stride = stride;
-		}
+		if (ensure_prune_tables(c, s.lmax) != TD_OK) return TD_FAIL;
 	}
 	// wave slots: enough to fill the chip (2 workgroups of 4 waves per CU share the LDS), bounded by HBM
 	const int wpb = (c->spec_ready ? c->spec_block : td_kernel_block_threads()) / TD_WAVE;
@@ -1051,6 +1386,7 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 	}
 	s.lmax = lmax; s.nw2 = nw2; s.nw1 = nw1; s.n_tiles = (int32_t)n_tiles;
 	if (with_workspace && ensure_workspace(c, s) != TD_OK) { s.n_tiles = 0; return TD_FAIL; }
+	s.for_spec = with_workspace && c->spec_ready;
 	s.n_tiles = 0;
 
 	// host -> device: page-locked caller memory goes straight to the DMA engine, anything else through pinned staging
@@ -1114,10 +1450,18 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	                     // slot's previous launch to the finish kernel)
 	s.mode = mode;
 	if (s.n_tiles == 0) { s.ran = true; s.last_ms = 0.0f; return TD_OK; }
-	if (c->spec_ready && c->match_len > 0 && !c->spec_window) {   // first batch through a window: the kernel variant that applies it
+	if (c->spec_ready && s.for_spec && c->match_len > 0 && !c->spec_window) {   // first batch through a window: the kernel variant that applies it
 		HIPCHK(c, sync_compute(c));
 		if (load_spec_kernel(c, c->spec_oob ? 1 : 0, 1) != TD_OK) return TD_FAIL;
+		if (!c->spec_ready) {   // the probe rejected that variant: this batch gets the generic kernel's workspace geometry after all
+			s.n_long = 0; s.lmax_small = s.lmax;
+			if (ensure_workspace(c, s) != TD_OK) return TD_FAIL;
+			s.for_spec = false;
+		}
 	}
+	// a batch is decoded by the kernel it was staged for: one staged before a background compile was handed over stays generic
+	const bool use_spec = c->spec_ready && s.for_spec;
+	if (s.for_spec && !c->spec_ready) return fail(c, "td_run: the resident batch was staged for a specialised kernel that is no longer loaded (upload it again)");
 	const OutLayout ol = out_layout(s.n_tiles, s.lmax, s.nw1);
 	TdKernelArgs ka{};
 	ka.hdr = c->d_hdr; ka.cols = c->d_cols; ka.hinfo = c->d_hinfo;
@@ -1143,13 +1487,13 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	// tests: every byte of the workspace the kernel reads must have been written by this launch -- garbage (NaN floats,
 	// all-ones masks) in place of whatever an earlier batch or model left there makes a read-before-write show
 	if (c->poison) HIPCHK(c, hipMemsetAsync(ka.ws, 0xFF, (size_t)s.ws_bytes, s.cs));
-	if (c->spec_ready) {   // the tile counter of the dynamic tile assignment starts at zero (the first tiles go by slot number)
+	if (use_spec) {   // the tile counter of the dynamic tile assignment starts at zero (the first tiles go by slot number)
 		int32_t*& tn = s.wsi ? c->d_tile_next2 : c->d_tile_next;
 		if (!tn) HIPCHK(c, hipMalloc((void**)&tn, 256));
 		HIPCHK(c, hipMemsetAsync(tn, 0, sizeof(int32_t), s.cs));
 	}
 	HIPCHK(c, hipEventRecord(s.ev_k0, s.cs));
-	if (c->spec_ready) {
+	if (use_spec) {
 		TdSpecArgs sa{};
 		sa.logsum = ka.logsum; sa.packed = ka.packed; sa.lens = ka.lens;
 		sa.n_tiles = ka.n_tiles; sa.n_slots = ka.n_slots; sa.lmax = ka.lmax; sa.nw2 = ka.nw2; sa.nw1 = ka.nw1;
@@ -1182,6 +1526,7 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 		HIPCHK(c, hipModuleLaunchKernel(c->spec_fn, blocks, 1, 1, (unsigned)c->spec_block, 1, 1, 0, s.cs, nullptr, cfg));
 	} else {
 		HIPCHK(c, td_launch_decode(&ka, s.cs));
+		c->batches_generic++;
 	}
 	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
 	s.ran = true;
@@ -1363,6 +1708,7 @@ static int upload_common(td_ctx* c, const void* bases, int is_ascii, const int64
 {
 	if (!c) return TD_FAIL;
 	if (tickets_outstanding(c)) return fail(c, "td_batch_upload: td_submit tickets are outstanding (td_wait them first)");
+	if (spec_handover(c, false) != TD_OK) return TD_FAIL;   // a finished background compile takes over before any geometry is chosen
 	TdSlot& s = c->slots[0];
 	TdRoute rt;
 	rt.cs = c->stream; rt.wsi = 0; rt.aux = c->stream; rt.fin = c->stream; rt.pipelined = false;
@@ -1428,6 +1774,7 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 	}
 	if (k < 0) return fail(c, "td_submit: all %d pipeline slots hold batches that have not been waited for", c->pipeline_depth);
 	if (mode == TD_MODE_RNA_DUST && labels) return fail(c, "td_submit: TD_MODE_RNA_DUST has no labels (pass NULL)");
+	if (spec_handover(c, false) != TD_OK) return TD_FAIL;   // a finished background compile takes over before any geometry is chosen
 	TdSlot& s = c->slots[k];
 	TdRoute rt;
 	rt.cs = c->stream; rt.wsi = 0; rt.aux = c->stream; rt.fin = c->stream; rt.pipelined = true;

@@ -58,4 +58,8 @@ float td_spec_prune_z(const td_model_desc* m, int n_seg, int sfx_first);
 void td_spec_prune_tables(const td_model_desc* m, const TdSpecPlan& p, int lcap, int stride, std::vector<float>& tab);
 void td_spec_layout(TdSpecLayout& L, const TdSpecPlan& p, int lmax);
 // lsum_oob: the logsum form (the plan's k.lsum_oob unless the context had to fall back); window: -start/-end support compiled in
-int td_spec_compile(const td_model_desc* m, const TdSpecPlan& p, int lsum_oob, int window, std::vector<char>& code, std::string& log);
+// *key_out: the cache key of the code object (a hash of the full source, every compile option and the compiler's version);
+// key_only: nothing else is done.  Safe to call from any host thread: it touches neither a context nor the device.
+int td_spec_compile(const td_model_desc* m, const TdSpecPlan& p, int lsum_oob, int window, std::vector<char>& code, std::string& log,
+                    uint64_t* key_out = nullptr, bool key_only = false);
+int td_spec_compiles_started(void);   // hiprtc compiles this process has actually started (cache hits do not count)

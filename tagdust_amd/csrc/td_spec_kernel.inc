@@ -2357,6 +2357,10 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 				for (int i = w.tmin + 1; i <= tmaxF; i++)
 					if (i > len && i <= lenF) labels[i * TD_WAVE + lane] = 0;
 			}
+#if TDS_TEST_WRONG_RESULT == 2
+			// test hook (see below): one interior label of every read of odd length becomes another valid label
+			if (H > 1 && lenF >= 3 && (lenF & 1)) labels[1 * TD_WAVE + lane] = (int8_t)(labels[1 * TD_WAVE + lane] == 0 ? 1 : 0);
+#endif
 			// the label path as runs, for the compact egress: the wave reads back the column it has just written (L2-hot) -- labels
 			// 0..lenF of a read whose window held a base, the one label 0 otherwise (what td_stage's finish kernel hands out)
 			if (ka.out_runs) {
@@ -2567,6 +2571,13 @@ extern "C" __global__ __launch_bounds__(TDS_BLOCK, TDS_MIN_WAVES) void td_spec_k
 		}
 
 		TDS_PHASE(8);   // DUST
+#if TDS_TEST_WRONG_RESULT == 1
+		// test hook: -DTDS_TEST_WRONG_RESULT=k through TD_SPEC_EXTRA_OPTS (part of the cache key, absent from every normal build) makes
+		// the kernel compute wrong VALUES -- nothing is read or written that it would not read or write anyway -- so that the load-time
+		// probe (td_api.hip) has something to reject: k = 1 flips the lowest mantissa bit of b_score in one lane of every tile, k = 2
+		// (above) changes one label of every read of odd length.
+		if (lane == 5) b_score = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, b_score) ^ 1u);
+#endif
 		ka.out_f[rid] = f_score;
 		ka.out_b[rid] = b_score;
 		ka.out_r[rid] = r_score;

@@ -55,3 +55,20 @@ hipError_t td_stage_art_left(const TdStageBatch& b, hipStream_t stream);
 hipError_t td_stage_finish(const TdStageBatch& b, hipStream_t stream);
 // memory-side probe of a candidate workspace allocation (milliseconds, best of three passes); see td_stage.hip
 hipError_t td_ws_probe(uint8_t* ws, int64_t slot_bytes, int n_slots, hipStream_t stream, float* ms);
+
+// The probe's comparison (td_api.hip, probe_spec_kernel): two decode launches over the same n_tiles full tiles of reads, outputs
+// in device order.  What a caller could see is compared -- the eight SoA words of every read bit for bit, labels[0..len], the keep
+// bits over len -- and the first n_counters words of the two launches' counters; padding no kernel defines is not looked at.
+// out[0] = differing reads (+ 1 when the counters differ), out[1 + 2 w], out[2 + 2 w] = the first differing read of tile w and
+// its first differing field (TD_PROBE_FIELD_*; read = n_tiles * 64 stands for the counters), out[1 + 2 w] = -1: tile w agrees.
+enum { TD_PROBE_FIELD_RES0 = 0 /* .. 7: the td_read_result fields in order */, TD_PROBE_FIELD_LABELS = 8, TD_PROBE_FIELD_SEQ = 9, TD_PROBE_FIELD_COUNTERS = 10 };
+struct TdProbeCmp {
+	const int32_t* lens;                   // [n_tiles * 64]
+	int32_t n_tiles, lmax, nw1, n_counters;
+	const uint8_t* soa_a; const uint8_t* soa_b; int64_t soa_stride;
+	const uint32_t* keep_a; const uint32_t* keep_b;
+	const int8_t* labels_a; const int8_t* labels_b;
+	const unsigned long long* counters_a; const unsigned long long* counters_b;
+	int32_t* out;                          // [1 + 2 * (n_tiles + 1)]
+};
+hipError_t td_probe_compare(const TdProbeCmp& p, hipStream_t stream);

@@ -281,3 +281,55 @@ hipError_t td_ws_probe(uint8_t* ws, int64_t slot_bytes, int n_slots, hipStream_t
 	*ms = best;
 	return e;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// The probe's comparison (td_stage.h): one wave per tile, one lane per read; one more wave for the counters.  A wave that found a
+// difference writes its first differing read and field with plain stores and adds its number of differing reads to out[0] -- one
+// atomic per mismatching wave, none when the kernels agree.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TD_WAVE) void td_probe_compare_kernel(const TdProbeCmp p)
+{
+	const int lane = threadIdx.x;
+	const int w = blockIdx.x;
+	int field = -1;
+	if (w < p.n_tiles) {
+		const int64_t k = (int64_t)w * TD_WAVE + lane;
+		const int len = p.lens[k];
+		if (len >= 1) {   // (a padding lane or a read without bases has no defined outputs)
+			for (int a = 7; a >= 0; a--) {
+				const uint32_t va = *(const uint32_t*)(p.soa_a + a * p.soa_stride + k * 4), vb = *(const uint32_t*)(p.soa_b + a * p.soa_stride + k * 4);
+				if (va != vb) field = TD_PROBE_FIELD_RES0 + a;
+			}
+			if (field < 0) {
+				const int8_t* la = p.labels_a + (int64_t)w * (p.lmax + 1) * TD_WAVE + lane;
+				const int8_t* lb = p.labels_b + (int64_t)w * (p.lmax + 1) * TD_WAVE + lane;
+				for (int q = 0; q <= len && q <= p.lmax; q++) if (la[q * TD_WAVE] != lb[q * TD_WAVE]) { field = TD_PROBE_FIELD_LABELS; break; }
+			}
+			if (field < 0) {
+				const uint32_t* ka = p.keep_a + (int64_t)w * p.nw1 * TD_WAVE + lane;
+				const uint32_t* kb = p.keep_b + (int64_t)w * p.nw1 * TD_WAVE + lane;
+				for (int c = 0; c < p.nw1 && c * 32 < len; c++) {
+					const int nb = len - c * 32;
+					const uint32_t mask = nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u);
+					if ((ka[c * TD_WAVE] ^ kb[c * TD_WAVE]) & mask) { field = TD_PROBE_FIELD_SEQ; break; }
+				}
+			}
+		}
+	} else {
+		for (int q = lane; q < p.n_counters; q += TD_WAVE) if (p.counters_a[q] != p.counters_b[q]) field = TD_PROBE_FIELD_COUNTERS;
+	}
+	const unsigned long long bad = __ballot(field >= 0);
+	if (bad == 0ull) return;
+	const int first = __ffsll((long long)bad) - 1;
+	if (lane == first) {
+		p.out[1 + 2 * w] = w < p.n_tiles ? w * TD_WAVE + lane : p.n_tiles * TD_WAVE;
+		p.out[2 + 2 * w] = field;
+		atomicAdd(p.out, w < p.n_tiles ? (int)__popcll(bad) : 1);
+	}
+}
+
+hipError_t td_probe_compare(const TdProbeCmp& p, hipStream_t stream)
+{
+	hipLaunchKernelGGL(td_probe_compare_kernel, dim3((unsigned)p.n_tiles + 1), dim3(TD_WAVE), 0, stream, p);
+	return hipGetLastError();
+}

@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "td_ctx_create", "td_ctx_destroy", "td_last_error", "td_logsum_table", "td_model_upload", "td_set_params",
     "td_batch_upload", "td_batch_upload_ascii", "td_run", "td_sync", "td_batch_download", "td_counts_reset",
     "td_counts_get", "td_diag_get", "td_counts_device_ptr", "td_last_kernel_ms", "td_timeline_origin", "td_last_kernel_times", "td_batch_info", "td_set_option", "td_get_option", "td_set_artifacts", "td_spec_source", "td_spec_prune_info", "td_spec_restart_info",
+    "td_spec_probe", "td_spec_probe_params", "td_spec_wait",
     "td_submit", "td_wait", "td_host_alloc", "td_host_free", "td_set_batch_window", "td_set_window", "td_arch_scores",
 ]
 MULTI_ABI_SYMBOLS = ["td_shard_bounds", "td_count_outcomes", "td_multi_create", "td_multi_destroy", "td_multi_last_error",
@@ -514,6 +515,35 @@ def spec_source(md):
     return buf.value.decode()
 
 
+PROBE_READS = 256
+
+
+def spec_probe(md):
+    """td_spec_probe: the reads a freshly loaded specialised kernel is checked with against the generic kernel, made from the
+    model description alone (no GPU needed): (codes uint8 0..4, offs int64 [257])."""
+    lib = load_library()
+    lib.td_spec_probe.argtypes = [C.POINTER(_ModelDesc), C.c_void_p, C.c_int64, C.c_void_p]
+    lib.td_spec_probe.restype = C.c_int64
+    d, keep = make_model_desc(md)
+    offs = np.zeros(PROBE_READS + 1, np.int64)
+    n = int(lib.td_spec_probe(C.byref(d), None, 0, offs.ctypes.data))
+    if n < 0:
+        raise TdError("td_spec_probe: bad model description")
+    codes = np.zeros(n, np.uint8)
+    lib.td_spec_probe(C.byref(d), codes.ctypes.data, n, None)
+    return codes, offs
+
+
+def spec_probe_params():
+    """The fixed parameters the probe is decoded with: dict(threshold, minlen, dust, window=(matchstart, matchend))."""
+    lib = load_library()
+    lib.td_spec_probe_params.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.td_spec_probe_params.restype = None
+    t, ml, du, a, b = C.c_float(0), C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    lib.td_spec_probe_params(C.byref(t), C.byref(ml), C.byref(du), C.byref(a), C.byref(b))
+    return dict(threshold=float(t.value), minlen=int(ml.value), dust=int(du.value), window=(int(a.value), int(b.value)))
+
+
 def spec_prune_info(md, lcap):
     """Position-pruning tables of the specialised kernel for this model: dict with n_seg (leading segments pruned, 0 = none),
     sfx_first (first trailing segment pruned, S = none), z, and the tables fb, bwb, wa, wb, fbs, bws, wc, wd."""
@@ -594,6 +624,11 @@ class TagdustHip:
         d, keep = make_model_desc(md)
         self._keep = keep
         self._chk(self.lib.td_model_upload(self.h, C.byref(d)))
+
+    def spec_wait(self):
+        """td_spec_wait: block until a background compile (option "async_compile") is finished and handed over."""
+        self.lib.td_spec_wait.argtypes = [C.c_void_p]
+        self._chk(self.lib.td_spec_wait(self.h))
 
     def set_params(self, threshold, minlen=16, dust=100):
         self._chk(self.lib.td_set_params(self.h, float(threshold), int(minlen), int(dust)))
