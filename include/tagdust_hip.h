@@ -178,11 +178,13 @@ int td_spec_restart_info(const td_model_desc* model, int32_t lcap, float* tab, i
  * file stays, so that the next process rejects it in milliseconds.  Option "spec_probe" 0 skips the probe (A/B runs).
  * td_spec_probe gives the reads themselves (host only, no GPU; a private fixed-seed generator that never touches rand()):
  * offs[TD_PROBE_READS + 1] when offs != NULL, the base codes 0..4 into codes when cap holds them all; returns the number of bases
- * (-1: bad description).  Reads that follow the architecture -- each HMM of every multi-HMM segment in turn, the most probable base
+ * (-1: bad description).  Reads that follow the architecture -- each HMM of every multi-HMM segment in turn (a second barcode segment steps
+ * through the combinations with the first), the most probable base
  * of every match column, random bases where the emission is flat, read segments of a random length up to avg_len (at most 256) --
  * mutated by substitutions, single-base insertions / deletions and N; one read in eight uniformly random; lengths ragged in every tile. */
 #define TD_PROBE_READS     256
-#define TD_PROBE_THRESHOLD 5.0f  /* Q: an architecture with little evidence per read (a two-base spacer) tops out near 7 */
+#define TD_PROBE_THRESHOLD 3.0f  /* Q: an architecture with little evidence per read tops out near 7 (a two-base spacer) or near 4 (a
+                                  * barcode between two read segments: R G B R) -- above that every probe read is a mismatch */
 #define TD_PROBE_MINLEN    16
 #define TD_PROBE_DUST      100
 #define TD_PROBE_WIN_START 2      /* td_set_window(2, 34) for the window variant */

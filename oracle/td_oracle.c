@@ -659,6 +659,19 @@ void tdo_label_read(const tdo_model* m, const tdo_params* p, tdo_workspace* ws,
 		memset(labels, 0, (size_t)len + 1);     /* ri->labels as read_fasta_fastq() leaves it, io.c:1755-1764 */
 	}
 	res->b_score = tdo_backward(m, ws, seq + woff, wlen);
+	if (!(res->b_score > NEG_INF)) {
+		/* A read without any valid path (fewer bases than mandatory segments).  The reference has no defined behaviour here:
+		 * forward_max_posterior_decoding() indexes the logsum table with NaN, and so would the restatement
+		 * below.  This guard is NOT the reference's: it states the device's rule for such a read (td_kernels.hip, "dead") --
+		 * architecture mismatch, Q = 0, b_score = -inf, the sequence as it was, labels zero; the other scores mean nothing.
+		 * DUST still looks at the (unchanged) sequence, as it does on the device. */
+		memset(labels, 0, (size_t)len + 1);
+		res->f_score = res->r_score = res->bar_prob = NEG_INF;
+		res->Q = 0.0f;
+		res->read_type = TDO_FAIL_ARCHITECTURE_MISMATCH;
+		if (p->dust && tdo_dust(seq, len, p->dust)) res->read_type = TDO_FAIL_LOW_COMPLEXITY;
+		return;
+	}
 	tdo_forward_decode(m, ws, seq + woff, wlen, res->b_score, &res->f_score, &res->r_score, &res->bar_prob, labels);
 	res->Q = tdo_qvalue(res->f_score, res->r_score, res->bar_prob);
 	tdo_extract_window(m, p, seq, qual, len, woff, wlen, labels, res->Q, &res->read_type, &res->barcode, &res->fingerprint);

@@ -74,6 +74,7 @@ extern "C" int64_t td_spec_probe(const td_model_desc* m, uint8_t* codes, int64_t
 			for (int p = 0; p < len; p++) rd.push_back(g.one_in(50) ? 4 : (uint8_t)g.below(4));
 		} else {
 			const int k = n_model++;
+			int earlier = 1;   // product of the sizes of the barcode segments in front of segment j
 			for (int j = 0; j < m->S; j++) {
 				const int nh = m->n_hmm[j], nc = m->n_col[j];
 				if (!(m->skip[j] == -INFINITY) && g.one_in(4)) continue;   // a segment the model may skip is skipped now and then
@@ -82,8 +83,12 @@ extern "C" int64_t td_spec_probe(const td_model_desc* m, uint8_t* codes, int64_t
 					for (int p = 0; p < len; p++) rd.push_back((uint8_t)g.below(4));
 					continue;
 				}
-				// every HMM of every multi-HMM segment gets its turn (segments of different sizes fall out of step on their own)
-				const int f = k % nh;
+				// every HMM of every multi-HMM segment gets its turn: k % nh.  A second barcode segment would only ever meet the
+				// first one's HMM of the same number that way (extract_reads reports the LAST barcode segment), so barcode segments
+				// step through their combinations: the first takes k % nh, a later one (k / product of the earlier sizes) % nh
+				const bool bseg = m->seg_type[j] == 'B' && nh > 1;
+				const int f = (bseg ? k / earlier : k) % nh;
+				if (bseg && earlier <= TD_PROBE_READS) earlier *= nh;
 				int g0 = 0, g1 = nc;
 				if (m->seg_type[j] == 'P' && nc > 1 && g.one_in(2)) {   // a partial segment loses its far end: the 5' one its start
 					if (j < first_read_seg) g0 = (int)g.below((uint32_t)nc); else g1 = 1 + (int)g.below((uint32_t)nc);

@@ -430,12 +430,91 @@ def scenarios(tmp):
         EXTRA["artifacts_b_r"] = {"art_fasta_text": np.frombuffer(open(fa, "rb").read(), np.uint8)}   # input data of -ref
         return fq, ["-seed", "42", "-ref", fa, "-fe", "9", "-1", "B:" + ",".join(bars), "-2", "R:N"]
     sc["artifacts_b_r"] = artifacts
+
+    # Segment orders away from "tags, one R:N, optional 3' P": two B / two F segments, tags 3' of the read segment, no read
+    # segment at all, two read segments around tags -- the branches of extract_reads (barcode_hmm.c:3172-3313) and the values
+    # of the specialised kernel's plan that the fixtures above never reach.
+    bars4 = ["ACAGTG", "CTTGTA", "GGCTAC", "TTAGGC"]
+
+    def free_order(fq, seed, follow):
+        """240 reads: follow(rng, dna) gives a read that follows the architecture (its tags already through mutate());
+        about 10 % are replaced by unrelated random reads of the same length, about 5 % carry N bases."""
+        rng = np.random.RandomState(seed)
+
+        def dna(n):
+            return "".join("ACGT"[k] for k in rng.randint(0, 4, n))
+        with open(fq, "w") as fh:
+            for i in range(240):
+                s_ = follow(rng, dna)
+                if rng.random_sample() < 0.1:
+                    s_ = dna(len(s_))
+                if rng.random_sample() < 0.05:
+                    s_ = "".join("N" if rng.random_sample() < 0.08 else ch for ch in s_)
+                fh.write("@READ%d\n%s\n+\n%s\n" % (i, s_, "I" * len(s_)))
+
+    def odd_len(rng, n, share=0.4):
+        """n, or n - 1 / n + 1 in `share` of the reads (a fingerprint of the wrong length)"""
+        return n + int(rng.choice([-1, 1])) if rng.random_sample() < share else n
+
+    def b_s_b_r():  # two B segments of different sizes: (mem << 16) | bar comes from the last one; four mandatory segments
+        fq = os.path.join(tmp, "bsbr.fq")
+        bars2 = ["AACC", "GGTT", "CATG"]
+
+        def follow(rng, dna):
+            b2 = dna(4) if rng.random_sample() < 0.1 else bars2[rng.randint(3)]     # the decoy is hit in the second B only
+            return mutate(rng, bars4[rng.randint(4)] + "GT" + b2, 0.02, 0.01) + dna(rng.randint(20, 51))
+        free_order(fq, 41, follow)
+        return fq, ["-seed", "42", "-1", "B:" + ",".join(bars4), "-2", "S:GT", "-3", "B:" + ",".join(bars2), "-4", "R:N"]
+    sc["b_s_b_r"] = b_s_b_r
+
+    def r_s_b_f():  # the read segment first, every tag 3' of it, F last: too_short breaks before bar is set
+        fq = os.path.join(tmp, "rsbf.fq")
+
+        def follow(rng, dna):
+            return dna(rng.randint(10, 51)) + mutate(rng, "GATCGG" + bars4[rng.randint(4)] + dna(odd_len(rng, 5)), 0.02, 0.01)
+        free_order(fq, 43, follow)
+        return fq, ["-seed", "42", "-1", "R:N", "-2", "S:GATCGG", "-3", "B:" + ",".join(bars4), "-4", "F:NNNNN"]
+    sc["r_s_b_f"] = r_s_b_f
+
+    def f_b_f_r():  # two F segments: one key across both, required_finger_len = 16, the key fills 32 bits and key << 8 wraps
+        fq = os.path.join(tmp, "fbfr.fq")
+
+        def follow(rng, dna):
+            # (a second UMI of 11 or 13 bases costs nothing: the read segment behind it gives or takes the base, whatever the
+            # share -- 4 reads of outcome 3 at a share of 1.  A first UMI of 3 or 5 in front of the barcode is what the model
+            # has to pay for with a delete or an insert, which leaves 15 or 17 fingerprint bases.)
+            return mutate(rng, dna(odd_len(rng, 4, 0.15)) + bars4[rng.randint(4)] + dna(odd_len(rng, 12)), 0.02, 0.01) + dna(rng.randint(10, 51))
+        free_order(fq, 47, follow)
+        return fq, ["-seed", "42", "-1", "F:NNNN", "-2", "B:" + ",".join(bars4), "-3", "F:NNNNNNNNNNNN", "-4", "R:N"]
+    sc["f_b_f_r"] = f_b_f_r
+
+    def b_f():  # no read segment, but a fingerprint: nothing of the read is kept
+        fq = os.path.join(tmp, "bf.fq")
+
+        def follow(rng, dna):
+            return mutate(rng, bars4[rng.randint(4)] + dna(odd_len(rng, 8)), 0.02, 0.01)
+        free_order(fq, 53, follow)
+        return fq, ["-seed", "42", "-1", "B:" + ",".join(bars4), "-2", "F:NNNNNNNN"]
+    sc["b_f"] = b_f
+
+    def r_g_b_r():  # two read segments with G and a barcode between them: the most label runs per read, READ1 / READ2 files
+        fq = os.path.join(tmp, "rgbr.fq")
+
+        def follow(rng, dna):
+            return dna(rng.randint(10, 41)) + mutate(rng, "G" * rng.randint(0, 4) + bars4[rng.randint(4)], 0.02, 0.01) + dna(rng.randint(10, 41))
+        free_order(fq, 59, follow)
+        return fq, ["-seed", "42", "-1", "R:N", "-2", "G:G", "-3", "B:" + ",".join(bars4), "-4", "R:N"]
+    sc["r_g_b_r"] = r_g_b_r
     return sc
+
 
 
 # fixtures whose reference CLI files tests/test_io.py compares with (test_writer_reproduces_reference_files, test_io_gpu,
 # test_whole_pipeline_without_the_reference)
-CLI_NAMES = ["c2_b4_r", "c3_b6_s_r_p", "scen2_endloss", "umi_f_s_r", "short_q_given", "casava_index", "b_r_s_r", "dust_b_r", "scen2_p_b_r_p"]
+CLI_NAMES = ["c2_b4_r", "c3_b6_s_r_p", "scen2_endloss", "umi_f_s_r", "short_q_given", "casava_index", "b_r_s_r", "dust_b_r", "scen2_p_b_r_p",
+             "b_s_b_r", "r_s_b_f", "f_b_f_r", "r_g_b_r"]      # (not b_f: the reference writes no .fq without a read segment)
+# fixtures whose outcome histogram must show outcome 0 and two more, five reads each, before they are committed
+FREE_ORDER_NAMES = ["b_s_b_r", "r_s_b_f", "f_b_f_r", "b_f", "r_g_b_r"]
 
 
 def record_cli():
@@ -489,6 +568,10 @@ def main():
             print("%-18s reads=%4d S=%d H=%3d C=%3d thr=%.4f outcomes=%s  %.0f KB" % (
                 name, d["n_reads"], d["S"], d["H"], d["C"], d["threshold"],
                 dict(zip(vals.tolist(), cnt.tolist())), kb))
+            if name in FREE_ORDER_NAMES:
+                hist = dict(zip(vals.tolist(), cnt.tolist()))
+                assert hist.get(0, 0) >= 5 and sum(1 for k, v in hist.items() if k != 0 and v >= 5) >= 2, (name, hist)
+                assert kb <= 32, (name, kb)
             tail = [l for l in log.splitlines() if "WARNING" in l]
             for l in tail:
                 print("   ", l)

@@ -30,7 +30,7 @@ def _single(g, seq, offs):
 
 
 @pytest.mark.parametrize("devices", [[0], [0, 0], [0, 0, 0]], ids=["N1", "N2-same-device", "N3-same-device"])
-@pytest.mark.parametrize("name", ["c3_b6_s_r_p", "artifacts_b_r", "c2_indel_varlen", "window_b_r"])
+@pytest.mark.parametrize("name", ["c3_b6_s_r_p", "artifacts_b_r", "c2_indel_varlen", "window_b_r", "b_s_b_r"])
 def test_multi_equals_single_context(name, devices):
     from tagdust_amd.lib import TagdustMulti
     g = load_golden(name)

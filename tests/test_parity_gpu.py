@@ -223,7 +223,7 @@ def test_ascii_upload_and_large_ragged_batch(ctx):
     assert np.array_equal(seq_after, oseq)
 
 
-@pytest.mark.parametrize("name", ["c2_b4_r", "c3_b6_s_r_p", "casava_index", "scen1_b_r", "o_b_s_r"])
+@pytest.mark.parametrize("name", ["c2_b4_r", "c3_b6_s_r_p", "casava_index", "scen1_b_r", "o_b_s_r", "b_s_b_r"])
 def test_runtime_hmm_loop_path(name, monkeypatch):
     """The specialised kernel's run-time HMM loop (normally only for segments with >= 16 HMMs, e.g. 96 barcodes) forced
     onto small barcode segments: same bits as the reference."""
@@ -355,6 +355,41 @@ def test_read_without_valid_path_is_a_mismatch(ctx):
     keep = np.r_[0:35, 36:n_good + 1]
     assert np.array_equal(res["read_type"][keep], g["read_type"][:n_good])
     assert np.array_equal(_bits(res["f_score"][keep]), _bits(g["f_score"][:n_good]))
+
+
+def test_probe_reads_without_a_path(ctx):
+    """The probe reads of a model with four mandatory segments (b_s_b_r): the generator pads its reads to 4 bases whatever the
+    model, and a read of four bases or fewer has no path through four mandatory segments.  Decoded under the probe's fixed
+    parameters, with reads of 1 .. 4 bases behind the 256 probe reads so that the rule is met whatever the generator drew: a read
+    the oracle reports as without a path (its guard, oracle/td_oracle.c; the reference is undefined there) comes
+    back as a mismatch with Q = 0 and b_score = -inf from both kernels; every other read agrees with the oracle in full."""
+    from oracle import pyoracle
+    from tagdust_amd import lib as tdlib
+    g = load_golden("b_s_b_r")
+    codes, offs = tdlib.spec_probe(g)
+    n_probe = len(offs) - 1
+    extra = [np.array([2, 0, 3, 1][:k], np.uint8) for k in (1, 2, 3, 4)]
+    seq = np.concatenate([codes] + extra)
+    offs = np.concatenate([offs, offs[-1] + np.cumsum([len(e) for e in extra])]).astype(np.int64)
+    p = tdlib.spec_probe_params()
+    ores, olab, oseq = pyoracle.label_batch(pyoracle.OracleModel(g), seq, offs, p["threshold"], p["minlen"], p["dust"], 4)
+    nopath = np.isneginf(ores["b_score"])
+    print("probe reads without a path:", int(nopath[:n_probe].sum()), "of", n_probe)
+    assert nopath[:n_probe].sum() <= 8 and nopath[n_probe:].all()
+    assert (ores["read_type"][nopath] == 1).all() and (ores["Q"][nopath] == 0.0).all()
+    g2 = dict(g)
+    g2.update(minlen=p["minlen"], dust=p["dust"])
+    res, labels, seq_after = _run(ctx, g2, seq, offs, threshold=p["threshold"])
+    assert (res["read_type"][nopath] == 1).all() and (res["mapq"][nopath] == 0.0).all() and np.isneginf(res["b_score"][nopath]).all()
+    assert np.array_equal(seq_after, oseq)          # (a read without a path keeps its sequence)
+    keep = ~nopath
+    for k in ("b_score", "f_score", "r_score", "bar_prob"):
+        assert np.array_equal(_bits(res[k][keep]), _bits(ores[k][keep])), k
+    assert np.allclose(res["mapq"][keep], ores["Q"][keep], rtol=0, atol=Q_TOL)
+    for k in ("read_type", "barcode", "fingerprint"):
+        assert np.array_equal(res[k][keep], ores[k][keep]), k
+    lab_keep = np.concatenate([np.full(int(offs[i + 1] - offs[i]) + 1, keep[i]) for i in range(len(keep))])
+    assert np.array_equal(labels[lab_keep], olab[lab_keep])
 
 
 def test_long_reads_switch_to_clamped_logsum(monkeypatch):
@@ -692,6 +727,119 @@ def test_random_architectures_against_oracle(ctx, seed):
     for k in ("read_type", "barcode", "fingerprint"):
         assert np.array_equal(res[k], ores[k]), (k, segs)
     assert np.array_equal(seq_after, oseq), segs
+
+
+def _free_order_arch(rng):
+    """A random architecture whose segments come in ANY order (beside _random_arch, whose tags all sit in front of its one read
+    segment and whose random stream the committed seeds are bound to): 0-2 read segments, 0-2 barcode segments, 0-2 fingerprints,
+    spacer / partial / optional / G segments, shuffled -- two B, two F (up to 32 fingerprint bases: the 32-bit key wraps), tags 3'
+    of the read segment, no read segment at all, two read segments around tags.  (segs, parts): parts[j](rng-driven) gives the
+    text of segment j for one read."""
+    def dna(n):
+        return "".join("ACGT"[x] for x in rng.randint(0, 4, n))
+    segs, parts = [], []
+    for _ in range(int(rng.choice(3, p=[0.2, 0.6, 0.2]))):
+        segs.append("R:N"); parts.append(lambda: dna(rng.randint(10, 46)))
+    for _ in range(int(rng.choice(3, p=[0.25, 0.5, 0.25]))):
+        L = int(rng.randint(4, 8))
+        bars = sorted({dna(L) for _ in range(int(rng.choice([2, 3, 5, 9])))})
+        # a random k-mer in place of the barcode in one read in ten
+        segs.append("B:" + ",".join(bars))
+        parts.append(lambda bars=bars, L=L: dna(L) if rng.random_sample() < 0.1 else bars[rng.randint(len(bars))])
+    for _ in range(int(rng.choice(3, p=[0.5, 0.25, 0.25]))):
+        nf = int(rng.choice([4, 6, 8, 12, 13, 16]))
+        # a UMI one base off in 15 % of the reads
+        segs.append("F:" + "N" * nf)
+        parts.append(lambda nf=nf: dna(nf + (int(rng.choice([-1, 1])) if rng.random_sample() < 0.15 else 0)))
+    if rng.random_sample() < 0.5:
+        sp = dna(rng.randint(2, 7)); segs.append("S:" + sp); parts.append(lambda sp=sp: sp)
+    if rng.random_sample() < 0.4:
+        pp = dna(rng.randint(5, 17)); segs.append("P:" + pp)
+        parts.append(lambda pp=pp: pp[rng.randint(0, len(pp)):] if rng.random_sample() < 0.5 else pp[:rng.randint(0, len(pp) + 1)])
+    if rng.random_sample() < 0.2:
+        segs.append("O:N"); parts.append(lambda: dna(rng.randint(0, 4)))
+    if rng.random_sample() < 0.2:
+        segs.append("G:G"); parts.append(lambda: "G" * rng.randint(0, 4))
+    if not segs:
+        bars = sorted({dna(6) for _ in range(5)})
+        segs.append("B:" + ",".join(bars)); parts.append(lambda bars=bars: bars[rng.randint(len(bars))])
+    while True:
+        order = rng.permutation(len(segs))
+        if not any(segs[order[i]] == "R:N" and segs[order[i + 1]] == "R:N" for i in range(len(order) - 1)):
+            break
+    return [segs[i] for i in order], [parts[i] for i in order]
+
+
+def _free_order_case(seed):
+    """Segments, 200 reads, the builder's model and the decode parameters of one free-order fuzz seed.  Reads follow the
+    segments, go through the mutation loop of test_random_architectures_against_oracle, and are replaced by a uniform random read
+    of floor .. 89 bases (floor = number of segments + 6) with p = 0.1 or when they came out shorter than floor: no read is
+    without a path through the model (those have a test of their own, test_probe_reads_without_a_path)."""
+    from tagdust_amd import lib as tdlib
+    rng = np.random.RandomState(20000 + seed)
+    segs, parts = _free_order_arch(rng)
+    code = {"A": 0, "C": 1, "G": 2, "T": 3, "N": 4}
+    floor = len(segs) + 6
+    reads = []
+    for i in range(200):
+        s_ = "".join(p() for p in parts)
+        out = []
+        for ch in s_:
+            u = rng.random_sample()
+            if u < 0.02:
+                out.append("ACGT"[rng.randint(4)])
+            elif u < 0.03:
+                continue
+            elif u < 0.04:
+                out.append(ch); out.append("ACGT"[rng.randint(4)])
+            elif u < 0.045:
+                out.append("N")
+            else:
+                out.append(ch)
+        s_ = "".join(out)
+        if rng.random_sample() < 0.1 or len(s_) < floor:
+            s_ = "".join("ACGT"[x] for x in rng.randint(0, 4, rng.randint(floor, 90)))
+        reads.append(np.array([code[ch] for ch in s_], np.uint8))
+    offs = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.int64)
+    seq = np.concatenate(reads)
+    md, _ = tdlib.build_model(segs, seq, offs, 0.05, 0.1)
+    thr = float(rng.choice([0.0, 1.5, 8.0]))
+    md.update(threshold=thr, minlen=int(rng.choice([8, 16])), dust=int(rng.choice([0, 100, 20])))
+    return segs, seq, offs, md
+
+
+# chosen on the CPU (generator + oracle) so that the conditions of tests/test_free_order.py hold: two outcomes with five reads each
+# for every seed; between them two B segments, tags behind the read segment, no read segment, two F, 13 or more fingerprint
+# bases, two read segments
+_FREE_ORDER_SEEDS = [7, 11, 13, 17, 34, 36]
+if os.environ.get("TD_FREE_ORDER_SEEDS"):      # e.g. TD_FREE_ORDER_SEEDS=100:180 for a longer one-off run
+    _a, _b = os.environ["TD_FREE_ORDER_SEEDS"].split(":")
+    _FREE_ORDER_SEEDS = list(range(int(_a), int(_b)))
+
+
+@pytest.mark.parametrize("seed", _FREE_ORDER_SEEDS)
+def test_free_order_architectures_against_oracle(ctx, seed):
+    """Segment lists in any order (_free_order_arch): the specialised kernel's plan -- first-segment labels, label runs, pruned
+    leading and trailing segments, restarts -- and both kernels' restatement of extract_reads on orders no fixture follows.
+    Both kernels equal the oracle bit for bit; the device counters equal serial counting."""
+    from oracle import pyoracle
+    segs, seq, offs, md = _free_order_case(seed)
+    thr = float(md["threshold"])
+    ores, olab, oseq = pyoracle.label_batch(pyoracle.OracleModel(md), seq, offs, thr, int(md["minlen"]), int(md["dust"]), 8)
+    assert np.isfinite(ores["b_score"]).all(), segs
+    res, labels, seq_after = _run(ctx, md, seq, offs, threshold=thr)
+    for k in ("b_score", "f_score", "r_score", "bar_prob"):
+        assert np.array_equal(_bits(res[k]), _bits(ores[k])), (k, segs)
+    assert np.array_equal(labels, olab), segs
+    assert np.allclose(res["mapq"], ores["Q"], rtol=0, atol=Q_TOL), segs
+    for k in ("read_type", "barcode", "fingerprint"):
+        assert np.array_equal(res[k], ores[k]), (k, segs)
+    assert np.array_equal(seq_after, oseq), segs
+    cnt = ctx.counts()
+    for c_ in range(8):
+        assert cnt[c_] == int(((ores["read_type"] & 0xFF) == c_).sum()), (c_, segs)
+    ok = (ores["read_type"] == 0) & (ores["barcode"] >= 0)
+    assert np.array_equal(cnt[8:], np.bincount(ores["barcode"][ok] & 0xFF, minlength=256)), segs
 
 
 @pytest.mark.parametrize("nb,linker_first,umi", [(60, False, True), (96, False, True), (96, True, False), (62, True, True), (97, False, False)],

@@ -57,7 +57,8 @@ def test_probe_leaves_rand_alone(probes):
 @pytest.mark.parametrize("name", GOLDEN_NAMES)
 def test_probe_exercises_the_model(probes, name):
     """Decoded by the oracle under the probe's fixed parameters: at least two outcomes, and for a model with a barcode segment
-    at least min(number of barcodes, 8) different barcodes among the extracted reads."""
+    at least min(number of barcodes, 8) different barcodes among the extracted reads -- of the LAST barcode segment, the one
+    whose barcode extract_reads reports ((segment << 16) | barcode, hence the mask)."""
     from oracle import pyoracle
     from tagdust_amd import lib
     g, codes, offs = probes[name]
@@ -70,8 +71,43 @@ def test_probe_exercises_the_model(probes, name):
     seg_type = np.asarray(g["seg_type"]).astype(np.int64)
     bsegs = [j for j in range(int(g["S"])) if seg_type[j] == ord("B")]
     if bsegs:
-        n_barcodes = int(np.asarray(g["n_hmm"])[bsegs[0]]) - 1      # (the last HMM of a barcode segment is the all-N decoy)
+        n_barcodes = int(np.asarray(g["n_hmm"])[bsegs[-1]]) - 1      # (the last HMM of a barcode segment is the all-N decoy)
         ok = (res["read_type"] == 0) & (res["barcode"] >= 0)
-        found = set(res["barcode"][ok].tolist())
+        assert ((res["barcode"][ok] >> 16) == bsegs[-1]).all()
+        found = set((res["barcode"][ok] & 0xFFFF).tolist())
         print(name, "barcodes", len(found), "of", n_barcodes)
         assert len(found) >= min(n_barcodes, 8)
+
+
+def test_probe_combines_the_barcodes_of_two_segments():
+    """Two barcode segments of equal size: were both to take HMM k % nh for the k-th architecture-following read, only the pairs
+    (i, i) would ever be probed.  Later barcode segments step through the combinations instead; decoded by the oracle, the
+    extracted architecture-following reads show at least min(nh1 * nh2, 8) different (first, second) barcode pairs -- the second
+    as extract_reads reports it, the first read off the labels."""
+    from oracle import pyoracle
+    from tagdust_amd import lib
+    rng = np.random.RandomState(5)
+    bars1, bars2 = ["ACAGTG", "CTTGTA", "GGCTAC"], ["TTAGGC", "CATGCA", "AGTCAA"]
+    segs = ["B:" + ",".join(bars1), "S:GT", "B:" + ",".join(bars2), "R:N"]
+    reads = []
+    for i in range(200):
+        s_ = bars1[rng.randint(3)] + "GT" + bars2[rng.randint(3)] + "".join("ACGT"[x] for x in rng.randint(0, 4, rng.randint(20, 50)))
+        reads.append(np.array(["ACGT".index(ch) for ch in s_], np.uint8))
+    offs = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.int64)
+    md, _ = lib.build_model(segs, np.concatenate(reads), offs, 0.05, 0.1)
+    nh1, nh2 = int(md["n_hmm"][0]), int(md["n_hmm"][2])
+    assert nh1 == nh2 == 4
+    codes, offs = lib.spec_probe(md)
+    p = lib.spec_probe_params()
+    res, labels, _ = pyoracle.label_batch(pyoracle.OracleModel(md), codes, offs, p["threshold"], p["minlen"], p["dust"], 4)
+    label = np.asarray(md["label"]).astype(np.int64)
+    pairs = set()
+    for r in range(N_PROBE):
+        if (r & 7) == 7 or res["read_type"][r] != 0:       # (one read in eight ignores the architecture)
+            continue
+        lab = label[labels[offs[r] + r + 1:offs[r + 1] + r + 1]]
+        first = set(((lab >> 16) & 0x7FFF)[(lab & 0xFFFF) == 0].tolist())
+        assert len(first) == 1 and int(res["barcode"][r]) >> 16 == 2
+        pairs.add((first.pop(), int(res["barcode"][r]) & 0xFFFF))
+    print("pairs", sorted(pairs))
+    assert len(pairs) >= min(nh1 * nh2, 8)
