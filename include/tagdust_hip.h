@@ -286,6 +286,11 @@ int td_arch_scores(td_ctx* ctx, const td_model_desc* const* models, int32_t n_mo
 /* ---- counters (the reference's serial outcome counting, barcode_hmm.c:354-384, done on device) ---- */
 int td_counts_reset(td_ctx* ctx);
 int td_counts_get(td_ctx* ctx, int64_t* counts /* [TD_NUM_COUNTERS] */);
+/* -ref: reads per artifact sequence, the reference's reference_fasta->mer_hash (src/barcode_hmm.c:381) -- hits[j] = reads whose
+ * outcome was ((j + 1) << 8) | 5 in TD_MODE_GET_LABEL / TD_MODE_RNA_DUST batches since the filter was set or the counters were
+ * reset, counted on the device behind every such batch (td_run and td_submit alike) while a filter is set.  cap = entries of
+ * hits: at least the filter's n_seq (TD_FAIL below that), the ones beyond it are zeroed; all zeros without a filter. */
+int td_artifact_hits_get(td_ctx* ctx, int64_t* hits, int32_t cap);
 /* The diagnostic words of the development knobs (TD_SPEC_PROFILE, TD_SPEC_PRUNE_STATS, TD_SPEC_ENDSTATS): a tail of their
  * own behind the counters above, so that no knob can disturb what td_counts_get / the all-reduce report.  Reset with the
  * counters.  diag[k] = historical slot 192 + k of DESIGN.md's knob table. */

@@ -126,6 +126,12 @@ typedef struct td_stream_file {
 } td_stream_file;
 int td_stream_run_multi(const td_stream_file* files, int32_t n_files, int32_t n_devices, const char* out_prefix, int32_t dust,
                         const td_stream_opts* opts, td_stream_stats* stats, int64_t* counts /* [TD_NUM_COUNTERS] */);
+/* The same with one more optional output: artifact_hits[n_artifacts] (may be NULL) receives, per -ref sequence, the records whose
+ * COMBINED outcome is that sequence's ((index + 1) << 8) | 5 -- the controller's reference_fasta->mer_hash (:344-349, :381).  A
+ * record that hits in two files counts once, for the larger outcome. */
+int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_files, int32_t n_devices, const char* out_prefix, int32_t dust,
+                             const td_stream_opts* opts, td_stream_stats* stats, int64_t* counts, int64_t* artifact_hits,
+                             int32_t n_artifacts);
 /* td_stream_run keeps the page-locked batch buffers of its last run (at most 1 GiB) for the next run of the process --
  * page-locking runs at about 1 GB/s, most of what a short file costs; this frees them. */
 void td_stream_release(void);

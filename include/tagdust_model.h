@@ -56,6 +56,17 @@ int  td_sequence_stats(const td_arch* arch, const uint8_t* codes, const int64_t*
 int  td_sequence_stats_window(const td_arch* arch, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
                               int32_t matchstart, int32_t matchend, td_seq_stats* out);
 
+/* ... over the first min(n_reads, scan_limit) reads: get_sequence_stats consumes batches of num_query records until more than
+ * 1 000 000 were seen (io.c:184) -- 1 000 001 reads with the release build's batches (what the two calls above use), 1 001 000
+ * with the 1000-record batches of the -DRTEST builds */
+int  td_sequence_stats_limit(const td_arch* arch, const uint8_t* codes, const int64_t* offs, int64_t n_reads, int64_t scan_limit,
+                             int32_t matchstart, int32_t matchend, td_seq_stats* out);
+/* The same statistics with the counting on the device of `ctx` (base histogram, read lengths, the two linker scans; exact
+ * 64-bit integer sums) and the same finish on the host: every field equals td_sequence_stats_limit's bit for bit.  Needs no
+ * model on the context and leaves its model, resident batch and counters alone.  n_reads = 0 is TD_FAIL. */
+int  td_sequence_stats_device(td_ctx* ctx, const td_arch* arch, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                              int64_t scan_limit, int32_t matchstart, int32_t matchend, td_seq_stats* out);
+
 /* sequencer_error_rate = param->sequencer_error_rate (-e, default 0.05; forced to 0.05 by calibration, calibrateQ.c:65),
  * indel_frequency = param->indel_frequency (-i, default 0.1) */
 int  td_model_build(const td_arch* arch, const td_seq_stats* stats, float sequencer_error_rate, float indel_frequency,

@@ -73,6 +73,8 @@ int  td_multi_decode(td_multi* m, const void* bases, int32_t is_ascii, const int
 /* Counters summed over the devices (all-reduced on the devices with RCCL when the communicator exists). */
 int  td_multi_counts(td_multi* m, int64_t* counts /* [TD_NUM_COUNTERS] */);
 int  td_multi_counts_reset(td_multi* m);
+/* td_artifact_hits_get summed over the devices, on the host (the all-reduce above keeps its TD_NUM_COUNTERS words) */
+int  td_multi_artifact_hits(td_multi* m, int64_t* hits, int32_t cap);
 /* 1 when td_multi_counts goes through ncclAllReduce, 0 when it sums on the host (one device without TD_MULTI_FORCE_RCCL,
  * or a device listed twice) */
 int32_t td_multi_uses_rccl(const td_multi* m);

@@ -1,0 +1,131 @@
+/*
+ * tagdust_run.h -- a whole TagDust2 run on this library alone: files in, demultiplexed files out (part of libtagdust_hip.so,
+ * plain C; the `tagdust-hip` executable is a main() of a few lines over it).  What the reference does in
+ *
+ *   main()                      src/main.c:95-217        (the checks, "Start Run")
+ *   interface()                 src/interface.c:49-480   (options, defaults, banner and cmd: line, the multiread rule)
+ *   hmm_controller_multiple()   src/barcode_hmm.c:51-460 (architectures per file, statistics, thresholds, models, the run, the log)
+ *   test_architectures()        src/test_architectures.c:20-289 (the -arch file)
+ *   free_param()                src/interface.c:709-726  (<out>_logfile.txt)
+ *
+ * composed from td_arch_parse, td_compare_architectures, td_sequence_stats_device, td_estimate_threshold, td_model_build,
+ * td_set_artifacts and the streaming pipelines td_stream_run / td_stream_run_multi.  The output files equal the reference
+ * binary's byte for byte.  Every entry point returns TD_OK / TD_FAIL and never calls exit(); the message of a failed call of this
+ * header is in td_run_last_error() (per thread) and, for td_run_execute, in the report.
+ */
+#ifndef TAGDUST_RUN_H
+#define TAGDUST_RUN_H
+
+#include <stddef.h>
+#include <stdint.h>
+#include "tagdust_hip.h"
+#include "tagdust_io.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define TD_RUN_MAX_SEGMENTS 10   /* options -1 .. -10 */
+#define TD_RUN_MAX_FILES    8    /* input files of one run (td_stream_run_multi's limit) */
+#define TD_RUN_MAX_DEVICES  16
+
+/* struct parameters (src/interface.h:90-160) as far as a `tagdust` run uses it; defaults as interface.c:66-129 */
+typedef struct td_run_opts {
+	char*    segments[TD_RUN_MAX_SEGMENTS];  /* -1 .. -10: "B:ACGT,TTGA", "R:N", ...; NULL = not given */
+	char*    arch_file;              /* -arch */
+	char*    outfile;                /* -o / -out */
+	int32_t  num_threads;            /* -t                     [8]  (thread ranges of the -ref filter and of the -arch score sums) */
+	float    confidence_threshold;   /* -Q / -q / -threshold   [0 = calibrate]; a given value switches calibration off and every
+	                                    file then runs with threshold 0 (barcode_hmm.c:102, :190-200, :314) */
+	float    sequencer_error_rate;   /* -e                     [0.05]; calibration forces 0.05 (calibrateQ.c:65, :117) */
+	float    indel_frequency;        /* -i                     [0.1] */
+	int32_t  minlen;                 /* -minlen                [16] */
+	int32_t  dust;                   /* -dust                  [100], 0 = off */
+	char*    reference_fasta;        /* -ref */
+	int32_t  filter_error;           /* -fe                    [2] */
+	int32_t  matchstart, matchend;   /* -start (stored as atoi - 1, interface.c:286), -end   [-1, -1] */
+	uint32_t seed;                   /* -seed                  [0 = time based, calibrateQ.c:27-31] */
+	int32_t  n_infiles;
+	char**   infile;
+	/* this library's own */
+	int32_t  n_devices;              /* --devices 0,1          [1] */
+	int32_t  devices[TD_RUN_MAX_DEVICES];   /*                 [{0}] */
+	int32_t  flavour;                /* --rtest: 0 = the release build's constants (batches of 1 000 001 records, 400 000 calibration
+	                                    reads on the C library's rand()); 1 = those of the -DRTEST builds (1000 / 4000 / the private
+	                                    generator, misc.c:878-887) */
+	int32_t  host_threads;           /* --host-threads         [0 = td_stream_opts picks] */
+	int32_t  batch_reads;            /* --batch-reads          [0 = td_stream_opts picks; 1000 in the RTEST flavour] */
+	int32_t  sync_compile;           /* --sync-compile: 1 = compile the model kernel before decoding; 0 = option "async_compile" */
+	int32_t  stats_on_host;          /* --stats-on-host: 1 = td_sequence_stats_limit instead of td_sequence_stats_device */
+	int32_t  force;                  /* --force: overwrite existing output files */
+	int32_t  dry_run;                /* --dry-run: print the plan and stop */
+	int32_t  help, version;          /* -h / -help, -v / -version */
+	int32_t  echo_log;               /* every log message also goes to stderr as it is made, as the reference does (the executable sets it) */
+	int32_t  argc;                   /* the command line as given, for the log's "cmd:" line */
+	char**   argv;
+} td_run_opts;
+
+td_run_opts* td_run_opts_new(void);            /* the defaults */
+void td_run_opts_free(td_run_opts* opts);
+const char* td_run_last_error(void);
+
+/* The reference's option table (interface.c:133-183) with one or two leading dashes, no abbreviations; an argument that is no
+ * option (or is "-") is an input file, wherever it stands.  An option the reference parses but this library does not implement
+ * (-show_finger_seq, -train, -exact5, -join, -split, -name / -format, -f / -filter, -a, -l / -log, -p, -simulation, -numbarcode,
+ * every -sim_*) fails with a message that names it, as does anything unknown: nothing is silently ignored.  argv[0] is the program name. */
+int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap);
+/* the usage text / the version line the executable prints */
+const char* td_run_usage(void);
+const char* td_run_version(void);
+
+/* ---- the decisions of a run that need no data and no GPU ----
+ * main.c:103-125 (an architecture or an arch file, -o, the files exist), per file where its architecture comes from
+ * (barcode_hmm.c:105-129: file 0 the command line's segments when there are any, else the arch file's best candidate, else R:N),
+ * "barcodes in more than one file" (:141-146), the number of output reads and the output files' names (td_writer_open's), the
+ * existing-output check (io.c:633-691: made when a file holds a barcode, like the reference's; skipped with `force`), the
+ * multiread rule (interface.c:441-450: DUST and -ref off, with a warning, when the command line's architecture has two or more
+ * R segments).  What depends on the arch file's choice is decided again by td_run_execute once the choice is made. */
+typedef struct td_run_plan_t td_run_plan_t;   /* (the function below has the plain name) */
+int  td_run_plan(const td_run_opts* opts, td_run_plan_t** out);
+void td_run_plan_free(td_run_plan_t* plan);
+/* the plan as text, one line per decision ("key: value"); returns the length, copies at most cap - 1 bytes + NUL */
+int64_t td_run_plan_describe(const td_run_plan_t* plan, char* buf, int64_t cap);
+/* What the run decides once every file's architecture is known (td_run_execute does, after the arch file's choice): the output
+ * files for these per-file architectures ("-1 B:ACGT,TTGA -2 R:N" each), one name per line, named after the barcode file's
+ * architecture with one set per read segment of the whole run.  -1 (td_run_last_error) for barcodes in two files, no read
+ * segment at all, or -- without opts->force -- an output file that exists. */
+int64_t td_run_output_files_describe(const td_run_opts* opts, const char* const* architectures, int32_t n_files, char* buf, int64_t cap);
+/* test_architectures.c:72-111 on its own: the candidates of an arch file, one "-1 X -2 Y ..." line each (as "Using:" prints them) */
+int64_t td_run_arch_file_describe(const char* arch_file, char* buf, int64_t cap);
+
+/* ---- the run ---- */
+typedef struct td_run_report {
+	char     error[1024];                     /* empty on success */
+	int64_t  counts[TD_NUM_COUNTERS];         /* the controller's counting over the combined records (barcode_hmm.c:354-384) */
+	int32_t  n_artifacts;                     /* -ref sequences */
+	int64_t* artifact_hits;                   /* [n_artifacts] reference_fasta->mer_hash */
+	char**   artifact_names;                  /* [n_artifacts] reference_fasta->sn */
+	int32_t  n_files;
+	float    thresholds[TD_RUN_MAX_FILES];    /* param->confidence_thresholds */
+	float    selected_threshold;              /* what the log's "selected threshold" line shows: the last file's */
+	char*    architectures[TD_RUN_MAX_FILES]; /* "-1 B:ACGT,TTGA -2 R:N" */
+	td_stream_stats stream;
+	double   arch_s, stats_s, calibration_s, compile_wait_s, stream_s;   /* seconds: -arch selection, statistics, calibration,
+	                                              td_model_upload (the compile, unless it runs in the background), streaming */
+	int32_t  stats_on_device;                 /* 1: the statistics were counted on the device */
+	char*    log;                             /* the text of <out>_logfile.txt */
+} td_run_report;
+/* In the controller's order: architectures per file, statistics over each file's head, thresholds, models, the run, the log.
+ * A failure before the first batch leaves no output files behind; one during the run leaves them as they are and says so.  The
+ * log written so far goes to <out>_logfile.txt either way.  report may be NULL; free its members with td_run_report_clear. */
+int  td_run_execute(const td_run_opts* opts, td_run_report* report);
+void td_run_report_clear(td_run_report* report);
+/* The controller's summary block (barcode_hmm.c:387-430) from a report: "Done.", the input files, the counts, "%0.1f%%\textracted",
+ * one "count\tname" line per artifact sequence that was hit -- the messages as they enter the log, without their time stamps,
+ * each ending in '\n'.  Returns the length, copies at most cap - 1 bytes + NUL. */
+int64_t td_run_format_summary(const td_run_opts* opts, const td_run_report* report, char* buf, int64_t cap);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

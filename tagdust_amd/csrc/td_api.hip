@@ -25,11 +25,13 @@
 #include <vector>
 
 #include "../../include/tagdust_hip.h"
+#include "../../include/tagdust_model.h"
 #include "td_device.h"
 #include "td_jit.h"
 #include "td_stage.h"
 #include "td_host_inner.h"
 #include "td_rnadust.h"
+#include "td_stats.h"
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t td_launch_decode(const TdKernelArgs* ka, hipStream_t stream);   // library-internal
 extern "C" __attribute__((visibility("hidden"))) int td_kernel_block_threads(void);
@@ -96,6 +98,7 @@ struct TdDecoded {
 	bool ran = false;
 	float last_ms = -1.0f;
 	int32_t runs_cap = 0;       // entries per read in d_runs (0: the last launch left no label runs)
+	bool hits_queued = false;   // the per-artifact hit count is queued behind the launch (ev_hits): it reads d_out like the finish kernel
 };
 struct TdFetch {
 	td_read_result* u_res = nullptr; int8_t* u_labels = nullptr; uint8_t* u_seq = nullptr;   // the caller's output buffers
@@ -136,7 +139,7 @@ struct TdSlot : TdStaged, TdDecoded, TdFetch {
 	uint8_t* h_res = nullptr;      size_t cap_h_res = 0;
 	uint8_t* h_seq = nullptr;      size_t cap_h_seq = 0;
 	int8_t*  h_lab = nullptr;      size_t cap_h_lab = 0;
-	hipEvent_t ev_up = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_done = nullptr, ev_down = nullptr, ev_pack = nullptr;
+	hipEvent_t ev_up = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_done = nullptr, ev_down = nullptr, ev_pack = nullptr, ev_hits = nullptr;
 };
 
 // Host threads a context may use for its copies between pageable caller memory and pinned staging: TD_HOST_THREADS, else the
@@ -307,6 +310,7 @@ struct td_ctx {
 	uint8_t* d_art_text = nullptr; int32_t* d_art_index = nullptr;
 	uint32_t* d_art_pk = nullptr; int32_t* d_art_seq = nullptr;   // the same text as 2-bit codes for TD_MODE_RNA_DUST (td_rnadust.hip)
 	int32_t art_n = 0, art_fe = 0, art_threads = 1;
+	unsigned long long* d_art_hits = nullptr;   // [art_n] reads per artifact sequence (td_artifact_hits_get)
 	int64_t win_first = 0, win_total = 0;   // td_set_batch_window
 	int32_t match_start = 0, match_len = 0;  // td_set_window (-start / -end); match_len = 0: whole reads
 	// batches: slot 0 is the resident batch of the synchronous calls; td_submit rotates over pipeline_depth slots
@@ -484,7 +488,7 @@ extern "C" void td_ctx_destroy(td_ctx* c)
 	if (c->s_up) (void)hipStreamSynchronize(c->s_up);
 	if (c->s_down) (void)hipStreamSynchronize(c->s_down);
 	void* bufs[] = { c->d_hdr, c->d_cols, c->d_hinfo, c->d_pred_off, c->d_pred_idx, c->d_logsum, c->d_counters,
-	                 c->d_ws, c->d_art_text, c->d_art_index, c->d_art_pk, c->d_art_seq, c->d_prune, c->d_tile_next, c->d_ws2, c->d_tile_next2 };
+	                 c->d_ws, c->d_art_text, c->d_art_index, c->d_art_pk, c->d_art_seq, c->d_art_hits, c->d_prune, c->d_tile_next, c->d_ws2, c->d_tile_next2 };
 	for (void* p : bufs) if (p) (void)hipFree(p);
 	for (int k = 0; k < TD_MAX_PIPELINE; k++) slot_release(c->slots[k]);
 	if (c->ev_origin) (void)hipEventDestroy(c->ev_origin);
@@ -1053,6 +1057,7 @@ extern "C" int td_set_artifacts(td_ctx* c, const uint8_t* string, const int32_t*
 	if (c->d_art_index) { HIPCHK(c, hipFree(c->d_art_index)); c->d_art_index = nullptr; }
 	if (c->d_art_pk) { HIPCHK(c, hipFree(c->d_art_pk)); c->d_art_pk = nullptr; }
 	if (c->d_art_seq) { HIPCHK(c, hipFree(c->d_art_seq)); c->d_art_seq = nullptr; }
+	if (c->d_art_hits) { HIPCHK(c, sync_compute(c)); HIPCHK(c, hipFree(c->d_art_hits)); c->d_art_hits = nullptr; }   // (a count may still be queued)
 	c->art_n = 0;
 	if (n_seq <= 0) return TD_OK;
 	if (!string || !s_index) return fail(c, "td_set_artifacts: null argument");
@@ -1081,6 +1086,8 @@ extern "C" int td_set_artifacts(td_ctx* c, const uint8_t* string, const int32_t*
 	HIPCHK(c, hipMalloc((void**)&c->d_art_seq, seq.size() * 4));
 	HIPCHK(c, hipMemcpy(c->d_art_pk, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
 	HIPCHK(c, hipMemcpy(c->d_art_seq, seq.data(), seq.size() * 4, hipMemcpyHostToDevice));
+	HIPCHK(c, hipMalloc((void**)&c->d_art_hits, sizeof(unsigned long long) * (size_t)n_seq));
+	HIPCHK(c, hipMemset(c->d_art_hits, 0, sizeof(unsigned long long) * (size_t)n_seq));
 	c->art_n = n_seq; c->art_fe = filter_error; c->art_threads = n_threads;
 	return TD_OK;
 }
@@ -1174,6 +1181,7 @@ static int slot_events(td_ctx* c, TdSlot& s)
 	HIPCHK(c, hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
 	HIPCHK(c, hipEventCreateWithFlags(&s.ev_down, hipEventDisableTiming));
 	HIPCHK(c, hipEventCreateWithFlags(&s.ev_pack, hipEventDisableTiming));
+	HIPCHK(c, hipEventCreateWithFlags(&s.ev_hits, hipEventDisableTiming));
 	return TD_OK;
 }
 
@@ -1184,7 +1192,7 @@ static void slot_release(TdSlot& s)
 	for (void* p : dev) if (p) (void)hipFree(p);
 	void* pinned[] = { s.h_raw, s.h_offs, s.h_res, s.h_seq, s.h_lab, s.h_keepo, s.h_rle };
 	for (void* p : pinned) if (p) (void)hipHostFree(p);
-	hipEvent_t ev[] = { s.ev_up, s.ev_k0, s.ev_k1, s.ev_done, s.ev_down, s.ev_pack };
+	hipEvent_t ev[] = { s.ev_up, s.ev_k0, s.ev_k1, s.ev_done, s.ev_down, s.ev_pack, s.ev_hits };
 	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
 	s = TdSlot();
 }
@@ -1438,6 +1446,18 @@ static int rle_capacity(const td_ctx* c)
 // the decode kernel over a staged slot
 static int slot_rna_dust(td_ctx* c, TdSlot& s);
 
+// -ref: the batch's reads per artifact sequence, added to the context's running hits on the batch's stream right behind the
+// launch that left out_type (and behind ev_k1, so that the kernel times stay the launch's own).  Only called while a filter is
+// set: a run without -ref launches nothing here.  The finish kernel waits for ev_hits, so that a slot whose batch has been
+// waited for is no longer read by this count either.
+static int slot_count_hits(td_ctx* c, TdSlot& s, const int32_t* out_type)
+{
+	HIPCHK(c, td_stage_art_hits(out_type, s.n_reads, c->art_n, c->d_art_hits, s.cs));
+	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));
+	s.hits_queued = true;
+	return TD_OK;
+}
+
 static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 {
 	if (mode == TD_MODE_RNA_DUST) return slot_rna_dust(c, s);
@@ -1529,6 +1549,7 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 		c->batches_generic++;
 	}
 	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
+	if (ka.art_n > 0 && slot_count_hits(c, s, ka.out_type) != TD_OK) return TD_FAIL;
 	s.ran = true;
 	s.last_ms = -1.0f;
 	c->last_slot = (int)(&s - c->slots);
@@ -1565,6 +1586,7 @@ static int slot_rna_dust(td_ctx* c, TdSlot& s)
 	HIPCHK(c, hipEventRecord(s.ev_k0, s.cs));
 	HIPCHK(c, td_launch_rna_dust(ra, s.cs));
 	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
+	if (ra.art_n > 0 && slot_count_hits(c, s, ra.out_type) != TD_OK) return TD_FAIL;
 	s.ran = true;
 	s.last_ms = -1.0f;
 	c->last_slot = (int)(&s - c->slots);
@@ -1642,7 +1664,7 @@ static int slot_fetch_begin(td_ctx* c, TdSlot& s, td_read_result* res, int8_t* l
 	s.sb.runs = (s.use_rle && s.runs_cap > 0) ? s.d_runs : nullptr;
 	s.sb.rle_overflow = s.use_rle ? (int32_t*)(s.d_rle + (size_t)n * (size_t)s.rle_cap) : nullptr;
 	s.sb.runs_overflow = (s.use_rle && s.runs_cap > 0) ? (const int32_t*)(s.d_runs + (size_t)s.n_tiles * (size_t)s.runs_cap * TD_WAVE) : nullptr;
-	if (s.fin != s.cs) HIPCHK(c, hipStreamWaitEvent(s.fin, s.ev_k1, 0));
+	if (s.fin != s.cs) HIPCHK(c, hipStreamWaitEvent(s.fin, s.hits_queued ? s.ev_hits : s.ev_k1, 0));
 	HIPCHK(c, td_stage_finish(s.sb, s.fin));
 	if (deferred) HIPCHK(c, hipEventRecord(s.ev_done, s.fin));
 	else if (slot_issue_copies(c, s, s.fin) != TD_OK) return TD_FAIL;
@@ -1987,6 +2009,7 @@ extern "C" int td_counts_reset(td_ctx* c)
 	HIPCHK(c, hipSetDevice(c->device));
 	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));   // (kernels of pipelined batches may still be counting)
 	HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(unsigned long long) * TD_COUNTER_WORDS, c->stream));
+	if (c->d_art_hits) HIPCHK(c, hipMemsetAsync(c->d_art_hits, 0, sizeof(unsigned long long) * (size_t)c->art_n, c->stream));
 	if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream));
 	return TD_OK;
 }
@@ -2009,4 +2032,35 @@ extern "C" int td_diag_get(td_ctx* c, int64_t* diag)
 	return TD_OK;
 }
 
+extern "C" int td_artifact_hits_get(td_ctx* c, int64_t* hits, int32_t cap)
+{
+	if (!c || !hits || cap < 0) return TD_FAIL;
+	if (cap < c->art_n) return fail(c, "td_artifact_hits_get: room for %d sequences, the filter has %d", cap, c->art_n);
+	memset(hits, 0, sizeof(int64_t) * (size_t)cap);
+	if (c->art_n == 0) return TD_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	HIPCHK(c, hipMemcpy(hits, c->d_art_hits, sizeof(int64_t) * (size_t)c->art_n, hipMemcpyDeviceToHost));
+	return TD_OK;
+}
+
 extern "C" void* td_counts_device_ptr(td_ctx* c) { return c ? (void*)c->d_counters : nullptr; }
+
+// ---------------------------------------------------------------------------------------------------------
+// sequence statistics with the counting on the device (td_stats.hip); the finish is td_sequence_stats' own
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int td_sequence_stats_device(td_ctx* c, const td_arch* arch, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                                        int64_t scan_limit, int32_t matchstart, int32_t matchend, td_seq_stats* out)
+{
+	if (!c) return TD_FAIL;
+	if (!arch || !codes || !offs || !out) return fail(c, "td_sequence_stats_device: null argument");
+	if (n_reads <= 0 || scan_limit <= 0) return fail(c, "td_sequence_stats_device: no reads to take the statistics over (the reference divides by zero)");
+	std::vector<uint8_t> five, three;
+	td_stats_linkers(arch, five, three);
+	TdSeqCounts k;
+	char err[512] = "";
+	if (td_stats_count_device(c->device, five, three, codes, offs, n_reads, scan_limit, &k, err, sizeof err) != TD_OK) return fail(c, "%s", err);
+	td_stats_finish(arch, k, out);
+	td_stats_apply_window(out, matchstart, matchend);
+	return TD_OK;
+}

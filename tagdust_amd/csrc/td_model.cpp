@@ -18,6 +18,7 @@
 
 #include "../../include/tagdust_model.h"
 #include "td_jit.h"
+#include "td_stats.h"
 
 namespace {
 
@@ -252,61 +253,84 @@ extern "C" void td_arch_free(td_arch* a)
 // ---------------------------------------------------------------------------------------------------------
 // get_sequence_stats(), io.c:52-300
 // ---------------------------------------------------------------------------------------------------------
-static int sequence_stats_limit(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads, td_seq_stats* ssi, int64_t scan_limit);
+// "count": everything that looks at the reads.  Every quantity is an integer (the reference's doubles hold counts).
+static int sequence_stats_count(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads, int64_t scan_limit, TdSeqCounts* k);
+
+// the reference reads batches of num_query reads and stops once more than 1 000 000 were seen (io.c:184): scan_limit is
+// 1 000 001 with the release build's batches of 1 000 001 records, 1 001 000 with the 1000 of its -DRTEST builds
+static int sequence_stats_limit(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads, td_seq_stats* ssi, int64_t scan_limit)
+{
+	if (!a || !codes || !offs || !ssi || n_reads < 0) return TD_FAIL;
+	TdSeqCounts k;
+	if (sequence_stats_count(a, codes, offs, n_reads, scan_limit, &k) != TD_OK) return TD_FAIL;
+	td_stats_finish(a, k, ssi);
+	return TD_OK;
+}
 
 extern "C" int td_sequence_stats(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads, td_seq_stats* ssi)
 {
-	// the reference reads batches of num_query = 1 000 001 reads and stops once more than 1 000 000 were seen (io.c:184)
 	return sequence_stats_limit(a, codes, offs, n_reads, ssi, 1000001);
 }
 
 // with -start / -end the average length is the window's (io.c:258-260); everything else is taken over the whole reads
-extern "C" int td_sequence_stats_window(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
-                                        int32_t matchstart, int32_t matchend, td_seq_stats* ssi)
+void td_stats_apply_window(td_seq_stats* ssi, int32_t matchstart, int32_t matchend)
 {
-	if (td_sequence_stats(a, codes, offs, n_reads, ssi) != TD_OK) return TD_FAIL;
 	if (matchstart != -1 || matchend != -1) {
 		// (matchend - matchstart) * total_read / total_read, rounded like every average (io.c:259-261)
 		ssi->average_length = (int)floor((double)(matchend - matchstart) + 0.5);
 	}
+}
+
+extern "C" int td_sequence_stats_window(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                                        int32_t matchstart, int32_t matchend, td_seq_stats* ssi)
+{
+	if (td_sequence_stats(a, codes, offs, n_reads, ssi) != TD_OK) return TD_FAIL;
+	td_stats_apply_window(ssi, matchstart, matchend);
 	return TD_OK;
 }
 
-static int sequence_stats_limit(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads, td_seq_stats* ssi, int64_t scan_limit)
+extern "C" int td_sequence_stats_limit(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads, int64_t scan_limit,
+                                       int32_t matchstart, int32_t matchend, td_seq_stats* ssi)
 {
-	if (!a || !codes || !offs || !ssi || n_reads < 0) return TD_FAIL;
-	memset(ssi, 0, sizeof *ssi);
-	for (int i = 0; i < 5; i++) ssi->background[i] = 1.0;
-	int five_len = 0, three_len = 0;
-	std::vector<int> five, three;
+	if (scan_limit < 1) return TD_FAIL;
+	if (sequence_stats_limit(a, codes, offs, n_reads, ssi, scan_limit) != TD_OK) return TD_FAIL;
+	td_stats_apply_window(ssi, matchstart, matchend);
+	return TD_OK;
+}
+
+void td_stats_linkers(const td_arch* a, std::vector<uint8_t>& five, std::vector<uint8_t>& three)
+{
+	five.clear(); three.clear();
 	const int last = a->n_segments - 1;
-	if (a->type[0] == 'P') {
-		five_len = a->seq_len[0];
-		ssi->expected_5_len = five_len;
-		for (int i = 0; i < five_len; i++) five.push_back(nuc_code(a->seqs[0][0][i]));
-	}
-	if (a->type[last] == 'P') {
-		three_len = a->seq_len[last];
-		ssi->expected_3_len = three_len;
-		for (int i = 0; i < three_len; i++) three.push_back(nuc_code(a->seqs[last][0][i]));
-	}
-	double five_s0 = 0, five_s1 = 0, five_s2 = 0, three_s0 = 0, three_s1 = 0, three_s2 = 0;
+	if (a->type[0] == 'P')
+		for (int i = 0; i < a->seq_len[0]; i++) five.push_back((uint8_t)nuc_code(a->seqs[0][0][i]));
+	if (a->type[last] == 'P')
+		for (int i = 0; i < a->seq_len[last]; i++) three.push_back((uint8_t)nuc_code(a->seqs[last][0][i]));
+}
+
+static int sequence_stats_count(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads, int64_t scan_limit, TdSeqCounts* k)
+{
+	*k = TdSeqCounts();
+	std::vector<uint8_t> five, three;
+	td_stats_linkers(a, five, three);
+	const int five_len = (int)five.size(), three_len = (int)three.size();
 	const int64_t total_read = n_reads < scan_limit ? n_reads : scan_limit;
+	k->n_reads = total_read;
 	for (int64_t r = 0; r < total_read; r++) {
 		const uint8_t* seq = codes + offs[r];
 		const int len = (int)(offs[r + 1] - offs[r]);
 		// seq[len] is the loader's 0 terminator (io.c:1759); anything further out is outside the reference's domain
-		auto at = [&](int k) -> int { return (k >= 0 && k < len) ? seq[k] : (k == len ? 0 : -1); };
-		if (len > ssi->max_seq_len) ssi->max_seq_len = len;
-		ssi->average_length += len;
-		for (int j = 0; j < len; j++) ssi->background[seq[j] > 4 ? 4 : seq[j]] += 1.0f;
+		auto at = [&](int i) -> int { return (i >= 0 && i < len) ? seq[i] : (i == len ? 0 : -1); };
+		if (len > k->len_max) k->len_max = len;
+		k->len_sum += len;
+		for (int j = 0; j < len; j++) k->base[seq[j] > 4 ? 4 : seq[j]]++;
 		if (five_len) { // longest exact match of a linker suffix against the read start, > 3 nt (:141-156)
 			for (int j = 0; j <= five_len; j++) {
 				int c;
 				for (c = 0; c < five_len - j; c++)
 					if (at(c) != five[j + c]) break;
 				if (c == five_len - j && c > 3) {
-					five_s0++; five_s1 += five_len - j; five_s2 += (five_len - j) * (five_len - j);
+					k->five[0]++; k->five[1] += five_len - j; k->five[2] += (five_len - j) * (five_len - j);
 					break;
 				}
 			}
@@ -317,12 +341,27 @@ static int sequence_stats_limit(const td_arch* a, const uint8_t* codes, const in
 				for (c = 0; c < three_len - j; c++)
 					if (at(len - (three_len - j - c)) != three[c]) break;
 				if (c == three_len - j && c > 3) {
-					three_s0++; three_s1 += three_len - j; three_s2 += (three_len - j) * (three_len - j);
+					k->three[0]++; k->three[1] += three_len - j; k->three[2] += (three_len - j) * (three_len - j);
 					break;
 				}
 			}
 		}
 	}
+	return TD_OK;
+}
+
+// "finish": the counts as the doubles the reference accumulated them in, then io.c:190-270
+void td_stats_finish(const td_arch* a, const TdSeqCounts& k, td_seq_stats* ssi)
+{
+	memset(ssi, 0, sizeof *ssi);
+	const int last = a->n_segments - 1;
+	const int five_len = a->type[0] == 'P' ? a->seq_len[0] : 0, three_len = a->type[last] == 'P' ? a->seq_len[last] : 0;
+	ssi->expected_5_len = five_len;
+	ssi->expected_3_len = three_len;
+	ssi->max_seq_len = (int32_t)k.len_max;
+	for (int i = 0; i < 5; i++) ssi->background[i] = 1.0 + (double)k.base[i];   // pseudocount 1 (io.c:117-119)
+	const double five_s0 = (double)k.five[0], five_s1 = (double)k.five[1], five_s2 = (double)k.five[2];
+	const double three_s0 = (double)k.three[0], three_s1 = (double)k.three[1], three_s2 = (double)k.three[2];
 	if (five_len) {
 		if (five_s0 <= 1) { ssi->mean_5_len = ssi->expected_5_len; ssi->stdev_5_len = 1.0; }
 		else {
@@ -339,11 +378,10 @@ static int sequence_stats_limit(const td_arch* a, const uint8_t* codes, const in
 			if (!ssi->stdev_3_len) ssi->stdev_3_len = 10000.0;
 		}
 	} else { ssi->mean_3_len = -1.0; ssi->stdev_3_len = -1.0; }
-	ssi->average_length = (int)floor((double)ssi->average_length / (double)total_read + 0.5); // :261
+	ssi->average_length = (int)floor((double)k.len_sum / (double)k.n_reads + 0.5); // :261
 	double sum = 0.0;
 	for (int i = 0; i < 5; i++) sum += ssi->background[i];
 	for (int i = 0; i < 5; i++) ssi->background[i] = p2sp(ssi->background[i] / sum); // :268-270 (float-valued)
-	return TD_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------

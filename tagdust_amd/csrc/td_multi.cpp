@@ -358,6 +358,19 @@ extern "C" int td_multi_counts_reset(td_multi* m)
 	return TD_OK;
 }
 
+// the contexts' own running hits, read back and added on the host: a handful of words per device, once per run -- no collective
+extern "C" int td_multi_artifact_hits(td_multi* m, int64_t* hits, int32_t cap)
+{
+	if (!m || !hits || cap < 0) return TD_FAIL;
+	memset(hits, 0, sizeof(int64_t) * (size_t)cap);
+	std::vector<int64_t> part((size_t)cap);
+	for (td_ctx* c : m->ctx) {
+		if (td_artifact_hits_get(c, part.data(), cap) != TD_OK) return mfail(m, "%s", td_last_error(c));
+		for (int32_t j = 0; j < cap; j++) hits[j] += part[(size_t)j];
+	}
+	return TD_OK;
+}
+
 extern "C" int td_multi_counts(td_multi* m, int64_t* counts)
 {
 	if (!m || !counts) return TD_FAIL;

@@ -1,0 +1,903 @@
+// td_run.cpp -- the whole-run driver (include/tagdust_run.h): what the reference's main() (src/main.c:95-217), interface()
+// (src/interface.c:49-480), hmm_controller_multiple() (src/barcode_hmm.c:51-460), test_architectures()
+// (src/test_architectures.c:20-289) and free_param() (src/interface.c:709-726) do, on this library's own entry points.
+// Host code; the device work is behind td_sequence_stats_device, td_compare_architectures, td_estimate_threshold and the
+// streaming pipelines.
+#include <ctype.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <time.h>
+#include <unistd.h>
+
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/tagdust_run.h"
+#include "../../include/tagdust_multi.h"
+#include "td_io_internal.h"
+
+namespace {
+
+thread_local std::string g_run_error;
+
+int run_fail(const char* fmt, ...)
+{
+	char buf[1024];
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(buf, sizeof buf, fmt, ap);
+	va_end(ap);
+	g_run_error = buf;
+	return TD_FAIL;
+}
+
+double now_s()
+{
+	struct timespec ts;
+	clock_gettime(CLOCK_MONOTONIC, &ts);
+	return (double)ts.tv_sec + (double)ts.tv_nsec * 1e-9;
+}
+
+char* dup_str(const char* s) { return s ? strdup(s) : nullptr; }
+bool file_exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0; }   // misc.c:file_exists
+
+int64_t copy_out(const std::string& s, char* buf, int64_t cap)
+{
+	if (buf && cap > 0) {
+		const int64_t n = std::min<int64_t>((int64_t)s.size(), cap - 1);
+		memcpy(buf, s.data(), (size_t)n);
+		buf[n] = 0;
+	}
+	return (int64_t)s.size();
+}
+
+// ---- architectures ----
+struct ArchDeleter { void operator()(td_arch* a) const { td_arch_free(a); } };
+typedef std::unique_ptr<td_arch, ArchDeleter> ArchPtr;
+
+// segments as "-1 B:ACGT -2 R:N" (pretty_print_selected_architecture's form, without "Using: ")
+std::string segments_text(const std::vector<std::string>& segs)
+{
+	std::string s;
+	for (size_t k = 0; k < segs.size(); k++) {
+		if (segs[k].empty()) continue;
+		if (!s.empty()) s += ' ';
+		s += '-' + std::to_string(k + 1) + ' ' + segs[k];
+	}
+	return s;
+}
+
+// QC_read_structure (interface.c:759-829) as far as it can fail, and td_arch_parse's own checks: no segment skipped, one length per segment
+bool parse_arch(const std::vector<std::string>& segs, ArchPtr& out, std::string& why)
+{
+	if (segs.empty()) { why = "ERROR: No read architecture found."; return false; }
+	for (size_t k = 0; k < segs.size(); k++) {
+		const std::string& s = segs[k];
+		if (s.empty()) { why = "ERROR: a hmm building lock was skipped??"; return false; }
+		if (!strchr("RGOPSFB", s[0])) { why = std::string("Segment type :") + s[0] + " not recognized."; return false; }
+		if (s.size() < 2 || s[1] != ':') { why = "Some problem with parsing an HMM segment: " + s + "."; return false; }
+		if (s[0] != 'R') {
+			size_t len = std::string::npos, start = 2;
+			for (size_t p = 2; p <= s.size(); p++)
+				if (p == s.size() || s[p] == ',') {
+					if (len != std::string::npos && p - start != len) { why = "ERROR: the sequences in the same segment have to have the same length."; return false; }
+					len = p - start; start = p + 1;
+				}
+			if (len == 0 || len == std::string::npos) { why = "Some problem with parsing an HMM segment: " + s + "."; return false; }
+		}
+	}
+	std::vector<const char*> p;
+	for (auto& s : segs) p.push_back(s.c_str());
+	td_arch* a = nullptr;
+	if (td_arch_parse(p.data(), (int32_t)p.size(), &a) != TD_OK) { why = "Some problem with parsing an HMM segment: " + segments_text(segs) + "."; return false; }
+	out.reset(a);
+	return true;
+}
+
+bool is_read_only(const td_arch* a) { return a->n_segments == 1 && a->type[0] == 'R'; }
+bool has_barcode(const td_arch* a) { for (int j = 0; j < a->n_segments; j++) if (a->type[j] == 'B') return true; return false; }
+int read_segments(const td_arch* a) { int n = 0; for (int j = 0; j < a->n_segments; j++) n += a->type[j] == 'R'; return n; }
+
+// byg_end (misc.c:160-205): the index behind the first occurrence of pattern in text, 0 when there is none
+size_t find_end(const std::string& text, const std::string& pattern)
+{
+	const size_t p = text.find(pattern);
+	return p == std::string::npos ? 0 : p + pattern.size();
+}
+
+// One line of an arch file (test_architectures.c:72-111): a line that contains "tagdust"; options -1 .. -9 and, as the reference
+// spells the tenth, "-:" ((char)(9 + 49)); the value is the word behind the first occurrence of the option's two characters.  A
+// line without -1 is no architecture.
+bool arch_line_segments(const std::string& line, std::vector<std::string>& segs)
+{
+	segs.clear();
+	if (!find_end(line, "tagdust")) return false;
+	std::vector<std::string> found(TD_RUN_MAX_SEGMENTS);
+	int last = -1;
+	for (int c = 0; c < TD_RUN_MAX_SEGMENTS; c++) {
+		const std::string opt = { '-', (char)(c + 49) };
+		size_t at = find_end(line, opt);
+		if (!at) { if (!c) return false; continue; }
+		while (at < line.size() && isspace((unsigned char)line[at])) at++;
+		size_t e = at;
+		while (e < line.size() && !isspace((unsigned char)line[e])) e++;
+		found[(size_t)c] = line.substr(at, e - at);
+		last = c;
+	}
+	for (int c = 0; c <= last; c++) segs.push_back(found[(size_t)c]);   // (an empty one is a skipped segment: parse_arch says so)
+	return true;
+}
+
+struct ArchFile {
+	std::vector<std::string> lines;                    // the candidates' lines as read (duplicates are an error)
+	std::vector<std::vector<std::string>> segs;
+};
+
+bool read_arch_file(const char* path, ArchFile& af, std::string& why)
+{
+	FILE* f = fopen(path, "r");
+	if (!f) { why = std::string("Failed to open file:") + path; return false; }
+	char* line = nullptr;
+	size_t cap = 0;
+	while (getline(&line, &cap, f) > 0) {
+		std::vector<std::string> segs;
+		if (!arch_line_segments(line, segs)) continue;
+		af.lines.push_back(line);
+		af.segs.push_back(segs);
+		if (af.lines.size() == 100) {   // MAX_NUM_ARCH, test_architectures.c:18, :128-133
+			why = "Error - your architechture file has too many architectures. Currently only 100 allowed.";
+			free(line); fclose(f);
+			return false;
+		}
+	}
+	free(line);
+	fclose(f);
+	if (af.lines.empty()) { why = std::string("Error - could not find any architectures in file: ") + path; return false; }
+	for (size_t i = 0; i < af.lines.size(); i++)
+		for (size_t j = i + 1; j < af.lines.size(); j++)
+			if (af.lines[i] == af.lines[j]) { why = std::string("ERROR: two architectures in ") + path + " are the same:" + af.lines[i]; return false; }
+	return true;
+}
+
+// ---- options ----
+struct OptSpec { const char* name; int arg; int id; };
+enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
+       O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
+       O_UNSUPPORTED = 100 };
+const OptSpec kOpts[] = {
+	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
+	{ "7", 1, O_SEG + 6 }, { "8", 1, O_SEG + 7 }, { "9", 1, O_SEG + 8 }, { "10", 1, O_SEG + 9 },
+	{ "arch", 1, O_ARCH }, { "o", 1, O_OUT }, { "out", 1, O_OUT }, { "t", 1, O_THREADS },
+	{ "Q", 1, O_Q }, { "q", 1, O_Q }, { "threshold", 1, O_Q }, { "e", 1, O_E }, { "i", 1, O_I },
+	{ "minlen", 1, O_MINLEN }, { "dust", 1, O_DUST }, { "ref", 1, O_REF }, { "fe", 1, O_FE },
+	{ "start", 1, O_START }, { "end", 1, O_END }, { "seed", 1, O_SEED },
+	{ "h", 0, O_HELP }, { "help", 0, O_HELP }, { "v", 0, O_VERSION }, { "version", 0, O_VERSION },
+	// parsed by the reference, not implemented here
+	{ "show_finger_seq", 0, O_UNSUPPORTED }, { "train", 1, O_UNSUPPORTED }, { "exact5", 1, O_UNSUPPORTED }, { "join", 0, O_UNSUPPORTED },
+	{ "split", 0, O_UNSUPPORTED }, { "name", 1, O_UNSUPPORTED }, { "format", 1, O_UNSUPPORTED }, { "f", 1, O_UNSUPPORTED },
+	{ "filter", 1, O_UNSUPPORTED }, { "a", 1, O_UNSUPPORTED }, { "l", 1, O_UNSUPPORTED }, { "L", 1, O_UNSUPPORTED }, { "log", 1, O_UNSUPPORTED },
+	{ "p", 1, O_UNSUPPORTED }, { "simulation", 1, O_UNSUPPORTED }, { "numbarcode", 1, O_UNSUPPORTED },
+	{ "sim_barlen", 1, O_UNSUPPORTED }, { "sim_barnum", 1, O_UNSUPPORTED }, { "sim_5seq", 1, O_UNSUPPORTED }, { "sim_3seq", 1, O_UNSUPPORTED },
+	{ "sim_readlen", 1, O_UNSUPPORTED }, { "sim_readlen_mod", 1, O_UNSUPPORTED }, { "sim_error_rate", 1, O_UNSUPPORTED },
+	{ "sim_InDel_frac", 1, O_UNSUPPORTED }, { "sim_numseq", 1, O_UNSUPPORTED }, { "sim_random_frac", 1, O_UNSUPPORTED },
+	{ "sim_endloss", 1, O_UNSUPPORTED },
+};
+// this library's own: long names, two dashes
+const OptSpec kOwnOpts[] = {
+	{ "devices", 1, O_DEVICES }, { "rtest", 0, O_RTEST }, { "host-threads", 1, O_HOST_THREADS }, { "batch-reads", 1, O_BATCH_READS },
+	{ "sync-compile", 0, O_SYNC_COMPILE }, { "stats-on-host", 0, O_STATS_ON_HOST }, { "force", 0, O_FORCE }, { "dry-run", 0, O_DRY_RUN },
+};
+
+bool parse_devices(const char* s, td_run_opts* o, std::string& why)
+{
+	o->n_devices = 0;
+	const char* p = s;
+	while (*p) {
+		char* end = nullptr;
+		const long v = strtol(p, &end, 10);
+		if (end == p || v < 0 || (*end && *end != ',')) { why = std::string("--devices: cannot read the device list \"") + s + "\" (want e.g. 0,1)"; return false; }
+		if (o->n_devices == TD_RUN_MAX_DEVICES) { why = "--devices: more than 16 devices"; return false; }
+		o->devices[o->n_devices++] = (int32_t)v;
+		p = *end ? end + 1 : end;
+		if (end[0] == ',' && !end[1]) { why = std::string("--devices: cannot read the device list \"") + s + "\""; return false; }
+	}
+	if (o->n_devices == 0) { why = "--devices: empty device list"; return false; }
+	return true;
+}
+
+}   // namespace
+
+extern "C" const char* td_run_last_error(void) { return g_run_error.c_str(); }
+
+extern "C" td_run_opts* td_run_opts_new(void)
+{
+	td_run_opts* o = (td_run_opts*)calloc(1, sizeof(td_run_opts));
+	if (!o) return nullptr;
+	o->num_threads = 8;                 // interface.c:70
+	o->confidence_threshold = 0.0f;     // :91
+	o->sequencer_error_rate = 0.05f;    // :87
+	o->indel_frequency = 0.1f;          // :88
+	o->minlen = 16;                     // :82
+	o->dust = 100;                      // :85
+	o->filter_error = 2;                // :99
+	o->matchstart = -1; o->matchend = -1;   // :80-81
+	o->seed = 0;                        // :124
+	o->n_devices = 1; o->devices[0] = 0;
+	return o;
+}
+
+extern "C" void td_run_opts_free(td_run_opts* o)
+{
+	if (!o) return;
+	for (int k = 0; k < TD_RUN_MAX_SEGMENTS; k++) free(o->segments[k]);
+	free(o->arch_file); free(o->outfile); free(o->reference_fasta);
+	for (int k = 0; k < o->n_infiles; k++) free(o->infile[k]);
+	free(o->infile);
+	for (int k = 0; k < o->argc; k++) free(o->argv[k]);
+	free(o->argv);
+	free(o);
+}
+
+extern "C" const char* td_run_version(void) { return "tagdust-hip 2.33 (TagDust 2.33 on libtagdust_hip, gfx950)\n"; }
+
+extern "C" const char* td_run_usage(void)
+{
+	return "\nUsage:   tagdust-hip [options] <file> [<file> ...] -o <output prefix>\n\n"
+	       "Options (as the reference's tagdust; one or two leading dashes):\n"
+	       "\t-1 .. -10   STR   the HMM building blocks of the read architecture, e.g. -1 B:ACGT,TTGA -2 R:N\n"
+	       "\t-arch       STR   file with candidate architectures, one tagdust command per line\n"
+	       "\t-o / -out   STR   output file prefix\n"
+	       "\t-Q          FLT   confidence threshold [calibrated]\n"
+	       "\t-e          FLT   expected sequencer error rate [0.05]\n"
+	       "\t-i          FLT   indel frequency [0.1]\n"
+	       "\t-start      INT   start of search area [1]\n"
+	       "\t-end        INT   end of search area [length of sequence]\n"
+	       "\t-minlen     INT   minimal accepted read length [16]\n"
+	       "\t-ref        STR   reference fasta file to be compared against\n"
+	       "\t-fe         INT   number of errors allowed when comparing to reference [2]\n"
+	       "\t-dust       INT   remove low complexity sequences [100]\n"
+	       "\t-t          INT   number of threads of the reference run to reproduce [8]\n"
+	       "\t-seed       INT   seed of the threshold calibration [time based]\n"
+	       "\t-h / -help, -v / -version\n"
+	       "Own options:\n"
+	       "\t--devices 0,1     HIP devices to run on [0]\n"
+	       "\t--rtest           the constants of the reference's -DRTEST builds (1000-record batches, 4000 calibration reads)\n"
+	       "\t--host-threads N  host threads of the parse and write stages\n"
+	       "\t--batch-reads N   records per batch\n"
+	       "\t--sync-compile    compile the model kernel before decoding (default: decode while it compiles)\n"
+	       "\t--stats-on-host   sequence statistics on the host\n"
+	       "\t--force           overwrite existing output files\n"
+	       "\t--dry-run         print the decisions of the run and stop\n\n";
+}
+
+extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
+{
+	auto bad = [&](const std::string& m) {
+		if (err && errcap) snprintf(err, errcap, "%s", m.c_str());
+		g_run_error = m;
+		return TD_FAIL;
+	};
+	if (!out || argc < 1 || !argv) return bad("td_run_parse_args: bad arguments");
+	*out = nullptr;
+	td_run_opts* o = td_run_opts_new();
+	if (!o) return bad("td_run_parse_args: out of memory");
+	std::unique_ptr<td_run_opts, void (*)(td_run_opts*)> guard(o, td_run_opts_free);
+	o->argv = (char**)calloc((size_t)argc, sizeof(char*));
+	for (int k = 0; k < argc; k++) o->argv[k] = dup_str(argv[k]);
+	o->argc = argc;
+	std::vector<std::string> files;
+	for (int k = 1; k < argc; k++) {
+		const std::string a = argv[k];
+		if (a.size() < 2 || a[0] != '-') { files.push_back(a); continue; }   // an input file ("-" = stdin)
+		const bool two = a[1] == '-';
+		const std::string name = a.substr(two ? 2 : 1);
+		const OptSpec* sp = nullptr;
+		for (const OptSpec& q : kOpts) if (name == q.name) sp = &q;
+		if (!sp && two) for (const OptSpec& q : kOwnOpts) if (name == q.name) sp = &q;
+		if (!sp) return bad("unknown option " + a);
+		if (sp->id == O_UNSUPPORTED) return bad("option " + a + " of the reference is not implemented by this program");
+		const char* v = nullptr;
+		if (sp->arg) {
+			if (k + 1 >= argc) return bad("option " + a + " requires an argument");
+			v = argv[++k];
+		}
+		std::string why;
+		if (sp->id >= O_SEG && sp->id < O_SEG + TD_RUN_MAX_SEGMENTS) {
+			free(o->segments[sp->id - O_SEG]);
+			o->segments[sp->id - O_SEG] = dup_str(v);
+			continue;
+		}
+		switch (sp->id) {
+		case O_ARCH: free(o->arch_file); o->arch_file = dup_str(v); break;
+		case O_OUT: free(o->outfile); o->outfile = dup_str(v); break;
+		case O_THREADS: o->num_threads = atoi(v); break;
+		case O_Q: o->confidence_threshold = (float)atof(v); break;
+		case O_E: o->sequencer_error_rate = (float)atof(v); break;
+		case O_I: o->indel_frequency = (float)atof(v); break;
+		case O_MINLEN: o->minlen = atoi(v); break;
+		case O_DUST: o->dust = atoi(v); break;
+		case O_REF: free(o->reference_fasta); o->reference_fasta = dup_str(v); break;
+		case O_FE: o->filter_error = atoi(v); break;
+		case O_START: o->matchstart = atoi(v) - 1; break;     // interface.c:286
+		case O_END: o->matchend = atoi(v); break;
+		case O_SEED: o->seed = (uint32_t)atoi(v); break;
+		case O_HELP: o->help = 1; break;
+		case O_VERSION: o->version = 1; break;
+		case O_DEVICES: if (!parse_devices(v, o, why)) return bad(why); break;
+		case O_RTEST: o->flavour = 1; break;
+		case O_HOST_THREADS: o->host_threads = atoi(v); break;
+		case O_BATCH_READS: o->batch_reads = atoi(v); break;
+		case O_SYNC_COMPILE: o->sync_compile = 1; break;
+		case O_STATS_ON_HOST: o->stats_on_host = 1; break;
+		case O_FORCE: o->force = 1; break;
+		case O_DRY_RUN: o->dry_run = 1; break;
+		default: return bad("unknown option " + a);
+		}
+	}
+	if (o->num_threads < 1) return bad("option -t: need at least one thread");
+	if (o->host_threads < 0 || o->batch_reads < 0) return bad("--host-threads / --batch-reads: negative value");
+	if ((int)files.size() > TD_RUN_MAX_FILES) return bad("more than 8 input files");
+	o->infile = (char**)calloc(files.size() ? files.size() : 1, sizeof(char*));
+	for (auto& f : files) o->infile[o->n_infiles++] = dup_str(f.c_str());
+	*out = guard.release();
+	return TD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the plan
+// ---------------------------------------------------------------------------------------------------------
+enum { SRC_CMDLINE = 0, SRC_ARCH_FILE = 1, SRC_DEFAULT = 2 };
+
+struct td_run_plan_t {
+	std::vector<int> source;                 // per input file
+	std::vector<std::vector<std::string>> segs;   // ... its segments when no data is needed to know them
+	ArchFile arch_file;
+	bool all_known = false;                  // no file waits for the arch file's choice
+	int bar_file = -1, num_out_reads = 0;
+	std::vector<std::string> out_files;
+	std::vector<std::string> warnings;
+	int dust = 0;
+	bool use_ref = false;
+};
+
+namespace {
+
+std::vector<std::string> cmdline_segments(const td_run_opts* o)
+{
+	int last = -1;
+	for (int k = 0; k < TD_RUN_MAX_SEGMENTS; k++) if (o->segments[k]) last = k;
+	std::vector<std::string> s;
+	for (int k = 0; k <= last; k++) s.push_back(o->segments[k] ? o->segments[k] : "");
+	return s;
+}
+
+// what the controller decides once every file's architecture is known (barcode_hmm.c:130-159): TD_FAIL with the reference's message
+int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& archs, int& bar_file, int& num_out_reads, std::vector<std::string>& names)
+{
+	bar_file = -1; num_out_reads = 0;
+	for (size_t k = 0; k < archs.size(); k++) {
+		if (has_barcode(archs[k])) {
+			if (bar_file >= 0) return run_fail("Barcodes seem to be in both architectures... ");
+			bar_file = (int)k;
+		}
+		num_out_reads += read_segments(archs[k]);
+	}
+	if (num_out_reads == 0) return run_fail("No read segment in any architecture: there would be no output file.");
+	// print_all() names its files after the barcode file's architecture, else the last file's (td_stream_run_multi; one file: td_writer_open)
+	td_writer_file_names_n(o->outfile, archs[(size_t)(bar_file >= 0 ? bar_file : (int)archs.size() - 1)], num_out_reads, names, nullptr);
+	if (bar_file >= 0 && !o->force)   // check_for_existing_demultiplexed_files_multiple, io.c:633-691 (made for the barcode file only)
+		for (auto& n : names)
+			if (file_exists(n)) return run_fail("Error: some output files already exists. (%s; --force overwrites)", n.c_str());
+	return TD_OK;
+}
+
+}   // namespace
+
+extern "C" void td_run_plan_free(td_run_plan_t* p) { delete p; }
+
+extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
+{
+	if (!o || !out) return run_fail("td_run_plan: bad arguments");
+	*out = nullptr;
+	std::unique_ptr<td_run_plan_t> p(new td_run_plan_t());
+	const std::vector<std::string> cmd = cmdline_segments(o);
+	// main.c:103-125
+	if (cmd.empty() && !o->arch_file) return run_fail("ERROR: No read architecture found.");
+	std::string why;
+	if (!cmd.empty()) { ArchPtr a; if (!parse_arch(cmd, a, why)) return run_fail("ERROR: Something wrong with the read architecture. %s", why.c_str()); }
+	if (o->n_infiles == 0) return run_fail("ERROR: No input file found.");
+	if (!o->outfile) return run_fail("ERROR: You need to specify an output file prefix using the -o / -out option.");
+	if (o->arch_file && !file_exists(o->arch_file)) return run_fail("ERROR: Arch file:%s does not exists.", o->arch_file);
+	for (int k = 0; k < o->n_infiles; k++)
+		if (strcmp(o->infile[k], "-") != 0 && !file_exists(o->infile[k])) return run_fail("ERROR: Input file:%s does not exists.", o->infile[k]);
+	// interface.c:419-450: two or more R segments in the command line's architecture switch DUST and -ref off
+	p->dust = o->dust;
+	p->use_ref = o->reference_fasta != nullptr;
+	int n_r = 0;
+	for (auto& s : cmd) n_r += !s.empty() && s[0] == 'R';
+	if (n_r >= 2 && (p->use_ref || p->dust)) {
+		p->warnings.push_back("WARNING: cannot dust or filter sequences by comparison to a known sequence if multiple reads are present in one input seqeunce.");
+		p->dust = 0;
+		p->use_ref = false;
+	}
+	if (p->use_ref && !file_exists(o->reference_fasta)) return run_fail("ERROR: Reference file:%s does not exists.", o->reference_fasta);
+	if (o->arch_file && !read_arch_file(o->arch_file, p->arch_file, why)) return run_fail("%s", why.c_str());
+	// barcode_hmm.c:105-129
+	p->all_known = true;
+	std::vector<ArchPtr> archs;
+	for (int k = 0; k < o->n_infiles; k++) {
+		std::vector<std::string> segs;
+		int src;
+		if (k == 0 && !cmd.empty()) { src = SRC_CMDLINE; segs = cmd; }
+		else if (o->arch_file) {
+			src = SRC_ARCH_FILE;
+			if (p->arch_file.segs.size() == 1) segs = p->arch_file.segs[0];   // (one candidate: nothing to choose)
+			else p->all_known = false;
+		} else { src = SRC_DEFAULT; segs = { "R:N" }; }
+		p->source.push_back(src);
+		p->segs.push_back(segs);
+		if (!segs.empty()) {
+			ArchPtr a;
+			if (!parse_arch(segs, a, why)) return run_fail("ERROR: Something wrong with the read architecture. %s", why.c_str());
+			archs.push_back(std::move(a));
+		}
+	}
+	std::vector<const td_arch*> view;
+	for (auto& a : archs) view.push_back(a.get());
+	if (p->all_known && decide_outputs(o, view, p->bar_file, p->num_out_reads, p->out_files) != TD_OK) return TD_FAIL;
+	*out = p.release();
+	return TD_OK;
+}
+
+extern "C" int64_t td_run_plan_describe(const td_run_plan_t* p, char* buf, int64_t cap)
+{
+	if (!p) return 0;
+	std::string s;
+	for (auto& w : p->warnings) s += "warning: " + w + "\n";
+	for (size_t k = 0; k < p->source.size(); k++) {
+		s += "file " + std::to_string(k) + " architecture: ";
+		if (p->source[k] == SRC_CMDLINE) s += "command line: " + segments_text(p->segs[k]);
+		else if (p->source[k] == SRC_DEFAULT) s += "default: " + segments_text(p->segs[k]);
+		else if (!p->segs[k].empty()) s += "arch file (one candidate): " + segments_text(p->segs[k]);
+		else s += "arch file: best of " + std::to_string(p->arch_file.segs.size()) + " candidates";
+		s += "\n";
+	}
+	for (size_t k = 0; k < p->arch_file.segs.size(); k++) s += "arch file candidate " + std::to_string(k) + ": " + segments_text(p->arch_file.segs[k]) + "\n";
+	s += "dust: " + std::to_string(p->dust) + "\n";
+	s += std::string("ref: ") + (p->use_ref ? "on" : "off") + "\n";
+	if (p->all_known) {
+		s += "barcode file: " + (p->bar_file >= 0 ? std::to_string(p->bar_file) : std::string("none")) + "\n";
+		s += "output reads: " + std::to_string(p->num_out_reads) + "\n";
+		for (auto& n : p->out_files) s += "output file: " + n + "\n";
+	} else {
+		s += "output files: named once the arch file's choice is made\n";
+	}
+	return copy_out(s, buf, cap);
+}
+
+extern "C" int64_t td_run_output_files_describe(const td_run_opts* o, const char* const* architectures, int32_t n_files, char* buf, int64_t cap)
+{
+	if (!o || !o->outfile || !architectures || n_files < 1) { run_fail("td_run_output_files_describe: bad arguments"); return -1; }
+	std::vector<ArchPtr> archs((size_t)n_files);
+	std::vector<const td_arch*> view;
+	std::string why;
+	for (int k = 0; k < n_files; k++) {
+		std::vector<std::string> segs;
+		if (!architectures[k] || !arch_line_segments(std::string("tagdust ") + architectures[k] + "\n", segs) || !parse_arch(segs, archs[(size_t)k], why)) {
+			run_fail("td_run_output_files_describe: file %d: %s", k, why.empty() ? "no architecture" : why.c_str());
+			return -1;
+		}
+		view.push_back(archs[(size_t)k].get());
+	}
+	int bar_file = -1, num_out_reads = 0;
+	std::vector<std::string> names;
+	if (decide_outputs(o, view, bar_file, num_out_reads, names) != TD_OK) return -1;
+	std::string s;
+	for (auto& n : names) s += n + "\n";
+	return copy_out(s, buf, cap);
+}
+
+extern "C" int64_t td_run_arch_file_describe(const char* path, char* buf, int64_t cap)
+{
+	ArchFile af;
+	std::string why;
+	if (!path || !read_arch_file(path, af, why)) { run_fail("%s", path ? why.c_str() : "td_run_arch_file_describe: NULL path"); return -1; }
+	std::string s;
+	for (auto& c : af.segs) s += segments_text(c) + "\n";
+	return copy_out(s, buf, cap);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the log
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+// append_message(), misc.c:285-335: "[YYYY-MM-DD HH:MM:SS]\t" in front of every message; the messages end in '\n' themselves
+struct Log {
+	std::string text;
+	bool echo = false;
+	void add(const std::string& msg)
+	{
+		char stamp[64];
+		const time_t now = time(nullptr);
+		struct tm tmv;
+		localtime_r(&now, &tmv);
+		strftime(stamp, sizeof stamp, "[%F %H:%M:%S]\t", &tmv);
+		if (echo) fprintf(stderr, "%s%s", stamp, msg.c_str());
+		text += stamp;
+		text += msg;
+	}
+	void addf(const char* fmt, ...)
+	{
+		char buf[2048];
+		va_list ap;
+		va_start(ap, fmt);
+		vsnprintf(buf, sizeof buf, fmt, ap);
+		va_end(ap);
+		add(buf);
+	}
+	// free_param(), interface.c:715-726
+	void write(const char* outfile) const
+	{
+		if (!outfile) return;
+		const std::string name = std::string(outfile) + "_logfile.txt";
+		if (FILE* f = fopen(name.c_str(), "w")) { fprintf(f, "%s\n", text.c_str()); fclose(f); }
+	}
+};
+
+// the messages of barcode_hmm.c:387-430
+std::vector<std::string> summary_messages(const td_run_opts* o, const td_run_report* r)
+{
+	std::vector<std::string> m;
+	char b[2048];
+	auto addf = [&](const char* fmt, ...) {
+		va_list ap;
+		va_start(ap, fmt);
+		vsnprintf(b, sizeof b, fmt, ap);
+		va_end(ap);
+		m.push_back(b);
+	};
+	int64_t total = 0;
+	for (int q = 0; q < TD_NUM_OUTCOME_SLOTS; q++) total += r->counts[q];
+	const int64_t ok = r->counts[TD_EXTRACT_SUCCESS];
+	addf("Done.\n\n");
+	for (int k = 0; k < o->n_infiles; k++) addf("%s\tInput file %d.\n", o->infile[k], k);
+	addf("%d\ttotal input reads\n", (int)total);
+	addf("%0.2f\tselected threshold\n", (double)r->selected_threshold);
+	addf("%d\tsuccessfully extracted\n", (int)ok);
+	addf("%0.1f%%\textracted\n", (double)((float)ok / (float)total * 100.0f));
+	addf("%d\tproblems with architecture\n", (int)r->counts[TD_EXTRACT_FAIL_ARCHITECTURE_MISMATCH]);
+	addf("%d\tbarcode / UMI not found\n", (int)r->counts[TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND]);
+	addf("%d\ttoo short\n", (int)r->counts[TD_EXTRACT_FAIL_READ_TOO_SHORT]);
+	addf("%d\tlow complexity\n", (int)r->counts[TD_EXTRACT_FAIL_LOW_COMPLEXITY]);
+	addf("%d\tmatch artifacts:\n", (int)r->counts[TD_EXTRACT_FAIL_MATCHES_ARTIFACTS]);
+	for (int j = 0; j < r->n_artifacts; j++)
+		if (r->artifact_hits && r->artifact_hits[j]) addf("%d\t%s\n", (int)r->artifact_hits[j], r->artifact_names && r->artifact_names[j] ? r->artifact_names[j] : "");
+	return m;
+}
+
+}   // namespace
+
+extern "C" int64_t td_run_format_summary(const td_run_opts* o, const td_run_report* r, char* buf, int64_t cap)
+{
+	if (!o || !r) return 0;
+	std::string s;
+	for (auto& m : summary_messages(o, r)) s += m;
+	return copy_out(s, buf, cap);
+}
+
+extern "C" void td_run_report_clear(td_run_report* r)
+{
+	if (!r) return;
+	if (r->artifact_names) for (int j = 0; j < r->n_artifacts; j++) free(r->artifact_names[j]);
+	free(r->artifact_names); free(r->artifact_hits); free(r->log);
+	for (int k = 0; k < TD_RUN_MAX_FILES; k++) free(r->architectures[k]);
+	memset(r, 0, sizeof *r);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the run
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+struct CtxDeleter { void operator()(td_ctx* c) const { td_ctx_destroy(c); } };
+struct TablesDeleter { void operator()(td_model_tables* t) const { td_model_tables_free(t); } };
+struct FastaDeleter { void operator()(td_fasta* f) const { td_fasta_free(f); } };
+
+struct FileState {
+	ArchPtr arch;
+	std::vector<std::string> segs;
+	std::vector<uint8_t> codes;            // the head of the file: what the statistics (and -arch) look at
+	std::vector<int64_t> offs;
+	td_seq_stats stats{};
+	float threshold = 0.0f;
+	std::vector<std::unique_ptr<td_ctx, CtxDeleter>> ctx;   // one per listed device
+	std::vector<td_ctx*> raw;
+};
+
+bool read_whole_file(const char* path, std::string& out)
+{
+	FILE* f = fopen(path, "rb");
+	if (!f) return false;
+	char buf[1 << 16];
+	size_t n;
+	while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, n);
+	fclose(f);
+	return true;
+}
+
+struct Run {
+	const td_run_opts* o;
+	td_run_report* rep;
+	Log log;
+	std::vector<FileState> files;
+	std::unique_ptr<td_fasta, FastaDeleter> fasta;
+	int dust = 0;
+	bool use_ref = false;
+	float error_rate = 0.05f;
+
+	int head_limit() const { return o->flavour ? 1001000 : 1000001; }   // io.c:125-188 with num_query 1000 / 1 000 001
+
+	int fail(const char* fmt, ...)
+	{
+		char buf[1024];
+		va_list ap;
+		va_start(ap, fmt);
+		vsnprintf(buf, sizeof buf, fmt, ap);
+		va_end(ap);
+		g_run_error = buf;
+		log.add(std::string(buf) + "\n");
+		return TD_FAIL;
+	}
+
+	int load_head(int k)
+	{
+		FileState& f = files[(size_t)k];
+		if (!f.offs.empty()) return TD_OK;
+		std::string why;
+		if (td_stream_head(o->infile[k], head_limit(), o->host_threads, f.codes, f.offs, why) != TD_OK) return fail("%s", why.c_str());
+		if (f.offs.size() < 2) return fail("Input file:%s holds no reads.", o->infile[k]);
+		if (f.codes.empty()) f.codes.push_back(0);   // (reads without bases: a valid pointer all the same)
+		return TD_OK;
+	}
+
+	td_ctx* first_ctx(int k)
+	{
+		FileState& f = files[(size_t)k];
+		if (f.ctx.empty()) {
+			for (int d = 0; d < o->n_devices; d++) {
+				td_ctx* c = nullptr;
+				if (td_ctx_create(o->devices[d], &c) != TD_OK) { fail("%s", td_last_error(nullptr)); return nullptr; }
+				f.ctx.emplace_back(c);
+				f.raw.push_back(c);
+				if (o->host_threads > 0) (void)td_set_option(c, "host_threads", o->host_threads > 16 ? 16 : o->host_threads);
+			}
+		}
+		return f.raw[0];
+	}
+
+	// test_architectures(), test_architectures.c:20-289
+	int select_architecture(int k, const ArchFile& af)
+	{
+		FileState& f = files[(size_t)k];
+		log.addf("Looking at file:%s\n", o->infile[k]);
+		log.addf("Searching for best architecture in file '%s'\n", o->arch_file);
+		size_t best = 0;
+		if (af.segs.size() > 1) {
+			if (load_head(k) != TD_OK) return TD_FAIL;
+			std::vector<ArchPtr> cand(af.segs.size());
+			std::vector<const td_arch*> ptr;
+			std::string why;
+			for (size_t c = 0; c < af.segs.size(); c++) {
+				if (!parse_arch(af.segs[c], cand[c], why)) return fail("%s", why.c_str());
+				ptr.push_back(cand[c].get());
+			}
+			td_ctx* ctx = first_ctx(k);
+			if (!ctx) return TD_FAIL;
+			const int64_t n = std::min<int64_t>((int64_t)f.offs.size() - 1, 100000);   // param->num_query, :38-42
+			std::vector<float> post(ptr.size());
+			int32_t b = -1;
+			if (td_compare_architectures(ctx, ptr.data(), (int32_t)ptr.size(), f.codes.data(), f.offs.data(), n, o->sequencer_error_rate,
+			                             o->indel_frequency, o->num_threads, post.data(), &b) != TD_OK || b < 0)
+				return fail("Test architecture on file %s failed: %s", o->infile[k], td_last_error(ctx));
+			best = (size_t)b;
+			log.add("Using: " + segments_text(af.segs[best]) + " \n");
+			log.addf("%0.2f Confidence.\n", (double)post[best]);
+		} else {
+			log.add("Using: " + segments_text(af.segs[0]) + " \n");
+			log.addf("Confidence: %0.2f\n", 1.0);
+		}
+		f.segs = af.segs[best];
+		return TD_OK;
+	}
+
+	int execute();
+	int run_files(td_stream_stats& st);
+};
+
+int Run::execute()
+{
+	const int K = o->n_infiles;
+	td_run_plan_t* plan_raw = nullptr;
+	// the banner and the cmd: line, interface.c:384-412; "Start Run", main.c:127
+	log.add("Tagdust 2.33, Copyright (C) 2013-2019 Timo Lassmann <timolassmann@gmail.com>\n");
+	{
+		std::string cmd = "cmd: ";
+		for (int k = 0; k < o->argc; k++) { cmd += o->argv[k]; cmd += ' '; }
+		log.add(cmd + "\n");
+	}
+	if (td_run_plan(o, &plan_raw) != TD_OK) { log.add(g_run_error + "\n"); return TD_FAIL; }
+	std::unique_ptr<td_run_plan_t> plan(plan_raw);
+	for (auto& w : plan->warnings) log.add(w + "\n");
+	dust = plan->dust;
+	use_ref = plan->use_ref;
+	log.add("Start Run\n--------------------------------------------------\n");
+	files.resize((size_t)K);
+	rep->n_files = K;
+
+	// 1. architectures per file, barcode_hmm.c:105-138
+	double t0 = now_s();
+	std::string why;
+	for (int k = 0; k < K; k++) {
+		FileState& f = files[(size_t)k];
+		if (plan->source[(size_t)k] == SRC_ARCH_FILE) { if (select_architecture(k, plan->arch_file) != TD_OK) return TD_FAIL; }
+		else f.segs = plan->segs[(size_t)k];
+		if (!parse_arch(f.segs, f.arch, why)) return fail("%s", why.c_str());
+		rep->architectures[k] = dup_str(segments_text(f.segs).c_str());
+	}
+	rep->arch_s = now_s() - t0;
+	std::vector<std::string> out_files;
+	int bar_file = -1, num_out_reads = 0;
+	{
+		std::vector<const td_arch*> view;
+		for (auto& f : files) view.push_back(f.arch.get());
+		if (decide_outputs(o, view, bar_file, num_out_reads, out_files) != TD_OK) { log.add(g_run_error + "\n"); return TD_FAIL; }
+	}
+
+	// 2. sequence statistics over the head of every file, io.c:52-300
+	t0 = now_s();
+	for (int k = 0; k < K; k++) {
+		FileState& f = files[(size_t)k];
+		if (load_head(k) != TD_OK) return TD_FAIL;
+		const int64_t n = (int64_t)f.offs.size() - 1;
+		if (o->stats_on_host) {
+			if (td_sequence_stats_limit(f.arch.get(), f.codes.data(), f.offs.data(), n, head_limit(), o->matchstart, o->matchend, &f.stats) != TD_OK)
+				return fail("sequence statistics of %s failed", o->infile[k]);
+		} else {
+			td_ctx* ctx = first_ctx(k);
+			if (!ctx) return TD_FAIL;
+			if (td_sequence_stats_device(ctx, f.arch.get(), f.codes.data(), f.offs.data(), n, head_limit(), o->matchstart, o->matchend, &f.stats) != TD_OK)
+				return fail("%s", td_last_error(ctx));
+		}
+		std::vector<uint8_t>().swap(f.codes);   // the run opens the file again, as the reference does
+		std::vector<int64_t>().swap(f.offs);
+		f.offs.push_back(0);
+	}
+	rep->stats_on_device = !o->stats_on_host;
+	rep->stats_s = now_s() - t0;
+
+	// contexts, window (param->matchstart / matchend apply to every run_pHMM call, calibration included)
+	for (int k = 0; k < K; k++) {
+		if (!first_ctx(k)) return TD_FAIL;
+		for (td_ctx* c : files[(size_t)k].raw)
+			if (td_set_window(c, o->matchstart, o->matchend) != TD_OK) return fail("%s", td_last_error(c));
+	}
+
+	// 3. thresholds, barcode_hmm.c:190-200 (estimateQthreshold, calibrateQ.c:17-235): srand(seed) once per file
+	t0 = now_s();
+	error_rate = o->sequencer_error_rate;
+	if (!o->confidence_threshold) {
+		const uint32_t seed = o->seed ? o->seed : (uint32_t)(time(nullptr) * 42);   // calibrateQ.c:27-31
+		for (int k = 0; k < K; k++) {
+			FileState& f = files[(size_t)k];
+			log.addf("Determining threshold for read%d.\n", k);
+			if (td_estimate_threshold(f.raw[0], f.arch.get(), &f.stats, o->indel_frequency, seed, o->flavour ? 4000 : 400000, o->flavour ? 1 : 0,
+			                          &f.threshold) != TD_OK)
+				return fail("estimateQthreshold failed: %s", td_last_error(f.raw[0]));
+			log.addf("Selected Threshold:: %f\n", (double)f.threshold);
+		}
+		error_rate = 0.05f;   // calibrateQ.c:65, :117: for the rest of the run
+	}
+	for (int k = 0; k < K; k++) { rep->thresholds[k] = files[(size_t)k].threshold; rep->selected_threshold = files[(size_t)k].threshold; }
+	rep->calibration_s = now_s() - t0;
+
+	// -ref, barcode_hmm.c:209-215
+	if (use_ref) {
+		std::string text;
+		if (!read_whole_file(o->reference_fasta, text)) return fail("Failed to open file:%s", o->reference_fasta);
+		td_fasta* fa = nullptr;
+		if (td_fasta_parse(text.data(), (int64_t)text.size(), &fa) != TD_OK || !fa) return fail("Failed to read the sequences of %s", o->reference_fasta);
+		fasta.reset(fa);
+		rep->n_artifacts = fa->n_seq;
+		rep->artifact_hits = (int64_t*)calloc((size_t)std::max(1, fa->n_seq), sizeof(int64_t));
+		rep->artifact_names = (char**)calloc((size_t)std::max(1, fa->n_seq), sizeof(char*));
+		for (int j = 0; j < fa->n_seq; j++) rep->artifact_names[j] = dup_str(fa->names[j]);
+	}
+
+	// 4. models and parameters, barcode_hmm.c:203-206
+	t0 = now_s();
+	for (int k = 0; k < K; k++) {
+		FileState& f = files[(size_t)k];
+		std::unique_ptr<td_model_tables, TablesDeleter> tables;
+		if (!is_read_only(f.arch.get())) {   // (an R:N file goes through run_rna_dust: no model on the device)
+			td_model_tables* t = nullptr;
+			if (td_model_build(f.arch.get(), &f.stats, error_rate, o->indel_frequency, &t) != TD_OK) return fail("building the model of %s failed", o->infile[k]);
+			tables.reset(t);
+		}
+		for (td_ctx* c : f.raw) {
+			if (tables) {
+				if (td_set_option(c, "async_compile", o->sync_compile ? 0 : 1) != TD_OK || td_model_upload(c, &tables->desc) != TD_OK) return fail("%s", td_last_error(c));
+			}
+			if (td_set_params(c, f.threshold, o->minlen, dust) != TD_OK) return fail("%s", td_last_error(c));
+			if (td_set_artifacts(c, fasta ? fasta->string : nullptr, fasta ? fasta->s_index : nullptr, fasta ? fasta->n_seq : 0, o->filter_error, o->num_threads) != TD_OK)
+				return fail("%s", td_last_error(c));
+			if (td_counts_reset(c) != TD_OK) return fail("%s", td_last_error(c));
+		}
+	}
+	rep->compile_wait_s = now_s() - t0;
+
+	// 5. the run
+	t0 = now_s();
+	td_stream_stats st{};
+	const int rc = run_files(st);
+	rep->stream = st;
+	rep->stream_s = now_s() - t0;
+	if (rc != TD_OK) {
+		const std::string msg = g_run_error;
+		return fail("%s -- the run failed after it had started: the output files are incomplete and were left as they are", msg.c_str());
+	}
+
+	// 6. the summary, barcode_hmm.c:387-430
+	for (auto& m : summary_messages(o, rep)) log.add(m);
+	return TD_OK;
+}
+
+int Run::run_files(td_stream_stats& st)
+{
+	const int K = o->n_infiles;
+	td_stream_opts so{};
+	so.batch_reads = o->batch_reads > 0 ? o->batch_reads : (o->flavour ? 1000 : 0);
+	so.n_threads = o->host_threads;
+	if (K == 1 && o->n_devices == 1 && !is_read_only(files[0].arch.get())) {
+		td_ctx* c = files[0].raw[0];
+		if (td_stream_run(c, o->infile[0], files[0].arch.get(), o->outfile, &so, &st) != TD_OK) return run_fail("%s", td_io_last_error());
+		if (td_counts_get(c, rep->counts) != TD_OK) return run_fail("%s", td_last_error(c));
+		if (rep->n_artifacts && td_artifact_hits_get(c, rep->artifact_hits, rep->n_artifacts) != TD_OK) return run_fail("%s", td_last_error(c));
+		return TD_OK;
+	}
+	std::vector<td_stream_file> sf((size_t)K);
+	for (int k = 0; k < K; k++) {
+		sf[(size_t)k].path = o->infile[k];
+		sf[(size_t)k].arch = files[(size_t)k].arch.get();
+		sf[(size_t)k].ctx = files[(size_t)k].raw.data();
+	}
+	if (td_stream_run_multi_hits(sf.data(), K, o->n_devices, o->outfile, dust, &so, &st, rep->counts, rep->artifact_hits, rep->n_artifacts) != TD_OK)
+		return run_fail("%s", td_io_last_error());
+	return TD_OK;
+}
+
+}   // namespace
+
+extern "C" int td_run_execute(const td_run_opts* o, td_run_report* report)
+{
+	if (!o) return run_fail("td_run_execute: NULL options");
+	td_run_report local{};
+	td_run_report* rep = report ? report : &local;
+	memset(rep, 0, sizeof *rep);
+	int rc;
+	{
+		Run run{ o, rep };
+		run.log.echo = o->echo_log != 0;
+		rc = run.execute();
+		run.log.write(o->outfile);
+		rep->log = dup_str(run.log.text.c_str());
+	}   // (contexts and their compile jobs are gone here)
+	if (rc != TD_OK) snprintf(rep->error, sizeof rep->error, "%s", g_run_error.c_str());
+	if (!report) td_run_report_clear(&local);
+	return rc;
+}

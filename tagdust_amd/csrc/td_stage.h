@@ -51,6 +51,8 @@ hipError_t td_stage_sort(const int64_t* offs, int64_t n_reads, int lmax, int32_t
 hipError_t td_stage_pack(const TdStageBatch& b, hipStream_t stream);
 // art_left[k] = read k is a left-over read of its thread range (art_threads ranges over the caller's order)
 hipError_t td_stage_art_left(const TdStageBatch& b, hipStream_t stream);
+// hits[a] += reads of the batch whose outcome out_type[k] (device order, k < n_reads) is artifact sequence a's ((a + 1) << 8 | 5)
+hipError_t td_stage_art_hits(const int32_t* out_type, int64_t n_reads, int32_t art_n, unsigned long long* hits, hipStream_t stream);
 // SoA / lane-interleaved kernel outputs -> per-read records, rewritten sequences and labels in the caller's order
 hipError_t td_stage_finish(const TdStageBatch& b, hipStream_t stream);
 // memory-side probe of a candidate workspace allocation (milliseconds, best of three passes); see td_stage.hip

@@ -129,6 +129,39 @@ hipError_t td_stage_art_left(const TdStageBatch& b, hipStream_t stream)
 	return hipGetLastError();
 }
 
+// -ref: reads per artifact sequence, the controller's reference_fasta->mer_hash (src/barcode_hmm.c:381) -- a read whose
+// outcome is ((index + 1) << 8) | 5 counts for sequence `index`.  The first ART_HITS_LDS sequences are counted in LDS and leave
+// the workgroup as one atomic per sequence that was hit; the others (a filter that long is unusual) go to memory as they come.
+#define ART_HITS_LDS 1024
+__global__ __launch_bounds__(STAGE_BLOCK) void td_art_hits_kernel(const int32_t* __restrict__ type, int64_t n_reads, int32_t art_n,
+                                                                    unsigned long long* __restrict__ hits)
+{
+	__shared__ uint32_t bin[ART_HITS_LDS];
+	for (int i = threadIdx.x; i < ART_HITS_LDS; i += STAGE_BLOCK) bin[i] = 0u;
+	__syncthreads();
+	const int64_t step = (int64_t)gridDim.x * STAGE_BLOCK;
+	for (int64_t k = (int64_t)blockIdx.x * STAGE_BLOCK + threadIdx.x; k < n_reads; k += step) {
+		const int32_t t = type[k];
+		if ((t & 0xFF) != 5) continue;   // EXTRACT_FAIL_MATCHES_ARTIFACTS, src/io.h:45
+		const int32_t a = (t >> 8) - 1;
+		if (a < 0 || a >= art_n) continue;
+		if (a < ART_HITS_LDS) atomicAdd(&bin[a], 1u);
+		else atomicAdd(hits + a, 1ull);
+	}
+	__syncthreads();
+	for (int i = threadIdx.x; i < ART_HITS_LDS && i < art_n; i += STAGE_BLOCK)
+		if (bin[i]) atomicAdd(hits + i, (unsigned long long)bin[i]);
+}
+
+hipError_t td_stage_art_hits(const int32_t* out_type, int64_t n_reads, int32_t art_n, unsigned long long* hits, hipStream_t stream)
+{
+	if (n_reads <= 0 || art_n <= 0) return hipSuccess;
+	int64_t blocks = (n_reads + STAGE_BLOCK * 8 - 1) / (STAGE_BLOCK * 8);   // eight reads per lane: few workgroups, few atomics
+	if (blocks > 1024) blocks = 1024;
+	hipLaunchKernelGGL(td_art_hits_kernel, dim3((unsigned)blocks), dim3(STAGE_BLOCK), 0, stream, out_type, n_reads, art_n, hits);
+	return hipGetLastError();
+}
+
 hipError_t td_stage_pack(const TdStageBatch& b, hipStream_t stream)
 {
 	if (b.n_tiles <= 0) return hipSuccess;

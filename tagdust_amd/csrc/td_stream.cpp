@@ -1218,6 +1218,39 @@ extern "C" int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* ar
 	return TD_OK;
 }
 
+// The head of a file as the run will read it, through the pipeline's own Source / Reader (plain memory, no GPU): plain, .gz, .bz2,
+// FASTA and SAM / BAM heads need no second parser.  Records are taken until at least `limit` are there or the file ends; the
+// producer is then told to stop and the source closed -- the run opens the file again, as the reference does.
+int td_stream_head(const char* path, int64_t limit, int32_t n_threads, std::vector<uint8_t>& codes, std::vector<int64_t>& offs, std::string& why)
+{
+	td_stream_opts want{};
+	want.n_threads = n_threads;
+	want.batch_reads = 1 << 16;
+	want.block_bytes = (int64_t)16 << 20;
+	const td_stream_opts o = resolve_opts(&want, false);
+	codes.clear();
+	offs.assign(1, 0);
+	RunError err;
+	Reader rd(err, o, true, false, o.n_threads);
+	if (!rd.src.open(path, o.block_bytes, why)) return TD_FAIL;
+	if (!rd.start(3)) { why = "td_stream_head: out of memory"; return TD_FAIL; }
+	Batch* b = nullptr;
+	while ((int64_t)offs.size() - 1 < limit && rd.ready->pop(b)) {
+		const int64_t take = std::min<int64_t>(b->n, limit - ((int64_t)offs.size() - 1));
+		const int64_t base = offs.back();
+		codes.insert(codes.end(), b->codes, b->codes + b->offs[take]);
+		for (int64_t i = 1; i <= take; i++) offs.push_back(base + b->offs[i]);
+		b->pieces.clear();
+		if (!rd.free_list->push(b)) break;
+	}
+	const bool enough = (int64_t)offs.size() - 1 >= limit;
+	rd.ready->abort();          // (the producer leaves whatever wait it is in)
+	rd.free_list->abort();
+	rd.stop();
+	if (err.failed() && !enough) { why = err.message(); return TD_FAIL; }
+	return TD_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Several input files of one run, several devices: the controller's loop for paired / three-read data
 // (hmm_controller_multiple, src/barcode_hmm.c:244-385).
@@ -1348,6 +1381,13 @@ bool plan_multi(const td_stream_file* files, const int K, const int N, const int
 extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files, int32_t n_devices, const char* out_prefix, int32_t dust,
                                    const td_stream_opts* opts, td_stream_stats* stats, int64_t* counts)
 {
+	return td_stream_run_multi_hits(files, n_files, n_devices, out_prefix, dust, opts, stats, counts, nullptr, 0);
+}
+
+extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_files, int32_t n_devices, const char* out_prefix, int32_t dust,
+                                        const td_stream_opts* opts, td_stream_stats* stats, int64_t* counts, int64_t* artifact_hits,
+                                        int32_t n_artifacts)
+{
 	if (!files || n_files < 1 || n_files > 8 || !out_prefix) { td_io_set_error("td_stream_run_multi: bad arguments (1..8 input files, an output prefix)"); return TD_FAIL; }
 	if (n_devices < 1) n_devices = 1;
 	const int K = n_files, N = n_devices;
@@ -1382,7 +1422,9 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 	int name_format = -1;
 	auto check = [&](const Tuple& t) -> std::string {
 		for (int k = 0; k < K; k++)
-			if (!t.b[(size_t)k] || t.b[(size_t)k]->n != t.b[0]->n) return "td_stream_run_multi: the input files differ in their number of records";
+			if (!t.b[(size_t)k] || t.b[(size_t)k]->n != t.b[0]->n)   // (the controller's own words behind ours, barcode_hmm.c:262)
+				return std::string("td_stream_run_multi: the input files differ in their number of records: Input File:") + files[0].path + " and " +
+				       files[k].path + " differ in number of entries.";
 		if (!first) return std::string();
 		first = false;
 		for (int64_t i = 0; i < std::min<int64_t>(1000, t.b[0]->n); i++) {
@@ -1397,6 +1439,7 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 	// the write stage: run_rna_dust for the files that no device sees, the per-record combination, print_all
 	int64_t cnt[TD_NUM_COUNTERS];
 	for (int q = 0; q < TD_NUM_COUNTERS; q++) cnt[q] = 0;
+	if (artifact_hits) for (int32_t q = 0; q < n_artifacts; q++) artifact_hits[q] = 0;
 	std::vector<int32_t> ctype, cbar;
 	auto write = [&](Tuple& t) -> bool {
 		const int64_t n = t.b[0]->n;
@@ -1424,6 +1467,8 @@ extern "C" int td_stream_run_multi(const td_stream_file* files, int32_t n_files,
 			cbar[(size_t)i] = t.b[(size_t)(m.bar_file >= 0 ? m.bar_file : 0)]->res[i].barcode;
 			cnt[c & (TD_NUM_OUTCOME_SLOTS - 1)]++;                                      // the controller's counting, :354-384
 			if (c == TD_EXTRACT_SUCCESS && cbar[(size_t)i] >= 0) cnt[TD_NUM_OUTCOME_SLOTS + (cbar[(size_t)i] & 0xFF)]++;
+			// reference_fasta->mer_hash (:381): on the combined outcome, which is the largest of the files' -- of two files' hits the later sequence
+			if (artifact_hits && (c & 0xFF) == TD_EXTRACT_FAIL_MATCHES_ARTIFACTS && (c >> 8) >= 1 && (c >> 8) <= n_artifacts) artifact_hits[(c >> 8) - 1]++;
 		}
 		bool ok = true;
 		for (int k = 0; k < K && ok; k++)

@@ -24,15 +24,24 @@ ABI_SYMBOLS = [
     "td_counts_get", "td_diag_get", "td_counts_device_ptr", "td_last_kernel_ms", "td_timeline_origin", "td_last_kernel_times", "td_batch_info", "td_set_option", "td_get_option", "td_set_artifacts", "td_spec_source", "td_spec_prune_info", "td_spec_restart_info",
     "td_spec_probe", "td_spec_probe_params", "td_spec_wait",
     "td_submit", "td_wait", "td_host_alloc", "td_host_free", "td_set_batch_window", "td_set_window", "td_arch_scores",
+    "td_artifact_hits_get",
 ]
 MULTI_ABI_SYMBOLS = ["td_shard_bounds", "td_count_outcomes", "td_multi_create", "td_multi_destroy", "td_multi_last_error",
                      "td_multi_size", "td_multi_ctx", "td_multi_model_upload", "td_multi_set_params", "td_multi_set_window", "td_multi_set_artifacts",
-                     "td_multi_decode", "td_multi_counts", "td_multi_counts_reset", "td_multi_uses_rccl", "td_bind_host_to_device", "td_host_halves_bench"]
+                     "td_multi_decode", "td_multi_counts", "td_multi_counts_reset", "td_multi_uses_rccl", "td_bind_host_to_device", "td_host_halves_bench",
+                     "td_multi_artifact_hits"]
 IO_ABI_SYMBOLS = ["td_io_last_error", "td_reads_parse", "td_reads_free", "td_writer_open", "td_writer_write", "td_writer_close",
-                  "td_fasta_parse", "td_fasta_free", "td_stream_run", "td_stream_run_multi", "td_stream_release", "td_format_q"]
+                  "td_fasta_parse", "td_fasta_free", "td_stream_run", "td_stream_run_multi", "td_stream_run_multi_hits", "td_stream_release",
+                  "td_format_q"]
 MODEL_ABI_SYMBOLS = ["td_arch_parse", "td_arch_free", "td_sequence_stats", "td_sequence_stats_window", "td_model_build", "td_model_tables_free",
                      "td_calibration_emit", "td_calibration_select", "td_calibration_free", "td_estimate_threshold",
-                     "td_compare_architectures", "td_simreads", "td_text_free"]
+                     "td_compare_architectures", "td_simreads", "td_text_free", "td_sequence_stats_limit",
+                     "td_sequence_stats_device"]
+
+# include/tagdust_run.h: the whole-run driver
+RUN_ABI_SYMBOLS = ["td_run_opts_new", "td_run_opts_free", "td_run_last_error", "td_run_parse_args", "td_run_usage", "td_run_version",
+                   "td_run_plan", "td_run_plan_free", "td_run_plan_describe", "td_run_output_files_describe", "td_run_arch_file_describe", "td_run_execute",
+                   "td_run_report_clear", "td_run_format_summary"]
 
 RESULT_DTYPE = np.dtype([
     ("f_score", "<f4"), ("b_score", "<f4"), ("r_score", "<f4"), ("bar_prob", "<f4"), ("mapq", "<f4"),
@@ -161,6 +170,11 @@ def load_library():
     lib.td_arch_free.restype = None
     lib.td_sequence_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_SeqStats)]
     lib.td_sequence_stats_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(_SeqStats)]
+    lib.td_sequence_stats_limit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(_SeqStats)]
+    lib.td_sequence_stats_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                             C.POINTER(_SeqStats)]
+    lib.td_artifact_hits_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    lib.td_multi_artifact_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     lib.td_model_build.argtypes = [C.c_void_p, C.POINTER(_SeqStats), C.c_float, C.c_float, C.POINTER(C.c_void_p)]
     lib.td_model_tables_free.argtypes = [C.c_void_p]
     lib.td_model_tables_free.restype = None
@@ -271,6 +285,49 @@ def _arch_and_stats(lib, segments, codes, offs):
         lib.td_arch_free(arch)
         raise TdError("td_sequence_stats failed")
     return arch, st
+
+
+def _parse_arch(lib, segments):
+    arr = (C.c_char_p * len(segments))(*[s.encode() for s in segments])
+    arch = C.c_void_p()
+    if lib.td_arch_parse(arr, len(segments), C.byref(arch)) != 0:
+        raise TdError("td_arch_parse failed for %r" % (segments,))
+    return arch
+
+
+def sequence_stats(segments, codes, offs, scan_limit=1000001, window=None):
+    """td_sequence_stats_limit on the host (no GPU needed): the _SeqStats structure itself, so that two results can be
+    compared as bytes."""
+    lib = load_library()
+    arch = _parse_arch(lib, segments)
+    try:
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offs = np.ascontiguousarray(offs, np.int64)
+        ms, me = window if window else (-1, -1)
+        st = _SeqStats()
+        if lib.td_sequence_stats_limit(arch, codes.ctypes.data, offs.ctypes.data, len(offs) - 1, int(scan_limit), int(ms), int(me),
+                                       C.byref(st)) != 0:
+            raise TdError("td_sequence_stats_limit failed")
+        return st
+    finally:
+        lib.td_arch_free(arch)
+
+
+def sequence_stats_device(ctx, segments, codes, offs, scan_limit=1000001, window=None):
+    """td_sequence_stats_device: the same statistics with the counting on ctx's device."""
+    lib = load_library()
+    arch = _parse_arch(lib, segments)
+    try:
+        codes = np.ascontiguousarray(codes, np.uint8)
+        offs = np.ascontiguousarray(offs, np.int64)
+        ms, me = window if window else (-1, -1)
+        st = _SeqStats()
+        if lib.td_sequence_stats_device(ctx.h, arch, codes.ctypes.data, offs.ctypes.data, len(offs) - 1, int(scan_limit), int(ms), int(me),
+                                        C.byref(st)) != 0:
+            raise TdError(lib.td_last_error(ctx.h).decode() or "td_sequence_stats_device failed")
+        return st
+    finally:
+        lib.td_arch_free(arch)
 
 
 def calibration_emit(segments, codes, offs, d=0.1, seed=42, n_reads=400000, rng=0):
@@ -497,6 +554,139 @@ def stream_run_multi(files, out_prefix, n_devices=1, dust=100, batch_reads=0, n_
                 lib.td_arch_free(a)
 
 
+class _RunOpts(C.Structure):
+    """td_run_opts (include/tagdust_run.h)"""
+    _fields_ = [("segments", C.c_char_p * 10), ("arch_file", C.c_char_p), ("outfile", C.c_char_p), ("num_threads", C.c_int32),
+                ("confidence_threshold", C.c_float), ("sequencer_error_rate", C.c_float), ("indel_frequency", C.c_float),
+                ("minlen", C.c_int32), ("dust", C.c_int32), ("reference_fasta", C.c_char_p), ("filter_error", C.c_int32),
+                ("matchstart", C.c_int32), ("matchend", C.c_int32), ("seed", C.c_uint32), ("n_infiles", C.c_int32),
+                ("infile", C.POINTER(C.c_char_p)), ("n_devices", C.c_int32), ("devices", C.c_int32 * 16), ("flavour", C.c_int32),
+                ("host_threads", C.c_int32), ("batch_reads", C.c_int32), ("sync_compile", C.c_int32), ("stats_on_host", C.c_int32),
+                ("force", C.c_int32), ("dry_run", C.c_int32), ("help", C.c_int32), ("version", C.c_int32), ("echo_log", C.c_int32),
+                ("argc", C.c_int32), ("argv", C.POINTER(C.c_char_p))]
+
+
+class _RunReport(C.Structure):
+    """td_run_report (include/tagdust_run.h)"""
+    _fields_ = [("error", C.c_char * 1024), ("counts", C.c_int64 * NUM_COUNTERS), ("n_artifacts", C.c_int32),
+                ("artifact_hits", C.POINTER(C.c_int64)), ("artifact_names", C.POINTER(C.c_char_p)), ("n_files", C.c_int32),
+                ("thresholds", C.c_float * 8), ("selected_threshold", C.c_float), ("architectures", C.c_char_p * 8),
+                ("stream", _StreamStats), ("arch_s", C.c_double), ("stats_s", C.c_double), ("calibration_s", C.c_double),
+                ("compile_wait_s", C.c_double), ("stream_s", C.c_double), ("stats_on_device", C.c_int32), ("log", C.c_char_p)]
+
+
+def _run_lib():
+    lib = load_library()
+    lib.td_run_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(_RunOpts)), C.c_char_p, C.c_size_t]
+    lib.td_run_opts_free.argtypes = [C.POINTER(_RunOpts)]
+    lib.td_run_opts_free.restype = None
+    lib.td_run_last_error.restype = C.c_char_p
+    lib.td_run_plan.argtypes = [C.POINTER(_RunOpts), C.POINTER(C.c_void_p)]
+    lib.td_run_plan_free.argtypes = [C.c_void_p]
+    lib.td_run_plan_free.restype = None
+    lib.td_run_plan_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+    lib.td_run_plan_describe.restype = C.c_int64
+    lib.td_run_output_files_describe.argtypes = [C.POINTER(_RunOpts), C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_int64]
+    lib.td_run_output_files_describe.restype = C.c_int64
+    lib.td_run_arch_file_describe.argtypes = [C.c_char_p, C.c_char_p, C.c_int64]
+    lib.td_run_arch_file_describe.restype = C.c_int64
+    lib.td_run_execute.argtypes = [C.POINTER(_RunOpts), C.POINTER(_RunReport)]
+    lib.td_run_report_clear.argtypes = [C.POINTER(_RunReport)]
+    lib.td_run_report_clear.restype = None
+    lib.td_run_format_summary.argtypes = [C.POINTER(_RunOpts), C.POINTER(_RunReport), C.c_char_p, C.c_int64]
+    lib.td_run_format_summary.restype = C.c_int64
+    return lib
+
+
+class RunOpts:
+    """td_run_parse_args: the tagdust command line (without the program name) as td_run_opts; .o is the C structure."""
+
+    def __init__(self, args):
+        self.lib = _run_lib()
+        argv = [b"tagdust-hip"] + [os.fsencode(a) for a in args]
+        arr = (C.c_char_p * len(argv))(*argv)
+        self.p = C.POINTER(_RunOpts)()
+        err = C.create_string_buffer(1024)
+        if self.lib.td_run_parse_args(len(argv), arr, C.byref(self.p), err, len(err)) != 0:
+            self.p = None
+            raise TdError(err.value.decode())
+        self.o = self.p.contents
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.lib.td_run_opts_free(self.p)
+            self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _text_of(call):
+    n = int(call(None, 0))
+    if n < 0:
+        raise TdError(_run_lib().td_run_last_error().decode())
+    buf = C.create_string_buffer(n + 1)
+    call(buf, n + 1)
+    return buf.value.decode()
+
+
+def run_plan(args):
+    """td_run_plan + td_run_plan_describe: the decisions of a run that need no data (no GPU), one "key: value" line each."""
+    o = RunOpts(args)
+    try:
+        plan = C.c_void_p()
+        if o.lib.td_run_plan(o.p, C.byref(plan)) != 0:
+            raise TdError(o.lib.td_run_last_error().decode())
+        try:
+            return _text_of(lambda b, n: o.lib.td_run_plan_describe(plan, b, n))
+        finally:
+            o.lib.td_run_plan_free(plan)
+    finally:
+        o.close()
+
+
+def run_output_files(args, architectures):
+    """td_run_output_files_describe: the output files of a run with these per-file architectures ("-1 B:ACGT -2 R:N" each)."""
+    o = RunOpts(args)
+    try:
+        arr = (C.c_char_p * len(architectures))(*[a.encode() for a in architectures])
+        return _text_of(lambda b, n: o.lib.td_run_output_files_describe(o.p, arr, len(architectures), b, n)).splitlines()
+    finally:
+        o.close()
+
+
+def run_arch_file(path):
+    """td_run_arch_file_describe: the candidate architectures of an -arch file, one list of "-k segment" words per candidate."""
+    lib = _run_lib()
+    return _text_of(lambda b, n: lib.td_run_arch_file_describe(os.fsencode(path), b, n)).splitlines()
+
+
+def run_execute(args):
+    """td_run_execute: a whole run from the tagdust command line (without the program name); returns the report as a dict."""
+    o = RunOpts(args)
+    rep = _RunReport()
+    try:
+        rc = o.lib.td_run_execute(o.p, C.byref(rep))
+        if rc != 0:
+            raise TdError(rep.error.decode())
+        n, k = int(rep.n_artifacts), int(rep.n_files)
+        return {
+            "counts": np.array(list(rep.counts), np.int64),
+            "artifact_hits": {rep.artifact_names[j].decode(): int(rep.artifact_hits[j]) for j in range(n)},
+            "thresholds": [float(rep.thresholds[i]) for i in range(k)],
+            "architectures": [rep.architectures[i].decode() for i in range(k)],
+            "stream": {f: getattr(rep.stream, f) for f, _ in _StreamStats._fields_},
+            "seconds": {f: getattr(rep, f + "_s") for f in ("arch", "stats", "calibration", "compile_wait", "stream")},
+            "stats_on_device": bool(rep.stats_on_device), "log": (rep.log or b"").decode(),
+        }
+    finally:
+        o.lib.td_run_report_clear(C.byref(rep))
+        o.close()
+
+
 def stream_release():
     """td_stream_release: free the page-locked batch buffers td_stream_run keeps for the next run of the process (at most 1 GiB;
     the library also frees them when the last context is destroyed)."""
@@ -697,6 +887,12 @@ class TagdustHip:
         self._chk(self.lib.td_counts_get(self.h, c.ctypes.data))
         return c
 
+    def artifact_hits(self, n_seq):
+        """td_artifact_hits_get: reads per -ref sequence since the filter was set / the counters were reset; int64[n_seq]."""
+        h = np.zeros(int(n_seq), np.int64)
+        self._chk(self.lib.td_artifact_hits_get(self.h, h.ctypes.data, len(h)))
+        return h
+
     def diag(self):
         """td_diag_get: the 64 diagnostic words of the development knobs (word k = historical slot 192 + k)."""
         d = np.zeros(NUM_DIAG_COUNTERS, np.int64)
@@ -836,6 +1032,12 @@ class TagdustMulti:
 
     def counts_reset(self):
         self._chk(self.lib.td_multi_counts_reset(self.h))
+
+    def artifact_hits(self, n_seq):
+        """td_multi_artifact_hits: reads per -ref sequence, summed over the devices; int64[n_seq]."""
+        h = np.zeros(int(n_seq), np.int64)
+        self._chk(self.lib.td_multi_artifact_hits(self.h, h.ctypes.data, len(h)))
+        return h
 
     def uses_rccl(self):
         return bool(self.lib.td_multi_uses_rccl(self.h))
