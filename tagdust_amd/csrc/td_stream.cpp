@@ -44,6 +44,7 @@
 
 #include "../../include/tagdust_io.h"
 #include "td_io_internal.h"
+#include "td_merge_internal.h"
 
 namespace {
 
@@ -1484,3 +1485,6 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 	if (err.failed()) { td_io_set_error(err.message()); return TD_FAIL; }
 	return TD_OK;
 }
+
+// td_merge_stream: the `merge` controller on the same readers
+#include "td_merge_stream.inc"

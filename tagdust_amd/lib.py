@@ -1066,3 +1066,107 @@ def simreads(barcodes, seed=42, rng=0, barnum=0, barlen=0, readlen=0, readlen_mo
         return C.string_at(out, n.value)
     finally:
         lib.td_text_free(out)
+
+
+# ---- include/tagdust_merge.h: merging of overlapping read pairs (used by the tests) ----
+MERGE_ABI_SYMBOLS = ["td_merge_opts_default", "td_merge_last_error", "td_merge_tables_build", "td_merge_tables_free", "td_merge_host",
+                     "td_merge_device", "td_merge_result_free", "td_merge_stream", "td_merge_parse_args", "td_merge_usage"]
+MERGE_TABLE_AUTO, MERGE_TABLE_LDS, MERGE_TABLE_GLOBAL = 0, 1, 2
+MERGE_WRITTEN, MERGE_BELOW, MERGE_NO_CANDIDATE = 0, 1, 2
+MERGE_RECORD_DTYPE = np.dtype([("best_d", "<i4"), ("out_len", "<i4"), ("id", "<i4"), ("aligned", "<i4"), ("status", "<i4")])
+
+
+class _MergeOpts(C.Structure):
+    _fields_ = [("min_overlap", C.c_int32), ("threshold", C.c_float), ("n_threads", C.c_int32), ("batch_pairs", C.c_int32),
+                ("device", C.c_int32), ("table_placement", C.c_int32)]
+
+
+class _MergeTables(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("dim", C.c_int32), ("qchar", C.c_uint8 * 256), ("qindex", C.c_int16 * 256),
+                ("profile", C.POINTER(C.c_float)), ("T", C.POINTER(C.c_float))]
+
+
+class _MergeResult(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("rec", C.c_void_p), ("out_off", C.POINTER(C.c_int64)), ("seq", C.c_void_p), ("qual", C.c_void_p),
+                ("n_written", C.c_int64), ("n_below", C.c_int64), ("n_too_short", C.c_int64), ("table_in_lds", C.c_int32),
+                ("n_on_host", C.c_int32), ("kernel_ms", C.c_float)]
+
+
+class _MergeStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("n_written", C.c_int64), ("n_below", C.c_int64), ("n_too_short", C.c_int64),
+                ("n_batches", C.c_int64), ("bytes_in", C.c_int64), ("bytes_out", C.c_int64), ("wall_s", C.c_double), ("read_s", C.c_double),
+                ("parse_s", C.c_double), ("tables_s", C.c_double), ("merge_s", C.c_double), ("kernel_s", C.c_double), ("write_s", C.c_double)]
+
+
+def _merge_lib():
+    lib = load_library()
+    lib.td_merge_last_error.restype = C.c_char_p
+    lib.td_merge_tables_build.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.POINTER(_MergeTables))]
+    lib.td_merge_tables_free.argtypes = [C.POINTER(_MergeTables)]
+    lib.td_merge_tables_free.restype = None
+    for f in (lib.td_merge_host, lib.td_merge_device):
+        f.argtypes = [C.POINTER(_Reads), C.POINTER(_Reads), C.POINTER(_MergeOpts), C.POINTER(C.POINTER(_MergeResult))]
+    lib.td_merge_result_free.argtypes = [C.POINTER(_MergeResult)]
+    lib.td_merge_result_free.restype = None
+    lib.td_merge_stream.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(_MergeOpts), C.POINTER(_MergeStats)]
+    return lib
+
+
+def merge_tables(qual):
+    """td_merge_tables_build for the quality characters in `qual` (bytes): nq, dim, qchar, qindex, profile [nq, 2], T [dim, dim]."""
+    lib = _merge_lib()
+    buf = np.frombuffer(bytes(qual), dtype=np.uint8)
+    p = C.POINTER(_MergeTables)()
+    if lib.td_merge_tables_build(buf.ctypes.data if len(buf) else None, len(buf), C.byref(p)) != 0:
+        raise TdError(lib.td_merge_last_error().decode())
+    try:
+        t = p.contents
+        nq, dim = int(t.nq), int(t.dim)
+        return {"nq": nq, "dim": dim, "qchar": bytes(t.qchar[:nq]), "qindex": np.array(t.qindex[:], np.int16),
+                "profile": np.ctypeslib.as_array(t.profile, shape=(nq, 2)).copy(), "T": np.ctypeslib.as_array(t.T, shape=(dim, dim)).copy()}
+    finally:
+        lib.td_merge_tables_free(p)
+
+
+def merge_batch(reads1, reads2, device=None, min_overlap=16, threshold=0.0, n_threads=0, table_placement=MERGE_TABLE_AUTO):
+    """td_merge_host (device None) or td_merge_device on two ParsedReads.  Returns rec (MERGE_RECORD_DTYPE), out_off, seq, qual (uint8
+    arrays), the counts, table_in_lds, n_on_host, kernel_ms."""
+    lib = _merge_lib()
+    o = _MergeOpts(int(min_overlap), float(threshold), int(n_threads), 0, -1 if device is None else int(device), int(table_placement))
+    p = C.POINTER(_MergeResult)()
+    call = lib.td_merge_host if device is None else lib.td_merge_device
+    if call(reads1._p, reads2._p, C.byref(o), C.byref(p)) != 0:
+        raise TdError(lib.td_merge_last_error().decode())
+    try:
+        r = p.contents
+        n = int(r.n_pairs)
+        out_off = np.ctypeslib.as_array(r.out_off, shape=(n + 1,)).copy()
+        total = int(out_off[-1])
+        rec = np.frombuffer(C.string_at(r.rec, n * MERGE_RECORD_DTYPE.itemsize), dtype=MERGE_RECORD_DTYPE).copy()
+        return {"rec": rec, "out_off": out_off, "seq": np.frombuffer(C.string_at(r.seq, total), np.uint8).copy(),
+                "qual": np.frombuffer(C.string_at(r.qual, total), np.uint8).copy(), "n_written": int(r.n_written), "n_below": int(r.n_below),
+                "n_too_short": int(r.n_too_short), "table_in_lds": int(r.table_in_lds), "n_on_host": int(r.n_on_host),
+                "kernel_ms": float(r.kernel_ms)}
+    finally:
+        lib.td_merge_result_free(p)
+
+
+def merge_text(res, names):
+    """the records `merge` prints for a merge_batch result: "@<name of read 1>\\n<seq>\\n+\\n<qual>\\n" per written pair (bytes)"""
+    seq, qual = res["seq"].tobytes(), res["qual"].tobytes()
+    out = []
+    for name, r, o in zip(names, res["rec"], res["out_off"]):
+        n = int(r["out_len"])
+        if n:
+            out.append(b"@" + name + b"\n" + seq[o:o + n] + b"\n+\n" + qual[o:o + n] + b"\n")
+    return b"".join(out)
+
+
+def merge_stream(in1, in2, out_path, device=None, min_overlap=16, threshold=0.0, n_threads=0, batch_pairs=0):
+    """td_merge_stream: two FASTQ files (plain, .gz, .bz2) to one file of merged reads; device None = the host path.  Returns the statistics."""
+    lib = _merge_lib()
+    o = _MergeOpts(int(min_overlap), float(threshold), int(n_threads), int(batch_pairs), -1 if device is None else int(device), MERGE_TABLE_AUTO)
+    st = _MergeStats()
+    if lib.td_merge_stream(os.fsencode(in1), os.fsencode(in2), os.fsencode(out_path), C.byref(o), C.byref(st)) != 0:
+        raise TdError(lib.td_merge_last_error().decode())
+    return {k: getattr(st, k) for k, _ in _MergeStats._fields_}
