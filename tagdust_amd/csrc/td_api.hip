@@ -4,38 +4,20 @@
 // private model copies, one context per GPU holds the flattened model in HBM and launches the decode
 // kernel (td_kernels.hip) over a resident batch.  No torch, no CPU fallback: every entry point fails
 // with TD_FAIL (and a message in td_last_error) when HIP does.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <cmath>
 #include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
 #include <unistd.h>
 
-#include <condition_variable>
-#include <deque>
-#include <functional>
-#include <map>
-#include <memory>
 #include <mutex>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "../../include/tagdust_hip.h"
 #include "../../include/tagdust_model.h"
-#include "td_device.h"
-#include "td_jit.h"
-#include "td_stage.h"
-#include "td_host_inner.h"
+#include "td_ctx.h"
 #include "td_rnadust.h"
 #include "td_stats.h"
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t td_launch_decode(const TdKernelArgs* ka, hipStream_t stream);   // library-internal
-extern "C" __attribute__((visibility("hidden"))) int td_kernel_block_threads(void);
-extern "C" __attribute__((visibility("hidden"))) hipError_t td_launch_decode_multi(const TdKernelArgs* d_args, int n_models, int max_slots, hipStream_t stream);
 
 static float g_logsum[TD_LOGSUM_SIZE];
 static bool g_logsum_ready = false;
@@ -52,99 +34,9 @@ static void init_logsum_host()
 // prob2scaledprob(), src/misc.c:85-92
 static float p2sp(float p) { return p == 0.0f ? -INFINITY : (float)log((double)p); }
 
-#define TD_MAX_PIPELINE 4
-// the device counter block: what the ABI reports, then the diagnostic tail of the development knobs (td_diag_get)
-#define TD_COUNTER_WORDS (TD_NUM_COUNTERS + TD_NUM_DIAG_COUNTERS)
-
-// One batch on its way through the device (see "batches" below).  What a slot knows about ITS BATCH lives in three groups, each
-// value-initialised as a whole by the step that owns it -- so that nothing a branch of that step does not set can survive from
-// the batch before (round 3's soak fault was exactly that: a label-run table of the previous, smaller batch):
-//   TdStaged  <- slot_stage():       the reads as staged on the device and the workspace geometry chosen for them
-//   TdDecoded <- slot_decode():      what the last launch over the staged batch was and left behind
-//   TdFetch   <- slot_fetch_begin(): where the results go and in which form they travel
-// slot_stage() also resets the two later groups, slot_decode() the last one.  What is left in TdSlot itself belongs to the slot,
-// not to a batch: device / pinned buffers with their capacities, events, the ticket.
-struct TdRoute {             // where a batch runs (chosen by the caller of slot_stage, per batch)
-	hipStream_t cs = nullptr;   // the compute stream (c->stream, or c->stream2 for every other pipelined batch)
-	hipStream_t aux = nullptr;  // the stream of its sort / pack kernels: cs itself, or the context's high-priority stream for them
-	hipStream_t fin = nullptr;  // ... and of its finish kernel (a stream of its own: it waits for the decode kernel, the next batch's pack must not)
-	int wsi = 0;                // ... and the workspace (0 / 1) that goes with cs
-	bool pipelined = false;     // a td_submit batch (the synchronous calls use slot 0 with pipelined = false)
-};
-struct TdStaged : TdRoute {
-	int64_t n_reads = 0, n_bases = 0;
-	int32_t n_tiles = 0, lmax = 0, nw2 = 0, nw1 = 0;
-	int is_ascii = 0;
-	bool sorted = false;      // device order differs from the caller's (reads of several lengths)
-	bool staged = false;      // inputs are packed on the device: td_run may launch
-	bool for_spec = false;    // ... and the workspace geometry is the specialised kernel's: a batch is decoded by the kernel it was staged
-	                          // for, also when a background compile is handed over between its upload and its td_run
-	bool raw_direct = false;  // the upload read the caller's page-locked buffer itself (no staging copy)
-	const uint8_t* raw_host = nullptr;   // the batch's bases on the host, valid until the batch has been waited for: the pinned staging
-	                                     // copy, or the caller's own page-locked buffer under the "stable_input" contract; else NULL
-	TdStageBatch sb{};
-	TdWsLayout lay{};
-	TdSpecLayout slay{};
-	int32_t n_wave_slots = 0;
-	int64_t ws_slot_bytes = 0;
-	// length classes (specialised kernel): the n_long longest tiles are longer than lmax_small, the geometry of most wave slots;
-	// n_big >= n_long slots keep the geometry of the batch's longest read (slay_big).  n_long = 0: one geometry.
-	int32_t n_long = 0, lmax_small = 0, n_big = 0;
-	TdSpecLayout slay_big{};
-	int64_t ws_bytes = 0;       // workspace bytes this batch's launch uses
-};
-struct TdDecoded {
-	int mode = 0;
-	bool ran = false;
-	float last_ms = -1.0f;
-	int32_t runs_cap = 0;       // entries per read in d_runs (0: the last launch left no label runs)
-	bool hits_queued = false;   // the per-artifact hit count is queued behind the launch (ev_hits): it reads d_out like the finish kernel
-};
-struct TdFetch {
-	td_read_result* u_res = nullptr; int8_t* u_labels = nullptr; uint8_t* u_seq = nullptr;   // the caller's output buffers
-	bool res_direct = false, lab_direct = false, seq_direct = false;                          // ... are page-locked
-	bool copies_deferred = false;   // td_wait issues the device-to-host copies (pipelined calls)
-	bool use_keep = false, use_rle = false;   // compact egress: keep bits instead of the rewritten sequence, label runs instead of labels
-	int32_t rle_cap = 0;
-	bool finished = false;          // the finish kernel is queued: slot_fetch_end has something to collect
-};
-struct TdSlot : TdStaged, TdDecoded, TdFetch {
-	int64_t ticket = 0;       // td_submit: 0 = free
-	void reset_staged(const TdRoute& r) { static_cast<TdStaged&>(*this) = TdStaged(); static_cast<TdRoute&>(*this) = r; reset_decoded(); }
-	void reset_decoded() { static_cast<TdDecoded&>(*this) = TdDecoded(); reset_fetch(); }
-	void reset_fetch() { static_cast<TdFetch&>(*this) = TdFetch(); }
-	// device
-	uint8_t* d_raw = nullptr;      size_t cap_raw = 0;
-	int64_t* d_offs = nullptr;     size_t cap_offs = 0;
-	int32_t* d_read_at = nullptr;  size_t cap_read_at = 0;
-	uint32_t* d_keys = nullptr;    size_t cap_keys = 0;
-	int32_t* d_vals = nullptr;     size_t cap_vals = 0;
-	uint8_t* d_sort_tmp = nullptr; size_t cap_sort_tmp = 0;
-	uint32_t* d_packed = nullptr;  size_t cap_packed = 0;
-	int32_t* d_lens = nullptr;     size_t cap_lens = 0;
-	uint8_t* d_art_left = nullptr; size_t cap_art_left = 0;
-	uint8_t* d_out = nullptr;      size_t cap_out = 0;    // decode-kernel outputs, device order
-	uint8_t* d_res = nullptr;      size_t cap_res = 0;    // results in the caller's order
-	uint8_t* d_seq = nullptr;      size_t cap_seq = 0;
-	int8_t*  d_lab = nullptr;      size_t cap_lab = 0;
-	// compact egress: what the host rebuilds the rewritten sequences and the labels from (slot_fetch_begin)
-	uint32_t* d_keepo = nullptr;   size_t cap_keepo = 0;
-	uint32_t* d_rle = nullptr;     size_t cap_rle = 0;     // (+ one word behind the runs: the overflow flag)
-	uint32_t* d_runs = nullptr;    size_t cap_runs = 0;    // label runs in device order, left by the specialised kernel (+ the overflow flag)
-	uint32_t* h_keepo = nullptr;   size_t cap_h_keepo = 0;
-	uint32_t* h_rle = nullptr;     size_t cap_h_rle = 0;
-	// pinned host staging for pageable caller memory
-	uint8_t* h_raw = nullptr;      size_t cap_h_raw = 0;
-	int64_t* h_offs = nullptr;     size_t cap_h_offs = 0;
-	uint8_t* h_res = nullptr;      size_t cap_h_res = 0;
-	uint8_t* h_seq = nullptr;      size_t cap_h_seq = 0;
-	int8_t*  h_lab = nullptr;      size_t cap_h_lab = 0;
-	hipEvent_t ev_up = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_done = nullptr, ev_down = nullptr, ev_pack = nullptr, ev_hits = nullptr;
-};
-
 // Host threads a context may use for its copies between pageable caller memory and pinned staging: TD_HOST_THREADS, else the
 // machine's threads, at most 16 (option "host_threads"; td_multi_create shares the machine's threads out over its devices).
-static int default_host_threads()
+int default_host_threads()
 {
 	int nt = (int)std::thread::hardware_concurrency();
 	if (const char* e = getenv("TD_HOST_THREADS")) nt = atoi(e);
@@ -184,175 +76,7 @@ __attribute__((constructor)) static void td_want_hw_queues()
 	if (!g_hwq_late) setenv("GPU_MAX_HW_QUEUES", "8", 0);
 }
 
-// The description a background compile works on: its own copy (a context's m_desc points into the context's vectors).
-struct ModelCopy {
-	td_model_desc d{};
-	std::vector<int32_t> n_hmm, n_col, finger_len, label;
-	std::vector<float> skip, trans, eM, eI, sM, sI, A;
-	std::vector<int8_t> seg_type;
-	void assign(const td_model_desc* m)
-	{
-		n_hmm.assign(m->n_hmm, m->n_hmm + m->S); n_col.assign(m->n_col, m->n_col + m->S); skip.assign(m->skip, m->skip + m->S);
-		seg_type.assign(m->seg_type, m->seg_type + m->S); finger_len.assign(m->finger_len, m->finger_len + m->S);
-		trans.assign(m->trans, m->trans + (size_t)m->C * 9); eM.assign(m->eM, m->eM + (size_t)m->C * 5); eI.assign(m->eI, m->eI + (size_t)m->C * 5);
-		sM.assign(m->sM, m->sM + m->C); sI.assign(m->sI, m->sI + m->C);
-		label.assign(m->label, m->label + m->H); A.assign(m->A, m->A + (size_t)m->H * m->H);
-		d = *m;
-		d.n_hmm = n_hmm.data(); d.n_col = n_col.data(); d.skip = skip.data(); d.seg_type = seg_type.data(); d.finger_len = finger_len.data();
-		d.trans = trans.data(); d.eM = eM.data(); d.eI = eI.data(); d.sM = sM.data(); d.sI = sI.data(); d.label = label.data(); d.A = A.data();
-	}
-};
-
-// One background compile.  The worker calls td_spec_compile on the job's own copies and nothing else: it touches no context and no
-// device.  Contexts that want the same code object share the job (g_jobs, by cache key); whoever lets go of it last joins the
-// thread, and every context waits for its jobs before it goes (td_ctx_destroy), so no thread is ever detached.
-struct SpecJob {
-	uint64_t key = 0;
-	ModelCopy model;
-	TdSpecPlan plan;
-	int lsum_oob = 0, window = 0;
-	std::mutex mu;
-	std::condition_variable cv;
-	bool done = false;
-	int rc = TD_FAIL;
-	std::vector<char> code;
-	std::string log;
-	std::thread th;
-	void run()
-	{
-		std::vector<char> out;
-		std::string lg;
-		const int r = td_spec_compile(&model.d, plan, lsum_oob, window, out, lg);
-		std::lock_guard<std::mutex> lk(mu);
-		code.swap(out); log.swap(lg); rc = r; done = true;
-		cv.notify_all();
-	}
-	bool finished() { std::lock_guard<std::mutex> lk(mu); return done; }
-	void wait() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return done; }); }
-	~SpecJob() { if (th.joinable()) th.join(); }
-};
-static std::mutex g_jobs_mu;
-static std::map<uint64_t, std::weak_ptr<SpecJob>> g_jobs;   // by cache key: one compile per code object in flight per process
-
-// A process that ends with a context it never destroyed must not run the library's static destructors under a compile that is
-// still going: registered (once, with the first job -- so it runs before the destructors of the statics above and of the code
-// cache, which were constructed when the library was loaded), this waits for every job in flight.
-static void wait_for_all_spec_jobs()
-{
-	std::vector<std::shared_ptr<SpecJob>> live;
-	{
-		std::lock_guard<std::mutex> lk(g_jobs_mu);
-		for (auto& kv : g_jobs) if (auto j = kv.second.lock()) live.push_back(j);
-	}
-	for (auto& j : live) j->wait();
-}
-
-// what the probe said about a code object on a device, for the life of the process
-struct ProbeVerdict { int mismatches = 0, read = -1, field = -1; };
-static std::mutex g_probe_mu;
-static std::map<std::pair<uint64_t, int>, ProbeVerdict> g_probe_verdicts;
-
-struct td_ctx {
-	int device = 0;
-	int host_threads = default_host_threads();
-	CopyPool pool;
-	hipStream_t stream = nullptr;
-	std::string err;
-	int n_cu = 0;
-	size_t hbm_total = 0;
-
-	// model
-	bool have_model = false;
-	TdModelHeader hdr{};
-	std::vector<int32_t> label;
-	TdModelHeader* d_hdr = nullptr;
-	TdCol* d_cols = nullptr;
-	uint32_t* d_hinfo = nullptr;
-	int32_t* d_pred_off = nullptr;
-	int32_t* d_pred_idx = nullptr;
-	float* d_logsum = nullptr;
-	unsigned long long* d_counters = nullptr;
-
-	// model-specialised kernel (td_spec_kernel.inc through hiprtc)
-	int specialize = 1;
-	bool spec_ready = false;
-	hipModule_t spec_mod = nullptr;
-	hipFunction_t spec_fn = nullptr;
-	std::vector<int32_t> m_n_hmm, m_n_col;
-	std::vector<float> m_trans;
-	// deep copy of the uploaded description (a batch with very long reads recompiles the kernel with the clamped logsum)
-	td_model_desc m_desc{};
-	TdSpecPlan plan;            // what the specialised kernel is for m_desc, under the TD_SPEC_* knobs as they stood at the upload
-	std::vector<float> m_skip, m_eM, m_eI, m_sM, m_sI, m_A;
-	std::vector<int8_t> m_seg_type;
-	std::vector<int32_t> m_finger_len;
-	bool spec_oob = false;      // the loaded kernel uses the clamp-free logsum
-	bool spec_window = false;   // the loaded kernel has the -start/-end window arithmetic compiled in
-	bool spec_oob_unsafe = false; // the clamp-free form failed its self-check once: never again in this context
-	float m_maxabs = 0.0f;      // largest |finite parameter|
-	int spec_block = 256, spec_waves_per_cu = 8;
-	// background compile and load-time probe (tagdust_hip.h, td_spec_wait / td_spec_probe)
-	int async_compile = 0;      // TD_ASYNC_COMPILE ["async_compile"]
-	int spec_probe = 1;         // ["spec_probe"]
-	int spec_state = 0;         // "spec_state" (1 / 2 are told apart when asked: is the job done?)
-	int batches_generic = 0;    // "spec_batches_generic"
-	int probe_us = 0;           // "spec_probe_us"
-	std::shared_ptr<SpecJob> job;                   // the compile this context waits for (nullptr: none)
-	int job_oob = 0, job_window = 0;                // ... and the variant it is
-	std::vector<std::shared_ptr<SpecJob>> retired;  // superseded jobs: never loaded, waited for when the context goes
-	std::string job_err;                            // the compiler's log of a failed background compile
-
-	// params
-	float threshold = 0.0f;
-	int32_t minlen = 16, dust = 100;
-
-	// -ref artifact filter
-	uint8_t* d_art_text = nullptr; int32_t* d_art_index = nullptr;
-	uint32_t* d_art_pk = nullptr; int32_t* d_art_seq = nullptr;   // the same text as 2-bit codes for TD_MODE_RNA_DUST (td_rnadust.hip)
-	int32_t art_n = 0, art_fe = 0, art_threads = 1;
-	unsigned long long* d_art_hits = nullptr;   // [art_n] reads per artifact sequence (td_artifact_hits_get)
-	int64_t win_first = 0, win_total = 0;   // td_set_batch_window
-	int32_t match_start = 0, match_len = 0;  // td_set_window (-start / -end); match_len = 0: whole reads
-	// batches: slot 0 is the resident batch of the synchronous calls; td_submit rotates over pipeline_depth slots
-	TdSlot slots[TD_MAX_PIPELINE];
-	int pipeline_depth = 3, next_slot = 0, last_slot = 0;
-	bool counted = false;   // td_ctx_create finished: this context counts among the live ones (the last one to go frees the stream cache)
-	int poison = 0;   // option "poison_workspace": fill the workspace with 0xFF bytes before every decode launch (tests)
-	// development / test knobs: read from the environment ONCE, when the context is created (never on the per-batch path), and
-	// settable afterwards through td_set_option under the names in brackets
-	int compact_egress = 1;    // TD_COMPACT_EGRESS ["compact_egress"]: keep bits + label runs instead of plain copies
-	int stable_input = 0;      // ["stable_input"]: the caller leaves a page-locked input buffer alone until td_wait (see tagdust_hip.h)
-	int rle_cap_forced = 0;    // TD_RLE_CAP ["rle_cap"]: entries of the label-run table (0: S + 2)
-	int length_classes = 1;    // TD_NO_LENGTH_CLASSES ["length_classes_enabled"]
-	int debug_wait = 0;        // TD_DEBUG_WAIT ["debug_wait"]
-	int debug_alloc = 0;       // TD_DEBUG_ALLOC
-	long wave_slots_forced = 0;   // TD_WAVE_SLOTS
-	int ws_candidates = 3;     // TD_WS_CANDIDATES
-	double lsum_limit = 1.0e6; // TD_SPEC_LSUM_LIMIT (tests: force the switch to the clamped logsum)
-	int selfcheck_fail = 0;    // TD_SPEC_SELFCHECK_FAIL (tests: exercise the fallback)
-	int64_t ticket_counter = 0;
-	hipStream_t s_up = nullptr, s_down = nullptr;   // copy streams of the pipelined calls
-	uint8_t* d_ws = nullptr;      size_t cap_ws = 0;  // workspace of the decode kernels on `stream` (they run one after the other)
-	// Pipelined batches alternate between two compute streams with a workspace each: a launch ends with its slowest wave
-	// (the waves of some XCDs take ~10 % longer for the same tiles), and the next batch's workgroups move in as the first
-	// one's retire instead of waiting for the last (option "overlap_decode", TD_OVERLAP; off when HBM cannot hold both).
-	hipStream_t stream2 = nullptr;
-	// With two decode kernels queued the machine never falls idle, so the small kernels around them (sort / pack of the next
-	// batch, finish of the last one) and the download's blit kernels would wait for a whole decode kernel: they run on a
-	// high-priority stream and take the compute units the retiring workgroups free before the next decode kernel does.
-	hipStream_t s_aux = nullptr, s_fin = nullptr;
-	uint8_t* d_ws2 = nullptr;     size_t cap_ws2 = 0;
-	int32_t* d_tile_next2 = nullptr;
-	int overlap = 1, submit_parity = 0;
-	bool half_slots = false;   // two workspaces of the full slot count do not fit: the pipelined launches use half the slots each
-	// position pruning tables of the specialised kernel (td_spec_prune_tables), for reads up to prune_lcap bases
-	float* d_prune = nullptr;     int prune_lcap = 0, prune_stride = 0;
-	bool prune_live = false;      // ... and they are real bounds (not the all-zero tables of reads beyond 8192 bases)
-	int32_t* d_tile_next = nullptr;   // tile counter of the specialised kernel's dynamic tile assignment
-	hipEvent_t ev_origin = nullptr;   // td_timeline_origin: the common origin of td_last_kernel_times
-};
-
-static int fail(td_ctx* c, const char* fmt, ...)
+int fail(td_ctx* c, const char* fmt, ...)
 {
 	char buf[512];
 	va_list ap;
@@ -361,46 +85,6 @@ static int fail(td_ctx* c, const char* fmt, ...)
 	va_end(ap);
 	if (c) c->err = buf; else g_create_error = buf;
 	return TD_FAIL;
-}
-
-#define HIPCHK(c, call)                                                                       \
-	do {                                                                                      \
-		hipError_t e_ = (call);                                                               \
-		if (e_ != hipSuccess) return fail((c), "%s failed: %s", #call, hipGetErrorString(e_)); \
-	} while (0)
-
-// everything queued on the compute streams has finished
-static hipError_t sync_compute(td_ctx* c)
-{
-	hipError_t e = hipStreamSynchronize(c->stream);
-	if (e == hipSuccess && c->stream2) e = hipStreamSynchronize(c->stream2);
-	if (e == hipSuccess && c->s_aux) e = hipStreamSynchronize(c->s_aux);
-	if (e == hipSuccess && c->s_fin) e = hipStreamSynchronize(c->s_fin);
-	return e;
-}
-
-template <typename T>
-static int ensure(td_ctx* c, T** p, size_t* cap, size_t bytes)
-{
-	if (*cap >= bytes && *p) return TD_OK;
-	if (*p) { HIPCHK(c, hipFree(*p)); *p = nullptr; *cap = 0; }
-	if (bytes == 0) bytes = 256;
-	HIPCHK(c, hipMalloc((void**)p, bytes));
-	*cap = bytes;
-	if (c && c->debug_alloc && bytes > (1u << 30)) fprintf(stderr, "tagdust_hip: hipMalloc(%zu) = %p\n", bytes, (void*)*p);
-	return TD_OK;
-}
-
-template <typename T>
-static int ensure_pinned(td_ctx* c, T** p, size_t* cap, size_t bytes)
-{
-	if (*cap >= bytes && *p) return TD_OK;
-	if (*p) { HIPCHK(c, hipHostFree(*p)); *p = nullptr; *cap = 0; }
-	if (bytes == 0) bytes = 256;
-	bytes += bytes / 4;   // head room: batches of a run differ a little in size
-	HIPCHK(c, hipHostMalloc((void**)p, bytes, hipHostMallocPortable));   // (several devices of one process may DMA from it)
-	*cap = bytes;
-	return TD_OK;
 }
 
 extern "C" const float* td_logsum_table(void)
@@ -441,7 +125,7 @@ extern "C" int td_ctx_create(int device, td_ctx** out)
 		return fail(nullptr, "td_ctx_create: device %d is %s; this library is built for gfx950 (MI355X) only", device, arch.c_str());
 	}
 	c->n_cu = prop.multiProcessorCount;
-	if (const char* e = getenv("TD_SPECIALIZE")) c->specialize = atoi(e) != 0;
+	if (const char* e = getenv("TD_SPECIALIZE")) c->spec.specialize = atoi(e) != 0;
 	if (const char* e = getenv("TD_OVERLAP")) c->overlap = atoi(e) != 0;
 	if (const char* e = getenv("TD_COMPACT_EGRESS")) c->compact_egress = atoi(e) != 0;
 	if (const char* e = getenv("TD_RLE_CAP")) { const int v = atoi(e); if (v >= 1 && v <= 127) c->rle_cap_forced = v; }
@@ -450,9 +134,9 @@ extern "C" int td_ctx_create(int device, td_ctx** out)
 	if (getenv("TD_DEBUG_ALLOC")) c->debug_alloc = 1;
 	if (const char* e = getenv("TD_WAVE_SLOTS")) { const long v = atol(e); if (v > 0) c->wave_slots_forced = v; }
 	if (const char* e = getenv("TD_WS_CANDIDATES")) c->ws_candidates = atoi(e);
-	if (const char* e = getenv("TD_SPEC_LSUM_LIMIT")) c->lsum_limit = atof(e);
-	if (getenv("TD_SPEC_SELFCHECK_FAIL")) c->selfcheck_fail = 1;
-	if (const char* e = getenv("TD_ASYNC_COMPILE")) c->async_compile = atoi(e) != 0;
+	if (const char* e = getenv("TD_SPEC_LSUM_LIMIT")) c->spec.lsum_limit = atof(e);
+	if (getenv("TD_SPEC_SELFCHECK_FAIL")) c->spec.selfcheck_fail = 1;
+	if (const char* e = getenv("TD_ASYNC_COMPILE")) c->spec.async_compile = atoi(e) != 0;
 	c->hbm_total = prop.totalGlobalMem;
 	init_logsum_host();
 	bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
@@ -472,33 +156,28 @@ extern "C" int td_ctx_create(int device, td_ctx** out)
 static void slot_release(TdSlot& s);
 static bool tickets_outstanding(const td_ctx* c);
 
+static void free_dev_model(DevModel& d)
+{
+	void* p[] = { d.d_hdr, d.d_cols, d.d_hinfo, d.d_pred_off, d.d_pred_idx };
+	for (void* q : p) if (q) (void)hipFree(q);
+	d = DevModel();
+}
+
 extern "C" void td_ctx_destroy(td_ctx* c)
 {
 	if (!c) return;
-	// the background compiles this context started (pending or superseded) finish first: as long as the compile at worst, and the
-	// code object is in the caches afterwards
-	if (c->job) { c->retired.push_back(c->job); c->job.reset(); }
-	for (auto& j : c->retired) j->wait();
-	c->retired.clear();
+	spec_retire_jobs(c, true);   // the background compiles this context started finish first
 	(void)hipSetDevice(c->device);
-	if (c->stream) (void)hipStreamSynchronize(c->stream);
-	if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-	if (c->s_aux) (void)hipStreamSynchronize(c->s_aux);
-	if (c->s_fin) (void)hipStreamSynchronize(c->s_fin);
-	if (c->s_up) (void)hipStreamSynchronize(c->s_up);
-	if (c->s_down) (void)hipStreamSynchronize(c->s_down);
-	void* bufs[] = { c->d_hdr, c->d_cols, c->d_hinfo, c->d_pred_off, c->d_pred_idx, c->d_logsum, c->d_counters,
-	                 c->d_ws, c->d_art_text, c->d_art_index, c->d_art_pk, c->d_art_seq, c->d_art_hits, c->d_prune, c->d_tile_next, c->d_ws2, c->d_tile_next2 };
+	hipStream_t streams[] = { c->stream, c->stream2, c->s_aux, c->s_fin, c->s_up, c->s_down };
+	for (hipStream_t st : streams) if (st) (void)hipStreamSynchronize(st);
+	free_dev_model(c->dev);
+	void* bufs[] = { c->d_logsum, c->d_counters, c->d_ws, c->d_art_text, c->d_art_index, c->d_art_pk, c->d_art_seq, c->d_art_hits,
+	                 c->spec.d_prune, c->d_tile_next, c->d_ws2, c->d_tile_next2 };
 	for (void* p : bufs) if (p) (void)hipFree(p);
 	for (int k = 0; k < TD_MAX_PIPELINE; k++) slot_release(c->slots[k]);
 	if (c->ev_origin) (void)hipEventDestroy(c->ev_origin);
-	if (c->s_up) (void)hipStreamDestroy(c->s_up);
-	if (c->s_down) (void)hipStreamDestroy(c->s_down);
-	if (c->spec_mod) (void)hipModuleUnload(c->spec_mod);
-	if (c->stream) (void)hipStreamDestroy(c->stream);
-	if (c->stream2) (void)hipStreamDestroy(c->stream2);
-	if (c->s_aux) (void)hipStreamDestroy(c->s_aux);
-	if (c->s_fin) (void)hipStreamDestroy(c->s_fin);
+	(void)spec_unload(c);
+	for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
 	bool last = false;
 	if (c->counted) { std::lock_guard<std::mutex> lk(g_live_mu); last = --g_live_ctx == 0; }
 	delete c;
@@ -510,314 +189,6 @@ extern "C" void td_ctx_destroy(td_ctx* c)
 // ---------------------------------------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------------------------------------
-static int ensure_prune_tables(td_ctx* c, int lmax);
-static double wall_ms();
-static inline int64_t align256(int64_t v);
-static void make_layout(TdWsLayout& L, int S, int H, int C, int lmax, int max_ncol);
-struct OutLayout { int64_t soa_stride, keep, labels, total; };
-static OutLayout out_layout(int64_t n_tiles, int lmax, int nw1);
-
-static const char* probe_field_name(int f)
-{
-	static const char* res[] = { "f_score", "b_score", "r_score", "bar_prob", "mapq", "read_type", "barcode", "fingerprint" };
-	if (f >= 0 && f < 8) return res[f];
-	return f == TD_PROBE_FIELD_LABELS ? "labels" : f == TD_PROBE_FIELD_SEQ ? "sequence" : f == TD_PROBE_FIELD_COUNTERS ? "counters" : "?";
-}
-
-// The whole-kernel probe (tagdust_hip.h, td_spec_probe): the loaded specialised kernel (c->spec_fn) and the generic kernel decode
-// the probe reads under the fixed probe parameters, on scratch buffers of their own; a device kernel compares what a caller could
-// see.  Nothing of the context's batches, slots or counters is touched.  The compute streams are idle when this runs.
-static int probe_spec_kernel(td_ctx* c, int window, ProbeVerdict& v)
-{
-	std::vector<int64_t> offs(TD_PROBE_READS + 1);
-	const int64_t n_bases = td_spec_probe(&c->m_desc, nullptr, 0, offs.data());
-	if (n_bases <= 0) return fail(c, "td_model_upload: the probe reads could not be made from this model");
-	std::vector<uint8_t> codes((size_t)n_bases);
-	(void)td_spec_probe(&c->m_desc, codes.data(), n_bases, nullptr);
-	const int n = TD_PROBE_READS, n_tiles = TD_PROBE_READS / TD_WAVE;
-	int lmax = 1;
-	for (int i = 0; i < n; i++) if (offs[(size_t)i + 1] - offs[(size_t)i] > lmax) lmax = (int)(offs[(size_t)i + 1] - offs[(size_t)i]);
-	const int nw2 = (lmax + 15) / 16, nw1 = (lmax + 31) / 32;
-	if (ensure_prune_tables(c, lmax) != TD_OK) return TD_FAIL;
-	TdWsLayout glay{};
-	make_layout(glay, c->hdr.S, c->hdr.H, c->hdr.C, lmax, c->hdr.max_ncol);
-	TdSpecLayout slay{};
-	td_spec_layout(slay, c->plan, lmax);
-	const int gwpb = td_kernel_block_threads() / TD_WAVE, swpb = c->plan.k.block / TD_WAVE;
-	const int gslots = (n_tiles + gwpb - 1) / gwpb * gwpb, sslots = (n_tiles + swpb - 1) / swpb * swpb;
-	const OutLayout ol = out_layout(n_tiles, lmax, nw1);
-	// one scratch allocation, carved up
-	int64_t o = 0;
-	auto carve = [&](int64_t bytes) { const int64_t at = o; o = align256(o + bytes); return at; };
-	const int64_t o_raw = carve(n_bases), o_offs = carve((int64_t)(n + 1) * 8), o_packed = carve((int64_t)n_tiles * (nw2 + nw1) * TD_WAVE * 4),
-	              o_lens = carve((int64_t)n * 4), o_outa = carve(ol.total), o_outb = carve(ol.total),
-	              o_cnt = carve((int64_t)2 * TD_COUNTER_WORDS * 8), o_cmp = carve(256), o_tile = carve(256);
-	const int64_t small_bytes = o;
-	const int64_t o_wsa = carve((int64_t)gslots * glay.slot_bytes), o_wsb = carve((int64_t)sslots * slay.slot_bytes);
-	uint8_t* d = nullptr;
-	HIPCHK(c, hipMalloc((void**)&d, (size_t)o));
-	struct Free { uint8_t* p; ~Free() { (void)hipFree(p); } } free_{ d };
-	hipStream_t st = c->stream;
-	HIPCHK(c, hipMemsetAsync(d, 0, (size_t)small_bytes, st));
-	HIPCHK(c, hipMemsetAsync(d + o_cmp, 0xFF, 256, st));   // "this tile agrees" = -1
-	HIPCHK(c, hipMemsetAsync(d + o_cmp, 0, 4, st));
-	HIPCHK(c, hipMemsetAsync(d + o_wsa, 0xFF, (size_t)(o - o_wsa), st));   // both workspaces poisoned: a read-before-write computes on NaNs
-	HIPCHK(c, hipMemcpyAsync(d + o_raw, codes.data(), (size_t)n_bases, hipMemcpyHostToDevice, st));
-	HIPCHK(c, hipMemcpyAsync(d + o_offs, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-	TdStageBatch sb{};
-	sb.raw = d + o_raw; sb.offs = (const int64_t*)(d + o_offs); sb.n_reads = n; sb.is_ascii = 0;
-	sb.n_tiles = n_tiles; sb.lmax = lmax; sb.nw2 = nw2; sb.nw1 = nw1;
-	sb.read_at = nullptr;   // the reads stay in the generator's order: ragged inside every tile
-	sb.packed = (uint32_t*)(d + o_packed); sb.lens = (int32_t*)(d + o_lens);
-	HIPCHK(c, td_stage_pack(sb, st));
-	unsigned long long* cnt_a = (unsigned long long*)(d + o_cnt);
-	unsigned long long* cnt_b = cnt_a + TD_COUNTER_WORDS;
-	const int64_t sst = ol.soa_stride / 4;
-	TdKernelArgs ka{};
-	ka.hdr = c->d_hdr; ka.cols = c->d_cols; ka.hinfo = c->d_hinfo; ka.pred_off = c->d_pred_off; ka.pred_idx = c->d_pred_idx; ka.logsum = c->d_logsum;
-	ka.packed = sb.packed; ka.lens = sb.lens;
-	ka.n_tiles = n_tiles; ka.n_slots = gslots; ka.lmax = lmax; ka.nw2 = nw2; ka.nw1 = nw1;
-	ka.mode = TD_MODE_GET_LABEL; ka.threshold = TD_PROBE_THRESHOLD; ka.minlen = TD_PROBE_MINLEN; ka.dust = TD_PROBE_DUST; ka.want_labels = 1;
-	if (window) { ka.win_start = TD_PROBE_WIN_START; ka.win_len = TD_PROBE_WIN_END - TD_PROBE_WIN_START; }
-	{
-		float* soa = (float*)(d + o_outa);
-		ka.out_f = soa; ka.out_b = soa + sst; ka.out_r = soa + 2 * sst; ka.out_bar = soa + 3 * sst; ka.out_q = soa + 4 * sst;
-		ka.out_type = (int32_t*)(soa + 5 * sst); ka.out_barcode = (int32_t*)(soa + 6 * sst); ka.out_finger = (int32_t*)(soa + 7 * sst);
-		ka.out_keep = (uint32_t*)(d + o_outa + ol.keep); ka.out_labels = (int8_t*)(d + o_outa + ol.labels);
-	}
-	ka.counters = cnt_a;
-	ka.ws = d + o_wsa; ka.lay = glay;
-	HIPCHK(c, td_launch_decode(&ka, st));
-	TdSpecArgs sa{};
-	sa.logsum = c->d_logsum; sa.packed = sb.packed; sa.lens = sb.lens;
-	sa.n_tiles = n_tiles; sa.n_slots = sslots; sa.lmax = lmax; sa.nw2 = nw2; sa.nw1 = nw1;
-	sa.mode = ka.mode; sa.threshold = ka.threshold; sa.minlen = ka.minlen; sa.dust = ka.dust;
-	sa.win_start = ka.win_start; sa.win_len = ka.win_len;
-	{
-		float* soa = (float*)(d + o_outb);
-		sa.out_f = soa; sa.out_b = soa + sst; sa.out_r = soa + 2 * sst; sa.out_bar = soa + 3 * sst; sa.out_q = soa + 4 * sst;
-		sa.out_type = (int32_t*)(soa + 5 * sst); sa.out_barcode = (int32_t*)(soa + 6 * sst); sa.out_finger = (int32_t*)(soa + 7 * sst);
-		sa.out_keep = (uint32_t*)(d + o_outb + ol.keep); sa.out_labels = (int8_t*)(d + o_outb + ol.labels);
-	}
-	sa.counters = cnt_b;
-	sa.ws = d + o_wsb; sa.lay = slay; sa.lay_big = slay;
-	sa.n_big = 0; sa.lmax_big = lmax; sa.out_lmax = lmax;
-	sa.prune = c->d_prune; sa.prune_stride = c->prune_stride;
-	sa.tile_next = (int32_t*)(d + o_tile);
-	{
-		size_t sz = sizeof sa;
-		void* cfg[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, &sa, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END };
-		HIPCHK(c, hipModuleLaunchKernel(c->spec_fn, (unsigned)(sslots / swpb), 1, 1, (unsigned)c->plan.k.block, 1, 1, 0, st, nullptr, cfg));
-	}
-	TdProbeCmp pc{};
-	pc.lens = sb.lens; pc.n_tiles = n_tiles; pc.lmax = lmax; pc.nw1 = nw1; pc.n_counters = TD_NUM_COUNTERS;
-	pc.soa_a = d + o_outa; pc.soa_b = d + o_outb; pc.soa_stride = ol.soa_stride;
-	pc.keep_a = ka.out_keep; pc.keep_b = sa.out_keep; pc.labels_a = ka.out_labels; pc.labels_b = sa.out_labels;
-	pc.counters_a = cnt_a; pc.counters_b = cnt_b;
-	pc.out = (int32_t*)(d + o_cmp);
-	HIPCHK(c, td_probe_compare(pc, st));
-	int32_t out[1 + 2 * (TD_PROBE_READS / TD_WAVE + 1)];
-	HIPCHK(c, hipMemcpyAsync(out, d + o_cmp, sizeof out, hipMemcpyDeviceToHost, st));
-	HIPCHK(c, hipStreamSynchronize(st));
-	// the bound tables were laid out for the probe's reads: the first batch lays them out for its own (as without a probe)
-	c->prune_lcap = 0; c->prune_live = false;
-	v = ProbeVerdict();
-	v.mismatches = out[0];
-	for (int w = 0; w <= n_tiles && v.read < 0; w++) if (out[1 + 2 * w] >= 0) { v.read = out[1 + 2 * w]; v.field = out[2 + 2 * w]; }
-	return TD_OK;
-}
-
-static int load_spec_kernel(td_ctx* c, int lsum_oob, int window = -1);
-static int start_spec_job(td_ctx* c, int lsum_oob, int window);
-
-// A compiled code object becomes the context's decode kernel: module load, logsum self-check, probe, spec_ready -- in that order.
-// The compute streams are idle.  background: a self-check that demands the clamped form sends that compile to the background
-// again (a hand-over) instead of compiling it here.  A kernel the probe rejects leaves the context on the generic kernel: TD_OK.
-static int install_spec_kernel(td_ctx* c, const std::vector<char>& code, uint64_t key, int lsum_oob, int window, bool background)
-{
-	if (c->spec_mod) { HIPCHK(c, hipModuleUnload(c->spec_mod)); c->spec_mod = nullptr; }
-	c->spec_fn = nullptr; c->spec_ready = false;
-	HIPCHK(c, hipModuleLoadData(&c->spec_mod, code.data()));
-	HIPCHK(c, hipModuleGetFunction(&c->spec_fn, c->spec_mod, "td_spec_kernel"));
-	// lsum() as compiled against the reference's formula on the operand pairs that matter (either or both operands -inf,
-	// gaps just below / at / above the 15.7 cut, huge gaps, equal operands).  The clamp-free form depends on hardware and
-	// toolchain behaviour nobody documents; if it ever stops holding, the clamped form is loaded instead -- loudly.
-	{
-		static const float g[] = { 0.0f, 0.0005f, 0.001f, 1.0f, 15.699f, 15.6999f, 15.7f, 15.7001f, 16.639f, 16.64f, 16.7f, 100.0f, 1.0e5f, 1.0e6f };
-		std::vector<float> pairs;
-		for (float base : { 0.0f, -3.25f, -700.0f }) {
-			for (float d : g) { pairs.push_back(base); pairs.push_back(base - d); pairs.push_back(base - d); pairs.push_back(base); }
-			pairs.push_back(base); pairs.push_back(-INFINITY); pairs.push_back(-INFINITY); pairs.push_back(base);
-		}
-		pairs.push_back(-INFINITY); pairs.push_back(-INFINITY);
-		const int n_pairs = (int)(pairs.size() / 2);
-		hipFunction_t chk = nullptr;
-		HIPCHK(c, hipModuleGetFunction(&chk, c->spec_mod, "td_spec_selfcheck"));
-		float* d_pairs = nullptr; int* d_bad = nullptr; int bad = -1;
-		HIPCHK(c, hipMalloc((void**)&d_pairs, pairs.size() * 4));
-		HIPCHK(c, hipMalloc((void**)&d_bad, 4));
-		HIPCHK(c, hipMemcpy(d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
-		HIPCHK(c, hipMemset(d_bad, 0, 4));
-		struct { const float* logsum; const float* pairs; int n; int pad; int* bad; } a = { c->d_logsum, d_pairs, n_pairs, 0, d_bad };
-		size_t sz = sizeof a;
-		void* cfg[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END };
-		const int block = c->plan.k.block;
-		hipError_t e = n_pairs <= block ? hipModuleLaunchKernel(chk, 1, 1, 1, (unsigned)block, 1, 1, 0, c->stream, nullptr, cfg) : hipErrorInvalidValue;
-		if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-		if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost);
-		(void)hipFree(d_pairs); (void)hipFree(d_bad);
-		if (e != hipSuccess) return fail(c, "td_model_upload: logsum self-check did not run: %s", hipGetErrorString(e));
-		if (c->selfcheck_fail && lsum_oob) bad = 1;   // tests: exercise the fallback
-		if (bad != 0) {
-			if (!lsum_oob) return fail(c, "td_model_upload: the compiled logsum differs from the reference formula on %d of %d operand pairs", bad, n_pairs);
-			fprintf(stderr, "tagdust_hip: clamp-free logsum failed its self-check on this device / toolchain (%d of %d pairs); using the clamped form\n", bad, n_pairs);
-			c->spec_oob_unsafe = true;
-			if (background) {
-				HIPCHK(c, hipModuleUnload(c->spec_mod));
-				c->spec_mod = nullptr; c->spec_fn = nullptr;
-				return start_spec_job(c, 0, window);
-			}
-			return load_spec_kernel(c, 0, window);
-		}
-	}
-	// the whole kernel against the generic one, once per (code object, device) and process
-	if (c->spec_probe) {
-		ProbeVerdict v;
-		bool known = false;
-		{
-			std::lock_guard<std::mutex> lk(g_probe_mu);
-			auto it = g_probe_verdicts.find({ key, c->device });
-			if (it != g_probe_verdicts.end()) { v = it->second; known = true; }
-		}
-		if (!known) {
-			const double t0 = wall_ms();
-			if (probe_spec_kernel(c, window, v) != TD_OK) return TD_FAIL;
-			c->probe_us = (int)((wall_ms() - t0) * 1000.0);
-			std::lock_guard<std::mutex> lk(g_probe_mu);
-			g_probe_verdicts[{ key, c->device }] = v;
-		}
-		if (v.mismatches != 0) {
-			fprintf(stderr, "tagdust_hip: PROBE REJECTED the specialised kernel %016llx on device %d: %d of %d probe reads differ from the generic "
-			        "kernel, first at read %d, field %s%s.  This context decodes with the generic kernel: correct, about ten times slower.\n",
-			        (unsigned long long)key, c->device, v.mismatches, TD_PROBE_READS, v.read, probe_field_name(v.field), known ? " (verdict of an earlier load)" : "");
-			HIPCHK(c, hipModuleUnload(c->spec_mod));
-			c->spec_mod = nullptr; c->spec_fn = nullptr;
-			c->spec_state = 4;
-			return TD_OK;
-		}
-	}
-	c->spec_ready = true;
-	c->spec_window = window != 0;
-	c->spec_oob = lsum_oob != 0;
-	c->spec_state = 3;
-	return TD_OK;
-}
-
-// Compile (or fetch from the cache) and load the model-specialised kernel, here and now.  lsum_oob selects the clamp-free logsum.
-static int load_spec_kernel(td_ctx* c, int lsum_oob, int window)
-{
-	if (window < 0) window = c->match_len > 0;   // a context with a -start/-end window gets the kernel that can apply it
-	if (c->spec_mod) { HIPCHK(c, hipModuleUnload(c->spec_mod)); c->spec_mod = nullptr; }
-	c->spec_fn = nullptr; c->spec_ready = false;
-	std::vector<char> code;
-	std::string log;
-	uint64_t key = 0;
-	if (td_spec_compile(&c->m_desc, c->plan, lsum_oob, window, code, log, &key) != TD_OK) {
-		c->spec_state = 5;
-		return fail(c, "td_model_upload: specialised kernel did not compile: %.400s", log.c_str());
-	}
-	return install_spec_kernel(c, code, key, lsum_oob, window, false);
-}
-
-// The same compile on a host thread (option "async_compile"): the context goes on with the generic kernel until
-// spec_handover finds the job done.  Contexts that ask for the same code object share one job.
-static int start_spec_job(td_ctx* c, int lsum_oob, int window)
-{
-	std::vector<char> none;
-	std::string log;
-	uint64_t key = 0;
-	(void)td_spec_compile(&c->m_desc, c->plan, lsum_oob, window, none, log, &key, true);
-	static std::once_flag at_exit_once;
-	std::call_once(at_exit_once, [] { (void)atexit(wait_for_all_spec_jobs); });
-	std::shared_ptr<SpecJob> job;
-	{
-		std::lock_guard<std::mutex> lk(g_jobs_mu);
-		for (auto it = g_jobs.begin(); it != g_jobs.end();) { if (it->second.expired()) it = g_jobs.erase(it); else ++it; }
-		auto it = g_jobs.find(key);
-		if (it != g_jobs.end()) job = it->second.lock();
-		if (!job) {
-			job = std::make_shared<SpecJob>();
-			job->key = key; job->model.assign(&c->m_desc); job->plan = c->plan; job->lsum_oob = lsum_oob; job->window = window;
-			SpecJob* raw = job.get();   // (the job outlives its thread: its destructor joins)
-			job->th = std::thread([raw] { raw->run(); });
-			g_jobs[key] = job;
-		}
-	}
-	c->job = job; c->job_oob = lsum_oob; c->job_window = window;
-	c->spec_state = 1;
-	return TD_OK;
-}
-
-// Hand-over of a finished background compile, polled where a batch is staged (block: td_spec_wait).  Everything queued on the
-// compute streams finishes first -- the step the mid-run reloads take too; outstanding tickets stay valid -- then the kernel is
-// installed as after a synchronous compile.
-static int spec_handover(td_ctx* c, bool block)
-{
-	if (!c->job) {
-		if (c->spec_state == 5 && !c->job_err.empty()) return fail(c, "%s", c->job_err.c_str());
-		return TD_OK;
-	}
-	if (!block && !c->job->finished()) return TD_OK;
-	c->job->wait();
-	std::shared_ptr<SpecJob> job = c->job;
-	c->job.reset();
-	if (job->rc != TD_OK) {
-		c->spec_state = 5;
-		char buf[512];
-		snprintf(buf, sizeof buf, "td_model_upload: specialised kernel did not compile (background compile): %.400s", job->log.c_str());
-		c->job_err = buf;
-		return fail(c, "%s", buf);
-	}
-	c->spec_state = 2;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
-	return install_spec_kernel(c, job->code, job->key, c->job_oob, c->job_window, true);
-}
-
-extern "C" int td_spec_wait(td_ctx* c)
-{
-	if (!c) return TD_FAIL;
-	while (c->job) if (spec_handover(c, true) != TD_OK) return TD_FAIL;   // (a self-check fallback starts a second job)
-	return spec_handover(c, false);
-}
-
-// The clamp-free logsum of the specialised kernel turns |a - b| * 4000 into an LDS byte address (a saturating conversion; the
-// shift form it replaced wrapped at |a - b| = 2^30 / 1000, and the limit still keeps that margin).  Every finite DP value is
-// a sum of at most 2 parameters per position, and the posterior terms add two such values, so 4 * max|parameter| * (L + 2)
-// bounds every finite difference; 6 * keeps a margin.
-static bool spec_lsum_range_ok(const td_ctx* c, int lmax)
-{
-	const double limit = c->lsum_limit;   // (1e6; tests lower it to force the switch to the clamped form)
-	return 6.0 * (double)c->m_maxabs * ((double)lmax + 2.0) < limit;
-}
-
-// The model as the generic kernel reads it from HBM: header, columns, per-HMM info, label predecessor lists.
-struct DevModel {
-	TdModelHeader h{};
-	TdModelHeader* d_hdr = nullptr;
-	TdCol* d_cols = nullptr;
-	uint32_t* d_hinfo = nullptr;
-	int32_t* d_pred_off = nullptr;
-	int32_t* d_pred_idx = nullptr;
-};
-
-static void free_dev_model(DevModel& d)
-{
-	void* p[] = { d.d_hdr, d.d_cols, d.d_hinfo, d.d_pred_off, d.d_pred_idx };
-	for (void* q : p) if (q) (void)hipFree(q);
-	d = DevModel();
-}
-
 // validate a description and put its tables on the device (synchronous copies)
 static int build_dev_model(td_ctx* c, const td_model_desc* m, DevModel& out)
 {
@@ -902,66 +273,18 @@ extern "C" int td_model_upload(td_ctx* c, const td_model_desc* m)
 	HIPCHK(c, hipSetDevice(c->device));
 	// a rejected upload (tickets in flight, an invalid description) leaves the context as it was
 	if (tickets_outstanding(c)) return fail(c, "td_model_upload: td_submit tickets are outstanding (td_wait them first)");
-	// a pending background compile is superseded: its result may land in the caches, never in this context
-	if (c->job) { c->retired.push_back(c->job); c->job.reset(); }
-	for (size_t k = 0; k < c->retired.size();) { if (c->retired[k]->finished()) c->retired.erase(c->retired.begin() + (long)k); else k++; }
-	c->job_err.clear();
+	spec_retire_jobs(c, false);   // a pending background compile is superseded: its result may land in the caches, never in this context
 	DevModel dm;
 	if (build_dev_model(c, m, dm) != TD_OK) return TD_FAIL;
-	const TdModelHeader h = dm.h;
 	// from here on the context holds no usable model / batch until every step below has succeeded
 	c->have_model = false;
 	for (int k = 0; k < TD_MAX_PIPELINE; k++) { c->slots[k].staged = false; c->slots[k].ran = false; }   // batches are staged per model
 	HIPCHK(c, sync_compute(c));
-	void* old[] = { c->d_hdr, c->d_cols, c->d_hinfo, c->d_pred_off, c->d_pred_idx };
-	for (void* p : old) if (p) (void)hipFree(p);
-	c->d_hdr = dm.d_hdr; c->d_cols = dm.d_cols; c->d_hinfo = dm.d_hinfo; c->d_pred_off = dm.d_pred_off; c->d_pred_idx = dm.d_pred_idx;
-	c->hdr = h;
-	c->label.assign(m->label, m->label + m->H);
-	c->m_n_hmm.assign(m->n_hmm, m->n_hmm + m->S);
-	c->m_n_col.assign(m->n_col, m->n_col + m->S);
-	c->m_trans.assign(m->trans, m->trans + (size_t)m->C * 9);
-
-	// model-specialised kernel: compile now (seconds); a failure is an error, never a silent fallback
-	if (c->spec_mod) { HIPCHK(c, hipModuleUnload(c->spec_mod)); c->spec_mod = nullptr; }
-	c->spec_fn = nullptr; c->spec_ready = false;
-	c->prune_lcap = 0; c->prune_live = false;   // the pruning tables belong to the model
-	c->half_slots = false;                      // ... and so does the workspace geometry
-	c->spec_state = 0; c->batches_generic = 0; c->probe_us = 0;
-	if (c->specialize) {
-		// keep what a later recompile needs
-		c->m_skip.assign(m->skip, m->skip + m->S);
-		c->m_seg_type.assign(m->seg_type, m->seg_type + m->S);
-		c->m_finger_len.assign(m->finger_len, m->finger_len + m->S);
-		c->m_eM.assign(m->eM, m->eM + (size_t)m->C * 5); c->m_eI.assign(m->eI, m->eI + (size_t)m->C * 5);
-		c->m_sM.assign(m->sM, m->sM + m->C); c->m_sI.assign(m->sI, m->sI + m->C);
-		c->m_A.assign(m->A, m->A + (size_t)m->H * m->H);
-		c->m_desc = *m;
-		c->m_desc.n_hmm = c->m_n_hmm.data(); c->m_desc.n_col = c->m_n_col.data(); c->m_desc.skip = c->m_skip.data();
-		c->m_desc.seg_type = c->m_seg_type.data(); c->m_desc.finger_len = c->m_finger_len.data();
-		c->m_desc.trans = c->m_trans.data(); c->m_desc.eM = c->m_eM.data(); c->m_desc.eI = c->m_eI.data();
-		c->m_desc.sM = c->m_sM.data(); c->m_desc.sI = c->m_sI.data(); c->m_desc.label = c->label.data(); c->m_desc.A = c->m_A.data();
-		float mx = 0.0f;
-		auto scan = [&](const float* v, size_t n) { for (size_t i = 0; i < n; i++) if (std::isfinite(v[i]) && fabsf(v[i]) > mx) mx = fabsf(v[i]); };
-		scan(m->trans, (size_t)m->C * 9); scan(m->eM, (size_t)m->C * 5); scan(m->eI, (size_t)m->C * 5);
-		scan(m->sM, m->C); scan(m->sI, m->C); scan(m->skip, m->S); scan(m->bg, 5);
-		c->m_maxabs = mx;
-		c->plan = td_spec_plan(&c->m_desc, td_spec_knobs());
-		// ... or, with "async_compile", on a host thread: the generic kernel decodes until the hand-over (spec_handover)
-		const int oob = c->spec_oob_unsafe ? 0 : c->plan.k.lsum_oob;
-		if ((c->async_compile ? start_spec_job(c, oob, c->match_len > 0) : load_spec_kernel(c, oob)) != TD_OK) return TD_FAIL;
-		c->spec_block = c->plan.k.block;
-		// resident waves per CU: two LDS tables fit a CU; a 1024-thread workgroup fills it alone
-		{
-			const int wpb = c->spec_block / TD_WAVE;
-			int blocks_per_cu = 32 / wpb;             // 32 waves per CU
-			if (blocks_per_cu > 2) blocks_per_cu = 2; // two logsum tables (<= 66.5 KB each) per 160 KB of LDS
-			if (blocks_per_cu < 1) blocks_per_cu = 1;
-			c->spec_waves_per_cu = blocks_per_cu * wpb;
-		}
-		const int by_regs = 4 * c->plan.k.min_waves;
-		if (c->spec_waves_per_cu > by_regs) c->spec_waves_per_cu = by_regs;
-	}
+	free_dev_model(c->dev);
+	c->dev = dm;
+	c->model.assign(m);
+	c->half_slots = false;   // the workspace geometry belongs to the model
+	if (spec_model_uploaded(c) != TD_OK) return TD_FAIL;
 	c->have_model = true;
 	return TD_OK;
 }
@@ -970,12 +293,12 @@ extern "C" int td_set_option(td_ctx* c, const char* name, int32_t value)
 {
 	if (!c || !name) return TD_FAIL;
 	if (!strcmp(name, "specialize")) {
-		c->specialize = value != 0; // takes effect at the next td_model_upload
+		c->spec.specialize = value != 0; // takes effect at the next td_model_upload
 		return TD_OK;
 	}
 	if (!strcmp(name, "poison_workspace")) { c->poison = value != 0; return TD_OK; }
-	if (!strcmp(name, "async_compile")) { c->async_compile = value != 0; return TD_OK; }   // ... the next td_model_upload
-	if (!strcmp(name, "spec_probe")) { c->spec_probe = value != 0; return TD_OK; }         // ... the next load of a specialised kernel
+	if (!strcmp(name, "async_compile")) { c->spec.async_compile = value != 0; return TD_OK; }   // ... the next td_model_upload
+	if (!strcmp(name, "spec_probe")) { c->spec.probe = value != 0; return TD_OK; }         // ... the next load of a specialised kernel
 	if (!strcmp(name, "compact_egress")) { c->compact_egress = value != 0; return TD_OK; }          // takes effect with the next download / td_submit
 	if (!strcmp(name, "stable_input")) {
 		if (tickets_outstanding(c)) return fail(c, "td_set_option: stable_input cannot change while tickets are outstanding");
@@ -984,7 +307,7 @@ extern "C" int td_set_option(td_ctx* c, const char* name, int32_t value)
 	}
 	if (!strcmp(name, "length_classes_enabled")) { c->length_classes = value != 0; return TD_OK; }  // ... the next upload
 	if (!strcmp(name, "debug_wait")) { c->debug_wait = value != 0; return TD_OK; }
-	if (!strcmp(name, "spec_lsum_limit")) { c->lsum_limit = value > 0 ? (double)value : 1.0e6; return TD_OK; }   // tests; next upload
+	if (!strcmp(name, "spec_lsum_limit")) { c->spec.lsum_limit = value > 0 ? (double)value : 1.0e6; return TD_OK; }   // tests; next upload
 	if (!strcmp(name, "rle_cap")) {
 		if (value < 0 || value > 127) return fail(c, "td_set_option: rle_cap must be 0 (default) .. 127");
 		c->rle_cap_forced = value;
@@ -1012,15 +335,15 @@ extern "C" int td_set_option(td_ctx* c, const char* name, int32_t value)
 extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 {
 	if (!c || !name || !value) return TD_FAIL;
-	if (!strcmp(name, "specialize")) { *value = c->specialize; return TD_OK; }
-	if (!strcmp(name, "spec_lsum_clamped")) { *value = c->spec_ready && !c->spec_oob; return TD_OK; }
+	if (!strcmp(name, "specialize")) { *value = c->spec.specialize; return TD_OK; }
+	if (!strcmp(name, "spec_lsum_clamped")) { *value = c->spec.ready && !c->spec.oob; return TD_OK; }
 	if (!strcmp(name, "pipeline_depth")) { *value = c->pipeline_depth; return TD_OK; }
-	if (!strcmp(name, "async_compile")) { *value = c->async_compile; return TD_OK; }
-	if (!strcmp(name, "spec_probe")) { *value = c->spec_probe; return TD_OK; }
-	if (!strcmp(name, "spec_state")) { *value = c->job ? (c->job->finished() ? 2 : 1) : c->spec_state; return TD_OK; }
-	if (!strcmp(name, "spec_batches_generic")) { *value = c->batches_generic; return TD_OK; }
+	if (!strcmp(name, "async_compile")) { *value = c->spec.async_compile; return TD_OK; }
+	if (!strcmp(name, "spec_probe")) { *value = c->spec.probe; return TD_OK; }
+	if (!strcmp(name, "spec_state")) { *value = spec_state_now(c); return TD_OK; }
+	if (!strcmp(name, "spec_batches_generic")) { *value = c->spec.batches_generic; return TD_OK; }
 	if (!strcmp(name, "spec_compiles_started")) { *value = td_spec_compiles_started(); return TD_OK; }
-	if (!strcmp(name, "spec_probe_us")) { *value = c->probe_us; return TD_OK; }
+	if (!strcmp(name, "spec_probe_us")) { *value = c->spec.probe_us; return TD_OK; }
 	if (!strcmp(name, "host_threads")) { *value = c->host_threads; return TD_OK; }
 	if (!strcmp(name, "artifacts_active")) { *value = c->art_n > 0; return TD_OK; }
 	if (!strcmp(name, "dust")) { *value = c->dust; return TD_OK; }   // param->dust as td_set_params set it
@@ -1036,13 +359,13 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	// which fast paths the model / the last batch actually got (read-only)
 	if (!strcmp(name, "prune_active")) {
 		// the loaded specialised kernel prunes by position AND the bound tables of the last batch's geometry are live
-		*value = c->spec_ready && c->prune_live && (c->plan.prune_segs > 0 || c->plan.sfx_first < c->plan.S);
+		*value = c->spec.ready && c->spec.prune_live && (c->spec.plan.prune_segs > 0 || c->spec.plan.sfx_first < c->spec.plan.S);
 		return TD_OK;
 	}
 	if (!strcmp(name, "overlap_active")) {
 		// pipelined batches alternate between two compute streams / workspaces (off: option, generic kernel, depth 1, or HBM
 		// could not hold the second workspace)
-		*value = c->overlap && c->pipeline_depth > 1 && c->spec_ready && c->stream2 != nullptr && c->d_ws2 != nullptr;
+		*value = c->overlap && c->pipeline_depth > 1 && c->spec.ready && c->stream2 != nullptr && c->d_ws2 != nullptr;
 		return TD_OK;
 	}
 	return fail(c, "td_get_option: unknown option %s", name);
@@ -1126,9 +449,9 @@ extern "C" int td_set_params(td_ctx* c, float threshold, int32_t minlen, int32_t
 // (td_batch_upload / td_run / td_batch_download) work on slot 0; td_submit / td_wait rotate over `pipeline_depth` slots
 // with the copies on their own streams, so that the upload of batch k+1 and the download of batch k-1 overlap the decode
 // kernel of batch k.  One HBM workspace serves all slots (decode kernels are serialised on the compute stream).
-static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
-static void make_layout(TdWsLayout& L, int S, int H, int C, int lmax, int max_ncol)
+void make_layout(TdWsLayout& L, int S, int H, int C, int lmax, int max_ncol)
 {
 	int64_t o = 0;
 	L.codes = o; o = align256(o + (int64_t)(lmax + 2) * TD_WAVE);
@@ -1144,9 +467,7 @@ static void make_layout(TdWsLayout& L, int S, int H, int C, int lmax, int max_nc
 	L.slot_bytes = o;
 }
 
-// output block of the decode kernels: eight SoA arrays over n_tiles*64 reads (f, b, r, bar, q, type, barcode, finger: equal
-// strides), then keep words, then labels -- all in device order
-static OutLayout out_layout(int64_t n_tiles, int lmax, int nw1)
+OutLayout out_layout(int64_t n_tiles, int lmax, int nw1)
 {
 	OutLayout o;
 	o.soa_stride = n_tiles * TD_WAVE * 4;      // a multiple of 256
@@ -1197,44 +518,21 @@ static void slot_release(TdSlot& s)
 	s = TdSlot();
 }
 
-// bound tables of the position pruning, for reads up to lcap >= lmax bases (kernels in flight read the old ones)
-static int ensure_prune_tables(td_ctx* c, int lmax)
-{
-	if (lmax <= c->prune_lcap && c->d_prune) return TD_OK;
-	HIPCHK(c, sync_compute(c));
-	const int lcap = (lmax + 2 + 255) / 256 * 256, stride = lcap + 24;   // (the scans request TDS_SCAN_B = 16 entries at a time: spare entries behind lcap)
-	std::vector<float> tab;
-	// (the bound recurrences cost columns x positions on the host: for reads beyond 8192 bases the tables stay zero, which
-	// the kernel reads as "nothing can be pruned" -- every position violates the zero bound -- and decodes densely)
-	c->prune_live = (c->plan.prune_segs > 0 || c->plan.sfx_first < c->plan.S) && lcap <= 8192;
-	if (c->prune_live) td_spec_prune_tables(&c->m_desc, c->plan, lcap, stride, tab);
-	else tab.assign((size_t)TD_PRUNE_TABLES * stride, 0.0f);
-	if (c->d_prune) { HIPCHK(c, hipFree(c->d_prune)); c->d_prune = nullptr; }
-	HIPCHK(c, hipMalloc((void**)&c->d_prune, tab.size() * sizeof(float)));
-	HIPCHK(c, hipMemcpy(c->d_prune, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-	c->prune_lcap = lcap; c->prune_stride = stride;
-	return TD_OK;
-}
-
 // Size the shared workspace for a batch with this geometry.  Growing it (or switching the kernel to the clamped logsum)
 // waits for the decode kernels in flight first.
 static int ensure_workspace(td_ctx* c, TdSlot& s)
 {
-	make_layout(s.lay, c->hdr.S, c->hdr.H, c->hdr.C, s.lmax, c->hdr.max_ncol);
+	make_layout(s.lay, c->dev.h.S, c->dev.h.H, c->dev.h.C, s.lmax, c->dev.h.max_ncol);
 	int64_t slot_bytes = s.lay.slot_bytes;
-	if (c->spec_ready && c->spec_oob && !spec_lsum_range_ok(c, s.lmax)) {
-		HIPCHK(c, sync_compute(c));
-		if (load_spec_kernel(c, 0) != TD_OK) return TD_FAIL;   // reads this long need the clamped logsum (seconds, once)
-	}
-	if (c->spec_ready) {
-		td_spec_layout(s.slay, c->plan, s.n_long > 0 ? s.lmax_small : s.lmax);   // the geometry of the many
-		td_spec_layout(s.slay_big, c->plan, s.lmax);
+	if (spec_before_batch(c, s.lmax) != TD_OK) return TD_FAIL;
+	if (c->spec.ready) {
+		td_spec_layout(s.slay, c->spec.plan, s.n_long > 0 ? s.lmax_small : s.lmax);   // the geometry of the many
+		td_spec_layout(s.slay_big, c->spec.plan, s.lmax);
 		slot_bytes = s.slay.slot_bytes;
-		if (ensure_prune_tables(c, s.lmax) != TD_OK) return TD_FAIL;
 	}
 	// wave slots: enough to fill the chip (2 workgroups of 4 waves per CU share the LDS), bounded by HBM
-	const int wpb = (c->spec_ready ? c->spec_block : td_kernel_block_threads()) / TD_WAVE;
-	int64_t want = (int64_t)c->n_cu * (c->spec_ready ? c->spec_waves_per_cu : 2 * wpb);
+	const int wpb = (c->spec.ready ? c->spec.block : td_kernel_block_threads()) / TD_WAVE;
+	int64_t want = (int64_t)c->n_cu * (c->spec.ready ? c->spec.waves_per_cu : 2 * wpb);
 	if (c->wave_slots_forced > 0) want = c->wave_slots_forced;
 	int64_t slots = want;
 	if (slots > s.n_tiles) slots = s.n_tiles;
@@ -1244,7 +542,7 @@ static int ensure_workspace(td_ctx* c, TdSlot& s)
 	// they are too many for that to pay -- more than a quarter of the slots -- the batch keeps one geometry
 	s.n_big = 0;
 	int64_t big_extra = 0;       // bytes the big slots take beyond a small slot each
-	if (c->spec_ready && s.n_long > 0) {
+	if (c->spec.ready && s.n_long > 0) {
 		if ((int64_t)s.n_long * 4 <= slots) {
 			s.n_big = s.n_long;
 			big_extra = (int64_t)s.n_big * (s.slay_big.slot_bytes - s.slay.slot_bytes);
@@ -1259,7 +557,7 @@ static int ensure_workspace(td_ctx* c, TdSlot& s)
 	// Pipelined batches overlap their launches on two streams with a workspace each.  When HBM cannot hold two workspaces of the
 	// full wave-slot count (config 5: 42 MiB per slot, 172 GB for 4096 slots) each launch gets half the slots instead -- two
 	// launches side by side still fill every SIMD, and the machine stays busy while one launch's slowest waves finish.
-	if (s.pipelined && c->overlap && c->pipeline_depth > 1 && c->spec_ready && !c->half_slots) {
+	if (s.pipelined && c->overlap && c->pipeline_depth > 1 && c->spec.ready && !c->half_slots) {
 		size_t free_b = 0, total_b = 0;
 		HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
 		const double avail = (double)free_b + (double)c->cap_ws + (double)c->cap_ws2;
@@ -1357,7 +655,7 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 	// the reads at the 99 % mark, the tiles beyond that mark (n_long of them) get wave slots of their own geometry and the rest
 	// keeps the geometry of the many -- one 1000-base read among 150-base reads no longer costs every slot 6.6 times the memory.
 	s.n_long = 0; s.lmax_small = lmax;
-	if (c->spec_ready && with_workspace && lmin != lmax && n_tiles >= 64 && c->length_classes) {
+	if (c->spec.ready && with_workspace && lmin != lmax && n_tiles >= 64 && c->length_classes) {
 		std::vector<int64_t> hist((size_t)lmax + 2, 0);
 		for (int64_t i = 0; i < n; i++) hist[(size_t)(offs[i + 1] - offs[i])]++;
 		// rank of the last read of the tile at the 99 % mark, its length, and the tiles that hold anything longer
@@ -1394,7 +692,7 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 	}
 	s.lmax = lmax; s.nw2 = nw2; s.nw1 = nw1; s.n_tiles = (int32_t)n_tiles;
 	if (with_workspace && ensure_workspace(c, s) != TD_OK) { s.n_tiles = 0; return TD_FAIL; }
-	s.for_spec = with_workspace && c->spec_ready;
+	s.for_spec = with_workspace && c->spec.ready;
 	s.n_tiles = 0;
 
 	// host -> device: page-locked caller memory goes straight to the DMA engine, anything else through pinned staging
@@ -1438,7 +736,7 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 // entries of a read's label-run table: a path visits one label per segment (+ the zeros behind a window, + one to spare)
 static int rle_capacity(const td_ctx* c)
 {
-	int cap = c->hdr.S + 2 < c->hdr.H ? c->hdr.S + 2 : c->hdr.H;
+	int cap = c->dev.h.S + 2 < c->dev.h.H ? c->dev.h.S + 2 : c->dev.h.H;
 	if (c->rle_cap_forced > 0) cap = c->rle_cap_forced;   // tests: force the overflow route
 	return cap;
 }
@@ -1470,31 +768,27 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	                     // slot's previous launch to the finish kernel)
 	s.mode = mode;
 	if (s.n_tiles == 0) { s.ran = true; s.last_ms = 0.0f; return TD_OK; }
-	if (c->spec_ready && s.for_spec && c->match_len > 0 && !c->spec_window) {   // first batch through a window: the kernel variant that applies it
+	if (c->spec.ready && s.for_spec && c->match_len > 0 && !c->spec.window) {   // first batch through a window: the kernel variant that applies it
 		HIPCHK(c, sync_compute(c));
-		if (load_spec_kernel(c, c->spec_oob ? 1 : 0, 1) != TD_OK) return TD_FAIL;
-		if (!c->spec_ready) {   // the probe rejected that variant: this batch gets the generic kernel's workspace geometry after all
+		if (spec_load_window_variant(c) != TD_OK) return TD_FAIL;
+		if (!c->spec.ready) {   // the probe rejected that variant: this batch gets the generic kernel's workspace geometry after all
 			s.n_long = 0; s.lmax_small = s.lmax;
 			if (ensure_workspace(c, s) != TD_OK) return TD_FAIL;
 			s.for_spec = false;
 		}
 	}
 	// a batch is decoded by the kernel it was staged for: one staged before a background compile was handed over stays generic
-	const bool use_spec = c->spec_ready && s.for_spec;
-	if (s.for_spec && !c->spec_ready) return fail(c, "td_run: the resident batch was staged for a specialised kernel that is no longer loaded (upload it again)");
+	const bool use_spec = c->spec.ready && s.for_spec;
+	if (s.for_spec && !c->spec.ready) return fail(c, "td_run: the resident batch was staged for a specialised kernel that is no longer loaded (upload it again)");
 	const OutLayout ol = out_layout(s.n_tiles, s.lmax, s.nw1);
 	TdKernelArgs ka{};
-	ka.hdr = c->d_hdr; ka.cols = c->d_cols; ka.hinfo = c->d_hinfo;
-	ka.pred_off = c->d_pred_off; ka.pred_idx = c->d_pred_idx; ka.logsum = c->d_logsum;
+	ka.hdr = c->dev.d_hdr; ka.cols = c->dev.d_cols; ka.hinfo = c->dev.d_hinfo;
+	ka.pred_off = c->dev.d_pred_off; ka.pred_idx = c->dev.d_pred_idx; ka.logsum = c->d_logsum;
 	ka.packed = s.d_packed; ka.lens = s.d_lens;
 	ka.n_tiles = s.n_tiles; ka.n_slots = s.n_wave_slots; ka.lmax = s.lmax; ka.nw2 = s.nw2; ka.nw1 = s.nw1;
 	ka.mode = mode; ka.threshold = c->threshold; ka.minlen = c->minlen; ka.dust = c->dust; ka.want_labels = 1;
 	ka.win_start = c->match_start; ka.win_len = c->match_len;
-	float* soa = (float*)s.d_out;
-	const int64_t st = ol.soa_stride / 4;
-	ka.out_f = soa; ka.out_b = soa + st; ka.out_r = soa + 2 * st; ka.out_bar = soa + 3 * st; ka.out_q = soa + 4 * st;
-	ka.out_type = (int32_t*)(soa + 5 * st); ka.out_barcode = (int32_t*)(soa + 6 * st); ka.out_finger = (int32_t*)(soa + 7 * st);
-	ka.out_keep = (uint32_t*)(s.d_out + ol.keep); ka.out_labels = (int8_t*)(s.d_out + ol.labels);
+	point_outputs(ka, s.d_out, ol);
 	ka.counters = c->d_counters;
 	ka.ws = s.wsi ? c->d_ws2 : c->d_ws; ka.lay = s.lay;
 	if (c->art_n > 0 && mode == TD_MODE_GET_LABEL) {
@@ -1514,16 +808,8 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	}
 	HIPCHK(c, hipEventRecord(s.ev_k0, s.cs));
 	if (use_spec) {
-		TdSpecArgs sa{};
-		sa.logsum = ka.logsum; sa.packed = ka.packed; sa.lens = ka.lens;
-		sa.n_tiles = ka.n_tiles; sa.n_slots = ka.n_slots; sa.lmax = ka.lmax; sa.nw2 = ka.nw2; sa.nw1 = ka.nw1;
-		sa.mode = ka.mode; sa.threshold = ka.threshold; sa.minlen = ka.minlen; sa.dust = ka.dust;
-		sa.win_start = ka.win_start; sa.win_len = ka.win_len;
-		sa.out_f = ka.out_f; sa.out_b = ka.out_b; sa.out_r = ka.out_r; sa.out_bar = ka.out_bar; sa.out_q = ka.out_q;
-		sa.out_type = ka.out_type; sa.out_barcode = ka.out_barcode; sa.out_finger = ka.out_finger;
-		sa.out_keep = ka.out_keep; sa.out_labels = ka.out_labels; sa.counters = ka.counters;
-		sa.art_text = ka.art_text; sa.art_index = ka.art_index; sa.art_left = ka.art_left; sa.art_n = ka.art_n; sa.art_fe = ka.art_fe;
-		sa.ws = ka.ws; sa.lay = s.slay;
+		TdSpecArgs sa = spec_args_from(ka);
+		sa.lay = s.slay;
 		sa.lmax = s.n_big > 0 ? s.lmax_small : s.lmax;
 		sa.n_big = s.n_big; sa.lmax_big = s.lmax; sa.lay_big = s.slay_big; sa.out_lmax = s.lmax;
 		// the label runs for the compact egress, and the flag that says a read had more of them -- only for a batch whose labels
@@ -1537,16 +823,12 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 			sa.out_runs = s.d_runs; sa.rle_overflow = (int32_t*)(s.d_runs + words - 1); sa.rle_cap = cap;
 			s.runs_cap = cap;
 		}
-		sa.prune = c->d_prune; sa.prune_stride = c->prune_stride;
+		sa.prune = c->spec.d_prune; sa.prune_stride = c->spec.prune_stride;
 		sa.tile_next = s.wsi ? c->d_tile_next2 : c->d_tile_next;
-		size_t sz = sizeof sa;
-		void* cfg[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, &sa, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END };
-		const int wpb = c->spec_block / TD_WAVE;
-		const unsigned blocks = (unsigned)((s.n_wave_slots + wpb - 1) / wpb);
-		HIPCHK(c, hipModuleLaunchKernel(c->spec_fn, blocks, 1, 1, (unsigned)c->spec_block, 1, 1, 0, s.cs, nullptr, cfg));
+		HIPCHK(c, spec_launch(c, sa, s.cs));
 	} else {
 		HIPCHK(c, td_launch_decode(&ka, s.cs));
-		c->batches_generic++;
+		c->spec.batches_generic++;
 	}
 	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
 	if (ka.art_n > 0 && slot_count_hits(c, s, ka.out_type) != TD_OK) return TD_FAIL;
@@ -1577,11 +859,7 @@ static int slot_rna_dust(td_ctx* c, TdSlot& s)
 		ra.art_pk = c->d_art_pk; ra.art_seq = c->d_art_seq; ra.art_left = s.d_art_left;
 		ra.art_n = c->art_n; ra.art_fe = c->art_fe;
 	}
-	float* soa = (float*)s.d_out;
-	const int64_t st = ol.soa_stride / 4;
-	ra.out_f = soa; ra.out_b = soa + st; ra.out_r = soa + 2 * st; ra.out_bar = soa + 3 * st; ra.out_q = soa + 4 * st;
-	ra.out_type = (int32_t*)(soa + 5 * st); ra.out_barcode = (int32_t*)(soa + 6 * st); ra.out_finger = (int32_t*)(soa + 7 * st);
-	ra.out_keep = (uint32_t*)(s.d_out + ol.keep);
+	point_outputs(ra, s.d_out, ol);
 	ra.counters = c->d_counters;
 	HIPCHK(c, hipEventRecord(s.ev_k0, s.cs));
 	HIPCHK(c, td_launch_rna_dust(ra, s.cs));
@@ -1672,7 +950,7 @@ static int slot_fetch_begin(td_ctx* c, TdSlot& s, td_read_result* res, int8_t* l
 	return TD_OK;
 }
 
-static double wall_ms()
+double wall_ms()
 {
 	struct timespec ts;
 	clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -1726,14 +1004,16 @@ static bool tickets_outstanding(const td_ctx* c)
 	return false;
 }
 
+// slot routing of the synchronous calls: everything on the context's first stream and workspace
+static TdRoute sync_route(const td_ctx* c) { return TdRoute{ c->stream, c->stream, c->stream, 0, false }; }
+
 static int upload_common(td_ctx* c, const void* bases, int is_ascii, const int64_t* offs, int64_t n)
 {
 	if (!c) return TD_FAIL;
 	if (tickets_outstanding(c)) return fail(c, "td_batch_upload: td_submit tickets are outstanding (td_wait them first)");
 	if (spec_handover(c, false) != TD_OK) return TD_FAIL;   // a finished background compile takes over before any geometry is chosen
 	TdSlot& s = c->slots[0];
-	TdRoute rt;
-	rt.cs = c->stream; rt.wsi = 0; rt.aux = c->stream; rt.fin = c->stream; rt.pipelined = false;
+	const TdRoute rt = sync_route(c);
 	if (slot_stage(c, s, rt, bases, is_ascii, offs, n, c->stream) != TD_OK) return TD_FAIL;
 	HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller may reuse its buffers
 	c->last_slot = 0;
@@ -1798,9 +1078,9 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 	if (mode == TD_MODE_RNA_DUST && labels) return fail(c, "td_submit: TD_MODE_RNA_DUST has no labels (pass NULL)");
 	if (spec_handover(c, false) != TD_OK) return TD_FAIL;   // a finished background compile takes over before any geometry is chosen
 	TdSlot& s = c->slots[k];
-	TdRoute rt;
-	rt.cs = c->stream; rt.wsi = 0; rt.aux = c->stream; rt.fin = c->stream; rt.pipelined = true;
-	if (c->overlap && c->pipeline_depth > 1 && c->spec_ready) {   // every other batch on the second stream / workspace
+	TdRoute rt = sync_route(c);
+	rt.pipelined = true;
+	if (c->overlap && c->pipeline_depth > 1 && c->spec.ready) {   // every other batch on the second stream / workspace
 		if (!c->stream2) HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
 		if (c->submit_parity) { rt.cs = c->stream2; rt.wsi = 1; }
 		c->submit_parity ^= 1;
@@ -1843,8 +1123,7 @@ extern "C" int td_arch_scores(td_ctx* c, const td_model_desc* const* models, int
 	HIPCHK(c, hipSetDevice(c->device));
 	TdSlot& s = c->slots[0];
 	// the reads are staged (sorted by length, packed) once; no model of the context is involved
-	TdRoute rt;
-	rt.cs = c->stream; rt.wsi = 0; rt.aux = c->stream; rt.fin = c->stream; rt.pipelined = false;
+	const TdRoute rt = sync_route(c);
 	if (slot_stage(c, s, rt, codes, 0, offs, n_reads, c->stream, false) != TD_OK) return TD_FAIL;
 	s.staged = false;                      // not a batch td_run could use: it has no workspace geometry
 	if (s.n_tiles == 0) return TD_OK;

@@ -1,4 +1,4 @@
-// td_jit.h -- interface between the C-ABI layer (td_api.hip) and the model-specialised kernel builder (td_jit.hip: plan, model
+// td_jit.h -- interface between the C-ABI layer (td_spec_host.hip, td_api.hip) and the model-specialised kernel builder (td_jit.hip: plan, model
 // section, layout, compile + cache; td_spec_bounds.cpp: the bound tables)
 #pragma once
 #include <string>

@@ -1,4 +1,4 @@
-// td_spec_probe.cpp -- the probe reads a freshly loaded model-specialised kernel is checked with (td_api.hip, probe_spec_kernel):
+// td_spec_probe.cpp -- the probe reads a freshly loaded model-specialised kernel is checked with (td_spec_host.hip, probe_spec_kernel):
 // TD_PROBE_READS reads made from the model description alone, decoded by the new kernel and by the generic ahead-of-time kernel;
 // the new kernel takes over only when every byte a caller could see agrees.  Host only, no GPU.
 //

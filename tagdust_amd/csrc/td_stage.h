@@ -58,7 +58,7 @@ hipError_t td_stage_finish(const TdStageBatch& b, hipStream_t stream);
 // memory-side probe of a candidate workspace allocation (milliseconds, best of three passes); see td_stage.hip
 hipError_t td_ws_probe(uint8_t* ws, int64_t slot_bytes, int n_slots, hipStream_t stream, float* ms);
 
-// The probe's comparison (td_api.hip, probe_spec_kernel): two decode launches over the same n_tiles full tiles of reads, outputs
+// The probe's comparison (td_spec_host.hip, probe_spec_kernel): two decode launches over the same n_tiles full tiles of reads, outputs
 // in device order.  What a caller could see is compared -- the eight SoA words of every read bit for bit, labels[0..len], the keep
 // bits over len -- and the first n_counters words of the two launches' counters; padding no kernel defines is not looked at.
 // out[0] = differing reads (+ 1 when the counters differ), out[1 + 2 w], out[2 + 2 w] = the first differing read of tile w and

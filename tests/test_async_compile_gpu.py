@@ -215,6 +215,29 @@ def test_probe_accepts_every_shipped_model(goldens, name):
         c.close()
 
 
+def test_async_selfcheck_falls_back_through_a_second_job(goldens, monkeypatch):
+    """A background compile whose clamp-free logsum fails the self-check at the hand-over (forced through
+    TD_SPEC_SELFCHECK_FAIL, which a context reads when it is created) is not loaded: the clamped form goes to the background as a
+    second job, the generic kernel decodes meanwhile, and td_spec_wait returns only when that second kernel has taken over.  The
+    ordinary cache directory serves: both code objects are usually there already."""
+    monkeypatch.setenv("TD_SPEC_SELFCHECK_FAIL", "1")
+    g = goldens("umi_f_s_r")
+    c = _ctx(g, 1)
+    try:
+        assert c.get_option("spec_state") in (1, 2)
+        res, labels, seq = _decode(c, g)
+        _assert_golden(g, res, labels, seq)
+        c.spec_wait()
+        assert c.get_option("spec_state") == 3
+        assert c.get_option("spec_lsum_clamped") == 1
+        n_generic = c.get_option("spec_batches_generic")
+        res2, labels2, seq2 = _decode(c, g)
+        assert res2.tobytes() == res.tobytes() and labels2.tobytes() == labels.tobytes() and seq2.tobytes() == seq.tobytes()
+        assert c.get_option("spec_batches_generic") == n_generic       # the clamped kernel ran this one
+    finally:
+        c.close()
+
+
 def test_concurrent_uploads_share_one_compile(goldens, monkeypatch, tmp_path):
     from tagdust_amd import TagdustHip
     _fresh(monkeypatch, tmp_path, 120)
