@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include "tagdust_hip.h"
 #include "tagdust_io.h"
+#include "tagdust_census.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -63,6 +64,9 @@ typedef struct td_run_opts {
 	int32_t  echo_log;               /* every log message also goes to stderr as it is made, as the reference does (the executable sets it) */
 	int32_t  argc;                   /* the command line as given, for the log's "cmd:" line */
 	char**   argv;
+	int32_t  unknown_barcodes;       /* --unknown-barcodes K   [0 = off]: the K most frequent barcode spellings of the reads that were not
+	                                    extracted (tagdust_census.h, the default outcomes) go to <out>_unknown_barcodes.txt */
+	int32_t  unknown_slots_log2;     /* --unknown-barcodes-slots N   [20]: the census table of every device has 2^N slots */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -82,7 +86,8 @@ const char* td_run_version(void);
  * main.c:103-125 (an architecture or an arch file, -o, the files exist), per file where its architecture comes from
  * (barcode_hmm.c:105-129: file 0 the command line's segments when there are any, else the arch file's best candidate, else R:N),
  * "barcodes in more than one file" (:141-146), the number of output reads and the output files' names (td_writer_open's), the
- * existing-output check (io.c:633-691: made when a file holds a barcode, like the reference's; skipped with `force`), the
+ * existing-output check (io.c:633-691: made when a file holds a barcode, like the reference's; skipped with `force`; with
+ * --unknown-barcodes <out>_unknown_barcodes.txt is one of the output files, and the option is refused with -start / -end), the
  * multiread rule (interface.c:441-450: DUST and -ref off, with a warning, when the command line's architecture has two or more
  * R segments).  What depends on the arch file's choice is decided again by td_run_execute once the choice is made. */
 typedef struct td_run_plan_t td_run_plan_t;   /* (the function below has the plain name) */
@@ -114,6 +119,9 @@ typedef struct td_run_report {
 	                                              td_model_upload (the compile, unless it runs in the background), streaming */
 	int32_t  stats_on_device;                 /* 1: the statistics were counted on the device */
 	char*    log;                             /* the text of <out>_logfile.txt */
+	int64_t  n_unknown;                       /* --unknown-barcodes: distinct spellings over all devices (0 without the option) */
+	td_census_entry* unknown;                 /* [n_unknown] by count descending, then key ascending */
+	td_census_totals unknown_totals;          /* summed over the devices */
 } td_run_report;
 /* In the controller's order: architectures per file, statistics over each file's head, thresholds, models, the run, the log.
  * A failure before the first batch leaves no output files behind; one during the run leaves them as they are and says so.  The

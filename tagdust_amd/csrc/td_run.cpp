@@ -168,6 +168,7 @@ bool read_arch_file(const char* path, ArchFile& af, std::string& why)
 struct OptSpec { const char* name; int arg; int id; };
 enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
+       O_UNKNOWN, O_UNKNOWN_SLOTS,
        O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
@@ -191,6 +192,7 @@ const OptSpec kOpts[] = {
 const OptSpec kOwnOpts[] = {
 	{ "devices", 1, O_DEVICES }, { "rtest", 0, O_RTEST }, { "host-threads", 1, O_HOST_THREADS }, { "batch-reads", 1, O_BATCH_READS },
 	{ "sync-compile", 0, O_SYNC_COMPILE }, { "stats-on-host", 0, O_STATS_ON_HOST }, { "force", 0, O_FORCE }, { "dry-run", 0, O_DRY_RUN },
+	{ "unknown-barcodes", 1, O_UNKNOWN }, { "unknown-barcodes-slots", 1, O_UNKNOWN_SLOTS },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -228,6 +230,7 @@ extern "C" td_run_opts* td_run_opts_new(void)
 	o->matchstart = -1; o->matchend = -1;   // :80-81
 	o->seed = 0;                        // :124
 	o->n_devices = 1; o->devices[0] = 0;
+	o->unknown_slots_log2 = 20;
 	return o;
 }
 
@@ -272,7 +275,10 @@ extern "C" const char* td_run_usage(void)
 	       "\t--sync-compile    compile the model kernel before decoding (default: decode while it compiles)\n"
 	       "\t--stats-on-host   sequence statistics on the host\n"
 	       "\t--force           overwrite existing output files\n"
-	       "\t--dry-run         print the decisions of the run and stop\n\n";
+	       "\t--dry-run         print the decisions of the run and stop\n"
+	       "\t--unknown-barcodes K        the K most frequent barcode spellings of the reads that were not extracted,\n"
+	       "\t                            into <output prefix>_unknown_barcodes.txt\n"
+	       "\t--unknown-barcodes-slots N  slots of the counting table on every device, as a power of two [20]\n\n";
 }
 
 extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
@@ -336,11 +342,14 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 		case O_STATS_ON_HOST: o->stats_on_host = 1; break;
 		case O_FORCE: o->force = 1; break;
 		case O_DRY_RUN: o->dry_run = 1; break;
+		case O_UNKNOWN: o->unknown_barcodes = atoi(v); if (o->unknown_barcodes < 1) return bad("--unknown-barcodes: need a number of lines K >= 1"); break;
+		case O_UNKNOWN_SLOTS: o->unknown_slots_log2 = atoi(v); break;
 		default: return bad("unknown option " + a);
 		}
 	}
 	if (o->num_threads < 1) return bad("option -t: need at least one thread");
 	if (o->host_threads < 0 || o->batch_reads < 0) return bad("--host-threads / --batch-reads: negative value");
+	if (o->unknown_slots_log2 < 4 || o->unknown_slots_log2 > 26) return bad("--unknown-barcodes-slots: need 4..26 (the table has 2^N slots)");
 	if ((int)files.size() > TD_RUN_MAX_FILES) return bad("more than 8 input files");
 	o->infile = (char**)calloc(files.size() ? files.size() : 1, sizeof(char*));
 	for (auto& f : files) o->infile[o->n_infiles++] = dup_str(f.c_str());
@@ -376,6 +385,8 @@ std::vector<std::string> cmdline_segments(const td_run_opts* o)
 	return s;
 }
 
+std::string unknown_file_name(const td_run_opts* o) { return std::string(o->outfile) + "_unknown_barcodes.txt"; }
+
 // what the controller decides once every file's architecture is known (barcode_hmm.c:130-159): TD_FAIL with the reference's message
 int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& archs, int& bar_file, int& num_out_reads, std::vector<std::string>& names)
 {
@@ -390,6 +401,10 @@ int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& arch
 	if (num_out_reads == 0) return run_fail("No read segment in any architecture: there would be no output file.");
 	// print_all() names its files after the barcode file's architecture, else the last file's (td_stream_run_multi; one file: td_writer_open)
 	td_writer_file_names_n(o->outfile, archs[(size_t)(bar_file >= 0 ? bar_file : (int)archs.size() - 1)], num_out_reads, names, nullptr);
+	if (o->unknown_barcodes > 0) {
+		if (bar_file < 0) return run_fail("--unknown-barcodes: no input file's architecture has a barcode segment.");
+		names.push_back(unknown_file_name(o));
+	}
 	if (bar_file >= 0 && !o->force)   // check_for_existing_demultiplexed_files_multiple, io.c:633-691 (made for the barcode file only)
 		for (auto& n : names)
 			if (file_exists(n)) return run_fail("Error: some output files already exists. (%s; --force overwrites)", n.c_str());
@@ -413,6 +428,8 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	if (o->n_infiles == 0) return run_fail("ERROR: No input file found.");
 	if (!o->outfile) return run_fail("ERROR: You need to specify an output file prefix using the -o / -out option.");
 	if (o->arch_file && !file_exists(o->arch_file)) return run_fail("ERROR: Arch file:%s does not exists.", o->arch_file);
+	if (o->unknown_barcodes > 0 && (o->matchstart != -1 || o->matchend != -1))
+		return run_fail("--unknown-barcodes cannot be combined with -start / -end: labels behind a window do not spell the barcode.");
 	for (int k = 0; k < o->n_infiles; k++)
 		if (strcmp(o->infile[k], "-") != 0 && !file_exists(o->infile[k])) return run_fail("ERROR: Input file:%s does not exists.", o->infile[k]);
 	// interface.c:419-450: two or more R segments in the command line's architecture switch DUST and -ref off
@@ -596,6 +613,7 @@ extern "C" void td_run_report_clear(td_run_report* r)
 	if (!r) return;
 	if (r->artifact_names) for (int j = 0; j < r->n_artifacts; j++) free(r->artifact_names[j]);
 	free(r->artifact_names); free(r->artifact_hits); free(r->log);
+	td_census_free(r->unknown);
 	for (int k = 0; k < TD_RUN_MAX_FILES; k++) free(r->architectures[k]);
 	memset(r, 0, sizeof *r);
 }
@@ -718,6 +736,7 @@ struct Run {
 
 	int execute();
 	int run_files(td_stream_stats& st);
+	int unknown_barcodes(int bar_file);
 };
 
 int Run::execute()
@@ -837,6 +856,9 @@ int Run::execute()
 			if (td_set_artifacts(c, fasta ? fasta->string : nullptr, fasta ? fasta->s_index : nullptr, fasta ? fasta->n_seq : 0, o->filter_error, o->num_threads) != TD_OK)
 				return fail("%s", td_last_error(c));
 			if (td_counts_reset(c) != TD_OK) return fail("%s", td_last_error(c));
+			// --unknown-barcodes: the contexts of the barcode file count what their reads spell in the last 'B' segment
+			if (o->unknown_barcodes > 0 && k == bar_file &&
+			    td_census_enable(c, -1, TD_CENSUS_DEFAULT_MASK, o->unknown_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
 		}
 	}
 	rep->compile_wait_s = now_s() - t0;
@@ -852,8 +874,81 @@ int Run::execute()
 		return fail("%s -- the run failed after it had started: the output files are incomplete and were left as they are", msg.c_str());
 	}
 
+	if (o->unknown_barcodes > 0 && unknown_barcodes(bar_file) != TD_OK) return TD_FAIL;
+
 	// 6. the summary, barcode_hmm.c:387-430
 	for (auto& m : summary_messages(o, rep)) log.add(m);
+	return TD_OK;
+}
+
+// Levenshtein distance of two short words
+int edit_distance(const std::string& a, const std::string& b)
+{
+	std::vector<int> row(b.size() + 1);
+	for (size_t j = 0; j <= b.size(); j++) row[j] = (int)j;
+	for (size_t i = 1; i <= a.size(); i++) {
+		int diag = row[0];
+		row[0] = (int)i;
+		for (size_t j = 1; j <= b.size(); j++) {
+			const int up = row[j];
+			row[j] = std::min(std::min(row[j] + 1, row[j - 1] + 1), diag + (a[i - 1] != b[j - 1]));
+			diag = up;
+		}
+	}
+	return row[b.size()];
+}
+
+// --unknown-barcodes: every device's census of the barcode file, merged (nothing of it enters the log), and <out>_unknown_barcodes.txt
+int Run::unknown_barcodes(int bar_file)
+{
+	FileState& f = files[(size_t)bar_file];
+	td_census_entry* acc = nullptr;
+	int64_t n_acc = 0;
+	td_census_totals sum{};
+	for (td_ctx* c : f.raw) {
+		int64_t n = 0;
+		td_census_totals t{};
+		if (td_census_get(c, nullptr, 0, &n, &t) != TD_OK) { td_census_free(acc); return fail("%s", td_last_error(c)); }
+		std::vector<td_census_entry> part((size_t)std::max<int64_t>(n, 1));
+		if (td_census_get(c, part.data(), n, &n, &t) != TD_OK) { td_census_free(acc); return fail("%s", td_last_error(c)); }
+		td_census_entry* merged = nullptr;
+		int64_t n_merged = 0;
+		const int rc = td_census_merge(acc, n_acc, part.data(), n, &merged, &n_merged);
+		td_census_free(acc);
+		if (rc != TD_OK) return fail("%s", td_last_error(nullptr));
+		acc = merged; n_acc = n_merged;
+		sum.eligible += t.eligible; sum.counted += t.counted; sum.skipped_empty += t.skipped_empty; sum.skipped_long += t.skipped_long;
+		sum.skipped_n += t.skipped_n; sum.overflow += t.overflow;
+	}
+	sum.distinct = n_acc;
+	rep->unknown = acc; rep->n_unknown = n_acc; rep->unknown_totals = sum;
+
+	const td_arch* a = f.arch.get();
+	int seg = -1;
+	for (int j = 0; j < a->n_segments; j++) if (a->type[j] == 'B') seg = j;
+	const std::string name = unknown_file_name(o);
+	FILE* out = fopen(name.c_str(), "w");
+	if (!out) return fail("Failed to open file:%s", name.c_str());
+	fprintf(out, "# unknown barcodes: what the reads that were not extracted spell in segment %d (%s) of %s\n", seg + 1, f.segs[(size_t)seg].c_str(), o->infile[bar_file]);
+	fprintf(out, "# eligible reads\t%lld\n# counted\t%lld\n# distinct sequences\t%lld\n# no base in the segment\t%lld\n# more than %d bases\t%lld\n# with N\t%lld\n",
+	        (long long)sum.eligible, (long long)sum.counted, (long long)sum.distinct, (long long)sum.skipped_empty, TD_CENSUS_MAX_WORD,
+	        (long long)sum.skipped_long, (long long)sum.skipped_n);
+	if (sum.overflow > 0)
+		fprintf(out, "# the counting table was too small: %lld reads were not counted (the counts below are exact; --unknown-barcodes-slots %d or more)\n",
+		        (long long)sum.overflow, o->unknown_slots_log2 + 1);
+	fprintf(out, "# count\tsequence\tnearest\tdistance\n");
+	const int n_listed = a->n_seq[seg] - 1;   // (the last one is the all-N wildcard)
+	for (int64_t i = 0; i < n_acc && i < o->unknown_barcodes; i++) {
+		char word[32];
+		if (td_census_key_text(acc[i].key, word) != TD_OK) { fclose(out); return fail("%s", td_last_error(nullptr)); }
+		int best = -1, best_d = 0;
+		for (int q = 0; q < n_listed; q++) {
+			const int d = edit_distance(word, a->seqs[seg][q]);
+			if (best < 0 || d < best_d) { best = q; best_d = d; }   // (ties go to the lower index)
+		}
+		fprintf(out, "%lld\t%s\t%s\t%d\n", (long long)acc[i].count, word, best >= 0 ? a->seqs[seg][best] : "-", best >= 0 ? best_d : -1);
+	}
+	fclose(out);
 	return TD_OK;
 }
 

@@ -43,6 +43,14 @@ RUN_ABI_SYMBOLS = ["td_run_opts_new", "td_run_opts_free", "td_run_last_error", "
                    "td_run_plan", "td_run_plan_free", "td_run_plan_describe", "td_run_output_files_describe", "td_run_arch_file_describe", "td_run_execute",
                    "td_run_report_clear", "td_run_format_summary"]
 
+# include/tagdust_census.h: the census of barcode spellings
+CENSUS_ABI_SYMBOLS = ["td_census_enable", "td_census_disable", "td_census_reset", "td_census_get", "td_census_host", "td_census_merge",
+                      "td_census_key_text", "td_census_free"]
+CENSUS_ENTRY_DTYPE = np.dtype([("key", "<u8"), ("count", "<i8")])
+CENSUS_TOTALS = ("eligible", "counted", "skipped_empty", "skipped_long", "skipped_n", "overflow", "distinct")
+CENSUS_DEFAULT_MASK = (1 << 1) | (1 << 3)   # EXTRACT_FAIL_ARCHITECTURE_MISMATCH, EXTRACT_FAIL_BAR_FINGER_NOT_FOUND
+CENSUS_MAX_WORD = 28
+
 RESULT_DTYPE = np.dtype([
     ("f_score", "<f4"), ("b_score", "<f4"), ("r_score", "<f4"), ("bar_prob", "<f4"), ("mapq", "<f4"),
     ("read_type", "<i4"), ("barcode", "<i4"), ("fingerprint", "<i4"),
@@ -563,7 +571,15 @@ class _RunOpts(C.Structure):
                 ("infile", C.POINTER(C.c_char_p)), ("n_devices", C.c_int32), ("devices", C.c_int32 * 16), ("flavour", C.c_int32),
                 ("host_threads", C.c_int32), ("batch_reads", C.c_int32), ("sync_compile", C.c_int32), ("stats_on_host", C.c_int32),
                 ("force", C.c_int32), ("dry_run", C.c_int32), ("help", C.c_int32), ("version", C.c_int32), ("echo_log", C.c_int32),
-                ("argc", C.c_int32), ("argv", C.POINTER(C.c_char_p))]
+                ("argc", C.c_int32), ("argv", C.POINTER(C.c_char_p)), ("unknown_barcodes", C.c_int32), ("unknown_slots_log2", C.c_int32)]
+
+
+class _CensusTotals(C.Structure):
+    """td_census_totals (include/tagdust_census.h)"""
+    _fields_ = [(f, C.c_int64) for f in CENSUS_TOTALS]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f in CENSUS_TOTALS}
 
 
 class _RunReport(C.Structure):
@@ -572,7 +588,8 @@ class _RunReport(C.Structure):
                 ("artifact_hits", C.POINTER(C.c_int64)), ("artifact_names", C.POINTER(C.c_char_p)), ("n_files", C.c_int32),
                 ("thresholds", C.c_float * 8), ("selected_threshold", C.c_float), ("architectures", C.c_char_p * 8),
                 ("stream", _StreamStats), ("arch_s", C.c_double), ("stats_s", C.c_double), ("calibration_s", C.c_double),
-                ("compile_wait_s", C.c_double), ("stream_s", C.c_double), ("stats_on_device", C.c_int32), ("log", C.c_char_p)]
+                ("compile_wait_s", C.c_double), ("stream_s", C.c_double), ("stats_on_device", C.c_int32), ("log", C.c_char_p),
+                ("n_unknown", C.c_int64), ("unknown", C.c_void_p), ("unknown_totals", _CensusTotals)]
 
 
 def _run_lib():
@@ -681,10 +698,88 @@ def run_execute(args):
             "stream": {f: getattr(rep.stream, f) for f, _ in _StreamStats._fields_},
             "seconds": {f: getattr(rep, f + "_s") for f in ("arch", "stats", "calibration", "compile_wait", "stream")},
             "stats_on_device": bool(rep.stats_on_device), "log": (rep.log or b"").decode(),
+            "unknown": _census_entries(rep.unknown, int(rep.n_unknown)), "unknown_totals": rep.unknown_totals.as_dict(),
         }
     finally:
         o.lib.td_run_report_clear(C.byref(rep))
         o.close()
+
+
+def _census_entries(ptr, n):
+    """n td_census_entry at ptr, copied"""
+    out = np.zeros(n, CENSUS_ENTRY_DTYPE)
+    if n:
+        C.memmove(out.ctypes.data, ptr, n * CENSUS_ENTRY_DTYPE.itemsize)
+    return out
+
+
+def _census_lib():
+    lib = load_library()
+    lib.td_census_enable.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_int32]
+    lib.td_census_disable.argtypes = [C.c_void_p]
+    lib.td_census_reset.argtypes = [C.c_void_p]
+    lib.td_census_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_CensusTotals)]
+    lib.td_census_host.argtypes = [C.POINTER(_ModelDesc), C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(_CensusTotals)]
+    lib.td_census_merge.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    lib.td_census_key_text.argtypes = [C.c_uint64, C.c_char_p]
+    lib.td_census_free.argtypes = [C.c_void_p]
+    lib.td_census_free.restype = None
+    return lib
+
+
+def census_host(md, seq, offs, read_type, labels, segment=-1, mask=CENSUS_DEFAULT_MASK):
+    """td_census_host: the census of a batch from host arrays (no GPU).  md: model mapping; read_type: the reads' final outcomes
+    (td_batch_download's, or the oracle's); labels as td_batch_download leaves them.  Returns (entries, totals dict)."""
+    lib = _census_lib()
+    desc, keep = make_model_desc(md)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
+    rr["read_type"] = np.asarray(read_type)
+    ptr, n, tot = C.c_void_p(), C.c_int64(), _CensusTotals()
+    rc = lib.td_census_host(C.byref(desc), int(segment), int(mask), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
+                            labels.ctypes.data, C.byref(ptr), C.byref(n), C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    try:
+        return _census_entries(ptr, n.value), tot.as_dict()
+    finally:
+        lib.td_census_free(ptr)
+
+
+def census_merge(a, b):
+    """td_census_merge: the sum of two census results, in td_census_get's order."""
+    lib = _census_lib()
+    a = np.ascontiguousarray(a, CENSUS_ENTRY_DTYPE)
+    b = np.ascontiguousarray(b, CENSUS_ENTRY_DTYPE)
+    ptr, n = C.c_void_p(), C.c_int64()
+    if lib.td_census_merge(a.ctypes.data, len(a), b.ctypes.data, len(b), C.byref(ptr), C.byref(n)) != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    try:
+        return _census_entries(ptr, n.value)
+    finally:
+        lib.td_census_free(ptr)
+
+
+def census_key_text(key):
+    """td_census_key_text: the bases a key spells ("ACGTTG")."""
+    lib = _census_lib()
+    buf = C.create_string_buffer(32)
+    if lib.td_census_key_text(int(key), buf) != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return buf.value.decode()
+
+
+def census_key(word):
+    """the key of a word of 1..28 bases over ACGT (tagdust_census.h)"""
+    assert 1 <= len(word) <= CENSUS_MAX_WORD
+    v = 0
+    for ch in word:
+        v = (v << 2) | "ACGT".index(ch)
+    return (len(word) << 56) | v
 
 
 def stream_release():
@@ -878,6 +973,26 @@ class TagdustHip:
         out = np.zeros((len(descs), n), np.float32)
         self._chk(self.lib.td_arch_scores(self.h, ptrs, len(descs), codes.ctypes.data, offs.ctypes.data, n, out.ctypes.data))
         return out
+
+    def census_enable(self, segment=-1, mask=CENSUS_DEFAULT_MASK, log2_slots=20):
+        self._chk(_census_lib().td_census_enable(self.h, int(segment), int(mask), int(log2_slots)))
+
+    def census_disable(self):
+        self._chk(_census_lib().td_census_disable(self.h))
+
+    def census_reset(self):
+        self._chk(_census_lib().td_census_reset(self.h))
+
+    def census(self, cap=None):
+        """td_census_get: (entries by count descending then key ascending -- at most cap of them --, totals dict)"""
+        lib = _census_lib()
+        n, tot = C.c_int64(), _CensusTotals()
+        if cap is None:
+            self._chk(lib.td_census_get(self.h, None, 0, C.byref(n), C.byref(tot)))
+            cap = n.value
+        out = np.zeros(int(cap), CENSUS_ENTRY_DTYPE)
+        self._chk(lib.td_census_get(self.h, out.ctypes.data, int(cap), C.byref(n), C.byref(tot)))
+        return out[:min(int(cap), n.value)], tot.as_dict()
 
     def counts_reset(self):
         self._chk(self.lib.td_counts_reset(self.h))
