@@ -57,6 +57,14 @@ int  td_writer_open(const char* out_prefix, const td_arch* arch, td_writer** out
 /* Append one decoded batch: res / seq_out exactly as td_batch_download returns them. */
 int  td_writer_write(td_writer* w, const td_reads* reads, const td_read_result* res, const uint8_t* seq_out);
 int  td_writer_close(td_writer* w);
+/* get_finger_seq() (src/io.c:1018-1029): the bases a fingerprint stands for, as the reference's -show_finger_seq prints them.
+ * len = fingerprint & 0xFF bases, taken from fingerprint >> 8 two bits each (A, C, G, T = 0..3), the last base in the lowest bits,
+ * with the reference's 32-bit signed arithmetic: the shift is arithmetic, so a fingerprint of more than 12 bases -- whose leading
+ * bases the int has lost, and which may be negative -- gives the text the reference gives.  buf receives len characters and a NUL;
+ * returns len. */
+int  td_fingerprint_text(int32_t fingerprint, char buf[256]);
+/* on != 0: td_writer_write prints ";FP:<td_fingerprint_text>" instead of ";FP:%d" (param->print_seq_finger, io.c:960-963) */
+int  td_writer_set_fingerprint_text(td_writer* w, int on);
 
 /* ---- one input file of any size as a pipeline: the reference's batch loop around run_pHMM (src/barcode_hmm.c:244-385) ----
  * read_fasta_fastq() of <= 1 000 001 records (io.c:1684-1815; plain files, or zcat / bzcat through popen like io_handler(),
@@ -83,6 +91,7 @@ typedef struct td_stream_opts {
 	                          of the result -- and 2^18 otherwise (results do not depend on the batching then) */
 	int32_t n_threads;     /* host threads of the parse stage and of the write stage, each; 0 = pick (<= 8) */
 	int64_t block_bytes;   /* bytes of input taken at a time; 0 = 64 MiB */
+	int32_t fingerprint_text;   /* != 0: ";FP:ACGT" (td_fingerprint_text) instead of ";FP:27" in the read names; 0 = as the reference's default */
 } td_stream_opts;
 typedef struct td_stream_stats {
 	int64_t n_reads, n_batches, bytes_in, bytes_out;

@@ -1,0 +1,80 @@
+/*
+ * tagdust_molecules.h -- how many molecules did each barcode yield: the extracted reads of a run counted per (barcode, fingerprint,
+ * start of the read), on the device behind every TD_MODE_GET_LABEL batch of a context (part of libtagdust_hip.so, plain C).  The
+ * reference extracts the fingerprint (UMI) and prints it; it counts nothing with it.
+ *
+ * A read is eligible when its final outcome (read_type & 0xFF, after the -ref filter and DUST) is TD_EXTRACT_SUCCESS.  Its read
+ * bases are the bases seq[p], in read order, at the positions p in 0..len-1 whose label belongs to an 'R' segment:
+ * model.seg_type[model.label[labels[p + 1]] & 0xFFFF] == 'R', the mapping extract_reads uses (src/barcode_hmm.c:3205-3208).  Its
+ * prefix is the first n = min(number of read bases, P) of them, P = prefix_bases; w holds the prefix, two bits per base (A, C, G,
+ * T = 0..3), the first base the most significant of the 2n bits.  An eligible read is in exactly one of three classes, checked
+ * in this order: skipped_empty when n == 0; skipped_n when a prefix base is not A, C, G or T; otherwise it is counted under
+ *
+ *     mix(k): k ^= k >> 30; k *= 0xBF58476D1CE4E5B9; k ^= k >> 27; k *= 0x94D049BB133111EB; k ^= k >> 31        (uint64_t)
+ *     a   = mix(((uint64_t)(uint32_t)fingerprint << 8) | n)
+ *     low = mix(w ^ a) & 0x00FFFFFFFFFFFFFF;   if (low == 0) low = 1
+ *     bin = barcode == -1 ? 0 : barcode & 0xFF          (the writer's file index, the bin of td_counts_get)
+ *     key = (uint64_t)bin << 56 | low                    (never 0)
+ *
+ * with the record's own fingerprint and barcode (td_read_result; the fingerprint is -1 without an 'F' segment).  So two reads are
+ * the same molecule when they have the same barcode, the same fingerprint and the same first P read bases.  The match is exact: a
+ * sequencing error in the prefix or in the UMI makes a new molecule (no neighbouring UMIs are collapsed).  Two limits:
+ *   - within one barcode two molecules whose 56-bit `low` collide are counted as one.  Among m molecules of a barcode about
+ *     m^2 / 2 * 2^-56 pairs do: 0.0007 for m = 10^7 -- one run in 1400 counts one molecule too few;
+ *   - the reference's fingerprint is an int of (bases << 8 | length): a UMI of more than 12 bases has lost its leading bases in
+ *     it, and such UMIs that differ only there are one fingerprint.
+ *
+ * The table is the census's (tagdust_census.h): 2^log2_slots slots of 16 bytes (a key and a count); a key that finds no slot
+ * within its probe window adds its reads to `overflow`, on every attempt alike, so a reported count is always exact.  Always
+ *     eligible == counted + skipped_empty + skipped_n + overflow      and      counted == the sum of all counts.
+ * The default of 2^26 slots (1 GiB) holds the 2^24 molecules of a large run at a quarter full, where no probe comes near the window.
+ */
+#ifndef TAGDUST_MOLECULES_H
+#define TAGDUST_MOLECULES_H
+
+#include <stdint.h>
+#include "tagdust_hip.h"
+#include "tagdust_census.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define TD_MOL_MAX_PREFIX          32
+#define TD_MOL_DEFAULT_PREFIX      20
+#define TD_MOL_DEFAULT_LOG2_SLOTS  26
+#define TD_MOL_LEVELS              10
+
+typedef struct td_mol_totals { int64_t eligible, counted, skipped_empty, skipped_n, overflow, molecules; } td_mol_totals;
+/* one barcode bin: reads counted, distinct molecules, and levels[min(count, 10) - 1] = molecules seen `count` times (the last
+ * level: 10 times or more) */
+typedef struct td_mol_row { int64_t reads, molecules, levels[TD_MOL_LEVELS]; } td_mol_row;
+
+/* Switches the molecule count of this context on (off by default): prefix_bases in 1..32, log2_slots in 4..30 (0 = the default).
+ * TD_FAIL with a message when no model is uploaded, a -start/-end window is set, or td_submit tickets are outstanding.  While it
+ * is on every TD_MODE_GET_LABEL batch (td_run and td_submit alike) adds to it, no other mode and not td_arch_scores;
+ * td_set_window fails; a later td_model_upload switches it off.  It may be on together with the census, each with its own table. */
+int td_mol_enable (td_ctx* ctx, int32_t prefix_bases, int32_t log2_slots);
+int td_mol_disable(td_ctx* ctx);                    /* frees the table */
+int td_mol_reset  (td_ctx* ctx);                    /* zero table and tallies; td_counts_reset does not touch it */
+/* Waits for the context's queued work.  The raw (key, count) pairs, compacted on the device: *n = the number of molecules; at
+ * most cap entries are copied, sorted as td_census_get sorts (count descending, then key ascending).  This is what is merged
+ * across devices: td_census_merge adds two such results.  entries may be NULL when cap is 0; totals may be NULL. */
+int td_mol_entries(td_ctx* ctx, td_census_entry* entries, int64_t cap, int64_t* n, td_mol_totals* totals);
+/* the summary per barcode bin, computed on the device by a sweep over the table; totals may be NULL */
+int td_mol_get    (td_ctx* ctx, td_mol_row rows[TD_NUM_BARCODE_BINS], td_mol_totals* totals);
+/* the same rows from entries, on the host: after merging several devices, and the yardstick of td_mol_get */
+int td_mol_summarise(const td_census_entry* entries, int64_t n, td_mol_row rows[TD_NUM_BARCODE_BINS]);
+/* the same entries from host arrays, no GPU: for hosts without one and as the yardstick of the device path.  Arguments as
+ * td_census_host takes them.  Never overflows.  *entries is freed with td_census_free; the message of a failure is
+ * td_last_error(NULL)'s. */
+int td_mol_host   (const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                   const td_read_result* res, const int8_t* labels, td_census_entry** entries, int64_t* n, td_mol_totals* totals);
+/* the key of a counted read: its record's barcode and fingerprint, its prefix word w of n bases (1..32) */
+uint64_t td_mol_key(int32_t barcode, int32_t fingerprint, uint64_t w, int32_t n);
+int32_t  td_mol_key_bin(uint64_t key);              /* the barcode bin a key belongs to */
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -21,6 +21,7 @@
 #include "tagdust_hip.h"
 #include "tagdust_io.h"
 #include "tagdust_census.h"
+#include "tagdust_molecules.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -67,6 +68,12 @@ typedef struct td_run_opts {
 	int32_t  unknown_barcodes;       /* --unknown-barcodes K   [0 = off]: the K most frequent barcode spellings of the reads that were not
 	                                    extracted (tagdust_census.h, the default outcomes) go to <out>_unknown_barcodes.txt */
 	int32_t  unknown_slots_log2;     /* --unknown-barcodes-slots N   [20]: the census table of every device has 2^N slots */
+	int32_t  fingerprint_seq;        /* --fingerprint-seq: ";FP:ACGT" instead of ";FP:27" in the read names, byte for byte what the
+	                                    reference's -show_finger_seq writes (td_fingerprint_text) */
+	int32_t  molecules;              /* --molecules: reads, molecules, duplication rate and duplication levels per barcode
+	                                    (tagdust_molecules.h) go to <out>_molecules.txt; one input file only */
+	int32_t  molecules_prefix;       /* --molecules-prefix P   [20]: read bases that tell molecules apart beside barcode and fingerprint, 1..32 */
+	int32_t  molecules_slots_log2;   /* --molecules-slots N    [26]: the counting table of every device has 2^N slots, 4..30 */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -87,7 +94,9 @@ const char* td_run_version(void);
  * (barcode_hmm.c:105-129: file 0 the command line's segments when there are any, else the arch file's best candidate, else R:N),
  * "barcodes in more than one file" (:141-146), the number of output reads and the output files' names (td_writer_open's), the
  * existing-output check (io.c:633-691: made when a file holds a barcode, like the reference's; skipped with `force`; with
- * --unknown-barcodes <out>_unknown_barcodes.txt is one of the output files, and the option is refused with -start / -end), the
+ * --unknown-barcodes <out>_unknown_barcodes.txt is one of the output files, and the option is refused with -start / -end; with
+ * --molecules <out>_molecules.txt is one, and the option is refused with -start / -end, with several input files -- the read and
+ * its UMI then sit in different files' contexts -- and for a read-only architecture, which has no model), the
  * multiread rule (interface.c:441-450: DUST and -ref off, with a warning, when the command line's architecture has two or more
  * R segments).  What depends on the arch file's choice is decided again by td_run_execute once the choice is made. */
 typedef struct td_run_plan_t td_run_plan_t;   /* (the function below has the plain name) */
@@ -122,6 +131,9 @@ typedef struct td_run_report {
 	int64_t  n_unknown;                       /* --unknown-barcodes: distinct spellings over all devices (0 without the option) */
 	td_census_entry* unknown;                 /* [n_unknown] by count descending, then key ascending */
 	td_census_totals unknown_totals;          /* summed over the devices */
+	td_mol_row* molecules;                    /* --molecules: [TD_NUM_BARCODE_BINS] one row per barcode bin (NULL without the option):
+	                                             one device's own summary (td_mol_get), or td_mol_summarise of the devices' merged entries */
+	td_mol_totals molecules_totals;           /* summed over the devices; molecules = distinct keys after the merge */
 } td_run_report;
 /* In the controller's order: architectures per file, statistics over each file's head, thresholds, models, the run, the log.
  * A failure before the first batch leaves no output files behind; one during the run leaves them as they are and says so.  The

@@ -172,6 +172,7 @@ extern "C" void td_ctx_destroy(td_ctx* c)
 	for (hipStream_t st : streams) if (st) (void)hipStreamSynchronize(st);
 	free_dev_model(c->dev);
 	census_release(c);
+	mol_release(c);
 	void* bufs[] = { c->d_logsum, c->d_counters, c->d_ws, c->d_art_text, c->d_art_index, c->d_art_pk, c->d_art_seq, c->d_art_hits,
 	                 c->spec.d_prune, c->d_tile_next, c->d_ws2, c->d_tile_next2 };
 	for (void* p : bufs) if (p) (void)hipFree(p);
@@ -282,6 +283,7 @@ extern "C" int td_model_upload(td_ctx* c, const td_model_desc* m)
 	for (int k = 0; k < TD_MAX_PIPELINE; k++) { c->slots[k].staged = false; c->slots[k].ran = false; }   // batches are staged per model
 	HIPCHK(c, sync_compute(c));
 	census_release(c);   // a census counts one model's segment: a new model switches it off
+	mol_release(c);      // ... and the molecule count reads one model's labels
 	free_dev_model(c->dev);
 	c->dev = dm;
 	c->model.assign(m);
@@ -366,6 +368,8 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	}
 	if (!strcmp(name, "census_active")) { *value = c->census.on; return TD_OK; }
 	if (!strcmp(name, "census_kernel_us")) return census_last_kernel_us(c, value);   // the count kernel's time of the last counted batch
+	if (!strcmp(name, "molecules_active")) { *value = c->molecules.on; return TD_OK; }
+	if (!strcmp(name, "molecules_kernel_us")) return mol_last_kernel_us(c, value);
 	if (!strcmp(name, "overlap_active")) {
 		// pipelined batches alternate between two compute streams / workspaces (off: option, generic kernel, depth 1, or HBM
 		// could not hold the second workspace)
@@ -425,6 +429,7 @@ extern "C" int td_set_window(td_ctx* c, int32_t matchstart, int32_t matchend)
 	if (matchstart == -1 && matchend == -1) { c->match_start = 0; c->match_len = 0; return TD_OK; }
 	if (matchstart < 0 || matchend <= matchstart) return fail(c, "td_set_window: need 0 <= matchstart < matchend (or -1, -1 for none)");
 	if (c->census.on) return fail(c, "td_set_window: a census is on (td_census_disable first): labels behind a window do not spell the barcode");
+	if (c->molecules.on) return fail(c, "td_set_window: a molecule count is on (td_mol_disable first): labels behind a window do not mark the read's bases");
 	c->match_start = matchstart; c->match_len = matchend - matchstart;
 	return TD_OK;
 }
@@ -838,6 +843,7 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
 	if (ka.art_n > 0 && slot_count_hits(c, s, ka.out_type) != TD_OK) return TD_FAIL;
 	if (c->census.on && mode == TD_MODE_GET_LABEL && census_count_slot(c, s, ka.out_type, ka.out_labels) != TD_OK) return TD_FAIL;
+	if (c->molecules.on && mode == TD_MODE_GET_LABEL && mol_count_slot(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
 	s.ran = true;
 	s.last_ms = -1.0f;
 	c->last_slot = (int)(&s - c->slots);

@@ -4,13 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
+#include "td_keytable.h"
+
 struct td_ctx;
 struct TdSlot;
 
 // tallies of the device table, 64 bits each, in the order of td_census_totals; behind them the compaction's cursor
 enum { TDC_ELIGIBLE = 0, TDC_COUNTED, TDC_EMPTY, TDC_LONG, TDC_N, TDC_OVERFLOW, TDC_DISTINCT, TDC_CURSOR, TDC_TALLY_WORDS };
-// linear probing looks at this many slots from the key's hash (the whole table when that is smaller): the same on every attempt
-#define TDC_PROBE_WINDOW 128
 
 struct TdCensusState {
 	bool on = false;
@@ -38,9 +40,7 @@ struct TdCensusArgs {
 	int32_t n_tiles, lmax, nw2, nw1, H;
 	int32_t segment, ordered;
 	uint32_t mask;
-	uint32_t slot_mask, window;            // 2^log2_slots - 1; slots a key looks at
-	unsigned long long* __restrict__ keys;
-	unsigned long long* __restrict__ counts;
+	TdKeyTable table;                      // td_keytable.h
 	unsigned long long* __restrict__ tallies;
 };
 
@@ -51,3 +51,8 @@ __attribute__((visibility("hidden"))) int census_count_slot(td_ctx* c, TdSlot& s
 __attribute__((visibility("hidden"))) int census_last_kernel_us(td_ctx* c, int32_t* us);
 // table and label copy freed, census off (the caller has made sure nothing of it is queued any more)
 __attribute__((visibility("hidden"))) void census_release(td_ctx* c);
+// host helpers of every result made of td_census_entry (td_molecules.hip uses them too): the order of td_census_get; a malloc'd copy
+// for td_census_free (NULL: out of memory); keys (any order, repeated) -> entries in that order
+__attribute__((visibility("hidden"))) bool census_entry_before(const td_census_entry& x, const td_census_entry& y);
+__attribute__((visibility("hidden"))) td_census_entry* census_copy_entries(const std::vector<td_census_entry>& v);
+__attribute__((visibility("hidden"))) void census_tally_keys(std::vector<uint64_t>& keys, std::vector<td_census_entry>& out);

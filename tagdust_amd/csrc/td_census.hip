@@ -18,32 +18,10 @@
 #include "../../include/tagdust_census.h"
 #include "td_ctx.h"
 
-typedef unsigned long long cs_u64;
+typedef kt_u64 cs_u64;
 
-#define CS_BLOCK 256
-#define CS_WAVES (CS_BLOCK / TD_WAVE)
-
-// splitmix64's finish: every key bit reaches the slot index
-__device__ __forceinline__ uint32_t cs_hash(cs_u64 k)
-{
-	k ^= k >> 30; k *= 0xBF58476D1CE4E5B9ull;
-	k ^= k >> 27; k *= 0x94D049BB133111EBull;
-	k ^= k >> 31;
-	return (uint32_t)(k >> 32);
-}
-
-__device__ __forceinline__ cs_u64 cs_readlane64(cs_u64 v, int lane)
-{
-	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-	const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-	return ((cs_u64)hi << 32) | lo;
-}
-
-__device__ __forceinline__ int cs_wave_sum(int v)
-{
-	for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
+#define CS_BLOCK KT_BLOCK
+#define CS_WAVES KT_WAVES
 
 __global__ __launch_bounds__(CS_BLOCK) void td_census_count_kernel(const TdCensusArgs a)
 {
@@ -99,35 +77,18 @@ __global__ __launch_bounds__(CS_BLOCK) void td_census_count_kernel(const TdCensu
 	const bool has_key = elig && !is_empty && !is_long && !has_n;
 	const cs_u64 key = has_key ? (((cs_u64)n << 56) | w) : 0ull;
 
-	// lanes with the same key leave as one: the first of them carries their number
-	int mine = 0;
-	cs_u64 todo = __builtin_amdgcn_ballot_w64(has_key);
-	while (todo) {
-		const int leader = __builtin_ctzll(todo);
-		const cs_u64 kv = cs_readlane64(key, leader);
-		const cs_u64 same = __builtin_amdgcn_ballot_w64(has_key && key == kv);
-		if (lane == leader) mine = __builtin_popcountll(same);
-		todo &= ~same;
-	}
-	// ... and the wave's distinct keys probe side by side
+	// lanes with the same key leave as one, the wave's distinct keys probe side by side (td_keytable.h)
+	const int mine = kt_wave_merge(has_key, key, lane);
 	bool placed = false, fresh = false;
-	if (mine > 0) {
-		const uint32_t h = cs_hash(key);
-		for (uint32_t i = 0; i < a.window; i++) {
-			const uint32_t slot = (h + i) & a.slot_mask;
-			cs_u64 cur = __hip_atomic_load(&a.keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (a slot's key changes once, from 0)
-			if (cur == 0ull) { cur = atomicCAS(&a.keys[slot], 0ull, key); fresh = cur == 0ull; if (fresh) cur = key; }
-			if (cur == key) { atomicAdd(&a.counts[slot], (cs_u64)mine); placed = true; break; }
-		}
-	}
+	kt_probe_add(a.table, key, mine, placed, fresh);
 	// tallies: one add per wave and tally
 	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig));
 	const int n_empty = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_empty));
 	const int n_long = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_long));
 	const int n_n = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_n));
 	const int n_fresh = __builtin_popcountll(__builtin_amdgcn_ballot_w64(fresh));
-	const int n_counted = cs_wave_sum(placed ? mine : 0);
-	const int n_over = cs_wave_sum(placed ? 0 : mine);
+	const int n_counted = kt_wave_sum(placed ? mine : 0);
+	const int n_over = kt_wave_sum(placed ? 0 : mine);
 	if (lane == 0) {
 		atomicAdd(&a.tallies[TDC_ELIGIBLE], (cs_u64)n_elig);
 		if (n_counted) atomicAdd(&a.tallies[TDC_COUNTED], (cs_u64)n_counted);
@@ -136,26 +97,6 @@ __global__ __launch_bounds__(CS_BLOCK) void td_census_count_kernel(const TdCensu
 		if (n_n) atomicAdd(&a.tallies[TDC_N], (cs_u64)n_n);
 		if (n_over) atomicAdd(&a.tallies[TDC_OVERFLOW], (cs_u64)n_over);
 		if (n_fresh) atomicAdd(&a.tallies[TDC_DISTINCT], (cs_u64)n_fresh);
-	}
-}
-
-// the occupied (key, count) pairs into a dense array: one add on the cursor per wave, the lanes behind it by their rank
-__global__ __launch_bounds__(CS_BLOCK) void td_census_compact_kernel(const cs_u64* __restrict__ keys, const cs_u64* __restrict__ counts,
-                                                                       int64_t n_slots, td_census_entry* __restrict__ out, int64_t cap,
-                                                                       cs_u64* __restrict__ cursor)
-{
-	const int lane = threadIdx.x & (TD_WAVE - 1);
-	const int64_t step = (int64_t)gridDim.x * CS_BLOCK;
-	for (int64_t i0 = (int64_t)blockIdx.x * CS_BLOCK + (threadIdx.x - lane); i0 < n_slots; i0 += step) {   // (i0 is the wave's)
-		const int64_t i = i0 + lane;
-		const cs_u64 kv = i < n_slots ? keys[i] : 0ull;
-		const cs_u64 occ = __builtin_amdgcn_ballot_w64(kv != 0ull);
-		if (occ == 0ull) continue;
-		cs_u64 base = 0ull;
-		if (lane == __builtin_ctzll(occ)) base = atomicAdd(cursor, (cs_u64)__builtin_popcountll(occ));
-		base = cs_readlane64(base, __builtin_ctzll(occ));
-		const int64_t at = (int64_t)base + __builtin_popcountll(occ & ((1ull << lane) - 1ull));
-		if (kv != 0ull && at < cap) { out[at].key = kv; out[at].count = (int64_t)counts[i]; }
 	}
 }
 
@@ -170,9 +111,30 @@ hipError_t td_census_launch_count(const TdCensusArgs& a, hipStream_t stream)
 // ---------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------
-namespace {
+// (td_census.h: shared with td_molecules.hip)
+bool census_entry_before(const td_census_entry& x, const td_census_entry& y) { return x.count != y.count ? x.count > y.count : x.key < y.key; }
 
-bool entry_before(const td_census_entry& x, const td_census_entry& y) { return x.count != y.count ? x.count > y.count : x.key < y.key; }
+td_census_entry* census_copy_entries(const std::vector<td_census_entry>& v)
+{
+	td_census_entry* p = (td_census_entry*)malloc(sizeof(td_census_entry) * (v.size() ? v.size() : 1));
+	if (p && !v.empty()) memcpy(p, v.data(), sizeof(td_census_entry) * v.size());
+	return p;
+}
+
+// keys (any order, repeated) -> entries in the order of td_census_get
+void census_tally_keys(std::vector<uint64_t>& keys, std::vector<td_census_entry>& out)
+{
+	std::sort(keys.begin(), keys.end());
+	for (size_t i = 0; i < keys.size();) {
+		size_t j = i;
+		while (j < keys.size() && keys[j] == keys[i]) j++;
+		out.push_back(td_census_entry{ keys[i], (int64_t)(j - i) });
+		i = j;
+	}
+	std::sort(out.begin(), out.end(), census_entry_before);
+}
+
+namespace {
 
 // the segment a census of this model counts: `segment` itself when it is a 'B' segment, the last 'B' segment for -1
 bool pick_segment(const td_model_desc* m, int32_t segment, int32_t& out, std::string& why)
@@ -189,26 +151,6 @@ bool pick_segment(const td_model_desc* m, int32_t segment, int32_t& out, std::st
 }
 
 bool mask_ok(uint32_t mask) { return mask != 0u && mask <= 0xFFu; }
-
-td_census_entry* copy_entries(const std::vector<td_census_entry>& v)
-{
-	td_census_entry* p = (td_census_entry*)malloc(sizeof(td_census_entry) * (v.size() ? v.size() : 1));
-	if (p && !v.empty()) memcpy(p, v.data(), sizeof(td_census_entry) * v.size());
-	return p;
-}
-
-// keys (any order, repeated) -> entries in the order of td_census_get
-void tally_keys(std::vector<uint64_t>& keys, std::vector<td_census_entry>& out)
-{
-	std::sort(keys.begin(), keys.end());
-	for (size_t i = 0; i < keys.size();) {
-		size_t j = i;
-		while (j < keys.size() && keys[j] == keys[i]) j++;
-		out.push_back(td_census_entry{ keys[i], (int64_t)(j - i) });
-		i = j;
-	}
-	std::sort(out.begin(), out.end(), entry_before);
-}
 
 }   // namespace
 
@@ -230,9 +172,9 @@ int census_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int8_
 	a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.lmax = s.lmax; a.nw2 = s.nw2; a.nw1 = s.nw1; a.H = z.H;   // (both decode kernels write labels with the stride of s.lmax)
 	a.segment = z.segment; a.ordered = z.ordered ? 1 : 0; a.mask = z.mask;
 	const uint64_t n_slots = 1ull << z.log2_slots;
-	a.slot_mask = (uint32_t)(n_slots - 1);
-	a.window = (uint32_t)std::min<uint64_t>(n_slots, TDC_PROBE_WINDOW);
-	a.keys = z.d_keys; a.counts = z.d_counts; a.tallies = z.d_tallies;
+	a.table.slot_mask = (uint32_t)(n_slots - 1);
+	a.table.window = (uint32_t)std::min<uint64_t>(n_slots, KT_PROBE_WINDOW);
+	a.table.keys = z.d_keys; a.table.counts = z.d_counts; a.tallies = z.d_tallies;
 	HIPCHK(c, hipEventRecord(z.ev_c0, s.cs));
 	HIPCHK(c, td_census_launch_count(a, s.cs));
 	HIPCHK(c, hipEventRecord(z.ev_c1, s.cs));
@@ -319,27 +261,11 @@ extern "C" int td_census_get(td_ctx* c, td_census_entry* entries, int64_t cap, i
 	HIPCHK(c, hipMemcpy(t, z.d_tallies, sizeof t, hipMemcpyDeviceToHost));
 	const int64_t distinct = (int64_t)t[TDC_DISTINCT];
 	std::vector<td_census_entry> v((size_t)distinct);
-	if (distinct > 0) {
-		td_census_entry* d_dense = nullptr;
-		HIPCHK(c, hipMalloc((void**)&d_dense, sizeof(td_census_entry) * (size_t)distinct));
-		const int64_t n_slots = (int64_t)1 << z.log2_slots;
-		int64_t blocks = (n_slots + CS_BLOCK - 1) / CS_BLOCK;
-		if (blocks > 2048) blocks = 2048;
-		hipError_t e = hipMemsetAsync(z.d_tallies + TDC_CURSOR, 0, sizeof(cs_u64), c->stream);
-		if (e == hipSuccess) {
-			hipLaunchKernelGGL(td_census_compact_kernel, dim3((unsigned)blocks), dim3(CS_BLOCK), 0, c->stream, z.d_keys, z.d_counts, n_slots,
-			                   d_dense, distinct, z.d_tallies + TDC_CURSOR);
-			e = hipGetLastError();
-		}
-		if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-		if (e == hipSuccess) e = hipMemcpy(v.data(), d_dense, sizeof(td_census_entry) * (size_t)distinct, hipMemcpyDeviceToHost);
-		cs_u64 found = 0;
-		if (e == hipSuccess) e = hipMemcpy(&found, z.d_tallies + TDC_CURSOR, sizeof found, hipMemcpyDeviceToHost);
-		(void)hipFree(d_dense);
-		if (e != hipSuccess) return fail(c, "td_census_get: compaction failed: %s", hipGetErrorString(e));
-		if ((int64_t)found != distinct) return fail(c, "td_census_get: the table holds %lld keys, its tally says %lld", (long long)found, (long long)distinct);
-	}
-	std::sort(v.begin(), v.end(), entry_before);
+	int64_t found = 0;
+	const hipError_t e = kt_compact(z.d_keys, z.d_counts, z.log2_slots, v.data(), distinct, z.d_tallies + TDC_CURSOR, c->stream, &found);
+	if (e != hipSuccess) return fail(c, "td_census_get: compaction failed: %s", hipGetErrorString(e));
+	if (found != distinct) return fail(c, "td_census_get: the table holds %lld keys, its tally says %lld", (long long)found, (long long)distinct);
+	std::sort(v.begin(), v.end(), census_entry_before);
 	const int64_t take = std::min<int64_t>(cap, distinct);
 	if (take > 0) memcpy(entries, v.data(), sizeof(td_census_entry) * (size_t)take);
 	*n = distinct;
@@ -404,9 +330,9 @@ extern "C" int td_census_host(const td_model_desc* m, int32_t segment, uint32_t 
 		else { keys.push_back(((uint64_t)cnt << 56) | w); t.counted++; }
 	}
 	std::vector<td_census_entry> v;
-	tally_keys(keys, v);
+	census_tally_keys(keys, v);
 	t.distinct = (int64_t)v.size();
-	if (!(*entries = copy_entries(v))) return fail(nullptr, "td_census_host: out of memory");
+	if (!(*entries = census_copy_entries(v))) return fail(nullptr, "td_census_host: out of memory");
 	*n = (int64_t)v.size();
 	if (totals) *totals = t;
 	return TD_OK;
@@ -424,8 +350,8 @@ extern "C" int td_census_merge(const td_census_entry* a, int64_t na, const td_ce
 		if (!v.empty() && v.back().key == e.key) v.back().count += e.count;
 		else v.push_back(e);
 	}
-	std::sort(v.begin(), v.end(), entry_before);
-	if (!(*out = copy_entries(v))) return fail(nullptr, "td_census_merge: out of memory");
+	std::sort(v.begin(), v.end(), census_entry_before);
+	if (!(*out = census_copy_entries(v))) return fail(nullptr, "td_census_merge: out of memory");
 	*n = (int64_t)v.size();
 	return TD_OK;
 }

@@ -12,6 +12,7 @@
 #include "td_stage.h"
 #include "td_host_inner.h"
 #include "td_census.h"
+#include "td_molecules.h"
 
 #define TD_HIDDEN __attribute__((visibility("hidden")))
 #define TD_MAX_PIPELINE 4
@@ -188,6 +189,7 @@ struct td_ctx {
 	int32_t art_n = 0, art_fe = 0, art_threads = 1;
 	unsigned long long* d_art_hits = nullptr;   // [art_n] reads per artifact sequence (td_artifact_hits_get)
 	TdCensusState census;       // include/tagdust_census.h: off unless td_census_enable switched it on
+	TdMolState molecules;       // include/tagdust_molecules.h: off unless td_mol_enable switched it on
 	int64_t win_first = 0, win_total = 0;   // td_set_batch_window
 	int32_t match_start = 0, match_len = 0;  // td_set_window (-start / -end); match_len = 0: whole reads
 	// batches: slot 0 is the resident batch of the synchronous calls; td_submit rotates over pipeline_depth slots

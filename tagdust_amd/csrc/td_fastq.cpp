@@ -191,6 +191,7 @@ struct td_writer {
 	std::vector<FILE*> files;
 	int num_alternatives = 2;
 	int num_out_reads = 1;
+	bool fingerprint_text = false;   // td_writer_set_fingerprint_text
 };
 
 void td_writer_file_names(const char* prefix, const td_arch* a, std::vector<std::string>& names, int* num_alternatives)
@@ -236,12 +237,29 @@ extern "C" int td_writer_open(const char* prefix, const td_arch* a, td_writer** 
 	return TD_OK;
 }
 
+extern "C" int td_fingerprint_text(int32_t fingerprint, char buf[256])
+{
+	if (!buf) return 0;
+	const int len = fingerprint & 0xFF;
+	int32_t key = fingerprint >> 8;   // (arithmetic, like the reference's int)
+	buf[len] = 0;
+	for (int i = 0; i < len; i++) { buf[len - i - 1] = "ACGT"[key & 0x3]; key >>= 2; }
+	return len;
+}
+
+extern "C" int td_writer_set_fingerprint_text(td_writer* w, int on)
+{
+	if (!w) return TD_FAIL;
+	w->fingerprint_text = on != 0;
+	return TD_OK;
+}
+
 // formats reads [lo, hi) into one buffer per output file (io.c:917-1001)
 static void format_range(const td_writer* w, const td_reads* rd, const td_read_result* res, const uint8_t* seq_out,
                          int64_t lo, int64_t hi, std::vector<std::string>* bufs)
 {
 	static const char alphabet[] = "ACGTNN";
-	char head[64];
+	char head[64], finger[256];
 	std::string seq, qual;
 	for (int64_t i = lo; i < hi; i++) {
 		size_t f; // io.c:923-934
@@ -254,7 +272,10 @@ static void format_range(const td_writer* w, const td_reads* rd, const td_read_r
 			if (f >= bufs->size()) return;
 			std::string& b = (*bufs)[f];
 			b += '@'; b.append(rd->text + rd->name_off[i], (size_t)rd->name_len[i]);
-			if (res[i].fingerprint != -1) { snprintf(head, sizeof head, ";FP:%d", res[i].fingerprint); b += head; }
+			if (res[i].fingerprint != -1) {
+				if (w->fingerprint_text) { (void)td_fingerprint_text(res[i].fingerprint, finger); b += ";FP:"; b += finger; }   // io.c:960-963
+				else { snprintf(head, sizeof head, ";FP:%d", res[i].fingerprint); b += head; }
+			}
 			snprintf(head, sizeof head, ";RQ:%0.2f\n", (double)res[i].mapq); b += head;
 			b += seq; b += "\n+\n"; b += qual; b += '\n';
 		};

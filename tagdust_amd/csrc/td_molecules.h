@@ -1,0 +1,52 @@
+// td_molecules.h -- the molecule count (include/tagdust_molecules.h) inside a context: its state, and what td_api.hip calls.  The
+// kernels and every td_mol_* entry point are in td_molecules.hip; the table is td_keytable.h's.  Nothing here is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "td_keytable.h"
+
+struct td_ctx;
+struct TdSlot;
+
+// tallies of the device table, 64 bits each, in the order of td_mol_totals; behind them the compaction's cursor
+enum { TDM_ELIGIBLE = 0, TDM_COUNTED, TDM_EMPTY, TDM_N, TDM_OVERFLOW, TDM_MOLECULES, TDM_CURSOR, TDM_TALLY_WORDS };
+// words of a barcode bin's summary row: reads, molecules, ten levels (td_mol_row)
+#define TDM_ROW_WORDS 12
+
+struct TdMolState {
+	bool on = false;
+	int32_t prefix = 0;         // P: read bases that belong to the key
+	int32_t log2_slots = 0;
+	int32_t H = 0;
+	uint64_t r_segs = 0;        // bit j: segment j is an 'R' segment
+	int32_t* d_label = nullptr;               // [H] model.label, the count's own copy
+	unsigned long long* d_keys = nullptr;     // [2^log2_slots], 0 = empty
+	unsigned long long* d_counts = nullptr;   // [2^log2_slots]
+	unsigned long long* d_tallies = nullptr;  // [TDM_TALLY_WORDS]
+	unsigned long long* d_rows = nullptr;     // [TD_NUM_BARCODE_BINS][TDM_ROW_WORDS] the summary sweep's result
+	hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   // around the last count launch (option "molecules_kernel_us")
+};
+
+struct TdMolArgs {
+	const uint32_t* __restrict__ packed;      // [n_tiles][nw2 + nw1][64]  2-bit words then N-mask words
+	const int32_t*  __restrict__ lens;        // [n_tiles*64]
+	const int32_t*  __restrict__ out_type;    // [n_tiles*64]  final outcomes of the decode launch
+	const int32_t*  __restrict__ out_barcode; // [n_tiles*64]
+	const int32_t*  __restrict__ out_finger;  // [n_tiles*64]
+	const int8_t*   __restrict__ labels;      // [n_tiles][lmax + 1][64]
+	const int32_t*  __restrict__ label;       // [H] model.label
+	int64_t n_reads;
+	uint64_t r_segs;
+	int32_t n_tiles, lmax, nw2, nw1, H, prefix;
+	TdKeyTable table;
+	unsigned long long* __restrict__ tallies;
+};
+
+// the count of one decoded slot, queued on its compute stream (td_api.hip calls it behind the decode launch while the count is on)
+__attribute__((visibility("hidden"))) int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode,
+                                                         const int32_t* out_finger, const int8_t* labels);
+// option "molecules_kernel_us" of td_get_option: the count kernel's time of the last counted batch (waits for it)
+__attribute__((visibility("hidden"))) int mol_last_kernel_us(td_ctx* c, int32_t* us);
+// table and label copy freed, count off (the caller has made sure nothing of it is queued any more)
+__attribute__((visibility("hidden"))) void mol_release(td_ctx* c);

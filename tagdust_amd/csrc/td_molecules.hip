@@ -1,0 +1,364 @@
+// td_molecules.hip -- the molecule count (include/tagdust_molecules.h): how many molecules each barcode yielded.
+//
+// Behind every TD_MODE_GET_LABEL launch of a context with the count on, one small kernel reads what the decode kernel left in
+// device order -- the outcome, barcode and fingerprint of every read, the lane-interleaved label bytes, the packed bases with their
+// N mask -- builds each extracted read's key from its barcode, its fingerprint and the first P bases of its read segments, and
+// counts it in the table of td_keytable.h, the census's.  One read per lane, one tile per wave, like the decode kernels.  Here
+// almost every read is eligible and almost every key is its own: the cost is the table's random traffic (a load, mostly a CAS, an
+// add per read), not the heavy hitter the census merges away -- the merge of equal keys in a wave stays, PCR copies sit together
+// often enough.  A second kernel sweeps the table into one summary row per barcode bin (td_mol_get).  td_mol_host is the same
+// definition over host arrays (no GPU), td_mol_summarise the same summary from entries.
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/tagdust_molecules.h"
+#include "td_ctx.h"
+
+#define KEY_LOW_MASK 0x00FFFFFFFFFFFFFFull
+
+// the key of tagdust_molecules.h (host and device: the same integer arithmetic)
+__host__ __device__ __forceinline__ kt_u64 mol_key(int32_t barcode, int32_t fingerprint, kt_u64 w, int n)
+{
+	const kt_u64 a = kt_mix(((kt_u64)(uint32_t)fingerprint << 8) | (kt_u64)n);
+	kt_u64 low = kt_mix(w ^ a) & KEY_LOW_MASK;
+	if (low == 0ull) low = 1ull;
+	const kt_u64 bin = barcode == -1 ? 0ull : (kt_u64)(barcode & 0xFF);
+	return (bin << 56) | low;
+}
+
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_count_kernel(const TdMolArgs a)
+{
+	// per label: 1 = it belongs to an 'R' segment
+	__shared__ uint8_t s_r[128];
+	for (int h = threadIdx.x; h < 128; h += KT_BLOCK) {
+		uint8_t v = 0;
+		if (h < a.H) { const int seg = a.label[h] & 0xFFFF; v = seg < 64 ? (uint8_t)((a.r_segs >> seg) & 1ull) : 0; }
+		s_r[h] = v;
+	}
+	__syncthreads();
+	const int lane = threadIdx.x & (TD_WAVE - 1);
+	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
+	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
+	const int64_t k = (int64_t)tile * TD_WAVE + lane;
+	bool elig = false;
+	if (k < a.n_reads) elig = ((uint32_t)a.out_type[k] & 0xFFu) == (uint32_t)TD_EXTRACT_SUCCESS;   // the outcome first: the other lanes read nothing more
+	if (__builtin_amdgcn_ballot_w64(elig) == 0ull) return;
+	int len = 0, barcode = -1, finger = -1;
+	if (elig) { len = a.lens[k]; barcode = a.out_barcode[k]; finger = a.out_finger[k]; }
+	int tmax = len;
+	for (int o = 32; o >= 1; o >>= 1) { const int t2 = __shfl_xor(tmax, o); tmax = t2 > tmax ? t2 : tmax; }
+	if (tmax > a.lmax) tmax = a.lmax;                 // (the batch's longest read: every index below stays inside the tile's arrays)
+	const uint32_t* pk = a.packed + (int64_t)tile * (a.nw2 + a.nw1) * TD_WAVE + lane;
+	const int8_t* lb = a.labels + (int64_t)tile * (a.lmax + 1) * TD_WAVE + lane;
+
+	kt_u64 w = 0ull;
+	int n = 0;
+	bool has_n = false, active = elig && len > 0;
+	uint32_t w2 = 0u, wn = 0u;                        // the 16 bases / the 32 N flags around p (a lane is active from p = 0 on)
+	for (int p = 0; p < tmax; p++) {                  // label bytes only until P read bases are collected or the read ends
+		if (__builtin_amdgcn_ballot_w64(active) == 0ull) break;
+		if (active) {
+			if ((p & 15) == 0) w2 = pk[(p >> 4) * TD_WAVE];
+			if ((p & 31) == 0) wn = pk[(a.nw2 + (p >> 5)) * TD_WAVE];
+			const uint32_t lab = (uint8_t)lb[(p + 1) * TD_WAVE];     // labels[p + 1] belongs to base p
+			if (lab < 128u && s_r[lab]) {
+				w = (w << 2) | (kt_u64)((w2 >> (2 * (p & 15))) & 3u);
+				has_n = has_n || ((wn >> (p & 31)) & 1u) != 0u;
+				if (++n >= a.prefix) active = false;
+			}
+			if (p + 1 >= len) active = false;
+		}
+	}
+	const bool is_empty = elig && n == 0;
+	const bool is_n = elig && n > 0 && has_n;
+	const bool has_key = elig && n > 0 && !has_n;
+	const kt_u64 key = has_key ? mol_key(barcode, finger, w, n) : 0ull;
+
+	// lanes with the same key leave as one, the wave's distinct keys probe side by side (td_keytable.h)
+	const int mine = kt_wave_merge(has_key, key, lane);
+	bool placed = false, fresh = false;
+	kt_probe_add(a.table, key, mine, placed, fresh);
+	// tallies: one add per wave and tally
+	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig));
+	const int n_empty = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_empty));
+	const int n_n = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_n));
+	const int n_fresh = __builtin_popcountll(__builtin_amdgcn_ballot_w64(fresh));
+	const int n_counted = kt_wave_sum(placed ? mine : 0);
+	const int n_over = kt_wave_sum(placed ? 0 : mine);
+	if (lane == 0) {
+		atomicAdd(&a.tallies[TDM_ELIGIBLE], (kt_u64)n_elig);
+		if (n_counted) atomicAdd(&a.tallies[TDM_COUNTED], (kt_u64)n_counted);
+		if (n_empty) atomicAdd(&a.tallies[TDM_EMPTY], (kt_u64)n_empty);
+		if (n_n) atomicAdd(&a.tallies[TDM_N], (kt_u64)n_n);
+		if (n_over) atomicAdd(&a.tallies[TDM_OVERFLOW], (kt_u64)n_over);
+		if (n_fresh) atomicAdd(&a.tallies[TDM_MOLECULES], (kt_u64)n_fresh);
+	}
+}
+
+// The table into one row per barcode bin.  Nearly all slots of a run fall into a handful of bins: a global atomic per slot would
+// queue on three or four addresses ("The counters"), so a workgroup sums in LDS -- 256 bins x 12 words of 8
+// bytes, 24 KB -- and adds what is not zero to the global rows once.
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_summary_kernel(const kt_u64* __restrict__ keys, const kt_u64* __restrict__ counts,
+                                                                   int64_t n_slots, kt_u64* __restrict__ rows)
+{
+	__shared__ kt_u64 s_rows[TD_NUM_BARCODE_BINS * TDM_ROW_WORDS];
+	for (int q = threadIdx.x; q < TD_NUM_BARCODE_BINS * TDM_ROW_WORDS; q += KT_BLOCK) s_rows[q] = 0ull;
+	__syncthreads();
+	const int64_t step = (int64_t)gridDim.x * KT_BLOCK;
+	for (int64_t i = (int64_t)blockIdx.x * KT_BLOCK + threadIdx.x; i < n_slots; i += step) {
+		const kt_u64 kv = keys[i];
+		if (kv == 0ull) continue;
+		const kt_u64 cnt = counts[i];
+		if (cnt == 0ull) continue;                    // (a claimed slot always has its add behind it once the stream is idle)
+		kt_u64* row = s_rows + (int)(kv >> 56) * TDM_ROW_WORDS;
+		const int level = (int)(cnt < (kt_u64)TD_MOL_LEVELS ? cnt : (kt_u64)TD_MOL_LEVELS) - 1;
+		atomicAdd(&row[0], cnt);
+		atomicAdd(&row[1], 1ull);
+		atomicAdd(&row[2 + level], 1ull);
+	}
+	__syncthreads();
+	for (int q = threadIdx.x; q < TD_NUM_BARCODE_BINS * TDM_ROW_WORDS; q += KT_BLOCK)
+		if (s_rows[q] != 0ull) atomicAdd(&rows[q], s_rows[q]);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+bool prefix_ok(int32_t p) { return p >= 1 && p <= TD_MOL_MAX_PREFIX; }
+
+void totals_from(const kt_u64* t, td_mol_totals* out)
+{
+	out->eligible = (int64_t)t[TDM_ELIGIBLE]; out->counted = (int64_t)t[TDM_COUNTED]; out->skipped_empty = (int64_t)t[TDM_EMPTY];
+	out->skipped_n = (int64_t)t[TDM_N]; out->overflow = (int64_t)t[TDM_OVERFLOW]; out->molecules = (int64_t)t[TDM_MOLECULES];
+}
+
+}   // namespace
+
+void mol_release(td_ctx* c)
+{
+	TdMolState& z = c->molecules;
+	void* p[] = { z.d_label, z.d_keys, z.d_counts, z.d_tallies, z.d_rows };
+	for (void* q : p) if (q) (void)hipFree(q);
+	hipEvent_t ev[] = { z.ev_c0, z.ev_c1 };
+	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+	z = TdMolState();
+}
+
+int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
+{
+	const TdMolState& z = c->molecules;
+	TdMolArgs a{};
+	a.packed = s.d_packed; a.lens = s.d_lens; a.out_type = out_type; a.out_barcode = out_barcode; a.out_finger = out_finger;
+	a.labels = labels; a.label = z.d_label;
+	a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.lmax = s.lmax; a.nw2 = s.nw2; a.nw1 = s.nw1; a.H = z.H;   // (both decode kernels write labels with the stride of s.lmax)
+	a.r_segs = z.r_segs; a.prefix = z.prefix;
+	const uint64_t n_slots = 1ull << z.log2_slots;
+	a.table.slot_mask = (uint32_t)(n_slots - 1);
+	a.table.window = (uint32_t)std::min<uint64_t>(n_slots, KT_PROBE_WINDOW);
+	a.table.keys = z.d_keys; a.table.counts = z.d_counts; a.tallies = z.d_tallies;
+	HIPCHK(c, hipEventRecord(z.ev_c0, s.cs));
+	if (a.n_tiles > 0) {
+		const unsigned blocks = (unsigned)((a.n_tiles + KT_WAVES - 1) / KT_WAVES);
+		hipLaunchKernelGGL(td_mol_count_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
+		HIPCHK(c, hipGetLastError());
+	}
+	HIPCHK(c, hipEventRecord(z.ev_c1, s.cs));
+	// the finish kernel waits for ev_hits: a slot whose batch has been waited for is no longer read by this count either
+	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));
+	s.hits_queued = true;
+	return TD_OK;
+}
+
+extern "C" int td_mol_enable(td_ctx* c, int32_t prefix_bases, int32_t log2_slots)
+{
+	if (!c) return TD_FAIL;
+	if (!c->have_model) return fail(c, "td_mol_enable: no model uploaded");
+	for (int k = 0; k < TD_MAX_PIPELINE; k++)
+		if (c->slots[k].ticket) return fail(c, "td_mol_enable: td_submit tickets are outstanding (td_wait them first)");
+	if (!prefix_ok(prefix_bases)) return fail(c, "td_mol_enable: prefix_bases = %d (1..%d supported)", prefix_bases, TD_MOL_MAX_PREFIX);
+	if (log2_slots == 0) log2_slots = TD_MOL_DEFAULT_LOG2_SLOTS;
+	if (log2_slots < 4 || log2_slots > 30) return fail(c, "td_mol_enable: log2_slots = %d (4..30 supported, 0 = the default of %d)", log2_slots, TD_MOL_DEFAULT_LOG2_SLOTS);
+	if (c->match_len > 0) return fail(c, "td_mol_enable: a -start/-end window is set (td_set_window): labels behind a window do not mark the read's bases");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	mol_release(c);
+	TdMolState& z = c->molecules;
+	const td_model_desc& m = c->model.d;
+	const size_t n_slots = (size_t)1 << log2_slots;
+	const size_t row_bytes = sizeof(kt_u64) * TD_NUM_BARCODE_BINS * TDM_ROW_WORDS;
+	bool ok = hipMalloc((void**)&z.d_label, sizeof(int32_t) * (size_t)m.H) == hipSuccess &&
+	          hipMalloc((void**)&z.d_keys, sizeof(kt_u64) * n_slots) == hipSuccess &&
+	          hipMalloc((void**)&z.d_counts, sizeof(kt_u64) * n_slots) == hipSuccess &&
+	          hipMalloc((void**)&z.d_tallies, sizeof(kt_u64) * TDM_TALLY_WORDS) == hipSuccess &&
+	          hipMalloc((void**)&z.d_rows, row_bytes) == hipSuccess &&
+	          hipMemcpy(z.d_label, m.label, sizeof(int32_t) * (size_t)m.H, hipMemcpyHostToDevice) == hipSuccess &&
+	          hipMemset(z.d_keys, 0, sizeof(kt_u64) * n_slots) == hipSuccess &&
+	          hipMemset(z.d_counts, 0, sizeof(kt_u64) * n_slots) == hipSuccess &&
+	          hipMemset(z.d_tallies, 0, sizeof(kt_u64) * TDM_TALLY_WORDS) == hipSuccess &&
+	          hipEventCreate(&z.ev_c0) == hipSuccess && hipEventCreate(&z.ev_c1) == hipSuccess;
+	if (!ok) {
+		const std::string e = hipGetErrorString(hipGetLastError());
+		mol_release(c);
+		return fail(c, "td_mol_enable: a table of 2^%d slots could not be set up: %s", log2_slots, e.c_str());
+	}
+	z.prefix = prefix_bases; z.log2_slots = log2_slots; z.H = m.H;
+	z.r_segs = 0;
+	for (int j = 0; j < m.S && j < 64; j++) if (m.seg_type[j] == 'R') z.r_segs |= 1ull << j;
+	z.on = true;
+	return TD_OK;
+}
+
+extern "C" int td_mol_disable(td_ctx* c)
+{
+	if (!c) return TD_FAIL;
+	if (!c->molecules.on) return TD_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	mol_release(c);
+	return TD_OK;
+}
+
+extern "C" int td_mol_reset(td_ctx* c)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (!z.on) return fail(c, "td_mol_reset: the molecule count is off (td_mol_enable)");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));   // (counts of pipelined batches may still be queued, on either compute stream)
+	const size_t n_slots = (size_t)1 << z.log2_slots;
+	HIPCHK(c, hipMemsetAsync(z.d_keys, 0, sizeof(kt_u64) * n_slots, c->stream));
+	HIPCHK(c, hipMemsetAsync(z.d_counts, 0, sizeof(kt_u64) * n_slots, c->stream));
+	HIPCHK(c, hipMemsetAsync(z.d_tallies, 0, sizeof(kt_u64) * TDM_TALLY_WORDS, c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	return TD_OK;
+}
+
+extern "C" int td_mol_entries(td_ctx* c, td_census_entry* entries, int64_t cap, int64_t* n, td_mol_totals* totals)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (!z.on) return fail(c, "td_mol_entries: the molecule count is off (td_mol_enable)");
+	if (cap < 0 || (cap > 0 && !entries) || !n) return fail(c, "td_mol_entries: bad arguments");
+	*n = 0;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	kt_u64 t[TDM_TALLY_WORDS];
+	HIPCHK(c, hipMemcpy(t, z.d_tallies, sizeof t, hipMemcpyDeviceToHost));
+	const int64_t distinct = (int64_t)t[TDM_MOLECULES];
+	std::vector<td_census_entry> v((size_t)distinct);
+	int64_t found = 0;
+	const hipError_t e = kt_compact(z.d_keys, z.d_counts, z.log2_slots, v.data(), distinct, z.d_tallies + TDM_CURSOR, c->stream, &found);
+	if (e != hipSuccess) return fail(c, "td_mol_entries: compaction failed: %s", hipGetErrorString(e));
+	if (found != distinct) return fail(c, "td_mol_entries: the table holds %lld keys, its tally says %lld", (long long)found, (long long)distinct);
+	std::sort(v.begin(), v.end(), census_entry_before);
+	const int64_t take = std::min<int64_t>(cap, distinct);
+	if (take > 0) memcpy(entries, v.data(), sizeof(td_census_entry) * (size_t)take);
+	*n = distinct;
+	if (totals) totals_from(t, totals);
+	return TD_OK;
+}
+
+extern "C" int td_mol_get(td_ctx* c, td_mol_row rows[TD_NUM_BARCODE_BINS], td_mol_totals* totals)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (!z.on) return fail(c, "td_mol_get: the molecule count is off (td_mol_enable)");
+	if (!rows) return fail(c, "td_mol_get: bad arguments");
+	static_assert(sizeof(td_mol_row) == sizeof(kt_u64) * TDM_ROW_WORDS, "td_mol_row is the device row");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	const int64_t n_slots = (int64_t)1 << z.log2_slots;
+	int64_t blocks = (n_slots + KT_BLOCK - 1) / KT_BLOCK;
+	if (blocks > 1024) blocks = 1024;
+	HIPCHK(c, hipMemsetAsync(z.d_rows, 0, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, c->stream));
+	hipLaunchKernelGGL(td_mol_summary_kernel, dim3((unsigned)blocks), dim3(KT_BLOCK), 0, c->stream, z.d_keys, z.d_counts, n_slots, z.d_rows);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipMemcpy(rows, z.d_rows, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, hipMemcpyDeviceToHost));
+	if (totals) {
+		kt_u64 t[TDM_TALLY_WORDS];
+		HIPCHK(c, hipMemcpy(t, z.d_tallies, sizeof t, hipMemcpyDeviceToHost));
+		totals_from(t, totals);
+	}
+	return TD_OK;
+}
+
+// the count kernel's time of the last batch, for tools/molecules_bench.py (option "molecules_kernel_us" of td_get_option)
+int mol_last_kernel_us(td_ctx* c, int32_t* us)
+{
+	TdMolState& z = c->molecules;
+	if (!z.on) return fail(c, "td_get_option: molecules_kernel_us: the molecule count is off");
+	HIPCHK(c, hipSetDevice(c->device));
+	float ms = 0.0f;
+	if (hipEventSynchronize(z.ev_c1) != hipSuccess || hipEventElapsedTime(&ms, z.ev_c0, z.ev_c1) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(c, "td_get_option: molecules_kernel_us: no batch has been counted yet");
+	}
+	*us = (int32_t)(ms * 1000.0f + 0.5f);
+	return TD_OK;
+}
+
+extern "C" int td_mol_summarise(const td_census_entry* entries, int64_t n, td_mol_row rows[TD_NUM_BARCODE_BINS])
+{
+	if (!rows || n < 0 || (n > 0 && !entries)) return fail(nullptr, "td_mol_summarise: bad arguments");
+	memset(rows, 0, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS);
+	for (int64_t i = 0; i < n; i++) {
+		if (entries[i].count <= 0) continue;
+		td_mol_row& r = rows[td_mol_key_bin(entries[i].key)];
+		r.reads += entries[i].count;
+		r.molecules++;
+		r.levels[std::min<int64_t>(entries[i].count, TD_MOL_LEVELS) - 1]++;
+	}
+	return TD_OK;
+}
+
+extern "C" int td_mol_host(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                           const td_read_result* res, const int8_t* labels, td_census_entry** entries, int64_t* n, td_mol_totals* totals)
+{
+	if (entries) *entries = nullptr;
+	if (n) *n = 0;
+	if (!m || m->S < 1 || m->H < 1 || !m->seg_type || !m->label) return fail(nullptr, "td_mol_host: no model");
+	if (!prefix_ok(prefix_bases)) return fail(nullptr, "td_mol_host: prefix_bases = %d (1..%d supported)", prefix_bases, TD_MOL_MAX_PREFIX);
+	if (!entries || !n || n_reads < 0 || (n_reads > 0 && (!offs || !res || !labels || !codes))) return fail(nullptr, "td_mol_host: bad arguments");
+	td_mol_totals t{};
+	std::vector<uint64_t> keys;
+	for (int64_t i = 0; i < n_reads; i++) {
+		if (((uint32_t)res[i].read_type & 0xFFu) != (uint32_t)TD_EXTRACT_SUCCESS) continue;
+		t.eligible++;
+		const int64_t len = offs[i + 1] - offs[i];
+		const int8_t* lab = labels + offs[i] + i;
+		const uint8_t* seq = codes + offs[i];
+		uint64_t w = 0;
+		int cnt = 0;
+		bool has_n = false;
+		for (int64_t p = 0; p < len && cnt < prefix_bases; p++) {
+			const int l = lab[p + 1];
+			if (l < 0 || l >= m->H) continue;
+			const int seg = m->label[l] & 0xFFFF;
+			if (seg >= m->S || m->seg_type[seg] != 'R') continue;
+			cnt++;
+			if (seq[p] > 3) has_n = true;
+			w = (w << 2) | (uint64_t)(seq[p] & 3u);
+		}
+		if (cnt == 0) t.skipped_empty++;
+		else if (has_n) t.skipped_n++;
+		else { keys.push_back(mol_key(res[i].barcode, res[i].fingerprint, w, cnt)); t.counted++; }
+	}
+	std::vector<td_census_entry> v;
+	census_tally_keys(keys, v);
+	t.molecules = (int64_t)v.size();
+	if (!(*entries = census_copy_entries(v))) return fail(nullptr, "td_mol_host: out of memory");
+	*n = (int64_t)v.size();
+	if (totals) *totals = t;
+	return TD_OK;
+}
+
+extern "C" uint64_t td_mol_key(int32_t barcode, int32_t fingerprint, uint64_t w, int32_t n) { return mol_key(barcode, fingerprint, w, n); }
+extern "C" int32_t td_mol_key_bin(uint64_t key) { return (int32_t)(key >> 56); }

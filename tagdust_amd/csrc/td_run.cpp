@@ -168,7 +168,7 @@ bool read_arch_file(const char* path, ArchFile& af, std::string& why)
 struct OptSpec { const char* name; int arg; int id; };
 enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
-       O_UNKNOWN, O_UNKNOWN_SLOTS,
+       O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS,
        O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
@@ -193,6 +193,8 @@ const OptSpec kOwnOpts[] = {
 	{ "devices", 1, O_DEVICES }, { "rtest", 0, O_RTEST }, { "host-threads", 1, O_HOST_THREADS }, { "batch-reads", 1, O_BATCH_READS },
 	{ "sync-compile", 0, O_SYNC_COMPILE }, { "stats-on-host", 0, O_STATS_ON_HOST }, { "force", 0, O_FORCE }, { "dry-run", 0, O_DRY_RUN },
 	{ "unknown-barcodes", 1, O_UNKNOWN }, { "unknown-barcodes-slots", 1, O_UNKNOWN_SLOTS },
+	{ "fingerprint-seq", 0, O_FINGER_SEQ }, { "molecules", 0, O_MOLECULES }, { "molecules-prefix", 1, O_MOLECULES_PREFIX },
+	{ "molecules-slots", 1, O_MOLECULES_SLOTS },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -231,6 +233,8 @@ extern "C" td_run_opts* td_run_opts_new(void)
 	o->seed = 0;                        // :124
 	o->n_devices = 1; o->devices[0] = 0;
 	o->unknown_slots_log2 = 20;
+	o->molecules_prefix = TD_MOL_DEFAULT_PREFIX;
+	o->molecules_slots_log2 = TD_MOL_DEFAULT_LOG2_SLOTS;
 	return o;
 }
 
@@ -278,7 +282,13 @@ extern "C" const char* td_run_usage(void)
 	       "\t--dry-run         print the decisions of the run and stop\n"
 	       "\t--unknown-barcodes K        the K most frequent barcode spellings of the reads that were not extracted,\n"
 	       "\t                            into <output prefix>_unknown_barcodes.txt\n"
-	       "\t--unknown-barcodes-slots N  slots of the counting table on every device, as a power of two [20]\n\n";
+	       "\t--unknown-barcodes-slots N  slots of the counting table on every device, as a power of two [20]\n"
+	       "\t--fingerprint-seq           fingerprints as bases in the read names, \";FP:ACGT\" (what the reference's -show_finger_seq\n"
+	       "\t                            writes; that spelling itself is not accepted)\n"
+	       "\t--molecules                 reads, molecules, duplication rate and duplication levels per barcode, counted by\n"
+	       "\t                            barcode, fingerprint and start of the read, into <output prefix>_molecules.txt\n"
+	       "\t--molecules-prefix P        bases of the read that belong to a molecule's identity, 1..32 [20]\n"
+	       "\t--molecules-slots N         slots of the counting table on every device, as a power of two, 4..30 [26]\n\n";
 }
 
 extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
@@ -344,12 +354,18 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 		case O_DRY_RUN: o->dry_run = 1; break;
 		case O_UNKNOWN: o->unknown_barcodes = atoi(v); if (o->unknown_barcodes < 1) return bad("--unknown-barcodes: need a number of lines K >= 1"); break;
 		case O_UNKNOWN_SLOTS: o->unknown_slots_log2 = atoi(v); break;
+		case O_FINGER_SEQ: o->fingerprint_seq = 1; break;
+		case O_MOLECULES: o->molecules = 1; break;
+		case O_MOLECULES_PREFIX: o->molecules_prefix = atoi(v); break;
+		case O_MOLECULES_SLOTS: o->molecules_slots_log2 = atoi(v); break;
 		default: return bad("unknown option " + a);
 		}
 	}
 	if (o->num_threads < 1) return bad("option -t: need at least one thread");
 	if (o->host_threads < 0 || o->batch_reads < 0) return bad("--host-threads / --batch-reads: negative value");
 	if (o->unknown_slots_log2 < 4 || o->unknown_slots_log2 > 26) return bad("--unknown-barcodes-slots: need 4..26 (the table has 2^N slots)");
+	if (o->molecules_prefix < 1 || o->molecules_prefix > TD_MOL_MAX_PREFIX) return bad("--molecules-prefix: need 1..32 bases");
+	if (o->molecules_slots_log2 < 4 || o->molecules_slots_log2 > 30) return bad("--molecules-slots: need 4..30 (the table has 2^N slots)");
 	if ((int)files.size() > TD_RUN_MAX_FILES) return bad("more than 8 input files");
 	o->infile = (char**)calloc(files.size() ? files.size() : 1, sizeof(char*));
 	for (auto& f : files) o->infile[o->n_infiles++] = dup_str(f.c_str());
@@ -386,6 +402,7 @@ std::vector<std::string> cmdline_segments(const td_run_opts* o)
 }
 
 std::string unknown_file_name(const td_run_opts* o) { return std::string(o->outfile) + "_unknown_barcodes.txt"; }
+std::string molecules_file_name(const td_run_opts* o) { return std::string(o->outfile) + "_molecules.txt"; }
 
 // what the controller decides once every file's architecture is known (barcode_hmm.c:130-159): TD_FAIL with the reference's message
 int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& archs, int& bar_file, int& num_out_reads, std::vector<std::string>& names)
@@ -404,6 +421,10 @@ int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& arch
 	if (o->unknown_barcodes > 0) {
 		if (bar_file < 0) return run_fail("--unknown-barcodes: no input file's architecture has a barcode segment.");
 		names.push_back(unknown_file_name(o));
+	}
+	if (o->molecules) {
+		if (archs.size() == 1 && is_read_only(archs[0])) return run_fail("--molecules: the architecture is a single read segment: there is no model whose labels mark a barcode or a fingerprint.");
+		names.push_back(molecules_file_name(o));
 	}
 	if (bar_file >= 0 && !o->force)   // check_for_existing_demultiplexed_files_multiple, io.c:633-691 (made for the barcode file only)
 		for (auto& n : names)
@@ -430,6 +451,10 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	if (o->arch_file && !file_exists(o->arch_file)) return run_fail("ERROR: Arch file:%s does not exists.", o->arch_file);
 	if (o->unknown_barcodes > 0 && (o->matchstart != -1 || o->matchend != -1))
 		return run_fail("--unknown-barcodes cannot be combined with -start / -end: labels behind a window do not spell the barcode.");
+	if (o->molecules && o->n_infiles != 1)
+		return run_fail("--molecules needs exactly one input file (%d given): a read and its fingerprint in different files are not joined.", o->n_infiles);
+	if (o->molecules && (o->matchstart != -1 || o->matchend != -1))
+		return run_fail("--molecules cannot be combined with -start / -end: labels behind a window do not mark the read's bases.");
 	for (int k = 0; k < o->n_infiles; k++)
 		if (strcmp(o->infile[k], "-") != 0 && !file_exists(o->infile[k])) return run_fail("ERROR: Input file:%s does not exists.", o->infile[k]);
 	// interface.c:419-450: two or more R segments in the command line's architecture switch DUST and -ref off
@@ -614,6 +639,7 @@ extern "C" void td_run_report_clear(td_run_report* r)
 	if (r->artifact_names) for (int j = 0; j < r->n_artifacts; j++) free(r->artifact_names[j]);
 	free(r->artifact_names); free(r->artifact_hits); free(r->log);
 	td_census_free(r->unknown);
+	free(r->molecules);
 	for (int k = 0; k < TD_RUN_MAX_FILES; k++) free(r->architectures[k]);
 	memset(r, 0, sizeof *r);
 }
@@ -737,6 +763,7 @@ struct Run {
 	int execute();
 	int run_files(td_stream_stats& st);
 	int unknown_barcodes(int bar_file);
+	int molecules();
 };
 
 int Run::execute()
@@ -859,6 +886,8 @@ int Run::execute()
 			// --unknown-barcodes: the contexts of the barcode file count what their reads spell in the last 'B' segment
 			if (o->unknown_barcodes > 0 && k == bar_file &&
 			    td_census_enable(c, -1, TD_CENSUS_DEFAULT_MASK, o->unknown_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
+			// --molecules: the contexts of the one input file count its extracted reads per barcode, fingerprint and start of the read
+			if (o->molecules && td_mol_enable(c, o->molecules_prefix, o->molecules_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
 		}
 	}
 	rep->compile_wait_s = now_s() - t0;
@@ -875,6 +904,7 @@ int Run::execute()
 	}
 
 	if (o->unknown_barcodes > 0 && unknown_barcodes(bar_file) != TD_OK) return TD_FAIL;
+	if (o->molecules && molecules() != TD_OK) return TD_FAIL;
 
 	// 6. the summary, barcode_hmm.c:387-430
 	for (auto& m : summary_messages(o, rep)) log.add(m);
@@ -952,10 +982,83 @@ int Run::unknown_barcodes(int bar_file)
 	return TD_OK;
 }
 
+// --molecules: one device's own summary, or every device's entries merged and summarised on the host (nothing of it enters the
+// log), and <out>_molecules.txt
+int Run::molecules()
+{
+	FileState& f = files[0];
+	td_mol_row* rows = (td_mol_row*)calloc(TD_NUM_BARCODE_BINS, sizeof(td_mol_row));
+	if (!rows) return fail("--molecules: out of memory");
+	rep->molecules = rows;
+	td_mol_totals sum{};
+	if (f.raw.size() == 1) {
+		if (td_mol_get(f.raw[0], rows, &sum) != TD_OK) return fail("%s", td_last_error(f.raw[0]));
+	} else {
+		td_census_entry* acc = nullptr;
+		int64_t n_acc = 0;
+		for (td_ctx* c : f.raw) {
+			int64_t n = 0;
+			td_mol_totals t{};
+			if (td_mol_entries(c, nullptr, 0, &n, &t) != TD_OK) { td_census_free(acc); return fail("%s", td_last_error(c)); }
+			std::vector<td_census_entry> part((size_t)std::max<int64_t>(n, 1));
+			if (td_mol_entries(c, part.data(), n, &n, &t) != TD_OK) { td_census_free(acc); return fail("%s", td_last_error(c)); }
+			td_census_entry* merged = nullptr;
+			int64_t n_merged = 0;
+			const int rc = td_census_merge(acc, n_acc, part.data(), n, &merged, &n_merged);
+			td_census_free(acc);
+			if (rc != TD_OK) return fail("%s", td_last_error(nullptr));
+			acc = merged; n_acc = n_merged;
+			sum.eligible += t.eligible; sum.counted += t.counted; sum.skipped_empty += t.skipped_empty; sum.skipped_n += t.skipped_n;
+			sum.overflow += t.overflow;
+		}
+		sum.molecules = n_acc;
+		const int rc = td_mol_summarise(acc, n_acc, rows);
+		td_census_free(acc);
+		if (rc != TD_OK) return fail("%s", td_last_error(nullptr));
+	}
+	rep->molecules_totals = sum;
+
+	const td_arch* a = f.arch.get();
+	int seg = -1;
+	for (int j = 0; j < a->n_segments; j++) if (a->type[j] == 'B') seg = j;
+	const std::string name = molecules_file_name(o);
+	FILE* out = fopen(name.c_str(), "w");
+	if (!out) return fail("Failed to open file:%s", name.c_str());
+	fprintf(out, "# molecules: the extracted reads of %s by barcode, fingerprint and the first bases of the read\n", o->infile[0]);
+	fprintf(out, "# prefix bases\t%d\n", o->molecules_prefix);
+	fprintf(out, "# extracted reads\t%lld\n# counted\t%lld\n# molecules\t%lld\n# no read base\t%lld\n# N in the prefix\t%lld\n",
+	        (long long)sum.eligible, (long long)sum.counted, (long long)sum.molecules, (long long)sum.skipped_empty, (long long)sum.skipped_n);
+	if (sum.overflow > 0)
+		fprintf(out, "# the counting table was too small: %lld reads were not counted (the counts below are exact; --molecules-slots %d or more)\n",
+		        (long long)sum.overflow, o->molecules_slots_log2 + 1);
+	fprintf(out, "# barcode\treads\tmolecules\tduplication\t1\t2\t3\t4\t5\t6\t7\t8\t9\t10+\n");
+	auto line = [&](const char* label, const td_mol_row& r) {
+		fprintf(out, "%s\t%lld\t%lld\t%0.4f", label, (long long)r.reads, (long long)r.molecules,
+		        r.reads > 0 ? 1.0 - (double)r.molecules / (double)r.reads : 0.0);
+		for (int q = 0; q < TD_MOL_LEVELS; q++) fprintf(out, "\t%lld", (long long)r.levels[q]);
+		fprintf(out, "\n");
+	};
+	if (seg >= 0) {
+		const int n_listed = std::min(a->n_seq[seg] - 1, (int)TD_NUM_BARCODE_BINS);   // (the last one is the all-N wildcard)
+		for (int q = 0; q < n_listed; q++) line(a->seqs[seg][q], rows[q]);
+	} else {
+		line("-", rows[0]);
+	}
+	td_mol_row total{};
+	for (int b = 0; b < TD_NUM_BARCODE_BINS; b++) {
+		total.reads += rows[b].reads; total.molecules += rows[b].molecules;
+		for (int q = 0; q < TD_MOL_LEVELS; q++) total.levels[q] += rows[b].levels[q];
+	}
+	line("total", total);
+	fclose(out);
+	return TD_OK;
+}
+
 int Run::run_files(td_stream_stats& st)
 {
 	const int K = o->n_infiles;
 	td_stream_opts so{};
+	so.fingerprint_text = o->fingerprint_seq;
 	so.batch_reads = o->batch_reads > 0 ? o->batch_reads : (o->flavour ? 1000 : 0);
 	so.n_threads = o->host_threads;
 	if (K == 1 && o->n_devices == 1 && !is_read_only(files[0].arch.get())) {

@@ -500,11 +500,11 @@ inline void codes_to_text(char* w, const uint8_t* s, size_t n) { static const ch
 // ctype / cbar: read_type and barcode of the record as the controller combines them over the input files of a run
 // (barcode_hmm.c:329-351; NULL: this file's own); file_base: index of this input file's first output file (io.c:917-1001: c)
 void format_records(const Batch& b, const Piece& pc, int64_t lo, int64_t hi, int num_alternatives, OutBufs& out,
-                    const int32_t* ctype = nullptr, const int32_t* cbar = nullptr, size_t file_base = 0)
+                    const int32_t* ctype = nullptr, const int32_t* cbar = nullptr, size_t file_base = 0, bool fingerprint_text = false)
 {
 	const char* text = pc.blk->data;
 	const std::vector<TdRec>& recs = *pc.recs;
-	char head[96];
+	char head[352];                                        // (";FP:" + up to 255 bases + ";RQ:" + the quality)
 	const size_t n_files = out.file.size();
 	for (int64_t r = lo; r < hi; r++) {
 		const TdRec& rec = recs[(size_t)r];
@@ -528,7 +528,11 @@ void format_records(const Batch& b, const Piece& pc, int64_t lo, int64_t hi, int
 			if (f < n_files) {                                 // io.c:955-975: "@<name>[;FP:%d];RQ:%0.2f"
 				if (head_len < 0) {
 					int k = 0;
-					if (rr.fingerprint != -1) { memcpy(head, ";FP:", 4); k = 4 + put_int(head + 4, rr.fingerprint); }
+					if (rr.fingerprint != -1) {
+						memcpy(head, ";FP:", 4);
+						if (fingerprint_text) { (void)td_fingerprint_text(rr.fingerprint, head + 4); k = 4 + (rr.fingerprint & 0xFF); }   // io.c:960-963
+						else k = 4 + put_int(head + 4, rr.fingerprint);
+					}
 					memcpy(head + k, ";RQ:", 4); k += 4;
 					k += put_q(head + k, rr.mapq);
 					head[k++] = '\n';
@@ -836,6 +840,7 @@ struct Writer {
 	RunError& err;
 	Pool pool;
 	const int num_alternatives;
+	bool fingerprint_text = false;      // td_stream_opts.fingerprint_text: ";FP:ACGT" instead of ";FP:27"
 	std::vector<int> fds;
 	std::vector<int64_t> file_off;
 	int64_t bytes_out = 0;
@@ -959,7 +964,7 @@ struct Writer {
 		}
 		pool.run((int64_t)subs.size(), [&](int64_t k) {
 			const Sub& sb = subs[(size_t)k];
-			format_records(*b, b->pieces[sb.piece], sb.lo, sb.hi, num_alternatives, bufs[(size_t)k], ctype, cbar, file_base);
+			format_records(*b, b->pieces[sb.piece], sb.lo, sb.hi, num_alternatives, bufs[(size_t)k], ctype, cbar, file_base, fingerprint_text);
 		});
 		dbg_format += now_s() - t0;
 		// Appends.  Buffered writes to one file serialise on its inode lock (8 threads on one file: 8 GB/s; one thread on each of
@@ -1190,6 +1195,7 @@ extern "C" int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* ar
 		int num_alternatives = 2;
 		td_writer_file_names(out_prefix, arch, names, &num_alternatives);
 		w.reset(new Writer(err, o.n_threads, num_alternatives));
+		w->fingerprint_text = o.fingerprint_text != 0;
 		if (!w->open(names, why)) { td_io_set_error("td_stream_run: cannot create " + why); return TD_FAIL; }
 	}
 	td_stream_stats st{};
@@ -1405,6 +1411,7 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 	int num_alternatives = 2;
 	td_writer_file_names_n(out_prefix, files[m.bar_file >= 0 ? m.bar_file : K - 1].arch, m.num_out_reads, names, &num_alternatives);
 	Writer w(err, o.n_threads, num_alternatives);
+	w.fingerprint_text = o.fingerprint_text != 0;
 	std::string why;
 	if (!w.open(names, why)) { td_io_set_error("td_stream_run_multi: cannot create " + why); return TD_FAIL; }
 	std::vector<size_t> file_base((size_t)K, 0);      // io.c:917-1001: c

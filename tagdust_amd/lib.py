@@ -32,7 +32,7 @@ MULTI_ABI_SYMBOLS = ["td_shard_bounds", "td_count_outcomes", "td_multi_create", 
                      "td_multi_artifact_hits"]
 IO_ABI_SYMBOLS = ["td_io_last_error", "td_reads_parse", "td_reads_free", "td_writer_open", "td_writer_write", "td_writer_close",
                   "td_fasta_parse", "td_fasta_free", "td_stream_run", "td_stream_run_multi", "td_stream_run_multi_hits", "td_stream_release",
-                  "td_format_q"]
+                  "td_format_q", "td_fingerprint_text", "td_writer_set_fingerprint_text"]
 MODEL_ABI_SYMBOLS = ["td_arch_parse", "td_arch_free", "td_sequence_stats", "td_sequence_stats_window", "td_model_build", "td_model_tables_free",
                      "td_calibration_emit", "td_calibration_select", "td_calibration_free", "td_estimate_threshold",
                      "td_compare_architectures", "td_simreads", "td_text_free", "td_sequence_stats_limit",
@@ -50,6 +50,15 @@ CENSUS_ENTRY_DTYPE = np.dtype([("key", "<u8"), ("count", "<i8")])
 CENSUS_TOTALS = ("eligible", "counted", "skipped_empty", "skipped_long", "skipped_n", "overflow", "distinct")
 CENSUS_DEFAULT_MASK = (1 << 1) | (1 << 3)   # EXTRACT_FAIL_ARCHITECTURE_MISMATCH, EXTRACT_FAIL_BAR_FINGER_NOT_FOUND
 CENSUS_MAX_WORD = 28
+
+# include/tagdust_molecules.h: molecules per barcode
+MOL_ABI_SYMBOLS = ["td_mol_enable", "td_mol_disable", "td_mol_reset", "td_mol_entries", "td_mol_get", "td_mol_summarise", "td_mol_host",
+                   "td_mol_key", "td_mol_key_bin"]
+MOL_TOTALS = ("eligible", "counted", "skipped_empty", "skipped_n", "overflow", "molecules")
+MOL_LEVELS = 10
+MOL_ROW_DTYPE = np.dtype([("reads", "<i8"), ("molecules", "<i8"), ("levels", "<i8", (MOL_LEVELS,))])
+MOL_DEFAULT_PREFIX = 20
+MOL_DEFAULT_LOG2_SLOTS = 26
 
 RESULT_DTYPE = np.dtype([
     ("f_score", "<f4"), ("b_score", "<f4"), ("r_score", "<f4"), ("bar_prob", "<f4"), ("mapq", "<f4"),
@@ -462,9 +471,21 @@ class ParsedReads:
             pass
 
 
-def write_demultiplexed(prefix, segments, reads, res, seq_out):
-    """print_all() for one input file through the library: res (RESULT_DTYPE) and seq_out as td_batch_download gives them."""
+def fingerprint_text(fingerprint):
+    """td_fingerprint_text: the bases a fingerprint stands for, as the reference's get_finger_seq gives them."""
     lib = load_library()
+    lib.td_fingerprint_text.argtypes = [C.c_int32, C.c_char_p]
+    buf = C.create_string_buffer(256)
+    n = lib.td_fingerprint_text(int(fingerprint), buf)
+    assert n == len(buf.value)
+    return buf.value.decode()
+
+
+def write_demultiplexed(prefix, segments, reads, res, seq_out, fingerprint_text=False):
+    """print_all() for one input file through the library: res (RESULT_DTYPE) and seq_out as td_batch_download gives them.
+    fingerprint_text: td_writer_set_fingerprint_text, ";FP:ACGT" instead of ";FP:27"."""
+    lib = load_library()
+    lib.td_writer_set_fingerprint_text.argtypes = [C.c_void_p, C.c_int]
     arr = (C.c_char_p * len(segments))(*[s.encode() for s in segments])
     arch = C.c_void_p()
     if lib.td_arch_parse(arr, len(segments), C.byref(arch)) != 0:
@@ -473,6 +494,8 @@ def write_demultiplexed(prefix, segments, reads, res, seq_out):
         w = C.c_void_p()
         if lib.td_writer_open(prefix.encode(), arch, C.byref(w)) != 0:
             raise TdError("td_writer_open failed for %s" % prefix)
+        if lib.td_writer_set_fingerprint_text(w, 1 if fingerprint_text else 0) != 0:
+            raise TdError("td_writer_set_fingerprint_text failed")
         res = np.ascontiguousarray(res, RESULT_DTYPE)
         seq_out = np.ascontiguousarray(seq_out, np.uint8)
         rc = lib.td_writer_write(w, reads._p, res.ctypes.data, seq_out.ctypes.data)
@@ -484,7 +507,7 @@ def write_demultiplexed(prefix, segments, reads, res, seq_out):
 
 
 class _StreamOpts(C.Structure):
-    _fields_ = [("batch_reads", C.c_int32), ("n_threads", C.c_int32), ("block_bytes", C.c_int64)]
+    _fields_ = [("batch_reads", C.c_int32), ("n_threads", C.c_int32), ("block_bytes", C.c_int64), ("fingerprint_text", C.c_int32)]
 
 
 class _StreamStats(C.Structure):
@@ -493,7 +516,7 @@ class _StreamStats(C.Structure):
                 ("write_s", C.c_double), ("codes_fnv", C.c_uint64)]
 
 
-def stream_run(ctx, in_path, segments=None, out_prefix=None, batch_reads=0, n_threads=0, block_bytes=0):
+def stream_run(ctx, in_path, segments=None, out_prefix=None, batch_reads=0, n_threads=0, block_bytes=0, fingerprint_text=False):
     """td_stream_run: one input file through parse -> decode -> write as a pipeline; ctx None = parse-only run (no GPU).
     Returns the statistics as a dict."""
     lib = load_library()
@@ -505,7 +528,7 @@ def stream_run(ctx, in_path, segments=None, out_prefix=None, batch_reads=0, n_th
         if lib.td_arch_parse(arr, len(segments), C.byref(arch)) != 0:
             raise TdError("td_arch_parse failed for %r" % (segments,))
     try:
-        o = _StreamOpts(int(batch_reads), int(n_threads), int(block_bytes))
+        o = _StreamOpts(int(batch_reads), int(n_threads), int(block_bytes), 1 if fingerprint_text else 0)
         st = _StreamStats()
         rc = lib.td_stream_run(ctx.h if ctx is not None else None, os.fsencode(in_path), arch if segments is not None else None,
                                os.fsencode(out_prefix) if out_prefix is not None else None, C.byref(o), C.byref(st))
@@ -521,7 +544,7 @@ class _StreamFile(C.Structure):
     _fields_ = [("path", C.c_char_p), ("arch", C.c_void_p), ("ctx", C.POINTER(C.c_void_p))]
 
 
-def stream_run_multi(files, out_prefix, n_devices=1, dust=100, batch_reads=0, n_threads=0, block_bytes=0):
+def stream_run_multi(files, out_prefix, n_devices=1, dust=100, batch_reads=0, n_threads=0, block_bytes=0, fingerprint_text=False):
     """td_stream_run_multi: the input files of one paired / multi-read run in lock-step.  files: a list of
     (path, segments, contexts) -- contexts = one TagdustHip per device holding that file's model and parameters.  A file whose
     architecture is a single read segment ("R:N") is not decoded but goes through run_rna_dust: with contexts (no model needed;
@@ -549,7 +572,7 @@ def stream_run_multi(files, out_prefix, n_devices=1, dust=100, batch_reads=0, n_
                 cp = (C.c_void_p * n_devices)(*[c.h for c in ctxs])
                 keep.append(cp)
                 arr[k].ctx = C.cast(cp, C.POINTER(C.c_void_p))
-        o = _StreamOpts(int(batch_reads), int(n_threads), int(block_bytes))
+        o = _StreamOpts(int(batch_reads), int(n_threads), int(block_bytes), 1 if fingerprint_text else 0)
         st = _StreamStats()
         counts = np.zeros(264, np.int64)
         rc = lib.td_stream_run_multi(arr, len(files), int(n_devices), os.fsencode(out_prefix), int(dust), C.byref(o), C.byref(st), counts.ctypes.data)
@@ -571,7 +594,8 @@ class _RunOpts(C.Structure):
                 ("infile", C.POINTER(C.c_char_p)), ("n_devices", C.c_int32), ("devices", C.c_int32 * 16), ("flavour", C.c_int32),
                 ("host_threads", C.c_int32), ("batch_reads", C.c_int32), ("sync_compile", C.c_int32), ("stats_on_host", C.c_int32),
                 ("force", C.c_int32), ("dry_run", C.c_int32), ("help", C.c_int32), ("version", C.c_int32), ("echo_log", C.c_int32),
-                ("argc", C.c_int32), ("argv", C.POINTER(C.c_char_p)), ("unknown_barcodes", C.c_int32), ("unknown_slots_log2", C.c_int32)]
+                ("argc", C.c_int32), ("argv", C.POINTER(C.c_char_p)), ("unknown_barcodes", C.c_int32), ("unknown_slots_log2", C.c_int32),
+                ("fingerprint_seq", C.c_int32), ("molecules", C.c_int32), ("molecules_prefix", C.c_int32), ("molecules_slots_log2", C.c_int32)]
 
 
 class _CensusTotals(C.Structure):
@@ -582,6 +606,14 @@ class _CensusTotals(C.Structure):
         return {f: int(getattr(self, f)) for f in CENSUS_TOTALS}
 
 
+class _MolTotals(C.Structure):
+    """td_mol_totals (include/tagdust_molecules.h)"""
+    _fields_ = [(f, C.c_int64) for f in MOL_TOTALS]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f in MOL_TOTALS}
+
+
 class _RunReport(C.Structure):
     """td_run_report (include/tagdust_run.h)"""
     _fields_ = [("error", C.c_char * 1024), ("counts", C.c_int64 * NUM_COUNTERS), ("n_artifacts", C.c_int32),
@@ -589,7 +621,8 @@ class _RunReport(C.Structure):
                 ("thresholds", C.c_float * 8), ("selected_threshold", C.c_float), ("architectures", C.c_char_p * 8),
                 ("stream", _StreamStats), ("arch_s", C.c_double), ("stats_s", C.c_double), ("calibration_s", C.c_double),
                 ("compile_wait_s", C.c_double), ("stream_s", C.c_double), ("stats_on_device", C.c_int32), ("log", C.c_char_p),
-                ("n_unknown", C.c_int64), ("unknown", C.c_void_p), ("unknown_totals", _CensusTotals)]
+                ("n_unknown", C.c_int64), ("unknown", C.c_void_p), ("unknown_totals", _CensusTotals),
+                ("molecules", C.c_void_p), ("molecules_totals", _MolTotals)]
 
 
 def _run_lib():
@@ -699,6 +732,7 @@ def run_execute(args):
             "seconds": {f: getattr(rep, f + "_s") for f in ("arch", "stats", "calibration", "compile_wait", "stream")},
             "stats_on_device": bool(rep.stats_on_device), "log": (rep.log or b"").decode(),
             "unknown": _census_entries(rep.unknown, int(rep.n_unknown)), "unknown_totals": rep.unknown_totals.as_dict(),
+            "molecules": _mol_rows(rep.molecules) if rep.molecules else None, "molecules_totals": rep.molecules_totals.as_dict(),
         }
     finally:
         o.lib.td_run_report_clear(C.byref(rep))
@@ -780,6 +814,75 @@ def census_key(word):
     for ch in word:
         v = (v << 2) | "ACGT".index(ch)
     return (len(word) << 56) | v
+
+
+def _mol_rows(ptr):
+    """the NUM_BARCODE_BINS td_mol_row at ptr, copied"""
+    out = np.zeros(NUM_BARCODE_BINS, MOL_ROW_DTYPE)
+    C.memmove(out.ctypes.data, ptr, out.nbytes)
+    return out
+
+
+def _mol_lib():
+    lib = _census_lib()
+    lib.td_mol_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.td_mol_disable.argtypes = [C.c_void_p]
+    lib.td_mol_reset.argtypes = [C.c_void_p]
+    lib.td_mol_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_MolTotals)]
+    lib.td_mol_get.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_MolTotals)]
+    lib.td_mol_summarise.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    lib.td_mol_host.argtypes = [C.POINTER(_ModelDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(_MolTotals)]
+    lib.td_mol_key.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_int32]
+    lib.td_mol_key.restype = C.c_uint64
+    lib.td_mol_key_bin.argtypes = [C.c_uint64]
+    lib.td_mol_key_bin.restype = C.c_int32
+    return lib
+
+
+def mol_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_host: the molecule count of a batch from host arrays (no GPU).  md: model mapping; res: the reads' records
+    (RESULT_DTYPE, or any mapping / structured array with read_type, barcode and fingerprint: td_batch_download's, or the
+    oracle's); labels as td_batch_download leaves them.  Returns (entries, totals dict)."""
+    lib = _mol_lib()
+    desc, keep = make_model_desc(md)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if len(seq) == 0:
+        seq = np.zeros(1, np.uint8)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
+    for f in ("read_type", "barcode", "fingerprint"):
+        rr[f] = np.asarray(res[f])
+    ptr, n, tot = C.c_void_p(), C.c_int64(), _MolTotals()
+    rc = lib.td_mol_host(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
+                         labels.ctypes.data, C.byref(ptr), C.byref(n), C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    try:
+        return _census_entries(ptr, n.value), tot.as_dict()
+    finally:
+        lib.td_census_free(ptr)
+
+
+def mol_summarise(entries):
+    """td_mol_summarise: one row per barcode bin (MOL_ROW_DTYPE[256]) from (key, count) entries."""
+    lib = _mol_lib()
+    e = np.ascontiguousarray(entries, CENSUS_ENTRY_DTYPE)
+    rows = np.zeros(NUM_BARCODE_BINS, MOL_ROW_DTYPE)
+    if lib.td_mol_summarise(e.ctypes.data, len(e), rows.ctypes.data) != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return rows
+
+
+def mol_key(barcode, fingerprint, w, n):
+    """td_mol_key: the key of a counted read"""
+    return int(_mol_lib().td_mol_key(int(barcode), int(fingerprint), int(w), int(n)))
+
+
+def mol_key_bin(key):
+    return int(_mol_lib().td_mol_key_bin(int(key)))
 
 
 def stream_release():
@@ -993,6 +1096,32 @@ class TagdustHip:
         out = np.zeros(int(cap), CENSUS_ENTRY_DTYPE)
         self._chk(lib.td_census_get(self.h, out.ctypes.data, int(cap), C.byref(n), C.byref(tot)))
         return out[:min(int(cap), n.value)], tot.as_dict()
+
+    def mol_enable(self, prefix_bases=MOL_DEFAULT_PREFIX, log2_slots=16):
+        self._chk(_mol_lib().td_mol_enable(self.h, int(prefix_bases), int(log2_slots)))
+
+    def mol_disable(self):
+        self._chk(_mol_lib().td_mol_disable(self.h))
+
+    def mol_reset(self):
+        self._chk(_mol_lib().td_mol_reset(self.h))
+
+    def mol_entries(self, cap=None):
+        """td_mol_entries: (the (key, count) pairs by count descending then key ascending -- at most cap of them --, totals dict)"""
+        lib = _mol_lib()
+        n, tot = C.c_int64(), _MolTotals()
+        if cap is None:
+            self._chk(lib.td_mol_entries(self.h, None, 0, C.byref(n), C.byref(tot)))
+            cap = n.value
+        out = np.zeros(int(cap), CENSUS_ENTRY_DTYPE)
+        self._chk(lib.td_mol_entries(self.h, out.ctypes.data, int(cap), C.byref(n), C.byref(tot)))
+        return out[:min(int(cap), n.value)], tot.as_dict()
+
+    def mol_get(self):
+        """td_mol_get: (the device's summary, MOL_ROW_DTYPE[256], totals dict)"""
+        rows, tot = np.zeros(NUM_BARCODE_BINS, MOL_ROW_DTYPE), _MolTotals()
+        self._chk(_mol_lib().td_mol_get(self.h, rows.ctypes.data, C.byref(tot)))
+        return rows, tot.as_dict()
 
     def counts_reset(self):
         self._chk(self.lib.td_counts_reset(self.h))

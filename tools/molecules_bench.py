@@ -1,0 +1,149 @@
+"""Measures the molecule count (include/tagdust_molecules.h) on 2^20 config-3-shaped reads with an 8-nt fingerprint, drawn with
+replacement from 2^18 molecules.
+
+    python tools/molecules_bench.py [--reads 1048576] [--molecules 262144] [--out profiles/molecules.json]        # on the MI355X
+
+The architecture is the flagship's with an F segment behind the barcode: B:<8 barcodes> F:NNNNNNNN S:GTA R:N P:<adapter>; a
+molecule is a barcode, a UMI and an insert, a read is a molecule with the 3' adapter's prefix at its end and 2 % substitutions in
+barcode, spacer and adapter (the flagship's generator; UMI and insert are copied as they are, so the molecules of a batch are
+known: the distinct draws).
+
+Measured: the count kernel's time from HIP events (option "molecules_kernel_us": events around its launch) beside the decode
+kernel's time of the same batch (td_last_kernel_ms), median of 5 batches, the table reset before each so that every batch claims
+its slots anew; the totals of one batch; the device summary's time (td_mol_get, 2^22 slots); and host-to-host reads/s of the batch
+through td_submit / td_wait with the count on and off in turn (on, off, on, off).  The yardstick is the run with the count off:
+the path without this feature.
+
+Expectation, written down before the first run, from the bytes the count kernel touches per read: the outcome, length, barcode
+and fingerprint (16 B), a label byte per position up to the 20th read base (the read starts at base 17: 37 B), three 2-bit words
+and two N-mask words (20 B) -- 73 B streamed -- and the table: a load of the key, a CAS on it for a new key, an add on the
+count, three touches of 8 B that each move a 64-byte sector or more at a random address, 200-400 B.  Under 0.5 KB against the
+56 KB a read costs the decode kernel: about one percent of the decode kernel's time, and no visible change host to host, where
+the count runs behind the decode kernel on its stream while the copies of the neighbouring batches are under way.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import bench  # noqa: E402  (the flagship workload's barcodes, spacer, adapter and read length)
+
+UMI = 8
+PREFIX = 20
+LOG2_SLOTS = 22
+
+
+def code(s):
+    return np.array(["ACGT".index(c) for c in s], np.uint8)
+
+
+def make_batch(n, n_mol, seed=1, sub=0.02):
+    rng = np.random.default_rng(seed)
+    L = bench.READ_LEN
+    bar = np.array([code(b) for b in bench.BARCODES], np.uint8)
+    mol = rng.integers(0, 4, size=(n_mol, L), dtype=np.uint8)
+    mol[:, :6] = bar[rng.integers(0, len(bar), n_mol)]
+    mol[:, 6 + UMI:6 + UMI + len(bench.SPACER)] = code(bench.SPACER)
+    draw = rng.integers(0, n_mol, n)
+    y = mol[draw]
+    ad = code(bench.ADAPTER)
+    keep = rng.integers(0, len(ad) + 1, n)
+    t0 = L - len(ad)
+    pos = np.arange(t0, L)[None, :]
+    start = (L - keep)[:, None]
+    in_ad = pos >= start
+    y[:, t0:] = np.where(in_ad, ad[np.clip(pos - start, 0, len(ad) - 1)], y[:, t0:])
+    structured = np.zeros((n, L), bool)
+    structured[:, :6] = True
+    structured[:, 6 + UMI:6 + UMI + len(bench.SPACER)] = True
+    structured[:, t0:] |= in_ad
+    structured &= rng.random((n, L)) < sub
+    np.copyto(y, rng.integers(0, 4, size=(n, L), dtype=np.uint8), where=structured)
+    return np.ascontiguousarray(y.reshape(-1)), np.arange(n + 1, dtype=np.int64) * L, int(len(np.unique(draw)))
+
+
+def measure(ctx, seq, offs, n):
+    from tagdust_amd import RESULT_DTYPE
+    out = {}
+    ctx.mol_enable(PREFIX, LOG2_SLOTS)
+    dec, cnt = [], []
+    for it in range(6):
+        ctx.mol_reset()
+        ctx.upload_batch(seq, offs)
+        ctx.run()
+        dec.append(ctx.last_kernel_ms())
+        cnt.append(ctx.get_option("molecules_kernel_us") / 1000.0)
+        if it == 0:
+            t0 = time.perf_counter()
+            rows, tot = ctx.mol_get()
+            out["device_summary_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+            out["totals_of_one_batch"] = tot
+            out["rows_of_one_batch"] = [[int(r["reads"]), int(r["molecules"])] for r in rows[:len(bench.BARCODES)]]
+    out["decode_kernel_ms_runs"] = [round(v, 3) for v in dec[1:]]
+    out["count_kernel_ms_runs"] = [round(v, 3) for v in cnt[1:]]
+    d, c = statistics.median(dec[1:]), statistics.median(cnt[1:])
+    out["decode_kernel_ms_median"], out["count_kernel_ms_median"] = round(d, 3), round(c, 3)
+    out["count_share_of_decode"] = round(c / d, 5)
+    out["count_kernel_reads_per_s"] = round(n / (c * 1e-3)) if c > 0 else None
+    ctx.mol_disable()
+    # host to host through td_submit / td_wait, the count on and off in turn
+    res = [np.zeros(n, RESULT_DTYPE) for _ in range(2)]
+    rates = {"on": [], "off": []}
+    for state in ("on", "off", "on", "off"):
+        if state == "on":
+            ctx.mol_enable(PREFIX, LOG2_SLOTS)
+        steps = 4
+        for t in [ctx.submit(seq, offs, res=r) for r in res]:      # warm-up: both slots, both result buffers
+            ctx.wait(t)
+        t0 = time.perf_counter()
+        tickets = []
+        for s in range(steps):
+            tickets.append(ctx.submit(seq, offs, res=res[s & 1]))
+            if len(tickets) == 2:
+                ctx.wait(tickets.pop(0))
+        for t in tickets:
+            ctx.wait(t)
+        rates[state].append(round(steps * n / (time.perf_counter() - t0)))
+        if state == "on":
+            ctx.mol_disable()
+    out["host_to_host_reads_per_s"] = rates
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reads", type=int, default=1 << 20)
+    ap.add_argument("--molecules", type=int, default=1 << 18)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "molecules.json"))
+    args = ap.parse_args()
+    from tagdust_amd import TagdustHip
+    from tagdust_amd import lib as tdlib
+    segs = ["B:" + ",".join(bench.BARCODES), "F:" + "N" * UMI, "S:" + bench.SPACER, "R:N", "P:" + bench.ADAPTER]
+    seq, offs, drawn = make_batch(args.reads, args.molecules)
+    head = min(args.reads, 100000)
+    md, _ = tdlib.build_model(segs, seq[:offs[head]], offs[:head + 1])
+    ctx = TagdustHip(args.device)
+    doc = {"reads": args.reads, "read_len": bench.READ_LEN, "molecules_drawn_from": args.molecules, "molecules_in_the_batch": drawn,
+           "architecture": " ".join(segs), "prefix_bases": PREFIX, "table_log2_slots": LOG2_SLOTS, "threshold": 5.0}
+    try:
+        ctx.set_option("async_compile", 0)
+        ctx.upload_model(md)
+        ctx.set_params(5.0, 16, 100)
+        doc.update(measure(ctx, seq, offs, args.reads))
+    finally:
+        ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    json.dump(doc, open(args.out, "w"), indent=1, sort_keys=True)
+    print(json.dumps(doc, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()
