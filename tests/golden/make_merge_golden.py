@@ -2,37 +2,82 @@
 
     python tests/golden/make_merge_golden.py [/path/to/reference]
 
-The reference's `merge` (src/merge.c) is compiled into a temporary directory with the flags of oracle/Makefile plus -DMERGE; nothing
-of it is kept.  Two runs are recorded: the defaults, and `-Q 0.9 -minlen 20`.  Every pair lies in the reference's defined domain
-for both runs: both reads longer than 20 bases, no '.'.
+The reference's `merge` (src/merge.c) is built by oracle/Makefile into oracle/_ref/merge (git-ignored); nothing of it is kept
+here.  Only inputs and what `merge -t 1` wrote for them are recorded, and every recorded run is first compared with the plain
+restatement of tests/merge_plain.py: the reference must exit 0 and its bytes must equal the restatement's text.
+
+First input pair, two runs: the defaults, and `-Q 0.9 -minlen 20`.  Every pair lies in the reference's defined domain for both
+runs: both reads longer than 20 bases, no '.'.
 
     r1.fq, r2.fq           300 pairs: reads of 21..150 bases, six quality characters, an N in every 17th read 1, an unrelated
                            read 2 in every 50th pair
     r1.fq.gz, r2.fq.gz     the same, compressed
     merged_default.fq      merge -t 1 r1.fq r2.fq
     merged_Q0.9_minlen20.fq  merge -t 1 -Q 0.9 -minlen 20 r1.fq r2.fq
+
+Second input pair: the sets of tests/merge_cases.py FIXTURE_SETS -- the edge shapes of the kernel (sweep boundaries, the 512-base
+limit, ties, '~' and '!'), pairs whose id / aligned equals a threshold exactly and their twins one mismatch worse, pairs over
+"!~F", over all 94 quality characters, and with every fifth base an N -- filtered to the reference's defined domain by
+merge_plain.in_reference_domain (a zero exit status does not mark it: outside it the binary may also write garbage).  A record is
+named <set><index in its set>, so the names tell which pairs the filter took out.
+
+    edge_r1.fq, edge_r2.fq   the pairs
+    edge_merged_default.fq   merge -t 1 -minlen 16 edge_r1.fq edge_r2.fq
+    edge_merged_Q<x>.fq      merge -t 1 -Q <x> edge_r1.fq edge_r2.fq, for x = 0.9, 0.95, 0.75, 0.7: the thresholds of the boundary pairs
 """
 import gzip
 import os
 import random
 import subprocess
 import sys
-import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+import merge_cases  # noqa: E402
+import merge_plain  # noqa: E402
+
 OUT = os.path.join(HERE, "merge")
-RFLAGS = ["-O2", "-funroll-loops", "-std=gnu99", "-fcommon", "-w", "-DkslDEBUGLEVEL=0", '-DPACKAGE_NAME="Tagdust"',
-          '-DPACKAGE_VERSION="2.33"', '-DPACKAGE_BUGREPORT="timolassmann@gmail.com"', "-DMERGE"]
-SOURCES = ["kslib.c", "interface.c", "nuc_code.c", "io.c", "misc.c", "merge.c"]
+ORACLE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle")
 QUALS = "#,5<AF"          # Phred 2, 11, 20, 27, 32, 37
 QUAL_WEIGHTS = [1, 2, 3, 4, 5, 5]   # mostly good bases: about 4 % miscalls, so that -Q 0.9 keeps some pairs and drops others
 COMP = {"A": "T", "C": "G", "G": "C", "T": "A", "N": "N"}
 
 
-def build_reference(ref, tmp):
-    exe = os.path.join(tmp, "merge")
-    subprocess.check_call(["gcc"] + RFLAGS + ["-o", exe] + [os.path.join(ref, "src", s) for s in SOURCES] + ["-lpthread", "-lm"])
-    return exe
+def build_reference(ref):
+    """oracle/_ref/merge by the recipe of oracle/Makefile"""
+    subprocess.check_call(["make", "-C", ORACLE, "_ref/merge"] + (["REF=" + ref] if ref else []))
+    return os.path.join(ORACLE, "_ref", "merge")
+
+
+def record(exe, out, args, in1, in2, min_overlap, threshold):
+    """runs the reference, holds its bytes against the restatement, and only then writes them"""
+    res = subprocess.run([exe, "-t", "1"] + args + [os.path.join(OUT, in1), os.path.join(OUT, in2)], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL)
+    assert res.returncode == 0, (out, res.returncode)
+    recs1 = merge_plain.parse_fastq(open(os.path.join(OUT, in1), "rb").read())
+    recs2 = merge_plain.parse_fastq(open(os.path.join(OUT, in2), "rb").read())
+    plain = merge_plain.merge_records(recs1, recs2, min_overlap, threshold)
+    assert all(merge_plain.in_reference_domain(len(a[1]), len(b[1]), min_overlap, m.best_d) for a, b, m in zip(recs1, recs2, plain)), out
+    assert res.stdout == merge_plain.text([r[0] for r in recs1], plain), out + ": the reference and the restatement differ"
+    with open(os.path.join(OUT, out), "wb") as f:
+        f.write(res.stdout)
+    print("%s: %d records, %d bytes" % (out, res.stdout.count(b"\n") // 4, len(res.stdout)))
+
+
+def edge_fixture():
+    """(names, pairs) of the second input pair: FIXTURE_SETS inside the reference's defined domain"""
+    names, pairs = [], []
+    for prefix, make in merge_cases.FIXTURE_SETS:
+        for k, (a, b) in enumerate(make()):
+            m = merge_plain.merge_pair(a[0], a[1], b[0], b[1], 16, 0.0)
+            if merge_plain.in_reference_domain(len(a[0]), len(b[0]), 16, m.best_d):
+                names.append("%s%d" % (prefix, k))
+                pairs.append((a, b))
+    # the pairs at a threshold and their twins: the full overlap must be the best candidate of each
+    for k, (a, b) in enumerate(merge_cases.boundary_pairs()):
+        bases, mismatches = merge_cases.BOUNDARY[k // 2][:2]
+        m = merge_plain.merge_pair(a[0], a[1], b[0], b[1], 16, 0.0)
+        assert (m.best_d, m.id, m.aligned) == (0, bases - mismatches - k % 2, bases) and "bound%d" % k in names, k
+    return names, pairs
 
 
 def revcomp(s):
@@ -71,7 +116,7 @@ def generate(n_pairs=300, seed=20151):
 
 
 def main():
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
+    exe = build_reference(sys.argv[1] if len(sys.argv) > 1 else None)
     os.makedirs(OUT, exist_ok=True)
     t1, t2 = generate()
     for name, text in (("r1.fq", t1), ("r2.fq", t2)):
@@ -80,14 +125,15 @@ def main():
         with open(os.path.join(OUT, name + ".gz"), "wb") as f:
             with gzip.GzipFile(fileobj=f, mode="wb", mtime=0) as g:
                 g.write(text.encode())
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = build_reference(ref, tmp)
-        for out, args in (("merged_default.fq", []), ("merged_Q0.9_minlen20.fq", ["-Q", "0.9", "-minlen", "20"])):
-            res = subprocess.run([exe, "-t", "1"] + args + [os.path.join(OUT, "r1.fq"), os.path.join(OUT, "r2.fq")],
-                                 stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True)
-            with open(os.path.join(OUT, out), "wb") as f:
-                f.write(res.stdout)
-            print("%s: %d records" % (out, res.stdout.count(b"\n") // 4))
+    record(exe, "merged_default.fq", [], "r1.fq", "r2.fq", 16, 0.0)
+    record(exe, "merged_Q0.9_minlen20.fq", ["-Q", "0.9", "-minlen", "20"], "r1.fq", "r2.fq", 20, 0.9)
+    names, pairs = edge_fixture()
+    for name, text in zip(("edge_r1.fq", "edge_r2.fq"), merge_cases.texts(pairs, names)):
+        with open(os.path.join(OUT, name), "wb") as f:
+            f.write(text)
+        print("%s: %d pairs, %d bytes" % (name, len(pairs), len(text)))
+    for out, min_overlap, threshold, args in merge_cases.EDGE_RUNS:
+        record(exe, out, args, "edge_r1.fq", "edge_r2.fq", min_overlap, threshold)
 
 
 if __name__ == "__main__":
