@@ -59,6 +59,10 @@ extern "C" {
 #define TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND  3
 #define TD_EXTRACT_FAIL_MATCHES_ARTIFACTS     5
 #define TD_EXTRACT_FAIL_LOW_COMPLEXITY        6
+/* not an outcome of the reference: an extracted read that is not the first of its molecule, set only while dedup is on
+ * (tagdust_molecules.h, td_mol_dedup_enable) and counted by td_counts_get under the outcome it was decoded with; the writers write
+ * such a record to no file */
+#define TD_EXTRACT_DUPLICATE                  7
 
 /* transition indices of td_model_desc.trans, src/barcode_hmm.h:87-96 */
 enum { TD_MM = 0, TD_MI = 1, TD_MD = 2, TD_II = 3, TD_IM = 4, TD_DD = 5, TD_DM = 6, TD_MSKIP = 7, TD_ISKIP = 8 };

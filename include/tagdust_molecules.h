@@ -28,6 +28,26 @@
  * within its probe window adds its reads to `overflow`, on every attempt alike, so a reported count is always exact.  Always
  *     eligible == counted + skipped_empty + skipped_n + overflow      and      counted == the sum of all counts.
  * The default of 2^26 slots (1 GiB) holds the 2^24 molecules of a large run at a quarter full, where no probe comes near the window.
+ *
+ * Dedup (td_mol_dedup_enable) -- one read per molecule -- extends the count and uses its eligibility, prefix and key unchanged.
+ * The reference has nothing of the kind; this is the definition, held by the device path and by td_mol_dedup_host alike:
+ *   - every read of a context has an ordinal: the number of reads submitted to the context in TD_MODE_GET_LABEL since dedup was
+ *     enabled or last reset (td_mol_reset), plus the read's index in its batch in the caller's order (not the device's
+ *     length-sorted order);
+ *   - a counted read is a duplicate when the table holds its key with a smaller first ordinal than its own, the first ordinal of a
+ *     key being the minimum over all counted reads seen so far with that key;
+ *   - eligible reads that are not counted (skipped_empty, skipped_n, overflow) cannot be judged: they are kept, and tallied as
+ *     `unjudged`;
+ *   - a duplicate's outcome becomes TD_EXTRACT_DUPLICATE (tagdust_hip.h; not an outcome of the reference); its barcode,
+ *     fingerprint, scores, labels and seq_out stay as decoded, and the writers write it to no file.  td_counts_get, the census and
+ *     the count itself see the outcome as decoded.
+ * Always
+ *     eligible == kept + duplicates      and      kept == molecules + skipped_empty + skipped_n + overflow,
+ * molecules being the keys that entered the table since the reset.  The result is a function of the context's sequence of reads
+ * alone: not of how it was cut into batches, of td_run or td_submit, of the tickets in flight or of the kernel variant.  Limits:
+ * the 56-bit collision above (two molecules that collide lose one read); and which keys overflow in a nearly full table depends on
+ * the claim order within a batch, as it does for the count.  No neighbouring UMIs are collapsed; a molecule split over two
+ * contexts survives in both (each has its own table).
  */
 #ifndef TAGDUST_MOLECULES_H
 #define TAGDUST_MOLECULES_H
@@ -56,7 +76,8 @@ typedef struct td_mol_row { int64_t reads, molecules, levels[TD_MOL_LEVELS]; } t
  * td_set_window fails; a later td_model_upload switches it off.  It may be on together with the census, each with its own table. */
 int td_mol_enable (td_ctx* ctx, int32_t prefix_bases, int32_t log2_slots);
 int td_mol_disable(td_ctx* ctx);                    /* frees the table */
-int td_mol_reset  (td_ctx* ctx);                    /* zero table and tallies; td_counts_reset does not touch it */
+int td_mol_reset  (td_ctx* ctx);                    /* zero table and tallies (dedup's first ordinals, ordinal counter and tallies
+                                                       with them); td_counts_reset does not touch it */
 /* Waits for the context's queued work.  The raw (key, count) pairs, compacted on the device: *n = the number of molecules; at
  * most cap entries are copied, sorted as td_census_get sorts (count descending, then key ascending).  This is what is merged
  * across devices: td_census_merge adds two such results.  entries may be NULL when cap is 0; totals may be NULL. */
@@ -70,6 +91,18 @@ int td_mol_summarise(const td_census_entry* entries, int64_t n, td_mol_row rows[
  * td_last_error(NULL)'s. */
 int td_mol_host   (const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
                    const td_read_result* res, const int8_t* labels, td_census_entry** entries, int64_t* n, td_mol_totals* totals);
+/* Dedup, see above.  td_mol_dedup_enable: TD_FAIL with a message unless the count is on (td_mol_enable first) and no td_submit
+ * tickets are outstanding; it allocates 8 more bytes per slot and starts from an empty table (it does what td_mol_reset does).
+ * td_mol_disable, and with it a new model, switches it off as well. */
+typedef struct td_mol_dedup_totals { int64_t kept, duplicates, unjudged; } td_mol_dedup_totals;
+int td_mol_dedup_enable (td_ctx* ctx);
+int td_mol_dedup_disable(td_ctx* ctx);              /* frees the first ordinals; table and count stay as they are */
+int td_mol_dedup_get    (td_ctx* ctx, td_mol_dedup_totals* totals);   /* waits for the context's queued work */
+/* the same decision from host arrays, no GPU, the reads in the given order (read i has ordinal i): is_duplicate[i] = 1 for a
+ * duplicate, else 0.  For hosts without a GPU and as the yardstick of the device path.  Arguments as td_mol_host takes them.
+ * Never overflows.  totals may be NULL. */
+int td_mol_dedup_host   (const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                         const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate, td_mol_dedup_totals* totals);
 /* the key of a counted read: its record's barcode and fingerprint, its prefix word w of n bases (1..32) */
 uint64_t td_mol_key(int32_t barcode, int32_t fingerprint, uint64_t w, int32_t n);
 int32_t  td_mol_key_bin(uint64_t key);              /* the barcode bin a key belongs to */

@@ -74,6 +74,9 @@ typedef struct td_run_opts {
 	                                    (tagdust_molecules.h) go to <out>_molecules.txt; one input file only */
 	int32_t  molecules_prefix;       /* --molecules-prefix P   [20]: read bases that tell molecules apart beside barcode and fingerprint, 1..32 */
 	int32_t  molecules_slots_log2;   /* --molecules-slots N    [26]: the counting table of every device has 2^N slots, 4..30 */
+	int32_t  dedup;                  /* --dedup: one read per molecule is written (tagdust_molecules.h, td_mol_dedup_enable): an extracted
+	                                    read that is not the first of its molecule goes to no file.  Implies --molecules (the parser sets
+	                                    it); one input file, one device */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -96,7 +99,10 @@ const char* td_run_version(void);
  * existing-output check (io.c:633-691: made when a file holds a barcode, like the reference's; skipped with `force`; with
  * --unknown-barcodes <out>_unknown_barcodes.txt is one of the output files, and the option is refused with -start / -end; with
  * --molecules <out>_molecules.txt is one, and the option is refused with -start / -end, with several input files -- the read and
- * its UMI then sit in different files' contexts -- and for a read-only architecture, which has no model), the
+ * its UMI then sit in different files' contexts -- and for a read-only architecture, which has no model; --dedup implies
+ * --molecules, is refused wherever that is and with more than one device -- each has its own table, a molecule split over two
+ * would survive twice -- and adds two lines, "# written" and "# duplicates removed", to <out>_molecules.txt and nothing to the
+ * log, the _un file or the counts), the
  * multiread rule (interface.c:441-450: DUST and -ref off, with a warning, when the command line's architecture has two or more
  * R segments).  What depends on the arch file's choice is decided again by td_run_execute once the choice is made. */
 typedef struct td_run_plan_t td_run_plan_t;   /* (the function below has the plain name) */
@@ -134,6 +140,8 @@ typedef struct td_run_report {
 	td_mol_row* molecules;                    /* --molecules: [TD_NUM_BARCODE_BINS] one row per barcode bin (NULL without the option):
 	                                             one device's own summary (td_mol_get), or td_mol_summarise of the devices' merged entries */
 	td_mol_totals molecules_totals;           /* summed over the devices; molecules = distinct keys after the merge */
+	int32_t  dedup;                           /* 1: the run removed duplicates (--dedup) */
+	td_mol_dedup_totals dedup_totals;         /* --dedup: extracted reads written, duplicates removed, reads that could not be judged */
 } td_run_report;
 /* In the controller's order: architectures per file, statistics over each file's head, thresholds, models, the run, the log.
  * A failure before the first batch leaves no output files behind; one during the run leaves them as they are and says so.  The

@@ -370,6 +370,8 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	if (!strcmp(name, "census_kernel_us")) return census_last_kernel_us(c, value);   // the count kernel's time of the last counted batch
 	if (!strcmp(name, "molecules_active")) { *value = c->molecules.on; return TD_OK; }
 	if (!strcmp(name, "molecules_kernel_us")) return mol_last_kernel_us(c, value);
+	if (!strcmp(name, "dedup_active")) { *value = c->molecules.dedup; return TD_OK; }
+	if (!strcmp(name, "dedup_kernel_us")) return mol_dedup_last_kernel_us(c, value);   // the two passes of the last batch
 	if (!strcmp(name, "overlap_active")) {
 		// pipelined batches alternate between two compute streams / workspaces (off: option, generic kernel, depth 1, or HBM
 		// could not hold the second workspace)
@@ -519,7 +521,7 @@ static int slot_events(td_ctx* c, TdSlot& s)
 static void slot_release(TdSlot& s)
 {
 	void* dev[] = { s.d_raw, s.d_offs, s.d_read_at, s.d_keys, s.d_vals, s.d_sort_tmp, s.d_packed, s.d_lens, s.d_art_left,
-	                s.d_out, s.d_res, s.d_seq, s.d_lab, s.d_keepo, s.d_rle, s.d_runs };
+	                s.d_out, s.d_res, s.d_seq, s.d_lab, s.d_keepo, s.d_rle, s.d_runs, s.d_judged };
 	for (void* p : dev) if (p) (void)hipFree(p);
 	void* pinned[] = { s.h_raw, s.h_offs, s.h_res, s.h_seq, s.h_lab, s.h_keepo, s.h_rle };
 	for (void* p : pinned) if (p) (void)hipHostFree(p);
@@ -844,6 +846,8 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	if (ka.art_n > 0 && slot_count_hits(c, s, ka.out_type) != TD_OK) return TD_FAIL;
 	if (c->census.on && mode == TD_MODE_GET_LABEL && census_count_slot(c, s, ka.out_type, ka.out_labels) != TD_OK) return TD_FAIL;
 	if (c->molecules.on && mode == TD_MODE_GET_LABEL && mol_count_slot(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
+	// dedup last: its second pass rewrites the outcomes the three counts above read
+	if (c->molecules.dedup && mode == TD_MODE_GET_LABEL && mol_dedup_slot(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
 	s.ran = true;
 	s.last_ms = -1.0f;
 	c->last_slot = (int)(&s - c->slots);

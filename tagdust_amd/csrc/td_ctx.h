@@ -94,6 +94,7 @@ struct TdSlot : TdStaged, TdDecoded, TdFetch {
 	uint32_t* d_keepo = nullptr;   size_t cap_keepo = 0;
 	uint32_t* d_rle = nullptr;     size_t cap_rle = 0;     // (+ one word behind the runs: the overflow flag)
 	uint32_t* d_runs = nullptr;    size_t cap_runs = 0;    // label runs in device order, left by the specialised kernel (+ the overflow flag)
+	int32_t* d_judged = nullptr;   size_t cap_judged = 0;  // dedup: every read's slot in the molecule table between its two passes (-1: not judged)
 	uint32_t* h_keepo = nullptr;   size_t cap_h_keepo = 0;
 	uint32_t* h_rle = nullptr;     size_t cap_h_rle = 0;
 	// pinned host staging for pageable caller memory

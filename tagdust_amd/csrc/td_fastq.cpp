@@ -262,6 +262,7 @@ static void format_range(const td_writer* w, const td_reads* rd, const td_read_r
 	char head[64], finger[256];
 	std::string seq, qual;
 	for (int64_t i = lo; i < hi; i++) {
+		if ((res[i].read_type & 0xFF) == TD_EXTRACT_DUPLICATE) continue;   // dedup: not the first read of its molecule, and no failure either
 		size_t f; // io.c:923-934
 		if (res[i].read_type == TD_EXTRACT_SUCCESS) f = (res[i].barcode != -1) ? (size_t)(res[i].barcode & 0xFF) : 0;
 		else f = (size_t)w->num_alternatives - 1;

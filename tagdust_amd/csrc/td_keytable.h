@@ -81,6 +81,21 @@ __device__ __forceinline__ void kt_probe_add(const TdKeyTable& t, kt_u64 key, in
 	}
 }
 
+// The slot that holds `key`, -1 when the table does not: a plain probe for a kernel queued behind the one that added the key.  The
+// key then sits in its window for good or has failed for good (nothing is removed, and a key claims the first empty slot of its
+// window: no empty slot lies in front of it).
+__device__ __forceinline__ int32_t kt_probe_find(const TdKeyTable& t, kt_u64 key)
+{
+	const uint32_t h = kt_hash(key);
+	for (uint32_t i = 0; i < t.window; i++) {
+		const uint32_t slot = (h + i) & t.slot_mask;
+		const kt_u64 cur = __hip_atomic_load(&t.keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		if (cur == key) return (int32_t)slot;
+		if (cur == 0ull) return -1;
+	}
+	return -1;
+}
+
 // the occupied (key, count) pairs into a dense array: one add on the cursor per wave, the lanes behind it by their rank
 static __global__ __launch_bounds__(KT_BLOCK) void td_keytable_compact_kernel(const kt_u64* __restrict__ keys, const kt_u64* __restrict__ counts,
                                                                                 int64_t n_slots, td_census_entry* __restrict__ out, int64_t cap,

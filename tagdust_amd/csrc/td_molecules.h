@@ -9,8 +9,10 @@
 struct td_ctx;
 struct TdSlot;
 
-// tallies of the device table, 64 bits each, in the order of td_mol_totals; behind them the compaction's cursor
-enum { TDM_ELIGIBLE = 0, TDM_COUNTED, TDM_EMPTY, TDM_N, TDM_OVERFLOW, TDM_MOLECULES, TDM_CURSOR, TDM_TALLY_WORDS };
+// tallies of the device table, 64 bits each, in the order of td_mol_totals; behind them the compaction's cursor, then dedup's
+// three in the order of td_mol_dedup_totals
+enum { TDM_ELIGIBLE = 0, TDM_COUNTED, TDM_EMPTY, TDM_N, TDM_OVERFLOW, TDM_MOLECULES, TDM_CURSOR, TDM_KEPT, TDM_DUPLICATES, TDM_UNJUDGED,
+       TDM_TALLY_WORDS };
 // words of a barcode bin's summary row: reads, molecules, ten levels (td_mol_row)
 #define TDM_ROW_WORDS 12
 
@@ -26,6 +28,14 @@ struct TdMolState {
 	unsigned long long* d_tallies = nullptr;  // [TDM_TALLY_WORDS]
 	unsigned long long* d_rows = nullptr;     // [TD_NUM_BARCODE_BINS][TDM_ROW_WORDS] the summary sweep's result
 	hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   // around the last count launch (option "molecules_kernel_us")
+	// dedup (td_mol_dedup_enable): the first ordinal of every slot's key, and what orders the two passes of neighbouring batches
+	bool dedup = false;
+	unsigned long long* d_first = nullptr;    // [2^log2_slots], all-ones = no read yet
+	int64_t next_ordinal = 0;                 // reads submitted in TD_MODE_GET_LABEL since dedup was enabled or last reset
+	hipEvent_t ev_p1[2] = { nullptr, nullptr };   // behind pass 1 of the last batch ([turn ^ 1]) and of the one before it ([turn])
+	bool p1_queued[2] = { false, false };
+	int turn = 0;
+	hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr;   // around the two passes of the last batch (option "dedup_kernel_us")
 };
 
 struct TdMolArgs {
@@ -41,11 +51,22 @@ struct TdMolArgs {
 	int32_t n_tiles, lmax, nw2, nw1, H, prefix;
 	TdKeyTable table;
 	unsigned long long* __restrict__ tallies;
+	// dedup's pass 1 alone
+	const int32_t* __restrict__ read_at;      // [n_reads] device position -> index in the caller's order (NULL: the same)
+	unsigned long long* __restrict__ first;   // [slot_mask + 1] the smallest ordinal of every slot's key
+	int32_t* __restrict__ judged;             // [n_tiles*64] the read's table slot, -1 = not judged
+	int64_t ordinal_base;                     // the ordinal of the batch's first read in the caller's order
 };
 
 // the count of one decoded slot, queued on its compute stream (td_api.hip calls it behind the decode launch while the count is on)
 __attribute__((visibility("hidden"))) int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode,
                                                          const int32_t* out_finger, const int8_t* labels);
+// dedup's two passes over one decoded slot, queued behind its count (td_api.hip calls it last in slot_decode while dedup is on):
+// pass 2 rewrites out_type, so everything that reads the decoded outcomes is queued in front of it
+__attribute__((visibility("hidden"))) int mol_dedup_slot(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode,
+                                                         const int32_t* out_finger, const int8_t* labels);
+// option "dedup_kernel_us" of td_get_option: the two passes' time of the last batch (waits for it)
+__attribute__((visibility("hidden"))) int mol_dedup_last_kernel_us(td_ctx* c, int32_t* us);
 // option "molecules_kernel_us" of td_get_option: the count kernel's time of the last counted batch (waits for it)
 __attribute__((visibility("hidden"))) int mol_last_kernel_us(td_ctx* c, int32_t* us);
 // table and label copy freed, count off (the caller has made sure nothing of it is queued any more)

@@ -8,12 +8,20 @@
 // add per read), not the heavy hitter the census merges away -- the merge of equal keys in a wave stays, PCR copies sit together
 // often enough.  A second kernel sweeps the table into one summary row per barcode bin (td_mol_get).  td_mol_host is the same
 // definition over host arrays (no GPU), td_mol_summarise the same summary from entries.
+//
+// Dedup (td_mol_dedup_enable) adds two launches behind the count.  Pass 1 builds every read's key again -- mol_lane_key is the one
+// text the count and it share --, finds the slot the count left the key in and lowers first[slot] to the read's ordinal, its
+// number in the caller's order over the whole context.  Pass 2 marks every read whose ordinal is not its slot's first as
+// TD_EXTRACT_DUPLICATE.  The minimum does not depend on the order the reads arrive in, so the two passes of neighbouring batches
+// may overlap but for one thing: pass 2 waits for pass 1 of the batch before it (an event), since that batch holds smaller
+// ordinals.  td_mol_dedup_host is the same decision on the host.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <string>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/tagdust_molecules.h"
@@ -31,23 +39,28 @@ __host__ __device__ __forceinline__ kt_u64 mol_key(int32_t barcode, int32_t fing
 	return (bin << 56) | low;
 }
 
-__global__ __launch_bounds__(KT_BLOCK) void td_mol_count_kernel(const TdMolArgs a)
+// per label: 1 = it belongs to an 'R' segment (the whole workgroup; ends in its barrier)
+__device__ __forceinline__ void mol_r_labels(const TdMolArgs& a, uint8_t* s_r)
 {
-	// per label: 1 = it belongs to an 'R' segment
-	__shared__ uint8_t s_r[128];
 	for (int h = threadIdx.x; h < 128; h += KT_BLOCK) {
 		uint8_t v = 0;
 		if (h < a.H) { const int seg = a.label[h] & 0xFFFF; v = seg < 64 ? (uint8_t)((a.r_segs >> seg) & 1ull) : 0; }
 		s_r[h] = v;
 	}
 	__syncthreads();
-	const int lane = threadIdx.x & (TD_WAVE - 1);
-	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
-	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
-	const int64_t k = (int64_t)tile * TD_WAVE + lane;
+}
+
+// what a lane's read is to the count: eligible, and then exactly one of the three classes (has_key: counted under `key`)
+struct MolLane { bool elig, is_empty, is_n, has_key; kt_u64 key; };
+
+// The key of read k = tile * 64 + lane: the label walk, the prefix word and the N mask (whole waves).  false: no lane of the wave
+// is eligible, nothing else was read.  The count kernel and dedup's pass 1 both call this: one text.
+__device__ __forceinline__ bool mol_lane_key(const TdMolArgs& a, const uint8_t* s_r, int tile, int lane, int64_t k, MolLane& m)
+{
 	bool elig = false;
 	if (k < a.n_reads) elig = ((uint32_t)a.out_type[k] & 0xFFu) == (uint32_t)TD_EXTRACT_SUCCESS;   // the outcome first: the other lanes read nothing more
-	if (__builtin_amdgcn_ballot_w64(elig) == 0ull) return;
+	m.elig = elig; m.is_empty = false; m.is_n = false; m.has_key = false; m.key = 0ull;
+	if (__builtin_amdgcn_ballot_w64(elig) == 0ull) return false;
 	int len = 0, barcode = -1, finger = -1;
 	if (elig) { len = a.lens[k]; barcode = a.out_barcode[k]; finger = a.out_finger[k]; }
 	int tmax = len;
@@ -74,10 +87,25 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_count_kernel(const TdMolArgs 
 			if (p + 1 >= len) active = false;
 		}
 	}
-	const bool is_empty = elig && n == 0;
-	const bool is_n = elig && n > 0 && has_n;
-	const bool has_key = elig && n > 0 && !has_n;
-	const kt_u64 key = has_key ? mol_key(barcode, finger, w, n) : 0ull;
+	m.is_empty = elig && n == 0;
+	m.is_n = elig && n > 0 && has_n;
+	m.has_key = elig && n > 0 && !has_n;
+	m.key = m.has_key ? mol_key(barcode, finger, w, n) : 0ull;
+	return true;
+}
+
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_count_kernel(const TdMolArgs a)
+{
+	__shared__ uint8_t s_r[128];
+	mol_r_labels(a, s_r);
+	const int lane = threadIdx.x & (TD_WAVE - 1);
+	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
+	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
+	const int64_t k = (int64_t)tile * TD_WAVE + lane;
+	MolLane m;
+	if (!mol_lane_key(a, s_r, tile, lane, k, m)) return;
+	const bool elig = m.elig, is_empty = m.is_empty, is_n = m.is_n, has_key = m.has_key;
+	const kt_u64 key = m.key;
 
 	// lanes with the same key leave as one, the wave's distinct keys probe side by side (td_keytable.h)
 	const int mine = kt_wave_merge(has_key, key, lane);
@@ -97,6 +125,61 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_count_kernel(const TdMolArgs 
 		if (n_n) atomicAdd(&a.tallies[TDM_N], (kt_u64)n_n);
 		if (n_over) atomicAdd(&a.tallies[TDM_OVERFLOW], (kt_u64)n_over);
 		if (n_fresh) atomicAdd(&a.tallies[TDM_MOLECULES], (kt_u64)n_fresh);
+	}
+}
+
+// Dedup, pass 1: behind the count kernel of the same batch on the same stream, so a counted read's key is in the table or has
+// overflowed for good and a plain probe finds which.  Leaves every lane's slot (-1: not judged, not eligible included) for pass 2
+// and lowers the slot's first ordinal to the read's own.
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_first_kernel(const TdMolArgs a)
+{
+	__shared__ uint8_t s_r[128];
+	mol_r_labels(a, s_r);
+	const int lane = threadIdx.x & (TD_WAVE - 1);
+	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
+	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
+	const int64_t k = (int64_t)tile * TD_WAVE + lane;
+	MolLane m;
+	int32_t slot = -1;
+	if (mol_lane_key(a, s_r, tile, lane, k, m) && m.has_key) {
+		slot = kt_probe_find(a.table, m.key);
+		if (slot >= 0) {
+			const int64_t at = a.read_at ? (int64_t)a.read_at[k] : k;     // the caller's order, not the length-sorted one
+			atomicMin(&a.first[slot], (kt_u64)(a.ordinal_base + at));
+		}
+	}
+	a.judged[k] = slot;                               // (judged has n_tiles * 64 words)
+}
+
+// Dedup, pass 2: a judged read whose ordinal is not its slot's first is a duplicate.  Every pass 1 that could still lower that
+// first -- this batch's and every earlier one's -- has finished (stream order and the event of the batch before).
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_mark_kernel(int32_t* __restrict__ out_type, const int32_t* __restrict__ judged,
+                                                                const int32_t* __restrict__ read_at, const kt_u64* first, int64_t ordinal_base,
+                                                                int64_t n_reads, int32_t n_tiles, kt_u64* __restrict__ tallies)
+{
+	const int lane = threadIdx.x & (TD_WAVE - 1);
+	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
+	if (tile >= n_tiles) return;
+	const int64_t k = (int64_t)tile * TD_WAVE + lane;
+	int32_t type = 0;
+	bool elig = false;
+	if (k < n_reads) { type = out_type[k]; elig = ((uint32_t)type & 0xFFu) == (uint32_t)TD_EXTRACT_SUCCESS; }
+	if (__builtin_amdgcn_ballot_w64(elig) == 0ull) return;
+	const int32_t slot = elig ? judged[k] : -1;
+	bool dup = false;
+	if (slot >= 0) {
+		const int64_t at = read_at ? (int64_t)read_at[k] : k;
+		dup = __hip_atomic_load(&first[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (kt_u64)(ordinal_base + at);
+	}
+	if (dup) out_type[k] = (int32_t)(((uint32_t)type & ~0xFFu) | (uint32_t)TD_EXTRACT_DUPLICATE);
+	// tallies: one add per wave and tally
+	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig));
+	const int n_dup = __builtin_popcountll(__builtin_amdgcn_ballot_w64(dup));
+	const int n_unjudged = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig && slot < 0));
+	if (lane == 0) {
+		if (n_elig - n_dup) atomicAdd(&tallies[TDM_KEPT], (kt_u64)(n_elig - n_dup));
+		if (n_dup) atomicAdd(&tallies[TDM_DUPLICATES], (kt_u64)n_dup);
+		if (n_unjudged) atomicAdd(&tallies[TDM_UNJUDGED], (kt_u64)n_unjudged);
 	}
 }
 
@@ -133,6 +216,34 @@ namespace {
 
 bool prefix_ok(int32_t p) { return p >= 1 && p <= TD_MOL_MAX_PREFIX; }
 
+// what read i is to the count on the host (td_mol_host and td_mol_dedup_host): not eligible, or one of the three classes; *key of
+// a counted read
+enum { MOL_NOT_ELIGIBLE = 0, MOL_EMPTY, MOL_HAS_N, MOL_COUNTED };
+int host_read_class(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t i,
+                    const td_read_result* res, const int8_t* labels, uint64_t* key)
+{
+	if (((uint32_t)res[i].read_type & 0xFFu) != (uint32_t)TD_EXTRACT_SUCCESS) return MOL_NOT_ELIGIBLE;
+	const int64_t len = offs[i + 1] - offs[i];
+	const int8_t* lab = labels + offs[i] + i;
+	const uint8_t* seq = codes + offs[i];
+	uint64_t w = 0;
+	int cnt = 0;
+	bool has_n = false;
+	for (int64_t p = 0; p < len && cnt < prefix_bases; p++) {
+		const int l = lab[p + 1];
+		if (l < 0 || l >= m->H) continue;
+		const int seg = m->label[l] & 0xFFFF;
+		if (seg >= m->S || m->seg_type[seg] != 'R') continue;
+		cnt++;
+		if (seq[p] > 3) has_n = true;
+		w = (w << 2) | (uint64_t)(seq[p] & 3u);
+	}
+	if (cnt == 0) return MOL_EMPTY;
+	if (has_n) return MOL_HAS_N;
+	*key = mol_key(res[i].barcode, res[i].fingerprint, w, cnt);
+	return MOL_COUNTED;
+}
+
 void totals_from(const kt_u64* t, td_mol_totals* out)
 {
 	out->eligible = (int64_t)t[TDM_ELIGIBLE]; out->counted = (int64_t)t[TDM_COUNTED]; out->skipped_empty = (int64_t)t[TDM_EMPTY];
@@ -144,16 +255,17 @@ void totals_from(const kt_u64* t, td_mol_totals* out)
 void mol_release(td_ctx* c)
 {
 	TdMolState& z = c->molecules;
-	void* p[] = { z.d_label, z.d_keys, z.d_counts, z.d_tallies, z.d_rows };
+	void* p[] = { z.d_label, z.d_keys, z.d_counts, z.d_tallies, z.d_rows, z.d_first };
 	for (void* q : p) if (q) (void)hipFree(q);
-	hipEvent_t ev[] = { z.ev_c0, z.ev_c1 };
+	hipEvent_t ev[] = { z.ev_c0, z.ev_c1, z.ev_p1[0], z.ev_p1[1], z.ev_d0, z.ev_d1 };
 	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
 	z = TdMolState();
 }
 
-int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
+// what the count kernel and dedup's pass 1 read of a decoded slot
+static TdMolArgs mol_args(const TdMolState& z, const TdSlot& s, const int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger,
+                          const int8_t* labels)
 {
-	const TdMolState& z = c->molecules;
 	TdMolArgs a{};
 	a.packed = s.d_packed; a.lens = s.d_lens; a.out_type = out_type; a.out_barcode = out_barcode; a.out_finger = out_finger;
 	a.labels = labels; a.label = z.d_label;
@@ -163,6 +275,13 @@ int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t*
 	a.table.slot_mask = (uint32_t)(n_slots - 1);
 	a.table.window = (uint32_t)std::min<uint64_t>(n_slots, KT_PROBE_WINDOW);
 	a.table.keys = z.d_keys; a.table.counts = z.d_counts; a.tallies = z.d_tallies;
+	return a;
+}
+
+int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
+{
+	const TdMolState& z = c->molecules;
+	const TdMolArgs a = mol_args(z, s, out_type, out_barcode, out_finger, labels);
 	HIPCHK(c, hipEventRecord(z.ev_c0, s.cs));
 	if (a.n_tiles > 0) {
 		const unsigned blocks = (unsigned)((a.n_tiles + KT_WAVES - 1) / KT_WAVES);
@@ -171,6 +290,36 @@ int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t*
 	}
 	HIPCHK(c, hipEventRecord(z.ev_c1, s.cs));
 	// the finish kernel waits for ev_hits: a slot whose batch has been waited for is no longer read by this count either
+	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));
+	s.hits_queued = true;
+	return TD_OK;
+}
+
+int mol_dedup_slot(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
+{
+	TdMolState& z = c->molecules;
+	const int64_t base = z.next_ordinal;              // batches get their ordinals in the order they are submitted in
+	z.next_ordinal += s.n_reads;
+	if (s.n_tiles <= 0) return TD_OK;
+	if (ensure(c, &s.d_judged, &s.cap_judged, (size_t)s.n_tiles * TD_WAVE * sizeof(int32_t)) != TD_OK) return TD_FAIL;
+	TdMolArgs a = mol_args(z, s, out_type, out_barcode, out_finger, labels);
+	a.read_at = s.sorted ? s.d_read_at : nullptr; a.first = z.d_first; a.judged = s.d_judged; a.ordinal_base = base;
+	const unsigned blocks = (unsigned)((a.n_tiles + KT_WAVES - 1) / KT_WAVES);
+	HIPCHK(c, hipEventRecord(z.ev_d0, s.cs));
+	hipLaunchKernelGGL(td_mol_first_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
+	HIPCHK(c, hipGetLastError());
+	// The batch before this one may run on the other compute stream, and it holds the smaller ordinals: its pass 1 has to be over
+	// before this batch's pass 2 reads a first ordinal.  (The batch before that one ran on this stream, or was waited for.)
+	const int t = z.turn;
+	HIPCHK(c, hipEventRecord(z.ev_p1[t], s.cs));
+	z.p1_queued[t] = true;
+	if (z.p1_queued[t ^ 1]) HIPCHK(c, hipStreamWaitEvent(s.cs, z.ev_p1[t ^ 1], 0));
+	z.turn = t ^ 1;
+	hipLaunchKernelGGL(td_mol_mark_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, out_type, (const int32_t*)s.d_judged, a.read_at,
+	                   (const kt_u64*)z.d_first, base, a.n_reads, a.n_tiles, z.d_tallies);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(z.ev_d1, s.cs));
+	// the finish kernel copies out_type only behind pass 2, and the slot is not restaged under it
 	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));
 	s.hits_queued = true;
 	return TD_OK;
@@ -235,8 +384,66 @@ extern "C" int td_mol_reset(td_ctx* c)
 	const size_t n_slots = (size_t)1 << z.log2_slots;
 	HIPCHK(c, hipMemsetAsync(z.d_keys, 0, sizeof(kt_u64) * n_slots, c->stream));
 	HIPCHK(c, hipMemsetAsync(z.d_counts, 0, sizeof(kt_u64) * n_slots, c->stream));
-	HIPCHK(c, hipMemsetAsync(z.d_tallies, 0, sizeof(kt_u64) * TDM_TALLY_WORDS, c->stream));
+	HIPCHK(c, hipMemsetAsync(z.d_tallies, 0, sizeof(kt_u64) * TDM_TALLY_WORDS, c->stream));   // (dedup's three among them)
+	if (z.dedup) HIPCHK(c, hipMemsetAsync(z.d_first, 0xFF, sizeof(kt_u64) * n_slots, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
+	z.next_ordinal = 0;
+	z.p1_queued[0] = z.p1_queued[1] = false;          // (nothing is queued any more)
+	return TD_OK;
+}
+
+extern "C" int td_mol_dedup_enable(td_ctx* c)
+{
+	if (!c) return fail(nullptr, "td_mol_dedup_enable: no context");
+	TdMolState& z = c->molecules;
+	if (!z.on) return fail(c, "td_mol_dedup_enable: the molecule count is off (td_mol_enable first): dedup judges the reads the count has keyed");
+	for (int k = 0; k < TD_MAX_PIPELINE; k++)
+		if (c->slots[k].ticket) return fail(c, "td_mol_dedup_enable: td_submit tickets are outstanding (td_wait them first)");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	if (!z.dedup) {
+		const size_t n_slots = (size_t)1 << z.log2_slots;
+		bool ok = hipMalloc((void**)&z.d_first, sizeof(kt_u64) * n_slots) == hipSuccess &&
+		          hipEventCreateWithFlags(&z.ev_p1[0], hipEventDisableTiming) == hipSuccess &&
+		          hipEventCreateWithFlags(&z.ev_p1[1], hipEventDisableTiming) == hipSuccess &&
+		          hipEventCreate(&z.ev_d0) == hipSuccess && hipEventCreate(&z.ev_d1) == hipSuccess;
+		if (!ok) {
+			const std::string e = hipGetErrorString(hipGetLastError());
+			(void)td_mol_dedup_disable(c);
+			return fail(c, "td_mol_dedup_enable: the first ordinals of 2^%d slots could not be set up: %s", z.log2_slots, e.c_str());
+		}
+		z.dedup = true;
+	}
+	return td_mol_reset(c);   // a first ordinal belongs to a key that entered the table with it: both start empty
+}
+
+extern "C" int td_mol_dedup_disable(td_ctx* c)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (!z.dedup && !z.d_first && !z.ev_p1[0] && !z.ev_p1[1] && !z.ev_d0 && !z.ev_d1) return TD_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	if (z.d_first) (void)hipFree(z.d_first);
+	hipEvent_t ev[] = { z.ev_p1[0], z.ev_p1[1], z.ev_d0, z.ev_d1 };
+	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+	z.d_first = nullptr; z.ev_p1[0] = z.ev_p1[1] = z.ev_d0 = z.ev_d1 = nullptr;
+	z.p1_queued[0] = z.p1_queued[1] = false;
+	z.dedup = false;
+	return TD_OK;
+}
+
+extern "C" int td_mol_dedup_get(td_ctx* c, td_mol_dedup_totals* totals)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (!z.dedup) return fail(c, "td_mol_dedup_get: dedup is off (td_mol_dedup_enable)");
+	if (!totals) return fail(c, "td_mol_dedup_get: bad arguments");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	kt_u64 t[TDM_TALLY_WORDS];
+	HIPCHK(c, hipMemcpy(t, z.d_tallies, sizeof t, hipMemcpyDeviceToHost));
+	totals->kept = (int64_t)t[TDM_KEPT]; totals->duplicates = (int64_t)t[TDM_DUPLICATES]; totals->unjudged = (int64_t)t[TDM_UNJUDGED];
 	return TD_OK;
 }
 
@@ -305,6 +512,22 @@ int mol_last_kernel_us(td_ctx* c, int32_t* us)
 	return TD_OK;
 }
 
+// the two passes' time of the last batch (option "dedup_kernel_us" of td_get_option).  Between them the stream waits for the batch
+// before: with batches in flight on both compute streams that wait is inside the figure, after a td_run it is not.
+int mol_dedup_last_kernel_us(td_ctx* c, int32_t* us)
+{
+	TdMolState& z = c->molecules;
+	if (!z.dedup) return fail(c, "td_get_option: dedup_kernel_us: dedup is off");
+	HIPCHK(c, hipSetDevice(c->device));
+	float ms = 0.0f;
+	if (hipEventSynchronize(z.ev_d1) != hipSuccess || hipEventElapsedTime(&ms, z.ev_d0, z.ev_d1) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(c, "td_get_option: dedup_kernel_us: no batch has been judged yet");
+	}
+	*us = (int32_t)(ms * 1000.0f + 0.5f);
+	return TD_OK;
+}
+
 extern "C" int td_mol_summarise(const td_census_entry* entries, int64_t n, td_mol_row rows[TD_NUM_BARCODE_BINS])
 {
 	if (!rows || n < 0 || (n > 0 && !entries)) return fail(nullptr, "td_mol_summarise: bad arguments");
@@ -330,32 +553,40 @@ extern "C" int td_mol_host(const td_model_desc* m, int32_t prefix_bases, const u
 	td_mol_totals t{};
 	std::vector<uint64_t> keys;
 	for (int64_t i = 0; i < n_reads; i++) {
-		if (((uint32_t)res[i].read_type & 0xFFu) != (uint32_t)TD_EXTRACT_SUCCESS) continue;
+		uint64_t key = 0;
+		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key);
+		if (cls == MOL_NOT_ELIGIBLE) continue;
 		t.eligible++;
-		const int64_t len = offs[i + 1] - offs[i];
-		const int8_t* lab = labels + offs[i] + i;
-		const uint8_t* seq = codes + offs[i];
-		uint64_t w = 0;
-		int cnt = 0;
-		bool has_n = false;
-		for (int64_t p = 0; p < len && cnt < prefix_bases; p++) {
-			const int l = lab[p + 1];
-			if (l < 0 || l >= m->H) continue;
-			const int seg = m->label[l] & 0xFFFF;
-			if (seg >= m->S || m->seg_type[seg] != 'R') continue;
-			cnt++;
-			if (seq[p] > 3) has_n = true;
-			w = (w << 2) | (uint64_t)(seq[p] & 3u);
-		}
-		if (cnt == 0) t.skipped_empty++;
-		else if (has_n) t.skipped_n++;
-		else { keys.push_back(mol_key(res[i].barcode, res[i].fingerprint, w, cnt)); t.counted++; }
+		if (cls == MOL_EMPTY) t.skipped_empty++;
+		else if (cls == MOL_HAS_N) t.skipped_n++;
+		else { keys.push_back(key); t.counted++; }
 	}
 	std::vector<td_census_entry> v;
 	census_tally_keys(keys, v);
 	t.molecules = (int64_t)v.size();
 	if (!(*entries = census_copy_entries(v))) return fail(nullptr, "td_mol_host: out of memory");
 	*n = (int64_t)v.size();
+	if (totals) *totals = t;
+	return TD_OK;
+}
+
+extern "C" int td_mol_dedup_host(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                                 const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate, td_mol_dedup_totals* totals)
+{
+	if (!m || m->S < 1 || m->H < 1 || !m->seg_type || !m->label) return fail(nullptr, "td_mol_dedup_host: no model");
+	if (!prefix_ok(prefix_bases)) return fail(nullptr, "td_mol_dedup_host: prefix_bases = %d (1..%d supported)", prefix_bases, TD_MOL_MAX_PREFIX);
+	if (n_reads < 0 || (n_reads > 0 && (!offs || !res || !labels || !codes || !is_duplicate))) return fail(nullptr, "td_mol_dedup_host: bad arguments");
+	td_mol_dedup_totals t{};
+	std::unordered_set<uint64_t> seen;                // the keys of the reads so far: a read's ordinal is its index, the first one stays
+	for (int64_t i = 0; i < n_reads; i++) {
+		is_duplicate[i] = 0;
+		uint64_t key = 0;
+		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key);
+		if (cls == MOL_NOT_ELIGIBLE) continue;
+		if (cls != MOL_COUNTED) { t.unjudged++; t.kept++; continue; }
+		if (seen.insert(key).second) t.kept++;
+		else { is_duplicate[i] = 1; t.duplicates++; }
+	}
 	if (totals) *totals = t;
 	return TD_OK;
 }

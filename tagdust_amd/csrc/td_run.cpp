@@ -168,7 +168,7 @@ bool read_arch_file(const char* path, ArchFile& af, std::string& why)
 struct OptSpec { const char* name; int arg; int id; };
 enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
-       O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS,
+       O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS, O_DEDUP,
        O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
@@ -194,7 +194,7 @@ const OptSpec kOwnOpts[] = {
 	{ "sync-compile", 0, O_SYNC_COMPILE }, { "stats-on-host", 0, O_STATS_ON_HOST }, { "force", 0, O_FORCE }, { "dry-run", 0, O_DRY_RUN },
 	{ "unknown-barcodes", 1, O_UNKNOWN }, { "unknown-barcodes-slots", 1, O_UNKNOWN_SLOTS },
 	{ "fingerprint-seq", 0, O_FINGER_SEQ }, { "molecules", 0, O_MOLECULES }, { "molecules-prefix", 1, O_MOLECULES_PREFIX },
-	{ "molecules-slots", 1, O_MOLECULES_SLOTS },
+	{ "molecules-slots", 1, O_MOLECULES_SLOTS }, { "dedup", 0, O_DEDUP },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -288,7 +288,9 @@ extern "C" const char* td_run_usage(void)
 	       "\t--molecules                 reads, molecules, duplication rate and duplication levels per barcode, counted by\n"
 	       "\t                            barcode, fingerprint and start of the read, into <output prefix>_molecules.txt\n"
 	       "\t--molecules-prefix P        bases of the read that belong to a molecule's identity, 1..32 [20]\n"
-	       "\t--molecules-slots N         slots of the counting table on every device, as a power of two, 4..30 [26]\n\n";
+	       "\t--molecules-slots N         slots of the counting table on every device, as a power of two, 4..30 [26]\n"
+	       "\t--dedup                     write one read per molecule: an extracted read that is not the first of its molecule in\n"
+	       "\t                            the input goes to no output file (implies --molecules; one input file, one device)\n\n";
 }
 
 extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
@@ -358,9 +360,11 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 		case O_MOLECULES: o->molecules = 1; break;
 		case O_MOLECULES_PREFIX: o->molecules_prefix = atoi(v); break;
 		case O_MOLECULES_SLOTS: o->molecules_slots_log2 = atoi(v); break;
+		case O_DEDUP: o->dedup = 1; break;
 		default: return bad("unknown option " + a);
 		}
 	}
+	if (o->dedup) o->molecules = 1;   // the duplicates are those of the molecule count
 	if (o->num_threads < 1) return bad("option -t: need at least one thread");
 	if (o->host_threads < 0 || o->batch_reads < 0) return bad("--host-threads / --batch-reads: negative value");
 	if (o->unknown_slots_log2 < 4 || o->unknown_slots_log2 > 26) return bad("--unknown-barcodes-slots: need 4..26 (the table has 2^N slots)");
@@ -388,6 +392,7 @@ struct td_run_plan_t {
 	std::vector<std::string> warnings;
 	int dust = 0;
 	bool use_ref = false;
+	bool dedup = false;
 };
 
 namespace {
@@ -455,6 +460,10 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 		return run_fail("--molecules needs exactly one input file (%d given): a read and its fingerprint in different files are not joined.", o->n_infiles);
 	if (o->molecules && (o->matchstart != -1 || o->matchend != -1))
 		return run_fail("--molecules cannot be combined with -start / -end: labels behind a window do not mark the read's bases.");
+	if (o->dedup && !o->molecules) return run_fail("--dedup needs --molecules: the duplicates are those of the molecule count.");
+	if (o->dedup && o->n_devices > 1)
+		return run_fail("--dedup needs exactly one device (%d given): each device has its own table, and a molecule split over two devices would survive twice.", o->n_devices);
+	p->dedup = o->dedup != 0;
 	for (int k = 0; k < o->n_infiles; k++)
 		if (strcmp(o->infile[k], "-") != 0 && !file_exists(o->infile[k])) return run_fail("ERROR: Input file:%s does not exists.", o->infile[k]);
 	// interface.c:419-450: two or more R segments in the command line's architecture switch DUST and -ref off
@@ -512,6 +521,7 @@ extern "C" int64_t td_run_plan_describe(const td_run_plan_t* p, char* buf, int64
 	for (size_t k = 0; k < p->arch_file.segs.size(); k++) s += "arch file candidate " + std::to_string(k) + ": " + segments_text(p->arch_file.segs[k]) + "\n";
 	s += "dust: " + std::to_string(p->dust) + "\n";
 	s += std::string("ref: ") + (p->use_ref ? "on" : "off") + "\n";
+	if (p->dedup) s += "dedup: one read per molecule is written (barcode, fingerprint and the start of the read)\n";
 	if (p->all_known) {
 		s += "barcode file: " + (p->bar_file >= 0 ? std::to_string(p->bar_file) : std::string("none")) + "\n";
 		s += "output reads: " + std::to_string(p->num_out_reads) + "\n";
@@ -888,6 +898,8 @@ int Run::execute()
 			    td_census_enable(c, -1, TD_CENSUS_DEFAULT_MASK, o->unknown_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
 			// --molecules: the contexts of the one input file count its extracted reads per barcode, fingerprint and start of the read
 			if (o->molecules && td_mol_enable(c, o->molecules_prefix, o->molecules_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
+			// --dedup: ... and mark every read that is not the first of its molecule; the writer leaves those out
+			if (o->dedup && td_mol_dedup_enable(c) != TD_OK) return fail("%s", td_last_error(c));
 		}
 	}
 	rep->compile_wait_s = now_s() - t0;
@@ -1017,6 +1029,10 @@ int Run::molecules()
 		if (rc != TD_OK) return fail("%s", td_last_error(nullptr));
 	}
 	rep->molecules_totals = sum;
+	if (o->dedup) {   // (one device: td_run_plan saw to it)
+		if (td_mol_dedup_get(f.raw[0], &rep->dedup_totals) != TD_OK) return fail("%s", td_last_error(f.raw[0]));
+		rep->dedup = 1;
+	}
 
 	const td_arch* a = f.arch.get();
 	int seg = -1;
@@ -1031,6 +1047,8 @@ int Run::molecules()
 	if (sum.overflow > 0)
 		fprintf(out, "# the counting table was too small: %lld reads were not counted (the counts below are exact; --molecules-slots %d or more)\n",
 		        (long long)sum.overflow, o->molecules_slots_log2 + 1);
+	if (o->dedup)
+		fprintf(out, "# written\t%lld\n# duplicates removed\t%lld\n", (long long)rep->dedup_totals.kept, (long long)rep->dedup_totals.duplicates);
 	fprintf(out, "# barcode\treads\tmolecules\tduplication\t1\t2\t3\t4\t5\t6\t7\t8\t9\t10+\n");
 	auto line = [&](const char* label, const td_mol_row& r) {
 		fprintf(out, "%s\t%lld\t%lld\t%0.4f", label, (long long)r.reads, (long long)r.molecules,

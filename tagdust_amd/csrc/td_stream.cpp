@@ -512,6 +512,7 @@ void format_records(const Batch& b, const Piece& pc, int64_t lo, int64_t hi, int
 		const td_read_result& rr = b.res[i];
 		size_t f;                                              // io.c:923-934
 		const int32_t rtype = ctype ? ctype[i] : rr.read_type, rbar = cbar ? cbar[i] : rr.barcode;
+		if ((rtype & 0xFF) == TD_EXTRACT_DUPLICATE) continue;  // dedup: not the first read of its molecule, and no failure either
 		if (rtype == TD_EXTRACT_SUCCESS) f = (rbar != -1) ? (size_t)(rbar & 0xFF) : 0;
 		else f = (size_t)num_alternatives - 1;
 		f += file_base;

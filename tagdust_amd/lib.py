@@ -53,8 +53,10 @@ CENSUS_MAX_WORD = 28
 
 # include/tagdust_molecules.h: molecules per barcode
 MOL_ABI_SYMBOLS = ["td_mol_enable", "td_mol_disable", "td_mol_reset", "td_mol_entries", "td_mol_get", "td_mol_summarise", "td_mol_host",
-                   "td_mol_key", "td_mol_key_bin"]
+                   "td_mol_key", "td_mol_key_bin", "td_mol_dedup_enable", "td_mol_dedup_disable", "td_mol_dedup_get", "td_mol_dedup_host"]
 MOL_TOTALS = ("eligible", "counted", "skipped_empty", "skipped_n", "overflow", "molecules")
+MOL_DEDUP_TOTALS = ("kept", "duplicates", "unjudged")
+EXTRACT_DUPLICATE = 7    # TD_EXTRACT_DUPLICATE (include/tagdust_hip.h): not an outcome of the reference
 MOL_LEVELS = 10
 MOL_ROW_DTYPE = np.dtype([("reads", "<i8"), ("molecules", "<i8"), ("levels", "<i8", (MOL_LEVELS,))])
 MOL_DEFAULT_PREFIX = 20
@@ -595,7 +597,8 @@ class _RunOpts(C.Structure):
                 ("host_threads", C.c_int32), ("batch_reads", C.c_int32), ("sync_compile", C.c_int32), ("stats_on_host", C.c_int32),
                 ("force", C.c_int32), ("dry_run", C.c_int32), ("help", C.c_int32), ("version", C.c_int32), ("echo_log", C.c_int32),
                 ("argc", C.c_int32), ("argv", C.POINTER(C.c_char_p)), ("unknown_barcodes", C.c_int32), ("unknown_slots_log2", C.c_int32),
-                ("fingerprint_seq", C.c_int32), ("molecules", C.c_int32), ("molecules_prefix", C.c_int32), ("molecules_slots_log2", C.c_int32)]
+                ("fingerprint_seq", C.c_int32), ("molecules", C.c_int32), ("molecules_prefix", C.c_int32), ("molecules_slots_log2", C.c_int32),
+                ("dedup", C.c_int32)]
 
 
 class _CensusTotals(C.Structure):
@@ -614,6 +617,14 @@ class _MolTotals(C.Structure):
         return {f: int(getattr(self, f)) for f in MOL_TOTALS}
 
 
+class _MolDedupTotals(C.Structure):
+    """td_mol_dedup_totals (include/tagdust_molecules.h)"""
+    _fields_ = [(f, C.c_int64) for f in MOL_DEDUP_TOTALS]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f in MOL_DEDUP_TOTALS}
+
+
 class _RunReport(C.Structure):
     """td_run_report (include/tagdust_run.h)"""
     _fields_ = [("error", C.c_char * 1024), ("counts", C.c_int64 * NUM_COUNTERS), ("n_artifacts", C.c_int32),
@@ -622,7 +633,7 @@ class _RunReport(C.Structure):
                 ("stream", _StreamStats), ("arch_s", C.c_double), ("stats_s", C.c_double), ("calibration_s", C.c_double),
                 ("compile_wait_s", C.c_double), ("stream_s", C.c_double), ("stats_on_device", C.c_int32), ("log", C.c_char_p),
                 ("n_unknown", C.c_int64), ("unknown", C.c_void_p), ("unknown_totals", _CensusTotals),
-                ("molecules", C.c_void_p), ("molecules_totals", _MolTotals)]
+                ("molecules", C.c_void_p), ("molecules_totals", _MolTotals), ("dedup", C.c_int32), ("dedup_totals", _MolDedupTotals)]
 
 
 def _run_lib():
@@ -733,6 +744,7 @@ def run_execute(args):
             "stats_on_device": bool(rep.stats_on_device), "log": (rep.log or b"").decode(),
             "unknown": _census_entries(rep.unknown, int(rep.n_unknown)), "unknown_totals": rep.unknown_totals.as_dict(),
             "molecules": _mol_rows(rep.molecules) if rep.molecules else None, "molecules_totals": rep.molecules_totals.as_dict(),
+            "dedup_totals": rep.dedup_totals.as_dict() if rep.dedup else None,
         }
     finally:
         o.lib.td_run_report_clear(C.byref(rep))
@@ -837,6 +849,11 @@ def _mol_lib():
     lib.td_mol_key.restype = C.c_uint64
     lib.td_mol_key_bin.argtypes = [C.c_uint64]
     lib.td_mol_key_bin.restype = C.c_int32
+    lib.td_mol_dedup_enable.argtypes = [C.c_void_p]
+    lib.td_mol_dedup_disable.argtypes = [C.c_void_p]
+    lib.td_mol_dedup_get.argtypes = [C.c_void_p, C.POINTER(_MolDedupTotals)]
+    lib.td_mol_dedup_host.argtypes = [C.POINTER(_ModelDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(_MolDedupTotals)]
     return lib
 
 
@@ -864,6 +881,29 @@ def mol_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
         return _census_entries(ptr, n.value), tot.as_dict()
     finally:
         lib.td_census_free(ptr)
+
+
+def mol_dedup_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_dedup_host: which reads of a batch are not the first of their molecule, the reads in the given order (no GPU).
+    Arguments as mol_host takes them.  Returns (is_duplicate, a bool per read; totals dict)."""
+    lib = _mol_lib()
+    desc, keep = make_model_desc(md)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if len(seq) == 0:
+        seq = np.zeros(1, np.uint8)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
+    for f in ("read_type", "barcode", "fingerprint"):
+        rr[f] = np.asarray(res[f])
+    dup = np.zeros(max(len(offs) - 1, 1), np.uint8)
+    tot = _MolDedupTotals()
+    rc = lib.td_mol_dedup_host(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
+                               labels.ctypes.data, dup.ctypes.data, C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return dup[:len(offs) - 1].astype(bool), tot.as_dict()
 
 
 def mol_summarise(entries):
@@ -1105,6 +1145,19 @@ class TagdustHip:
 
     def mol_reset(self):
         self._chk(_mol_lib().td_mol_reset(self.h))
+
+    def mol_dedup_enable(self):
+        """td_mol_dedup_enable: from now on a read that is not the first of its molecule gets read_type EXTRACT_DUPLICATE"""
+        self._chk(_mol_lib().td_mol_dedup_enable(self.h))
+
+    def mol_dedup_disable(self):
+        self._chk(_mol_lib().td_mol_dedup_disable(self.h))
+
+    def mol_dedup_get(self):
+        """td_mol_dedup_get: {kept, duplicates, unjudged}"""
+        tot = _MolDedupTotals()
+        self._chk(_mol_lib().td_mol_dedup_get(self.h, C.byref(tot)))
+        return tot.as_dict()
 
     def mol_entries(self, cap=None):
         """td_mol_entries: (the (key, count) pairs by count descending then key ascending -- at most cap of them --, totals dict)"""

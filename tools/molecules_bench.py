@@ -14,6 +14,14 @@ its slots anew; the totals of one batch; the device summary's time (td_mol_get, 
 through td_submit / td_wait with the count on and off in turn (on, off, on, off).  The yardstick is the run with the count off:
 the path without this feature.
 
+Dedup (td_mol_dedup_enable) gets a row of its own on the same workload: the two passes' time from HIP events (option
+"dedup_kernel_us": events around both launches of a td_run batch, nothing else in flight), median of 5 batches with the table
+reset before each, the totals of one batch, and a third state "dedup" in the host-to-host rotation (on, off, dedup, on, off,
+dedup), to be held against "on" -- the count alone -- of the same process.  Expectation, written down before the first run: pass
+1 walks the labels again as the count does and adds a probe (a load that mostly hits the key's first slot) and one 8-byte atomic
+minimum at a random address, so it should cost about what the count kernel costs; pass 2 reads 12 bytes per read in order and one
+random 8-byte word: less than half of that.  The table's random traffic bounds both.
+
 Expectation, written down before the first run, from the bytes the count kernel touches per read: the outcome, length, barcode
 and fingerprint (16 B), a label byte per position up to the 20th read base (the read starts at base 17: 37 B), three 2-bit words
 and two N-mask words (20 B) -- 73 B streamed -- and the table: a load of the key, a CAS on it for a new key, an add on the
@@ -92,13 +100,29 @@ def measure(ctx, seq, offs, n):
     out["decode_kernel_ms_median"], out["count_kernel_ms_median"] = round(d, 3), round(c, 3)
     out["count_share_of_decode"] = round(c / d, 5)
     out["count_kernel_reads_per_s"] = round(n / (c * 1e-3)) if c > 0 else None
+    # dedup's two passes behind the count
+    ctx.mol_dedup_enable()
+    dd = []
+    for it in range(6):
+        ctx.mol_reset()
+        ctx.upload_batch(seq, offs)
+        ctx.run()
+        dd.append(ctx.get_option("dedup_kernel_us") / 1000.0)
+        if it == 0:
+            out["dedup_totals_of_one_batch"] = ctx.mol_dedup_get()
+    out["dedup_passes"] = 2
+    out["dedup_kernel_ms_runs"] = [round(v, 3) for v in dd[1:]]
+    out["dedup_kernel_ms_median"] = round(statistics.median(dd[1:]), 3)
+    out["dedup_share_of_decode"] = round(statistics.median(dd[1:]) / d, 5)
     ctx.mol_disable()
-    # host to host through td_submit / td_wait, the count on and off in turn
+    # host to host through td_submit / td_wait: the count on, off, and on with dedup, in turn
     res = [np.zeros(n, RESULT_DTYPE) for _ in range(2)]
-    rates = {"on": [], "off": []}
-    for state in ("on", "off", "on", "off"):
-        if state == "on":
+    rates = {"on": [], "off": [], "dedup": []}
+    for state in ("on", "off", "dedup", "on", "off", "dedup"):
+        if state != "off":
             ctx.mol_enable(PREFIX, LOG2_SLOTS)
+        if state == "dedup":
+            ctx.mol_dedup_enable()
         steps = 4
         for t in [ctx.submit(seq, offs, res=r) for r in res]:      # warm-up: both slots, both result buffers
             ctx.wait(t)
@@ -111,7 +135,7 @@ def measure(ctx, seq, offs, n):
         for t in tickets:
             ctx.wait(t)
         rates[state].append(round(steps * n / (time.perf_counter() - t0)))
-        if state == "on":
+        if state != "off":
             ctx.mol_disable()
     out["host_to_host_reads_per_s"] = rates
     return out
