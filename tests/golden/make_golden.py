@@ -505,6 +505,85 @@ def scenarios(tmp):
         free_order(fq, 59, follow)
         return fq, ["-seed", "42", "-1", "R:N", "-2", "G:G", "-3", "B:" + ",".join(bars4), "-4", "R:N"]
     sc["r_g_b_r"] = r_g_b_r
+
+    # -start / -end on architectures other than "B R": the labels are stored relative to the window but make_extracted_read
+    # applies them to absolute read positions (barcode_hmm.c:3325-3356), and the labels behind the window stay 0 -- HMM 0 of
+    # segment 0 -- so the bases behind the window are kept exactly when the first segment is a read segment.
+    def win_r_s_b_r():  # a read segment FIRST under a window: the tail behind -end is kept; two read segments, -Q; -dust is given, but
+        # with two read segments the reference switches it off with a warning (interface.c:441-445)
+        fq = os.path.join(tmp, "wrsbr.fq")
+        rng = np.random.RandomState(61)
+
+        def dna(n):
+            return "".join("ACGT"[k] for k in rng.randint(0, 4, n))
+        with open(fq, "w") as fh:
+            for i in range(240):
+                b = dna(6) if rng.random_sample() < 0.1 else bars4[rng.randint(4)]          # a k-mer that is no barcode: decoy
+                r1 = dna(rng.randint(10, 27))                                                # some first reads shorter than -minlen
+                s_ = dna(2) + r1 + mutate(rng, "GATCGG" + b, 0.02, 0.01) + dna(rng.randint(14, 50))
+                if rng.random_sample() < 0.1:
+                    s_ = dna(len(s_))
+                s_ = s_ + dna(max(0, 58 - len(s_)))                                          # every read reaches -end ...
+                if i % 5 == 0:
+                    s_ = s_[:58]                                                             # ... and some end with it: no tail
+                if rng.random_sample() < 0.05:
+                    s_ = "".join("N" if rng.random_sample() < 0.08 else ch for ch in s_)
+                fh.write("@READ%d\n%s\n+\n%s\n" % (i, s_, "I" * len(s_)))
+        return fq, ["-Q", "3", "-start", "3", "-end", "58", "-dust", "30", "-1", "R:N", "-2", "S:GATCGG", "-3", "B:" + ",".join(bars4), "-4", "R:N"]
+    sc["win_r_s_b_r"] = win_r_s_b_r
+
+    def win_b_f_r_ref():  # B F R under a window with -ref: the F key is built from window-relative bases, the filter sees the
+        # rewritten read's first 63 characters with 65 at every removed position (9 in front, everything from -end on), the
+        # threshold is the reference's own calibration under the window.  243 reads, not 240: three thread ranges of 81 leave one
+        # left-over read each (80, 161, 242) -- 240 reads in three ranges would leave none.  A left-over read goes through
+        # bpm_check_error, which starts counting at the read's length and looks at its first 31 kept characters: it can hit only
+        # when length - 31 + removed head fits into -fe, hence 4-nt barcodes, -end 40 and reads of 40 bases at those positions.
+        fq = os.path.join(tmp, "wbfr.fq")
+        fa = os.path.join(tmp, "wart.fa")
+        rng = np.random.RandomState(67)
+        bars = read_tags(os.path.join(dev, "EDITTAG_4nt_ed_2.txt"), 4)
+
+        def dna(n):
+            return "".join("ACGT"[k] for k in rng.randint(0, 4, n))
+        arts = [dna(L) for L in (70, 48, 95)]
+        with open(fa, "w") as fh:
+            for k, a in enumerate(arts):
+                fh.write(">artifact %d\n%s\n" % (k + 1, "\n".join(a[x:x + 40] for x in range(0, len(a), 40))))
+        comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
+        with open(fq, "w") as fh:
+            for i in range(243):
+                left_over = i in (80, 161, 242)
+                kind = "art" if left_over else str(rng.choice(["art", "plain", "low", "cut", "umi", "random"], p=[0.3, 0.3, 0.1, 0.12, 0.08, 0.1]))
+                head = bars[rng.randint(4)] + dna(5 if kind != "umi" else int(rng.choice([4, 6])))
+                if not left_over:
+                    head = mutate(rng, head, 0.02, 0.01)
+                pre = dna(3)
+                if kind == "art":     # a window of an artifact, either strand; the read ends soon behind -end so that the removed tail stays cheap
+                    a = arts[rng.randint(len(arts))]
+                    L = (40 if left_over else int(rng.randint(40, 45))) - 3 - len(head)
+                    st = int(rng.randint(0, len(a) - L + 1))
+                    ins = a[st:st + L]
+                    if rng.random_sample() < 0.5:
+                        ins = "".join(comp[ch] for ch in reversed(ins))
+                    if not left_over:
+                        ins = mutate(rng, ins, 0.02, 0.0)
+                elif kind == "low":
+                    u = dna(int(rng.randint(1, 3)))
+                    ins = (u * 80)[:int(rng.randint(30, 60))]
+                else:
+                    ins = dna(int(rng.randint(30, 60)))
+                if kind == "cut":     # nothing in front of the barcode: the window starts behind its third base
+                    pre = ""
+                s_ = pre + head + ins
+                if kind == "random":
+                    s_ = dna(len(s_))
+                s_ = s_ + dna(max(0, 40 - len(s_)))
+                fh.write("@READ%d;%s\n%s\n+\n%s\n" % (i, kind.upper(), s_, "I" * len(s_)))
+        os.environ["REF_DUMP_THREADS"] = "3"
+        EXTRA["win_b_f_r_ref"] = {"art_fasta_text": np.frombuffer(open(fa, "rb").read(), np.uint8)}
+        return fq, ["-seed", "42", "-start", "4", "-end", "40", "-ref", fa, "-fe", "20", "-dust", "30",
+                    "-1", "B:" + ",".join(bars), "-2", "F:NNNNN", "-3", "R:N"]
+    sc["win_b_f_r_ref"] = win_b_f_r_ref
     return sc
 
 
@@ -515,6 +594,8 @@ CLI_NAMES = ["c2_b4_r", "c3_b6_s_r_p", "scen2_endloss", "umi_f_s_r", "short_q_gi
              "b_s_b_r", "r_s_b_f", "f_b_f_r", "r_g_b_r"]      # (not b_f: the reference writes no .fq without a read segment)
 # fixtures whose outcome histogram must show outcome 0 and two more, five reads each, before they are committed
 FREE_ORDER_NAMES = ["b_s_b_r", "r_s_b_f", "f_b_f_r", "b_f", "r_g_b_r"]
+# -start / -end fixtures with conditions of their own (tests/test_window_cases.py) and the same size limit
+WINDOW_NAMES = ["win_r_s_b_r", "win_b_f_r_ref"]
 
 
 def record_cli():
@@ -571,6 +652,11 @@ def main():
             if name in FREE_ORDER_NAMES:
                 hist = dict(zip(vals.tolist(), cnt.tolist()))
                 assert hist.get(0, 0) >= 5 and sum(1 for k, v in hist.items() if k != 0 and v >= 5) >= 2, (name, hist)
+                assert kb <= 32, (name, kb)
+            if name in WINDOW_NAMES:      # the conditions tests/test_window_cases.py keeps asserting on the committed files
+                sys.path.insert(0, os.path.dirname(HERE))
+                import test_window_cases
+                test_window_cases.FIXTURE_CHECKS[name]({k: np.asarray(v) for k, v in d.items()})
                 assert kb <= 32, (name, kb)
             tail = [l for l in log.splitlines() if "WARNING" in l]
             for l in tail:

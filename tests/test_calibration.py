@@ -9,7 +9,8 @@ from conftest import load_golden, GOLDEN_NAMES
 from tagdust_amd import lib as tdlib
 from test_model_builder import _segments
 
-CALIBRATED = [n for n in GOLDEN_NAMES if n not in ("short_q_given", "window_b_r")]   # those were run with -Q (no calibration)
+# those were run with -Q (no calibration) or, win_b_f_r_ref, calibrated by the reference under a -start / -end window
+CALIBRATED = [n for n in GOLDEN_NAMES if n not in ("short_q_given", "window_b_r", "win_r_s_b_r", "win_b_f_r_ref")]
 
 
 @pytest.mark.parametrize("name", CALIBRATED)

@@ -30,7 +30,7 @@ def _single(g, seq, offs):
 
 
 @pytest.mark.parametrize("devices", [[0], [0, 0], [0, 0, 0]], ids=["N1", "N2-same-device", "N3-same-device"])
-@pytest.mark.parametrize("name", ["c3_b6_s_r_p", "artifacts_b_r", "c2_indel_varlen", "window_b_r", "b_s_b_r"])
+@pytest.mark.parametrize("name", ["c3_b6_s_r_p", "artifacts_b_r", "c2_indel_varlen", "window_b_r", "b_s_b_r", "win_b_f_r_ref"])
 def test_multi_equals_single_context(name, devices):
     from tagdust_amd.lib import TagdustMulti
     g = load_golden(name)
@@ -77,7 +77,7 @@ def test_multi_decode_ascii_and_empty_shards():
 
 
 @pytest.mark.parametrize("pieces,devices", [("3", [0]), ("5", [0, 0]), ("64", [0])])
-@pytest.mark.parametrize("name", ["artifacts_b_r", "c2_indel_varlen", "window_b_r"])
+@pytest.mark.parametrize("name", ["artifacts_b_r", "c2_indel_varlen", "window_b_r", "win_b_f_r_ref"])
 def test_multi_decode_in_pipelined_pieces(name, pieces, devices, monkeypatch):
     """td_multi_decode puts a device's range through td_submit / td_wait in pieces of whole tiles (TD_MULTI_PIECES; 2^17 reads each
     by default): ragged reads, an artifact filter whose thread ranges are those of the whole batch, a -start/-end

@@ -842,6 +842,158 @@ def test_free_order_architectures_against_oracle(ctx, seed):
     assert np.array_equal(cnt[8:], np.bincount(ores["barcode"][ok] & 0xFF, minlength=256)), segs
 
 
+# The windowed fuzz: (generator, seed, (matchstart, matchend), artifact filter (thread count, -fe) or None), chosen on the CPU
+# (generator + oracle) so that the conditions of tests/test_window_cases.py hold -- per case two outcomes with five reads each, 20
+# reads that end inside the window, 8 reads without a path or without a base in the window; between them what each is there for:
+_WINDOW_CASES = [
+    ("free", 5, (0, 70), (3, 20)),    # R B R: a read segment first (the tail is kept), two read segments, artifact filter on 3 threads
+    ("free", 13, (5, 75), None),      # R P F F: a read segment first, 24 fingerprint bases inside the window
+    ("free", 17, (5, 104), None),     # R B P S F R: six segments, two read segments, F behind an internal P
+    ("free", 10, (5, 15), None),      # S B: no read segment, a window of 10 bases
+    ("tags", 15, (5, 37), None),      # B F S R: the window ends inside the read segment of most reads
+    ("tags", 14, (5, 60), None),      # P B S R with 30 barcodes: more than 32 labels, 5' P pruned
+    ("tags", 9, (5, 48), (2, 14)),    # B R: artifact filter on 2 threads, DUST
+    ("tags", 2, (9, 60), (5, 24)),    # B F R P: a 3' P segment that the window cuts, artifact filter on 5 threads, matchstart 9
+]
+
+
+def _windowed_case(case):
+    """Segments, reads, the builder's model (its statistics taken under the window, as the reference takes them), decode parameters
+    and artifact filter of one case of the windowed fuzz.  200 reads follow the segments behind `matchstart` random bases and go
+    through the mutation loop of the other fuzz tests with N at 0.5 % of the positions; one in ten is replaced by an unrelated read,
+    one in sixteen turns low-complexity behind its first 12 bases; about a third is cut to end inside the window and about a third
+    padded to run past matchend, none shorter than matchstart + segments + 2.  12 more reads of 1, matchstart, matchstart + 1, ..
+    matchstart + segments + 1 bases are spread over the batch: no base in the window, or no path through the model."""
+    from tagdust_amd import lib as tdlib
+    gen, seed, (ms, me), art = case
+    rng = np.random.RandomState(30000 + seed)
+    segs, parts = (_random_arch if gen == "tags" else _free_order_arch)(rng)
+
+    def dna(n):
+        return "".join("ACGT"[x] for x in rng.randint(0, 4, n))
+    floor = ms + len(segs) + 2
+    assert floor < me
+    reads = []
+    for i in range(200):
+        s_ = "".join(p() for p in parts)
+        out = []
+        for ch in s_:
+            u = rng.random_sample()
+            if u < 0.02:
+                out.append("ACGT"[rng.randint(4)])
+            elif u < 0.03:
+                continue
+            elif u < 0.04:
+                out.append(ch); out.append("ACGT"[rng.randint(4)])
+            elif u < 0.045:
+                out.append("N")
+            else:
+                out.append(ch)
+        s_ = dna(ms) + "".join(out)
+        if rng.random_sample() < 0.1:
+            s_ = dna(len(s_))
+        if rng.random_sample() < 1.0 / 16:
+            s_ = s_[:12] + (dna(int(rng.randint(1, 4))) * 100)[:max(len(s_) - 12, 30)]
+        u = rng.random_sample()
+        if u < 1.0 / 3:      # ends inside the window
+            s_ = (s_ + dna(me))[:int(rng.randint(floor, me))]
+        elif u < 2.0 / 3:    # runs past matchend
+            s_ = s_ + dna(max(0, int(rng.randint(me + 1, me + 31)) - len(s_)))
+        elif len(s_) < floor:
+            s_ = s_ + dna(floor - len(s_))
+        reads.append(s_)
+    short = [n_ for n_ in [1] + list(range(ms, floor)) if n_ >= 1]
+    for k in range(12):
+        reads.insert(int(rng.randint(0, len(reads) + 1)), dna(short[k % len(short)]))
+    code = {"A": 0, "C": 1, "G": 2, "T": 3, "N": 4}
+    reads = [np.array([code[ch] for ch in s_], np.uint8) for s_ in reads]
+    offs = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.int64)
+    seq = np.concatenate(reads)
+    md, _ = tdlib.build_model(segs, seq, offs, 0.05, 0.1, window=(ms, me))
+    md.update(threshold=float(rng.choice([0.0, 1.5, 8.0])), minlen=int(rng.choice([8, 16])), dust=int(rng.choice([0, 100, 20])))
+    artifacts, nthreads = None, 8
+    if art:                  # texts partly cut from the reads (as the filter sees them: the start of a read), -fe, thread count; DUST on
+        nthreads, fe = art
+        texts = []
+        for j in range(4):
+            r0 = reads[int(rng.randint(len(reads)))]
+            texts.append(np.minimum(r0[:60], 3) if j < 3 else rng.randint(0, 4, 80).astype(np.uint8))
+        a_index = np.concatenate([[0], np.cumsum([len(t_) + 1 for t_ in texts])]).astype(np.int32)
+        a_string = np.concatenate([np.concatenate([[ord("X")], t_]) for t_ in texts]).astype(np.uint8)
+        artifacts = (a_string, a_index, fe)
+        md.update(dust=20)
+    return segs, seq, offs, md, artifacts, nthreads
+
+
+_WINDOW_ORACLE = {}
+
+
+def _windowed_oracle(case):
+    """_windowed_case(case) and the oracle's results for it, computed once for both kernels (and for tests/test_window_cases.py)"""
+    from oracle import pyoracle
+    if case not in _WINDOW_ORACLE:
+        segs, seq, offs, md, artifacts, nthreads = _windowed_case(case)
+        o = pyoracle.label_batch(pyoracle.OracleModel(md), seq, offs, float(md["threshold"]), int(md["minlen"]), int(md["dust"]),
+                                 nthreads, artifacts=artifacts, window=case[2])
+        for a in o:
+            a.setflags(write=False)
+        _WINDOW_ORACLE[case] = (segs, seq, offs, md, artifacts, nthreads) + o
+    return _WINDOW_ORACLE[case]
+
+
+@pytest.mark.parametrize("case", _WINDOW_CASES, ids=["%s%d-%d-%d" % (c[0], c[1], c[2][0], c[2][1]) for c in _WINDOW_CASES])
+def test_windowed_architectures_against_oracle(ctx, case):
+    """-start / -end (td_set_window) over architecture shapes: the specialised kernel's TDS_WINDOW variant -- unpack loop, random
+    model, zeroed labels behind the window, label runs, extraction and everything behind it on the whole read -- and the generic
+    kernel's window branches, on read segments first (the tail behind matchend is kept), F / P / S / G / O segments, pruned
+    segments, more than 32 labels, two read segments, no read segment, an artifact filter; reads that end inside the window, reads
+    without a base in it and reads without a path (for which the oracle's guard states the device's rule: mismatch, Q = 0,
+    b_score = -inf, the sequence as it was).  The window is set before the model is uploaded: one specialised kernel per case.
+    Label run, then MODE_GET_PROB and MODE_ARCH_COMP on the resident batch.  Both kernels equal the oracle bit for bit; the device
+    counters equal td_count_outcomes over the oracle's results."""
+    from tagdust_amd import lib as tdlib, MODE_GET_PROB, MODE_ARCH_COMP, RESULT_DTYPE
+    segs, seq, offs, md, artifacts, nthreads, ores, olab, oseq = _windowed_oracle(case)
+    if artifacts:
+        ctx.set_artifacts(artifacts[0], artifacts[1], artifacts[2], nthreads)
+    else:
+        ctx.set_artifacts(None)
+    ctx.set_window(*case[2])
+    try:
+        ctx.upload_model(md)
+        ctx.set_params(float(md["threshold"]), int(md["minlen"]), int(md["dust"]))
+        ctx.upload_batch(seq, offs)
+        ctx.counts_reset()
+        ctx.run()
+        res, labels, seq_after = ctx.download()
+        cnt = ctx.counts()
+        ctx.run(MODE_GET_PROB)
+        res2, _, _ = ctx.download(labels=False, seq=False)
+        ctx.run(MODE_ARCH_COMP)
+        res3, _, _ = ctx.download(labels=False, seq=False)
+    finally:
+        ctx.set_window(-1, -1)
+        ctx.set_artifacts(None)
+    nopath = np.isneginf(ores["b_score"])
+    keep = ~nopath
+    assert np.array_equal(_bits(res["b_score"]), _bits(ores["b_score"])), segs
+    for k in ("f_score", "r_score", "bar_prob"):      # (a read without a path has b_score = -inf; its other scores mean nothing)
+        assert np.array_equal(_bits(res[k][keep]), _bits(ores[k][keep])), (k, segs)
+    assert (res["mapq"][nopath] == 0.0).all()
+    assert np.allclose(res["mapq"], ores["Q"], rtol=0, atol=Q_TOL), segs
+    lab_keep = np.repeat(keep, np.diff(offs) + 1)
+    assert np.array_equal(labels[lab_keep], olab[lab_keep]), segs
+    for k in ("read_type", "barcode", "fingerprint"):
+        assert np.array_equal(res[k], ores[k]), (k, segs)
+    assert np.array_equal(seq_after, oseq), segs
+    as_res = np.zeros(len(ores), RESULT_DTYPE)
+    for k in ("read_type", "barcode", "fingerprint"):
+        as_res[k] = ores[k]
+    assert np.array_equal(cnt, tdlib.count_outcomes(as_res, np.diff(offs))), segs
+    assert np.array_equal(_bits(res2["f_score"][keep]), _bits(ores["f_score"][keep])), segs
+    assert np.allclose(res2["mapq"], ores["Q"], rtol=0, atol=Q_TOL), segs
+    assert np.array_equal(_bits(res3["b_score"]), _bits(ores["b_score"])), segs
+
+
 @pytest.mark.parametrize("nb,linker_first,umi", [(60, False, True), (96, False, True), (96, True, False), (62, True, True), (97, False, False)],
                          ids=["H64-first", "H100-first", "H100-behind-5p-linker", "H67-behind-5p-linker", "H99-b97-r"])
 def test_many_label_architectures_against_oracle(ctx, nb, linker_first, umi):

@@ -393,7 +393,7 @@ def test_length_outliers_get_their_own_wave_slots(monkeypatch):
     assert np.array_equal(lab, olab) and np.array_equal(sq, oseq)
 
 
-@pytest.mark.parametrize("name", ["c3_b6_s_r_p", "c2_indel_varlen", "window_b_r", "b_r_s_r", "r_g_b_r", "b_f"])
+@pytest.mark.parametrize("name", ["c3_b6_s_r_p", "c2_indel_varlen", "window_b_r", "b_r_s_r", "r_g_b_r", "b_f", "win_r_s_b_r", "win_b_f_r_ref"])
 def test_compact_egress_equals_plain_copies(name, monkeypatch):
     """The rewritten sequences and the labels come back as keep bits and label runs and are rebuilt on the host (td_api.hip
     "Compact egress"); with the plain device-side copies (TD_COMPACT_EGRESS=0), with a run table too small for any read

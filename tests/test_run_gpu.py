@@ -80,7 +80,7 @@ def _same_files(d):
 
 
 # ---- G3 ----
-CASES = [(n, [], False) for n in ("c2_b4_r", "c3_b6_s_r_p", "umi_f_s_r", "b_r_s_r", "dust_b_r", "window_b_r", "c5_big_b96_f_r_p")]
+CASES = [(n, [], False) for n in ("c2_b4_r", "c3_b6_s_r_p", "umi_f_s_r", "b_r_s_r", "dust_b_r", "window_b_r", "win_r_s_b_r", "c5_big_b96_f_r_p")]
 CASES += [("c5_big_b96_f_r_p", ["--stats-on-host"], False), ("c3_b6_s_r_p", ["--sync-compile"], True)]
 
 
