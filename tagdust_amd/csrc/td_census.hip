@@ -27,12 +27,7 @@ __global__ __launch_bounds__(CS_BLOCK) void td_census_count_kernel(const TdCensu
 {
 	// per label: 1 = the segment, 2 = a later segment, 0 = an earlier one
 	__shared__ uint8_t s_cls[128];
-	for (int h = threadIdx.x; h < 128; h += CS_BLOCK) {
-		uint8_t v = 0;
-		if (h < a.H) { const int seg = a.label[h] & 0xFFFF; v = seg == a.segment ? 1 : (seg > a.segment ? 2 : 0); }
-		s_cls[h] = v;
-	}
-	__syncthreads();
+	kt_label_classes(s_cls, a.label, a.H, [&](int seg) { return seg == a.segment ? 1 : (seg > a.segment ? 2 : 0); });
 	const int lane = threadIdx.x & (TD_WAVE - 1);
 	const int tile = blockIdx.x * CS_WAVES + (threadIdx.x >> 6);
 	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
@@ -45,95 +40,39 @@ __global__ __launch_bounds__(CS_BLOCK) void td_census_count_kernel(const TdCensu
 		if (elig) len = a.lens[k];
 	}
 	if (__builtin_amdgcn_ballot_w64(elig) == 0ull) return;
-	int tmax = len;
-	for (int o = 32; o >= 1; o >>= 1) { const int t2 = __shfl_xor(tmax, o); tmax = t2 > tmax ? t2 : tmax; }
-	if (tmax > a.lmax) tmax = a.lmax;                 // (the batch's longest read: every index below stays inside the tile's arrays)
-	const uint32_t* pk = a.packed + (int64_t)tile * (a.nw2 + a.nw1) * TD_WAVE + lane;
-	const int8_t* lb = a.labels + (int64_t)tile * (a.lmax + 1) * TD_WAVE + lane;
-
 	cs_u64 w = 0ull;
 	int n = 0;
-	bool has_n = false, active = elig && len > 0;
-	uint32_t w2 = 0u, wn = 0u;                        // the 16 bases / the 32 N flags around p (a lane is active from p = 0 on)
-	for (int p = 0; p < tmax; p++) {
-		if (__builtin_amdgcn_ballot_w64(active) == 0ull) break;
-		if (active) {
-			if ((p & 15) == 0) w2 = pk[(p >> 4) * TD_WAVE];
-			if ((p & 31) == 0) wn = pk[(a.nw2 + (p >> 5)) * TD_WAVE];
-			const uint32_t lab = (uint8_t)lb[(p + 1) * TD_WAVE];     // labels[p + 1] belongs to base p
-			const uint32_t cls = lab < 128u ? s_cls[lab] : 0u;
-			if (cls == 1u) {
-				n++;
-				if (n <= TD_CENSUS_MAX_WORD) {
-					w = (w << 2) | (cs_u64)((w2 >> (2 * (p & 15))) & 3u);
-					has_n = has_n || ((wn >> (p & 31)) & 1u) != 0u;
-				}
-			} else if (cls == 2u && a.ordered) active = false;       // the path has left the segment for good
-			if (p + 1 >= len) active = false;
-		}
-	}
+	bool has_n = false;
+	kt_walk_tile(a.tile, s_cls, tile, lane, len, [&](uint32_t cls, uint32_t base, bool base_is_n) {
+		if (cls == 1u) {
+			n++;
+			if (n <= TD_CENSUS_MAX_WORD) { w = (w << 2) | (cs_u64)base; has_n = has_n || base_is_n; }
+		} else if (cls == 2u && a.ordered) return false;             // the path has left the segment for good
+		return true;
+	});
 	const bool is_empty = elig && n == 0, is_long = elig && n > TD_CENSUS_MAX_WORD;
 	const bool is_n = elig && !is_empty && !is_long && has_n;
 	const bool has_key = elig && !is_empty && !is_long && !has_n;
-	const cs_u64 key = has_key ? (((cs_u64)n << 56) | w) : 0ull;
-
-	// lanes with the same key leave as one, the wave's distinct keys probe side by side (td_keytable.h)
-	const int mine = kt_wave_merge(has_key, key, lane);
-	bool placed = false, fresh = false;
-	kt_probe_add(a.table, key, mine, placed, fresh);
+	const KtWaveAdded added = kt_wave_add(a.table, has_key, has_key ? (((cs_u64)n << 56) | w) : 0ull, lane);
 	// tallies: one add per wave and tally
 	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig));
 	const int n_empty = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_empty));
 	const int n_long = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_long));
 	const int n_n = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_n));
-	const int n_fresh = __builtin_popcountll(__builtin_amdgcn_ballot_w64(fresh));
-	const int n_counted = kt_wave_sum(placed ? mine : 0);
-	const int n_over = kt_wave_sum(placed ? 0 : mine);
 	if (lane == 0) {
 		atomicAdd(&a.tallies[TDC_ELIGIBLE], (cs_u64)n_elig);
-		if (n_counted) atomicAdd(&a.tallies[TDC_COUNTED], (cs_u64)n_counted);
+		if (added.counted) atomicAdd(&a.tallies[TDC_COUNTED], (cs_u64)added.counted);
 		if (n_empty) atomicAdd(&a.tallies[TDC_EMPTY], (cs_u64)n_empty);
 		if (n_long) atomicAdd(&a.tallies[TDC_LONG], (cs_u64)n_long);
 		if (n_n) atomicAdd(&a.tallies[TDC_N], (cs_u64)n_n);
-		if (n_over) atomicAdd(&a.tallies[TDC_OVERFLOW], (cs_u64)n_over);
-		if (n_fresh) atomicAdd(&a.tallies[TDC_DISTINCT], (cs_u64)n_fresh);
+		if (added.overflow) atomicAdd(&a.tallies[TDC_OVERFLOW], (cs_u64)added.overflow);
+		if (added.fresh) atomicAdd(&a.tallies[TDC_DISTINCT], (cs_u64)added.fresh);
 	}
-}
-
-hipError_t td_census_launch_count(const TdCensusArgs& a, hipStream_t stream)
-{
-	if (a.n_tiles <= 0) return hipSuccess;
-	const unsigned blocks = (unsigned)((a.n_tiles + CS_WAVES - 1) / CS_WAVES);
-	hipLaunchKernelGGL(td_census_count_kernel, dim3(blocks), dim3(CS_BLOCK), 0, stream, a);
-	return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------
-// (td_census.h: shared with td_molecules.hip)
-bool census_entry_before(const td_census_entry& x, const td_census_entry& y) { return x.count != y.count ? x.count > y.count : x.key < y.key; }
-
-td_census_entry* census_copy_entries(const std::vector<td_census_entry>& v)
-{
-	td_census_entry* p = (td_census_entry*)malloc(sizeof(td_census_entry) * (v.size() ? v.size() : 1));
-	if (p && !v.empty()) memcpy(p, v.data(), sizeof(td_census_entry) * v.size());
-	return p;
-}
-
-// keys (any order, repeated) -> entries in the order of td_census_get
-void census_tally_keys(std::vector<uint64_t>& keys, std::vector<td_census_entry>& out)
-{
-	std::sort(keys.begin(), keys.end());
-	for (size_t i = 0; i < keys.size();) {
-		size_t j = i;
-		while (j < keys.size() && keys[j] == keys[i]) j++;
-		out.push_back(td_census_entry{ keys[i], (int64_t)(j - i) });
-		i = j;
-	}
-	std::sort(out.begin(), out.end(), census_entry_before);
-}
-
 namespace {
 
 // the segment a census of this model counts: `segment` itself when it is a 'B' segment, the last 'B' segment for -1
@@ -156,32 +95,19 @@ bool mask_ok(uint32_t mask) { return mask != 0u && mask <= 0xFFu; }
 
 void census_release(td_ctx* c)
 {
-	TdCensusState& z = c->census;
-	void* p[] = { z.d_label, z.d_keys, z.d_counts, z.d_tallies };
-	for (void* q : p) if (q) (void)hipFree(q);
-	hipEvent_t ev[] = { z.ev_c0, z.ev_c1 };
-	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-	z = TdCensusState();
+	kt_table_release(c->census.table);
+	c->census = TdCensusState();
 }
 
 int census_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int8_t* labels)
 {
 	const TdCensusState& z = c->census;
 	TdCensusArgs a{};
-	a.packed = s.d_packed; a.lens = s.d_lens; a.out_type = out_type; a.labels = labels; a.label = z.d_label;
-	a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.lmax = s.lmax; a.nw2 = s.nw2; a.nw1 = s.nw1; a.H = z.H;   // (both decode kernels write labels with the stride of s.lmax)
+	a.tile = kt_tile_view(s, labels); a.lens = s.d_lens; a.out_type = out_type; a.label = z.table.d_label;
+	a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.H = z.table.H;
 	a.segment = z.segment; a.ordered = z.ordered ? 1 : 0; a.mask = z.mask;
-	const uint64_t n_slots = 1ull << z.log2_slots;
-	a.table.slot_mask = (uint32_t)(n_slots - 1);
-	a.table.window = (uint32_t)std::min<uint64_t>(n_slots, KT_PROBE_WINDOW);
-	a.table.keys = z.d_keys; a.table.counts = z.d_counts; a.tallies = z.d_tallies;
-	HIPCHK(c, hipEventRecord(z.ev_c0, s.cs));
-	HIPCHK(c, td_census_launch_count(a, s.cs));
-	HIPCHK(c, hipEventRecord(z.ev_c1, s.cs));
-	// the finish kernel waits for ev_hits: a slot whose batch has been waited for is no longer read by this count either
-	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));
-	s.hits_queued = true;
-	return TD_OK;
+	a.table = kt_table_view(z.table); a.tallies = z.table.d_tallies;
+	return kt_count_slot(c, z.table, s, (const void*)td_census_count_kernel, &a);
 }
 
 extern "C" int td_census_enable(td_ctx* c, int32_t segment, uint32_t outcome_mask, int32_t log2_slots)
@@ -201,22 +127,12 @@ extern "C" int td_census_enable(td_ctx* c, int32_t segment, uint32_t outcome_mas
 	census_release(c);
 	TdCensusState& z = c->census;
 	const td_model_desc& m = c->model.d;
-	const size_t n_slots = (size_t)1 << log2_slots;
-	bool ok = hipMalloc((void**)&z.d_label, sizeof(int32_t) * (size_t)m.H) == hipSuccess &&
-	          hipMalloc((void**)&z.d_keys, sizeof(cs_u64) * n_slots) == hipSuccess &&
-	          hipMalloc((void**)&z.d_counts, sizeof(cs_u64) * n_slots) == hipSuccess &&
-	          hipMalloc((void**)&z.d_tallies, sizeof(cs_u64) * TDC_TALLY_WORDS) == hipSuccess &&
-	          hipMemcpy(z.d_label, m.label, sizeof(int32_t) * (size_t)m.H, hipMemcpyHostToDevice) == hipSuccess &&
-	          hipMemset(z.d_keys, 0, sizeof(cs_u64) * n_slots) == hipSuccess &&
-	          hipMemset(z.d_counts, 0, sizeof(cs_u64) * n_slots) == hipSuccess &&
-	          hipMemset(z.d_tallies, 0, sizeof(cs_u64) * TDC_TALLY_WORDS) == hipSuccess &&
-	          hipEventCreate(&z.ev_c0) == hipSuccess && hipEventCreate(&z.ev_c1) == hipSuccess;
-	if (!ok) {
-		const std::string e = hipGetErrorString(hipGetLastError());
+	const hipError_t e = kt_table_create(z.table, m.label, m.H, log2_slots, TDC_TALLY_WORDS);
+	if (e != hipSuccess) {
 		census_release(c);
-		return fail(c, "td_census_enable: a table of 2^%d slots could not be set up: %s", log2_slots, e.c_str());
+		return fail(c, "td_census_enable: a table of 2^%d slots could not be set up: %s", log2_slots, hipGetErrorString(e));
 	}
-	z.segment = seg; z.mask = outcome_mask; z.log2_slots = log2_slots; z.H = m.H;
+	z.segment = seg; z.mask = outcome_mask;
 	z.ordered = true;
 	for (int h = 0; h + 1 < m.H; h++) if ((m.label[h] & 0xFFFF) > (m.label[h + 1] & 0xFFFF)) z.ordered = false;
 	z.on = true;
@@ -240,10 +156,7 @@ extern "C" int td_census_reset(td_ctx* c)
 	if (!z.on) return fail(c, "td_census_reset: the census is off (td_census_enable)");
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, sync_compute(c));   // (counts of pipelined batches may still be queued, on either compute stream)
-	const size_t n_slots = (size_t)1 << z.log2_slots;
-	HIPCHK(c, hipMemsetAsync(z.d_keys, 0, sizeof(cs_u64) * n_slots, c->stream));
-	HIPCHK(c, hipMemsetAsync(z.d_counts, 0, sizeof(cs_u64) * n_slots, c->stream));
-	HIPCHK(c, hipMemsetAsync(z.d_tallies, 0, sizeof(cs_u64) * TDC_TALLY_WORDS, c->stream));
+	HIPCHK(c, kt_table_zero(z.table, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	return TD_OK;
 }
@@ -253,26 +166,12 @@ extern "C" int td_census_get(td_ctx* c, td_census_entry* entries, int64_t cap, i
 	if (!c) return TD_FAIL;
 	TdCensusState& z = c->census;
 	if (!z.on) return fail(c, "td_census_get: the census is off (td_census_enable)");
-	if (cap < 0 || (cap > 0 && !entries) || !n) return fail(c, "td_census_get: bad arguments");
-	*n = 0;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
 	cs_u64 t[TDC_TALLY_WORDS];
-	HIPCHK(c, hipMemcpy(t, z.d_tallies, sizeof t, hipMemcpyDeviceToHost));
-	const int64_t distinct = (int64_t)t[TDC_DISTINCT];
-	std::vector<td_census_entry> v((size_t)distinct);
-	int64_t found = 0;
-	const hipError_t e = kt_compact(z.d_keys, z.d_counts, z.log2_slots, v.data(), distinct, z.d_tallies + TDC_CURSOR, c->stream, &found);
-	if (e != hipSuccess) return fail(c, "td_census_get: compaction failed: %s", hipGetErrorString(e));
-	if (found != distinct) return fail(c, "td_census_get: the table holds %lld keys, its tally says %lld", (long long)found, (long long)distinct);
-	std::sort(v.begin(), v.end(), census_entry_before);
-	const int64_t take = std::min<int64_t>(cap, distinct);
-	if (take > 0) memcpy(entries, v.data(), sizeof(td_census_entry) * (size_t)take);
-	*n = distinct;
+	if (kt_table_entries(c, "td_census_get", z.table, TDC_DISTINCT, TDC_CURSOR, entries, cap, n, t) != TD_OK) return TD_FAIL;
 	if (totals) {
 		totals->eligible = (int64_t)t[TDC_ELIGIBLE]; totals->counted = (int64_t)t[TDC_COUNTED]; totals->skipped_empty = (int64_t)t[TDC_EMPTY];
 		totals->skipped_long = (int64_t)t[TDC_LONG]; totals->skipped_n = (int64_t)t[TDC_N]; totals->overflow = (int64_t)t[TDC_OVERFLOW];
-		totals->distinct = distinct;
+		totals->distinct = *n;
 	}
 	return TD_OK;
 }
@@ -280,16 +179,9 @@ extern "C" int td_census_get(td_ctx* c, td_census_entry* entries, int64_t cap, i
 // the count kernel's time of the last batch, for tools/census_bench.py (option "census_kernel_us" of td_get_option)
 int census_last_kernel_us(td_ctx* c, int32_t* us)
 {
-	TdCensusState& z = c->census;
-	if (!z.on) return fail(c, "td_get_option: census_kernel_us: the census is off");
-	HIPCHK(c, hipSetDevice(c->device));
-	float ms = 0.0f;
-	if (hipEventSynchronize(z.ev_c1) != hipSuccess || hipEventElapsedTime(&ms, z.ev_c0, z.ev_c1) != hipSuccess) {
-		(void)hipGetLastError();
-		return fail(c, "td_get_option: census_kernel_us: no batch has been counted yet");
-	}
-	*us = (int32_t)(ms * 1000.0f + 0.5f);
-	return TD_OK;
+	const TdCountTable& t = c->census.table;
+	if (!c->census.on) return fail(c, "td_get_option: census_kernel_us: the census is off");
+	return kt_last_kernel_us(c, t.ev_c0, t.ev_c1, us, "td_get_option: census_kernel_us: no batch has been counted yet");
 }
 
 extern "C" int td_census_host(const td_model_desc* m, int32_t segment, uint32_t outcome_mask, const uint8_t* codes, const int64_t* offs,
@@ -330,29 +222,11 @@ extern "C" int td_census_host(const td_model_desc* m, int32_t segment, uint32_t 
 		else { keys.push_back(((uint64_t)cnt << 56) | w); t.counted++; }
 	}
 	std::vector<td_census_entry> v;
-	census_tally_keys(keys, v);
+	kt_tally_keys(keys, v);
 	t.distinct = (int64_t)v.size();
-	if (!(*entries = census_copy_entries(v))) return fail(nullptr, "td_census_host: out of memory");
+	if (!(*entries = kt_copy_entries(v))) return fail(nullptr, "td_census_host: out of memory");
 	*n = (int64_t)v.size();
 	if (totals) *totals = t;
-	return TD_OK;
-}
-
-extern "C" int td_census_merge(const td_census_entry* a, int64_t na, const td_census_entry* b, int64_t nb, td_census_entry** out, int64_t* n)
-{
-	if (!out || !n || na < 0 || nb < 0 || (na > 0 && !a) || (nb > 0 && !b)) return fail(nullptr, "td_census_merge: bad arguments");
-	std::vector<td_census_entry> all;
-	all.insert(all.end(), a, a + na);
-	all.insert(all.end(), b, b + nb);
-	std::sort(all.begin(), all.end(), [](const td_census_entry& x, const td_census_entry& y) { return x.key < y.key; });
-	std::vector<td_census_entry> v;
-	for (const td_census_entry& e : all) {
-		if (!v.empty() && v.back().key == e.key) v.back().count += e.count;
-		else v.push_back(e);
-	}
-	std::sort(v.begin(), v.end(), census_entry_before);
-	if (!(*out = census_copy_entries(v))) return fail(nullptr, "td_census_merge: out of memory");
-	*n = (int64_t)v.size();
 	return TD_OK;
 }
 
@@ -367,5 +241,3 @@ extern "C" int td_census_key_text(uint64_t key, char buf[32])
 	buf[len] = 0;
 	return TD_OK;
 }
-
-extern "C" void td_census_free(td_census_entry* entries) { free(entries); }

@@ -1,17 +1,23 @@
 // td_keytable.h -- the counting table the census (td_census.hip) and the molecule count (td_molecules.hip) share: 64-bit keys, never
-// 0, counted in an open-addressing table in HBM.  Device code and the launch of the compaction kernel; each unit that includes it
-// gets its own copy of the kernel (static), there is one text.
+// 0, counted in an open-addressing table in HBM.  Here: the table as a context owns it (TdCountTable; its life, its results and
+// the host helpers of every td_census_entry result are in td_keytable.hip), and the device code both count kernels are made of --
+// the walk over a decoded tile, the probe, the wave's tail.  The device functions are inline: a probe belongs inside its kernel.
 //
 // Lanes of a wave that hold the same key leave as one probe and one add of their number (kt_wave_merge); the distinct keys of a
 // wave probe side by side (kt_probe_add).  Nothing is ever removed from the table and the probe window is fixed, so a key finds or
 // claims its slot on every attempt or fails on every attempt: a count in the table is exact, what did not fit is the caller's
-// overflow tally.  kt_compact leaves the occupied (key, count) pairs in a dense array.
+// overflow tally.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/tagdust_census.h"
 #include "td_device.h"
+
+struct td_ctx;
+struct TdSlot;
 
 typedef unsigned long long kt_u64;
 
@@ -20,12 +26,54 @@ typedef unsigned long long kt_u64;
 // linear probing looks at this many slots from the key's hash (the whole table when that is smaller): the same on every attempt
 #define KT_PROBE_WINDOW 128
 #define KT_SLOT_BYTES 16   // a key and a count, 8 bytes each
+#define KT_HIDDEN __attribute__((visibility("hidden")))
 
 struct TdKeyTable {
 	kt_u64* __restrict__ keys;      // [slot_mask + 1], 0 = empty
 	kt_u64* __restrict__ counts;    // [slot_mask + 1]
 	uint32_t slot_mask, window;     // 2^log2_slots - 1; slots a key looks at
 };
+
+// a decoded tile in device order, as both decode kernels leave it: labels have the stride of the batch's lmax
+struct TdTileView {
+	const uint32_t* __restrict__ packed;   // [n_tiles][nw2 + nw1][64]  2-bit words then N-mask words
+	const int8_t*   __restrict__ labels;   // [n_tiles][lmax + 1][64]
+	int32_t lmax, nw2, nw1;
+};
+
+// a counting table that belongs to a context
+struct TdCountTable {
+	int32_t log2_slots = 0, H = 0, tally_words = 0;
+	int32_t* d_label = nullptr;    // [H] model.label, the table's own copy
+	kt_u64* d_keys = nullptr;      // [2^log2_slots], 0 = empty
+	kt_u64* d_counts = nullptr;    // [2^log2_slots]
+	kt_u64* d_tallies = nullptr;   // [tally_words] the owner's tallies, the compaction's cursor among them
+	hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   // around the last count launch (the "*_kernel_us" options)
+};
+
+// label copy, table, tallies and events, all zeroed (a failure leaves what it got: kt_table_release) / all of it freed
+KT_HIDDEN hipError_t kt_table_create(TdCountTable& t, const int32_t* label, int32_t H, int32_t log2_slots, int32_t tally_words);
+KT_HIDDEN void kt_table_release(TdCountTable& t);
+// keys, counts and tallies to zero, queued on `stream`
+KT_HIDDEN hipError_t kt_table_zero(const TdCountTable& t, hipStream_t stream);
+KT_HIDDEN TdKeyTable kt_table_view(const TdCountTable& t);
+KT_HIDDEN TdTileView kt_tile_view(const TdSlot& s, const int8_t* labels);
+// The count of one decoded slot: `kernel` (KT_BLOCK threads, a tile per wave, *args its one argument) on the slot's compute stream
+// between the table's two events.  The finish kernel waits for ev_hits: a slot whose batch has been waited for is no longer read
+// by this count either.
+KT_HIDDEN int kt_count_slot(td_ctx* c, const TdCountTable& t, TdSlot& s, const void* kernel, void* args);
+// What the table holds, in the order of td_census_get (`who`: the entry point, for its messages): tallies[t.tally_words] down,
+// the occupied pairs -- tallies[distinct_word] of them, the compaction's cursor is tallies[cursor_word] -- held against that
+// tally and sorted; *n = their number, entries[min(cap, *n)] the first of them.  Waits for the compute streams.
+KT_HIDDEN int kt_table_entries(td_ctx* c, const char* who, const TdCountTable& t, int distinct_word, int cursor_word, td_census_entry* entries,
+                               int64_t cap, int64_t* n, kt_u64* tallies);
+// microseconds between two recorded events (waits for the second); `none_yet`: the message when they have not been recorded
+KT_HIDDEN int kt_last_kernel_us(td_ctx* c, hipEvent_t e0, hipEvent_t e1, int32_t* us, const char* none_yet);
+// host helpers of every result made of td_census_entry: the order of td_census_get; a malloc'd copy for td_census_free (NULL: out
+// of memory); keys (any order, repeated) -> entries in that order
+KT_HIDDEN bool kt_entry_before(const td_census_entry& x, const td_census_entry& y);
+KT_HIDDEN td_census_entry* kt_copy_entries(const std::vector<td_census_entry>& v);
+KT_HIDDEN void kt_tally_keys(std::vector<uint64_t>& keys, std::vector<td_census_entry>& out);
 
 #ifdef __HIPCC__
 // splitmix64's finish: every bit of k reaches every bit of the result
@@ -96,50 +144,51 @@ __device__ __forceinline__ int32_t kt_probe_find(const TdKeyTable& t, kt_u64 key
 	return -1;
 }
 
-// the occupied (key, count) pairs into a dense array: one add on the cursor per wave, the lanes behind it by their rank
-static __global__ __launch_bounds__(KT_BLOCK) void td_keytable_compact_kernel(const kt_u64* __restrict__ keys, const kt_u64* __restrict__ counts,
-                                                                                int64_t n_slots, td_census_entry* __restrict__ out, int64_t cap,
-                                                                                kt_u64* __restrict__ cursor)
+// The tail of a count kernel (whole waves): lanes with the same key leave as one, the wave's distinct keys probe side by side.
+// What the wave's reads with a key came to: counted in the table, not fitted, keys new to the table.
+struct KtWaveAdded { int counted, overflow, fresh; };
+__device__ __forceinline__ KtWaveAdded kt_wave_add(const TdKeyTable& t, bool has_key, kt_u64 key, int lane)
 {
-	const int lane = threadIdx.x & (TD_WAVE - 1);
-	const int64_t step = (int64_t)gridDim.x * KT_BLOCK;
-	for (int64_t i0 = (int64_t)blockIdx.x * KT_BLOCK + (threadIdx.x - lane); i0 < n_slots; i0 += step) {   // (i0 is the wave's)
-		const int64_t i = i0 + lane;
-		const kt_u64 kv = i < n_slots ? keys[i] : 0ull;
-		const kt_u64 occ = __builtin_amdgcn_ballot_w64(kv != 0ull);
-		if (occ == 0ull) continue;
-		kt_u64 base = 0ull;
-		if (lane == __builtin_ctzll(occ)) base = atomicAdd(cursor, (kt_u64)__builtin_popcountll(occ));
-		base = kt_readlane64(base, __builtin_ctzll(occ));
-		const int64_t at = (int64_t)base + __builtin_popcountll(occ & ((1ull << lane) - 1ull));
-		if (kv != 0ull && at < cap) { out[at].key = kv; out[at].count = (int64_t)counts[i]; }
-	}
+	const int mine = kt_wave_merge(has_key, key, lane);
+	bool placed = false, fresh = false;
+	kt_probe_add(t, key, mine, placed, fresh);
+	KtWaveAdded r;
+	r.counted = kt_wave_sum(placed ? mine : 0);
+	r.overflow = kt_wave_sum(placed ? 0 : mine);
+	r.fresh = __builtin_popcountll(__builtin_amdgcn_ballot_w64(fresh));
+	return r;
 }
 
-// the table's `distinct` occupied pairs into out[distinct] (host memory, any order); *found = what the sweep met.  Synchronous on
-// `stream`; cursor is a device word of the caller's.
-static hipError_t kt_compact(const kt_u64* keys, const kt_u64* counts, int log2_slots, td_census_entry* out, int64_t distinct,
-                             kt_u64* cursor, hipStream_t stream, int64_t* found)
+// s_cls[128], the class of every label a walk can meet: cls(segment) below H, 0 beyond (the whole workgroup; ends in its barrier)
+template <typename Cls>
+__device__ __forceinline__ void kt_label_classes(uint8_t* s_cls, const int32_t* __restrict__ label, int H, Cls cls)
 {
-	*found = 0;
-	if (distinct <= 0) return hipSuccess;
-	td_census_entry* d_dense = nullptr;
-	hipError_t e = hipMalloc((void**)&d_dense, sizeof(td_census_entry) * (size_t)distinct);
-	if (e != hipSuccess) return e;
-	const int64_t n_slots = (int64_t)1 << log2_slots;
-	int64_t blocks = (n_slots + KT_BLOCK - 1) / KT_BLOCK;
-	if (blocks > 2048) blocks = 2048;
-	e = hipMemsetAsync(cursor, 0, sizeof(kt_u64), stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(td_keytable_compact_kernel, dim3((unsigned)blocks), dim3(KT_BLOCK), 0, stream, keys, counts, n_slots, d_dense, distinct, cursor);
-		e = hipGetLastError();
+	for (int h = threadIdx.x; h < 128; h += KT_BLOCK) s_cls[h] = h < H ? (uint8_t)cls(label[h] & 0xFFFF) : (uint8_t)0;
+	__syncthreads();
+}
+
+// The walk of a wave over its decoded tile, one read per lane (whole waves): for base p = 0, 1, .. of the lane's read
+// visit(class of labels[p + 1], the base's 2-bit code, the base is an N) until it returns false or the read's `len` bases are
+// through (len = 0: the lane takes no part).  Label bytes are read only as far as some lane still walks.
+template <typename Visit>
+__device__ __forceinline__ void kt_walk_tile(const TdTileView& v, const uint8_t* s_cls, int tile, int lane, int len, Visit visit)
+{
+	bool active = len > 0;
+	int tmax = len;
+	for (int o = 32; o >= 1; o >>= 1) { const int t2 = __shfl_xor(tmax, o); tmax = t2 > tmax ? t2 : tmax; }
+	if (tmax > v.lmax) tmax = v.lmax;                 // (the batch's longest read: every index below stays inside the tile's arrays)
+	const uint32_t* pk = v.packed + (int64_t)tile * (v.nw2 + v.nw1) * TD_WAVE + lane;
+	const int8_t* lb = v.labels + (int64_t)tile * (v.lmax + 1) * TD_WAVE + lane;
+	uint32_t w2 = 0u, wn = 0u;                        // the 16 bases / the 32 N flags around p (a lane is active from p = 0 on)
+	for (int p = 0; p < tmax; p++) {
+		if (__builtin_amdgcn_ballot_w64(active) == 0ull) break;
+		if (active) {
+			if ((p & 15) == 0) w2 = pk[(p >> 4) * TD_WAVE];
+			if ((p & 31) == 0) wn = pk[(v.nw2 + (p >> 5)) * TD_WAVE];
+			const uint32_t lab = (uint8_t)lb[(p + 1) * TD_WAVE];     // labels[p + 1] belongs to base p
+			if (!visit(lab < 128u ? (uint32_t)s_cls[lab] : 0u, (w2 >> (2 * (p & 15))) & 3u, ((wn >> (p & 31)) & 1u) != 0u)) active = false;
+			if (p + 1 >= len) active = false;
+		}
 	}
-	if (e == hipSuccess) e = hipStreamSynchronize(stream);
-	if (e == hipSuccess) e = hipMemcpy(out, d_dense, sizeof(td_census_entry) * (size_t)distinct, hipMemcpyDeviceToHost);
-	kt_u64 f = 0;
-	if (e == hipSuccess) e = hipMemcpy(&f, cursor, sizeof f, hipMemcpyDeviceToHost);
-	(void)hipFree(d_dense);
-	*found = (int64_t)f;
-	return e;
 }
 #endif

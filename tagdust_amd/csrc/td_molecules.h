@@ -19,15 +19,9 @@ enum { TDM_ELIGIBLE = 0, TDM_COUNTED, TDM_EMPTY, TDM_N, TDM_OVERFLOW, TDM_MOLECU
 struct TdMolState {
 	bool on = false;
 	int32_t prefix = 0;         // P: read bases that belong to the key
-	int32_t log2_slots = 0;
-	int32_t H = 0;
 	uint64_t r_segs = 0;        // bit j: segment j is an 'R' segment
-	int32_t* d_label = nullptr;               // [H] model.label, the count's own copy
-	unsigned long long* d_keys = nullptr;     // [2^log2_slots], 0 = empty
-	unsigned long long* d_counts = nullptr;   // [2^log2_slots]
-	unsigned long long* d_tallies = nullptr;  // [TDM_TALLY_WORDS]
+	TdCountTable table;         // td_keytable.h, TDM_TALLY_WORDS tallies
 	unsigned long long* d_rows = nullptr;     // [TD_NUM_BARCODE_BINS][TDM_ROW_WORDS] the summary sweep's result
-	hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   // around the last count launch (option "molecules_kernel_us")
 	// dedup (td_mol_dedup_enable): the first ordinal of every slot's key, and what orders the two passes of neighbouring batches
 	bool dedup = false;
 	unsigned long long* d_first = nullptr;    // [2^log2_slots], all-ones = no read yet
@@ -39,16 +33,15 @@ struct TdMolState {
 };
 
 struct TdMolArgs {
-	const uint32_t* __restrict__ packed;      // [n_tiles][nw2 + nw1][64]  2-bit words then N-mask words
+	TdTileView tile;                          // td_keytable.h
 	const int32_t*  __restrict__ lens;        // [n_tiles*64]
 	const int32_t*  __restrict__ out_type;    // [n_tiles*64]  final outcomes of the decode launch
 	const int32_t*  __restrict__ out_barcode; // [n_tiles*64]
 	const int32_t*  __restrict__ out_finger;  // [n_tiles*64]
-	const int8_t*   __restrict__ labels;      // [n_tiles][lmax + 1][64]
 	const int32_t*  __restrict__ label;       // [H] model.label
 	int64_t n_reads;
 	uint64_t r_segs;
-	int32_t n_tiles, lmax, nw2, nw1, H, prefix;
+	int32_t n_tiles, H, prefix;
 	TdKeyTable table;
 	unsigned long long* __restrict__ tallies;
 	// dedup's pass 1 alone

@@ -42,12 +42,7 @@ __host__ __device__ __forceinline__ kt_u64 mol_key(int32_t barcode, int32_t fing
 // per label: 1 = it belongs to an 'R' segment (the whole workgroup; ends in its barrier)
 __device__ __forceinline__ void mol_r_labels(const TdMolArgs& a, uint8_t* s_r)
 {
-	for (int h = threadIdx.x; h < 128; h += KT_BLOCK) {
-		uint8_t v = 0;
-		if (h < a.H) { const int seg = a.label[h] & 0xFFFF; v = seg < 64 ? (uint8_t)((a.r_segs >> seg) & 1ull) : 0; }
-		s_r[h] = v;
-	}
-	__syncthreads();
+	kt_label_classes(s_r, a.label, a.H, [&](int seg) { return seg < 64 ? (int)((a.r_segs >> seg) & 1ull) : 0; });
 }
 
 // what a lane's read is to the count: eligible, and then exactly one of the three classes (has_key: counted under `key`)
@@ -63,30 +58,15 @@ __device__ __forceinline__ bool mol_lane_key(const TdMolArgs& a, const uint8_t* 
 	if (__builtin_amdgcn_ballot_w64(elig) == 0ull) return false;
 	int len = 0, barcode = -1, finger = -1;
 	if (elig) { len = a.lens[k]; barcode = a.out_barcode[k]; finger = a.out_finger[k]; }
-	int tmax = len;
-	for (int o = 32; o >= 1; o >>= 1) { const int t2 = __shfl_xor(tmax, o); tmax = t2 > tmax ? t2 : tmax; }
-	if (tmax > a.lmax) tmax = a.lmax;                 // (the batch's longest read: every index below stays inside the tile's arrays)
-	const uint32_t* pk = a.packed + (int64_t)tile * (a.nw2 + a.nw1) * TD_WAVE + lane;
-	const int8_t* lb = a.labels + (int64_t)tile * (a.lmax + 1) * TD_WAVE + lane;
-
 	kt_u64 w = 0ull;
 	int n = 0;
-	bool has_n = false, active = elig && len > 0;
-	uint32_t w2 = 0u, wn = 0u;                        // the 16 bases / the 32 N flags around p (a lane is active from p = 0 on)
-	for (int p = 0; p < tmax; p++) {                  // label bytes only until P read bases are collected or the read ends
-		if (__builtin_amdgcn_ballot_w64(active) == 0ull) break;
-		if (active) {
-			if ((p & 15) == 0) w2 = pk[(p >> 4) * TD_WAVE];
-			if ((p & 31) == 0) wn = pk[(a.nw2 + (p >> 5)) * TD_WAVE];
-			const uint32_t lab = (uint8_t)lb[(p + 1) * TD_WAVE];     // labels[p + 1] belongs to base p
-			if (lab < 128u && s_r[lab]) {
-				w = (w << 2) | (kt_u64)((w2 >> (2 * (p & 15))) & 3u);
-				has_n = has_n || ((wn >> (p & 31)) & 1u) != 0u;
-				if (++n >= a.prefix) active = false;
-			}
-			if (p + 1 >= len) active = false;
-		}
-	}
+	bool has_n = false;
+	kt_walk_tile(a.tile, s_r, tile, lane, len, [&](uint32_t cls, uint32_t base, bool base_is_n) {   // until P read bases are collected
+		if (!cls) return true;
+		w = (w << 2) | (kt_u64)base;
+		has_n = has_n || base_is_n;
+		return ++n < a.prefix;
+	});
 	m.is_empty = elig && n == 0;
 	m.is_n = elig && n > 0 && has_n;
 	m.has_key = elig && n > 0 && !has_n;
@@ -104,27 +84,18 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_count_kernel(const TdMolArgs 
 	const int64_t k = (int64_t)tile * TD_WAVE + lane;
 	MolLane m;
 	if (!mol_lane_key(a, s_r, tile, lane, k, m)) return;
-	const bool elig = m.elig, is_empty = m.is_empty, is_n = m.is_n, has_key = m.has_key;
-	const kt_u64 key = m.key;
-
-	// lanes with the same key leave as one, the wave's distinct keys probe side by side (td_keytable.h)
-	const int mine = kt_wave_merge(has_key, key, lane);
-	bool placed = false, fresh = false;
-	kt_probe_add(a.table, key, mine, placed, fresh);
+	const KtWaveAdded added = kt_wave_add(a.table, m.has_key, m.key, lane);
 	// tallies: one add per wave and tally
-	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig));
-	const int n_empty = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_empty));
-	const int n_n = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_n));
-	const int n_fresh = __builtin_popcountll(__builtin_amdgcn_ballot_w64(fresh));
-	const int n_counted = kt_wave_sum(placed ? mine : 0);
-	const int n_over = kt_wave_sum(placed ? 0 : mine);
+	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(m.elig));
+	const int n_empty = __builtin_popcountll(__builtin_amdgcn_ballot_w64(m.is_empty));
+	const int n_n = __builtin_popcountll(__builtin_amdgcn_ballot_w64(m.is_n));
 	if (lane == 0) {
 		atomicAdd(&a.tallies[TDM_ELIGIBLE], (kt_u64)n_elig);
-		if (n_counted) atomicAdd(&a.tallies[TDM_COUNTED], (kt_u64)n_counted);
+		if (added.counted) atomicAdd(&a.tallies[TDM_COUNTED], (kt_u64)added.counted);
 		if (n_empty) atomicAdd(&a.tallies[TDM_EMPTY], (kt_u64)n_empty);
 		if (n_n) atomicAdd(&a.tallies[TDM_N], (kt_u64)n_n);
-		if (n_over) atomicAdd(&a.tallies[TDM_OVERFLOW], (kt_u64)n_over);
-		if (n_fresh) atomicAdd(&a.tallies[TDM_MOLECULES], (kt_u64)n_fresh);
+		if (added.overflow) atomicAdd(&a.tallies[TDM_OVERFLOW], (kt_u64)added.overflow);
+		if (added.fresh) atomicAdd(&a.tallies[TDM_MOLECULES], (kt_u64)added.fresh);
 	}
 }
 
@@ -252,13 +223,23 @@ void totals_from(const kt_u64* t, td_mol_totals* out)
 
 }   // namespace
 
+// dedup's first ordinals and events freed (nothing of it is queued any more)
+static void dedup_release(TdMolState& z)
+{
+	if (z.d_first) (void)hipFree(z.d_first);
+	hipEvent_t ev[] = { z.ev_p1[0], z.ev_p1[1], z.ev_d0, z.ev_d1 };
+	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+	z.d_first = nullptr; z.ev_p1[0] = z.ev_p1[1] = z.ev_d0 = z.ev_d1 = nullptr;
+	z.p1_queued[0] = z.p1_queued[1] = false;
+	z.dedup = false;
+}
+
 void mol_release(td_ctx* c)
 {
 	TdMolState& z = c->molecules;
-	void* p[] = { z.d_label, z.d_keys, z.d_counts, z.d_tallies, z.d_rows, z.d_first };
-	for (void* q : p) if (q) (void)hipFree(q);
-	hipEvent_t ev[] = { z.ev_c0, z.ev_c1, z.ev_p1[0], z.ev_p1[1], z.ev_d0, z.ev_d1 };
-	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+	kt_table_release(z.table);
+	if (z.d_rows) (void)hipFree(z.d_rows);
+	dedup_release(z);
 	z = TdMolState();
 }
 
@@ -267,32 +248,17 @@ static TdMolArgs mol_args(const TdMolState& z, const TdSlot& s, const int32_t* o
                           const int8_t* labels)
 {
 	TdMolArgs a{};
-	a.packed = s.d_packed; a.lens = s.d_lens; a.out_type = out_type; a.out_barcode = out_barcode; a.out_finger = out_finger;
-	a.labels = labels; a.label = z.d_label;
-	a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.lmax = s.lmax; a.nw2 = s.nw2; a.nw1 = s.nw1; a.H = z.H;   // (both decode kernels write labels with the stride of s.lmax)
+	a.tile = kt_tile_view(s, labels); a.lens = s.d_lens; a.out_type = out_type; a.out_barcode = out_barcode; a.out_finger = out_finger;
+	a.label = z.table.d_label; a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.H = z.table.H;
 	a.r_segs = z.r_segs; a.prefix = z.prefix;
-	const uint64_t n_slots = 1ull << z.log2_slots;
-	a.table.slot_mask = (uint32_t)(n_slots - 1);
-	a.table.window = (uint32_t)std::min<uint64_t>(n_slots, KT_PROBE_WINDOW);
-	a.table.keys = z.d_keys; a.table.counts = z.d_counts; a.tallies = z.d_tallies;
+	a.table = kt_table_view(z.table); a.tallies = z.table.d_tallies;
 	return a;
 }
 
 int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
 {
-	const TdMolState& z = c->molecules;
-	const TdMolArgs a = mol_args(z, s, out_type, out_barcode, out_finger, labels);
-	HIPCHK(c, hipEventRecord(z.ev_c0, s.cs));
-	if (a.n_tiles > 0) {
-		const unsigned blocks = (unsigned)((a.n_tiles + KT_WAVES - 1) / KT_WAVES);
-		hipLaunchKernelGGL(td_mol_count_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
-		HIPCHK(c, hipGetLastError());
-	}
-	HIPCHK(c, hipEventRecord(z.ev_c1, s.cs));
-	// the finish kernel waits for ev_hits: a slot whose batch has been waited for is no longer read by this count either
-	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));
-	s.hits_queued = true;
-	return TD_OK;
+	TdMolArgs a = mol_args(c->molecules, s, out_type, out_barcode, out_finger, labels);
+	return kt_count_slot(c, c->molecules.table, s, (const void*)td_mol_count_kernel, &a);
 }
 
 int mol_dedup_slot(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
@@ -316,7 +282,7 @@ int mol_dedup_slot(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_b
 	if (z.p1_queued[t ^ 1]) HIPCHK(c, hipStreamWaitEvent(s.cs, z.ev_p1[t ^ 1], 0));
 	z.turn = t ^ 1;
 	hipLaunchKernelGGL(td_mol_mark_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, out_type, (const int32_t*)s.d_judged, a.read_at,
-	                   (const kt_u64*)z.d_first, base, a.n_reads, a.n_tiles, z.d_tallies);
+	                   (const kt_u64*)z.d_first, base, a.n_reads, a.n_tiles, z.table.d_tallies);
 	HIPCHK(c, hipGetLastError());
 	HIPCHK(c, hipEventRecord(z.ev_d1, s.cs));
 	// the finish kernel copies out_type only behind pass 2, and the slot is not restaged under it
@@ -340,24 +306,13 @@ extern "C" int td_mol_enable(td_ctx* c, int32_t prefix_bases, int32_t log2_slots
 	mol_release(c);
 	TdMolState& z = c->molecules;
 	const td_model_desc& m = c->model.d;
-	const size_t n_slots = (size_t)1 << log2_slots;
-	const size_t row_bytes = sizeof(kt_u64) * TD_NUM_BARCODE_BINS * TDM_ROW_WORDS;
-	bool ok = hipMalloc((void**)&z.d_label, sizeof(int32_t) * (size_t)m.H) == hipSuccess &&
-	          hipMalloc((void**)&z.d_keys, sizeof(kt_u64) * n_slots) == hipSuccess &&
-	          hipMalloc((void**)&z.d_counts, sizeof(kt_u64) * n_slots) == hipSuccess &&
-	          hipMalloc((void**)&z.d_tallies, sizeof(kt_u64) * TDM_TALLY_WORDS) == hipSuccess &&
-	          hipMalloc((void**)&z.d_rows, row_bytes) == hipSuccess &&
-	          hipMemcpy(z.d_label, m.label, sizeof(int32_t) * (size_t)m.H, hipMemcpyHostToDevice) == hipSuccess &&
-	          hipMemset(z.d_keys, 0, sizeof(kt_u64) * n_slots) == hipSuccess &&
-	          hipMemset(z.d_counts, 0, sizeof(kt_u64) * n_slots) == hipSuccess &&
-	          hipMemset(z.d_tallies, 0, sizeof(kt_u64) * TDM_TALLY_WORDS) == hipSuccess &&
-	          hipEventCreate(&z.ev_c0) == hipSuccess && hipEventCreate(&z.ev_c1) == hipSuccess;
-	if (!ok) {
-		const std::string e = hipGetErrorString(hipGetLastError());
+	hipError_t e = kt_table_create(z.table, m.label, m.H, log2_slots, TDM_TALLY_WORDS);
+	if (e == hipSuccess) e = hipMalloc((void**)&z.d_rows, sizeof(kt_u64) * TD_NUM_BARCODE_BINS * TDM_ROW_WORDS);
+	if (e != hipSuccess) {
 		mol_release(c);
-		return fail(c, "td_mol_enable: a table of 2^%d slots could not be set up: %s", log2_slots, e.c_str());
+		return fail(c, "td_mol_enable: a table of 2^%d slots could not be set up: %s", log2_slots, hipGetErrorString(e));
 	}
-	z.prefix = prefix_bases; z.log2_slots = log2_slots; z.H = m.H;
+	z.prefix = prefix_bases;
 	z.r_segs = 0;
 	for (int j = 0; j < m.S && j < 64; j++) if (m.seg_type[j] == 'R') z.r_segs |= 1ull << j;
 	z.on = true;
@@ -381,11 +336,8 @@ extern "C" int td_mol_reset(td_ctx* c)
 	if (!z.on) return fail(c, "td_mol_reset: the molecule count is off (td_mol_enable)");
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, sync_compute(c));   // (counts of pipelined batches may still be queued, on either compute stream)
-	const size_t n_slots = (size_t)1 << z.log2_slots;
-	HIPCHK(c, hipMemsetAsync(z.d_keys, 0, sizeof(kt_u64) * n_slots, c->stream));
-	HIPCHK(c, hipMemsetAsync(z.d_counts, 0, sizeof(kt_u64) * n_slots, c->stream));
-	HIPCHK(c, hipMemsetAsync(z.d_tallies, 0, sizeof(kt_u64) * TDM_TALLY_WORDS, c->stream));   // (dedup's three among them)
-	if (z.dedup) HIPCHK(c, hipMemsetAsync(z.d_first, 0xFF, sizeof(kt_u64) * n_slots, c->stream));
+	HIPCHK(c, kt_table_zero(z.table, c->stream));   // (dedup's three tallies among them)
+	if (z.dedup) HIPCHK(c, hipMemsetAsync(z.d_first, 0xFF, sizeof(kt_u64) << z.table.log2_slots, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	z.next_ordinal = 0;
 	z.p1_queued[0] = z.p1_queued[1] = false;          // (nothing is queued any more)
@@ -402,15 +354,14 @@ extern "C" int td_mol_dedup_enable(td_ctx* c)
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, sync_compute(c));
 	if (!z.dedup) {
-		const size_t n_slots = (size_t)1 << z.log2_slots;
-		bool ok = hipMalloc((void**)&z.d_first, sizeof(kt_u64) * n_slots) == hipSuccess &&
+		bool ok = hipMalloc((void**)&z.d_first, sizeof(kt_u64) << z.table.log2_slots) == hipSuccess &&
 		          hipEventCreateWithFlags(&z.ev_p1[0], hipEventDisableTiming) == hipSuccess &&
 		          hipEventCreateWithFlags(&z.ev_p1[1], hipEventDisableTiming) == hipSuccess &&
 		          hipEventCreate(&z.ev_d0) == hipSuccess && hipEventCreate(&z.ev_d1) == hipSuccess;
 		if (!ok) {
 			const std::string e = hipGetErrorString(hipGetLastError());
 			(void)td_mol_dedup_disable(c);
-			return fail(c, "td_mol_dedup_enable: the first ordinals of 2^%d slots could not be set up: %s", z.log2_slots, e.c_str());
+			return fail(c, "td_mol_dedup_enable: the first ordinals of 2^%d slots could not be set up: %s", z.table.log2_slots, e.c_str());
 		}
 		z.dedup = true;
 	}
@@ -424,12 +375,7 @@ extern "C" int td_mol_dedup_disable(td_ctx* c)
 	if (!z.dedup && !z.d_first && !z.ev_p1[0] && !z.ev_p1[1] && !z.ev_d0 && !z.ev_d1) return TD_OK;
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, sync_compute(c));
-	if (z.d_first) (void)hipFree(z.d_first);
-	hipEvent_t ev[] = { z.ev_p1[0], z.ev_p1[1], z.ev_d0, z.ev_d1 };
-	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-	z.d_first = nullptr; z.ev_p1[0] = z.ev_p1[1] = z.ev_d0 = z.ev_d1 = nullptr;
-	z.p1_queued[0] = z.p1_queued[1] = false;
-	z.dedup = false;
+	dedup_release(z);
 	return TD_OK;
 }
 
@@ -442,7 +388,7 @@ extern "C" int td_mol_dedup_get(td_ctx* c, td_mol_dedup_totals* totals)
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, sync_compute(c));
 	kt_u64 t[TDM_TALLY_WORDS];
-	HIPCHK(c, hipMemcpy(t, z.d_tallies, sizeof t, hipMemcpyDeviceToHost));
+	HIPCHK(c, hipMemcpy(t, z.table.d_tallies, sizeof t, hipMemcpyDeviceToHost));
 	totals->kept = (int64_t)t[TDM_KEPT]; totals->duplicates = (int64_t)t[TDM_DUPLICATES]; totals->unjudged = (int64_t)t[TDM_UNJUDGED];
 	return TD_OK;
 }
@@ -452,22 +398,8 @@ extern "C" int td_mol_entries(td_ctx* c, td_census_entry* entries, int64_t cap, 
 	if (!c) return TD_FAIL;
 	TdMolState& z = c->molecules;
 	if (!z.on) return fail(c, "td_mol_entries: the molecule count is off (td_mol_enable)");
-	if (cap < 0 || (cap > 0 && !entries) || !n) return fail(c, "td_mol_entries: bad arguments");
-	*n = 0;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
 	kt_u64 t[TDM_TALLY_WORDS];
-	HIPCHK(c, hipMemcpy(t, z.d_tallies, sizeof t, hipMemcpyDeviceToHost));
-	const int64_t distinct = (int64_t)t[TDM_MOLECULES];
-	std::vector<td_census_entry> v((size_t)distinct);
-	int64_t found = 0;
-	const hipError_t e = kt_compact(z.d_keys, z.d_counts, z.log2_slots, v.data(), distinct, z.d_tallies + TDM_CURSOR, c->stream, &found);
-	if (e != hipSuccess) return fail(c, "td_mol_entries: compaction failed: %s", hipGetErrorString(e));
-	if (found != distinct) return fail(c, "td_mol_entries: the table holds %lld keys, its tally says %lld", (long long)found, (long long)distinct);
-	std::sort(v.begin(), v.end(), census_entry_before);
-	const int64_t take = std::min<int64_t>(cap, distinct);
-	if (take > 0) memcpy(entries, v.data(), sizeof(td_census_entry) * (size_t)take);
-	*n = distinct;
+	if (kt_table_entries(c, "td_mol_entries", z.table, TDM_MOLECULES, TDM_CURSOR, entries, cap, n, t) != TD_OK) return TD_FAIL;
 	if (totals) totals_from(t, totals);
 	return TD_OK;
 }
@@ -481,17 +413,17 @@ extern "C" int td_mol_get(td_ctx* c, td_mol_row rows[TD_NUM_BARCODE_BINS], td_mo
 	static_assert(sizeof(td_mol_row) == sizeof(kt_u64) * TDM_ROW_WORDS, "td_mol_row is the device row");
 	HIPCHK(c, hipSetDevice(c->device));
 	HIPCHK(c, sync_compute(c));
-	const int64_t n_slots = (int64_t)1 << z.log2_slots;
+	const int64_t n_slots = (int64_t)1 << z.table.log2_slots;
 	int64_t blocks = (n_slots + KT_BLOCK - 1) / KT_BLOCK;
 	if (blocks > 1024) blocks = 1024;
 	HIPCHK(c, hipMemsetAsync(z.d_rows, 0, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, c->stream));
-	hipLaunchKernelGGL(td_mol_summary_kernel, dim3((unsigned)blocks), dim3(KT_BLOCK), 0, c->stream, z.d_keys, z.d_counts, n_slots, z.d_rows);
+	hipLaunchKernelGGL(td_mol_summary_kernel, dim3((unsigned)blocks), dim3(KT_BLOCK), 0, c->stream, z.table.d_keys, z.table.d_counts, n_slots, z.d_rows);
 	HIPCHK(c, hipGetLastError());
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	HIPCHK(c, hipMemcpy(rows, z.d_rows, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, hipMemcpyDeviceToHost));
 	if (totals) {
 		kt_u64 t[TDM_TALLY_WORDS];
-		HIPCHK(c, hipMemcpy(t, z.d_tallies, sizeof t, hipMemcpyDeviceToHost));
+		HIPCHK(c, hipMemcpy(t, z.table.d_tallies, sizeof t, hipMemcpyDeviceToHost));
 		totals_from(t, totals);
 	}
 	return TD_OK;
@@ -500,32 +432,18 @@ extern "C" int td_mol_get(td_ctx* c, td_mol_row rows[TD_NUM_BARCODE_BINS], td_mo
 // the count kernel's time of the last batch, for tools/molecules_bench.py (option "molecules_kernel_us" of td_get_option)
 int mol_last_kernel_us(td_ctx* c, int32_t* us)
 {
-	TdMolState& z = c->molecules;
-	if (!z.on) return fail(c, "td_get_option: molecules_kernel_us: the molecule count is off");
-	HIPCHK(c, hipSetDevice(c->device));
-	float ms = 0.0f;
-	if (hipEventSynchronize(z.ev_c1) != hipSuccess || hipEventElapsedTime(&ms, z.ev_c0, z.ev_c1) != hipSuccess) {
-		(void)hipGetLastError();
-		return fail(c, "td_get_option: molecules_kernel_us: no batch has been counted yet");
-	}
-	*us = (int32_t)(ms * 1000.0f + 0.5f);
-	return TD_OK;
+	const TdCountTable& t = c->molecules.table;
+	if (!c->molecules.on) return fail(c, "td_get_option: molecules_kernel_us: the molecule count is off");
+	return kt_last_kernel_us(c, t.ev_c0, t.ev_c1, us, "td_get_option: molecules_kernel_us: no batch has been counted yet");
 }
 
 // the two passes' time of the last batch (option "dedup_kernel_us" of td_get_option).  Between them the stream waits for the batch
 // before: with batches in flight on both compute streams that wait is inside the figure, after a td_run it is not.
 int mol_dedup_last_kernel_us(td_ctx* c, int32_t* us)
 {
-	TdMolState& z = c->molecules;
+	const TdMolState& z = c->molecules;
 	if (!z.dedup) return fail(c, "td_get_option: dedup_kernel_us: dedup is off");
-	HIPCHK(c, hipSetDevice(c->device));
-	float ms = 0.0f;
-	if (hipEventSynchronize(z.ev_d1) != hipSuccess || hipEventElapsedTime(&ms, z.ev_d0, z.ev_d1) != hipSuccess) {
-		(void)hipGetLastError();
-		return fail(c, "td_get_option: dedup_kernel_us: no batch has been judged yet");
-	}
-	*us = (int32_t)(ms * 1000.0f + 0.5f);
-	return TD_OK;
+	return kt_last_kernel_us(c, z.ev_d0, z.ev_d1, us, "td_get_option: dedup_kernel_us: no batch has been judged yet");
 }
 
 extern "C" int td_mol_summarise(const td_census_entry* entries, int64_t n, td_mol_row rows[TD_NUM_BARCODE_BINS])
@@ -562,9 +480,9 @@ extern "C" int td_mol_host(const td_model_desc* m, int32_t prefix_bases, const u
 		else { keys.push_back(key); t.counted++; }
 	}
 	std::vector<td_census_entry> v;
-	census_tally_keys(keys, v);
+	kt_tally_keys(keys, v);
 	t.molecules = (int64_t)v.size();
-	if (!(*entries = census_copy_entries(v))) return fail(nullptr, "td_mol_host: out of memory");
+	if (!(*entries = kt_copy_entries(v))) return fail(nullptr, "td_mol_host: out of memory");
 	*n = (int64_t)v.size();
 	if (totals) *totals = t;
 	return TD_OK;

@@ -774,6 +774,30 @@ struct Run {
 	int run_files(td_stream_stats& st);
 	int unknown_barcodes(int bar_file);
 	int molecules();
+
+	// Every device's entries of a file, merged: acc[n_acc] is the caller's to td_census_free (NULL after a failure), per[d] the
+	// totals of device d.  `get` is td_census_get or td_mol_entries.
+	template <typename Totals>
+	int merged_entries(const FileState& f, int (*get)(td_ctx*, td_census_entry*, int64_t, int64_t*, Totals*), td_census_entry*& acc, int64_t& n_acc,
+	                   std::vector<Totals>& per)
+	{
+		acc = nullptr; n_acc = 0;
+		for (td_ctx* c : f.raw) {
+			int64_t n = 0, n_merged = 0;
+			Totals t{};
+			td_census_entry* merged = nullptr;
+			bool ok = get(c, nullptr, 0, &n, &t) == TD_OK;
+			std::vector<td_census_entry> part((size_t)std::max<int64_t>(n, 1));
+			ok = ok && get(c, part.data(), n, &n, &t) == TD_OK;
+			if (!ok) fail("%s", td_last_error(c));
+			else if (!(ok = td_census_merge(acc, n_acc, part.data(), n, &merged, &n_merged) == TD_OK)) fail("%s", td_last_error(nullptr));
+			td_census_free(acc);
+			acc = merged; n_acc = n_merged;
+			if (!ok) return TD_FAIL;
+			per.push_back(t);
+		}
+		return TD_OK;
+	}
 };
 
 int Run::execute()
@@ -947,18 +971,9 @@ int Run::unknown_barcodes(int bar_file)
 	td_census_entry* acc = nullptr;
 	int64_t n_acc = 0;
 	td_census_totals sum{};
-	for (td_ctx* c : f.raw) {
-		int64_t n = 0;
-		td_census_totals t{};
-		if (td_census_get(c, nullptr, 0, &n, &t) != TD_OK) { td_census_free(acc); return fail("%s", td_last_error(c)); }
-		std::vector<td_census_entry> part((size_t)std::max<int64_t>(n, 1));
-		if (td_census_get(c, part.data(), n, &n, &t) != TD_OK) { td_census_free(acc); return fail("%s", td_last_error(c)); }
-		td_census_entry* merged = nullptr;
-		int64_t n_merged = 0;
-		const int rc = td_census_merge(acc, n_acc, part.data(), n, &merged, &n_merged);
-		td_census_free(acc);
-		if (rc != TD_OK) return fail("%s", td_last_error(nullptr));
-		acc = merged; n_acc = n_merged;
+	std::vector<td_census_totals> per;
+	if (merged_entries(f, td_census_get, acc, n_acc, per) != TD_OK) return TD_FAIL;
+	for (const td_census_totals& t : per) {
 		sum.eligible += t.eligible; sum.counted += t.counted; sum.skipped_empty += t.skipped_empty; sum.skipped_long += t.skipped_long;
 		sum.skipped_n += t.skipped_n; sum.overflow += t.overflow;
 	}
@@ -1008,18 +1023,9 @@ int Run::molecules()
 	} else {
 		td_census_entry* acc = nullptr;
 		int64_t n_acc = 0;
-		for (td_ctx* c : f.raw) {
-			int64_t n = 0;
-			td_mol_totals t{};
-			if (td_mol_entries(c, nullptr, 0, &n, &t) != TD_OK) { td_census_free(acc); return fail("%s", td_last_error(c)); }
-			std::vector<td_census_entry> part((size_t)std::max<int64_t>(n, 1));
-			if (td_mol_entries(c, part.data(), n, &n, &t) != TD_OK) { td_census_free(acc); return fail("%s", td_last_error(c)); }
-			td_census_entry* merged = nullptr;
-			int64_t n_merged = 0;
-			const int rc = td_census_merge(acc, n_acc, part.data(), n, &merged, &n_merged);
-			td_census_free(acc);
-			if (rc != TD_OK) return fail("%s", td_last_error(nullptr));
-			acc = merged; n_acc = n_merged;
+		std::vector<td_mol_totals> per;
+		if (merged_entries(f, td_mol_entries, acc, n_acc, per) != TD_OK) return TD_FAIL;
+		for (const td_mol_totals& t : per) {
 			sum.eligible += t.eligible; sum.counted += t.counted; sum.skipped_empty += t.skipped_empty; sum.skipped_n += t.skipped_n;
 			sum.overflow += t.overflow;
 		}

@@ -162,12 +162,20 @@ def test_refusals():
 
 
 def test_one_table_implementation():
-    """the census and the molecule count include the same device header; neither unit has a probe loop or a compaction of its own"""
+    """the census and the molecule count include the same device header; neither unit has a probe loop or a compaction of its own:
+    both count through the header's one tail (kt_wave_add: kt_wave_merge, then kt_probe_add) and read their table through the
+    shared unit's kt_table_entries"""
     csrc = os.path.join(REPO, "tagdust_amd", "csrc")
+    header = open(os.path.join(csrc, "td_keytable.h")).read()
     for unit in ("td_census.hip", "td_molecules.hip"):
         text = open(os.path.join(csrc, unit)).read()
-        assert "atomicCAS" not in text and "kt_probe_add(" in text and "kt_wave_merge(" in text and "kt_compact(" in text
-    assert open(os.path.join(csrc, "td_keytable.h")).read().count("atomicCAS") == 1
+        assert "atomicCAS" not in text and "kt_wave_add(" in text and "kt_table_entries(" in text
+        assert "compact_kernel" not in text and not re.search(r"__global__[^;{]*compact", text)
+    at = header.index("KtWaveAdded kt_wave_add(")
+    tail = header[at:header.index("\n}\n", at)]
+    assert "kt_wave_merge(" in tail and "kt_probe_add(" in tail
+    assert header.count("atomicCAS") == 1 and "__global__" not in header
+    assert open(os.path.join(csrc, "td_keytable.hip")).read().count("__global__") == 1
 
 
 def test_header_symbols_are_exported_and_bound(library):

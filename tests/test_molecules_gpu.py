@@ -450,6 +450,18 @@ def test_census_and_molecules_together_each_equal_what_they_give_alone(ctx):
     cen, ctot = ctx.census()
     assert pairs(ent) == pairs(mol_alone[0]) and tot == mol_alone[1] and pairs(ent) == pairs(yardstick(c, P)[0])
     assert pairs(cen) == pairs(census_alone[0]) and ctot == census_alone[1] and ctot["counted"] > 0
+    # each reset clears its own table and tallies, and nothing of the other's
+    ctx.census_reset()
+    ent2, tot2 = ctx.mol_entries()
+    cen2, ctot2 = ctx.census()
+    assert pairs(ent2) == pairs(ent) and tot2 == tot
+    assert len(cen2) == 0 and ctot2 and all(v == 0 for v in ctot2.values())
+    run_batch(ctx, c)
+    ctx.mol_reset()
+    ent3, tot3 = ctx.mol_entries()
+    cen3, ctot3 = ctx.census()
+    assert pairs(cen3) == pairs(census_alone[0]) and ctot3 == census_alone[1]
+    assert len(ent3) == 0 and tot3 and all(v == 0 for v in tot3.values())
 
 
 # ---- 11: the command ----

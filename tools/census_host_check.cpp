@@ -2,41 +2,15 @@
 // stand-alone program, for running it under the host sanitizers: no GPU is used, no Python.
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//       -x hip tagdust_amd/csrc/td_census.hip tools/census_host_check.cpp -o /tmp/census_host_check
+//       -x hip tagdust_amd/csrc/td_keytable.hip tagdust_amd/csrc/td_census.hip tools/census_host_check.cpp -o /tmp/census_host_check
 //   ASAN_OPTIONS=detect_leaks=0 /tmp/census_host_check        # (the HIP runtime the unit links keeps its own allocations)
 //
 // Generated reads (lengths 0..200, N bases, every outcome), generated labels over a B-S-B-R model; the census of each B segment
 // and of -1 is held against a restatement with std::map, the census of two halves merged against the whole, every key through
 // td_census_key_text and back.  Exit status 0 when all of it agrees.
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../tagdust_amd/csrc/td_ctx.h"
+#define HOST_CHECK_NAME "census_host_check"
+#include "host_check.h"
 #include "../include/tagdust_census.h"
-
-// td_api.hip is not part of this program: the message sink of the unit under test
-static std::string g_err;
-int fail(td_ctx*, const char* fmt, ...)
-{
-	char buf[512];
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(buf, sizeof buf, fmt, ap);
-	va_end(ap);
-	g_err = buf;
-	return TD_FAIL;
-}
-int default_host_threads() { return 1; }
-
-static uint32_t rnd(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "census_host_check: %s:%d: %s failed (%s)\n", __FILE__, __LINE__, #cond, g_err.c_str()); return 1; } } while (0)
 
 int main()
 {

@@ -2,42 +2,16 @@
 // sanitizers: no GPU is used, no Python.
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//       -x hip tagdust_amd/csrc/td_census.hip tagdust_amd/csrc/td_molecules.hip tools/dedup_host_check.cpp -o /tmp/dedup_host_check
+//       -x hip tagdust_amd/csrc/td_keytable.hip tagdust_amd/csrc/td_molecules.hip tools/dedup_host_check.cpp -o /tmp/dedup_host_check
 //   ASAN_OPTIONS=detect_leaks=0 /tmp/dedup_host_check            # (the HIP runtime the units link keeps its own allocations)
 //
 // Generated reads (lengths 0..200, N bases, every outcome, barcodes -1..299, few fingerprints of either sign), generated labels
 // over an F-B-R-S-R model; for prefixes of 1, 7, 16 and 32 bases the marks and totals are held against a restatement with
 // std::map over td_mol_host's own keys of each single read, the identities against td_mol_host's totals, and the reversed batch
 // must keep the last read of every key.  is_duplicate has exactly n_reads bytes.  Exit status 0 when all of it agrees.
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../tagdust_amd/csrc/td_ctx.h"
+#define HOST_CHECK_NAME "dedup_host_check"
+#include "host_check.h"
 #include "../include/tagdust_molecules.h"
-
-// td_api.hip is not part of this program: the message sink of the units under test
-static std::string g_err;
-int fail(td_ctx*, const char* fmt, ...)
-{
-	char buf[512];
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(buf, sizeof buf, fmt, ap);
-	va_end(ap);
-	g_err = buf;
-	return TD_FAIL;
-}
-int default_host_threads() { return 1; }
-
-static uint32_t rnd(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "dedup_host_check: %s:%d: %s failed (%s)\n", __FILE__, __LINE__, #cond, g_err.c_str()); return 1; } } while (0)
 
 struct Batch {
 	std::vector<int64_t> offs{ 0 };

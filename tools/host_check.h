@@ -1,0 +1,32 @@
+// host_check.h -- what the stand-alone programs over the host side of the counting units (tools/census_host_check.cpp,
+// molecules_host_check.cpp, dedup_host_check.cpp) share: the message sink td_api.hip would be, a generator, CHECK.  The program
+// defines HOST_CHECK_NAME, its name in the messages, before it includes this.
+#pragma once
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../tagdust_amd/csrc/td_ctx.h"
+
+// td_api.hip is not part of these programs: the message sink of the units under test
+static std::string g_err;
+int fail(td_ctx*, const char* fmt, ...)
+{
+	char buf[512];
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(buf, sizeof buf, fmt, ap);
+	va_end(ap);
+	g_err = buf;
+	return TD_FAIL;
+}
+int default_host_threads() { return 1; }
+
+static uint32_t rnd(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
+
+#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, HOST_CHECK_NAME ": %s:%d: %s failed (%s)\n", __FILE__, __LINE__, #cond, g_err.c_str()); return 1; } } while (0)

@@ -3,7 +3,7 @@
 // no Python.
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//       -x hip tagdust_amd/csrc/td_census.hip tagdust_amd/csrc/td_molecules.hip tagdust_amd/csrc/td_fastq.cpp \
+//       -x hip tagdust_amd/csrc/td_keytable.hip tagdust_amd/csrc/td_molecules.hip tagdust_amd/csrc/td_fastq.cpp \
 //       tools/molecules_host_check.cpp -o /tmp/molecules_host_check
 //   ASAN_OPTIONS=detect_leaks=0 /tmp/molecules_host_check        # (the HIP runtime the units link keeps its own allocations)
 //
@@ -11,34 +11,10 @@
 // F-B-R-S-R model; the count for prefixes of 1, 7, 16, 31 and 32 bases is held against a restatement with std::map, the summary
 // against a restatement, two parts merged against the whole, every fingerprint's text against get_finger_seq restated -- for the
 // lengths 0..255 the low byte can name, whose last character is buf[255].  Exit status 0 when all of it agrees.
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <map>
-#include <string>
-#include <vector>
-
-#include "../tagdust_amd/csrc/td_ctx.h"
+#define HOST_CHECK_NAME "molecules_host_check"
+#include "host_check.h"
 #include "../include/tagdust_io.h"
 #include "../include/tagdust_molecules.h"
-
-// td_api.hip is not part of this program: the message sink of the units under test
-static std::string g_err;
-int fail(td_ctx*, const char* fmt, ...)
-{
-	char buf[512];
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(buf, sizeof buf, fmt, ap);
-	va_end(ap);
-	g_err = buf;
-	return TD_FAIL;
-}
-int default_host_threads() { return 1; }
-
-static uint32_t rnd(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 
 static uint64_t mix(uint64_t k)
 {
@@ -47,8 +23,6 @@ static uint64_t mix(uint64_t k)
 	k ^= k >> 31;
 	return k;
 }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "molecules_host_check: %s:%d: %s failed (%s)\n", __FILE__, __LINE__, #cond, g_err.c_str()); return 1; } } while (0)
 
 int main()
 {
