@@ -18,7 +18,8 @@
  *
  * with the record's own fingerprint and barcode (td_read_result; the fingerprint is -1 without an 'F' segment).  So two reads are
  * the same molecule when they have the same barcode, the same fingerprint and the same first P read bases.  The match is exact: a
- * sequencing error in the prefix or in the UMI makes a new molecule (no neighbouring UMIs are collapsed).  Two limits:
+ * sequencing error in the prefix or in the UMI makes a new molecule (the count itself collapses no neighbouring UMIs; the collapse
+ * below does, on top of it).  Two limits:
  *   - within one barcode two molecules whose 56-bit `low` collide are counted as one.  Among m molecules of a barcode about
  *     m^2 / 2 * 2^-56 pairs do: 0.0007 for m = 10^7 -- one run in 1400 counts one molecule too few;
  *   - the reference's fingerprint is an int of (bases << 8 | length): a UMI of more than 12 bases has lost its leading bases in
@@ -46,8 +47,34 @@
  * molecules being the keys that entered the table since the reset.  The result is a function of the context's sequence of reads
  * alone: not of how it was cut into batches, of td_run or td_submit, of the tickets in flight or of the kernel variant.  Limits:
  * the 56-bit collision above (two molecules that collide lose one read); and which keys overflow in a nearly full table depends on
- * the claim order within a batch, as it does for the count.  No neighbouring UMIs are collapsed; a molecule split over two
- * contexts survives in both (each has its own table).
+ * the claim order within a batch, as it does for the count.  Dedup matches exactly, with or without the collapse below; a molecule
+ * split over two contexts survives in both (each has its own table).
+ *
+ * Collapse (td_mol_collapse_enable) -- UMIs one mismatch apart counted as one molecule -- reads the count's table and changes
+ * nothing in it.  The reference has nothing of the kind; this is the definition, held bit for bit by the device path and by
+ * td_mol_collapse_host:
+ *   - origin.  A key is a hash, so beside every key the table keeps what it was made of: the counted read's prefix word w, its
+ *     record's fingerprint and its prefix length n (td_mol_origin), the arguments of td_mol_key beside the barcode bin, which is
+ *     the key's top byte.  All reads of a key have the same origin, but for the 56-bit collision above: then it is that of any
+ *     one of the colliding molecules;
+ *   - neighbours.  L = fingerprint & 0xFF, m = min(L, 12), the bases an int fingerprint still holds.  The neighbours of molecule
+ *     u are the 3 * m keys
+ *         td_mol_key(bin(u), fingerprint ^ (d << (8 + 2 * i)), w, n)      i in 0..m-1, d in 1..3     (xor on the uint32 pattern)
+ *     that the table holds: the same barcode bin, the same prefix, a UMI at Hamming distance exactly one.  A key that overflowed
+ *     is in nobody's neighbourhood; a molecule with fingerprint -1 (no 'F' segment) has no neighbours;
+ *   - parent (the directional rule of UMI-tools, made deterministic).  v qualifies as a parent of u when
+ *     count(v) >= 2 * count(u) - 1 and (count(v), key(v)) comes strictly before (count(u), key(u)) in the order of td_census_get
+ *     (count descending, then key ascending).  The parent of u is the qualifying neighbour that comes first in that order;
+ *     without one u is a root.  Two neighbours qualify for each other only when both have count 1, and then the key decides: the
+ *     relation is a forest, and every step up is strictly earlier in a total order, so the walk to a root ends;
+ *   - collapse.  Every molecule is counted under its root: collapsed(root) = the sum of the counts of the root's tree.  Always
+ *         molecules_after + absorbed == molecules_before      and      the sum of collapsed == counted,
+ *     and the reads of a barcode bin are unchanged (a parent is in its child's bin).  longest_chain is the largest number of
+ *     steps from a molecule to its root.
+ * The result is a function of the set of (key, count, origin) alone: not of slot positions, batching, tickets in flight or kernel
+ * variant.  Limits: distance one only; the UMI only (an error in the prefix still makes a new molecule); the leading bases of a
+ * UMI of more than 12 are not in the fingerprint and take no part; the tree can differ from UMI-tools' breadth-first clusters, in
+ * which the largest root claims a shared descendant -- here the child chooses; dedup is not changed by it.
  */
 #ifndef TAGDUST_MOLECULES_H
 #define TAGDUST_MOLECULES_H
@@ -103,6 +130,30 @@ int td_mol_dedup_get    (td_ctx* ctx, td_mol_dedup_totals* totals);   /* waits f
  * Never overflows.  totals may be NULL. */
 int td_mol_dedup_host   (const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
                          const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate, td_mol_dedup_totals* totals);
+/* Collapse, see above.  td_mol_collapse_enable: TD_FAIL with a message unless the count is on, the model has an 'F' segment and no
+ * td_submit tickets are outstanding; it allocates 16 more bytes per slot (the origins) and starts from an empty table, so every key
+ * in the table has its origin.  td_mol_disable, and with it a new model, switches it off as well; td_mol_reset clears the origins. */
+typedef struct td_mol_origin { uint64_t w; int32_t fingerprint; int32_t n; } td_mol_origin;   /* 16 bytes */
+typedef struct td_mol_collapse_totals { int64_t molecules_before, molecules_after, absorbed, longest_chain; } td_mol_collapse_totals;
+int td_mol_collapse_enable (td_ctx* ctx);
+int td_mol_collapse_disable(td_ctx* ctx);           /* frees the origins and what the collapse itself allocated; table and count stay */
+/* td_mol_entries with the origin of every entry in a parallel array, in the same order (collapse on) */
+int td_mol_origins         (td_ctx* ctx, td_census_entry* entries, td_mol_origin* origins, int64_t cap, int64_t* n, td_mol_totals* totals);
+/* Both wait for the context's queued work and run the collapse on the device; keys, counts and origins stay untouched, so both may
+ * be called in the middle of a run and again later.  td_mol_collapse_get: the rows of td_mol_get made from the collapsed counts
+ * (molecules = roots, levels from collapsed).  td_mol_collapse_entries: the roots with collapsed as their count, in the order of
+ * td_census_get, with their origins; *n = the number of roots, at most cap are copied.  totals may be NULL. */
+int td_mol_collapse_get    (td_ctx* ctx, td_mol_row rows[TD_NUM_BARCODE_BINS], td_mol_collapse_totals* totals);
+int td_mol_collapse_entries(td_ctx* ctx, td_census_entry* entries, td_mol_origin* origins, int64_t cap, int64_t* n, td_mol_collapse_totals* totals);
+/* td_mol_host plus the origin of every entry (*origins is freed with free) */
+int td_mol_host_origins    (const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                            const td_read_result* res, const int8_t* labels, td_census_entry** entries, td_mol_origin** origins, int64_t* n,
+                            td_mol_totals* totals);
+/* The collapse on the host, no GPU: what td_mol_collapse_entries returns, from entries and their origins.  A key may be given more
+ * than once: its counts are added first, so the td_mol_origins results of several devices, concatenated, are a valid input -- the
+ * multi-device path, and the yardstick of the device.  *out_entries is freed with td_census_free, *out_origins with free. */
+int td_mol_collapse_host   (const td_census_entry* entries, const td_mol_origin* origins, int64_t n,
+                            td_census_entry** out_entries, td_mol_origin** out_origins, int64_t* out_n, td_mol_collapse_totals* totals);
 /* the key of a counted read: its record's barcode and fingerprint, its prefix word w of n bases (1..32) */
 uint64_t td_mol_key(int32_t barcode, int32_t fingerprint, uint64_t w, int32_t n);
 int32_t  td_mol_key_bin(uint64_t key);              /* the barcode bin a key belongs to */

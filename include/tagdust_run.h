@@ -77,6 +77,8 @@ typedef struct td_run_opts {
 	int32_t  dedup;                  /* --dedup: one read per molecule is written (tagdust_molecules.h, td_mol_dedup_enable): an extracted
 	                                    read that is not the first of its molecule goes to no file.  Implies --molecules (the parser sets
 	                                    it); one input file, one device */
+	int32_t  collapse_umis;          /* --collapse-umis: fingerprints one mismatch apart are counted as one molecule (tagdust_molecules.h,
+	                                    td_mol_collapse_enable).  Implies --molecules (the parser sets it); refused without an F segment */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -102,7 +104,9 @@ const char* td_run_version(void);
  * its UMI then sit in different files' contexts -- and for a read-only architecture, which has no model; --dedup implies
  * --molecules, is refused wherever that is and with more than one device -- each has its own table, a molecule split over two
  * would survive twice -- and adds two lines, "# written" and "# duplicates removed", to <out>_molecules.txt and nothing to the
- * log, the _un file or the counts), the
+ * log, the _un file or the counts; --collapse-umis implies --molecules, is refused wherever that is and for an architecture without
+ * an F segment, may be given with --dedup, which still matches exactly, and adds three lines -- "# UMI collapse", "# molecules
+ * after collapse", "# absorbed" -- and two columns behind "10+", "collapsed" and "duplication_collapsed", to <out>_molecules.txt), the
  * multiread rule (interface.c:441-450: DUST and -ref off, with a warning, when the command line's architecture has two or more
  * R segments).  What depends on the arch file's choice is decided again by td_run_execute once the choice is made. */
 typedef struct td_run_plan_t td_run_plan_t;   /* (the function below has the plain name) */
@@ -142,6 +146,10 @@ typedef struct td_run_report {
 	td_mol_totals molecules_totals;           /* summed over the devices; molecules = distinct keys after the merge */
 	int32_t  dedup;                           /* 1: the run removed duplicates (--dedup) */
 	td_mol_dedup_totals dedup_totals;         /* --dedup: extracted reads written, duplicates removed, reads that could not be judged */
+	int32_t  collapse;                        /* 1: the run collapsed neighbouring UMIs (--collapse-umis) */
+	td_mol_collapse_totals collapse_totals;   /* --collapse-umis: molecules before and after, absorbed, the longest chain */
+	td_mol_row* molecules_collapsed;          /* --collapse-umis: [TD_NUM_BARCODE_BINS] the rows from the collapsed counts (NULL without the
+	                                             option): td_mol_collapse_get's, or td_mol_summarise of td_mol_collapse_host over the devices' td_mol_origins */
 } td_run_report;
 /* In the controller's order: architectures per file, statistics over each file's head, thresholds, models, the run, the log.
  * A failure before the first batch leaves no output files behind; one during the run leaves them as they are and says so.  The

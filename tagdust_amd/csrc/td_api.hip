@@ -372,6 +372,8 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	if (!strcmp(name, "molecules_kernel_us")) return mol_last_kernel_us(c, value);
 	if (!strcmp(name, "dedup_active")) { *value = c->molecules.dedup; return TD_OK; }
 	if (!strcmp(name, "dedup_kernel_us")) return mol_dedup_last_kernel_us(c, value);   // the two passes of the last batch
+	if (!strcmp(name, "collapse_active")) { *value = c->molecules.collapse; return TD_OK; }
+	if (!strcmp(name, "collapse_origin_kernel_us")) return mol_origin_last_kernel_us(c, value);   // the origin pass of the last batch
 	if (!strcmp(name, "overlap_active")) {
 		// pipelined batches alternate between two compute streams / workspaces (off: option, generic kernel, depth 1, or HBM
 		// could not hold the second workspace)
@@ -846,6 +848,7 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	if (ka.art_n > 0 && slot_count_hits(c, s, ka.out_type) != TD_OK) return TD_FAIL;
 	if (c->census.on && mode == TD_MODE_GET_LABEL && census_count_slot(c, s, ka.out_type, ka.out_labels) != TD_OK) return TD_FAIL;
 	if (c->molecules.on && mode == TD_MODE_GET_LABEL && mol_count_slot(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
+	if (c->molecules.collapse && mode == TD_MODE_GET_LABEL && mol_origin_slot(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
 	// dedup last: its second pass rewrites the outcomes the three counts above read
 	if (c->molecules.dedup && mode == TD_MODE_GET_LABEL && mol_dedup_slot(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
 	s.ran = true;

@@ -4,15 +4,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/tagdust_molecules.h"
 #include "td_keytable.h"
 
 struct td_ctx;
 struct TdSlot;
 
 // tallies of the device table, 64 bits each, in the order of td_mol_totals; behind them the compaction's cursor, then dedup's
-// three in the order of td_mol_dedup_totals
+// three in the order of td_mol_dedup_totals, then the collapse's: the cursor of its two gathers, its roots, its longest chain
 enum { TDM_ELIGIBLE = 0, TDM_COUNTED, TDM_EMPTY, TDM_N, TDM_OVERFLOW, TDM_MOLECULES, TDM_CURSOR, TDM_KEPT, TDM_DUPLICATES, TDM_UNJUDGED,
-       TDM_TALLY_WORDS };
+       TDM_GATHERED, TDM_ROOTS, TDM_CHAIN, TDM_TALLY_WORDS };
 // words of a barcode bin's summary row: reads, molecules, ten levels (td_mol_row)
 #define TDM_ROW_WORDS 12
 
@@ -30,6 +31,14 @@ struct TdMolState {
 	bool p1_queued[2] = { false, false };
 	int turn = 0;
 	hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr;   // around the two passes of the last batch (option "dedup_kernel_us")
+	// collapse (td_mol_collapse_enable): the origin of every slot's key; what a collapse computes, allocated by the first one
+	bool collapse = false;
+	td_mol_origin* d_origin = nullptr;        // [2^log2_slots], n == 0 = no origin yet
+	hipEvent_t ev_o0 = nullptr, ev_o1 = nullptr;   // around the origin pass of the last batch (option "collapse_origin_kernel_us")
+	uint32_t* d_occ = nullptr;                // [cap_occ] the occupied slots' indices
+	int64_t cap_occ = 0;
+	uint32_t* d_parent = nullptr;             // [2^log2_slots] the slot of every occupied slot's parent, its own for a root
+	unsigned long long* d_collapsed = nullptr;   // [2^log2_slots] the count of a root's tree, 0 for every other slot
 };
 
 struct TdMolArgs {
@@ -49,6 +58,8 @@ struct TdMolArgs {
 	unsigned long long* __restrict__ first;   // [slot_mask + 1] the smallest ordinal of every slot's key
 	int32_t* __restrict__ judged;             // [n_tiles*64] the read's table slot, -1 = not judged
 	int64_t ordinal_base;                     // the ordinal of the batch's first read in the caller's order
+	// the collapse's origin pass alone
+	td_mol_origin* origin;                    // [slot_mask + 1] (not __restrict__: lanes of other waves write the same words)
 };
 
 // the count of one decoded slot, queued on its compute stream (td_api.hip calls it behind the decode launch while the count is on)
@@ -58,6 +69,12 @@ __attribute__((visibility("hidden"))) int mol_count_slot(td_ctx* c, TdSlot& s, c
 // pass 2 rewrites out_type, so everything that reads the decoded outcomes is queued in front of it
 __attribute__((visibility("hidden"))) int mol_dedup_slot(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode,
                                                          const int32_t* out_finger, const int8_t* labels);
+// the collapse's origin pass over one decoded slot, queued behind its count and in front of dedup, whose second pass rewrites the
+// outcomes it reads (td_api.hip calls it in slot_decode while the collapse is on)
+__attribute__((visibility("hidden"))) int mol_origin_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode,
+                                                          const int32_t* out_finger, const int8_t* labels);
+// option "collapse_origin_kernel_us" of td_get_option: the origin pass's time of the last batch (waits for it)
+__attribute__((visibility("hidden"))) int mol_origin_last_kernel_us(td_ctx* c, int32_t* us);
 // option "dedup_kernel_us" of td_get_option: the two passes' time of the last batch (waits for it)
 __attribute__((visibility("hidden"))) int mol_dedup_last_kernel_us(td_ctx* c, int32_t* us);
 // option "molecules_kernel_us" of td_get_option: the count kernel's time of the last counted batch (waits for it)

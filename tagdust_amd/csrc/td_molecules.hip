@@ -15,12 +15,20 @@
 // TD_EXTRACT_DUPLICATE.  The minimum does not depend on the order the reads arrive in, so the two passes of neighbouring batches
 // may overlap but for one thing: pass 2 waits for pass 1 of the batch before it (an event), since that batch holds smaller
 // ordinals.  td_mol_dedup_host is the same decision on the host.
+//
+// Collapse (td_mol_collapse_enable) adds one launch behind the count, in front of dedup: the origin pass builds every read's key
+// once more, finds its slot and leaves what the key was made of beside it (16 bytes per slot).  The collapse itself runs when it
+// is asked for, over an idle table: the occupied slots' indices gathered into a dense list, then one molecule per lane -- the
+// parent pass probes the 3 * m keys one UMI mismatch away and keeps the best qualifying one, the root pass walks up and adds the
+// molecule's count to its root's --, then the summary sweep above over the collapsed counts, or a gather of the roots.
+// td_mol_collapse_host is the same definition on the host.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <string>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -46,7 +54,8 @@ __device__ __forceinline__ void mol_r_labels(const TdMolArgs& a, uint8_t* s_r)
 }
 
 // what a lane's read is to the count: eligible, and then exactly one of the three classes (has_key: counted under `key`)
-struct MolLane { bool elig, is_empty, is_n, has_key; kt_u64 key; };
+// (w, n, finger: what the key was made of, for the collapse's origin pass)
+struct MolLane { bool elig, is_empty, is_n, has_key; kt_u64 key, w; int32_t n, finger; };
 
 // The key of read k = tile * 64 + lane: the label walk, the prefix word and the N mask (whole waves).  false: no lane of the wave
 // is eligible, nothing else was read.  The count kernel and dedup's pass 1 both call this: one text.
@@ -54,7 +63,7 @@ __device__ __forceinline__ bool mol_lane_key(const TdMolArgs& a, const uint8_t* 
 {
 	bool elig = false;
 	if (k < a.n_reads) elig = ((uint32_t)a.out_type[k] & 0xFFu) == (uint32_t)TD_EXTRACT_SUCCESS;   // the outcome first: the other lanes read nothing more
-	m.elig = elig; m.is_empty = false; m.is_n = false; m.has_key = false; m.key = 0ull;
+	m.elig = elig; m.is_empty = false; m.is_n = false; m.has_key = false; m.key = 0ull; m.w = 0ull; m.n = 0; m.finger = -1;
 	if (__builtin_amdgcn_ballot_w64(elig) == 0ull) return false;
 	int len = 0, barcode = -1, finger = -1;
 	if (elig) { len = a.lens[k]; barcode = a.out_barcode[k]; finger = a.out_finger[k]; }
@@ -71,6 +80,7 @@ __device__ __forceinline__ bool mol_lane_key(const TdMolArgs& a, const uint8_t* 
 	m.is_n = elig && n > 0 && has_n;
 	m.has_key = elig && n > 0 && !has_n;
 	m.key = m.has_key ? mol_key(barcode, finger, w, n) : 0ull;
+	m.w = w; m.n = n; m.finger = finger;
 	return true;
 }
 
@@ -154,6 +164,143 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_mark_kernel(int32_t* __restri
 	}
 }
 
+// Collapse, the origin pass: behind the count kernel of the same batch on the same stream, so a counted read's key is in the table or
+// has overflowed for good.  One lane per distinct key of the wave goes on; a slot without an origin yet (n == 0: a counted read has
+// n >= 1) gets it in two plain 8-byte stores, n last.  Origin passes of two batches may meet in a slot: both write the same words.
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_origin_kernel(const TdMolArgs a)
+{
+	__shared__ uint8_t s_r[128];
+	mol_r_labels(a, s_r);
+	const int lane = threadIdx.x & (TD_WAVE - 1);
+	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
+	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
+	const int64_t k = (int64_t)tile * TD_WAVE + lane;
+	MolLane m;
+	if (!mol_lane_key(a, s_r, tile, lane, k, m)) return;
+	if (kt_wave_merge(m.has_key, m.key, lane) <= 0) return;
+	const int32_t slot = kt_probe_find(a.table, m.key);
+	if (slot < 0) return;                             // overflowed: it is in nobody's neighbourhood
+	kt_u64* o = (kt_u64*)&a.origin[slot];
+	if ((uint32_t)(__hip_atomic_load(&o[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) != 0u) return;
+	o[0] = m.w;
+	o[1] = (kt_u64)(uint32_t)m.finger | ((kt_u64)(uint32_t)m.n << 32);
+}
+
+// Collapse: the indices of the occupied slots into a dense list, the pattern of td_keytable.hip's sweep over the pairs (one add on
+// the cursor per wave, the lanes behind it by their rank) -- a quarter-full table would leave three lanes in four idle below
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_occupied_kernel(const kt_u64* __restrict__ keys, int64_t n_slots, uint32_t* __restrict__ occ,
+                                                                    int64_t cap, kt_u64* __restrict__ cursor)
+{
+	const int lane = threadIdx.x & (TD_WAVE - 1);
+	const int64_t step = (int64_t)gridDim.x * KT_BLOCK;
+	for (int64_t i0 = (int64_t)blockIdx.x * KT_BLOCK + (threadIdx.x - lane); i0 < n_slots; i0 += step) {   // (i0 is the wave's)
+		const int64_t i = i0 + lane;
+		const kt_u64 kv = i < n_slots ? keys[i] : 0ull;
+		const kt_u64 hit = __builtin_amdgcn_ballot_w64(kv != 0ull);
+		if (hit == 0ull) continue;
+		kt_u64 base = 0ull;
+		if (lane == __builtin_ctzll(hit)) base = atomicAdd(cursor, (kt_u64)__builtin_popcountll(hit));
+		base = kt_readlane64(base, __builtin_ctzll(hit));
+		const int64_t at = (int64_t)base + __builtin_popcountll(hit & ((1ull << lane) - 1ull));
+		if (kv != 0ull && at < cap) occ[at] = (uint32_t)i;
+	}
+}
+
+// (count, key) of v comes strictly before that of u in the order of td_census_get
+__host__ __device__ __forceinline__ bool mol_before(kt_u64 cv, kt_u64 kv, kt_u64 cu, kt_u64 ku) { return cv != cu ? cv > cu : kv < ku; }
+// UMI bases that take part: what an int fingerprint of (bases << 8 | length) still holds; none without a fingerprint
+__host__ __device__ __forceinline__ int mol_umi_bases(int32_t fingerprint)
+{
+	if (fingerprint == -1) return 0;
+	const int L = fingerprint & 0xFF;
+	return L < 12 ? L : 12;
+}
+// the key of u's neighbour with base i changed by d (1..3)
+__host__ __device__ __forceinline__ kt_u64 mol_neighbour_key(kt_u64 key, const td_mol_origin& o, int i, uint32_t d)
+{
+	return mol_key((int32_t)(key >> 56), (int32_t)((uint32_t)o.fingerprint ^ (d << (8 + 2 * i))), o.w, o.n);
+}
+
+// Collapse, the parent pass: one molecule per lane.  The three neighbours of a position probe side by side -- their first loads are
+// independent, and most end there, at an empty slot.  Reads keys, counts and origins only; parent[slot] is the lane's own.
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_parent_kernel(const TdKeyTable t, const td_mol_origin* __restrict__ origin,
+                                                                  const uint32_t* __restrict__ occ, int64_t n_occ, uint32_t* __restrict__ parent)
+{
+	const int64_t q = (int64_t)blockIdx.x * KT_BLOCK + threadIdx.x;
+	if (q >= n_occ) return;
+	const uint32_t slot = occ[q];
+	const kt_u64 ku = t.keys[slot], cu = t.counts[slot];
+	const td_mol_origin o = origin[slot];
+	const int m = o.n > 0 ? mol_umi_bases(o.fingerprint) : 0;
+	uint32_t best = slot;
+	kt_u64 kb = ku, cb = cu;                          // the best so far: u itself, which every qualifying neighbour comes before
+	for (int i = 0; i < m; i++) {
+		kt_u64 kv[3], first[3];
+		uint32_t at[3];
+#pragma unroll
+		for (int d = 0; d < 3; d++) {
+			kv[d] = mol_neighbour_key(ku, o, i, (uint32_t)d + 1u);
+			at[d] = kt_hash(kv[d]) & t.slot_mask;
+			first[d] = t.keys[at[d]];
+		}
+#pragma unroll
+		for (int d = 0; d < 3; d++) {
+			if (first[d] == 0ull) continue;               // not in the table
+			const int32_t sv = first[d] == kv[d] ? (int32_t)at[d] : kt_probe_find(t, kv[d]);
+			if (sv < 0) continue;
+			const kt_u64 cv = t.counts[sv];
+			if (cv + 1ull >= 2ull * cu && mol_before(cv, kv[d], cb, kb)) { best = (uint32_t)sv; kb = kv[d]; cb = cv; }
+		}
+	}
+	parent[slot] = best;
+}
+
+// Collapse, the root pass: every molecule walks parent[] to its root -- each step is strictly earlier in the order of the slots'
+// own (count, key), so it ends -- and adds its count there; the longest walk is a wave maximum, then one atomic per wave.
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_root_kernel(const kt_u64* __restrict__ counts, const uint32_t* __restrict__ occ, int64_t n_occ,
+                                                                const uint32_t* __restrict__ parent, kt_u64* __restrict__ collapsed,
+                                                                kt_u64* __restrict__ tallies)
+{
+	const int lane = threadIdx.x & (TD_WAVE - 1);
+	const int64_t q = (int64_t)blockIdx.x * KT_BLOCK + threadIdx.x;
+	int steps = 0;
+	bool is_root = false;
+	if (q < n_occ) {
+		const uint32_t slot = occ[q];
+		uint32_t at = slot, up = parent[at];
+		while (up != at && (int64_t)steps < n_occ) { at = up; up = parent[at]; steps++; }   // (no walk is longer than the list)
+		is_root = at == slot;
+		atomicAdd(&collapsed[at], counts[slot]);
+	}
+	for (int w = 32; w >= 1; w >>= 1) { const int s2 = __shfl_xor(steps, w); steps = s2 > steps ? s2 : steps; }
+	const int n_roots = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_root));
+	if (lane == 0) {
+		if (n_roots) atomicAdd(&tallies[TDM_ROOTS], (kt_u64)n_roots);
+		if (steps) atomicMax(&tallies[TDM_CHAIN], (kt_u64)steps);
+	}
+}
+
+// Collapse: (key, value, origin) of the listed slots whose value is not 0 into dense arrays -- every molecule with its count
+// (td_mol_origins), or the roots with their collapsed counts
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_gather_kernel(const kt_u64* __restrict__ keys, const kt_u64* __restrict__ values,
+                                                                  const td_mol_origin* __restrict__ origin, const uint32_t* __restrict__ occ,
+                                                                  int64_t n_occ, td_census_entry* __restrict__ out, td_mol_origin* __restrict__ out_origin,
+                                                                  int64_t cap, kt_u64* __restrict__ cursor)
+{
+	const int lane = threadIdx.x & (TD_WAVE - 1);
+	const int64_t q = (int64_t)blockIdx.x * KT_BLOCK + threadIdx.x;
+	uint32_t slot = 0u;
+	kt_u64 v = 0ull;
+	if (q < n_occ) { slot = occ[q]; v = values[slot]; }
+	const kt_u64 hit = __builtin_amdgcn_ballot_w64(v != 0ull);
+	if (hit == 0ull) return;
+	kt_u64 base = 0ull;
+	if (lane == __builtin_ctzll(hit)) base = atomicAdd(cursor, (kt_u64)__builtin_popcountll(hit));
+	base = kt_readlane64(base, __builtin_ctzll(hit));
+	const int64_t at = (int64_t)base + __builtin_popcountll(hit & ((1ull << lane) - 1ull));
+	if (v != 0ull && at < cap) { out[at].key = keys[slot]; out[at].count = (int64_t)v; out_origin[at] = origin[slot]; }
+}
+
 // The table into one row per barcode bin.  Nearly all slots of a run fall into a handful of bins: a global atomic per slot would
 // queue on three or four addresses ("The counters"), so a workgroup sums in LDS -- 256 bins x 12 words of 8
 // bytes, 24 KB -- and adds what is not zero to the global rows once.
@@ -191,7 +338,7 @@ bool prefix_ok(int32_t p) { return p >= 1 && p <= TD_MOL_MAX_PREFIX; }
 // a counted read
 enum { MOL_NOT_ELIGIBLE = 0, MOL_EMPTY, MOL_HAS_N, MOL_COUNTED };
 int host_read_class(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t i,
-                    const td_read_result* res, const int8_t* labels, uint64_t* key)
+                    const td_read_result* res, const int8_t* labels, uint64_t* key, td_mol_origin* origin = nullptr)
 {
 	if (((uint32_t)res[i].read_type & 0xFFu) != (uint32_t)TD_EXTRACT_SUCCESS) return MOL_NOT_ELIGIBLE;
 	const int64_t len = offs[i + 1] - offs[i];
@@ -212,6 +359,7 @@ int host_read_class(const td_model_desc* m, int32_t prefix_bases, const uint8_t*
 	if (cnt == 0) return MOL_EMPTY;
 	if (has_n) return MOL_HAS_N;
 	*key = mol_key(res[i].barcode, res[i].fingerprint, w, cnt);
+	if (origin) *origin = td_mol_origin{ w, res[i].fingerprint, cnt };
 	return MOL_COUNTED;
 }
 
@@ -234,12 +382,25 @@ static void dedup_release(TdMolState& z)
 	z.dedup = false;
 }
 
+// the collapse's origins, events and work arrays freed (nothing of it is queued any more)
+static void collapse_release(TdMolState& z)
+{
+	void* p[] = { z.d_origin, z.d_occ, z.d_parent, z.d_collapsed };
+	for (void* q : p) if (q) (void)hipFree(q);
+	hipEvent_t ev[] = { z.ev_o0, z.ev_o1 };
+	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+	z.d_origin = nullptr; z.d_occ = nullptr; z.d_parent = nullptr; z.d_collapsed = nullptr; z.cap_occ = 0;
+	z.ev_o0 = z.ev_o1 = nullptr;
+	z.collapse = false;
+}
+
 void mol_release(td_ctx* c)
 {
 	TdMolState& z = c->molecules;
 	kt_table_release(z.table);
 	if (z.d_rows) (void)hipFree(z.d_rows);
 	dedup_release(z);
+	collapse_release(z);
 	z = TdMolState();
 }
 
@@ -259,6 +420,22 @@ int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t*
 {
 	TdMolArgs a = mol_args(c->molecules, s, out_type, out_barcode, out_finger, labels);
 	return kt_count_slot(c, c->molecules.table, s, (const void*)td_mol_count_kernel, &a);
+}
+
+int mol_origin_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
+{
+	TdMolState& z = c->molecules;
+	TdMolArgs a = mol_args(z, s, out_type, out_barcode, out_finger, labels);
+	a.origin = z.d_origin;
+	HIPCHK(c, hipEventRecord(z.ev_o0, s.cs));
+	if (s.n_tiles > 0) {
+		hipLaunchKernelGGL(td_mol_origin_kernel, dim3((unsigned)((a.n_tiles + KT_WAVES - 1) / KT_WAVES)), dim3(KT_BLOCK), 0, s.cs, a);
+		HIPCHK(c, hipGetLastError());
+	}
+	HIPCHK(c, hipEventRecord(z.ev_o1, s.cs));
+	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));       // the slot is not restaged under this pass
+	s.hits_queued = true;
+	return TD_OK;
 }
 
 int mol_dedup_slot(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
@@ -338,6 +515,7 @@ extern "C" int td_mol_reset(td_ctx* c)
 	HIPCHK(c, sync_compute(c));   // (counts of pipelined batches may still be queued, on either compute stream)
 	HIPCHK(c, kt_table_zero(z.table, c->stream));   // (dedup's three tallies among them)
 	if (z.dedup) HIPCHK(c, hipMemsetAsync(z.d_first, 0xFF, sizeof(kt_u64) << z.table.log2_slots, c->stream));
+	if (z.collapse) HIPCHK(c, hipMemsetAsync(z.d_origin, 0, sizeof(td_mol_origin) << z.table.log2_slots, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	z.next_ordinal = 0;
 	z.p1_queued[0] = z.p1_queued[1] = false;          // (nothing is queued any more)
@@ -426,6 +604,321 @@ extern "C" int td_mol_get(td_ctx* c, td_mol_row rows[TD_NUM_BARCODE_BINS], td_mo
 		HIPCHK(c, hipMemcpy(t, z.table.d_tallies, sizeof t, hipMemcpyDeviceToHost));
 		totals_from(t, totals);
 	}
+	return TD_OK;
+}
+
+// ---- collapse ----
+extern "C" int td_mol_collapse_enable(td_ctx* c)
+{
+	if (!c) return fail(nullptr, "td_mol_collapse_enable: no context");
+	TdMolState& z = c->molecules;
+	if (!z.on) return fail(c, "td_mol_collapse_enable: the molecule count is off (td_mol_enable first): the collapse reads the count's table");
+	const td_model_desc& m = c->model.d;
+	bool has_f = false;
+	for (int j = 0; j < m.S; j++) has_f = has_f || m.seg_type[j] == 'F';
+	if (!has_f) return fail(c, "td_mol_collapse_enable: the model has no 'F' segment: there is no UMI whose neighbours could be collapsed");
+	for (int k = 0; k < TD_MAX_PIPELINE; k++)
+		if (c->slots[k].ticket) return fail(c, "td_mol_collapse_enable: td_submit tickets are outstanding (td_wait them first)");
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	if (!z.collapse) {
+		bool ok = hipMalloc((void**)&z.d_origin, sizeof(td_mol_origin) << z.table.log2_slots) == hipSuccess &&
+		          hipEventCreate(&z.ev_o0) == hipSuccess && hipEventCreate(&z.ev_o1) == hipSuccess;
+		if (!ok) {
+			const std::string e = hipGetErrorString(hipGetLastError());
+			collapse_release(z);
+			return fail(c, "td_mol_collapse_enable: the origins of 2^%d slots could not be set up: %s", z.table.log2_slots, e.c_str());
+		}
+		z.collapse = true;
+	}
+	return td_mol_reset(c);   // an origin belongs to a key that entered the table with it: both start empty
+}
+
+extern "C" int td_mol_collapse_disable(td_ctx* c)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (!z.collapse && !z.d_origin && !z.ev_o0 && !z.ev_o1) return TD_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	collapse_release(z);
+	return TD_OK;
+}
+
+int mol_origin_last_kernel_us(td_ctx* c, int32_t* us)
+{
+	const TdMolState& z = c->molecules;
+	if (!z.collapse) return fail(c, "td_get_option: collapse_origin_kernel_us: the collapse is off");
+	return kt_last_kernel_us(c, z.ev_o0, z.ev_o1, us, "td_get_option: collapse_origin_kernel_us: no batch has left its origins yet");
+}
+
+namespace {
+
+unsigned blocks_for(int64_t n) { return (unsigned)((n + KT_BLOCK - 1) / KT_BLOCK); }
+
+// Waits for the context's work; tallies[TDM_TALLY_WORDS] down, and the occupied slots' indices in z.d_occ: *n_occ of them, held
+// against the count's own tally of distinct keys
+int collapse_occupied(td_ctx* c, const char* who, kt_u64* tallies, int64_t* n_occ)
+{
+	TdMolState& z = c->molecules;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	HIPCHK(c, hipMemcpy(tallies, z.table.d_tallies, sizeof(kt_u64) * TDM_TALLY_WORDS, hipMemcpyDeviceToHost));
+	const int64_t distinct = (int64_t)tallies[TDM_MOLECULES];
+	*n_occ = distinct;
+	if (distinct == 0) return TD_OK;
+	if (distinct > z.cap_occ) {
+		if (z.d_occ) (void)hipFree(z.d_occ);
+		z.d_occ = nullptr; z.cap_occ = 0;
+		HIPCHK(c, hipMalloc((void**)&z.d_occ, sizeof(uint32_t) * (size_t)distinct));
+		z.cap_occ = distinct;
+	}
+	const int64_t n_slots = (int64_t)1 << z.table.log2_slots;
+	kt_u64* cursor = z.table.d_tallies + TDM_GATHERED;
+	kt_u64 found = 0;
+	HIPCHK(c, hipMemsetAsync(cursor, 0, sizeof(kt_u64), c->stream));
+	hipLaunchKernelGGL(td_mol_occupied_kernel, dim3(std::min(blocks_for(n_slots), 2048u)), dim3(KT_BLOCK), 0, c->stream,
+	                   (const kt_u64*)z.table.d_keys, n_slots, z.d_occ, distinct, cursor);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipMemcpy(&found, cursor, sizeof found, hipMemcpyDeviceToHost));
+	if ((int64_t)found != distinct) return fail(c, "%s: the table holds %lld keys, its tally says %lld", who, (long long)found, (long long)distinct);
+	return TD_OK;
+}
+
+// The listed slots whose `values` word is not 0 as sorted entries with their origins: `expect` of them; *n = their number, the first
+// min(cap, *n) copied
+int collapse_gather(td_ctx* c, const char* who, const kt_u64* values, int64_t n_occ, int64_t expect, td_census_entry* entries,
+                    td_mol_origin* origins, int64_t cap, int64_t* n)
+{
+	TdMolState& z = c->molecules;
+	*n = expect;
+	if (expect == 0) return TD_OK;
+	std::vector<td_census_entry> v((size_t)expect);
+	std::vector<td_mol_origin> vo((size_t)expect);
+	td_census_entry* d_e = nullptr;
+	td_mol_origin* d_o = nullptr;
+	kt_u64* cursor = z.table.d_tallies + TDM_GATHERED;
+	kt_u64 found = 0;
+	hipError_t e = hipMalloc((void**)&d_e, sizeof(td_census_entry) * (size_t)expect);
+	if (e == hipSuccess) e = hipMalloc((void**)&d_o, sizeof(td_mol_origin) * (size_t)expect);
+	if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(kt_u64), c->stream);
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(td_mol_gather_kernel, dim3(blocks_for(n_occ)), dim3(KT_BLOCK), 0, c->stream, (const kt_u64*)z.table.d_keys, values,
+		                   (const td_mol_origin*)z.d_origin, (const uint32_t*)z.d_occ, n_occ, d_e, d_o, expect, cursor);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (e == hipSuccess) e = hipMemcpy(v.data(), d_e, sizeof(td_census_entry) * (size_t)expect, hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(vo.data(), d_o, sizeof(td_mol_origin) * (size_t)expect, hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(&found, cursor, sizeof found, hipMemcpyDeviceToHost);
+	if (d_e) (void)hipFree(d_e);
+	if (d_o) (void)hipFree(d_o);
+	if (e != hipSuccess) return fail(c, "%s: the gather failed: %s", who, hipGetErrorString(e));
+	if ((int64_t)found != expect) return fail(c, "%s: %lld entries were gathered, %lld expected", who, (long long)found, (long long)expect);
+	std::vector<int64_t> order((size_t)expect);
+	for (int64_t i = 0; i < expect; i++) order[(size_t)i] = i;
+	std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return kt_entry_before(v[(size_t)x], v[(size_t)y]); });
+	const int64_t take = std::min<int64_t>(cap, expect);
+	for (int64_t i = 0; i < take; i++) { entries[i] = v[(size_t)order[(size_t)i]]; origins[i] = vo[(size_t)order[(size_t)i]]; }
+	return TD_OK;
+}
+
+// The collapse on the device: z.d_occ, z.d_parent and z.d_collapsed of the table as it stands; the totals
+int collapse_run(td_ctx* c, const char* who, int64_t* n_occ, td_mol_collapse_totals* totals)
+{
+	TdMolState& z = c->molecules;
+	if (!z.collapse) return fail(c, "%s: the collapse is off (td_mol_collapse_enable)", who);
+	kt_u64 t[TDM_TALLY_WORDS];
+	if (collapse_occupied(c, who, t, n_occ) != TD_OK) return TD_FAIL;
+	const size_t n_slots = (size_t)1 << z.table.log2_slots;
+	if (!z.d_parent) HIPCHK(c, hipMalloc((void**)&z.d_parent, sizeof(uint32_t) * n_slots));
+	if (!z.d_collapsed) HIPCHK(c, hipMalloc((void**)&z.d_collapsed, sizeof(kt_u64) * n_slots));
+	HIPCHK(c, hipMemsetAsync(z.d_collapsed, 0, sizeof(kt_u64) * n_slots, c->stream));
+	HIPCHK(c, hipMemsetAsync(z.table.d_tallies + TDM_ROOTS, 0, sizeof(kt_u64) * 2, c->stream));   // (TDM_ROOTS, TDM_CHAIN)
+	static_assert(TDM_CHAIN == TDM_ROOTS + 1, "the two are zeroed together");
+	if (*n_occ > 0) {
+		hipLaunchKernelGGL(td_mol_parent_kernel, dim3(blocks_for(*n_occ)), dim3(KT_BLOCK), 0, c->stream, kt_table_view(z.table),
+		                   (const td_mol_origin*)z.d_origin, (const uint32_t*)z.d_occ, *n_occ, z.d_parent);
+		HIPCHK(c, hipGetLastError());
+		hipLaunchKernelGGL(td_mol_root_kernel, dim3(blocks_for(*n_occ)), dim3(KT_BLOCK), 0, c->stream, (const kt_u64*)z.table.d_counts,
+		                   (const uint32_t*)z.d_occ, *n_occ, (const uint32_t*)z.d_parent, z.d_collapsed, z.table.d_tallies);
+		HIPCHK(c, hipGetLastError());
+	}
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	kt_u64 rc[2];
+	HIPCHK(c, hipMemcpy(rc, z.table.d_tallies + TDM_ROOTS, sizeof rc, hipMemcpyDeviceToHost));
+	totals->molecules_before = *n_occ; totals->molecules_after = (int64_t)rc[0];
+	totals->absorbed = *n_occ - (int64_t)rc[0]; totals->longest_chain = (int64_t)rc[1];
+	return TD_OK;
+}
+
+// entries with repeated keys (any order) and their origins -> one entry per key, in the order of td_census_get
+void host_add_repeated(const td_census_entry* entries, const td_mol_origin* origins, int64_t n, std::vector<td_census_entry>& v,
+                       std::vector<td_mol_origin>& vo)
+{
+	std::vector<int64_t> order((size_t)n);
+	for (int64_t i = 0; i < n; i++) order[(size_t)i] = i;
+	std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return entries[x].key < entries[y].key; });
+	std::vector<td_census_entry> e;
+	std::vector<td_mol_origin> eo;
+	for (int64_t i : order) {
+		if (entries[i].count <= 0) continue;
+		if (!e.empty() && e.back().key == entries[i].key) e.back().count += entries[i].count;
+		else { e.push_back(entries[i]); eo.push_back(origins[i]); }
+	}
+	std::vector<size_t> by((size_t)e.size());
+	for (size_t i = 0; i < e.size(); i++) by[i] = i;
+	std::sort(by.begin(), by.end(), [&](size_t x, size_t y) { return kt_entry_before(e[x], e[y]); });
+	for (size_t i : by) { v.push_back(e[i]); vo.push_back(eo[i]); }
+}
+
+td_mol_origin* copy_origins(const std::vector<td_mol_origin>& v)
+{
+	td_mol_origin* p = (td_mol_origin*)malloc(sizeof(td_mol_origin) * (v.size() ? v.size() : 1));
+	if (p && !v.empty()) memcpy(p, v.data(), sizeof(td_mol_origin) * v.size());
+	return p;
+}
+
+}   // namespace
+
+extern "C" int td_mol_origins(td_ctx* c, td_census_entry* entries, td_mol_origin* origins, int64_t cap, int64_t* n, td_mol_totals* totals)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (!z.collapse) return fail(c, "td_mol_origins: the collapse is off (td_mol_collapse_enable)");
+	if (cap < 0 || (cap > 0 && (!entries || !origins)) || !n) return fail(c, "td_mol_origins: bad arguments");
+	*n = 0;
+	kt_u64 t[TDM_TALLY_WORDS];
+	int64_t n_occ = 0;
+	if (collapse_occupied(c, "td_mol_origins", t, &n_occ) != TD_OK) return TD_FAIL;
+	if (collapse_gather(c, "td_mol_origins", z.table.d_counts, n_occ, n_occ, entries, origins, cap, n) != TD_OK) return TD_FAIL;
+	if (totals) totals_from(t, totals);
+	return TD_OK;
+}
+
+extern "C" int td_mol_collapse_get(td_ctx* c, td_mol_row rows[TD_NUM_BARCODE_BINS], td_mol_collapse_totals* totals)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (!rows) return fail(c, "td_mol_collapse_get: bad arguments");
+	int64_t n_occ = 0;
+	td_mol_collapse_totals t{};
+	if (collapse_run(c, "td_mol_collapse_get", &n_occ, &t) != TD_OK) return TD_FAIL;
+	// the count's own sweep over the collapsed counts: a slot that is no root has 0 there and is skipped
+	const int64_t n_slots = (int64_t)1 << z.table.log2_slots;
+	HIPCHK(c, hipMemsetAsync(z.d_rows, 0, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, c->stream));
+	hipLaunchKernelGGL(td_mol_summary_kernel, dim3(std::min(blocks_for(n_slots), 1024u)), dim3(KT_BLOCK), 0, c->stream, (const kt_u64*)z.table.d_keys,
+	                   (const kt_u64*)z.d_collapsed, n_slots, z.d_rows);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipMemcpy(rows, z.d_rows, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, hipMemcpyDeviceToHost));
+	if (totals) *totals = t;
+	return TD_OK;
+}
+
+extern "C" int td_mol_collapse_entries(td_ctx* c, td_census_entry* entries, td_mol_origin* origins, int64_t cap, int64_t* n,
+                                       td_mol_collapse_totals* totals)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (cap < 0 || (cap > 0 && (!entries || !origins)) || !n) return fail(c, "td_mol_collapse_entries: bad arguments");
+	*n = 0;
+	int64_t n_occ = 0;
+	td_mol_collapse_totals t{};
+	if (collapse_run(c, "td_mol_collapse_entries", &n_occ, &t) != TD_OK) return TD_FAIL;
+	if (collapse_gather(c, "td_mol_collapse_entries", z.d_collapsed, n_occ, t.molecules_after, entries, origins, cap, n) != TD_OK) return TD_FAIL;
+	if (totals) *totals = t;
+	return TD_OK;
+}
+
+extern "C" int td_mol_collapse_host(const td_census_entry* entries, const td_mol_origin* origins, int64_t n, td_census_entry** out_entries,
+                                    td_mol_origin** out_origins, int64_t* out_n, td_mol_collapse_totals* totals)
+{
+	if (out_entries) *out_entries = nullptr;
+	if (out_origins) *out_origins = nullptr;
+	if (out_n) *out_n = 0;
+	if (!out_entries || !out_origins || !out_n || n < 0 || (n > 0 && (!entries || !origins))) return fail(nullptr, "td_mol_collapse_host: bad arguments");
+	std::vector<td_census_entry> v;
+	std::vector<td_mol_origin> vo;
+	host_add_repeated(entries, origins, n, v, vo);
+	const size_t N = v.size();
+	std::unordered_map<uint64_t, size_t> at;
+	for (size_t u = 0; u < N; u++) at[v[u].key] = u;
+	// v is in the order of td_census_get: "v comes before u" is "its index is smaller", and the first qualifying neighbour the smallest
+	std::vector<size_t> parent(N);
+	for (size_t u = 0; u < N; u++) {
+		parent[u] = u;
+		const int m = vo[u].n > 0 ? mol_umi_bases(vo[u].fingerprint) : 0;
+		for (int i = 0; i < m; i++)
+			for (uint32_t d = 1; d <= 3; d++) {
+				const auto f = at.find(mol_neighbour_key(v[u].key, vo[u], i, d));
+				if (f == at.end()) continue;
+				const size_t q = f->second;
+				if (v[q].count >= 2 * v[u].count - 1 && q < parent[u]) parent[u] = q;
+			}
+	}
+	// a parent has a smaller index: roots and depths in one pass from the front
+	std::vector<size_t> root(N);
+	std::vector<int64_t> depth(N), collapsed(N, 0);
+	td_mol_collapse_totals t{};
+	for (size_t u = 0; u < N; u++) {
+		root[u] = parent[u] == u ? u : root[parent[u]];
+		depth[u] = parent[u] == u ? 0 : depth[parent[u]] + 1;
+		collapsed[root[u]] += v[u].count;
+		t.longest_chain = std::max(t.longest_chain, depth[u]);
+	}
+	std::vector<size_t> roots;
+	for (size_t u = 0; u < N; u++) if (root[u] == u) roots.push_back(u);
+	std::vector<td_census_entry> r;
+	for (size_t u : roots) r.push_back(td_census_entry{ v[u].key, collapsed[u] });
+	std::vector<size_t> by(r.size());
+	for (size_t i = 0; i < by.size(); i++) by[i] = i;
+	std::sort(by.begin(), by.end(), [&](size_t x, size_t y) { return kt_entry_before(r[x], r[y]); });
+	std::vector<td_census_entry> re;
+	std::vector<td_mol_origin> ro;
+	for (size_t i : by) { re.push_back(r[i]); ro.push_back(vo[roots[i]]); }
+	t.molecules_before = (int64_t)N; t.molecules_after = (int64_t)re.size(); t.absorbed = t.molecules_before - t.molecules_after;
+	td_census_entry* pe = kt_copy_entries(re);
+	td_mol_origin* po = copy_origins(ro);
+	if (!pe || !po) { free(pe); free(po); return fail(nullptr, "td_mol_collapse_host: out of memory"); }
+	*out_entries = pe; *out_origins = po; *out_n = (int64_t)re.size();
+	if (totals) *totals = t;
+	return TD_OK;
+}
+
+extern "C" int td_mol_host_origins(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                                   const td_read_result* res, const int8_t* labels, td_census_entry** entries, td_mol_origin** origins, int64_t* n,
+                                   td_mol_totals* totals)
+{
+	if (entries) *entries = nullptr;
+	if (origins) *origins = nullptr;
+	if (n) *n = 0;
+	if (!m || m->S < 1 || m->H < 1 || !m->seg_type || !m->label) return fail(nullptr, "td_mol_host_origins: no model");
+	if (!prefix_ok(prefix_bases)) return fail(nullptr, "td_mol_host_origins: prefix_bases = %d (1..%d supported)", prefix_bases, TD_MOL_MAX_PREFIX);
+	if (!entries || !origins || !n || n_reads < 0 || (n_reads > 0 && (!offs || !res || !labels || !codes))) return fail(nullptr, "td_mol_host_origins: bad arguments");
+	td_mol_totals t{};
+	std::vector<td_census_entry> each;                // one entry of count 1 per counted read
+	std::vector<td_mol_origin> each_o;
+	for (int64_t i = 0; i < n_reads; i++) {
+		uint64_t key = 0;
+		td_mol_origin o{};
+		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key, &o);
+		if (cls == MOL_NOT_ELIGIBLE) continue;
+		t.eligible++;
+		if (cls == MOL_EMPTY) t.skipped_empty++;
+		else if (cls == MOL_HAS_N) t.skipped_n++;
+		else { each.push_back(td_census_entry{ key, 1 }); each_o.push_back(o); t.counted++; }
+	}
+	std::vector<td_census_entry> v;
+	std::vector<td_mol_origin> vo;
+	host_add_repeated(each.data(), each_o.data(), (int64_t)each.size(), v, vo);
+	t.molecules = (int64_t)v.size();
+	td_census_entry* pe = kt_copy_entries(v);
+	td_mol_origin* po = copy_origins(vo);
+	if (!pe || !po) { free(pe); free(po); return fail(nullptr, "td_mol_host_origins: out of memory"); }
+	*entries = pe; *origins = po; *n = (int64_t)v.size();
+	if (totals) *totals = t;
 	return TD_OK;
 }
 

@@ -100,6 +100,7 @@ bool parse_arch(const std::vector<std::string>& segs, ArchPtr& out, std::string&
 }
 
 bool is_read_only(const td_arch* a) { return a->n_segments == 1 && a->type[0] == 'R'; }
+bool has_fingerprint(const td_arch* a) { for (int j = 0; j < a->n_segments; j++) if (a->type[j] == 'F') return true; return false; }
 bool has_barcode(const td_arch* a) { for (int j = 0; j < a->n_segments; j++) if (a->type[j] == 'B') return true; return false; }
 int read_segments(const td_arch* a) { int n = 0; for (int j = 0; j < a->n_segments; j++) n += a->type[j] == 'R'; return n; }
 
@@ -168,7 +169,7 @@ bool read_arch_file(const char* path, ArchFile& af, std::string& why)
 struct OptSpec { const char* name; int arg; int id; };
 enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
-       O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS, O_DEDUP,
+       O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS, O_DEDUP, O_COLLAPSE,
        O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
@@ -194,7 +195,7 @@ const OptSpec kOwnOpts[] = {
 	{ "sync-compile", 0, O_SYNC_COMPILE }, { "stats-on-host", 0, O_STATS_ON_HOST }, { "force", 0, O_FORCE }, { "dry-run", 0, O_DRY_RUN },
 	{ "unknown-barcodes", 1, O_UNKNOWN }, { "unknown-barcodes-slots", 1, O_UNKNOWN_SLOTS },
 	{ "fingerprint-seq", 0, O_FINGER_SEQ }, { "molecules", 0, O_MOLECULES }, { "molecules-prefix", 1, O_MOLECULES_PREFIX },
-	{ "molecules-slots", 1, O_MOLECULES_SLOTS }, { "dedup", 0, O_DEDUP },
+	{ "molecules-slots", 1, O_MOLECULES_SLOTS }, { "dedup", 0, O_DEDUP }, { "collapse-umis", 0, O_COLLAPSE },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -290,7 +291,10 @@ extern "C" const char* td_run_usage(void)
 	       "\t--molecules-prefix P        bases of the read that belong to a molecule's identity, 1..32 [20]\n"
 	       "\t--molecules-slots N         slots of the counting table on every device, as a power of two, 4..30 [26]\n"
 	       "\t--dedup                     write one read per molecule: an extracted read that is not the first of its molecule in\n"
-	       "\t                            the input goes to no output file (implies --molecules; one input file, one device)\n\n";
+	       "\t                            the input goes to no output file (implies --molecules; one input file, one device)\n"
+	       "\t--collapse-umis             count fingerprints one mismatch apart as one molecule where the counts say the rarer one is\n"
+	       "\t                            a misread of the other: two more columns in <output prefix>_molecules.txt (implies\n"
+	       "\t                            --molecules; needs an F segment; --dedup still matches exactly)\n\n";
 }
 
 extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
@@ -361,10 +365,12 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 		case O_MOLECULES_PREFIX: o->molecules_prefix = atoi(v); break;
 		case O_MOLECULES_SLOTS: o->molecules_slots_log2 = atoi(v); break;
 		case O_DEDUP: o->dedup = 1; break;
+		case O_COLLAPSE: o->collapse_umis = 1; break;
 		default: return bad("unknown option " + a);
 		}
 	}
 	if (o->dedup) o->molecules = 1;   // the duplicates are those of the molecule count
+	if (o->collapse_umis) o->molecules = 1;   // ... and so are the molecules that are collapsed
 	if (o->num_threads < 1) return bad("option -t: need at least one thread");
 	if (o->host_threads < 0 || o->batch_reads < 0) return bad("--host-threads / --batch-reads: negative value");
 	if (o->unknown_slots_log2 < 4 || o->unknown_slots_log2 > 26) return bad("--unknown-barcodes-slots: need 4..26 (the table has 2^N slots)");
@@ -393,6 +399,7 @@ struct td_run_plan_t {
 	int dust = 0;
 	bool use_ref = false;
 	bool dedup = false;
+	bool collapse = false;
 };
 
 namespace {
@@ -429,6 +436,8 @@ int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& arch
 	}
 	if (o->molecules) {
 		if (archs.size() == 1 && is_read_only(archs[0])) return run_fail("--molecules: the architecture is a single read segment: there is no model whose labels mark a barcode or a fingerprint.");
+		if (o->collapse_umis && !has_fingerprint(archs[0]))
+			return run_fail("--collapse-umis: the architecture has no fingerprint (F) segment: there is no UMI whose neighbours could be collapsed.");
 		names.push_back(molecules_file_name(o));
 	}
 	if (bar_file >= 0 && !o->force)   // check_for_existing_demultiplexed_files_multiple, io.c:633-691 (made for the barcode file only)
@@ -464,6 +473,7 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	if (o->dedup && o->n_devices > 1)
 		return run_fail("--dedup needs exactly one device (%d given): each device has its own table, and a molecule split over two devices would survive twice.", o->n_devices);
 	p->dedup = o->dedup != 0;
+	p->collapse = o->collapse_umis != 0;
 	for (int k = 0; k < o->n_infiles; k++)
 		if (strcmp(o->infile[k], "-") != 0 && !file_exists(o->infile[k])) return run_fail("ERROR: Input file:%s does not exists.", o->infile[k]);
 	// interface.c:419-450: two or more R segments in the command line's architecture switch DUST and -ref off
@@ -522,6 +532,7 @@ extern "C" int64_t td_run_plan_describe(const td_run_plan_t* p, char* buf, int64
 	s += "dust: " + std::to_string(p->dust) + "\n";
 	s += std::string("ref: ") + (p->use_ref ? "on" : "off") + "\n";
 	if (p->dedup) s += "dedup: one read per molecule is written (barcode, fingerprint and the start of the read)\n";
+	if (p->collapse) s += "collapse: fingerprints one mismatch apart are counted as one molecule (directional rule; the count and --dedup stay exact)\n";
 	if (p->all_known) {
 		s += "barcode file: " + (p->bar_file >= 0 ? std::to_string(p->bar_file) : std::string("none")) + "\n";
 		s += "output reads: " + std::to_string(p->num_out_reads) + "\n";
@@ -650,6 +661,7 @@ extern "C" void td_run_report_clear(td_run_report* r)
 	free(r->artifact_names); free(r->artifact_hits); free(r->log);
 	td_census_free(r->unknown);
 	free(r->molecules);
+	free(r->molecules_collapsed);
 	for (int k = 0; k < TD_RUN_MAX_FILES; k++) free(r->architectures[k]);
 	memset(r, 0, sizeof *r);
 }
@@ -924,6 +936,8 @@ int Run::execute()
 			if (o->molecules && td_mol_enable(c, o->molecules_prefix, o->molecules_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
 			// --dedup: ... and mark every read that is not the first of its molecule; the writer leaves those out
 			if (o->dedup && td_mol_dedup_enable(c) != TD_OK) return fail("%s", td_last_error(c));
+			// --collapse-umis: ... and keep what every key was made of, for the collapse behind the run
+			if (o->collapse_umis && td_mol_collapse_enable(c) != TD_OK) return fail("%s", td_last_error(c));
 		}
 	}
 	rep->compile_wait_s = now_s() - t0;
@@ -1035,6 +1049,36 @@ int Run::molecules()
 		if (rc != TD_OK) return fail("%s", td_last_error(nullptr));
 	}
 	rep->molecules_totals = sum;
+	// --collapse-umis: one device's own collapse, or every device's molecules with their origins collapsed on the host
+	td_mol_row* crows = nullptr;
+	if (o->collapse_umis) {
+		crows = (td_mol_row*)calloc(TD_NUM_BARCODE_BINS, sizeof(td_mol_row));
+		if (!crows) return fail("--collapse-umis: out of memory");
+		rep->molecules_collapsed = crows;
+		if (f.raw.size() == 1) {
+			if (td_mol_collapse_get(f.raw[0], crows, &rep->collapse_totals) != TD_OK) return fail("%s", td_last_error(f.raw[0]));
+		} else {
+			std::vector<td_census_entry> all;
+			std::vector<td_mol_origin> all_o;
+			for (td_ctx* c : f.raw) {
+				int64_t n = 0;
+				if (td_mol_origins(c, nullptr, nullptr, 0, &n, nullptr) != TD_OK) return fail("%s", td_last_error(c));
+				const size_t at = all.size();
+				all.resize(at + (size_t)n); all_o.resize(at + (size_t)n);
+				if (n > 0 && td_mol_origins(c, all.data() + at, all_o.data() + at, n, &n, nullptr) != TD_OK) return fail("%s", td_last_error(c));
+			}
+			td_census_entry* roots = nullptr;
+			td_mol_origin* roots_o = nullptr;
+			int64_t n_roots = 0;
+			if (td_mol_collapse_host(all.data(), all_o.data(), (int64_t)all.size(), &roots, &roots_o, &n_roots, &rep->collapse_totals) != TD_OK)
+				return fail("%s", td_last_error(nullptr));
+			const int rc = td_mol_summarise(roots, n_roots, crows);
+			td_census_free(roots);
+			free(roots_o);
+			if (rc != TD_OK) return fail("%s", td_last_error(nullptr));
+		}
+		rep->collapse = 1;
+	}
 	if (o->dedup) {   // (one device: td_run_plan saw to it)
 		if (td_mol_dedup_get(f.raw[0], &rep->dedup_totals) != TD_OK) return fail("%s", td_last_error(f.raw[0]));
 		rep->dedup = 1;
@@ -1055,25 +1099,32 @@ int Run::molecules()
 		        (long long)sum.overflow, o->molecules_slots_log2 + 1);
 	if (o->dedup)
 		fprintf(out, "# written\t%lld\n# duplicates removed\t%lld\n", (long long)rep->dedup_totals.kept, (long long)rep->dedup_totals.duplicates);
-	fprintf(out, "# barcode\treads\tmolecules\tduplication\t1\t2\t3\t4\t5\t6\t7\t8\t9\t10+\n");
-	auto line = [&](const char* label, const td_mol_row& r) {
+	if (crows)
+		fprintf(out, "# UMI collapse\tfingerprints one mismatch apart, directional rule\n# molecules after collapse\t%lld\n# absorbed\t%lld\n",
+		        (long long)rep->collapse_totals.molecules_after, (long long)rep->collapse_totals.absorbed);
+	fprintf(out, "# barcode\treads\tmolecules\tduplication\t1\t2\t3\t4\t5\t6\t7\t8\t9\t10+%s\n", crows ? "\tcollapsed\tduplication_collapsed" : "");
+	// (collapsed: the molecules of the row after the collapse, with --collapse-umis)
+	auto line = [&](const char* label, const td_mol_row& r, int64_t collapsed) {
 		fprintf(out, "%s\t%lld\t%lld\t%0.4f", label, (long long)r.reads, (long long)r.molecules,
 		        r.reads > 0 ? 1.0 - (double)r.molecules / (double)r.reads : 0.0);
 		for (int q = 0; q < TD_MOL_LEVELS; q++) fprintf(out, "\t%lld", (long long)r.levels[q]);
+		if (crows) fprintf(out, "\t%lld\t%0.4f", (long long)collapsed, r.reads > 0 ? 1.0 - (double)collapsed / (double)r.reads : 0.0);
 		fprintf(out, "\n");
 	};
 	if (seg >= 0) {
 		const int n_listed = std::min(a->n_seq[seg] - 1, (int)TD_NUM_BARCODE_BINS);   // (the last one is the all-N wildcard)
-		for (int q = 0; q < n_listed; q++) line(a->seqs[seg][q], rows[q]);
+		for (int q = 0; q < n_listed; q++) line(a->seqs[seg][q], rows[q], crows ? crows[q].molecules : 0);
 	} else {
-		line("-", rows[0]);
+		line("-", rows[0], crows ? crows[0].molecules : 0);
 	}
 	td_mol_row total{};
+	int64_t total_collapsed = 0;
 	for (int b = 0; b < TD_NUM_BARCODE_BINS; b++) {
 		total.reads += rows[b].reads; total.molecules += rows[b].molecules;
 		for (int q = 0; q < TD_MOL_LEVELS; q++) total.levels[q] += rows[b].levels[q];
+		if (crows) total_collapsed += crows[b].molecules;
 	}
-	line("total", total);
+	line("total", total, total_collapsed);
 	fclose(out);
 	return TD_OK;
 }

@@ -53,9 +53,13 @@ CENSUS_MAX_WORD = 28
 
 # include/tagdust_molecules.h: molecules per barcode
 MOL_ABI_SYMBOLS = ["td_mol_enable", "td_mol_disable", "td_mol_reset", "td_mol_entries", "td_mol_get", "td_mol_summarise", "td_mol_host",
-                   "td_mol_key", "td_mol_key_bin", "td_mol_dedup_enable", "td_mol_dedup_disable", "td_mol_dedup_get", "td_mol_dedup_host"]
+                   "td_mol_key", "td_mol_key_bin", "td_mol_dedup_enable", "td_mol_dedup_disable", "td_mol_dedup_get", "td_mol_dedup_host",
+                   "td_mol_collapse_enable", "td_mol_collapse_disable", "td_mol_origins", "td_mol_collapse_get", "td_mol_collapse_entries",
+                   "td_mol_host_origins", "td_mol_collapse_host"]
 MOL_TOTALS = ("eligible", "counted", "skipped_empty", "skipped_n", "overflow", "molecules")
 MOL_DEDUP_TOTALS = ("kept", "duplicates", "unjudged")
+MOL_COLLAPSE_TOTALS = ("molecules_before", "molecules_after", "absorbed", "longest_chain")
+MOL_ORIGIN_DTYPE = np.dtype([("w", "<u8"), ("fingerprint", "<i4"), ("n", "<i4")])   # td_mol_origin
 EXTRACT_DUPLICATE = 7    # TD_EXTRACT_DUPLICATE (include/tagdust_hip.h): not an outcome of the reference
 MOL_LEVELS = 10
 MOL_ROW_DTYPE = np.dtype([("reads", "<i8"), ("molecules", "<i8"), ("levels", "<i8", (MOL_LEVELS,))])
@@ -598,7 +602,7 @@ class _RunOpts(C.Structure):
                 ("force", C.c_int32), ("dry_run", C.c_int32), ("help", C.c_int32), ("version", C.c_int32), ("echo_log", C.c_int32),
                 ("argc", C.c_int32), ("argv", C.POINTER(C.c_char_p)), ("unknown_barcodes", C.c_int32), ("unknown_slots_log2", C.c_int32),
                 ("fingerprint_seq", C.c_int32), ("molecules", C.c_int32), ("molecules_prefix", C.c_int32), ("molecules_slots_log2", C.c_int32),
-                ("dedup", C.c_int32)]
+                ("dedup", C.c_int32), ("collapse_umis", C.c_int32)]
 
 
 class _CensusTotals(C.Structure):
@@ -625,6 +629,14 @@ class _MolDedupTotals(C.Structure):
         return {f: int(getattr(self, f)) for f in MOL_DEDUP_TOTALS}
 
 
+class _MolCollapseTotals(C.Structure):
+    """td_mol_collapse_totals (include/tagdust_molecules.h)"""
+    _fields_ = [(f, C.c_int64) for f in MOL_COLLAPSE_TOTALS]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f in MOL_COLLAPSE_TOTALS}
+
+
 class _RunReport(C.Structure):
     """td_run_report (include/tagdust_run.h)"""
     _fields_ = [("error", C.c_char * 1024), ("counts", C.c_int64 * NUM_COUNTERS), ("n_artifacts", C.c_int32),
@@ -633,7 +645,8 @@ class _RunReport(C.Structure):
                 ("stream", _StreamStats), ("arch_s", C.c_double), ("stats_s", C.c_double), ("calibration_s", C.c_double),
                 ("compile_wait_s", C.c_double), ("stream_s", C.c_double), ("stats_on_device", C.c_int32), ("log", C.c_char_p),
                 ("n_unknown", C.c_int64), ("unknown", C.c_void_p), ("unknown_totals", _CensusTotals),
-                ("molecules", C.c_void_p), ("molecules_totals", _MolTotals), ("dedup", C.c_int32), ("dedup_totals", _MolDedupTotals)]
+                ("molecules", C.c_void_p), ("molecules_totals", _MolTotals), ("dedup", C.c_int32), ("dedup_totals", _MolDedupTotals),
+                ("collapse", C.c_int32), ("collapse_totals", _MolCollapseTotals), ("molecules_collapsed", C.c_void_p)]
 
 
 def _run_lib():
@@ -745,6 +758,8 @@ def run_execute(args):
             "unknown": _census_entries(rep.unknown, int(rep.n_unknown)), "unknown_totals": rep.unknown_totals.as_dict(),
             "molecules": _mol_rows(rep.molecules) if rep.molecules else None, "molecules_totals": rep.molecules_totals.as_dict(),
             "dedup_totals": rep.dedup_totals.as_dict() if rep.dedup else None,
+            "collapse_totals": rep.collapse_totals.as_dict() if rep.collapse else None,
+            "molecules_collapsed": _mol_rows(rep.molecules_collapsed) if rep.molecules_collapsed else None,
         }
     finally:
         o.lib.td_run_report_clear(C.byref(rep))
@@ -854,7 +869,69 @@ def _mol_lib():
     lib.td_mol_dedup_get.argtypes = [C.c_void_p, C.POINTER(_MolDedupTotals)]
     lib.td_mol_dedup_host.argtypes = [C.POINTER(_ModelDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.POINTER(_MolDedupTotals)]
+    lib.td_mol_collapse_enable.argtypes = [C.c_void_p]
+    lib.td_mol_collapse_disable.argtypes = [C.c_void_p]
+    lib.td_mol_origins.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_MolTotals)]
+    lib.td_mol_collapse_get.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_MolCollapseTotals)]
+    lib.td_mol_collapse_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_MolCollapseTotals)]
+    lib.td_mol_host_origins.argtypes = [C.POINTER(_ModelDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(_MolTotals)]
+    lib.td_mol_collapse_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_int64), C.POINTER(_MolCollapseTotals)]
+    lib.free.argtypes = [C.c_void_p]
+    lib.free.restype = None
     return lib
+
+
+def _mol_origin_array(ptr, n):
+    """n td_mol_origin at ptr, copied"""
+    out = np.zeros(n, MOL_ORIGIN_DTYPE)
+    if n:
+        C.memmove(out.ctypes.data, ptr, n * MOL_ORIGIN_DTYPE.itemsize)
+    return out
+
+
+def mol_host_origins(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_host_origins: mol_host plus what every key was made of.  Returns (entries, origins MOL_ORIGIN_DTYPE, totals dict)."""
+    lib = _mol_lib()
+    desc, keep = make_model_desc(md)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if len(seq) == 0:
+        seq = np.zeros(1, np.uint8)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
+    for f in ("read_type", "barcode", "fingerprint"):
+        rr[f] = np.asarray(res[f])
+    ptr, optr, n, tot = C.c_void_p(), C.c_void_p(), C.c_int64(), _MolTotals()
+    rc = lib.td_mol_host_origins(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
+                                 labels.ctypes.data, C.byref(ptr), C.byref(optr), C.byref(n), C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    try:
+        return _census_entries(ptr, n.value), _mol_origin_array(optr, n.value), tot.as_dict()
+    finally:
+        lib.td_census_free(ptr)
+        lib.free(optr)
+
+
+def mol_collapse_host(entries, origins):
+    """td_mol_collapse_host: the collapse of (key, count) entries with their origins, repeated keys added first (no GPU).  Returns
+    (the roots with their collapsed counts, their origins, totals dict)."""
+    lib = _mol_lib()
+    e = np.ascontiguousarray(entries, CENSUS_ENTRY_DTYPE)
+    o = np.ascontiguousarray(origins, MOL_ORIGIN_DTYPE)
+    if len(e) != len(o):
+        raise ValueError("entries and origins differ in length")
+    ptr, optr, n, tot = C.c_void_p(), C.c_void_p(), C.c_int64(), _MolCollapseTotals()
+    if lib.td_mol_collapse_host(e.ctypes.data, o.ctypes.data, len(e), C.byref(ptr), C.byref(optr), C.byref(n), C.byref(tot)) != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    try:
+        return _census_entries(ptr, n.value), _mol_origin_array(optr, n.value), tot.as_dict()
+    finally:
+        lib.td_census_free(ptr)
+        lib.free(optr)
 
 
 def mol_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
@@ -1158,6 +1235,37 @@ class TagdustHip:
         tot = _MolDedupTotals()
         self._chk(_mol_lib().td_mol_dedup_get(self.h, C.byref(tot)))
         return tot.as_dict()
+
+    def mol_collapse_enable(self):
+        """td_mol_collapse_enable: from now on the table keeps what every key was made of"""
+        self._chk(_mol_lib().td_mol_collapse_enable(self.h))
+
+    def mol_collapse_disable(self):
+        self._chk(_mol_lib().td_mol_collapse_disable(self.h))
+
+    def _mol_with_origins(self, call, totals, cap):
+        n = C.c_int64()
+        if cap is None:
+            self._chk(call(self.h, None, None, 0, C.byref(n), C.byref(totals)))
+            cap = n.value
+        e, o = np.zeros(max(int(cap), 1), CENSUS_ENTRY_DTYPE), np.zeros(max(int(cap), 1), MOL_ORIGIN_DTYPE)
+        self._chk(call(self.h, e.ctypes.data, o.ctypes.data, int(cap), C.byref(n), C.byref(totals)))
+        k = min(int(cap), n.value)
+        return e[:k], o[:k], totals.as_dict()
+
+    def mol_origins(self, cap=None):
+        """td_mol_origins: (entries as mol_entries gives them, their origins MOL_ORIGIN_DTYPE, totals dict)"""
+        return self._mol_with_origins(_mol_lib().td_mol_origins, _MolTotals(), cap)
+
+    def mol_collapse_entries(self, cap=None):
+        """td_mol_collapse_entries: (the roots with their collapsed counts, their origins, collapse totals dict)"""
+        return self._mol_with_origins(_mol_lib().td_mol_collapse_entries, _MolCollapseTotals(), cap)
+
+    def mol_collapse_get(self):
+        """td_mol_collapse_get: (the summary from the collapsed counts, MOL_ROW_DTYPE[256], collapse totals dict)"""
+        rows, tot = np.zeros(NUM_BARCODE_BINS, MOL_ROW_DTYPE), _MolCollapseTotals()
+        self._chk(_mol_lib().td_mol_collapse_get(self.h, rows.ctypes.data, C.byref(tot)))
+        return rows, tot.as_dict()
 
     def mol_entries(self, cap=None):
         """td_mol_entries: (the (key, count) pairs by count descending then key ascending -- at most cap of them --, totals dict)"""

@@ -28,6 +28,24 @@ and two N-mask words (20 B) -- 73 B streamed -- and the table: a load of the key
 count, three touches of 8 B that each move a 64-byte sector or more at a random address, 200-400 B.  Under 0.5 KB against the
 56 KB a read costs the decode kernel: about one percent of the decode kernel's time, and no visible change host to host, where
 the count runs behind the decode kernel on its stream while the copies of the neighbouring batches are under way.
+
+The UMI collapse (td_mol_collapse_enable) has a mode of its own, --collapse, which adds a "collapse" section to the same file and
+measures nothing else:
+
+    python tools/molecules_bench.py --collapse
+
+The same workload with 0.5 % substitutions per UMI base on top, so that there is something to collapse.  Per batch: the origin
+pass from HIP events (option "collapse_origin_kernel_us") beside the count kernel and the decode kernel of the same batch, median
+of 5 batches with the table reset before each.  End of run: td_mol_collapse_get from the call to the rows on the host, the first
+call (it allocates the parent and collapsed arrays) and the second.  Host to host: td_submit / td_wait with the collapse on and
+with the count alone in turn in one process, two passes of each after a first pass of the process that is discarded (the first
+pass pays for the first touches of every buffer).  The yardstick is the count alone in the same process.  Expectation, written
+down before the first run: the origin pass is dedup's pass 1 with a 16-byte store for a key's first read in place of the atomic
+minimum -- a walk, a probe, at most one store --, so it should cost about what dedup's pass 1 costs, which is about what the count
+kernel costs; the collapse touches 3 * m + 2 = 26 random words per molecule for an 8-nt UMI (24 probes that mostly end at an empty
+or a foreign slot, the parent's count, the root's add) besides two sweeps over the table's keys, so at the 60-100 ns a random
+touch of a quarter-full 64 MiB table costs a lane and some ten thousand lanes in flight, 2.8 * 10^5 molecules should take well
+under 10 ms, less than the host's sort of the entries; host to host nothing visible.
 """
 import argparse
 import json
@@ -52,7 +70,7 @@ def code(s):
     return np.array(["ACGT".index(c) for c in s], np.uint8)
 
 
-def make_batch(n, n_mol, seed=1, sub=0.02):
+def make_batch(n, n_mol, seed=1, sub=0.02, umi_sub=0.0):
     rng = np.random.default_rng(seed)
     L = bench.READ_LEN
     bar = np.array([code(b) for b in bench.BARCODES], np.uint8)
@@ -74,6 +92,9 @@ def make_batch(n, n_mol, seed=1, sub=0.02):
     structured[:, t0:] |= in_ad
     structured &= rng.random((n, L)) < sub
     np.copyto(y, rng.integers(0, 4, size=(n, L), dtype=np.uint8), where=structured)
+    if umi_sub > 0:                                                # misread UMI bases: always another base
+        hit = rng.random((n, UMI)) < umi_sub
+        y[:, 6:6 + UMI] = np.where(hit, (y[:, 6:6 + UMI] + rng.integers(1, 4, size=(n, UMI), dtype=np.uint8)) & 3, y[:, 6:6 + UMI])
     return np.ascontiguousarray(y.reshape(-1)), np.arange(n + 1, dtype=np.int64) * L, int(len(np.unique(draw)))
 
 
@@ -141,17 +162,67 @@ def measure(ctx, seq, offs, n):
     return out
 
 
+def measure_collapse(ctx, seq, offs, n):
+    from tagdust_amd import RESULT_DTYPE
+    out = {"umi_substitution_rate": 0.005}
+    ctx.mol_enable(PREFIX, LOG2_SLOTS)
+    ctx.mol_collapse_enable()
+    dec, cnt, org = [], [], []
+    for it in range(6):
+        ctx.mol_reset()
+        ctx.upload_batch(seq, offs)
+        ctx.run()
+        dec.append(ctx.last_kernel_ms())
+        cnt.append(ctx.get_option("molecules_kernel_us") / 1000.0)
+        org.append(ctx.get_option("collapse_origin_kernel_us") / 1000.0)
+        if it == 0:
+            for name in ("collapse_get_ms_first_call", "collapse_get_ms_second_call"):
+                t0 = time.perf_counter()
+                rows, tot = ctx.mol_collapse_get()
+                out[name] = round((time.perf_counter() - t0) * 1e3, 3)
+            out["collapse_totals_of_one_batch"] = tot
+            out["rows_of_one_batch_collapsed"] = [[int(r["reads"]), int(r["molecules"])] for r in rows[:len(bench.BARCODES)]]
+    d, c, o = statistics.median(dec[1:]), statistics.median(cnt[1:]), statistics.median(org[1:])
+    out["decode_kernel_ms_median"], out["count_kernel_ms_median"], out["origin_kernel_ms_median"] = round(d, 3), round(c, 3), round(o, 3)
+    out["origin_kernel_ms_runs"] = [round(v, 3) for v in org[1:]]
+    out["origin_share_of_decode"], out["origin_over_count"] = round(o / d, 5), round(o / c, 3) if c > 0 else None
+    ctx.mol_disable()
+    # host to host: the first pass of the process is discarded, then the collapse and the count alone in turn, twice each
+    res = [np.zeros(n, RESULT_DTYPE) for _ in range(2)]
+    rates = {"discarded_first_pass": [], "collapse": [], "count_alone": []}
+    for k, state in enumerate(("count_alone", "collapse", "count_alone", "collapse", "count_alone")):
+        ctx.mol_enable(PREFIX, LOG2_SLOTS)
+        if state == "collapse":
+            ctx.mol_collapse_enable()
+        steps = 4
+        for t in [ctx.submit(seq, offs, res=r) for r in res]:      # warm-up: both slots, both result buffers
+            ctx.wait(t)
+        t0 = time.perf_counter()
+        tickets = []
+        for s in range(steps):
+            tickets.append(ctx.submit(seq, offs, res=res[s & 1]))
+            if len(tickets) == 2:
+                ctx.wait(tickets.pop(0))
+        for t in tickets:
+            ctx.wait(t)
+        rates["discarded_first_pass" if k == 0 else state].append(round(steps * n / (time.perf_counter() - t0)))
+        ctx.mol_disable()
+    out["host_to_host_reads_per_s"] = rates
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reads", type=int, default=1 << 20)
     ap.add_argument("--molecules", type=int, default=1 << 18)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "molecules.json"))
+    ap.add_argument("--collapse", action="store_true", help="measure the UMI collapse alone and add a \"collapse\" section to --out")
     args = ap.parse_args()
     from tagdust_amd import TagdustHip
     from tagdust_amd import lib as tdlib
     segs = ["B:" + ",".join(bench.BARCODES), "F:" + "N" * UMI, "S:" + bench.SPACER, "R:N", "P:" + bench.ADAPTER]
-    seq, offs, drawn = make_batch(args.reads, args.molecules)
+    seq, offs, drawn = make_batch(args.reads, args.molecules, umi_sub=0.005 if args.collapse else 0.0)
     head = min(args.reads, 100000)
     md, _ = tdlib.build_model(segs, seq[:offs[head]], offs[:head + 1])
     ctx = TagdustHip(args.device)
@@ -161,10 +232,16 @@ def main():
         ctx.set_option("async_compile", 0)
         ctx.upload_model(md)
         ctx.set_params(5.0, 16, 100)
-        doc.update(measure(ctx, seq, offs, args.reads))
+        if args.collapse:
+            section = dict(doc, **measure_collapse(ctx, seq, offs, args.reads))
+        else:
+            doc.update(measure(ctx, seq, offs, args.reads))
     finally:
         ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if args.collapse:                                              # the file's other figures stay what they are
+        doc = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        doc["collapse"] = section
     json.dump(doc, open(args.out, "w"), indent=1, sort_keys=True)
     print(json.dumps(doc, sort_keys=True))
 
