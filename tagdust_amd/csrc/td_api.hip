@@ -154,7 +154,6 @@ extern "C" int td_ctx_create(int device, td_ctx** out)
 }
 
 static void slot_release(TdSlot& s);
-static bool tickets_outstanding(const td_ctx* c);
 
 static void free_dev_model(DevModel& d)
 {
@@ -847,10 +846,8 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
 	if (ka.art_n > 0 && slot_count_hits(c, s, ka.out_type) != TD_OK) return TD_FAIL;
 	if (c->census.on && mode == TD_MODE_GET_LABEL && census_count_slot(c, s, ka.out_type, ka.out_labels) != TD_OK) return TD_FAIL;
-	if (c->molecules.on && mode == TD_MODE_GET_LABEL && mol_count_slot(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
-	if (c->molecules.collapse && mode == TD_MODE_GET_LABEL && mol_origin_slot(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
-	// dedup last: its second pass rewrites the outcomes the three counts above read
-	if (c->molecules.dedup && mode == TD_MODE_GET_LABEL && mol_dedup_slot(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
+	// the molecule count last: dedup's second pass, the last launch in there, rewrites the outcomes the counts above read
+	if (c->molecules.on && mode == TD_MODE_GET_LABEL && mol_slot_decoded(c, s, ka.out_type, ka.out_barcode, ka.out_finger, ka.out_labels) != TD_OK) return TD_FAIL;
 	s.ran = true;
 	s.last_ms = -1.0f;
 	c->last_slot = (int)(&s - c->slots);
@@ -1017,7 +1014,7 @@ static int slot_fetch_end(td_ctx* c, TdSlot& s)
 	return TD_OK;
 }
 
-static bool tickets_outstanding(const td_ctx* c)
+bool tickets_outstanding(const td_ctx* c)
 {
 	for (int k = 0; k < TD_MAX_PIPELINE; k++) if (c->slots[k].ticket) return true;
 	return false;

@@ -1,5 +1,5 @@
 // td_census.h -- the census of barcode spellings (include/tagdust_census.h) inside a context: its state, and what td_api.hip
-// calls.  The kernels and every td_census_* entry point are in td_census.hip.  Nothing here is exported.
+// calls.  The kernel and every td_census_* entry point that takes a context are in td_census.hip.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -6,30 +6,19 @@
 // the decode kernels.  Lanes of a wave that hold the same key leave as one probe and one add of their number; the distinct keys
 // of a wave probe side by side.  Nothing is ever removed from the table and the probe window is fixed, so a key finds or claims
 // its slot on every attempt or fails on every attempt: a reported count is exact, what did not fit is in the overflow tally.
-// td_census_host is the same definition over host arrays (no GPU), td_census_merge adds two results.
+// The same definition over host arrays (td_census_host), td_census_merge and td_census_key_text are in td_census_host.cpp.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
 
 #include "../../include/tagdust_census.h"
 #include "td_ctx.h"
 
-typedef kt_u64 cs_u64;
-
-#define CS_BLOCK KT_BLOCK
-#define CS_WAVES KT_WAVES
-
-__global__ __launch_bounds__(CS_BLOCK) void td_census_count_kernel(const TdCensusArgs a)
+__global__ __launch_bounds__(KT_BLOCK) void td_census_count_kernel(const TdCensusArgs a)
 {
 	// per label: 1 = the segment, 2 = a later segment, 0 = an earlier one
 	__shared__ uint8_t s_cls[128];
 	kt_label_classes(s_cls, a.label, a.H, [&](int seg) { return seg == a.segment ? 1 : (seg > a.segment ? 2 : 0); });
 	const int lane = threadIdx.x & (TD_WAVE - 1);
-	const int tile = blockIdx.x * CS_WAVES + (threadIdx.x >> 6);
+	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
 	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
 	const int64_t k = (int64_t)tile * TD_WAVE + lane;
 	bool elig = false;
@@ -40,58 +29,35 @@ __global__ __launch_bounds__(CS_BLOCK) void td_census_count_kernel(const TdCensu
 		if (elig) len = a.lens[k];
 	}
 	if (__builtin_amdgcn_ballot_w64(elig) == 0ull) return;
-	cs_u64 w = 0ull;
+	kt_u64 w = 0ull;
 	int n = 0;
 	bool has_n = false;
 	kt_walk_tile(a.tile, s_cls, tile, lane, len, [&](uint32_t cls, uint32_t base, bool base_is_n) {
 		if (cls == 1u) {
 			n++;
-			if (n <= TD_CENSUS_MAX_WORD) { w = (w << 2) | (cs_u64)base; has_n = has_n || base_is_n; }
+			if (n <= TD_CENSUS_MAX_WORD) { w = (w << 2) | (kt_u64)base; has_n = has_n || base_is_n; }
 		} else if (cls == 2u && a.ordered) return false;             // the path has left the segment for good
 		return true;
 	});
 	const bool is_empty = elig && n == 0, is_long = elig && n > TD_CENSUS_MAX_WORD;
 	const bool is_n = elig && !is_empty && !is_long && has_n;
 	const bool has_key = elig && !is_empty && !is_long && !has_n;
-	const KtWaveAdded added = kt_wave_add(a.table, has_key, has_key ? (((cs_u64)n << 56) | w) : 0ull, lane);
+	const KtWaveAdded added = kt_wave_add(a.table, has_key, has_key ? (((kt_u64)n << 56) | w) : 0ull, lane);
 	// tallies: one add per wave and tally
 	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig));
 	const int n_empty = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_empty));
 	const int n_long = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_long));
 	const int n_n = __builtin_popcountll(__builtin_amdgcn_ballot_w64(is_n));
 	if (lane == 0) {
-		atomicAdd(&a.tallies[TDC_ELIGIBLE], (cs_u64)n_elig);
-		if (added.counted) atomicAdd(&a.tallies[TDC_COUNTED], (cs_u64)added.counted);
-		if (n_empty) atomicAdd(&a.tallies[TDC_EMPTY], (cs_u64)n_empty);
-		if (n_long) atomicAdd(&a.tallies[TDC_LONG], (cs_u64)n_long);
-		if (n_n) atomicAdd(&a.tallies[TDC_N], (cs_u64)n_n);
-		if (added.overflow) atomicAdd(&a.tallies[TDC_OVERFLOW], (cs_u64)added.overflow);
-		if (added.fresh) atomicAdd(&a.tallies[TDC_DISTINCT], (cs_u64)added.fresh);
+		atomicAdd(&a.tallies[TDC_ELIGIBLE], (kt_u64)n_elig);
+		if (added.counted) atomicAdd(&a.tallies[TDC_COUNTED], (kt_u64)added.counted);
+		if (n_empty) atomicAdd(&a.tallies[TDC_EMPTY], (kt_u64)n_empty);
+		if (n_long) atomicAdd(&a.tallies[TDC_LONG], (kt_u64)n_long);
+		if (n_n) atomicAdd(&a.tallies[TDC_N], (kt_u64)n_n);
+		if (added.overflow) atomicAdd(&a.tallies[TDC_OVERFLOW], (kt_u64)added.overflow);
+		if (added.fresh) atomicAdd(&a.tallies[TDC_DISTINCT], (kt_u64)added.fresh);
 	}
 }
-
-// ---------------------------------------------------------------------------------------------------------
-// host
-// ---------------------------------------------------------------------------------------------------------
-namespace {
-
-// the segment a census of this model counts: `segment` itself when it is a 'B' segment, the last 'B' segment for -1
-bool pick_segment(const td_model_desc* m, int32_t segment, int32_t& out, std::string& why)
-{
-	if (!m || m->S < 1 || !m->seg_type || !m->label) { why = "no model"; return false; }
-	int last = -1;
-	for (int j = 0; j < m->S; j++) if (m->seg_type[j] == 'B') last = j;
-	if (last < 0) { why = "the model has no 'B' segment: there is no barcode to take a census of"; return false; }
-	if (segment == -1) { out = last; return true; }
-	if (segment < 0 || segment >= m->S) { why = "segment " + std::to_string(segment) + " is out of range (0.." + std::to_string(m->S - 1) + ", or -1 for the last 'B' segment)"; return false; }
-	if (m->seg_type[segment] != 'B') { why = "segment " + std::to_string(segment) + " is a '" + std::string(1, (char)m->seg_type[segment]) + "' segment, not a 'B' segment"; return false; }
-	out = segment;
-	return true;
-}
-
-bool mask_ok(uint32_t mask) { return mask != 0u && mask <= 0xFFu; }
-
-}   // namespace
 
 void census_release(td_ctx* c)
 {
@@ -107,23 +73,21 @@ int census_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int8_
 	a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.H = z.table.H;
 	a.segment = z.segment; a.ordered = z.ordered ? 1 : 0; a.mask = z.mask;
 	a.table = kt_table_view(z.table); a.tallies = z.table.d_tallies;
-	return kt_count_slot(c, z.table, s, (const void*)td_census_count_kernel, &a);
+	if (kt_count_slot(c, z.table, s, (const void*)td_census_count_kernel, &a) != TD_OK) return TD_FAIL;
+	return kt_slot_read_behind(c, s);
 }
 
 extern "C" int td_census_enable(td_ctx* c, int32_t segment, uint32_t outcome_mask, int32_t log2_slots)
 {
 	if (!c) return TD_FAIL;
 	if (!c->have_model) return fail(c, "td_census_enable: no model uploaded");
-	for (int k = 0; k < TD_MAX_PIPELINE; k++)
-		if (c->slots[k].ticket) return fail(c, "td_census_enable: td_submit tickets are outstanding (td_wait them first)");
+	if (tickets_outstanding(c)) return fail(c, "td_census_enable: td_submit tickets are outstanding (td_wait them first)");
 	int32_t seg = -1;
-	std::string why;
-	if (!pick_segment(&c->model.d, segment, seg, why)) return fail(c, "td_census_enable: %s", why.c_str());
-	if (!mask_ok(outcome_mask)) return fail(c, "td_census_enable: outcome_mask 0x%x is not a non-empty subset of bits 0..7", outcome_mask);
+	if (census_pick_segment(c, "td_census_enable", &c->model.d, segment, &seg) != TD_OK) return TD_FAIL;
+	if (!census_mask_ok(outcome_mask)) return fail(c, "td_census_enable: outcome_mask 0x%x is not a non-empty subset of bits 0..7", outcome_mask);
 	if (log2_slots < 4 || log2_slots > 26) return fail(c, "td_census_enable: log2_slots = %d (4..26 supported)", log2_slots);
 	if (c->match_len > 0) return fail(c, "td_census_enable: a -start/-end window is set (td_set_window): labels behind a window do not spell the barcode");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
 	census_release(c);
 	TdCensusState& z = c->census;
 	const td_model_desc& m = c->model.d;
@@ -143,8 +107,7 @@ extern "C" int td_census_disable(td_ctx* c)
 {
 	if (!c) return TD_FAIL;
 	if (!c->census.on) return TD_OK;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
 	census_release(c);
 	return TD_OK;
 }
@@ -154,8 +117,7 @@ extern "C" int td_census_reset(td_ctx* c)
 	if (!c) return TD_FAIL;
 	TdCensusState& z = c->census;
 	if (!z.on) return fail(c, "td_census_reset: the census is off (td_census_enable)");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));   // (counts of pipelined batches may still be queued, on either compute stream)
+	if (wait_compute(c) != TD_OK) return TD_FAIL;   // (counts of pipelined batches may still be queued, on either compute stream)
 	HIPCHK(c, kt_table_zero(z.table, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	return TD_OK;
@@ -166,7 +128,7 @@ extern "C" int td_census_get(td_ctx* c, td_census_entry* entries, int64_t cap, i
 	if (!c) return TD_FAIL;
 	TdCensusState& z = c->census;
 	if (!z.on) return fail(c, "td_census_get: the census is off (td_census_enable)");
-	cs_u64 t[TDC_TALLY_WORDS];
+	kt_u64 t[TDC_TALLY_WORDS];
 	if (kt_table_entries(c, "td_census_get", z.table, TDC_DISTINCT, TDC_CURSOR, entries, cap, n, t) != TD_OK) return TD_FAIL;
 	if (totals) {
 		totals->eligible = (int64_t)t[TDC_ELIGIBLE]; totals->counted = (int64_t)t[TDC_COUNTED]; totals->skipped_empty = (int64_t)t[TDC_EMPTY];
@@ -182,62 +144,4 @@ int census_last_kernel_us(td_ctx* c, int32_t* us)
 	const TdCountTable& t = c->census.table;
 	if (!c->census.on) return fail(c, "td_get_option: census_kernel_us: the census is off");
 	return kt_last_kernel_us(c, t.ev_c0, t.ev_c1, us, "td_get_option: census_kernel_us: no batch has been counted yet");
-}
-
-extern "C" int td_census_host(const td_model_desc* m, int32_t segment, uint32_t outcome_mask, const uint8_t* codes, const int64_t* offs,
-                              int64_t n_reads, const td_read_result* res, const int8_t* labels,
-                              td_census_entry** entries, int64_t* n, td_census_totals* totals)
-{
-	if (entries) *entries = nullptr;
-	if (n) *n = 0;
-	int32_t seg = -1;
-	std::string why;
-	if (!pick_segment(m, segment, seg, why)) return fail(nullptr, "td_census_host: %s", why.c_str());
-	if (!mask_ok(outcome_mask)) return fail(nullptr, "td_census_host: outcome_mask 0x%x is not a non-empty subset of bits 0..7", outcome_mask);
-	if (!entries || !n || n_reads < 0 || (n_reads > 0 && (!offs || !res || !labels))) return fail(nullptr, "td_census_host: bad arguments");
-	td_census_totals t{};
-	std::vector<uint64_t> keys;
-	for (int64_t i = 0; i < n_reads; i++) {
-		const uint32_t type = (uint32_t)res[i].read_type & 0xFFu;
-		if (type >= 8u || !((outcome_mask >> type) & 1u)) continue;
-		t.eligible++;
-		const int64_t len = offs[i + 1] - offs[i];
-		const int8_t* lab = labels + offs[i] + i;
-		const uint8_t* seq = codes + offs[i];
-		uint64_t w = 0;
-		int cnt = 0;
-		bool has_n = false;
-		for (int64_t p = 0; p < len; p++) {
-			const int l = lab[p + 1];
-			if (l < 0 || l >= m->H || (m->label[l] & 0xFFFF) != seg) continue;
-			cnt++;
-			if (cnt <= TD_CENSUS_MAX_WORD) {
-				if (seq[p] > 3) has_n = true;
-				w = (w << 2) | (uint64_t)(seq[p] & 3u);
-			}
-		}
-		if (cnt == 0) t.skipped_empty++;
-		else if (cnt > TD_CENSUS_MAX_WORD) t.skipped_long++;
-		else if (has_n) t.skipped_n++;
-		else { keys.push_back(((uint64_t)cnt << 56) | w); t.counted++; }
-	}
-	std::vector<td_census_entry> v;
-	kt_tally_keys(keys, v);
-	t.distinct = (int64_t)v.size();
-	if (!(*entries = kt_copy_entries(v))) return fail(nullptr, "td_census_host: out of memory");
-	*n = (int64_t)v.size();
-	if (totals) *totals = t;
-	return TD_OK;
-}
-
-extern "C" int td_census_key_text(uint64_t key, char buf[32])
-{
-	if (!buf) return TD_FAIL;
-	buf[0] = 0;
-	const int len = (int)(key >> 56);
-	if (len < 1 || len > TD_CENSUS_MAX_WORD) return fail(nullptr, "td_census_key_text: 0x%llx is no key (length %d)", (unsigned long long)key, len);
-	if (len < TD_CENSUS_MAX_WORD && ((key & 0x00FFFFFFFFFFFFFFull) >> (2 * len)) != 0) return fail(nullptr, "td_census_key_text: 0x%llx is no key (bits beyond its %d bases)", (unsigned long long)key, len);
-	for (int i = 0; i < len; i++) buf[i] = "ACGT"[(key >> (2 * (len - 1 - i))) & 3u];
-	buf[len] = 0;
-	return TD_OK;
 }

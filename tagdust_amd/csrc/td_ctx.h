@@ -227,6 +227,7 @@ struct td_ctx {
 };
 
 TD_HIDDEN int fail(td_ctx* c, const char* fmt, ...);   // (td_api.hip) TD_FAIL, and the message for td_last_error
+TD_HIDDEN bool tickets_outstanding(const td_ctx* c);   // (td_api.hip) a td_submit batch has not been waited for
 
 #define HIPCHK(c, call)                                                                       \
 	do {                                                                                      \
@@ -242,6 +243,14 @@ static hipError_t sync_compute(td_ctx* c)
 	if (e == hipSuccess && c->s_aux) e = hipStreamSynchronize(c->s_aux);
 	if (e == hipSuccess && c->s_fin) e = hipStreamSynchronize(c->s_fin);
 	return e;
+}
+
+// the context's device is the current one and nothing is queued on its compute streams any more
+static int wait_compute(td_ctx* c)
+{
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, sync_compute(c));
+	return TD_OK;
 }
 
 template <typename T>

@@ -1,7 +1,8 @@
 // td_keytable.h -- the counting table the census (td_census.hip) and the molecule count (td_molecules.hip) share: 64-bit keys, never
-// 0, counted in an open-addressing table in HBM.  Here: the table as a context owns it (TdCountTable; its life, its results and
-// the host helpers of every td_census_entry result are in td_keytable.hip), and the device code both count kernels are made of --
-// the walk over a decoded tile, the probe, the wave's tail.  The device functions are inline: a probe belongs inside its kernel.
+// 0, counted in an open-addressing table in HBM.  Here: the table as a context owns it (TdCountTable; its life and its results are
+// in td_keytable.hip), and the device code both count kernels are made of -- the walk over a decoded tile, the probe, the wave's
+// tail, a wave's places behind a cursor.  The device functions are inline: a probe belongs inside its kernel.  The arithmetic of a
+// key and the host helpers of every td_census_entry result come from td_count_key.h, which the host units read without this file.
 //
 // Lanes of a wave that hold the same key leave as one probe and one add of their number (kt_wave_merge); the distinct keys of a
 // wave probe side by side (kt_probe_add).  Nothing is ever removed from the table and the probe window is fixed, so a key finds or
@@ -11,22 +12,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <vector>
+#include <functional>
 
-#include "../../include/tagdust_census.h"
+#include "td_count_key.h"
 #include "td_device.h"
 
-struct td_ctx;
 struct TdSlot;
-
-typedef unsigned long long kt_u64;
 
 #define KT_BLOCK 256
 #define KT_WAVES (KT_BLOCK / TD_WAVE)
 // linear probing looks at this many slots from the key's hash (the whole table when that is smaller): the same on every attempt
 #define KT_PROBE_WINDOW 128
 #define KT_SLOT_BYTES 16   // a key and a count, 8 bytes each
-#define KT_HIDDEN __attribute__((visibility("hidden")))
 
 struct TdKeyTable {
 	kt_u64* __restrict__ keys;      // [slot_mask + 1], 0 = empty
@@ -59,9 +56,17 @@ KT_HIDDEN hipError_t kt_table_zero(const TdCountTable& t, hipStream_t stream);
 KT_HIDDEN TdKeyTable kt_table_view(const TdCountTable& t);
 KT_HIDDEN TdTileView kt_tile_view(const TdSlot& s, const int8_t* labels);
 // The count of one decoded slot: `kernel` (KT_BLOCK threads, a tile per wave, *args its one argument) on the slot's compute stream
-// between the table's two events.  The finish kernel waits for ev_hits: a slot whose batch has been waited for is no longer read
-// by this count either.
+// between the table's two events.
 KT_HIDDEN int kt_count_slot(td_ctx* c, const TdCountTable& t, TdSlot& s, const void* kernel, void* args);
+// ... and behind the last launch that reads the decoded slot: the finish kernel waits for ev_hits, so a slot whose batch has been
+// waited for is no longer read by these launches either
+KT_HIDDEN int kt_slot_read_behind(td_ctx* c, TdSlot& s);
+// The bracket around a sweep that fills dense arrays behind a cursor (kt_wave_place): up to two device arrays of `count` elements of
+// size0 / size1 bytes (0: none), the cursor zeroed, launch(array 0, array 1) on the context's stream and waited for, the arrays
+// copied down to out0 / out1 and freed; *found = what the cursor came to, the caller holds it against what it expects.  A HIP
+// failure is "`who`: `what`: <its text>".
+KT_HIDDEN int kt_sweep_dense(td_ctx* c, const char* who, const char* what, kt_u64* cursor, size_t count, void* out0, size_t size0, void* out1,
+                             size_t size1, const std::function<void(void*, void*)>& launch, int64_t* found);
 // What the table holds, in the order of td_census_get (`who`: the entry point, for its messages): tallies[t.tally_words] down,
 // the occupied pairs -- tallies[distinct_word] of them, the compaction's cursor is tallies[cursor_word] -- held against that
 // tally and sorted; *n = their number, entries[min(cap, *n)] the first of them.  Waits for the compute streams.
@@ -69,22 +74,8 @@ KT_HIDDEN int kt_table_entries(td_ctx* c, const char* who, const TdCountTable& t
                                int64_t cap, int64_t* n, kt_u64* tallies);
 // microseconds between two recorded events (waits for the second); `none_yet`: the message when they have not been recorded
 KT_HIDDEN int kt_last_kernel_us(td_ctx* c, hipEvent_t e0, hipEvent_t e1, int32_t* us, const char* none_yet);
-// host helpers of every result made of td_census_entry: the order of td_census_get; a malloc'd copy for td_census_free (NULL: out
-// of memory); keys (any order, repeated) -> entries in that order
-KT_HIDDEN bool kt_entry_before(const td_census_entry& x, const td_census_entry& y);
-KT_HIDDEN td_census_entry* kt_copy_entries(const std::vector<td_census_entry>& v);
-KT_HIDDEN void kt_tally_keys(std::vector<uint64_t>& keys, std::vector<td_census_entry>& out);
 
 #ifdef __HIPCC__
-// splitmix64's finish: every bit of k reaches every bit of the result
-__host__ __device__ __forceinline__ kt_u64 kt_mix(kt_u64 k)
-{
-	k ^= k >> 30; k *= 0xBF58476D1CE4E5B9ull;
-	k ^= k >> 27; k *= 0x94D049BB133111EBull;
-	k ^= k >> 31;
-	return k;
-}
-
 __device__ __forceinline__ uint32_t kt_hash(kt_u64 k) { return (uint32_t)(kt_mix(k) >> 32); }
 
 __device__ __forceinline__ kt_u64 kt_readlane64(kt_u64 v, int lane)
@@ -98,6 +89,18 @@ __device__ __forceinline__ int kt_wave_sum(int v)
 {
 	for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
 	return v;
+}
+
+// A wave's places in a dense array behind `cursor` (whole waves): the lanes with `take` get consecutive positions -- one add on the
+// cursor by the first of them, the others behind it by their rank --, every other lane -1
+__device__ __forceinline__ int64_t kt_wave_place(bool take, kt_u64* __restrict__ cursor, int lane)
+{
+	const kt_u64 hit = __builtin_amdgcn_ballot_w64(take);
+	if (hit == 0ull) return -1;
+	kt_u64 base = 0ull;
+	if (lane == __builtin_ctzll(hit)) base = atomicAdd(cursor, (kt_u64)__builtin_popcountll(hit));
+	base = kt_readlane64(base, __builtin_ctzll(hit));
+	return take ? (int64_t)base + __builtin_popcountll(hit & ((1ull << lane) - 1ull)) : -1;
 }
 
 // lanes with the same key leave as one: the first of them gets their number, the others 0 (whole waves only)

@@ -1,7 +1,7 @@
-// td_keytable.hip -- the host side of td_keytable.h: the life of a context's counting table, the bracket around a count launch,
-// the table's contents as sorted entries (with the compaction kernel), and the host helpers of every td_census_entry result.
+// td_keytable.hip -- the host side of td_keytable.h: the life of a context's counting table, the bracket around a count launch, the
+// bracket around a sweep into dense arrays, and the table's contents as sorted entries (with the compaction kernel).  The host
+// helpers of every td_census_entry result are in td_census_host.cpp.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -18,13 +18,8 @@ __global__ __launch_bounds__(KT_BLOCK) void td_keytable_compact_kernel(const kt_
 	for (int64_t i0 = (int64_t)blockIdx.x * KT_BLOCK + (threadIdx.x - lane); i0 < n_slots; i0 += step) {   // (i0 is the wave's)
 		const int64_t i = i0 + lane;
 		const kt_u64 kv = i < n_slots ? keys[i] : 0ull;
-		const kt_u64 occ = __builtin_amdgcn_ballot_w64(kv != 0ull);
-		if (occ == 0ull) continue;
-		kt_u64 base = 0ull;
-		if (lane == __builtin_ctzll(occ)) base = atomicAdd(cursor, (kt_u64)__builtin_popcountll(occ));
-		base = kt_readlane64(base, __builtin_ctzll(occ));
-		const int64_t at = (int64_t)base + __builtin_popcountll(occ & ((1ull << lane) - 1ull));
-		if (kv != 0ull && at < cap) { out[at].key = kv; out[at].count = (int64_t)counts[i]; }
+		const int64_t at = kt_wave_place(kv != 0ull, cursor, lane);
+		if (at >= 0 && at < cap) { out[at].key = kv; out[at].count = (int64_t)counts[i]; }
 	}
 }
 
@@ -75,8 +70,33 @@ int kt_count_slot(td_ctx* c, const TdCountTable& t, TdSlot& s, const void* kerne
 	HIPCHK(c, hipEventRecord(t.ev_c0, s.cs));
 	if (s.n_tiles > 0) HIPCHK(c, hipLaunchKernel(kernel, dim3((unsigned)((s.n_tiles + KT_WAVES - 1) / KT_WAVES)), dim3(KT_BLOCK), &args, 0, s.cs));
 	HIPCHK(c, hipEventRecord(t.ev_c1, s.cs));
+	return TD_OK;
+}
+
+int kt_slot_read_behind(td_ctx* c, TdSlot& s)
+{
 	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));
 	s.hits_queued = true;
+	return TD_OK;
+}
+
+int kt_sweep_dense(td_ctx* c, const char* who, const char* what, kt_u64* cursor, size_t count, void* out0, size_t size0, void* out1, size_t size1,
+                   const std::function<void(void*, void*)>& launch, int64_t* found)
+{
+	void* d[2] = { nullptr, nullptr };
+	void* const out[2] = { out0, out1 };
+	const size_t bytes[2] = { size0 * count, size1 * count };
+	kt_u64 met = 0;
+	hipError_t e = hipSuccess;
+	for (int k = 0; k < 2; k++) if (e == hipSuccess && bytes[k]) e = hipMalloc(&d[k], bytes[k]);
+	if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(kt_u64), c->stream);
+	if (e == hipSuccess) { launch(d[0], d[1]); e = hipGetLastError(); }
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	for (int k = 0; k < 2; k++) if (e == hipSuccess && bytes[k]) e = hipMemcpy(out[k], d[k], bytes[k], hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(&met, cursor, sizeof met, hipMemcpyDeviceToHost);
+	for (void* p : d) if (p) (void)hipFree(p);
+	if (e != hipSuccess) return fail(c, "%s: %s: %s", who, what, hipGetErrorString(e));
+	*found = (int64_t)met;
 	return TD_OK;
 }
 
@@ -85,29 +105,20 @@ int kt_table_entries(td_ctx* c, const char* who, const TdCountTable& t, int dist
 {
 	if (cap < 0 || (cap > 0 && !entries) || !n) return fail(c, "%s: bad arguments", who);
 	*n = 0;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
 	HIPCHK(c, hipMemcpy(tallies, t.d_tallies, sizeof(kt_u64) * (size_t)t.tally_words, hipMemcpyDeviceToHost));
 	const int64_t distinct = (int64_t)tallies[distinct_word];
 	std::vector<td_census_entry> v((size_t)distinct);
 	if (distinct > 0) {   // the occupied pairs into a dense array on the device, what the sweep met into the cursor
-		td_census_entry* d_dense = nullptr;
 		kt_u64* cursor = t.d_tallies + cursor_word;
-		kt_u64 found = 0;
+		int64_t found = 0;
 		const int64_t n_slots = (int64_t)1 << t.log2_slots;
 		const unsigned blocks = (unsigned)std::min<int64_t>((n_slots + KT_BLOCK - 1) / KT_BLOCK, 2048);
-		hipError_t e = hipMalloc((void**)&d_dense, sizeof(td_census_entry) * (size_t)distinct);
-		if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(kt_u64), c->stream);
-		if (e == hipSuccess) {
-			hipLaunchKernelGGL(td_keytable_compact_kernel, dim3(blocks), dim3(KT_BLOCK), 0, c->stream, t.d_keys, t.d_counts, n_slots, d_dense, distinct, cursor);
-			e = hipGetLastError();
-		}
-		if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-		if (e == hipSuccess) e = hipMemcpy(v.data(), d_dense, sizeof(td_census_entry) * (size_t)distinct, hipMemcpyDeviceToHost);
-		if (e == hipSuccess) e = hipMemcpy(&found, cursor, sizeof found, hipMemcpyDeviceToHost);
-		(void)hipFree(d_dense);
-		if (e != hipSuccess) return fail(c, "%s: compaction failed: %s", who, hipGetErrorString(e));
-		if ((int64_t)found != distinct) return fail(c, "%s: the table holds %lld keys, its tally says %lld", who, (long long)found, (long long)distinct);
+		if (kt_sweep_dense(c, who, "compaction failed", cursor, (size_t)distinct, v.data(), sizeof(td_census_entry), nullptr, 0, [&](void* d_dense, void*) {
+			    hipLaunchKernelGGL(td_keytable_compact_kernel, dim3(blocks), dim3(KT_BLOCK), 0, c->stream, t.d_keys, t.d_counts, n_slots,
+			                       (td_census_entry*)d_dense, distinct, cursor);
+		    }, &found) != TD_OK) return TD_FAIL;
+		if (found != distinct) return fail(c, "%s: the table holds %lld keys, its tally says %lld", who, (long long)found, (long long)distinct);
 	}
 	std::sort(v.begin(), v.end(), kt_entry_before);
 	const int64_t take = std::min<int64_t>(cap, distinct);
@@ -127,45 +138,3 @@ int kt_last_kernel_us(td_ctx* c, hipEvent_t e0, hipEvent_t e1, int32_t* us, cons
 	*us = (int32_t)(ms * 1000.0f + 0.5f);
 	return TD_OK;
 }
-
-bool kt_entry_before(const td_census_entry& x, const td_census_entry& y) { return x.count != y.count ? x.count > y.count : x.key < y.key; }
-
-td_census_entry* kt_copy_entries(const std::vector<td_census_entry>& v)
-{
-	td_census_entry* p = (td_census_entry*)malloc(sizeof(td_census_entry) * (v.size() ? v.size() : 1));
-	if (p && !v.empty()) memcpy(p, v.data(), sizeof(td_census_entry) * v.size());
-	return p;
-}
-
-void kt_tally_keys(std::vector<uint64_t>& keys, std::vector<td_census_entry>& out)
-{
-	std::sort(keys.begin(), keys.end());
-	for (size_t i = 0; i < keys.size();) {
-		size_t j = i;
-		while (j < keys.size() && keys[j] == keys[i]) j++;
-		out.push_back(td_census_entry{ keys[i], (int64_t)(j - i) });
-		i = j;
-	}
-	std::sort(out.begin(), out.end(), kt_entry_before);
-}
-
-// (include/tagdust_census.h; the molecule count's entries go through these two as well)
-extern "C" int td_census_merge(const td_census_entry* a, int64_t na, const td_census_entry* b, int64_t nb, td_census_entry** out, int64_t* n)
-{
-	if (!out || !n || na < 0 || nb < 0 || (na > 0 && !a) || (nb > 0 && !b)) return fail(nullptr, "td_census_merge: bad arguments");
-	std::vector<td_census_entry> all;
-	all.insert(all.end(), a, a + na);
-	all.insert(all.end(), b, b + nb);
-	std::sort(all.begin(), all.end(), [](const td_census_entry& x, const td_census_entry& y) { return x.key < y.key; });
-	std::vector<td_census_entry> v;
-	for (const td_census_entry& e : all) {
-		if (!v.empty() && v.back().key == e.key) v.back().count += e.count;
-		else v.push_back(e);
-	}
-	std::sort(v.begin(), v.end(), kt_entry_before);
-	if (!(*out = kt_copy_entries(v))) return fail(nullptr, "td_census_merge: out of memory");
-	*n = (int64_t)v.size();
-	return TD_OK;
-}
-
-extern "C" void td_census_free(td_census_entry* entries) { free(entries); }

@@ -1,5 +1,6 @@
 // td_molecules.h -- the molecule count (include/tagdust_molecules.h) inside a context: its state, and what td_api.hip calls.  The
-// kernels and every td_mol_* entry point are in td_molecules.hip; the table is td_keytable.h's.  Nothing here is exported.
+// kernels and every td_mol_* entry point that takes a context are in td_molecules.hip; the table is td_keytable.h's.  Nothing here
+// is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,8 +36,8 @@ struct TdMolState {
 	bool collapse = false;
 	td_mol_origin* d_origin = nullptr;        // [2^log2_slots], n == 0 = no origin yet
 	hipEvent_t ev_o0 = nullptr, ev_o1 = nullptr;   // around the origin pass of the last batch (option "collapse_origin_kernel_us")
-	uint32_t* d_occ = nullptr;                // [cap_occ] the occupied slots' indices
-	int64_t cap_occ = 0;
+	uint32_t* d_occ = nullptr;                // the occupied slots' indices, cap_occ bytes of them
+	size_t cap_occ = 0;
 	uint32_t* d_parent = nullptr;             // [2^log2_slots] the slot of every occupied slot's parent, its own for a root
 	unsigned long long* d_collapsed = nullptr;   // [2^log2_slots] the count of a root's tree, 0 for every other slot
 };
@@ -62,17 +63,11 @@ struct TdMolArgs {
 	td_mol_origin* origin;                    // [slot_mask + 1] (not __restrict__: lanes of other waves write the same words)
 };
 
-// the count of one decoded slot, queued on its compute stream (td_api.hip calls it behind the decode launch while the count is on)
-__attribute__((visibility("hidden"))) int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode,
-                                                         const int32_t* out_finger, const int8_t* labels);
-// dedup's two passes over one decoded slot, queued behind its count (td_api.hip calls it last in slot_decode while dedup is on):
-// pass 2 rewrites out_type, so everything that reads the decoded outcomes is queued in front of it
-__attribute__((visibility("hidden"))) int mol_dedup_slot(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode,
-                                                         const int32_t* out_finger, const int8_t* labels);
-// the collapse's origin pass over one decoded slot, queued behind its count and in front of dedup, whose second pass rewrites the
-// outcomes it reads (td_api.hip calls it in slot_decode while the collapse is on)
-__attribute__((visibility("hidden"))) int mol_origin_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode,
-                                                          const int32_t* out_finger, const int8_t* labels);
+// A decoded slot's launches, queued on its compute stream behind the decode launch (td_api.hip calls it last in slot_decode while
+// the count is on): the count, the collapse's origin pass, dedup's two passes, each when it is on.  Dedup's second pass rewrites
+// out_type, so everything else that reads the decoded outcomes is queued in front of it.
+__attribute__((visibility("hidden"))) int mol_slot_decoded(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode,
+                                                           const int32_t* out_finger, const int8_t* labels);
 // option "collapse_origin_kernel_us" of td_get_option: the origin pass's time of the last batch (waits for it)
 __attribute__((visibility("hidden"))) int mol_origin_last_kernel_us(td_ctx* c, int32_t* us);
 // option "dedup_kernel_us" of td_get_option: the two passes' time of the last batch (waits for it)

@@ -6,51 +6,39 @@
 // counts it in the table of td_keytable.h, the census's.  One read per lane, one tile per wave, like the decode kernels.  Here
 // almost every read is eligible and almost every key is its own: the cost is the table's random traffic (a load, mostly a CAS, an
 // add per read), not the heavy hitter the census merges away -- the merge of equal keys in a wave stays, PCR copies sit together
-// often enough.  A second kernel sweeps the table into one summary row per barcode bin (td_mol_get).  td_mol_host is the same
-// definition over host arrays (no GPU), td_mol_summarise the same summary from entries.
+// often enough.  A second kernel sweeps the table into one summary row per barcode bin (td_mol_get).  The same definitions over
+// host arrays (td_mol_host, td_mol_host_origins, td_mol_dedup_host, td_mol_collapse_host), td_mol_summarise and td_mol_key are in
+// td_molecules_host.cpp; the key's arithmetic, one text for both sides, in td_count_key.h.
 //
 // Dedup (td_mol_dedup_enable) adds two launches behind the count.  Pass 1 builds every read's key again -- mol_lane_key is the one
 // text the count and it share --, finds the slot the count left the key in and lowers first[slot] to the read's ordinal, its
 // number in the caller's order over the whole context.  Pass 2 marks every read whose ordinal is not its slot's first as
 // TD_EXTRACT_DUPLICATE.  The minimum does not depend on the order the reads arrive in, so the two passes of neighbouring batches
 // may overlap but for one thing: pass 2 waits for pass 1 of the batch before it (an event), since that batch holds smaller
-// ordinals.  td_mol_dedup_host is the same decision on the host.
+// ordinals.
 //
 // Collapse (td_mol_collapse_enable) adds one launch behind the count, in front of dedup: the origin pass builds every read's key
 // once more, finds its slot and leaves what the key was made of beside it (16 bytes per slot).  The collapse itself runs when it
 // is asked for, over an idle table: the occupied slots' indices gathered into a dense list, then one molecule per lane -- the
 // parent pass probes the 3 * m keys one UMI mismatch away and keeps the best qualifying one, the root pass walks up and adds the
 // molecule's count to its root's --, then the summary sweep above over the collapsed counts, or a gather of the roots.
-// td_mol_collapse_host is the same definition on the host.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <string>
-#include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include "../../include/tagdust_molecules.h"
 #include "td_ctx.h"
 
-#define KEY_LOW_MASK 0x00FFFFFFFFFFFFFFull
-
-// the key of tagdust_molecules.h (host and device: the same integer arithmetic)
-__host__ __device__ __forceinline__ kt_u64 mol_key(int32_t barcode, int32_t fingerprint, kt_u64 w, int n)
-{
-	const kt_u64 a = kt_mix(((kt_u64)(uint32_t)fingerprint << 8) | (kt_u64)n);
-	kt_u64 low = kt_mix(w ^ a) & KEY_LOW_MASK;
-	if (low == 0ull) low = 1ull;
-	const kt_u64 bin = barcode == -1 ? 0ull : (kt_u64)(barcode & 0xFF);
-	return (bin << 56) | low;
-}
-
-// per label: 1 = it belongs to an 'R' segment (the whole workgroup; ends in its barrier)
-__device__ __forceinline__ void mol_r_labels(const TdMolArgs& a, uint8_t* s_r)
+// The head of the three kernels with a tile per wave.  s_r[128], per label: 1 = it belongs to an 'R' segment (the whole workgroup;
+// ends in its barrier, in front of any wave that leaves); then the lane and the wave's tile.  false: the wave has no tile.
+__device__ __forceinline__ bool mol_wave_tile(const TdMolArgs& a, uint8_t* s_r, int& lane, int& tile)
 {
 	kt_label_classes(s_r, a.label, a.H, [&](int seg) { return seg < 64 ? (int)((a.r_segs >> seg) & 1ull) : 0; });
+	lane = threadIdx.x & (TD_WAVE - 1);
+	tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
+	return tile < a.n_tiles;                          // (whole waves; no workgroup barrier behind this)
 }
 
 // what a lane's read is to the count: eligible, and then exactly one of the three classes (has_key: counted under `key`)
@@ -58,7 +46,7 @@ __device__ __forceinline__ void mol_r_labels(const TdMolArgs& a, uint8_t* s_r)
 struct MolLane { bool elig, is_empty, is_n, has_key; kt_u64 key, w; int32_t n, finger; };
 
 // The key of read k = tile * 64 + lane: the label walk, the prefix word and the N mask (whole waves).  false: no lane of the wave
-// is eligible, nothing else was read.  The count kernel and dedup's pass 1 both call this: one text.
+// is eligible, nothing else was read.  The count kernel, dedup's pass 1 and the origin pass all call this: one text.
 __device__ __forceinline__ bool mol_lane_key(const TdMolArgs& a, const uint8_t* s_r, int tile, int lane, int64_t k, MolLane& m)
 {
 	bool elig = false;
@@ -87,10 +75,8 @@ __device__ __forceinline__ bool mol_lane_key(const TdMolArgs& a, const uint8_t* 
 __global__ __launch_bounds__(KT_BLOCK) void td_mol_count_kernel(const TdMolArgs a)
 {
 	__shared__ uint8_t s_r[128];
-	mol_r_labels(a, s_r);
-	const int lane = threadIdx.x & (TD_WAVE - 1);
-	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
-	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
+	int lane, tile;
+	if (!mol_wave_tile(a, s_r, lane, tile)) return;
 	const int64_t k = (int64_t)tile * TD_WAVE + lane;
 	MolLane m;
 	if (!mol_lane_key(a, s_r, tile, lane, k, m)) return;
@@ -115,10 +101,8 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_count_kernel(const TdMolArgs 
 __global__ __launch_bounds__(KT_BLOCK) void td_mol_first_kernel(const TdMolArgs a)
 {
 	__shared__ uint8_t s_r[128];
-	mol_r_labels(a, s_r);
-	const int lane = threadIdx.x & (TD_WAVE - 1);
-	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
-	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
+	int lane, tile;
+	if (!mol_wave_tile(a, s_r, lane, tile)) return;
 	const int64_t k = (int64_t)tile * TD_WAVE + lane;
 	MolLane m;
 	int32_t slot = -1;
@@ -170,10 +154,8 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_mark_kernel(int32_t* __restri
 __global__ __launch_bounds__(KT_BLOCK) void td_mol_origin_kernel(const TdMolArgs a)
 {
 	__shared__ uint8_t s_r[128];
-	mol_r_labels(a, s_r);
-	const int lane = threadIdx.x & (TD_WAVE - 1);
-	const int tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
-	if (tile >= a.n_tiles) return;                    // (whole waves; no workgroup barrier below)
+	int lane, tile;
+	if (!mol_wave_tile(a, s_r, lane, tile)) return;
 	const int64_t k = (int64_t)tile * TD_WAVE + lane;
 	MolLane m;
 	if (!mol_lane_key(a, s_r, tile, lane, k, m)) return;
@@ -186,8 +168,8 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_origin_kernel(const TdMolArgs
 	o[1] = (kt_u64)(uint32_t)m.finger | ((kt_u64)(uint32_t)m.n << 32);
 }
 
-// Collapse: the indices of the occupied slots into a dense list, the pattern of td_keytable.hip's sweep over the pairs (one add on
-// the cursor per wave, the lanes behind it by their rank) -- a quarter-full table would leave three lanes in four idle below
+// Collapse: the indices of the occupied slots into a dense list, like td_keytable.hip's sweep over the pairs (kt_wave_place) -- a
+// quarter-full table would leave three lanes in four idle below
 __global__ __launch_bounds__(KT_BLOCK) void td_mol_occupied_kernel(const kt_u64* __restrict__ keys, int64_t n_slots, uint32_t* __restrict__ occ,
                                                                     int64_t cap, kt_u64* __restrict__ cursor)
 {
@@ -196,29 +178,9 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_occupied_kernel(const kt_u64*
 	for (int64_t i0 = (int64_t)blockIdx.x * KT_BLOCK + (threadIdx.x - lane); i0 < n_slots; i0 += step) {   // (i0 is the wave's)
 		const int64_t i = i0 + lane;
 		const kt_u64 kv = i < n_slots ? keys[i] : 0ull;
-		const kt_u64 hit = __builtin_amdgcn_ballot_w64(kv != 0ull);
-		if (hit == 0ull) continue;
-		kt_u64 base = 0ull;
-		if (lane == __builtin_ctzll(hit)) base = atomicAdd(cursor, (kt_u64)__builtin_popcountll(hit));
-		base = kt_readlane64(base, __builtin_ctzll(hit));
-		const int64_t at = (int64_t)base + __builtin_popcountll(hit & ((1ull << lane) - 1ull));
-		if (kv != 0ull && at < cap) occ[at] = (uint32_t)i;
+		const int64_t at = kt_wave_place(kv != 0ull, cursor, lane);
+		if (at >= 0 && at < cap) occ[at] = (uint32_t)i;
 	}
-}
-
-// (count, key) of v comes strictly before that of u in the order of td_census_get
-__host__ __device__ __forceinline__ bool mol_before(kt_u64 cv, kt_u64 kv, kt_u64 cu, kt_u64 ku) { return cv != cu ? cv > cu : kv < ku; }
-// UMI bases that take part: what an int fingerprint of (bases << 8 | length) still holds; none without a fingerprint
-__host__ __device__ __forceinline__ int mol_umi_bases(int32_t fingerprint)
-{
-	if (fingerprint == -1) return 0;
-	const int L = fingerprint & 0xFF;
-	return L < 12 ? L : 12;
-}
-// the key of u's neighbour with base i changed by d (1..3)
-__host__ __device__ __forceinline__ kt_u64 mol_neighbour_key(kt_u64 key, const td_mol_origin& o, int i, uint32_t d)
-{
-	return mol_key((int32_t)(key >> 56), (int32_t)((uint32_t)o.fingerprint ^ (d << (8 + 2 * i))), o.w, o.n);
 }
 
 // Collapse, the parent pass: one molecule per lane.  The three neighbours of a position probe side by side -- their first loads are
@@ -292,13 +254,8 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_gather_kernel(const kt_u64* _
 	uint32_t slot = 0u;
 	kt_u64 v = 0ull;
 	if (q < n_occ) { slot = occ[q]; v = values[slot]; }
-	const kt_u64 hit = __builtin_amdgcn_ballot_w64(v != 0ull);
-	if (hit == 0ull) return;
-	kt_u64 base = 0ull;
-	if (lane == __builtin_ctzll(hit)) base = atomicAdd(cursor, (kt_u64)__builtin_popcountll(hit));
-	base = kt_readlane64(base, __builtin_ctzll(hit));
-	const int64_t at = (int64_t)base + __builtin_popcountll(hit & ((1ull << lane) - 1ull));
-	if (v != 0ull && at < cap) { out[at].key = keys[slot]; out[at].count = (int64_t)v; out_origin[at] = origin[slot]; }
+	const int64_t at = kt_wave_place(v != 0ull, cursor, lane);
+	if (at >= 0 && at < cap) { out[at].key = keys[slot]; out[at].count = (int64_t)v; out_origin[at] = origin[slot]; }
 }
 
 // The table into one row per barcode bin.  Nearly all slots of a run fall into a handful of bins: a global atomic per slot would
@@ -330,48 +287,33 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_summary_kernel(const kt_u64* 
 // ---------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------
-namespace {
+static unsigned blocks_for(int64_t n) { return (unsigned)((n + KT_BLOCK - 1) / KT_BLOCK); }
 
-bool prefix_ok(int32_t p) { return p >= 1 && p <= TD_MOL_MAX_PREFIX; }
-
-// what read i is to the count on the host (td_mol_host and td_mol_dedup_host): not eligible, or one of the three classes; *key of
-// a counted read
-enum { MOL_NOT_ELIGIBLE = 0, MOL_EMPTY, MOL_HAS_N, MOL_COUNTED };
-int host_read_class(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t i,
-                    const td_read_result* res, const int8_t* labels, uint64_t* key, td_mol_origin* origin = nullptr)
-{
-	if (((uint32_t)res[i].read_type & 0xFFu) != (uint32_t)TD_EXTRACT_SUCCESS) return MOL_NOT_ELIGIBLE;
-	const int64_t len = offs[i + 1] - offs[i];
-	const int8_t* lab = labels + offs[i] + i;
-	const uint8_t* seq = codes + offs[i];
-	uint64_t w = 0;
-	int cnt = 0;
-	bool has_n = false;
-	for (int64_t p = 0; p < len && cnt < prefix_bases; p++) {
-		const int l = lab[p + 1];
-		if (l < 0 || l >= m->H) continue;
-		const int seg = m->label[l] & 0xFFFF;
-		if (seg >= m->S || m->seg_type[seg] != 'R') continue;
-		cnt++;
-		if (seq[p] > 3) has_n = true;
-		w = (w << 2) | (uint64_t)(seq[p] & 3u);
-	}
-	if (cnt == 0) return MOL_EMPTY;
-	if (has_n) return MOL_HAS_N;
-	*key = mol_key(res[i].barcode, res[i].fingerprint, w, cnt);
-	if (origin) *origin = td_mol_origin{ w, res[i].fingerprint, cnt };
-	return MOL_COUNTED;
-}
-
-void totals_from(const kt_u64* t, td_mol_totals* out)
+// the count's totals from its tallies as they came down
+static void totals_from(const kt_u64* t, td_mol_totals* out)
 {
 	out->eligible = (int64_t)t[TDM_ELIGIBLE]; out->counted = (int64_t)t[TDM_COUNTED]; out->skipped_empty = (int64_t)t[TDM_EMPTY];
 	out->skipped_n = (int64_t)t[TDM_N]; out->overflow = (int64_t)t[TDM_OVERFLOW]; out->molecules = (int64_t)t[TDM_MOLECULES];
 }
 
-}   // namespace
+// the summary sweep over the table's keys and `counts` (the count's own, or the collapsed ones: a slot that is no root has 0 there
+// and is skipped), the rows down
+static int summary_rows(td_ctx* c, const kt_u64* counts, td_mol_row rows[TD_NUM_BARCODE_BINS])
+{
+	TdMolState& z = c->molecules;
+	static_assert(sizeof(td_mol_row) == sizeof(kt_u64) * TDM_ROW_WORDS, "td_mol_row is the device row");
+	const int64_t n_slots = (int64_t)1 << z.table.log2_slots;
+	HIPCHK(c, hipMemsetAsync(z.d_rows, 0, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, c->stream));
+	hipLaunchKernelGGL(td_mol_summary_kernel, dim3(std::min(blocks_for(n_slots), 1024u)), dim3(KT_BLOCK), 0, c->stream, (const kt_u64*)z.table.d_keys,
+	                   counts, n_slots, z.d_rows);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipMemcpy(rows, z.d_rows, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, hipMemcpyDeviceToHost));
+	return TD_OK;
+}
 
-// dedup's first ordinals and events freed (nothing of it is queued any more)
+// dedup's first ordinals and events freed (nothing of it is queued any more).  They exist while z.dedup is set and inside a
+// td_mol_dedup_enable that has not yet succeeded, which frees what it got itself.
 static void dedup_release(TdMolState& z)
 {
 	if (z.d_first) (void)hipFree(z.d_first);
@@ -382,7 +324,7 @@ static void dedup_release(TdMolState& z)
 	z.dedup = false;
 }
 
-// the collapse's origins, events and work arrays freed (nothing of it is queued any more)
+// the collapse's origins, events and work arrays freed (nothing of it is queued any more); they exist as dedup's do
 static void collapse_release(TdMolState& z)
 {
 	void* p[] = { z.d_origin, z.d_occ, z.d_parent, z.d_collapsed };
@@ -404,82 +346,63 @@ void mol_release(td_ctx* c)
 	z = TdMolState();
 }
 
-// what the count kernel and dedup's pass 1 read of a decoded slot
-static TdMolArgs mol_args(const TdMolState& z, const TdSlot& s, const int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger,
-                          const int8_t* labels)
+// A decoded slot's launches, queued on its compute stream: the count, then the collapse's origin pass, then dedup's two passes, each
+// only when it is on and each between its own two events.  The order matters: dedup's pass 2 rewrites the outcomes the others read.
+int mol_slot_decoded(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
 {
+	TdMolState& z = c->molecules;
+	const unsigned blocks = (unsigned)((s.n_tiles + KT_WAVES - 1) / KT_WAVES);
 	TdMolArgs a{};
 	a.tile = kt_tile_view(s, labels); a.lens = s.d_lens; a.out_type = out_type; a.out_barcode = out_barcode; a.out_finger = out_finger;
 	a.label = z.table.d_label; a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.H = z.table.H;
 	a.r_segs = z.r_segs; a.prefix = z.prefix;
 	a.table = kt_table_view(z.table); a.tallies = z.table.d_tallies;
-	return a;
-}
-
-int mol_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
-{
-	TdMolArgs a = mol_args(c->molecules, s, out_type, out_barcode, out_finger, labels);
-	return kt_count_slot(c, c->molecules.table, s, (const void*)td_mol_count_kernel, &a);
-}
-
-int mol_origin_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
-{
-	TdMolState& z = c->molecules;
-	TdMolArgs a = mol_args(z, s, out_type, out_barcode, out_finger, labels);
-	a.origin = z.d_origin;
-	HIPCHK(c, hipEventRecord(z.ev_o0, s.cs));
-	if (s.n_tiles > 0) {
-		hipLaunchKernelGGL(td_mol_origin_kernel, dim3((unsigned)((a.n_tiles + KT_WAVES - 1) / KT_WAVES)), dim3(KT_BLOCK), 0, s.cs, a);
-		HIPCHK(c, hipGetLastError());
+	if (kt_count_slot(c, z.table, s, (const void*)td_mol_count_kernel, &a) != TD_OK) return TD_FAIL;
+	if (z.collapse) {
+		a.origin = z.d_origin;
+		HIPCHK(c, hipEventRecord(z.ev_o0, s.cs));
+		if (s.n_tiles > 0) {
+			hipLaunchKernelGGL(td_mol_origin_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
+			HIPCHK(c, hipGetLastError());
+		}
+		HIPCHK(c, hipEventRecord(z.ev_o1, s.cs));
 	}
-	HIPCHK(c, hipEventRecord(z.ev_o1, s.cs));
-	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));       // the slot is not restaged under this pass
-	s.hits_queued = true;
-	return TD_OK;
-}
-
-int mol_dedup_slot(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
-{
-	TdMolState& z = c->molecules;
-	const int64_t base = z.next_ordinal;              // batches get their ordinals in the order they are submitted in
-	z.next_ordinal += s.n_reads;
-	if (s.n_tiles <= 0) return TD_OK;
-	if (ensure(c, &s.d_judged, &s.cap_judged, (size_t)s.n_tiles * TD_WAVE * sizeof(int32_t)) != TD_OK) return TD_FAIL;
-	TdMolArgs a = mol_args(z, s, out_type, out_barcode, out_finger, labels);
-	a.read_at = s.sorted ? s.d_read_at : nullptr; a.first = z.d_first; a.judged = s.d_judged; a.ordinal_base = base;
-	const unsigned blocks = (unsigned)((a.n_tiles + KT_WAVES - 1) / KT_WAVES);
-	HIPCHK(c, hipEventRecord(z.ev_d0, s.cs));
-	hipLaunchKernelGGL(td_mol_first_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
-	HIPCHK(c, hipGetLastError());
-	// The batch before this one may run on the other compute stream, and it holds the smaller ordinals: its pass 1 has to be over
-	// before this batch's pass 2 reads a first ordinal.  (The batch before that one ran on this stream, or was waited for.)
-	const int t = z.turn;
-	HIPCHK(c, hipEventRecord(z.ev_p1[t], s.cs));
-	z.p1_queued[t] = true;
-	if (z.p1_queued[t ^ 1]) HIPCHK(c, hipStreamWaitEvent(s.cs, z.ev_p1[t ^ 1], 0));
-	z.turn = t ^ 1;
-	hipLaunchKernelGGL(td_mol_mark_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, out_type, (const int32_t*)s.d_judged, a.read_at,
-	                   (const kt_u64*)z.d_first, base, a.n_reads, a.n_tiles, z.table.d_tallies);
-	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipEventRecord(z.ev_d1, s.cs));
-	// the finish kernel copies out_type only behind pass 2, and the slot is not restaged under it
-	HIPCHK(c, hipEventRecord(s.ev_hits, s.cs));
-	s.hits_queued = true;
-	return TD_OK;
+	if (z.dedup) {
+		a.ordinal_base = z.next_ordinal;              // batches get their ordinals in the order they are submitted in
+		z.next_ordinal += s.n_reads;
+	}
+	if (z.dedup && s.n_tiles > 0) {
+		if (ensure(c, &s.d_judged, &s.cap_judged, (size_t)s.n_tiles * TD_WAVE * sizeof(int32_t)) != TD_OK) return TD_FAIL;
+		a.read_at = s.sorted ? s.d_read_at : nullptr; a.first = z.d_first; a.judged = s.d_judged;
+		HIPCHK(c, hipEventRecord(z.ev_d0, s.cs));
+		hipLaunchKernelGGL(td_mol_first_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
+		HIPCHK(c, hipGetLastError());
+		// The batch before this one may run on the other compute stream, and it holds the smaller ordinals: its pass 1 has to be over
+		// before this batch's pass 2 reads a first ordinal.  (The batch before that one ran on this stream, or was waited for.)
+		const int t = z.turn;
+		HIPCHK(c, hipEventRecord(z.ev_p1[t], s.cs));
+		z.p1_queued[t] = true;
+		if (z.p1_queued[t ^ 1]) HIPCHK(c, hipStreamWaitEvent(s.cs, z.ev_p1[t ^ 1], 0));
+		z.turn = t ^ 1;
+		hipLaunchKernelGGL(td_mol_mark_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, out_type, (const int32_t*)s.d_judged, a.read_at,
+		                   (const kt_u64*)z.d_first, a.ordinal_base, a.n_reads, a.n_tiles, z.table.d_tallies);
+		HIPCHK(c, hipGetLastError());
+		HIPCHK(c, hipEventRecord(z.ev_d1, s.cs));
+	}
+	// behind the last of them: the finish kernel copies out_type only behind pass 2, and the slot is not restaged under any of these
+	return kt_slot_read_behind(c, s);
 }
 
 extern "C" int td_mol_enable(td_ctx* c, int32_t prefix_bases, int32_t log2_slots)
 {
 	if (!c) return TD_FAIL;
 	if (!c->have_model) return fail(c, "td_mol_enable: no model uploaded");
-	for (int k = 0; k < TD_MAX_PIPELINE; k++)
-		if (c->slots[k].ticket) return fail(c, "td_mol_enable: td_submit tickets are outstanding (td_wait them first)");
-	if (!prefix_ok(prefix_bases)) return fail(c, "td_mol_enable: prefix_bases = %d (1..%d supported)", prefix_bases, TD_MOL_MAX_PREFIX);
+	if (tickets_outstanding(c)) return fail(c, "td_mol_enable: td_submit tickets are outstanding (td_wait them first)");
+	if (!mol_prefix_ok(prefix_bases)) return fail(c, "td_mol_enable: prefix_bases = %d (1..%d supported)", prefix_bases, TD_MOL_MAX_PREFIX);
 	if (log2_slots == 0) log2_slots = TD_MOL_DEFAULT_LOG2_SLOTS;
 	if (log2_slots < 4 || log2_slots > 30) return fail(c, "td_mol_enable: log2_slots = %d (4..30 supported, 0 = the default of %d)", log2_slots, TD_MOL_DEFAULT_LOG2_SLOTS);
 	if (c->match_len > 0) return fail(c, "td_mol_enable: a -start/-end window is set (td_set_window): labels behind a window do not mark the read's bases");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
 	mol_release(c);
 	TdMolState& z = c->molecules;
 	const td_model_desc& m = c->model.d;
@@ -499,10 +422,8 @@ extern "C" int td_mol_enable(td_ctx* c, int32_t prefix_bases, int32_t log2_slots
 extern "C" int td_mol_disable(td_ctx* c)
 {
 	if (!c) return TD_FAIL;
-	if (!c->molecules.on) return TD_OK;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
-	mol_release(c);
+	if (c->molecules.on && wait_compute(c) != TD_OK) return TD_FAIL;
+	mol_release(c);   // (off: there is nothing to free)
 	return TD_OK;
 }
 
@@ -511,8 +432,7 @@ extern "C" int td_mol_reset(td_ctx* c)
 	if (!c) return TD_FAIL;
 	TdMolState& z = c->molecules;
 	if (!z.on) return fail(c, "td_mol_reset: the molecule count is off (td_mol_enable)");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));   // (counts of pipelined batches may still be queued, on either compute stream)
+	if (wait_compute(c) != TD_OK) return TD_FAIL;   // (counts of pipelined batches may still be queued, on either compute stream)
 	HIPCHK(c, kt_table_zero(z.table, c->stream));   // (dedup's three tallies among them)
 	if (z.dedup) HIPCHK(c, hipMemsetAsync(z.d_first, 0xFF, sizeof(kt_u64) << z.table.log2_slots, c->stream));
 	if (z.collapse) HIPCHK(c, hipMemsetAsync(z.d_origin, 0, sizeof(td_mol_origin) << z.table.log2_slots, c->stream));
@@ -527,10 +447,8 @@ extern "C" int td_mol_dedup_enable(td_ctx* c)
 	if (!c) return fail(nullptr, "td_mol_dedup_enable: no context");
 	TdMolState& z = c->molecules;
 	if (!z.on) return fail(c, "td_mol_dedup_enable: the molecule count is off (td_mol_enable first): dedup judges the reads the count has keyed");
-	for (int k = 0; k < TD_MAX_PIPELINE; k++)
-		if (c->slots[k].ticket) return fail(c, "td_mol_dedup_enable: td_submit tickets are outstanding (td_wait them first)");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
+	if (tickets_outstanding(c)) return fail(c, "td_mol_dedup_enable: td_submit tickets are outstanding (td_wait them first)");
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
 	if (!z.dedup) {
 		bool ok = hipMalloc((void**)&z.d_first, sizeof(kt_u64) << z.table.log2_slots) == hipSuccess &&
 		          hipEventCreateWithFlags(&z.ev_p1[0], hipEventDisableTiming) == hipSuccess &&
@@ -538,7 +456,7 @@ extern "C" int td_mol_dedup_enable(td_ctx* c)
 		          hipEventCreate(&z.ev_d0) == hipSuccess && hipEventCreate(&z.ev_d1) == hipSuccess;
 		if (!ok) {
 			const std::string e = hipGetErrorString(hipGetLastError());
-			(void)td_mol_dedup_disable(c);
+			dedup_release(z);
 			return fail(c, "td_mol_dedup_enable: the first ordinals of 2^%d slots could not be set up: %s", z.table.log2_slots, e.c_str());
 		}
 		z.dedup = true;
@@ -549,11 +467,8 @@ extern "C" int td_mol_dedup_enable(td_ctx* c)
 extern "C" int td_mol_dedup_disable(td_ctx* c)
 {
 	if (!c) return TD_FAIL;
-	TdMolState& z = c->molecules;
-	if (!z.dedup && !z.d_first && !z.ev_p1[0] && !z.ev_p1[1] && !z.ev_d0 && !z.ev_d1) return TD_OK;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
-	dedup_release(z);
+	if (c->molecules.dedup && wait_compute(c) != TD_OK) return TD_FAIL;
+	dedup_release(c->molecules);   // (off: there is nothing to free)
 	return TD_OK;
 }
 
@@ -563,8 +478,7 @@ extern "C" int td_mol_dedup_get(td_ctx* c, td_mol_dedup_totals* totals)
 	TdMolState& z = c->molecules;
 	if (!z.dedup) return fail(c, "td_mol_dedup_get: dedup is off (td_mol_dedup_enable)");
 	if (!totals) return fail(c, "td_mol_dedup_get: bad arguments");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
 	kt_u64 t[TDM_TALLY_WORDS];
 	HIPCHK(c, hipMemcpy(t, z.table.d_tallies, sizeof t, hipMemcpyDeviceToHost));
 	totals->kept = (int64_t)t[TDM_KEPT]; totals->duplicates = (int64_t)t[TDM_DUPLICATES]; totals->unjudged = (int64_t)t[TDM_UNJUDGED];
@@ -588,17 +502,8 @@ extern "C" int td_mol_get(td_ctx* c, td_mol_row rows[TD_NUM_BARCODE_BINS], td_mo
 	TdMolState& z = c->molecules;
 	if (!z.on) return fail(c, "td_mol_get: the molecule count is off (td_mol_enable)");
 	if (!rows) return fail(c, "td_mol_get: bad arguments");
-	static_assert(sizeof(td_mol_row) == sizeof(kt_u64) * TDM_ROW_WORDS, "td_mol_row is the device row");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
-	const int64_t n_slots = (int64_t)1 << z.table.log2_slots;
-	int64_t blocks = (n_slots + KT_BLOCK - 1) / KT_BLOCK;
-	if (blocks > 1024) blocks = 1024;
-	HIPCHK(c, hipMemsetAsync(z.d_rows, 0, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, c->stream));
-	hipLaunchKernelGGL(td_mol_summary_kernel, dim3((unsigned)blocks), dim3(KT_BLOCK), 0, c->stream, z.table.d_keys, z.table.d_counts, n_slots, z.d_rows);
-	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	HIPCHK(c, hipMemcpy(rows, z.d_rows, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, hipMemcpyDeviceToHost));
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
+	if (summary_rows(c, z.table.d_counts, rows) != TD_OK) return TD_FAIL;
 	if (totals) {
 		kt_u64 t[TDM_TALLY_WORDS];
 		HIPCHK(c, hipMemcpy(t, z.table.d_tallies, sizeof t, hipMemcpyDeviceToHost));
@@ -617,10 +522,8 @@ extern "C" int td_mol_collapse_enable(td_ctx* c)
 	bool has_f = false;
 	for (int j = 0; j < m.S; j++) has_f = has_f || m.seg_type[j] == 'F';
 	if (!has_f) return fail(c, "td_mol_collapse_enable: the model has no 'F' segment: there is no UMI whose neighbours could be collapsed");
-	for (int k = 0; k < TD_MAX_PIPELINE; k++)
-		if (c->slots[k].ticket) return fail(c, "td_mol_collapse_enable: td_submit tickets are outstanding (td_wait them first)");
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
+	if (tickets_outstanding(c)) return fail(c, "td_mol_collapse_enable: td_submit tickets are outstanding (td_wait them first)");
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
 	if (!z.collapse) {
 		bool ok = hipMalloc((void**)&z.d_origin, sizeof(td_mol_origin) << z.table.log2_slots) == hipSuccess &&
 		          hipEventCreate(&z.ev_o0) == hipSuccess && hipEventCreate(&z.ev_o1) == hipSuccess;
@@ -637,11 +540,8 @@ extern "C" int td_mol_collapse_enable(td_ctx* c)
 extern "C" int td_mol_collapse_disable(td_ctx* c)
 {
 	if (!c) return TD_FAIL;
-	TdMolState& z = c->molecules;
-	if (!z.collapse && !z.d_origin && !z.ev_o0 && !z.ev_o1) return TD_OK;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
-	collapse_release(z);
+	if (c->molecules.collapse && wait_compute(c) != TD_OK) return TD_FAIL;
+	collapse_release(c->molecules);   // (off: there is nothing to free)
 	return TD_OK;
 }
 
@@ -654,35 +554,25 @@ int mol_origin_last_kernel_us(td_ctx* c, int32_t* us)
 
 namespace {
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + KT_BLOCK - 1) / KT_BLOCK); }
-
 // Waits for the context's work; tallies[TDM_TALLY_WORDS] down, and the occupied slots' indices in z.d_occ: *n_occ of them, held
 // against the count's own tally of distinct keys
 int collapse_occupied(td_ctx* c, const char* who, kt_u64* tallies, int64_t* n_occ)
 {
 	TdMolState& z = c->molecules;
-	HIPCHK(c, hipSetDevice(c->device));
-	HIPCHK(c, sync_compute(c));
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
 	HIPCHK(c, hipMemcpy(tallies, z.table.d_tallies, sizeof(kt_u64) * TDM_TALLY_WORDS, hipMemcpyDeviceToHost));
 	const int64_t distinct = (int64_t)tallies[TDM_MOLECULES];
 	*n_occ = distinct;
 	if (distinct == 0) return TD_OK;
-	if (distinct > z.cap_occ) {
-		if (z.d_occ) (void)hipFree(z.d_occ);
-		z.d_occ = nullptr; z.cap_occ = 0;
-		HIPCHK(c, hipMalloc((void**)&z.d_occ, sizeof(uint32_t) * (size_t)distinct));
-		z.cap_occ = distinct;
-	}
+	if (ensure(c, &z.d_occ, &z.cap_occ, sizeof(uint32_t) * (size_t)distinct) != TD_OK) return TD_FAIL;
 	const int64_t n_slots = (int64_t)1 << z.table.log2_slots;
 	kt_u64* cursor = z.table.d_tallies + TDM_GATHERED;
-	kt_u64 found = 0;
-	HIPCHK(c, hipMemsetAsync(cursor, 0, sizeof(kt_u64), c->stream));
-	hipLaunchKernelGGL(td_mol_occupied_kernel, dim3(std::min(blocks_for(n_slots), 2048u)), dim3(KT_BLOCK), 0, c->stream,
-	                   (const kt_u64*)z.table.d_keys, n_slots, z.d_occ, distinct, cursor);
-	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	HIPCHK(c, hipMemcpy(&found, cursor, sizeof found, hipMemcpyDeviceToHost));
-	if ((int64_t)found != distinct) return fail(c, "%s: the table holds %lld keys, its tally says %lld", who, (long long)found, (long long)distinct);
+	int64_t found = 0;
+	if (kt_sweep_dense(c, who, "the sweep over the occupied slots failed", cursor, 0, nullptr, 0, nullptr, 0, [&](void*, void*) {
+		    hipLaunchKernelGGL(td_mol_occupied_kernel, dim3(std::min(blocks_for(n_slots), 2048u)), dim3(KT_BLOCK), 0, c->stream,
+		                       (const kt_u64*)z.table.d_keys, n_slots, z.d_occ, distinct, cursor);
+	    }, &found) != TD_OK) return TD_FAIL;
+	if (found != distinct) return fail(c, "%s: the table holds %lld keys, its tally says %lld", who, (long long)found, (long long)distinct);
 	return TD_OK;
 }
 
@@ -696,31 +586,15 @@ int collapse_gather(td_ctx* c, const char* who, const kt_u64* values, int64_t n_
 	if (expect == 0) return TD_OK;
 	std::vector<td_census_entry> v((size_t)expect);
 	std::vector<td_mol_origin> vo((size_t)expect);
-	td_census_entry* d_e = nullptr;
-	td_mol_origin* d_o = nullptr;
 	kt_u64* cursor = z.table.d_tallies + TDM_GATHERED;
-	kt_u64 found = 0;
-	hipError_t e = hipMalloc((void**)&d_e, sizeof(td_census_entry) * (size_t)expect);
-	if (e == hipSuccess) e = hipMalloc((void**)&d_o, sizeof(td_mol_origin) * (size_t)expect);
-	if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof(kt_u64), c->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(td_mol_gather_kernel, dim3(blocks_for(n_occ)), dim3(KT_BLOCK), 0, c->stream, (const kt_u64*)z.table.d_keys, values,
-		                   (const td_mol_origin*)z.d_origin, (const uint32_t*)z.d_occ, n_occ, d_e, d_o, expect, cursor);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	if (e == hipSuccess) e = hipMemcpy(v.data(), d_e, sizeof(td_census_entry) * (size_t)expect, hipMemcpyDeviceToHost);
-	if (e == hipSuccess) e = hipMemcpy(vo.data(), d_o, sizeof(td_mol_origin) * (size_t)expect, hipMemcpyDeviceToHost);
-	if (e == hipSuccess) e = hipMemcpy(&found, cursor, sizeof found, hipMemcpyDeviceToHost);
-	if (d_e) (void)hipFree(d_e);
-	if (d_o) (void)hipFree(d_o);
-	if (e != hipSuccess) return fail(c, "%s: the gather failed: %s", who, hipGetErrorString(e));
-	if ((int64_t)found != expect) return fail(c, "%s: %lld entries were gathered, %lld expected", who, (long long)found, (long long)expect);
-	std::vector<int64_t> order((size_t)expect);
-	for (int64_t i = 0; i < expect; i++) order[(size_t)i] = i;
-	std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return kt_entry_before(v[(size_t)x], v[(size_t)y]); });
-	const int64_t take = std::min<int64_t>(cap, expect);
-	for (int64_t i = 0; i < take; i++) { entries[i] = v[(size_t)order[(size_t)i]]; origins[i] = vo[(size_t)order[(size_t)i]]; }
+	int64_t found = 0;
+	if (kt_sweep_dense(c, who, "the gather failed", cursor, (size_t)expect, v.data(), sizeof(td_census_entry), vo.data(), sizeof(td_mol_origin),
+	                   [&](void* d_e, void* d_o) {
+		    hipLaunchKernelGGL(td_mol_gather_kernel, dim3(blocks_for(n_occ)), dim3(KT_BLOCK), 0, c->stream, (const kt_u64*)z.table.d_keys, values,
+		                       (const td_mol_origin*)z.d_origin, (const uint32_t*)z.d_occ, n_occ, (td_census_entry*)d_e, (td_mol_origin*)d_o, expect, cursor);
+	    }, &found) != TD_OK) return TD_FAIL;
+	if (found != expect) return fail(c, "%s: %lld entries were gathered, %lld expected", who, (long long)found, (long long)expect);
+	mol_emit_ordered(v.data(), vo.data(), expect, cap, entries, origins);
 	return TD_OK;
 }
 
@@ -753,33 +627,6 @@ int collapse_run(td_ctx* c, const char* who, int64_t* n_occ, td_mol_collapse_tot
 	return TD_OK;
 }
 
-// entries with repeated keys (any order) and their origins -> one entry per key, in the order of td_census_get
-void host_add_repeated(const td_census_entry* entries, const td_mol_origin* origins, int64_t n, std::vector<td_census_entry>& v,
-                       std::vector<td_mol_origin>& vo)
-{
-	std::vector<int64_t> order((size_t)n);
-	for (int64_t i = 0; i < n; i++) order[(size_t)i] = i;
-	std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return entries[x].key < entries[y].key; });
-	std::vector<td_census_entry> e;
-	std::vector<td_mol_origin> eo;
-	for (int64_t i : order) {
-		if (entries[i].count <= 0) continue;
-		if (!e.empty() && e.back().key == entries[i].key) e.back().count += entries[i].count;
-		else { e.push_back(entries[i]); eo.push_back(origins[i]); }
-	}
-	std::vector<size_t> by((size_t)e.size());
-	for (size_t i = 0; i < e.size(); i++) by[i] = i;
-	std::sort(by.begin(), by.end(), [&](size_t x, size_t y) { return kt_entry_before(e[x], e[y]); });
-	for (size_t i : by) { v.push_back(e[i]); vo.push_back(eo[i]); }
-}
-
-td_mol_origin* copy_origins(const std::vector<td_mol_origin>& v)
-{
-	td_mol_origin* p = (td_mol_origin*)malloc(sizeof(td_mol_origin) * (v.size() ? v.size() : 1));
-	if (p && !v.empty()) memcpy(p, v.data(), sizeof(td_mol_origin) * v.size());
-	return p;
-}
-
 }   // namespace
 
 extern "C" int td_mol_origins(td_ctx* c, td_census_entry* entries, td_mol_origin* origins, int64_t cap, int64_t* n, td_mol_totals* totals)
@@ -805,14 +652,7 @@ extern "C" int td_mol_collapse_get(td_ctx* c, td_mol_row rows[TD_NUM_BARCODE_BIN
 	int64_t n_occ = 0;
 	td_mol_collapse_totals t{};
 	if (collapse_run(c, "td_mol_collapse_get", &n_occ, &t) != TD_OK) return TD_FAIL;
-	// the count's own sweep over the collapsed counts: a slot that is no root has 0 there and is skipped
-	const int64_t n_slots = (int64_t)1 << z.table.log2_slots;
-	HIPCHK(c, hipMemsetAsync(z.d_rows, 0, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, c->stream));
-	hipLaunchKernelGGL(td_mol_summary_kernel, dim3(std::min(blocks_for(n_slots), 1024u)), dim3(KT_BLOCK), 0, c->stream, (const kt_u64*)z.table.d_keys,
-	                   (const kt_u64*)z.d_collapsed, n_slots, z.d_rows);
-	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	HIPCHK(c, hipMemcpy(rows, z.d_rows, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS, hipMemcpyDeviceToHost));
+	if (summary_rows(c, z.d_collapsed, rows) != TD_OK) return TD_FAIL;   // the count's own sweep over the collapsed counts
 	if (totals) *totals = t;
 	return TD_OK;
 }
@@ -828,96 +668,6 @@ extern "C" int td_mol_collapse_entries(td_ctx* c, td_census_entry* entries, td_m
 	td_mol_collapse_totals t{};
 	if (collapse_run(c, "td_mol_collapse_entries", &n_occ, &t) != TD_OK) return TD_FAIL;
 	if (collapse_gather(c, "td_mol_collapse_entries", z.d_collapsed, n_occ, t.molecules_after, entries, origins, cap, n) != TD_OK) return TD_FAIL;
-	if (totals) *totals = t;
-	return TD_OK;
-}
-
-extern "C" int td_mol_collapse_host(const td_census_entry* entries, const td_mol_origin* origins, int64_t n, td_census_entry** out_entries,
-                                    td_mol_origin** out_origins, int64_t* out_n, td_mol_collapse_totals* totals)
-{
-	if (out_entries) *out_entries = nullptr;
-	if (out_origins) *out_origins = nullptr;
-	if (out_n) *out_n = 0;
-	if (!out_entries || !out_origins || !out_n || n < 0 || (n > 0 && (!entries || !origins))) return fail(nullptr, "td_mol_collapse_host: bad arguments");
-	std::vector<td_census_entry> v;
-	std::vector<td_mol_origin> vo;
-	host_add_repeated(entries, origins, n, v, vo);
-	const size_t N = v.size();
-	std::unordered_map<uint64_t, size_t> at;
-	for (size_t u = 0; u < N; u++) at[v[u].key] = u;
-	// v is in the order of td_census_get: "v comes before u" is "its index is smaller", and the first qualifying neighbour the smallest
-	std::vector<size_t> parent(N);
-	for (size_t u = 0; u < N; u++) {
-		parent[u] = u;
-		const int m = vo[u].n > 0 ? mol_umi_bases(vo[u].fingerprint) : 0;
-		for (int i = 0; i < m; i++)
-			for (uint32_t d = 1; d <= 3; d++) {
-				const auto f = at.find(mol_neighbour_key(v[u].key, vo[u], i, d));
-				if (f == at.end()) continue;
-				const size_t q = f->second;
-				if (v[q].count >= 2 * v[u].count - 1 && q < parent[u]) parent[u] = q;
-			}
-	}
-	// a parent has a smaller index: roots and depths in one pass from the front
-	std::vector<size_t> root(N);
-	std::vector<int64_t> depth(N), collapsed(N, 0);
-	td_mol_collapse_totals t{};
-	for (size_t u = 0; u < N; u++) {
-		root[u] = parent[u] == u ? u : root[parent[u]];
-		depth[u] = parent[u] == u ? 0 : depth[parent[u]] + 1;
-		collapsed[root[u]] += v[u].count;
-		t.longest_chain = std::max(t.longest_chain, depth[u]);
-	}
-	std::vector<size_t> roots;
-	for (size_t u = 0; u < N; u++) if (root[u] == u) roots.push_back(u);
-	std::vector<td_census_entry> r;
-	for (size_t u : roots) r.push_back(td_census_entry{ v[u].key, collapsed[u] });
-	std::vector<size_t> by(r.size());
-	for (size_t i = 0; i < by.size(); i++) by[i] = i;
-	std::sort(by.begin(), by.end(), [&](size_t x, size_t y) { return kt_entry_before(r[x], r[y]); });
-	std::vector<td_census_entry> re;
-	std::vector<td_mol_origin> ro;
-	for (size_t i : by) { re.push_back(r[i]); ro.push_back(vo[roots[i]]); }
-	t.molecules_before = (int64_t)N; t.molecules_after = (int64_t)re.size(); t.absorbed = t.molecules_before - t.molecules_after;
-	td_census_entry* pe = kt_copy_entries(re);
-	td_mol_origin* po = copy_origins(ro);
-	if (!pe || !po) { free(pe); free(po); return fail(nullptr, "td_mol_collapse_host: out of memory"); }
-	*out_entries = pe; *out_origins = po; *out_n = (int64_t)re.size();
-	if (totals) *totals = t;
-	return TD_OK;
-}
-
-extern "C" int td_mol_host_origins(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
-                                   const td_read_result* res, const int8_t* labels, td_census_entry** entries, td_mol_origin** origins, int64_t* n,
-                                   td_mol_totals* totals)
-{
-	if (entries) *entries = nullptr;
-	if (origins) *origins = nullptr;
-	if (n) *n = 0;
-	if (!m || m->S < 1 || m->H < 1 || !m->seg_type || !m->label) return fail(nullptr, "td_mol_host_origins: no model");
-	if (!prefix_ok(prefix_bases)) return fail(nullptr, "td_mol_host_origins: prefix_bases = %d (1..%d supported)", prefix_bases, TD_MOL_MAX_PREFIX);
-	if (!entries || !origins || !n || n_reads < 0 || (n_reads > 0 && (!offs || !res || !labels || !codes))) return fail(nullptr, "td_mol_host_origins: bad arguments");
-	td_mol_totals t{};
-	std::vector<td_census_entry> each;                // one entry of count 1 per counted read
-	std::vector<td_mol_origin> each_o;
-	for (int64_t i = 0; i < n_reads; i++) {
-		uint64_t key = 0;
-		td_mol_origin o{};
-		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key, &o);
-		if (cls == MOL_NOT_ELIGIBLE) continue;
-		t.eligible++;
-		if (cls == MOL_EMPTY) t.skipped_empty++;
-		else if (cls == MOL_HAS_N) t.skipped_n++;
-		else { each.push_back(td_census_entry{ key, 1 }); each_o.push_back(o); t.counted++; }
-	}
-	std::vector<td_census_entry> v;
-	std::vector<td_mol_origin> vo;
-	host_add_repeated(each.data(), each_o.data(), (int64_t)each.size(), v, vo);
-	t.molecules = (int64_t)v.size();
-	td_census_entry* pe = kt_copy_entries(v);
-	td_mol_origin* po = copy_origins(vo);
-	if (!pe || !po) { free(pe); free(po); return fail(nullptr, "td_mol_host_origins: out of memory"); }
-	*entries = pe; *origins = po; *n = (int64_t)v.size();
 	if (totals) *totals = t;
 	return TD_OK;
 }
@@ -938,69 +688,3 @@ int mol_dedup_last_kernel_us(td_ctx* c, int32_t* us)
 	if (!z.dedup) return fail(c, "td_get_option: dedup_kernel_us: dedup is off");
 	return kt_last_kernel_us(c, z.ev_d0, z.ev_d1, us, "td_get_option: dedup_kernel_us: no batch has been judged yet");
 }
-
-extern "C" int td_mol_summarise(const td_census_entry* entries, int64_t n, td_mol_row rows[TD_NUM_BARCODE_BINS])
-{
-	if (!rows || n < 0 || (n > 0 && !entries)) return fail(nullptr, "td_mol_summarise: bad arguments");
-	memset(rows, 0, sizeof(td_mol_row) * TD_NUM_BARCODE_BINS);
-	for (int64_t i = 0; i < n; i++) {
-		if (entries[i].count <= 0) continue;
-		td_mol_row& r = rows[td_mol_key_bin(entries[i].key)];
-		r.reads += entries[i].count;
-		r.molecules++;
-		r.levels[std::min<int64_t>(entries[i].count, TD_MOL_LEVELS) - 1]++;
-	}
-	return TD_OK;
-}
-
-extern "C" int td_mol_host(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
-                           const td_read_result* res, const int8_t* labels, td_census_entry** entries, int64_t* n, td_mol_totals* totals)
-{
-	if (entries) *entries = nullptr;
-	if (n) *n = 0;
-	if (!m || m->S < 1 || m->H < 1 || !m->seg_type || !m->label) return fail(nullptr, "td_mol_host: no model");
-	if (!prefix_ok(prefix_bases)) return fail(nullptr, "td_mol_host: prefix_bases = %d (1..%d supported)", prefix_bases, TD_MOL_MAX_PREFIX);
-	if (!entries || !n || n_reads < 0 || (n_reads > 0 && (!offs || !res || !labels || !codes))) return fail(nullptr, "td_mol_host: bad arguments");
-	td_mol_totals t{};
-	std::vector<uint64_t> keys;
-	for (int64_t i = 0; i < n_reads; i++) {
-		uint64_t key = 0;
-		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key);
-		if (cls == MOL_NOT_ELIGIBLE) continue;
-		t.eligible++;
-		if (cls == MOL_EMPTY) t.skipped_empty++;
-		else if (cls == MOL_HAS_N) t.skipped_n++;
-		else { keys.push_back(key); t.counted++; }
-	}
-	std::vector<td_census_entry> v;
-	kt_tally_keys(keys, v);
-	t.molecules = (int64_t)v.size();
-	if (!(*entries = kt_copy_entries(v))) return fail(nullptr, "td_mol_host: out of memory");
-	*n = (int64_t)v.size();
-	if (totals) *totals = t;
-	return TD_OK;
-}
-
-extern "C" int td_mol_dedup_host(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
-                                 const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate, td_mol_dedup_totals* totals)
-{
-	if (!m || m->S < 1 || m->H < 1 || !m->seg_type || !m->label) return fail(nullptr, "td_mol_dedup_host: no model");
-	if (!prefix_ok(prefix_bases)) return fail(nullptr, "td_mol_dedup_host: prefix_bases = %d (1..%d supported)", prefix_bases, TD_MOL_MAX_PREFIX);
-	if (n_reads < 0 || (n_reads > 0 && (!offs || !res || !labels || !codes || !is_duplicate))) return fail(nullptr, "td_mol_dedup_host: bad arguments");
-	td_mol_dedup_totals t{};
-	std::unordered_set<uint64_t> seen;                // the keys of the reads so far: a read's ordinal is its index, the first one stays
-	for (int64_t i = 0; i < n_reads; i++) {
-		is_duplicate[i] = 0;
-		uint64_t key = 0;
-		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key);
-		if (cls == MOL_NOT_ELIGIBLE) continue;
-		if (cls != MOL_COUNTED) { t.unjudged++; t.kept++; continue; }
-		if (seen.insert(key).second) t.kept++;
-		else { is_duplicate[i] = 1; t.duplicates++; }
-	}
-	if (totals) *totals = t;
-	return TD_OK;
-}
-
-extern "C" uint64_t td_mol_key(int32_t barcode, int32_t fingerprint, uint64_t w, int32_t n) { return mol_key(barcode, fingerprint, w, n); }
-extern "C" int32_t td_mol_key_bin(uint64_t key) { return (int32_t)(key >> 56); }

@@ -214,6 +214,38 @@ def test_a_full_table_of_sixteen_slots_with_overflow(ctx):
     assert ctx.mol_collapse_get()[1] == col[2]
 
 
+def origins_with_cap(ctx, cap):
+    """td_mol_origins itself: (n as it reports it, the first min(cap, n) entries, their origins)"""
+    import ctypes as C
+    from tagdust_amd import lib as tdlib
+    n = C.c_int64(-1)
+    e, o = np.zeros(max(cap, 1), tdlib.CENSUS_ENTRY_DTYPE), np.zeros(max(cap, 1), tdlib.MOL_ORIGIN_DTYPE)
+    ctx._chk(tdlib._mol_lib().td_mol_origins(ctx.h, e.ctypes.data if cap else None, o.ctypes.data if cap else None, cap, C.byref(n), None))
+    return n.value, e[:min(cap, n.value)], o[:min(cap, n.value)]
+
+
+@pytest.mark.parametrize("log2_slots", [10, 4])
+def test_origins_with_a_cap_are_the_head_of_all_of_them(ctx, log2_slots):
+    """td_mol_origins with room for none, for three and for all: the same n each time, the three are the head of the whole, and the
+    whole is td_mol_host_origins over the oracle's labels -- in 16 slots, where the table is full, over the keys the device holds"""
+    c, _ = exact_case(4, extra=12 if log2_slots == 4 else 0)
+    P = 20
+    raw, _ = yardstick(c, P)
+    begin(ctx, c, P, log2_slots)
+    run_batch(ctx, c)
+    n0, e0, o0 = origins_with_cap(ctx, 0)
+    n3, e3, o3 = origins_with_cap(ctx, 3)
+    n, e, o = origins_with_cap(ctx, n0)
+    assert n0 == n3 == n == len(e) and len(e0) == len(o0) == 0 and len(e3) == len(o3) == 3
+    assert np.array_equal(e3, e[:3]) and np.array_equal(o3, o[:3])
+    if log2_slots == 4:
+        assert n == 16 < len(raw[0]) and ctx.mol_origins()[2]["overflow"] > 0
+        held = np.isin(raw[0]["key"], e["key"])
+        assert held.sum() == 16 and np.array_equal(e, raw[0][held]) and np.array_equal(o, raw[1][held])
+    else:
+        assert n == len(raw[0]) == 15 and np.array_equal(e, raw[0]) and np.array_equal(o, raw[1])
+
+
 # ---- paths and state ----
 def test_behind_the_specialised_kernel_and_with_length_classes():
     from oracle import pyoracle

@@ -221,7 +221,7 @@ def test_enable_needs_the_count():
     at = src.index('extern "C" int td_mol_dedup_enable(')
     body = src[at:src.index("\n}\n", at)]
     assert 'if (!z.on) return fail(c, "td_mol_dedup_enable: the molecule count is off (td_mol_enable first)' in body
-    assert "tickets are outstanding" in body
+    assert 'if (tickets_outstanding(c)) return fail(c, "td_mol_dedup_enable: td_submit tickets are outstanding' in body
     lib = tdlib._mol_lib()
     assert lib.td_mol_dedup_enable(None) != 0
     assert b"td_mol_dedup_enable" in lib.td_last_error(None)

@@ -164,7 +164,8 @@ def test_refusals():
 def test_one_table_implementation():
     """the census and the molecule count include the same device header; neither unit has a probe loop or a compaction of its own:
     both count through the header's one tail (kt_wave_add: kt_wave_merge, then kt_probe_add) and read their table through the
-    shared unit's kt_table_entries"""
+    shared unit's kt_table_entries; the key's arithmetic and the cursor pattern are each written once, and the host units are
+    plain C++"""
     csrc = os.path.join(REPO, "tagdust_amd", "csrc")
     header = open(os.path.join(csrc, "td_keytable.h")).read()
     for unit in ("td_census.hip", "td_molecules.hip"):
@@ -176,6 +177,19 @@ def test_one_table_implementation():
     assert "kt_wave_merge(" in tail and "kt_probe_add(" in tail
     assert header.count("atomicCAS") == 1 and "__global__" not in header
     assert open(os.path.join(csrc, "td_keytable.hip")).read().count("__global__") == 1
+    # the key's arithmetic is written once, in the header both sides read; the cursor pattern once, in the device header; and the host
+    # units with the header they include are plain C++
+    shared, host_units = "td_count_key.h", ("td_census_host.cpp", "td_molecules_host.cpp")
+    for unit in ("td_census.hip", "td_molecules.hip", "td_keytable.hip", "td_keytable.h") + host_units:
+        text = open(os.path.join(csrc, unit)).read()
+        assert not re.search(r"\b(kt_mix|mol_key)\s*\([^;{]*\)\s*\{", text), unit
+        assert ("atomicAdd(cursor" in text) == (unit == "td_keytable.h"), unit
+    text = open(os.path.join(csrc, shared)).read()
+    assert len(re.findall(r"\bkt_mix\s*\([^;{]*\)\s*\{", text)) == 1 and len(re.findall(r"\bmol_key\s*\([^;{]*\)\s*\{", text)) == 1
+    for unit in host_units + (shared,):
+        text = open(os.path.join(csrc, unit)).read()
+        assert "hip/" not in text and "__global__" not in text and "atomicAdd(cursor" not in text, unit
+        assert not re.search(r'#include\s*"(td_ctx|td_device|td_keytable)\.h"', text), unit
 
 
 def test_header_symbols_are_exported_and_bound(library):

@@ -1,9 +1,9 @@
 // census_host_check.cpp -- the host side of include/tagdust_census.h (td_census_host, td_census_merge, td_census_key_text) as a
-// stand-alone program, for running it under the host sanitizers: no GPU is used, no Python.
+// stand-alone program, for running it under the host sanitizers: no GPU, no HIP runtime, no Python.
 //
-//   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//       -x hip tagdust_amd/csrc/td_keytable.hip tagdust_amd/csrc/td_census.hip tools/census_host_check.cpp -o /tmp/census_host_check
-//   ASAN_OPTIONS=detect_leaks=0 /tmp/census_host_check        # (the HIP runtime the unit links keeps its own allocations)
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+//       tagdust_amd/csrc/td_census_host.cpp tools/census_host_check.cpp -o /tmp/census_host_check
+//   /tmp/census_host_check                                       # (leak detection stays on)
 //
 // Generated reads (lengths 0..200, N bases, every outcome), generated labels over a B-S-B-R model; the census of each B segment
 // and of -1 is held against a restatement with std::map, the census of two halves merged against the whole, every key through

@@ -1,9 +1,9 @@
 // collapse_host_check.cpp -- td_mol_host_origins and td_mol_collapse_host (include/tagdust_molecules.h) as a stand-alone program, for
-// running them under the host sanitizers: no GPU is used, no Python.
+// running them under the host sanitizers: no GPU, no HIP runtime, no Python.
 //
-//   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//       -x hip tagdust_amd/csrc/td_keytable.hip tagdust_amd/csrc/td_molecules.hip tools/collapse_host_check.cpp -o /tmp/collapse_host_check
-//   ASAN_OPTIONS=detect_leaks=0 /tmp/collapse_host_check         # (the HIP runtime the units link keeps its own allocations)
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+//       tagdust_amd/csrc/td_census_host.cpp tagdust_amd/csrc/td_molecules_host.cpp tools/collapse_host_check.cpp -o /tmp/collapse_host_check
+//   /tmp/collapse_host_check                                     # (leak detection stays on)
 //
 // Generated reads (lengths 0..200, N bases, every outcome, barcodes -1..299, 4-nt fingerprints from a small alphabet so that
 // neighbours meet, some -1), generated labels over an F-B-R-S-R model; for prefixes of 1, 2 and 32 bases td_mol_host_origins is held

@@ -1,6 +1,7 @@
-// host_check.h -- what the stand-alone programs over the host side of the counting units (tools/census_host_check.cpp,
-// molecules_host_check.cpp, dedup_host_check.cpp) share: the message sink td_api.hip would be, a generator, CHECK.  The program
-// defines HOST_CHECK_NAME, its name in the messages, before it includes this.
+// host_check.h -- what the stand-alone programs over the host units of the two counts (tools/census_host_check.cpp,
+// molecules_host_check.cpp, dedup_host_check.cpp, collapse_host_check.cpp) share: the message sink td_api.hip would be, a
+// generator, CHECK.  The program defines HOST_CHECK_NAME, its name in the messages, before it includes this.  tools/host_checks.sh
+// builds and runs them all.
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
@@ -11,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "../tagdust_amd/csrc/td_ctx.h"
+#include "../tagdust_amd/csrc/td_count_key.h"
 
 // td_api.hip is not part of these programs: the message sink of the units under test
 static std::string g_err;
@@ -25,7 +26,6 @@ int fail(td_ctx*, const char* fmt, ...)
 	g_err = buf;
 	return TD_FAIL;
 }
-int default_host_threads() { return 1; }
 
 static uint32_t rnd(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 

@@ -1,11 +1,11 @@
 // molecules_host_check.cpp -- the host side of include/tagdust_molecules.h (td_mol_host, td_mol_summarise, td_mol_key) and
-// td_fingerprint_text of include/tagdust_io.h as a stand-alone program, for running them under the host sanitizers: no GPU is used,
-// no Python.
+// td_fingerprint_text of include/tagdust_io.h as a stand-alone program, for running them under the host sanitizers: no GPU, no HIP
+// runtime, no Python.
 //
-//   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//       -x hip tagdust_amd/csrc/td_keytable.hip tagdust_amd/csrc/td_molecules.hip tagdust_amd/csrc/td_fastq.cpp \
-//       tools/molecules_host_check.cpp -o /tmp/molecules_host_check
-//   ASAN_OPTIONS=detect_leaks=0 /tmp/molecules_host_check        # (the HIP runtime the units link keeps its own allocations)
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+//       tagdust_amd/csrc/td_census_host.cpp tagdust_amd/csrc/td_molecules_host.cpp tagdust_amd/csrc/td_fastq.cpp \
+//       tools/molecules_host_check.cpp -o /tmp/molecules_host_check -lpthread
+//   /tmp/molecules_host_check                                    # (leak detection stays on)
 //
 // Generated reads (lengths 0..200, N bases, every outcome, barcodes -1..299, fingerprints of any sign), generated labels over an
 // F-B-R-S-R model; the count for prefixes of 1, 7, 16, 31 and 32 bases is held against a restatement with std::map, the summary
