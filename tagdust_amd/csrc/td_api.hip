@@ -462,35 +462,6 @@ extern "C" int td_set_params(td_ctx* c, float threshold, int32_t minlen, int32_t
 // (td_batch_upload / td_run / td_batch_download) work on slot 0; td_submit / td_wait rotate over `pipeline_depth` slots
 // with the copies on their own streams, so that the upload of batch k+1 and the download of batch k-1 overlap the decode
 // kernel of batch k.  One HBM workspace serves all slots (decode kernels are serialised on the compute stream).
-int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
-void make_layout(TdWsLayout& L, int S, int H, int C, int lmax, int max_ncol)
-{
-	int64_t o = 0;
-	L.codes = o; o = align256(o + (int64_t)(lmax + 2) * TD_WAVE);
-	L.sb = o;    o = align256(o + (int64_t)(S + 1) * (lmax + 2) * TD_WAVE * 4);
-	L.sf = o;    o = align256(o + (int64_t)(S + 1) * (lmax + 2) * TD_WAVE * 4);
-	L.bw = o;    o = align256(o + (int64_t)C * lmax * TD_WAVE * 8);
-	L.fwrow = o; o = align256(o + (int64_t)max_ncol * TD_WAVE * 8);
-	L.dp = o;    o = align256(o + (int64_t)lmax * H * TD_WAVE * 4);
-	L.path = o;  o = align256(o + (int64_t)lmax * H * TD_WAVE);
-	L.acc = o;   o = align256(o + (int64_t)H * TD_WAVE * 4);
-	L.total = o; o = align256(o + (int64_t)H * TD_WAVE * 4);
-	L.dust = o;  o = align256(o + (int64_t)64 * TD_WAVE);
-	L.slot_bytes = o;
-}
-
-OutLayout out_layout(int64_t n_tiles, int lmax, int nw1)
-{
-	OutLayout o;
-	o.soa_stride = n_tiles * TD_WAVE * 4;      // a multiple of 256
-	int64_t p = 8 * o.soa_stride;
-	o.keep = p; p = align256(p + n_tiles * nw1 * TD_WAVE * 4);
-	o.labels = p; p = align256(p + n_tiles * (int64_t)(lmax + 1) * TD_WAVE);
-	o.total = p;
-	return o;
-}
-
 // is this host pointer page-locked (hipHostMalloc / hipHostRegister)?  Then the DMA engines can use it directly.
 static bool is_pinned(const void* p)
 {
@@ -531,109 +502,69 @@ static void slot_release(TdSlot& s)
 	s = TdSlot();
 }
 
-// Size the shared workspace for a batch with this geometry.  Growing it (or switching the kernel to the clamped logsum)
-// waits for the decode kernels in flight first.
+// the device's free memory, when the workspace plan asks for it
+static int hbm_free(td_ctx* c, size_t& free_b)
+{
+	size_t total_b = 0;
+	HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+	return TD_OK;
+}
+
+// Size the shared workspace for a batch with this geometry: td_batch_plan.cpp decides, this applies the decision and does what
+// needs the device.  Growing the workspace (or switching the kernel to the clamped logsum) waits for the decode kernels in flight first.
 static int ensure_workspace(td_ctx* c, TdSlot& s)
 {
-	make_layout(s.lay, c->dev.h.S, c->dev.h.H, c->dev.h.C, s.lmax, c->dev.h.max_ncol);
-	int64_t slot_bytes = s.lay.slot_bytes;
 	if (spec_before_batch(c, s.lmax) != TD_OK) return TD_FAIL;
+	make_layout(s.lay, c->dev.h.S, c->dev.h.H, c->dev.h.C, s.lmax, c->dev.h.max_ncol);
+	TdWsRequest rq;
+	rq.small_slot_bytes = rq.big_slot_bytes = s.lay.slot_bytes;
 	if (c->spec.ready) {
 		td_spec_layout(s.slay, c->spec.plan, s.n_long > 0 ? s.lmax_small : s.lmax);   // the geometry of the many
 		td_spec_layout(s.slay_big, c->spec.plan, s.lmax);
-		slot_bytes = s.slay.slot_bytes;
+		rq.small_slot_bytes = s.slay.slot_bytes; rq.big_slot_bytes = s.slay_big.slot_bytes;
 	}
-	// wave slots: enough to fill the chip (2 workgroups of 4 waves per CU share the LDS), bounded by HBM
-	const int wpb = (c->spec.ready ? c->spec.block : td_kernel_block_threads()) / TD_WAVE;
-	int64_t want = (int64_t)c->n_cu * (c->spec.ready ? c->spec.waves_per_cu : 2 * wpb);
-	if (c->wave_slots_forced > 0) want = c->wave_slots_forced;
-	int64_t slots = want;
-	if (slots > s.n_tiles) slots = s.n_tiles;
-	if (slots < 1) slots = 1;
-	slots = (slots + wpb - 1) / wpb * wpb; // whole workgroups
-	// length classes: the long tiles need a slot each of the big geometry (they are the first tiles the lowest slots take); when
-	// they are too many for that to pay -- more than a quarter of the slots -- the batch keeps one geometry
-	s.n_big = 0;
-	int64_t big_extra = 0;       // bytes the big slots take beyond a small slot each
-	if (c->spec.ready && s.n_long > 0) {
-		if ((int64_t)s.n_long * 4 <= slots) {
-			s.n_big = s.n_long;
-			big_extra = (int64_t)s.n_big * (s.slay_big.slot_bytes - s.slay.slot_bytes);
-		} else {
-			s.n_long = 0; s.lmax_small = s.lmax;
-			s.slay = s.slay_big;
-			slot_bytes = s.slay.slot_bytes;
-		}
-	}
-	uint8_t*& ws = s.wsi ? c->d_ws2 : c->d_ws;
-	size_t& cap_ws = s.wsi ? c->cap_ws2 : c->cap_ws;
-	// Pipelined batches overlap their launches on two streams with a workspace each.  When HBM cannot hold two workspaces of the
-	// full wave-slot count (config 5: 42 MiB per slot, 172 GB for 4096 slots) each launch gets half the slots instead -- two
-	// launches side by side still fill every SIMD, and the machine stays busy while one launch's slowest waves finish.
-	if (s.pipelined && c->overlap && c->pipeline_depth > 1 && c->spec.ready && !c->half_slots) {
-		size_t free_b = 0, total_b = 0;
-		HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-		const double avail = (double)free_b + (double)c->cap_ws + (double)c->cap_ws2;
-		if (2.0 * (double)(slots * slot_bytes + big_extra) > 0.8 * avail && (double)(slots * slot_bytes + big_extra) <= 0.8 * avail) c->half_slots = true;
-	}
-	if (c->half_slots && s.pipelined) {
-		int64_t half = (slots / 2 + wpb - 1) / wpb * wpb;
-		if (half < wpb) half = wpb;
-		if (half >= s.n_big * 4 || s.n_big == 0) slots = half;
-	}
-	if ((size_t)(slots * slot_bytes + big_extra) > cap_ws) {
-		size_t free_b = 0, total_b = 0;
-		HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-		if (s.wsi == 1 && (double)(slots * slot_bytes + big_extra) > (c->half_slots ? 0.6 : 0.4) * (double)(free_b + cap_ws)) {
-			// HBM cannot hold a second workspace of this size beside the first: this and all later batches run on the first stream
-			c->overlap = 0;
-			s.wsi = 0; s.cs = c->stream;
-			return ensure_workspace(c, s);
-		}
-		const int64_t budget = (int64_t)((double)(free_b + cap_ws) * 0.85);
-		if (slots * slot_bytes + big_extra > budget) {
-			if (big_extra > budget / 2) {   // not even the long tiles' slots fit beside a useful number of others: one geometry
-				s.n_long = 0; s.lmax_small = s.lmax; s.n_big = 0; big_extra = 0;
-				s.slay = s.slay_big;
-				slot_bytes = s.slay.slot_bytes;
+	rq.n_tiles = s.n_tiles; rq.n_long = s.n_long; rq.lmax_small = s.lmax_small; rq.lmax = s.lmax;
+	rq.wpb = (c->spec.ready ? c->spec.block : td_kernel_block_threads()) / TD_WAVE;
+	rq.want_slots = c->wave_slots_forced > 0 ? c->wave_slots_forced : (int64_t)c->n_cu * (c->spec.ready ? c->spec.waves_per_cu : 2 * rq.wpb);
+	rq.spec_ready = c->spec.ready; rq.pipelined = s.pipelined; rq.overlap = c->overlap; rq.pipeline_depth = c->pipeline_depth;
+	rq.half_slots = c->half_slots; rq.wsi = s.wsi;
+	rq.cap_ws = c->cap_ws; rq.cap_ws2 = c->cap_ws2; rq.ws_candidates = c->ws_candidates;
+	const TdWsPlan p = plan_workspace(rq, [](void* ctx, size_t* free_b) { return hbm_free((td_ctx*)ctx, *free_b) == TD_OK; }, c);
+	c->half_slots = p.half_slots;
+	if (p.overlap_given_up) { c->overlap = 0; s.wsi = 0; s.cs = c->stream; }
+	s.n_long = p.n_long; s.lmax_small = p.lmax_small; s.n_big = p.n_big;
+	if (p.one_geometry) s.slay = s.slay_big;
+	if (p.query_failed) return TD_FAIL;   // (hbm_free left the message)
+	if (p.no_fit) return fail(c, "td_batch_upload: workspace of %lld bytes per wave does not fit in HBM", (long long)p.ws_slot_bytes);
+	if (p.alloc_bytes > 0) {
+		uint8_t*& ws = s.wsi ? c->d_ws2 : c->d_ws;
+		size_t& cap_ws = s.wsi ? c->cap_ws2 : c->cap_ws;
+		const size_t need = p.alloc_bytes;
+		HIPCHK(c, sync_compute(c));
+		if (p.n_candidates <= 1) {
+			if (ensure(c, &ws, &cap_ws, need) != TD_OK) return TD_FAIL;
+		} else {   // candidates that exist side by side: a memory-side probe runs over each, the fastest stays, the others are freed
+			if (ws) { HIPCHK(c, hipFree(ws)); ws = nullptr; cap_ws = 0; }
+			uint8_t* cand[4] = { nullptr, nullptr, nullptr, nullptr };
+			float ms[4] = { 0, 0, 0, 0 };
+			int n_ok = 0, best = -1;
+			for (int k = 0; k < p.n_candidates; k++) {
+				if (hipMalloc((void**)&cand[k], need) != hipSuccess) { (void)hipGetLastError(); cand[k] = nullptr; break; }
+				n_ok++;
 			}
-			slots = (budget - big_extra) / slot_bytes / wpb * wpb;
-		}
-		if (slots < wpb || slots < s.n_big) return fail(c, "td_batch_upload: workspace of %lld bytes per wave does not fit in HBM", (long long)slot_bytes);
-		if ((size_t)(slots * slot_bytes + big_extra) > cap_ws) {
-			HIPCHK(c, sync_compute(c));
-			const size_t need = (size_t)(slots * slot_bytes + big_extra);
-			// Where the driver places a large allocation decides how fast the kernel's spill stream runs over it (up to
-			// 9 % on one box).  A large workspace is therefore chosen among a few candidates that
-			// exist side by side: a memory-side probe runs over each, the fastest stays, the others are freed.
-			int n_cand = c->ws_candidates;
-			if (n_cand > 4) n_cand = 4;
-			if (need < ((size_t)2 << 30) || (double)need * n_cand > 0.6 * (double)(free_b + cap_ws)) n_cand = 1;
-			if (n_cand <= 1) {
-				if (ensure(c, &ws, &cap_ws, need) != TD_OK) return TD_FAIL;
-			} else {
-				if (ws) { HIPCHK(c, hipFree(ws)); ws = nullptr; cap_ws = 0; }
-				uint8_t* cand[4] = { nullptr, nullptr, nullptr, nullptr };
-				float ms[4] = { 0, 0, 0, 0 };
-				int n_ok = 0, best = -1;
-				for (int k = 0; k < n_cand; k++) {
-					if (hipMalloc((void**)&cand[k], need) != hipSuccess) { (void)hipGetLastError(); cand[k] = nullptr; break; }
-					n_ok++;
-				}
-				for (int k = 0; k < n_ok; k++) {
-					if (td_ws_probe(cand[k], slot_bytes, (int)slots, c->stream, &ms[k]) != hipSuccess) ms[k] = 1e30f;
-					if (best < 0 || ms[k] < ms[best]) best = k;
-				}
-				if (best < 0) return fail(c, "td_batch_upload: workspace of %zu bytes could not be allocated", need);
-				if (c->debug_alloc) fprintf(stderr, "tagdust_hip: workspace candidates: probe %.2f %.2f %.2f %.2f ms -> #%d\n", ms[0], ms[1], ms[2], ms[3], best);
-				for (int k = 0; k < n_ok; k++) if (k != best) (void)hipFree(cand[k]);
-				ws = cand[best]; cap_ws = need;
+			for (int k = 0; k < n_ok; k++) {
+				if (td_ws_probe(cand[k], p.ws_slot_bytes, p.n_wave_slots, c->stream, &ms[k]) != hipSuccess) ms[k] = 1e30f;
+				if (best < 0 || ms[k] < ms[best]) best = k;
 			}
+			if (best < 0) return fail(c, "td_batch_upload: workspace of %zu bytes could not be allocated", need);
+			if (c->debug_alloc) fprintf(stderr, "tagdust_hip: workspace candidates: probe %.2f %.2f %.2f %.2f ms -> #%d\n", ms[0], ms[1], ms[2], ms[3], best);
+			for (int k = 0; k < n_ok; k++) if (k != best) (void)hipFree(cand[k]);
+			ws = cand[best]; cap_ws = need;
 		}
 	}
-	s.n_wave_slots = (int32_t)slots;
-	s.ws_slot_bytes = slot_bytes;
-	s.ws_bytes = slots * slot_bytes + big_extra;
+	s.n_wave_slots = p.n_wave_slots;
+	s.ws_slot_bytes = p.ws_slot_bytes;
+	s.ws_bytes = p.ws_bytes;
 	return TD_OK;
 }
 
@@ -663,29 +594,9 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 	if (bad >= 0) return fail(c, "td_batch_upload: read %lld has length %lld", (long long)bad, (long long)(offs[bad + 1] - offs[bad]));
 	const int64_t n_bases = n > 0 ? offs[n] - base : 0;
 	const int64_t n_tiles = (n + TD_WAVE - 1) / TD_WAVE;
-	// Length classes.  The reads are sorted by length on the device, so tile t holds the reads ranked 64 t .. 64 t + 63: from the
-	// histogram of the lengths, the longest read of every tile.  When the batch's longest read is at least half as long again as
-	// the reads at the 99 % mark, the tiles beyond that mark (n_long of them) get wave slots of their own geometry and the rest
-	// keeps the geometry of the many -- one 1000-base read among 150-base reads no longer costs every slot 6.6 times the memory.
-	s.n_long = 0; s.lmax_small = lmax;
-	if (c->spec.ready && with_workspace && lmin != lmax && n_tiles >= 64 && c->length_classes) {
-		std::vector<int64_t> hist((size_t)lmax + 2, 0);
-		for (int64_t i = 0; i < n; i++) hist[(size_t)(offs[i + 1] - offs[i])]++;
-		// rank of the last read of the tile at the 99 % mark, its length, and the tiles that hold anything longer
-		const int64_t t99 = n_tiles - 1 - (n_tiles + 99) / 100;
-		const int64_t rank = t99 * TD_WAVE + TD_WAVE - 1;
-		int64_t acc = 0;
-		int l99 = lmax;
-		for (int l = 0; l <= lmax; l++) { acc += hist[(size_t)l]; if (acc > rank) { l99 = l; break; } }
-		if (l99 < 1) l99 = 1;
-		if ((int64_t)lmax * 2 >= (int64_t)l99 * 3) {
-			int64_t upto = 0;   // reads of length <= l99
-			for (int l = 0; l <= l99; l++) upto += hist[(size_t)l];
-			const int64_t first_long_tile = upto / TD_WAVE;                 // (a tile that mixes both kinds counts as long)
-			s.n_long = (int32_t)(n_tiles - first_long_tile);
-			s.lmax_small = l99;
-		}
-	}
+	// length classes (td_batch_plan.cpp): do the batch's longest tiles get wave slots of their own geometry?
+	const TdLengthClasses lc = plan_length_classes(offs, n, lmin, lmax, n_tiles, c->spec.ready && with_workspace && c->length_classes);
+	s.n_long = lc.n_long; s.lmax_small = lc.lmax_small;
 	const int nw2 = (lmax + 15) / 16, nw1 = (lmax + 31) / 32;
 	const bool sorted = n > 0 && lmin != lmax;
 

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/tagdust_hip.h"
 #include "td_device.h"
+#include "td_batch_plan.h"
 #include "td_jit.h"
 #include "td_stage.h"
 #include "td_host_inner.h"
@@ -284,12 +285,6 @@ extern "C" TD_HIDDEN hipError_t td_launch_decode_multi(const TdKernelArgs* d_arg
 
 // td_api.hip
 TD_HIDDEN double wall_ms();
-TD_HIDDEN int64_t align256(int64_t v);
-TD_HIDDEN void make_layout(TdWsLayout& L, int S, int H, int C, int lmax, int max_ncol);
-// output block of the decode kernels: eight SoA arrays over n_tiles*64 reads (f, b, r, bar, q, type, barcode, finger: equal
-// strides), then keep words, then labels -- all in device order
-struct OutLayout { int64_t soa_stride, keep, labels, total; };
-TD_HIDDEN OutLayout out_layout(int64_t n_tiles, int lmax, int nw1);
 
 // the output pointers of a launch's argument struct into such a block (out_labels where the struct has one: run_rna_dust has none)
 template <typename Args> static auto point_labels(Args& a, int8_t* p, int) -> decltype((void)a.out_labels) { a.out_labels = p; }

@@ -1,6 +1,7 @@
-"""The plain C++ host units of the two counts (tagdust_amd/csrc/td_census_host.cpp, td_molecules_host.cpp) build with the host
-compiler alone -- no hipcc, no HIP header, no HIP runtime -- and the stand-alone programs over them (tools/*_host_check.cpp, the
-ones tools/host_checks.sh runs under the sanitizers) agree with their restatements.  No GPU, no sanitizer here."""
+"""The plain C++ host units of the two counts (tagdust_amd/csrc/td_census_host.cpp, td_molecules_host.cpp) and of the batch geometry
+(td_batch_plan.cpp) build with the host compiler alone -- no hipcc, no HIP header, no HIP runtime -- and the stand-alone programs
+over them (tools/*_host_check.cpp, the ones tools/host_checks.sh runs under the sanitizers) agree with their restatements.  No GPU,
+no sanitizer here."""
 import os
 import shutil
 import subprocess
@@ -10,8 +11,11 @@ import pytest
 from conftest import REPO
 
 CSRC = os.path.join(REPO, "tagdust_amd", "csrc")
-# the program, and what it links beside the two host units (td_fingerprint_text is td_fastq.cpp's)
-PROGRAMS = [("census_host_check", []), ("molecules_host_check", ["td_fastq.cpp"]), ("dedup_host_check", []), ("collapse_host_check", [])]
+# the program, and what it links beside the two host units of the counts (td_fingerprint_text is td_fastq.cpp's); the batch plan's
+# links its own unit alone
+COUNT_UNITS = ("td_census_host.cpp", "td_molecules_host.cpp")
+PROGRAMS = [("census_host_check", []), ("molecules_host_check", ["td_fastq.cpp"]), ("dedup_host_check", []), ("collapse_host_check", []),
+            ("batch_plan_host_check", ["td_batch_plan.cpp"])]
 
 
 def host_compiler():
@@ -41,11 +45,11 @@ def compiled(cxx, as_cxx, source, out_dir):
 
 @pytest.fixture(scope="module")
 def host_objects(tmp_path_factory):
-    """the two host units, compiled once for the four programs"""
+    """the two host units of the counts, compiled once for the four programs over them"""
     cxx, as_cxx = host_compiler()
     assert cxx, "no host C++ compiler: set CXX, or install g++"
     d = str(tmp_path_factory.mktemp("host_units"))
-    return [compiled(cxx, as_cxx, os.path.join(CSRC, u), d) for u in ("td_census_host.cpp", "td_molecules_host.cpp")]
+    return [compiled(cxx, as_cxx, os.path.join(CSRC, u), d) for u in COUNT_UNITS]
 
 
 @pytest.mark.parametrize("name,extra", PROGRAMS, ids=[p[0] for p in PROGRAMS])
@@ -54,5 +58,5 @@ def test_the_host_units_build_and_agree_without_hip(tmp_path, host_objects, name
     d = str(tmp_path)
     objs = [compiled(cxx, as_cxx, s, d) for s in [os.path.join(CSRC, e) for e in extra] + [os.path.join(REPO, "tools", name + ".cpp")]]
     exe = os.path.join(d, name)
-    run(cxx + host_objects + objs + ["-o", exe, "-lpthread"])
+    run(cxx + ([] if name == "batch_plan_host_check" else host_objects) + objs + ["-o", exe, "-lpthread"])
     assert (name + ": ok") in run([exe]).splitlines()
