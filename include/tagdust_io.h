@@ -107,6 +107,11 @@ typedef struct td_stream_stats {
 int td_format_q(float q, char* buf);
 int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* arch, const char* out_prefix,
                   const td_stream_opts* opts, td_stream_stats* stats);
+/* td_stream_run without its third stage: the same reader and the same td_submit / td_wait of every batch on `ctx`
+ * (TD_MODE_GET_LABEL), no writer and no output file.  What the context accumulates is the result: its counters, a census, the
+ * molecule count -- the survey in front of td_mol_dedup_freeze (tagdust_molecules.h).  Input files and errors as td_stream_run's;
+ * stats: bytes_out and write_s stay 0. */
+int td_stream_survey(td_ctx* ctx, const char* in_path, const td_stream_opts* opts, td_stream_stats* stats);
 /* ---- several input files of one run, several devices (BASELINE configs[3]: the CASAVA three-read shape) ----
  * The controller's loop for paired / multi-read data (hmm_controller_multiple, src/barcode_hmm.c:244-385): the next batch_reads
  * records of EVERY input file (the files must hold the same reads in the same order: equal record counts, :257-268, and the first

@@ -47,8 +47,9 @@
  * molecules being the keys that entered the table since the reset.  The result is a function of the context's sequence of reads
  * alone: not of how it was cut into batches, of td_run or td_submit, of the tickets in flight or of the kernel variant.  Limits:
  * the 56-bit collision above (two molecules that collide lose one read); and which keys overflow in a nearly full table depends on
- * the claim order within a batch, as it does for the count.  Dedup matches exactly, with or without the collapse below; a molecule
- * split over two contexts survives in both (each has its own table).
+ * the claim order within a batch, as it does for the count.  Dedup matches exactly, with or without the collapse below (the frozen
+ * state further down, DESIGN.md section 17, is the second pass that does not); a molecule split over two contexts survives in both
+ * (each has its own table).
  *
  * Collapse (td_mol_collapse_enable) -- UMIs one mismatch apart counted as one molecule -- reads the count's table and changes
  * nothing in it.  The reference has nothing of the kind; this is the definition, held bit for bit by the device path and by
@@ -74,7 +75,36 @@
  * The result is a function of the set of (key, count, origin) alone: not of slot positions, batching, tickets in flight or kernel
  * variant.  Limits: distance one only; the UMI only (an error in the prefix still makes a new molecule); the leading bases of a
  * UMI of more than 12 are not in the fingerprint and take no part; the tree can differ from UMI-tools' breadth-first clusters, in
- * which the largest root claims a shared descendant -- here the child chooses; dedup is not changed by it.
+ * which the largest root claims a shared descendant -- here the child chooses; dedup is not changed by it (unless the context is
+ * frozen: below, and DESIGN.md section 17).
+ *
+ * Survey, freeze, replay (td_mol_dedup_freeze) -- one read per COLLAPSED molecule.  Which read of a tree survives is only known once
+ * the counts are final, so it takes a second pass over the same reads.  The reference has nothing of the kind; this is the
+ * definition, held by the device path and by td_mol_dedup_collapsed_host alike.  A context with count, dedup and collapse on is in
+ * one of two states:
+ *   - survey: everything above, unchanged -- the count, the origins, the first ordinals, the exact marks;
+ *   - frozen, entered by td_mol_dedup_freeze: it waits for the context's queued work, runs the collapse as td_mol_collapse_get does,
+ *     computes for every molecule u   keeper(u) = first(root(u)),   the first ordinal of the ROOT'S OWN KEY -- not the minimum over
+ *     the tree --, zeroes dedup's three tallies and sets the ordinal counter to 0.
+ * While frozen a TD_MODE_GET_LABEL batch changes nothing in the table: keys, counts, origins, first ordinals and the count's totals
+ * (eligible .. molecules) stay as the survey left them, and td_mol_get, td_mol_entries, td_mol_origins, td_mol_collapse_get and
+ * td_mol_collapse_entries return the survey's results as often as they are asked.  A read's ordinal is the number of reads
+ * submitted since the freeze plus its index in its batch in the caller's order, the rule of the survey.  The batch is replayed:
+ *   - an eligible read whose key the table holds is a duplicate (TD_EXTRACT_DUPLICATE, every other field as decoded) when
+ *     keeper(its key) != its ordinal, and kept otherwise;
+ *   - an eligible read with no key in the table -- skipped_empty, skipped_n, a key that overflowed in the survey, a key never
+ *     surveyed -- is kept and tallied `unjudged`;
+ *   - td_mol_dedup_get returns the replay's tallies.
+ * td_mol_dedup_freeze called again recomputes the keepers and restarts the ordinals.  td_mol_reset ends the frozen state with an
+ * empty table; so do td_mol_disable, td_mol_dedup_disable, td_mol_collapse_disable and a new model.  When the same reads are
+ * replayed in the same order:
+ *   - the one written read of a tree is the first read of the input that carries the root's barcode, fingerprint and prefix, so
+ *     every written judged read spells an entry of td_mol_collapse_entries and its ";FP:" is the UMI the table reports;
+ *   - eligible(survey) == kept + duplicates      and      kept == molecules_after + skipped_empty + skipped_n + overflow.
+ * The result is a function of the surveyed sequence of reads and the replayed sequence of reads alone: not of either pass's
+ * batching, of td_run or td_submit, of the tickets in flight, of length classes or of the kernel variant.  Limits: those of dedup
+ * and of the collapse; the input is decoded twice; replaying other reads, or the same in another order, is defined (the rule
+ * above) but keeps no longer one read per molecule.
  */
 #ifndef TAGDUST_MOLECULES_H
 #define TAGDUST_MOLECULES_H
@@ -154,6 +184,16 @@ int td_mol_host_origins    (const td_model_desc* model, int32_t prefix_bases, co
  * multi-device path, and the yardstick of the device.  *out_entries is freed with td_census_free, *out_origins with free. */
 int td_mol_collapse_host   (const td_census_entry* entries, const td_mol_origin* origins, int64_t n,
                             td_census_entry** out_entries, td_mol_origin** out_origins, int64_t* out_n, td_mol_collapse_totals* totals);
+/* The frozen state, see above.  td_mol_dedup_freeze: TD_FAIL with a message when the count, dedup or the collapse is off or td_submit
+ * tickets are outstanding.  The first call allocates 8 more bytes per slot (the keepers); whatever frees dedup's or the collapse's
+ * arrays frees them.  totals (may be NULL): the collapse's, as td_mol_collapse_get gives them. */
+int td_mol_dedup_freeze    (td_ctx* ctx, td_mol_collapse_totals* totals);
+/* the same decision from host arrays, no GPU: the given sequence is surveyed and the same sequence replayed, read i has ordinal i;
+ * is_duplicate[i] = 1 for a duplicate, else 0.  For hosts without a GPU and as the yardstick of the device path.  Arguments as
+ * td_mol_dedup_host takes them.  Never overflows.  totals and collapse_totals may be NULL. */
+int td_mol_dedup_collapsed_host(const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs,
+                                int64_t n_reads, const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate,
+                                td_mol_dedup_totals* totals, td_mol_collapse_totals* collapse_totals);
 /* the key of a counted read: its record's barcode and fingerprint, its prefix word w of n bases (1..32) */
 uint64_t td_mol_key(int32_t barcode, int32_t fingerprint, uint64_t w, int32_t n);
 int32_t  td_mol_key_bin(uint64_t key);              /* the barcode bin a key belongs to */

@@ -79,6 +79,9 @@ typedef struct td_run_opts {
 	                                    it); one input file, one device */
 	int32_t  collapse_umis;          /* --collapse-umis: fingerprints one mismatch apart are counted as one molecule (tagdust_molecules.h,
 	                                    td_mol_collapse_enable).  Implies --molecules (the parser sets it); refused without an F segment */
+	int32_t  dedup_collapsed;        /* --dedup-collapsed: one read per COLLAPSED molecule is written (tagdust_molecules.h, td_mol_dedup_freeze):
+	                                    the input file is read twice -- td_stream_survey, the freeze, td_stream_run.  Implies --dedup,
+	                                    --collapse-umis and --molecules (the parser sets them); refused wherever they are and for the input "-" */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -106,7 +109,10 @@ const char* td_run_version(void);
  * would survive twice -- and adds two lines, "# written" and "# duplicates removed", to <out>_molecules.txt and nothing to the
  * log, the _un file or the counts; --collapse-umis implies --molecules, is refused wherever that is and for an architecture without
  * an F segment, may be given with --dedup, which still matches exactly, and adds three lines -- "# UMI collapse", "# molecules
- * after collapse", "# absorbed" -- and two columns behind "10+", "collapsed" and "duplication_collapsed", to <out>_molecules.txt), the
+ * after collapse", "# absorbed" -- and two columns behind "10+", "collapsed" and "duplication_collapsed", to <out>_molecules.txt;
+ * --dedup-collapsed implies --dedup, --collapse-umis and --molecules, is refused wherever they are and for the input "-" -- stdin
+ * cannot be read twice --, gives "# written" and "# duplicates removed" the replay's numbers and adds one line, "# dedup", in front
+ * of them, while every other output of the run reports the second pass alone), the
  * multiread rule (interface.c:441-450: DUST and -ref off, with a warning, when the command line's architecture has two or more
  * R segments).  What depends on the arch file's choice is decided again by td_run_execute once the choice is made. */
 typedef struct td_run_plan_t td_run_plan_t;   /* (the function below has the plain name) */
@@ -150,6 +156,8 @@ typedef struct td_run_report {
 	td_mol_collapse_totals collapse_totals;   /* --collapse-umis: molecules before and after, absorbed, the longest chain */
 	td_mol_row* molecules_collapsed;          /* --collapse-umis: [TD_NUM_BARCODE_BINS] the rows from the collapsed counts (NULL without the
 	                                             option): td_mol_collapse_get's, or td_mol_summarise of td_mol_collapse_host over the devices' td_mol_origins */
+	int32_t  dedup_collapsed;                 /* 1: the duplicates removed are those of the collapsed molecules (--dedup-collapsed) */
+	double   survey_s;                        /* --dedup-collapsed: seconds of the first pass, td_stream_survey and the freeze (inside stream_s) */
 } td_run_report;
 /* In the controller's order: architectures per file, statistics over each file's head, thresholds, models, the run, the log.
  * A failure before the first batch leaves no output files behind; one during the run leaves them as they are and says so.  The

@@ -371,6 +371,8 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	if (!strcmp(name, "molecules_kernel_us")) return mol_last_kernel_us(c, value);
 	if (!strcmp(name, "dedup_active")) { *value = c->molecules.dedup; return TD_OK; }
 	if (!strcmp(name, "dedup_kernel_us")) return mol_dedup_last_kernel_us(c, value);   // the two passes of the last batch
+	if (!strcmp(name, "dedup_frozen")) { *value = c->molecules.frozen; return TD_OK; }   // td_mol_dedup_freeze: batches are replayed
+	if (!strcmp(name, "dedup_replay_kernel_us")) return mol_replay_last_kernel_us(c, value);   // the replay kernel of the last batch
 	if (!strcmp(name, "collapse_active")) { *value = c->molecules.collapse; return TD_OK; }
 	if (!strcmp(name, "collapse_origin_kernel_us")) return mol_origin_last_kernel_us(c, value);   // the origin pass of the last batch
 	if (!strcmp(name, "overlap_active")) {

@@ -40,6 +40,11 @@ struct TdMolState {
 	size_t cap_occ = 0;
 	uint32_t* d_parent = nullptr;             // [2^log2_slots] the slot of every occupied slot's parent, its own for a root
 	unsigned long long* d_collapsed = nullptr;   // [2^log2_slots] the count of a root's tree, 0 for every other slot
+	// the frozen state (td_mol_dedup_freeze; count, dedup and collapse all on): the table is read-only and every batch is replayed
+	// against keeper[]; the first freeze allocates it and the two events, whatever frees dedup's or the collapse's arrays frees them
+	bool frozen = false;
+	unsigned long long* d_keeper = nullptr;   // [2^log2_slots] of an occupied slot: the first ordinal of its root's own key
+	hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;   // around the replay kernel of the last batch (option "dedup_replay_kernel_us")
 };
 
 struct TdMolArgs {
@@ -61,17 +66,22 @@ struct TdMolArgs {
 	int64_t ordinal_base;                     // the ordinal of the batch's first read in the caller's order
 	// the collapse's origin pass alone
 	td_mol_origin* origin;                    // [slot_mask + 1] (not __restrict__: lanes of other waves write the same words)
+	// the replay kernel alone (with read_at and ordinal_base)
+	const unsigned long long* __restrict__ keeper;   // [slot_mask + 1] the ordinal of the one read that a slot's tree keeps
 };
 
 // A decoded slot's launches, queued on its compute stream behind the decode launch (td_api.hip calls it last in slot_decode while
-// the count is on): the count, the collapse's origin pass, dedup's two passes, each when it is on.  Dedup's second pass rewrites
-// out_type, so everything else that reads the decoded outcomes is queued in front of it.
+// the count is on): the count, the collapse's origin pass, dedup's two passes, each when it is on -- or, in the frozen state, the
+// replay kernel alone.  Dedup's second pass and the replay rewrite out_type, so everything else that reads the decoded outcomes is
+// queued in front of them.
 __attribute__((visibility("hidden"))) int mol_slot_decoded(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode,
                                                            const int32_t* out_finger, const int8_t* labels);
 // option "collapse_origin_kernel_us" of td_get_option: the origin pass's time of the last batch (waits for it)
 __attribute__((visibility("hidden"))) int mol_origin_last_kernel_us(td_ctx* c, int32_t* us);
 // option "dedup_kernel_us" of td_get_option: the two passes' time of the last batch (waits for it)
 __attribute__((visibility("hidden"))) int mol_dedup_last_kernel_us(td_ctx* c, int32_t* us);
+// option "dedup_replay_kernel_us" of td_get_option: the replay kernel's time of the last batch of the frozen state (waits for it)
+__attribute__((visibility("hidden"))) int mol_replay_last_kernel_us(td_ctx* c, int32_t* us);
 // option "molecules_kernel_us" of td_get_option: the count kernel's time of the last counted batch (waits for it)
 __attribute__((visibility("hidden"))) int mol_last_kernel_us(td_ctx* c, int32_t* us);
 // table and label copy freed, count off (the caller has made sure nothing of it is queued any more)

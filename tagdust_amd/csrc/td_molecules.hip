@@ -8,7 +8,8 @@
 // add per read), not the heavy hitter the census merges away -- the merge of equal keys in a wave stays, PCR copies sit together
 // often enough.  A second kernel sweeps the table into one summary row per barcode bin (td_mol_get).  The same definitions over
 // host arrays (td_mol_host, td_mol_host_origins, td_mol_dedup_host, td_mol_collapse_host), td_mol_summarise and td_mol_key are in
-// td_molecules_host.cpp; the key's arithmetic, one text for both sides, in td_count_key.h.
+// td_molecules_host.cpp (td_mol_dedup_collapsed_host, the frozen state's yardstick, with them); the key's arithmetic, one text for
+// both sides, in td_count_key.h.
 //
 // Dedup (td_mol_dedup_enable) adds two launches behind the count.  Pass 1 builds every read's key again -- mol_lane_key is the one
 // text the count and it share --, finds the slot the count left the key in and lowers first[slot] to the read's ordinal, its
@@ -22,6 +23,11 @@
 // is asked for, over an idle table: the occupied slots' indices gathered into a dense list, then one molecule per lane -- the
 // parent pass probes the 3 * m keys one UMI mismatch away and keeps the best qualifying one, the root pass walks up and adds the
 // molecule's count to its root's --, then the summary sweep above over the collapsed counts, or a gather of the roots.
+//
+// The frozen state (td_mol_dedup_freeze, with count, dedup and collapse on) is the second pass that makes dedup follow the
+// collapse: the collapse runs once more, the keeper pass leaves beside every occupied slot the first ordinal of its root's own
+// key, and from then on a batch gets one launch, the replay kernel -- key, probe, one load of keeper[slot], the compare with the
+// read's ordinal.  The table is read-only then: no event orders neighbouring batches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -148,6 +154,38 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_mark_kernel(int32_t* __restri
 	}
 }
 
+// The frozen state, the replay: one launch per batch, behind the decode.  The table and keeper[] are only read: a read whose key the
+// table holds is a duplicate unless it is the one read its tree keeps; an eligible read without a key in the table -- empty, N, a
+// key that overflowed in the survey or was never surveyed -- is kept and tallied unjudged.
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_replay_kernel(const TdMolArgs a)
+{
+	__shared__ uint8_t s_r[128];
+	int lane, tile;
+	if (!mol_wave_tile(a, s_r, lane, tile)) return;
+	const int64_t k = (int64_t)tile * TD_WAVE + lane;
+	MolLane m;
+	if (!mol_lane_key(a, s_r, tile, lane, k, m)) return;
+	const int32_t slot = m.has_key ? kt_probe_find(a.table, m.key) : -1;
+	bool dup = false;
+	if (slot >= 0) {
+		const int64_t at = a.read_at ? (int64_t)a.read_at[k] : k;     // the caller's order, not the length-sorted one
+		dup = a.keeper[slot] != (kt_u64)(a.ordinal_base + at);
+	}
+	if (dup) {
+		int32_t* type = const_cast<int32_t*>(a.out_type);             // (the lane's own word; every other field stays as decoded)
+		type[k] = (int32_t)(((uint32_t)type[k] & ~0xFFu) | (uint32_t)TD_EXTRACT_DUPLICATE);
+	}
+	// tallies: one add per wave and tally
+	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(m.elig));
+	const int n_dup = __builtin_popcountll(__builtin_amdgcn_ballot_w64(dup));
+	const int n_unjudged = __builtin_popcountll(__builtin_amdgcn_ballot_w64(m.elig && slot < 0));
+	if (lane == 0) {
+		if (n_elig - n_dup) atomicAdd(&a.tallies[TDM_KEPT], (kt_u64)(n_elig - n_dup));
+		if (n_dup) atomicAdd(&a.tallies[TDM_DUPLICATES], (kt_u64)n_dup);
+		if (n_unjudged) atomicAdd(&a.tallies[TDM_UNJUDGED], (kt_u64)n_unjudged);
+	}
+}
+
 // Collapse, the origin pass: behind the count kernel of the same batch on the same stream, so a counted read's key is in the table or
 // has overflowed for good.  One lane per distinct key of the wave goes on; a slot without an origin yet (n == 0: a counted read has
 // n >= 1) gets it in two plain 8-byte stores, n last.  Origin passes of two batches may meet in a slot: both write the same words.
@@ -242,6 +280,19 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_root_kernel(const kt_u64* __r
 	}
 }
 
+// The freeze, the keeper pass: one occupied slot per lane walks parent[] to its root as the root pass does and leaves the first
+// ordinal of the root's own key -- not the minimum over the tree -- in its own word, one plain 8-byte store.
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_keeper_kernel(const uint32_t* __restrict__ occ, int64_t n_occ, const uint32_t* __restrict__ parent,
+                                                                  const kt_u64* __restrict__ first, kt_u64* __restrict__ keeper)
+{
+	const int64_t q = (int64_t)blockIdx.x * KT_BLOCK + threadIdx.x;
+	if (q >= n_occ) return;
+	const uint32_t slot = occ[q];
+	uint32_t at = slot, up = parent[at];
+	for (int64_t steps = 0; up != at && steps < n_occ; steps++) { at = up; up = parent[at]; }   // (no walk is longer than the list)
+	keeper[slot] = first[at];
+}
+
 // Collapse: (key, value, origin) of the listed slots whose value is not 0 into dense arrays -- every molecule with its count
 // (td_mol_origins), or the roots with their collapsed counts
 __global__ __launch_bounds__(KT_BLOCK) void td_mol_gather_kernel(const kt_u64* __restrict__ keys, const kt_u64* __restrict__ values,
@@ -312,6 +363,16 @@ static int summary_rows(td_ctx* c, const kt_u64* counts, td_mol_row rows[TD_NUM_
 	return TD_OK;
 }
 
+// the frozen state's keeper array and events freed, the state ended (nothing of it is queued any more)
+static void keeper_release(TdMolState& z)
+{
+	if (z.d_keeper) (void)hipFree(z.d_keeper);
+	hipEvent_t ev[] = { z.ev_r0, z.ev_r1 };
+	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+	z.d_keeper = nullptr; z.ev_r0 = z.ev_r1 = nullptr;
+	z.frozen = false;
+}
+
 // dedup's first ordinals and events freed (nothing of it is queued any more).  They exist while z.dedup is set and inside a
 // td_mol_dedup_enable that has not yet succeeded, which frees what it got itself.
 static void dedup_release(TdMolState& z)
@@ -322,6 +383,7 @@ static void dedup_release(TdMolState& z)
 	z.d_first = nullptr; z.ev_p1[0] = z.ev_p1[1] = z.ev_d0 = z.ev_d1 = nullptr;
 	z.p1_queued[0] = z.p1_queued[1] = false;
 	z.dedup = false;
+	keeper_release(z);
 }
 
 // the collapse's origins, events and work arrays freed (nothing of it is queued any more); they exist as dedup's do
@@ -334,6 +396,7 @@ static void collapse_release(TdMolState& z)
 	z.d_origin = nullptr; z.d_occ = nullptr; z.d_parent = nullptr; z.d_collapsed = nullptr; z.cap_occ = 0;
 	z.ev_o0 = z.ev_o1 = nullptr;
 	z.collapse = false;
+	keeper_release(z);
 }
 
 void mol_release(td_ctx* c)
@@ -348,6 +411,8 @@ void mol_release(td_ctx* c)
 
 // A decoded slot's launches, queued on its compute stream: the count, then the collapse's origin pass, then dedup's two passes, each
 // only when it is on and each between its own two events.  The order matters: dedup's pass 2 rewrites the outcomes the others read.
+// In the frozen state the replay kernel alone, between its own two events: keys, counts, origins, first ordinals and the count's
+// tallies stay as the survey left them.
 int mol_slot_decoded(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
 {
 	TdMolState& z = c->molecules;
@@ -357,6 +422,18 @@ int mol_slot_decoded(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out
 	a.label = z.table.d_label; a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.H = z.table.H;
 	a.r_segs = z.r_segs; a.prefix = z.prefix;
 	a.table = kt_table_view(z.table); a.tallies = z.table.d_tallies;
+	if (z.frozen) {
+		a.ordinal_base = z.next_ordinal;              // reads submitted since the freeze: the rule of the survey
+		z.next_ordinal += s.n_reads;
+		a.read_at = s.sorted ? s.d_read_at : nullptr; a.keeper = z.d_keeper;
+		HIPCHK(c, hipEventRecord(z.ev_r0, s.cs));
+		if (s.n_tiles > 0) {
+			hipLaunchKernelGGL(td_mol_replay_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
+			HIPCHK(c, hipGetLastError());
+		}
+		HIPCHK(c, hipEventRecord(z.ev_r1, s.cs));
+		return kt_slot_read_behind(c, s);
+	}
 	if (kt_count_slot(c, z.table, s, (const void*)td_mol_count_kernel, &a) != TD_OK) return TD_FAIL;
 	if (z.collapse) {
 		a.origin = z.d_origin;
@@ -439,6 +516,7 @@ extern "C" int td_mol_reset(td_ctx* c)
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	z.next_ordinal = 0;
 	z.p1_queued[0] = z.p1_queued[1] = false;          // (nothing is queued any more)
+	z.frozen = false;                                 // (the table is empty: the context surveys again)
 	return TD_OK;
 }
 
@@ -468,6 +546,7 @@ extern "C" int td_mol_dedup_disable(td_ctx* c)
 {
 	if (!c) return TD_FAIL;
 	if (c->molecules.dedup && wait_compute(c) != TD_OK) return TD_FAIL;
+	if (c->molecules.frozen && td_mol_reset(c) != TD_OK) return TD_FAIL;   // the frozen state ends with an empty table
 	dedup_release(c->molecules);   // (off: there is nothing to free)
 	return TD_OK;
 }
@@ -541,6 +620,7 @@ extern "C" int td_mol_collapse_disable(td_ctx* c)
 {
 	if (!c) return TD_FAIL;
 	if (c->molecules.collapse && wait_compute(c) != TD_OK) return TD_FAIL;
+	if (c->molecules.frozen && td_mol_reset(c) != TD_OK) return TD_FAIL;   // the frozen state ends with an empty table
 	collapse_release(c->molecules);   // (off: there is nothing to free)
 	return TD_OK;
 }
@@ -670,6 +750,50 @@ extern "C" int td_mol_collapse_entries(td_ctx* c, td_census_entry* entries, td_m
 	if (collapse_gather(c, "td_mol_collapse_entries", z.d_collapsed, n_occ, t.molecules_after, entries, origins, cap, n) != TD_OK) return TD_FAIL;
 	if (totals) *totals = t;
 	return TD_OK;
+}
+
+// ---- the frozen state ----
+extern "C" int td_mol_dedup_freeze(td_ctx* c, td_mol_collapse_totals* totals)
+{
+	if (!c) return fail(nullptr, "td_mol_dedup_freeze: no context");
+	TdMolState& z = c->molecules;
+	if (!z.on) return fail(c, "td_mol_dedup_freeze: the molecule count is off (td_mol_enable)");
+	if (!z.dedup) return fail(c, "td_mol_dedup_freeze: dedup is off (td_mol_dedup_enable)");
+	if (!z.collapse) return fail(c, "td_mol_dedup_freeze: the collapse is off (td_mol_collapse_enable)");
+	if (tickets_outstanding(c)) return fail(c, "td_mol_dedup_freeze: td_submit tickets are outstanding (td_wait them first)");
+	int64_t n_occ = 0;
+	td_mol_collapse_totals t{};
+	if (collapse_run(c, "td_mol_dedup_freeze", &n_occ, &t) != TD_OK) return TD_FAIL;   // (waits for the context's queued work)
+	if (!z.d_keeper) {
+		const bool ok = hipMalloc((void**)&z.d_keeper, sizeof(kt_u64) << z.table.log2_slots) == hipSuccess &&
+		                hipEventCreate(&z.ev_r0) == hipSuccess && hipEventCreate(&z.ev_r1) == hipSuccess;
+		if (!ok) {
+			const std::string e = hipGetErrorString(hipGetLastError());
+			keeper_release(z);
+			return fail(c, "td_mol_dedup_freeze: the keepers of 2^%d slots could not be set up: %s", z.table.log2_slots, e.c_str());
+		}
+	}
+	if (n_occ > 0) {
+		hipLaunchKernelGGL(td_mol_keeper_kernel, dim3(blocks_for(n_occ)), dim3(KT_BLOCK), 0, c->stream, (const uint32_t*)z.d_occ, n_occ,
+		                   (const uint32_t*)z.d_parent, (const kt_u64*)z.d_first, z.d_keeper);
+		HIPCHK(c, hipGetLastError());
+	}
+	HIPCHK(c, hipMemsetAsync(z.table.d_tallies + TDM_KEPT, 0, sizeof(kt_u64) * 3, c->stream));   // (TDM_KEPT, TDM_DUPLICATES, TDM_UNJUDGED)
+	static_assert(TDM_DUPLICATES == TDM_KEPT + 1 && TDM_UNJUDGED == TDM_KEPT + 2, "the three are zeroed together");
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	z.next_ordinal = 0;
+	z.p1_queued[0] = z.p1_queued[1] = false;          // (nothing is queued any more)
+	z.frozen = true;
+	if (totals) *totals = t;
+	return TD_OK;
+}
+
+// the replay kernel's time of the last batch of the frozen state (option "dedup_replay_kernel_us" of td_get_option)
+int mol_replay_last_kernel_us(td_ctx* c, int32_t* us)
+{
+	const TdMolState& z = c->molecules;
+	if (!z.frozen) return fail(c, "td_get_option: dedup_replay_kernel_us: the context is not frozen (td_mol_dedup_freeze)");
+	return kt_last_kernel_us(c, z.ev_r0, z.ev_r1, us, "td_get_option: dedup_replay_kernel_us: no batch has been replayed yet");
 }
 
 // the count kernel's time of the last batch, for tools/molecules_bench.py (option "molecules_kernel_us" of td_get_option)

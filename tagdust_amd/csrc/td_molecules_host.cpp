@@ -1,7 +1,7 @@
 // td_molecules_host.cpp -- the host side of the molecule count (include/tagdust_molecules.h): the definitions the device
 // (td_molecules.hip) is held against, over host arrays -- td_mol_host and td_mol_host_origins (one walk over the reads, the second
-// keeps what every key was made of), td_mol_dedup_host, td_mol_collapse_host --, td_mol_summarise, which a run over several
-// devices calls on merged entries, and the key itself.  Plain C++: no device is used and no HIP header read.
+// keeps what every key was made of), td_mol_dedup_host, td_mol_collapse_host, td_mol_dedup_collapsed_host --, td_mol_summarise,
+// which a run over several devices calls on merged entries, and the key itself.  Plain C++: no device is used and no HIP header read.
 #include <stdlib.h>
 #include <string.h>
 
@@ -75,6 +75,48 @@ void host_add_repeated(const td_census_entry* entries, const td_mol_origin* orig
 	}
 	v.resize(e.size()); vo.resize(e.size());
 	mol_emit_ordered(e.data(), eo.data(), (int64_t)e.size(), (int64_t)e.size(), v.data(), vo.data());
+}
+
+// The collapse's forest over v, one entry per key in the order of td_census_get, with its origins: parent and root of every entry
+// (indices into v; a root is its own), the count of every root's tree (0 elsewhere) and the totals.  td_mol_collapse_host and
+// td_mol_dedup_collapsed_host both stand on this one copy.
+struct HostForest {
+	std::vector<size_t> parent, root;
+	std::vector<int64_t> collapsed;
+	td_mol_collapse_totals totals{};
+};
+void host_forest(const std::vector<td_census_entry>& v, const std::vector<td_mol_origin>& vo, HostForest& f)
+{
+	const size_t N = v.size();
+	std::unordered_map<uint64_t, size_t> at;
+	for (size_t u = 0; u < N; u++) at[v[u].key] = u;
+	// v is in the order of td_census_get: "v comes before u" is "its index is smaller", and the first qualifying neighbour the smallest
+	f.parent.assign(N, 0);
+	for (size_t u = 0; u < N; u++) {
+		f.parent[u] = u;
+		const int m = vo[u].n > 0 ? mol_umi_bases(vo[u].fingerprint) : 0;
+		for (int i = 0; i < m; i++)
+			for (uint32_t d = 1; d <= 3; d++) {
+				const auto g = at.find(mol_neighbour_key(v[u].key, vo[u], i, d));
+				if (g == at.end()) continue;
+				const size_t q = g->second;
+				if (v[q].count >= 2 * v[u].count - 1 && q < f.parent[u]) f.parent[u] = q;
+			}
+	}
+	// a parent has a smaller index: roots and depths in one pass from the front
+	f.root.assign(N, 0);
+	f.collapsed.assign(N, 0);
+	std::vector<int64_t> depth(N);
+	td_mol_collapse_totals t{};
+	for (size_t u = 0; u < N; u++) {
+		f.root[u] = f.parent[u] == u ? u : f.root[f.parent[u]];
+		depth[u] = f.parent[u] == u ? 0 : depth[f.parent[u]] + 1;
+		f.collapsed[f.root[u]] += v[u].count;
+		t.longest_chain = std::max(t.longest_chain, depth[u]);
+		t.molecules_after += f.root[u] == u;
+	}
+	t.molecules_before = (int64_t)N; t.absorbed = t.molecules_before - t.molecules_after;
+	f.totals = t;
 }
 
 td_mol_origin* copy_origins(const std::vector<td_mol_origin>& v)
@@ -156,6 +198,48 @@ extern "C" int td_mol_dedup_host(const td_model_desc* m, int32_t prefix_bases, c
 	return TD_OK;
 }
 
+extern "C" int td_mol_dedup_collapsed_host(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                                           const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate, td_mol_dedup_totals* totals,
+                                           td_mol_collapse_totals* collapse_totals)
+{
+	if (host_checks("td_mol_dedup_collapsed_host", m, prefix_bases, n_reads >= 0 && (n_reads == 0 || (offs && res && labels && codes && is_duplicate))) != TD_OK)
+		return TD_FAIL;
+	// the survey: every counted read's key and origin, and the first ordinal of every key (a read's ordinal is its index)
+	std::vector<uint64_t> key_of((size_t)n_reads, 0);
+	std::vector<int> cls_of((size_t)n_reads, MOL_NOT_ELIGIBLE);
+	std::vector<td_census_entry> each;
+	std::vector<td_mol_origin> each_o;
+	std::unordered_map<uint64_t, int64_t> first;
+	for (int64_t i = 0; i < n_reads; i++) {
+		td_mol_origin o{};
+		cls_of[(size_t)i] = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key_of[(size_t)i], &o);
+		if (cls_of[(size_t)i] != MOL_COUNTED) continue;
+		each.push_back(td_census_entry{ key_of[(size_t)i], 1 });
+		each_o.push_back(o);
+		first.emplace(key_of[(size_t)i], i);              // (the first one stays)
+	}
+	// the freeze: the collapse, and for every key the first ordinal of its root's own key
+	std::vector<td_census_entry> v;
+	std::vector<td_mol_origin> vo;
+	host_add_repeated(each.data(), each_o.data(), (int64_t)each.size(), v, vo);
+	HostForest f;
+	host_forest(v, vo, f);
+	std::unordered_map<uint64_t, int64_t> keeper;
+	for (size_t u = 0; u < v.size(); u++) keeper[v[u].key] = first[v[f.root[u]].key];
+	// the replay of the same reads
+	td_mol_dedup_totals t{};
+	for (int64_t i = 0; i < n_reads; i++) {
+		is_duplicate[i] = 0;
+		if (cls_of[(size_t)i] == MOL_NOT_ELIGIBLE) continue;
+		if (cls_of[(size_t)i] != MOL_COUNTED) { t.unjudged++; t.kept++; continue; }
+		if (keeper[key_of[(size_t)i]] == i) t.kept++;
+		else { is_duplicate[i] = 1; t.duplicates++; }
+	}
+	if (totals) *totals = t;
+	if (collapse_totals) *collapse_totals = f.totals;
+	return TD_OK;
+}
+
 extern "C" int td_mol_collapse_host(const td_census_entry* entries, const td_mol_origin* origins, int64_t n, td_census_entry** out_entries,
                                     td_mol_origin** out_origins, int64_t* out_n, td_mol_collapse_totals* totals)
 {
@@ -166,44 +250,19 @@ extern "C" int td_mol_collapse_host(const td_census_entry* entries, const td_mol
 	std::vector<td_census_entry> v;
 	std::vector<td_mol_origin> vo;
 	host_add_repeated(entries, origins, n, v, vo);
-	const size_t N = v.size();
-	std::unordered_map<uint64_t, size_t> at;
-	for (size_t u = 0; u < N; u++) at[v[u].key] = u;
-	// v is in the order of td_census_get: "v comes before u" is "its index is smaller", and the first qualifying neighbour the smallest
-	std::vector<size_t> parent(N);
-	for (size_t u = 0; u < N; u++) {
-		parent[u] = u;
-		const int m = vo[u].n > 0 ? mol_umi_bases(vo[u].fingerprint) : 0;
-		for (int i = 0; i < m; i++)
-			for (uint32_t d = 1; d <= 3; d++) {
-				const auto f = at.find(mol_neighbour_key(v[u].key, vo[u], i, d));
-				if (f == at.end()) continue;
-				const size_t q = f->second;
-				if (v[q].count >= 2 * v[u].count - 1 && q < parent[u]) parent[u] = q;
-			}
-	}
-	// a parent has a smaller index: roots and depths in one pass from the front
-	std::vector<size_t> root(N);
-	std::vector<int64_t> depth(N), collapsed(N, 0);
-	td_mol_collapse_totals t{};
-	for (size_t u = 0; u < N; u++) {
-		root[u] = parent[u] == u ? u : root[parent[u]];
-		depth[u] = parent[u] == u ? 0 : depth[parent[u]] + 1;
-		collapsed[root[u]] += v[u].count;
-		t.longest_chain = std::max(t.longest_chain, depth[u]);
-	}
+	HostForest f;
+	host_forest(v, vo, f);
 	std::vector<td_census_entry> r;                   // the roots with their collapsed counts, then in the order of td_census_get
 	std::vector<td_mol_origin> r_o;
-	for (size_t u = 0; u < N; u++) if (root[u] == u) { r.push_back(td_census_entry{ v[u].key, collapsed[u] }); r_o.push_back(vo[u]); }
+	for (size_t u = 0; u < v.size(); u++) if (f.root[u] == u) { r.push_back(td_census_entry{ v[u].key, f.collapsed[u] }); r_o.push_back(vo[u]); }
 	std::vector<td_census_entry> re(r.size());
 	std::vector<td_mol_origin> ro(r.size());
 	mol_emit_ordered(r.data(), r_o.data(), (int64_t)r.size(), (int64_t)r.size(), re.data(), ro.data());
-	t.molecules_before = (int64_t)N; t.molecules_after = (int64_t)re.size(); t.absorbed = t.molecules_before - t.molecules_after;
 	td_census_entry* pe = kt_copy_entries(re);
 	td_mol_origin* po = copy_origins(ro);
 	if (!pe || !po) { free(pe); free(po); return fail(nullptr, "td_mol_collapse_host: out of memory"); }
 	*out_entries = pe; *out_origins = po; *out_n = (int64_t)re.size();
-	if (totals) *totals = t;
+	if (totals) *totals = f.totals;
 	return TD_OK;
 }
 

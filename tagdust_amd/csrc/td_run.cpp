@@ -170,7 +170,7 @@ struct OptSpec { const char* name; int arg; int id; };
 enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
        O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS, O_DEDUP, O_COLLAPSE,
-       O_UNSUPPORTED = 100 };
+       O_DEDUP_COLLAPSED, O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
 	{ "7", 1, O_SEG + 6 }, { "8", 1, O_SEG + 7 }, { "9", 1, O_SEG + 8 }, { "10", 1, O_SEG + 9 },
@@ -196,6 +196,7 @@ const OptSpec kOwnOpts[] = {
 	{ "unknown-barcodes", 1, O_UNKNOWN }, { "unknown-barcodes-slots", 1, O_UNKNOWN_SLOTS },
 	{ "fingerprint-seq", 0, O_FINGER_SEQ }, { "molecules", 0, O_MOLECULES }, { "molecules-prefix", 1, O_MOLECULES_PREFIX },
 	{ "molecules-slots", 1, O_MOLECULES_SLOTS }, { "dedup", 0, O_DEDUP }, { "collapse-umis", 0, O_COLLAPSE },
+	{ "dedup-collapsed", 0, O_DEDUP_COLLAPSED },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -294,7 +295,10 @@ extern "C" const char* td_run_usage(void)
 	       "\t                            the input goes to no output file (implies --molecules; one input file, one device)\n"
 	       "\t--collapse-umis             count fingerprints one mismatch apart as one molecule where the counts say the rarer one is\n"
 	       "\t                            a misread of the other: two more columns in <output prefix>_molecules.txt (implies\n"
-	       "\t                            --molecules; needs an F segment; --dedup still matches exactly)\n\n";
+	       "\t                            --molecules; needs an F segment; --dedup still matches exactly)\n"
+	       "\t--dedup-collapsed           write one read per collapsed molecule: the input file is read twice, first to count, then to\n"
+	       "\t                            write the first read that carries each collapsed molecule's own barcode, fingerprint and start\n"
+	       "\t                            (implies --dedup, --collapse-umis and --molecules; a file, not stdin)\n\n";
 }
 
 extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
@@ -366,9 +370,11 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 		case O_MOLECULES_SLOTS: o->molecules_slots_log2 = atoi(v); break;
 		case O_DEDUP: o->dedup = 1; break;
 		case O_COLLAPSE: o->collapse_umis = 1; break;
+		case O_DEDUP_COLLAPSED: o->dedup_collapsed = 1; break;
 		default: return bad("unknown option " + a);
 		}
 	}
+	if (o->dedup_collapsed) { o->dedup = 1; o->collapse_umis = 1; }   // the second pass of the two together
 	if (o->dedup) o->molecules = 1;   // the duplicates are those of the molecule count
 	if (o->collapse_umis) o->molecules = 1;   // ... and so are the molecules that are collapsed
 	if (o->num_threads < 1) return bad("option -t: need at least one thread");
@@ -400,6 +406,7 @@ struct td_run_plan_t {
 	bool use_ref = false;
 	bool dedup = false;
 	bool collapse = false;
+	bool dedup_collapsed = false;
 };
 
 namespace {
@@ -472,8 +479,14 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	if (o->dedup && !o->molecules) return run_fail("--dedup needs --molecules: the duplicates are those of the molecule count.");
 	if (o->dedup && o->n_devices > 1)
 		return run_fail("--dedup needs exactly one device (%d given): each device has its own table, and a molecule split over two devices would survive twice.", o->n_devices);
+	if (o->dedup_collapsed && !(o->dedup && o->collapse_umis))
+		return run_fail("--dedup-collapsed needs --dedup and --collapse-umis: it is the second pass that makes the one follow the other.");
+	if (o->dedup_collapsed)
+		for (int k = 0; k < o->n_infiles; k++)
+			if (!strcmp(o->infile[k], "-")) return run_fail("--dedup-collapsed cannot read the input from stdin (-): the input is read twice.");
 	p->dedup = o->dedup != 0;
 	p->collapse = o->collapse_umis != 0;
+	p->dedup_collapsed = o->dedup_collapsed != 0;
 	for (int k = 0; k < o->n_infiles; k++)
 		if (strcmp(o->infile[k], "-") != 0 && !file_exists(o->infile[k])) return run_fail("ERROR: Input file:%s does not exists.", o->infile[k]);
 	// interface.c:419-450: two or more R segments in the command line's architecture switch DUST and -ref off
@@ -533,6 +546,8 @@ extern "C" int64_t td_run_plan_describe(const td_run_plan_t* p, char* buf, int64
 	s += std::string("ref: ") + (p->use_ref ? "on" : "off") + "\n";
 	if (p->dedup) s += "dedup: one read per molecule is written (barcode, fingerprint and the start of the read)\n";
 	if (p->collapse) s += "collapse: fingerprints one mismatch apart are counted as one molecule (directional rule; the count and --dedup stay exact)\n";
+	if (p->dedup_collapsed)
+		s += "dedup-collapsed: the input is read twice, a survey and then the run: one read per collapsed molecule is written, the first that carries the root's barcode, fingerprint and start\n";
 	if (p->all_known) {
 		s += "barcode file: " + (p->bar_file >= 0 ? std::to_string(p->bar_file) : std::string("none")) + "\n";
 		s += "output reads: " + std::to_string(p->num_out_reads) + "\n";
@@ -1082,6 +1097,7 @@ int Run::molecules()
 	if (o->dedup) {   // (one device: td_run_plan saw to it)
 		if (td_mol_dedup_get(f.raw[0], &rep->dedup_totals) != TD_OK) return fail("%s", td_last_error(f.raw[0]));
 		rep->dedup = 1;
+		rep->dedup_collapsed = o->dedup_collapsed != 0;
 	}
 
 	const td_arch* a = f.arch.get();
@@ -1097,6 +1113,7 @@ int Run::molecules()
 	if (sum.overflow > 0)
 		fprintf(out, "# the counting table was too small: %lld reads were not counted (the counts below are exact; --molecules-slots %d or more)\n",
 		        (long long)sum.overflow, o->molecules_slots_log2 + 1);
+	if (o->dedup_collapsed) fprintf(out, "# dedup\tcollapsed molecules\n");
 	if (o->dedup)
 		fprintf(out, "# written\t%lld\n# duplicates removed\t%lld\n", (long long)rep->dedup_totals.kept, (long long)rep->dedup_totals.duplicates);
 	if (crows)
@@ -1138,6 +1155,17 @@ int Run::run_files(td_stream_stats& st)
 	so.n_threads = o->host_threads;
 	if (K == 1 && o->n_devices == 1 && !is_read_only(files[0].arch.get())) {
 		td_ctx* c = files[0].raw[0];
+		if (o->dedup_collapsed) {
+			// Survey, freeze, replay (tagdust_molecules.h).  The survey decodes the whole file for the molecule table alone; every other
+			// accumulator of the context -- outcome counters, artifact hits, the census of --unknown-barcodes -- is reset behind it, so
+			// that it reports exactly one pass, the second.
+			td_stream_stats survey{};
+			const double t0 = now_s();
+			if (td_stream_survey(c, o->infile[0], &so, &survey) != TD_OK) return run_fail("%s", td_io_last_error());
+			if (td_mol_dedup_freeze(c, nullptr) != TD_OK || td_counts_reset(c) != TD_OK || (o->unknown_barcodes > 0 && td_census_reset(c) != TD_OK))
+				return run_fail("%s", td_last_error(c));
+			rep->survey_s = now_s() - t0;
+		}
 		if (td_stream_run(c, o->infile[0], files[0].arch.get(), o->outfile, &so, &st) != TD_OK) return run_fail("%s", td_io_last_error());
 		if (td_counts_get(c, rep->counts) != TD_OK) return run_fail("%s", td_last_error(c));
 		if (rep->n_artifacts && td_artifact_hits_get(c, rep->artifact_hits, rep->n_artifacts) != TD_OK) return run_fail("%s", td_last_error(c));

@@ -1,5 +1,5 @@
 // td_stream.cpp -- input files of any size through the decode path as a pipeline (include/tagdust_io.h): td_stream_run, one
-// input file on one device, and td_stream_run_multi, the K input files of a paired / multi-read run in lock-step on N devices.
+// input file on one device (td_stream_survey: the same without a write stage), and td_stream_run_multi, the K input files of a paired / multi-read run in lock-step on N devices.
 //
 //   reader / parser thread (per file) caller's thread                     writer thread
 //   block k+1: read or map, find      batch k: td_submit ... td_wait      batch k-1: format per output file, append
@@ -1221,6 +1221,28 @@ extern "C" int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* ar
 		fprintf(stderr, "td_stream: formatting %.3f s, appends %.3f s beside it (write stage %.3f s)\n", w ? w->dbg_format : 0.0, w ? w->dbg_pwrite : 0.0, st.write_s);
 	st.wall_s = now_s() - t_start;
 	st.codes_fnv = ctx ? 0 : fnv;
+	if (stats) *stats = st;
+	if (err.failed()) { td_io_set_error(err.message()); return TD_FAIL; }
+	return TD_OK;
+}
+
+// A decode-only run: reader, then submit and wait, no writer and no output files -- what the context accumulates (its counters, a
+// census, the molecule count's survey) is the result.
+extern "C" int td_stream_survey(td_ctx* ctx, const char* in_path, const td_stream_opts* opts, td_stream_stats* stats)
+{
+	if (!ctx || !in_path) { td_io_set_error("td_stream_survey: needs a context and an input path"); return TD_FAIL; }
+	const td_stream_opts o = resolve_opts(opts, artifacts_active(ctx));
+	const double t_start = now_s();
+	RunError err;
+	std::vector<std::unique_ptr<Reader>> readers;
+	readers.emplace_back(new Reader(err, o, false, true, o.n_threads));
+	std::string why;
+	if (!readers[0]->src.open(in_path, o.block_bytes, why)) { td_io_set_error(why); return TD_FAIL; }
+	td_stream_stats st{};
+	td_ctx* const one[1] = { ctx };
+	run_stages("td_stream_survey: ", err, readers, { Target{ one, false } }, 1, pipeline_depth(ctx), nullptr,
+	           [](const Tuple&) { return std::string(); }, [](Tuple&) { return true; }, st);
+	st.wall_s = now_s() - t_start;
 	if (stats) *stats = st;
 	if (err.failed()) { td_io_set_error(err.message()); return TD_FAIL; }
 	return TD_OK;

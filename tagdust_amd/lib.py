@@ -31,7 +31,7 @@ MULTI_ABI_SYMBOLS = ["td_shard_bounds", "td_count_outcomes", "td_multi_create", 
                      "td_multi_decode", "td_multi_counts", "td_multi_counts_reset", "td_multi_uses_rccl", "td_bind_host_to_device", "td_host_halves_bench",
                      "td_multi_artifact_hits"]
 IO_ABI_SYMBOLS = ["td_io_last_error", "td_reads_parse", "td_reads_free", "td_writer_open", "td_writer_write", "td_writer_close",
-                  "td_fasta_parse", "td_fasta_free", "td_stream_run", "td_stream_run_multi", "td_stream_run_multi_hits", "td_stream_release",
+                  "td_fasta_parse", "td_fasta_free", "td_stream_run", "td_stream_survey", "td_stream_run_multi", "td_stream_run_multi_hits", "td_stream_release",
                   "td_format_q", "td_fingerprint_text", "td_writer_set_fingerprint_text"]
 MODEL_ABI_SYMBOLS = ["td_arch_parse", "td_arch_free", "td_sequence_stats", "td_sequence_stats_window", "td_model_build", "td_model_tables_free",
                      "td_calibration_emit", "td_calibration_select", "td_calibration_free", "td_estimate_threshold",
@@ -55,7 +55,7 @@ CENSUS_MAX_WORD = 28
 MOL_ABI_SYMBOLS = ["td_mol_enable", "td_mol_disable", "td_mol_reset", "td_mol_entries", "td_mol_get", "td_mol_summarise", "td_mol_host",
                    "td_mol_key", "td_mol_key_bin", "td_mol_dedup_enable", "td_mol_dedup_disable", "td_mol_dedup_get", "td_mol_dedup_host",
                    "td_mol_collapse_enable", "td_mol_collapse_disable", "td_mol_origins", "td_mol_collapse_get", "td_mol_collapse_entries",
-                   "td_mol_host_origins", "td_mol_collapse_host"]
+                   "td_mol_host_origins", "td_mol_collapse_host", "td_mol_dedup_freeze", "td_mol_dedup_collapsed_host"]
 MOL_TOTALS = ("eligible", "counted", "skipped_empty", "skipped_n", "overflow", "molecules")
 MOL_DEDUP_TOTALS = ("kept", "duplicates", "unjudged")
 MOL_COLLAPSE_TOTALS = ("molecules_before", "molecules_after", "absorbed", "longest_chain")
@@ -546,6 +546,19 @@ def stream_run(ctx, in_path, segments=None, out_prefix=None, batch_reads=0, n_th
             lib.td_arch_free(arch)
 
 
+def stream_survey(ctx, in_path, batch_reads=0, n_threads=0, block_bytes=0):
+    """td_stream_survey: one input file through parse -> decode, nothing written; what the context accumulates is the result.
+    Returns the statistics as a dict."""
+    lib = load_library()
+    lib.td_stream_survey.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(_StreamOpts), C.POINTER(_StreamStats)]
+    lib.td_io_last_error.restype = C.c_char_p
+    o = _StreamOpts(int(batch_reads), int(n_threads), int(block_bytes), 0)
+    st = _StreamStats()
+    if lib.td_stream_survey(ctx.h, os.fsencode(in_path), C.byref(o), C.byref(st)) != 0:
+        raise TdError(lib.td_io_last_error().decode() or "td_stream_survey failed")
+    return {k: getattr(st, k) for k, _ in _StreamStats._fields_}
+
+
 class _StreamFile(C.Structure):
     _fields_ = [("path", C.c_char_p), ("arch", C.c_void_p), ("ctx", C.POINTER(C.c_void_p))]
 
@@ -602,7 +615,7 @@ class _RunOpts(C.Structure):
                 ("force", C.c_int32), ("dry_run", C.c_int32), ("help", C.c_int32), ("version", C.c_int32), ("echo_log", C.c_int32),
                 ("argc", C.c_int32), ("argv", C.POINTER(C.c_char_p)), ("unknown_barcodes", C.c_int32), ("unknown_slots_log2", C.c_int32),
                 ("fingerprint_seq", C.c_int32), ("molecules", C.c_int32), ("molecules_prefix", C.c_int32), ("molecules_slots_log2", C.c_int32),
-                ("dedup", C.c_int32), ("collapse_umis", C.c_int32)]
+                ("dedup", C.c_int32), ("collapse_umis", C.c_int32), ("dedup_collapsed", C.c_int32)]
 
 
 class _CensusTotals(C.Structure):
@@ -646,7 +659,8 @@ class _RunReport(C.Structure):
                 ("compile_wait_s", C.c_double), ("stream_s", C.c_double), ("stats_on_device", C.c_int32), ("log", C.c_char_p),
                 ("n_unknown", C.c_int64), ("unknown", C.c_void_p), ("unknown_totals", _CensusTotals),
                 ("molecules", C.c_void_p), ("molecules_totals", _MolTotals), ("dedup", C.c_int32), ("dedup_totals", _MolDedupTotals),
-                ("collapse", C.c_int32), ("collapse_totals", _MolCollapseTotals), ("molecules_collapsed", C.c_void_p)]
+                ("collapse", C.c_int32), ("collapse_totals", _MolCollapseTotals), ("molecules_collapsed", C.c_void_p),
+                ("dedup_collapsed", C.c_int32), ("survey_s", C.c_double)]
 
 
 def _run_lib():
@@ -760,6 +774,7 @@ def run_execute(args):
             "dedup_totals": rep.dedup_totals.as_dict() if rep.dedup else None,
             "collapse_totals": rep.collapse_totals.as_dict() if rep.collapse else None,
             "molecules_collapsed": _mol_rows(rep.molecules_collapsed) if rep.molecules_collapsed else None,
+            "dedup_collapsed": bool(rep.dedup_collapsed), "survey_s": float(rep.survey_s),
         }
     finally:
         o.lib.td_run_report_clear(C.byref(rep))
@@ -869,6 +884,9 @@ def _mol_lib():
     lib.td_mol_dedup_get.argtypes = [C.c_void_p, C.POINTER(_MolDedupTotals)]
     lib.td_mol_dedup_host.argtypes = [C.POINTER(_ModelDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.POINTER(_MolDedupTotals)]
+    lib.td_mol_dedup_freeze.argtypes = [C.c_void_p, C.POINTER(_MolCollapseTotals)]
+    lib.td_mol_dedup_collapsed_host.argtypes = [C.POINTER(_ModelDesc), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.POINTER(_MolDedupTotals), C.POINTER(_MolCollapseTotals)]
     lib.td_mol_collapse_enable.argtypes = [C.c_void_p]
     lib.td_mol_collapse_disable.argtypes = [C.c_void_p]
     lib.td_mol_origins.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_MolTotals)]
@@ -981,6 +999,30 @@ def mol_dedup_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
     if rc != 0:
         raise TdError(lib.td_last_error(None).decode())
     return dup[:len(offs) - 1].astype(bool), tot.as_dict()
+
+
+def mol_dedup_collapsed_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_dedup_collapsed_host: which reads are not the one read their collapsed molecule keeps -- the reads surveyed and the same
+    reads replayed, in the given order (no GPU).  Arguments as mol_host takes them.  Returns (is_duplicate, a bool per read; dedup
+    totals dict; collapse totals dict)."""
+    lib = _mol_lib()
+    desc, keep = make_model_desc(md)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if len(seq) == 0:
+        seq = np.zeros(1, np.uint8)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
+    for f in ("read_type", "barcode", "fingerprint"):
+        rr[f] = np.asarray(res[f])
+    dup = np.zeros(max(len(offs) - 1, 1), np.uint8)
+    tot, ctot = _MolDedupTotals(), _MolCollapseTotals()
+    rc = lib.td_mol_dedup_collapsed_host(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
+                                         labels.ctypes.data, dup.ctypes.data, C.byref(tot), C.byref(ctot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return dup[:len(offs) - 1].astype(bool), tot.as_dict(), ctot.as_dict()
 
 
 def mol_summarise(entries):
@@ -1234,6 +1276,12 @@ class TagdustHip:
         """td_mol_dedup_get: {kept, duplicates, unjudged}"""
         tot = _MolDedupTotals()
         self._chk(_mol_lib().td_mol_dedup_get(self.h, C.byref(tot)))
+        return tot.as_dict()
+
+    def mol_dedup_freeze(self):
+        """td_mol_dedup_freeze: the collapse, the keepers, and from now on every batch is replayed against them; collapse totals dict"""
+        tot = _MolCollapseTotals()
+        self._chk(_mol_lib().td_mol_dedup_freeze(self.h, C.byref(tot)))
         return tot.as_dict()
 
     def mol_collapse_enable(self):

@@ -46,6 +46,28 @@ kernel costs; the collapse touches 3 * m + 2 = 26 random words per molecule for 
 or a foreign slot, the parent's count, the root's add) besides two sweeps over the table's keys, so at the 60-100 ns a random
 touch of a quarter-full 64 MiB table costs a lane and some ten thousand lanes in flight, 2.8 * 10^5 molecules should take well
 under 10 ms, less than the host's sort of the entries; host to host nothing visible.
+
+One read per collapsed molecule (td_mol_dedup_freeze: survey, freeze, replay) has a mode of its own, --dedup-collapsed, which adds
+a "dedup_collapsed" section to the same file and measures nothing else:
+
+    python tools/molecules_bench.py --dedup-collapsed [--with-command | --command-only]
+
+The collapse's workload (0.5 % substitutions per UMI base).  Per iteration, the table reset before each: one td_run batch surveyed
+(count, origin pass, exact dedup's two passes: option "dedup_kernel_us", the yardstick of measurement 1 on the same visit),
+td_mol_collapse_get from call to return (the yardstick of measurement 2), td_mol_dedup_freeze from call to return -- the first call
+of the process allocates the keepers --, then the same batch replayed by td_run (option "dedup_replay_kernel_us"); medians of 5
+iterations behind a first one.  Host to host: td_submit / td_wait in the frozen state (one batch surveyed, the freeze, then the
+timed steps: their ordinals run on, so hardly a read is its tree's keeper, which is the same work -- key, probe, load, compare --
+with more stores), with exact dedup and with the count alone in turn in one process, two passes of each after a first pass that
+is discarded.  --with-command: the whole command on a FASTQ of the batch, --dedup-collapsed against --dedup --collapse-umis of
+the same build (a path this mode does not touch), same file, same box: a first run that is discarded (it compiles the model kernel,
+the later ones find it in the cache), then the two in turn, twice each, seconds on the wall.  Expectations, written down before the first run:
+  1. the replay kernel takes at most what exact dedup's two passes take on the same visit (0.30 ms per 2^20 reads on an earlier
+     visit): one launch in place of two, one walk and one probe as pass 1 has, one random 8-byte load, no atomic on the table;
+  2. td_mol_dedup_freeze takes about what td_mol_collapse_get takes (1.2 ms on an earlier visit): the same three launches without
+     the summary sweep, plus one sweep over the occupied list and, the first time, one allocation of 8 bytes per slot (32 MiB);
+  3. host to host: no expectation set in advance;
+  4. the command: up to twice the streaming seconds -- the survey decodes everything a second time --, expected and accepted.
 """
 import argparse
 import json
@@ -211,6 +233,117 @@ def measure_collapse(ctx, seq, offs, n):
     return out
 
 
+def measure_dedup_collapsed(ctx, seq, offs, n):
+    from tagdust_amd import RESULT_DTYPE
+    out = {"umi_substitution_rate": 0.005}
+    ctx.mol_enable(PREFIX, LOG2_SLOTS)
+    ctx.mol_dedup_enable()
+    ctx.mol_collapse_enable()
+    dec, exact, rep, frz, col = [], [], [], [], []
+    for it in range(6):
+        ctx.mol_reset()
+        ctx.upload_batch(seq, offs)
+        ctx.run()                                                  # the survey
+        dec.append(ctx.last_kernel_ms())
+        exact.append(ctx.get_option("dedup_kernel_us") / 1000.0)
+        if it == 0:
+            out["exact_dedup_totals_of_one_batch"] = ctx.mol_dedup_get()
+        ctx.mol_collapse_get()                                     # (the first of the process allocates parent and collapsed)
+        t0 = time.perf_counter()
+        ctx.mol_collapse_get()
+        col.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        ctot = ctx.mol_dedup_freeze()
+        frz.append((time.perf_counter() - t0) * 1e3)
+        ctx.upload_batch(seq, offs)
+        ctx.run()                                                  # the replay
+        rep.append(ctx.get_option("dedup_replay_kernel_us") / 1000.0)
+        if it == 0:
+            out["freeze_ms_first_call"] = round(frz[0], 3)
+            out["collapse_totals_of_one_batch"] = ctot
+            out["replay_totals_of_one_batch"] = ctx.mol_dedup_get()
+            out["count_totals_of_one_batch"] = ctx.mol_get()[1]
+    med = statistics.median
+    out["decode_kernel_ms_median"] = round(med(dec[1:]), 3)
+    out["exact_dedup_two_passes_ms_runs"], out["exact_dedup_two_passes_ms_median"] = [round(v, 3) for v in exact[1:]], round(med(exact[1:]), 3)
+    out["replay_kernel_ms_runs"], out["replay_kernel_ms_median"] = [round(v, 3) for v in rep[1:]], round(med(rep[1:]), 3)
+    out["replay_over_exact_dedup"] = round(med(rep[1:]) / med(exact[1:]), 3) if med(exact[1:]) > 0 else None
+    out["freeze_ms_runs"], out["freeze_ms_median"] = [round(v, 3) for v in frz[1:]], round(med(frz[1:]), 3)
+    out["collapse_get_ms_runs"], out["collapse_get_ms_median"] = [round(v, 3) for v in col[1:]], round(med(col[1:]), 3)
+    ctx.mol_disable()
+    # host to host: the first pass of the process is discarded, then the three states in turn, twice each
+    res = [np.zeros(n, RESULT_DTYPE) for _ in range(2)]
+    rates = {"discarded_first_pass": [], "frozen": [], "exact_dedup": [], "count_alone": []}
+    for k, state in enumerate(("count_alone", "frozen", "exact_dedup", "count_alone", "frozen", "exact_dedup", "count_alone")):
+        ctx.mol_enable(PREFIX, LOG2_SLOTS)
+        if state != "count_alone":
+            ctx.mol_dedup_enable()
+        if state == "frozen":
+            ctx.mol_collapse_enable()
+            ctx.upload_batch(seq, offs)
+            ctx.run()
+            ctx.mol_dedup_freeze()
+        steps = 4
+        for t in [ctx.submit(seq, offs, res=r) for r in res]:      # warm-up: both slots, both result buffers
+            ctx.wait(t)
+        t0 = time.perf_counter()
+        tickets = []
+        for s in range(steps):
+            tickets.append(ctx.submit(seq, offs, res=res[s & 1]))
+            if len(tickets) == 2:
+                ctx.wait(tickets.pop(0))
+        for t in tickets:
+            ctx.wait(t)
+        rates["discarded_first_pass" if k == 0 else state].append(round(steps * n / (time.perf_counter() - t0)))
+        ctx.mol_disable()
+    out["host_to_host_reads_per_s"] = rates
+    return out
+
+
+def measure_command(segs, seq, offs):
+    """the whole command once each way on a FASTQ of the batch: seconds on the wall and the report's streaming seconds"""
+    import shutil
+    import subprocess
+    import tempfile
+    from tagdust_amd import build as tdbuild
+    d = tempfile.mkdtemp(prefix="td_molecules_bench_")
+    try:
+        n, L = len(offs) - 1, bench.READ_LEN
+        alpha = np.frombuffer(b"ACGT", np.uint8)
+        bases = alpha[seq].reshape(n, L)
+        rec = np.empty((n, 12 + 1 + L + 3 + L + 1), np.uint8)
+        names = np.char.zfill(np.arange(n).astype("S11"), 11)
+        rec[:, 0] = ord("@")
+        rec[:, 1:12] = np.frombuffer(names.tobytes(), np.uint8).reshape(n, 11)
+        rec[:, 12] = 10
+        rec[:, 13:13 + L] = bases
+        rec[:, 13 + L:16 + L] = np.frombuffer(b"\n+\n", np.uint8)
+        rec[:, 16 + L:16 + 2 * L] = ord("I")
+        rec[:, 16 + 2 * L] = 10
+        fq = os.path.join(d, "in.fq")
+        rec.tofile(fq)
+        base = [tdbuild.EXE, "-Q", "20"] + [w for k, s in enumerate(segs) for w in ("-%d" % (k + 1), s)] + [fq, "--molecules-slots", str(LOG2_SLOTS)]
+        out = {"fastq_bytes": os.path.getsize(fq), "dedup_and_collapse_umis": {"wall_s_runs": []}, "dedup_collapsed": {"wall_s_runs": []}}
+        runs = [("discarded_first_run", ["--dedup", "--collapse-umis"])]   # (it compiles the model kernel; the later runs find it cached)
+        runs += [("dedup_and_collapse_umis", ["--dedup", "--collapse-umis"]), ("dedup_collapsed", ["--dedup-collapsed"])] * 2
+        for name, opts in runs:
+            t0 = time.perf_counter()
+            p = subprocess.run(base + opts + ["--force", "-o", os.path.join(d, name)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+            wall = time.perf_counter() - t0
+            if p.returncode != 0:
+                raise RuntimeError(p.stderr.decode(errors="replace")[-2000:])
+            if name == "discarded_first_run":
+                out[name] = {"wall_s": round(wall, 3)}
+                continue
+            text = open(os.path.join(d, name + "_molecules.txt")).read().splitlines()
+            out[name]["wall_s_runs"].append(round(wall, 3))
+            out[name]["molecules_file_head"] = [l for l in text if l.startswith("# ") and not l.startswith("# molecules:")][:13]
+        out["wall_ratio"] = round(min(out["dedup_collapsed"]["wall_s_runs"]) / min(out["dedup_and_collapse_umis"]["wall_s_runs"]), 3)
+        return out
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reads", type=int, default=1 << 20)
@@ -218,13 +351,22 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "molecules.json"))
     ap.add_argument("--collapse", action="store_true", help="measure the UMI collapse alone and add a \"collapse\" section to --out")
+    ap.add_argument("--dedup-collapsed", action="store_true", help="measure survey, freeze and replay alone and add a \"dedup_collapsed\" section to --out")
+    ap.add_argument("--with-command", action="store_true", help="with --dedup-collapsed: the whole command each way on a FASTQ of the batch")
+    ap.add_argument("--command-only", action="store_true", help="with --dedup-collapsed: the whole command alone, into the section that --out already has")
     args = ap.parse_args()
     from tagdust_amd import TagdustHip
     from tagdust_amd import lib as tdlib
     segs = ["B:" + ",".join(bench.BARCODES), "F:" + "N" * UMI, "S:" + bench.SPACER, "R:N", "P:" + bench.ADAPTER]
-    seq, offs, drawn = make_batch(args.reads, args.molecules, umi_sub=0.005 if args.collapse else 0.0)
+    seq, offs, drawn = make_batch(args.reads, args.molecules, umi_sub=0.005 if args.collapse or args.dedup_collapsed else 0.0)
     head = min(args.reads, 100000)
     md, _ = tdlib.build_model(segs, seq[:offs[head]], offs[:head + 1])
+    if args.dedup_collapsed and args.command_only:
+        doc = json.load(open(args.out))
+        doc["dedup_collapsed"]["command"] = measure_command(segs, seq, offs)
+        json.dump(doc, open(args.out, "w"), indent=1, sort_keys=True)
+        print(json.dumps(doc["dedup_collapsed"]["command"], sort_keys=True))
+        return
     ctx = TagdustHip(args.device)
     doc = {"reads": args.reads, "read_len": bench.READ_LEN, "molecules_drawn_from": args.molecules, "molecules_in_the_batch": drawn,
            "architecture": " ".join(segs), "prefix_bases": PREFIX, "table_log2_slots": LOG2_SLOTS, "threshold": 5.0}
@@ -234,14 +376,18 @@ def main():
         ctx.set_params(5.0, 16, 100)
         if args.collapse:
             section = dict(doc, **measure_collapse(ctx, seq, offs, args.reads))
+        elif args.dedup_collapsed:
+            section = dict(doc, **measure_dedup_collapsed(ctx, seq, offs, args.reads))
         else:
             doc.update(measure(ctx, seq, offs, args.reads))
     finally:
         ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    if args.collapse:                                              # the file's other figures stay what they are
+    if args.dedup_collapsed and args.with_command:                 # (the context is closed: the command has the device to itself)
+        section["command"] = measure_command(segs, seq, offs)
+    if args.collapse or args.dedup_collapsed:                      # the file's other figures stay what they are
         doc = json.load(open(args.out)) if os.path.exists(args.out) else {}
-        doc["collapse"] = section
+        doc["collapse" if args.collapse else "dedup_collapsed"] = section
     json.dump(doc, open(args.out, "w"), indent=1, sort_keys=True)
     print(json.dumps(doc, sort_keys=True))
 
