@@ -129,7 +129,14 @@ int td_stream_survey(td_ctx* ctx, const char* in_path, const td_stream_opts* opt
  * -fe and -t) on every file's contexts; with N > 1 devices each range is submitted with td_set_batch_window, so that the
  * filter's thread ranges are those of the whole batch, and the windows are reset to whole batches at the end.  A filter on some
  * files' contexts but not on others', or an R:N file without contexts in such a run, fails.  batch_reads then defaults to the
- * reference's 1 000 001 records (thread ranges, and with them batch boundaries, are part of the result). */
+ * reference's 1 000 001 records (thread ranges, and with them batch boundaries, are part of the result).
+ * Pair mode (tagdust_molecules.h, mate mode): when the contexts of the one decoded file report "mate_bases" > 0, the first file in
+ * call order other than it is its mate file -- its reader gets page-locked buffers, and before the decoded file's td_submit of a
+ * tuple the run calls td_mol_mate_next with that tuple's batch of the mate file.  TD_FAIL with a message for more than one device,
+ * for more than one decoded file (every other file must be R:N), and for a -ref filter on any context or dust != 0: the mate's own
+ * outcome is not joined to the count, so a mate that could fail would take a molecule's one kept read out of the files.  The
+ * per-record combination stays: the maximum makes a duplicate (dedup) TD_EXTRACT_DUPLICATE, which no file's output holds; counts
+ * counts it under TD_EXTRACT_SUCCESS and its barcode bin, as the single-file run's device counters do. */
 typedef struct td_stream_file {
 	const char*    path;   /* one input file (plain, .gz, .bz2) */
 	const td_arch* arch;   /* its architecture: param->read_structures[i], barcode_hmm.c:105-137 */

@@ -105,6 +105,25 @@
  * batching, of td_run or td_submit, of the tickets in flight, of length classes or of the kernel variant.  Limits: those of dedup
  * and of the collapse; the input is decoded twice; replaying other reads, or the same in another order, is defined (the rule
  * above) but keeps no longer one read per molecule.
+ *
+ * Mate mode (td_mol_mate_enable) -- the first bases of a read's MATE, a read of a second file, as part of the key.  UMI protocols put
+ * barcode and UMI into read 1 and the cDNA into read 2 (Drop-seq, CEL-seq, inDrop, the CASAVA three-read layout): the file that is
+ * decoded has few or no read bases of its own, and without the mate every read is skipped_empty or all molecules of a barcode and UMI
+ * share one key.  The reference has nothing of the kind; this is the definition, held by the device path and by the *_mated host
+ * functions alike.  A context with the count on may be put into mate mode with M = mate_bases, M >= 1 and P + M <= 32.  While it is
+ * on, every TD_MODE_GET_LABEL batch of n reads comes with a mate batch: codes (bytes 0..3 = A, C, G, T; any other value is N) and
+ * offs[n + 1]; mate i belongs to read i of the batch in the caller's order.  For an eligible read (eligibility is unchanged):
+ *   - the own prefix is as above: n1 = min(read bases, P), word w1;
+ *   - the mate prefix is n2 = min(len(mate i), M), word w2, two bits per base, the first base the most significant;
+ *   - n = n1 + n2 and w = (w1 << 2 * n2) | w2;
+ *   - the read is skipped_empty when n == 0, skipped_n when any of those n bases is not A, C, G or T, and otherwise counted under
+ *     td_mol_key(barcode, fingerprint, w, n) with origin {w, fingerprint, n}.
+ * Dedup (ordinals, first, mark), the collapse (a neighbour keeps w and n), freeze and replay, the identities and td_mol_summarise
+ * follow from that key unchanged.  With mate mode off every result is bit for bit what it is without this paragraph.  Limits:
+ *   - the split between n1 and n2 is not in the key: two reads whose own read segments are shorter than P by different amounts can
+ *     share a word (own ACG + mate T.. and own AC + mate GT..);
+ *   - the mate's own outcome takes no part: the mate is not decoded, filtered or DUSTed here, only its first M bases are read.  A
+ *     run that joins files (tagdust_run.h, --mate-bases) therefore refuses a -ref filter and DUST.
  */
 #ifndef TAGDUST_MOLECULES_H
 #define TAGDUST_MOLECULES_H
@@ -148,6 +167,28 @@ int td_mol_summarise(const td_census_entry* entries, int64_t n, td_mol_row rows[
  * td_last_error(NULL)'s. */
 int td_mol_host   (const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
                    const td_read_result* res, const int8_t* labels, td_census_entry** entries, int64_t* n, td_mol_totals* totals);
+/* Mate mode, see above.  One mate batch: codes and offs[n_reads + 1] as a batch's own input, and M. */
+typedef struct td_mol_mate { const uint8_t* codes; const int64_t* offs; int32_t bases; } td_mol_mate;
+/* td_mol_mate_enable: TD_FAIL with a message unless the count is on, no td_submit tickets are outstanding and 1 <= mate_bases <=
+ * 32 - prefix_bases; it starts from an empty table (it does what td_mol_reset does), so a table never mixes keys of two kinds.
+ * td_mol_mate_disable empties the table as well; td_mol_disable, and with it a new model, switches mate mode off. */
+int td_mol_mate_enable (td_ctx* ctx, int32_t mate_bases);
+int td_mol_mate_disable(td_ctx* ctx);
+/* Names the mate batch of the next batch that is staged for TD_MODE_GET_LABEL: td_submit takes it when its mode is
+ * TD_MODE_GET_LABEL (no other mode needs or consumes one); td_batch_upload, which does not know the mode yet, takes it when its
+ * n_reads is the batch's, and it then serves every td_run of that resident batch.  The staging copies the mate with the batch's own
+ * input on the same upload stream -- page-locked memory straight, anything else through pinned staging --, so codes and offs must
+ * stay valid and unchanged as long as the batch's own input must.  A TD_MODE_GET_LABEL td_run or td_submit in mate mode without a
+ * mate for its batch, or with one of another n_reads, is TD_FAIL with a message: nothing is counted, the named mate is dropped and
+ * the context stays usable.  A call names one batch: a second call before the staging replaces the first.
+ * td_get_option: "mate_bases" (0 = off) and "mate_kernel_us", the mate kernel's time of the last staged mate batch. */
+int td_mol_mate_next   (td_ctx* ctx, const uint8_t* codes, const int64_t* offs, int64_t n_reads);
+/* The four host definitions over reads with the mate joined into the key: the arguments of td_mol_host, td_mol_host_origins,
+ * td_mol_dedup_host and td_mol_dedup_collapsed_host plus the mate batch behind labels.  mate == NULL is the unmated function (those
+ * four are this call).  TD_FAIL with a message when mate->bases < 1 or prefix_bases + mate->bases > 32. */
+int td_mol_host_mated   (const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                         const td_read_result* res, const int8_t* labels, const td_mol_mate* mate, td_census_entry** entries, int64_t* n,
+                         td_mol_totals* totals);
 /* Dedup, see above.  td_mol_dedup_enable: TD_FAIL with a message unless the count is on (td_mol_enable first) and no td_submit
  * tickets are outstanding; it allocates 8 more bytes per slot and starts from an empty table (it does what td_mol_reset does).
  * td_mol_disable, and with it a new model, switches it off as well. */
@@ -160,6 +201,9 @@ int td_mol_dedup_get    (td_ctx* ctx, td_mol_dedup_totals* totals);   /* waits f
  * Never overflows.  totals may be NULL. */
 int td_mol_dedup_host   (const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
                          const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate, td_mol_dedup_totals* totals);
+int td_mol_dedup_host_mated(const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                            const td_read_result* res, const int8_t* labels, const td_mol_mate* mate, uint8_t* is_duplicate,
+                            td_mol_dedup_totals* totals);
 /* Collapse, see above.  td_mol_collapse_enable: TD_FAIL with a message unless the count is on, the model has an 'F' segment and no
  * td_submit tickets are outstanding; it allocates 16 more bytes per slot (the origins) and starts from an empty table, so every key
  * in the table has its origin.  td_mol_disable, and with it a new model, switches it off as well; td_mol_reset clears the origins. */
@@ -179,6 +223,9 @@ int td_mol_collapse_entries(td_ctx* ctx, td_census_entry* entries, td_mol_origin
 int td_mol_host_origins    (const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
                             const td_read_result* res, const int8_t* labels, td_census_entry** entries, td_mol_origin** origins, int64_t* n,
                             td_mol_totals* totals);
+int td_mol_host_origins_mated(const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                              const td_read_result* res, const int8_t* labels, const td_mol_mate* mate, td_census_entry** entries,
+                              td_mol_origin** origins, int64_t* n, td_mol_totals* totals);
 /* The collapse on the host, no GPU: what td_mol_collapse_entries returns, from entries and their origins.  A key may be given more
  * than once: its counts are added first, so the td_mol_origins results of several devices, concatenated, are a valid input -- the
  * multi-device path, and the yardstick of the device.  *out_entries is freed with td_census_free, *out_origins with free. */
@@ -194,6 +241,9 @@ int td_mol_dedup_freeze    (td_ctx* ctx, td_mol_collapse_totals* totals);
 int td_mol_dedup_collapsed_host(const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs,
                                 int64_t n_reads, const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate,
                                 td_mol_dedup_totals* totals, td_mol_collapse_totals* collapse_totals);
+int td_mol_dedup_collapsed_host_mated(const td_model_desc* model, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs,
+                                      int64_t n_reads, const td_read_result* res, const int8_t* labels, const td_mol_mate* mate,
+                                      uint8_t* is_duplicate, td_mol_dedup_totals* totals, td_mol_collapse_totals* collapse_totals);
 /* the key of a counted read: its record's barcode and fingerprint, its prefix word w of n bases (1..32) */
 uint64_t td_mol_key(int32_t barcode, int32_t fingerprint, uint64_t w, int32_t n);
 int32_t  td_mol_key_bin(uint64_t key);              /* the barcode bin a key belongs to */

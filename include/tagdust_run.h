@@ -82,6 +82,13 @@ typedef struct td_run_opts {
 	int32_t  dedup_collapsed;        /* --dedup-collapsed: one read per COLLAPSED molecule is written (tagdust_molecules.h, td_mol_dedup_freeze):
 	                                    the input file is read twice -- td_stream_survey, the freeze, td_stream_run.  Implies --dedup,
 	                                    --collapse-umis and --molecules (the parser sets them); refused wherever they are and for the input "-" */
+	int32_t  mate_bases;             /* --mate-bases M         [0 = off]: with two or more input files, the first M bases (1..31) of the read's
+	                                    mate -- the record of the first file in call order other than the decoded one -- join the molecule
+	                                    key behind the read's own prefix (tagdust_molecules.h, td_mol_mate_enable).  Implies --molecules
+	                                    (the parser sets it) and lifts its one-input-file rule; refused with one input file, when
+	                                    molecules_prefix + M > 32, with an effective DUST other than 0 or a -ref filter (the mate's own outcome
+	                                    is not joined), with more than one device, with --dedup-collapsed (the survey reads one file), and
+	                                    unless exactly one file has an architecture other than R:N */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -112,7 +119,9 @@ const char* td_run_version(void);
  * after collapse", "# absorbed" -- and two columns behind "10+", "collapsed" and "duplication_collapsed", to <out>_molecules.txt;
  * --dedup-collapsed implies --dedup, --collapse-umis and --molecules, is refused wherever they are and for the input "-" -- stdin
  * cannot be read twice --, gives "# written" and "# duplicates removed" the replay's numbers and adds one line, "# dedup", in front
- * of them, while every other output of the run reports the second pass alone), the
+ * of them, while every other output of the run reports the second pass alone; --mate-bases, see td_run_opts, adds a "mate:" line
+ * to the plan and two lines, "# mate bases" and "# mate file", behind "# prefix bases" to <out>_molecules.txt, and the run gives the
+ * files other than the decoded one no contexts, so their reads are uploaded once, as mates, by the decoded file's context), the
  * multiread rule (interface.c:441-450: DUST and -ref off, with a warning, when the command line's architecture has two or more
  * R segments).  What depends on the arch file's choice is decided again by td_run_execute once the choice is made. */
 typedef struct td_run_plan_t td_run_plan_t;   /* (the function below has the plain name) */

@@ -373,6 +373,8 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	if (!strcmp(name, "dedup_kernel_us")) return mol_dedup_last_kernel_us(c, value);   // the two passes of the last batch
 	if (!strcmp(name, "dedup_frozen")) { *value = c->molecules.frozen; return TD_OK; }   // td_mol_dedup_freeze: batches are replayed
 	if (!strcmp(name, "dedup_replay_kernel_us")) return mol_replay_last_kernel_us(c, value);   // the replay kernel of the last batch
+	if (!strcmp(name, "mate_bases")) { *value = c->molecules.mate_bases; return TD_OK; }   // td_mol_mate_enable's M, 0 = off
+	if (!strcmp(name, "mate_kernel_us")) return mol_mate_last_kernel_us(c, value);   // the mate kernel of the last staged mate batch
 	if (!strcmp(name, "collapse_active")) { *value = c->molecules.collapse; return TD_OK; }
 	if (!strcmp(name, "collapse_origin_kernel_us")) return mol_origin_last_kernel_us(c, value);   // the origin pass of the last batch
 	if (!strcmp(name, "overlap_active")) {
@@ -465,7 +467,7 @@ extern "C" int td_set_params(td_ctx* c, float threshold, int32_t minlen, int32_t
 // with the copies on their own streams, so that the upload of batch k+1 and the download of batch k-1 overlap the decode
 // kernel of batch k.  One HBM workspace serves all slots (decode kernels are serialised on the compute stream).
 // is this host pointer page-locked (hipHostMalloc / hipHostRegister)?  Then the DMA engines can use it directly.
-static bool is_pinned(const void* p)
+bool is_pinned(const void* p)
 {
 	if (!p) return false;
 	hipPointerAttribute_t a;
@@ -495,9 +497,10 @@ static int slot_events(td_ctx* c, TdSlot& s)
 static void slot_release(TdSlot& s)
 {
 	void* dev[] = { s.d_raw, s.d_offs, s.d_read_at, s.d_keys, s.d_vals, s.d_sort_tmp, s.d_packed, s.d_lens, s.d_art_left,
-	                s.d_out, s.d_res, s.d_seq, s.d_lab, s.d_keepo, s.d_rle, s.d_runs, s.d_judged };
+	                s.d_out, s.d_res, s.d_seq, s.d_lab, s.d_keepo, s.d_rle, s.d_runs, s.d_judged, s.d_mate_raw, s.d_mate_offs, s.d_mate_w,
+	                s.d_mate_n };
 	for (void* p : dev) if (p) (void)hipFree(p);
-	void* pinned[] = { s.h_raw, s.h_offs, s.h_res, s.h_seq, s.h_lab, s.h_keepo, s.h_rle };
+	void* pinned[] = { s.h_raw, s.h_offs, s.h_res, s.h_seq, s.h_lab, s.h_keepo, s.h_rle, s.h_mate_raw, s.h_mate_offs };
 	for (void* p : pinned) if (p) (void)hipHostFree(p);
 	hipEvent_t ev[] = { s.ev_up, s.ev_k0, s.ev_k1, s.ev_done, s.ev_down, s.ev_pack, s.ev_hits };
 	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -572,7 +575,7 @@ static int ensure_workspace(td_ctx* c, TdSlot& s)
 
 // Reads -> device, sorted and packed.  Copies go on `up` (the compute stream itself for the synchronous calls); the
 // kernels on the compute stream wait for them through ev_up.
-static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* bases, int is_ascii, const int64_t* offs, int64_t n, hipStream_t up, bool with_workspace = true)
+static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* bases, int is_ascii, const int64_t* offs, int64_t n, hipStream_t up, bool with_workspace = true, bool take_mate = false)
 {
 	s.reset_staged(route);   // nothing of the slot's previous batch survives (nor of its launch, nor of its download)
 	if (with_workspace && !c->have_model) return fail(c, "td_batch_upload: no model uploaded");
@@ -634,6 +637,7 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 	}
 	HIPCHK(c, hipMemcpyAsync(s.d_offs, s.h_offs, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, up));
 	if (n_bases > 0) HIPCHK(c, hipMemcpyAsync(s.d_raw, src, (size_t)n_bases, hipMemcpyHostToDevice, up));
+	if (take_mate && mol_mate_stage(c, s, n, up) != TD_OK) return TD_FAIL;   // mate mode: the named mate batch travels with its reads
 	if (up != s.aux) {
 		HIPCHK(c, hipEventRecord(s.ev_up, up));
 		HIPCHK(c, hipStreamWaitEvent(s.aux, s.ev_up, 0));
@@ -649,6 +653,7 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 	b.out_soa = s.d_out; b.soa_stride = ol.soa_stride;
 	b.keep = (const uint32_t*)(s.d_out + ol.keep); b.labels = (const int8_t*)(s.d_out + ol.labels);
 	HIPCHK(c, td_stage_pack(b, s.aux));
+	if (take_mate && mol_mate_launch(c, s, n) != TD_OK) return TD_FAIL;   // (in front of ev_pack: the decode stream's wait covers it)
 	if (s.aux != s.cs) {   // the decode kernel's stream waits for the packed batch
 		HIPCHK(c, hipEventRecord(s.ev_pack, s.aux));
 		HIPCHK(c, hipStreamWaitEvent(s.cs, s.ev_pack, 0));
@@ -690,6 +695,12 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	if (!s.staged) return fail(c, "td_run: no batch resident (td_batch_upload failed or was not called)");
 	if (s.n_tiles > 0 && s.n_wave_slots == 0) return fail(c, "td_run: the resident batch was staged for TD_MODE_RNA_DUST, without a decode workspace (upload it again)");
 	HIPCHK(c, hipSetDevice(c->device));
+	// mate mode: a batch that was staged without its mates (or with those of another M) is not counted, and not decoded either
+	if (mode == TD_MODE_GET_LABEL && c->molecules.mate_bases > 0 && c->molecules.mate_bases != s.mate_m) {
+		c->molecules.mate_named = false;
+		return fail(c, "td_run: mate mode is on (td_mol_mate_enable, %d bases) and the resident batch of %lld reads was staged without a mate "
+		            "batch of as many reads: td_mol_mate_next first, then td_batch_upload; nothing was counted", c->molecules.mate_bases, (long long)s.n_reads);
+	}
 	s.reset_decoded();   // (runs_cap above all: a launch of the generic kernel, or an empty batch, must not hand the label runs of this
 	                     // slot's previous launch to the finish kernel)
 	s.mode = mode;
@@ -943,7 +954,9 @@ static int upload_common(td_ctx* c, const void* bases, int is_ascii, const int64
 	if (spec_handover(c, false) != TD_OK) return TD_FAIL;   // a finished background compile takes over before any geometry is chosen
 	TdSlot& s = c->slots[0];
 	const TdRoute rt = sync_route(c);
-	if (slot_stage(c, s, rt, bases, is_ascii, offs, n, c->stream) != TD_OK) return TD_FAIL;
+	// mate mode: the mode is td_run's to say, so the named mate batch is taken now when it is this batch's
+	const bool take_mate = c->molecules.mate_bases > 0 && c->molecules.mate_named && c->molecules.mate_reads == n;
+	if (slot_stage(c, s, rt, bases, is_ascii, offs, n, c->stream, true, take_mate) != TD_OK) return TD_FAIL;
 	HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller may reuse its buffers
 	c->last_slot = 0;
 	return TD_OK;
@@ -1006,6 +1019,8 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 	if (k < 0) return fail(c, "td_submit: all %d pipeline slots hold batches that have not been waited for", c->pipeline_depth);
 	if (mode == TD_MODE_RNA_DUST && labels) return fail(c, "td_submit: TD_MODE_RNA_DUST has no labels (pass NULL)");
 	if (spec_handover(c, false) != TD_OK) return TD_FAIL;   // a finished background compile takes over before any geometry is chosen
+	const bool take_mate = c->molecules.mate_bases > 0 && mode == TD_MODE_GET_LABEL;   // (no other mode needs or consumes a mate)
+	if (take_mate && mol_mate_check(c, n_reads, "td_submit") != TD_OK) return TD_FAIL;
 	TdSlot& s = c->slots[k];
 	TdRoute rt = sync_route(c);
 	rt.pipelined = true;
@@ -1015,12 +1030,12 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 		c->submit_parity ^= 1;
 		rt.aux = c->s_aux; rt.fin = c->s_fin;
 	}
-	if (slot_stage(c, s, rt, bases, is_ascii != 0, offs, n_reads, c->s_up, mode != TD_MODE_RNA_DUST) != TD_OK) return TD_FAIL;
+	if (slot_stage(c, s, rt, bases, is_ascii != 0, offs, n_reads, c->s_up, mode != TD_MODE_RNA_DUST, take_mate) != TD_OK) return TD_FAIL;
 	if (slot_decode(c, s, mode, labels != nullptr) != TD_OK) return TD_FAIL;
 	if (slot_fetch_begin(c, s, res, labels, seq_out, true) != TD_OK) return TD_FAIL;
 	// "returns once the reads have left the caller's buffers": a page-locked source is read by the DMA engine itself, so wait
 	// for that copy (a few ms at PCIe rate, beside the previous batch's kernel; everything of this batch is queued already)
-	if (s.raw_direct && !c->stable_input) HIPCHK(c, hipEventSynchronize(s.ev_up));
+	if ((s.raw_direct || s.mate_direct) && !c->stable_input) HIPCHK(c, hipEventSynchronize(s.ev_up));
 	s.ticket = ++c->ticket_counter;
 	c->next_slot = (k + 1) % c->pipeline_depth;
 	*ticket = s.ticket;

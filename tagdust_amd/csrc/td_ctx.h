@@ -44,6 +44,8 @@ struct TdStaged : TdRoute {
 	bool for_spec = false;    // ... and the workspace geometry is the specialised kernel's: a batch is decoded by the kernel it was staged
 	                          // for, also when a background compile is handed over between its upload and its td_run
 	bool raw_direct = false;  // the upload read the caller's page-locked buffer itself (no staging copy)
+	int32_t mate_m = 0;       // mate mode: d_mate_w / d_mate_n hold this batch's mates, made with M = mate_m (0: no mate batch was staged)
+	bool mate_direct = false; // ... and the upload read the caller's page-locked mate buffer itself
 	const uint8_t* raw_host = nullptr;   // the batch's bases on the host, valid until the batch has been waited for: the pinned staging
 	                                     // copy, or the caller's own page-locked buffer under the "stable_input" contract; else NULL
 	TdStageBatch sb{};
@@ -96,6 +98,13 @@ struct TdSlot : TdStaged, TdDecoded, TdFetch {
 	uint32_t* d_rle = nullptr;     size_t cap_rle = 0;     // (+ one word behind the runs: the overflow flag)
 	uint32_t* d_runs = nullptr;    size_t cap_runs = 0;    // label runs in device order, left by the specialised kernel (+ the overflow flag)
 	int32_t* d_judged = nullptr;   size_t cap_judged = 0;  // dedup: every read's slot in the molecule table between its two passes (-1: not judged)
+	// mate mode (td_molecules.hip): the mate batch as uploaded, and what the mate kernel makes of it, in the caller's order
+	uint8_t* d_mate_raw = nullptr; size_t cap_mate_raw = 0;
+	int64_t* d_mate_offs = nullptr; size_t cap_mate_offs = 0;
+	unsigned long long* d_mate_w = nullptr; size_t cap_mate_w = 0;
+	uint8_t* d_mate_n = nullptr;   size_t cap_mate_n = 0;
+	uint8_t* h_mate_raw = nullptr; size_t cap_h_mate_raw = 0;   // (pinned staging, as h_raw and h_offs)
+	int64_t* h_mate_offs = nullptr; size_t cap_h_mate_offs = 0;
 	uint32_t* h_keepo = nullptr;   size_t cap_h_keepo = 0;
 	uint32_t* h_rle = nullptr;     size_t cap_h_rle = 0;
 	// pinned host staging for pageable caller memory
@@ -228,6 +237,7 @@ struct td_ctx {
 };
 
 TD_HIDDEN int fail(td_ctx* c, const char* fmt, ...);   // (td_api.hip) TD_FAIL, and the message for td_last_error
+TD_HIDDEN bool is_pinned(const void* p);                // (td_api.hip) this host pointer is page-locked: the DMA engines can use it directly
 TD_HIDDEN bool tickets_outstanding(const td_ctx* c);   // (td_api.hip) a td_submit batch has not been waited for
 
 #define HIPCHK(c, call)                                                                       \

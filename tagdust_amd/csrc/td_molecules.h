@@ -45,6 +45,14 @@ struct TdMolState {
 	bool frozen = false;
 	unsigned long long* d_keeper = nullptr;   // [2^log2_slots] of an occupied slot: the first ordinal of its root's own key
 	hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;   // around the replay kernel of the last batch (option "dedup_replay_kernel_us")
+	// mate mode (td_mol_mate_enable): M, and the mate batch td_mol_mate_next named for the next TD_MODE_GET_LABEL staging (the caller's
+	// pointers, read by that staging alone)
+	int32_t mate_bases = 0;                   // M: the mate's bases that belong to the key (0 = off)
+	bool mate_named = false;
+	const uint8_t* mate_codes = nullptr;
+	const int64_t* mate_offs = nullptr;
+	int64_t mate_reads = 0;
+	hipEvent_t ev_m0 = nullptr, ev_m1 = nullptr;   // around the mate kernel of the last staged mate batch (option "mate_kernel_us")
 };
 
 struct TdMolArgs {
@@ -59,7 +67,11 @@ struct TdMolArgs {
 	int32_t n_tiles, H, prefix;
 	TdKeyTable table;
 	unsigned long long* __restrict__ tallies;
-	// dedup's pass 1 alone
+	// mate mode (mate_bases > 0; with read_at: the mate kernel leaves both in the caller's order)
+	const unsigned long long* __restrict__ mate_w;   // [n_reads] the mate's prefix word
+	const uint8_t* __restrict__ mate_n;       // [n_reads] its length n2 in the low 7 bits, bit 7 = one of those bases is an N
+	int32_t mate_bases;                       // M (0 = off: neither array is read)
+	// dedup's pass 1 and mate mode
 	const int32_t* __restrict__ read_at;      // [n_reads] device position -> index in the caller's order (NULL: the same)
 	unsigned long long* __restrict__ first;   // [slot_mask + 1] the smallest ordinal of every slot's key
 	int32_t* __restrict__ judged;             // [n_tiles*64] the read's table slot, -1 = not judged
@@ -76,6 +88,15 @@ struct TdMolArgs {
 // queued in front of them.
 __attribute__((visibility("hidden"))) int mol_slot_decoded(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode,
                                                            const int32_t* out_finger, const int8_t* labels);
+// Mate mode, inside slot_stage.  mol_mate_stage: the mate batch td_mol_mate_next named goes into the slot with the batch's own input, its
+// copies queued on `up` in front of the upload event (the named batch is consumed).  mol_mate_launch: the mate kernel over it on the
+// slot's aux stream, behind the upload event and in front of ev_pack.  mol_mate_check: TD_FAIL with a message (`who` in it) unless a
+// mate batch of n reads is named; a wrong one is dropped.
+__attribute__((visibility("hidden"))) int mol_mate_check(td_ctx* c, int64_t n, const char* who);
+__attribute__((visibility("hidden"))) int mol_mate_stage(td_ctx* c, TdSlot& s, int64_t n, hipStream_t up);
+__attribute__((visibility("hidden"))) int mol_mate_launch(td_ctx* c, TdSlot& s, int64_t n);
+// option "mate_kernel_us" of td_get_option: the mate kernel's time of the last staged mate batch (waits for it)
+__attribute__((visibility("hidden"))) int mol_mate_last_kernel_us(td_ctx* c, int32_t* us);
 // option "collapse_origin_kernel_us" of td_get_option: the origin pass's time of the last batch (waits for it)
 __attribute__((visibility("hidden"))) int mol_origin_last_kernel_us(td_ctx* c, int32_t* us);
 // option "dedup_kernel_us" of td_get_option: the two passes' time of the last batch (waits for it)

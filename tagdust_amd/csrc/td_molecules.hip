@@ -28,6 +28,11 @@
 // collapse: the collapse runs once more, the keeper pass leaves beside every occupied slot the first ordinal of its root's own
 // key, and from then on a batch gets one launch, the replay kernel -- key, probe, one load of keeper[slot], the compare with the
 // read's ordinal.  The table is read-only then: no event orders neighbouring batches.
+//
+// Mate mode (td_mol_mate_enable) joins the first M bases of every read's mate, a read of a second file, into the key.  The mate batch
+// travels with the batch's own input on the same upload stream into the batch's slot; the mate kernel, one mate per lane on the
+// slot's aux stream between the upload event and ev_pack, turns it into a word and a byte per read in the caller's order, and
+// mol_lane_key appends them behind the label walk.  The mates are not decoded: their outcome takes no part.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -70,6 +75,14 @@ __device__ __forceinline__ bool mol_lane_key(const TdMolArgs& a, const uint8_t* 
 		has_n = has_n || base_is_n;
 		return ++n < a.prefix;
 	});
+	if (a.mate_bases > 0 && elig) {                   // (mate mode is the launch's: one wave-uniform test when it is off)
+		const int64_t at = a.read_at ? (int64_t)a.read_at[k] : k;         // the caller's order, not the length-sorted one
+		const uint32_t mn = a.mate_n[at];
+		const int n2 = (int)(mn & 0x7Fu);                                 // (n + n2 <= P + M <= 32: the shift is at most 62)
+		w = (w << (2 * n2)) | a.mate_w[at];
+		n += n2;
+		has_n = has_n || (mn & 0x80u) != 0u;
+	}
 	m.is_empty = elig && n == 0;
 	m.is_n = elig && n > 0 && has_n;
 	m.has_key = elig && n > 0 && !has_n;
@@ -99,6 +112,28 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_count_kernel(const TdMolArgs 
 		if (added.overflow) atomicAdd(&a.tallies[TDM_OVERFLOW], (kt_u64)added.overflow);
 		if (added.fresh) atomicAdd(&a.tallies[TDM_MOLECULES], (kt_u64)added.fresh);
 	}
+}
+
+// Mate mode: one mate per lane.  Reads the first min(len, M) bytes of mate i -- never past offs[i + 1], so never past the staged
+// bytes -- and leaves, in the caller's order, its prefix word (two bits per base, the first base the most significant) and a byte:
+// the number of bases in the low 7 bits, bit 7 set when one of them is not A, C, G or T.  The host has checked that offs ascends.
+__global__ __launch_bounds__(KT_BLOCK) void td_mol_mate_kernel(const uint8_t* __restrict__ raw, const int64_t* __restrict__ offs, int64_t n_reads,
+                                                                int32_t mate_bases, kt_u64* __restrict__ mate_w, uint8_t* __restrict__ mate_n)
+{
+	const int64_t i = (int64_t)blockIdx.x * KT_BLOCK + threadIdx.x;
+	if (i >= n_reads) return;
+	const int64_t o0 = offs[i], len = offs[i + 1] - o0;
+	const int n2 = len < (int64_t)mate_bases ? (len > 0 ? (int)len : 0) : mate_bases;
+	const uint8_t* p = raw + o0;
+	kt_u64 w = 0ull;
+	uint32_t any_n = 0u;
+	for (int q = 0; q < n2; q++) {
+		const uint32_t b = p[q];
+		any_n |= b > 3u ? 0x80u : 0u;
+		w = (w << 2) | (kt_u64)(b & 3u);
+	}
+	mate_w[i] = w;
+	mate_n[i] = (uint8_t)((uint32_t)n2 | any_n);
 }
 
 // Dedup, pass 1: behind the count kernel of the same batch on the same stream, so a counted read's key is in the table or has
@@ -406,7 +441,9 @@ void mol_release(td_ctx* c)
 	if (z.d_rows) (void)hipFree(z.d_rows);
 	dedup_release(z);
 	collapse_release(z);
-	z = TdMolState();
+	hipEvent_t ev[] = { z.ev_m0, z.ev_m1 };
+	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+	z = TdMolState();                                 // (mate mode off with it, a named mate batch forgotten)
 }
 
 // A decoded slot's launches, queued on its compute stream: the count, then the collapse's origin pass, then dedup's two passes, each
@@ -422,6 +459,10 @@ int mol_slot_decoded(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out
 	a.label = z.table.d_label; a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.H = z.table.H;
 	a.r_segs = z.r_segs; a.prefix = z.prefix;
 	a.table = kt_table_view(z.table); a.tallies = z.table.d_tallies;
+	if (z.mate_bases > 0) {                           // (slot_decode has checked that the slot holds this batch's mates, made with this M)
+		a.mate_w = s.d_mate_w; a.mate_n = s.d_mate_n; a.mate_bases = z.mate_bases;
+		a.read_at = s.sorted ? s.d_read_at : nullptr;
+	}
 	if (z.frozen) {
 		a.ordinal_base = z.next_ordinal;              // reads submitted since the freeze: the rule of the survey
 		z.next_ordinal += s.n_reads;
@@ -518,6 +559,111 @@ extern "C" int td_mol_reset(td_ctx* c)
 	z.p1_queued[0] = z.p1_queued[1] = false;          // (nothing is queued any more)
 	z.frozen = false;                                 // (the table is empty: the context surveys again)
 	return TD_OK;
+}
+
+// ---- mate mode ----
+extern "C" int td_mol_mate_enable(td_ctx* c, int32_t mate_bases)
+{
+	if (!c) return fail(nullptr, "td_mol_mate_enable: no context");
+	TdMolState& z = c->molecules;
+	if (!z.on) return fail(c, "td_mol_mate_enable: the molecule count is off (td_mol_enable first): the mate joins the count's key");
+	if (tickets_outstanding(c)) return fail(c, "td_mol_mate_enable: td_submit tickets are outstanding (td_wait them first)");
+	if (mate_bases < 1 || z.prefix + mate_bases > TD_MOL_MAX_PREFIX)
+		return fail(c, "td_mol_mate_enable: mate_bases = %d with prefix_bases = %d (1..%d supported: both share one 64-bit word of %d bases)", mate_bases,
+		            z.prefix, TD_MOL_MAX_PREFIX - z.prefix, TD_MOL_MAX_PREFIX);
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
+	if (!z.ev_m0) HIPCHK(c, hipEventCreate(&z.ev_m0));
+	if (!z.ev_m1) HIPCHK(c, hipEventCreate(&z.ev_m1));
+	z.mate_bases = mate_bases;
+	z.mate_named = false;
+	return td_mol_reset(c);   // a table never mixes keys made with and without a mate, or with two M
+}
+
+extern "C" int td_mol_mate_disable(td_ctx* c)
+{
+	if (!c) return TD_FAIL;
+	TdMolState& z = c->molecules;
+	if (!z.on || z.mate_bases == 0) return TD_OK;     // (off: there is nothing to do)
+	if (tickets_outstanding(c)) return fail(c, "td_mol_mate_disable: td_submit tickets are outstanding (td_wait them first)");
+	z.mate_bases = 0;
+	z.mate_named = false;
+	return td_mol_reset(c);
+}
+
+extern "C" int td_mol_mate_next(td_ctx* c, const uint8_t* codes, const int64_t* offs, int64_t n_reads)
+{
+	if (!c) return fail(nullptr, "td_mol_mate_next: no context");
+	TdMolState& z = c->molecules;
+	if (z.mate_bases == 0) return fail(c, "td_mol_mate_next: mate mode is off (td_mol_mate_enable)");
+	if (!offs || n_reads < 0 || (!codes && n_reads > 0 && offs[n_reads] > offs[0])) return fail(c, "td_mol_mate_next: bad arguments");
+	z.mate_codes = codes; z.mate_offs = offs; z.mate_reads = n_reads; z.mate_named = true;
+	return TD_OK;
+}
+
+int mol_mate_check(td_ctx* c, int64_t n, const char* who)
+{
+	TdMolState& z = c->molecules;
+	if (!z.mate_named)
+		return fail(c, "%s: mate mode is on (td_mol_mate_enable, %d bases) and no mate batch is named for this batch of %lld reads (td_mol_mate_next "
+		            "first); nothing was counted", who, z.mate_bases, (long long)n);
+	if (z.mate_reads != n) {
+		z.mate_named = false;
+		return fail(c, "%s: the named mate batch has %lld reads, the batch %lld: mate i belongs to read i; the mate batch is dropped, nothing was counted",
+		            who, (long long)z.mate_reads, (long long)n);
+	}
+	return TD_OK;
+}
+
+int mol_mate_stage(td_ctx* c, TdSlot& s, int64_t n, hipStream_t up)
+{
+	TdMolState& z = c->molecules;
+	const uint8_t* codes = z.mate_codes;
+	const int64_t* offs = z.mate_offs;
+	z.mate_named = false;                             // consumed, whatever happens below
+	const int64_t base = offs[0];
+	if (ensure_pinned(c, &s.h_mate_offs, &s.cap_h_mate_offs, (size_t)(n + 1) * 8) != TD_OK) return TD_FAIL;
+	s.h_mate_offs[0] = 0;
+	for (int64_t i = 0; i < n; i++) {                 // the kernel trusts these: every mate ends where the next begins, none is negative
+		const int64_t l = offs[i + 1] - offs[i];
+		if (l < 0 || l > 100000) return fail(c, "td_mol_mate_next: mate %lld has length %lld", (long long)i, (long long)l);
+		s.h_mate_offs[i + 1] = offs[i + 1] - base;
+	}
+	const int64_t n_bases = n > 0 ? offs[n] - base : 0;
+	if (ensure(c, &s.d_mate_raw, &s.cap_mate_raw, (size_t)n_bases) != TD_OK || ensure(c, &s.d_mate_offs, &s.cap_mate_offs, (size_t)(n + 1) * 8) != TD_OK ||
+	    ensure(c, &s.d_mate_w, &s.cap_mate_w, (size_t)n * 8) != TD_OK || ensure(c, &s.d_mate_n, &s.cap_mate_n, (size_t)n) != TD_OK)
+		return TD_FAIL;
+	// host -> device as the batch's own bases go: page-locked caller memory straight to the DMA engine, anything else through pinned staging
+	const void* src = codes + base;
+	s.mate_direct = n_bases > 0 && is_pinned(src);
+	if (n_bases > 0 && !s.mate_direct) {
+		if (ensure_pinned(c, &s.h_mate_raw, &s.cap_h_mate_raw, (size_t)n_bases) != TD_OK) return TD_FAIL;
+		c->pool.copy(s.h_mate_raw, src, (size_t)n_bases, c->host_threads);
+		src = s.h_mate_raw;
+	}
+	HIPCHK(c, hipMemcpyAsync(s.d_mate_offs, s.h_mate_offs, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, up));
+	if (n_bases > 0) HIPCHK(c, hipMemcpyAsync(s.d_mate_raw, src, (size_t)n_bases, hipMemcpyHostToDevice, up));
+	s.mate_m = z.mate_bases;
+	return TD_OK;
+}
+
+int mol_mate_launch(td_ctx* c, TdSlot& s, int64_t n)
+{
+	TdMolState& z = c->molecules;
+	HIPCHK(c, hipEventRecord(z.ev_m0, s.aux));
+	if (n > 0) {
+		hipLaunchKernelGGL(td_mol_mate_kernel, dim3(blocks_for(n)), dim3(KT_BLOCK), 0, s.aux, (const uint8_t*)s.d_mate_raw, (const int64_t*)s.d_mate_offs, n,
+		                   z.mate_bases, s.d_mate_w, s.d_mate_n);
+		HIPCHK(c, hipGetLastError());
+	}
+	HIPCHK(c, hipEventRecord(z.ev_m1, s.aux));
+	return TD_OK;
+}
+
+int mol_mate_last_kernel_us(td_ctx* c, int32_t* us)
+{
+	const TdMolState& z = c->molecules;
+	if (z.mate_bases == 0) return fail(c, "td_get_option: mate_kernel_us: mate mode is off");
+	return kt_last_kernel_us(c, z.ev_m0, z.ev_m1, us, "td_get_option: mate_kernel_us: no mate batch has been staged yet");
 }
 
 extern "C" int td_mol_dedup_enable(td_ctx* c)

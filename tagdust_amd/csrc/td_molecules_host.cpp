@@ -1,6 +1,7 @@
 // td_molecules_host.cpp -- the host side of the molecule count (include/tagdust_molecules.h): the definitions the device
 // (td_molecules.hip) is held against, over host arrays -- td_mol_host and td_mol_host_origins (one walk over the reads, the second
-// keeps what every key was made of), td_mol_dedup_host, td_mol_collapse_host, td_mol_dedup_collapsed_host --, td_mol_summarise,
+// keeps what every key was made of), td_mol_dedup_host, td_mol_collapse_host, td_mol_dedup_collapsed_host, each over reads also as
+// *_mated with the mate batch joined into the key (the unmated name is the call with no mate) --, td_mol_summarise,
 // which a run over several devices calls on merged entries, and the key itself.  Plain C++: no device is used and no HIP header read.
 #include <stdlib.h>
 #include <string.h>
@@ -24,8 +25,9 @@ namespace {
 
 // what read i is to the count on the host: not eligible, or one of the three classes; *key and *origin of a counted read
 enum { MOL_NOT_ELIGIBLE = 0, MOL_EMPTY, MOL_HAS_N, MOL_COUNTED };
+// (mate: NULL, or the mate batch whose first min(len(mate i), bases) bases follow the read's own prefix in the word)
 int host_read_class(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t i,
-                    const td_read_result* res, const int8_t* labels, uint64_t* key, td_mol_origin* origin)
+                    const td_read_result* res, const int8_t* labels, const td_mol_mate* mate, uint64_t* key, td_mol_origin* origin)
 {
 	if (((uint32_t)res[i].read_type & 0xFFu) != (uint32_t)TD_EXTRACT_SUCCESS) return MOL_NOT_ELIGIBLE;
 	const int64_t len = offs[i + 1] - offs[i];
@@ -43,6 +45,15 @@ int host_read_class(const td_model_desc* m, int32_t prefix_bases, const uint8_t*
 		if (seq[p] > 3) has_n = true;
 		w = (w << 2) | (uint64_t)(seq[p] & 3u);
 	}
+	if (mate) {                                       // the mate's prefix behind the read's own: never past the mate's own end
+		const int64_t mlen = mate->offs[i + 1] - mate->offs[i];
+		const uint8_t* ms = mate->codes + mate->offs[i];
+		for (int64_t p = 0; p < mlen && p < mate->bases; p++) {
+			cnt++;
+			if (ms[p] > 3) has_n = true;
+			w = (w << 2) | (uint64_t)(ms[p] & 3u);
+		}
+	}
 	if (cnt == 0) return MOL_EMPTY;
 	if (has_n) return MOL_HAS_N;
 	*key = mol_key(res[i].barcode, res[i].fingerprint, w, cnt);
@@ -51,11 +62,20 @@ int host_read_class(const td_model_desc* m, int32_t prefix_bases, const uint8_t*
 }
 
 // what opens every *_host function over reads (`who`, for its messages; args_ok: its own pointers and sizes)
-int host_checks(const char* who, const td_model_desc* m, int32_t prefix_bases, bool args_ok)
+int host_checks(const char* who, const td_model_desc* m, int32_t prefix_bases, const td_mol_mate* mate, int64_t n_reads, bool args_ok)
 {
 	if (!m || m->S < 1 || m->H < 1 || !m->seg_type || !m->label) return fail(nullptr, "%s: no model", who);
 	if (!mol_prefix_ok(prefix_bases)) return fail(nullptr, "%s: prefix_bases = %d (1..%d supported)", who, prefix_bases, TD_MOL_MAX_PREFIX);
 	if (!args_ok) return fail(nullptr, "%s: bad arguments", who);
+	if (mate) {
+		if (mate->bases < 1) return fail(nullptr, "%s: mate bases = %d (at least 1)", who, mate->bases);
+		if (prefix_bases + mate->bases > TD_MOL_MAX_PREFIX)
+			return fail(nullptr, "%s: prefix_bases + mate bases = %d + %d (at most %d together: they share one 64-bit word)", who, prefix_bases,
+			            mate->bases, TD_MOL_MAX_PREFIX);
+		if (n_reads > 0 && (!mate->offs || !mate->codes)) return fail(nullptr, "%s: bad arguments (the mate batch)", who);
+		for (int64_t i = 0; i < n_reads; i++)
+			if (mate->offs[i + 1] < mate->offs[i]) return fail(nullptr, "%s: mate %lld has a negative length", who, (long long)i);
+	}
 	return TD_OK;
 }
 
@@ -126,24 +146,24 @@ td_mol_origin* copy_origins(const std::vector<td_mol_origin>& v)
 	return p;
 }
 
-// td_mol_host (with_origins false: they are dropped) and td_mol_host_origins, `who` in the messages: the walk over the reads, the
+// td_mol_host_mated (with_origins false: they are dropped) and td_mol_host_origins_mated, `who` in the messages: the walk over the reads, the
 // entries in the order of td_census_get
 int host_count(const char* who, bool with_origins, const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs,
-               int64_t n_reads, const td_read_result* res, const int8_t* labels, td_census_entry** entries, td_mol_origin** origins, int64_t* n,
-               td_mol_totals* totals)
+               int64_t n_reads, const td_read_result* res, const int8_t* labels, const td_mol_mate* mate, td_census_entry** entries,
+               td_mol_origin** origins, int64_t* n, td_mol_totals* totals)
 {
 	if (entries) *entries = nullptr;
 	if (origins) *origins = nullptr;
 	if (n) *n = 0;
 	const bool args_ok = entries && (origins || !with_origins) && n && n_reads >= 0 && (n_reads == 0 || (offs && res && labels && codes));
-	if (host_checks(who, m, prefix_bases, args_ok) != TD_OK) return TD_FAIL;
+	if (host_checks(who, m, prefix_bases, mate, n_reads, args_ok) != TD_OK) return TD_FAIL;
 	td_mol_totals t{};
 	std::vector<td_census_entry> each;                // one entry of count 1 per counted read
 	std::vector<td_mol_origin> each_o;
 	for (int64_t i = 0; i < n_reads; i++) {
 		uint64_t key = 0;
 		td_mol_origin o{};
-		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key, &o);
+		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, mate, &key, &o);
 		if (cls == MOL_NOT_ELIGIBLE) continue;
 		t.eligible++;
 		if (cls == MOL_EMPTY) t.skipped_empty++;
@@ -165,30 +185,52 @@ int host_count(const char* who, bool with_origins, const td_model_desc* m, int32
 
 }   // namespace
 
+extern "C" int td_mol_host_mated(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                                 const td_read_result* res, const int8_t* labels, const td_mol_mate* mate, td_census_entry** entries, int64_t* n,
+                                 td_mol_totals* totals)
+{
+	return host_count(mate ? "td_mol_host_mated" : "td_mol_host", false, m, prefix_bases, codes, offs, n_reads, res, labels, mate, entries, nullptr, n, totals);
+}
+
 extern "C" int td_mol_host(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
                            const td_read_result* res, const int8_t* labels, td_census_entry** entries, int64_t* n, td_mol_totals* totals)
 {
-	return host_count("td_mol_host", false, m, prefix_bases, codes, offs, n_reads, res, labels, entries, nullptr, n, totals);
+	return td_mol_host_mated(m, prefix_bases, codes, offs, n_reads, res, labels, nullptr, entries, n, totals);
+}
+
+extern "C" int td_mol_host_origins_mated(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                                         const td_read_result* res, const int8_t* labels, const td_mol_mate* mate, td_census_entry** entries,
+                                         td_mol_origin** origins, int64_t* n, td_mol_totals* totals)
+{
+	return host_count(mate ? "td_mol_host_origins_mated" : "td_mol_host_origins", true, m, prefix_bases, codes, offs, n_reads, res, labels, mate, entries,
+	                  origins, n, totals);
 }
 
 extern "C" int td_mol_host_origins(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
                                    const td_read_result* res, const int8_t* labels, td_census_entry** entries, td_mol_origin** origins, int64_t* n,
                                    td_mol_totals* totals)
 {
-	return host_count("td_mol_host_origins", true, m, prefix_bases, codes, offs, n_reads, res, labels, entries, origins, n, totals);
+	return td_mol_host_origins_mated(m, prefix_bases, codes, offs, n_reads, res, labels, nullptr, entries, origins, n, totals);
 }
 
 extern "C" int td_mol_dedup_host(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
                                  const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate, td_mol_dedup_totals* totals)
 {
-	if (host_checks("td_mol_dedup_host", m, prefix_bases, n_reads >= 0 && (n_reads == 0 || (offs && res && labels && codes && is_duplicate))) != TD_OK) return TD_FAIL;
+	return td_mol_dedup_host_mated(m, prefix_bases, codes, offs, n_reads, res, labels, nullptr, is_duplicate, totals);
+}
+
+extern "C" int td_mol_dedup_host_mated(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs, int64_t n_reads,
+                                       const td_read_result* res, const int8_t* labels, const td_mol_mate* mate, uint8_t* is_duplicate,
+                                       td_mol_dedup_totals* totals)
+{
+	if (host_checks(mate ? "td_mol_dedup_host_mated" : "td_mol_dedup_host", m, prefix_bases, mate, n_reads, n_reads >= 0 && (n_reads == 0 || (offs && res && labels && codes && is_duplicate))) != TD_OK) return TD_FAIL;
 	td_mol_dedup_totals t{};
 	std::unordered_set<uint64_t> seen;                // the keys of the reads so far: a read's ordinal is its index, the first one stays
 	for (int64_t i = 0; i < n_reads; i++) {
 		is_duplicate[i] = 0;
 		uint64_t key = 0;
 		td_mol_origin o{};
-		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key, &o);
+		const int cls = host_read_class(m, prefix_bases, codes, offs, i, res, labels, mate, &key, &o);
 		if (cls == MOL_NOT_ELIGIBLE) continue;
 		if (cls != MOL_COUNTED) { t.unjudged++; t.kept++; continue; }
 		if (seen.insert(key).second) t.kept++;
@@ -202,7 +244,14 @@ extern "C" int td_mol_dedup_collapsed_host(const td_model_desc* m, int32_t prefi
                                            const td_read_result* res, const int8_t* labels, uint8_t* is_duplicate, td_mol_dedup_totals* totals,
                                            td_mol_collapse_totals* collapse_totals)
 {
-	if (host_checks("td_mol_dedup_collapsed_host", m, prefix_bases, n_reads >= 0 && (n_reads == 0 || (offs && res && labels && codes && is_duplicate))) != TD_OK)
+	return td_mol_dedup_collapsed_host_mated(m, prefix_bases, codes, offs, n_reads, res, labels, nullptr, is_duplicate, totals, collapse_totals);
+}
+
+extern "C" int td_mol_dedup_collapsed_host_mated(const td_model_desc* m, int32_t prefix_bases, const uint8_t* codes, const int64_t* offs,
+                                                 int64_t n_reads, const td_read_result* res, const int8_t* labels, const td_mol_mate* mate,
+                                                 uint8_t* is_duplicate, td_mol_dedup_totals* totals, td_mol_collapse_totals* collapse_totals)
+{
+	if (host_checks(mate ? "td_mol_dedup_collapsed_host_mated" : "td_mol_dedup_collapsed_host", m, prefix_bases, mate, n_reads, n_reads >= 0 && (n_reads == 0 || (offs && res && labels && codes && is_duplicate))) != TD_OK)
 		return TD_FAIL;
 	// the survey: every counted read's key and origin, and the first ordinal of every key (a read's ordinal is its index)
 	std::vector<uint64_t> key_of((size_t)n_reads, 0);
@@ -212,7 +261,7 @@ extern "C" int td_mol_dedup_collapsed_host(const td_model_desc* m, int32_t prefi
 	std::unordered_map<uint64_t, int64_t> first;
 	for (int64_t i = 0; i < n_reads; i++) {
 		td_mol_origin o{};
-		cls_of[(size_t)i] = host_read_class(m, prefix_bases, codes, offs, i, res, labels, &key_of[(size_t)i], &o);
+		cls_of[(size_t)i] = host_read_class(m, prefix_bases, codes, offs, i, res, labels, mate, &key_of[(size_t)i], &o);
 		if (cls_of[(size_t)i] != MOL_COUNTED) continue;
 		each.push_back(td_census_entry{ key_of[(size_t)i], 1 });
 		each_o.push_back(o);

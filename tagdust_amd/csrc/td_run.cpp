@@ -170,7 +170,7 @@ struct OptSpec { const char* name; int arg; int id; };
 enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
        O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS, O_DEDUP, O_COLLAPSE,
-       O_DEDUP_COLLAPSED, O_UNSUPPORTED = 100 };
+       O_DEDUP_COLLAPSED, O_MATE_BASES, O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
 	{ "7", 1, O_SEG + 6 }, { "8", 1, O_SEG + 7 }, { "9", 1, O_SEG + 8 }, { "10", 1, O_SEG + 9 },
@@ -196,7 +196,7 @@ const OptSpec kOwnOpts[] = {
 	{ "unknown-barcodes", 1, O_UNKNOWN }, { "unknown-barcodes-slots", 1, O_UNKNOWN_SLOTS },
 	{ "fingerprint-seq", 0, O_FINGER_SEQ }, { "molecules", 0, O_MOLECULES }, { "molecules-prefix", 1, O_MOLECULES_PREFIX },
 	{ "molecules-slots", 1, O_MOLECULES_SLOTS }, { "dedup", 0, O_DEDUP }, { "collapse-umis", 0, O_COLLAPSE },
-	{ "dedup-collapsed", 0, O_DEDUP_COLLAPSED },
+	{ "dedup-collapsed", 0, O_DEDUP_COLLAPSED }, { "mate-bases", 1, O_MATE_BASES },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -298,7 +298,11 @@ extern "C" const char* td_run_usage(void)
 	       "\t                            --molecules; needs an F segment; --dedup still matches exactly)\n"
 	       "\t--dedup-collapsed           write one read per collapsed molecule: the input file is read twice, first to count, then to\n"
 	       "\t                            write the first read that carries each collapsed molecule's own barcode, fingerprint and start\n"
-	       "\t                            (implies --dedup, --collapse-umis and --molecules; a file, not stdin)\n\n";
+	       "\t                            (implies --dedup, --collapse-umis and --molecules; a file, not stdin)\n"
+	       "\t--mate-bases M              two or more input files: the first M bases of the read's mate, the record of the first other\n"
+	       "\t                            file, belong to a molecule's identity behind the read's own --molecules-prefix bases, 1..31,\n"
+	       "\t                            both at most 32 together (implies --molecules; one file with an architecture other than R:N,\n"
+	       "\t                            one device, -dust 0, no -ref)\n\n";
 }
 
 extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
@@ -371,12 +375,17 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 		case O_DEDUP: o->dedup = 1; break;
 		case O_COLLAPSE: o->collapse_umis = 1; break;
 		case O_DEDUP_COLLAPSED: o->dedup_collapsed = 1; break;
+		case O_MATE_BASES:
+			o->mate_bases = atoi(v);
+			if (o->mate_bases < 1 || o->mate_bases > TD_MOL_MAX_PREFIX - 1) return bad("--mate-bases: need 1..31 bases of the mate");
+			break;
 		default: return bad("unknown option " + a);
 		}
 	}
 	if (o->dedup_collapsed) { o->dedup = 1; o->collapse_umis = 1; }   // the second pass of the two together
 	if (o->dedup) o->molecules = 1;   // the duplicates are those of the molecule count
 	if (o->collapse_umis) o->molecules = 1;   // ... and so are the molecules that are collapsed
+	if (o->mate_bases) o->molecules = 1;      // ... and the mate joins the molecule count's key
 	if (o->num_threads < 1) return bad("option -t: need at least one thread");
 	if (o->host_threads < 0 || o->batch_reads < 0) return bad("--host-threads / --batch-reads: negative value");
 	if (o->unknown_slots_log2 < 4 || o->unknown_slots_log2 > 26) return bad("--unknown-barcodes-slots: need 4..26 (the table has 2^N slots)");
@@ -407,6 +416,8 @@ struct td_run_plan_t {
 	bool dedup = false;
 	bool collapse = false;
 	bool dedup_collapsed = false;
+	int mate_bases = 0;                      // --mate-bases: 0 = off
+	int mol_file = 0, mate_file = -1;        // ... the one decoded file and its mate, once every architecture is known
 };
 
 namespace {
@@ -424,9 +435,22 @@ std::string unknown_file_name(const td_run_opts* o) { return std::string(o->outf
 std::string molecules_file_name(const td_run_opts* o) { return std::string(o->outfile) + "_molecules.txt"; }
 
 // what the controller decides once every file's architecture is known (barcode_hmm.c:130-159): TD_FAIL with the reference's message
-int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& archs, int& bar_file, int& num_out_reads, std::vector<std::string>& names)
+// (mol_file: the file whose contexts count molecules -- file 0, or with --mate-bases the one file that is decoded; mate_file: its mate)
+int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& archs, int& bar_file, int& num_out_reads, std::vector<std::string>& names,
+                   int* mol_file = nullptr, int* mate_file = nullptr)
 {
 	bar_file = -1; num_out_reads = 0;
+	int mol = 0, mate = -1;
+	if (o->mate_bases) {
+		int n_decoded = 0;
+		for (size_t k = 0; k < archs.size(); k++) if (!is_read_only(archs[k]) && n_decoded++ == 0) mol = (int)k;
+		if (n_decoded != 1)
+			return run_fail("--mate-bases: exactly one input file may have an architecture other than R:N (%d have): barcode and fingerprint of a "
+			                "molecule come from one decoded file, every other file gives reads.", n_decoded);
+		mate = mol == 0 ? 1 : 0;                 // the first file in call order other than the decoded one
+	}
+	if (mol_file) *mol_file = mol;
+	if (mate_file) *mate_file = mate;
 	for (size_t k = 0; k < archs.size(); k++) {
 		if (has_barcode(archs[k])) {
 			if (bar_file >= 0) return run_fail("Barcodes seem to be in both architectures... ");
@@ -443,7 +467,7 @@ int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& arch
 	}
 	if (o->molecules) {
 		if (archs.size() == 1 && is_read_only(archs[0])) return run_fail("--molecules: the architecture is a single read segment: there is no model whose labels mark a barcode or a fingerprint.");
-		if (o->collapse_umis && !has_fingerprint(archs[0]))
+		if (o->collapse_umis && !has_fingerprint(archs[(size_t)mol]))
 			return run_fail("--collapse-umis: the architecture has no fingerprint (F) segment: there is no UMI whose neighbours could be collapsed.");
 		names.push_back(molecules_file_name(o));
 	}
@@ -472,7 +496,18 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	if (o->arch_file && !file_exists(o->arch_file)) return run_fail("ERROR: Arch file:%s does not exists.", o->arch_file);
 	if (o->unknown_barcodes > 0 && (o->matchstart != -1 || o->matchend != -1))
 		return run_fail("--unknown-barcodes cannot be combined with -start / -end: labels behind a window do not spell the barcode.");
-	if (o->molecules && o->n_infiles != 1)
+	if (o->mate_bases) {
+		if (o->n_infiles < 2)
+			return run_fail("--mate-bases needs two or more input files (%d given): the mate is the record of a second file.", o->n_infiles);
+		if (o->molecules_prefix + o->mate_bases > TD_MOL_MAX_PREFIX)
+			return run_fail("--molecules-prefix %d and --mate-bases %d are %d bases together: at most %d fit the key's one 64-bit word.", o->molecules_prefix,
+			                o->mate_bases, o->molecules_prefix + o->mate_bases, TD_MOL_MAX_PREFIX);
+		if (o->n_devices > 1)
+			return run_fail("--mate-bases needs exactly one device (%d given): the mate batch travels with its reads to the one context that counts them.", o->n_devices);
+		if (o->dedup_collapsed)
+			return run_fail("--mate-bases cannot be combined with --dedup-collapsed: the survey reads one file.");
+	}
+	if (o->molecules && !o->mate_bases && o->n_infiles != 1)
 		return run_fail("--molecules needs exactly one input file (%d given): a read and its fingerprint in different files are not joined.", o->n_infiles);
 	if (o->molecules && (o->matchstart != -1 || o->matchend != -1))
 		return run_fail("--molecules cannot be combined with -start / -end: labels behind a window do not mark the read's bases.");
@@ -499,6 +534,10 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 		p->dust = 0;
 		p->use_ref = false;
 	}
+	p->mate_bases = o->mate_bases;
+	if (o->mate_bases && (p->dust != 0 || p->use_ref))
+		return run_fail("--mate-bases: the mate is not decoded and its outcome is not joined to the count, so a mate that DUST or the -ref filter "
+		                "rejects would take a molecule's one kept read out of the files: run with -dust 0 and without -ref.");
 	if (p->use_ref && !file_exists(o->reference_fasta)) return run_fail("ERROR: Reference file:%s does not exists.", o->reference_fasta);
 	if (o->arch_file && !read_arch_file(o->arch_file, p->arch_file, why)) return run_fail("%s", why.c_str());
 	// barcode_hmm.c:105-129
@@ -523,7 +562,7 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	}
 	std::vector<const td_arch*> view;
 	for (auto& a : archs) view.push_back(a.get());
-	if (p->all_known && decide_outputs(o, view, p->bar_file, p->num_out_reads, p->out_files) != TD_OK) return TD_FAIL;
+	if (p->all_known && decide_outputs(o, view, p->bar_file, p->num_out_reads, p->out_files, &p->mol_file, &p->mate_file) != TD_OK) return TD_FAIL;
 	*out = p.release();
 	return TD_OK;
 }
@@ -548,6 +587,11 @@ extern "C" int64_t td_run_plan_describe(const td_run_plan_t* p, char* buf, int64
 	if (p->collapse) s += "collapse: fingerprints one mismatch apart are counted as one molecule (directional rule; the count and --dedup stay exact)\n";
 	if (p->dedup_collapsed)
 		s += "dedup-collapsed: the input is read twice, a survey and then the run: one read per collapsed molecule is written, the first that carries the root's barcode, fingerprint and start\n";
+	if (p->mate_bases) {
+		s += "mate: " + std::to_string(p->mate_bases) + " bases of the mate join the molecule key behind the read's own prefix; the mate's own outcome takes no part";
+		if (p->all_known) s += " (file " + std::to_string(p->mol_file) + " is decoded, file " + std::to_string(p->mate_file) + " is its mate)";
+		s += "\n";
+	}
 	if (p->all_known) {
 		s += "barcode file: " + (p->bar_file >= 0 ? std::to_string(p->bar_file) : std::string("none")) + "\n";
 		s += "output reads: " + std::to_string(p->num_out_reads) + "\n";
@@ -721,6 +765,7 @@ struct Run {
 	int dust = 0;
 	bool use_ref = false;
 	float error_rate = 0.05f;
+	int mol_file = 0, mate_file = -1;     // the file whose contexts count molecules; with --mate-bases its mate, else -1
 
 	int head_limit() const { return o->flavour ? 1001000 : 1000001; }   // io.c:125-188 with num_query 1000 / 1 000 001
 
@@ -863,7 +908,7 @@ int Run::execute()
 	{
 		std::vector<const td_arch*> view;
 		for (auto& f : files) view.push_back(f.arch.get());
-		if (decide_outputs(o, view, bar_file, num_out_reads, out_files) != TD_OK) { log.add(g_run_error + "\n"); return TD_FAIL; }
+		if (decide_outputs(o, view, bar_file, num_out_reads, out_files, &mol_file, &mate_file) != TD_OK) { log.add(g_run_error + "\n"); return TD_FAIL; }
 	}
 
 	// 2. sequence statistics over the head of every file, io.c:52-300
@@ -947,12 +992,16 @@ int Run::execute()
 			// --unknown-barcodes: the contexts of the barcode file count what their reads spell in the last 'B' segment
 			if (o->unknown_barcodes > 0 && k == bar_file &&
 			    td_census_enable(c, -1, TD_CENSUS_DEFAULT_MASK, o->unknown_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
-			// --molecules: the contexts of the one input file count its extracted reads per barcode, fingerprint and start of the read
+			// --molecules: the contexts of the one input file (with --mate-bases: of the one decoded file) count its extracted reads per
+			// barcode, fingerprint and start of the read
+			if (k != mol_file) continue;
 			if (o->molecules && td_mol_enable(c, o->molecules_prefix, o->molecules_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
 			// --dedup: ... and mark every read that is not the first of its molecule; the writer leaves those out
 			if (o->dedup && td_mol_dedup_enable(c) != TD_OK) return fail("%s", td_last_error(c));
 			// --collapse-umis: ... and keep what every key was made of, for the collapse behind the run
 			if (o->collapse_umis && td_mol_collapse_enable(c) != TD_OK) return fail("%s", td_last_error(c));
+			// --mate-bases: ... and take the first bases of every read's mate into the key (td_stream_run_multi names the mate batches)
+			if (o->mate_bases && td_mol_mate_enable(c, o->mate_bases) != TD_OK) return fail("%s", td_last_error(c));
 		}
 	}
 	rep->compile_wait_s = now_s() - t0;
@@ -1042,7 +1091,7 @@ int Run::unknown_barcodes(int bar_file)
 // log), and <out>_molecules.txt
 int Run::molecules()
 {
-	FileState& f = files[0];
+	FileState& f = files[(size_t)mol_file];
 	td_mol_row* rows = (td_mol_row*)calloc(TD_NUM_BARCODE_BINS, sizeof(td_mol_row));
 	if (!rows) return fail("--molecules: out of memory");
 	rep->molecules = rows;
@@ -1106,8 +1155,9 @@ int Run::molecules()
 	const std::string name = molecules_file_name(o);
 	FILE* out = fopen(name.c_str(), "w");
 	if (!out) return fail("Failed to open file:%s", name.c_str());
-	fprintf(out, "# molecules: the extracted reads of %s by barcode, fingerprint and the first bases of the read\n", o->infile[0]);
+	fprintf(out, "# molecules: the extracted reads of %s by barcode, fingerprint and the first bases of the read\n", o->infile[mol_file]);
 	fprintf(out, "# prefix bases\t%d\n", o->molecules_prefix);
+	if (o->mate_bases) fprintf(out, "# mate bases\t%d\n# mate file\t%s\n", o->mate_bases, o->infile[mate_file]);
 	fprintf(out, "# extracted reads\t%lld\n# counted\t%lld\n# molecules\t%lld\n# no read base\t%lld\n# N in the prefix\t%lld\n",
 	        (long long)sum.eligible, (long long)sum.counted, (long long)sum.molecules, (long long)sum.skipped_empty, (long long)sum.skipped_n);
 	if (sum.overflow > 0)
@@ -1175,7 +1225,8 @@ int Run::run_files(td_stream_stats& st)
 	for (int k = 0; k < K; k++) {
 		sf[(size_t)k].path = o->infile[k];
 		sf[(size_t)k].arch = files[(size_t)k].arch.get();
-		sf[(size_t)k].ctx = files[(size_t)k].raw.data();
+		// (--mate-bases: the other files get no contexts -- their reads are uploaded once, as mates, by the decoded file's context)
+		sf[(size_t)k].ctx = o->mate_bases && k != mol_file ? nullptr : files[(size_t)k].raw.data();
 	}
 	if (td_stream_run_multi_hits(sf.data(), K, o->n_devices, o->outfile, dust, &so, &st, rep->counts, rep->artifact_hits, rep->n_artifacts) != TD_OK)
 		return run_fail("%s", td_io_last_error());

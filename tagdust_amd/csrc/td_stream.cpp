@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "../../include/tagdust_io.h"
+#include "../../include/tagdust_molecules.h"   // td_mol_mate_next: pair mode of td_stream_run_multi
 #include "td_io_internal.h"
 #include "td_merge_internal.h"
 
@@ -1050,6 +1051,7 @@ struct Tuple {                        // batch j of every input file: records [j
 struct Target {                       // where the batches of one input file go
 	td_ctx* const* ctx;               // its context on each of the N devices; NULL: no device sees this file
 	bool rna;                         // run_rna_dust (TD_MODE_RNA_DUST: the reads come back unchanged) instead of the HMM
+	int mate = -1;                    // pair mode: the file whose batch is this file's mate batch (td_mol_mate_next), else -1
 };
 
 // Starts the readers, runs the write stage on a thread of its own (`write` for every finished tuple in input order, then the
@@ -1136,7 +1138,9 @@ void run_stages(const std::string& prefix, RunError& err, const std::vector<std:
 				if (hi <= lo) continue;
 				const bool r = dev[(size_t)k].rna;
 				// (the window: the artifact filter's thread ranges are those of the whole batch, not of a device's range)
+				// (pair mode, one device: the tuple's batch of the mate file goes up with this one, on the same upload stream)
 				ok = (N == 1 || td_set_batch_window(ctx, lo, n) == TD_OK) &&
+				     (dev[(size_t)k].mate < 0 || td_mol_mate_next(ctx, t->b[(size_t)dev[(size_t)k].mate]->codes, t->b[(size_t)dev[(size_t)k].mate]->offs, n) == TD_OK) &&
 				     td_submit(ctx, b->codes, 0, b->offs + lo, hi - lo, r ? TD_MODE_RNA_DUST : TD_MODE_GET_LABEL, b->res + lo, nullptr,
 				               r ? nullptr : b->seq_out + b->offs[lo], &t->tickets[(size_t)(k * N + d)]) == TD_OK;
 				if (!ok) err.fail(prefix + td_last_error(ctx));
@@ -1355,6 +1359,8 @@ struct MultiPlan {
 	int n_art = 0;                    // files whose contexts have a -ref artifact filter: none or all
 	std::vector<int> read_present;    // read segments of every file
 	std::vector<char> rna;            // run_rna_dust on the file's devices (TD_MODE_RNA_DUST)
+	// pair mode (tagdust_molecules.h, mate mode): the contexts of the one decoded file report mate_bases > 0
+	int mol_file = -1, mate_file = -1;   // the decoded file and its mate: the first file in call order other than it (-1: no pair mode)
 };
 
 // false: the files cannot make a run (td_io_set_error says why)
@@ -1402,6 +1408,39 @@ bool plan_multi(const td_stream_file* files, const int K, const int N, const int
 			if (!artifacts_active(files[k].ctx[0])) { td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set for some files but not for ") + files[k].path); return false; }
 		}
 	}
+	// pair mode: a decoded file whose contexts are in mate mode takes the first other file's batches as its mate batches
+	int n_decoded = 0, decoded = -1;
+	for (int k = 0; k < K; k++) {
+		if (!files[k].ctx || m.rna[(size_t)k]) continue;
+		n_decoded++;
+		int32_t mb = 0;
+		(void)td_get_option(files[k].ctx[0], "mate_bases", &mb);
+		if (mb > 0 && decoded < 0) decoded = k;
+	}
+	if (decoded >= 0) {
+		if (N > 1) { td_io_set_error("td_stream_run_multi: mate mode is on and " + std::to_string(N) + " devices are given: a mate batch travels with its reads to one context (one device)"); return false; }
+		if (n_decoded != 1 || K < 2) {
+			td_io_set_error("td_stream_run_multi: mate mode is on and " + std::to_string(n_decoded) + " of " + std::to_string(K) +
+			                " files are decoded: exactly one may be, and every other file, at least one, must be R:N");
+			return false;
+		}
+		for (int k = 0; k < K; k++) {
+			const td_arch* a = files[k].arch;
+			if (k != decoded && !(a->n_segments == 1 && a->type[0] == 'R')) {
+				td_io_set_error(std::string("td_stream_run_multi: mate mode is on and ") + files[k].path + " is not R:N: every file but the decoded one must be");
+				return false;
+			}
+		}
+		int32_t cd = 0;
+		(void)td_get_option(files[decoded].ctx[0], "dust", &cd);
+		if (m.n_art > 0 || dust != 0 || cd != 0) {
+			td_io_set_error("td_stream_run_multi: mate mode is on with a -ref filter or DUST: the mate's own outcome is not joined to the count, so a mate "
+			                "that could fail would take a molecule's one kept read out of the files (run with dust 0 and without a filter)");
+			return false;
+		}
+		m.mol_file = decoded;
+		m.mate_file = decoded == 0 ? 1 : 0;
+	}
 	if (m.num_out_reads == 0) { td_io_set_error("td_stream_run_multi: no read segment in any architecture: no output files to create (io.c:846-852)"); return false; }
 	return true;
 }
@@ -1443,8 +1482,9 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 	std::vector<Target> dev;
 	for (int k = 0; k < K; k++) {
 		// (a file that is not decoded needs no page-locked buffers, nor does one whose reads come back unchanged need room for rewritten ones)
-		readers.emplace_back(new Reader(err, o, files[k].ctx == nullptr, files[k].ctx != nullptr && !m.rna[(size_t)k], std::max(1, o.n_threads / K)));
-		dev.push_back(Target{ files[k].ctx, m.rna[(size_t)k] != 0 });
+		// (... but the mate file of pair mode does: its batches are uploaded from where they lie)
+		readers.emplace_back(new Reader(err, o, files[k].ctx == nullptr && k != m.mate_file, files[k].ctx != nullptr && !m.rna[(size_t)k], std::max(1, o.n_threads / K)));
+		dev.push_back(Target{ files[k].ctx, m.rna[(size_t)k] != 0, k == m.mol_file ? m.mate_file : -1 });
 		if (!readers.back()->src.open(files[k].path, o.block_bytes, why)) { td_io_set_error(why); return TD_FAIL; }
 	}
 
@@ -1496,8 +1536,11 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 			for (int k = 0; k < K; k++) c = std::max(c, t.b[(size_t)k]->res[i].read_type);
 			ctype[(size_t)i] = c;
 			cbar[(size_t)i] = t.b[(size_t)(m.bar_file >= 0 ? m.bar_file : 0)]->res[i].barcode;
-			cnt[c & (TD_NUM_OUTCOME_SLOTS - 1)]++;                                      // the controller's counting, :354-384
-			if (c == TD_EXTRACT_SUCCESS && cbar[(size_t)i] >= 0) cnt[TD_NUM_OUTCOME_SLOTS + (cbar[(size_t)i] & 0xFF)]++;
+			// the controller's counting, :354-384; a duplicate (dedup, tagdust_molecules.h) counts as the extracted read it was decoded
+			// as, under its barcode bin: what the single-file run's device counters do
+			const int32_t cc = (c & 0xFF) == TD_EXTRACT_DUPLICATE ? TD_EXTRACT_SUCCESS : c;
+			cnt[cc & (TD_NUM_OUTCOME_SLOTS - 1)]++;
+			if (cc == TD_EXTRACT_SUCCESS && cbar[(size_t)i] >= 0) cnt[TD_NUM_OUTCOME_SLOTS + (cbar[(size_t)i] & 0xFF)]++;
 			// reference_fasta->mer_hash (:381): on the combined outcome, which is the largest of the files' -- of two files' hits the later sequence
 			if (artifact_hits && (c & 0xFF) == TD_EXTRACT_FAIL_MATCHES_ARTIFACTS && (c >> 8) >= 1 && (c >> 8) <= n_artifacts) artifact_hits[(c >> 8) - 1]++;
 		}

@@ -55,7 +55,9 @@ CENSUS_MAX_WORD = 28
 MOL_ABI_SYMBOLS = ["td_mol_enable", "td_mol_disable", "td_mol_reset", "td_mol_entries", "td_mol_get", "td_mol_summarise", "td_mol_host",
                    "td_mol_key", "td_mol_key_bin", "td_mol_dedup_enable", "td_mol_dedup_disable", "td_mol_dedup_get", "td_mol_dedup_host",
                    "td_mol_collapse_enable", "td_mol_collapse_disable", "td_mol_origins", "td_mol_collapse_get", "td_mol_collapse_entries",
-                   "td_mol_host_origins", "td_mol_collapse_host", "td_mol_dedup_freeze", "td_mol_dedup_collapsed_host"]
+                   "td_mol_host_origins", "td_mol_collapse_host", "td_mol_dedup_freeze", "td_mol_dedup_collapsed_host",
+                   "td_mol_mate_enable", "td_mol_mate_disable", "td_mol_mate_next", "td_mol_host_mated", "td_mol_host_origins_mated",
+                   "td_mol_dedup_host_mated", "td_mol_dedup_collapsed_host_mated"]
 MOL_TOTALS = ("eligible", "counted", "skipped_empty", "skipped_n", "overflow", "molecules")
 MOL_DEDUP_TOTALS = ("kept", "duplicates", "unjudged")
 MOL_COLLAPSE_TOTALS = ("molecules_before", "molecules_after", "absorbed", "longest_chain")
@@ -618,6 +620,12 @@ class _RunOpts(C.Structure):
                 ("dedup", C.c_int32), ("collapse_umis", C.c_int32), ("dedup_collapsed", C.c_int32)]
 
 
+class _RunOptsMate(C.Structure):
+    """td_run_opts (include/tagdust_run.h) as it is now: _RunOpts -- whose last field tests/test_dedup_collapsed.py pins -- and the
+    field appended behind it; this is the structure every td_run_* call is given"""
+    _fields_ = _RunOpts._fields_ + [("mate_bases", C.c_int32)]
+
+
 class _CensusTotals(C.Structure):
     """td_census_totals (include/tagdust_census.h)"""
     _fields_ = [(f, C.c_int64) for f in CENSUS_TOTALS]
@@ -650,6 +658,11 @@ class _MolCollapseTotals(C.Structure):
         return {f: int(getattr(self, f)) for f in MOL_COLLAPSE_TOTALS}
 
 
+class _MolMate(C.Structure):
+    """td_mol_mate (include/tagdust_molecules.h)"""
+    _fields_ = [("codes", C.c_void_p), ("offs", C.c_void_p), ("bases", C.c_int32)]
+
+
 class _RunReport(C.Structure):
     """td_run_report (include/tagdust_run.h)"""
     _fields_ = [("error", C.c_char * 1024), ("counts", C.c_int64 * NUM_COUNTERS), ("n_artifacts", C.c_int32),
@@ -665,23 +678,23 @@ class _RunReport(C.Structure):
 
 def _run_lib():
     lib = load_library()
-    lib.td_run_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(_RunOpts)), C.c_char_p, C.c_size_t]
-    lib.td_run_opts_free.argtypes = [C.POINTER(_RunOpts)]
+    lib.td_run_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(_RunOptsMate)), C.c_char_p, C.c_size_t]
+    lib.td_run_opts_free.argtypes = [C.POINTER(_RunOptsMate)]
     lib.td_run_opts_free.restype = None
     lib.td_run_last_error.restype = C.c_char_p
-    lib.td_run_plan.argtypes = [C.POINTER(_RunOpts), C.POINTER(C.c_void_p)]
+    lib.td_run_plan.argtypes = [C.POINTER(_RunOptsMate), C.POINTER(C.c_void_p)]
     lib.td_run_plan_free.argtypes = [C.c_void_p]
     lib.td_run_plan_free.restype = None
     lib.td_run_plan_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.td_run_plan_describe.restype = C.c_int64
-    lib.td_run_output_files_describe.argtypes = [C.POINTER(_RunOpts), C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_int64]
+    lib.td_run_output_files_describe.argtypes = [C.POINTER(_RunOptsMate), C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_int64]
     lib.td_run_output_files_describe.restype = C.c_int64
     lib.td_run_arch_file_describe.argtypes = [C.c_char_p, C.c_char_p, C.c_int64]
     lib.td_run_arch_file_describe.restype = C.c_int64
-    lib.td_run_execute.argtypes = [C.POINTER(_RunOpts), C.POINTER(_RunReport)]
+    lib.td_run_execute.argtypes = [C.POINTER(_RunOptsMate), C.POINTER(_RunReport)]
     lib.td_run_report_clear.argtypes = [C.POINTER(_RunReport)]
     lib.td_run_report_clear.restype = None
-    lib.td_run_format_summary.argtypes = [C.POINTER(_RunOpts), C.POINTER(_RunReport), C.c_char_p, C.c_int64]
+    lib.td_run_format_summary.argtypes = [C.POINTER(_RunOptsMate), C.POINTER(_RunReport), C.c_char_p, C.c_int64]
     lib.td_run_format_summary.restype = C.c_int64
     return lib
 
@@ -693,7 +706,7 @@ class RunOpts:
         self.lib = _run_lib()
         argv = [b"tagdust-hip"] + [os.fsencode(a) for a in args]
         arr = (C.c_char_p * len(argv))(*argv)
-        self.p = C.POINTER(_RunOpts)()
+        self.p = C.POINTER(_RunOptsMate)()
         err = C.create_string_buffer(1024)
         if self.lib.td_run_parse_args(len(argv), arr, C.byref(self.p), err, len(err)) != 0:
             self.p = None
@@ -896,6 +909,15 @@ def _mol_lib():
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(_MolTotals)]
     lib.td_mol_collapse_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_int64), C.POINTER(_MolCollapseTotals)]
+    lib.td_mol_mate_enable.argtypes = [C.c_void_p, C.c_int32]
+    lib.td_mol_mate_disable.argtypes = [C.c_void_p]
+    lib.td_mol_mate_next.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    mate = C.POINTER(_MolMate)
+    lib.td_mol_host_mated.argtypes = lib.td_mol_host.argtypes[:7] + [mate] + lib.td_mol_host.argtypes[7:]
+    lib.td_mol_host_origins_mated.argtypes = lib.td_mol_host_origins.argtypes[:7] + [mate] + lib.td_mol_host_origins.argtypes[7:]
+    lib.td_mol_dedup_host_mated.argtypes = lib.td_mol_dedup_host.argtypes[:7] + [mate] + lib.td_mol_dedup_host.argtypes[7:]
+    lib.td_mol_dedup_collapsed_host_mated.argtypes = (lib.td_mol_dedup_collapsed_host.argtypes[:7] + [mate] +
+                                                      lib.td_mol_dedup_collapsed_host.argtypes[7:])
     lib.free.argtypes = [C.c_void_p]
     lib.free.restype = None
     return lib
@@ -1019,6 +1041,93 @@ def mol_dedup_collapsed_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAUL
     tot, ctot = _MolDedupTotals(), _MolCollapseTotals()
     rc = lib.td_mol_dedup_collapsed_host(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
                                          labels.ctypes.data, dup.ctypes.data, C.byref(tot), C.byref(ctot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return dup[:len(offs) - 1].astype(bool), tot.as_dict(), ctot.as_dict()
+
+
+def _mol_mated_args(md, seq, offs, res, labels, mate):
+    """what the *_mated host functions share: the model description, the arrays as the C side reads them, and the td_mol_mate (mate:
+    None, or (codes, offs, bases) with one mate per read in the reads' order).  The last item keeps everything alive."""
+    desc, keep = make_model_desc(md)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if len(seq) == 0:
+        seq = np.zeros(1, np.uint8)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
+    for f in ("read_type", "barcode", "fingerprint"):
+        rr[f] = np.asarray(res[f])
+    mp, mkeep = None, None
+    if mate is not None:
+        mc = np.ascontiguousarray(mate[0], np.uint8)
+        if len(mc) == 0:
+            mc = np.zeros(1, np.uint8)
+        mo = np.ascontiguousarray(mate[1], np.int64)
+        if len(mo) != len(offs):
+            raise ValueError("the mate batch has %d reads, the batch %d" % (len(mo) - 1, len(offs) - 1))
+        mm = _MolMate(mc.ctypes.data, mo.ctypes.data, int(mate[2]))
+        mp, mkeep = C.byref(mm), (mc, mo, mm)
+    return desc, seq, offs, rr, labels, mp, (keep, mkeep)
+
+
+def mol_host_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_host_mated: mol_host with the mate batch joined into the key (mate: (codes, offs, bases), or None for mol_host itself)."""
+    lib = _mol_lib()
+    desc, seq, offs, rr, labels, mp, keep = _mol_mated_args(md, seq, offs, res, labels, mate)
+    ptr, n, tot = C.c_void_p(), C.c_int64(), _MolTotals()
+    rc = lib.td_mol_host_mated(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
+                               labels.ctypes.data, mp, C.byref(ptr), C.byref(n), C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    try:
+        return _census_entries(ptr, n.value), tot.as_dict()
+    finally:
+        lib.td_census_free(ptr)
+
+
+def mol_host_origins_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_host_origins_mated: mol_host_origins with the mate batch joined into the key (mate as mol_host_mated takes it)."""
+    lib = _mol_lib()
+    desc, seq, offs, rr, labels, mp, keep = _mol_mated_args(md, seq, offs, res, labels, mate)
+    ptr, optr, n, tot = C.c_void_p(), C.c_void_p(), C.c_int64(), _MolTotals()
+    rc = lib.td_mol_host_origins_mated(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
+                                       labels.ctypes.data, mp, C.byref(ptr), C.byref(optr), C.byref(n), C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    try:
+        return _census_entries(ptr, n.value), _mol_origin_array(optr, n.value), tot.as_dict()
+    finally:
+        lib.td_census_free(ptr)
+        lib.free(optr)
+
+
+def mol_dedup_host_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_dedup_host_mated: mol_dedup_host with the mate batch joined into the key (mate as mol_host_mated takes it)."""
+    lib = _mol_lib()
+    desc, seq, offs, rr, labels, mp, keep = _mol_mated_args(md, seq, offs, res, labels, mate)
+    dup = np.zeros(max(len(offs) - 1, 1), np.uint8)
+    tot = _MolDedupTotals()
+    rc = lib.td_mol_dedup_host_mated(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
+                                     labels.ctypes.data, mp, dup.ctypes.data, C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return dup[:len(offs) - 1].astype(bool), tot.as_dict()
+
+
+def mol_dedup_collapsed_host_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_dedup_collapsed_host_mated: mol_dedup_collapsed_host with the mate batch joined into the key (mate as mol_host_mated
+    takes it)."""
+    lib = _mol_lib()
+    desc, seq, offs, rr, labels, mp, keep = _mol_mated_args(md, seq, offs, res, labels, mate)
+    dup = np.zeros(max(len(offs) - 1, 1), np.uint8)
+    tot, ctot = _MolDedupTotals(), _MolCollapseTotals()
+    rc = lib.td_mol_dedup_collapsed_host_mated(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1,
+                                               rr.ctypes.data, labels.ctypes.data, mp, dup.ctypes.data, C.byref(tot), C.byref(ctot))
     del keep
     if rc != 0:
         raise TdError(lib.td_last_error(None).decode())
@@ -1264,6 +1373,19 @@ class TagdustHip:
 
     def mol_reset(self):
         self._chk(_mol_lib().td_mol_reset(self.h))
+
+    def mol_mate_enable(self, mate_bases):
+        """td_mol_mate_enable: from now on the first mate_bases bases of every read's mate belong to its key (an empty table)"""
+        self._chk(_mol_lib().td_mol_mate_enable(self.h, int(mate_bases)))
+
+    def mol_mate_disable(self):
+        self._chk(_mol_lib().td_mol_mate_disable(self.h))
+
+    def mol_mate_next(self, codes, offs):
+        """td_mol_mate_next: the mate batch of the next batch staged for MODE_GET_LABEL (numpy uint8 / int64 arrays, or PinnedArray
+        views; kept alive here until the next call, by the caller as long as the batch's own input)"""
+        self._mate = (np.ascontiguousarray(codes, np.uint8) if len(codes) else np.zeros(1, np.uint8), np.ascontiguousarray(offs, np.int64))
+        self._chk(_mol_lib().td_mol_mate_next(self.h, self._mate[0].ctypes.data, self._mate[1].ctypes.data, len(self._mate[1]) - 1))
 
     def mol_dedup_enable(self):
         """td_mol_dedup_enable: from now on a read that is not the first of its molecule gets read_type EXTRACT_DUPLICATE"""

@@ -68,6 +68,28 @@ the later ones find it in the cache), then the two in turn, twice each, seconds 
      the summary sweep, plus one sweep over the occupied list and, the first time, one allocation of 8 bytes per slot (32 MiB);
   3. host to host: no expectation set in advance;
   4. the command: up to twice the streaming seconds -- the survey decodes everything a second time --, expected and accepted.
+
+Mate mode (td_mol_mate_enable: the first bases of a read's mate joined into the key) has a mode of its own, --mate, which adds a
+"mate" section to the same file and measures nothing else:
+
+    python tools/molecules_bench.py --mate
+
+The same workload plus a mate of 150 bases per read (one mate per molecule, copied as it is), P = 12 own bases and M = 20 of the
+mate.  Per batch: the mate kernel from HIP events (option "mate_kernel_us") beside the count kernel with the mate on and the decode
+kernel of the same batch, median of 5 batches with the table reset before each; the count kernel with mate mode off (P = 12) the
+same way.  Host to host: td_submit / td_wait with mate mode on and off in turn in one process, two passes of each after a first pass
+that is discarded; the state with mate mode off is the yardstick.  Nobody has measured what the second upload costs.  Expectation,
+written down before the first run:
+  1. 150 B more host to device per read beside the 150 B of the read itself and its 8-byte offset: the upload roughly doubles
+     (158 -> 316 B per read), and so does the host's staging copy of pageable input;
+  2. about 9 B more per eligible lane in each of the kernels over mol_lane_key (an 8-byte word and a byte at the read's index in
+     the caller's order -- the batch is of one length here, so that index is the lane's own and the loads are coalesced): beside
+     the 73 B streamed and 200-400 B of table traffic per read, a few percent of the count kernel at most;
+  3. the mate kernel touches one or two 64-byte lines of its mate per read (20 bytes at a stride of 150) and writes 9 B: 2^20 reads
+     move 64-128 MiB, some tens of microseconds at HBM rate -- the same order as the count kernel, far below the decode kernel;
+  4. host to host: no expectation set in advance.  The decode kernel bounds the pipeline and the upload runs beside it, so the
+     doubled copy may not show at all; if the loss is more than the extra copy's bytes explain, the next step is to copy only the
+     first M bytes of each mate (not built here).
 """
 import argparse
 import json
@@ -92,7 +114,10 @@ def code(s):
     return np.array(["ACGT".index(c) for c in s], np.uint8)
 
 
-def make_batch(n, n_mol, seed=1, sub=0.02, umi_sub=0.0):
+MATE_PREFIX, MATE_BASES, MATE_LEN = 12, 20, 150
+
+
+def make_batch(n, n_mol, seed=1, sub=0.02, umi_sub=0.0, with_mates=False):
     rng = np.random.default_rng(seed)
     L = bench.READ_LEN
     bar = np.array([code(b) for b in bench.BARCODES], np.uint8)
@@ -117,7 +142,11 @@ def make_batch(n, n_mol, seed=1, sub=0.02, umi_sub=0.0):
     if umi_sub > 0:                                                # misread UMI bases: always another base
         hit = rng.random((n, UMI)) < umi_sub
         y[:, 6:6 + UMI] = np.where(hit, (y[:, 6:6 + UMI] + rng.integers(1, 4, size=(n, UMI), dtype=np.uint8)) & 3, y[:, 6:6 + UMI])
-    return np.ascontiguousarray(y.reshape(-1)), np.arange(n + 1, dtype=np.int64) * L, int(len(np.unique(draw)))
+    batch = (np.ascontiguousarray(y.reshape(-1)), np.arange(n + 1, dtype=np.int64) * L, int(len(np.unique(draw))))
+    if with_mates:                                                 # one mate per molecule, copied as it is
+        mates = rng.integers(0, 4, size=(n_mol, MATE_LEN), dtype=np.uint8)[draw]
+        batch += (np.ascontiguousarray(mates.reshape(-1)), np.arange(n + 1, dtype=np.int64) * MATE_LEN)
+    return batch
 
 
 def measure(ctx, seq, offs, n):
@@ -300,6 +329,67 @@ def measure_dedup_collapsed(ctx, seq, offs, n):
     return out
 
 
+def measure_mate(ctx, seq, offs, n, mseq, moffs):
+    from tagdust_amd import RESULT_DTYPE
+    out = {"prefix_bases": MATE_PREFIX, "mate_bases": MATE_BASES, "mate_len": MATE_LEN,
+           "upload_bytes_per_read": {"mate_off": int(offs[1] - offs[0]) + 8, "mate_on": int(offs[1] - offs[0]) + 8 + MATE_LEN + 8}}
+    med = statistics.median
+    for state in ("mate_on", "mate_off"):
+        ctx.mol_enable(MATE_PREFIX, LOG2_SLOTS)
+        if state == "mate_on":
+            ctx.mol_mate_enable(MATE_BASES)
+        dec, cnt, mk = [], [], []
+        for it in range(6):
+            ctx.mol_reset()
+            if state == "mate_on":
+                ctx.mol_mate_next(mseq, moffs)
+            ctx.upload_batch(seq, offs)
+            ctx.run()
+            dec.append(ctx.last_kernel_ms())
+            cnt.append(ctx.get_option("molecules_kernel_us") / 1000.0)
+            if state == "mate_on":
+                mk.append(ctx.get_option("mate_kernel_us") / 1000.0)
+            if it == 0:
+                out["totals_of_one_batch_" + state] = ctx.mol_get()[1]
+        out["decode_kernel_ms_median_" + state] = round(med(dec[1:]), 3)
+        out["count_kernel_ms_runs_" + state], out["count_kernel_ms_median_" + state] = [round(v, 3) for v in cnt[1:]], round(med(cnt[1:]), 3)
+        if mk:
+            out["mate_kernel_ms_runs"], out["mate_kernel_ms_median"] = [round(v, 3) for v in mk[1:]], round(med(mk[1:]), 3)
+            out["mate_kernel_share_of_decode"] = round(med(mk[1:]) / med(dec[1:]), 5)
+        ctx.mol_disable()
+    out["count_kernel_mate_on_over_off"] = round(out["count_kernel_ms_median_mate_on"] / out["count_kernel_ms_median_mate_off"], 3) \
+        if out["count_kernel_ms_median_mate_off"] > 0 else None
+    # host to host: the first pass of the process is discarded, then mate mode on and off in turn, twice each
+    res = [np.zeros(n, RESULT_DTYPE) for _ in range(2)]
+    rates = {"discarded_first_pass": [], "mate_on": [], "mate_off": []}
+    for k, state in enumerate(("mate_off", "mate_on", "mate_off", "mate_on", "mate_off")):
+        ctx.mol_enable(MATE_PREFIX, LOG2_SLOTS)
+        if state == "mate_on":
+            ctx.mol_mate_enable(MATE_BASES)
+
+        def submit(r):
+            if state == "mate_on":
+                ctx.mol_mate_next(mseq, moffs)
+            return ctx.submit(seq, offs, res=r)
+
+        steps = 4
+        for t in [submit(r) for r in res]:                         # warm-up: both slots, both result buffers
+            ctx.wait(t)
+        t0 = time.perf_counter()
+        tickets = []
+        for s in range(steps):
+            tickets.append(submit(res[s & 1]))
+            if len(tickets) == 2:
+                ctx.wait(tickets.pop(0))
+        for t in tickets:
+            ctx.wait(t)
+        rates["discarded_first_pass" if k == 0 else state].append(round(steps * n / (time.perf_counter() - t0)))
+        ctx.mol_disable()
+    out["host_to_host_reads_per_s"] = rates
+    out["host_to_host_mate_on_over_off"] = round(max(rates["mate_on"]) / max(rates["mate_off"]), 4)
+    return out
+
+
 def measure_command(segs, seq, offs):
     """the whole command once each way on a FASTQ of the batch: seconds on the wall and the report's streaming seconds"""
     import shutil
@@ -352,13 +442,15 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "molecules.json"))
     ap.add_argument("--collapse", action="store_true", help="measure the UMI collapse alone and add a \"collapse\" section to --out")
     ap.add_argument("--dedup-collapsed", action="store_true", help="measure survey, freeze and replay alone and add a \"dedup_collapsed\" section to --out")
+    ap.add_argument("--mate", action="store_true", help="measure mate mode alone and add a \"mate\" section to --out")
     ap.add_argument("--with-command", action="store_true", help="with --dedup-collapsed: the whole command each way on a FASTQ of the batch")
     ap.add_argument("--command-only", action="store_true", help="with --dedup-collapsed: the whole command alone, into the section that --out already has")
     args = ap.parse_args()
     from tagdust_amd import TagdustHip
     from tagdust_amd import lib as tdlib
     segs = ["B:" + ",".join(bench.BARCODES), "F:" + "N" * UMI, "S:" + bench.SPACER, "R:N", "P:" + bench.ADAPTER]
-    seq, offs, drawn = make_batch(args.reads, args.molecules, umi_sub=0.005 if args.collapse or args.dedup_collapsed else 0.0)
+    seq, offs, drawn, *mates = make_batch(args.reads, args.molecules, umi_sub=0.005 if args.collapse or args.dedup_collapsed else 0.0,
+                                          with_mates=args.mate)
     head = min(args.reads, 100000)
     md, _ = tdlib.build_model(segs, seq[:offs[head]], offs[:head + 1])
     if args.dedup_collapsed and args.command_only:
@@ -378,6 +470,8 @@ def main():
             section = dict(doc, **measure_collapse(ctx, seq, offs, args.reads))
         elif args.dedup_collapsed:
             section = dict(doc, **measure_dedup_collapsed(ctx, seq, offs, args.reads))
+        elif args.mate:
+            section = dict(doc, **measure_mate(ctx, seq, offs, args.reads, *mates))
         else:
             doc.update(measure(ctx, seq, offs, args.reads))
     finally:
@@ -385,9 +479,9 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     if args.dedup_collapsed and args.with_command:                 # (the context is closed: the command has the device to itself)
         section["command"] = measure_command(segs, seq, offs)
-    if args.collapse or args.dedup_collapsed:                      # the file's other figures stay what they are
+    if args.collapse or args.dedup_collapsed or args.mate:         # the file's other figures stay what they are
         doc = json.load(open(args.out)) if os.path.exists(args.out) else {}
-        doc["collapse" if args.collapse else "dedup_collapsed"] = section
+        doc["collapse" if args.collapse else "dedup_collapsed" if args.dedup_collapsed else "mate"] = section
     json.dump(doc, open(args.out, "w"), indent=1, sort_keys=True)
     print(json.dumps(doc, sort_keys=True))
 

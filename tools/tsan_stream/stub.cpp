@@ -21,6 +21,7 @@ int td_submit(td_ctx*, const void*, int32_t, const int64_t* offs, int64_t n, int
 { memset(res, 0, sizeof(td_read_result) * (size_t)n); for (int64_t i = 0; i < n; i++) { res[i].barcode = (int32_t)(i % 3); res[i].fingerprint = -1; res[i].mapq = 12.345f; } memset(seq_out, 1, (size_t)(offs[n] - offs[0])); *ticket = ++g_t; return 0; }
 int td_wait(td_ctx*, int64_t) { return 0; }
 int td_set_batch_window(td_ctx*, int64_t, int64_t) { return 0; }
+int td_mol_mate_next(td_ctx*, const uint8_t*, const int64_t*, int64_t) { return 0; }   // (pair mode: "mate_bases" reads 0 here, never called)
 }
 int main(int argc, char** argv)
 {
