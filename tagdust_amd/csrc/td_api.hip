@@ -368,15 +368,12 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	if (!strcmp(name, "census_active")) { *value = c->census.on; return TD_OK; }
 	if (!strcmp(name, "census_kernel_us")) return census_last_kernel_us(c, value);   // the count kernel's time of the last counted batch
 	if (!strcmp(name, "molecules_active")) { *value = c->molecules.on; return TD_OK; }
-	if (!strcmp(name, "molecules_kernel_us")) return mol_last_kernel_us(c, value);
-	if (!strcmp(name, "dedup_active")) { *value = c->molecules.dedup; return TD_OK; }
-	if (!strcmp(name, "dedup_kernel_us")) return mol_dedup_last_kernel_us(c, value);   // the two passes of the last batch
-	if (!strcmp(name, "dedup_frozen")) { *value = c->molecules.frozen; return TD_OK; }   // td_mol_dedup_freeze: batches are replayed
-	if (!strcmp(name, "dedup_replay_kernel_us")) return mol_replay_last_kernel_us(c, value);   // the replay kernel of the last batch
-	if (!strcmp(name, "mate_bases")) { *value = c->molecules.mate_bases; return TD_OK; }   // td_mol_mate_enable's M, 0 = off
-	if (!strcmp(name, "mate_kernel_us")) return mol_mate_last_kernel_us(c, value);   // the mate kernel of the last staged mate batch
-	if (!strcmp(name, "collapse_active")) { *value = c->molecules.collapse; return TD_OK; }
-	if (!strcmp(name, "collapse_origin_kernel_us")) return mol_origin_last_kernel_us(c, value);   // the origin pass of the last batch
+	if (!strcmp(name, "dedup_active")) { *value = c->molecules.dedup.on; return TD_OK; }
+	if (!strcmp(name, "dedup_frozen")) { *value = c->molecules.frozen.on; return TD_OK; }   // td_mol_dedup_freeze: batches are replayed
+	if (!strcmp(name, "mate_bases")) { *value = c->molecules.mate.bases; return TD_OK; }   // td_mol_mate_enable's M, 0 = off
+	if (!strcmp(name, "collapse_active")) { *value = c->molecules.collapse.on; return TD_OK; }
+	// molecules_, dedup_, collapse_origin_, dedup_replay_ and mate_kernel_us: the stage's time of the last batch (-1: none of them)
+	if (const int rc = mol_kernel_us(c, name, value); rc >= 0) return rc;
 	if (!strcmp(name, "overlap_active")) {
 		// pipelined batches alternate between two compute streams / workspaces (off: option, generic kernel, depth 1, or HBM
 		// could not hold the second workspace)
@@ -696,10 +693,10 @@ static int slot_decode(td_ctx* c, TdSlot& s, int mode, bool want_labels = true)
 	if (s.n_tiles > 0 && s.n_wave_slots == 0) return fail(c, "td_run: the resident batch was staged for TD_MODE_RNA_DUST, without a decode workspace (upload it again)");
 	HIPCHK(c, hipSetDevice(c->device));
 	// mate mode: a batch that was staged without its mates (or with those of another M) is not counted, and not decoded either
-	if (mode == TD_MODE_GET_LABEL && c->molecules.mate_bases > 0 && c->molecules.mate_bases != s.mate_m) {
-		c->molecules.mate_named = false;
+	if (mode == TD_MODE_GET_LABEL && c->molecules.mate.bases > 0 && c->molecules.mate.bases != s.mate_m) {
+		c->molecules.mate.named = false;
 		return fail(c, "td_run: mate mode is on (td_mol_mate_enable, %d bases) and the resident batch of %lld reads was staged without a mate "
-		            "batch of as many reads: td_mol_mate_next first, then td_batch_upload; nothing was counted", c->molecules.mate_bases, (long long)s.n_reads);
+		            "batch of as many reads: td_mol_mate_next first, then td_batch_upload; nothing was counted", c->molecules.mate.bases, (long long)s.n_reads);
 	}
 	s.reset_decoded();   // (runs_cap above all: a launch of the generic kernel, or an empty batch, must not hand the label runs of this
 	                     // slot's previous launch to the finish kernel)
@@ -955,7 +952,7 @@ static int upload_common(td_ctx* c, const void* bases, int is_ascii, const int64
 	TdSlot& s = c->slots[0];
 	const TdRoute rt = sync_route(c);
 	// mate mode: the mode is td_run's to say, so the named mate batch is taken now when it is this batch's
-	const bool take_mate = c->molecules.mate_bases > 0 && c->molecules.mate_named && c->molecules.mate_reads == n;
+	const bool take_mate = c->molecules.mate.bases > 0 && c->molecules.mate.named && c->molecules.mate.reads == n;
 	if (slot_stage(c, s, rt, bases, is_ascii, offs, n, c->stream, true, take_mate) != TD_OK) return TD_FAIL;
 	HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller may reuse its buffers
 	c->last_slot = 0;
@@ -1019,7 +1016,7 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 	if (k < 0) return fail(c, "td_submit: all %d pipeline slots hold batches that have not been waited for", c->pipeline_depth);
 	if (mode == TD_MODE_RNA_DUST && labels) return fail(c, "td_submit: TD_MODE_RNA_DUST has no labels (pass NULL)");
 	if (spec_handover(c, false) != TD_OK) return TD_FAIL;   // a finished background compile takes over before any geometry is chosen
-	const bool take_mate = c->molecules.mate_bases > 0 && mode == TD_MODE_GET_LABEL;   // (no other mode needs or consumes a mate)
+	const bool take_mate = c->molecules.mate.bases > 0 && mode == TD_MODE_GET_LABEL;   // (no other mode needs or consumes a mate)
 	if (take_mate && mol_mate_check(c, n_reads, "td_submit") != TD_OK) return TD_FAIL;
 	TdSlot& s = c->slots[k];
 	TdRoute rt = sync_route(c);

@@ -73,7 +73,7 @@ int census_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int8_
 	a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.H = z.table.H;
 	a.segment = z.segment; a.ordered = z.ordered ? 1 : 0; a.mask = z.mask;
 	a.table = kt_table_view(z.table); a.tallies = z.table.d_tallies;
-	if (kt_count_slot(c, z.table, s, (const void*)td_census_count_kernel, &a) != TD_OK) return TD_FAIL;
+	if (kt_launch_slot(c, z.table.ev, s, (const void*)td_census_count_kernel, &a) != TD_OK) return TD_FAIL;
 	return kt_slot_read_behind(c, s);
 }
 
@@ -143,5 +143,5 @@ int census_last_kernel_us(td_ctx* c, int32_t* us)
 {
 	const TdCountTable& t = c->census.table;
 	if (!c->census.on) return fail(c, "td_get_option: census_kernel_us: the census is off");
-	return kt_last_kernel_us(c, t.ev_c0, t.ev_c1, us, "td_get_option: census_kernel_us: no batch has been counted yet");
+	return kt_last_kernel_us(c, t.ev, us, "td_get_option: census_kernel_us: no batch has been counted yet");
 }

@@ -38,6 +38,12 @@ struct TdTileView {
 	int32_t lmax, nw2, nw1;
 };
 
+// Two timing events around what a stage queued for the last batch (the "*_kernel_us" options of td_get_option)
+struct KtEventPair { hipEvent_t e0 = nullptr, e1 = nullptr; };
+// both events, or on a failure none / both destroyed, the pair empty again
+KT_HIDDEN hipError_t kt_pair_create(KtEventPair& ev);
+KT_HIDDEN void kt_pair_destroy(KtEventPair& ev);
+
 // a counting table that belongs to a context
 struct TdCountTable {
 	int32_t log2_slots = 0, H = 0, tally_words = 0;
@@ -45,7 +51,7 @@ struct TdCountTable {
 	kt_u64* d_keys = nullptr;      // [2^log2_slots], 0 = empty
 	kt_u64* d_counts = nullptr;    // [2^log2_slots]
 	kt_u64* d_tallies = nullptr;   // [tally_words] the owner's tallies, the compaction's cursor among them
-	hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;   // around the last count launch (the "*_kernel_us" options)
+	KtEventPair ev;                // around the last count launch
 };
 
 // label copy, table, tallies and events, all zeroed (a failure leaves what it got: kt_table_release) / all of it freed
@@ -55,9 +61,10 @@ KT_HIDDEN void kt_table_release(TdCountTable& t);
 KT_HIDDEN hipError_t kt_table_zero(const TdCountTable& t, hipStream_t stream);
 KT_HIDDEN TdKeyTable kt_table_view(const TdCountTable& t);
 KT_HIDDEN TdTileView kt_tile_view(const TdSlot& s, const int8_t* labels);
-// The count of one decoded slot: `kernel` (KT_BLOCK threads, a tile per wave, *args its one argument) on the slot's compute stream
-// between the table's two events.
-KT_HIDDEN int kt_count_slot(td_ctx* c, const TdCountTable& t, TdSlot& s, const void* kernel, void* args);
+// One launch over a decoded slot: `kernel` (KT_BLOCK threads, a tile per wave, *args its one argument) on the slot's compute stream,
+// checked; a slot without tiles gets no launch.  kt_launch_slot: the same between the two events of `ev`, which are recorded either way.
+KT_HIDDEN int kt_launch_tiles(td_ctx* c, TdSlot& s, const void* kernel, void* args);
+KT_HIDDEN int kt_launch_slot(td_ctx* c, const KtEventPair& ev, TdSlot& s, const void* kernel, void* args);
 // ... and behind the last launch that reads the decoded slot: the finish kernel waits for ev_hits, so a slot whose batch has been
 // waited for is no longer read by these launches either
 KT_HIDDEN int kt_slot_read_behind(td_ctx* c, TdSlot& s);
@@ -72,8 +79,8 @@ KT_HIDDEN int kt_sweep_dense(td_ctx* c, const char* who, const char* what, kt_u6
 // tally and sorted; *n = their number, entries[min(cap, *n)] the first of them.  Waits for the compute streams.
 KT_HIDDEN int kt_table_entries(td_ctx* c, const char* who, const TdCountTable& t, int distinct_word, int cursor_word, td_census_entry* entries,
                                int64_t cap, int64_t* n, kt_u64* tallies);
-// microseconds between two recorded events (waits for the second); `none_yet`: the message when they have not been recorded
-KT_HIDDEN int kt_last_kernel_us(td_ctx* c, hipEvent_t e0, hipEvent_t e1, int32_t* us, const char* none_yet);
+// microseconds between a pair's two recorded events (waits for the second); `none_yet`: the message when they have not been recorded
+KT_HIDDEN int kt_last_kernel_us(td_ctx* c, const KtEventPair& ev, int32_t* us, const char* none_yet);
 
 #ifdef __HIPCC__
 __device__ __forceinline__ uint32_t kt_hash(kt_u64 k) { return (uint32_t)(kt_mix(k) >> 32); }

@@ -1,4 +1,4 @@
-// td_keytable.hip -- the host side of td_keytable.h: the life of a context's counting table, the bracket around a count launch, the
+// td_keytable.hip -- the host side of td_keytable.h: the life of a context's counting table, the bracket around a launch over a decoded slot, the
 // bracket around a sweep into dense arrays, and the table's contents as sorted entries (with the compaction kernel).  The host
 // helpers of every td_census_entry result are in td_census_host.cpp.
 #include <hip/hip_runtime.h>
@@ -34,8 +34,7 @@ hipError_t kt_table_create(TdCountTable& t, const int32_t* label, int32_t H, int
 	if (e == hipSuccess) e = hipMemcpy(t.d_label, label, sizeof(int32_t) * (size_t)H, hipMemcpyHostToDevice);
 	if (e == hipSuccess) e = kt_table_zero(t, nullptr);
 	if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-	if (e == hipSuccess) e = hipEventCreate(&t.ev_c0);
-	if (e == hipSuccess) e = hipEventCreate(&t.ev_c1);
+	if (e == hipSuccess) e = kt_pair_create(t.ev);
 	return e;
 }
 
@@ -43,9 +42,23 @@ void kt_table_release(TdCountTable& t)
 {
 	void* p[] = { t.d_label, t.d_keys, t.d_counts, t.d_tallies };
 	for (void* q : p) if (q) (void)hipFree(q);
-	hipEvent_t ev[] = { t.ev_c0, t.ev_c1 };
-	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+	kt_pair_destroy(t.ev);
 	t = TdCountTable();
+}
+
+hipError_t kt_pair_create(KtEventPair& ev)
+{
+	hipError_t e = hipEventCreate(&ev.e0);
+	if (e == hipSuccess) e = hipEventCreate(&ev.e1);
+	if (e != hipSuccess) kt_pair_destroy(ev);
+	return e;
+}
+
+void kt_pair_destroy(KtEventPair& ev)
+{
+	if (ev.e0) (void)hipEventDestroy(ev.e0);
+	if (ev.e1) (void)hipEventDestroy(ev.e1);
+	ev = KtEventPair();
 }
 
 hipError_t kt_table_zero(const TdCountTable& t, hipStream_t stream)
@@ -65,11 +78,17 @@ TdKeyTable kt_table_view(const TdCountTable& t)
 
 TdTileView kt_tile_view(const TdSlot& s, const int8_t* labels) { return TdTileView{ s.d_packed, labels, s.lmax, s.nw2, s.nw1 }; }
 
-int kt_count_slot(td_ctx* c, const TdCountTable& t, TdSlot& s, const void* kernel, void* args)
+int kt_launch_tiles(td_ctx* c, TdSlot& s, const void* kernel, void* args)
 {
-	HIPCHK(c, hipEventRecord(t.ev_c0, s.cs));
 	if (s.n_tiles > 0) HIPCHK(c, hipLaunchKernel(kernel, dim3((unsigned)((s.n_tiles + KT_WAVES - 1) / KT_WAVES)), dim3(KT_BLOCK), &args, 0, s.cs));
-	HIPCHK(c, hipEventRecord(t.ev_c1, s.cs));
+	return TD_OK;
+}
+
+int kt_launch_slot(td_ctx* c, const KtEventPair& ev, TdSlot& s, const void* kernel, void* args)
+{
+	HIPCHK(c, hipEventRecord(ev.e0, s.cs));
+	if (kt_launch_tiles(c, s, kernel, args) != TD_OK) return TD_FAIL;
+	HIPCHK(c, hipEventRecord(ev.e1, s.cs));
 	return TD_OK;
 }
 
@@ -127,11 +146,11 @@ int kt_table_entries(td_ctx* c, const char* who, const TdCountTable& t, int dist
 	return TD_OK;
 }
 
-int kt_last_kernel_us(td_ctx* c, hipEvent_t e0, hipEvent_t e1, int32_t* us, const char* none_yet)
+int kt_last_kernel_us(td_ctx* c, const KtEventPair& ev, int32_t* us, const char* none_yet)
 {
 	HIPCHK(c, hipSetDevice(c->device));
 	float ms = 0.0f;
-	if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
+	if (hipEventSynchronize(ev.e1) != hipSuccess || hipEventElapsedTime(&ms, ev.e0, ev.e1) != hipSuccess) {
 		(void)hipGetLastError();
 		return fail(c, "%s", none_yet);
 	}

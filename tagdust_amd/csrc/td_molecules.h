@@ -18,41 +18,56 @@ enum { TDM_ELIGIBLE = 0, TDM_COUNTED, TDM_EMPTY, TDM_N, TDM_OVERFLOW, TDM_MOLECU
 // words of a barcode bin's summary row: reads, molecules, ten levels (td_mol_row)
 #define TDM_ROW_WORDS 12
 
-struct TdMolState {
+// The count's state, and inside it one group per stage behind the count.  A group is value-initialised as a whole by what ends its
+// stage -- free what it owns, then group = Group() -- as TdSlot's groups are (td_ctx.h): "off" is never a set of fields nulled by hand.
+// dedup (td_mol_dedup_enable): the first ordinal of every slot's key, and what orders the two passes of neighbouring batches
+struct TdMolDedup {
 	bool on = false;
-	int32_t prefix = 0;         // P: read bases that belong to the key
-	uint64_t r_segs = 0;        // bit j: segment j is an 'R' segment
-	TdCountTable table;         // td_keytable.h, TDM_TALLY_WORDS tallies
-	unsigned long long* d_rows = nullptr;     // [TD_NUM_BARCODE_BINS][TDM_ROW_WORDS] the summary sweep's result
-	// dedup (td_mol_dedup_enable): the first ordinal of every slot's key, and what orders the two passes of neighbouring batches
-	bool dedup = false;
 	unsigned long long* d_first = nullptr;    // [2^log2_slots], all-ones = no read yet
-	int64_t next_ordinal = 0;                 // reads submitted in TD_MODE_GET_LABEL since dedup was enabled or last reset
+	int64_t next_ordinal = 0;                 // reads submitted in TD_MODE_GET_LABEL since dedup was enabled, last reset or frozen
 	hipEvent_t ev_p1[2] = { nullptr, nullptr };   // behind pass 1 of the last batch ([turn ^ 1]) and of the one before it ([turn])
 	bool p1_queued[2] = { false, false };
 	int turn = 0;
-	hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr;   // around the two passes of the last batch (option "dedup_kernel_us")
-	// collapse (td_mol_collapse_enable): the origin of every slot's key; what a collapse computes, allocated by the first one
-	bool collapse = false;
+	KtEventPair ev;                           // around the two passes of the last batch (option "dedup_kernel_us")
+	void start_over() { next_ordinal = 0; p1_queued[0] = p1_queued[1] = false; }   // ordinals from 0, nothing of pass 1 is queued
+};
+// collapse (td_mol_collapse_enable): the origin of every slot's key; what a collapse computes, allocated by the first one
+struct TdMolCollapse {
+	bool on = false;
 	td_mol_origin* d_origin = nullptr;        // [2^log2_slots], n == 0 = no origin yet
-	hipEvent_t ev_o0 = nullptr, ev_o1 = nullptr;   // around the origin pass of the last batch (option "collapse_origin_kernel_us")
 	uint32_t* d_occ = nullptr;                // the occupied slots' indices, cap_occ bytes of them
 	size_t cap_occ = 0;
 	uint32_t* d_parent = nullptr;             // [2^log2_slots] the slot of every occupied slot's parent, its own for a root
 	unsigned long long* d_collapsed = nullptr;   // [2^log2_slots] the count of a root's tree, 0 for every other slot
-	// the frozen state (td_mol_dedup_freeze; count, dedup and collapse all on): the table is read-only and every batch is replayed
-	// against keeper[]; the first freeze allocates it and the two events, whatever frees dedup's or the collapse's arrays frees them
-	bool frozen = false;
+	KtEventPair ev;                           // around the origin pass of the last batch (option "collapse_origin_kernel_us")
+};
+// the frozen state (td_mol_dedup_freeze; count, dedup and collapse all on): the table is read-only and every batch is replayed
+// against keeper[]; the first freeze allocates it and the pair, whatever ends dedup or the collapse ends this group
+struct TdMolFrozen {
+	bool on = false;
 	unsigned long long* d_keeper = nullptr;   // [2^log2_slots] of an occupied slot: the first ordinal of its root's own key
-	hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;   // around the replay kernel of the last batch (option "dedup_replay_kernel_us")
-	// mate mode (td_mol_mate_enable): M, and the mate batch td_mol_mate_next named for the next TD_MODE_GET_LABEL staging (the caller's
-	// pointers, read by that staging alone)
-	int32_t mate_bases = 0;                   // M: the mate's bases that belong to the key (0 = off)
-	bool mate_named = false;
-	const uint8_t* mate_codes = nullptr;
-	const int64_t* mate_offs = nullptr;
-	int64_t mate_reads = 0;
-	hipEvent_t ev_m0 = nullptr, ev_m1 = nullptr;   // around the mate kernel of the last staged mate batch (option "mate_kernel_us")
+	KtEventPair ev;                           // around the replay kernel of the last batch (option "dedup_replay_kernel_us")
+};
+// mate mode (td_mol_mate_enable): M, and the mate batch td_mol_mate_next named for the next TD_MODE_GET_LABEL staging (the caller's
+// pointers, read by that staging alone)
+struct TdMolMate {
+	int32_t bases = 0;                        // M: the mate's bases that belong to the key (0 = off)
+	bool named = false;
+	const uint8_t* codes = nullptr;
+	const int64_t* offs = nullptr;
+	int64_t reads = 0;
+	KtEventPair ev;                           // around the mate kernel of the last staged mate batch (option "mate_kernel_us")
+};
+struct TdMolState {
+	bool on = false;
+	int32_t prefix = 0;         // P: read bases that belong to the key
+	uint64_t r_segs = 0;        // bit j: segment j is an 'R' segment
+	TdCountTable table;         // td_keytable.h, TDM_TALLY_WORDS tallies; its pair is option "molecules_kernel_us"
+	unsigned long long* d_rows = nullptr;     // [TD_NUM_BARCODE_BINS][TDM_ROW_WORDS] the summary sweep's result
+	TdMolDedup dedup;
+	TdMolCollapse collapse;
+	TdMolFrozen frozen;
+	TdMolMate mate;
 };
 
 struct TdMolArgs {
@@ -71,7 +86,7 @@ struct TdMolArgs {
 	const unsigned long long* __restrict__ mate_w;   // [n_reads] the mate's prefix word
 	const uint8_t* __restrict__ mate_n;       // [n_reads] its length n2 in the low 7 bits, bit 7 = one of those bases is an N
 	int32_t mate_bases;                       // M (0 = off: neither array is read)
-	// dedup's pass 1 and mate mode
+	// dedup's pass 1, the replay and mate mode
 	const int32_t* __restrict__ read_at;      // [n_reads] device position -> index in the caller's order (NULL: the same)
 	unsigned long long* __restrict__ first;   // [slot_mask + 1] the smallest ordinal of every slot's key
 	int32_t* __restrict__ judged;             // [n_tiles*64] the read's table slot, -1 = not judged
@@ -95,15 +110,8 @@ __attribute__((visibility("hidden"))) int mol_slot_decoded(td_ctx* c, TdSlot& s,
 __attribute__((visibility("hidden"))) int mol_mate_check(td_ctx* c, int64_t n, const char* who);
 __attribute__((visibility("hidden"))) int mol_mate_stage(td_ctx* c, TdSlot& s, int64_t n, hipStream_t up);
 __attribute__((visibility("hidden"))) int mol_mate_launch(td_ctx* c, TdSlot& s, int64_t n);
-// option "mate_kernel_us" of td_get_option: the mate kernel's time of the last staged mate batch (waits for it)
-__attribute__((visibility("hidden"))) int mol_mate_last_kernel_us(td_ctx* c, int32_t* us);
-// option "collapse_origin_kernel_us" of td_get_option: the origin pass's time of the last batch (waits for it)
-__attribute__((visibility("hidden"))) int mol_origin_last_kernel_us(td_ctx* c, int32_t* us);
-// option "dedup_kernel_us" of td_get_option: the two passes' time of the last batch (waits for it)
-__attribute__((visibility("hidden"))) int mol_dedup_last_kernel_us(td_ctx* c, int32_t* us);
-// option "dedup_replay_kernel_us" of td_get_option: the replay kernel's time of the last batch of the frozen state (waits for it)
-__attribute__((visibility("hidden"))) int mol_replay_last_kernel_us(td_ctx* c, int32_t* us);
-// option "molecules_kernel_us" of td_get_option: the count kernel's time of the last counted batch (waits for it)
-__attribute__((visibility("hidden"))) int mol_last_kernel_us(td_ctx* c, int32_t* us);
+// The "*_kernel_us" options of td_get_option that belong here -- molecules_, dedup_, collapse_origin_, dedup_replay_ and mate_: the time
+// between the stage's two events of the last batch (waits for it).  TD_OK, TD_FAIL with the message, or -1: `name` is none of them.
+__attribute__((visibility("hidden"))) int mol_kernel_us(td_ctx* c, const char* name, int32_t* us);
 // table and label copy freed, count off (the caller has made sure nothing of it is queued any more)
 __attribute__((visibility("hidden"))) void mol_release(td_ctx* c);

@@ -34,6 +34,7 @@
 // slot's aux stream between the upload event and ev_pack, turns it into a word and a byte per read in the caller's order, and
 // mol_lane_key appends them behind the label walk.  The mates are not decoded: their outcome takes no part.
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include <algorithm>
 #include <string>
@@ -51,6 +52,9 @@ __device__ __forceinline__ bool mol_wave_tile(const TdMolArgs& a, uint8_t* s_r, 
 	tile = blockIdx.x * KT_WAVES + (threadIdx.x >> 6);
 	return tile < a.n_tiles;                          // (whole waves; no workgroup barrier behind this)
 }
+
+// read k of the device's order in the caller's order, which the length sort may have left (read_at NULL: it has not)
+__device__ __forceinline__ int64_t mol_caller_at(const int32_t* __restrict__ read_at, int64_t k) { return read_at ? (int64_t)read_at[k] : k; }
 
 // what a lane's read is to the count: eligible, and then exactly one of the three classes (has_key: counted under `key`)
 // (w, n, finger: what the key was made of, for the collapse's origin pass)
@@ -76,7 +80,7 @@ __device__ __forceinline__ bool mol_lane_key(const TdMolArgs& a, const uint8_t* 
 		return ++n < a.prefix;
 	});
 	if (a.mate_bases > 0 && elig) {                   // (mate mode is the launch's: one wave-uniform test when it is off)
-		const int64_t at = a.read_at ? (int64_t)a.read_at[k] : k;         // the caller's order, not the length-sorted one
+		const int64_t at = mol_caller_at(a.read_at, k);
 		const uint32_t mn = a.mate_n[at];
 		const int n2 = (int)(mn & 0x7Fu);                                 // (n + n2 <= P + M <= 32: the shift is at most 62)
 		w = (w << (2 * n2)) | a.mate_w[at];
@@ -136,6 +140,22 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_mate_kernel(const uint8_t* __
 	mate_n[i] = (uint8_t)((uint32_t)n2 | any_n);
 }
 
+// The verdict on a wave's reads, the tail of dedup's pass 2 and of the replay (whole waves).  A duplicate's outcome becomes
+// TD_EXTRACT_DUPLICATE -- `type` is the lane's outcome word as read, its upper 24 bits stay, and so does every other field --; an
+// eligible read that is none is kept, without a slot it is tallied unjudged as well.  One add per wave and tally.
+__device__ __forceinline__ void mol_wave_verdict(int32_t* out_type, kt_u64* tallies, int64_t k, int lane, int32_t type, bool elig, int32_t slot, bool dup)
+{
+	if (dup) out_type[k] = (int32_t)(((uint32_t)type & ~0xFFu) | (uint32_t)TD_EXTRACT_DUPLICATE);   // (the lane's own word)
+	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig));
+	const int n_dup = __builtin_popcountll(__builtin_amdgcn_ballot_w64(dup));
+	const int n_unjudged = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig && slot < 0));
+	if (lane == 0) {
+		if (n_elig - n_dup) atomicAdd(&tallies[TDM_KEPT], (kt_u64)(n_elig - n_dup));
+		if (n_dup) atomicAdd(&tallies[TDM_DUPLICATES], (kt_u64)n_dup);
+		if (n_unjudged) atomicAdd(&tallies[TDM_UNJUDGED], (kt_u64)n_unjudged);
+	}
+}
+
 // Dedup, pass 1: behind the count kernel of the same batch on the same stream, so a counted read's key is in the table or has
 // overflowed for good and a plain probe finds which.  Leaves every lane's slot (-1: not judged, not eligible included) for pass 2
 // and lowers the slot's first ordinal to the read's own.
@@ -149,16 +169,15 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_first_kernel(const TdMolArgs 
 	int32_t slot = -1;
 	if (mol_lane_key(a, s_r, tile, lane, k, m) && m.has_key) {
 		slot = kt_probe_find(a.table, m.key);
-		if (slot >= 0) {
-			const int64_t at = a.read_at ? (int64_t)a.read_at[k] : k;     // the caller's order, not the length-sorted one
-			atomicMin(&a.first[slot], (kt_u64)(a.ordinal_base + at));
-		}
+		if (slot >= 0) atomicMin(&a.first[slot], (kt_u64)(a.ordinal_base + mol_caller_at(a.read_at, k)));
 	}
 	a.judged[k] = slot;                               // (judged has n_tiles * 64 words)
 }
 
 // Dedup, pass 2: a judged read whose ordinal is not its slot's first is a duplicate.  Every pass 1 that could still lower that
-// first -- this batch's and every earlier one's -- has finished (stream order and the event of the batch before).
+// first -- this batch's and every earlier one's -- has finished (stream order and the event of the batch before).  It reads no
+// label -- no LDS table, no barrier, so not the head of the other per-tile kernels -- and takes the eight values it needs by
+// themselves: with the 208 bytes of TdMolArgs for its arguments the two passes measured 2 us in 300 slower (profiles/mol_stage_refactor_ab.json).
 __global__ __launch_bounds__(KT_BLOCK) void td_mol_mark_kernel(int32_t* __restrict__ out_type, const int32_t* __restrict__ judged,
                                                                 const int32_t* __restrict__ read_at, const kt_u64* first, int64_t ordinal_base,
                                                                 int64_t n_reads, int32_t n_tiles, kt_u64* __restrict__ tallies)
@@ -174,19 +193,10 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_mark_kernel(int32_t* __restri
 	const int32_t slot = elig ? judged[k] : -1;
 	bool dup = false;
 	if (slot >= 0) {
-		const int64_t at = read_at ? (int64_t)read_at[k] : k;
+		const int64_t at = mol_caller_at(read_at, k);
 		dup = __hip_atomic_load(&first[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (kt_u64)(ordinal_base + at);
 	}
-	if (dup) out_type[k] = (int32_t)(((uint32_t)type & ~0xFFu) | (uint32_t)TD_EXTRACT_DUPLICATE);
-	// tallies: one add per wave and tally
-	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig));
-	const int n_dup = __builtin_popcountll(__builtin_amdgcn_ballot_w64(dup));
-	const int n_unjudged = __builtin_popcountll(__builtin_amdgcn_ballot_w64(elig && slot < 0));
-	if (lane == 0) {
-		if (n_elig - n_dup) atomicAdd(&tallies[TDM_KEPT], (kt_u64)(n_elig - n_dup));
-		if (n_dup) atomicAdd(&tallies[TDM_DUPLICATES], (kt_u64)n_dup);
-		if (n_unjudged) atomicAdd(&tallies[TDM_UNJUDGED], (kt_u64)n_unjudged);
-	}
+	mol_wave_verdict(out_type, tallies, k, lane, type, elig, slot, dup);
 }
 
 // The frozen state, the replay: one launch per batch, behind the decode.  The table and keeper[] are only read: a read whose key the
@@ -203,22 +213,11 @@ __global__ __launch_bounds__(KT_BLOCK) void td_mol_replay_kernel(const TdMolArgs
 	const int32_t slot = m.has_key ? kt_probe_find(a.table, m.key) : -1;
 	bool dup = false;
 	if (slot >= 0) {
-		const int64_t at = a.read_at ? (int64_t)a.read_at[k] : k;     // the caller's order, not the length-sorted one
+		const int64_t at = mol_caller_at(a.read_at, k);
 		dup = a.keeper[slot] != (kt_u64)(a.ordinal_base + at);
 	}
-	if (dup) {
-		int32_t* type = const_cast<int32_t*>(a.out_type);             // (the lane's own word; every other field stays as decoded)
-		type[k] = (int32_t)(((uint32_t)type[k] & ~0xFFu) | (uint32_t)TD_EXTRACT_DUPLICATE);
-	}
-	// tallies: one add per wave and tally
-	const int n_elig = __builtin_popcountll(__builtin_amdgcn_ballot_w64(m.elig));
-	const int n_dup = __builtin_popcountll(__builtin_amdgcn_ballot_w64(dup));
-	const int n_unjudged = __builtin_popcountll(__builtin_amdgcn_ballot_w64(m.elig && slot < 0));
-	if (lane == 0) {
-		if (n_elig - n_dup) atomicAdd(&a.tallies[TDM_KEPT], (kt_u64)(n_elig - n_dup));
-		if (n_dup) atomicAdd(&a.tallies[TDM_DUPLICATES], (kt_u64)n_dup);
-		if (n_unjudged) atomicAdd(&a.tallies[TDM_UNJUDGED], (kt_u64)n_unjudged);
-	}
+	// (the outcome is the lane's own word, the kernel's one store into the decoded batch; the duplicates' lanes alone read it again)
+	mol_wave_verdict(const_cast<int32_t*>(a.out_type), a.tallies, k, lane, dup ? a.out_type[k] : 0, m.elig, slot, dup);
 }
 
 // Collapse, the origin pass: behind the count kernel of the same batch on the same stream, so a counted read's key is in the table or
@@ -398,40 +397,34 @@ static int summary_rows(td_ctx* c, const kt_u64* counts, td_mol_row rows[TD_NUM_
 	return TD_OK;
 }
 
-// the frozen state's keeper array and events freed, the state ended (nothing of it is queued any more)
-static void keeper_release(TdMolState& z)
+// one array of an element of `elem_bytes` per table slot: first ordinals, origins, parents, collapsed counts, keepers
+static hipError_t alloc_per_slot(const TdMolState& z, void** p, size_t elem_bytes) { return hipMalloc(p, elem_bytes << z.table.log2_slots); }
+
+// A stage's group released: what it owns freed, the group as it was before the stage was ever on (nothing of it is queued any more).
+// A group's arrays and events exist while it is on and inside an enable that has not yet succeeded, which releases what it got.
+static void frozen_release(TdMolState& z)
 {
-	if (z.d_keeper) (void)hipFree(z.d_keeper);
-	hipEvent_t ev[] = { z.ev_r0, z.ev_r1 };
-	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-	z.d_keeper = nullptr; z.ev_r0 = z.ev_r1 = nullptr;
-	z.frozen = false;
+	if (z.frozen.d_keeper) (void)hipFree(z.frozen.d_keeper);
+	kt_pair_destroy(z.frozen.ev);
+	z.frozen = TdMolFrozen();
 }
 
-// dedup's first ordinals and events freed (nothing of it is queued any more).  They exist while z.dedup is set and inside a
-// td_mol_dedup_enable that has not yet succeeded, which frees what it got itself.
 static void dedup_release(TdMolState& z)
 {
-	if (z.d_first) (void)hipFree(z.d_first);
-	hipEvent_t ev[] = { z.ev_p1[0], z.ev_p1[1], z.ev_d0, z.ev_d1 };
-	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-	z.d_first = nullptr; z.ev_p1[0] = z.ev_p1[1] = z.ev_d0 = z.ev_d1 = nullptr;
-	z.p1_queued[0] = z.p1_queued[1] = false;
-	z.dedup = false;
-	keeper_release(z);
+	if (z.dedup.d_first) (void)hipFree(z.dedup.d_first);
+	for (hipEvent_t e : z.dedup.ev_p1) if (e) (void)hipEventDestroy(e);
+	kt_pair_destroy(z.dedup.ev);
+	z.dedup = TdMolDedup();
+	frozen_release(z);                                // the frozen state needs dedup and the collapse: it ends with either
 }
 
-// the collapse's origins, events and work arrays freed (nothing of it is queued any more); they exist as dedup's do
 static void collapse_release(TdMolState& z)
 {
-	void* p[] = { z.d_origin, z.d_occ, z.d_parent, z.d_collapsed };
+	void* p[] = { z.collapse.d_origin, z.collapse.d_occ, z.collapse.d_parent, z.collapse.d_collapsed };
 	for (void* q : p) if (q) (void)hipFree(q);
-	hipEvent_t ev[] = { z.ev_o0, z.ev_o1 };
-	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-	z.d_origin = nullptr; z.d_occ = nullptr; z.d_parent = nullptr; z.d_collapsed = nullptr; z.cap_occ = 0;
-	z.ev_o0 = z.ev_o1 = nullptr;
-	z.collapse = false;
-	keeper_release(z);
+	kt_pair_destroy(z.collapse.ev);
+	z.collapse = TdMolCollapse();
+	frozen_release(z);
 }
 
 void mol_release(td_ctx* c)
@@ -441,71 +434,59 @@ void mol_release(td_ctx* c)
 	if (z.d_rows) (void)hipFree(z.d_rows);
 	dedup_release(z);
 	collapse_release(z);
-	hipEvent_t ev[] = { z.ev_m0, z.ev_m1 };
-	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+	kt_pair_destroy(z.mate.ev);
 	z = TdMolState();                                 // (mate mode off with it, a named mate batch forgotten)
 }
 
 // A decoded slot's launches, queued on its compute stream: the count, then the collapse's origin pass, then dedup's two passes, each
-// only when it is on and each between its own two events.  The order matters: dedup's pass 2 rewrites the outcomes the others read.
-// In the frozen state the replay kernel alone, between its own two events: keys, counts, origins, first ordinals and the count's
+// only when it is on and each between its own pair of events.  The order matters: dedup's pass 2 rewrites the outcomes the others
+// read.  In the frozen state the replay kernel alone, between its own pair: keys, counts, origins, first ordinals and the count's
 // tallies stay as the survey left them.
 int mol_slot_decoded(td_ctx* c, TdSlot& s, int32_t* out_type, const int32_t* out_barcode, const int32_t* out_finger, const int8_t* labels)
 {
 	TdMolState& z = c->molecules;
-	const unsigned blocks = (unsigned)((s.n_tiles + KT_WAVES - 1) / KT_WAVES);
 	TdMolArgs a{};
 	a.tile = kt_tile_view(s, labels); a.lens = s.d_lens; a.out_type = out_type; a.out_barcode = out_barcode; a.out_finger = out_finger;
 	a.label = z.table.d_label; a.n_reads = s.n_reads; a.n_tiles = s.n_tiles; a.H = z.table.H;
 	a.r_segs = z.r_segs; a.prefix = z.prefix;
 	a.table = kt_table_view(z.table); a.tallies = z.table.d_tallies;
-	if (z.mate_bases > 0) {                           // (slot_decode has checked that the slot holds this batch's mates, made with this M)
-		a.mate_w = s.d_mate_w; a.mate_n = s.d_mate_n; a.mate_bases = z.mate_bases;
+	if (z.mate.bases > 0) {                           // (slot_decode has checked that the slot holds this batch's mates, made with this M)
+		a.mate_w = s.d_mate_w; a.mate_n = s.d_mate_n; a.mate_bases = z.mate.bases;
 		a.read_at = s.sorted ? s.d_read_at : nullptr;
 	}
-	if (z.frozen) {
-		a.ordinal_base = z.next_ordinal;              // reads submitted since the freeze: the rule of the survey
-		z.next_ordinal += s.n_reads;
-		a.read_at = s.sorted ? s.d_read_at : nullptr; a.keeper = z.d_keeper;
-		HIPCHK(c, hipEventRecord(z.ev_r0, s.cs));
-		if (s.n_tiles > 0) {
-			hipLaunchKernelGGL(td_mol_replay_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
-			HIPCHK(c, hipGetLastError());
-		}
-		HIPCHK(c, hipEventRecord(z.ev_r1, s.cs));
+	if (z.frozen.on) {
+		a.ordinal_base = z.dedup.next_ordinal;        // reads submitted since the freeze: the rule of the survey
+		z.dedup.next_ordinal += s.n_reads;
+		a.read_at = s.sorted ? s.d_read_at : nullptr; a.keeper = z.frozen.d_keeper;
+		if (kt_launch_slot(c, z.frozen.ev, s, (const void*)td_mol_replay_kernel, &a) != TD_OK) return TD_FAIL;
 		return kt_slot_read_behind(c, s);
 	}
-	if (kt_count_slot(c, z.table, s, (const void*)td_mol_count_kernel, &a) != TD_OK) return TD_FAIL;
-	if (z.collapse) {
-		a.origin = z.d_origin;
-		HIPCHK(c, hipEventRecord(z.ev_o0, s.cs));
-		if (s.n_tiles > 0) {
-			hipLaunchKernelGGL(td_mol_origin_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
-			HIPCHK(c, hipGetLastError());
-		}
-		HIPCHK(c, hipEventRecord(z.ev_o1, s.cs));
+	if (kt_launch_slot(c, z.table.ev, s, (const void*)td_mol_count_kernel, &a) != TD_OK) return TD_FAIL;
+	if (z.collapse.on) {
+		a.origin = z.collapse.d_origin;
+		if (kt_launch_slot(c, z.collapse.ev, s, (const void*)td_mol_origin_kernel, &a) != TD_OK) return TD_FAIL;
 	}
-	if (z.dedup) {
-		a.ordinal_base = z.next_ordinal;              // batches get their ordinals in the order they are submitted in
-		z.next_ordinal += s.n_reads;
+	if (z.dedup.on) {
+		a.ordinal_base = z.dedup.next_ordinal;        // batches get their ordinals in the order they are submitted in
+		z.dedup.next_ordinal += s.n_reads;
 	}
-	if (z.dedup && s.n_tiles > 0) {
+	if (z.dedup.on && s.n_tiles > 0) {                // (a batch without tiles leaves dedup's pair as the batch before left it)
+		TdMolDedup& d = z.dedup;
 		if (ensure(c, &s.d_judged, &s.cap_judged, (size_t)s.n_tiles * TD_WAVE * sizeof(int32_t)) != TD_OK) return TD_FAIL;
-		a.read_at = s.sorted ? s.d_read_at : nullptr; a.first = z.d_first; a.judged = s.d_judged;
-		HIPCHK(c, hipEventRecord(z.ev_d0, s.cs));
-		hipLaunchKernelGGL(td_mol_first_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, a);
-		HIPCHK(c, hipGetLastError());
+		a.read_at = s.sorted ? s.d_read_at : nullptr; a.first = d.d_first; a.judged = s.d_judged;
+		HIPCHK(c, hipEventRecord(d.ev.e0, s.cs));
+		if (kt_launch_tiles(c, s, (const void*)td_mol_first_kernel, &a) != TD_OK) return TD_FAIL;
 		// The batch before this one may run on the other compute stream, and it holds the smaller ordinals: its pass 1 has to be over
 		// before this batch's pass 2 reads a first ordinal.  (The batch before that one ran on this stream, or was waited for.)
-		const int t = z.turn;
-		HIPCHK(c, hipEventRecord(z.ev_p1[t], s.cs));
-		z.p1_queued[t] = true;
-		if (z.p1_queued[t ^ 1]) HIPCHK(c, hipStreamWaitEvent(s.cs, z.ev_p1[t ^ 1], 0));
-		z.turn = t ^ 1;
-		hipLaunchKernelGGL(td_mol_mark_kernel, dim3(blocks), dim3(KT_BLOCK), 0, s.cs, out_type, (const int32_t*)s.d_judged, a.read_at,
-		                   (const kt_u64*)z.d_first, a.ordinal_base, a.n_reads, a.n_tiles, z.table.d_tallies);
+		const int t = d.turn;
+		HIPCHK(c, hipEventRecord(d.ev_p1[t], s.cs));
+		d.p1_queued[t] = true;
+		if (d.p1_queued[t ^ 1]) HIPCHK(c, hipStreamWaitEvent(s.cs, d.ev_p1[t ^ 1], 0));
+		d.turn = t ^ 1;
+		hipLaunchKernelGGL(td_mol_mark_kernel, dim3((unsigned)((s.n_tiles + KT_WAVES - 1) / KT_WAVES)), dim3(KT_BLOCK), 0, s.cs, out_type,
+		                   (const int32_t*)s.d_judged, a.read_at, (const kt_u64*)d.d_first, a.ordinal_base, a.n_reads, a.n_tiles, z.table.d_tallies);
 		HIPCHK(c, hipGetLastError());
-		HIPCHK(c, hipEventRecord(z.ev_d1, s.cs));
+		HIPCHK(c, hipEventRecord(d.ev.e1, s.cs));
 	}
 	// behind the last of them: the finish kernel copies out_type only behind pass 2, and the slot is not restaged under any of these
 	return kt_slot_read_behind(c, s);
@@ -552,12 +533,11 @@ extern "C" int td_mol_reset(td_ctx* c)
 	if (!z.on) return fail(c, "td_mol_reset: the molecule count is off (td_mol_enable)");
 	if (wait_compute(c) != TD_OK) return TD_FAIL;   // (counts of pipelined batches may still be queued, on either compute stream)
 	HIPCHK(c, kt_table_zero(z.table, c->stream));   // (dedup's three tallies among them)
-	if (z.dedup) HIPCHK(c, hipMemsetAsync(z.d_first, 0xFF, sizeof(kt_u64) << z.table.log2_slots, c->stream));
-	if (z.collapse) HIPCHK(c, hipMemsetAsync(z.d_origin, 0, sizeof(td_mol_origin) << z.table.log2_slots, c->stream));
+	if (z.dedup.on) HIPCHK(c, hipMemsetAsync(z.dedup.d_first, 0xFF, sizeof(kt_u64) << z.table.log2_slots, c->stream));
+	if (z.collapse.on) HIPCHK(c, hipMemsetAsync(z.collapse.d_origin, 0, sizeof(td_mol_origin) << z.table.log2_slots, c->stream));
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	z.next_ordinal = 0;
-	z.p1_queued[0] = z.p1_queued[1] = false;          // (nothing is queued any more)
-	z.frozen = false;                                 // (the table is empty: the context surveys again)
+	z.dedup.start_over();                             // (nothing is queued any more)
+	z.frozen.on = false;                              // (the table is empty: the context surveys again; the keepers wait for the next freeze)
 	return TD_OK;
 }
 
@@ -572,10 +552,9 @@ extern "C" int td_mol_mate_enable(td_ctx* c, int32_t mate_bases)
 		return fail(c, "td_mol_mate_enable: mate_bases = %d with prefix_bases = %d (1..%d supported: both share one 64-bit word of %d bases)", mate_bases,
 		            z.prefix, TD_MOL_MAX_PREFIX - z.prefix, TD_MOL_MAX_PREFIX);
 	if (wait_compute(c) != TD_OK) return TD_FAIL;
-	if (!z.ev_m0) HIPCHK(c, hipEventCreate(&z.ev_m0));
-	if (!z.ev_m1) HIPCHK(c, hipEventCreate(&z.ev_m1));
-	z.mate_bases = mate_bases;
-	z.mate_named = false;
+	if (!z.mate.ev.e0) HIPCHK(c, kt_pair_create(z.mate.ev));   // (the pair outlives td_mol_mate_disable: the count's release destroys it)
+	z.mate.bases = mate_bases;
+	z.mate.named = false;
 	return td_mol_reset(c);   // a table never mixes keys made with and without a mate, or with two M
 }
 
@@ -583,10 +562,10 @@ extern "C" int td_mol_mate_disable(td_ctx* c)
 {
 	if (!c) return TD_FAIL;
 	TdMolState& z = c->molecules;
-	if (!z.on || z.mate_bases == 0) return TD_OK;     // (off: there is nothing to do)
+	if (!z.on || z.mate.bases == 0) return TD_OK;     // (off: there is nothing to do)
 	if (tickets_outstanding(c)) return fail(c, "td_mol_mate_disable: td_submit tickets are outstanding (td_wait them first)");
-	z.mate_bases = 0;
-	z.mate_named = false;
+	z.mate.bases = 0;
+	z.mate.named = false;
 	return td_mol_reset(c);
 }
 
@@ -594,32 +573,32 @@ extern "C" int td_mol_mate_next(td_ctx* c, const uint8_t* codes, const int64_t* 
 {
 	if (!c) return fail(nullptr, "td_mol_mate_next: no context");
 	TdMolState& z = c->molecules;
-	if (z.mate_bases == 0) return fail(c, "td_mol_mate_next: mate mode is off (td_mol_mate_enable)");
+	if (z.mate.bases == 0) return fail(c, "td_mol_mate_next: mate mode is off (td_mol_mate_enable)");
 	if (!offs || n_reads < 0 || (!codes && n_reads > 0 && offs[n_reads] > offs[0])) return fail(c, "td_mol_mate_next: bad arguments");
-	z.mate_codes = codes; z.mate_offs = offs; z.mate_reads = n_reads; z.mate_named = true;
+	z.mate.codes = codes; z.mate.offs = offs; z.mate.reads = n_reads; z.mate.named = true;
 	return TD_OK;
 }
 
 int mol_mate_check(td_ctx* c, int64_t n, const char* who)
 {
-	TdMolState& z = c->molecules;
-	if (!z.mate_named)
+	TdMolMate& z = c->molecules.mate;
+	if (!z.named)
 		return fail(c, "%s: mate mode is on (td_mol_mate_enable, %d bases) and no mate batch is named for this batch of %lld reads (td_mol_mate_next "
-		            "first); nothing was counted", who, z.mate_bases, (long long)n);
-	if (z.mate_reads != n) {
-		z.mate_named = false;
+		            "first); nothing was counted", who, z.bases, (long long)n);
+	if (z.reads != n) {
+		z.named = false;
 		return fail(c, "%s: the named mate batch has %lld reads, the batch %lld: mate i belongs to read i; the mate batch is dropped, nothing was counted",
-		            who, (long long)z.mate_reads, (long long)n);
+		            who, (long long)z.reads, (long long)n);
 	}
 	return TD_OK;
 }
 
 int mol_mate_stage(td_ctx* c, TdSlot& s, int64_t n, hipStream_t up)
 {
-	TdMolState& z = c->molecules;
-	const uint8_t* codes = z.mate_codes;
-	const int64_t* offs = z.mate_offs;
-	z.mate_named = false;                             // consumed, whatever happens below
+	TdMolMate& z = c->molecules.mate;
+	const uint8_t* codes = z.codes;
+	const int64_t* offs = z.offs;
+	z.named = false;                                  // consumed, whatever happens below
 	const int64_t base = offs[0];
 	if (ensure_pinned(c, &s.h_mate_offs, &s.cap_h_mate_offs, (size_t)(n + 1) * 8) != TD_OK) return TD_FAIL;
 	s.h_mate_offs[0] = 0;
@@ -642,28 +621,21 @@ int mol_mate_stage(td_ctx* c, TdSlot& s, int64_t n, hipStream_t up)
 	}
 	HIPCHK(c, hipMemcpyAsync(s.d_mate_offs, s.h_mate_offs, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, up));
 	if (n_bases > 0) HIPCHK(c, hipMemcpyAsync(s.d_mate_raw, src, (size_t)n_bases, hipMemcpyHostToDevice, up));
-	s.mate_m = z.mate_bases;
+	s.mate_m = z.bases;
 	return TD_OK;
 }
 
 int mol_mate_launch(td_ctx* c, TdSlot& s, int64_t n)
 {
-	TdMolState& z = c->molecules;
-	HIPCHK(c, hipEventRecord(z.ev_m0, s.aux));
+	const TdMolMate& z = c->molecules.mate;
+	HIPCHK(c, hipEventRecord(z.ev.e0, s.aux));
 	if (n > 0) {
 		hipLaunchKernelGGL(td_mol_mate_kernel, dim3(blocks_for(n)), dim3(KT_BLOCK), 0, s.aux, (const uint8_t*)s.d_mate_raw, (const int64_t*)s.d_mate_offs, n,
-		                   z.mate_bases, s.d_mate_w, s.d_mate_n);
+		                   z.bases, s.d_mate_w, s.d_mate_n);
 		HIPCHK(c, hipGetLastError());
 	}
-	HIPCHK(c, hipEventRecord(z.ev_m1, s.aux));
+	HIPCHK(c, hipEventRecord(z.ev.e1, s.aux));
 	return TD_OK;
-}
-
-int mol_mate_last_kernel_us(td_ctx* c, int32_t* us)
-{
-	const TdMolState& z = c->molecules;
-	if (z.mate_bases == 0) return fail(c, "td_get_option: mate_kernel_us: mate mode is off");
-	return kt_last_kernel_us(c, z.ev_m0, z.ev_m1, us, "td_get_option: mate_kernel_us: no mate batch has been staged yet");
 }
 
 extern "C" int td_mol_dedup_enable(td_ctx* c)
@@ -673,17 +645,17 @@ extern "C" int td_mol_dedup_enable(td_ctx* c)
 	if (!z.on) return fail(c, "td_mol_dedup_enable: the molecule count is off (td_mol_enable first): dedup judges the reads the count has keyed");
 	if (tickets_outstanding(c)) return fail(c, "td_mol_dedup_enable: td_submit tickets are outstanding (td_wait them first)");
 	if (wait_compute(c) != TD_OK) return TD_FAIL;
-	if (!z.dedup) {
-		bool ok = hipMalloc((void**)&z.d_first, sizeof(kt_u64) << z.table.log2_slots) == hipSuccess &&
-		          hipEventCreateWithFlags(&z.ev_p1[0], hipEventDisableTiming) == hipSuccess &&
-		          hipEventCreateWithFlags(&z.ev_p1[1], hipEventDisableTiming) == hipSuccess &&
-		          hipEventCreate(&z.ev_d0) == hipSuccess && hipEventCreate(&z.ev_d1) == hipSuccess;
+	if (!z.dedup.on) {
+		TdMolDedup& d = z.dedup;
+		bool ok = alloc_per_slot(z, (void**)&d.d_first, sizeof(kt_u64)) == hipSuccess &&
+		          hipEventCreateWithFlags(&d.ev_p1[0], hipEventDisableTiming) == hipSuccess &&
+		          hipEventCreateWithFlags(&d.ev_p1[1], hipEventDisableTiming) == hipSuccess && kt_pair_create(d.ev) == hipSuccess;
 		if (!ok) {
 			const std::string e = hipGetErrorString(hipGetLastError());
 			dedup_release(z);
 			return fail(c, "td_mol_dedup_enable: the first ordinals of 2^%d slots could not be set up: %s", z.table.log2_slots, e.c_str());
 		}
-		z.dedup = true;
+		z.dedup.on = true;
 	}
 	return td_mol_reset(c);   // a first ordinal belongs to a key that entered the table with it: both start empty
 }
@@ -691,8 +663,8 @@ extern "C" int td_mol_dedup_enable(td_ctx* c)
 extern "C" int td_mol_dedup_disable(td_ctx* c)
 {
 	if (!c) return TD_FAIL;
-	if (c->molecules.dedup && wait_compute(c) != TD_OK) return TD_FAIL;
-	if (c->molecules.frozen && td_mol_reset(c) != TD_OK) return TD_FAIL;   // the frozen state ends with an empty table
+	if (c->molecules.dedup.on && wait_compute(c) != TD_OK) return TD_FAIL;
+	if (c->molecules.frozen.on && td_mol_reset(c) != TD_OK) return TD_FAIL;   // the frozen state ends with an empty table
 	dedup_release(c->molecules);   // (off: there is nothing to free)
 	return TD_OK;
 }
@@ -701,7 +673,7 @@ extern "C" int td_mol_dedup_get(td_ctx* c, td_mol_dedup_totals* totals)
 {
 	if (!c) return TD_FAIL;
 	TdMolState& z = c->molecules;
-	if (!z.dedup) return fail(c, "td_mol_dedup_get: dedup is off (td_mol_dedup_enable)");
+	if (!z.dedup.on) return fail(c, "td_mol_dedup_get: dedup is off (td_mol_dedup_enable)");
 	if (!totals) return fail(c, "td_mol_dedup_get: bad arguments");
 	if (wait_compute(c) != TD_OK) return TD_FAIL;
 	kt_u64 t[TDM_TALLY_WORDS];
@@ -749,15 +721,14 @@ extern "C" int td_mol_collapse_enable(td_ctx* c)
 	if (!has_f) return fail(c, "td_mol_collapse_enable: the model has no 'F' segment: there is no UMI whose neighbours could be collapsed");
 	if (tickets_outstanding(c)) return fail(c, "td_mol_collapse_enable: td_submit tickets are outstanding (td_wait them first)");
 	if (wait_compute(c) != TD_OK) return TD_FAIL;
-	if (!z.collapse) {
-		bool ok = hipMalloc((void**)&z.d_origin, sizeof(td_mol_origin) << z.table.log2_slots) == hipSuccess &&
-		          hipEventCreate(&z.ev_o0) == hipSuccess && hipEventCreate(&z.ev_o1) == hipSuccess;
+	if (!z.collapse.on) {
+		bool ok = alloc_per_slot(z, (void**)&z.collapse.d_origin, sizeof(td_mol_origin)) == hipSuccess && kt_pair_create(z.collapse.ev) == hipSuccess;
 		if (!ok) {
 			const std::string e = hipGetErrorString(hipGetLastError());
 			collapse_release(z);
 			return fail(c, "td_mol_collapse_enable: the origins of 2^%d slots could not be set up: %s", z.table.log2_slots, e.c_str());
 		}
-		z.collapse = true;
+		z.collapse.on = true;
 	}
 	return td_mol_reset(c);   // an origin belongs to a key that entered the table with it: both start empty
 }
@@ -765,22 +736,15 @@ extern "C" int td_mol_collapse_enable(td_ctx* c)
 extern "C" int td_mol_collapse_disable(td_ctx* c)
 {
 	if (!c) return TD_FAIL;
-	if (c->molecules.collapse && wait_compute(c) != TD_OK) return TD_FAIL;
-	if (c->molecules.frozen && td_mol_reset(c) != TD_OK) return TD_FAIL;   // the frozen state ends with an empty table
+	if (c->molecules.collapse.on && wait_compute(c) != TD_OK) return TD_FAIL;
+	if (c->molecules.frozen.on && td_mol_reset(c) != TD_OK) return TD_FAIL;   // the frozen state ends with an empty table
 	collapse_release(c->molecules);   // (off: there is nothing to free)
 	return TD_OK;
 }
 
-int mol_origin_last_kernel_us(td_ctx* c, int32_t* us)
-{
-	const TdMolState& z = c->molecules;
-	if (!z.collapse) return fail(c, "td_get_option: collapse_origin_kernel_us: the collapse is off");
-	return kt_last_kernel_us(c, z.ev_o0, z.ev_o1, us, "td_get_option: collapse_origin_kernel_us: no batch has left its origins yet");
-}
-
 namespace {
 
-// Waits for the context's work; tallies[TDM_TALLY_WORDS] down, and the occupied slots' indices in z.d_occ: *n_occ of them, held
+// Waits for the context's work; tallies[TDM_TALLY_WORDS] down, and the occupied slots' indices in the collapse's d_occ: *n_occ of them, held
 // against the count's own tally of distinct keys
 int collapse_occupied(td_ctx* c, const char* who, kt_u64* tallies, int64_t* n_occ)
 {
@@ -790,13 +754,13 @@ int collapse_occupied(td_ctx* c, const char* who, kt_u64* tallies, int64_t* n_oc
 	const int64_t distinct = (int64_t)tallies[TDM_MOLECULES];
 	*n_occ = distinct;
 	if (distinct == 0) return TD_OK;
-	if (ensure(c, &z.d_occ, &z.cap_occ, sizeof(uint32_t) * (size_t)distinct) != TD_OK) return TD_FAIL;
+	if (ensure(c, &z.collapse.d_occ, &z.collapse.cap_occ, sizeof(uint32_t) * (size_t)distinct) != TD_OK) return TD_FAIL;
 	const int64_t n_slots = (int64_t)1 << z.table.log2_slots;
 	kt_u64* cursor = z.table.d_tallies + TDM_GATHERED;
 	int64_t found = 0;
 	if (kt_sweep_dense(c, who, "the sweep over the occupied slots failed", cursor, 0, nullptr, 0, nullptr, 0, [&](void*, void*) {
 		    hipLaunchKernelGGL(td_mol_occupied_kernel, dim3(std::min(blocks_for(n_slots), 2048u)), dim3(KT_BLOCK), 0, c->stream,
-		                       (const kt_u64*)z.table.d_keys, n_slots, z.d_occ, distinct, cursor);
+		                       (const kt_u64*)z.table.d_keys, n_slots, z.collapse.d_occ, distinct, cursor);
 	    }, &found) != TD_OK) return TD_FAIL;
 	if (found != distinct) return fail(c, "%s: the table holds %lld keys, its tally says %lld", who, (long long)found, (long long)distinct);
 	return TD_OK;
@@ -817,32 +781,32 @@ int collapse_gather(td_ctx* c, const char* who, const kt_u64* values, int64_t n_
 	if (kt_sweep_dense(c, who, "the gather failed", cursor, (size_t)expect, v.data(), sizeof(td_census_entry), vo.data(), sizeof(td_mol_origin),
 	                   [&](void* d_e, void* d_o) {
 		    hipLaunchKernelGGL(td_mol_gather_kernel, dim3(blocks_for(n_occ)), dim3(KT_BLOCK), 0, c->stream, (const kt_u64*)z.table.d_keys, values,
-		                       (const td_mol_origin*)z.d_origin, (const uint32_t*)z.d_occ, n_occ, (td_census_entry*)d_e, (td_mol_origin*)d_o, expect, cursor);
+		                       (const td_mol_origin*)z.collapse.d_origin, (const uint32_t*)z.collapse.d_occ, n_occ, (td_census_entry*)d_e, (td_mol_origin*)d_o, expect, cursor);
 	    }, &found) != TD_OK) return TD_FAIL;
 	if (found != expect) return fail(c, "%s: %lld entries were gathered, %lld expected", who, (long long)found, (long long)expect);
 	mol_emit_ordered(v.data(), vo.data(), expect, cap, entries, origins);
 	return TD_OK;
 }
 
-// The collapse on the device: z.d_occ, z.d_parent and z.d_collapsed of the table as it stands; the totals
+// The collapse on the device: d_occ, d_parent and d_collapsed of the table as it stands; the totals
 int collapse_run(td_ctx* c, const char* who, int64_t* n_occ, td_mol_collapse_totals* totals)
 {
 	TdMolState& z = c->molecules;
-	if (!z.collapse) return fail(c, "%s: the collapse is off (td_mol_collapse_enable)", who);
+	TdMolCollapse& o = z.collapse;
+	if (!o.on) return fail(c, "%s: the collapse is off (td_mol_collapse_enable)", who);
 	kt_u64 t[TDM_TALLY_WORDS];
 	if (collapse_occupied(c, who, t, n_occ) != TD_OK) return TD_FAIL;
-	const size_t n_slots = (size_t)1 << z.table.log2_slots;
-	if (!z.d_parent) HIPCHK(c, hipMalloc((void**)&z.d_parent, sizeof(uint32_t) * n_slots));
-	if (!z.d_collapsed) HIPCHK(c, hipMalloc((void**)&z.d_collapsed, sizeof(kt_u64) * n_slots));
-	HIPCHK(c, hipMemsetAsync(z.d_collapsed, 0, sizeof(kt_u64) * n_slots, c->stream));
+	if (!o.d_parent) HIPCHK(c, alloc_per_slot(z, (void**)&o.d_parent, sizeof(uint32_t)));
+	if (!o.d_collapsed) HIPCHK(c, alloc_per_slot(z, (void**)&o.d_collapsed, sizeof(kt_u64)));
+	HIPCHK(c, hipMemsetAsync(o.d_collapsed, 0, sizeof(kt_u64) << z.table.log2_slots, c->stream));
 	HIPCHK(c, hipMemsetAsync(z.table.d_tallies + TDM_ROOTS, 0, sizeof(kt_u64) * 2, c->stream));   // (TDM_ROOTS, TDM_CHAIN)
 	static_assert(TDM_CHAIN == TDM_ROOTS + 1, "the two are zeroed together");
 	if (*n_occ > 0) {
 		hipLaunchKernelGGL(td_mol_parent_kernel, dim3(blocks_for(*n_occ)), dim3(KT_BLOCK), 0, c->stream, kt_table_view(z.table),
-		                   (const td_mol_origin*)z.d_origin, (const uint32_t*)z.d_occ, *n_occ, z.d_parent);
+		                   (const td_mol_origin*)o.d_origin, (const uint32_t*)o.d_occ, *n_occ, o.d_parent);
 		HIPCHK(c, hipGetLastError());
 		hipLaunchKernelGGL(td_mol_root_kernel, dim3(blocks_for(*n_occ)), dim3(KT_BLOCK), 0, c->stream, (const kt_u64*)z.table.d_counts,
-		                   (const uint32_t*)z.d_occ, *n_occ, (const uint32_t*)z.d_parent, z.d_collapsed, z.table.d_tallies);
+		                   (const uint32_t*)o.d_occ, *n_occ, (const uint32_t*)o.d_parent, o.d_collapsed, z.table.d_tallies);
 		HIPCHK(c, hipGetLastError());
 	}
 	HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -859,7 +823,7 @@ extern "C" int td_mol_origins(td_ctx* c, td_census_entry* entries, td_mol_origin
 {
 	if (!c) return TD_FAIL;
 	TdMolState& z = c->molecules;
-	if (!z.collapse) return fail(c, "td_mol_origins: the collapse is off (td_mol_collapse_enable)");
+	if (!z.collapse.on) return fail(c, "td_mol_origins: the collapse is off (td_mol_collapse_enable)");
 	if (cap < 0 || (cap > 0 && (!entries || !origins)) || !n) return fail(c, "td_mol_origins: bad arguments");
 	*n = 0;
 	kt_u64 t[TDM_TALLY_WORDS];
@@ -878,7 +842,7 @@ extern "C" int td_mol_collapse_get(td_ctx* c, td_mol_row rows[TD_NUM_BARCODE_BIN
 	int64_t n_occ = 0;
 	td_mol_collapse_totals t{};
 	if (collapse_run(c, "td_mol_collapse_get", &n_occ, &t) != TD_OK) return TD_FAIL;
-	if (summary_rows(c, z.d_collapsed, rows) != TD_OK) return TD_FAIL;   // the count's own sweep over the collapsed counts
+	if (summary_rows(c, z.collapse.d_collapsed, rows) != TD_OK) return TD_FAIL;   // the count's own sweep over the collapsed counts
 	if (totals) *totals = t;
 	return TD_OK;
 }
@@ -893,7 +857,7 @@ extern "C" int td_mol_collapse_entries(td_ctx* c, td_census_entry* entries, td_m
 	int64_t n_occ = 0;
 	td_mol_collapse_totals t{};
 	if (collapse_run(c, "td_mol_collapse_entries", &n_occ, &t) != TD_OK) return TD_FAIL;
-	if (collapse_gather(c, "td_mol_collapse_entries", z.d_collapsed, n_occ, t.molecules_after, entries, origins, cap, n) != TD_OK) return TD_FAIL;
+	if (collapse_gather(c, "td_mol_collapse_entries", z.collapse.d_collapsed, n_occ, t.molecules_after, entries, origins, cap, n) != TD_OK) return TD_FAIL;
 	if (totals) *totals = t;
 	return TD_OK;
 }
@@ -904,57 +868,64 @@ extern "C" int td_mol_dedup_freeze(td_ctx* c, td_mol_collapse_totals* totals)
 	if (!c) return fail(nullptr, "td_mol_dedup_freeze: no context");
 	TdMolState& z = c->molecules;
 	if (!z.on) return fail(c, "td_mol_dedup_freeze: the molecule count is off (td_mol_enable)");
-	if (!z.dedup) return fail(c, "td_mol_dedup_freeze: dedup is off (td_mol_dedup_enable)");
-	if (!z.collapse) return fail(c, "td_mol_dedup_freeze: the collapse is off (td_mol_collapse_enable)");
+	if (!z.dedup.on) return fail(c, "td_mol_dedup_freeze: dedup is off (td_mol_dedup_enable)");
+	if (!z.collapse.on) return fail(c, "td_mol_dedup_freeze: the collapse is off (td_mol_collapse_enable)");
 	if (tickets_outstanding(c)) return fail(c, "td_mol_dedup_freeze: td_submit tickets are outstanding (td_wait them first)");
 	int64_t n_occ = 0;
 	td_mol_collapse_totals t{};
 	if (collapse_run(c, "td_mol_dedup_freeze", &n_occ, &t) != TD_OK) return TD_FAIL;   // (waits for the context's queued work)
-	if (!z.d_keeper) {
-		const bool ok = hipMalloc((void**)&z.d_keeper, sizeof(kt_u64) << z.table.log2_slots) == hipSuccess &&
-		                hipEventCreate(&z.ev_r0) == hipSuccess && hipEventCreate(&z.ev_r1) == hipSuccess;
+	if (!z.frozen.d_keeper) {
+		const bool ok = alloc_per_slot(z, (void**)&z.frozen.d_keeper, sizeof(kt_u64)) == hipSuccess && kt_pair_create(z.frozen.ev) == hipSuccess;
 		if (!ok) {
 			const std::string e = hipGetErrorString(hipGetLastError());
-			keeper_release(z);
+			frozen_release(z);
 			return fail(c, "td_mol_dedup_freeze: the keepers of 2^%d slots could not be set up: %s", z.table.log2_slots, e.c_str());
 		}
 	}
 	if (n_occ > 0) {
-		hipLaunchKernelGGL(td_mol_keeper_kernel, dim3(blocks_for(n_occ)), dim3(KT_BLOCK), 0, c->stream, (const uint32_t*)z.d_occ, n_occ,
-		                   (const uint32_t*)z.d_parent, (const kt_u64*)z.d_first, z.d_keeper);
+		hipLaunchKernelGGL(td_mol_keeper_kernel, dim3(blocks_for(n_occ)), dim3(KT_BLOCK), 0, c->stream, (const uint32_t*)z.collapse.d_occ, n_occ,
+		                   (const uint32_t*)z.collapse.d_parent, (const kt_u64*)z.dedup.d_first, z.frozen.d_keeper);
 		HIPCHK(c, hipGetLastError());
 	}
 	HIPCHK(c, hipMemsetAsync(z.table.d_tallies + TDM_KEPT, 0, sizeof(kt_u64) * 3, c->stream));   // (TDM_KEPT, TDM_DUPLICATES, TDM_UNJUDGED)
 	static_assert(TDM_DUPLICATES == TDM_KEPT + 1 && TDM_UNJUDGED == TDM_KEPT + 2, "the three are zeroed together");
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	z.next_ordinal = 0;
-	z.p1_queued[0] = z.p1_queued[1] = false;          // (nothing is queued any more)
-	z.frozen = true;
+	z.dedup.start_over();                             // (nothing is queued any more: the replay's ordinals are those of the reads since)
+	z.frozen.on = true;
 	if (totals) *totals = t;
 	return TD_OK;
 }
 
-// the replay kernel's time of the last batch of the frozen state (option "dedup_replay_kernel_us" of td_get_option)
-int mol_replay_last_kernel_us(td_ctx* c, int32_t* us)
-{
-	const TdMolState& z = c->molecules;
-	if (!z.frozen) return fail(c, "td_get_option: dedup_replay_kernel_us: the context is not frozen (td_mol_dedup_freeze)");
-	return kt_last_kernel_us(c, z.ev_r0, z.ev_r1, us, "td_get_option: dedup_replay_kernel_us: no batch has been replayed yet");
-}
+// ---- the "*_kernel_us" options ----
+// One row per option: the stage's pair, whether the stage is on, and what it refuses with while it is off / before its first batch.
+// dedup_kernel_us: between the two passes the stream waits for the batch before -- with batches in flight on both compute streams
+// that wait is inside the figure, after a td_run it is not.
+static const struct {
+	const char* name;
+	const KtEventPair& (*pair)(const TdMolState&);
+	bool (*on)(const TdMolState&);
+	const char* off;
+	const char* none_yet;
+} kMolKernelUs[] = {
+	{ "molecules_kernel_us", [](const TdMolState& z) -> const KtEventPair& { return z.table.ev; }, [](const TdMolState& z) { return z.on; },
+	  "td_get_option: molecules_kernel_us: the molecule count is off", "td_get_option: molecules_kernel_us: no batch has been counted yet" },
+	{ "dedup_kernel_us", [](const TdMolState& z) -> const KtEventPair& { return z.dedup.ev; }, [](const TdMolState& z) { return z.dedup.on; },
+	  "td_get_option: dedup_kernel_us: dedup is off", "td_get_option: dedup_kernel_us: no batch has been judged yet" },
+	{ "collapse_origin_kernel_us", [](const TdMolState& z) -> const KtEventPair& { return z.collapse.ev; }, [](const TdMolState& z) { return z.collapse.on; },
+	  "td_get_option: collapse_origin_kernel_us: the collapse is off", "td_get_option: collapse_origin_kernel_us: no batch has left its origins yet" },
+	{ "dedup_replay_kernel_us", [](const TdMolState& z) -> const KtEventPair& { return z.frozen.ev; }, [](const TdMolState& z) { return z.frozen.on; },
+	  "td_get_option: dedup_replay_kernel_us: the context is not frozen (td_mol_dedup_freeze)",
+	  "td_get_option: dedup_replay_kernel_us: no batch has been replayed yet" },
+	{ "mate_kernel_us", [](const TdMolState& z) -> const KtEventPair& { return z.mate.ev; }, [](const TdMolState& z) { return z.mate.bases != 0; },
+	  "td_get_option: mate_kernel_us: mate mode is off", "td_get_option: mate_kernel_us: no mate batch has been staged yet" },
+};
 
-// the count kernel's time of the last batch, for tools/molecules_bench.py (option "molecules_kernel_us" of td_get_option)
-int mol_last_kernel_us(td_ctx* c, int32_t* us)
+int mol_kernel_us(td_ctx* c, const char* name, int32_t* us)
 {
-	const TdCountTable& t = c->molecules.table;
-	if (!c->molecules.on) return fail(c, "td_get_option: molecules_kernel_us: the molecule count is off");
-	return kt_last_kernel_us(c, t.ev_c0, t.ev_c1, us, "td_get_option: molecules_kernel_us: no batch has been counted yet");
-}
-
-// the two passes' time of the last batch (option "dedup_kernel_us" of td_get_option).  Between them the stream waits for the batch
-// before: with batches in flight on both compute streams that wait is inside the figure, after a td_run it is not.
-int mol_dedup_last_kernel_us(td_ctx* c, int32_t* us)
-{
-	const TdMolState& z = c->molecules;
-	if (!z.dedup) return fail(c, "td_get_option: dedup_kernel_us: dedup is off");
-	return kt_last_kernel_us(c, z.ev_d0, z.ev_d1, us, "td_get_option: dedup_kernel_us: no batch has been judged yet");
+	for (const auto& o : kMolKernelUs) {
+		if (strcmp(name, o.name) != 0) continue;
+		if (!o.on(c->molecules)) return fail(c, "%s", o.off);
+		return kt_last_kernel_us(c, o.pair(c->molecules), us, o.none_yet);
+	}
+	return -1;
 }

@@ -931,31 +931,6 @@ def _mol_origin_array(ptr, n):
     return out
 
 
-def mol_host_origins(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
-    """td_mol_host_origins: mol_host plus what every key was made of.  Returns (entries, origins MOL_ORIGIN_DTYPE, totals dict)."""
-    lib = _mol_lib()
-    desc, keep = make_model_desc(md)
-    seq = np.ascontiguousarray(seq, np.uint8)
-    if len(seq) == 0:
-        seq = np.zeros(1, np.uint8)
-    offs = np.ascontiguousarray(offs, np.int64)
-    labels = np.ascontiguousarray(labels, np.int8)
-    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
-    for f in ("read_type", "barcode", "fingerprint"):
-        rr[f] = np.asarray(res[f])
-    ptr, optr, n, tot = C.c_void_p(), C.c_void_p(), C.c_int64(), _MolTotals()
-    rc = lib.td_mol_host_origins(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
-                                 labels.ctypes.data, C.byref(ptr), C.byref(optr), C.byref(n), C.byref(tot))
-    del keep
-    if rc != 0:
-        raise TdError(lib.td_last_error(None).decode())
-    try:
-        return _census_entries(ptr, n.value), _mol_origin_array(optr, n.value), tot.as_dict()
-    finally:
-        lib.td_census_free(ptr)
-        lib.free(optr)
-
-
 def mol_collapse_host(entries, origins):
     """td_mol_collapse_host: the collapse of (key, count) entries with their origins, repeated keys added first (no GPU).  Returns
     (the roots with their collapsed counts, their origins, totals dict)."""
@@ -974,10 +949,12 @@ def mol_collapse_host(entries, origins):
         lib.free(optr)
 
 
-def mol_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
-    """td_mol_host: the molecule count of a batch from host arrays (no GPU).  md: model mapping; res: the reads' records
-    (RESULT_DTYPE, or any mapping / structured array with read_type, barcode and fingerprint: td_batch_download's, or the
-    oracle's); labels as td_batch_download leaves them.  Returns (entries, totals dict)."""
+def _mol_host_call(symbol, md, seq, offs, res, labels, mate, prefix_bases, out):
+    """What the eight host yardsticks over a batch share.  Prepares the model description, the arrays as the C side reads them and the
+    td_mol_mate (mate: None, or (codes, offs, bases) with one mate per read in the reads' order); calls `symbol`, a *_mated entry point
+    -- with mate None it is the unmated one, messages included --; raises TdError on failure; converts and frees what C allocated.
+    out: "entries" (entries, totals), "origins" (entries, origins, totals), "marks" (is_duplicate, dedup totals) or "collapsed"
+    (is_duplicate, dedup totals, collapse totals)."""
     lib = _mol_lib()
     desc, keep = make_model_desc(md)
     seq = np.ascontiguousarray(seq, np.uint8)
@@ -985,153 +962,88 @@ def mol_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
         seq = np.zeros(1, np.uint8)
     offs = np.ascontiguousarray(offs, np.int64)
     labels = np.ascontiguousarray(labels, np.int8)
-    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
+    n = len(offs) - 1
+    rr = np.zeros(n, RESULT_DTYPE)
     for f in ("read_type", "barcode", "fingerprint"):
         rr[f] = np.asarray(res[f])
-    ptr, n, tot = C.c_void_p(), C.c_int64(), _MolTotals()
-    rc = lib.td_mol_host(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
-                         labels.ctypes.data, C.byref(ptr), C.byref(n), C.byref(tot))
-    del keep
-    if rc != 0:
-        raise TdError(lib.td_last_error(None).decode())
-    try:
-        return _census_entries(ptr, n.value), tot.as_dict()
-    finally:
-        lib.td_census_free(ptr)
-
-
-def mol_dedup_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
-    """td_mol_dedup_host: which reads of a batch are not the first of their molecule, the reads in the given order (no GPU).
-    Arguments as mol_host takes them.  Returns (is_duplicate, a bool per read; totals dict)."""
-    lib = _mol_lib()
-    desc, keep = make_model_desc(md)
-    seq = np.ascontiguousarray(seq, np.uint8)
-    if len(seq) == 0:
-        seq = np.zeros(1, np.uint8)
-    offs = np.ascontiguousarray(offs, np.int64)
-    labels = np.ascontiguousarray(labels, np.int8)
-    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
-    for f in ("read_type", "barcode", "fingerprint"):
-        rr[f] = np.asarray(res[f])
-    dup = np.zeros(max(len(offs) - 1, 1), np.uint8)
-    tot = _MolDedupTotals()
-    rc = lib.td_mol_dedup_host(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
-                               labels.ctypes.data, dup.ctypes.data, C.byref(tot))
-    del keep
-    if rc != 0:
-        raise TdError(lib.td_last_error(None).decode())
-    return dup[:len(offs) - 1].astype(bool), tot.as_dict()
-
-
-def mol_dedup_collapsed_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
-    """td_mol_dedup_collapsed_host: which reads are not the one read their collapsed molecule keeps -- the reads surveyed and the same
-    reads replayed, in the given order (no GPU).  Arguments as mol_host takes them.  Returns (is_duplicate, a bool per read; dedup
-    totals dict; collapse totals dict)."""
-    lib = _mol_lib()
-    desc, keep = make_model_desc(md)
-    seq = np.ascontiguousarray(seq, np.uint8)
-    if len(seq) == 0:
-        seq = np.zeros(1, np.uint8)
-    offs = np.ascontiguousarray(offs, np.int64)
-    labels = np.ascontiguousarray(labels, np.int8)
-    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
-    for f in ("read_type", "barcode", "fingerprint"):
-        rr[f] = np.asarray(res[f])
-    dup = np.zeros(max(len(offs) - 1, 1), np.uint8)
-    tot, ctot = _MolDedupTotals(), _MolCollapseTotals()
-    rc = lib.td_mol_dedup_collapsed_host(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
-                                         labels.ctypes.data, dup.ctypes.data, C.byref(tot), C.byref(ctot))
-    del keep
-    if rc != 0:
-        raise TdError(lib.td_last_error(None).decode())
-    return dup[:len(offs) - 1].astype(bool), tot.as_dict(), ctot.as_dict()
-
-
-def _mol_mated_args(md, seq, offs, res, labels, mate):
-    """what the *_mated host functions share: the model description, the arrays as the C side reads them, and the td_mol_mate (mate:
-    None, or (codes, offs, bases) with one mate per read in the reads' order).  The last item keeps everything alive."""
-    desc, keep = make_model_desc(md)
-    seq = np.ascontiguousarray(seq, np.uint8)
-    if len(seq) == 0:
-        seq = np.zeros(1, np.uint8)
-    offs = np.ascontiguousarray(offs, np.int64)
-    labels = np.ascontiguousarray(labels, np.int8)
-    rr = np.zeros(len(offs) - 1, RESULT_DTYPE)
-    for f in ("read_type", "barcode", "fingerprint"):
-        rr[f] = np.asarray(res[f])
-    mp, mkeep = None, None
+    mp = None
     if mate is not None:
         mc = np.ascontiguousarray(mate[0], np.uint8)
         if len(mc) == 0:
             mc = np.zeros(1, np.uint8)
         mo = np.ascontiguousarray(mate[1], np.int64)
         if len(mo) != len(offs):
-            raise ValueError("the mate batch has %d reads, the batch %d" % (len(mo) - 1, len(offs) - 1))
+            raise ValueError("the mate batch has %d reads, the batch %d" % (len(mo) - 1, n))
         mm = _MolMate(mc.ctypes.data, mo.ctypes.data, int(mate[2]))
-        mp, mkeep = C.byref(mm), (mc, mo, mm)
-    return desc, seq, offs, rr, labels, mp, (keep, mkeep)
-
-
-def mol_host_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
-    """td_mol_host_mated: mol_host with the mate batch joined into the key (mate: (codes, offs, bases), or None for mol_host itself)."""
-    lib = _mol_lib()
-    desc, seq, offs, rr, labels, mp, keep = _mol_mated_args(md, seq, offs, res, labels, mate)
-    ptr, n, tot = C.c_void_p(), C.c_int64(), _MolTotals()
-    rc = lib.td_mol_host_mated(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
-                               labels.ctypes.data, mp, C.byref(ptr), C.byref(n), C.byref(tot))
+        mp = C.byref(mm)
+    ptr, optr, count = C.c_void_p(), C.c_void_p(), C.c_int64()
+    dup = np.zeros(max(n, 1), np.uint8)
+    if out in ("entries", "origins"):
+        tots = [_MolTotals()]
+        outs = [C.byref(ptr)] + ([C.byref(optr)] if out == "origins" else []) + [C.byref(count)]
+    else:
+        tots = [_MolDedupTotals()] + ([_MolCollapseTotals()] if out == "collapsed" else [])
+        outs = [dup.ctypes.data]
+    rc = getattr(lib, symbol)(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, n, rr.ctypes.data, labels.ctypes.data, mp,
+                              *outs, *[C.byref(t) for t in tots])
     del keep
     if rc != 0:
         raise TdError(lib.td_last_error(None).decode())
     try:
-        return _census_entries(ptr, n.value), tot.as_dict()
-    finally:
-        lib.td_census_free(ptr)
-
-
-def mol_host_origins_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
-    """td_mol_host_origins_mated: mol_host_origins with the mate batch joined into the key (mate as mol_host_mated takes it)."""
-    lib = _mol_lib()
-    desc, seq, offs, rr, labels, mp, keep = _mol_mated_args(md, seq, offs, res, labels, mate)
-    ptr, optr, n, tot = C.c_void_p(), C.c_void_p(), C.c_int64(), _MolTotals()
-    rc = lib.td_mol_host_origins_mated(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
-                                       labels.ctypes.data, mp, C.byref(ptr), C.byref(optr), C.byref(n), C.byref(tot))
-    del keep
-    if rc != 0:
-        raise TdError(lib.td_last_error(None).decode())
-    try:
-        return _census_entries(ptr, n.value), _mol_origin_array(optr, n.value), tot.as_dict()
+        if out == "entries":
+            return _census_entries(ptr, count.value), tots[0].as_dict()
+        if out == "origins":
+            return _census_entries(ptr, count.value), _mol_origin_array(optr, count.value), tots[0].as_dict()
+        return (dup[:n].astype(bool),) + tuple(t.as_dict() for t in tots)
     finally:
         lib.td_census_free(ptr)
         lib.free(optr)
 
 
+def mol_host_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_host_mated: mol_host with the mate batch joined into the key (mate: (codes, offs, bases), or None for mol_host itself)."""
+    return _mol_host_call("td_mol_host_mated", md, seq, offs, res, labels, mate, prefix_bases, "entries")
+
+
+def mol_host_origins_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_host_origins_mated: mol_host_origins with the mate batch joined into the key (mate as mol_host_mated takes it)."""
+    return _mol_host_call("td_mol_host_origins_mated", md, seq, offs, res, labels, mate, prefix_bases, "origins")
+
+
 def mol_dedup_host_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
     """td_mol_dedup_host_mated: mol_dedup_host with the mate batch joined into the key (mate as mol_host_mated takes it)."""
-    lib = _mol_lib()
-    desc, seq, offs, rr, labels, mp, keep = _mol_mated_args(md, seq, offs, res, labels, mate)
-    dup = np.zeros(max(len(offs) - 1, 1), np.uint8)
-    tot = _MolDedupTotals()
-    rc = lib.td_mol_dedup_host_mated(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1, rr.ctypes.data,
-                                     labels.ctypes.data, mp, dup.ctypes.data, C.byref(tot))
-    del keep
-    if rc != 0:
-        raise TdError(lib.td_last_error(None).decode())
-    return dup[:len(offs) - 1].astype(bool), tot.as_dict()
+    return _mol_host_call("td_mol_dedup_host_mated", md, seq, offs, res, labels, mate, prefix_bases, "marks")
 
 
 def mol_dedup_collapsed_host_mated(md, seq, offs, res, labels, mate, prefix_bases=MOL_DEFAULT_PREFIX):
     """td_mol_dedup_collapsed_host_mated: mol_dedup_collapsed_host with the mate batch joined into the key (mate as mol_host_mated
     takes it)."""
-    lib = _mol_lib()
-    desc, seq, offs, rr, labels, mp, keep = _mol_mated_args(md, seq, offs, res, labels, mate)
-    dup = np.zeros(max(len(offs) - 1, 1), np.uint8)
-    tot, ctot = _MolDedupTotals(), _MolCollapseTotals()
-    rc = lib.td_mol_dedup_collapsed_host_mated(C.byref(desc), int(prefix_bases), seq.ctypes.data, offs.ctypes.data, len(offs) - 1,
-                                               rr.ctypes.data, labels.ctypes.data, mp, dup.ctypes.data, C.byref(tot), C.byref(ctot))
-    del keep
-    if rc != 0:
-        raise TdError(lib.td_last_error(None).decode())
-    return dup[:len(offs) - 1].astype(bool), tot.as_dict(), ctot.as_dict()
+    return _mol_host_call("td_mol_dedup_collapsed_host_mated", md, seq, offs, res, labels, mate, prefix_bases, "collapsed")
+
+
+def mol_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_host: the molecule count of a batch from host arrays (no GPU).  md: model mapping; res: the reads' records
+    (RESULT_DTYPE, or any mapping / structured array with read_type, barcode and fingerprint: td_batch_download's, or the
+    oracle's); labels as td_batch_download leaves them.  Returns (entries, totals dict)."""
+    return mol_host_mated(md, seq, offs, res, labels, None, prefix_bases)
+
+
+def mol_host_origins(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_host_origins: mol_host plus what every key was made of.  Returns (entries, origins MOL_ORIGIN_DTYPE, totals dict)."""
+    return mol_host_origins_mated(md, seq, offs, res, labels, None, prefix_bases)
+
+
+def mol_dedup_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_dedup_host: which reads of a batch are not the first of their molecule, the reads in the given order (no GPU).
+    Arguments as mol_host takes them.  Returns (is_duplicate, a bool per read; totals dict)."""
+    return mol_dedup_host_mated(md, seq, offs, res, labels, None, prefix_bases)
+
+
+def mol_dedup_collapsed_host(md, seq, offs, res, labels, prefix_bases=MOL_DEFAULT_PREFIX):
+    """td_mol_dedup_collapsed_host: which reads are not the one read their collapsed molecule keeps -- the reads surveyed and the same
+    reads replayed, in the given order (no GPU).  Arguments as mol_host takes them.  Returns (is_duplicate, a bool per read; dedup
+    totals dict; collapse totals dict)."""
+    return mol_dedup_collapsed_host_mated(md, seq, offs, res, labels, None, prefix_bases)
 
 
 def mol_summarise(entries):

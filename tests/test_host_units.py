@@ -15,7 +15,7 @@ CSRC = os.path.join(REPO, "tagdust_amd", "csrc")
 # links its own unit alone
 COUNT_UNITS = ("td_census_host.cpp", "td_molecules_host.cpp")
 PROGRAMS = [("census_host_check", []), ("molecules_host_check", ["td_fastq.cpp"]), ("dedup_host_check", []), ("collapse_host_check", []),
-            ("batch_plan_host_check", ["td_batch_plan.cpp"])]
+            ("dedup_collapsed_host_check", []), ("mate_host_check", []), ("batch_plan_host_check", ["td_batch_plan.cpp"])]
 
 
 def host_compiler():
@@ -45,7 +45,7 @@ def compiled(cxx, as_cxx, source, out_dir):
 
 @pytest.fixture(scope="module")
 def host_objects(tmp_path_factory):
-    """the two host units of the counts, compiled once for the four programs over them"""
+    """the two host units of the counts, compiled once for the programs over them"""
     cxx, as_cxx = host_compiler()
     assert cxx, "no host C++ compiler: set CXX, or install g++"
     d = str(tmp_path_factory.mktemp("host_units"))
@@ -60,3 +60,10 @@ def test_the_host_units_build_and_agree_without_hip(tmp_path, host_objects, name
     exe = os.path.join(d, name)
     run(cxx + ([] if name == "batch_plan_host_check" else host_objects) + objs + ["-o", exe, "-lpthread"])
     assert (name + ": ok") in run([exe]).splitlines()
+
+
+def test_the_sanitizer_script_builds_and_runs_every_program():
+    script = open(os.path.join(REPO, "tools", "host_checks.sh")).read()
+    for name, _ in PROGRAMS:
+        assert ("tools/%s.cpp -o $OUT/%s" % (name, name)) in script, name
+        assert ("\n$OUT/%s &&" % name) in script, name
