@@ -34,17 +34,6 @@ static void init_logsum_host()
 // prob2scaledprob(), src/misc.c:85-92
 static float p2sp(float p) { return p == 0.0f ? -INFINITY : (float)log((double)p); }
 
-// Host threads a context may use for its copies between pageable caller memory and pinned staging: TD_HOST_THREADS, else the
-// machine's threads, at most 16 (option "host_threads"; td_multi_create shares the machine's threads out over its devices).
-int default_host_threads()
-{
-	int nt = (int)std::thread::hardware_concurrency();
-	if (const char* e = getenv("TD_HOST_THREADS")) nt = atoi(e);
-	if (nt > 16) nt = 16;
-	if (nt < 1) nt = 1;
-	return nt;
-}
-
 // The copy threads of one context: started once, reused by every batch (the calling thread takes a share of each copy itself).
 // The pipelined calls keep six streams busy (two compute streams, upload, download and two for the small kernels around the
 // decode).  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues, four unless told otherwise: two of the

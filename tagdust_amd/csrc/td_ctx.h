@@ -172,11 +172,13 @@ struct TdSpecState {
 	bool prune_live = false;    // ... and they are real bounds (not the all-zero tables of reads beyond 8192 bases)
 };
 
-TD_HIDDEN int default_host_threads();
 struct td_ctx {
 	int device = 0;
-	int host_threads = default_host_threads();
-	CopyPool pool;
+	// Host threads the context may use for its copies between pageable caller memory and pinned staging (option "host_threads";
+	// td_multi_create shares the machine's threads out over its devices), and the threads themselves: started by the first batch
+	// that needs them, reused by every later one.
+	int host_threads = td_context_threads();
+	TdWorkers pool;
 	hipStream_t stream = nullptr;
 	std::string err;
 	int n_cu = 0;

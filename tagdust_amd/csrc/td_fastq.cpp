@@ -9,6 +9,7 @@
 
 #include "../../include/tagdust_io.h"
 #include "td_io_internal.h"
+#include "td_workers.h"
 
 namespace {
 
@@ -118,12 +119,8 @@ extern "C" int td_reads_parse(const char* text, int64_t len, int32_t n_threads, 
 	cut.push_back(len);
 	const int nchunk = (int)cut.size() - 1;
 	std::vector<std::vector<Rec>> recs((size_t)nchunk);
-	{
-		std::vector<std::thread> th;
-		for (int k = 1; k < nchunk; k++) th.emplace_back(td_parse_range, text, cut[(size_t)k], cut[(size_t)k + 1], std::ref(recs[(size_t)k]));
-		td_parse_range(text, cut[0], cut[1], recs[0]);
-		for (auto& t : th) t.join();
-	}
+	TdWorkers pool(nchunk);                  // for this call: the record pass, then the base codes (ranges adds what it needs)
+	pool.run(nchunk, [&](int64_t k) { td_parse_range(text, cut[(size_t)k], cut[(size_t)k + 1], recs[(size_t)k]); });
 	int64_t n = 0;
 	for (auto& v : recs) {
 		// "Length of sequence and base qualities differ" ends the reference's run (io.c:1776-1781): a short or cut-off
@@ -165,12 +162,7 @@ extern "C" int td_reads_parse(const char* text, int64_t len, int32_t n_threads, 
 		}
 	};
 	if (n_threads == 1 || n < 65536) encode(0, n);
-	else {
-		std::vector<std::thread> th;
-		const int64_t per = (n + n_threads - 1) / n_threads;
-		for (int t = 0; t < n_threads; t++) { const int64_t lo = t * per, hi = lo + per < n ? lo + per : n; if (lo < hi) th.emplace_back(encode, lo, hi); }
-		for (auto& t : th) t.join();
-	}
+	else pool.ranges(n, n_threads, encode);
 	*out = r;
 	return TD_OK;
 }
@@ -301,19 +293,14 @@ extern "C" int td_writer_write(td_writer* w, const td_reads* rd, const td_read_r
 	if (w->files.empty()) return TD_OK;
 	// records are formatted by several threads over contiguous read ranges and appended range by range, so every file
 	// keeps the input order, like the reference's single loop
-	int nt = (int)std::thread::hardware_concurrency();
-	if (const char* e = getenv("TD_HOST_THREADS")) nt = atoi(e);
-	if (nt > 16) nt = 16;
-	if (nt < 1 || rd->n_reads < 65536) nt = 1;
+	const int nt = rd->n_reads < 65536 ? 1 : td_context_threads();
 	std::vector<std::vector<std::string>> parts((size_t)nt, std::vector<std::string>(w->files.size()));
 	const int64_t per = (rd->n_reads + nt - 1) / nt;
-	std::vector<std::thread> th;
-	for (int t = 1; t < nt; t++) {
+	TdWorkers pool(nt);
+	pool.run(nt, [&](int64_t t) {
 		const int64_t lo = t * per, hi = lo + per < rd->n_reads ? lo + per : rd->n_reads;
-		if (lo < hi) th.emplace_back(format_range, w, rd, res, seq_out, lo, hi, &parts[(size_t)t]);
-	}
-	format_range(w, rd, res, seq_out, 0, per < rd->n_reads ? per : rd->n_reads, &parts[0]);
-	for (auto& t : th) t.join();
+		if (lo < hi) format_range(w, rd, res, seq_out, lo, hi, &parts[(size_t)t]);
+	});
 	for (int t = 0; t < nt; t++)
 		for (size_t f = 0; f < w->files.size(); f++) {
 			const std::string& b = parts[(size_t)t][f];

@@ -6,93 +6,13 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <condition_variable>
-#include <deque>
 #include <functional>
-#include <mutex>
-#include <thread>
-#include <vector>
 
-// The copy threads of one context: started once, reused by every batch (the calling thread takes a share of each copy itself).
-struct CopyPool {
-	struct Job { char* dst; const char* src; size_t bytes; const std::function<void(int64_t, int64_t)>* fn; int64_t lo, hi; };
-	std::vector<std::thread> th;
-	std::mutex mu;
-	std::condition_variable cv_job, cv_done;
-	std::deque<Job> q;
-	int pending = 0;
-	bool stop = false;
-
-	void start(int n_workers)
-	{
-		for (int k = (int)th.size(); k < n_workers; k++)
-			th.emplace_back([this] {
-				for (;;) {
-					Job j;
-					{
-						std::unique_lock<std::mutex> lk(mu);
-						cv_job.wait(lk, [this] { return stop || !q.empty(); });
-						if (q.empty()) return;   // stop
-						j = q.front(); q.pop_front();
-					}
-					if (j.fn) (*j.fn)(j.lo, j.hi); else memcpy(j.dst, j.src, j.bytes);
-					{
-						std::lock_guard<std::mutex> lk(mu);
-						if (--pending == 0) cv_done.notify_all();
-					}
-				}
-			});
-	}
-	// memcpy(dst, src, bytes) on nt threads (this one included)
-	void copy(void* dst, const void* src, size_t bytes, int nt)
-	{
-		const size_t chunk = (size_t)1 << 20;
-		const size_t nchunks = (bytes + chunk - 1) / chunk;
-		if ((size_t)nt > nchunks) nt = (int)nchunks;
-		if (nchunks <= 4 || nt <= 1) { memcpy(dst, src, bytes); return; }
-		start(nt - 1);
-		const size_t per = (nchunks + (size_t)nt - 1) / (size_t)nt * chunk;
-		{
-			std::lock_guard<std::mutex> lk(mu);
-			for (size_t lo = per; lo < bytes; lo += per) {
-				q.push_back(Job{ (char*)dst + lo, (const char*)src + lo, lo + per < bytes ? per : bytes - lo, nullptr, 0, 0 });
-				pending++;
-			}
-		}
-		cv_job.notify_all();
-		memcpy(dst, src, per < bytes ? per : bytes);
-		std::unique_lock<std::mutex> lk(mu);
-		cv_done.wait(lk, [this] { return pending == 0; });
-	}
-	// fn(lo, hi) over [0, n) in contiguous ranges on nt threads (this one included)
-	void ranges(int64_t n, int nt, const std::function<void(int64_t, int64_t)>& fn)
-	{
-		if (n <= 0) return;
-		if (nt > n / 4096) nt = (int)(n / 4096);
-		if (nt <= 1) { fn(0, n); return; }
-		start(nt - 1);
-		const int64_t per = (n + nt - 1) / nt;
-		{
-			std::lock_guard<std::mutex> lk(mu);
-			for (int64_t lo = per; lo < n; lo += per) { q.push_back(Job{ nullptr, nullptr, 0, &fn, lo, lo + per < n ? lo + per : n }); pending++; }
-		}
-		cv_job.notify_all();
-		fn(0, per < n ? per : n);
-		std::unique_lock<std::mutex> lk(mu);
-		cv_done.wait(lk, [this] { return pending == 0; });
-	}
-	~CopyPool()
-	{
-		{ std::lock_guard<std::mutex> lk(mu); stop = true; }
-		cv_job.notify_all();
-		for (auto& t : th) t.join();
-	}
-};
-
+#include "td_workers.h"
 
 // make_extracted_read(), barcode_hmm.c:3343-3350, from the keep bits and the batch's bases on the host (base codes as the device
 // sees them: init_nuc_code for sequence text, anything above 4 is 4): out[offs[i] + p] = kept ? code : 65.
-static inline void td_host_rebuild_sequences(CopyPool& pool, int host_threads, int64_t n, const uint8_t* raw, const int64_t* offs,
+static inline void td_host_rebuild_sequences(TdWorkers& pool, int host_threads, int64_t n, const uint8_t* raw, const int64_t* offs,
                                              const uint32_t* kb, int nw1, int ascii, uint8_t* out)
 {
 	static const struct Lut { uint8_t t[256]; Lut() { for (int k = 0; k < 256; k++) t[k] = 4; t['A'] = t['a'] = 0; t['C'] = t['c'] = 1; t['G'] = t['g'] = 2; t['T'] = t['t'] = t['U'] = t['u'] = 3; } } lut;
@@ -129,7 +49,7 @@ static inline void td_host_rebuild_sequences(CopyPool& pool, int host_threads, i
 }
 
 // ri->labels (barcode_hmm.c:4503-4514) from (length << 8 | label) runs: read i's len + 1 labels at out + offs[i] + i
-static inline void td_host_expand_labels(CopyPool& pool, int host_threads, int64_t n, const int64_t* offs, const uint32_t* rl, int cap, int8_t* out)
+static inline void td_host_expand_labels(TdWorkers& pool, int host_threads, int64_t n, const int64_t* offs, const uint32_t* rl, int cap, int8_t* out)
 {
 	const std::function<void(int64_t, int64_t)> fn = [=](int64_t lo, int64_t hi) {
 		for (int64_t i = lo; i < hi; i++) {

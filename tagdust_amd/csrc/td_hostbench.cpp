@@ -54,7 +54,7 @@ extern "C" int td_host_halves_bench(int64_t n_reads, int32_t read_len, int32_t n
 		r[0] = (7u << 8) | 2u; r[1] = (3u << 8) | 9u; r[2] = ((uint32_t)(L - 15) << 8) | 11u; r[3] = (6u << 8) | 12u; r[4] = 0; r[5] = 0;
 	}
 	memset(res_pinned, 1, sizeof(td_read_result) * (size_t)n);
-	CopyPool pool;
+	TdWorkers pool;
 	auto one = [&]() {
 		// td_submit's half: the offsets pass (longest / shortest read, relative offsets into page-locked memory), the staging copy
 		int lmax = 1;

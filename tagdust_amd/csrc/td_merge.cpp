@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <thread>
 #include <vector>
 
@@ -31,33 +32,6 @@ extern "C" void td_merge_opts_default(td_merge_opts* o)
 	o->batch_pairs = 0;
 	o->device = 0;
 	o->table_placement = TD_MERGE_TABLE_AUTO;
-}
-
-int td_merge_pick_threads(int n_threads)
-{
-	if (n_threads > 0) return n_threads > 64 ? 64 : n_threads;
-	int hw = (int)std::thread::hardware_concurrency();
-	if (hw < 1) hw = 1;
-	return hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1);
-}
-
-void td_merge_parallel(int64_t n, int n_threads, int64_t chunk, void (*task)(int64_t, int64_t, void*), void* arg)
-{
-	if (n <= 0) return;
-	const int64_t nchunk = (n + chunk - 1) / chunk;
-	if (n_threads > nchunk) n_threads = (int)nchunk;
-	std::atomic<int64_t> next(0);
-	auto work = [&] {
-		for (;;) {
-			const int64_t k = next.fetch_add(1);
-			if (k >= nchunk) return;
-			task(k * chunk, std::min(n, (k + 1) * chunk), arg);
-		}
-	};
-	std::vector<std::thread> th;
-	for (int t = 1; t < n_threads; t++) th.emplace_back(work);
-	work();
-	for (auto& t : th) t.join();
 }
 
 // ---- the tables ----
@@ -172,7 +146,18 @@ void td_merge_pair_host(const TdMergeView& v, int64_t p, const td_merge_tables& 
 
 // ---- one batch ----
 namespace {
-struct HostArg { const TdMergeView* v; const td_merge_tables* t; const td_merge_opts* o; td_merge_result* res; bool only_long; };
+// task(k) for k in [0, n): on the pool of the stream that owns one for its run, or (pool NULL: the one-batch entry) on n_threads
+// threads made and joined here, the calling one included -- a pool made for one call's two sections measured 12 % behind this
+void run_chunks(TdWorkers* pool, int n_threads, int64_t n, const std::function<void(int64_t)>& task)
+{
+	if (pool) { pool->run(n, task); return; }
+	std::atomic<int64_t> next(0);
+	auto work = [&] { for (int64_t k; (k = next.fetch_add(1)) < n;) task(k); };
+	std::vector<std::thread> th;
+	for (int t = 1; t < n_threads && t < n; t++) th.emplace_back(work);
+	work();
+	for (auto& t : th) t.join();
+}
 
 void scan_bytes(const uint8_t* codes, const uint8_t* qual, int64_t lo, int64_t hi, bool* present, bool& bad)
 {
@@ -180,13 +165,13 @@ void scan_bytes(const uint8_t* codes, const uint8_t* qual, int64_t lo, int64_t h
 }
 }
 
-bool td_merge_batch(const TdMergeView& v, const td_merge_opts& o, TdMergeDevice* dev, td_merge_result* res, double* tables_s, std::string& err)
+bool td_merge_batch(const TdMergeView& v, const td_merge_opts& o, TdMergeDevice* dev, TdWorkers* pool, td_merge_result* res, double* tables_s, std::string& err)
 {
 	memset(res, 0, sizeof *res);
 	if (o.min_overlap < 0) { err = "td_merge: min_overlap must not be negative"; return false; }
 	const int64_t n = v.n;
 	const int64_t nb1 = n ? v.offs1[n] : 0, nb2 = n ? v.offs2[n] : 0;
-	const int T = td_merge_pick_threads(o.n_threads);
+	const int T = td_stage_threads(o.n_threads, 64);
 	for (int64_t p = 0; p < n; p++)
 		if (v.offs1[p + 1] - v.offs1[p] > (1 << 24) || v.offs2[p + 1] - v.offs2[p] > (1 << 24)) { err = "td_merge: a read of more than 2^24 bases"; return false; }
 	// the quality characters of the batch, and the one base code the reference cannot reverse-complement
@@ -195,8 +180,9 @@ bool td_merge_batch(const TdMergeView& v, const td_merge_opts& o, TdMergeDevice*
 	{
 		struct A { const TdMergeView* v; int64_t nb1; std::atomic<int> bad; std::atomic<uint64_t> bits[4]; } a{ &v, nb1, { 0 }, {} };
 		for (auto& b : a.bits) b = 0;
-		td_merge_parallel(nb1 + nb2, T, (int64_t)1 << 20, [](int64_t lo, int64_t hi, void* arg) {
-			A& a = *(A*)arg;
+		const int64_t nb = nb1 + nb2, chunk = (int64_t)1 << 20;
+		run_chunks(pool, T, (nb + chunk - 1) / chunk, [&](int64_t k) {
+			const int64_t lo = k * chunk, hi = std::min(nb, (k + 1) * chunk);
 			bool pr[256] = { false }, bad = false;
 			if (lo < a.nb1) scan_bytes(a.v->codes1, a.v->qual1, lo, std::min(hi, a.nb1), pr, bad);
 			if (hi > a.nb1) scan_bytes(a.v->codes2, a.v->qual2, std::max(lo, a.nb1) - a.nb1, hi - a.nb1, pr, bad);
@@ -206,7 +192,7 @@ bool td_merge_batch(const TdMergeView& v, const td_merge_opts& o, TdMergeDevice*
 				for (int b = 0; b < 64; b++) if (pr[w * 64 + b]) m |= (uint64_t)1 << b;
 				if (m) a.bits[w].fetch_or(m);
 			}
-		}, &a);
+		});
 		if (a.bad) { err = "td_merge: a read holds '.' (base code 5), which the reference's reverse complement does not define"; return false; }
 		for (int c = 0; c < 256; c++) present[c] = (a.bits[c / 64].load() >> (c % 64)) & 1;
 	}
@@ -224,15 +210,13 @@ bool td_merge_batch(const TdMergeView& v, const td_merge_opts& o, TdMergeDevice*
 	bool ok = true;
 	if (dev) ok = td_merge_device_run(dev, v, *t, o.min_overlap, o.threshold, o.table_placement, res->rec, res->seq, res->qual, &res->table_in_lds, &res->kernel_ms, err);
 	if (ok) {
-		HostArg h{ &v, t, &o, res, dev != nullptr };
-		td_merge_parallel(n, T, 256, [](int64_t lo, int64_t hi, void* arg) {
-			HostArg& h = *(HostArg*)arg;
-			for (int64_t p = lo; p < hi; p++) {
-				const bool is_long = h.v->offs1[p + 1] - h.v->offs1[p] > TD_MERGE_STAGE_BASES || h.v->offs2[p + 1] - h.v->offs2[p] > TD_MERGE_STAGE_BASES;
-				if (h.only_long && !is_long) continue;
-				td_merge_pair_host(*h.v, p, *h.t, h.o->min_overlap, h.o->threshold, &h.res->rec[p], h.res->seq + h.res->out_off[p], h.res->qual + h.res->out_off[p]);
+		run_chunks(pool, T, (n + 255) / 256, [&](int64_t k) {
+			for (int64_t p = k * 256; p < std::min(n, (k + 1) * 256); p++) {
+				const bool is_long = v.offs1[p + 1] - v.offs1[p] > TD_MERGE_STAGE_BASES || v.offs2[p + 1] - v.offs2[p] > TD_MERGE_STAGE_BASES;
+				if (dev && !is_long) continue;
+				td_merge_pair_host(v, p, *t, o.min_overlap, o.threshold, &res->rec[p], res->seq + res->out_off[p], res->qual + res->out_off[p]);
 			}
-		}, &h);
+		});
 		for (int64_t p = 0; p < n; p++) {
 			const int s = res->rec[p].status;
 			if (s == TD_MERGE_WRITTEN) res->n_written++; else if (s == TD_MERGE_BELOW) res->n_below++; else res->n_too_short++;
@@ -281,7 +265,7 @@ int merge_reads(const td_reads* r1, const td_reads* r2, const td_merge_opts* opt
 		if (!dev) { td_merge_set_error(err); return TD_FAIL; }
 	}
 	td_merge_result* res = (td_merge_result*)calloc(1, sizeof(td_merge_result));
-	const bool ok = res && td_merge_batch(v, o, dev, res, nullptr, err);
+	const bool ok = res && td_merge_batch(v, o, dev, nullptr, res, nullptr, err);
 	if (dev) td_merge_device_close(dev);
 	if (!ok) { td_merge_result_free(res); td_merge_set_error(res ? err : "td_merge: out of memory"); return TD_FAIL; }
 	*out = res;
@@ -308,7 +292,7 @@ extern "C" int td_merge_stream(const char* in1, const char* in2, const char* out
 	td_merge_opts mo;
 	if (opts) mo = *opts; else td_merge_opts_default(&mo);
 	if (mo.min_overlap < 0) { td_merge_set_error("td_merge_stream: min_overlap must not be negative"); return TD_FAIL; }
-	mo.n_threads = td_merge_pick_threads(mo.n_threads);
+	mo.n_threads = td_stage_threads(mo.n_threads, 64);
 	std::string err;
 	TdMergeDevice* dev = nullptr;
 	if (mo.device >= 0) {
@@ -318,7 +302,7 @@ extern "C" int td_merge_stream(const char* in1, const char* in2, const char* out
 	td_merge_stats st{};
 	double tables_s = 0.0;
 	const int rc = td_merge_stream_run(in1, in2, out_path, mo.n_threads, mo.batch_pairs, dev != nullptr,
-		[&](const TdMergeView& v, td_merge_result* res, std::string& e) { return td_merge_batch(v, mo, dev, res, &tables_s, e); }, &st, err);
+		[&](const TdMergeView& v, TdWorkers& pool, td_merge_result* res, std::string& e) { return td_merge_batch(v, mo, dev, &pool, res, &tables_s, e); }, &st, err);
 	td_merge_device_close(dev);
 	st.tables_s = tables_s;
 	if (stats) *stats = st;

@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/tagdust_merge.h"
+#include "td_workers.h"
 
 #if defined(__HIPCC__)
 #define TD_MERGE_HD __host__ __device__
@@ -72,14 +73,11 @@ void td_merge_device_close(TdMergeDevice* d);
 bool td_merge_device_run(TdMergeDevice* d, const TdMergeView& v, const td_merge_tables& t, int min_overlap, float threshold,
                          int placement, td_merge_record* rec, char* seq, char* qual, int* table_in_lds, float* kernel_ms, std::string& err);
 
-// One batch, the whole of it: the checks ('.' codes), the tables, every pair on `dev` (NULL: on n_threads host threads; pairs the
-// kernel does not take on the host), out_off and the counts.  res: rec / out_off / seq / qual are allocated here (malloc).
+// One batch, the whole of it: the checks ('.' codes), the tables, every pair on `dev` (NULL: on host threads; pairs the kernel does
+// not take on the host), the host's share on `pool` (NULL: on o.n_threads threads made for this batch), out_off and the counts.  res: rec / out_off / seq / qual are allocated here (malloc).
 // tables_s / kernel_ms may be NULL.
-bool td_merge_batch(const TdMergeView& v, const td_merge_opts& o, TdMergeDevice* dev, td_merge_result* res, double* tables_s, std::string& err);
-// run task(lo, hi) over [0, n) in chunks on n_threads threads (the calling one included)
-void td_merge_parallel(int64_t n, int n_threads, int64_t chunk, void (*task)(int64_t lo, int64_t hi, void* arg), void* arg);
-int td_merge_pick_threads(int n_threads);
-// the pipeline under td_merge_stream (td_merge_stream.inc, in td_stream.cpp): readers, checks, writer; merge_batch fills a result
-// (td_merge_batch) for the view it is given
+bool td_merge_batch(const TdMergeView& v, const td_merge_opts& o, TdMergeDevice* dev, TdWorkers* pool, td_merge_result* res, double* tables_s, std::string& err);
+// the pipeline under td_merge_stream (td_merge_stream.inc, in td_stream.cpp): readers, checks, writer; merge_batch fills a result (td_merge_batch)
+// for the view it is given, on the pool of n_threads that the run owns
 int td_merge_stream_run(const char* in1, const char* in2, const char* out_path, int n_threads, int batch_pairs, bool pinned,
-                        const std::function<bool(const TdMergeView&, td_merge_result*, std::string&)>& merge_batch, td_merge_stats* stats, std::string& error);
+                        const std::function<bool(const TdMergeView&, TdWorkers&, td_merge_result*, std::string&)>& merge_batch, td_merge_stats* stats, std::string& error);

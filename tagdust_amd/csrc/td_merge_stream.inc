@@ -1,5 +1,5 @@
 // td_merge_stream.inc -- the pipeline under td_merge_stream (include/tagdust_merge.h); included at the end of td_stream.cpp, whose
-// Source / Reader / Pool / Queue / RunError / names_differ it uses: the controller of the reference's `merge` (src/merge.c:59-216) as a pipeline.
+// Source / Reader / TdWorkers / Queue / RunError / names_differ it uses: the controller of the reference's `merge` (src/merge.c:59-216) as a pipeline.
 //
 //   reader / parser thread per file      caller's thread                          writer thread
 //   the next batch of each file          equal counts, first 1000 names, quality   "@name\nseq\n+\nqual\n" per written pair,
@@ -16,7 +16,7 @@ struct MergeDone {
 };
 
 // the quality bytes of a batch, contiguous under its offsets; false: a record without qualities (FASTA)
-bool merge_pack_qual(const Batch& b, Pool& pool, std::vector<uint8_t>& q)
+bool merge_pack_qual(const Batch& b, TdWorkers& pool, std::vector<uint8_t>& q)
 {
 	q.resize((size_t)b.n_bases + 1);
 	std::vector<char> bad(b.pieces.size(), 0);
@@ -50,7 +50,7 @@ bool write_all(int fd, const char* p, size_t n)
 // on the device or on the host).  pinned: the readers' batch buffers are page-locked.  This file knows nothing of the merger but
 // its plain structs, so td_stream.cpp still links without it.
 int td_merge_stream_run(const char* in1, const char* in2, const char* out_path, int n_threads, int batch_pairs, bool pinned,
-                        const std::function<bool(const TdMergeView&, td_merge_result*, std::string&)>& merge_batch, td_merge_stats* stats, std::string& error)
+                        const std::function<bool(const TdMergeView&, TdWorkers&, td_merge_result*, std::string&)>& merge_batch, td_merge_stats* stats, std::string& error)
 {
 	td_stream_opts want{};
 	want.batch_reads = batch_pairs > 0 ? batch_pairs : (1 << 18);
@@ -75,7 +75,7 @@ int td_merge_stream_run(const char* in1, const char* in2, const char* out_path, 
 	err.watch(&done);
 	for (auto& r : readers)
 		if (!r->start(n_batches)) { err.fail("td_merge_stream: page-locked memory exhausted"); break; }
-	Pool write_pool(o.n_threads), pack_pool(o.n_threads);
+	TdWorkers write_pool(o.n_threads), pack_pool(o.n_threads), merge_pool(n_threads);      // (merge_pool: td_merge_batch's, on the calling thread)
 	std::thread t_write([&] {
 		std::unique_ptr<MergeDone> d;
 		while (done.pop(d)) {
@@ -151,7 +151,7 @@ int td_merge_stream_run(const char* in1, const char* in2, const char* out_path, 
 		std::unique_ptr<MergeDone> d(new MergeDone());
 		d->b1 = b1; d->b2 = b2;
 		std::string e;
-		if (!merge_batch(v, &d->res, e)) { err.fail("td_merge_stream: " + e); break; }
+		if (!merge_batch(v, merge_pool, &d->res, e)) { err.fail("td_merge_stream: " + e); break; }
 		st.kernel_s += (double)d->res.kernel_ms * 1e-3;
 		st.merge_s += now_s() - t0;
 		if (!done.push(std::move(d))) break;

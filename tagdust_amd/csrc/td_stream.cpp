@@ -46,6 +46,7 @@
 #include "../../include/tagdust_molecules.h"   // td_mol_mate_next: pair mode of td_stream_run_multi
 #include "td_io_internal.h"
 #include "td_merge_internal.h"
+#include "td_workers.h"
 
 namespace {
 
@@ -53,73 +54,6 @@ double now_s()
 {
 	return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-
-// ---- a few persistent threads that run task(k) for k in [0, n) ----
-class Pool {
-public:
-	explicit Pool(int n_threads)
-	{
-		for (int t = 1; t < n_threads; t++) th_.emplace_back([this] { worker(); });
-	}
-	~Pool()
-	{
-		{ std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
-		cv_.notify_all();
-		for (auto& t : th_) t.join();
-	}
-	int size() const { return (int)th_.size() + 1; }
-	void run(int64_t n, const std::function<void(int64_t)>& task)
-	{
-		if (n <= 0) return;
-		if (th_.empty() || n == 1) { for (int64_t k = 0; k < n; k++) task(k); return; }
-		{
-			std::lock_guard<std::mutex> lk(mu_);
-			task_ = &task; next_ = 0; n_ = n; left_ = n; gen_++;
-		}
-		cv_.notify_all();
-		drain();                               // the calling thread takes tasks too
-		std::unique_lock<std::mutex> lk(mu_);
-		done_.wait(lk, [this] { return left_ == 0; });
-		task_ = nullptr;
-	}
-
-private:
-	void drain()
-	{
-		for (;;) {
-			int64_t k;
-			const std::function<void(int64_t)>* t;
-			{
-				std::lock_guard<std::mutex> lk(mu_);
-				if (!task_ || next_ >= n_) return;
-				k = next_++; t = task_;
-			}
-			(*t)(k);
-			std::lock_guard<std::mutex> lk(mu_);
-			if (--left_ == 0) done_.notify_all();
-		}
-	}
-	void worker()
-	{
-		uint64_t seen = 0;
-		for (;;) {
-			{
-				std::unique_lock<std::mutex> lk(mu_);
-				cv_.wait(lk, [&] { return stop_ || (gen_ != seen && task_); });
-				if (stop_) return;
-				seen = gen_;
-			}
-			drain();
-		}
-	}
-	std::vector<std::thread> th_;
-	std::mutex mu_;
-	std::condition_variable cv_, done_;
-	const std::function<void(int64_t)>* task_ = nullptr;
-	int64_t next_ = 0, n_ = 0, left_ = 0;
-	uint64_t gen_ = 0;
-	bool stop_ = false;
-};
 
 // ---- bounded FIFO between the stages ----
 template <typename T>
@@ -593,7 +527,7 @@ struct Reader {
 	const bool want_seq;       // page-locked room for rewritten sequences (not for a file that goes through TD_MODE_RNA_DUST)
 	const int parse_threads;
 	Source src;
-	std::unique_ptr<Pool> parse_pool;
+	std::unique_ptr<TdWorkers> parse_pool;
 	std::unique_ptr<Queue<Batch*>> ready, free_list;
 	std::vector<Batch*> all;
 	int64_t bytes_in = 0;
@@ -613,7 +547,7 @@ struct Reader {
 	// two batches, the two threads; false: not even those two batches could be had (nothing was started)
 	bool start(int n_batches)
 	{
-		parse_pool.reset(new Pool(parse_threads));
+		parse_pool.reset(new TdWorkers(parse_threads));
 		ready.reset(new Queue<Batch*>((size_t)n_batches));
 		free_list.reset(new Queue<Batch*>((size_t)n_batches));
 		err.watch(ready.get());
@@ -840,7 +774,7 @@ struct Reader {
 // ---- the output side of stage 3: the output files, a pool that formats a batch's records, an appender thread that writes them ----
 struct Writer {
 	RunError& err;
-	Pool pool;
+	TdWorkers pool;
 	const int num_alternatives;
 	bool fingerprint_text = false;      // td_stream_opts.fingerprint_text: ";FP:ACGT" instead of ";FP:27"
 	std::vector<int> fds;
@@ -852,7 +786,7 @@ struct Writer {
 	// appends have been written (append_wait).
 	struct Wr { size_t file, k0, k1; int64_t at; };
 	struct AppendJob { int set; std::vector<Wr> wr; };
-	std::unique_ptr<Pool> append_pool;
+	std::unique_ptr<TdWorkers> append_pool;
 	std::thread appender;
 	std::mutex ap_mu;
 	std::condition_variable ap_cv;
@@ -944,7 +878,7 @@ struct Writer {
 	{
 		if (!ap_started) {
 			ap_started = true;
-			append_pool.reset(new Pool(pool.size()));
+			append_pool.reset(new TdWorkers(pool.size()));
 			appender = std::thread([this] { append_loop(); });
 		}
 		const int set = ap_set;
@@ -1019,10 +953,7 @@ td_stream_opts resolve_opts(const td_stream_opts* opts, bool reference_batches)
 	if (o.batch_reads <= 0) o.batch_reads = reference_batches ? 1000001 : (1 << 18);
 	if (o.block_bytes <= 0) o.block_bytes = (int64_t)64 << 20;
 	if (o.block_bytes < 4096) o.block_bytes = 4096;
-	int hw = (int)std::thread::hardware_concurrency();
-	if (hw < 1) hw = 1;
-	if (o.n_threads <= 0) o.n_threads = hw >= 16 ? 8 : (hw >= 4 ? hw / 2 : 1);
-	if (o.n_threads > 32) o.n_threads = 32;
+	o.n_threads = td_stage_threads(o.n_threads, 32);
 	return o;
 }
 

@@ -12,10 +12,11 @@ from conftest import REPO
 
 CSRC = os.path.join(REPO, "tagdust_amd", "csrc")
 # the program, and what it links beside the two host units of the counts (td_fingerprint_text is td_fastq.cpp's); the batch plan's
-# links its own unit alone
+# links its own unit alone, the worker pool's (td_workers.h) nothing at all
 COUNT_UNITS = ("td_census_host.cpp", "td_molecules_host.cpp")
+WITHOUT_COUNT_UNITS = ("batch_plan_host_check", "workers_host_check")
 PROGRAMS = [("census_host_check", []), ("molecules_host_check", ["td_fastq.cpp"]), ("dedup_host_check", []), ("collapse_host_check", []),
-            ("dedup_collapsed_host_check", []), ("mate_host_check", []), ("batch_plan_host_check", ["td_batch_plan.cpp"])]
+            ("dedup_collapsed_host_check", []), ("mate_host_check", []), ("batch_plan_host_check", ["td_batch_plan.cpp"]), ("workers_host_check", [])]
 
 
 def host_compiler():
@@ -58,7 +59,7 @@ def test_the_host_units_build_and_agree_without_hip(tmp_path, host_objects, name
     d = str(tmp_path)
     objs = [compiled(cxx, as_cxx, s, d) for s in [os.path.join(CSRC, e) for e in extra] + [os.path.join(REPO, "tools", name + ".cpp")]]
     exe = os.path.join(d, name)
-    run(cxx + ([] if name == "batch_plan_host_check" else host_objects) + objs + ["-o", exe, "-lpthread"])
+    run(cxx + ([] if name in WITHOUT_COUNT_UNITS else host_objects) + objs + ["-o", exe, "-lpthread"])
     assert (name + ": ok") in run([exe]).splitlines()
 
 

@@ -29,7 +29,7 @@ bool td_merge_device_run(TdMergeDevice*, const TdMergeView&, const td_merge_tabl
 }
 
 // nor are the streaming pipeline's readers (td_stream.cpp)
-int td_merge_stream_run(const char*, const char*, const char*, int, int, bool, const std::function<bool(const TdMergeView&, td_merge_result*, std::string&)>&,
+int td_merge_stream_run(const char*, const char*, const char*, int, int, bool, const std::function<bool(const TdMergeView&, TdWorkers&, td_merge_result*, std::string&)>&,
                         td_merge_stats*, std::string& err)
 {
 	err = "no stream in this program";

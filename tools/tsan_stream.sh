@@ -3,13 +3,16 @@
 # ThreadSanitizer on the CPU: td_stream.cpp + td_fastq.cpp as they are, the device entry points replaced by stand-ins
 # (tools/tsan_stream/stub.cpp), a 60 000-read ragged FASTQ file in batches of 777 reads and blocks of 20 KB -- parse-only and
 # with the stubbed decode + real formatting / appends, each twice (the second run reuses the cached batch buffers), and the
-# multi-file pipeline (td_stream_run_multi: two input files in lock-step, two "devices", one file not decoded).
+# multi-file pipeline (td_stream_run_multi: two input files in lock-step, two "devices", one file not decoded).  Before them the
+# pool those stages work on, alone (tools/workers_host_check.cpp over csrc/td_workers.h): "workers_host_check: ok".
 # usage: tools/tsan_stream.sh      (prints the result lines, the last two of runs into a full disk; any ThreadSanitizer report goes to stderr)
 set -e
 cd "$(dirname "$0")/.."
 OUT=/tmp/td_tsan
 mkdir -p $OUT
 g++ -std=c++17 -O1 -g -fsanitize=thread -pthread -Iinclude -w -o $OUT/tsan_stream tools/tsan_stream/stub.cpp tagdust_amd/csrc/td_stream.cpp tagdust_amd/csrc/td_fastq.cpp
+g++ -std=c++17 -O1 -g -fsanitize=thread -pthread -o $OUT/workers_host_check tools/workers_host_check.cpp
+$OUT/workers_host_check
 python3 - <<'PY'
 import numpy as np
 rng = np.random.RandomState(1)
