@@ -87,7 +87,7 @@ extern "C" const char* td_last_error(const td_ctx* ctx)
 	return ctx ? ctx->err.c_str() : g_create_error.c_str();
 }
 
-extern "C" void td_stream_release(void);   // td_stream.cpp: the page-locked batch buffers td_stream_run keeps between runs
+extern "C" void td_stream_release(void);   // td_stream_reader.cpp: the page-locked batch buffers td_stream_run keeps between runs
 static std::mutex g_live_mu;
 static int g_live_ctx = 0;
 

@@ -1,4 +1,4 @@
-// td_io_internal.h -- shared between td_fastq.cpp (whole-text parser / writer) and td_stream.cpp (streaming pipeline)
+// td_io_internal.h -- shared between td_fastq.cpp (whole-text parser / writer) and the streaming pipeline (td_stream*.cpp, td_stream_internal.h)
 #pragma once
 #include <stdint.h>
 
@@ -51,7 +51,7 @@ inline void td_encode_bases(const unsigned char* s, uint8_t* dst, const int64_t 
 // print_all()'s file set for one input file (src/io.c:859-915): names in file-index order; *num_alternatives as io.c:923-934 uses it
 void td_writer_file_names(const char* prefix, const td_arch* a, std::vector<std::string>& names, int* num_alternatives);
 void td_writer_file_names_n(const char* prefix, const td_arch* a, int n_out_reads, std::vector<std::string>& names, int* num_alternatives);
-// the first min(limit, records of the file) records of an input file of any kind td_stream_run reads (td_stream.cpp): base codes and offsets
+// the first min(limit, records of the file) records of an input file of any kind td_stream_run reads (td_stream_reader.cpp): base codes and offsets
 int td_stream_head(const char* path, int64_t limit, int32_t n_threads, std::vector<uint8_t>& codes, std::vector<int64_t>& offs, std::string& why);
 // "td_..." message of the last failure on this thread (td_io_last_error)
 void td_io_set_error(const std::string& msg);

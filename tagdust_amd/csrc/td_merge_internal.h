@@ -1,5 +1,5 @@
 // td_merge_internal.h -- shared between td_merge.cpp (tables, host path, command line), td_merge.hip (the kernel and its host side)
-// and td_merge_stream.inc (td_merge_stream, inside td_stream.cpp)
+// and td_merge_stream.cpp (td_merge_stream's pipeline, on the readers of td_stream_internal.h)
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -77,7 +77,7 @@ bool td_merge_device_run(TdMergeDevice* d, const TdMergeView& v, const td_merge_
 // not take on the host), the host's share on `pool` (NULL: on o.n_threads threads made for this batch), out_off and the counts.  res: rec / out_off / seq / qual are allocated here (malloc).
 // tables_s / kernel_ms may be NULL.
 bool td_merge_batch(const TdMergeView& v, const td_merge_opts& o, TdMergeDevice* dev, TdWorkers* pool, td_merge_result* res, double* tables_s, std::string& err);
-// the pipeline under td_merge_stream (td_merge_stream.inc, in td_stream.cpp): readers, checks, writer; merge_batch fills a result (td_merge_batch)
+// the pipeline under td_merge_stream (td_merge_stream.cpp): readers, checks, writer; merge_batch fills a result (td_merge_batch)
 // for the view it is given, on the pool of n_threads that the run owns
 int td_merge_stream_run(const char* in1, const char* in2, const char* out_path, int n_threads, int batch_pairs, bool pinned,
                         const std::function<bool(const TdMergeView&, TdWorkers&, td_merge_result*, std::string&)>& merge_batch, td_merge_stats* stats, std::string& error);

@@ -1,10 +1,22 @@
-// td_merge_stream.inc -- the pipeline under td_merge_stream (include/tagdust_merge.h); included at the end of td_stream.cpp, whose
-// Source / Reader / TdWorkers / Queue / RunError / names_differ it uses: the controller of the reference's `merge` (src/merge.c:59-216) as a pipeline.
+// td_merge_stream.cpp -- the pipeline under td_merge_stream (include/tagdust_merge.h) on the decode pipeline's input side
+// (td_stream_internal.h: Source / Reader / Queue / RunError, the lock-step check, the readers' epilogue): the controller of the
+// reference's `merge` (src/merge.c:59-216) as a pipeline.
 //
 //   reader / parser thread per file      caller's thread                          writer thread
 //   the next batch of each file          equal counts, first 1000 names, quality   "@name\nseq\n+\nqual\n" per written pair,
 //                                        bytes packed, td_merge_batch (device or   formatted by a pool, appended in order
 //                                        host)
+#include <errno.h>
+#include <fcntl.h>
+#include <string.h>
+#include <unistd.h>
+
+#include <algorithm>
+
+#include "td_merge_internal.h"
+#include "td_stream_internal.h"
+
+using namespace tdstream;
 
 namespace {
 
@@ -47,8 +59,8 @@ bool write_all(int fd, const char* p, size_t n)
 } // namespace
 
 // The pipeline of td_merge_stream (td_merge.cpp): `merge_batch` is what the calling thread does with a batch of pairs (td_merge_batch
-// on the device or on the host).  pinned: the readers' batch buffers are page-locked.  This file knows nothing of the merger but
-// its plain structs, so td_stream.cpp still links without it.
+// on the device or on the host).  pinned: the readers' batch buffers are page-locked.  This unit knows nothing of the merger but
+// its plain structs, so it links without td_merge.cpp, and the decode pipeline's units link without this one.
 int td_merge_stream_run(const char* in1, const char* in2, const char* out_path, int n_threads, int batch_pairs, bool pinned,
                         const std::function<bool(const TdMergeView&, TdWorkers&, td_merge_result*, std::string&)>& merge_batch, td_merge_stats* stats, std::string& error)
 {
@@ -130,18 +142,9 @@ int td_merge_stream_run(const char* in1, const char* in2, const char* out_path, 
 		Batch* b1 = nullptr; Batch* b2 = nullptr;
 		const bool got1 = readers[0]->ready->pop(b1), got2 = readers[1]->ready->pop(b2);
 		if (err.failed() || (!got1 && !got2)) break;
-		if (!got1 || !got2 || b1->n != b2->n) {                  // merge.c:164-174, the reference's own words behind ours
-			err.fail(std::string("td_merge_stream: the input files differ in their number of records: Input File:") + in1 + " and " + in2 + " differ in number of entries.");
-			break;
-		}
-		if (first) {                                              // merge.c:178-193
-			first = false;
-			for (int64_t i = 0; i < std::min<int64_t>(1000, b1->n) && !err.failed(); i++) {
-				const std::string na = record_name(*b1, i), nb = record_name(*b2, i);
-				if (names_differ(na, nb, name_format)) err.fail("td_merge_stream: the input files seem to contain reads in different order: " + na + " / " + nb);
-			}
-			if (err.failed()) break;
-		}
+		Batch* const pair[2] = { b1, b2 };                       // (NULL: that reader has ended)
+		const std::string objection = lockstep_objection("td_merge_stream: ", pair, paths, 2, first, name_format);   // merge.c:164-193
+		if (!objection.empty()) { err.fail(objection); break; }
 		const double t0 = now_s();
 		if (!merge_pack_qual(*b1, pack_pool, q1) || !merge_pack_qual(*b2, pack_pool, q2)) { err.fail("td_merge_stream: FASTA input: the reads have no base qualities"); break; }
 		TdMergeView v;
@@ -159,12 +162,7 @@ int td_merge_stream_run(const char* in1, const char* in2, const char* out_path, 
 	done.close();
 	t_write.join();
 	if (!to_stdout && close(fd) != 0) err.fail(std::string("td_merge_stream: close failed: ") + strerror(errno));
-	for (auto& r : readers) { r->ready->abort(); r->free_list->abort(); }    // (a producer still at work after a failure leaves its wait)
-	for (auto& r : readers) r->stop();
-	for (auto& r : readers) {
-		st.bytes_in += r->bytes_in; st.parse_s += r->parse_s; st.read_s += r->read_s;
-		r->release(!err.failed());
-	}
+	finish_readers(readers, !err.failed(), st.bytes_in, st.parse_s, st.read_s);
 	st.wall_s = now_s() - t_start;
 	if (stats) *stats = st;
 	if (err.failed()) { error = err.message(); return TD_FAIL; }

@@ -12,941 +12,29 @@
 // two host steps on several threads.  Batches hold exactly `batch_reads` records like the reference's (the -ref artifact
 // filter's per-thread read ranges are taken over a batch, barcode_hmm.c:2478-2583, so the boundaries are part of the result).
 //
-// The pieces: a Reader per input file (Source, parse pool, the batches it owns, its allocator and producer threads), one
-// run_stages() for both entry points (the device stage over tuples of one batch per file, the write-stage thread, the
-// teardown), one Writer (output files, format pool, appender thread) and one RunError that all of them share: the first
-// failure anywhere is the run's message and ends every stage.  An entry point validates its arguments, sets these up and
-// gives run_stages what is its own: the check of a tuple and what the write stage does with a finished one.
-#include <errno.h>
-#include <fcntl.h>
+// The pieces: a Reader per input file (td_stream_reader.cpp: Source, parse pool, the batches it owns, its allocator and producer
+// threads), one run_stages() for both entry points, here (the device stage over tuples of one batch per file, the write-stage
+// thread, the teardown), one Writer (td_stream_writer.cpp: output files, format pool, appender thread) and one RunError that all
+// of them share (td_stream_internal.h, with the queues between the stages): the first failure anywhere is the run's message and
+// ends every stage.  An entry point validates its arguments, sets these up and gives run_stages what is its own: the check of a
+// tuple and what the write stage does with a finished one.  td_merge_stream.cpp is the `merge` controller on the same readers.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
-#include <math.h>
-#if defined(__SSE2__)
-#include <emmintrin.h>
-#endif
+#include <algorithm>
 
-#include <chrono>
-#include <cmath>
-#include <condition_variable>
-#include <deque>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-
-#include "../../include/tagdust_io.h"
 #include "../../include/tagdust_molecules.h"   // td_mol_mate_next: pair mode of td_stream_run_multi
-#include "td_io_internal.h"
-#include "td_merge_internal.h"
-#include "td_workers.h"
+#include "td_stream_internal.h"
 
-namespace {
-
-double now_s()
-{
-	return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// ---- bounded FIFO between the stages ----
-template <typename T>
-class Queue {
-public:
-	explicit Queue(size_t cap) : cap_(cap) {}
-	bool push(T v)          // false: the pipeline was aborted
-	{
-		std::unique_lock<std::mutex> lk(mu_);
-		cv_.wait(lk, [&] { return abort_ || q_.size() < cap_; });
-		if (abort_) return false;
-		q_.push_back(std::move(v));
-		cv_.notify_all();
-		return true;
-	}
-	bool pop(T& v)          // false: closed and empty, or aborted
-	{
-		std::unique_lock<std::mutex> lk(mu_);
-		cv_.wait(lk, [&] { return abort_ || closed_ || !q_.empty(); });
-		if (abort_ || q_.empty()) return false;
-		v = std::move(q_.front());
-		q_.pop_front();
-		cv_.notify_all();
-		return true;
-	}
-	int try_pop(T& v)       // 1: got one; 0: nothing there right now; -1: closed and empty, or aborted
-	{
-		std::lock_guard<std::mutex> lk(mu_);
-		if (abort_) return -1;
-		if (q_.empty()) return closed_ ? -1 : 0;
-		v = std::move(q_.front());
-		q_.pop_front();
-		cv_.notify_all();
-		return 1;
-	}
-	void close() { std::lock_guard<std::mutex> lk(mu_); closed_ = true; cv_.notify_all(); }
-	void abort() { std::lock_guard<std::mutex> lk(mu_); abort_ = true; cv_.notify_all(); }
-
-private:
-	std::mutex mu_;
-	std::condition_variable cv_;
-	std::deque<T> q_;
-	size_t cap_;
-	bool closed_ = false, abort_ = false;
-};
-
-// ---- input text: one mapping of a plain file, or blocks read from a pipe ----
-struct Block {
-	const char* data = nullptr;
-	int64_t len = 0;
-	char* owned = nullptr;          // malloc'ed (pipe input); a mapped file is owned by the Source
-	~Block() { free(owned); }
-};
-
-class Source {
-public:
-	~Source()
-	{
-		if (map_ && map_ != MAP_FAILED) munmap(map_, (size_t)map_len_);
-		if (pipe_) pclose(pipe_);
-		if (fd_ >= 0) close(fd_);
-	}
-	bool open(const char* path, int64_t block_bytes, std::string& err)
-	{
-		block_ = block_bytes;
-		const std::string p = path;
-		auto ends = [&](const char* sfx) { const size_t n = strlen(sfx); return p.size() >= n && p.compare(p.size() - n, n, sfx) == 0; };
-		struct stat st;
-		if (p != "-" && stat(path, &st) != 0) { err = "td_stream_run: cannot find input file " + p; return false; }
-		std::string q;
-		for (char ch : p) { if (ch == '\'') q += "'\\''"; else q += ch; }
-		const bool sam = ends(".sam") || ends(".sam.gz"), bam = ends(".bam") || ends(".bam.gz");
-		if (sam || bam) {
-			// io_handler(), io.c:467-575: alignments come as text from `samtools view` (-S for SAM text), secondary and
-			// QC-failed records dropped (-F 768); a .gz of either goes through zcat first.  read_sam_chunk (io.c:1498-1660) takes
-			// QNAME, SEQ and QUAL of every line that does not start with '@'.
-			const std::string view = std::string("samtools view ") + (sam ? "-SF 768 " : "-F 768 ");
-			cmd_ = ends(".gz") ? "zcat -- '" + q + "' | " + view + "-" : view + "'" + q + "'";
-			if (p == "-") { err = "td_stream_run: SAM/BAM input from stdin is not supported"; return false; }
-			pipe_ = popen(cmd_.c_str(), "r");
-			if (!pipe_) { err = "td_stream_run: cannot start " + cmd_; return false; }
-			fd_in_ = fileno(pipe_);
-			sam_ = true;
-			return true;
-		}
-		if (ends(".gz") || ends(".bz2")) {             // io_handler(), io.c:382-608: zcat / bzcat through popen
-			cmd_ = std::string(ends(".gz") ? "zcat" : "bzcat") + " -- '" + q + "'";
-			pipe_ = popen(cmd_.c_str(), "r");
-			if (!pipe_) { err = "td_stream_run: cannot start " + cmd_; return false; }
-			fd_in_ = fileno(pipe_);
-			return true;
-		}
-		if (p == "-") { fd_in_ = 0; return true; }
-		fd_ = ::open(path, O_RDONLY);
-		if (fd_ < 0) { err = "td_stream_run: cannot open " + p + ": " + strerror(errno); return false; }
-		if (S_ISREG(st.st_mode)) {
-			map_len_ = st.st_size;
-			if (map_len_ == 0) { eof_ = true; return true; }
-			map_ = mmap(nullptr, (size_t)map_len_, PROT_READ, MAP_PRIVATE, fd_, 0);
-			if (map_ != MAP_FAILED) {
-				(void)madvise(map_, (size_t)map_len_, MADV_SEQUENTIAL);
-				fasta_ = ((const char*)map_)[0] == '>';
-				return true;
-			}
-			map_ = nullptr;                            // fall back to read()
-		}
-		fd_in_ = fd_;
-		return true;
-	}
-	// the next block of whole records (nullptr at the end); *read_s += time spent waiting for bytes
-	std::shared_ptr<Block> next(double* read_s, std::string& err)
-	{
-		if (eof_) return nullptr;
-		auto b = std::make_shared<Block>();
-		if (map_) {
-			const char* text = (const char*)map_;
-			int64_t end = map_pos_ + block_;
-			end = end >= map_len_ ? map_len_ : td_next_record_start(text, map_len_, end, fasta_);
-			b->data = text + map_pos_; b->len = end - map_pos_;
-			(void)madvise((void*)((uintptr_t)(text + map_pos_) & ~(uintptr_t)4095), (size_t)(b->len + 4096), MADV_WILLNEED);
-			map_pos_ = end;
-			if (map_pos_ >= map_len_) eof_ = true;
-			return b;
-		}
-		// pipe / stdin: fill a buffer, cut it at the last record start found in its tail, carry the rest over
-		const double t0 = now_s();
-		const int64_t cap = block_ + (int64_t)carry_.size() + 1;
-		b->owned = (char*)malloc((size_t)cap);
-		if (!b->owned) { err = "td_stream_run: out of memory"; return nullptr; }
-		int64_t have = (int64_t)carry_.size();
-		if (have) memcpy(b->owned, carry_.data(), (size_t)have);
-		carry_.clear();
-		bool end_of_input = false;
-		while (have < cap - 1) {
-			const ssize_t r = read(fd_in_, b->owned + have, (size_t)(cap - 1 - have));
-			if (r < 0) { if (errno == EINTR) continue; err = std::string("td_stream_run: read failed: ") + strerror(errno); return nullptr; }
-			if (r == 0) { end_of_input = true; break; }
-			have += r;
-		}
-		if (end_of_input && pipe_) {
-			// the decompressor's verdict: a truncated or corrupt .gz / .bz2 ends the stream early with a non-zero status -- an error,
-			// not the end of the input (io_handler's pclose, io.c:382-608, ignores it; a partial set of output files helps nobody)
-			const int status = pclose(pipe_);
-			pipe_ = nullptr;
-			if (status != 0) {
-				err = "td_stream_run: `" + cmd_ + "` failed (status " + std::to_string(status) + "): truncated or corrupt input" + (sam_ ? ", or no samtools on PATH" : "");
-				return nullptr;
-			}
-		}
-		*read_s += now_s() - t0;
-		if (sam_) {
-			std::shared_ptr<Block> r = sam_block(b, have, end_of_input, err);
-			if (r && r->len == 0) return eof_ ? nullptr : next(read_s, err);   // header lines only
-			return r;
-		}
-		if (first_block_) { fasta_ = have > 0 && b->owned[0] == '>'; first_block_ = false; }
-		int64_t cut = have;
-		if (!end_of_input) {
-			// the last record start in the buffer: search forward from ever earlier points of the tail
-			cut = -1;
-			for (int64_t back = 1 << 16; cut < 0; back *= 4) {
-				int64_t from = have - back;
-				if (from < 1) from = 1;
-				int64_t p = td_next_record_start(b->owned, have, from, fasta_), last = -1;
-				while (p < have) { last = p; p = td_next_record_start(b->owned, have, p + 1, fasta_); }
-				if (last > 0) cut = last;
-				else if (from == 1) { err = "td_stream_run: no record boundary within a block of input (raise block_bytes)"; return nullptr; }
-			}
-			carry_.assign(b->owned + cut, b->owned + have);
-		} else {
-			eof_ = true;
-		}
-		b->data = b->owned; b->len = cut;
-		if (cut == 0 && eof_) return nullptr;
-		return b;
-	}
-
-private:
-	// Alignment text -> the four-line records the parser takes: '@' QNAME, SEQ, '+', QUAL (fields 1, 10 and 11 of every line that
-	// is not a header line, read_sam_chunk, io.c:1498-1660).  Whole lines only; the rest is carried over to the next block.
-	std::shared_ptr<Block> sam_block(std::shared_ptr<Block> b, int64_t have, const bool end_of_input, std::string& err)
-	{
-		int64_t cut = have;
-		if (!end_of_input) {
-			while (cut > 0 && b->owned[cut - 1] != '\n') --cut;
-			if (cut == 0) { err = "td_stream_run: no line end within a block of SAM input (raise block_bytes)"; return nullptr; }
-			carry_.assign(b->owned + cut, b->owned + have);
-		} else {
-			eof_ = true;
-		}
-		auto out = std::make_shared<Block>();
-		out->owned = (char*)malloc((size_t)cut + 8);      // a record shrinks: 11+ tab-separated fields against 3 of them and 5 bytes
-		if (!out->owned) { err = "td_stream_run: out of memory"; return nullptr; }
-		char* o = out->owned;
-		const char* t = b->owned;
-		const char* const end = t + cut;
-		auto blank = [](const char ch) { return ch == ' ' || ch == '\t' || ch == '\r' || ch == '\v' || ch == '\f'; };
-		while (t < end) {
-			const char* nl = (const char*)memchr(t, '\n', (size_t)(end - t));
-			const char* le = nl ? nl : end;
-			if (le > t && t[0] != '@') {
-				const char* f[12];
-				int nf = 0;
-				const char* c = t;
-				f[nf++] = c;
-				while (c < le && nf < 12) { if (blank(*c)) f[nf++] = c + 1; ++c; }
-				if (nf < 11) { err = "td_stream_run: SAM line with fewer than 11 fields: " + std::string(t, (size_t)std::min<int64_t>(le - t, 60)); return nullptr; }
-				auto field_end = [&](const char* s) { while (s < le && !blank(*s)) ++s; return s; };
-				const char* n1 = field_end(f[0]);
-				const char* s1 = field_end(f[9]);
-				const char* q1 = field_end(f[10]);
-				if (q1 - f[10] != s1 - f[9]) { err = "td_stream_run: SAM record without one quality per base: " + std::string(f[0], (size_t)(n1 - f[0])); return nullptr; }
-				*o++ = '@'; memcpy(o, f[0], (size_t)(n1 - f[0])); o += n1 - f[0]; *o++ = '\n';
-				memcpy(o, f[9], (size_t)(s1 - f[9])); o += s1 - f[9]; *o++ = '\n';
-				*o++ = '+'; *o++ = '\n';
-				memcpy(o, f[10], (size_t)(q1 - f[10])); o += q1 - f[10]; *o++ = '\n';
-			}
-			t = nl ? nl + 1 : end;
-		}
-		out->data = out->owned; out->len = o - out->owned;
-		return out;
-	}
-
-	int fd_ = -1, fd_in_ = -1;
-	std::string cmd_;
-	bool sam_ = false;
-	FILE* pipe_ = nullptr;
-	void* map_ = nullptr;
-	int64_t map_len_ = 0, map_pos_ = 0, block_ = 0;
-	bool eof_ = false, fasta_ = false, first_block_ = true;
-	std::vector<char> carry_;
-};
-
-// ---- a decode batch: exactly batch_reads records (fewer at the end), device-ready buffers in page-locked memory ----
-struct Piece {                      // records [lo, hi) of one parsed chunk of a block
-	std::shared_ptr<Block> blk;
-	std::shared_ptr<std::vector<TdRec>> recs;
-	int64_t lo = 0, hi = 0;
-	int64_t first = 0;              // index of record lo within the batch
-};
-
-struct Batch {
-	int64_t n = 0, n_bases = 0;
-	uint8_t* codes = nullptr;  size_t cap_codes = 0;
-	uint8_t* seq_out = nullptr; size_t cap_seq = 0;
-	int64_t* offs = nullptr;
-	td_read_result* res = nullptr;
-	std::vector<Piece> pieces;
-	int64_t cap_reads = 0;     // offs / res hold this many reads
-	const uint8_t* seq_src = nullptr;   // what the writer prints: seq_out, or codes for a file that is not decoded (run_rna_dust)
-};
-
-// Page-locked batch buffers outlive a run: page-locking runs at about 1 GB/s, which is most of what a short file costs.  The
-// buffers of the last run (up to 1 GiB) wait here for the next one of the same process; td_stream_release frees them.
-std::mutex g_cache_mu;
-std::vector<Batch*> g_cache;
-const size_t kCacheBytes = (size_t)1 << 30;
-
-size_t batch_bytes(const Batch* b)
-{
-	return b->cap_codes + b->cap_seq + (size_t)b->cap_reads * (sizeof(int64_t) + sizeof(td_read_result));
-}
-
-// batch buffers: page-locked for the device; plain memory for a parse-only run (no GPU runtime needed then)
-void* buf_alloc(bool dry, size_t bytes) { return dry ? malloc(bytes ? bytes : 1) : td_host_alloc(bytes); }
-void buf_free(bool dry, void* p) { if (dry) free(p); else td_host_free(p); }
-
-bool grow_buf(bool dry, uint8_t** p, size_t* cap, size_t need, size_t keep, size_t hint)
-{
-	if (*cap >= need) return true;
-	size_t want = need + need / 4 + 4096;
-	if (want < hint) want = hint;          // what a whole batch is expected to need: allocated once, reused by later batches
-	uint8_t* q = (uint8_t*)buf_alloc(dry, want);
-	if (!q) return false;
-	if (*p && keep) memcpy(q, *p, keep);
-	if (*p) buf_free(dry, *p);
-	*p = q; *cap = want;
-	return true;
-}
-
-// a growing byte buffer without the zero-fill of std::string::resize
-struct Bytes {
-	char* p = nullptr;
-	size_t n = 0, cap = 0;
-	Bytes() = default;
-	Bytes(const Bytes&) = delete;
-	Bytes& operator=(const Bytes&) = delete;
-	Bytes(Bytes&& o) noexcept : p(o.p), n(o.n), cap(o.cap) { o.p = nullptr; o.n = o.cap = 0; }
-	~Bytes() { free(p); }
-	char* room(size_t more)
-	{
-		if (n + more > cap) {
-			size_t c = cap ? cap * 2 : (size_t)1 << 16;
-			while (c < n + more) c *= 2;
-			p = (char*)realloc(p, c);
-			cap = c;
-		}
-		return p + n;
-	}
-};
-
-// "%d"
-inline int put_int(char* w, int v)
-{
-	char tmp[16];
-	int k = 0;
-	unsigned u = v < 0 ? 0u - (unsigned)v : (unsigned)v;
-	do { tmp[k++] = (char)('0' + u % 10); u /= 10; } while (u);
-	int o = 0;
-	if (v < 0) w[o++] = '-';
-	while (k) w[o++] = tmp[--k];
-	return o;
-}
-
-// "%0.2f" of a float, digit for digit what printf prints: the float times 100 is exact in double (24 x 7 significant bits),
-// nearbyint rounds it half-to-even like printf rounds the exact decimal expansion; anything unusual goes to snprintf
-inline int put_q(char* w, float q)
-{
-	const double x = (double)q * 100.0;
-	if (!(x >= 0.0 && x < 1.0e15) || (x == 0.0 && std::signbit(q))) return snprintf(w, 48, "%0.2f", (double)q);   // (at most 42 characters)
-	unsigned long long u = (unsigned long long)nearbyint(x);
-	char tmp[24];
-	int k = 0;
-	tmp[k++] = (char)('0' + u % 10); u /= 10;
-	tmp[k++] = (char)('0' + u % 10); u /= 10;
-	tmp[k++] = '.';
-	do { tmp[k++] = (char)('0' + u % 10); u /= 10; } while (u);
-	int o = 0;
-	while (k) w[o++] = tmp[--k];
-	return o;
-}
-
-// formats the records of one piece sub-range into one buffer per output file (print_all(), io.c:917-1001)
-struct OutBufs { std::vector<Bytes> file; };
-
-// The rewritten sequence of a read is base codes 0..4 with removed positions as 65: the stretches of kept bases become the
-// records.  Sixteen bytes at a time where the host has SSE2 (every x86-64 has): the write stage is the slower host stage of the
-// pipeline, and these two loops were half of its formatting time.
-#if defined(__SSE2__)
-// number of leading bytes of s[0, n) that are >= 5 (GE = true) / < 5 (GE = false)
-template <bool GE>
-inline int64_t span_of(const uint8_t* s, int64_t n)
-{
-	int64_t g = 0;
-	const __m128i five = _mm_set1_epi8(5);
-	for (; g + 16 <= n; g += 16) {
-		const __m128i v = _mm_loadu_si128((const __m128i*)(s + g));
-		const unsigned ge = (unsigned)_mm_movemask_epi8(_mm_cmpeq_epi8(_mm_max_epu8(v, five), v));   // bit k: s[g + k] >= 5
-		const unsigned stop = GE ? (~ge & 0xFFFFu) : ge;   // first byte that ends the span
-		if (stop) return g + __builtin_ctz(stop);
-	}
-	while (g < n && ((s[g] >= 5) == GE)) g++;
-	return g;
-}
-// w[k] = "ACGTN"[s[k]] for codes 0..4
-inline void codes_to_text(char* w, const uint8_t* s, size_t n)
-{
-	size_t k = 0;
-	const __m128i a = _mm_set1_epi8('A'), c1 = _mm_set1_epi8(1), c2 = _mm_set1_epi8(2), c3 = _mm_set1_epi8(3), c4 = _mm_set1_epi8(4);
-	const __m128i d1 = _mm_set1_epi8('C' - 'A'), d2 = _mm_set1_epi8('G' - 'A'), d3 = _mm_set1_epi8('T' - 'A'), d4 = _mm_set1_epi8('N' - 'A');
-	for (; k + 16 <= n; k += 16) {
-		const __m128i v = _mm_loadu_si128((const __m128i*)(s + k));
-		__m128i o = a;
-		o = _mm_add_epi8(o, _mm_and_si128(_mm_cmpeq_epi8(v, c1), d1));
-		o = _mm_add_epi8(o, _mm_and_si128(_mm_cmpeq_epi8(v, c2), d2));
-		o = _mm_add_epi8(o, _mm_and_si128(_mm_cmpeq_epi8(v, c3), d3));
-		o = _mm_add_epi8(o, _mm_and_si128(_mm_cmpeq_epi8(v, c4), d4));
-		_mm_storeu_si128((__m128i*)(w + k), o);
-	}
-	static const char alphabet[] = "ACGTNN";
-	for (; k < n; k++) w[k] = alphabet[s[k]];
-}
-#else
-template <bool GE>
-inline int64_t span_of(const uint8_t* s, int64_t n) { int64_t g = 0; while (g < n && ((s[g] >= 5) == GE)) g++; return g; }
-inline void codes_to_text(char* w, const uint8_t* s, size_t n) { static const char alphabet[] = "ACGTNN"; for (size_t k = 0; k < n; k++) w[k] = alphabet[s[k]]; }
-#endif
-
-// ctype / cbar: read_type and barcode of the record as the controller combines them over the input files of a run
-// (barcode_hmm.c:329-351; NULL: this file's own); file_base: index of this input file's first output file (io.c:917-1001: c)
-void format_records(const Batch& b, const Piece& pc, int64_t lo, int64_t hi, int num_alternatives, OutBufs& out,
-                    const int32_t* ctype = nullptr, const int32_t* cbar = nullptr, size_t file_base = 0, bool fingerprint_text = false)
-{
-	const char* text = pc.blk->data;
-	const std::vector<TdRec>& recs = *pc.recs;
-	char head[352];                                        // (";FP:" + up to 255 bases + ";RQ:" + the quality)
-	const size_t n_files = out.file.size();
-	for (int64_t r = lo; r < hi; r++) {
-		const TdRec& rec = recs[(size_t)r];
-		const int64_t i = pc.first + (r - pc.lo);             // index in the batch
-		const td_read_result& rr = b.res[i];
-		size_t f;                                              // io.c:923-934
-		const int32_t rtype = ctype ? ctype[i] : rr.read_type, rbar = cbar ? cbar[i] : rr.barcode;
-		if ((rtype & 0xFF) == TD_EXTRACT_DUPLICATE) continue;  // dedup: not the first read of its molecule, and no failure either
-		if (rtype == TD_EXTRACT_SUCCESS) f = (rbar != -1) ? (size_t)(rbar & 0xFF) : 0;
-		else f = (size_t)num_alternatives - 1;
-		f += file_base;
-		const uint8_t* s = (b.seq_src ? b.seq_src : b.seq_out) + b.offs[i];
-		const int64_t len = b.offs[i + 1] - b.offs[i];
-		const char* q = rec.qual_off >= 0 ? text + rec.qual_off : nullptr;
-		int head_len = -1;
-		int64_t g = 0;
-		while (g < len) {
-			g += span_of<true>(s + g, len - g);                // removed positions (65) split the read into records
-			const int64_t g0 = g;
-			g += span_of<false>(s + g, len - g);
-			if (g == g0) break;
-			if (f < n_files) {                                 // io.c:955-975: "@<name>[;FP:%d];RQ:%0.2f"
-				if (head_len < 0) {
-					int k = 0;
-					if (rr.fingerprint != -1) {
-						memcpy(head, ";FP:", 4);
-						if (fingerprint_text) { (void)td_fingerprint_text(rr.fingerprint, head + 4); k = 4 + (rr.fingerprint & 0xFF); }   // io.c:960-963
-						else k = 4 + put_int(head + 4, rr.fingerprint);
-					}
-					memcpy(head + k, ";RQ:", 4); k += 4;
-					k += put_q(head + k, rr.mapq);
-					head[k++] = '\n';
-					head_len = k;
-				}
-				const size_t run = (size_t)(g - g0);
-				Bytes& o = out.file[f];
-				const size_t total = 1 + (size_t)rec.name_len + (size_t)head_len + run + 3 + run + 1;
-				char* w = o.room(total);
-				*w++ = '@';
-				memcpy(w, text + rec.name_off, (size_t)rec.name_len); w += rec.name_len;
-				memcpy(w, head, (size_t)head_len); w += head_len;
-				codes_to_text(w, s + g0, run);
-				w += run;
-				*w++ = '\n'; *w++ = '+'; *w++ = '\n';
-				if (q) memcpy(w, q + g0, run); else memset(w, '.', run);
-				w += run;
-				*w++ = '\n';
-				o.n += total;
-			}
-			f += (size_t)num_alternatives;
-		}
-	}
-}
-
-// ---- the error of a run: the first message stays, and failing ends the run by aborting every queue between its stages ----
-class RunError {
-public:
-	template <typename Q>
-	void watch(Q* q)        // q->abort() when the run fails (at once when it already has); q outlives the run's threads
-	{
-		std::lock_guard<std::mutex> lk(mu_);
-		if (!msg_.empty()) q->abort();
-		aborts_.push_back([q] { q->abort(); });
-	}
-	void fail(const std::string& m)
-	{
-		std::lock_guard<std::mutex> lk(mu_);
-		if (msg_.empty()) msg_ = m;
-		for (auto& a : aborts_) a();
-	}
-	bool failed() { std::lock_guard<std::mutex> lk(mu_); return !msg_.empty(); }
-	std::string message() { std::lock_guard<std::mutex> lk(mu_); return msg_; }
-
-private:
-	std::mutex mu_;
-	std::string msg_;
-	std::vector<std::function<void()>> aborts_;
-};
-
-// ---- stage 1 of one input file: its source, the batches it owns, an allocator thread and a producer thread with a parse pool ----
-struct Reader {
-	RunError& err;
-	const td_stream_opts o;
-	const bool dry;            // batch buffers in plain memory: a file that no device sees
-	const bool want_seq;       // page-locked room for rewritten sequences (not for a file that goes through TD_MODE_RNA_DUST)
-	const int parse_threads;
-	Source src;
-	std::unique_ptr<TdWorkers> parse_pool;
-	std::unique_ptr<Queue<Batch*>> ready, free_list;
-	std::vector<Batch*> all;
-	int64_t bytes_in = 0;
-	double read_s = 0, parse_s = 0;
-	double dbg_pass1 = 0, dbg_grow = 0, dbg_encode = 0;
-	size_t batch_hint = 0;
-	std::mutex all_mu;
-	std::condition_variable hint_cv;
-	bool hint_ready = false, stop_alloc = false;
-	std::thread t_alloc, t_prod;
-
-	Reader(RunError& e, const td_stream_opts& opts, bool dry_, bool want_seq_, int parse_threads_)
-		: err(e), o(opts), dry(dry_), want_seq(want_seq_), parse_threads(parse_threads_) {}
-	~Reader() { stop(); release(false); }
-
-	// the queues (n_batches: `depth` on the device, one being filled, one being written, one spare on either side), the first
-	// two batches, the two threads; false: not even those two batches could be had (nothing was started)
-	bool start(int n_batches)
-	{
-		parse_pool.reset(new TdWorkers(parse_threads));
-		ready.reset(new Queue<Batch*>((size_t)n_batches));
-		free_list.reset(new Queue<Batch*>((size_t)n_batches));
-		err.watch(ready.get());
-		err.watch(free_list.get());
-		for (int k = 0; k < 2; k++) {
-			Batch* b = new_batch();
-			if (!b) return false;
-			free_list->push(b);
-		}
-		t_alloc = std::thread([this, n_batches] { allocator(n_batches - 2); });
-		t_prod = std::thread([this] { producer(); });
-		return true;
-	}
-
-	// ends the two threads: once the input has been read to its end or the run has failed (the producer leaves a wait on an
-	// aborted queue), also when start() failed or was never called
-	void stop()
-	{
-		if (t_prod.joinable()) t_prod.join();
-		{ std::lock_guard<std::mutex> lk(all_mu); stop_alloc = true; }
-		hint_cv.notify_all();
-		if (free_list) free_list->abort();          // (an allocator waiting to hand over a batch)
-		if (t_alloc.joinable()) t_alloc.join();
-	}
-
-	// the batches of a finished run: kept for the next one (page-locked, within the cache's size) or freed
-	void release(bool keep)
-	{
-		std::lock_guard<std::mutex> lk(g_cache_mu);
-		size_t held = 0;
-		for (const Batch* q : g_cache) held += batch_bytes(q);
-		for (Batch* q : all) {
-			if (!dry && keep && q->codes && held + batch_bytes(q) <= kCacheBytes) {
-				q->pieces.clear(); q->n = 0; q->n_bases = 0; q->seq_src = nullptr;
-				held += batch_bytes(q);
-				g_cache.push_back(q);
-				continue;
-			}
-			buf_free(dry, q->codes); buf_free(dry, q->seq_out); buf_free(dry, q->offs); buf_free(dry, q->res);
-			delete q;
-		}
-		all.clear();
-	}
-
-	Batch* new_batch()
-	{
-		if (!dry) {   // one the last run left behind?
-			std::lock_guard<std::mutex> lk(g_cache_mu);
-			for (size_t k = 0; k < g_cache.size(); k++)
-				if (g_cache[k]->cap_reads >= o.batch_reads) {
-					Batch* b = g_cache[k];
-					g_cache.erase(g_cache.begin() + (long)k);
-					b->offs[0] = 0;
-					std::lock_guard<std::mutex> lk2(all_mu);
-					all.push_back(b);
-					return b;
-				}
-		}
-		Batch* b = new Batch();
-		b->cap_reads = o.batch_reads;
-		b->offs = (int64_t*)buf_alloc(dry, sizeof(int64_t) * ((size_t)o.batch_reads + 1));
-		b->res = (td_read_result*)buf_alloc(dry, sizeof(td_read_result) * (size_t)o.batch_reads);
-		if (!b->offs || !b->res) { buf_free(dry, b->offs); buf_free(dry, b->res); delete b; return nullptr; }
-		b->offs[0] = 0;
-		{ std::lock_guard<std::mutex> lk(all_mu); all.push_back(b); }
-		return b;
-	}
-
-	// The batch buffers are page-locked, and page-locking runs at about 1 GB/s: the pipeline starts with two batches and this
-	// thread adds the others, sized for a whole batch (known after the first block), while the first ones are already at work.
-	void allocator(int n_more)
-	{
-		size_t hint = 0;
-		{
-			std::unique_lock<std::mutex> lk(all_mu);
-			hint_cv.wait(lk, [&] { return hint_ready || stop_alloc; });
-			if (stop_alloc) return;
-			hint = batch_hint;
-		}
-		for (int k = 0; k < n_more; k++) {
-			{ std::lock_guard<std::mutex> lk(all_mu); if (stop_alloc) return; }
-			Batch* b = new_batch();
-			if (!b || !grow_buf(dry, &b->codes, &b->cap_codes, hint, 0, hint) || (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, hint, 0, hint))) return;   // (the pipeline runs with what it has)
-			if (!free_list->push(b)) return;
-		}
-	}
-
-	// read / map a block, find its records, hand them out to batches, base-code them
-	void producer()
-	{
-		Batch* cur = nullptr;
-		const int P = parse_pool->size();
-		for (;;) {
-			std::string e;
-			std::shared_ptr<Block> blk = src.next(&read_s, e);
-			if (!blk) { if (!e.empty()) { err.fail(e); return; } break; }
-			const double t0 = now_s();
-			bytes_in += blk->len;
-			// records: P chunks cut at record starts, each parsed by the reference's line state machine
-			const bool fasta = blk->len > 0 && blk->data[0] == '>';
-			std::vector<int64_t> cut(1, 0);
-			const int nchunk_want = blk->len < (1 << 20) ? 1 : P * 4;
-			for (int t = 1; t < nchunk_want; t++) {
-				const int64_t p = td_next_record_start(blk->data, blk->len, blk->len / nchunk_want * t, fasta);
-				if (p < blk->len && p > cut.back()) cut.push_back(p);
-			}
-			cut.push_back(blk->len);
-			const int nchunk = (int)cut.size() - 1;
-			std::vector<std::shared_ptr<std::vector<TdRec>>> recs((size_t)nchunk);
-			for (auto& r : recs) r = std::make_shared<std::vector<TdRec>>();
-			std::vector<int64_t> bad((size_t)nchunk, -1);
-			parse_pool->run(nchunk, [&](int64_t k) {
-				std::vector<TdRec>& v = *recs[(size_t)k];
-				v.reserve((size_t)((cut[(size_t)k + 1] - cut[(size_t)k]) / 200 + 16));
-				td_parse_range(blk->data, cut[(size_t)k], cut[(size_t)k + 1], v);
-				// "Length of sequence and base qualities differ" ends the reference's run (io.c:1776-1781)
-				for (size_t i = 0; i < v.size(); i++)
-					if (v[i].qual_off >= 0 && v[i].qual_len != (v[i].seq_off >= 0 ? v[i].seq_len : 0)) { bad[(size_t)k] = (int64_t)i; break; }
-			});
-			dbg_pass1 += now_s() - t0;
-			for (int k = 0; k < nchunk; k++)
-				if (bad[(size_t)k] >= 0) {
-					const TdRec& q = (*recs[(size_t)k])[(size_t)bad[(size_t)k]];
-					char msg[256];
-					snprintf(msg, sizeof msg, "td_stream_run: record \"%.*s\": sequence has %d characters, base qualities %d",
-					         q.name_len < 60 ? q.name_len : 60, blk->data + q.name_off, q.seq_off >= 0 ? q.seq_len : 0, q.qual_len);
-					err.fail(msg);
-					return;
-				}
-			{   // bases a full batch of reads like this block's will hold (+6 %)
-				int64_t nrec = 0, nb = 0;
-				for (auto& r : recs) { nrec += (int64_t)r->size(); for (const TdRec& q : *r) nb += q.seq_off >= 0 ? q.seq_len : 0; }
-				if (nrec > 0) {
-					const size_t h = (size_t)((double)nb / (double)nrec * (double)o.batch_reads * 1.06) + 4096;
-					std::lock_guard<std::mutex> lk(all_mu);
-					if (h > batch_hint) batch_hint = h;
-					hint_ready = true;
-					hint_cv.notify_all();
-				}
-			}
-			// hand the records out to batches of exactly batch_reads, in order (offsets by a running sum); the pieces handed out
-			// are base-coded (init_nuc_code) in parallel and full batches passed on whenever two are waiting, and before this
-			// thread might have to wait for a free batch
-			struct Job { Batch* b; size_t piece; };
-			std::vector<Job> jobs;
-			std::vector<Batch*> full;
-			double t_seg = t0;
-			auto flush = [&]() -> bool {
-				const double tf0 = now_s();
-				std::vector<Batch*> touched = full;
-				if (cur) touched.push_back(cur);
-				for (Batch* b : touched) {
-					// page-locked room for the codes going in and the rewritten sequences coming back (bases of earlier pieces of
-					// a batch are already encoded: keep them)
-					bool mine = false;
-					size_t keep = 0;
-					for (const Job& j : jobs) if (j.b == b) { keep = (size_t)b->offs[b->pieces[j.piece].first]; mine = true; break; }
-					if (!mine) continue;
-					if (!grow_buf(dry, &b->codes, &b->cap_codes, (size_t)b->n_bases + 1, keep, batch_hint) ||
-					    (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, (size_t)b->n_bases + 1, 0, batch_hint))) { err.fail("td_stream_run: page-locked memory exhausted"); return false; }
-				}
-				dbg_grow += now_s() - tf0;
-				const double tf1 = now_s();
-				struct Sub { Batch* b; size_t piece; int64_t lo, hi; };
-				std::vector<Sub> subs;
-				for (const Job& j : jobs) {
-					const Piece& pc = j.b->pieces[j.piece];
-					for (int64_t a = pc.lo; a < pc.hi; a += 16384) subs.push_back(Sub{ j.b, j.piece, a, std::min<int64_t>(a + 16384, pc.hi) });
-				}
-				parse_pool->run((int64_t)subs.size(), [&](int64_t k) {
-					const Sub& sb = subs[(size_t)k];
-					const Piece& pc = sb.b->pieces[sb.piece];
-					const std::vector<TdRec>& v = *pc.recs;
-					for (int64_t r = sb.lo; r < sb.hi; r++) {
-						const TdRec& q = v[(size_t)r];
-						if (q.seq_off < 0) continue;
-						uint8_t* dst = sb.b->codes + sb.b->offs[pc.first + (r - pc.lo)];
-						const unsigned char* sq = (const unsigned char*)pc.blk->data + q.seq_off;
-						td_encode_bases(sq, dst, q.seq_len);
-					}
-				});
-				jobs.clear();
-				dbg_encode += now_s() - tf1;
-				parse_s += now_s() - t_seg;                             // (time spent waiting for a free batch is not parsing)
-				for (Batch* b : full) if (!ready->push(b)) return false;
-				full.clear();
-				t_seg = now_s();
-				return true;
-			};
-			for (int k = 0; k < nchunk; k++) {
-				const std::vector<TdRec>& v = *recs[(size_t)k];
-				int64_t lo = 0;
-				while (lo < (int64_t)v.size()) {
-					if (!cur) {
-						if (!full.empty() && !flush()) return;
-						parse_s += now_s() - t_seg;
-						if (!free_list->pop(cur)) return;                  // aborted
-						t_seg = now_s();
-						cur->n = 0; cur->n_bases = 0; cur->pieces.clear();
-					}
-					const int64_t take = std::min<int64_t>((int64_t)v.size() - lo, (int64_t)o.batch_reads - cur->n);
-					Piece pc; pc.blk = blk; pc.recs = recs[(size_t)k]; pc.lo = lo; pc.hi = lo + take; pc.first = cur->n;
-					int64_t total = cur->n_bases;
-					for (int64_t r = lo; r < lo + take; r++) {
-						total += v[(size_t)r].seq_off >= 0 ? v[(size_t)r].seq_len : 0;
-						cur->offs[cur->n + (r - lo) + 1] = total;
-					}
-					cur->n += take; cur->n_bases = total;
-					cur->pieces.push_back(pc);
-					jobs.push_back(Job{ cur, cur->pieces.size() - 1 });
-					lo += take;
-					if (cur->n == o.batch_reads) { full.push_back(cur); cur = nullptr; }
-				}
-			}
-			if (!flush()) return;
-		}
-		if (getenv("TD_STREAM_DEBUG")) fprintf(stderr, "td_stream: records %.3f s, buffers %.3f s, base codes %.3f s (parse stage %.3f s)\n", dbg_pass1, dbg_grow, dbg_encode, parse_s);
-		if (cur && cur->n > 0) { if (!ready->push(cur)) return; }
-		else if (cur) free_list->push(cur);
-		ready->close();
-	}
-};
-
-// ---- the output side of stage 3: the output files, a pool that formats a batch's records, an appender thread that writes them ----
-struct Writer {
-	RunError& err;
-	TdWorkers pool;
-	const int num_alternatives;
-	bool fingerprint_text = false;      // td_stream_opts.fingerprint_text: ";FP:ACGT" instead of ";FP:27"
-	std::vector<int> fds;
-	std::vector<int64_t> file_off;
-	int64_t bytes_out = 0;
-	double dbg_format = 0, dbg_pwrite = 0;
-	// Appends run beside the formatting of the next batch: every append is a pwrite at an offset fixed when the batch was
-	// formatted, so the order in which they reach the files is free.  Two sets of formatted text; a set is reused once its
-	// appends have been written (append_wait).
-	struct Wr { size_t file, k0, k1; int64_t at; };
-	struct AppendJob { int set; std::vector<Wr> wr; };
-	std::unique_ptr<TdWorkers> append_pool;
-	std::thread appender;
-	std::mutex ap_mu;
-	std::condition_variable ap_cv;
-	std::deque<AppendJob> ap_jobs;
-	bool ap_busy[2] = { false, false }, ap_stop = false, ap_started = false;
-	int ap_errno = 0, ap_set = 0;
-	std::vector<OutBufs> ap_bufs[2];
-
-	Writer(RunError& e, int n_threads, int num_alternatives_) : err(e), pool(n_threads), num_alternatives(num_alternatives_) {}
-	~Writer() { (void)close(); }
-
-	// creates the output files; false: `why` says which one could not be created, and none of them stays open
-	bool open(const std::vector<std::string>& names, std::string& why)
-	{
-		for (auto& nm : names) {
-			const int fd = ::open(nm.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-			if (fd < 0) { why = nm + ": " + strerror(errno); (void)close(); return false; }
-			fds.push_back(fd);
-		}
-		file_off.assign(fds.size(), 0);
-		return true;
-	}
-	// waits for the appends of every batch written; false if one of them failed
-	bool finish() { return append_wait(-1); }
-	// stops the appender (after a failure appends may still be queued: none may outlive the descriptors) and closes the files;
-	// the errno of the first close that failed, 0 if none did
-	int close()
-	{
-		append_stop();
-		int first = 0;
-		for (int fd : fds) if (::close(fd) != 0 && !first) first = errno;
-		fds.clear();
-		return first;
-	}
-
-	void append_loop()
-	{
-		for (;;) {
-			AppendJob job;
-			{
-				std::unique_lock<std::mutex> lk(ap_mu);
-				ap_cv.wait(lk, [&] { return ap_stop || !ap_jobs.empty(); });
-				if (ap_jobs.empty()) return;
-				job = std::move(ap_jobs.front());
-				ap_jobs.pop_front();
-			}
-			const double t0 = now_s();
-			const std::vector<OutBufs>& bufs = ap_bufs[job.set];
-			std::vector<int> wrc(job.wr.size(), 0);
-			append_pool->run((int64_t)job.wr.size(), [&](int64_t t) {
-				const Wr& w = job.wr[(size_t)t];
-				int64_t at = w.at;
-				for (size_t k = w.k0; k < w.k1; k++) {
-					const Bytes& sb = bufs[k].file[w.file];
-					size_t off = 0;
-					while (off < sb.n) {
-						const ssize_t r = pwrite(fds[w.file], sb.p + off, sb.n - off, (off_t)(at + (int64_t)off));
-						if (r < 0) { if (errno == EINTR) continue; wrc[(size_t)t] = errno ? errno : EIO; return; }
-						off += (size_t)r;
-					}
-					at += (int64_t)sb.n;
-				}
-			});
-			std::lock_guard<std::mutex> lk(ap_mu);
-			dbg_pwrite += now_s() - t0;
-			for (int e : wrc) if (e && !ap_errno) ap_errno = e;
-			ap_busy[job.set] = false;
-			ap_cv.notify_all();
-		}
-	}
-	// waits until the appends of `set` (-1: of every set) are in the files; false if one of them failed
-	bool append_wait(int set)
-	{
-		std::unique_lock<std::mutex> lk(ap_mu);
-		ap_cv.wait(lk, [&] { return set < 0 ? (!ap_busy[0] && !ap_busy[1]) : !ap_busy[set]; });
-		if (ap_errno) { const int e = ap_errno; lk.unlock(); err.fail(std::string("td_stream_run: write failed: ") + strerror(e)); return false; }
-		return true;
-	}
-	void append_stop()
-	{
-		{ std::lock_guard<std::mutex> lk(ap_mu); ap_stop = true; }
-		ap_cv.notify_all();
-		if (appender.joinable()) appender.join();
-	}
-
-	// format the records of one batch per output file (on the pool) and hand the appends (in input order per file) to the
-	// appender thread; finish() before the files are closed
-	bool write_batch(Batch* b, const int32_t* ctype, const int32_t* cbar, size_t file_base)
-	{
-		if (!ap_started) {
-			ap_started = true;
-			append_pool.reset(new TdWorkers(pool.size()));
-			appender = std::thread([this] { append_loop(); });
-		}
-		const int set = ap_set;
-		ap_set ^= 1;
-		if (!append_wait(set)) return false;
-		std::vector<OutBufs>& bufs = ap_bufs[set];
-		const double t0 = now_s();
-		const int W = pool.size();
-		struct Sub { size_t piece; int64_t lo, hi; };
-		std::vector<Sub> subs;
-		const int64_t step = std::max<int64_t>(4096, (b->n + W * 4 - 1) / (W * 4));
-		for (size_t p = 0; p < b->pieces.size(); p++)
-			for (int64_t a = b->pieces[p].lo; a < b->pieces[p].hi; a += step)
-				subs.push_back(Sub{ p, a, std::min<int64_t>(a + step, b->pieces[p].hi) });
-		if (bufs.size() < subs.size()) bufs.resize(subs.size());
-		for (size_t k = 0; k < subs.size(); k++) {
-			if (bufs[k].file.size() != fds.size()) bufs[k].file.resize(fds.size());
-			for (auto& s : bufs[k].file) s.n = 0;
-		}
-		pool.run((int64_t)subs.size(), [&](int64_t k) {
-			const Sub& sb = subs[(size_t)k];
-			format_records(*b, b->pieces[sb.piece], sb.lo, sb.hi, num_alternatives, bufs[(size_t)k], ctype, cbar, file_base, fingerprint_text);
-		});
-		dbg_format += now_s() - t0;
-		// Appends.  Buffered writes to one file serialise on its inode lock (8 threads on one file: 8 GB/s; one thread on each of
-		// nine files: 56 GB/s, tools/ubench/file_write.cpp), so a file gets one task that appends its share of every sub-range
-		// in order -- or a few tasks over runs of sub-ranges when it takes most of the bytes (no barcode segment: two files)
-		std::vector<Wr> wr;
-		int64_t total_bytes = 0;
-		std::vector<int64_t> per_file(fds.size(), 0);
-		for (size_t f = 0; f < fds.size(); f++) {
-			for (size_t k = 0; k < subs.size(); k++) per_file[f] += (int64_t)bufs[k].file[f].n;
-			total_bytes += per_file[f];
-		}
-		for (size_t f = 0; f < fds.size(); f++) {
-			if (!per_file[f]) continue;
-			int parts = (int)((double)per_file[f] / (double)total_bytes * (double)W + 0.5);
-			if (parts > 4) parts = 4;
-			if (parts < 1) parts = 1;
-			const int64_t target = (per_file[f] + parts - 1) / parts;
-			int64_t at = file_off[f], acc = 0;
-			size_t k0 = 0;
-			for (size_t k = 0; k < subs.size(); k++) {
-				acc += (int64_t)bufs[k].file[f].n;
-				if (acc >= target || k + 1 == subs.size()) {
-					if (acc > 0) wr.push_back(Wr{ f, k0, k + 1, at });
-					at += acc; acc = 0; k0 = k + 1;
-				}
-			}
-			file_off[f] += per_file[f];
-			bytes_out += per_file[f];
-		}
-		{
-			std::lock_guard<std::mutex> lk(ap_mu);
-			ap_busy[set] = true;
-			ap_jobs.push_back(AppendJob{ set, std::move(wr) });
-		}
-		ap_cv.notify_all();
-		return true;
-	}
-};
+using namespace tdstream;
 
 // ---- td_stream_opts as the run uses them (the defaults of include/tagdust_io.h) ----
 // The reference reads 1 000 001 records at a time (param->num_query, barcode_hmm.c:172).  Per-read results do not depend on how
 // a file is cut into batches -- except through the -ref artifact filter, whose per-thread read ranges are taken over a batch:
 // with a filter set (and in a parse-only run) the batches are the reference's (reference_batches), otherwise they are 2^18
 // reads (one tile per wave slot of the device; a quarter of the page-locked memory and a pipeline that fills four times sooner).
-td_stream_opts resolve_opts(const td_stream_opts* opts, bool reference_batches)
+td_stream_opts tdstream::resolve_opts(const td_stream_opts* opts, bool reference_batches)
 {
 	td_stream_opts o{};
 	if (opts) o = *opts;
@@ -956,6 +44,8 @@ td_stream_opts resolve_opts(const td_stream_opts* opts, bool reference_batches)
 	o.n_threads = td_stage_threads(o.n_threads, 32);
 	return o;
 }
+
+namespace {
 
 // batches (record ranges of every file) in flight on the devices: the option of a context of the run, 3 when it has none
 int pipeline_depth(td_ctx* ctx)
@@ -1093,25 +183,11 @@ void run_stages(const std::string& prefix, RunError& err, const std::vector<std:
 		if (e) err.fail(prefix + "close failed: " + strerror(e));
 	}
 	if (N > 1) for (const Target& tg : dev) if (tg.ctx) for (int d = 0; d < N; d++) (void)td_set_batch_window(tg.ctx[d], 0, 0);
-	for (auto& r : readers) r->stop();
-	for (auto& r : readers) {
-		st.bytes_in += r->bytes_in; st.parse_s += r->parse_s; st.read_s += r->read_s;
-		r->release(!err.failed());
-	}
+	finish_readers(readers, !err.failed(), st.bytes_in, st.parse_s, st.read_s);
 	if (writer) st.bytes_out = writer->bytes_out;
 }
 
 } // namespace
-
-extern "C" void td_stream_release(void)
-{
-	std::lock_guard<std::mutex> lk(g_cache_mu);
-	for (Batch* q : g_cache) { td_host_free(q->codes); td_host_free(q->seq_out); td_host_free(q->offs); td_host_free(q->res); delete q; }
-	g_cache.clear();
-}
-
-// the writer's "%0.2f" (tests compare it with printf digit for digit); returns the number of characters written to buf[48]
-extern "C" int td_format_q(float q, char* buf) { return put_q(buf, q); }
 
 extern "C" int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* arch, const char* out_prefix,
                              const td_stream_opts* opts, td_stream_stats* stats)
@@ -1183,39 +259,6 @@ extern "C" int td_stream_survey(td_ctx* ctx, const char* in_path, const td_strea
 	return TD_OK;
 }
 
-// The head of a file as the run will read it, through the pipeline's own Source / Reader (plain memory, no GPU): plain, .gz, .bz2,
-// FASTA and SAM / BAM heads need no second parser.  Records are taken until at least `limit` are there or the file ends; the
-// producer is then told to stop and the source closed -- the run opens the file again, as the reference does.
-int td_stream_head(const char* path, int64_t limit, int32_t n_threads, std::vector<uint8_t>& codes, std::vector<int64_t>& offs, std::string& why)
-{
-	td_stream_opts want{};
-	want.n_threads = n_threads;
-	want.batch_reads = 1 << 16;
-	want.block_bytes = (int64_t)16 << 20;
-	const td_stream_opts o = resolve_opts(&want, false);
-	codes.clear();
-	offs.assign(1, 0);
-	RunError err;
-	Reader rd(err, o, true, false, o.n_threads);
-	if (!rd.src.open(path, o.block_bytes, why)) return TD_FAIL;
-	if (!rd.start(3)) { why = "td_stream_head: out of memory"; return TD_FAIL; }
-	Batch* b = nullptr;
-	while ((int64_t)offs.size() - 1 < limit && rd.ready->pop(b)) {
-		const int64_t take = std::min<int64_t>(b->n, limit - ((int64_t)offs.size() - 1));
-		const int64_t base = offs.back();
-		codes.insert(codes.end(), b->codes, b->codes + b->offs[take]);
-		for (int64_t i = 1; i <= take; i++) offs.push_back(base + b->offs[i]);
-		b->pieces.clear();
-		if (!rd.free_list->push(b)) break;
-	}
-	const bool enough = (int64_t)offs.size() - 1 >= limit;
-	rd.ready->abort();          // (the producer leaves whatever wait it is in)
-	rd.free_list->abort();
-	rd.stop();
-	if (err.failed() && !enough) { why = err.message(); return TD_FAIL; }
-	return TD_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Several input files of one run, several devices: the controller's loop for paired / three-read data
 // (hmm_controller_multiple, src/barcode_hmm.c:244-385).
@@ -1241,46 +284,6 @@ bool rna_dust_low(const uint8_t* s, int64_t len, int dust_cut)
 	for (int j = 0; j < 64; j++) sc += (double)trip[j] * ((double)trip[j] - 1.0) / 2.0;
 	sc = sc / (double)(c - 3) * 10.0;
 	return sc > (double)dust_cut;
-}
-
-// compare_read_names(), src/io.c:2128-2393: the same place on the flow cell (CASAVA 1.8 / <= 1.7 names), else the same name up
-// to the first blank or ';'.  The format is taken from the first name seen (`detected`, like the reference's static).
-bool names_differ(const std::string& a, const std::string& b, int& detected)
-{
-	char i1[100], f1[100], i2[100], f2[100];
-	int r1 = 0, l1 = 0, t1 = 0, x1 = 0, y1 = 0, r2 = 0, l2 = 0, t2 = 0, x2 = 0, y2 = 0;
-	i1[0] = f1[0] = i2[0] = f2[0] = 0;
-	if (detected == -1) {
-		if (sscanf(a.c_str(), "%99[^:]:%d:%99[^:]:%d:%d:%d:%d ", i1, &r1, f1, &l1, &t1, &x1, &y1) == 7) detected = 1;
-		else if (sscanf(a.c_str(), "%99[^:]:%d:%d:%d:%d", i1, &l1, &t1, &x1, &y1) == 5) detected = 2;
-		else detected = 1000;
-	}
-	if (detected == 1) {
-		if (sscanf(a.c_str(), "%99[^:]:%d:%99[^:]:%d:%d:%d:%d ", i1, &r1, f1, &l1, &t1, &x1, &y1) != 7) return true;
-		if (sscanf(b.c_str(), "%99[^:]:%d:%99[^:]:%d:%d:%d:%d ", i2, &r2, f2, &l2, &t2, &x2, &y2) != 7) return true;
-		return y1 != y2 || x1 != x2 || t1 != t2 || l1 != l2 || strcmp(f1, f2) != 0 || r1 != r2 || strcmp(i1, i2) != 0;
-	}
-	if (detected == 2) {
-		if (sscanf(a.c_str(), "%99[^:]:%d:%d:%d:%d", i1, &l1, &t1, &x1, &y1) != 5) return true;
-		if (sscanf(b.c_str(), "%99[^:]:%d:%d:%d:%d", i2, &l2, &t2, &x2, &y2) != 5) return true;
-		return y1 != y2 || x1 != x2 || t1 != t2 || l1 != l2 || strcmp(i1, i2) != 0;
-	}
-	for (size_t i = 0; i < a.size(); i++) {
-		if (isspace((unsigned char)a[i]) || a[i] == ';') break;
-		if (i >= b.size() || a[i] != b[i]) return true;
-	}
-	return false;
-}
-
-// name of record i of a batch
-std::string record_name(const Batch& b, int64_t i)
-{
-	for (const Piece& pc : b.pieces)
-		if (i >= pc.first && i < pc.first + (pc.hi - pc.lo)) {
-			const TdRec& r = (*pc.recs)[(size_t)(pc.lo + (i - pc.first))];
-			return std::string(pc.blk->data + r.name_off, (size_t)r.name_len);
-		}
-	return std::string();
 }
 
 // what the architectures and contexts of the input files say about the run (barcode_hmm.c:105-153)
@@ -1422,22 +425,9 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 	// barcode_hmm.c:257-289: the files hold the same number of records, and the first 1000 names of every pair of files name the same reads
 	bool first = true;
 	int name_format = -1;
-	auto check = [&](const Tuple& t) -> std::string {
-		for (int k = 0; k < K; k++)
-			if (!t.b[(size_t)k] || t.b[(size_t)k]->n != t.b[0]->n)   // (the controller's own words behind ours, barcode_hmm.c:262)
-				return std::string("td_stream_run_multi: the input files differ in their number of records: Input File:") + files[0].path + " and " +
-				       files[k].path + " differ in number of entries.";
-		if (!first) return std::string();
-		first = false;
-		for (int64_t i = 0; i < std::min<int64_t>(1000, t.b[0]->n); i++) {
-			const std::string na = record_name(*t.b[0], i);
-			for (int k = 1; k < K; k++) {
-				const std::string nb = record_name(*t.b[(size_t)k], i);
-				if (names_differ(na, nb, name_format)) return "td_stream_run_multi: the input files seem to contain reads in different order: " + na + " / " + nb;
-			}
-		}
-		return std::string();
-	};
+	std::vector<const char*> paths;
+	for (int k = 0; k < K; k++) paths.push_back(files[k].path);
+	auto check = [&](const Tuple& t) { return lockstep_objection("td_stream_run_multi: ", t.b.data(), paths.data(), K, first, name_format); };
 	// the write stage: run_rna_dust for the files that no device sees, the per-record combination, print_all
 	int64_t cnt[TD_NUM_COUNTERS];
 	for (int q = 0; q < TD_NUM_COUNTERS; q++) cnt[q] = 0;
@@ -1489,6 +479,3 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 	if (err.failed()) { td_io_set_error(err.message()); return TD_FAIL; }
 	return TD_OK;
 }
-
-// td_merge_stream: the `merge` controller on the same readers
-#include "td_merge_stream.inc"

@@ -146,9 +146,10 @@ def test_pipeline_with_too_few_batch_buffers_does_not_hang(tmp_path):
     (tools/tsan_stream/stub.cpp), the allocator cut off after N allocations: every N ends -- with the same files as an
     unlimited run, or with the 'exhausted' error when not even one batch could be had."""
     exe = str(tmp_path / "stream_stub")
+    csrc = os.path.join(REPO, "tagdust_amd", "csrc")     # the decode pipeline's units, td_stream*.cpp, as tools/tsan_stream.sh names them
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-pthread", "-I" + os.path.join(REPO, "include"), "-w", "-o", exe,
-                           os.path.join(REPO, "tools", "tsan_stream", "stub.cpp"), os.path.join(REPO, "tagdust_amd", "csrc", "td_stream.cpp"),
-                           os.path.join(REPO, "tagdust_amd", "csrc", "td_fastq.cpp")])
+                           os.path.join(REPO, "tools", "tsan_stream", "stub.cpp"), *sorted(glob.glob(os.path.join(csrc, "td_stream*.cpp"))),
+                           os.path.join(csrc, "td_fastq.cpp")])
     rng = np.random.RandomState(4)
     fq = str(tmp_path / "in.fq")
     with open(fq, "wb") as fh:

@@ -28,7 +28,7 @@ bool td_merge_device_run(TdMergeDevice*, const TdMergeView&, const td_merge_tabl
 	return false;
 }
 
-// nor are the streaming pipeline's readers (td_stream.cpp)
+// nor are the streaming pipeline's readers (td_merge_stream.cpp over td_stream_reader.cpp)
 int td_merge_stream_run(const char*, const char*, const char*, int, int, bool, const std::function<bool(const TdMergeView&, TdWorkers&, td_merge_result*, std::string&)>&,
                         td_merge_stats*, std::string& err)
 {

@@ -1,6 +1,7 @@
 #!/bin/bash
-# The streaming pipeline (csrc/td_stream.cpp: reader/parser threads, writer thread, appender thread, their pools, the caller's thread) under
-# ThreadSanitizer on the CPU: td_stream.cpp + td_fastq.cpp as they are, the device entry points replaced by stand-ins
+# The streaming pipeline (csrc/td_stream*.cpp: reader/parser threads, writer thread, appender thread, their pools, the caller's thread) under
+# ThreadSanitizer on the CPU: the decode pipeline's units (td_stream.cpp, td_stream_reader.cpp, td_stream_writer.cpp; not the merge
+# controller, td_merge_stream.cpp) + td_fastq.cpp as they are, the device entry points replaced by stand-ins
 # (tools/tsan_stream/stub.cpp), a 60 000-read ragged FASTQ file in batches of 777 reads and blocks of 20 KB -- parse-only and
 # with the stubbed decode + real formatting / appends, each twice (the second run reuses the cached batch buffers), and the
 # multi-file pipeline (td_stream_run_multi: two input files in lock-step, two "devices", one file not decoded).  Before them the
@@ -10,7 +11,7 @@ set -e
 cd "$(dirname "$0")/.."
 OUT=/tmp/td_tsan
 mkdir -p $OUT
-g++ -std=c++17 -O1 -g -fsanitize=thread -pthread -Iinclude -w -o $OUT/tsan_stream tools/tsan_stream/stub.cpp tagdust_amd/csrc/td_stream.cpp tagdust_amd/csrc/td_fastq.cpp
+g++ -std=c++17 -O1 -g -fsanitize=thread -pthread -Iinclude -w -o $OUT/tsan_stream tools/tsan_stream/stub.cpp tagdust_amd/csrc/td_stream*.cpp tagdust_amd/csrc/td_fastq.cpp
 g++ -std=c++17 -O1 -g -fsanitize=thread -pthread -o $OUT/workers_host_check tools/workers_host_check.cpp
 $OUT/workers_host_check
 python3 - <<'PY'
