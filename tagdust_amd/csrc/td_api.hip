@@ -3,7 +3,9 @@
 // Replaces the reference's run_pHMM() fan-out (src/barcode_hmm.c:1895-2029): instead of T pthreads with
 // private model copies, one context per GPU holds the flattened model in HBM and launches the decode
 // kernel (td_kernels.hip) over a resident batch.  No torch, no CPU fallback: every entry point fails
-// with TD_FAIL (and a message in td_last_error) when HIP does.
+// with TD_FAIL (and a message in td_last_error) when HIP does.  What is decided without the device stands in plain C++ units
+// and is only applied here: a description checked and flattened, the -ref text packed, the logsum table (td_model_flat.cpp),
+// the geometry of a batch (td_batch_plan.cpp).
 #include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -16,23 +18,11 @@
 
 #include "../../include/tagdust_model.h"
 #include "td_ctx.h"
+#include "td_model_flat.h"
 #include "td_rnadust.h"
 #include "td_stats.h"
 
-static float g_logsum[TD_LOGSUM_SIZE];
-static bool g_logsum_ready = false;
 static std::string g_create_error;
-
-static void init_logsum_host()
-{
-	// init_logsum(), src/misc.c:57-63: (float) log(1. + exp((double) -i / SCALE)), SCALE = 1000.0f
-	if (g_logsum_ready) return;
-	for (int i = 0; i < TD_LOGSUM_SIZE; i++) g_logsum[i] = (float)log(1.0 + exp((double)-i / (double)1000.0f));
-	g_logsum_ready = true;
-}
-
-// prob2scaledprob(), src/misc.c:85-92
-static float p2sp(float p) { return p == 0.0f ? -INFINITY : (float)log((double)p); }
 
 // The copy threads of one context: started once, reused by every batch (the calling thread takes a share of each copy itself).
 // The pipelined calls keep six streams busy (two compute streams, upload, download and two for the small kernels around the
@@ -74,12 +64,6 @@ int fail(td_ctx* c, const char* fmt, ...)
 	va_end(ap);
 	if (c) c->err = buf; else g_create_error = buf;
 	return TD_FAIL;
-}
-
-extern "C" const float* td_logsum_table(void)
-{
-	init_logsum_host();
-	return g_logsum;
 }
 
 extern "C" const char* td_last_error(const td_ctx* ctx)
@@ -127,11 +111,10 @@ extern "C" int td_ctx_create(int device, td_ctx** out)
 	if (getenv("TD_SPEC_SELFCHECK_FAIL")) c->spec.selfcheck_fail = 1;
 	if (const char* e = getenv("TD_ASYNC_COMPILE")) c->spec.async_compile = atoi(e) != 0;
 	c->hbm_total = prop.totalGlobalMem;
-	init_logsum_host();
 	bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
 	          hipMalloc((void**)&c->d_logsum, sizeof(float) * TD_LOGSUM_LIVE) == hipSuccess &&
 	          hipMalloc((void**)&c->d_counters, sizeof(unsigned long long) * TD_COUNTER_WORDS) == hipSuccess &&
-	          hipMemcpy(c->d_logsum, g_logsum, sizeof(float) * TD_LOGSUM_LIVE, hipMemcpyHostToDevice) == hipSuccess &&
+	          hipMemcpy(c->d_logsum, td_logsum_table(), sizeof(float) * TD_LOGSUM_LIVE, hipMemcpyHostToDevice) == hipSuccess &&
 	          hipMemset(c->d_counters, 0, sizeof(unsigned long long) * TD_COUNTER_WORDS) == hipSuccess;
 	if (!ok) {
 		td_ctx_destroy(c);
@@ -179,79 +162,23 @@ extern "C" void td_ctx_destroy(td_ctx* c)
 // ---------------------------------------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------------------------------------
-// validate a description and put its tables on the device (synchronous copies)
+// validate a description (td_model_flat.cpp) and put its tables on the device (synchronous copies)
 static int build_dev_model(td_ctx* c, const td_model_desc* m, DevModel& out)
 {
-	if (m->S < 1 || m->S > TD_MAX_SEGMENTS) return fail(c, "td_model_upload: %d segments (1..%d supported)", m->S, TD_MAX_SEGMENTS);
-	if (m->H < 1 || m->H > TD_MAX_HMMS) return fail(c, "td_model_upload: %d HMMs (1..%d supported)", m->H, TD_MAX_HMMS);
-	if (!m->n_hmm || !m->n_col || !m->skip || !m->seg_type || !m->finger_len || !m->trans || !m->eM || !m->eI ||
-	    !m->sM || !m->sI || !m->label || !m->A)
-		return fail(c, "td_model_upload: NULL table pointer");
-	TdModelHeader h{};
-	h.S = m->S; h.H = m->H; h.C = m->C; h.avg_len = m->avg_len;
-	for (int i = 0; i < 5; i++) h.bg[i] = m->bg[i];
-	// random model constants, barcode_hmm.c:4520,4523 (float/double mix exactly as written there)
-	h.r_stay = p2sp((float)(1.0 - (1.0 / (double)(float)m->avg_len)));
-	h.r_exit = p2sp((float)(1.0 / (double)(float)m->avg_len));
-	int co = 0, ho = 0, req = 0, maxc = 0;
-	for (int j = 0; j < m->S; j++) {
-		if (m->n_hmm[j] < 1 || m->n_col[j] < 1) return fail(c, "td_model_upload: segment %d has %d HMMs x %d columns", j, m->n_hmm[j], m->n_col[j]);
-		TdSeg& s = h.seg[j];
-		s.n_hmm = m->n_hmm[j]; s.n_col = m->n_col[j]; s.col_off = co; s.hmm_off = ho;
-		s.skip = m->skip[j]; s.skip_live = !(m->skip[j] == -INFINITY); s.type = m->seg_type[j];
-		co += s.n_hmm * s.n_col; ho += s.n_hmm;
-		if (m->seg_type[j] == 'F') req += m->finger_len[j];
-		if (s.n_col > maxc) maxc = s.n_col;
-	}
-	if (co != m->C || ho != m->H) return fail(c, "td_model_upload: inconsistent sizes (columns %d vs C %d, HMMs %d vs H %d)", co, m->C, ho, m->H);
-	h.required_finger_len = req;
-	h.max_ncol = maxc;
-
-	std::vector<TdCol> cols(m->C);
-	for (int k = 0; k < m->C; k++) {
-		TdCol& q = cols[k];
-		memset(&q, 0, sizeof q);
-		uint32_t fl = 0;
-		for (int t = 0; t < 9; t++) { q.t[t] = m->trans[k * 9 + t]; if (!(q.t[t] == -INFINITY)) fl |= 1u << t; }
-		q.sM = m->sM[k]; if (!(q.sM == -INFINITY)) fl |= TDF_SM;
-		q.sI = m->sI[k]; if (!(q.sI == -INFINITY)) fl |= TDF_SI;
-		for (int e = 0; e < 5; e++) { q.eM[e] = m->eM[k * 5 + e]; q.eI[e] = m->eI[k * 5 + e]; }
-		q.flags = fl;
-	}
-	// per-HMM info for extract_reads (barcode_hmm.c:3205-3226): type | segment | hmm | decoy
-	std::vector<uint32_t> hinfo(m->H);
-	for (int hh = 0; hh < m->H; hh++) {
-		const int seg = m->label[hh] & 0xFFFF, f = (m->label[hh] >> 16) & 0x7FFF;
-		if (seg >= m->S) return fail(c, "td_model_upload: label[%d] names segment %d", hh, seg);
-		uint32_t v = (uint32_t)(uint8_t)m->seg_type[seg] | ((uint32_t)seg << 8) | ((uint32_t)f << 16);
-		if (m->seg_type[seg] == 'B' && f == m->n_hmm[seg] - 1) v |= 0x80000000u; // all-N decoy, interface.c:521-527
-		hinfo[hh] = v;
-	}
-	// label transition matrix -> predecessor lists (only u < v; staying in v is handled in the kernel)
-	std::vector<int32_t> poff(m->H + 1, 0), pidx;
-	for (int v = 0; v < m->H; v++) {
-		poff[v] = (int32_t)pidx.size();
-		for (int u = 0; u < v; u++) {
-			const float a = m->A[u * m->H + v];
-			if (a != 0.0f && a != 1.0f) return fail(c, "td_model_upload: transition matrix entry [%d][%d] = %g is not 0/1", u, v, a);
-			if (a == 1.0f) pidx.push_back(u);
-		}
-		if (m->A[v * m->H + v] != 1.0f) return fail(c, "td_model_upload: transition matrix diagonal [%d] must be 1", v);
-	}
-	poff[m->H] = (int32_t)pidx.size();
-	if (pidx.empty()) pidx.push_back(0);
-
+	TdFlatModel f;
+	std::string why;
+	if (!td_flatten_model(m, f, why)) return fail(c, "%s", why.c_str());
 	DevModel d;
-	d.h = h;
-	bool ok = hipMalloc((void**)&d.d_hdr, sizeof h) == hipSuccess && hipMalloc((void**)&d.d_cols, sizeof(TdCol) * cols.size()) == hipSuccess &&
-	          hipMalloc((void**)&d.d_hinfo, sizeof(uint32_t) * hinfo.size()) == hipSuccess &&
-	          hipMalloc((void**)&d.d_pred_off, sizeof(int32_t) * poff.size()) == hipSuccess &&
-	          hipMalloc((void**)&d.d_pred_idx, sizeof(int32_t) * pidx.size()) == hipSuccess &&
-	          hipMemcpy(d.d_hdr, &h, sizeof h, hipMemcpyHostToDevice) == hipSuccess &&
-	          hipMemcpy(d.d_cols, cols.data(), sizeof(TdCol) * cols.size(), hipMemcpyHostToDevice) == hipSuccess &&
-	          hipMemcpy(d.d_hinfo, hinfo.data(), sizeof(uint32_t) * hinfo.size(), hipMemcpyHostToDevice) == hipSuccess &&
-	          hipMemcpy(d.d_pred_off, poff.data(), sizeof(int32_t) * poff.size(), hipMemcpyHostToDevice) == hipSuccess &&
-	          hipMemcpy(d.d_pred_idx, pidx.data(), sizeof(int32_t) * pidx.size(), hipMemcpyHostToDevice) == hipSuccess;
+	d.h = f.h;
+	bool ok = hipMalloc((void**)&d.d_hdr, sizeof f.h) == hipSuccess && hipMalloc((void**)&d.d_cols, sizeof(TdCol) * f.cols.size()) == hipSuccess &&
+	          hipMalloc((void**)&d.d_hinfo, sizeof(uint32_t) * f.hinfo.size()) == hipSuccess &&
+	          hipMalloc((void**)&d.d_pred_off, sizeof(int32_t) * f.pred_off.size()) == hipSuccess &&
+	          hipMalloc((void**)&d.d_pred_idx, sizeof(int32_t) * f.pred_idx.size()) == hipSuccess &&
+	          hipMemcpy(d.d_hdr, &f.h, sizeof f.h, hipMemcpyHostToDevice) == hipSuccess &&
+	          hipMemcpy(d.d_cols, f.cols.data(), sizeof(TdCol) * f.cols.size(), hipMemcpyHostToDevice) == hipSuccess &&
+	          hipMemcpy(d.d_hinfo, f.hinfo.data(), sizeof(uint32_t) * f.hinfo.size(), hipMemcpyHostToDevice) == hipSuccess &&
+	          hipMemcpy(d.d_pred_off, f.pred_off.data(), sizeof(int32_t) * f.pred_off.size(), hipMemcpyHostToDevice) == hipSuccess &&
+	          hipMemcpy(d.d_pred_idx, f.pred_idx.data(), sizeof(int32_t) * f.pred_idx.size(), hipMemcpyHostToDevice) == hipSuccess;
 	if (!ok) { free_dev_model(d); return fail(c, "td_model_upload: device tables: %s", hipGetErrorString(hipGetLastError())); }
 	out = d;
 	return TD_OK;
@@ -386,26 +313,16 @@ extern "C" int td_set_artifacts(td_ctx* c, const uint8_t* string, const int32_t*
 	if (n_seq <= 0) return TD_OK;
 	if (!string || !s_index) return fail(c, "td_set_artifacts: null argument");
 	if (n_threads < 1) return fail(c, "td_set_artifacts: n_threads = %d", n_threads);
-	for (int32_t j = 0; j < n_seq; j++)
-		if (s_index[j + 1] < s_index[j] || s_index[j] < 0) return fail(c, "td_set_artifacts: s_index is not ascending at %d", j);
+	// the text as TD_MODE_RNA_DUST reads it (td_model_flat.cpp)
+	std::vector<int32_t> seq;
+	std::vector<uint32_t> pk;
+	std::string why;
+	if (!td_pack_artifacts(string, s_index, n_seq, seq, pk, why)) return fail(c, "%s", why.c_str());
 	const size_t bytes = (size_t)s_index[n_seq];
 	HIPCHK(c, hipMalloc((void**)&c->d_art_text, bytes ? bytes : 1));
 	HIPCHK(c, hipMalloc((void**)&c->d_art_index, sizeof(int32_t) * ((size_t)n_seq + 1)));
 	if (bytes) HIPCHK(c, hipMemcpy(c->d_art_text, string, bytes, hipMemcpyHostToDevice));
 	HIPCHK(c, hipMemcpy(c->d_art_index, s_index, sizeof(int32_t) * ((size_t)n_seq + 1), hipMemcpyHostToDevice));
-	// TD_MODE_RNA_DUST reads the text as 2-bit codes (only the low two bits are looked at; the leading 'X' is 'X' & 3 = 0),
-	// 16 per dword, every sequence from a dword boundary: one wave-uniform load per 16 characters
-	std::vector<int32_t> seq((size_t)n_seq * 2);
-	size_t words = 0;
-	for (int32_t j = 0; j < n_seq; j++) {
-		seq[(size_t)j * 2] = (int32_t)words;
-		seq[(size_t)j * 2 + 1] = s_index[j + 1] - s_index[j];
-		words += (size_t)(s_index[j + 1] - s_index[j] + 15) / 16;
-	}
-	std::vector<uint32_t> pk(words + 1, 0u);
-	for (int32_t j = 0; j < n_seq; j++)
-		for (int32_t q = 0; q < seq[(size_t)j * 2 + 1]; q++)
-			pk[(size_t)seq[(size_t)j * 2] + (size_t)(q >> 4)] |= (uint32_t)(string[s_index[j] + q] & 3u) << (2 * (q & 15));
 	HIPCHK(c, hipMalloc((void**)&c->d_art_pk, pk.size() * 4));
 	HIPCHK(c, hipMalloc((void**)&c->d_art_seq, seq.size() * 4));
 	HIPCHK(c, hipMemcpy(c->d_art_pk, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));

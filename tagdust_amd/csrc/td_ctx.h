@@ -1,5 +1,6 @@
 // td_ctx.h -- what the two host units of the C-ABI layer share: the context and its batch slots (td_api.hip runs them), the state of
 // the model-specialised kernel inside the context (td_spec_host.hip runs that), the few helpers both call.  Nothing here is exported.
+// (The plain C++ units they apply -- td_model_flat.cpp, td_batch_plan.cpp, td_spec_plan.cpp, td_spec_bounds.cpp -- know nothing of it.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>

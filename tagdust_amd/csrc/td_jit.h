@@ -1,10 +1,14 @@
-// td_jit.h -- interface between the C-ABI layer (td_spec_host.hip, td_api.hip) and the model-specialised kernel builder (td_jit.hip: plan, model
-// section, layout, compile + cache; td_spec_bounds.cpp: the bound tables)
+// td_jit.h -- interface between the C-ABI layer (td_spec_host.hip, td_api.hip) and the model-specialised kernel builder (td_spec_plan.cpp:
+// knobs, plan, model section, layout; td_spec_bounds.cpp: the bound tables -- both plain C++; td_jit.hip: full source, compile + cache)
 #pragma once
 #include <string>
 #include <vector>
 #include "../../include/tagdust_hip.h"
 #include "td_device.h"
+
+#ifndef TD_HIDDEN
+#define TD_HIDDEN __attribute__((visibility("hidden")))
+#endif
 
 // The TD_SPEC_* environment knobs (DESIGN.md has the table).  They are read when a model is uploaded, or when a context-free
 // query is made, and hold for that model.
@@ -53,6 +57,9 @@ struct TdSpecPlan {
 	int restart = 0;                         // the kernel restarts the far sweeps of the pruned segments (TDS_RESTART)
 };
 TdSpecPlan td_spec_plan(const td_model_desc* m, const TdSpecKnobs& k);
+// the plan and the model's parameters as constexpr source text; td_jit.hip puts it in front of td_spec_kernel.inc (lsum_oob, window: as
+// td_spec_compile's)
+TD_HIDDEN std::string td_spec_model_section(const td_model_desc* m, const TdSpecPlan& p, int lsum_oob, int window);
 
 float td_spec_prune_z(const td_model_desc* m, int n_seg, int sfx_first);
 void td_spec_prune_tables(const td_model_desc* m, const TdSpecPlan& p, int lcap, int stride, std::vector<float>& tab);

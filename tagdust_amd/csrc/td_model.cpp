@@ -1,5 +1,6 @@
 // td_model.cpp -- host-side model construction (declared in include/tagdust_model.h): own restatement of how the
-// reference turns a read architecture + sequence statistics into the tables of struct model_bag.  Pure host code.
+// reference turns a read architecture + sequence statistics into the tables of struct model_bag.  Pure host code: the two calls
+// of that header that drive a context are td_calibrate.cpp's, so that this unit links without one (tools/model_host_check.cpp).
 //
 // The float/double mixing below is deliberate and follows the reference expression by expression: prob2scaledprob()
 // takes a *float* parameter (src/misc.c:85), so every double-valued argument expression is narrowed to float before the
@@ -13,28 +14,15 @@
 #include <algorithm>
 #include <chrono>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/tagdust_model.h"
-#include "td_jit.h"
+#include "td_model_inner.h"
 #include "td_stats.h"
 
 namespace {
 
 const double INV_SQRT_2PI = 0.3989422804014327; // src/misc.h:75
-
-float p2sp(float p) { return (p == 0.0) ? -INFINITY : (float)log((double)p); }   // prob2scaledprob, misc.c:85-92
-float sp2p(float p) { return (p == -INFINITY) ? 0.0f : (float)exp((double)p); }  // scaledprob2prob, misc.c:98-105
-
-float logsum_f(float a, float b) // logsum, misc.c:72-78
-{
-	const float* T = td_logsum_table();
-	const float mx = (a > b) ? a : b;
-	const float mn = (a < b) ? a : b;
-	if (mn == -INFINITY || (mx - mn) >= 15.7f) return mx;
-	return mx + T[(int)((mx - mn) * 1000.0f)];
-}
 
 double gaussian_pdf(double x, double m, double s) // misc.c:375-379
 {
@@ -258,7 +246,7 @@ static int sequence_stats_count(const td_arch* a, const uint8_t* codes, const in
 
 // the reference reads batches of num_query reads and stops once more than 1 000 000 were seen (io.c:184): scan_limit is
 // 1 000 001 with the release build's batches of 1 000 001 records, 1 001 000 with the 1000 of its -DRTEST builds
-static int sequence_stats_limit(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads, td_seq_stats* ssi, int64_t scan_limit)
+int sequence_stats_limit(const td_arch* a, const uint8_t* codes, const int64_t* offs, int64_t n_reads, td_seq_stats* ssi, int64_t scan_limit)
 {
 	if (!a || !codes || !offs || !ssi || n_reads < 0) return TD_FAIL;
 	TdSeqCounts k;
@@ -817,70 +805,37 @@ extern "C" float td_calibration_select(const float* mapq, const uint8_t* is_rand
 	return thres4 < 20 ? thres4 : 20.0f;
 }
 
-extern "C" int td_estimate_threshold(td_ctx* ctx, const td_arch* a, const td_seq_stats* ssi, float d, uint32_t seed,
-                                     int32_t n_reads, int32_t rng, float* threshold)
+// td_estimate_threshold (td_calibrate.cpp) scores the calibration reads in these classes.
+// The simulated reads come out of the model itself: most are as long as the data, the read segment's geometric length gives
+// a few of ten times that.  The decode workspace is laid out for a batch's longest read, so the reads are scored in three
+// length classes (up to the 75th / 95th percentile / the rest): 30 GB of workspace instead of 260 GB for 400 000 reads of a
+// 150-nt architecture -- which would also leave no room for the second workspace of the pipelined calls afterwards.
+std::vector<TdCalClass> td_calibration_classes(const uint8_t* codes, const int64_t* offs, int64_t n)
 {
-	if (!ctx || !threshold) return TD_FAIL;
-	// The scoring model's kernel is compiled (seconds) while the host emits the reads (seconds, bound to one thread by the
-	// rand() sequence): the compile only fills the code cache td_model_upload looks into.
-	std::thread warm;
-	td_model_tables* scoring = nullptr;
-	int32_t specialize = 0;
-	const bool overlap = getenv("TD_CAL_OVERLAP") ? atoi(getenv("TD_CAL_OVERLAP")) != 0 : true;
-	if (overlap && td_get_option(ctx, "specialize", &specialize) == TD_OK && specialize &&
-	    td_model_build(a, ssi, 0.05f, d, &scoring) == TD_OK) {
-		warm = std::thread([scoring] {
-			const TdSpecPlan plan = td_spec_plan(&scoring->desc, td_spec_knobs());
-			std::vector<char> code; std::string log;
-			(void)td_spec_compile(&scoring->desc, plan, plan.k.lsum_oob, 0, code, log);
-		});
-	}
-	td_calibration* cal = nullptr;
-	const int emitted = td_calibration_emit(a, ssi, d, seed, n_reads, rng, &cal);
-	if (warm.joinable()) warm.join();
-	td_model_tables_free(scoring);
-	if (emitted != TD_OK) return TD_FAIL;
-	int rc = TD_FAIL;
-	// The simulated reads come out of the model itself: most are as long as the data, the read segment's geometric length gives
-	// a few of ten times that.  The decode workspace is laid out for a batch's longest read, so the reads are scored in three
-	// length classes (up to the 75th / 95th percentile / the rest): 30 GB of workspace instead of 260 GB for 400 000 reads of a
-	// 150-nt architecture -- which would also leave no room for the second workspace of the pipelined calls afterwards.
-	const int64_t n = cal->n_reads;
-	std::vector<float> q((size_t)n);
-	bool ok = td_model_upload(ctx, &cal->scoring->desc) == TD_OK;
-	if (ok && n > 0) {
-		std::vector<int32_t> lens((size_t)n), sorted;
-		for (int64_t i = 0; i < n; i++) lens[(size_t)i] = (int32_t)(cal->offs[i + 1] - cal->offs[i]);
-		sorted = lens;
-		std::sort(sorted.begin(), sorted.end());
-		const int32_t cut[3] = { sorted[(size_t)((n - 1) * 3 / 4)], sorted[(size_t)((n - 1) * 19 / 20)], sorted[(size_t)(n - 1)] };
-		int32_t lo = -1;
-		for (int k = 0; k < 3 && ok; k++) {
-			if (cut[k] <= lo) continue;
-			std::vector<int64_t> idx;
-			std::vector<int64_t> offs(1, 0);
-			std::vector<uint8_t> codes;
-			for (int64_t i = 0; i < n; i++) {
-				if (lens[(size_t)i] <= lo || lens[(size_t)i] > cut[k]) continue;
-				idx.push_back(i);
-				codes.insert(codes.end(), cal->codes + cal->offs[i], cal->codes + cal->offs[i + 1]);
-				offs.push_back((int64_t)codes.size());
-			}
-			lo = cut[k];
-			if (idx.empty()) continue;
-			if (codes.empty()) codes.push_back(0);
-			std::vector<td_read_result> res(idx.size());
-			ok = td_batch_upload(ctx, codes.data(), offs.data(), (int64_t)idx.size()) == TD_OK && td_run(ctx, TD_MODE_GET_PROB) == TD_OK &&
-			     td_batch_download(ctx, res.data(), nullptr, nullptr) == TD_OK;
-			for (size_t j = 0; ok && j < idx.size(); j++) q[(size_t)idx[j]] = res[j].mapq;
+	std::vector<TdCalClass> out;
+	if (n <= 0) return out;
+	std::vector<int32_t> lens((size_t)n), sorted;
+	for (int64_t i = 0; i < n; i++) lens[(size_t)i] = (int32_t)(offs[i + 1] - offs[i]);
+	sorted = lens;
+	std::sort(sorted.begin(), sorted.end());
+	const int32_t cut[3] = { sorted[(size_t)((n - 1) * 3 / 4)], sorted[(size_t)((n - 1) * 19 / 20)], sorted[(size_t)(n - 1)] };
+	int32_t lo = -1;
+	for (int k = 0; k < 3; k++) {
+		if (cut[k] <= lo) continue;
+		TdCalClass c;
+		c.offs.assign(1, 0);
+		for (int64_t i = 0; i < n; i++) {
+			if (lens[(size_t)i] <= lo || lens[(size_t)i] > cut[k]) continue;
+			c.idx.push_back(i);
+			c.codes.insert(c.codes.end(), codes + offs[i], codes + offs[i + 1]);
+			c.offs.push_back((int64_t)c.codes.size());
 		}
+		lo = cut[k];
+		if (c.idx.empty()) continue;
+		if (c.codes.empty()) c.codes.push_back(0);
+		out.push_back(std::move(c));
 	}
-	if (ok) {
-		*threshold = td_calibration_select(q.data(), cal->is_random, n);
-		rc = TD_OK;
-	}
-	td_calibration_free(cal);
-	return rc;
+	return out;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -978,32 +933,12 @@ extern "C" int td_simreads(const td_sim_params* p, const char* const* barcodes, 
 extern "C" void td_text_free(char* text) { free(text); }
 
 // ---------------------------------------------------------------------------------------------------------
-// architecture selection, test_architectures.c:20-289
+// architecture selection, test_architectures.c:20-289: the candidates' scores into posteriors (td_compare_architectures, td_calibrate.cpp)
 // ---------------------------------------------------------------------------------------------------------
-extern "C" int td_compare_architectures(td_ctx* ctx, const td_arch* const* archs, int32_t n_arch, const uint8_t* codes,
-                                        const int64_t* offs, int64_t n_reads, float e, float d, int32_t n_threads,
-                                        float* posterior, int32_t* best)
+void td_arch_posteriors(const float* b, int32_t n_arch, int64_t n_score, int32_t n_threads, float* posterior, int32_t* best)
 {
-	if (!ctx || !archs || n_arch < 1 || !codes || !offs || !posterior || !best || n_reads < 1) return TD_FAIL;
-	if (n_threads < 1) n_threads = 1;
-	// test_architectures() sets num_query = 100 000 (:38-42): statistics then scan batches of 100 000 reads until more than
-	// 1 000 000 were seen (1 100 000 reads), and the candidates are scored on the first batch only (:182-184)
-	const int64_t n_score = n_reads < 100000 ? n_reads : 100000;
-	// every candidate's own sequence statistics and model (test_architectures.c:60-170), then all of them over the first
-	// batch in one launch of the generic kernel (td_arch_scores: no per-candidate compile, reads staged once)
-	std::vector<td_model_tables*> tabs((size_t)n_arch, nullptr);
-	std::vector<const td_model_desc*> descs((size_t)n_arch, nullptr);
-	int rc = TD_OK;
-	for (int k = 0; k < n_arch && rc == TD_OK; k++) {
-		td_seq_stats st;
-		if (sequence_stats_limit(archs[k], codes, offs, n_reads, &st, 1100000) != TD_OK || td_model_build(archs[k], &st, e, d, &tabs[(size_t)k]) != TD_OK) rc = TD_FAIL;
-		else descs[(size_t)k] = &tabs[(size_t)k]->desc;
-	}
-	std::vector<float> b((size_t)n_arch * (size_t)n_score);
-	if (rc == TD_OK && td_arch_scores(ctx, descs.data(), n_arch, codes, offs, n_score, b.data()) != TD_OK) rc = TD_FAIL;
-	for (td_model_tables* t : tabs) td_model_tables_free(t);
-	for (int k = 0; k < n_arch && rc == TD_OK; k++) {
-		const float* bk = b.data() + (size_t)k * (size_t)n_score;
+	for (int k = 0; k < n_arch; k++) {
+		const float* bk = b + (size_t)k * (size_t)n_score;
 		float total = p2sp(1.0);                                      // ab->arch_posterior[i] = prob2scaledprob(1.0), test_architectures.c:164
 		const int64_t interval = n_score / n_threads;                  // barcode_hmm.c:1911
 		for (int t = 0; t < n_threads; t++) {
@@ -1014,7 +949,6 @@ extern "C" int td_compare_architectures(td_ctx* ctx, const td_arch* const* archs
 		}
 		posterior[k] = total;
 	}
-	if (rc != TD_OK) return TD_FAIL;
 	if (n_arch > 1) {
 		float sum = posterior[0];                                      // barcode_hmm.c:2009-2016
 		for (int k = 1; k < n_arch; k++) sum = logsum_f(sum, posterior[k]);
@@ -1031,5 +965,4 @@ extern "C" int td_compare_architectures(td_ctx* ctx, const td_arch* const* archs
 		posterior[0] = 1.0f;
 		*best = 0;
 	}
-	return TD_OK;
 }

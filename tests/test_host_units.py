@@ -1,5 +1,6 @@
-"""The plain C++ host units of the two counts (tagdust_amd/csrc/td_census_host.cpp, td_molecules_host.cpp) and of the batch geometry
-(td_batch_plan.cpp) build with the host compiler alone -- no hipcc, no HIP header, no HIP runtime -- and the stand-alone programs
+"""The plain C++ host units of the two counts (tagdust_amd/csrc/td_census_host.cpp, td_molecules_host.cpp), of the batch geometry
+(td_batch_plan.cpp) and of the model path (td_model.cpp, td_model_flat.cpp, td_spec_plan.cpp, td_spec_bounds.cpp) build with the host
+compiler alone -- no hipcc, no HIP header, no HIP runtime -- and the stand-alone programs
 over them (tools/*_host_check.cpp, the ones tools/host_checks.sh runs under the sanitizers) agree with their restatements.  No GPU,
 no sanitizer here."""
 import os
@@ -12,11 +13,12 @@ from conftest import REPO
 
 CSRC = os.path.join(REPO, "tagdust_amd", "csrc")
 # the program, and what it links beside the two host units of the counts (td_fingerprint_text is td_fastq.cpp's); the batch plan's
-# links its own unit alone, the worker pool's (td_workers.h) nothing at all
+# links its own unit alone, the worker pool's (td_workers.h) nothing at all, the model path's its four units
 COUNT_UNITS = ("td_census_host.cpp", "td_molecules_host.cpp")
-WITHOUT_COUNT_UNITS = ("batch_plan_host_check", "workers_host_check")
+WITHOUT_COUNT_UNITS = ("batch_plan_host_check", "workers_host_check", "model_host_check")
 PROGRAMS = [("census_host_check", []), ("molecules_host_check", ["td_fastq.cpp"]), ("dedup_host_check", []), ("collapse_host_check", []),
-            ("dedup_collapsed_host_check", []), ("mate_host_check", []), ("batch_plan_host_check", ["td_batch_plan.cpp"]), ("workers_host_check", [])]
+            ("dedup_collapsed_host_check", []), ("mate_host_check", []), ("batch_plan_host_check", ["td_batch_plan.cpp"]), ("workers_host_check", []),
+            ("model_host_check", ["td_model.cpp", "td_model_flat.cpp", "td_spec_plan.cpp", "td_spec_bounds.cpp"])]
 
 
 def host_compiler():

@@ -47,7 +47,7 @@ def test_restart_bounds_dominate_reference_values(name):
 
 
 def _first_read_like(g):
-    """Index of the first segment the plan treats like a read segment (td_jit.hip, read_like: one HMM of one column whose only
+    """Index of the first segment the plan treats like a read segment (td_spec_plan.cpp, read_like: one HMM of one column whose only
     live transitions are I->I and I->skip and which is entered through its insert state), or None.  The leading segments that
     can be pruned are the ones in front of it (td_spec_plan; every fixture is within the plan's limit on labels)."""
     II, ISKIP = 3, 8

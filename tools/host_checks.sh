@@ -1,5 +1,5 @@
 #!/bin/bash
-# The nine stand-alone programs over the library's plain C++ host units (tools/*_host_check.cpp), built with the host compiler under
+# The ten stand-alone programs over the library's plain C++ host units (tools/*_host_check.cpp), built with the host compiler under
 # AddressSanitizer and UBSan and run, leak detection on: no GPU, no HIP runtime, no Python.  Every step must succeed; the last line
 # is "host_checks: ok".   usage: tools/host_checks.sh   (CXX: the compiler, default g++; OUT: where the programs go)
 set -e
@@ -19,6 +19,7 @@ $CXX $SAN $C/td_census_host.cpp $C/td_molecules_host.cpp tools/mate_host_check.c
 $CXX $SAN -ffp-contract=off tools/merge_host_check.cpp $C/td_merge.cpp -o $OUT/merge_host_check -lpthread &&
 $CXX $SAN $C/td_batch_plan.cpp tools/batch_plan_host_check.cpp -o $OUT/batch_plan_host_check &&
 $CXX $SAN tools/workers_host_check.cpp -o $OUT/workers_host_check -lpthread &&
+$CXX $SAN $C/td_model.cpp $C/td_model_flat.cpp $C/td_spec_plan.cpp $C/td_spec_bounds.cpp tools/model_host_check.cpp -o $OUT/model_host_check &&
 $OUT/census_host_check &&
 $OUT/molecules_host_check &&
 $OUT/dedup_host_check &&
@@ -27,6 +28,7 @@ $OUT/dedup_collapsed_host_check &&
 $OUT/mate_host_check &&
 $OUT/batch_plan_host_check &&
 $OUT/workers_host_check &&
+$OUT/model_host_check &&
 $OUT/merge_host_check $G/r1.fq $G/r2.fq $G/merged_default.fq 16 0 &&
 $OUT/merge_host_check $G/r1.fq $G/r2.fq $G/merged_Q0.9_minlen20.fq 20 0.9 &&
 echo "host_checks: ok"

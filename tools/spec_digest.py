@@ -2,7 +2,7 @@
 """What the host side of the specialised kernel produces, as digests: for every model fixture of tests/golden and every TD_SPEC_*
 variant below, one sha256 over the generated source, the eight bound tables (with n_seg, sfx_first, z) and the eight impulse-response
 tables (with the restart flag) at lcap 40, 258 and 1026.  Run against two builds (TD_LIB_PATH names the library) the two outputs are
-equal exactly when td_jit.hip / td_spec_bounds.cpp generate the same kernels and tables.   usage: tools/spec_digest.py out.json"""
+equal exactly when td_spec_plan.cpp / td_jit.hip / td_spec_bounds.cpp generate the same kernels and tables.   usage: tools/spec_digest.py out.json"""
 import glob
 import hashlib
 import json
