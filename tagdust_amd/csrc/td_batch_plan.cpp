@@ -1,6 +1,8 @@
 // td_batch_plan.cpp -- see td_batch_plan.h.  Plain C++: integers in, integers out.
 #include "td_batch_plan.h"
 
+#include "../../include/tagdust_hip.h"
+
 #include <vector>
 
 int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
@@ -139,4 +141,58 @@ TdWsPlan plan_workspace(const TdWsRequest& rq, TdFreeMemFn free_mem, void* arg)
 		p.ws_bytes = slots * slot_bytes + big_extra;
 		return p;
 	}
+}
+
+// One output as plain bytes: into the caller's buffer when that is page-locked, else through pinned staging.
+static TdEgressChannel plain_channel(int k, size_t bytes, TdPageLockedFn page_locked, void* arg)
+{
+	TdEgressChannel ch;
+	ch.form = page_locked(arg, k) ? TD_EG_DIRECT : TD_EG_STAGED;
+	ch.copy_bytes = ch.alloc_bytes = bytes;
+	return ch;
+}
+
+static TdEgressChannel compact_channel(size_t copy_bytes, size_t alloc_bytes)
+{
+	TdEgressChannel ch;
+	ch.form = TD_EG_COMPACT;
+	ch.copy_bytes = copy_bytes; ch.alloc_bytes = alloc_bytes;
+	return ch;
+}
+
+// Compact egress.  The rewritten sequence is the input with some positions turned into the spacer byte: the keep bits (one
+// per base) come back instead and the host rebuilds it from its staging copy of the input -- unless the caller's page-locked
+// buffer was the DMA source, which the caller may have refilled since.  ri->labels is a handful of runs per read (the path
+// moves through the segments in order): (length, label) pairs come back and the host expands them.  A fifth of the bytes
+// over PCIe, and that much less work for the download's blit kernels, which compete with the decode kernel for CUs.
+TdEgressPlan plan_egress(const TdEgressRequest& rq, TdPageLockedFn page_locked, void* arg)
+{
+	TdEgressPlan p;
+	if (rq.n_reads == 0) return p;
+	const size_t n = (size_t)rq.n_reads, seq_bytes = (size_t)rq.n_bases;
+	p.rle_cap = rq.runs_cap > 0 ? rq.runs_cap : rq.rle_capacity;
+	p.lab_plain_bytes = (size_t)(rq.n_bases + rq.n_reads);   // (ri->labels has one entry more than the read has bases)
+	if (rq.want[TD_CH_RES]) p.ch[TD_CH_RES] = plain_channel(TD_CH_RES, n * sizeof(td_read_result), page_locked, arg);
+	if (rq.want[TD_CH_SEQ]) {
+		const size_t keep_bytes = n * (size_t)rq.nw1 * 4;
+		if (rq.compact_egress && seq_bytes && rq.raw_host) p.ch[TD_CH_SEQ] = compact_channel(keep_bytes, keep_bytes);
+		else p.ch[TD_CH_SEQ] = plain_channel(TD_CH_SEQ, seq_bytes, page_locked, arg);   // (no bases: buffers, and nothing to copy)
+	}
+	if (rq.want[TD_CH_LAB]) {
+		if (rq.compact_egress) {
+			// the overflow flag travels behind the runs in the same copy (a copy of a few bytes of its own would be carried out by a blit
+			// kernel); the table has a word to spare behind it
+			const size_t runs = n * (size_t)p.rle_cap;
+			p.ch[TD_CH_LAB] = compact_channel((runs + 1) * 4, (runs + 2) * 4);
+			p.rle_flag_word = runs;
+			p.finish_reads_runs = rq.runs_cap > 0;
+			if (p.finish_reads_runs) p.runs_flag_word = (size_t)rq.n_tiles * (size_t)rq.runs_cap * TD_WAVE;
+		} else p.ch[TD_CH_LAB] = plain_channel(TD_CH_LAB, p.lab_plain_bytes, page_locked, arg);
+	}
+	return p;
+}
+
+void plan_labels_plain(TdEgressPlan& p, TdPageLockedFn page_locked, void* arg)
+{
+	p.ch[TD_CH_LAB] = plain_channel(TD_CH_LAB, p.lab_plain_bytes, page_locked, arg);
 }

@@ -1,6 +1,7 @@
 // td_batch_plan.h -- the geometry of a batch, decided in plain integers: the byte layouts of a wave slot and of the output block, which
 // of the batch's tiles count as long (length classes), and the workspace plan -- how many wave slots the launch gets, of which
-// geometry, and what has to be allocated for them.  No HIP header and nothing of the context comes with it: td_api.hip fills a
+// geometry, and what has to be allocated for them -- and the egress plan: in which form each output comes back, and every byte
+// count of the way back.  No HIP header and nothing of the context comes with it: td_batch.hip fills a
 // request from the context, the slot and the route, applies the result to them and does what needs the device; the unit and the
 // stand-alone program over it (tools/batch_plan_host_check.cpp) build with a plain C++ compiler.  Nothing here is exported.
 #pragma once
@@ -56,3 +57,39 @@ struct TdWsPlan {
 // free_mem(arg, &bytes): the device's free memory now; false when it cannot be told.  Asked only where the plan depends on it.
 typedef bool (*TdFreeMemFn)(void* arg, size_t* free_bytes);
 TD_HIDDEN TdWsPlan plan_workspace(const TdWsRequest& rq, TdFreeMemFn free_mem, void* arg);
+
+// The egress plan of one batch: which of the three outputs come back from the device, and in which form.
+//   compact: the host rebuilds the output from something smaller -- the rewritten sequences from one keep bit per base (and its copy
+//            of the input), the labels from a table of rle_cap (length, label) runs per read with an overflow flag in the word behind it;
+//   direct:  plain bytes, copied into the caller's buffer, which is page-locked;
+//   staged:  plain bytes through pinned staging, copied out by the host.
+enum { TD_CH_RES = 0, TD_CH_SEQ = 1, TD_CH_LAB = 2, TD_N_CHANNELS = 3 };   // results, rewritten sequences, labels
+enum { TD_EG_NONE = 0, TD_EG_COMPACT, TD_EG_DIRECT, TD_EG_STAGED };
+struct TdEgressRequest {
+	int64_t n_reads = 0, n_bases = 0;
+	int32_t nw1 = 0, n_tiles = 0;
+	bool want[TD_N_CHANNELS] = { false, false, false };
+	bool compact_egress = false;      // the option
+	bool raw_host = false;            // the batch's bases are still on the host (staging copy, or the caller's own under "stable_input")
+	int32_t runs_cap = 0;             // entries per read of the label runs the decode launch left (0: none)
+	int32_t rle_capacity = 0;         // ... and of a table the finish kernel scans from the labels
+};
+struct TdEgressChannel {
+	int form = TD_EG_NONE;
+	size_t copy_bytes = 0;            // what the device-to-host copy moves (0: there is none)
+	size_t alloc_bytes = 0;           // what its device buffer and its pinned landing hold (compact: d_keepo / h_keepo, d_rle / h_rle)
+};
+struct TdEgressPlan {
+	TdEgressChannel ch[TD_N_CHANNELS];
+	int32_t rle_cap = 0;              // entries per read of the run table
+	size_t rle_flag_word = 0;         // its overflow flag: the word behind the runs (labels compact)
+	bool finish_reads_runs = false;   // the finish kernel takes the runs from d_runs, whose own flag is at
+	size_t runs_flag_word = 0;        // ... this word
+	size_t lab_plain_bytes = 0;       // the labels as plain bytes, should the run table overflow
+};
+// page_locked(arg, channel): is the caller's buffer of this output page-locked?  Asked only for a channel that travels as plain bytes,
+// in the order results, sequences, labels.
+typedef bool (*TdPageLockedFn)(void* arg, int channel);
+TD_HIDDEN TdEgressPlan plan_egress(const TdEgressRequest& rq, TdPageLockedFn page_locked, void* arg);
+// a read had more label runs than the table holds: the labels travel as plain bytes after all
+TD_HIDDEN void plan_labels_plain(TdEgressPlan& p, TdPageLockedFn page_locked, void* arg);

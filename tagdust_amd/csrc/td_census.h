@@ -1,5 +1,5 @@
-// td_census.h -- the census of barcode spellings (include/tagdust_census.h) inside a context: its state, and what td_api.hip
-// calls.  The kernel and every td_census_* entry point that takes a context are in td_census.hip.  Nothing here is exported.
+// td_census.h -- the census of barcode spellings (include/tagdust_census.h) inside a context: its state, and what td_api.hip and td_batch.hip
+// call.  The kernel and every td_census_* entry point that takes a context are in td_census.hip.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,7 +35,7 @@ struct TdCensusArgs {
 	unsigned long long* __restrict__ tallies;
 };
 
-// the count of one decoded slot, queued on its compute stream (td_api.hip calls it behind the decode launch while the census is on)
+// the count of one decoded slot, queued on its compute stream (td_batch.hip calls it behind the decode launch while the census is on)
 __attribute__((visibility("hidden"))) int census_count_slot(td_ctx* c, TdSlot& s, const int32_t* out_type, const int8_t* labels);
 // option "census_kernel_us" of td_get_option: the count kernel's time of the last counted batch (waits for it)
 __attribute__((visibility("hidden"))) int census_last_kernel_us(td_ctx* c, int32_t* us);

@@ -1,5 +1,6 @@
-// td_ctx.h -- what the two host units of the C-ABI layer share: the context and its batch slots (td_api.hip runs them), the state of
-// the model-specialised kernel inside the context (td_spec_host.hip runs that), the few helpers both call.  Nothing here is exported.
+// td_ctx.h -- what the three host units of the C-ABI layer share: the context (td_api.hip keeps house in it) and its batch slots
+// (td_batch.hip runs them), the state of the model-specialised kernel inside the context (td_spec_host.hip runs that), the few
+// helpers they call.  Nothing here is exported.
 // (The plain C++ units they apply -- td_model_flat.cpp, td_batch_plan.cpp, td_spec_plan.cpp, td_spec_bounds.cpp -- know nothing of it.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,12 +22,12 @@
 // the device counter block: what the ABI reports, then the diagnostic tail of the development knobs (td_diag_get)
 #define TD_COUNTER_WORDS (TD_NUM_COUNTERS + TD_NUM_DIAG_COUNTERS)
 
-// One batch on its way through the device (see "batches" in td_api.hip).  What a slot knows about ITS BATCH lives in three groups,
+// One batch on its way through the device (see "batches" in td_batch.hip).  What a slot knows about ITS BATCH lives in three groups,
 // each value-initialised as a whole by the step that owns it -- so that nothing a branch of that step does not set can survive from
 // the batch before (round 3's soak fault was exactly that: a label-run table of the previous, smaller batch):
 //   TdStaged  <- slot_stage():       the reads as staged on the device and the workspace geometry chosen for them
 //   TdDecoded <- slot_decode():      what the last launch over the staged batch was and left behind
-//   TdFetch   <- slot_fetch_begin(): where the results go and in which form they travel
+//   TdFetch   <- slot_fetch_begin(): where the results go, and the plan of the form they travel in (td_batch_plan.cpp, plan_egress)
 // slot_stage() also resets the two later groups, slot_decode() the last one.  What is left in TdSlot itself belongs to the slot,
 // not to a batch: device / pinned buffers with their capacities, events, the ticket.
 struct TdRoute {             // where a batch runs (chosen by the caller of slot_stage, per batch)
@@ -69,10 +70,8 @@ struct TdDecoded {
 };
 struct TdFetch {
 	td_read_result* u_res = nullptr; int8_t* u_labels = nullptr; uint8_t* u_seq = nullptr;   // the caller's output buffers
-	bool res_direct = false, lab_direct = false, seq_direct = false;                          // ... are page-locked
+	TdEgressPlan plan;              // per output: not wanted, compact (keep bits / label runs), straight into the caller's page-locked buffer, staged
 	bool copies_deferred = false;   // td_wait issues the device-to-host copies (pipelined calls)
-	bool use_keep = false, use_rle = false;   // compact egress: keep bits instead of the rewritten sequence, label runs instead of labels
-	int32_t rle_cap = 0;
 	bool finished = false;          // the finish kernel is queued: slot_fetch_end has something to collect
 };
 struct TdSlot : TdStaged, TdDecoded, TdFetch {
@@ -240,8 +239,11 @@ struct td_ctx {
 };
 
 TD_HIDDEN int fail(td_ctx* c, const char* fmt, ...);   // (td_api.hip) TD_FAIL, and the message for td_last_error
-TD_HIDDEN bool is_pinned(const void* p);                // (td_api.hip) this host pointer is page-locked: the DMA engines can use it directly
-TD_HIDDEN bool tickets_outstanding(const td_ctx* c);   // (td_api.hip) a td_submit batch has not been waited for
+TD_HIDDEN bool is_pinned(const void* p);                // (td_batch.hip) this host pointer is page-locked: the DMA engines can use it directly
+TD_HIDDEN bool tickets_outstanding(const td_ctx* c);   // (td_batch.hip) a td_submit batch has not been waited for
+TD_HIDDEN void slot_release(TdSlot& s);                 // (td_batch.hip) a slot's buffers and events go (td_ctx_destroy)
+TD_HIDDEN int build_dev_model(td_ctx* c, const td_model_desc* m, DevModel& out);   // (td_api.hip) a description validated and its tables on the device
+TD_HIDDEN void free_dev_model(DevModel& d);                                         // (td_api.hip) ... and gone again (td_arch_scores brings candidates of its own)
 
 #define HIPCHK(c, call)                                                                       \
 	do {                                                                                      \
@@ -296,7 +298,7 @@ extern "C" TD_HIDDEN hipError_t td_launch_decode(const TdKernelArgs* ka, hipStre
 extern "C" TD_HIDDEN int td_kernel_block_threads(void);
 extern "C" TD_HIDDEN hipError_t td_launch_decode_multi(const TdKernelArgs* d_args, int n_models, int max_slots, hipStream_t stream);
 
-// td_api.hip
+// td_batch.hip
 TD_HIDDEN double wall_ms();
 
 // the output pointers of a launch's argument struct into such a block (out_labels where the struct has one: run_rna_dust has none)

@@ -1,5 +1,5 @@
 // td_host_inner.h -- the HOST halves of td_submit / td_wait that touch every byte of a batch: the staging copy into page-locked
-// memory, the rebuilding of the rewritten sequences from keep bits, the expansion of the label runs.  No HIP in here: td_api.hip
+// memory, the rebuilding of the rewritten sequences from keep bits, the expansion of the label runs.  No HIP in here: td_batch.hip
 // calls these around its device calls, and csrc/td_hostbench.cpp runs them alone (tools/host_scale.py: what do N ranks' host
 // halves cost one host when they run side by side?).
 #pragma once

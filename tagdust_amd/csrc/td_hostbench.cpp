@@ -2,7 +2,7 @@
 //
 // At 13-15 ms per 2^20-read step a rank's host work -- staging 157 MB into page-locked memory, rebuilding 157 MB of rewritten
 // sequences from keep bits, expanding 158 MB of labels from runs, copying 32 MB of records -- is of the order of the decode kernel
-// itself, and eight ranks do it on one host.  This runs exactly those routines (td_host_inner.h: the code td_api.hip calls around
+// itself, and eight ranks do it on one host.  This runs exactly those routines (td_host_inner.h: the code td_batch.hip calls around
 // its device calls) on plain memory, back to back, so that N processes side by side show what N ranks' host halves cost the
 // machine: the 8-GPU ceiling the host sets, measured without eight GPUs.
 #include <stdio.h>

@@ -1,4 +1,4 @@
-// td_jit.h -- interface between the C-ABI layer (td_spec_host.hip, td_api.hip) and the model-specialised kernel builder (td_spec_plan.cpp:
+// td_jit.h -- interface between the C-ABI layer (td_spec_host.hip, td_api.hip, td_batch.hip) and the model-specialised kernel builder (td_spec_plan.cpp:
 // knobs, plan, model section, layout; td_spec_bounds.cpp: the bound tables -- both plain C++; td_jit.hip: full source, compile + cache)
 #pragma once
 #include <string>

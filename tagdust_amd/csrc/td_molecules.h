@@ -1,4 +1,4 @@
-// td_molecules.h -- the molecule count (include/tagdust_molecules.h) inside a context: its state, and what td_api.hip calls.  The
+// td_molecules.h -- the molecule count (include/tagdust_molecules.h) inside a context: its state, and what td_api.hip and td_batch.hip call.  The
 // kernels and every td_mol_* entry point that takes a context are in td_molecules.hip; the table is td_keytable.h's.  Nothing here
 // is exported.
 #pragma once
@@ -97,7 +97,7 @@ struct TdMolArgs {
 	const unsigned long long* __restrict__ keeper;   // [slot_mask + 1] the ordinal of the one read that a slot's tree keeps
 };
 
-// A decoded slot's launches, queued on its compute stream behind the decode launch (td_api.hip calls it last in slot_decode while
+// A decoded slot's launches, queued on its compute stream behind the decode launch (td_batch.hip calls it last behind a decode launch while
 // the count is on): the count, the collapse's origin pass, dedup's two passes, each when it is on -- or, in the frozen state, the
 // replay kernel alone.  Dedup's second pass and the replay rewrite out_type, so everything else that reads the decoded outcomes is
 // queued in front of them.

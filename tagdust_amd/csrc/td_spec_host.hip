@@ -1,6 +1,6 @@
 // td_spec_host.hip -- the host life of the model-specialised kernel inside a context (c->spec, td_ctx.h): plan and compile at the
 // model upload, now or on a host thread; module load, logsum self-check and whole-kernel probe before a compiled kernel takes over;
-// the reloads a batch can ask for; the bound tables; the launch.  td_api.hip calls in through the spec_* functions of td_ctx.h.
+// the reloads a batch can ask for; the bound tables; the launch.  td_api.hip and td_batch.hip call in through the spec_* functions of td_ctx.h.
 #include <stdlib.h>
 #include <algorithm>
 #include <cmath>

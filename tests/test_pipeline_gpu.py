@@ -136,6 +136,33 @@ def test_submit_prob_mode_and_partial_outputs():
         c.wait(c.submit(seq, offs, mode=MODE_GET_PROB, res=res))
         assert np.array_equal(_bits(res["f_score"]), _bits(g["f_score"]))
         assert np.allclose(res["mapq"], g["mapq"], rtol=0, atol=1e-4)
+        # Label mode, every form an output can travel in (td_batch_plan.cpp, plan_egress) and the outputs one at a time: compact egress
+        # on, off, and with a run table too small for any read (the fall-back to the labels as they are), into pageable and into
+        # page-locked buffers -- the bytes of the synchronous path, and a buffer that was not named is not touched.
+        from tagdust_amd.lib import PinnedArray
+        c.upload_batch(seq, offs)
+        c.run()
+        want = dict(zip(("res", "labels", "seq_out"), c.download()))
+        shapes = {"res": ((n,), RESULT_DTYPE), "labels": ((int(offs[-1]) + n,), np.int8), "seq_out": ((int(offs[-1]),), np.uint8)}
+        pins = {k: PinnedArray(*v) for k, v in shapes.items()}
+        try:
+            for compact, rle_cap in ((1, 0), (0, 0), (1, 1)):
+                c.set_option("compact_egress", compact)
+                c.set_option("rle_cap", rle_cap)
+                for pinned in (False, True):
+                    for names in (("res",), ("seq_out",), ("labels",), ("seq_out", "labels"), ("res", "labels", "seq_out")):
+                        bufs = {k: pins[k].array if pinned else np.zeros(*shapes[k]) for k in shapes}
+                        for b in bufs.values():
+                            b.view(np.uint8)[:] = 99
+                        c.wait(c.submit(seq, offs, **{k: bufs[k] for k in names}))
+                        for k, b in bufs.items():
+                            if k in names:
+                                assert b.tobytes() == want[k].tobytes(), (compact, rle_cap, pinned, names, k)
+                            else:
+                                assert (b.view(np.uint8) == 99).all(), (compact, rle_cap, pinned, names, k)
+        finally:
+            for p in pins.values():
+                p.free()
     finally:
         c.close()
 
@@ -395,7 +422,7 @@ def test_length_outliers_get_their_own_wave_slots(monkeypatch):
 
 @pytest.mark.parametrize("name", ["c3_b6_s_r_p", "c2_indel_varlen", "window_b_r", "b_r_s_r", "r_g_b_r", "b_f", "win_r_s_b_r", "win_b_f_r_ref"])
 def test_compact_egress_equals_plain_copies(name, monkeypatch):
-    """The rewritten sequences and the labels come back as keep bits and label runs and are rebuilt on the host (td_api.hip
+    """The rewritten sequences and the labels come back as keep bits and label runs and are rebuilt on the host (td_batch_plan.cpp
     "Compact egress"); with the plain device-side copies (TD_COMPACT_EGRESS=0), with a run table too small for any read
     (TD_RLE_CAP=1: every batch takes the fall-back to the labels as they are) and with page-locked input (the keep bits cannot be
     used: the caller may have refilled the buffer) the bytes are the same, for base codes and for sequence text."""

@@ -1,4 +1,4 @@
-// batch_plan_host_check.cpp -- the batch geometry unit (tagdust_amd/csrc/td_batch_plan.cpp: length classes, workspace plan) as a
+// batch_plan_host_check.cpp -- the batch geometry unit (tagdust_amd/csrc/td_batch_plan.cpp: length classes, workspace plan, egress plan) as a
 // stand-alone program, for running it under the host sanitizers: no GPU is used, no Python.
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined
@@ -8,7 +8,10 @@
 // (a) cases whose expected values are derived by hand beside them; (b) a generated sweep held against old_lengths() / old_workspace(),
 // the arithmetic as it stood inside td_api.hip's slot_stage() / ensure_workspace() before the unit existed, restated over plain
 // integers (recursion and all) and sharing nothing with the unit: every field and the number of memory queries must agree, and every
-// branch of (a) must be taken by at least 1 % of the cases; (c) what holds for every swept plan that succeeds.  Exit status 0 when
+// branch of (a) must be taken by at least 1 % of the cases; (c) what holds for every swept plan that succeeds.  The egress plan the
+// same way: by hand, then the whole small input space against old_egress() / old_overflow() -- slot_fetch_begin(),
+// slot_issue_copies() and slot_fetch_end() as they decided and counted before the plan existed -- with every form of every output
+// taken by at least 1 % of the cases, every copy inside its buffers and both overflow flags inside theirs.  Exit status 0 when
 // all of it agrees.
 #define HOST_CHECK_NAME "batch_plan_host_check"
 #include "host_check.h"
@@ -545,10 +548,296 @@ static int sweep_workspace(bool verbose)
 	return bad;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// the egress plan
+// ---------------------------------------------------------------------------------------------------------
+// the caller's three output buffers as the plan gets to see them: page-locked or not, and which of them it asked about, in order
+struct Pins { bool pinned[3] = { false, false, false }; int asked[8] = { 0 }; int n_asked = 0; };
+static bool page_locked(void* arg, int k) { Pins* q = (Pins*)arg; if (q->n_asked < 8) q->asked[q->n_asked] = k; q->n_asked++; return q->pinned[k]; }
+
+// slot_fetch_begin() / slot_issue_copies() / slot_fetch_end() as they stood in td_api.hip, as far as they decide and count: the
+// context and the slot as plain integers in, every ensure()d size, every copy and every host-side step out
+enum { ACT_NONE, ACT_COPY, ACT_REBUILD, ACT_EXPAND };
+struct OldEg {
+	// context and slot
+	int compact_egress, rle_cap_forced, S, H;
+	int64_t n_reads, n_bases; int32_t nw1, n_tiles, runs_cap; bool raw_host;
+	bool u_res, u_seq, u_labels;            // the caller passed a buffer
+	bool pinned[3];
+	// slot_fetch_begin
+	bool use_keep, use_rle, res_direct, seq_direct, lab_direct; int32_t rle_cap;
+	size_t d_res, d_seq, d_lab, h_res, h_seq, h_lab, d_keepo, h_keepo, d_rle, h_rle;   // bytes ensure()d (NOT: the buffer was not asked for)
+	size_t rle_flag, runs_flag; bool sb_rle_out, sb_runs;
+	int asked[8], n_asked;
+	// slot_issue_copies: bytes per output, and whether the compact buffers were the source
+	size_t copy[3]; bool copy_compact[3], copy_direct[3];
+	// slot_fetch_end, host side
+	int act[3]; size_t act_bytes[3];
+};
+static const size_t NOT = (size_t)-1;
+static bool old_pinned(OldEg& o, int k) { if (o.n_asked < 8) o.asked[o.n_asked] = k; o.n_asked++; return o.pinned[k]; }
+static int old_rle_capacity(const OldEg& o)
+{
+	int cap = o.S + 2 < o.H ? o.S + 2 : o.H;
+	if (o.rle_cap_forced > 0) cap = o.rle_cap_forced;
+	return cap;
+}
+
+static void old_egress(OldEg& o)
+{
+	o.use_keep = o.use_rle = o.res_direct = o.seq_direct = o.lab_direct = false; o.rle_cap = 0;
+	o.d_res = o.d_seq = o.d_lab = o.h_res = o.h_seq = o.h_lab = o.d_keepo = o.h_keepo = o.d_rle = o.h_rle = NOT;
+	o.rle_flag = o.runs_flag = 0; o.sb_rle_out = o.sb_runs = false; o.n_asked = 0;
+	for (int k = 0; k < 3; k++) { o.copy[k] = 0; o.copy_compact[k] = o.copy_direct[k] = false; o.act[k] = ACT_NONE; o.act_bytes[k] = 0; }
+	// --- slot_fetch_begin
+	const int64_t n = o.n_reads;
+	if (n == 0) return;
+	const size_t res_bytes = (size_t)n * 32, seq_bytes = (size_t)o.n_bases, lab_bytes = (size_t)(o.n_bases + n);
+	const bool compact = o.compact_egress != 0;
+	o.use_keep = compact && o.u_seq && seq_bytes && o.raw_host;
+	o.use_rle = compact && o.u_labels;
+	o.rle_cap = o.runs_cap > 0 ? o.runs_cap : old_rle_capacity(o);
+	if (o.u_res) o.d_res = res_bytes;
+	if (o.u_seq && !o.use_keep) o.d_seq = seq_bytes;
+	if (o.u_labels && !o.use_rle) o.d_lab = lab_bytes;
+	if (o.u_res && !(o.res_direct = old_pinned(o, 0))) o.h_res = res_bytes;
+	if (o.u_seq && !o.use_keep && !(o.seq_direct = old_pinned(o, 1))) o.h_seq = seq_bytes;
+	if (o.u_labels && !o.use_rle && !(o.lab_direct = old_pinned(o, 2))) o.h_lab = lab_bytes;
+	const size_t keepo_bytes = (size_t)n * (size_t)o.nw1 * 4, rle_bytes = ((size_t)n * (size_t)o.rle_cap + 2) * 4;
+	if (o.use_keep) o.d_keepo = o.h_keepo = keepo_bytes;
+	if (o.use_rle) { o.d_rle = o.h_rle = rle_bytes; o.rle_flag = (size_t)n * (size_t)o.rle_cap; }
+	o.sb_rle_out = o.use_rle;
+	o.sb_runs = o.use_rle && o.runs_cap > 0;
+	if (o.sb_runs) o.runs_flag = (size_t)o.n_tiles * (size_t)o.runs_cap * 64;
+	// --- slot_issue_copies
+	if (o.u_res) { o.copy[0] = res_bytes; o.copy_direct[0] = o.res_direct; }
+	if (o.u_seq && seq_bytes) {
+		if (o.use_keep) { o.copy[1] = (size_t)n * (size_t)o.nw1 * 4; o.copy_compact[1] = true; }
+		else { o.copy[1] = seq_bytes; o.copy_direct[1] = o.seq_direct; }
+	}
+	if (o.u_labels) {
+		if (o.use_rle) { o.copy[2] = ((size_t)n * (size_t)o.rle_cap + 1) * 4; o.copy_compact[2] = true; }
+		else { o.copy[2] = lab_bytes; o.copy_direct[2] = o.lab_direct; }
+	}
+	// --- slot_fetch_end, the run table did not overflow
+	if (o.u_res && !o.res_direct) { o.act[0] = ACT_COPY; o.act_bytes[0] = (size_t)n * 32; }
+	if (o.u_seq && o.n_bases) {
+		if (o.use_keep) o.act[1] = ACT_REBUILD;
+		else if (!o.seq_direct) { o.act[1] = ACT_COPY; o.act_bytes[1] = (size_t)o.n_bases; }
+	}
+	if (o.u_labels) {
+		if (o.use_rle) o.act[2] = ACT_EXPAND;
+		else if (!o.lab_direct) { o.act[2] = ACT_COPY; o.act_bytes[2] = (size_t)(o.n_bases + n); }
+	}
+}
+
+// ... and slot_fetch_end's fall-back when it did (only reached with use_rle): the labels as they are, in a copy of their own
+static void old_overflow(OldEg& o)
+{
+	const size_t lab_bytes = (size_t)(o.n_bases + o.n_reads);
+	o.d_lab = lab_bytes;
+	o.n_asked = 0;
+	if (!(o.lab_direct = old_pinned(o, 2))) o.h_lab = lab_bytes;
+	o.copy[2] = lab_bytes; o.copy_compact[2] = false; o.copy_direct[2] = o.lab_direct;
+	o.use_rle = false;
+	o.act[2] = ACT_NONE; o.act_bytes[2] = 0;
+	if (!o.lab_direct) { o.act[2] = ACT_COPY; o.act_bytes[2] = lab_bytes; }
+}
+
+// what td_batch.hip's walk over the channels does on the host with channel k of a plan
+static int plan_act(const TdEgressPlan& p, int k, size_t& bytes)
+{
+	const TdEgressChannel& ch = p.ch[k];
+	bytes = 0;
+	if (!ch.copy_bytes) return ACT_NONE;
+	if (ch.form == TD_EG_STAGED) { bytes = ch.copy_bytes; return ACT_COPY; }
+	if (ch.form == TD_EG_COMPACT) return k == TD_CH_SEQ ? ACT_REBUILD : ACT_EXPAND;
+	return ACT_NONE;
+}
+
+static bool channel_is(const TdEgressChannel& ch, int form, size_t copy_bytes, size_t alloc_bytes)
+{
+	return ch.form == form && ch.copy_bytes == copy_bytes && ch.alloc_bytes == alloc_bytes;
+}
+
+static int egress_by_hand()
+{
+	// 65 reads of 40 bases: 2600 bases, nw1 = (40 + 31) / 32 = 2 keep words per read, 2 tiles; a model with S + 2 = 7 < H: 7 runs per read.
+	// Records are 32 bytes: 65 * 32 = 2080.  Labels as plain bytes: 2600 + 65 = 2665.
+	TdEgressRequest rq;
+	rq.n_reads = 65; rq.n_bases = 2600; rq.nw1 = 2; rq.n_tiles = 2;
+	rq.want[0] = rq.want[1] = rq.want[2] = true;
+	rq.compact_egress = true; rq.raw_host = true; rq.runs_cap = 7; rq.rle_capacity = 7;
+	// all three pageable, compact: the records through staging (the one plain channel, the one question); keep bits 65 * 2 * 4 = 520 bytes;
+	// runs 65 * 7 = 455 words, the flag is word 455, 456 words = 1824 bytes travel, 457 words = 1828 bytes are allocated; the decode
+	// kernel's own table has 2 * 7 * 64 = 896 words in front of its flag
+	{
+		Pins q;
+		const TdEgressPlan p = plan_egress(rq, page_locked, &q);
+		CHECK(channel_is(p.ch[TD_CH_RES], TD_EG_STAGED, 2080, 2080) && channel_is(p.ch[TD_CH_SEQ], TD_EG_COMPACT, 520, 520) && channel_is(p.ch[TD_CH_LAB], TD_EG_COMPACT, 1824, 1828));
+		CHECK(p.rle_cap == 7 && p.rle_flag_word == 455 && p.finish_reads_runs && p.runs_flag_word == 896 && p.lab_plain_bytes == 2665);
+		CHECK(q.n_asked == 1 && q.asked[0] == TD_CH_RES);
+		// a read overflowed the table, the caller's label buffer is page-locked: 2665 bytes straight into it, one question
+		TdEgressPlan p2 = p;
+		Pins q2;
+		q2.pinned[TD_CH_LAB] = true;
+		plan_labels_plain(p2, page_locked, &q2);
+		CHECK(channel_is(p2.ch[TD_CH_LAB], TD_EG_DIRECT, 2665, 2665) && q2.n_asked == 1 && q2.asked[0] == TD_CH_LAB);
+		CHECK(memcmp(&p2.ch[TD_CH_RES], &p.ch[TD_CH_RES], sizeof p.ch[0]) == 0 && memcmp(&p2.ch[TD_CH_SEQ], &p.ch[TD_CH_SEQ], sizeof p.ch[0]) == 0 && p2.rle_cap == 7);
+	}
+	// the input was page-locked and read by the DMA engine, no "stable_input": the host has no copy to rebuild from, no keep bits -- the
+	// sequences as plain bytes through staging, and a second question
+	{
+		TdEgressRequest r = rq;
+		r.raw_host = false;
+		Pins q;
+		const TdEgressPlan p = plan_egress(r, page_locked, &q);
+		CHECK(channel_is(p.ch[TD_CH_RES], TD_EG_STAGED, 2080, 2080) && channel_is(p.ch[TD_CH_SEQ], TD_EG_STAGED, 2600, 2600) && channel_is(p.ch[TD_CH_LAB], TD_EG_COMPACT, 1824, 1828));
+		CHECK(q.n_asked == 2 && q.asked[0] == TD_CH_RES && q.asked[1] == TD_CH_SEQ);
+	}
+	// the generic kernel left no runs (runs_cap = 0): the finish kernel scans them from the labels into a table of rle_capacity = 7
+	{
+		TdEgressRequest r = rq;
+		r.runs_cap = 0;
+		Pins q;
+		const TdEgressPlan p = plan_egress(r, page_locked, &q);
+		CHECK(channel_is(p.ch[TD_CH_LAB], TD_EG_COMPACT, 1824, 1828) && p.rle_cap == 7 && p.rle_flag_word == 455 && !p.finish_reads_runs && p.runs_flag_word == 0);
+		CHECK(channel_is(p.ch[TD_CH_SEQ], TD_EG_COMPACT, 520, 520) && q.n_asked == 1);
+		// with the table forced to one entry (the tests' overflow route): 65 words of runs, 66 travel, 67 are allocated
+		r.rle_capacity = 1;
+		const TdEgressPlan p1 = plan_egress(r, page_locked, &q);
+		CHECK(channel_is(p1.ch[TD_CH_LAB], TD_EG_COMPACT, 264, 268) && p1.rle_cap == 1 && p1.rle_flag_word == 65);
+	}
+	// results only, into a page-locked buffer: one direct copy, nothing else planned
+	{
+		TdEgressRequest r = rq;
+		r.want[TD_CH_SEQ] = r.want[TD_CH_LAB] = false;
+		Pins q;
+		q.pinned[TD_CH_RES] = true;
+		const TdEgressPlan p = plan_egress(r, page_locked, &q);
+		CHECK(channel_is(p.ch[TD_CH_RES], TD_EG_DIRECT, 2080, 2080) && channel_is(p.ch[TD_CH_SEQ], TD_EG_NONE, 0, 0) && channel_is(p.ch[TD_CH_LAB], TD_EG_NONE, 0, 0));
+		CHECK(p.rle_flag_word == 0 && !p.finish_reads_runs && p.runs_flag_word == 0 && q.n_asked == 1 && q.asked[0] == TD_CH_RES);
+	}
+	// 65 reads of no bases (nw1 = 1, nothing staged on the host): the sequences stay plain -- buffers of no bytes, no copy, but the
+	// question is asked; labels are one entry per read, 65 * 7 runs all the same
+	{
+		TdEgressRequest r = rq;
+		r.n_bases = 0; r.nw1 = 1; r.raw_host = false;
+		Pins q;
+		q.pinned[TD_CH_SEQ] = true;
+		const TdEgressPlan p = plan_egress(r, page_locked, &q);
+		CHECK(channel_is(p.ch[TD_CH_SEQ], TD_EG_DIRECT, 0, 0) && channel_is(p.ch[TD_CH_LAB], TD_EG_COMPACT, 1824, 1828) && p.lab_plain_bytes == 65);
+		CHECK(q.n_asked == 2 && q.asked[1] == TD_CH_SEQ);
+		r.raw_host = true;   // (even if the host had them)
+		const TdEgressPlan pr = plan_egress(r, page_locked, &q);
+		CHECK(channel_is(pr.ch[TD_CH_SEQ], TD_EG_DIRECT, 0, 0));
+	}
+	// no reads: nothing is planned and nothing asked
+	{
+		TdEgressRequest r = rq;
+		r.n_reads = 0; r.n_bases = 0; r.n_tiles = 0;
+		Pins q;
+		const TdEgressPlan p = plan_egress(r, page_locked, &q);
+		const TdEgressPlan none;
+		CHECK(q.n_asked == 0 && p.rle_cap == 0 && p.rle_flag_word == 0 && p.runs_flag_word == 0 && !p.finish_reads_runs && p.lab_plain_bytes == 0);
+		for (int k = 0; k < TD_N_CHANNELS; k++) CHECK(channel_is(p.ch[k], TD_EG_NONE, 0, 0) && channel_is(none.ch[k], TD_EG_NONE, 0, 0));
+	}
+	return 0;
+}
+
+// one plan against the restatement: every field, the questions, and what holds for any plan (c)
+static int egress_agrees(const TdEgressPlan& p, const Pins& q, const OldEg& o)
+{
+	const bool wanted[3] = { o.u_res, o.u_seq, o.u_labels }, compact[3] = { false, o.use_keep, o.use_rle }, direct[3] = { o.res_direct, o.seq_direct, o.lab_direct };
+	const size_t dev_plain[3] = { o.d_res, o.d_seq, o.d_lab }, host_plain[3] = { o.h_res, o.h_seq, o.h_lab };
+	const size_t dev_compact[3] = { NOT, o.d_keepo, o.d_rle }, host_compact[3] = { NOT, o.h_keepo, o.h_rle };
+	const size_t user_bytes[3] = { (size_t)o.n_reads * 32, (size_t)o.n_bases, (size_t)(o.n_bases + o.n_reads) };   // the caller's buffers, by the ABI
+	CHECK(q.n_asked == o.n_asked && q.n_asked <= 3);
+	for (int j = 0; j < q.n_asked; j++) CHECK(q.asked[j] == o.asked[j]);
+	for (int k = 0; k < 3; k++) {
+		const TdEgressChannel& ch = p.ch[k];
+		const bool planned = o.n_reads > 0 && wanted[k];
+		const int form = !planned ? TD_EG_NONE : compact[k] ? TD_EG_COMPACT : direct[k] ? TD_EG_DIRECT : TD_EG_STAGED;
+		CHECK(ch.form == form && ch.copy_bytes == o.copy[k]);
+		CHECK(o.copy[k] == 0 || (o.copy_compact[k] == (form == TD_EG_COMPACT) && o.copy_direct[k] == (form == TD_EG_DIRECT)));
+		// the buffers: exactly those of the channel's form, of the plan's size
+		const bool is_plain = form == TD_EG_DIRECT || form == TD_EG_STAGED;
+		CHECK((dev_plain[k] != NOT) == is_plain && (host_plain[k] != NOT) == (form == TD_EG_STAGED));
+		CHECK((dev_compact[k] != NOT) == (form == TD_EG_COMPACT) && (host_compact[k] != NOT) == (form == TD_EG_COMPACT));
+		if (is_plain) CHECK(ch.alloc_bytes == dev_plain[k] && (form == TD_EG_DIRECT || ch.alloc_bytes == host_plain[k]));
+		if (form == TD_EG_COMPACT) CHECK(ch.alloc_bytes == dev_compact[k] && ch.alloc_bytes == host_compact[k]);
+		if (form == TD_EG_NONE) CHECK(ch.alloc_bytes == 0 && ch.copy_bytes == 0);
+		size_t bytes = 0;
+		CHECK(plan_act(p, k, bytes) == o.act[k] && bytes == o.act_bytes[k]);
+		// (c) a copy stays inside its source and its destination
+		CHECK(ch.copy_bytes <= ch.alloc_bytes && (form != TD_EG_DIRECT || ch.copy_bytes <= user_bytes[k]));
+		CHECK(form != TD_EG_STAGED || bytes <= user_bytes[k]);
+	}
+	CHECK(p.rle_cap == o.rle_cap && p.rle_flag_word == o.rle_flag && p.finish_reads_runs == o.sb_runs && p.runs_flag_word == o.runs_flag);
+	CHECK((p.ch[TD_CH_LAB].form == TD_EG_COMPACT) == o.sb_rle_out);
+	CHECK(p.lab_plain_bytes == (o.n_reads > 0 ? user_bytes[2] : 0));
+	// (c) the flags lie inside what is allocated -- the run table's also inside what travels, the host reads it from there; the decode
+	// kernel's table is (n_tiles * runs_cap * 64 + 1) words (slot_decode)
+	if (p.ch[TD_CH_LAB].form == TD_EG_COMPACT) CHECK((p.rle_flag_word + 1) * 4 <= p.ch[TD_CH_LAB].copy_bytes && (p.rle_flag_word + 1) * 4 <= p.ch[TD_CH_LAB].alloc_bytes);
+	if (p.finish_reads_runs) CHECK(o.runs_cap > 0 && (p.runs_flag_word + 1) * 4 <= ((size_t)o.n_tiles * (size_t)o.runs_cap * 64 + 1) * 4);
+	return 0;
+}
+
+static int sweep_egress(bool verbose)
+{
+	int64_t taken[3][4] = { { 0 } };
+	int n_cases = 0;
+	const int64_t reads[4] = { 0, 1, 64, 65 };
+	for (int bits = 0; bits < 1 << 11; bits++) for (int ri = 0; ri < 4; ri++) {
+		OldEg o{};
+		o.u_res = bits & 1; o.u_seq = bits >> 1 & 1; o.u_labels = bits >> 2 & 1;
+		o.pinned[0] = bits >> 3 & 1; o.pinned[1] = bits >> 4 & 1; o.pinned[2] = bits >> 5 & 1;
+		o.compact_egress = bits >> 6 & 1; o.raw_host = bits >> 7 & 1;
+		o.S = 5; o.H = 9;                                   // rle_capacity: 7 ...
+		o.runs_cap = bits >> 8 & 1 ? 5 : 0;                 // (a launch that ran under another setting of the option left 5)
+		o.rle_cap_forced = bits >> 9 & 1 ? 1 : 0;           // ... or the forced 1
+		const int len = bits >> 10 & 1 ? 40 : 0;
+		o.n_reads = reads[ri]; o.n_bases = o.n_reads * len; o.nw1 = ((len > 1 ? len : 1) + 31) / 32; o.n_tiles = (int32_t)((o.n_reads + 63) / 64);
+		TdEgressRequest rq;
+		rq.n_reads = o.n_reads; rq.n_bases = o.n_bases; rq.nw1 = o.nw1; rq.n_tiles = o.n_tiles;
+		rq.want[TD_CH_RES] = o.u_res; rq.want[TD_CH_SEQ] = o.u_seq; rq.want[TD_CH_LAB] = o.u_labels;
+		rq.compact_egress = o.compact_egress != 0; rq.raw_host = o.raw_host; rq.runs_cap = o.runs_cap; rq.rle_capacity = old_rle_capacity(o);
+		Pins q;
+		for (int k = 0; k < 3; k++) q.pinned[k] = o.pinned[k];
+		TdEgressPlan p = plan_egress(rq, page_locked, &q);
+		old_egress(o);
+		if (egress_agrees(p, q, o)) { fprintf(stderr, HOST_CHECK_NAME ": egress sweep: case %d, %lld reads\n", bits, (long long)o.n_reads); return 1; }
+		for (int k = 0; k < 3; k++) taken[k][p.ch[k].form]++;
+		n_cases++;
+		if (o.use_rle) {   // the run table overflowed: the label channel planned again, everything else as it was
+			const TdEgressPlan before = p;
+			Pins q2;
+			for (int k = 0; k < 3; k++) q2.pinned[k] = o.pinned[k];
+			plan_labels_plain(p, page_locked, &q2);
+			old_overflow(o);
+			CHECK(q2.n_asked == 1 && o.n_asked == 1 && q2.asked[0] == o.asked[0]);
+			const TdEgressChannel& L = p.ch[TD_CH_LAB];
+			CHECK(L.form == (o.lab_direct ? TD_EG_DIRECT : TD_EG_STAGED) && L.copy_bytes == o.copy[2] && L.alloc_bytes == o.d_lab && (o.lab_direct || L.alloc_bytes == o.h_lab));
+			size_t bytes = 0;
+			CHECK(plan_act(p, TD_CH_LAB, bytes) == o.act[2] && bytes == o.act_bytes[2] && L.copy_bytes <= L.alloc_bytes && L.copy_bytes <= (size_t)(o.n_bases + o.n_reads));
+			CHECK(memcmp(&p.ch[TD_CH_RES], &before.ch[TD_CH_RES], sizeof p.ch[0]) == 0 && memcmp(&p.ch[TD_CH_SEQ], &before.ch[TD_CH_SEQ], sizeof p.ch[0]) == 0 && p.rle_cap == before.rle_cap);
+		}
+	}
+	static const char* const ch_names[3] = { "results", "sequences", "labels" };
+	static const char* const form_names[4] = { "none", "compact", "direct", "staged" };
+	int bad = 0;
+	for (int k = 0; k < 3; k++) for (int f = 0; f < 4; f++) {
+		if (k == TD_CH_RES && f == TD_EG_COMPACT) { if (taken[k][f]) bad = 1; continue; }   // (the records have no compact form)
+		if (verbose) printf("%8.2f %%  %s %s\n", 100.0 * (double)taken[k][f] / n_cases, ch_names[k], form_names[f]);
+		if (taken[k][f] * 100 < n_cases) { fprintf(stderr, HOST_CHECK_NAME ": egress sweep: %s %s in %lld of %d cases\n", ch_names[k], form_names[f], (long long)taken[k][f], n_cases); bad = 1; }
+	}
+	return bad;
+}
+
 int main(int argc, char** argv)
 {
 	const bool verbose = argc > 1 && strcmp(argv[1], "-v") == 0;   // -v: the share of the swept cases that takes each branch
-	if (by_hand() || sweep_lengths(verbose) || sweep_workspace(verbose)) return 1;
+	if (by_hand() || sweep_lengths(verbose) || sweep_workspace(verbose) || egress_by_hand() || sweep_egress(verbose)) return 1;
 	printf("batch_plan_host_check: ok\n");
 	return 0;
 }

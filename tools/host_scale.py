@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What do N ranks' HOST halves cost one host?  Runs the host side of td_submit / td_wait -- the staging copy into page-locked
 memory, the rebuilding of rewritten sequences from keep bits, the expansion of labels from runs, the copy of the records;
-td_host_halves_bench in the library: the routines td_api.hip calls around its device calls, no device involved -- back to back in
+td_host_halves_bench in the library: the routines td_batch.hip calls around its device calls, no device involved -- back to back in
 1, 2, 4 and 8 processes side by side, each with its share of the CPUs this job may use (as bench.py's bind_rank_to_numa gives
 every rank its share), for both kinds of caller buffers.  Prints and writes (second argument) a JSON record: aggregate reads/s
 and GB/s of host memory traffic per process count -- the ceiling the host sets for the 8-GPU run, measured without eight GPUs.
