@@ -134,7 +134,12 @@ int td_stream_survey(td_ctx* ctx, const char* in_path, const td_stream_opts* opt
  * call order other than it is its mate file -- its reader gets page-locked buffers, and before the decoded file's td_submit of a
  * tuple the run calls td_mol_mate_next with that tuple's batch of the mate file.  TD_FAIL with a message for more than one device,
  * for more than one decoded file (every other file must be R:N), and for a -ref filter on any context or dust != 0: the mate's own
- * outcome is not joined to the count, so a mate that could fail would take a molecule's one kept read out of the files.  The
+ * outcome is not joined to the count, so a mate that could fail would take a molecule's one kept read out of the files.  With the
+ * mate filter on -- the decoded file's contexts report "mate_filter" (td_mol_mate_filter_enable) -- and exactly two files, dust != 0
+ * and a -ref filter on the decoded file's contexts are accepted: the mate file still gets no contexts and is uploaded once, as mates,
+ * the device joins its outcome to the decoded record's in front of the count, and its record's own type counts as 0 in the
+ * per-record combination (the decoded record already carries the maximum); the contexts' dust must equal the call's.  With the
+ * filter on, three or more files and (dust != 0 or a filter) the run fails with a message that names the third file.  The
  * per-record combination stays: the maximum makes a duplicate (dedup) TD_EXTRACT_DUPLICATE, which no file's output holds; counts
  * counts it under TD_EXTRACT_SUCCESS and its barcode bin, as the single-file run's device counters do. */
 typedef struct td_stream_file {

@@ -123,7 +123,26 @@
  *   - the split between n1 and n2 is not in the key: two reads whose own read segments are shorter than P by different amounts can
  *     share a word (own ACG + mate T.. and own AC + mate GT..);
  *   - the mate's own outcome takes no part: the mate is not decoded, filtered or DUSTed here, only its first M bases are read.  A
- *     run that joins files (tagdust_run.h, --mate-bases) therefore refuses a -ref filter and DUST.
+ *     run that joins files (tagdust_run.h, --mate-bases) therefore refuses a -ref filter and DUST -- unless the mate filter is on.
+ *
+ * Mate filter (td_mol_mate_filter_enable) -- the mate's outcome joined to its read's, the reference's combination of a record over its
+ * files (HMMER3_MAX, src/barcode_hmm.c:344-350) moved in front of the count.  It applies to a context in mate mode.  While it is on,
+ * the mate batch of every TD_MODE_GET_LABEL batch is judged, and the verdict is joined to its read before anything reads the outcomes:
+ *   - mate type.  t2[i] is what TD_MODE_RNA_DUST leaves in read_type for mate i when the mates are taken as a batch of their own,
+ *     given as codes, under this context's settings as they stand when the batch is staged (td_batch_upload, td_submit): `dust` of
+ *     td_set_params; the artifacts, filter_error and n_threads of td_set_artifacts; the thread ranges of td_set_batch_window.  That is
+ *     do_rna_dust (src/barcode_hmm.c:2370-2395): 0, then match_to_reference sets (1-based sequence << 8) | 5, then DUST sets 6
+ *     whatever the type was.  Mate i is a left-over read of its thread range exactly when read i is: run_rna_dust (:2059-2068) and
+ *     run_pHMM (:1911-1922) split the same n the same way;
+ *   - join.  read_type[i] = max(read_type[i] as decoded, t2[i]), both signed ints, whole words.  read_type[i] as decoded includes
+ *     the read's own -ref and DUST.  Barcode, fingerprint, scores, labels and seq_out stay as decoded;
+ *   - the joined outcome is what everything sees that reads a batch's outcomes behind its decode: td_read_result, the -ref hit count
+ *     (td_artifact_hits_get; the reference counts hits from the combined type, :378-382), the census, the count's eligibility,
+ *     dedup's first ordinals and marks, the replay of a frozen context, the writers;
+ *   - td_counts_get does not: it is the decode kernel's own tally and stays as decoded.
+ * The host definition needs no function of its own: the four *_mated host functions, run over the same records with read_type
+ * replaced by the joined value, are the yardstick of the device path.  With dust == 0 and no artifacts every t2 is 0, and every
+ * result is bit for bit what it is with the filter off.  Limits: one mate -- a third file's outcome is not joined; one device.
  */
 #ifndef TAGDUST_MOLECULES_H
 #define TAGDUST_MOLECULES_H
@@ -183,6 +202,19 @@ int td_mol_mate_disable(td_ctx* ctx);
  * the context stays usable.  A call names one batch: a second call before the staging replaces the first.
  * td_get_option: "mate_bases" (0 = off) and "mate_kernel_us", the mate kernel's time of the last staged mate batch. */
 int td_mol_mate_next   (td_ctx* ctx, const uint8_t* codes, const int64_t* offs, int64_t n_reads);
+/* The mate filter, see above.  Both are TD_FAIL with a message unless mate mode is on and no td_submit tickets are outstanding; both
+ * start from an empty table (they do what td_mol_reset does), so a table never holds counts made under two eligibility rules.  A
+ * batch is judged as it is staged: one that is resident across the switch has to be uploaded again (td_run says so).
+ * td_mol_mate_disable, td_mol_disable and a new model switch the filter off as well.
+ * td_get_option: "mate_filter" (0 / 1); "mate_filter_kernel_us" and "mate_join_kernel_us", the filter kernel's time of the last staged
+ * mate batch and the join kernel's of the last decoded batch (TD_FAIL while the filter is off or before the first such launch; with
+ * dust == 0 and no artifacts neither kernel is launched). */
+int td_mol_mate_filter_enable (td_ctx* ctx);
+int td_mol_mate_filter_disable(td_ctx* ctx);
+/* t2 of the batch resident in the context (td_batch_upload / td_run path), in the caller's order: *n = its number of reads, at most
+ * cap types are copied.  Waits for the context's queued work.  TD_FAIL with a message while the filter is off or when the resident
+ * batch was staged without its mates. */
+int td_mol_mate_types  (td_ctx* ctx, int32_t* types, int64_t cap, int64_t* n);
 /* The four host definitions over reads with the mate joined into the key: the arguments of td_mol_host, td_mol_host_origins,
  * td_mol_dedup_host and td_mol_dedup_collapsed_host plus the mate batch behind labels.  mate == NULL is the unmated function (those
  * four are this call).  TD_FAIL with a message when mate->bases < 1 or prefix_bases + mate->bases > 32. */

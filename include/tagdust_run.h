@@ -89,6 +89,12 @@ typedef struct td_run_opts {
 	                                    molecules_prefix + M > 32, with an effective DUST other than 0 or a -ref filter (the mate's own outcome
 	                                    is not joined), with more than one device, with --dedup-collapsed (the survey reads one file), and
 	                                    unless exactly one file has an architecture other than R:N */
+	int32_t  mate_filter;            /* --mate-filter: with --mate-bases, the mate is judged as the reference judges an R:N file -- this run's
+	                                    DUST and -ref filter -- and its outcome joined to its read's in front of the count (tagdust_molecules.h,
+	                                    td_mol_mate_filter_enable): a read whose mate fails is neither counted nor kept by --dedup.  Lifts
+	                                    --mate-bases' refusal of DUST and -ref for two input files; refused without --mate-bases, and with
+	                                    three or more files unless DUST is 0 and there is no -ref (a third file's outcome is not joined).
+	                                    The one-device, one-decoded-file and no --dedup-collapsed rules of --mate-bases stay */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -121,7 +127,9 @@ const char* td_run_version(void);
  * cannot be read twice --, gives "# written" and "# duplicates removed" the replay's numbers and adds one line, "# dedup", in front
  * of them, while every other output of the run reports the second pass alone; --mate-bases, see td_run_opts, adds a "mate:" line
  * to the plan and two lines, "# mate bases" and "# mate file", behind "# prefix bases" to <out>_molecules.txt, and the run gives the
- * files other than the decoded one no contexts, so their reads are uploaded once, as mates, by the decoded file's context), the
+ * files other than the decoded one no contexts, so their reads are uploaded once, as mates, by the decoded file's context;
+ * --mate-filter, see td_run_opts, says in that "mate:" line that the filter is on and with what -- dust and the -ref file or none --
+ * and adds one line, "# mate filter", behind "# mate file"), the
  * multiread rule (interface.c:441-450: DUST and -ref off, with a warning, when the command line's architecture has two or more
  * R segments).  What depends on the arch file's choice is decided again by td_run_execute once the choice is made. */
 typedef struct td_run_plan_t td_run_plan_t;   /* (the function below has the plain name) */

@@ -284,8 +284,10 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	if (!strcmp(name, "dedup_active")) { *value = c->molecules.dedup.on; return TD_OK; }
 	if (!strcmp(name, "dedup_frozen")) { *value = c->molecules.frozen.on; return TD_OK; }   // td_mol_dedup_freeze: batches are replayed
 	if (!strcmp(name, "mate_bases")) { *value = c->molecules.mate.bases; return TD_OK; }   // td_mol_mate_enable's M, 0 = off
+	if (!strcmp(name, "mate_filter")) { *value = c->molecules.mate.filter ? 1 : 0; return TD_OK; }   // td_mol_mate_filter_enable
 	if (!strcmp(name, "collapse_active")) { *value = c->molecules.collapse.on; return TD_OK; }
-	// molecules_, dedup_, collapse_origin_, dedup_replay_ and mate_kernel_us: the stage's time of the last batch (-1: none of them)
+	// molecules_, dedup_, collapse_origin_, dedup_replay_, mate_, mate_filter_ and mate_join_kernel_us: the stage's time of the last
+	// batch (-1: none of them)
 	if (const int rc = mol_kernel_us(c, name, value); rc >= 0) return rc;
 	if (!strcmp(name, "overlap_active")) {
 		// pipelined batches alternate between two compute streams / workspaces (off: option, generic kernel, depth 1, or HBM

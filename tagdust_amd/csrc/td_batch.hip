@@ -51,7 +51,7 @@ void slot_release(TdSlot& s)
 {
 	void* dev[] = { s.d_raw, s.d_offs, s.d_read_at, s.d_keys, s.d_vals, s.d_sort_tmp, s.d_packed, s.d_lens, s.d_art_left,
 	                s.d_out, s.d_res, s.d_seq, s.d_lab, s.d_keepo, s.d_rle, s.d_runs, s.d_judged, s.d_mate_raw, s.d_mate_offs, s.d_mate_w,
-	                s.d_mate_n };
+	                s.d_mate_n, s.d_mate_type };
 	for (void* p : dev) if (p) (void)hipFree(p);
 	void* pinned[] = { s.h_raw, s.h_offs, s.h_res, s.h_seq, s.h_lab, s.h_keepo, s.h_rle, s.h_mate_raw, s.h_mate_offs };
 	for (void* p : pinned) if (p) (void)hipHostFree(p);
@@ -253,6 +253,13 @@ static int launch_begin(td_ctx* c, TdSlot& s, int mode, bool& empty)
 		return fail(c, "td_run: mate mode is on (td_mol_mate_enable, %d bases) and the resident batch of %lld reads was staged without a mate "
 		            "batch of as many reads: td_mol_mate_next first, then td_batch_upload; nothing was counted", c->molecules.mate.bases, (long long)s.n_reads);
 	}
+	// the mate filter: a batch staged under the other state of the switch has the wrong verdicts, or none
+	if (mode == TD_MODE_GET_LABEL && c->molecules.mate.bases > 0 && c->molecules.mate.filter != s.mate_judged) {
+		c->molecules.mate.named = false;
+		return fail(c, "td_run: the mate filter is %s (td_mol_mate_filter_%s) and the resident batch of %lld reads was staged while it was %s: "
+		            "td_mol_mate_next first, then td_batch_upload; nothing was counted", c->molecules.mate.filter ? "on" : "off",
+		            c->molecules.mate.filter ? "enable" : "disable", (long long)s.n_reads, s.mate_judged ? "on" : "off");
+	}
 	s.reset_decoded();   // (runs_cap above all: a launch of the generic kernel, or an empty batch, must not hand the label runs of this
 	                     // slot's previous launch to the finish kernel)
 	s.mode = mode;
@@ -271,12 +278,14 @@ static int slot_art_left(td_ctx* c, TdSlot& s)
 }
 
 // ... launch_end, behind the launch (ev_k0 stands in front of it): its stop event, then the counts that read the outcomes it left
-// -- the -ref hits when it ran with the filter, census and molecule count over a labelled batch -- and the slot has run.
+// -- the -ref hits when it ran with the filter, census and molecule count over a labelled batch -- and the slot has run.  With the
+// mate filter on, the join of the mates' verdicts stands in front of all of them: they read one outcome per pair.
 static int launch_end(td_ctx* c, TdSlot& s, bool with_artifacts)
 {
 	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
 	TdKernelArgs o{};
 	point_outputs(o, s.d_out, out_layout(s.n_tiles, s.lmax, s.nw1));
+	if (c->molecules.mate.filter && s.mode == TD_MODE_GET_LABEL && mol_mate_join(c, s, o.out_type) != TD_OK) return TD_FAIL;
 	if (with_artifacts && slot_count_hits(c, s, o.out_type) != TD_OK) return TD_FAIL;
 	if (c->census.on && s.mode == TD_MODE_GET_LABEL && census_count_slot(c, s, o.out_type, o.out_labels) != TD_OK) return TD_FAIL;
 	// the molecule count last: dedup's second pass, the last launch in there, rewrites the outcomes the counts above read

@@ -48,6 +48,9 @@ struct TdStaged : TdRoute {
 	bool raw_direct = false;  // the upload read the caller's page-locked buffer itself (no staging copy)
 	int32_t mate_m = 0;       // mate mode: d_mate_w / d_mate_n hold this batch's mates, made with M = mate_m (0: no mate batch was staged)
 	bool mate_direct = false; // ... and the upload read the caller's page-locked mate buffer itself
+	bool mate_judged = false; // the mate filter was on when the mate batch was staged: the batch's outcomes are joined with the mates'
+	bool mate_typed = false;  // ... and the filter kernel ran (dust != 0 or artifacts set): d_mate_type holds this batch's mate types;
+	                          // judged and not typed: every mate type is 0, d_mate_type is not read
 	const uint8_t* raw_host = nullptr;   // the batch's bases on the host, valid until the batch has been waited for: the pinned staging
 	                                     // copy, or the caller's own page-locked buffer under the "stable_input" contract; else NULL
 	TdStageBatch sb{};
@@ -103,6 +106,7 @@ struct TdSlot : TdStaged, TdDecoded, TdFetch {
 	int64_t* d_mate_offs = nullptr; size_t cap_mate_offs = 0;
 	unsigned long long* d_mate_w = nullptr; size_t cap_mate_w = 0;
 	uint8_t* d_mate_n = nullptr;   size_t cap_mate_n = 0;
+	int32_t* d_mate_type = nullptr; size_t cap_mate_type = 0;   // the mate filter's verdicts (td_mate_filter.hip), allocated by its first launch
 	uint8_t* h_mate_raw = nullptr; size_t cap_h_mate_raw = 0;   // (pinned staging, as h_raw and h_offs)
 	int64_t* h_mate_offs = nullptr; size_t cap_h_mate_offs = 0;
 	uint32_t* h_keepo = nullptr;   size_t cap_h_keepo = 0;

@@ -57,6 +57,10 @@ struct TdMolMate {
 	const int64_t* offs = nullptr;
 	int64_t reads = 0;
 	KtEventPair ev;                           // around the mate kernel of the last staged mate batch (option "mate_kernel_us")
+	// the mate filter (td_mol_mate_filter_enable): the mates are judged as TD_MODE_RNA_DUST judges and the verdict joined to the read's
+	bool filter = false;
+	KtEventPair ev_filter;                    // around the filter kernel of the last staged mate batch (option "mate_filter_kernel_us")
+	KtEventPair ev_join;                      // around the join kernel of the last decoded batch (option "mate_join_kernel_us")
 };
 struct TdMolState {
 	bool on = false;
@@ -106,11 +110,14 @@ __attribute__((visibility("hidden"))) int mol_slot_decoded(td_ctx* c, TdSlot& s,
 // Mate mode, inside slot_stage.  mol_mate_stage: the mate batch td_mol_mate_next named goes into the slot with the batch's own input, its
 // copies queued on `up` in front of the upload event (the named batch is consumed).  mol_mate_launch: the mate kernel over it on the
 // slot's aux stream, behind the upload event and in front of ev_pack.  mol_mate_check: TD_FAIL with a message (`who` in it) unless a
-// mate batch of n reads is named; a wrong one is dropped.
+// mate batch of n reads is named; a wrong one is dropped.  With the mate filter on mol_mate_launch queues the filter kernel
+// (td_mate_filter.hip) behind the mate kernel when dust or artifacts are set, and mol_mate_join, called by launch_end in front of
+// everything that reads a TD_MODE_GET_LABEL batch's outcomes, queues the join on the slot's compute stream.
 __attribute__((visibility("hidden"))) int mol_mate_check(td_ctx* c, int64_t n, const char* who);
 __attribute__((visibility("hidden"))) int mol_mate_stage(td_ctx* c, TdSlot& s, int64_t n, hipStream_t up);
 __attribute__((visibility("hidden"))) int mol_mate_launch(td_ctx* c, TdSlot& s, int64_t n);
-// The "*_kernel_us" options of td_get_option that belong here -- molecules_, dedup_, collapse_origin_, dedup_replay_ and mate_: the time
+__attribute__((visibility("hidden"))) int mol_mate_join(td_ctx* c, TdSlot& s, int32_t* out_type);
+// The "*_kernel_us" options of td_get_option that belong here -- molecules_, dedup_, collapse_origin_, dedup_replay_, mate_, mate_filter_ and mate_join_: the time
 // between the stage's two events of the last batch (waits for it).  TD_OK, TD_FAIL with the message, or -1: `name` is none of them.
 __attribute__((visibility("hidden"))) int mol_kernel_us(td_ctx* c, const char* name, int32_t* us);
 // table and label copy freed, count off (the caller has made sure nothing of it is queued any more)

@@ -32,7 +32,10 @@
 // Mate mode (td_mol_mate_enable) joins the first M bases of every read's mate, a read of a second file, into the key.  The mate batch
 // travels with the batch's own input on the same upload stream into the batch's slot; the mate kernel, one mate per lane on the
 // slot's aux stream between the upload event and ev_pack, turns it into a word and a byte per read in the caller's order, and
-// mol_lane_key appends them behind the label walk.  The mates are not decoded: their outcome takes no part.
+// mol_lane_key appends them behind the label walk.  The mates are not decoded, and their outcome takes no part -- unless the mate
+// filter is on (td_mol_mate_filter_enable): then the filter kernel of td_mate_filter.hip follows the mate kernel on the same stream and
+// judges every mate as TD_MODE_RNA_DUST would, and a join kernel behind the decode launch raises every read's outcome to its mate's
+// before the -ref hit count, the census, the count and dedup read it (mol_mate_join, called by td_batch.hip's launch_end).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -42,6 +45,7 @@
 
 #include "../../include/tagdust_molecules.h"
 #include "td_ctx.h"
+#include "td_mate_filter.h"
 
 // The head of the three kernels with a tile per wave.  s_r[128], per label: 1 = it belongs to an 'R' segment (the whole workgroup;
 // ends in its barrier, in front of any wave that leaves); then the lane and the wave's tile.  false: the wave has no tile.
@@ -435,7 +439,9 @@ void mol_release(td_ctx* c)
 	dedup_release(z);
 	collapse_release(z);
 	kt_pair_destroy(z.mate.ev);
-	z = TdMolState();                                 // (mate mode off with it, a named mate batch forgotten)
+	kt_pair_destroy(z.mate.ev_filter);
+	kt_pair_destroy(z.mate.ev_join);
+	z = TdMolState();                                 // (mate mode and the mate filter off with it, a named mate batch forgotten)
 }
 
 // A decoded slot's launches, queued on its compute stream: the count, then the collapse's origin pass, then dedup's two passes, each
@@ -566,7 +572,44 @@ extern "C" int td_mol_mate_disable(td_ctx* c)
 	if (tickets_outstanding(c)) return fail(c, "td_mol_mate_disable: td_submit tickets are outstanding (td_wait them first)");
 	z.mate.bases = 0;
 	z.mate.named = false;
+	z.mate.filter = false;                            // (the filter judges mates: it goes with them)
 	return td_mol_reset(c);
+}
+
+// ---- the mate filter ----
+static int mate_filter_switch(td_ctx* c, bool on, const char* who)
+{
+	if (!c) return fail(nullptr, "%s: no context", who);
+	TdMolState& z = c->molecules;
+	if (!z.on || z.mate.bases == 0) return fail(c, "%s: mate mode is off (td_mol_mate_enable first): the filter judges the mates of a batch", who);
+	if (tickets_outstanding(c)) return fail(c, "%s: td_submit tickets are outstanding (td_wait them first)", who);
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
+	if (on && !z.mate.ev_filter.e0) HIPCHK(c, kt_pair_create(z.mate.ev_filter));   // (the pairs outlive the switch: the count's release destroys them)
+	if (on && !z.mate.ev_join.e0) HIPCHK(c, kt_pair_create(z.mate.ev_join));
+	z.mate.filter = on;
+	z.mate.named = false;
+	return td_mol_reset(c);   // a table never holds counts made under two eligibility rules
+}
+
+extern "C" int td_mol_mate_filter_enable(td_ctx* c) { return mate_filter_switch(c, true, "td_mol_mate_filter_enable"); }
+extern "C" int td_mol_mate_filter_disable(td_ctx* c) { return mate_filter_switch(c, false, "td_mol_mate_filter_disable"); }
+
+extern "C" int td_mol_mate_types(td_ctx* c, int32_t* types, int64_t cap, int64_t* n)
+{
+	if (!c) return fail(nullptr, "td_mol_mate_types: no context");
+	if (!n || cap < 0 || (!types && cap > 0)) return fail(c, "td_mol_mate_types: bad arguments");
+	const TdMolState& z = c->molecules;
+	if (!z.mate.filter) return fail(c, "td_mol_mate_types: the mate filter is off (td_mol_mate_filter_enable)");
+	const TdSlot& s = c->slots[0];
+	if (!s.staged || s.mate_m == 0 || !s.mate_judged)
+		return fail(c, "td_mol_mate_types: no batch is resident that was staged with its mates while the filter was on (td_mol_mate_next, then td_batch_upload)");
+	if (wait_compute(c) != TD_OK) return TD_FAIL;
+	*n = s.n_reads;
+	const int64_t m = s.n_reads < cap ? s.n_reads : cap;
+	if (m <= 0) return TD_OK;
+	if (!s.mate_typed) { memset(types, 0, (size_t)m * sizeof(int32_t)); return TD_OK; }   // neither DUST nor artifacts: the kernel did not run
+	HIPCHK(c, hipMemcpy(types, s.d_mate_type, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+	return TD_OK;
 }
 
 extern "C" int td_mol_mate_next(td_ctx* c, const uint8_t* codes, const int64_t* offs, int64_t n_reads)
@@ -608,7 +651,9 @@ int mol_mate_stage(td_ctx* c, TdSlot& s, int64_t n, hipStream_t up)
 		s.h_mate_offs[i + 1] = offs[i + 1] - base;
 	}
 	const int64_t n_bases = n > 0 ? offs[n] - base : 0;
-	if (ensure(c, &s.d_mate_raw, &s.cap_mate_raw, (size_t)n_bases) != TD_OK || ensure(c, &s.d_mate_offs, &s.cap_mate_offs, (size_t)(n + 1) * 8) != TD_OK ||
+	// (the filter kernel loads whole dwords: the bytes up to the next multiple of 4 belong to the allocation, nobody uses their values)
+	const size_t raw_bytes = z.filter ? ((size_t)n_bases + 3) & ~(size_t)3 : (size_t)n_bases;
+	if (ensure(c, &s.d_mate_raw, &s.cap_mate_raw, raw_bytes) != TD_OK || ensure(c, &s.d_mate_offs, &s.cap_mate_offs, (size_t)(n + 1) * 8) != TD_OK ||
 	    ensure(c, &s.d_mate_w, &s.cap_mate_w, (size_t)n * 8) != TD_OK || ensure(c, &s.d_mate_n, &s.cap_mate_n, (size_t)n) != TD_OK)
 		return TD_FAIL;
 	// host -> device as the batch's own bases go: page-locked caller memory straight to the DMA engine, anything else through pinned staging
@@ -635,6 +680,33 @@ int mol_mate_launch(td_ctx* c, TdSlot& s, int64_t n)
 		HIPCHK(c, hipGetLastError());
 	}
 	HIPCHK(c, hipEventRecord(z.ev.e1, s.aux));
+	if (!z.filter) return TD_OK;
+	// The mate filter: the mates judged under the context's settings as they stand now.  Without DUST and artifacts every verdict is
+	// 0: no launch, no buffer, and the join is left out as well.
+	s.mate_judged = true;
+	if (c->dust == 0 && c->art_n == 0) return TD_OK;
+	if (ensure(c, &s.d_mate_type, &s.cap_mate_type, (size_t)n * sizeof(int32_t)) != TD_OK) return TD_FAIL;
+	TdMateFilterArgs fa{};
+	fa.raw = s.d_mate_raw; fa.offs = s.d_mate_offs; fa.n_reads = n; fa.dust = c->dust;
+	fa.art_pk = c->d_art_pk; fa.art_seq = c->d_art_seq; fa.art_n = c->art_n; fa.art_fe = c->art_fe;
+	fa.art_threads = c->art_threads; fa.win_first = c->win_first; fa.win_total = c->win_total;
+	fa.mate_type = s.d_mate_type;
+	HIPCHK(c, hipEventRecord(z.ev_filter.e0, s.aux));
+	HIPCHK(c, td_launch_mate_filter(fa, s.aux));
+	HIPCHK(c, hipEventRecord(z.ev_filter.e1, s.aux));
+	s.mate_typed = true;
+	return TD_OK;
+}
+
+// out_type[k] = max(out_type[k], the type of read k's mate) on the slot's compute stream: behind ev_k1, in front of the -ref hit
+// count, the census and the count.  (The stream's wait for ev_pack covers the filter kernel.)
+int mol_mate_join(td_ctx* c, TdSlot& s, int32_t* out_type)
+{
+	const TdMolMate& z = c->molecules.mate;
+	if (!s.mate_typed) return TD_OK;                  // (every mate type is 0, and no outcome is below 0)
+	HIPCHK(c, hipEventRecord(z.ev_join.e0, s.cs));
+	HIPCHK(c, td_launch_mate_join(out_type, s.d_mate_type, s.sorted ? s.d_read_at : nullptr, s.n_reads, s.cs));
+	HIPCHK(c, hipEventRecord(z.ev_join.e1, s.cs));
 	return TD_OK;
 }
 
@@ -918,6 +990,10 @@ static const struct {
 	  "td_get_option: dedup_replay_kernel_us: no batch has been replayed yet" },
 	{ "mate_kernel_us", [](const TdMolState& z) -> const KtEventPair& { return z.mate.ev; }, [](const TdMolState& z) { return z.mate.bases != 0; },
 	  "td_get_option: mate_kernel_us: mate mode is off", "td_get_option: mate_kernel_us: no mate batch has been staged yet" },
+	{ "mate_filter_kernel_us", [](const TdMolState& z) -> const KtEventPair& { return z.mate.ev_filter; }, [](const TdMolState& z) { return z.mate.filter; },
+	  "td_get_option: mate_filter_kernel_us: the mate filter is off", "td_get_option: mate_filter_kernel_us: no mate batch has been judged yet" },
+	{ "mate_join_kernel_us", [](const TdMolState& z) -> const KtEventPair& { return z.mate.ev_join; }, [](const TdMolState& z) { return z.mate.filter; },
+	  "td_get_option: mate_join_kernel_us: the mate filter is off", "td_get_option: mate_join_kernel_us: no batch has been joined yet" },
 };
 
 int mol_kernel_us(td_ctx* c, const char* name, int32_t* us)

@@ -170,7 +170,7 @@ struct OptSpec { const char* name; int arg; int id; };
 enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
        O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS, O_DEDUP, O_COLLAPSE,
-       O_DEDUP_COLLAPSED, O_MATE_BASES, O_UNSUPPORTED = 100 };
+       O_DEDUP_COLLAPSED, O_MATE_BASES, O_MATE_FILTER, O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
 	{ "7", 1, O_SEG + 6 }, { "8", 1, O_SEG + 7 }, { "9", 1, O_SEG + 8 }, { "10", 1, O_SEG + 9 },
@@ -196,7 +196,7 @@ const OptSpec kOwnOpts[] = {
 	{ "unknown-barcodes", 1, O_UNKNOWN }, { "unknown-barcodes-slots", 1, O_UNKNOWN_SLOTS },
 	{ "fingerprint-seq", 0, O_FINGER_SEQ }, { "molecules", 0, O_MOLECULES }, { "molecules-prefix", 1, O_MOLECULES_PREFIX },
 	{ "molecules-slots", 1, O_MOLECULES_SLOTS }, { "dedup", 0, O_DEDUP }, { "collapse-umis", 0, O_COLLAPSE },
-	{ "dedup-collapsed", 0, O_DEDUP_COLLAPSED }, { "mate-bases", 1, O_MATE_BASES },
+	{ "dedup-collapsed", 0, O_DEDUP_COLLAPSED }, { "mate-bases", 1, O_MATE_BASES }, { "mate-filter", 0, O_MATE_FILTER },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -302,7 +302,9 @@ extern "C" const char* td_run_usage(void)
 	       "\t--mate-bases M              two or more input files: the first M bases of the read's mate, the record of the first other\n"
 	       "\t                            file, belong to a molecule's identity behind the read's own --molecules-prefix bases, 1..31,\n"
 	       "\t                            both at most 32 together (implies --molecules; one file with an architecture other than R:N,\n"
-	       "\t                            one device, -dust 0, no -ref)\n\n";
+	       "\t                            one device, -dust 0, no -ref)\n"
+	       "\t--mate-filter               with --mate-bases and two input files: DUST and the -ref filter judge the mate as well, and a\n"
+	       "\t                            read whose mate fails is neither counted nor kept by --dedup (lifts -dust 0 / no -ref)\n\n";
 }
 
 extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
@@ -379,6 +381,7 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 			o->mate_bases = atoi(v);
 			if (o->mate_bases < 1 || o->mate_bases > TD_MOL_MAX_PREFIX - 1) return bad("--mate-bases: need 1..31 bases of the mate");
 			break;
+		case O_MATE_FILTER: o->mate_filter = 1; break;
 		default: return bad("unknown option " + a);
 		}
 	}
@@ -417,6 +420,8 @@ struct td_run_plan_t {
 	bool collapse = false;
 	bool dedup_collapsed = false;
 	int mate_bases = 0;                      // --mate-bases: 0 = off
+	bool mate_filter = false;                // --mate-filter
+	std::string ref_file;                    // -ref, for the plan's "mate:" line
 	int mol_file = 0, mate_file = -1;        // ... the one decoded file and its mate, once every architecture is known
 };
 
@@ -429,6 +434,17 @@ std::vector<std::string> cmdline_segments(const td_run_opts* o)
 	std::vector<std::string> s;
 	for (int k = 0; k <= last; k++) s.push_back(o->segments[k] ? o->segments[k] : "");
 	return s;
+}
+
+// --mate-filter with DUST or -ref: the outcome of one mate is joined on the device, a third file's is not (mol / mate: decide_outputs')
+int mate_filter_files(const td_run_opts* o, int dust, bool use_ref, int mol, int mate)
+{
+	if (!o->mate_filter || o->n_infiles < 3 || (dust == 0 && !use_ref)) return TD_OK;
+	int third = 0;
+	while (third == mol || third == mate) third++;
+	return run_fail("--mate-filter with DUST or -ref takes exactly two input files (%d given): the outcome of %s would be joined behind the count, "
+	                "where a failing read takes a molecule's one kept read out of the files: run with -dust 0 and without -ref, or without that file.",
+	                o->n_infiles, o->infile[third]);
 }
 
 std::string unknown_file_name(const td_run_opts* o) { return std::string(o->outfile) + "_unknown_barcodes.txt"; }
@@ -507,6 +523,8 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 		if (o->dedup_collapsed)
 			return run_fail("--mate-bases cannot be combined with --dedup-collapsed: the survey reads one file.");
 	}
+	if (o->mate_filter && !o->mate_bases)
+		return run_fail("--mate-filter needs --mate-bases: it judges the mate that --mate-bases joins to its read.");
 	if (o->molecules && !o->mate_bases && o->n_infiles != 1)
 		return run_fail("--molecules needs exactly one input file (%d given): a read and its fingerprint in different files are not joined.", o->n_infiles);
 	if (o->molecules && (o->matchstart != -1 || o->matchend != -1))
@@ -535,7 +553,9 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 		p->use_ref = false;
 	}
 	p->mate_bases = o->mate_bases;
-	if (o->mate_bases && (p->dust != 0 || p->use_ref))
+	p->mate_filter = o->mate_filter != 0;
+	if (p->use_ref) p->ref_file = o->reference_fasta;
+	if (o->mate_bases && !o->mate_filter && (p->dust != 0 || p->use_ref))
 		return run_fail("--mate-bases: the mate is not decoded and its outcome is not joined to the count, so a mate that DUST or the -ref filter "
 		                "rejects would take a molecule's one kept read out of the files: run with -dust 0 and without -ref.");
 	if (p->use_ref && !file_exists(o->reference_fasta)) return run_fail("ERROR: Reference file:%s does not exists.", o->reference_fasta);
@@ -563,6 +583,7 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	std::vector<const td_arch*> view;
 	for (auto& a : archs) view.push_back(a.get());
 	if (p->all_known && decide_outputs(o, view, p->bar_file, p->num_out_reads, p->out_files, &p->mol_file, &p->mate_file) != TD_OK) return TD_FAIL;
+	if (p->all_known && mate_filter_files(o, p->dust, p->use_ref, p->mol_file, p->mate_file) != TD_OK) return TD_FAIL;
 	*out = p.release();
 	return TD_OK;
 }
@@ -588,7 +609,10 @@ extern "C" int64_t td_run_plan_describe(const td_run_plan_t* p, char* buf, int64
 	if (p->dedup_collapsed)
 		s += "dedup-collapsed: the input is read twice, a survey and then the run: one read per collapsed molecule is written, the first that carries the root's barcode, fingerprint and start\n";
 	if (p->mate_bases) {
-		s += "mate: " + std::to_string(p->mate_bases) + " bases of the mate join the molecule key behind the read's own prefix; the mate's own outcome takes no part";
+		s += "mate: " + std::to_string(p->mate_bases) + " bases of the mate join the molecule key behind the read's own prefix; ";
+		if (!p->mate_filter) s += "the mate's own outcome takes no part";
+		else s += "mate filter on: the mate is judged with dust " + std::to_string(p->dust) + " and -ref " + (p->use_ref ? p->ref_file : std::string("none")) +
+		          ", and its outcome is joined to the read's in front of the count";
 		if (p->all_known) s += " (file " + std::to_string(p->mol_file) + " is decoded, file " + std::to_string(p->mate_file) + " is its mate)";
 		s += "\n";
 	}
@@ -908,7 +932,8 @@ int Run::execute()
 	{
 		std::vector<const td_arch*> view;
 		for (auto& f : files) view.push_back(f.arch.get());
-		if (decide_outputs(o, view, bar_file, num_out_reads, out_files, &mol_file, &mate_file) != TD_OK) { log.add(g_run_error + "\n"); return TD_FAIL; }
+		if (decide_outputs(o, view, bar_file, num_out_reads, out_files, &mol_file, &mate_file) != TD_OK ||
+		    mate_filter_files(o, dust, use_ref, mol_file, mate_file) != TD_OK) { log.add(g_run_error + "\n"); return TD_FAIL; }
 	}
 
 	// 2. sequence statistics over the head of every file, io.c:52-300
@@ -1002,6 +1027,8 @@ int Run::execute()
 			if (o->collapse_umis && td_mol_collapse_enable(c) != TD_OK) return fail("%s", td_last_error(c));
 			// --mate-bases: ... and take the first bases of every read's mate into the key (td_stream_run_multi names the mate batches)
 			if (o->mate_bases && td_mol_mate_enable(c, o->mate_bases) != TD_OK) return fail("%s", td_last_error(c));
+			// --mate-filter: ... and judge every mate with this context's DUST and -ref, its outcome joined to the read's in front of the count
+			if (o->mate_filter && td_mol_mate_filter_enable(c) != TD_OK) return fail("%s", td_last_error(c));
 		}
 	}
 	rep->compile_wait_s = now_s() - t0;
@@ -1158,6 +1185,7 @@ int Run::molecules()
 	fprintf(out, "# molecules: the extracted reads of %s by barcode, fingerprint and the first bases of the read\n", o->infile[mol_file]);
 	fprintf(out, "# prefix bases\t%d\n", o->molecules_prefix);
 	if (o->mate_bases) fprintf(out, "# mate bases\t%d\n# mate file\t%s\n", o->mate_bases, o->infile[mate_file]);
+	if (o->mate_filter) fprintf(out, "# mate filter\tdust %d, -ref %s\n", dust, use_ref ? o->reference_fasta : "none");
 	fprintf(out, "# extracted reads\t%lld\n# counted\t%lld\n# molecules\t%lld\n# no read base\t%lld\n# N in the prefix\t%lld\n",
 	        (long long)sum.eligible, (long long)sum.counted, (long long)sum.molecules, (long long)sum.skipped_empty, (long long)sum.skipped_n);
 	if (sum.overflow > 0)

@@ -295,6 +295,7 @@ struct MultiPlan {
 	std::vector<char> rna;            // run_rna_dust on the file's devices (TD_MODE_RNA_DUST)
 	// pair mode (tagdust_molecules.h, mate mode): the contexts of the one decoded file report mate_bases > 0
 	int mol_file = -1, mate_file = -1;   // the decoded file and its mate: the first file in call order other than it (-1: no pair mode)
+	bool mate_filter = false;            // ... and its contexts report "mate_filter": the mate's outcome is joined on the device
 };
 
 // false: the files cannot make a run (td_io_set_error says why)
@@ -331,17 +332,6 @@ bool plan_multi(const td_stream_file* files, const int K, const int N, const int
 			}
 		}
 	}
-	// -ref (hmm_controller_multiple, barcode_hmm.c:209-214, :313-325): the controller hands the one FASTA to every file's step
-	if (m.n_art > 0) {
-		for (int k = 0; k < K; k++) {
-			if (!files[k].ctx) {
-				td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set, but ") + files[k].path +
-				                " (R:N) has no contexts: its reads must be filtered too (give it contexts: TD_MODE_RNA_DUST)");
-				return false;
-			}
-			if (!artifacts_active(files[k].ctx[0])) { td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set for some files but not for ") + files[k].path); return false; }
-		}
-	}
 	// pair mode: a decoded file whose contexts are in mate mode takes the first other file's batches as its mate batches
 	int n_decoded = 0, decoded = -1;
 	for (int k = 0; k < K; k++) {
@@ -350,6 +340,35 @@ bool plan_multi(const td_stream_file* files, const int K, const int N, const int
 		int32_t mb = 0;
 		(void)td_get_option(files[k].ctx[0], "mate_bases", &mb);
 		if (mb > 0 && decoded < 0) decoded = k;
+	}
+	int32_t mate_dust = 0;
+	if (decoded >= 0) {
+		int32_t mf = 0;
+		(void)td_get_option(files[decoded].ctx[0], "mate_filter", &mf);
+		(void)td_get_option(files[decoded].ctx[0], "dust", &mate_dust);
+		m.mate_filter = mf != 0;
+	}
+	const int mate = decoded < 0 ? -1 : (decoded == 0 ? 1 : 0);
+	// the mate filter (tagdust_molecules.h): one mate's outcome is joined in front of the count, a third file's would come behind it
+	if (m.mate_filter && K >= 3 && (m.n_art > 0 || dust != 0 || mate_dust != 0)) {
+		int third = 0;
+		while (third == decoded || third == mate) third++;
+		td_io_set_error(std::string("td_stream_run_multi: the mate filter is on with a -ref filter or DUST and ") + std::to_string(K) + " files are given: the outcome of " +
+		                files[third].path + " would be joined behind the count, so a read of it that could fail would take a molecule's one kept read out of "
+		                "the files (two files, or dust 0 and no filter)");
+		return false;
+	}
+	// -ref (hmm_controller_multiple, barcode_hmm.c:209-214, :313-325): the controller hands the one FASTA to every file's step
+	if (m.n_art > 0) {
+		for (int k = 0; k < K; k++) {
+			if (m.mate_filter && k == mate) continue;   // (the decoded file's contexts filter its reads as their mates)
+			if (!files[k].ctx) {
+				td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set, but ") + files[k].path +
+				                " (R:N) has no contexts: its reads must be filtered too (give it contexts: TD_MODE_RNA_DUST)");
+				return false;
+			}
+			if (!artifacts_active(files[k].ctx[0])) { td_io_set_error(std::string("td_stream_run_multi: a -ref artifact filter is set for some files but not for ") + files[k].path); return false; }
+		}
 	}
 	if (decoded >= 0) {
 		if (N > 1) { td_io_set_error("td_stream_run_multi: mate mode is on and " + std::to_string(N) + " devices are given: a mate batch travels with its reads to one context (one device)"); return false; }
@@ -365,15 +384,19 @@ bool plan_multi(const td_stream_file* files, const int K, const int N, const int
 				return false;
 			}
 		}
-		int32_t cd = 0;
-		(void)td_get_option(files[decoded].ctx[0], "dust", &cd);
-		if (m.n_art > 0 || dust != 0 || cd != 0) {
+		const int32_t cd = mate_dust;
+		if (m.mate_filter && cd != dust) {   // (the decoded file's contexts run the DUST of this call over the mates)
+			td_io_set_error(std::string("td_stream_run_multi: the mate filter is on and ") + files[decoded].path + " has contexts with dust " + std::to_string(cd) +
+			                ", the call has dust " + std::to_string(dust));
+			return false;
+		}
+		if (!m.mate_filter && (m.n_art > 0 || dust != 0 || cd != 0)) {
 			td_io_set_error("td_stream_run_multi: mate mode is on with a -ref filter or DUST: the mate's own outcome is not joined to the count, so a mate "
 			                "that could fail would take a molecule's one kept read out of the files (run with dust 0 and without a filter)");
 			return false;
 		}
 		m.mol_file = decoded;
-		m.mate_file = decoded == 0 ? 1 : 0;
+		m.mate_file = mate;
 	}
 	if (m.num_out_reads == 0) { td_io_set_error("td_stream_run_multi: no read segment in any architecture: no output files to create (io.c:846-852)"); return false; }
 	return true;
@@ -447,6 +470,8 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 					memset(&r, 0, sizeof r);
 					r.mapq = -1.0f; r.barcode = -1; r.fingerprint = -1;        // read_fasta_fastq's defaults, io.c:1698-1702
 					r.read_type = TD_EXTRACT_SUCCESS;
+					// (the mate filter: the device has judged this file's reads as mates, and the decoded record carries the maximum)
+					if (m.mate_filter && k == m.mate_file) continue;
 					if (dust && rna_dust_low(b->codes + b->offs[i], b->offs[i + 1] - b->offs[i], dust)) r.read_type = TD_EXTRACT_FAIL_LOW_COMPLEXITY;
 				}
 			});

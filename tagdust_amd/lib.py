@@ -57,7 +57,8 @@ MOL_ABI_SYMBOLS = ["td_mol_enable", "td_mol_disable", "td_mol_reset", "td_mol_en
                    "td_mol_collapse_enable", "td_mol_collapse_disable", "td_mol_origins", "td_mol_collapse_get", "td_mol_collapse_entries",
                    "td_mol_host_origins", "td_mol_collapse_host", "td_mol_dedup_freeze", "td_mol_dedup_collapsed_host",
                    "td_mol_mate_enable", "td_mol_mate_disable", "td_mol_mate_next", "td_mol_host_mated", "td_mol_host_origins_mated",
-                   "td_mol_dedup_host_mated", "td_mol_dedup_collapsed_host_mated"]
+                   "td_mol_dedup_host_mated", "td_mol_dedup_collapsed_host_mated",
+                   "td_mol_mate_filter_enable", "td_mol_mate_filter_disable", "td_mol_mate_types"]
 MOL_TOTALS = ("eligible", "counted", "skipped_empty", "skipped_n", "overflow", "molecules")
 MOL_DEDUP_TOTALS = ("kept", "duplicates", "unjudged")
 MOL_COLLAPSE_TOTALS = ("molecules_before", "molecules_after", "absorbed", "longest_chain")
@@ -623,7 +624,7 @@ class _RunOpts(C.Structure):
 class _RunOptsMate(C.Structure):
     """td_run_opts (include/tagdust_run.h) as it is now: _RunOpts -- whose last field tests/test_dedup_collapsed.py pins -- and the
     field appended behind it; this is the structure every td_run_* call is given"""
-    _fields_ = _RunOpts._fields_ + [("mate_bases", C.c_int32)]
+    _fields_ = _RunOpts._fields_ + [("mate_bases", C.c_int32), ("mate_filter", C.c_int32)]
 
 
 class _CensusTotals(C.Structure):
@@ -912,6 +913,9 @@ def _mol_lib():
     lib.td_mol_mate_enable.argtypes = [C.c_void_p, C.c_int32]
     lib.td_mol_mate_disable.argtypes = [C.c_void_p]
     lib.td_mol_mate_next.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.td_mol_mate_filter_enable.argtypes = [C.c_void_p]
+    lib.td_mol_mate_filter_disable.argtypes = [C.c_void_p]
+    lib.td_mol_mate_types.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     mate = C.POINTER(_MolMate)
     lib.td_mol_host_mated.argtypes = lib.td_mol_host.argtypes[:7] + [mate] + lib.td_mol_host.argtypes[7:]
     lib.td_mol_host_origins_mated.argtypes = lib.td_mol_host_origins.argtypes[:7] + [mate] + lib.td_mol_host_origins.argtypes[7:]
@@ -1204,6 +1208,10 @@ class TagdustHip:
     def set_window(self, matchstart=-1, matchend=-1):
         self._chk(self.lib.td_set_window(self.h, int(matchstart), int(matchend)))
 
+    def set_batch_window(self, first_read=0, total_reads=0):
+        """td_set_batch_window: the batches that follow are reads first_read.. of a batch of total_reads (0, 0: whole batches)"""
+        self._chk(self.lib.td_set_batch_window(self.h, int(first_read), int(total_reads)))
+
     def upload_batch(self, codes, offs):
         codes = np.ascontiguousarray(codes, np.uint8)
         self.offs = np.ascontiguousarray(offs, np.int64)
@@ -1298,6 +1306,23 @@ class TagdustHip:
         views; kept alive here until the next call, by the caller as long as the batch's own input)"""
         self._mate = (np.ascontiguousarray(codes, np.uint8) if len(codes) else np.zeros(1, np.uint8), np.ascontiguousarray(offs, np.int64))
         self._chk(_mol_lib().td_mol_mate_next(self.h, self._mate[0].ctypes.data, self._mate[1].ctypes.data, len(self._mate[1]) - 1))
+
+    def mol_mate_filter_enable(self):
+        """td_mol_mate_filter_enable: from now on every mate is judged as MODE_RNA_DUST judges (this context's dust, artifacts and
+        thread ranges) and a read's outcome is the maximum of its own and its mate's (an empty table)"""
+        self._chk(_mol_lib().td_mol_mate_filter_enable(self.h))
+
+    def mol_mate_filter_disable(self):
+        self._chk(_mol_lib().td_mol_mate_filter_disable(self.h))
+
+    def mol_mate_types(self):
+        """td_mol_mate_types: the mate types of the resident batch in the caller's order (int32)"""
+        lib = _mol_lib()
+        n = C.c_int64()
+        self._chk(lib.td_mol_mate_types(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.int32)
+        self._chk(lib.td_mol_mate_types(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value]
 
     def mol_dedup_enable(self):
         """td_mol_dedup_enable: from now on a read that is not the first of its molecule gets read_type EXTRACT_DUPLICATE"""

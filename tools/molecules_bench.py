@@ -90,6 +90,27 @@ written down before the first run:
   4. host to host: no expectation set in advance.  The decode kernel bounds the pipeline and the upload runs beside it, so the
      doubled copy may not show at all; if the loss is more than the extra copy's bytes explain, the next step is to copy only the
      first M bytes of each mate (not built here).
+
+The mate filter (td_mol_mate_filter_enable: the mate judged by DUST and -ref, its outcome joined to the read's in front of the count)
+has a mode of its own, --mate-filter, which adds a "mate_filter" section to the same file and measures nothing else:
+
+    python tools/molecules_bench.py --mate-filter
+
+The mate workload above (2^20 reads with a 150-base mate, P = 12, M = 20) with -dust 100 and 16 artifact sequences of 100 nt
+(tools/rna_dust_bench.py's), n_threads 16, set on the context in both states, so that the read's own filter costs the same in both
+and the difference is the mate's.  Per batch: the filter kernel (option "mate_filter_kernel_us") and the join kernel
+("mate_join_kernel_us") from HIP events, median and range of 5 batches behind one that is discarded; beside them td_rna_dust_kernel
+over the same mates as a batch of their own in a second context of the same process (td_last_kernel_ms), the same way -- that kernel
+does the same arithmetic from packed tiles and is the yardstick.  Host to host: td_submit / td_wait with the filter off and on in
+turn in one process, two passes of each after a first pass that is discarded.  Expectation, written down before the first run:
+  1. the filter kernel runs td_rna_dust_kernel's columns -- 16 sequences x 101 characters x 2 strands per mate, 2.7 ms per 2^20 reads
+     when that kernel was measured on this filter -- and stages 150 B per mate through LDS (157 MB as coalesced dwords: 40-50 us at
+     HBM rate) where that kernel reads 56 B of packed words: within 10 % of the yardstick, 2.7-3.0 ms.  It holds 93 VGPRs and
+     32 KiB of LDS per workgroup (5 waves per SIMD, the yardstick 8); the columns are VALU-bound, so that should not show;
+  2. the join kernel moves 12 B per read (two loads, one store, the batch is of one length: all coalesced): 12 MiB, 5-10 us, the
+     price of a launch;
+  3. host to host: the filter kernel runs on the slot's high-priority aux stream beside the decode kernel of the batch before, whose
+     compute units it takes while it runs: a loss of up to filter / decode kernel time, no more.  No threshold is set.
 """
 import argparse
 import json
@@ -390,6 +411,87 @@ def measure_mate(ctx, seq, offs, n, mseq, moffs):
     return out
 
 
+def measure_mate_filter(ctx, seq, offs, n, mseq, moffs, device):
+    """the mate filter: its two kernels per batch beside td_rna_dust_kernel over the same mates, then host to host on against off"""
+    from tagdust_amd import RESULT_DTYPE, TagdustHip
+    from tagdust_amd import lib as tdlib
+    import rna_dust_bench
+    string, s_index, _ = tdlib.parse_fasta(rna_dust_bench.artifact_fasta(16))
+    T = 16
+    out = {"prefix_bases": MATE_PREFIX, "mate_bases": MATE_BASES, "mate_len": MATE_LEN, "dust": 100, "n_artifacts": 16, "artifact_len": 100,
+           "n_threads": T, "box_to_box_spread": "+-7 % between machines of the pool: a ratio below that is no finding"}
+    med = statistics.median
+    spread = lambda v: {"runs": [round(x, 3) for x in v], "median": round(med(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+    ctx.set_artifacts(string, s_index, 2, T)
+    ctx.mol_enable(MATE_PREFIX, LOG2_SLOTS)
+    ctx.mol_mate_enable(MATE_BASES)
+    ctx.mol_mate_filter_enable()
+    dec, cnt, mk, fk, jk = [], [], [], [], []
+    for it in range(6):
+        ctx.mol_reset()
+        ctx.mol_mate_next(mseq, moffs)
+        ctx.upload_batch(seq, offs)
+        ctx.run()
+        dec.append(ctx.last_kernel_ms())
+        cnt.append(ctx.get_option("molecules_kernel_us") / 1000.0)
+        mk.append(ctx.get_option("mate_kernel_us") / 1000.0)
+        fk.append(ctx.get_option("mate_filter_kernel_us") / 1000.0)
+        jk.append(ctx.get_option("mate_join_kernel_us") / 1000.0)
+        if it == 0:
+            t2 = ctx.mol_mate_types()
+            out["mate_types_of_one_batch"] = {"passed": int((t2 == 0).sum()), "low_complexity": int((t2 == 6).sum()),
+                                              "matches_artifact": int(((t2 & 0xFF) == 5).sum())}
+            out["totals_of_one_batch"] = ctx.mol_get()[1]
+    out["decode_kernel_ms"], out["count_kernel_ms"], out["mate_kernel_ms"] = spread(dec[1:]), spread(cnt[1:]), spread(mk[1:])
+    out["filter_kernel_ms"], out["join_kernel_ms"] = spread(fk[1:]), spread(jk[1:])
+    ctx.mol_disable()
+    # the yardstick: td_rna_dust_kernel over the same mates as a batch of their own, same settings, same process
+    rd = TagdustHip(device)
+    try:
+        rd.set_params(0.0, 16, 100)
+        rd.set_artifacts(string, s_index, 2, T)
+        res = np.zeros(n, RESULT_DTYPE)
+        ms = []
+        for it in range(6):
+            rd.wait(rd.submit(mseq, moffs, mode=tdlib.MODE_RNA_DUST, res=res))
+            ms.append(rd.last_kernel_ms())
+        out["rna_dust_kernel_ms_same_mates"] = spread(ms[1:])
+        out["rna_dust_mode_equals_mate_types"] = bool(np.array_equal(res["read_type"], t2))
+    finally:
+        rd.close()
+    out["filter_over_rna_dust_kernel"] = round(out["filter_kernel_ms"]["median"] / out["rna_dust_kernel_ms_same_mates"]["median"], 3)
+    out["filter_kernel_share_of_decode"] = round(out["filter_kernel_ms"]["median"] / out["decode_kernel_ms"]["median"], 4)
+    # host to host: the first pass of the process is discarded, then the filter off and on in turn, twice each
+    res = [np.zeros(n, RESULT_DTYPE) for _ in range(2)]
+    rates = {"discarded_first_pass": [], "filter_on": [], "filter_off": []}
+    for k, state in enumerate(("filter_off", "filter_on", "filter_off", "filter_on", "filter_off")):
+        ctx.mol_enable(MATE_PREFIX, LOG2_SLOTS)
+        ctx.mol_mate_enable(MATE_BASES)
+        if state == "filter_on":
+            ctx.mol_mate_filter_enable()
+
+        def submit(r):
+            ctx.mol_mate_next(mseq, moffs)
+            return ctx.submit(seq, offs, res=r)
+
+        steps = 4
+        for t in [submit(r) for r in res]:                         # warm-up: both slots, both result buffers
+            ctx.wait(t)
+        t0 = time.perf_counter()
+        tickets = []
+        for s in range(steps):
+            tickets.append(submit(res[s & 1]))
+            if len(tickets) == 2:
+                ctx.wait(tickets.pop(0))
+        for t in tickets:
+            ctx.wait(t)
+        rates["discarded_first_pass" if k == 0 else state].append(round(steps * n / (time.perf_counter() - t0)))
+        ctx.mol_disable()
+    out["host_to_host_reads_per_s"] = rates
+    out["host_to_host_filter_on_over_off"] = round(max(rates["filter_on"]) / max(rates["filter_off"]), 4)
+    return out
+
+
 def measure_command(segs, seq, offs):
     """the whole command once each way on a FASTQ of the batch: seconds on the wall and the report's streaming seconds"""
     import shutil
@@ -443,6 +545,7 @@ def main():
     ap.add_argument("--collapse", action="store_true", help="measure the UMI collapse alone and add a \"collapse\" section to --out")
     ap.add_argument("--dedup-collapsed", action="store_true", help="measure survey, freeze and replay alone and add a \"dedup_collapsed\" section to --out")
     ap.add_argument("--mate", action="store_true", help="measure mate mode alone and add a \"mate\" section to --out")
+    ap.add_argument("--mate-filter", action="store_true", help="measure the mate filter alone and add a \"mate_filter\" section to --out")
     ap.add_argument("--with-command", action="store_true", help="with --dedup-collapsed: the whole command each way on a FASTQ of the batch")
     ap.add_argument("--command-only", action="store_true", help="with --dedup-collapsed: the whole command alone, into the section that --out already has")
     args = ap.parse_args()
@@ -450,7 +553,7 @@ def main():
     from tagdust_amd import lib as tdlib
     segs = ["B:" + ",".join(bench.BARCODES), "F:" + "N" * UMI, "S:" + bench.SPACER, "R:N", "P:" + bench.ADAPTER]
     seq, offs, drawn, *mates = make_batch(args.reads, args.molecules, umi_sub=0.005 if args.collapse or args.dedup_collapsed else 0.0,
-                                          with_mates=args.mate)
+                                          with_mates=args.mate or args.mate_filter)
     head = min(args.reads, 100000)
     md, _ = tdlib.build_model(segs, seq[:offs[head]], offs[:head + 1])
     if args.dedup_collapsed and args.command_only:
@@ -472,6 +575,8 @@ def main():
             section = dict(doc, **measure_dedup_collapsed(ctx, seq, offs, args.reads))
         elif args.mate:
             section = dict(doc, **measure_mate(ctx, seq, offs, args.reads, *mates))
+        elif args.mate_filter:
+            section = dict(doc, **measure_mate_filter(ctx, seq, offs, args.reads, *mates, args.device))
         else:
             doc.update(measure(ctx, seq, offs, args.reads))
     finally:
@@ -479,9 +584,9 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     if args.dedup_collapsed and args.with_command:                 # (the context is closed: the command has the device to itself)
         section["command"] = measure_command(segs, seq, offs)
-    if args.collapse or args.dedup_collapsed or args.mate:         # the file's other figures stay what they are
+    if args.collapse or args.dedup_collapsed or args.mate or args.mate_filter:         # the file's other figures stay what they are
         doc = json.load(open(args.out)) if os.path.exists(args.out) else {}
-        doc["collapse" if args.collapse else "dedup_collapsed" if args.dedup_collapsed else "mate"] = section
+        doc["collapse" if args.collapse else "dedup_collapsed" if args.dedup_collapsed else "mate" if args.mate else "mate_filter"] = section
     json.dump(doc, open(args.out, "w"), indent=1, sort_keys=True)
     print(json.dumps(doc, sort_keys=True))
 
