@@ -22,6 +22,7 @@
 #include "tagdust_io.h"
 #include "tagdust_census.h"
 #include "tagdust_molecules.h"
+#include "tagdust_samples.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -95,6 +96,15 @@ typedef struct td_run_opts {
 	                                    --mate-bases' refusal of DUST and -ref for two input files; refused without --mate-bases, and with
 	                                    three or more files unless DUST is 0 and there is no -ref (a third file's outcome is not joined).
 	                                    The one-device, one-decoded-file and no --dedup-collapsed rules of --mate-bases stay */
+	char*    samples_file;           /* --samples FILE         [NULL = off]: combinatorial barcodes (tagdust_samples.h).  FILE holds one sample
+	                                    per line: the name, then one barcode spelling per 'B' segment of the barcode file's architecture as
+	                                    that lists them, separated by white space; '#' lines and blank lines are skipped.  It is resolved once
+	                                    the architectures are known (so it works with -arch); a spelling that its segment does not list, a
+	                                    wrong column count, a repeated row or name is an error that names the line.  The output files are
+	                                    <out>_BC_<name>[_READ<k>].fq in sheet order, then _un; <out>_samples.txt reports the samples and the
+	                                    combinations no sample has; <out>_molecules.txt labels its rows with the sample names.  Refused with
+	                                    -start / -end and when no input file's architecture has a 'B' segment; barcodes spread over several
+	                                    input files are not joined (the controller's rule of one barcode file stays) */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -175,6 +185,12 @@ typedef struct td_run_report {
 	                                             option): td_mol_collapse_get's, or td_mol_summarise of td_mol_collapse_host over the devices' td_mol_origins */
 	int32_t  dedup_collapsed;                 /* 1: the duplicates removed are those of the collapsed molecules (--dedup-collapsed) */
 	double   survey_s;                        /* --dedup-collapsed: seconds of the first pass, td_stream_survey and the freeze (inside stream_s) */
+	int32_t  n_samples;                       /* --samples: rows of the sheet (0 without the option) */
+	int64_t  n_sample_keys;                   /* ... distinct barcode combinations over all devices */
+	td_census_entry* samples;                 /* [n_sample_keys] td_samples_get's entries, merged with td_census_merge */
+	td_samples_totals samples_totals;         /* summed over the devices.  With one file on one device `counts` are the context's own tally
+	                                             (td_counts_get), and the reads that lost their extraction here are moved from slot
+	                                             TD_EXTRACT_SUCCESS to slot TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND; the barcode bins stay the decode kernel's */
 } td_run_report;
 /* In the controller's order: architectures per file, statistics over each file's head, thresholds, models, the run, the log.
  * A failure before the first batch leaves no output files behind; one during the run leaves them as they are and says so.  The

@@ -213,6 +213,7 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 	}
 
 	s.n_reads = n; s.n_bases = n_bases; s.n_tiles = (int32_t)n_tiles; s.is_ascii = is_ascii; s.sorted = sorted;
+	s.samples_gen = c->samples.on ? c->samples.gen : 0;
 	s.staged = true;
 	return TD_OK;
 }
@@ -260,6 +261,11 @@ static int launch_begin(td_ctx* c, TdSlot& s, int mode, bool& empty)
 		            "td_mol_mate_next first, then td_batch_upload; nothing was counted", c->molecules.mate.filter ? "on" : "off",
 		            c->molecules.mate.filter ? "enable" : "disable", (long long)s.n_reads, s.mate_judged ? "on" : "off");
 	}
+	// sample assignment: a batch staged under another state of the switch, or another sheet, is not rewritten, and not decoded either
+	if (mode == TD_MODE_GET_LABEL && s.samples_gen != (c->samples.on ? c->samples.gen : 0))
+		return fail(c, "td_run: sample assignment is %s (td_samples_%s) and the resident batch of %lld reads was staged %s: upload it again; "
+		            "nothing was assigned", c->samples.on ? "on" : "off", c->samples.on ? "enable" : "disable", (long long)s.n_reads,
+		            s.samples_gen ? (c->samples.on ? "under an earlier sheet" : "while it was on") : "while it was off");
 	s.reset_decoded();   // (runs_cap above all: a launch of the generic kernel, or an empty batch, must not hand the label runs of this
 	                     // slot's previous launch to the finish kernel)
 	s.mode = mode;
@@ -279,7 +285,9 @@ static int slot_art_left(td_ctx* c, TdSlot& s)
 
 // ... launch_end, behind the launch (ev_k0 stands in front of it): its stop event, then the counts that read the outcomes it left
 // -- the -ref hits when it ran with the filter, census and molecule count over a labelled batch -- and the slot has run.  With the
-// mate filter on, the join of the mates' verdicts stands in front of all of them: they read one outcome per pair.
+// mate filter on, the join of the mates' verdicts stands in front of all of them: they read one outcome per pair.  Sample assignment
+// (td_samples.hip) rewrites outcome and barcode behind the join and the hits, in front of census and molecule count: they read one
+// sample per read.
 static int launch_end(td_ctx* c, TdSlot& s, bool with_artifacts)
 {
 	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
@@ -287,6 +295,7 @@ static int launch_end(td_ctx* c, TdSlot& s, bool with_artifacts)
 	point_outputs(o, s.d_out, out_layout(s.n_tiles, s.lmax, s.nw1));
 	if (c->molecules.mate.filter && s.mode == TD_MODE_GET_LABEL && mol_mate_join(c, s, o.out_type) != TD_OK) return TD_FAIL;
 	if (with_artifacts && slot_count_hits(c, s, o.out_type) != TD_OK) return TD_FAIL;
+	if (c->samples.on && s.mode == TD_MODE_GET_LABEL && samples_slot(c, s, o.out_type, o.out_barcode, o.out_labels) != TD_OK) return TD_FAIL;
 	if (c->census.on && s.mode == TD_MODE_GET_LABEL && census_count_slot(c, s, o.out_type, o.out_labels) != TD_OK) return TD_FAIL;
 	// the molecule count last: dedup's second pass, the last launch in there, rewrites the outcomes the counts above read
 	if (c->molecules.on && s.mode == TD_MODE_GET_LABEL && mol_slot_decoded(c, s, o.out_type, o.out_barcode, o.out_finger, o.out_labels) != TD_OK) return TD_FAIL;

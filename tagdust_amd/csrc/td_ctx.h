@@ -16,6 +16,7 @@
 #include "td_host_inner.h"
 #include "td_census.h"
 #include "td_molecules.h"
+#include "td_samples.h"
 
 #define TD_HIDDEN __attribute__((visibility("hidden")))
 #define TD_MAX_PIPELINE 4
@@ -51,6 +52,7 @@ struct TdStaged : TdRoute {
 	bool mate_judged = false; // the mate filter was on when the mate batch was staged: the batch's outcomes are joined with the mates'
 	bool mate_typed = false;  // ... and the filter kernel ran (dust != 0 or artifacts set): d_mate_type holds this batch's mate types;
 	                          // judged and not typed: every mate type is 0, d_mate_type is not read
+	int32_t samples_gen = 0;  // sample assignment (td_samples.hip) as it stood when the batch was staged: the enable's number, 0 = off
 	const uint8_t* raw_host = nullptr;   // the batch's bases on the host, valid until the batch has been waited for: the pinned staging
 	                                     // copy, or the caller's own page-locked buffer under the "stable_input" contract; else NULL
 	TdStageBatch sb{};
@@ -207,6 +209,7 @@ struct td_ctx {
 	unsigned long long* d_art_hits = nullptr;   // [art_n] reads per artifact sequence (td_artifact_hits_get)
 	TdCensusState census;       // include/tagdust_census.h: off unless td_census_enable switched it on
 	TdMolState molecules;       // include/tagdust_molecules.h: off unless td_mol_enable switched it on
+	TdSamplesState samples;     // include/tagdust_samples.h: off unless td_samples_enable switched it on
 	int64_t win_first = 0, win_total = 0;   // td_set_batch_window
 	int32_t match_start = 0, match_len = 0;  // td_set_window (-start / -end); match_len = 0: whole reads
 	// batches: slot 0 is the resident batch of the synchronous calls; td_submit rotates over pipeline_depth slots

@@ -214,6 +214,17 @@ void td_writer_file_names_n(const char* prefix, const td_arch* a, int n_out_read
 	}
 }
 
+void td_writer_file_names_samples(const char* prefix, const std::vector<std::string>& samples, int n_out_reads, std::vector<std::string>& names, int* num_alternatives)
+{
+	if (num_alternatives) *num_alternatives = (int)samples.size() + 1;
+	names.clear();
+	for (int i = 0; i < n_out_reads; i++) {
+		const std::string rd = n_out_reads > 1 ? "_READ" + std::to_string(i + 1) : "";
+		for (const std::string& s : samples) names.push_back(std::string(prefix) + "_BC_" + s + rd + ".fq");
+		names.push_back(std::string(prefix) + "_un" + rd + ".fq");
+	}
+}
+
 extern "C" int td_writer_open(const char* prefix, const td_arch* a, td_writer** out)
 {
 	if (!prefix || !a || !out) return TD_FAIL;

@@ -51,6 +51,11 @@ inline void td_encode_bases(const unsigned char* s, uint8_t* dst, const int64_t 
 // print_all()'s file set for one input file (src/io.c:859-915): names in file-index order; *num_alternatives as io.c:923-934 uses it
 void td_writer_file_names(const char* prefix, const td_arch* a, std::vector<std::string>& names, int* num_alternatives);
 void td_writer_file_names_n(const char* prefix, const td_arch* a, int n_out_reads, std::vector<std::string>& names, int* num_alternatives);
+// ... with sample assignment on (tagdust_samples.h): <prefix>_BC_<sample>[_READ<k>].fq in sheet order, then _un; *num_alternatives = samples + 1
+void td_writer_file_names_samples(const char* prefix, const std::vector<std::string>& samples, int n_out_reads, std::vector<std::string>& names, int* num_alternatives);
+// the sample names of a file's contexts (option "samples", td_samples_name): empty when assignment is off in all of them; false (why) when
+// the contexts disagree
+bool td_stream_sample_names(td_ctx* const* ctx, int n_ctx, std::vector<std::string>& samples, std::string& why);
 // the first min(limit, records of the file) records of an input file of any kind td_stream_run reads (td_stream_reader.cpp): base codes and offsets
 int td_stream_head(const char* path, int64_t limit, int32_t n_threads, std::vector<uint8_t>& codes, std::vector<int64_t>& offs, std::string& why);
 // "td_..." message of the last failure on this thread (td_io_last_error)

@@ -13,6 +13,7 @@
 #include <time.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -170,7 +171,7 @@ struct OptSpec { const char* name; int arg; int id; };
 enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
        O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS, O_DEDUP, O_COLLAPSE,
-       O_DEDUP_COLLAPSED, O_MATE_BASES, O_MATE_FILTER, O_UNSUPPORTED = 100 };
+       O_DEDUP_COLLAPSED, O_MATE_BASES, O_MATE_FILTER, O_SAMPLES, O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
 	{ "7", 1, O_SEG + 6 }, { "8", 1, O_SEG + 7 }, { "9", 1, O_SEG + 8 }, { "10", 1, O_SEG + 9 },
@@ -197,6 +198,7 @@ const OptSpec kOwnOpts[] = {
 	{ "fingerprint-seq", 0, O_FINGER_SEQ }, { "molecules", 0, O_MOLECULES }, { "molecules-prefix", 1, O_MOLECULES_PREFIX },
 	{ "molecules-slots", 1, O_MOLECULES_SLOTS }, { "dedup", 0, O_DEDUP }, { "collapse-umis", 0, O_COLLAPSE },
 	{ "dedup-collapsed", 0, O_DEDUP_COLLAPSED }, { "mate-bases", 1, O_MATE_BASES }, { "mate-filter", 0, O_MATE_FILTER },
+	{ "samples", 1, O_SAMPLES },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -244,7 +246,7 @@ extern "C" void td_run_opts_free(td_run_opts* o)
 {
 	if (!o) return;
 	for (int k = 0; k < TD_RUN_MAX_SEGMENTS; k++) free(o->segments[k]);
-	free(o->arch_file); free(o->outfile); free(o->reference_fasta);
+	free(o->arch_file); free(o->outfile); free(o->reference_fasta); free(o->samples_file);
 	for (int k = 0; k < o->n_infiles; k++) free(o->infile[k]);
 	free(o->infile);
 	for (int k = 0; k < o->argc; k++) free(o->argv[k]);
@@ -304,7 +306,10 @@ extern "C" const char* td_run_usage(void)
 	       "\t                            both at most 32 together (implies --molecules; one file with an architecture other than R:N,\n"
 	       "\t                            one device, -dust 0, no -ref)\n"
 	       "\t--mate-filter               with --mate-bases and two input files: DUST and the -ref filter judge the mate as well, and a\n"
-	       "\t                            read whose mate fails is neither counted nor kept by --dedup (lifts -dust 0 / no -ref)\n\n";
+	       "\t                            read whose mate fails is neither counted nor kept by --dedup (lifts -dust 0 / no -ref)\n"
+	       "\t--samples FILE              combinatorial barcodes: FILE lists one sample per line, the name and one barcode per B segment;\n"
+	       "\t                            a read is written to <output prefix>_BC_<name>.fq by ALL its barcodes, to _un when they are\n"
+	       "\t                            incomplete or name no sample; the counts go to <output prefix>_samples.txt\n\n";
 }
 
 extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
@@ -382,6 +387,7 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 			if (o->mate_bases < 1 || o->mate_bases > TD_MOL_MAX_PREFIX - 1) return bad("--mate-bases: need 1..31 bases of the mate");
 			break;
 		case O_MATE_FILTER: o->mate_filter = 1; break;
+		case O_SAMPLES: free(o->samples_file); o->samples_file = dup_str(v); break;
 		default: return bad("unknown option " + a);
 		}
 	}
@@ -423,6 +429,7 @@ struct td_run_plan_t {
 	bool mate_filter = false;                // --mate-filter
 	std::string ref_file;                    // -ref, for the plan's "mate:" line
 	int mol_file = 0, mate_file = -1;        // ... the one decoded file and its mate, once every architecture is known
+	std::string samples_line;                // --samples: the plan's "samples:" line
 };
 
 namespace {
@@ -447,13 +454,76 @@ int mate_filter_files(const td_run_opts* o, int dust, bool use_ref, int mol, int
 	                o->n_infiles, o->infile[third]);
 }
 
+// --samples FILE (tagdust_samples.h): one sample per line -- the name, then one barcode spelling per 'B' segment as the architecture
+// lists them, separated by white space; '#' lines and blank lines are skipped
+struct SampleSheet {
+	std::vector<int> segs;                 // the 'B' segments of the architecture, in order
+	std::vector<std::string> names;
+	std::vector<const char*> name_ptrs;    // (as td_samples_enable takes them)
+	std::vector<int32_t> tuples;           // [names.size() * segs.size()]
+	int n() const { return (int)names.size(); }
+};
+
+// TD_FAIL with a message that names the line.  The sheet's own rules (rows and names pairwise different, the name's characters) are
+// checked here too, so that the plan refuses what td_samples_enable would.
+int read_sample_sheet(const char* path, const td_arch* a, SampleSheet& sh)
+{
+	sh = SampleSheet();
+	for (int j = 0; j < a->n_segments; j++) if (a->type[j] == 'B') sh.segs.push_back(j);
+	const int m = (int)sh.segs.size();
+	if (m > TD_SAMPLES_MAX_SEGMENTS) return run_fail("--samples: the architecture has %d barcode segments (at most %d).", m, TD_SAMPLES_MAX_SEGMENTS);
+	FILE* f = fopen(path, "r");
+	if (!f) return run_fail("--samples: cannot open the sample sheet %s.", path);
+	char buf[4096];
+	int line = 0;
+	std::vector<int> at_line;
+	int rc = TD_OK;
+	while (rc == TD_OK && fgets(buf, sizeof buf, f)) {
+		line++;
+		std::vector<std::string> w;
+		for (char* tok = strtok(buf, " \t\r\n"); tok; tok = strtok(nullptr, " \t\r\n")) w.push_back(tok);
+		if (w.empty() || w[0][0] == '#') continue;
+		if ((int)w.size() != m + 1) { rc = run_fail("--samples: %s line %d: %d columns, need %d (the name and one barcode per barcode segment).", path, line, (int)w.size(), m + 1); break; }
+		if (sh.n() == TD_SAMPLES_MAX) { rc = run_fail("--samples: %s line %d: more than %d samples.", path, line, TD_SAMPLES_MAX); break; }
+		const std::string& name = w[0];
+		bool ok = !name.empty() && name.size() <= TD_SAMPLES_MAX_NAME;
+		for (const char ch : name) ok = ok && ((ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z') || (ch >= '0' && ch <= '9') || ch == '.' || ch == '_' || ch == '-');
+		if (!ok) { rc = run_fail("--samples: %s line %d: the name '%s' is not 1..%d characters of [A-Za-z0-9._-].", path, line, name.c_str(), TD_SAMPLES_MAX_NAME); break; }
+		std::vector<int32_t> row;
+		for (int t = 0; t < m && rc == TD_OK; t++) {
+			const int seg = sh.segs[(size_t)t];
+			int found = -1;
+			for (int q = 0; q < a->n_seq[seg] - 1; q++) if (w[(size_t)t + 1] == a->seqs[seg][q]) found = q;   // (the last one is the all-N wildcard)
+			if (found < 0) rc = run_fail("--samples: %s line %d: '%s' is not a barcode of segment %d.", path, line, w[(size_t)t + 1].c_str(), seg + 1);
+			row.push_back(found);
+		}
+		if (rc != TD_OK) break;
+		for (int s = 0; s < sh.n() && rc == TD_OK; s++) {
+			if (sh.names[(size_t)s] == name) rc = run_fail("--samples: %s line %d: the name '%s' is taken by line %d.", path, line, name.c_str(), at_line[(size_t)s]);
+			else if (std::equal(row.begin(), row.end(), sh.tuples.begin() + (size_t)s * m))
+				rc = run_fail("--samples: %s line %d: the barcodes repeat those of line %d.", path, line, at_line[(size_t)s]);
+		}
+		if (rc != TD_OK) break;
+		sh.names.push_back(name);
+		sh.tuples.insert(sh.tuples.end(), row.begin(), row.end());
+		at_line.push_back(line);
+	}
+	fclose(f);
+	if (rc != TD_OK) return rc;
+	if (sh.n() == 0) return run_fail("--samples: %s lists no sample.", path);
+	for (const std::string& s : sh.names) sh.name_ptrs.push_back(s.c_str());
+	return TD_OK;
+}
+
+std::string samples_file_name(const td_run_opts* o) { return std::string(o->outfile) + "_samples.txt"; }
 std::string unknown_file_name(const td_run_opts* o) { return std::string(o->outfile) + "_unknown_barcodes.txt"; }
 std::string molecules_file_name(const td_run_opts* o) { return std::string(o->outfile) + "_molecules.txt"; }
 
 // what the controller decides once every file's architecture is known (barcode_hmm.c:130-159): TD_FAIL with the reference's message
 // (mol_file: the file whose contexts count molecules -- file 0, or with --mate-bases the one file that is decoded; mate_file: its mate)
+// (sheet: --samples resolved against the barcode file's architecture -- here, where the architectures are known, so that it works with -arch)
 int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& archs, int& bar_file, int& num_out_reads, std::vector<std::string>& names,
-                   int* mol_file = nullptr, int* mate_file = nullptr)
+                   int* mol_file = nullptr, int* mate_file = nullptr, SampleSheet* sheet = nullptr)
 {
 	bar_file = -1; num_out_reads = 0;
 	int mol = 0, mate = -1;
@@ -469,14 +539,26 @@ int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& arch
 	if (mate_file) *mate_file = mate;
 	for (size_t k = 0; k < archs.size(); k++) {
 		if (has_barcode(archs[k])) {
-			if (bar_file >= 0) return run_fail("Barcodes seem to be in both architectures... ");
+			if (bar_file >= 0)
+				return run_fail("Barcodes seem to be in both architectures... %s", o->samples_file ? "(--samples: barcodes spread over several input files are not "
+				                "joined; the controller's rule of one barcode file stays, and a sheet lists the barcode segments of that one file.)" : "");
 			bar_file = (int)k;
 		}
 		num_out_reads += read_segments(archs[k]);
 	}
 	if (num_out_reads == 0) return run_fail("No read segment in any architecture: there would be no output file.");
 	// print_all() names its files after the barcode file's architecture, else the last file's (td_stream_run_multi; one file: td_writer_open)
-	td_writer_file_names_n(o->outfile, archs[(size_t)(bar_file >= 0 ? bar_file : (int)archs.size() - 1)], num_out_reads, names, nullptr);
+	SampleSheet local;
+	SampleSheet& sh = sheet ? *sheet : local;
+	sh = SampleSheet();
+	if (o->samples_file) {
+		if (bar_file < 0) return run_fail("--samples: no input file's architecture has a barcode segment.");
+		if (read_sample_sheet(o->samples_file, archs[(size_t)bar_file], sh) != TD_OK) return TD_FAIL;
+		td_writer_file_names_samples(o->outfile, sh.names, num_out_reads, names, nullptr);
+		names.push_back(samples_file_name(o));
+	} else {
+		td_writer_file_names_n(o->outfile, archs[(size_t)(bar_file >= 0 ? bar_file : (int)archs.size() - 1)], num_out_reads, names, nullptr);
+	}
 	if (o->unknown_barcodes > 0) {
 		if (bar_file < 0) return run_fail("--unknown-barcodes: no input file's architecture has a barcode segment.");
 		names.push_back(unknown_file_name(o));
@@ -512,6 +594,9 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	if (o->arch_file && !file_exists(o->arch_file)) return run_fail("ERROR: Arch file:%s does not exists.", o->arch_file);
 	if (o->unknown_barcodes > 0 && (o->matchstart != -1 || o->matchend != -1))
 		return run_fail("--unknown-barcodes cannot be combined with -start / -end: labels behind a window do not spell the barcode.");
+	if (o->samples_file && (o->matchstart != -1 || o->matchend != -1))
+		return run_fail("--samples cannot be combined with -start / -end: labels behind a window do not mark the barcodes.");
+	if (o->samples_file && !file_exists(o->samples_file)) return run_fail("--samples: the sample sheet %s does not exist.", o->samples_file);
 	if (o->mate_bases) {
 		if (o->n_infiles < 2)
 			return run_fail("--mate-bases needs two or more input files (%d given): the mate is the record of a second file.", o->n_infiles);
@@ -582,7 +667,18 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	}
 	std::vector<const td_arch*> view;
 	for (auto& a : archs) view.push_back(a.get());
-	if (p->all_known && decide_outputs(o, view, p->bar_file, p->num_out_reads, p->out_files, &p->mol_file, &p->mate_file) != TD_OK) return TD_FAIL;
+	SampleSheet sheet;
+	if (p->all_known && decide_outputs(o, view, p->bar_file, p->num_out_reads, p->out_files, &p->mol_file, &p->mate_file, &sheet) != TD_OK) return TD_FAIL;
+	if (o->samples_file) {
+		p->samples_line = std::string("samples: ") + o->samples_file + ": ";
+		if (!p->all_known) p->samples_line += "resolved once the arch file's choice is made";
+		else {
+			p->samples_line += std::to_string(sheet.n()) + " samples by segment";
+			for (size_t t = 0; t < sheet.segs.size(); t++) p->samples_line += (t ? ", " : (sheet.segs.size() > 1 ? "s " : " ")) + std::to_string(sheet.segs[t] + 1);
+			p->samples_line += " of file " + std::to_string(p->bar_file) + "; a read whose barcodes are incomplete or name no sample goes to _un";
+		}
+		p->samples_line += "\n";
+	}
 	if (p->all_known && mate_filter_files(o, p->dust, p->use_ref, p->mol_file, p->mate_file) != TD_OK) return TD_FAIL;
 	*out = p.release();
 	return TD_OK;
@@ -616,6 +712,7 @@ extern "C" int64_t td_run_plan_describe(const td_run_plan_t* p, char* buf, int64
 		if (p->all_known) s += " (file " + std::to_string(p->mol_file) + " is decoded, file " + std::to_string(p->mate_file) + " is its mate)";
 		s += "\n";
 	}
+	s += p->samples_line;
 	if (p->all_known) {
 		s += "barcode file: " + (p->bar_file >= 0 ? std::to_string(p->bar_file) : std::string("none")) + "\n";
 		s += "output reads: " + std::to_string(p->num_out_reads) + "\n";
@@ -743,6 +840,7 @@ extern "C" void td_run_report_clear(td_run_report* r)
 	if (r->artifact_names) for (int j = 0; j < r->n_artifacts; j++) free(r->artifact_names[j]);
 	free(r->artifact_names); free(r->artifact_hits); free(r->log);
 	td_census_free(r->unknown);
+	td_census_free(r->samples);
 	free(r->molecules);
 	free(r->molecules_collapsed);
 	for (int k = 0; k < TD_RUN_MAX_FILES; k++) free(r->architectures[k]);
@@ -790,6 +888,8 @@ struct Run {
 	bool use_ref = false;
 	float error_rate = 0.05f;
 	int mol_file = 0, mate_file = -1;     // the file whose contexts count molecules; with --mate-bases its mate, else -1
+	SampleSheet sheet;                    // --samples, resolved against the barcode file's architecture (no sample without the option)
+	bool device_counts = false;           // rep->counts are a context's own tally (td_counts_get), not the combined records'
 
 	int head_limit() const { return o->flavour ? 1001000 : 1000001; }   // io.c:125-188 with num_query 1000 / 1 000 001
 
@@ -870,6 +970,7 @@ struct Run {
 	int run_files(td_stream_stats& st);
 	int unknown_barcodes(int bar_file);
 	int molecules();
+	int samples(int bar_file);
 
 	// Every device's entries of a file, merged: acc[n_acc] is the caller's to td_census_free (NULL after a failure), per[d] the
 	// totals of device d.  `get` is td_census_get or td_mol_entries.
@@ -932,7 +1033,7 @@ int Run::execute()
 	{
 		std::vector<const td_arch*> view;
 		for (auto& f : files) view.push_back(f.arch.get());
-		if (decide_outputs(o, view, bar_file, num_out_reads, out_files, &mol_file, &mate_file) != TD_OK ||
+		if (decide_outputs(o, view, bar_file, num_out_reads, out_files, &mol_file, &mate_file, &sheet) != TD_OK ||
 		    mate_filter_files(o, dust, use_ref, mol_file, mate_file) != TD_OK) { log.add(g_run_error + "\n"); return TD_FAIL; }
 	}
 
@@ -1017,6 +1118,9 @@ int Run::execute()
 			// --unknown-barcodes: the contexts of the barcode file count what their reads spell in the last 'B' segment
 			if (o->unknown_barcodes > 0 && k == bar_file &&
 			    td_census_enable(c, -1, TD_CENSUS_DEFAULT_MASK, o->unknown_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
+			// --samples: the contexts of the barcode file assign every extracted read by all its barcodes, in front of census and count
+			if (sheet.n() > 0 && k == bar_file &&
+			    td_samples_enable(c, sheet.tuples.data(), sheet.name_ptrs.data(), sheet.n(), 16) != TD_OK) return fail("%s", td_last_error(c));
 			// --molecules: the contexts of the one input file (with --mate-bases: of the one decoded file) count its extracted reads per
 			// barcode, fingerprint and start of the read
 			if (k != mol_file) continue;
@@ -1044,6 +1148,7 @@ int Run::execute()
 		return fail("%s -- the run failed after it had started: the output files are incomplete and were left as they are", msg.c_str());
 	}
 
+	if (sheet.n() > 0 && samples(bar_file) != TD_OK) return TD_FAIL;
 	if (o->unknown_barcodes > 0 && unknown_barcodes(bar_file) != TD_OK) return TD_FAIL;
 	if (o->molecules && molecules() != TD_OK) return TD_FAIL;
 
@@ -1109,6 +1214,62 @@ int Run::unknown_barcodes(int bar_file)
 			if (best < 0 || d < best_d) { best = q; best_d = d; }   // (ties go to the lower index)
 		}
 		fprintf(out, "%lld\t%s\t%s\t%d\n", (long long)acc[i].count, word, best >= 0 ? a->seqs[seg][best] : "-", best >= 0 ? best_d : -1);
+	}
+	fclose(out);
+	return TD_OK;
+}
+
+// --samples: every device's combination count of the barcode file, merged with td_census_merge, the totals summed (nothing of it
+// enters the log), and <out>_samples.txt
+int Run::samples(int bar_file)
+{
+	FileState& f = files[(size_t)bar_file];
+	td_census_entry* acc = nullptr;
+	int64_t n_acc = 0;
+	td_samples_totals sum{};
+	std::vector<td_samples_totals> per;
+	if (merged_entries(f, td_samples_get, acc, n_acc, per) != TD_OK) return TD_FAIL;
+	for (const td_samples_totals& t : per) {
+		sum.eligible += t.eligible; sum.assigned += t.assigned; sum.unlisted += t.unlisted; sum.incomplete += t.incomplete; sum.overflow += t.overflow;
+	}
+	rep->samples = acc; rep->n_sample_keys = n_acc; rep->samples_totals = sum; rep->n_samples = sheet.n();
+	// a context's own tally is the decode kernel's: the reads that lost their extraction here move to "barcode / UMI not found"
+	if (device_counts) {
+		rep->counts[TD_EXTRACT_SUCCESS] -= sum.unlisted + sum.incomplete;
+		rep->counts[TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND] += sum.unlisted + sum.incomplete;
+	}
+	const td_arch* a = f.arch.get();
+	const int m = (int)sheet.segs.size();
+	const std::string name = samples_file_name(o);
+	FILE* out = fopen(name.c_str(), "w");
+	if (!out) return fail("Failed to open file:%s", name.c_str());
+	fprintf(out, "# samples: the extracted reads of %s by all their barcodes\n# sheet\t%s\n# samples\t%d\n# segments", o->infile[bar_file], o->samples_file, sheet.n());
+	for (int t = 0; t < m; t++) fprintf(out, "\t%d (%s)", sheet.segs[(size_t)t] + 1, f.segs[(size_t)sheet.segs[(size_t)t]].c_str());
+	fprintf(out, "\n# extracted reads\t%lld\n# assigned\t%lld\n# not in the sheet\t%lld\n# incomplete\t%lld\n# not counted\t%lld\n", (long long)sum.eligible,
+	        (long long)sum.assigned, (long long)sum.unlisted, (long long)sum.incomplete, (long long)sum.overflow);
+	if (sum.overflow > 0) fprintf(out, "# the counting table was too small: the counts below are exact, %lld reads are in none of them\n", (long long)sum.overflow);
+	fprintf(out, "# sample");
+	for (int t = 0; t < m; t++) fprintf(out, "\tbarcode %d", t + 1);
+	fprintf(out, "\treads\tshare\n");
+	std::vector<char> listed((size_t)std::max<int64_t>(n_acc, 1), 0);
+	for (int s = 0; s < sheet.n(); s++) {
+		const uint64_t key = td_samples_key(sheet.tuples.data() + (size_t)s * m, m);
+		int64_t reads = 0;
+		for (int64_t i = 0; i < n_acc; i++) if (acc[i].key == key) { reads = acc[i].count; listed[(size_t)i] = 1; }
+		fprintf(out, "%s", sheet.names[(size_t)s].c_str());
+		for (int t = 0; t < m; t++) fprintf(out, "\t%s", a->seqs[sheet.segs[(size_t)t]][sheet.tuples[(size_t)s * m + t]]);
+		fprintf(out, "\t%lld\t%0.4f\n", (long long)reads, sum.eligible > 0 ? (double)reads / (double)sum.eligible : 0.0);
+	}
+	fprintf(out, "# combinations not in the sheet\n");
+	for (int64_t i = 0; i < n_acc; i++) {   // (td_samples_get's order: count descending, then key ascending)
+		if (listed[(size_t)i]) continue;
+		int32_t calls[TD_SAMPLES_MAX_SEGMENTS], km = 0;
+		if (td_samples_key_calls(acc[i].key, calls, &km) != TD_OK || km != m) { fclose(out); return fail("--samples: 0x%llx is no key of %d segments", (unsigned long long)acc[i].key, m); }
+		for (int t = 0; t < m; t++) {
+			const int seg = sheet.segs[(size_t)t];
+			fprintf(out, "%s%s", t ? "\t" : "", calls[t] < 0 || calls[t] >= a->n_seq[seg] ? "-" : a->seqs[seg][calls[t]]);   // (the decoy's own spelling is its N's)
+		}
+		fprintf(out, "\t%lld\t%0.4f\n", (long long)acc[i].count, sum.eligible > 0 ? (double)acc[i].count / (double)sum.eligible : 0.0);
 	}
 	fclose(out);
 	return TD_OK;
@@ -1206,7 +1367,9 @@ int Run::molecules()
 		if (crows) fprintf(out, "\t%lld\t%0.4f", (long long)collapsed, r.reads > 0 ? 1.0 - (double)collapsed / (double)r.reads : 0.0);
 		fprintf(out, "\n");
 	};
-	if (seg >= 0) {
+	if (sheet.n() > 0 && seg >= 0) {   // --samples: a bin is a sample
+		for (int q = 0; q < sheet.n(); q++) line(sheet.names[(size_t)q].c_str(), rows[q], crows ? crows[q].molecules : 0);
+	} else if (seg >= 0) {
 		const int n_listed = std::min(a->n_seq[seg] - 1, (int)TD_NUM_BARCODE_BINS);   // (the last one is the all-N wildcard)
 		for (int q = 0; q < n_listed; q++) line(a->seqs[seg][q], rows[q], crows ? crows[q].molecules : 0);
 	} else {
@@ -1240,12 +1403,14 @@ int Run::run_files(td_stream_stats& st)
 			td_stream_stats survey{};
 			const double t0 = now_s();
 			if (td_stream_survey(c, o->infile[0], &so, &survey) != TD_OK) return run_fail("%s", td_io_last_error());
-			if (td_mol_dedup_freeze(c, nullptr) != TD_OK || td_counts_reset(c) != TD_OK || (o->unknown_barcodes > 0 && td_census_reset(c) != TD_OK))
+			if (td_mol_dedup_freeze(c, nullptr) != TD_OK || td_counts_reset(c) != TD_OK || (o->unknown_barcodes > 0 && td_census_reset(c) != TD_OK) ||
+			    (sheet.n() > 0 && td_samples_reset(c) != TD_OK))
 				return run_fail("%s", td_last_error(c));
 			rep->survey_s = now_s() - t0;
 		}
 		if (td_stream_run(c, o->infile[0], files[0].arch.get(), o->outfile, &so, &st) != TD_OK) return run_fail("%s", td_io_last_error());
 		if (td_counts_get(c, rep->counts) != TD_OK) return run_fail("%s", td_last_error(c));
+		device_counts = true;
 		if (rep->n_artifacts && td_artifact_hits_get(c, rep->artifact_hits, rep->n_artifacts) != TD_OK) return run_fail("%s", td_last_error(c));
 		return TD_OK;
 	}

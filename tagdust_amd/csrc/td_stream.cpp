@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "../../include/tagdust_molecules.h"   // td_mol_mate_next: pair mode of td_stream_run_multi
+#include "../../include/tagdust_samples.h"     // td_samples_name: the output files of a run with sample assignment on
 #include "td_stream_internal.h"
 
 using namespace tdstream;
@@ -43,6 +44,26 @@ td_stream_opts tdstream::resolve_opts(const td_stream_opts* opts, bool reference
 	if (o.block_bytes < 4096) o.block_bytes = 4096;
 	o.n_threads = td_stage_threads(o.n_threads, 32);
 	return o;
+}
+
+// Sample assignment (tagdust_samples.h): the decoded file's contexts say whether it is on, the way pair mode reads "mate_bases"; the
+// output files are then the sheet's.  Contexts of one file that disagree about the sheet cannot write one file set.
+bool td_stream_sample_names(td_ctx* const* ctx, int n_ctx, std::vector<std::string>& samples, std::string& why)
+{
+	samples.clear();
+	for (int d = 0; d < n_ctx; d++) {
+		int32_t n = 0;
+		(void)td_get_option(ctx[d], "samples", &n);
+		std::vector<std::string> mine;
+		for (int32_t s = 0; s < n; s++) { const char* name = td_samples_name(ctx[d], s); mine.push_back(name ? name : ""); }
+		if (d == 0) samples = mine;
+		else if (mine != samples) {
+			why = "the contexts of one input file disagree about the sample sheet (td_samples_enable): context 0 has " + std::to_string(samples.size()) +
+			      " samples, context " + std::to_string(d) + " has " + std::to_string(mine.size()) + (mine.size() == samples.size() ? " with other names" : "");
+			return false;
+		}
+	}
+	return true;
 }
 
 namespace {
@@ -205,7 +226,15 @@ extern "C" int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* ar
 	if (ctx) {
 		std::vector<std::string> names;
 		int num_alternatives = 2;
-		td_writer_file_names(out_prefix, arch, names, &num_alternatives);
+		std::vector<std::string> samples;
+		td_ctx* const own[1] = { ctx };
+		if (!td_stream_sample_names(own, 1, samples, why)) { td_io_set_error("td_stream_run: " + why); return TD_FAIL; }
+		if (samples.empty()) td_writer_file_names(out_prefix, arch, names, &num_alternatives);
+		else {
+			int n_r = 0;
+			for (int j = 0; j < arch->n_segments; j++) n_r += arch->type[j] == 'R';
+			td_writer_file_names_samples(out_prefix, samples, n_r, names, &num_alternatives);
+		}
 		w.reset(new Writer(err, o.n_threads, num_alternatives));
 		w->fingerprint_text = o.fingerprint_text != 0;
 		if (!w->open(names, why)) { td_io_set_error("td_stream_run: cannot create " + why); return TD_FAIL; }
@@ -428,10 +457,16 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 	// print_all() names its files after param->read_structure: the barcode file's architecture, else the last file's
 	std::vector<std::string> names;
 	int num_alternatives = 2;
-	td_writer_file_names_n(out_prefix, files[m.bar_file >= 0 ? m.bar_file : K - 1].arch, m.num_out_reads, names, &num_alternatives);
+	std::string why;
+	std::vector<std::string> samples;   // sample assignment: on in the contexts of the barcode file
+	if (m.bar_file >= 0 && files[m.bar_file].ctx && !td_stream_sample_names(files[m.bar_file].ctx, N, samples, why)) {
+		td_io_set_error("td_stream_run_multi: " + why);
+		return TD_FAIL;
+	}
+	if (samples.empty()) td_writer_file_names_n(out_prefix, files[m.bar_file >= 0 ? m.bar_file : K - 1].arch, m.num_out_reads, names, &num_alternatives);
+	else td_writer_file_names_samples(out_prefix, samples, m.num_out_reads, names, &num_alternatives);
 	Writer w(err, o.n_threads, num_alternatives);
 	w.fingerprint_text = o.fingerprint_text != 0;
-	std::string why;
 	if (!w.open(names, why)) { td_io_set_error("td_stream_run_multi: cannot create " + why); return TD_FAIL; }
 	std::vector<size_t> file_base((size_t)K, 0);      // io.c:917-1001: c
 	{ size_t c = 0; for (int k = 0; k < K; k++) { file_base[(size_t)k] = c; c += (size_t)num_alternatives * (size_t)m.read_present[(size_t)k]; } }

@@ -51,6 +51,15 @@ CENSUS_TOTALS = ("eligible", "counted", "skipped_empty", "skipped_long", "skippe
 CENSUS_DEFAULT_MASK = (1 << 1) | (1 << 3)   # EXTRACT_FAIL_ARCHITECTURE_MISMATCH, EXTRACT_FAIL_BAR_FINGER_NOT_FOUND
 CENSUS_MAX_WORD = 28
 
+# include/tagdust_samples.h: sample assignment by all 'B' segments
+SAMPLES_ABI_SYMBOLS = ["td_samples_enable", "td_samples_disable", "td_samples_reset", "td_samples_get", "td_samples_name", "td_samples_key",
+                       "td_samples_key_calls", "td_samples_host"]
+SAMPLES_TOTALS = ("eligible", "assigned", "unlisted", "incomplete", "overflow")
+SAMPLES_MAX = 255
+SAMPLES_MAX_SEGMENTS = 4
+EXTRACT_SUCCESS = 0
+EXTRACT_FAIL_BAR_FINGER_NOT_FOUND = 3
+
 # include/tagdust_molecules.h: molecules per barcode
 MOL_ABI_SYMBOLS = ["td_mol_enable", "td_mol_disable", "td_mol_reset", "td_mol_entries", "td_mol_get", "td_mol_summarise", "td_mol_host",
                    "td_mol_key", "td_mol_key_bin", "td_mol_dedup_enable", "td_mol_dedup_disable", "td_mol_dedup_get", "td_mol_dedup_host",
@@ -627,12 +636,26 @@ class _RunOptsMate(C.Structure):
     _fields_ = _RunOpts._fields_ + [("mate_bases", C.c_int32), ("mate_filter", C.c_int32)]
 
 
+class _RunOptsSamples(C.Structure):
+    """td_run_opts as it is now: _RunOptsMate -- whose last fields tests/test_mate_filter.py pins -- and the field appended behind it;
+    this is the structure every td_run_* call is given"""
+    _fields_ = _RunOptsMate._fields_ + [("samples_file", C.c_char_p)]
+
+
 class _CensusTotals(C.Structure):
     """td_census_totals (include/tagdust_census.h)"""
     _fields_ = [(f, C.c_int64) for f in CENSUS_TOTALS]
 
     def as_dict(self):
         return {f: int(getattr(self, f)) for f in CENSUS_TOTALS}
+
+
+class _SamplesTotals(C.Structure):
+    """td_samples_totals (include/tagdust_samples.h)"""
+    _fields_ = [(f, C.c_int64) for f in SAMPLES_TOTALS]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f in SAMPLES_TOTALS}
 
 
 class _MolTotals(C.Structure):
@@ -677,25 +700,33 @@ class _RunReport(C.Structure):
                 ("dedup_collapsed", C.c_int32), ("survey_s", C.c_double)]
 
 
+class _RunReportSamples(C.Structure):
+    """td_run_report as it is now: _RunReport -- whose last fields tests/test_dedup_collapsed.py pins -- and the fields appended
+    behind them; this is the structure td_run_execute fills"""
+    _fields_ = _RunReport._fields_ + [("n_samples", C.c_int32), ("n_sample_keys", C.c_int64), ("samples", C.c_void_p),
+                                      ("samples_totals", _SamplesTotals)]
+
+
 def _run_lib():
     lib = load_library()
-    lib.td_run_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(_RunOptsMate)), C.c_char_p, C.c_size_t]
-    lib.td_run_opts_free.argtypes = [C.POINTER(_RunOptsMate)]
+    lib.td_run_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(_RunOptsSamples)), C.c_char_p, C.c_size_t]
+    lib.td_run_opts_free.argtypes = [C.POINTER(_RunOptsSamples)]
     lib.td_run_opts_free.restype = None
     lib.td_run_last_error.restype = C.c_char_p
-    lib.td_run_plan.argtypes = [C.POINTER(_RunOptsMate), C.POINTER(C.c_void_p)]
+    lib.td_run_plan.argtypes = [C.POINTER(_RunOptsSamples), C.POINTER(C.c_void_p)]
     lib.td_run_plan_free.argtypes = [C.c_void_p]
     lib.td_run_plan_free.restype = None
     lib.td_run_plan_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.td_run_plan_describe.restype = C.c_int64
-    lib.td_run_output_files_describe.argtypes = [C.POINTER(_RunOptsMate), C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_int64]
+    lib.td_run_output_files_describe.argtypes = [C.POINTER(_RunOptsSamples), C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_int64]
     lib.td_run_output_files_describe.restype = C.c_int64
     lib.td_run_arch_file_describe.argtypes = [C.c_char_p, C.c_char_p, C.c_int64]
     lib.td_run_arch_file_describe.restype = C.c_int64
-    lib.td_run_execute.argtypes = [C.POINTER(_RunOptsMate), C.POINTER(_RunReport)]
-    lib.td_run_report_clear.argtypes = [C.POINTER(_RunReport)]
+    lib.td_run_execute.argtypes = [C.POINTER(_RunOptsSamples), C.POINTER(_RunReportSamples)]
+    lib.td_run_report_clear.argtypes = [C.POINTER(_RunReportSamples)]
     lib.td_run_report_clear.restype = None
-    lib.td_run_format_summary.argtypes = [C.POINTER(_RunOptsMate), C.POINTER(_RunReport), C.c_char_p, C.c_int64]
+    # (the summary reads the report's leading fields alone -- counts, threshold, artifacts: a _RunReport will do as well)
+    lib.td_run_format_summary.argtypes = [C.POINTER(_RunOptsSamples), C.c_void_p, C.c_char_p, C.c_int64]
     lib.td_run_format_summary.restype = C.c_int64
     return lib
 
@@ -707,7 +738,7 @@ class RunOpts:
         self.lib = _run_lib()
         argv = [b"tagdust-hip"] + [os.fsencode(a) for a in args]
         arr = (C.c_char_p * len(argv))(*argv)
-        self.p = C.POINTER(_RunOptsMate)()
+        self.p = C.POINTER(_RunOptsSamples)()
         err = C.create_string_buffer(1024)
         if self.lib.td_run_parse_args(len(argv), arr, C.byref(self.p), err, len(err)) != 0:
             self.p = None
@@ -769,7 +800,7 @@ def run_arch_file(path):
 def run_execute(args):
     """td_run_execute: a whole run from the tagdust command line (without the program name); returns the report as a dict."""
     o = RunOpts(args)
-    rep = _RunReport()
+    rep = _RunReportSamples()
     try:
         rc = o.lib.td_run_execute(o.p, C.byref(rep))
         if rc != 0:
@@ -789,6 +820,8 @@ def run_execute(args):
             "collapse_totals": rep.collapse_totals.as_dict() if rep.collapse else None,
             "molecules_collapsed": _mol_rows(rep.molecules_collapsed) if rep.molecules_collapsed else None,
             "dedup_collapsed": bool(rep.dedup_collapsed), "survey_s": float(rep.survey_s),
+            "samples": _census_entries(rep.samples, int(rep.n_sample_keys)) if rep.n_samples else None,
+            "samples_totals": rep.samples_totals.as_dict() if rep.n_samples else None,
         }
     finally:
         o.lib.td_run_report_clear(C.byref(rep))
@@ -870,6 +903,70 @@ def census_key(word):
     for ch in word:
         v = (v << 2) | "ACGT".index(ch)
     return (len(word) << 56) | v
+
+
+def _samples_lib():
+    lib = _census_lib()
+    lib.td_samples_enable.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_int32, C.c_int32]
+    lib.td_samples_disable.argtypes = [C.c_void_p]
+    lib.td_samples_reset.argtypes = [C.c_void_p]
+    lib.td_samples_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_SamplesTotals)]
+    lib.td_samples_name.argtypes = [C.c_void_p, C.c_int32]
+    lib.td_samples_name.restype = C.c_char_p
+    lib.td_samples_key.argtypes = [C.c_void_p, C.c_int32]
+    lib.td_samples_key.restype = C.c_uint64
+    lib.td_samples_key_calls.argtypes = [C.c_uint64, C.c_void_p, C.POINTER(C.c_int32)]
+    lib.td_samples_host.argtypes = [C.POINTER(_ModelDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(_SamplesTotals)]
+    return lib
+
+
+def _samples_sheet(tuples):
+    """a sheet as the int32 [n_samples, m] array the library reads"""
+    t = np.ascontiguousarray(tuples, np.int32)
+    if t.ndim == 1:
+        t = t.reshape(-1, 1)
+    return t
+
+
+def samples_host(md, tuples, offs, res, labels):
+    """td_samples_host: sample assignment of a batch from host arrays (no GPU).  md: model mapping; tuples: the sheet, one row of m
+    HMM indices per sample; res: RESULT_DTYPE records (td_batch_download's, or the oracle's), left alone; labels as
+    td_batch_download leaves them.  Returns (the rewritten records, entries, totals dict)."""
+    lib = _samples_lib()
+    desc, keep = make_model_desc(md)
+    t = _samples_sheet(tuples)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    rr = np.array(res, RESULT_DTYPE, copy=True)
+    ptr, n, tot = C.c_void_p(), C.c_int64(), _SamplesTotals()
+    rc = lib.td_samples_host(C.byref(desc), t.ctypes.data, len(t), offs.ctypes.data, len(offs) - 1, rr.ctypes.data, labels.ctypes.data,
+                             C.byref(ptr), C.byref(n), C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    try:
+        return rr, _census_entries(ptr, n.value), tot.as_dict()
+    finally:
+        lib.td_census_free(ptr)
+
+
+def samples_key(calls):
+    """td_samples_key: the key of a read's calls, one per chosen segment (-1: none)"""
+    c = np.ascontiguousarray(calls, np.int32)
+    key = int(_samples_lib().td_samples_key(c.ctypes.data, len(c)))
+    if key == 0:
+        raise TdError("td_samples_key: %r are no calls" % (list(calls),))
+    return key
+
+
+def samples_key_calls(key):
+    """td_samples_key_calls: the calls a key stands for, one per chosen segment (-1: none)"""
+    lib = _samples_lib()
+    calls, m = np.zeros(SAMPLES_MAX_SEGMENTS, np.int32), C.c_int32()
+    if lib.td_samples_key_calls(int(key), calls.ctypes.data, C.byref(m)) != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return [int(c) for c in calls[:m.value]]
 
 
 def _mol_rows(ptr):
@@ -1283,6 +1380,36 @@ class TagdustHip:
             cap = n.value
         out = np.zeros(int(cap), CENSUS_ENTRY_DTYPE)
         self._chk(lib.td_census_get(self.h, out.ctypes.data, int(cap), C.byref(n), C.byref(tot)))
+        return out[:min(int(cap), n.value)], tot.as_dict()
+
+    def samples_enable(self, tuples, names=None, log2_slots=16):
+        """td_samples_enable: tuples = the sheet, one row of m HMM indices per sample; names = None, or one name (or None) per sample"""
+        t = _samples_sheet(tuples)
+        arr = None
+        if names is not None:
+            arr = (C.c_char_p * len(names))(*[None if s is None else s.encode() for s in names])
+            assert len(names) == len(t)
+        self._chk(_samples_lib().td_samples_enable(self.h, t.ctypes.data, arr, len(t), int(log2_slots)))
+
+    def samples_disable(self):
+        self._chk(_samples_lib().td_samples_disable(self.h))
+
+    def samples_reset(self):
+        self._chk(_samples_lib().td_samples_reset(self.h))
+
+    def samples_name(self, s):
+        name = _samples_lib().td_samples_name(self.h, int(s))
+        return None if name is None else name.decode()
+
+    def samples(self, cap=None):
+        """td_samples_get: (entries by count descending then key ascending -- at most cap of them --, totals dict)"""
+        lib = _samples_lib()
+        n, tot = C.c_int64(), _SamplesTotals()
+        if cap is None:
+            self._chk(lib.td_samples_get(self.h, None, 0, C.byref(n), C.byref(tot)))
+            cap = n.value
+        out = np.zeros(int(cap), CENSUS_ENTRY_DTYPE)
+        self._chk(lib.td_samples_get(self.h, out.ctypes.data, int(cap), C.byref(n), C.byref(tot)))
         return out[:min(int(cap), n.value)], tot.as_dict()
 
     def mol_enable(self, prefix_bases=MOL_DEFAULT_PREFIX, log2_slots=16):
