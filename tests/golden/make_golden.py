@@ -506,6 +506,20 @@ def scenarios(tmp):
         return fq, ["-seed", "42", "-1", "R:N", "-2", "G:G", "-3", "B:" + ",".join(bars4), "-4", "R:N"]
     sc["r_g_b_r"] = r_g_b_r
 
+    # Two BIG barcode segments (shape A of tests/plan_shapes.py: 16 and 24 8-nt barcodes around a spacer, 45 HMMs): pins the oracle
+    # itself where both segments run in the specialised kernel's run-time HMM loop and the restarted sweeps bridge both.
+    def plan_a():
+        sys.path.insert(0, os.path.dirname(HERE))
+        import plan_shapes
+        spec, seed, _ = plan_shapes.SHAPES["A"]
+        segs, reads = plan_shapes.make_reads(spec, seed, 240)
+        fq = os.path.join(tmp, "plana.fq")
+        with open(fq, "w") as fh:
+            for i, s_ in enumerate(reads):
+                fh.write("@READ%d\n%s\n+\n%s\n" % (i, s_, "I" * len(s_)))
+        return fq, ["-seed", "42"] + [x for k, s_ in enumerate(segs) for x in ("-%d" % (k + 1), s_)]
+    sc["plan_a_b16_s_b24_r"] = plan_a
+
     # -start / -end on architectures other than "B R": the labels are stored relative to the window but make_extracted_read
     # applies them to absolute read positions (barcode_hmm.c:3325-3356), and the labels behind the window stay 0 -- HMM 0 of
     # segment 0 -- so the bases behind the window are kept exactly when the first segment is a read segment.
@@ -651,6 +665,11 @@ def main():
                 dict(zip(vals.tolist(), cnt.tolist())), kb))
             if name in FREE_ORDER_NAMES:
                 hist = dict(zip(vals.tolist(), cnt.tolist()))
+                assert hist.get(0, 0) >= 5 and sum(1 for k, v in hist.items() if k != 0 and v >= 5) >= 2, (name, hist)
+                assert kb <= 32, (name, kb)
+            if name == "plan_a_b16_s_b24_r":      # 240 reads, outcome 0 and two more with five reads each (tests/test_oracle_golden.py)
+                hist = dict(zip(vals.tolist(), cnt.tolist()))
+                assert d["n_reads"] == 240 and list(d["n_hmm"]) == [17, 2, 25, 1], (name, d["n_hmm"])
                 assert hist.get(0, 0) >= 5 and sum(1 for k, v in hist.items() if k != 0 and v >= 5) >= 2, (name, hist)
                 assert kb <= 32, (name, kb)
             if name in WINDOW_NAMES:      # the conditions tests/test_window_cases.py keeps asserting on the committed files

@@ -665,12 +665,9 @@ if os.environ.get("TD_FUZZ_SEEDS"):      # e.g. TD_FUZZ_SEEDS=100:180 for a long
     _FUZZ_SEEDS = list(range(int(_a), int(_b)))
 
 
-@pytest.mark.parametrize("seed", _FUZZ_SEEDS)
-def test_random_architectures_against_oracle(ctx, seed):
-    """Model shapes beyond the fixtures: random segment lists (optional / partial / barcode / fingerprint / spacer / G /
-    read segments of random sizes), models from the library's own builder, reads with substitutions, indels, Ns and a
-    share of unrelated sequences; both kernels must equal the oracle bit for bit."""
-    from oracle import pyoracle
+def _random_case(seed):
+    """Segments, 400 reads, the builder's model with its decode parameters, artifact filter (or None) and thread count of one seed
+    of the tag fuzz (also read by tools/plan_survey.py)."""
     from tagdust_amd import lib as tdlib
     rng = np.random.RandomState(1000 + seed)
     segs, parts = _random_arch(rng)
@@ -717,6 +714,17 @@ def test_random_architectures_against_oracle(ctx, seed):
         art = (a_string, a_index, int(rng.randint(2, 14)))
         md["art_n"], md["art_string"], md["art_index"] = len(texts), a_string, a_index
         md["art_filter_error"], md["art_threads"] = art[2], nthreads
+    return segs, seq, offs, md, art, nthreads
+
+
+@pytest.mark.parametrize("seed", _FUZZ_SEEDS)
+def test_random_architectures_against_oracle(ctx, seed):
+    """Model shapes beyond the fixtures: random segment lists (optional / partial / barcode / fingerprint / spacer / G /
+    read segments of random sizes), models from the library's own builder, reads with substitutions, indels, Ns and a
+    share of unrelated sequences; both kernels must equal the oracle bit for bit."""
+    from oracle import pyoracle
+    segs, seq, offs, md, art, nthreads = _random_case(seed)
+    thr = float(md["threshold"])
     ores, olab, oseq = pyoracle.label_batch(pyoracle.OracleModel(md), seq, offs, thr, int(md["minlen"]), int(md["dust"]),
                                             nthreads, artifacts=art)
     res, labels, seq_after = _run(ctx, md, seq, offs, threshold=thr)
@@ -994,15 +1002,12 @@ def test_windowed_architectures_against_oracle(ctx, case):
     assert np.array_equal(_bits(res3["b_score"]), _bits(ores["b_score"])), segs
 
 
-@pytest.mark.parametrize("nb,linker_first,umi", [(60, False, True), (96, False, True), (96, True, False), (62, True, True), (97, False, False)],
-                         ids=["H64-first", "H100-first", "H100-behind-5p-linker", "H67-behind-5p-linker", "H99-b97-r"])
-def test_many_label_architectures_against_oracle(ctx, nb, linker_first, umi):
-    """Architectures at and near the reference's limit of 100 HMMs (total_prob[100], barcode_hmm.c:4186): the run-time HMM
-    loop, the workspace label DP (:4447-4472 over > 32 labels) and -- with the big segment first -- the in-sweep label sums,
-    and with a 5' linker in front of it the run-wise label DP.  Models from the library's own builder; reads with
-    substitutions, indels, Ns, wrong-length UMIs, non-barcodes, short inserts and unrelated sequences; both kernels equal the
-    oracle bit for bit."""
-    from oracle import pyoracle
+_MANY_LABEL_CASES = [(60, False, True), (96, False, True), (96, True, False), (62, True, True), (97, False, False)]
+
+
+def _many_label_case(nb, linker_first, umi):
+    """Segments, 330 reads and the builder's model (threshold 1.0, minlen 16, dust 100) of one many-label architecture (also read by
+    tools/plan_survey.py)."""
     from tagdust_amd import lib as tdlib
     rng = np.random.RandomState(4000 + nb + 7 * linker_first)
 
@@ -1046,8 +1051,21 @@ def test_many_label_architectures_against_oracle(ctx, nb, linker_first, umi):
     seq = np.concatenate(reads)
     md, _ = tdlib.build_model(segs, seq, offs, 0.05, 0.1)
     assert int(md["H"]) == nb + 1 + (1 if umi else 0) + 1 + (1 if nb != 97 else 0) + (1 if linker_first else 0)
+    md.update(threshold=1.0, minlen=16, dust=100)
+    return segs, seq, offs, md
+
+
+@pytest.mark.parametrize("nb,linker_first,umi", _MANY_LABEL_CASES,
+                         ids=["H64-first", "H100-first", "H100-behind-5p-linker", "H67-behind-5p-linker", "H99-b97-r"])
+def test_many_label_architectures_against_oracle(ctx, nb, linker_first, umi):
+    """Architectures at and near the reference's limit of 100 HMMs (total_prob[100], barcode_hmm.c:4186): the run-time HMM
+    loop, the workspace label DP (:4447-4472 over > 32 labels) and -- with the big segment first -- the in-sweep label sums,
+    and with a 5' linker in front of it the run-wise label DP.  Models from the library's own builder; reads with
+    substitutions, indels, Ns, wrong-length UMIs, non-barcodes, short inserts and unrelated sequences; both kernels equal the
+    oracle bit for bit."""
+    from oracle import pyoracle
+    segs, seq, offs, md = _many_label_case(nb, linker_first, umi)
     thr = 1.0
-    md.update(threshold=thr, minlen=16, dust=100)
     ores, olab, oseq = pyoracle.label_batch(pyoracle.OracleModel(md), seq, offs, thr, 16, 100, 16)
     assert len(set(ores["read_type"].tolist())) >= 3
     res, labels, seq_after = _run(ctx, md, seq, offs, threshold=thr)

@@ -408,8 +408,62 @@ def test_other_modes_add_nothing(ctx):
     assert len(ent) == 0 and not any(tot.values())
 
 
+def test_full_sheet_behind_the_specialised_kernel():
+    """Two 16-barcode 8-nt indices around a spacer (tests/plan_shapes.py: both segments in the run-time HMM loop, barcodes dealt
+    round-robin so that all 256 pairs occur) under a sheet of TD_SAMPLES_MAX = 255 rows in a shuffled order -- every pair but one:
+    sample index 254, the binary search over a full row[], and the one pair left out counted as unlisted."""
+    import plan_shapes
+    from oracle import pyoracle
+    from tagdust_amd import TagdustHip, RESULT_DTYPE, lib as tdlib
+    segs, seq, offs, md = plan_shapes.make_case(*plan_shapes.SAMPLES_SHAPE)
+    thr = float(md["threshold"])
+    ores, olab, _ = pyoracle.label_batch(pyoracle.OracleModel(md), seq, offs, thr, int(md["minlen"]), int(md["dust"]), 4)
+    res = np.zeros(len(ores), RESULT_DTYPE)
+    for f in RESULT_DTYPE.names:
+        res[f] = ores["Q" if f == "mapq" else f]
+    left_out = (5, 9)
+    rows = [(a, b) for a in range(16) for b in range(16) if (a, b) != left_out]
+    sheet = [rows[k] for k in np.random.RandomState(3).permutation(len(rows))]
+    assert len(sheet) == tdlib.SAMPLES_MAX == 255
+    want, want_ent, want_tot = tdlib.samples_host(md, sheet, offs, res, olab)
+    print("yardstick totals", want_tot, "entries", len(want_ent))
+    counts = dict(pairs(want_ent))
+    assert counts.get(tdlib.samples_key(list(left_out)), 0) > 0 and want_tot["unlisted"] >= counts[tdlib.samples_key(list(left_out))]
+    assert all(counts.get(tdlib.samples_key(list(r)), 0) > 0 for r in sheet)         # every sample has a read ...
+    kept = want["read_type"] == SUCCESS
+    assert set((want["barcode"][kept] & 0xFF).tolist()) == set(range(255))              # ... index 254 among them
+    assert want_tot["assigned"] >= 255 and want_tot["incomplete"] >= 1 and want_tot["overflow"] == 0
+    ctx = TagdustHip(0)
+    try:
+        ctx.set_option("specialize", 1)
+        ctx.upload_model(md)
+        ctx.set_params(thr, int(md["minlen"]), int(md["dust"]))
+        ctx.upload_batch(seq, offs)
+        ctx.run()
+        plain = ctx.download()
+        assert np.array_equal(plain[0]["read_type"], res["read_type"]) and np.array_equal(plain[0]["barcode"], res["barcode"])
+        assert np.array_equal(plain[1], olab)
+        ctx.samples_enable(sheet, None, 16)
+        assert ctx.get_option("samples") == 255
+        ctx.upload_batch(seq, offs)
+        ctx.run()
+        got = ctx.download()
+        ent, tot = ctx.samples()
+        assert ctx.get_option("spec_state") == 3 and ctx.get_option("spec_batches_generic") == 0
+        assert ctx.samples_name(254) == "S255" and ctx.samples_name(255) is None
+    finally:
+        ctx.close()
+    print("device totals", tot)
+    same_but_for_the_rewrite(got, plain, want)
+    assert tot == want_tot and pairs(ent) == pairs(want_ent)
+    check_identities(ent, tot)
+    unlisted = (plain[0]["read_type"] == SUCCESS) & (got[0]["read_type"] == DEMOTED)
+    assert int(unlisted.sum()) == tot["unlisted"] + tot["incomplete"]
+    assert dict(pairs(ent))[tdlib.samples_key(list(left_out))] == counts[tdlib.samples_key(list(left_out))]
+
+
 # ---- the command ----
-SAMPLE_NAMES = ["s%d" % (k + 1) for k in range(len(SHEET))]
+SAMPLE_NAMES =["s%d" % (k + 1) for k in range(len(SHEET))]
 
 
 def fastq(seq, offs):
