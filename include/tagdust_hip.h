@@ -63,6 +63,10 @@ extern "C" {
  * (tagdust_molecules.h, td_mol_dedup_enable) and counted by td_counts_get under the outcome it was decoded with; the writers write
  * such a record to no file */
 #define TD_EXTRACT_DUPLICATE                  7
+/* not an outcome of the reference: an extracted read with more low-quality barcode / UMI bases than allowed, set only while the
+ * base-quality filter is on (tagdust_quality.h, td_qual_enable) and counted by td_counts_get under the outcome it was decoded with
+ * (there is no slot 8); the writers write such a record to the _un file like any other read that was not extracted */
+#define TD_EXTRACT_FAIL_LOW_BASE_QUALITY      8
 
 /* transition indices of td_model_desc.trans, src/barcode_hmm.h:87-96 */
 enum { TD_MM = 0, TD_MI = 1, TD_MD = 2, TD_II = 3, TD_IM = 4, TD_DD = 5, TD_DM = 6, TD_MSKIP = 7, TD_ISKIP = 8 };

@@ -23,6 +23,7 @@
 #include "tagdust_census.h"
 #include "tagdust_molecules.h"
 #include "tagdust_samples.h"
+#include "tagdust_quality.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -105,6 +106,16 @@ typedef struct td_run_opts {
 	                                    combinations no sample has; <out>_molecules.txt labels its rows with the sample names.  Refused with
 	                                    -start / -end and when no input file's architecture has a 'B' segment; barcodes spread over several
 	                                    input files are not joined (the controller's rule of one barcode file stays) */
+	int32_t  min_base_quality;       /* --min-base-quality Q   [0 = off]: the base-quality filter (tagdust_quality.h, td_qual_enable): an
+	                                    extracted read with more than max_low_bases barcode / UMI bases below Q (1..93) goes to the _un file
+	                                    and is neither assigned, counted nor kept by --dedup.  Adds a "quality:" line to the plan and one line
+	                                    behind the summary's counts to the log.  Refused with -start / -end, with more than one device, with
+	                                    more than one decoded file (--mate-bases' layout, barcode and UMI in read 1 and R:N files beside
+	                                    it, is in), for a read-only architecture and for FASTA input (the run fails at the first record
+	                                    without a quality line) */
+	int32_t  max_low_bases;          /* --max-low-bases K      [0] */
+	int32_t  quality_segments;       /* --quality-segments B|F|BF   [BF = TD_QUAL_SEG_B | TD_QUAL_SEG_F]: the segments whose bases are judged */
+	int32_t  quality_offset;         /* --quality-offset 33|64 [33] */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -191,6 +202,10 @@ typedef struct td_run_report {
 	td_samples_totals samples_totals;         /* summed over the devices.  With one file on one device `counts` are the context's own tally
 	                                             (td_counts_get), and the reads that lost their extraction here are moved from slot
 	                                             TD_EXTRACT_SUCCESS to slot TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND; the barcode bins stay the decode kernel's */
+	int32_t  quality;                         /* 1: the run dropped reads by base quality (--min-base-quality) */
+	td_qual_totals quality_totals;            /* ... td_qual_get's totals of the decoded file's context.  With one file on one device the reads
+	                                             it failed are moved from slot TD_EXTRACT_SUCCESS to slot TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND
+	                                             of `counts`, as the samples rewrite's are: the log's "extracted" agrees with the files */
 } td_run_report;
 /* In the controller's order: architectures per file, statistics over each file's head, thresholds, models, the run, the log.
  * A failure before the first batch leaves no output files behind; one during the run leaves them as they are and says so.  The

@@ -51,9 +51,9 @@ void slot_release(TdSlot& s)
 {
 	void* dev[] = { s.d_raw, s.d_offs, s.d_read_at, s.d_keys, s.d_vals, s.d_sort_tmp, s.d_packed, s.d_lens, s.d_art_left,
 	                s.d_out, s.d_res, s.d_seq, s.d_lab, s.d_keepo, s.d_rle, s.d_runs, s.d_judged, s.d_mate_raw, s.d_mate_offs, s.d_mate_w,
-	                s.d_mate_n, s.d_mate_type };
+	                s.d_mate_n, s.d_mate_type, s.d_qual_w };
 	for (void* p : dev) if (p) (void)hipFree(p);
-	void* pinned[] = { s.h_raw, s.h_offs, s.h_res, s.h_seq, s.h_lab, s.h_keepo, s.h_rle, s.h_mate_raw, s.h_mate_offs };
+	void* pinned[] = { s.h_raw, s.h_offs, s.h_res, s.h_seq, s.h_lab, s.h_keepo, s.h_rle, s.h_mate_raw, s.h_mate_offs, s.h_qual_w };
 	for (void* p : pinned) if (p) (void)hipHostFree(p);
 	hipEvent_t ev[] = { s.ev_up, s.ev_k0, s.ev_k1, s.ev_done, s.ev_down, s.ev_pack, s.ev_hits };
 	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -128,7 +128,7 @@ static int ensure_workspace(td_ctx* c, TdSlot& s)
 
 // Reads -> device, sorted and packed.  Copies go on `up` (the compute stream itself for the synchronous calls); the
 // kernels on the compute stream wait for them through ev_up.
-static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* bases, int is_ascii, const int64_t* offs, int64_t n, hipStream_t up, bool with_workspace = true, bool take_mate = false)
+static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* bases, int is_ascii, const int64_t* offs, int64_t n, hipStream_t up, bool with_workspace = true, bool take_mate = false, bool take_qual = false)
 {
 	s.reset_staged(route);   // nothing of the slot's previous batch survives (nor of its launch, nor of its download)
 	if (with_workspace && !c->have_model) return fail(c, "td_batch_upload: no model uploaded");
@@ -191,6 +191,7 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 	HIPCHK(c, hipMemcpyAsync(s.d_offs, s.h_offs, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, up));
 	if (n_bases > 0) HIPCHK(c, hipMemcpyAsync(s.d_raw, src, (size_t)n_bases, hipMemcpyHostToDevice, up));
 	if (take_mate && mol_mate_stage(c, s, n, up) != TD_OK) return TD_FAIL;   // mate mode: the named mate batch travels with its reads
+	if (take_qual && qual_stage(c, s, offs, n, up) != TD_OK) return TD_FAIL;  // the base-quality filter: the named qualities, one bit per base
 	if (up != s.aux) {
 		HIPCHK(c, hipEventRecord(s.ev_up, up));
 		HIPCHK(c, hipStreamWaitEvent(s.aux, s.ev_up, 0));
@@ -266,6 +267,16 @@ static int launch_begin(td_ctx* c, TdSlot& s, int mode, bool& empty)
 		return fail(c, "td_run: sample assignment is %s (td_samples_%s) and the resident batch of %lld reads was staged %s: upload it again; "
 		            "nothing was assigned", c->samples.on ? "on" : "off", c->samples.on ? "enable" : "disable", (long long)s.n_reads,
 		            s.samples_gen ? (c->samples.on ? "under an earlier sheet" : "while it was on") : "while it was off");
+	// the base-quality filter: a batch staged without its qualities, or under another enable, has no verdicts to give
+	if (mode == TD_MODE_GET_LABEL && s.qual_gen != (c->quality.on ? c->quality.gen : 0)) {
+		c->quality.named = false;
+		if (!c->quality.on)
+			return fail(c, "td_run: the base-quality filter is off (td_qual_disable) and the resident batch of %lld reads was staged while it was on: "
+			            "upload it again; nothing was decoded", (long long)s.n_reads);
+		return fail(c, "td_run: the base-quality filter is on (td_qual_enable) and the resident batch of %lld reads was staged %s: td_qual_next "
+		            "first, then td_batch_upload; nothing was decoded", (long long)s.n_reads,
+		            s.qual_gen ? "under an earlier td_qual_enable" : "without qualities named for as many reads");
+	}
 	s.reset_decoded();   // (runs_cap above all: a launch of the generic kernel, or an empty batch, must not hand the label runs of this
 	                     // slot's previous launch to the finish kernel)
 	s.mode = mode;
@@ -287,7 +298,8 @@ static int slot_art_left(td_ctx* c, TdSlot& s)
 // -- the -ref hits when it ran with the filter, census and molecule count over a labelled batch -- and the slot has run.  With the
 // mate filter on, the join of the mates' verdicts stands in front of all of them: they read one outcome per pair.  Sample assignment
 // (td_samples.hip) rewrites outcome and barcode behind the join and the hits, in front of census and molecule count: they read one
-// sample per read.
+// sample per read.  The base-quality filter (td_quality.hip) gives its verdicts behind the join and the hits and in front of all
+// three: a read it drops is neither assigned nor counted.
 static int launch_end(td_ctx* c, TdSlot& s, bool with_artifacts)
 {
 	HIPCHK(c, hipEventRecord(s.ev_k1, s.cs));
@@ -295,6 +307,7 @@ static int launch_end(td_ctx* c, TdSlot& s, bool with_artifacts)
 	point_outputs(o, s.d_out, out_layout(s.n_tiles, s.lmax, s.nw1));
 	if (c->molecules.mate.filter && s.mode == TD_MODE_GET_LABEL && mol_mate_join(c, s, o.out_type) != TD_OK) return TD_FAIL;
 	if (with_artifacts && slot_count_hits(c, s, o.out_type) != TD_OK) return TD_FAIL;
+	if (c->quality.on && s.mode == TD_MODE_GET_LABEL && qual_slot(c, s, o.out_type, o.out_labels) != TD_OK) return TD_FAIL;
 	if (c->samples.on && s.mode == TD_MODE_GET_LABEL && samples_slot(c, s, o.out_type, o.out_barcode, o.out_labels) != TD_OK) return TD_FAIL;
 	if (c->census.on && s.mode == TD_MODE_GET_LABEL && census_count_slot(c, s, o.out_type, o.out_labels) != TD_OK) return TD_FAIL;
 	// the molecule count last: dedup's second pass, the last launch in there, rewrites the outcomes the counts above read
@@ -560,7 +573,9 @@ static int upload_common(td_ctx* c, const void* bases, int is_ascii, const int64
 	const TdRoute rt = sync_route(c);
 	// mate mode: the mode is td_run's to say, so the named mate batch is taken now when it is this batch's
 	const bool take_mate = c->molecules.mate.bases > 0 && c->molecules.mate.named && c->molecules.mate.reads == n;
-	if (slot_stage(c, s, rt, bases, is_ascii, offs, n, c->stream, true, take_mate) != TD_OK) return TD_FAIL;
+	// ... and so are the named qualities while the base-quality filter is on
+	const bool take_qual = c->quality.on && c->quality.named && c->quality.next_reads == n && offs && n >= 0;
+	if (slot_stage(c, s, rt, bases, is_ascii, offs, n, c->stream, true, take_mate, take_qual) != TD_OK) return TD_FAIL;
 	HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller may reuse its buffers
 	c->last_slot = 0;
 	return TD_OK;
@@ -617,6 +632,8 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 	if (spec_handover(c, false) != TD_OK) return TD_FAIL;   // a finished background compile takes over before any geometry is chosen
 	const bool take_mate = c->molecules.mate.bases > 0 && mode == TD_MODE_GET_LABEL;   // (no other mode needs or consumes a mate)
 	if (take_mate && mol_mate_check(c, n_reads, "td_submit") != TD_OK) return TD_FAIL;
+	const bool take_qual = c->quality.on && mode == TD_MODE_GET_LABEL;
+	if (take_qual && qual_check(c, n_reads, "td_submit") != TD_OK) return TD_FAIL;
 	TdSlot& s = c->slots[k];
 	TdRoute rt = sync_route(c);
 	rt.pipelined = true;
@@ -626,7 +643,7 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 		c->submit_parity ^= 1;
 		rt.aux = c->s_aux; rt.fin = c->s_fin;
 	}
-	if (slot_stage(c, s, rt, bases, is_ascii != 0, offs, n_reads, c->s_up, mode != TD_MODE_RNA_DUST, take_mate) != TD_OK) return TD_FAIL;
+	if (slot_stage(c, s, rt, bases, is_ascii != 0, offs, n_reads, c->s_up, mode != TD_MODE_RNA_DUST, take_mate, take_qual) != TD_OK) return TD_FAIL;
 	if (slot_decode(c, s, mode, labels != nullptr) != TD_OK) return TD_FAIL;
 	if (slot_fetch_begin(c, s, res, labels, seq_out, true) != TD_OK) return TD_FAIL;
 	// "returns once the reads have left the caller's buffers": a page-locked source is read by the DMA engine itself, so wait

@@ -17,6 +17,7 @@
 #include "td_census.h"
 #include "td_molecules.h"
 #include "td_samples.h"
+#include "td_quality.h"
 
 #define TD_HIDDEN __attribute__((visibility("hidden")))
 #define TD_MAX_PIPELINE 4
@@ -53,6 +54,8 @@ struct TdStaged : TdRoute {
 	bool mate_typed = false;  // ... and the filter kernel ran (dust != 0 or artifacts set): d_mate_type holds this batch's mate types;
 	                          // judged and not typed: every mate type is 0, d_mate_type is not read
 	int32_t samples_gen = 0;  // sample assignment (td_samples.hip) as it stood when the batch was staged: the enable's number, 0 = off
+	int32_t qual_gen = 0;     // the base-quality filter (td_quality.hip): the enable under which the batch's qualities were staged, 0 = none were
+	int64_t qual_words = 0;   // ... and the words of d_qual_w that are this batch's (the spare zero word included)
 	const uint8_t* raw_host = nullptr;   // the batch's bases on the host, valid until the batch has been waited for: the pinned staging
 	                                     // copy, or the caller's own page-locked buffer under the "stable_input" contract; else NULL
 	TdStageBatch sb{};
@@ -109,6 +112,9 @@ struct TdSlot : TdStaged, TdDecoded, TdFetch {
 	unsigned long long* d_mate_w = nullptr; size_t cap_mate_w = 0;
 	uint8_t* d_mate_n = nullptr;   size_t cap_mate_n = 0;
 	int32_t* d_mate_type = nullptr; size_t cap_mate_type = 0;   // the mate filter's verdicts (td_mate_filter.hip), allocated by its first launch
+	// the base-quality filter (td_quality.hip): one low flag per base of the batch, packed on the host into page-locked words
+	uint32_t* d_qual_w = nullptr;  size_t cap_qual_w = 0;
+	uint32_t* h_qual_w = nullptr;  size_t cap_h_qual_w = 0;
 	uint8_t* h_mate_raw = nullptr; size_t cap_h_mate_raw = 0;   // (pinned staging, as h_raw and h_offs)
 	int64_t* h_mate_offs = nullptr; size_t cap_h_mate_offs = 0;
 	uint32_t* h_keepo = nullptr;   size_t cap_h_keepo = 0;
@@ -210,6 +216,7 @@ struct td_ctx {
 	TdCensusState census;       // include/tagdust_census.h: off unless td_census_enable switched it on
 	TdMolState molecules;       // include/tagdust_molecules.h: off unless td_mol_enable switched it on
 	TdSamplesState samples;     // include/tagdust_samples.h: off unless td_samples_enable switched it on
+	TdQualState quality;        // include/tagdust_quality.h: off unless td_qual_enable switched it on
 	int64_t win_first = 0, win_total = 0;   // td_set_batch_window
 	int32_t match_start = 0, match_len = 0;  // td_set_window (-start / -end); match_len = 0: whole reads
 	// batches: slot 0 is the resident batch of the synchronous calls; td_submit rotates over pipeline_depth slots

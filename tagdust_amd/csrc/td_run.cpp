@@ -171,7 +171,8 @@ struct OptSpec { const char* name; int arg; int id; };
 enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MINLEN, O_DUST, O_REF, O_FE, O_START, O_END, O_SEED,
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
        O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS, O_DEDUP, O_COLLAPSE,
-       O_DEDUP_COLLAPSED, O_MATE_BASES, O_MATE_FILTER, O_SAMPLES, O_UNSUPPORTED = 100 };
+       O_DEDUP_COLLAPSED, O_MATE_BASES, O_MATE_FILTER, O_SAMPLES, O_MIN_BASE_QUALITY, O_MAX_LOW_BASES, O_QUALITY_SEGMENTS, O_QUALITY_OFFSET,
+       O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
 	{ "7", 1, O_SEG + 6 }, { "8", 1, O_SEG + 7 }, { "9", 1, O_SEG + 8 }, { "10", 1, O_SEG + 9 },
@@ -198,7 +199,8 @@ const OptSpec kOwnOpts[] = {
 	{ "fingerprint-seq", 0, O_FINGER_SEQ }, { "molecules", 0, O_MOLECULES }, { "molecules-prefix", 1, O_MOLECULES_PREFIX },
 	{ "molecules-slots", 1, O_MOLECULES_SLOTS }, { "dedup", 0, O_DEDUP }, { "collapse-umis", 0, O_COLLAPSE },
 	{ "dedup-collapsed", 0, O_DEDUP_COLLAPSED }, { "mate-bases", 1, O_MATE_BASES }, { "mate-filter", 0, O_MATE_FILTER },
-	{ "samples", 1, O_SAMPLES },
+	{ "samples", 1, O_SAMPLES }, { "min-base-quality", 1, O_MIN_BASE_QUALITY }, { "max-low-bases", 1, O_MAX_LOW_BASES },
+	{ "quality-segments", 1, O_QUALITY_SEGMENTS }, { "quality-offset", 1, O_QUALITY_OFFSET },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -239,6 +241,8 @@ extern "C" td_run_opts* td_run_opts_new(void)
 	o->unknown_slots_log2 = 20;
 	o->molecules_prefix = TD_MOL_DEFAULT_PREFIX;
 	o->molecules_slots_log2 = TD_MOL_DEFAULT_LOG2_SLOTS;
+	o->quality_segments = TD_QUAL_SEG_B | TD_QUAL_SEG_F;
+	o->quality_offset = 33;
 	return o;
 }
 
@@ -309,7 +313,13 @@ extern "C" const char* td_run_usage(void)
 	       "\t                            read whose mate fails is neither counted nor kept by --dedup (lifts -dust 0 / no -ref)\n"
 	       "\t--samples FILE              combinatorial barcodes: FILE lists one sample per line, the name and one barcode per B segment;\n"
 	       "\t                            a read is written to <output prefix>_BC_<name>.fq by ALL its barcodes, to _un when they are\n"
-	       "\t                            incomplete or name no sample; the counts go to <output prefix>_samples.txt\n\n";
+	       "\t                            incomplete or name no sample; the counts go to <output prefix>_samples.txt\n"
+	       "\t--min-base-quality Q        drop an extracted read with low-quality barcode or UMI bases: more than --max-low-bases of them\n"
+	       "\t                            below Q, 1..93; it goes to _un and is neither counted nor kept by --dedup (FASTQ input, one\n"
+	       "\t                            device, one decoded file; not with -start / -end)\n"
+	       "\t--max-low-bases K           low-quality barcode / UMI bases a read may have [0]\n"
+	       "\t--quality-segments B|F|BF   judge the bases of the barcode segments, of the fingerprint segments, or of both [BF]\n"
+	       "\t--quality-offset 33|64      what a quality character's code is counted from [33]\n\n";
 }
 
 extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts** out, char* err, size_t errcap)
@@ -328,6 +338,7 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 	for (int k = 0; k < argc; k++) o->argv[k] = dup_str(argv[k]);
 	o->argc = argc;
 	std::vector<std::string> files;
+	bool given_quality_detail = false;   // --max-low-bases / --quality-segments / --quality-offset: they say how --min-base-quality judges
 	for (int k = 1; k < argc; k++) {
 		const std::string a = argv[k];
 		if (a.size() < 2 || a[0] != '-') { files.push_back(a); continue; }   // an input file ("-" = stdin)
@@ -388,6 +399,27 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 			break;
 		case O_MATE_FILTER: o->mate_filter = 1; break;
 		case O_SAMPLES: free(o->samples_file); o->samples_file = dup_str(v); break;
+		case O_MIN_BASE_QUALITY:
+			o->min_base_quality = atoi(v);
+			if (o->min_base_quality < 1 || o->min_base_quality > 93) return bad("--min-base-quality: need a quality Q of 1..93");
+			break;
+		case O_MAX_LOW_BASES:
+			o->max_low_bases = atoi(v);
+			if (o->max_low_bases < 0 || (v[0] < '0' || v[0] > '9')) return bad("--max-low-bases: need a number of bases K >= 0");
+			given_quality_detail = true;
+			break;
+		case O_QUALITY_SEGMENTS:
+			if (!strcmp(v, "B")) o->quality_segments = TD_QUAL_SEG_B;
+			else if (!strcmp(v, "F")) o->quality_segments = TD_QUAL_SEG_F;
+			else if (!strcmp(v, "BF") || !strcmp(v, "FB")) o->quality_segments = TD_QUAL_SEG_B | TD_QUAL_SEG_F;
+			else return bad("--quality-segments: need B, F or BF");
+			given_quality_detail = true;
+			break;
+		case O_QUALITY_OFFSET:
+			o->quality_offset = atoi(v);
+			if (o->quality_offset != 33 && o->quality_offset != 64) return bad("--quality-offset: need 33 or 64");
+			given_quality_detail = true;
+			break;
 		default: return bad("unknown option " + a);
 		}
 	}
@@ -395,6 +427,8 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 	if (o->dedup) o->molecules = 1;   // the duplicates are those of the molecule count
 	if (o->collapse_umis) o->molecules = 1;   // ... and so are the molecules that are collapsed
 	if (o->mate_bases) o->molecules = 1;      // ... and the mate joins the molecule count's key
+	if (given_quality_detail && !o->min_base_quality)
+		return bad("--max-low-bases / --quality-segments / --quality-offset need --min-base-quality: they say how it judges");
 	if (o->num_threads < 1) return bad("option -t: need at least one thread");
 	if (o->host_threads < 0 || o->batch_reads < 0) return bad("--host-threads / --batch-reads: negative value");
 	if (o->unknown_slots_log2 < 4 || o->unknown_slots_log2 > 26) return bad("--unknown-barcodes-slots: need 4..26 (the table has 2^N slots)");
@@ -430,6 +464,7 @@ struct td_run_plan_t {
 	std::string ref_file;                    // -ref, for the plan's "mate:" line
 	int mol_file = 0, mate_file = -1;        // ... the one decoded file and its mate, once every architecture is known
 	std::string samples_line;                // --samples: the plan's "samples:" line
+	std::string quality_line;                // --min-base-quality: the plan's "quality:" line
 };
 
 namespace {
@@ -569,6 +604,15 @@ int decide_outputs(const td_run_opts* o, const std::vector<const td_arch*>& arch
 			return run_fail("--collapse-umis: the architecture has no fingerprint (F) segment: there is no UMI whose neighbours could be collapsed.");
 		names.push_back(molecules_file_name(o));
 	}
+	if (o->min_base_quality) {   // the base-quality filter judges the one decoded file's barcode / UMI bases
+		int n_decoded = 0, dec = 0;
+		for (size_t k = 0; k < archs.size(); k++) if (!is_read_only(archs[k]) && n_decoded++ == 0) dec = (int)k;
+		if (n_decoded == 0) return run_fail("--min-base-quality: the architecture is a single read segment: there is no model whose labels mark a barcode or a fingerprint.");
+		if (n_decoded > 1)
+			return run_fail("--min-base-quality: exactly one input file may have an architecture other than R:N (%d have): one file's verdicts are the run's.", n_decoded);
+		const bool b = (o->quality_segments & TD_QUAL_SEG_B) && has_barcode(archs[(size_t)dec]), f = (o->quality_segments & TD_QUAL_SEG_F) && has_fingerprint(archs[(size_t)dec]);
+		if (!b && !f) return run_fail("--min-base-quality: the architecture has no segment of the types --quality-segments names: there is no base to judge.");
+	}
 	if (bar_file >= 0 && !o->force)   // check_for_existing_demultiplexed_files_multiple, io.c:633-691 (made for the barcode file only)
 		for (auto& n : names)
 			if (file_exists(n)) return run_fail("Error: some output files already exists. (%s; --force overwrites)", n.c_str());
@@ -597,6 +641,10 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	if (o->samples_file && (o->matchstart != -1 || o->matchend != -1))
 		return run_fail("--samples cannot be combined with -start / -end: labels behind a window do not mark the barcodes.");
 	if (o->samples_file && !file_exists(o->samples_file)) return run_fail("--samples: the sample sheet %s does not exist.", o->samples_file);
+	if (o->min_base_quality && (o->matchstart != -1 || o->matchend != -1))
+		return run_fail("--min-base-quality cannot be combined with -start / -end: labels behind a window do not mark the bases.");
+	if (o->min_base_quality && o->n_devices > 1)
+		return run_fail("--min-base-quality needs exactly one device (%d given): a batch's quality lines travel with its reads to one context.", o->n_devices);
 	if (o->mate_bases) {
 		if (o->n_infiles < 2)
 			return run_fail("--mate-bases needs two or more input files (%d given): the mate is the record of a second file.", o->n_infiles);
@@ -679,6 +727,11 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 		}
 		p->samples_line += "\n";
 	}
+	if (o->min_base_quality)
+		p->quality_line = "quality: an extracted read with more than " + std::to_string(o->max_low_bases) + " bases below Q" + std::to_string(o->min_base_quality) +
+		                  " (offset " + std::to_string(o->quality_offset) + ") in its " +
+		                  (o->quality_segments == TD_QUAL_SEG_B ? "barcode" : (o->quality_segments == TD_QUAL_SEG_F ? "fingerprint" : "barcode or fingerprint")) +
+		                  " segments goes to _un and is neither assigned, counted nor kept by --dedup\n";
 	if (p->all_known && mate_filter_files(o, p->dust, p->use_ref, p->mol_file, p->mate_file) != TD_OK) return TD_FAIL;
 	*out = p.release();
 	return TD_OK;
@@ -713,6 +766,7 @@ extern "C" int64_t td_run_plan_describe(const td_run_plan_t* p, char* buf, int64
 		s += "\n";
 	}
 	s += p->samples_line;
+	s += p->quality_line;
 	if (p->all_known) {
 		s += "barcode file: " + (p->bar_file >= 0 ? std::to_string(p->bar_file) : std::string("none")) + "\n";
 		s += "output reads: " + std::to_string(p->num_out_reads) + "\n";
@@ -821,6 +875,9 @@ std::vector<std::string> summary_messages(const td_run_opts* o, const td_run_rep
 	addf("%d\tmatch artifacts:\n", (int)r->counts[TD_EXTRACT_FAIL_MATCHES_ARTIFACTS]);
 	for (int j = 0; j < r->n_artifacts; j++)
 		if (r->artifact_hits && r->artifact_hits[j]) addf("%d\t%s\n", (int)r->artifact_hits[j], r->artifact_names && r->artifact_names[j] ? r->artifact_names[j] : "");
+	// --min-base-quality: one line behind the counts (only with the option: a report made without it may end in front of these fields)
+	if (o->min_base_quality && r->quality)
+		addf("%d\tlow base quality in barcode / UMI (Q < %d, more than %d bases)\n", (int)r->quality_totals.failed, o->min_base_quality, o->max_low_bases);
 	return m;
 }
 
@@ -890,6 +947,7 @@ struct Run {
 	int mol_file = 0, mate_file = -1;     // the file whose contexts count molecules; with --mate-bases its mate, else -1
 	SampleSheet sheet;                    // --samples, resolved against the barcode file's architecture (no sample without the option)
 	bool device_counts = false;           // rep->counts are a context's own tally (td_counts_get), not the combined records'
+	int qual_file = -1;                   // --min-base-quality: the one decoded file, whose context judges (-1 without the option)
 
 	int head_limit() const { return o->flavour ? 1001000 : 1000001; }   // io.c:125-188 with num_query 1000 / 1 000 001
 
@@ -971,6 +1029,7 @@ struct Run {
 	int unknown_barcodes(int bar_file);
 	int molecules();
 	int samples(int bar_file);
+	int quality();
 
 	// Every device's entries of a file, merged: acc[n_acc] is the caller's to td_census_free (NULL after a failure), per[d] the
 	// totals of device d.  `get` is td_census_get or td_mol_entries.
@@ -1121,6 +1180,12 @@ int Run::execute()
 			// --samples: the contexts of the barcode file assign every extracted read by all its barcodes, in front of census and count
 			if (sheet.n() > 0 && k == bar_file &&
 			    td_samples_enable(c, sheet.tuples.data(), sheet.name_ptrs.data(), sheet.n(), 16) != TD_OK) return fail("%s", td_last_error(c));
+			// --min-base-quality: the context of the one decoded file drops extracted reads with low-quality barcode / UMI bases, in front
+			// of samples, census and count (the streaming run names every batch's quality lines)
+			if (o->min_base_quality && tables) {
+				if (td_qual_enable(c, o->min_base_quality, o->quality_offset, o->max_low_bases, o->quality_segments) != TD_OK) return fail("%s", td_last_error(c));
+				qual_file = k;
+			}
 			// --molecules: the contexts of the one input file (with --mate-bases: of the one decoded file) count its extracted reads per
 			// barcode, fingerprint and start of the read
 			if (k != mol_file) continue;
@@ -1148,6 +1213,7 @@ int Run::execute()
 		return fail("%s -- the run failed after it had started: the output files are incomplete and were left as they are", msg.c_str());
 	}
 
+	if (qual_file >= 0 && quality() != TD_OK) return TD_FAIL;
 	if (sheet.n() > 0 && samples(bar_file) != TD_OK) return TD_FAIL;
 	if (o->unknown_barcodes > 0 && unknown_barcodes(bar_file) != TD_OK) return TD_FAIL;
 	if (o->molecules && molecules() != TD_OK) return TD_FAIL;
@@ -1216,6 +1282,22 @@ int Run::unknown_barcodes(int bar_file)
 		fprintf(out, "%lld\t%s\t%s\t%d\n", (long long)acc[i].count, word, best >= 0 ? a->seqs[seg][best] : "-", best >= 0 ? best_d : -1);
 	}
 	fclose(out);
+	return TD_OK;
+}
+
+// --min-base-quality: the totals of the decoded file's context (one device); behind the summary's counts in the log
+int Run::quality()
+{
+	td_ctx* c = files[(size_t)qual_file].raw[0];
+	td_qual_totals t{};
+	if (td_qual_get(c, &t) != TD_OK) return fail("%s", td_last_error(c));
+	rep->quality = 1;
+	rep->quality_totals = t;
+	// a context's own tally is the decode kernel's: the reads that lost their extraction here move to "barcode / UMI not found"
+	if (device_counts) {
+		rep->counts[TD_EXTRACT_SUCCESS] -= t.failed;
+		rep->counts[TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND] += t.failed;
+	}
 	return TD_OK;
 }
 
@@ -1404,7 +1486,7 @@ int Run::run_files(td_stream_stats& st)
 			const double t0 = now_s();
 			if (td_stream_survey(c, o->infile[0], &so, &survey) != TD_OK) return run_fail("%s", td_io_last_error());
 			if (td_mol_dedup_freeze(c, nullptr) != TD_OK || td_counts_reset(c) != TD_OK || (o->unknown_barcodes > 0 && td_census_reset(c) != TD_OK) ||
-			    (sheet.n() > 0 && td_samples_reset(c) != TD_OK))
+			    (sheet.n() > 0 && td_samples_reset(c) != TD_OK) || (o->min_base_quality && td_qual_reset(c) != TD_OK))
 				return run_fail("%s", td_last_error(c));
 			rep->survey_s = now_s() - t0;
 		}

@@ -26,6 +26,7 @@
 
 #include "../../include/tagdust_molecules.h"   // td_mol_mate_next: pair mode of td_stream_run_multi
 #include "../../include/tagdust_samples.h"     // td_samples_name: the output files of a run with sample assignment on
+#include "../../include/tagdust_quality.h"     // td_qual_next: the quality lines of a file whose context has the base-quality filter on
 #include "td_stream_internal.h"
 
 using namespace tdstream;
@@ -76,6 +77,14 @@ int pipeline_depth(td_ctx* ctx)
 	return depth;
 }
 
+// the base-quality filter (tagdust_quality.h) is on in this context: its batches carry the records' quality lines
+bool quality_active(td_ctx* ctx)
+{
+	int32_t on = 0;
+	(void)td_get_option(ctx, "quality_filter", &on);
+	return on != 0;
+}
+
 bool artifacts_active(td_ctx* ctx)
 {
 	int32_t art = 0;
@@ -94,6 +103,7 @@ struct Target {                       // where the batches of one input file go
 	td_ctx* const* ctx;               // its context on each of the N devices; NULL: no device sees this file
 	bool rna;                         // run_rna_dust (TD_MODE_RNA_DUST: the reads come back unchanged) instead of the HMM
 	int mate = -1;                    // pair mode: the file whose batch is this file's mate batch (td_mol_mate_next), else -1
+	bool qual = false;                // the base-quality filter is on in ctx[0]: the batch's quality lines are named (td_qual_next)
 };
 
 // Starts the readers, runs the write stage on a thread of its own (`write` for every finished tuple in input order, then the
@@ -183,6 +193,7 @@ void run_stages(const std::string& prefix, RunError& err, const std::vector<std:
 				// (pair mode, one device: the tuple's batch of the mate file goes up with this one, on the same upload stream)
 				ok = (N == 1 || td_set_batch_window(ctx, lo, n) == TD_OK) &&
 				     (dev[(size_t)k].mate < 0 || td_mol_mate_next(ctx, t->b[(size_t)dev[(size_t)k].mate]->codes, t->b[(size_t)dev[(size_t)k].mate]->offs, n) == TD_OK) &&
+				     (!dev[(size_t)k].qual || r || td_qual_next(ctx, b->qual, hi - lo) == TD_OK) &&
 				     td_submit(ctx, b->codes, 0, b->offs + lo, hi - lo, r ? TD_MODE_RNA_DUST : TD_MODE_GET_LABEL, b->res + lo, nullptr,
 				               r ? nullptr : b->seq_out + b->offs[lo], &t->tickets[(size_t)(k * N + d)]) == TD_OK;
 				if (!ok) err.fail(prefix + td_last_error(ctx));
@@ -220,6 +231,8 @@ extern "C" int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* ar
 	RunError err;
 	std::vector<std::unique_ptr<Reader>> readers;
 	readers.emplace_back(new Reader(err, o, ctx == nullptr, true, o.n_threads));
+	const bool judged = ctx && quality_active(ctx);
+	readers[0]->want_qual = judged; readers[0]->path = in_path;
 	std::string why;
 	if (!readers[0]->src.open(in_path, o.block_bytes, why)) { td_io_set_error(why); return TD_FAIL; }
 	std::unique_ptr<Writer> w;
@@ -255,7 +268,7 @@ extern "C" int td_stream_run(td_ctx* ctx, const char* in_path, const td_arch* ar
 		return true;
 	};
 	td_ctx* const one[1] = { ctx };
-	run_stages("td_stream_run: ", err, readers, { Target{ ctx ? one : nullptr, false } }, 1, pipeline_depth(ctx), w.get(),
+	run_stages("td_stream_run: ", err, readers, { Target{ ctx ? one : nullptr, false, -1, judged } }, 1, pipeline_depth(ctx), w.get(),
 	           [](const Tuple&) { return std::string(); }, write, st);
 	if (!err.failed() && getenv("TD_STREAM_DEBUG"))
 		fprintf(stderr, "td_stream: formatting %.3f s, appends %.3f s beside it (write stage %.3f s)\n", w ? w->dbg_format : 0.0, w ? w->dbg_pwrite : 0.0, st.write_s);
@@ -276,11 +289,13 @@ extern "C" int td_stream_survey(td_ctx* ctx, const char* in_path, const td_strea
 	RunError err;
 	std::vector<std::unique_ptr<Reader>> readers;
 	readers.emplace_back(new Reader(err, o, false, true, o.n_threads));
+	const bool judged = quality_active(ctx);
+	readers[0]->want_qual = judged; readers[0]->path = in_path;
 	std::string why;
 	if (!readers[0]->src.open(in_path, o.block_bytes, why)) { td_io_set_error(why); return TD_FAIL; }
 	td_stream_stats st{};
 	td_ctx* const one[1] = { ctx };
-	run_stages("td_stream_survey: ", err, readers, { Target{ one, false } }, 1, pipeline_depth(ctx), nullptr,
+	run_stages("td_stream_survey: ", err, readers, { Target{ one, false, -1, judged } }, 1, pipeline_depth(ctx), nullptr,
 	           [](const Tuple&) { return std::string(); }, [](Tuple&) { return true; }, st);
 	st.wall_s = now_s() - t_start;
 	if (stats) *stats = st;
@@ -325,6 +340,7 @@ struct MultiPlan {
 	// pair mode (tagdust_molecules.h, mate mode): the contexts of the one decoded file report mate_bases > 0
 	int mol_file = -1, mate_file = -1;   // the decoded file and its mate: the first file in call order other than it (-1: no pair mode)
 	bool mate_filter = false;            // ... and its contexts report "mate_filter": the mate's outcome is joined on the device
+	int qual_file = -1;                  // the decoded file whose contexts report "quality_filter" (tagdust_quality.h), -1: none
 };
 
 // false: the files cannot make a run (td_io_set_error says why)
@@ -366,6 +382,7 @@ bool plan_multi(const td_stream_file* files, const int K, const int N, const int
 	for (int k = 0; k < K; k++) {
 		if (!files[k].ctx || m.rna[(size_t)k]) continue;
 		n_decoded++;
+		for (int d = 0; d < N; d++) if (quality_active(files[k].ctx[d]) && m.qual_file < 0) m.qual_file = k;
 		int32_t mb = 0;
 		(void)td_get_option(files[k].ctx[0], "mate_bases", &mb);
 		if (mb > 0 && decoded < 0) decoded = k;
@@ -376,6 +393,12 @@ bool plan_multi(const td_stream_file* files, const int K, const int N, const int
 		(void)td_get_option(files[decoded].ctx[0], "mate_filter", &mf);
 		(void)td_get_option(files[decoded].ctx[0], "dust", &mate_dust);
 		m.mate_filter = mf != 0;
+	}
+	// the base-quality filter: a batch's quality lines travel with its reads to one context, and one file's verdicts are the run's
+	if (m.qual_file >= 0 && (N > 1 || n_decoded != 1)) {
+		td_io_set_error("td_stream_run_multi: the base-quality filter is on (td_qual_enable) and " + (N > 1 ? std::to_string(N) + " devices are given: one device"
+		                : std::to_string(n_decoded) + " files are decoded: exactly one may be, every other file must be R:N"));
+		return false;
 	}
 	const int mate = decoded < 0 ? -1 : (decoded == 0 ? 1 : 0);
 	// the mate filter (tagdust_molecules.h): one mate's outcome is joined in front of the count, a third file's would come behind it
@@ -476,7 +499,8 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 		// (a file that is not decoded needs no page-locked buffers, nor does one whose reads come back unchanged need room for rewritten ones)
 		// (... but the mate file of pair mode does: its batches are uploaded from where they lie)
 		readers.emplace_back(new Reader(err, o, files[k].ctx == nullptr && k != m.mate_file, files[k].ctx != nullptr && !m.rna[(size_t)k], std::max(1, o.n_threads / K)));
-		dev.push_back(Target{ files[k].ctx, m.rna[(size_t)k] != 0, k == m.mol_file ? m.mate_file : -1 });
+		dev.push_back(Target{ files[k].ctx, m.rna[(size_t)k] != 0, k == m.mol_file ? m.mate_file : -1, k == m.qual_file });
+		readers.back()->want_qual = k == m.qual_file; readers.back()->path = files[k].path;
 		if (!readers.back()->src.open(files[k].path, o.block_bytes, why)) { td_io_set_error(why); return TD_FAIL; }
 	}
 
@@ -519,7 +543,8 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 			cbar[(size_t)i] = t.b[(size_t)(m.bar_file >= 0 ? m.bar_file : 0)]->res[i].barcode;
 			// the controller's counting, :354-384; a duplicate (dedup, tagdust_molecules.h) counts as the extracted read it was decoded
 			// as, under its barcode bin: what the single-file run's device counters do
-			const int32_t cc = (c & 0xFF) == TD_EXTRACT_DUPLICATE ? TD_EXTRACT_SUCCESS : c;
+			// ... and a read the base-quality filter dropped (tagdust_quality.h) as what its file says it is, not extracted: slot 3
+			const int32_t cc = (c & 0xFF) == TD_EXTRACT_DUPLICATE ? TD_EXTRACT_SUCCESS : (c == TD_EXTRACT_FAIL_LOW_BASE_QUALITY ? TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND : c);
 			cnt[cc & (TD_NUM_OUTCOME_SLOTS - 1)]++;
 			if (cc == TD_EXTRACT_SUCCESS && cbar[(size_t)i] >= 0) cnt[TD_NUM_OUTCOME_SLOTS + (cbar[(size_t)i] & 0xFF)]++;
 			// reference_fasta->mer_hash (:381): on the combined outcome, which is the largest of the files' -- of two files' hits the later sequence

@@ -138,6 +138,8 @@ struct Batch {
 	int64_t n = 0, n_bases = 0;
 	uint8_t* codes = nullptr;  size_t cap_codes = 0;
 	uint8_t* seq_out = nullptr; size_t cap_seq = 0;
+	uint8_t* qual = nullptr;   size_t cap_qual = 0;   // the records' quality lines, read i's at offs[i]: only for a file whose
+	                                                  // context has the base-quality filter on (Reader::want_qual)
 	int64_t* offs = nullptr;
 	td_read_result* res = nullptr;
 	std::vector<Piece> pieces;
@@ -173,6 +175,9 @@ struct Reader {
 	const bool dry;            // batch buffers in plain memory: a file that no device sees
 	const bool want_seq;       // page-locked room for rewritten sequences (not for a file that goes through TD_MODE_RNA_DUST)
 	const int parse_threads;
+	bool want_qual = false;    // the base-quality filter is on in the file's context (tagdust_quality.h): batches carry the quality
+	                           // lines, and a record without one (FASTA) ends the run; set before start()
+	std::string path;          // ... the file's name for that message
 	Source src;
 	std::unique_ptr<TdWorkers> parse_pool;
 	std::unique_ptr<Queue<Batch*>> ready, free_list;

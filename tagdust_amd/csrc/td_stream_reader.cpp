@@ -193,7 +193,7 @@ const size_t kCacheBytes = (size_t)1 << 30;
 
 size_t batch_bytes(const Batch* b)
 {
-	return b->cap_codes + b->cap_seq + (size_t)b->cap_reads * (sizeof(int64_t) + sizeof(td_read_result));
+	return b->cap_codes + b->cap_seq + b->cap_qual + (size_t)b->cap_reads * (sizeof(int64_t) + sizeof(td_read_result));
 }
 
 // batch buffers: page-locked for the device; plain memory for a parse-only run (no GPU runtime needed then)
@@ -253,7 +253,7 @@ void Reader::release(bool keep)
 			g_cache.push_back(q);
 			continue;
 		}
-		buf_free(dry, q->codes); buf_free(dry, q->seq_out); buf_free(dry, q->offs); buf_free(dry, q->res);
+		buf_free(dry, q->codes); buf_free(dry, q->seq_out); buf_free(dry, q->qual); buf_free(dry, q->offs); buf_free(dry, q->res);
 		delete q;
 	}
 	all.clear();
@@ -297,7 +297,8 @@ void Reader::allocator(int n_more)
 	for (int k = 0; k < n_more; k++) {
 		{ std::lock_guard<std::mutex> lk(all_mu); if (stop_alloc) return; }
 		Batch* b = new_batch();
-		if (!b || !grow_buf(dry, &b->codes, &b->cap_codes, hint, 0, hint) || (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, hint, 0, hint))) return;   // (the pipeline runs with what it has)
+		if (!b || !grow_buf(dry, &b->codes, &b->cap_codes, hint, 0, hint) || (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, hint, 0, hint)) ||
+		    (want_qual && !grow_buf(dry, &b->qual, &b->cap_qual, hint, 0, hint))) return;   // (the pipeline runs with what it has)
 		if (!free_list->push(b)) return;
 	}
 }
@@ -333,11 +334,20 @@ void Reader::producer()
 			// "Length of sequence and base qualities differ" ends the reference's run (io.c:1776-1781)
 			for (size_t i = 0; i < v.size(); i++)
 				if (v[i].qual_off >= 0 && v[i].qual_len != (v[i].seq_off >= 0 ? v[i].seq_len : 0)) { bad[(size_t)k] = (int64_t)i; break; }
+			// the base-quality filter has nothing to judge in a record without a quality line (FASTA)
+			if (want_qual && bad[(size_t)k] < 0)
+				for (size_t i = 0; i < v.size(); i++)
+					if (v[i].qual_off < 0) { bad[(size_t)k] = (int64_t)i; break; }
 		});
 		dbg_pass1 += now_s() - t0;
 		for (int k = 0; k < nchunk; k++)
 			if (bad[(size_t)k] >= 0) {
 				const TdRec& q = (*recs[(size_t)k])[(size_t)bad[(size_t)k]];
+				if (q.qual_off < 0) {
+					err.fail("td_stream_run: the base-quality filter is on and record \"" + std::string(blk->data + q.name_off, (size_t)(q.name_len < 60 ? q.name_len : 60)) +
+					         "\" of " + path + " has no quality line (FASTA): there is nothing to judge (run without --min-base-quality, or give FASTQ)");
+					return;
+				}
 				char msg[256];
 				snprintf(msg, sizeof msg, "td_stream_run: record \"%.*s\": sequence has %d characters, base qualities %d",
 				         q.name_len < 60 ? q.name_len : 60, blk->data + q.name_off, q.seq_off >= 0 ? q.seq_len : 0, q.qual_len);
@@ -374,7 +384,8 @@ void Reader::producer()
 				for (const Job& j : jobs) if (j.b == b) { keep = (size_t)b->offs[b->pieces[j.piece].first]; mine = true; break; }
 				if (!mine) continue;
 				if (!grow_buf(dry, &b->codes, &b->cap_codes, (size_t)b->n_bases + 1, keep, batch_hint) ||
-				    (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, (size_t)b->n_bases + 1, 0, batch_hint))) { err.fail("td_stream_run: page-locked memory exhausted"); return false; }
+				    (want_seq && !grow_buf(dry, &b->seq_out, &b->cap_seq, (size_t)b->n_bases + 1, 0, batch_hint)) ||
+				    (want_qual && !grow_buf(dry, &b->qual, &b->cap_qual, (size_t)b->n_bases + 1, keep, batch_hint))) { err.fail("td_stream_run: page-locked memory exhausted"); return false; }
 			}
 			dbg_grow += now_s() - tf0;
 			const double tf1 = now_s();
@@ -394,6 +405,8 @@ void Reader::producer()
 					uint8_t* dst = sb.b->codes + sb.b->offs[pc.first + (r - pc.lo)];
 					const unsigned char* sq = (const unsigned char*)pc.blk->data + q.seq_off;
 					td_encode_bases(sq, dst, q.seq_len);
+					// the base-quality filter: the quality line beside the codes (a record has one byte per base: checked above)
+					if (want_qual && q.qual_off >= 0) memcpy(sb.b->qual + sb.b->offs[pc.first + (r - pc.lo)], pc.blk->data + q.qual_off, (size_t)q.seq_len);
 				}
 			});
 			jobs.clear();
@@ -545,6 +558,6 @@ int td_stream_head(const char* path, int64_t limit, int32_t n_threads, std::vect
 extern "C" void td_stream_release(void)
 {
 	std::lock_guard<std::mutex> lk(g_cache_mu);
-	for (Batch* q : g_cache) { td_host_free(q->codes); td_host_free(q->seq_out); td_host_free(q->offs); td_host_free(q->res); delete q; }
+	for (Batch* q : g_cache) { td_host_free(q->codes); td_host_free(q->seq_out); td_host_free(q->qual); td_host_free(q->offs); td_host_free(q->res); delete q; }
 	g_cache.clear();
 }

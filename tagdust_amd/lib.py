@@ -60,6 +60,13 @@ SAMPLES_MAX_SEGMENTS = 4
 EXTRACT_SUCCESS = 0
 EXTRACT_FAIL_BAR_FINGER_NOT_FOUND = 3
 
+# include/tagdust_quality.h: the base-quality filter
+QUALITY_ABI_SYMBOLS = ["td_qual_pack", "td_qual_host", "td_qual_enable", "td_qual_disable", "td_qual_reset", "td_qual_get", "td_qual_next"]
+QUALITY_TOTALS = ("eligible", "passed", "failed", "low_bases")
+QUAL_SEG_B = 1
+QUAL_SEG_F = 2
+EXTRACT_FAIL_LOW_BASE_QUALITY = 8    # TD_EXTRACT_FAIL_LOW_BASE_QUALITY (include/tagdust_hip.h): not an outcome of the reference
+
 # include/tagdust_molecules.h: molecules per barcode
 MOL_ABI_SYMBOLS = ["td_mol_enable", "td_mol_disable", "td_mol_reset", "td_mol_entries", "td_mol_get", "td_mol_summarise", "td_mol_host",
                    "td_mol_key", "td_mol_key_bin", "td_mol_dedup_enable", "td_mol_dedup_disable", "td_mol_dedup_get", "td_mol_dedup_host",
@@ -642,6 +649,13 @@ class _RunOptsSamples(C.Structure):
     _fields_ = _RunOptsMate._fields_ + [("samples_file", C.c_char_p)]
 
 
+class _RunOptsQuality(C.Structure):
+    """td_run_opts as it is now: _RunOptsSamples -- whose last field tests/test_samples.py pins -- and the fields appended behind it;
+    this is the structure every td_run_* call is given"""
+    _fields_ = _RunOptsSamples._fields_ + [("min_base_quality", C.c_int32), ("max_low_bases", C.c_int32), ("quality_segments", C.c_int32),
+                                           ("quality_offset", C.c_int32)]
+
+
 class _CensusTotals(C.Structure):
     """td_census_totals (include/tagdust_census.h)"""
     _fields_ = [(f, C.c_int64) for f in CENSUS_TOTALS]
@@ -656,6 +670,19 @@ class _SamplesTotals(C.Structure):
 
     def as_dict(self):
         return {f: int(getattr(self, f)) for f in SAMPLES_TOTALS}
+
+
+class _QualParams(C.Structure):
+    """td_qual_params (include/tagdust_quality.h)"""
+    _fields_ = [("min_quality", C.c_int32), ("offset", C.c_int32), ("max_low", C.c_int32), ("segments", C.c_int32)]
+
+
+class _QualTotals(C.Structure):
+    """td_qual_totals (include/tagdust_quality.h)"""
+    _fields_ = [(f, C.c_int64) for f in QUALITY_TOTALS]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f in QUALITY_TOTALS}
 
 
 class _MolTotals(C.Structure):
@@ -707,26 +734,31 @@ class _RunReportSamples(C.Structure):
                                       ("samples_totals", _SamplesTotals)]
 
 
+class _RunReportQuality(C.Structure):
+    """td_run_report as it is now: _RunReportSamples and the fields appended behind it; this is the structure td_run_execute fills"""
+    _fields_ = _RunReportSamples._fields_ + [("quality", C.c_int32), ("quality_totals", _QualTotals)]
+
+
 def _run_lib():
     lib = load_library()
-    lib.td_run_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(_RunOptsSamples)), C.c_char_p, C.c_size_t]
-    lib.td_run_opts_free.argtypes = [C.POINTER(_RunOptsSamples)]
+    lib.td_run_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(_RunOptsQuality)), C.c_char_p, C.c_size_t]
+    lib.td_run_opts_free.argtypes = [C.POINTER(_RunOptsQuality)]
     lib.td_run_opts_free.restype = None
     lib.td_run_last_error.restype = C.c_char_p
-    lib.td_run_plan.argtypes = [C.POINTER(_RunOptsSamples), C.POINTER(C.c_void_p)]
+    lib.td_run_plan.argtypes = [C.POINTER(_RunOptsQuality), C.POINTER(C.c_void_p)]
     lib.td_run_plan_free.argtypes = [C.c_void_p]
     lib.td_run_plan_free.restype = None
     lib.td_run_plan_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.td_run_plan_describe.restype = C.c_int64
-    lib.td_run_output_files_describe.argtypes = [C.POINTER(_RunOptsSamples), C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_int64]
+    lib.td_run_output_files_describe.argtypes = [C.POINTER(_RunOptsQuality), C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_int64]
     lib.td_run_output_files_describe.restype = C.c_int64
     lib.td_run_arch_file_describe.argtypes = [C.c_char_p, C.c_char_p, C.c_int64]
     lib.td_run_arch_file_describe.restype = C.c_int64
-    lib.td_run_execute.argtypes = [C.POINTER(_RunOptsSamples), C.POINTER(_RunReportSamples)]
-    lib.td_run_report_clear.argtypes = [C.POINTER(_RunReportSamples)]
+    lib.td_run_execute.argtypes = [C.POINTER(_RunOptsQuality), C.POINTER(_RunReportQuality)]
+    lib.td_run_report_clear.argtypes = [C.POINTER(_RunReportQuality)]
     lib.td_run_report_clear.restype = None
     # (the summary reads the report's leading fields alone -- counts, threshold, artifacts: a _RunReport will do as well)
-    lib.td_run_format_summary.argtypes = [C.POINTER(_RunOptsSamples), C.c_void_p, C.c_char_p, C.c_int64]
+    lib.td_run_format_summary.argtypes = [C.POINTER(_RunOptsQuality), C.c_void_p, C.c_char_p, C.c_int64]
     lib.td_run_format_summary.restype = C.c_int64
     return lib
 
@@ -738,7 +770,7 @@ class RunOpts:
         self.lib = _run_lib()
         argv = [b"tagdust-hip"] + [os.fsencode(a) for a in args]
         arr = (C.c_char_p * len(argv))(*argv)
-        self.p = C.POINTER(_RunOptsSamples)()
+        self.p = C.POINTER(_RunOptsQuality)()
         err = C.create_string_buffer(1024)
         if self.lib.td_run_parse_args(len(argv), arr, C.byref(self.p), err, len(err)) != 0:
             self.p = None
@@ -800,7 +832,7 @@ def run_arch_file(path):
 def run_execute(args):
     """td_run_execute: a whole run from the tagdust command line (without the program name); returns the report as a dict."""
     o = RunOpts(args)
-    rep = _RunReportSamples()
+    rep = _RunReportQuality()
     try:
         rc = o.lib.td_run_execute(o.p, C.byref(rep))
         if rc != 0:
@@ -822,6 +854,7 @@ def run_execute(args):
             "dedup_collapsed": bool(rep.dedup_collapsed), "survey_s": float(rep.survey_s),
             "samples": _census_entries(rep.samples, int(rep.n_sample_keys)) if rep.n_samples else None,
             "samples_totals": rep.samples_totals.as_dict() if rep.n_samples else None,
+            "quality_totals": rep.quality_totals.as_dict() if rep.quality else None,
         }
     finally:
         o.lib.td_run_report_clear(C.byref(rep))
@@ -967,6 +1000,48 @@ def samples_key_calls(key):
     if lib.td_samples_key_calls(int(key), calls.ctypes.data, C.byref(m)) != 0:
         raise TdError(lib.td_last_error(None).decode())
     return [int(c) for c in calls[:m.value]]
+
+
+def _qual_lib():
+    lib = load_library()
+    lib.td_qual_pack.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    lib.td_qual_host.argtypes = [C.POINTER(_ModelDesc), C.POINTER(_QualParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(_QualTotals)]
+    lib.td_qual_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.td_qual_disable.argtypes = [C.c_void_p]
+    lib.td_qual_reset.argtypes = [C.c_void_p]
+    lib.td_qual_get.argtypes = [C.c_void_p, C.POINTER(_QualTotals)]
+    lib.td_qual_next.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    return lib
+
+
+def qual_pack(qual, thr):
+    """td_qual_pack: one low flag per quality byte, uint32 [(n + 31) // 32 + 1] with the spare zero word"""
+    lib = _qual_lib()
+    q = np.ascontiguousarray(qual, np.uint8)
+    words = np.full((len(q) + 31) // 32 + 1, 0xFFFFFFFF, np.uint32)   # (every word is the call's to write)
+    if lib.td_qual_pack(q.ctypes.data if len(q) else None, len(q), int(thr), words.ctypes.data) != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return words
+
+
+def qual_host(md, offs, res, labels, qual, min_quality, offset=33, max_low=0, segments=QUAL_SEG_B | QUAL_SEG_F):
+    """td_qual_host: the base-quality filter of a batch from host arrays (no GPU).  md: model mapping; res: RESULT_DTYPE records
+    (td_batch_download's, or the oracle's), left alone; labels as td_batch_download leaves them; qual: read i's bytes at offs[i].
+    Returns (the rewritten records, totals dict)."""
+    lib = _qual_lib()
+    desc, keep = make_model_desc(md)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    qual = np.ascontiguousarray(qual, np.uint8)
+    rr = np.array(res, RESULT_DTYPE, copy=True)
+    p, tot = _QualParams(int(min_quality), int(offset), int(max_low), int(segments)), _QualTotals()
+    rc = lib.td_qual_host(C.byref(desc), C.byref(p), offs.ctypes.data, len(offs) - 1, rr.ctypes.data, labels.ctypes.data, qual.ctypes.data,
+                          C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return rr, tot.as_dict()
 
 
 def _mol_rows(ptr):
@@ -1411,6 +1486,27 @@ class TagdustHip:
         out = np.zeros(int(cap), CENSUS_ENTRY_DTYPE)
         self._chk(lib.td_samples_get(self.h, out.ctypes.data, int(cap), C.byref(n), C.byref(tot)))
         return out[:min(int(cap), n.value)], tot.as_dict()
+
+    def qual_enable(self, min_quality, offset=33, max_low=0, segments=QUAL_SEG_B | QUAL_SEG_F):
+        """td_qual_enable: drop extracted reads with more than max_low barcode / UMI bases below min_quality"""
+        self._chk(_qual_lib().td_qual_enable(self.h, int(min_quality), int(offset), int(max_low), int(segments)))
+
+    def qual_disable(self):
+        self._chk(_qual_lib().td_qual_disable(self.h))
+
+    def qual_reset(self):
+        self._chk(_qual_lib().td_qual_reset(self.h))
+
+    def qual_next(self, qual, n_reads):
+        """td_qual_next: the quality bytes of the next TD_MODE_GET_LABEL batch, read i's at qual[offs[i]:]; a numpy uint8 array the
+        caller keeps alive until the batch is staged (upload_batch or submit has returned)"""
+        self._chk(_qual_lib().td_qual_next(self.h, qual.ctypes.data if qual is not None else None, int(n_reads)))
+
+    def qual_totals(self):
+        """td_qual_get: the totals dict (waits for the queued work)"""
+        tot = _QualTotals()
+        self._chk(_qual_lib().td_qual_get(self.h, C.byref(tot)))
+        return tot.as_dict()
 
     def mol_enable(self, prefix_bases=MOL_DEFAULT_PREFIX, log2_slots=16):
         self._chk(_mol_lib().td_mol_enable(self.h, int(prefix_bases), int(log2_slots)))

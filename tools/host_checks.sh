@@ -1,5 +1,5 @@
 #!/bin/bash
-# The eleven stand-alone programs over the library's plain C++ host units (tools/*_host_check.cpp), built with the host compiler under
+# The twelve stand-alone programs over the library's plain C++ host units (tools/*_host_check.cpp), built with the host compiler under
 # AddressSanitizer and UBSan and run, leak detection on: no GPU, no HIP runtime, no Python.  Every step must succeed; the last line
 # is "host_checks: ok".   usage: tools/host_checks.sh   (CXX: the compiler, default g++; OUT: where the programs go)
 set -e
@@ -17,6 +17,7 @@ $CXX $SAN $C/td_census_host.cpp $C/td_molecules_host.cpp tools/collapse_host_che
 $CXX $SAN $C/td_census_host.cpp $C/td_molecules_host.cpp tools/dedup_collapsed_host_check.cpp -o $OUT/dedup_collapsed_host_check &&
 $CXX $SAN $C/td_census_host.cpp $C/td_molecules_host.cpp tools/mate_host_check.cpp -o $OUT/mate_host_check &&
 $CXX $SAN $C/td_census_host.cpp $C/td_samples_host.cpp tools/samples_host_check.cpp -o $OUT/samples_host_check &&
+$CXX $SAN $C/td_quality_host.cpp tools/quality_host_check.cpp -o $OUT/quality_host_check &&
 $CXX $SAN -ffp-contract=off tools/merge_host_check.cpp $C/td_merge.cpp -o $OUT/merge_host_check -lpthread &&
 $CXX $SAN $C/td_batch_plan.cpp tools/batch_plan_host_check.cpp -o $OUT/batch_plan_host_check &&
 $CXX $SAN tools/workers_host_check.cpp -o $OUT/workers_host_check -lpthread &&
@@ -28,6 +29,7 @@ $OUT/collapse_host_check &&
 $OUT/dedup_collapsed_host_check &&
 $OUT/mate_host_check &&
 $OUT/samples_host_check &&
+$OUT/quality_host_check &&
 $OUT/batch_plan_host_check &&
 $OUT/workers_host_check &&
 $OUT/model_host_check &&

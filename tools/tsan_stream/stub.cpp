@@ -22,6 +22,7 @@ int td_submit(td_ctx*, const void*, int32_t, const int64_t* offs, int64_t n, int
 int td_wait(td_ctx*, int64_t) { return 0; }
 int td_set_batch_window(td_ctx*, int64_t, int64_t) { return 0; }
 int td_mol_mate_next(td_ctx*, const uint8_t*, const int64_t*, int64_t) { return 0; }   // (pair mode: "mate_bases" reads 0 here, never called)
+int td_qual_next(td_ctx*, const uint8_t*, int64_t) { return 0; }   // (the base-quality filter: "quality_filter" reads 0 here, never called)
 const char* td_samples_name(td_ctx*, int32_t) { return nullptr; }   // (sample assignment: "samples" reads 0 here, never called)
 }
 int main(int argc, char** argv)
