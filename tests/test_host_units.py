@@ -18,7 +18,8 @@ COUNT_UNITS = ("td_census_host.cpp", "td_molecules_host.cpp")
 WITHOUT_COUNT_UNITS = ("batch_plan_host_check", "workers_host_check", "model_host_check")
 PROGRAMS = [("census_host_check", []), ("molecules_host_check", ["td_fastq.cpp"]), ("dedup_host_check", []), ("collapse_host_check", []),
             ("dedup_collapsed_host_check", []), ("mate_host_check", []), ("batch_plan_host_check", ["td_batch_plan.cpp"]), ("workers_host_check", []),
-            ("model_host_check", ["td_model.cpp", "td_model_flat.cpp", "td_spec_plan.cpp", "td_spec_bounds.cpp"])]
+            ("model_host_check", ["td_model.cpp", "td_model_flat.cpp", "td_spec_plan.cpp", "td_spec_bounds.cpp"]),
+            ("run_host_check", ["td_run_opts.cpp", "td_run_plan.cpp", "td_run_report.cpp", "td_model.cpp", "td_model_flat.cpp", "td_fastq.cpp", "td_samples_host.cpp"])]
 
 
 def host_compiler():

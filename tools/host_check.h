@@ -1,6 +1,6 @@
 // host_check.h -- what the stand-alone programs over the host units of the two counts (tools/census_host_check.cpp,
 // molecules_host_check.cpp, dedup_host_check.cpp, collapse_host_check.cpp, dedup_collapsed_host_check.cpp, mate_host_check.cpp, samples_host_check.cpp, quality_host_check.cpp) share: the message sink td_api.hip would be, a
-// generator, CHECK (tools/batch_plan_host_check.cpp, over the batch geometry unit, and tools/model_host_check.cpp, over the model path, take the last two).  The program defines HOST_CHECK_NAME, its name in the messages, before it includes this.  tools/host_checks.sh
+// generator, CHECK (tools/batch_plan_host_check.cpp, over the batch geometry unit, and tools/model_host_check.cpp, over the model path, take the last two; tools/run_host_check.cpp, over the whole-run driver's device-free units, the sink and CHECK).  The program defines HOST_CHECK_NAME, its name in the messages, before it includes this.  tools/host_checks.sh
 // builds and runs them all.
 #pragma once
 #include <stdarg.h>

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The twelve stand-alone programs over the library's plain C++ host units (tools/*_host_check.cpp), built with the host compiler under
+# The thirteen stand-alone programs over the library's plain C++ host units (tools/*_host_check.cpp), built with the host compiler under
 # AddressSanitizer and UBSan and run, leak detection on: no GPU, no HIP runtime, no Python.  Every step must succeed; the last line
 # is "host_checks: ok".   usage: tools/host_checks.sh   (CXX: the compiler, default g++; OUT: where the programs go)
 set -e
@@ -22,6 +22,7 @@ $CXX $SAN -ffp-contract=off tools/merge_host_check.cpp $C/td_merge.cpp -o $OUT/m
 $CXX $SAN $C/td_batch_plan.cpp tools/batch_plan_host_check.cpp -o $OUT/batch_plan_host_check &&
 $CXX $SAN tools/workers_host_check.cpp -o $OUT/workers_host_check -lpthread &&
 $CXX $SAN $C/td_model.cpp $C/td_model_flat.cpp $C/td_spec_plan.cpp $C/td_spec_bounds.cpp tools/model_host_check.cpp -o $OUT/model_host_check &&
+$CXX $SAN $C/td_run_opts.cpp $C/td_run_plan.cpp $C/td_run_report.cpp $C/td_model.cpp $C/td_model_flat.cpp $C/td_fastq.cpp $C/td_census_host.cpp $C/td_samples_host.cpp $C/td_molecules_host.cpp tools/run_host_check.cpp -o $OUT/run_host_check -lpthread &&
 $OUT/census_host_check &&
 $OUT/molecules_host_check &&
 $OUT/dedup_host_check &&
@@ -33,6 +34,7 @@ $OUT/quality_host_check &&
 $OUT/batch_plan_host_check &&
 $OUT/workers_host_check &&
 $OUT/model_host_check &&
+$OUT/run_host_check &&
 $OUT/merge_host_check $G/r1.fq $G/r2.fq $G/merged_default.fq 16 0 &&
 $OUT/merge_host_check $G/r1.fq $G/r2.fq $G/merged_Q0.9_minlen20.fq 20 0.9 &&
 echo "host_checks: ok"
