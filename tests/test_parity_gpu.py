@@ -186,7 +186,8 @@ def test_backward_only_mode(ctx, name):
 
 def test_ascii_upload_and_large_ragged_batch(ctx):
     """td_batch_upload_ascii (nuc_code mapping incl. lower case, U, IUPAC -> N) on a ragged batch large enough to use the
-    threaded host packing and several tiles per wave; HIP == oracle."""
+    threaded host packing; HIP == oracle.  (1094 tiles: on a chip with 2048 wave slots or more every wave still gets one tile --
+    waves that decode several tiles are tests/test_wave_reuse_gpu.py's.)"""
     from oracle import pyoracle
     g = load_golden("c2_b4_r")
     rng = np.random.RandomState(99)

@@ -225,8 +225,10 @@ def _same(a, b):
 @pytest.mark.parametrize("workload,n", [("c3", 1 << 16), ("c2", 1 << 16), ("c5", 1 << 14)], ids=["config3", "config2", "config5"])
 def test_pruned_equals_dense_and_fallbacks(workload, n):
     """Same bytes with pruning off, on, and on with each fall-back route forced: the total_prob check failing for every tile
-    (second, dense pass), the spill cut guessed too short (rows missing -> dense pass), a wave giving up after repeated
-    failures.  The statistics counters (TD_SPEC_PRUNE_STATS) show which route ran."""
+    (second, dense pass), the spill cut guessed too short (rows missing -> dense pass).  The statistics counters
+    (TD_SPEC_PRUNE_STATS) show which route ran.  (At most 1024 tiles: every wave gets one tile, so no wave gives up after repeated
+    failures here -- that, and every other state a wave carries to its next tile, is
+    tests/test_wave_reuse_gpu.py::test_carried_state_acts_on_later_tiles.)"""
     S0 = 232 - 192    # diagnostic words: decisions, sum of required cuts, spill too short, failed checks, tiles, sum of cuts, dense tiles
     dense = _decode(workload, n, {"TD_SPEC_PRUNE": "0", "TD_SPEC_PRUNE_STATS": "0"})
     on = _decode(workload, n, {"TD_SPEC_PRUNE": "1", "TD_SPEC_PRUNE_STATS": "1"})
@@ -235,7 +237,8 @@ def test_pruned_equals_dense_and_fallbacks(workload, n):
     tiles = (n + 63) // 64
     assert st[4] == tiles and st[6] == 0 and st[2] == 0 and st[3] == 0      # every tile pruned, no second pass
     assert st[5] / tiles < 0.5 * (100 if workload == "c2" else 150)          # mean cut well inside the read
-    # every tile's total_prob check fails: second pass for the first tiles of a wave, then the wave stops trying
+    # every tile's total_prob check fails: second pass for the first tiles of a wave (one tile per wave here; that the wave then stops
+    # trying is shown in tests/test_wave_reuse_gpu.py)
     forced = _decode(workload, n, {"TD_SPEC_PRUNE": "1", "TD_SPEC_PRUNE_STATS": "1", "TD_SPEC_EXTRA_OPTS": "-DTDS_PRUNE_TT=1000.0f"})
     assert _same(dense, forced)
     st = forced[3][S0:S0 + 8]
