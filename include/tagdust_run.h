@@ -105,7 +105,7 @@ typedef struct td_run_opts {
 	                                    <out>_BC_<name>[_READ<k>].fq in sheet order, then _un; <out>_samples.txt reports the samples and the
 	                                    combinations no sample has; <out>_molecules.txt labels its rows with the sample names.  Refused with
 	                                    -start / -end and when no input file's architecture has a 'B' segment; barcodes spread over several
-	                                    input files are not joined (the controller's rule of one barcode file stays) */
+	                                    input files are joined only with --join-barcodes (else the controller's rule of one barcode file stays) */
 	int32_t  min_base_quality;       /* --min-base-quality Q   [0 = off]: the base-quality filter (tagdust_quality.h, td_qual_enable): an
 	                                    extracted read with more than max_low_bases barcode / UMI bases below Q (1..93) goes to the _un file
 	                                    and is neither assigned, counted nor kept by --dedup.  Adds a "quality:" line to the plan and one line
@@ -116,6 +116,15 @@ typedef struct td_run_opts {
 	int32_t  max_low_bases;          /* --max-low-bases K      [0] */
 	int32_t  quality_segments;       /* --quality-segments B|F|BF   [BF = TD_QUAL_SEG_B | TD_QUAL_SEG_F]: the segments whose bases are judged */
 	int32_t  quality_offset;         /* --quality-offset 33|64 [33] */
+	int32_t  join_barcodes;          /* --join-barcodes        [0]: with --samples, the barcodes of a sample lie in several input files
+	                                    (tagdust_samples.h, the join across input files).  The barcode files are those whose architecture
+	                                    has a 'B' segment, in call order; the sheet's barcode columns are their 'B' segments, files first.
+	                                    The first barcode file's contexts hold the sheet, every other one's export their calls.  Adds a
+	                                    "join:" line to the plan; <out>_samples.txt names the file of each column and has a "# partner
+	                                    failed" line.  Refused without --samples, with more than one device, with --unknown-barcodes, with
+	                                    -start / -end, when the barcode files have more than four 'B' segments together and when only one
+	                                    file has barcodes; --molecules, --mate-bases and --min-base-quality are refused for two decoded
+	                                    files by their own rules */
 } td_run_opts;
 
 td_run_opts* td_run_opts_new(void);            /* the defaults */
@@ -206,6 +215,7 @@ typedef struct td_run_report {
 	td_qual_totals quality_totals;            /* ... td_qual_get's totals of the decoded file's context.  With one file on one device the reads
 	                                             it failed are moved from slot TD_EXTRACT_SUCCESS to slot TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND
 	                                             of `counts`, as the samples rewrite's are: the log's "extracted" agrees with the files */
+	int64_t  partner_failed;                  /* --join-barcodes: reads extracted in the first barcode file whose partner in another was not */
 } td_run_report;
 /* In the controller's order: architectures per file, statistics over each file's head, thresholds, models, the run, the log.
  * A failure before the first batch leaves no output files behind; one during the run leaves them as they are and says so.  The

@@ -68,6 +68,53 @@ int td_samples_key_calls(uint64_t key, int32_t calls[TD_SAMPLES_MAX_SEGMENTS], i
 int td_samples_host   (const td_model_desc* model, const int32_t* tuples, int32_t n_samples, const int64_t* offs, int64_t n_reads,
                        td_read_result* res, const int8_t* labels, td_census_entry** entries, int64_t* n, td_samples_totals* totals);
 
+/*
+ * The join across input files (dual-index runs: I1.fq and I2.fq carry one barcode each).  The files whose model has a 'B' segment
+ * are the barcode files, in call order; their 'B' segments are the COLUMNS t = 0..m-1 of the sheet, files first, then model order
+ * within a file, 2 <= m <= TD_SAMPLES_MAX_SEGMENTS.  The first barcode file is the PRIMARY: its contexts hold the sheet and assign.
+ * Every other barcode file is an EXPORTER: its contexts hand over one word per read of a batch, in the caller's order,
+ *     0xFFFFFFFF                                   the read's final read_type != TD_EXTRACT_SUCCESS ("partner failed")
+ *     byte first_column + u = call_u + 1           else, for the exporter's own u-th 'B' segment (0: no position; the decoy n_hmm)
+ * -- the call by the rule above; all other bytes 0.  Words of several exporters combine by bitwise OR (all ones absorbs).
+ *
+ * In a primary context a read whose own final read_type is TD_EXTRACT_SUCCESS and whose partner word is 0xFFFFFFFF is not
+ * eligible: nothing of it changes, nothing is counted, it is tallied as partner_failed.  Otherwise it is eligible and its calls
+ * word is its own (bytes first_column..first_column + m_own - 1) OR the partner word; classes, rewrite, key and count are those
+ * above with m = the number of columns, the decoy of column t being column_hmms[t], and barcode = (j_last_own << 16) | s.  Always
+ *     eligible == assigned + unlisted + incomplete     and     reads that are SUCCESS in the primary == eligible + partner_failed.
+ * A partner word of 0 contributes nothing.  Limits: one device; at most four columns in all; no window, and in a whole run no
+ * --unknown-barcodes, --molecules or quality filter with the join yet.
+ */
+typedef struct td_samples_join_totals { td_samples_totals t; int64_t partner_failed; } td_samples_join_totals;
+
+/* Exporter side.  Needs an uploaded model with 1..4 - first_column 'B' segments, no window, no outstanding tickets; not together
+ * with td_samples_enable or the join on one context.  While it is on, every TD_MODE_GET_LABEL batch leaves its words in the array
+ * td_samples_export_next named for it (n_reads words, page-locked or pageable; valid after td_run / td_wait): name it in front of
+ * td_batch_upload / td_submit.  A batch without a named array, or one named for another number of reads, is refused with a
+ * message and the context stays usable. */
+int td_samples_export_enable (td_ctx* ctx, int32_t first_column);
+int td_samples_export_disable(td_ctx* ctx);
+int td_samples_export_next   (td_ctx* ctx, uint32_t* words, int64_t n_reads);
+/* Primary side.  As td_samples_enable, with a sheet of m_total columns: column_hmms[m_total] holds every column's n_hmm, the
+ * context's own columns (first_column..) are held against its model.  td_samples_join_next names the partner words of the next
+ * TD_MODE_GET_LABEL batch (read when the batch is staged); the rules are td_samples_export_next's.  td_samples_disable,
+ * td_samples_reset and td_samples_name serve the join too; td_samples_get reports it without partner_failed. */
+int td_samples_join_enable(td_ctx* ctx, const int32_t* tuples, const char* const* names, int32_t n_samples, int32_t log2_slots,
+                           int32_t m_total, int32_t first_column, const int32_t* column_hmms);
+int td_samples_join_next  (td_ctx* ctx, const uint32_t* words, int64_t n_reads);
+int td_samples_join_get   (td_ctx* ctx, td_census_entry* entries, int64_t cap, int64_t* n, td_samples_join_totals* totals);
+/* td_get_option: "samples_export" (1 while the context exports), "samples_join" (the joined sheet's n_samples, 0 = off),
+ * "samples_export_kernel_us" and "samples_join_kernel_us", the kernels' times of the last batch; "batch_sorted", 1 when the device
+ * order of the batch td_run decoded last differs from the caller's (reads of several lengths: both sides of the join then carry
+ * their words between the two orders) -- its meaning holds for td_batch_upload / td_run; with td_submit tickets in flight it speaks
+ * of whichever batch was submitted or waited for last. */
+/* The same definitions from host arrays, no GPU (arguments as td_samples_host's). */
+int td_samples_export_host(const td_model_desc* model, int32_t first_column, const int64_t* offs, int64_t n_reads,
+                           const td_read_result* res, const int8_t* labels, uint32_t* words);
+int td_samples_join_host  (const td_model_desc* model, const int32_t* tuples, int32_t n_samples, int32_t m_total, int32_t first_column,
+                           const int32_t* column_hmms, const uint32_t* words, const int64_t* offs, int64_t n_reads, td_read_result* res,
+                           const int8_t* labels, td_census_entry** entries, int64_t* n, td_samples_join_totals* totals);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,7 @@ extern "C" void td_ctx_destroy(td_ctx* c)
 	census_release(c);
 	mol_release(c);
 	samples_release(c);
+	samples_export_release(c);
 	qual_release(c);
 	void* bufs[] = { c->d_logsum, c->d_counters, c->d_ws, c->d_art_text, c->d_art_index, c->d_art_pk, c->d_art_seq, c->d_art_hits,
 	                 c->spec.d_prune, c->d_tile_next, c->d_ws2, c->d_tile_next2 };
@@ -199,6 +200,7 @@ extern "C" int td_model_upload(td_ctx* c, const td_model_desc* m)
 	census_release(c);   // a census counts one model's segment: a new model switches it off
 	mol_release(c);      // ... and the molecule count reads one model's labels
 	samples_release(c);  // ... and a sheet lists one model's barcodes
+	samples_export_release(c);   // ... as do the words a context exports
 	qual_release(c);     // ... and the base-quality filter judges one model's segments
 	free_dev_model(c->dev);
 	c->dev = dm;
@@ -286,6 +288,17 @@ extern "C" int td_get_option(td_ctx* c, const char* name, int32_t* value)
 	if (!strcmp(name, "census_kernel_us")) return census_last_kernel_us(c, value);   // the count kernel's time of the last counted batch
 	if (!strcmp(name, "samples")) { *value = c->samples.on ? c->samples.plan.n_samples : 0; return TD_OK; }   // td_samples_enable's n_samples, 0 = off
 	if (!strcmp(name, "samples_kernel_us")) return samples_last_kernel_us(c, value);   // the kernel's time of the last batch
+	// the join across input files: the context is an exporter (1) / the primary (its sheet's n_samples), and the kernels' times
+	if (!strcmp(name, "samples_export")) { *value = c->samples_export.on; return TD_OK; }
+	if (!strcmp(name, "samples_join")) { *value = c->samples.on && c->samples.join ? c->samples.plan.n_samples : 0; return TD_OK; }
+	// ... and whether the last batch's device order differs from the caller's (reads of several lengths): both sides of the join
+	// then carry their words between the two orders
+	if (!strcmp(name, "batch_sorted")) { *value = c->slots[c->last_slot].sorted ? 1 : 0; return TD_OK; }
+	if (!strcmp(name, "samples_export_kernel_us")) return samples_export_last_kernel_us(c, value);
+	if (!strcmp(name, "samples_join_kernel_us")) {
+		if (!c->samples.on || !c->samples.join) return fail(c, "td_get_option: samples_join_kernel_us: the join is off");
+		return samples_last_kernel_us(c, value);
+	}
 	if (!strcmp(name, "quality_filter")) { *value = c->quality.on; return TD_OK; }   // td_qual_enable: 1 = on
 	if (!strcmp(name, "quality_kernel_us")) return qual_last_kernel_us(c, value);    // the judge kernel's time of the last batch
 	if (!strcmp(name, "molecules_active")) { *value = c->molecules.on; return TD_OK; }
@@ -348,6 +361,7 @@ extern "C" int td_set_window(td_ctx* c, int32_t matchstart, int32_t matchend)
 	if (c->census.on) return fail(c, "td_set_window: a census is on (td_census_disable first): labels behind a window do not spell the barcode");
 	if (c->molecules.on) return fail(c, "td_set_window: a molecule count is on (td_mol_disable first): labels behind a window do not mark the read's bases");
 	if (c->samples.on) return fail(c, "td_set_window: sample assignment is on (td_samples_disable first): labels behind a window do not mark the barcodes");
+	if (c->samples_export.on) return fail(c, "td_set_window: the context exports its barcode calls (td_samples_export_disable first): labels behind a window do not mark the barcodes");
 	if (c->quality.on) return fail(c, "td_set_window: the base-quality filter is on (td_qual_disable first): labels behind a window do not mark the bases");
 	c->match_start = matchstart; c->match_len = matchend - matchstart;
 	return TD_OK;

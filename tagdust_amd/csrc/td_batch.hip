@@ -51,9 +51,9 @@ void slot_release(TdSlot& s)
 {
 	void* dev[] = { s.d_raw, s.d_offs, s.d_read_at, s.d_keys, s.d_vals, s.d_sort_tmp, s.d_packed, s.d_lens, s.d_art_left,
 	                s.d_out, s.d_res, s.d_seq, s.d_lab, s.d_keepo, s.d_rle, s.d_runs, s.d_judged, s.d_mate_raw, s.d_mate_offs, s.d_mate_w,
-	                s.d_mate_n, s.d_mate_type, s.d_qual_w };
+	                s.d_mate_n, s.d_mate_type, s.d_qual_w, s.d_smp_w };
 	for (void* p : dev) if (p) (void)hipFree(p);
-	void* pinned[] = { s.h_raw, s.h_offs, s.h_res, s.h_seq, s.h_lab, s.h_keepo, s.h_rle, s.h_mate_raw, s.h_mate_offs, s.h_qual_w };
+	void* pinned[] = { s.h_raw, s.h_offs, s.h_res, s.h_seq, s.h_lab, s.h_keepo, s.h_rle, s.h_mate_raw, s.h_mate_offs, s.h_qual_w, s.h_smp_w };
 	for (void* p : pinned) if (p) (void)hipHostFree(p);
 	hipEvent_t ev[] = { s.ev_up, s.ev_k0, s.ev_k1, s.ev_done, s.ev_down, s.ev_pack, s.ev_hits };
 	for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -128,7 +128,7 @@ static int ensure_workspace(td_ctx* c, TdSlot& s)
 
 // Reads -> device, sorted and packed.  Copies go on `up` (the compute stream itself for the synchronous calls); the
 // kernels on the compute stream wait for them through ev_up.
-static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* bases, int is_ascii, const int64_t* offs, int64_t n, hipStream_t up, bool with_workspace = true, bool take_mate = false, bool take_qual = false)
+static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* bases, int is_ascii, const int64_t* offs, int64_t n, hipStream_t up, bool with_workspace = true, bool take_mate = false, bool take_qual = false, bool take_words = false)
 {
 	s.reset_staged(route);   // nothing of the slot's previous batch survives (nor of its launch, nor of its download)
 	if (with_workspace && !c->have_model) return fail(c, "td_batch_upload: no model uploaded");
@@ -192,6 +192,7 @@ static int slot_stage(td_ctx* c, TdSlot& s, const TdRoute& route, const void* ba
 	if (n_bases > 0) HIPCHK(c, hipMemcpyAsync(s.d_raw, src, (size_t)n_bases, hipMemcpyHostToDevice, up));
 	if (take_mate && mol_mate_stage(c, s, n, up) != TD_OK) return TD_FAIL;   // mate mode: the named mate batch travels with its reads
 	if (take_qual && qual_stage(c, s, offs, n, up) != TD_OK) return TD_FAIL;  // the base-quality filter: the named qualities, one bit per base
+	if (take_words && samples_words_stage(c, s, n, up) != TD_OK) return TD_FAIL;   // the join across input files: partner words in / the export's array named
 	if (up != s.aux) {
 		HIPCHK(c, hipEventRecord(s.ev_up, up));
 		HIPCHK(c, hipStreamWaitEvent(s.aux, s.ev_up, 0));
@@ -267,6 +268,21 @@ static int launch_begin(td_ctx* c, TdSlot& s, int mode, bool& empty)
 		return fail(c, "td_run: sample assignment is %s (td_samples_%s) and the resident batch of %lld reads was staged %s: upload it again; "
 		            "nothing was assigned", c->samples.on ? "on" : "off", c->samples.on ? "enable" : "disable", (long long)s.n_reads,
 		            s.samples_gen ? (c->samples.on ? "under an earlier sheet" : "while it was on") : "while it was off");
+	// the join across input files: a batch staged without its partner words, or without an array for the words it exports
+	if (mode == TD_MODE_GET_LABEL && c->samples.on && c->samples.join && !s.join_words) {
+		c->samples.next.named = false;
+		return fail(c, "td_run: the context joins its partners' barcode calls (td_samples_join_enable) and the resident batch of %lld reads was staged "
+		            "without words named for as many reads: td_samples_join_next first, then td_batch_upload; nothing was decoded", (long long)s.n_reads);
+	}
+	if (mode == TD_MODE_GET_LABEL && s.export_gen != (c->samples_export.on ? c->samples_export.gen : 0)) {
+		c->samples_export.next.named = false;
+		if (!c->samples_export.on)
+			return fail(c, "td_run: the export is off (td_samples_export_disable) and the resident batch of %lld reads was staged while it was on: "
+			            "upload it again; nothing was decoded", (long long)s.n_reads);
+		return fail(c, "td_run: the context exports its barcode calls (td_samples_export_enable) and the resident batch of %lld reads was staged %s: "
+		            "td_samples_export_next first, then td_batch_upload; nothing was decoded", (long long)s.n_reads,
+		            s.export_gen ? "under an earlier td_samples_export_enable" : "without an array named for as many words");
+	}
 	// the base-quality filter: a batch staged without its qualities, or under another enable, has no verdicts to give
 	if (mode == TD_MODE_GET_LABEL && s.qual_gen != (c->quality.on ? c->quality.gen : 0)) {
 		c->quality.named = false;
@@ -309,6 +325,8 @@ static int launch_end(td_ctx* c, TdSlot& s, bool with_artifacts)
 	if (with_artifacts && slot_count_hits(c, s, o.out_type) != TD_OK) return TD_FAIL;
 	if (c->quality.on && s.mode == TD_MODE_GET_LABEL && qual_slot(c, s, o.out_type, o.out_labels) != TD_OK) return TD_FAIL;
 	if (c->samples.on && s.mode == TD_MODE_GET_LABEL && samples_slot(c, s, o.out_type, o.out_barcode, o.out_labels) != TD_OK) return TD_FAIL;
+	// (a context assigns or exports: the exporter side of the join stands at the same place and changes nothing of the batch)
+	if (c->samples_export.on && s.mode == TD_MODE_GET_LABEL && samples_export_slot(c, s, o.out_type, o.out_labels) != TD_OK) return TD_FAIL;
 	if (c->census.on && s.mode == TD_MODE_GET_LABEL && census_count_slot(c, s, o.out_type, o.out_labels) != TD_OK) return TD_FAIL;
 	// the molecule count last: dedup's second pass, the last launch in there, rewrites the outcomes the counts above read
 	if (c->molecules.on && s.mode == TD_MODE_GET_LABEL && mol_slot_decoded(c, s, o.out_type, o.out_barcode, o.out_finger, o.out_labels) != TD_OK) return TD_FAIL;
@@ -455,6 +473,8 @@ static int slot_issue_copies(td_ctx* c, TdSlot& s, hipStream_t down)
 		const TdLeg leg = egress_leg(s, k);
 		if (s.plan.ch[k].copy_bytes) HIPCHK(c, hipMemcpyAsync(leg.dst, leg.src, s.plan.ch[k].copy_bytes, hipMemcpyDeviceToHost, down));
 	}
+	// a pipelined exporter's words travel with the results (td_run has copied a synchronous batch's out itself)
+	if (s.pipelined && s.export_gen && s.mode == TD_MODE_GET_LABEL && samples_export_issue_copy(c, s, down) != TD_OK) return TD_FAIL;
 	HIPCHK(c, hipEventRecord(s.ev_down, down));
 	return TD_OK;
 }
@@ -526,6 +546,7 @@ static int slot_fetch_end(td_ctx* c, TdSlot& s)
 		if (slot_issue_copies(c, s, c->s_down) != TD_OK) return TD_FAIL;
 	}
 	HIPCHK(c, hipEventSynchronize(s.ev_down));
+	if (s.pipelined && s.export_gen && s.mode == TD_MODE_GET_LABEL) samples_export_copy_out(s);
 	const double t2 = dbg ? wall_ms() : 0.0;
 	struct Rep { bool on; double t0, t1, t2; ~Rep() { if (on) fprintf(stderr, "td_wait: device %.2f ms, download %.2f ms, host %.2f ms\n", t1 - t0, t2 - t1, wall_ms() - t2); } } rep_{ dbg, t0, t1, t2 };
 	TdEgressPlan& p = s.plan;
@@ -575,7 +596,10 @@ static int upload_common(td_ctx* c, const void* bases, int is_ascii, const int64
 	const bool take_mate = c->molecules.mate.bases > 0 && c->molecules.mate.named && c->molecules.mate.reads == n;
 	// ... and so are the named qualities while the base-quality filter is on
 	const bool take_qual = c->quality.on && c->quality.named && c->quality.next_reads == n && offs && n >= 0;
-	if (slot_stage(c, s, rt, bases, is_ascii, offs, n, c->stream, true, take_mate, take_qual) != TD_OK) return TD_FAIL;
+	// ... and the words of the join across input files, on either side of it
+	const TdSamplesNamed& words = c->samples_export.on ? c->samples_export.next : c->samples.next;
+	const bool take_words = (c->samples_export.on || (c->samples.on && c->samples.join)) && words.named && words.reads == n && n >= 0;
+	if (slot_stage(c, s, rt, bases, is_ascii, offs, n, c->stream, true, take_mate, take_qual, take_words) != TD_OK) return TD_FAIL;
 	HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller may reuse its buffers
 	c->last_slot = 0;
 	return TD_OK;
@@ -595,7 +619,14 @@ extern "C" int td_run(td_ctx* c, int mode)
 {
 	if (!c) return TD_FAIL;
 	if (!c->have_model && mode != TD_MODE_RNA_DUST) return fail(c, "td_run: no model uploaded");
-	return slot_decode(c, c->slots[0], mode);
+	TdSlot& s = c->slots[0];
+	if (slot_decode(c, s, mode) != TD_OK) return TD_FAIL;
+	if (c->samples_export.on && mode == TD_MODE_GET_LABEL && s.n_reads > 0) {   // the exporter's words are valid when td_run returns
+		if (samples_export_issue_copy(c, s, s.cs) != TD_OK) return TD_FAIL;
+		HIPCHK(c, hipStreamSynchronize(s.cs));
+		samples_export_copy_out(s);
+	}
+	return TD_OK;
 }
 
 extern "C" int td_batch_download(td_ctx* c, td_read_result* res, int8_t* labels, uint8_t* seq_out)
@@ -634,6 +665,8 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 	if (take_mate && mol_mate_check(c, n_reads, "td_submit") != TD_OK) return TD_FAIL;
 	const bool take_qual = c->quality.on && mode == TD_MODE_GET_LABEL;
 	if (take_qual && qual_check(c, n_reads, "td_submit") != TD_OK) return TD_FAIL;
+	const bool take_words = (c->samples_export.on || (c->samples.on && c->samples.join)) && mode == TD_MODE_GET_LABEL;
+	if (take_words && samples_words_check(c, n_reads, "td_submit") != TD_OK) return TD_FAIL;
 	TdSlot& s = c->slots[k];
 	TdRoute rt = sync_route(c);
 	rt.pipelined = true;
@@ -643,7 +676,7 @@ extern "C" int td_submit(td_ctx* c, const void* bases, int32_t is_ascii, const i
 		c->submit_parity ^= 1;
 		rt.aux = c->s_aux; rt.fin = c->s_fin;
 	}
-	if (slot_stage(c, s, rt, bases, is_ascii != 0, offs, n_reads, c->s_up, mode != TD_MODE_RNA_DUST, take_mate, take_qual) != TD_OK) return TD_FAIL;
+	if (slot_stage(c, s, rt, bases, is_ascii != 0, offs, n_reads, c->s_up, mode != TD_MODE_RNA_DUST, take_mate, take_qual, take_words) != TD_OK) return TD_FAIL;
 	if (slot_decode(c, s, mode, labels != nullptr) != TD_OK) return TD_FAIL;
 	if (slot_fetch_begin(c, s, res, labels, seq_out, true) != TD_OK) return TD_FAIL;
 	// "returns once the reads have left the caller's buffers": a page-locked source is read by the DMA engine itself, so wait

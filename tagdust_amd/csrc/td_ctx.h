@@ -54,6 +54,9 @@ struct TdStaged : TdRoute {
 	bool mate_typed = false;  // ... and the filter kernel ran (dust != 0 or artifacts set): d_mate_type holds this batch's mate types;
 	                          // judged and not typed: every mate type is 0, d_mate_type is not read
 	int32_t samples_gen = 0;  // sample assignment (td_samples.hip) as it stood when the batch was staged: the enable's number, 0 = off
+	int32_t export_gen = 0;   // the join's exporter side: the td_samples_export_enable under which the batch's word array was named, 0 = none was
+	bool join_words = false;  // ... its primary side: d_smp_w holds this batch's partner words
+	uint32_t* smp_dst = nullptr;   // ... the exporter's array the batch's words go to (valid until the batch has been waited for)
 	int32_t qual_gen = 0;     // the base-quality filter (td_quality.hip): the enable under which the batch's qualities were staged, 0 = none were
 	int64_t qual_words = 0;   // ... and the words of d_qual_w that are this batch's (the spare zero word included)
 	const uint8_t* raw_host = nullptr;   // the batch's bases on the host, valid until the batch has been waited for: the pinned staging
@@ -115,6 +118,9 @@ struct TdSlot : TdStaged, TdDecoded, TdFetch {
 	// the base-quality filter (td_quality.hip): one low flag per base of the batch, packed on the host into page-locked words
 	uint32_t* d_qual_w = nullptr;  size_t cap_qual_w = 0;
 	uint32_t* h_qual_w = nullptr;  size_t cap_h_qual_w = 0;
+	// the join across input files (td_samples.hip): one word per read in the caller's order -- the partner words in, or the export words out
+	uint32_t* d_smp_w = nullptr;   size_t cap_smp_w = 0;
+	uint32_t* h_smp_w = nullptr;   size_t cap_h_smp_w = 0;
 	uint8_t* h_mate_raw = nullptr; size_t cap_h_mate_raw = 0;   // (pinned staging, as h_raw and h_offs)
 	int64_t* h_mate_offs = nullptr; size_t cap_h_mate_offs = 0;
 	uint32_t* h_keepo = nullptr;   size_t cap_h_keepo = 0;
@@ -216,6 +222,7 @@ struct td_ctx {
 	TdCensusState census;       // include/tagdust_census.h: off unless td_census_enable switched it on
 	TdMolState molecules;       // include/tagdust_molecules.h: off unless td_mol_enable switched it on
 	TdSamplesState samples;     // include/tagdust_samples.h: off unless td_samples_enable switched it on
+	TdSamplesExportState samples_export;   // ... its exporter side of the join: off unless td_samples_export_enable switched it on
 	TdQualState quality;        // include/tagdust_quality.h: off unless td_qual_enable switched it on
 	int64_t win_first = 0, win_total = 0;   // td_set_batch_window
 	int32_t match_start = 0, match_len = 0;  // td_set_window (-start / -end); match_len = 0: whole reads

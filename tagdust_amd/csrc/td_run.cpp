@@ -301,8 +301,18 @@ int Run::execute()
 			if (o->unknown_barcodes > 0 && k == roles.bar_file &&
 			    td_census_enable(c, -1, TD_CENSUS_DEFAULT_MASK, o->unknown_slots_log2) != TD_OK) return fail("%s", td_last_error(c));
 			// --samples: the contexts of the barcode file assign every extracted read by all its barcodes, in front of census and count
-			if (sheet.n() > 0 && k == roles.bar_file &&
+			if (sheet.n() > 0 && k == roles.bar_file && !o->join_barcodes &&
 			    td_samples_enable(c, sheet.tuples.data(), sample_names.data(), sheet.n(), 16) != TD_OK) return fail("%s", td_last_error(c));
+			// --join-barcodes: the first barcode file's contexts hold the sheet over the columns of all barcode files and join the calls
+			// that the contexts of every other barcode file export (td_stream_run_multi carries the words from file to file)
+			if (o->join_barcodes)
+				for (size_t q = 0; q < roles.bar_files.size(); q++) {
+					if (roles.bar_files[q] != k) continue;
+					const int rc = q == 0 ? td_samples_join_enable(c, sheet.tuples.data(), sample_names.data(), sheet.n(), 16, (int32_t)roles.column_hmms.size(),
+					                                               roles.first_column[q], roles.column_hmms.data())
+					                      : td_samples_export_enable(c, roles.first_column[q]);
+					if (rc != TD_OK) return fail("%s", td_last_error(c));
+				}
 			// --min-base-quality: the context of the one decoded file drops extracted reads with low-quality barcode / UMI bases, in front
 			// of samples, census and count (the streaming run names every batch's quality lines)
 			if (k == roles.qual_file &&
@@ -391,7 +401,11 @@ int Run::samples()
 	int64_t n_acc = 0;
 	td_samples_totals sum{};
 	std::vector<td_samples_totals> per;
-	if (merged_entries(f, td_samples_get, acc, n_acc, per) != TD_OK) return TD_FAIL;
+	if (o->join_barcodes) {   // (one device: the join's totals are the one context's, partner_failed among them)
+		std::vector<td_samples_join_totals> jper;
+		if (merged_entries(f, td_samples_join_get, acc, n_acc, jper) != TD_OK) return TD_FAIL;
+		for (const td_samples_join_totals& t : jper) { per.push_back(t.t); rep->partner_failed += t.partner_failed; }
+	} else if (merged_entries(f, td_samples_get, acc, n_acc, per) != TD_OK) return TD_FAIL;
 	for (const td_samples_totals& t : per) {
 		sum.eligible += t.eligible; sum.assigned += t.assigned; sum.unlisted += t.unlisted; sum.incomplete += t.incomplete; sum.overflow += t.overflow;
 	}
@@ -402,7 +416,13 @@ int Run::samples()
 		rep->counts[TD_EXTRACT_FAIL_BAR_FINGER_NOT_FOUND] += sum.unlisted + sum.incomplete;
 	}
 	std::string text;
-	const bool ok = samples_text(o, f.arch.get(), f.segs, o->infile[roles.bar_file], roles.sheet, *rep, text);
+	bool ok;
+	if (o->join_barcodes) {
+		std::vector<const td_arch*> archs;
+		std::vector<std::vector<std::string>> segs;
+		for (const FileState& g : files) { archs.push_back(g.arch.get()); segs.push_back(g.segs); }
+		ok = samples_text_join(o, archs, segs, o->infile, roles.sheet, *rep, text);
+	} else ok = samples_text(o, f.arch.get(), f.segs, o->infile[roles.bar_file], roles.sheet, *rep, text);
 	if (write_text(samples_file_name(o), text) != TD_OK) return TD_FAIL;
 	return ok ? TD_OK : fail("%s", std::string(g_run_error).c_str());
 }

@@ -59,7 +59,8 @@ bool read_arch_file(const char* path, ArchFile& af, std::string& why);
 // --samples FILE (tagdust_samples.h): one sample per line -- the name, then one barcode spelling per 'B' segment as the architecture
 // lists them, separated by white space; '#' lines and blank lines are skipped
 struct SampleSheet {
-	std::vector<int> segs;                 // the 'B' segments of the architecture, in order
+	std::vector<int> segs;                 // the 'B' segments of the architecture, in order (--join-barcodes: of every barcode file, files first)
+	std::vector<int> files;                // --join-barcodes: the input file of every column (empty without the option: all of the barcode file)
 	std::vector<std::string> names;
 	std::vector<int32_t> tuples;           // [names.size() * segs.size()]
 	int n() const { return (int)names.size(); }
@@ -67,6 +68,10 @@ struct SampleSheet {
 // TD_FAIL with a message that names the line.  The sheet's own rules (rows and names pairwise different, the name's characters) are
 // checked here too, so that the plan refuses what td_samples_enable would.
 int read_sample_sheet(const char* path, const td_arch* a, SampleSheet& sh);
+// --join-barcodes: the sheet's columns are the 'B' segments of the files `bar_files` (indices into archs and infile), files first;
+// a message names file and segment of the column it is about
+int read_sample_sheet_join(const char* path, const std::vector<const td_arch*>& archs, const std::vector<int>& bar_files, const char* const* infile,
+                           SampleSheet& sh);
 
 // Which file plays which part, once every file's architecture is known (barcode_hmm.c:130-159): decided in one place, for the plan,
 // for td_run_output_files_describe and for the run.
@@ -77,6 +82,11 @@ struct RunRoles {
 	int mol_file = 0;                      // the file whose contexts count molecules: file 0, or with --mate-bases the one decoded file
 	int mate_file = -1;                    // ... its mate with --mate-bases, else -1
 	int qual_file = -1;                    // --min-base-quality: the one decoded file, whose context judges (-1 without the option)
+	std::vector<int> bar_files;            // --join-barcodes: every file whose architecture has a barcode segment, in call order; bar_file is
+	                                       // the first of them, whose contexts hold the sheet (empty without the option)
+	std::vector<int> first_column;         // ... [bar_files.size()] the sheet column of each one's first 'B' segment
+	std::vector<int32_t> column_hmms;      // ... [columns] the HMMs of every column's segment (its barcodes and the all-N decoy)
+	std::string join_line;                 // ... the plan's "join:" line
 	SampleSheet sheet;                     // --samples, resolved against the barcode file's architecture (no sample without the option)
 };
 // TD_FAIL with the reference's message, or this library's for its own options
@@ -110,6 +120,9 @@ std::vector<std::string> summary_messages(const td_run_opts* o, const td_run_rep
 bool unknown_barcodes_text(const td_run_opts* o, const td_arch* a, const std::vector<std::string>& segs, const char* infile, const td_run_report& r, std::string& out);
 bool samples_text(const td_run_opts* o, const td_arch* a, const std::vector<std::string>& segs, const char* infile, const SampleSheet& sheet,
                   const td_run_report& r, std::string& out);
+// ... with --join-barcodes: a column's architecture, segment strings and file name are those of sheet.files[t] in archs / segs / infile
+bool samples_text_join(const td_run_opts* o, const std::vector<const td_arch*>& archs, const std::vector<std::vector<std::string>>& segs,
+                       const char* const* infile, const SampleSheet& sheet, const td_run_report& r, std::string& out);
 std::string molecules_text(const td_run_opts* o, const td_arch* a, const char* infile, const char* mate_infile, int dust, bool use_ref,
                            const SampleSheet& sheet, const td_run_report& r);
 

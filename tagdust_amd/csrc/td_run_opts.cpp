@@ -32,6 +32,7 @@ enum { O_SEG = 1 /* .. 10 */, O_ARCH = 20, O_OUT, O_THREADS, O_Q, O_E, O_I, O_MI
        O_HELP, O_VERSION, O_DEVICES, O_RTEST, O_HOST_THREADS, O_BATCH_READS, O_SYNC_COMPILE, O_STATS_ON_HOST, O_FORCE, O_DRY_RUN,
        O_UNKNOWN, O_UNKNOWN_SLOTS, O_FINGER_SEQ, O_MOLECULES, O_MOLECULES_PREFIX, O_MOLECULES_SLOTS, O_DEDUP, O_COLLAPSE,
        O_DEDUP_COLLAPSED, O_MATE_BASES, O_MATE_FILTER, O_SAMPLES, O_MIN_BASE_QUALITY, O_MAX_LOW_BASES, O_QUALITY_SEGMENTS, O_QUALITY_OFFSET,
+       O_JOIN_BARCODES,
        O_UNSUPPORTED = 100 };
 const OptSpec kOpts[] = {
 	{ "1", 1, O_SEG + 0 }, { "2", 1, O_SEG + 1 }, { "3", 1, O_SEG + 2 }, { "4", 1, O_SEG + 3 }, { "5", 1, O_SEG + 4 }, { "6", 1, O_SEG + 5 },
@@ -61,6 +62,7 @@ const OptSpec kOwnOpts[] = {
 	{ "dedup-collapsed", 0, O_DEDUP_COLLAPSED }, { "mate-bases", 1, O_MATE_BASES }, { "mate-filter", 0, O_MATE_FILTER },
 	{ "samples", 1, O_SAMPLES }, { "min-base-quality", 1, O_MIN_BASE_QUALITY }, { "max-low-bases", 1, O_MAX_LOW_BASES },
 	{ "quality-segments", 1, O_QUALITY_SEGMENTS }, { "quality-offset", 1, O_QUALITY_OFFSET },
+	{ "join-barcodes", 0, O_JOIN_BARCODES },
 };
 
 bool parse_devices(const char* s, td_run_opts* o, std::string& why)
@@ -174,6 +176,10 @@ extern "C" const char* td_run_usage(void)
 	       "\t--samples FILE              combinatorial barcodes: FILE lists one sample per line, the name and one barcode per B segment;\n"
 	       "\t                            a read is written to <output prefix>_BC_<name>.fq by ALL its barcodes, to _un when they are\n"
 	       "\t                            incomplete or name no sample; the counts go to <output prefix>_samples.txt\n"
+	       "\t--join-barcodes             with --samples: the barcodes of a sample lie in several input files (dual-index runs, I1.fq and\n"
+	       "\t                            I2.fq): the sheet's barcode columns are the B segments of all files, files first in call order,\n"
+	       "\t                            at most four; a read whose partner in another barcode file is not extracted goes to _un (one\n"
+	       "\t                            device; not with --unknown-barcodes, --molecules, --min-base-quality or -start / -end)\n"
 	       "\t--min-base-quality Q        drop an extracted read with low-quality barcode or UMI bases: more than --max-low-bases of them\n"
 	       "\t                            below Q, 1..93; it goes to _un and is neither counted nor kept by --dedup (FASTQ input, one\n"
 	       "\t                            device, one decoded file; not with -start / -end)\n"
@@ -280,6 +286,7 @@ extern "C" int td_run_parse_args(int argc, const char* const* argv, td_run_opts*
 			if (o->quality_offset != 33 && o->quality_offset != 64) return bad("--quality-offset: need 33 or 64");
 			given_quality_detail = true;
 			break;
+		case O_JOIN_BARCODES: o->join_barcodes = 1; break;
 		default: return bad("unknown option " + a);
 		}
 	}

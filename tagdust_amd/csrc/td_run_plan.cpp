@@ -117,12 +117,11 @@ bool read_arch_file(const char* path, ArchFile& af, std::string& why)
 	return true;
 }
 
-int read_sample_sheet(const char* path, const td_arch* a, SampleSheet& sh)
+// the rows of a sheet whose column t is segment sh.segs[t] of col_arch[t]; infile != NULL: --join-barcodes, the messages name the
+// column's file (sh.files[t], infile[sh.files[t]]) beside its segment
+static int read_sheet_rows(const char* path, const std::vector<const td_arch*>& col_arch, const char* const* infile, SampleSheet& sh)
 {
-	sh = SampleSheet();
-	for (int j = 0; j < a->n_segments; j++) if (a->type[j] == 'B') sh.segs.push_back(j);
 	const int m = (int)sh.segs.size();
-	if (m > TD_SAMPLES_MAX_SEGMENTS) return run_fail("--samples: the architecture has %d barcode segments (at most %d).", m, TD_SAMPLES_MAX_SEGMENTS);
 	FILE* f = fopen(path, "r");
 	if (!f) return run_fail("--samples: cannot open the sample sheet %s.", path);
 	char buf[4096];
@@ -134,7 +133,11 @@ int read_sample_sheet(const char* path, const td_arch* a, SampleSheet& sh)
 		std::vector<std::string> w;
 		for (char* tok = strtok(buf, " \t\r\n"); tok; tok = strtok(nullptr, " \t\r\n")) w.push_back(tok);
 		if (w.empty() || w[0][0] == '#') continue;
-		if ((int)w.size() != m + 1) { rc = run_fail("--samples: %s line %d: %d columns, need %d (the name and one barcode per barcode segment).", path, line, (int)w.size(), m + 1); break; }
+		if ((int)w.size() != m + 1) {
+			rc = run_fail("--samples: %s line %d: %d columns, need %d (the name and one barcode per barcode segment%s).", path, line, (int)w.size(), m + 1,
+			              infile ? " of every barcode file, files first" : "");
+			break;
+		}
 		if (sh.n() == TD_SAMPLES_MAX) { rc = run_fail("--samples: %s line %d: more than %d samples.", path, line, TD_SAMPLES_MAX); break; }
 		const std::string& name = w[0];
 		bool ok = !name.empty() && name.size() <= TD_SAMPLES_MAX_NAME;
@@ -143,9 +146,13 @@ int read_sample_sheet(const char* path, const td_arch* a, SampleSheet& sh)
 		std::vector<int32_t> row;
 		for (int t = 0; t < m && rc == TD_OK; t++) {
 			const int seg = sh.segs[(size_t)t];
+			const td_arch* a = col_arch[(size_t)t];
 			int found = -1;
 			for (int q = 0; q < a->n_seq[seg] - 1; q++) if (w[(size_t)t + 1] == a->seqs[seg][q]) found = q;   // (the last one is the all-N wildcard)
-			if (found < 0) rc = run_fail("--samples: %s line %d: '%s' is not a barcode of segment %d.", path, line, w[(size_t)t + 1].c_str(), seg + 1);
+			if (found < 0 && !infile) rc = run_fail("--samples: %s line %d: '%s' is not a barcode of segment %d.", path, line, w[(size_t)t + 1].c_str(), seg + 1);
+			else if (found < 0)
+				rc = run_fail("--samples: %s line %d: '%s' (column %d) is not a barcode of segment %d of file %d (%s).", path, line, w[(size_t)t + 1].c_str(), t + 1,
+				              seg + 1, sh.files[(size_t)t], infile[sh.files[(size_t)t]]);
 			row.push_back(found);
 		}
 		if (rc != TD_OK) break;
@@ -165,6 +172,26 @@ int read_sample_sheet(const char* path, const td_arch* a, SampleSheet& sh)
 	return TD_OK;
 }
 
+int read_sample_sheet(const char* path, const td_arch* a, SampleSheet& sh)
+{
+	sh = SampleSheet();
+	for (int j = 0; j < a->n_segments; j++) if (a->type[j] == 'B') sh.segs.push_back(j);
+	const int m = (int)sh.segs.size();
+	if (m > TD_SAMPLES_MAX_SEGMENTS) return run_fail("--samples: the architecture has %d barcode segments (at most %d).", m, TD_SAMPLES_MAX_SEGMENTS);
+	return read_sheet_rows(path, std::vector<const td_arch*>((size_t)m, a), nullptr, sh);
+}
+
+int read_sample_sheet_join(const char* path, const std::vector<const td_arch*>& archs, const std::vector<int>& bar_files, const char* const* infile,
+                           SampleSheet& sh)
+{
+	sh = SampleSheet();
+	std::vector<const td_arch*> col_arch;
+	for (const int k : bar_files)
+		for (int j = 0; j < archs[(size_t)k]->n_segments; j++)
+			if (archs[(size_t)k]->type[j] == 'B') { sh.segs.push_back(j); sh.files.push_back(k); col_arch.push_back(archs[(size_t)k]); }
+	return read_sheet_rows(path, col_arch, infile, sh);
+}
+
 int decide_roles(const td_run_opts* o, const std::vector<const td_arch*>& archs, RunRoles& r)
 {
 	r = RunRoles();
@@ -180,19 +207,44 @@ int decide_roles(const td_run_opts* o, const std::vector<const td_arch*>& archs,
 	}
 	for (size_t k = 0; k < archs.size(); k++) {
 		if (has_barcode(archs[k])) {
-			if (r.bar_file >= 0)
+			if (o->join_barcodes) r.bar_files.push_back((int)k);   // --join-barcodes: every barcode file, the first holds the sheet
+			if (r.bar_file >= 0 && !o->join_barcodes)
 				return run_fail("Barcodes seem to be in both architectures... %s", o->samples_file ? "(--samples: barcodes spread over several input files are not "
 				                "joined; the controller's rule of one barcode file stays, and a sheet lists the barcode segments of that one file.)" : "");
-			r.bar_file = (int)k;
+			if (r.bar_file < 0) r.bar_file = (int)k;
 		}
 		r.num_out_reads += read_segments(archs[k]);
+	}
+	std::vector<const char*> in_names;     // (td_run_output_files_describe decides without input files: a file is then named by "-")
+	for (size_t k = 0; k < archs.size(); k++) in_names.push_back((int)k < o->n_infiles && o->infile ? o->infile[k] : "-");
+	if (o->join_barcodes) {
+		if (!o->samples_file) return run_fail("--join-barcodes needs --samples: the sheet names the barcodes of every file that are joined.");
+		int columns = 0;
+		for (const int k : r.bar_files) {
+			r.first_column.push_back(columns);
+			for (int j = 0; j < archs[(size_t)k]->n_segments; j++)
+				if (archs[(size_t)k]->type[j] == 'B') { columns++; r.column_hmms.push_back(archs[(size_t)k]->n_seq[j]); }
+		}
+		if (r.bar_files.size() == 1)
+			return run_fail("--join-barcodes: only one input file (%s) has barcode segments: there is nothing to join, drop the option (--samples alone "
+			                "assigns by all barcode segments of one file).", in_names[(size_t)r.bar_files[0]]);
+		if (!r.bar_files.empty() && columns > TD_SAMPLES_MAX_SEGMENTS)
+			return run_fail("--join-barcodes: the barcode files have %d barcode segments together (at most %d).", columns, TD_SAMPLES_MAX_SEGMENTS);
 	}
 	if (r.num_out_reads == 0) return run_fail("No read segment in any architecture: there would be no output file.");
 	// print_all() names its files after the barcode file's architecture, else the last file's (td_stream_run_multi; one file: td_writer_open)
 	// (--samples is resolved here, where the architectures are known, so that it works with -arch)
 	if (o->samples_file) {
 		if (r.bar_file < 0) return run_fail("--samples: no input file's architecture has a barcode segment.");
-		if (read_sample_sheet(o->samples_file, archs[(size_t)r.bar_file], r.sheet) != TD_OK) return TD_FAIL;
+		if (o->join_barcodes) {
+			if (read_sample_sheet_join(o->samples_file, archs, r.bar_files, in_names.data(), r.sheet) != TD_OK) return TD_FAIL;
+			r.join_line = "join: files ";
+			for (size_t q = 0; q < r.bar_files.size(); q++) r.join_line += (q ? "," : "") + std::to_string(r.bar_files[q]);
+			r.join_line += "; columns";
+			for (size_t t = 0; t < r.sheet.segs.size(); t++)
+				r.join_line += std::string(t ? ", " : " ") + std::to_string(t + 1) + " = segment " + std::to_string(r.sheet.segs[t] + 1) + " of file " + std::to_string(r.sheet.files[t]);
+			r.join_line += "; file " + std::to_string(r.bar_file) + " holds the sheet, a read whose partner in another barcode file is not extracted goes to _un\n";
+		} else if (read_sample_sheet(o->samples_file, archs[(size_t)r.bar_file], r.sheet) != TD_OK) return TD_FAIL;
 		td_writer_file_names_samples(o->outfile, r.sheet.names, r.num_out_reads, r.out_files, nullptr);
 		r.out_files.push_back(samples_file_name(o));
 	} else {
@@ -251,6 +303,15 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 	if (o->n_infiles == 0) return run_fail("ERROR: No input file found.");
 	if (!o->outfile) return run_fail("ERROR: You need to specify an output file prefix using the -o / -out option.");
 	if (o->arch_file && !file_exists(o->arch_file)) return run_fail("ERROR: Arch file:%s does not exists.", o->arch_file);
+	if (o->join_barcodes) {
+		if (!o->samples_file) return run_fail("--join-barcodes needs --samples: the sheet names the barcodes of every file that are joined.");
+		if (o->n_devices > 1)
+			return run_fail("--join-barcodes needs exactly one device (%d given): a batch's barcode calls travel from one file's context to another's.", o->n_devices);
+		if (o->unknown_barcodes > 0)
+			return run_fail("--join-barcodes cannot be combined with --unknown-barcodes: the census spells one file's last barcode segment, not the joined tuple.");
+		if (o->matchstart != -1 || o->matchend != -1)
+			return run_fail("--join-barcodes cannot be combined with -start / -end: labels behind a window do not mark the barcodes.");
+	}
 	if (o->unknown_barcodes > 0 && (o->matchstart != -1 || o->matchend != -1))
 		return run_fail("--unknown-barcodes cannot be combined with -start / -end: labels behind a window do not spell the barcode.");
 	if (o->samples_file && (o->matchstart != -1 || o->matchend != -1))
@@ -338,7 +399,9 @@ extern "C" int td_run_plan(const td_run_opts* o, td_run_plan_t** out)
 		else {
 			p->samples_line += std::to_string(r.sheet.n()) + " samples by segment";
 			for (size_t t = 0; t < r.sheet.segs.size(); t++) p->samples_line += (t ? ", " : (r.sheet.segs.size() > 1 ? "s " : " ")) + std::to_string(r.sheet.segs[t] + 1);
-			p->samples_line += " of file " + std::to_string(r.bar_file) + "; a read whose barcodes are incomplete or name no sample goes to _un";
+			if (!o->join_barcodes) p->samples_line += " of file " + std::to_string(r.bar_file);
+			else p->samples_line += " of the joined files";
+			p->samples_line += "; a read whose barcodes are incomplete or name no sample goes to _un";
 		}
 		p->samples_line += "\n";
 	}
@@ -381,6 +444,7 @@ extern "C" int64_t td_run_plan_describe(const td_run_plan_t* p, char* buf, int64
 		s += "\n";
 	}
 	s += p->samples_line;
+	if (p->all_known) s += p->roles.join_line;
 	s += p->quality_line;
 	if (p->all_known) {
 		s += "barcode file: " + (p->roles.bar_file >= 0 ? std::to_string(p->roles.bar_file) : std::string("none")) + "\n";

@@ -137,17 +137,23 @@ bool unknown_barcodes_text(const td_run_opts* o, const td_arch* a, const std::ve
 }
 
 // --samples: one line per sample of the sheet, then the combinations no sample has
-bool samples_text(const td_run_opts* o, const td_arch* a, const std::vector<std::string>& segs, const char* infile, const SampleSheet& sheet,
-                  const td_run_report& r, std::string& out)
+// One text for both forms: column t of the sheet is segment sheet.segs[t] of col_arch[t], spelled col_segs[t]; col_file != NULL: the
+// join across input files, every column is named with its file and the reads whose partner failed get a line
+static bool samples_text_columns(const td_run_opts* o, const std::vector<const td_arch*>& col_arch, const std::vector<std::string>& col_segs,
+                                 const std::vector<const char*>* col_file, const char* infile, const SampleSheet& sheet, const td_run_report& r, std::string& out)
 {
 	const td_samples_totals& sum = r.samples_totals;
 	const td_census_entry* acc = r.samples;
 	const int64_t n_acc = r.n_sample_keys;
 	const int m = (int)sheet.segs.size();
 	appendf(out, "# samples: the extracted reads of %s by all their barcodes\n# sheet\t%s\n# samples\t%d\n# segments", infile, o->samples_file, sheet.n());
-	for (int t = 0; t < m; t++) appendf(out, "\t%d (%s)", sheet.segs[(size_t)t] + 1, segs[(size_t)sheet.segs[(size_t)t]].c_str());
+	for (int t = 0; t < m; t++) {
+		if (!col_file) appendf(out, "\t%d (%s)", sheet.segs[(size_t)t] + 1, col_segs[(size_t)t].c_str());
+		else appendf(out, "\t%d of %s (%s)", sheet.segs[(size_t)t] + 1, (*col_file)[(size_t)t], col_segs[(size_t)t].c_str());
+	}
 	appendf(out, "\n# extracted reads\t%lld\n# assigned\t%lld\n# not in the sheet\t%lld\n# incomplete\t%lld\n# not counted\t%lld\n", (long long)sum.eligible,
 	        (long long)sum.assigned, (long long)sum.unlisted, (long long)sum.incomplete, (long long)sum.overflow);
+	if (col_file) appendf(out, "# partner failed\t%lld\n", (long long)r.partner_failed);
 	if (sum.overflow > 0) appendf(out, "# the counting table was too small: the counts below are exact, %lld reads are in none of them\n", (long long)sum.overflow);
 	out += "# sample";
 	for (int t = 0; t < m; t++) appendf(out, "\tbarcode %d", t + 1);
@@ -158,7 +164,7 @@ bool samples_text(const td_run_opts* o, const td_arch* a, const std::vector<std:
 		int64_t reads = 0;
 		for (int64_t i = 0; i < n_acc; i++) if (acc[i].key == key) { reads = acc[i].count; listed[(size_t)i] = 1; }
 		out += sheet.names[(size_t)s];
-		for (int t = 0; t < m; t++) appendf(out, "\t%s", a->seqs[sheet.segs[(size_t)t]][sheet.tuples[(size_t)s * m + t]]);
+		for (int t = 0; t < m; t++) appendf(out, "\t%s", col_arch[(size_t)t]->seqs[sheet.segs[(size_t)t]][sheet.tuples[(size_t)s * m + t]]);
 		appendf(out, "\t%lld\t%0.4f\n", (long long)reads, sum.eligible > 0 ? (double)reads / (double)sum.eligible : 0.0);
 	}
 	out += "# combinations not in the sheet\n";
@@ -168,11 +174,33 @@ bool samples_text(const td_run_opts* o, const td_arch* a, const std::vector<std:
 		if (td_samples_key_calls(acc[i].key, calls, &km) != TD_OK || km != m) { run_fail("--samples: 0x%llx is no key of %d segments", (unsigned long long)acc[i].key, m); return false; }
 		for (int t = 0; t < m; t++) {
 			const int seg = sheet.segs[(size_t)t];
+			const td_arch* a = col_arch[(size_t)t];
 			appendf(out, "%s%s", t ? "\t" : "", calls[t] < 0 || calls[t] >= a->n_seq[seg] ? "-" : a->seqs[seg][calls[t]]);   // (the decoy's own spelling is its N's)
 		}
 		appendf(out, "\t%lld\t%0.4f\n", (long long)acc[i].count, sum.eligible > 0 ? (double)acc[i].count / (double)sum.eligible : 0.0);
 	}
 	return true;
+}
+
+bool samples_text(const td_run_opts* o, const td_arch* a, const std::vector<std::string>& segs, const char* infile, const SampleSheet& sheet,
+                  const td_run_report& r, std::string& out)
+{
+	std::vector<std::string> col_segs;
+	for (const int seg : sheet.segs) col_segs.push_back(segs[(size_t)seg]);
+	return samples_text_columns(o, std::vector<const td_arch*>(sheet.segs.size(), a), col_segs, nullptr, infile, sheet, r, out);
+}
+
+bool samples_text_join(const td_run_opts* o, const std::vector<const td_arch*>& archs, const std::vector<std::vector<std::string>>& segs,
+                       const char* const* infile, const SampleSheet& sheet, const td_run_report& r, std::string& out)
+{
+	std::vector<const td_arch*> col_arch;
+	std::vector<std::string> col_segs;
+	std::vector<const char*> col_file;
+	for (size_t t = 0; t < sheet.segs.size(); t++) {
+		const size_t k = (size_t)sheet.files[t];
+		col_arch.push_back(archs[k]); col_segs.push_back(segs[k][(size_t)sheet.segs[t]]); col_file.push_back(infile[k]);
+	}
+	return samples_text_columns(o, col_arch, col_segs, &col_file, infile[sheet.files[0]], sheet, r, out);
 }
 
 // --molecules: one row per sample, per listed barcode of the last 'B' segment, or one "-" row; then the total

@@ -56,8 +56,21 @@ KT_BOTH int smp_find(const uint32_t* row, const uint8_t* sample, int n, uint32_t
 
 KT_BOTH kt_u64 smp_key(uint32_t calls, int m) { return ((kt_u64)m << 56) | (kt_u64)calls; }
 
+// The join across input files: what an exporter hands over for a read that was not extracted.  OR-ed with any other word it stays
+// all ones, so the words of several exporters combine without a special case.
+#define SMP_PARTNER_FAILED 0xFFFFFFFFu
+
+// the export word of a read: its own calls (bytes first_column.., the plan's tc puts them there) when it was extracted
+KT_BOTH uint32_t smp_export_word(bool extracted, uint32_t calls) { return extracted ? calls : SMP_PARTNER_FAILED; }
+
 // td_samples_host.cpp: the model's 'B' segments and the sheet checked, the plan filled; TD_FAIL with who's message (naming the row)
 KT_HIDDEN int smp_plan_build(td_ctx* c, const char* who, const td_model_desc* m, const int32_t* tuples, int32_t n_samples, TdSamplePlan& out);
+// ... the plan of a join: m_total columns of column_hmms[t] HMMs each, the model's own 'B' segments at first_column.. (their entries
+// of column_hmms are held against the model), a sheet of m_total columns; last_seg is the last OWN segment
+KT_HIDDEN int smp_join_plan_build(td_ctx* c, const char* who, const td_model_desc* m, const int32_t* tuples, int32_t n_samples, int32_t m_total,
+                                  int32_t first_column, const int32_t* column_hmms, TdSamplePlan& out);
+// ... and of an exporter: no sheet, only tc (the own calls at bytes first_column..), ordered and last_seg are read
+KT_HIDDEN int smp_export_plan_build(td_ctx* c, const char* who, const td_model_desc* m, int32_t first_column, TdSamplePlan& out);
 // ... and the names: 1..64 characters of [A-Za-z0-9._-], pairwise different, "S<s+1>" for a NULL one
 KT_HIDDEN int smp_names_check(td_ctx* c, const char* who, const char* const* names, int32_t n_samples, std::vector<std::string>& out);
 

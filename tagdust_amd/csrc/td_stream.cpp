@@ -96,14 +96,18 @@ bool artifacts_active(td_ctx* ctx)
 struct Tuple {                        // batch j of every input file: records [j * batch_reads, ...) of each
 	std::vector<Batch*> b;            // [file]; the batches stay their readers'
 	std::vector<int64_t> tickets;     // [file * N + device]; 0: nothing was submitted
-	Tuple(int K, int N) : b((size_t)K, nullptr), tickets((size_t)(K * N), 0) {}
+	std::vector<std::vector<uint32_t>> words;   // [file] the join across input files: an exporter's words, the primary's partner words
+	Tuple(int K, int N) : b((size_t)K, nullptr), tickets((size_t)(K * N), 0), words((size_t)K) {}
 };
+
+enum { JOIN_NONE = 0, JOIN_EXPORTER, JOIN_PRIMARY };   // a file's side of the join across input files (tagdust_samples.h)
 
 struct Target {                       // where the batches of one input file go
 	td_ctx* const* ctx;               // its context on each of the N devices; NULL: no device sees this file
 	bool rna;                         // run_rna_dust (TD_MODE_RNA_DUST: the reads come back unchanged) instead of the HMM
 	int mate = -1;                    // pair mode: the file whose batch is this file's mate batch (td_mol_mate_next), else -1
 	bool qual = false;                // the base-quality filter is on in ctx[0]: the batch's quality lines are named (td_qual_next)
+	int join = JOIN_NONE;             // its contexts export their barcode calls / join the exporters' (one device)
 };
 
 // Starts the readers, runs the write stage on a thread of its own (`write` for every finished tuple in input order, then the
@@ -181,24 +185,51 @@ void run_stages(const std::string& prefix, RunError& err, const std::vector<std:
 		const double t0 = now_s();
 		const int64_t n = t->b[0]->n;
 		bool ok = true;
-		for (int k = 0; k < K && ok; k++) {
-			if (!dev[(size_t)k].ctx) continue;
+		auto submit_file = [&](const int k) {
 			Batch* b = t->b[(size_t)k];
+			const Target& tg = dev[(size_t)k];
 			for (int d = 0; d < N && ok; d++) {      // run_pHMM's contiguous ranges over the devices (barcode_hmm.c:1911-1922)
-				td_ctx* ctx = dev[(size_t)k].ctx[d];
+				td_ctx* ctx = tg.ctx[d];
 				const int64_t interval = n / N, lo = (int64_t)d * interval, hi = (d == N - 1) ? n : lo + interval;
 				if (hi <= lo) continue;
-				const bool r = dev[(size_t)k].rna;
+				const bool r = tg.rna;
 				// (the window: the artifact filter's thread ranges are those of the whole batch, not of a device's range)
 				// (pair mode, one device: the tuple's batch of the mate file goes up with this one, on the same upload stream)
+				// (the join across input files, one device: an exporter's words come back into the tuple, the primary's go up with its batch)
 				ok = (N == 1 || td_set_batch_window(ctx, lo, n) == TD_OK) &&
-				     (dev[(size_t)k].mate < 0 || td_mol_mate_next(ctx, t->b[(size_t)dev[(size_t)k].mate]->codes, t->b[(size_t)dev[(size_t)k].mate]->offs, n) == TD_OK) &&
-				     (!dev[(size_t)k].qual || r || td_qual_next(ctx, b->qual, hi - lo) == TD_OK) &&
+				     (tg.mate < 0 || td_mol_mate_next(ctx, t->b[(size_t)tg.mate]->codes, t->b[(size_t)tg.mate]->offs, n) == TD_OK) &&
+				     (!tg.qual || r || td_qual_next(ctx, b->qual, hi - lo) == TD_OK) &&
+				     (tg.join != JOIN_EXPORTER || td_samples_export_next(ctx, t->words[(size_t)k].data() + lo, hi - lo) == TD_OK) &&
+				     (tg.join != JOIN_PRIMARY || td_samples_join_next(ctx, t->words[(size_t)k].data() + lo, hi - lo) == TD_OK) &&
 				     td_submit(ctx, b->codes, 0, b->offs + lo, hi - lo, r ? TD_MODE_RNA_DUST : TD_MODE_GET_LABEL, b->res + lo, nullptr,
 				               r ? nullptr : b->seq_out + b->offs[lo], &t->tickets[(size_t)(k * N + d)]) == TD_OK;
 				if (!ok) err.fail(prefix + td_last_error(ctx));
 			}
+		};
+		// The join across input files (tagdust_samples.h): the exporters first, their words waited for and OR-ed into the primary's,
+		// then the primary, then every other file as ever.  A ticket waited for here is zeroed: the teardown does not wait twice.
+		int primary = -1;
+		for (int k = 0; k < K; k++) {
+			if (dev[(size_t)k].join == JOIN_NONE) continue;
+			t->words[(size_t)k].assign((size_t)(n > 0 ? n : 1), 0u);
+			if (dev[(size_t)k].join == JOIN_PRIMARY) primary = k;
 		}
+		for (int k = 0; k < K && ok; k++) if (dev[(size_t)k].join == JOIN_EXPORTER) submit_file(k);
+		for (int k = 0; k < K; k++) {
+			if (dev[(size_t)k].join != JOIN_EXPORTER) continue;
+			for (int d = 0; d < N; d++) {
+				int64_t& ticket = t->tickets[(size_t)(k * N + d)];
+				if (ticket && td_wait(dev[(size_t)k].ctx[d], ticket) != TD_OK) {
+					if (ok) err.fail(prefix + td_last_error(dev[(size_t)k].ctx[d]));
+					ok = false;
+				}
+				ticket = 0;
+			}
+			if (ok && primary >= 0) for (int64_t i = 0; i < n; i++) t->words[(size_t)primary][(size_t)i] |= t->words[(size_t)k][(size_t)i];
+		}
+		if (primary >= 0 && ok) submit_file(primary);
+		for (int k = 0; k < K && ok; k++) if (dev[(size_t)k].ctx && dev[(size_t)k].join == JOIN_NONE) submit_file(k);
+
 		st.decode_s += now_s() - t0;
 		flying.push_back(std::move(t));     // (also after a failed submit: the ranges already on other devices are waited for below)
 		if (!ok) break;
@@ -341,21 +372,52 @@ struct MultiPlan {
 	int mol_file = -1, mate_file = -1;   // the decoded file and its mate: the first file in call order other than it (-1: no pair mode)
 	bool mate_filter = false;            // ... and its contexts report "mate_filter": the mate's outcome is joined on the device
 	int qual_file = -1;                  // the decoded file whose contexts report "quality_filter" (tagdust_quality.h), -1: none
+	// the join across input files (tagdust_samples.h): several files hold barcodes, bar_file is the primary; [file] JOIN_*
+	std::vector<int> join;
 };
+
+// Several files hold barcodes: they make a join when there is one device, every one of them has contexts, exactly one of them
+// reports "samples_join" and every other one "samples_export".  roles: [file] JOIN_*; *primary: the joining file.
+bool join_roles(const td_stream_file* files, const int K, const int N, std::vector<int>& roles, int* primary)
+{
+	roles.assign((size_t)K, JOIN_NONE);
+	*primary = -1;
+	if (N != 1) return false;
+	for (int k = 0; k < K; k++) {
+		const td_arch* a = files[k].arch;
+		bool has_bar = false;
+		if (a) for (int j = 0; j < a->n_segments; j++) if (a->type[j] == 'B') has_bar = true;
+		if (!has_bar) continue;
+		if (!files[k].ctx || !files[k].ctx[0]) return false;
+		int32_t joins = 0, exports = 0;
+		(void)td_get_option(files[k].ctx[0], "samples_join", &joins);
+		(void)td_get_option(files[k].ctx[0], "samples_export", &exports);
+		if (joins > 0 && *primary < 0) { roles[(size_t)k] = JOIN_PRIMARY; *primary = k; }
+		else if (exports != 0 && joins == 0) roles[(size_t)k] = JOIN_EXPORTER;
+		else return false;
+	}
+	return *primary >= 0;
+}
 
 // false: the files cannot make a run (td_io_set_error says why)
 bool plan_multi(const td_stream_file* files, const int K, const int N, const int32_t dust, MultiPlan& m)
 {
 	m.read_present.assign((size_t)K, 0);
 	m.rna.assign((size_t)K, 0);
+	m.join.assign((size_t)K, JOIN_NONE);
+	int join_primary = -1;
 	for (int k = 0; k < K; k++) {
 		const td_arch* a = files[k].arch;
 		if (!files[k].path || !a || a->n_segments < 1) { td_io_set_error("td_stream_run_multi: every input file needs a path and an architecture"); return false; }
 		bool has_bar = false;
 		for (int j = 0; j < a->n_segments; j++) { if (a->type[j] == 'B') has_bar = true; if (a->type[j] == 'R') m.read_present[(size_t)k]++; }
 		if (has_bar) {
-			if (m.bar_file >= 0) { td_io_set_error("td_stream_run_multi: barcodes seem to be in both architectures (barcode_hmm.c:140-145)"); return false; }
-			m.bar_file = k;
+			// a second barcode file: only as a side of the join across input files, which its contexts and the others' must say
+			if (m.bar_file >= 0 && join_primary < 0 && !join_roles(files, K, N, m.join, &join_primary)) {
+				td_io_set_error("td_stream_run_multi: barcodes seem to be in both architectures (barcode_hmm.c:140-145)");
+				return false;
+			}
+			if (m.bar_file < 0) m.bar_file = k;
 		}
 		m.num_out_reads += m.read_present[(size_t)k];
 		// run_rna_dust (barcode_hmm.c:315-319) is what the controller runs instead of the HMM for an architecture that is one read segment
@@ -377,6 +439,7 @@ bool plan_multi(const td_stream_file* files, const int K, const int N, const int
 			}
 		}
 	}
+	if (join_primary >= 0) m.bar_file = join_primary;   // the file whose contexts hold the sheet names the output files and the samples
 	// pair mode: a decoded file whose contexts are in mate mode takes the first other file's batches as its mate batches
 	int n_decoded = 0, decoded = -1;
 	for (int k = 0; k < K; k++) {
@@ -393,6 +456,17 @@ bool plan_multi(const td_stream_file* files, const int K, const int N, const int
 		(void)td_get_option(files[decoded].ctx[0], "mate_filter", &mf);
 		(void)td_get_option(files[decoded].ctx[0], "dust", &mate_dust);
 		m.mate_filter = mf != 0;
+	}
+	// the join across input files stands alone yet: a mate batch or a quality verdict of one file is not carried to the others
+	if (join_primary >= 0 && decoded >= 0) {
+		td_io_set_error(std::string("td_stream_run_multi: barcode calls are joined across input files (td_samples_join_enable) and mate mode is on in the contexts of ") +
+		                files[decoded].path + ": the join and mate mode do not go together yet (td_mol_mate_disable)");
+		return false;
+	}
+	if (join_primary >= 0 && m.qual_file >= 0) {
+		td_io_set_error(std::string("td_stream_run_multi: barcode calls are joined across input files (td_samples_join_enable) and the base-quality filter is on in the "
+		                            "contexts of ") + files[m.qual_file].path + ": the join and the filter do not go together yet (td_qual_disable)");
+		return false;
 	}
 	// the base-quality filter: a batch's quality lines travel with its reads to one context, and one file's verdicts are the run's
 	if (m.qual_file >= 0 && (N > 1 || n_decoded != 1)) {
@@ -499,7 +573,7 @@ extern "C" int td_stream_run_multi_hits(const td_stream_file* files, int32_t n_f
 		// (a file that is not decoded needs no page-locked buffers, nor does one whose reads come back unchanged need room for rewritten ones)
 		// (... but the mate file of pair mode does: its batches are uploaded from where they lie)
 		readers.emplace_back(new Reader(err, o, files[k].ctx == nullptr && k != m.mate_file, files[k].ctx != nullptr && !m.rna[(size_t)k], std::max(1, o.n_threads / K)));
-		dev.push_back(Target{ files[k].ctx, m.rna[(size_t)k] != 0, k == m.mol_file ? m.mate_file : -1, k == m.qual_file });
+		dev.push_back(Target{ files[k].ctx, m.rna[(size_t)k] != 0, k == m.mol_file ? m.mate_file : -1, k == m.qual_file, m.join[(size_t)k] });
 		readers.back()->want_qual = k == m.qual_file; readers.back()->path = files[k].path;
 		if (!readers.back()->src.open(files[k].path, o.block_bytes, why)) { td_io_set_error(why); return TD_FAIL; }
 	}

@@ -53,8 +53,12 @@ CENSUS_MAX_WORD = 28
 
 # include/tagdust_samples.h: sample assignment by all 'B' segments
 SAMPLES_ABI_SYMBOLS = ["td_samples_enable", "td_samples_disable", "td_samples_reset", "td_samples_get", "td_samples_name", "td_samples_key",
-                       "td_samples_key_calls", "td_samples_host"]
+                       "td_samples_key_calls", "td_samples_host",
+                       # ... and the join across input files
+                       "td_samples_export_enable", "td_samples_export_disable", "td_samples_export_next", "td_samples_join_enable",
+                       "td_samples_join_next", "td_samples_join_get", "td_samples_export_host", "td_samples_join_host"]
 SAMPLES_TOTALS = ("eligible", "assigned", "unlisted", "incomplete", "overflow")
+SAMPLES_PARTNER_FAILED = 0xFFFFFFFF   # the export word of a read that was not extracted
 SAMPLES_MAX = 255
 SAMPLES_MAX_SEGMENTS = 4
 EXTRACT_SUCCESS = 0
@@ -672,6 +676,14 @@ class _SamplesTotals(C.Structure):
         return {f: int(getattr(self, f)) for f in SAMPLES_TOTALS}
 
 
+class _SamplesJoinTotals(C.Structure):
+    """td_samples_join_totals (include/tagdust_samples.h)"""
+    _fields_ = [("t", _SamplesTotals), ("partner_failed", C.c_int64)]
+
+    def as_dict(self):
+        return dict(self.t.as_dict(), partner_failed=int(self.partner_failed))
+
+
 class _QualParams(C.Structure):
     """td_qual_params (include/tagdust_quality.h)"""
     _fields_ = [("min_quality", C.c_int32), ("offset", C.c_int32), ("max_low", C.c_int32), ("segments", C.c_int32)]
@@ -739,26 +751,36 @@ class _RunReportQuality(C.Structure):
     _fields_ = _RunReportSamples._fields_ + [("quality", C.c_int32), ("quality_totals", _QualTotals)]
 
 
+class _RunOptsJoin(C.Structure):
+    """td_run_opts as it is now: _RunOptsQuality and the field appended behind it"""
+    _fields_ = _RunOptsQuality._fields_ + [("join_barcodes", C.c_int32)]
+
+
+class _RunReportJoin(C.Structure):
+    """td_run_report as it is now: _RunReportQuality and the field appended behind it; this is the structure td_run_execute fills"""
+    _fields_ = _RunReportQuality._fields_ + [("partner_failed", C.c_int64)]
+
+
 def _run_lib():
     lib = load_library()
-    lib.td_run_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(_RunOptsQuality)), C.c_char_p, C.c_size_t]
-    lib.td_run_opts_free.argtypes = [C.POINTER(_RunOptsQuality)]
+    lib.td_run_parse_args.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(_RunOptsJoin)), C.c_char_p, C.c_size_t]
+    lib.td_run_opts_free.argtypes = [C.POINTER(_RunOptsJoin)]
     lib.td_run_opts_free.restype = None
     lib.td_run_last_error.restype = C.c_char_p
-    lib.td_run_plan.argtypes = [C.POINTER(_RunOptsQuality), C.POINTER(C.c_void_p)]
+    lib.td_run_plan.argtypes = [C.POINTER(_RunOptsJoin), C.POINTER(C.c_void_p)]
     lib.td_run_plan_free.argtypes = [C.c_void_p]
     lib.td_run_plan_free.restype = None
     lib.td_run_plan_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     lib.td_run_plan_describe.restype = C.c_int64
-    lib.td_run_output_files_describe.argtypes = [C.POINTER(_RunOptsQuality), C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_int64]
+    lib.td_run_output_files_describe.argtypes = [C.POINTER(_RunOptsJoin), C.POINTER(C.c_char_p), C.c_int32, C.c_char_p, C.c_int64]
     lib.td_run_output_files_describe.restype = C.c_int64
     lib.td_run_arch_file_describe.argtypes = [C.c_char_p, C.c_char_p, C.c_int64]
     lib.td_run_arch_file_describe.restype = C.c_int64
-    lib.td_run_execute.argtypes = [C.POINTER(_RunOptsQuality), C.POINTER(_RunReportQuality)]
-    lib.td_run_report_clear.argtypes = [C.POINTER(_RunReportQuality)]
+    lib.td_run_execute.argtypes = [C.POINTER(_RunOptsJoin), C.POINTER(_RunReportJoin)]
+    lib.td_run_report_clear.argtypes = [C.POINTER(_RunReportJoin)]
     lib.td_run_report_clear.restype = None
     # (the summary reads the report's leading fields alone -- counts, threshold, artifacts: a _RunReport will do as well)
-    lib.td_run_format_summary.argtypes = [C.POINTER(_RunOptsQuality), C.c_void_p, C.c_char_p, C.c_int64]
+    lib.td_run_format_summary.argtypes = [C.POINTER(_RunOptsJoin), C.c_void_p, C.c_char_p, C.c_int64]
     lib.td_run_format_summary.restype = C.c_int64
     return lib
 
@@ -770,7 +792,7 @@ class RunOpts:
         self.lib = _run_lib()
         argv = [b"tagdust-hip"] + [os.fsencode(a) for a in args]
         arr = (C.c_char_p * len(argv))(*argv)
-        self.p = C.POINTER(_RunOptsQuality)()
+        self.p = C.POINTER(_RunOptsJoin)()
         err = C.create_string_buffer(1024)
         if self.lib.td_run_parse_args(len(argv), arr, C.byref(self.p), err, len(err)) != 0:
             self.p = None
@@ -832,7 +854,7 @@ def run_arch_file(path):
 def run_execute(args):
     """td_run_execute: a whole run from the tagdust command line (without the program name); returns the report as a dict."""
     o = RunOpts(args)
-    rep = _RunReportQuality()
+    rep = _RunReportJoin()
     try:
         rc = o.lib.td_run_execute(o.p, C.byref(rep))
         if rc != 0:
@@ -855,6 +877,7 @@ def run_execute(args):
             "samples": _census_entries(rep.samples, int(rep.n_sample_keys)) if rep.n_samples else None,
             "samples_totals": rep.samples_totals.as_dict() if rep.n_samples else None,
             "quality_totals": rep.quality_totals.as_dict() if rep.quality else None,
+            "partner_failed": int(rep.partner_failed),
         }
     finally:
         o.lib.td_run_report_clear(C.byref(rep))
@@ -951,6 +974,16 @@ def _samples_lib():
     lib.td_samples_key_calls.argtypes = [C.c_uint64, C.c_void_p, C.POINTER(C.c_int32)]
     lib.td_samples_host.argtypes = [C.POINTER(_ModelDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(_SamplesTotals)]
+    lib.td_samples_export_enable.argtypes = [C.c_void_p, C.c_int32]
+    lib.td_samples_export_disable.argtypes = [C.c_void_p]
+    lib.td_samples_export_next.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.td_samples_join_enable.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    lib.td_samples_join_next.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    lib.td_samples_join_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_SamplesJoinTotals)]
+    lib.td_samples_export_host.argtypes = [C.POINTER(_ModelDesc), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.td_samples_join_host.argtypes = [C.POINTER(_ModelDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                         C.POINTER(_SamplesJoinTotals)]
     return lib
 
 
@@ -975,6 +1008,50 @@ def samples_host(md, tuples, offs, res, labels):
     ptr, n, tot = C.c_void_p(), C.c_int64(), _SamplesTotals()
     rc = lib.td_samples_host(C.byref(desc), t.ctypes.data, len(t), offs.ctypes.data, len(offs) - 1, rr.ctypes.data, labels.ctypes.data,
                              C.byref(ptr), C.byref(n), C.byref(tot))
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    try:
+        return rr, _census_entries(ptr, n.value), tot.as_dict()
+    finally:
+        lib.td_census_free(ptr)
+
+
+def samples_export_host(md, first_column, offs, res, labels):
+    """td_samples_export_host: the export words (uint32, one per read) of a batch from host arrays (no GPU); the model's own 'B'
+    segments are columns first_column.. of the join"""
+    lib = _samples_lib()
+    desc, keep = make_model_desc(md)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    rr = np.ascontiguousarray(np.array(res, RESULT_DTYPE, copy=True))
+    words = np.zeros(max(len(offs) - 1, 1), np.uint32)
+    rc = lib.td_samples_export_host(C.byref(desc), int(first_column), offs.ctypes.data, len(offs) - 1, rr.ctypes.data, labels.ctypes.data,
+                                    words.ctypes.data)
+    del keep
+    if rc != 0:
+        raise TdError(lib.td_last_error(None).decode())
+    return words[:len(offs) - 1]
+
+
+def samples_join_host(md, tuples, first_column, column_hmms, words, offs, res, labels):
+    """td_samples_join_host: the join of a primary's batch with its partners' export words from host arrays (no GPU).  tuples: the
+    sheet, one row of len(column_hmms) HMM indices per sample.  Returns (the rewritten records, entries, totals dict with
+    partner_failed)."""
+    lib = _samples_lib()
+    desc, keep = make_model_desc(md)
+    t = _samples_sheet(tuples)
+    hm = np.ascontiguousarray(column_hmms, np.int32)
+    offs = np.ascontiguousarray(offs, np.int64)
+    labels = np.ascontiguousarray(labels, np.int8)
+    w = np.ascontiguousarray(words, np.uint32)
+    assert len(w) == len(offs) - 1
+    if len(w) == 0:
+        w = np.zeros(1, np.uint32)
+    rr = np.array(res, RESULT_DTYPE, copy=True)
+    ptr, n, tot = C.c_void_p(), C.c_int64(), _SamplesJoinTotals()
+    rc = lib.td_samples_join_host(C.byref(desc), t.ctypes.data, len(t), len(hm), int(first_column), hm.ctypes.data, w.ctypes.data,
+                                  offs.ctypes.data, len(offs) - 1, rr.ctypes.data, labels.ctypes.data, C.byref(ptr), C.byref(n), C.byref(tot))
     del keep
     if rc != 0:
         raise TdError(lib.td_last_error(None).decode())
@@ -1485,6 +1562,45 @@ class TagdustHip:
             cap = n.value
         out = np.zeros(int(cap), CENSUS_ENTRY_DTYPE)
         self._chk(lib.td_samples_get(self.h, out.ctypes.data, int(cap), C.byref(n), C.byref(tot)))
+        return out[:min(int(cap), n.value)], tot.as_dict()
+
+    def samples_export_enable(self, first_column=0):
+        """td_samples_export_enable: from now on every MODE_GET_LABEL batch leaves its export words in the array samples_export_next named"""
+        self._chk(_samples_lib().td_samples_export_enable(self.h, int(first_column)))
+
+    def samples_export_disable(self):
+        self._chk(_samples_lib().td_samples_export_disable(self.h))
+
+    def samples_export_next(self, words, n_reads):
+        """td_samples_export_next: the uint32 array (numpy or PinnedArray view, kept alive by the caller until the batch has been
+        waited for; None: no array) that receives the next MODE_GET_LABEL batch's export words"""
+        self._chk(_samples_lib().td_samples_export_next(self.h, words.ctypes.data if words is not None else None, int(n_reads)))
+
+    def samples_join_enable(self, tuples, column_hmms, first_column=0, names=None, log2_slots=16):
+        """td_samples_join_enable: the sheet has len(column_hmms) columns, this context's own 'B' segments are columns first_column.."""
+        t = _samples_sheet(tuples)
+        hm = np.ascontiguousarray(column_hmms, np.int32)
+        arr = None
+        if names is not None:
+            arr = (C.c_char_p * len(names))(*[None if s is None else s.encode() for s in names])
+            assert len(names) == len(t)
+        self._chk(_samples_lib().td_samples_join_enable(self.h, t.ctypes.data, arr, len(t), int(log2_slots), len(hm), int(first_column),
+                                                        hm.ctypes.data))
+
+    def samples_join_next(self, words, n_reads):
+        """td_samples_join_next: the partner words (uint32, one per read, the caller's order) of the next MODE_GET_LABEL batch; read
+        when the batch is staged (upload_batch or submit has returned)"""
+        self._chk(_samples_lib().td_samples_join_next(self.h, words.ctypes.data if words is not None else None, int(n_reads)))
+
+    def samples_join(self, cap=None):
+        """td_samples_join_get: (entries as samples(), totals dict with partner_failed)"""
+        lib = _samples_lib()
+        n, tot = C.c_int64(), _SamplesJoinTotals()
+        if cap is None:
+            self._chk(lib.td_samples_join_get(self.h, None, 0, C.byref(n), C.byref(tot)))
+            cap = n.value
+        out = np.zeros(int(cap), CENSUS_ENTRY_DTYPE)
+        self._chk(lib.td_samples_join_get(self.h, out.ctypes.data, int(cap), C.byref(n), C.byref(tot)))
         return out[:min(int(cap), n.value)], tot.as_dict()
 
     def qual_enable(self, min_quality, offset=33, max_low=0, segments=QUAL_SEG_B | QUAL_SEG_F):

@@ -250,6 +250,26 @@ static int checks()
 		const std::string sheet = put("roles_sheet.txt", "left ACGT\nright TTGA\n");
 		CHECK(roles(with({ "--samples", sheet, "--molecules" }), { "B:ACGT,TTGA R:N" }, r) == "" && r.sheet.n() == 2 && r.sheet.segs == std::vector<int>({ 0 }));
 		CHECK(r.out_files == std::vector<std::string>({ out + "_BC_left.fq", out + "_BC_right.fq", out + "_un.fq", out + "_samples.txt", out + "_molecules.txt" }));
+		// --join-barcodes: every barcode file is collected, the first holds the sheet, the columns are the files' 'B' segments, files first
+		const std::string joined = put("roles_joined.txt", "a ACGT CC TT\nb TTGA GG AA\n");
+		CHECK(roles(with({ "--samples", joined, "--join-barcodes" }), { "R:N", "B:ACGT,TTGA", "B:CC,GG S:A B:TT,AA R:N" }, r) == "");
+		CHECK(r.bar_file == 1 && r.bar_files == std::vector<int>({ 1, 2 }) && r.first_column == std::vector<int>({ 0, 1 }) && r.num_out_reads == 2);
+		CHECK(r.column_hmms == std::vector<int32_t>({ 3, 3, 3 }) && r.sheet.n() == 2 && r.sheet.segs == std::vector<int>({ 0, 0, 2 }) && r.sheet.files == std::vector<int>({ 1, 2, 2 }));
+		CHECK(r.sheet.tuples == std::vector<int32_t>({ 0, 0, 0, 1, 1, 1 }));
+		CHECK(r.join_line == "join: files 1,2; columns 1 = segment 1 of file 1, 2 = segment 1 of file 2, 3 = segment 3 of file 2; file 1 holds the sheet, a read whose "
+		                     "partner in another barcode file is not extracted goes to _un\n");
+		CHECK(r.out_files == std::vector<std::string>({ out + "_BC_a_READ1.fq", out + "_BC_b_READ1.fq", out + "_un_READ1.fq", out + "_BC_a_READ2.fq", out + "_BC_b_READ2.fq",
+		                                                out + "_un_READ2.fq", out + "_samples.txt" }));
+		CHECK(roles(with({ "--samples", joined, "--join-barcodes" }), { "B:ACGT,TTGA R:N", "R:N" }, r) ==
+		      "--join-barcodes: only one input file (-) has barcode segments: there is nothing to join, drop the option (--samples alone assigns by all barcode "
+		      "segments of one file).");
+		CHECK(roles(with({ "--samples", joined, "--join-barcodes" }), { "B:AC,GT S:A B:AC,GT S:A B:AC,GT", "B:AC,GT S:A B:AC,GT R:N" }, r) ==
+		      "--join-barcodes: the barcode files have 5 barcode segments together (at most 4).");
+		CHECK(roles(with({ "--samples", joined, "--join-barcodes" }), { "B:ACGT,TTGA", "B:CC,GG R:N" }, r) ==
+		      "--samples: " + joined + " line 1: 4 columns, need 3 (the name and one barcode per barcode segment of every barcode file, files first).");
+		const std::string wrong = put("roles_wrong.txt", "a ACGT CC TT\nb TTGA GG CC\n");
+		CHECK(roles(with({ "--samples", wrong, "--join-barcodes" }), { "B:ACGT,TTGA", "B:CC,GG S:A B:TT,AA R:N" }, r) ==
+		      "--samples: " + wrong + " line 2: 'CC' (column 3) is not a barcode of segment 3 of file 1 (-).");
 		// an output file that exists
 		put("out_BC_TTGA.fq", "");
 		CHECK(roles(o, { "B:ACGT,TTGA R:N" }, r) == "Error: some output files already exists. (" + out + "_BC_TTGA.fq; --force overwrites)");

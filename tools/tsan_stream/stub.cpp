@@ -24,6 +24,8 @@ int td_set_batch_window(td_ctx*, int64_t, int64_t) { return 0; }
 int td_mol_mate_next(td_ctx*, const uint8_t*, const int64_t*, int64_t) { return 0; }   // (pair mode: "mate_bases" reads 0 here, never called)
 int td_qual_next(td_ctx*, const uint8_t*, int64_t) { return 0; }   // (the base-quality filter: "quality_filter" reads 0 here, never called)
 const char* td_samples_name(td_ctx*, int32_t) { return nullptr; }   // (sample assignment: "samples" reads 0 here, never called)
+int td_samples_export_next(td_ctx*, uint32_t*, int64_t) { return 0; }        // (the join across input files: one input file here, never called)
+int td_samples_join_next(td_ctx*, const uint32_t*, int64_t) { return 0; }
 }
 int main(int argc, char** argv)
 {
